@@ -6,10 +6,13 @@ Configs (SURVEY.md §8d restatements of BASELINE.json's configs; one module each
 
   --config segment  (default; BASELINE config 2)  every step seals one 2^po2-cycle segment whose witness is already
                     resident in HBM when the clock starts; N GPUs = N ranks each doing K steps ("scaling": "weak").
-                    The same run then measures, as guarded secondary legs: the SYN-HEAVY constraint system, the resident
-                    code group, a short block (S distinct segments, witgen in the clock, all verified), the host-preflight
-                    witness pipeline and the block's fold to one receipt; then roofline{} (live HBM traffic and VALU issue
-                    from rocprofv3 --pmc child runs) and cpu_baseline{}.
+                    A plain run stops there: set up, warm up, time the K steps, print the line.  With --full the same run
+                    then certifies the timed seals and measures, as guarded secondary legs: the SYN-HEAVY constraint system,
+                    the resident code group, a short block (S distinct segments, witgen in the clock, all verified), the
+                    host-preflight witness pipeline and the block's fold to one receipt; then roofline{} (live HBM traffic and
+                    VALU issue from rocprofv3 --pmc child runs) and cpu_baseline{}.
+                    --dump-outputs DIR writes what the last timed step returned (its seal words and output globals) as
+                    DIR/seal.npy and DIR/output.npy (float64, exact for u32 words): the same arguments seal the same segments.
   --config block    (configs 3/4)  one block = S DISTINCT segments (seeds base+i, the last one a po2-18 tail), handed out
                     round-robin over the ranks and through a shared work index inside a rank; witness generation runs
                     inside the clock, every seal is verified on the host after the clock stops; value = S / wall ("strong").
@@ -17,7 +20,8 @@ Configs (SURVEY.md §8d restatements of BASELINE.json's configs; one module each
                     RECURSION circuit: every node verifies its child seals in-circuit), one native call per rank.
   --config dev      (config 1)  RISC0_DEV_MODE plumbing: fake receipts, no GPU — the partition, control plane and assembly only.
 
-    python bench.py                         # N=1, K=60, W=2 (about a minute)
+    python bench.py                         # N=1, K=60, W=2: the headline alone (seconds)
+    python bench.py --full                  # ... and everything else the segment config measures (about a minute)
     python bench.py --gpus 8                # self-launching: spawns 8 ranks (one GPU each), kills siblings if one dies
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \\
         bench.py --gpus N --steps K --warmup W          # the driver's launch shape
@@ -28,6 +32,7 @@ gathers) is a key/value store that survives a dead rank (benchlib/control.py): r
 from __future__ import annotations
 
 import argparse
+import errno
 import json
 import os
 import sys
@@ -55,7 +60,12 @@ def parse_args(argv=None):
                          "when it is loaded, ~10 s the first time on this machine)")
     ap.add_argument("--inflight", type=int, default=int(os.environ.get("ZKH_INFLIGHT", "3")),
                     help="segments sealed concurrently per GPU (one host thread + HIP stream each); 1 = strictly serial")
-    g = ap.add_argument_group("segment config: what else the default run measures")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="segment config: write the last timed step's seal words and output globals as DIR/seal.npy and DIR/output.npy (float64)")
+    g = ap.add_argument_group("segment config: what else a --full run measures")
+    g.add_argument("--full", action="store_true",
+                   help="after the headline also certify the timed seals and run the secondary legs, the roofline and the CPU baseline below "
+                        "(a plain run times the K steps and prints the line, nothing else)")
     g.add_argument("--no-cpu-baseline", action="store_true")
     g.add_argument("--cpu-full-host", action="store_true",
                    help="cpu_baseline: a larger sample for both legs (the po2-20 unit itself alone, 1/16-unit seals on every core): +~45 s")
@@ -106,7 +116,15 @@ def parse_args(argv=None):
                    help="ranks: one process per GPU (the driver's shape).  session: ONE process, zkh_session_create with N devices x "
                         "--inflight lanes (the library's own executor: C++ threads, one work index)")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)       # benchlib/roofline.py's rocprofv3 child runs
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.dump_outputs and (args.config != "segment" or args.launcher != "ranks"):
+        ap.error("--dump-outputs: only the segment config with the ranks launcher writes its outputs")
+    return args
+
+
+def lean(args) -> bool:
+    """a plain segment run: the headline only (no certification, secondary legs, roofline or CPU baseline)"""
+    return args.config == "segment" and args.launcher == "ranks" and not args.full
 
 
 def main() -> int:
@@ -115,11 +133,22 @@ def main() -> int:
     dev = args.config == "dev"
     # a source-only snapshot (the GPU box) has no built library: build it before anything else — once, under a file lock, so the
     # ranks of a launcher-started run serialise on it and all but the first find it done (a current tree costs milliseconds)
-    build_s = 0.0
+    build_s, build_current = 0.0, None
     if not dev:
         from zeth_amd import build as _build
         t_build = time.perf_counter()
-        _build.ensure_built(oracle=not args.no_cpu_baseline and not args.pmc_child)
+        try:
+            _build.ensure_built(oracle=not args.no_cpu_baseline and not args.pmc_child and not lean(args))
+            build_current = True
+        except OSError as e:
+            # a checkout this account may not write (another account's, a read-only mount) whose build it cannot confirm current
+            # (no recorded tree digest, or a stale one): nothing can be built here, so the library that is there is the one
+            # measured, and the line says so (config.build_current: false)
+            if e.errno not in (errno.EACCES, errno.EPERM, errno.EROFS) or not os.path.exists(_build.LIB):
+                raise
+            build_current = False
+            sys.stderr.write(f"bench: cannot update the build ({e}); measuring the library that is there, which may be older than "
+                             f"the sources: {_build.LIB}\n")
         build_s = time.perf_counter() - t_build
     if args.pmc_child:
         from benchlib.segment import run_pmc_child
@@ -212,6 +241,8 @@ def main() -> int:
         for fn in after:
             fn()
         line["build_s"] = round(build_s, 2)
+        if build_current is not None and isinstance(line.get("config"), dict):
+            line["config"]["build_current"] = build_current
         line["command_wall_s"] = round(time.perf_counter() - t_start, 1)
         if run.failed_ranks:
             line["failed_in"] = run.failed_in

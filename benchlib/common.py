@@ -16,6 +16,30 @@ BASE_SEED = 0x5EED0000
 BENCH_NOISE = 0x2E80            # fixed blinding seed: bench seals must be reproducible run to run (product default: OS RNG)
 
 
+DUMP_LIMIT_BYTES = 64 << 20     # --dump-outputs: everything written, in all
+
+
+def dump_outputs(out_dir: str, arrays: dict) -> list:
+    """--dump-outputs: every array as out_dir/<name>.npy, integer words widened to float64 (exact up to 2^53), floats kept at
+    float32 / float64; refuses to write more than DUMP_LIMIT_BYTES in all.  -> the paths written."""
+    import numpy as np
+    conv = {}
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        conv[name] = a if a.dtype in (np.float32, np.float64) else a.astype(np.float64)
+        if a.dtype.kind in "iu" and a.size and max(-int(a.min()), int(a.max())) >= 1 << 53:
+            raise ValueError(f"dump_outputs: {name} holds words that float64 cannot carry exactly")
+    total = sum(a.nbytes for a in conv.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise ValueError(f"dump_outputs: {total} bytes > {DUMP_LIMIT_BYTES}")
+    os.makedirs(out_dir, exist_ok=True)
+    paths = []
+    for name, a in conv.items():
+        paths.append(os.path.join(out_dir, name + ".npy"))
+        np.save(paths[-1], a)
+    return paths
+
+
 def seal_algorithmic_bytes(wa: int, wc: int, wd: int, n_taps: int, n_combos: int, n: int) -> float:
     """SURVEY.md §8d per-op read-once + write-once bytes for ONE seal, parametric in the column counts."""
     groups = [wc, wd, wa]

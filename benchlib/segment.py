@@ -1,9 +1,10 @@
 """--config segment (BASELINE config 2; the default line): every step seals one 2^po2-cycle segment whose witness is already
 resident in HBM when the clock starts; N GPUs = N ranks each doing K steps ("scaling": "weak").
 
-The headline is measured first and on its own.  Everything after it is a SECONDARY leg of the same run — the heavy constraint
-system, the resident code group, a short block (configs 3 / 4 in small), the host-preflight witness pipeline, the block folded to
-one receipt — each guarded: a leg that fails is reported as `{"error": ...}` in its place and never takes the headline with it."""
+The headline is measured first and on its own; a plain run ends with it.  With --full everything after it is a SECONDARY leg of
+the same run — the certification of the timed seals, the heavy constraint system, the resident code group, a short block
+(configs 3 / 4 in small), the host-preflight witness pipeline, the block folded to one receipt — each guarded: a leg that fails is
+reported as `{"error": ...}` in its place and never takes the headline with it."""
 from __future__ import annotations
 
 import hashlib
@@ -11,8 +12,8 @@ import json
 import os
 import time
 
-from .common import (BASE_SEED, BENCH_NOISE, HBM_PEAK_GBPS, ROOT, Fault, Run, WorkIndex, block_segments, config_common, fold_lanes,
-                     maybe_fault, merged_prof, recursive_fold, recursive_prepare, run_lanes, seal_algorithmic_bytes, seal_block)
+from .common import (BASE_SEED, BENCH_NOISE, HBM_PEAK_GBPS, ROOT, Fault, Run, WorkIndex, block_segments, config_common, dump_outputs,
+                     fold_lanes, maybe_fault, merged_prof, recursive_fold, recursive_prepare, run_lanes, seal_algorithmic_bytes, seal_block)
 from .control import LegAborted, RankFailed
 
 
@@ -70,6 +71,7 @@ def run_segment(run: Run):
     from zeth_amd.host import partition_round_robin
     from zeth_amd.prover import Segment, SegmentProver
     args, ctl, rank, world = run.args, run.ctl, run.rank, run.world
+    full = args.full                              # a plain run: the headline only
     wa, wc, wd = run.widths
     n = run.n
     inflight = run.inflight = max(1, min(args.inflight, args.steps))
@@ -87,16 +89,24 @@ def run_segment(run: Run):
         t_s = time.perf_counter()
         ln.last = ln.prover.seal(seg, code, data, out)   # returns with the seal words on the host
         ln.seal_s.append(time.perf_counter() - t_s)
-        ln.sealed.append((seg, ln.last))                 # kept: every timed seal is verified after the clock
+        if full:
+            ln.sealed.append((seg, ln.last))             # kept: every timed seal is verified after the clock
+        return ln.last
+
+    final = {}                                           # the receipt of the last timed step (--dump-outputs)
 
     def timed(ln):
         # the K timed steps are handed out through a shared work index (work stealing), so K need not be a
-        # multiple of the number of seals in flight
+        # multiple of the number of seals in flight.  Step k seals witness slot (warmup + k) of the ring, which holds the same
+        # segments on every lane: what step k computes does not depend on the lane that takes it
         try:
-            done = 0
-            while idx.take(args.steps) is not None:
-                seal_one(ln, args.warmup + done)
-                done += 1
+            while True:
+                k = idx.take(args.steps)
+                if k is None:
+                    break
+                rec = seal_one(ln, args.warmup + k)
+                if k == args.steps - 1:
+                    final["receipt"] = rec
             ln.hal.sync()
         except Exception as e:                   # surfaced after join
             ln.err = e
@@ -104,11 +114,11 @@ def run_segment(run: Run):
     # ---------------------------------------------------------------- the headline ----
     try:
         lanes = [run.lane() for _ in range(inflight)]
-        for w, ln in enumerate(lanes):
+        for ln in lanes:
             ring = max(1, min(-(-args.steps // inflight) + args.warmup, 2))
             ln.wit = []
             for j in range(ring):                    # witnesses resident in HBM before the clock starts
-                k = mine[(w + j * inflight) % len(mine)]
+                k = mine[j % len(mine)]
                 seg = Segment(index=k, po2=args.po2, seed=BASE_SEED + k, noise_seed=BENCH_NOISE)
                 t_w = time.perf_counter()
                 ln.wit.append((seg, *ln.prover.witgen(seg)))
@@ -118,7 +128,7 @@ def run_segment(run: Run):
             for i in range(args.warmup):
                 seal_one(ln, i)
             ln.hal.sync()
-        if not args.no_prof:
+        if full and not args.no_prof:
             for ln in lanes:
                 ln.hal.prof_reset()
                 ln.hal.prof_enable(True)
@@ -148,7 +158,7 @@ def run_segment(run: Run):
         run.failed_in = "headline"
     headline_ranks = world - len(run.failed_ranks)         # the ranks whose steps are in `value`
     prof = []
-    if not args.no_prof:
+    if full and not args.no_prof:
         prof = merged_prof(lanes)
         for ln in lanes:
             ln.hal.prof_enable(False)
@@ -183,7 +193,7 @@ def run_segment(run: Run):
                 "golden_seals_compared": len(zero) if golden is not None else 0,
                 "verify_ms_per_seal_host": 1e3 * (time.perf_counter() - t_v) / max(1, len(sealed))}
 
-    certify = None if args.no_certify else secondary(run, "certify", certify_leg)
+    certify = None if args.no_certify or not full else secondary(run, "certify", certify_leg)
 
     # With several seals in flight the HIP-event brackets of one stream include time its kernels spent sharing the GPU with the
     # other streams.  One more seal, alone on the GPU and outside the timed region, gives the unshared per-kernel durations next
@@ -246,7 +256,7 @@ def run_segment(run: Run):
             for h in ln.host:
                 ln.hal.host_free(h)
         return out
-    pcie = secondary(run, "pcie", pcie_leg) if args.ingress == "host" else None
+    pcie = secondary(run, "pcie", pcie_leg) if full and args.ingress == "host" else None
 
     REPS, EXTRA_WARM = 2, 2
 
@@ -328,7 +338,7 @@ def run_segment(run: Run):
                 "workload": f"same step with the SYN-HEAVY constraint system ({len(hc.steps)} steps, {len(hc.taps)} taps, "
                             f"{len(hc.combos)} tap combos, degree 5, ConstExt, nested AndCond; {lanes[0].extra.circuit.compiled_parts()} generated kernels)",
                 "kernels_ms_per_seal_unshared": {k: round(v["total_ms"], 3) for k, v in sorted(hprof.items(), key=lambda kv: -kv[1]["total_ms"])[:6]}}
-    heavy = secondary(run, "syn_heavy", heavy_leg) if args.circuit == "syn_a" and not args.no_heavy and args.po2 >= 13 else None
+    heavy = secondary(run, "syn_heavy", heavy_leg) if full and args.circuit == "syn_a" and not args.no_heavy and args.po2 >= 13 else None
 
     # The same step with the committed code (control) group of this segment size kept resident in HBM instead of being re-committed
     # for every segment (zkh_prover_cache_code; the group is a function of (circuit, po2) alone, 0.6 GB at po2 20).  Upstream's
@@ -342,7 +352,7 @@ def run_segment(run: Run):
                 "seals_identical_to_recomputing_prover": bool(same),
                 "note": "NOT the headline: the code group's iNTT / expand-NTT / leaf hashing / Merkle fold are skipped because "
                         "its committed form is resident (opt-in: SegmentProver(resident_code_group=True))"}
-    resident = secondary(run, "code_group_resident", resident_leg) if not args.no_resident and args.po2 >= 13 else None
+    resident = secondary(run, "code_group_resident", resident_leg) if full and not args.no_resident and args.po2 >= 13 else None
 
     # A short block in the same run (BASELINE's metric is "segments/sec + seal wall-clock" of a block: configs 3/4): S DISTINCT
     # segments, the last one a po2-18 tail, round-robin over the ranks, witness generation INSIDE the clock, every seal verified on
@@ -391,7 +401,7 @@ def run_segment(run: Run):
                 "verify_s_rank0": verify_s,
                 "workload": f"{S} distinct 2^{args.po2}-cycle segments (last one 2^{bsegs[-1].po2}), round-robin over {world} GPU(s), "
                             f"{inflight} in flight per GPU; `--config block` runs S = 256"}
-    block = secondary(run, "block", block_leg) if not args.no_block and args.po2 >= 13 and S > 0 else None
+    block = secondary(run, "block", block_leg) if full and not args.no_block and args.po2 >= 13 and S > 0 else None
     block_ok = isinstance(block, dict) and "error" not in block and "skipped" not in block
 
     # The same block with upstream's witness SHAPE: a sequential host preflight per segment replays the cycles
@@ -518,6 +528,10 @@ def run_segment(run: Run):
 
     if rank != 0:
         return None, []
+    if args.dump_outputs:                                  # what a caller of the timed path received from its last step
+        if "receipt" not in final:
+            raise SystemExit("bench: --dump-outputs: rank 0 did not seal the last timed step")
+        dump_outputs(args.dump_outputs, {"seal": final["receipt"].seal, "output": final["receipt"].output})
     # ---------------------------------------------------------------- the line ----
     last = next((ln.last for ln in lanes if ln.last is not None), None)
     value = steps_done / dt
@@ -526,7 +540,7 @@ def run_segment(run: Run):
                              f"code (control) group is re-committed per segment as upstream's SegmentProver does (`value` does NOT keep it resident)"),
                 "parallelism": f"segments round-robin over {world} GPU(s), no collectives; {inflight} segment(s) in flight per GPU",
                 "seal_words": int(last.seal.size) if last is not None else 0,
-                "value_recomputes_code_group": True})
+                "value_recomputes_code_group": True, "full_run": full})
     line = {
         "metric": "segments/sec", "value": value, "unit": "segments/s", "n_gpus": world, "steps": args.steps,
         "warmup": args.warmup, "ms_per_step": 1e3 * dt / args.steps, "higher_is_better": True, "scaling": "weak",
@@ -581,7 +595,7 @@ def run_segment(run: Run):
         if live:
             from .roofline import add_heavy_valu
             after.append(lambda: add_heavy_valu(line, args, n, run.device))
-    if not args.no_cpu_baseline and not run.failed_ranks:
+    if full and not args.no_cpu_baseline and not run.failed_ranks:
         def _cpu():
             from .cpu_baseline import cpu_baseline
             try:

@@ -1,10 +1,13 @@
 """The driver's contract for bench.py, checked on the committed lines of the last GPU runs (profiles/r06_*.json; config 5: r04_*, r05_config5_* and
 r06_config5_*): the one JSON line carries BASELINE.json's metric with every field the contract names, a roofline object for the dominant kernel and
-a CPU baseline; and the command line still parses the driver's flags.  (No GPU: the line is a committed measurement.)"""
+a CPU baseline (a --full run); and the command line still parses the driver's flags.  (No GPU: the line is a committed measurement.  One
+-m gpu test runs a plain line and checks the outputs it dumps.)"""
 import json
 import os
 import subprocess
 import sys
+
+import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -187,8 +190,74 @@ def test_bench_accepts_the_drivers_flags():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=120)
     assert out.returncode == 0
     for flag in ("--gpus", "--steps", "--warmup", "--config", "--join-circuit", "--fold-inflight", "--no-fused-lift", "--fold", "--executor",
-                 "--recompute-code", "--no-preflight-leg", "--no-join3", "--witness", "--cpu-full-host", "--with-p2-join"):
+                 "--recompute-code", "--no-preflight-leg", "--no-join3", "--witness", "--cpu-full-host", "--with-p2-join", "--full", "--dump-outputs"):
         assert flag in out.stdout, flag
+
+
+def test_a_plain_run_is_the_headline_and_full_is_opt_in():
+    """`bench.py --gpus 1 --steps K --warmup W` times the K steps and prints the line; certification, the secondary legs, the roofline and
+    the CPU baseline run with --full only.  --dump-outputs belongs to the segment config's ranks launcher."""
+    bench = _load_bench()
+    a = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "3"])
+    assert bench.lean(a) and not a.full and a.dump_outputs is None and a.steps == 7 and a.warmup == 3
+    assert not bench.lean(bench.parse_args(["--full"])) and bench.parse_args(["--dump-outputs", "d"]).dump_outputs == "d"
+    assert not bench.lean(bench.parse_args(["--config", "block"])) and not bench.lean(bench.parse_args(["--launcher", "session"]))
+    for bad in (["--config", "block", "--dump-outputs", "d"], ["--launcher", "session", "--dump-outputs", "d"]):
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *bad], capture_output=True, text=True, timeout=120)
+        assert out.returncode == 2 and "--dump-outputs" in out.stderr and not out.stdout
+
+
+def test_dump_outputs_writes_exact_float64(tmp_path):
+    import numpy as np
+    from benchlib.common import DUMP_LIMIT_BYTES, dump_outputs
+    seal = np.array([0, 1, 2013265920, 0xFFFFFFFF], dtype=np.uint32)
+    half = np.linspace(-1, 1, 5, dtype=np.float32)
+    paths = dump_outputs(str(tmp_path / "out"), {"seal": seal, "half": half})
+    assert sorted(os.path.basename(p) for p in paths) == ["half.npy", "seal.npy"]
+    s = np.load(tmp_path / "out" / "seal.npy")
+    h = np.load(tmp_path / "out" / "half.npy")
+    assert s.dtype == np.float64 and np.array_equal(s.astype(np.uint64), seal.astype(np.uint64))
+    assert h.dtype == np.float32 and np.array_equal(h, half)
+    with pytest.raises(ValueError, match="bytes"):
+        dump_outputs(str(tmp_path / "big"), {"x": np.zeros(DUMP_LIMIT_BYTES // 8 + 1, dtype=np.uint32)})
+    with pytest.raises(ValueError, match="exactly"):
+        dump_outputs(str(tmp_path / "wide"), {"x": np.array([1 << 60], dtype=np.uint64)})
+    assert not (tmp_path / "big").exists() and not (tmp_path / "wide").exists()
+
+
+@pytest.mark.gpu
+def test_a_plain_run_dumps_the_last_steps_seal(hal, tmp_path):
+    """A plain run on the GPU: the line says what it measured and nothing else ran; --dump-outputs holds the receipt of the last timed step.
+    Step k of K seals ring slot (W + k) mod 2, so K = 4 and K = 5 end on different segments: each dump must be the seal of ITS slot's segment
+    (not the other's), and the host verifier must accept it."""
+    import numpy as np
+    from benchlib.common import BASE_SEED, BENCH_NOISE
+    from zeth_amd.circuits import syn_air
+    from zeth_amd.prover import Segment, SegmentProver, SegmentReceipt
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "ZKH_SHARE_GPUS")}
+    warmup, inflight, po2 = 1, 2, 16
+    desc = syn_air.syn_a()
+    prover = SegmentProver(hal, desc)
+    want = [prover.prove_segment(Segment(index=k, po2=po2, seed=BASE_SEED + k, noise_seed=BENCH_NOISE)) for k in range(2)]
+    assert not np.array_equal(want[0].seal, want[1].seal)
+    for steps in (4, 5):
+        out_dir = tmp_path / f"k{steps}"
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", str(warmup), "--po2", str(po2),
+                            "--inflight", str(inflight), "--dump-outputs", str(out_dir)], env=env, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        l = json.loads(r.stdout.strip().splitlines()[-1])
+        assert l["metric"] == "segments/sec" and l["unit"] == "segments/s" and l["higher_is_better"] is True and l["dtype"] == "u32"
+        assert l["steps"] == steps and l["warmup"] == warmup and abs(l["value"] - 1e3 / l["ms_per_step"]) / l["value"] < 1e-6
+        assert l["config"]["full_run"] is False and l["config"]["build_current"] is True
+        for key in ("certify", "block", "syn_heavy", "code_group_resident", "roofline", "cpu_baseline", "timed_seals_verified"):
+            assert key not in l, key
+        slot = (warmup + steps - 1) % 2
+        seal, out = np.load(out_dir / "seal.npy"), np.load(out_dir / "output.npy")
+        assert seal.dtype == np.float64 and out.dtype == np.float64
+        seal, out = seal.astype(np.uint32), out.astype(np.uint32)
+        assert np.array_equal(seal, want[slot].seal) and np.array_equal(out, want[slot].output), steps
+        assert not np.array_equal(seal, want[1 - slot].seal), steps
+        SegmentReceipt(seal=seal, index=slot, po2=po2, output=out).verify(desc, prover.control_root(po2))
 
 
 def _load_bench():
@@ -252,3 +321,23 @@ def test_host_placement_helpers_parse_sysfs(tmp_path):
     assert hal.pci_numa_cpus("0000:aa:00.0", str(tmp_path)) == (-1, [])         # unknown device
     (dev / "numa_node").write_text("-1\n")
     assert hal.pci_numa_cpus("0000:c1:00.0", str(tmp_path)) == (-1, [])         # the kernel reports no node
+
+
+def test_a_current_build_is_used_without_writing_the_checkout(monkeypatch):
+    """bench.py, smoke() and the tests may run under an account that cannot write the checkout it was built in: a build whose recorded
+    tree digest is current is found without creating, truncating or locking any file."""
+    import builtins
+    from zeth_amd import build as b
+    assert b.ensure_built(oracle=True) == b.LIB                       # current (the suite's conftest built it)
+    real_open = builtins.open
+
+    def read_only_open(path, mode="r", *a, **k):
+        if any(c in mode for c in "wax+"):
+            raise PermissionError(f"read-only checkout: {path}")
+        return real_open(path, mode, *a, **k)
+
+    def no_makedirs(*a, **k):
+        raise PermissionError("read-only checkout")
+    monkeypatch.setattr(builtins, "open", read_only_open)
+    monkeypatch.setattr(os, "makedirs", no_makedirs)
+    assert b.ensure_built(oracle=True) == b.LIB and b.ensure_built() == b.LIB

@@ -8,7 +8,7 @@ set -u
 want() { [ -z "${ONLY:-}" ] || [[ " $ONLY " == *" $1 "* ]]; }
 OUT=$(realpath -m "${1:-gpurun_out/prof}"); mkdir -p "$OUT"
 ROOT=$PWD; export TMPDIR=/tmp
-BENCH="python $ROOT/bench.py --steps 12 --warmup 2 --no-live-traffic"
+BENCH="python $ROOT/bench.py --full --steps 12 --warmup 2 --no-live-traffic"
 SHORT="python $ROOT/bench.py --steps 2 --warmup 1 --inflight 1 --no-cpu-baseline --no-prof --no-heavy --no-resident --no-block --no-certify --no-live-traffic"
 python -c "from zeth_amd import build; build.ensure_built(); build.build_examples()" > /dev/null 2>&1 || echo "collect_profiles: build failed"   # the box gets source only
 cd /tmp

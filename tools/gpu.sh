@@ -4,7 +4,7 @@
 # Recipes (each step under its own `timeout`; counter passes never share a run with tracing domains):
 #   tests        the whole -m gpu suite + smoke()
 #   new [FILE]   one test file (default tests/test_session_gpu.py), fail fast
-#   bench        the driver's command (python bench.py) + its 8-rank form on ONE GPU (ZKH_SHARE_GPUS=1)
+#   bench        the full measurement (python bench.py --full) + its 8-rank form on ONE GPU (ZKH_SHARE_GPUS=1)
 #   foldlanes    config 5 (g++ host, streamed) at 4 / 5 / 6 / 8 fold lanes per GPU
 #   inflight     the headline at 2 .. 6 seals in flight per GPU
 #   torchrun2    the driver's N > 1 launch shape (python -m torch.distributed.run ... bench.py --gpus 2) on ONE GPU
@@ -12,7 +12,7 @@
 #   chained      bench.py --config block --chained (S = 256 SYN-C segments, pre == prev.post checked after the clock)
 #   config5      BASELINE config 5 (S = 1024 -> one succinct receipt): streamed pipeline, two phases, and the g++ host
 #   ab VAR       A/B of one env switch of the library (e.g. ZKH_REC_GRAPH): bench with and without VAR=1, 3 repeats each
-#   repro        the DRIVER'S exact command (python bench.py --gpus 1 --steps 20 --warmup 5) five times on this lease: spread of `value` and of
+#   repro        the DRIVER'S command with --full (python bench.py --full --gpus 1 --steps 20 --warmup 5) five times on this lease: spread of `value` and of
 #                every secondary figure (syn_heavy, resident code, block, preflight) -> repro_summary.json  (round-5 verdict, item 1)
 #   devices      N > 1 readiness on ONE GPU: 8 ranks sharing it (--allow-shared-gpu; config.devices), the same without the flag (must
 #                refuse), the in-process launcher (--launcher session, 8 devices x 1 lane and 1 device x 3 lanes), the RCCL probe at world 1
@@ -57,13 +57,13 @@ knobs)
   timeout 1200 python tools/exp_codegen.py syn_heavy ${KNOB_VARIANTS:-GATHER=0,LOCALITY=0 PART=4800 PART=6400 PART=2400 REGS=80 REGS=112 REGS=128 PREFETCH=2 PREFETCH=8 EPOCH=32 EPOCH=96 LOCWIN=32 LOCWIN=96 REGS=112,PART=4800} > $O/exp_codegen.jsonl 2> $O/err.txt; cat $O/exp_codegen.jsonl ;;
 bench)
   O=gpurun_out/${1:-bench}; mkdir -p $O
-  ( time timeout 600 python bench.py > $O/bench_default.json 2> $O/bench_default.err ) 2> $O/bench_default.time; line $O/bench_default.json
-  ( time ZKH_SHARE_GPUS=1 timeout 900 python bench.py --gpus 8 --steps 6 --warmup 1 --no-heavy > $O/bench_8rank_one_gpu.json 2> $O/bench_8rank.err ) 2> $O/bench_8rank.time; line $O/bench_8rank_one_gpu.json
+  ( time timeout 600 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err ) 2> $O/bench_default.time; line $O/bench_default.json
+  ( time ZKH_SHARE_GPUS=1 timeout 900 python bench.py --full --gpus 8 --steps 6 --warmup 1 --no-heavy > $O/bench_8rank_one_gpu.json 2> $O/bench_8rank.err ) 2> $O/bench_8rank.time; line $O/bench_8rank_one_gpu.json
   grep real $O/*.time; tail -3 $O/bench_default.err | grep -v amdgpu.ids ;;
 repro)
   O=gpurun_out/${1:-repro}; mkdir -p $O
   for i in 1 2 3 4 5; do
-    ( time timeout 600 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/driver_cmd_$i.json 2> $O/driver_cmd_$i.err ) 2> $O/driver_cmd_$i.time; line $O/driver_cmd_$i.json
+    ( time timeout 600 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/driver_cmd_$i.json 2> $O/driver_cmd_$i.err ) 2> $O/driver_cmd_$i.time; line $O/driver_cmd_$i.json
   done
   python - $O <<'PY'
 import json, sys
@@ -73,7 +73,7 @@ def col(f):
     v = [f(l) for l in ls]
     m = sum(v) / len(v)
     return {"runs": [round(x, 3) for x in v], "mean": round(m, 3), "spread_pct": round(100 * (max(v) - min(v)) / m, 2)}
-out = {"command": "python bench.py --gpus 1 --steps 20 --warmup 5 (five times, one lease)",
+out = {"command": "python bench.py --full --gpus 1 --steps 20 --warmup 5 (five times, one lease)",
        "value": col(lambda l: l["value"]), "syn_heavy": col(lambda l: l["syn_heavy"]["segments_per_s"]),
        "syn_heavy_min": col(lambda l: l["syn_heavy"]["min"]), "syn_heavy_max": col(lambda l: l["syn_heavy"]["max"]),
        "resident_code": col(lambda l: l["code_group_resident"]["segments_per_s"]), "block": col(lambda l: l["block"]["segments_per_s"]),
@@ -93,11 +93,11 @@ fuzzsoak)
   done | tee $O/summary.txt ;;
 devices)
   O=gpurun_out/${1:-devices}; mkdir -p $O
-  ( time timeout 900 python bench.py --gpus 8 --steps 6 --warmup 1 --no-heavy --allow-shared-gpu > $O/bench_8rank_one_gpu.json 2> $O/bench_8rank.err ) 2> $O/bench_8rank.time; line $O/bench_8rank_one_gpu.json
+  ( time timeout 900 python bench.py --full --gpus 8 --steps 6 --warmup 1 --no-heavy --allow-shared-gpu > $O/bench_8rank_one_gpu.json 2> $O/bench_8rank.err ) 2> $O/bench_8rank.time; line $O/bench_8rank_one_gpu.json
   timeout 300 python bench.py --gpus 8 --steps 6 --warmup 1 --no-heavy > $O/bench_8rank_refused.out 2> $O/bench_8rank_refused.err; echo "8 ranks on one GPU without --allow-shared-gpu: rc=$? (must be non-zero)"; grep -h "distinct GPUs" $O/bench_8rank_refused.err | head -1 | cut -c1-240
   ( time timeout 600 python bench.py --gpus 8 --launcher session --inflight 1 --steps 6 --warmup 1 --allow-shared-gpu > $O/bench_session_8dev_one_gpu.json 2> $O/bench_session8.err ) 2> $O/bench_session8.time; line $O/bench_session_8dev_one_gpu.json
   ( time timeout 600 python bench.py --gpus 1 --launcher session > $O/bench_session_1gpu.json 2> $O/bench_session1.err ) 2> $O/bench_session1.time; line $O/bench_session_1gpu.json
-  ZKH_DIST_BACKEND=nccl timeout 600 python bench.py --gpus 2 --steps 6 --warmup 1 --no-heavy --no-block --no-resident --no-cpu-baseline --allow-shared-gpu > $O/bench_2rank_forced_rccl.json 2> $O/bench_2rank_forced_rccl.err; line $O/bench_2rank_forced_rccl.json
+  ZKH_DIST_BACKEND=nccl timeout 600 python bench.py --full --gpus 2 --steps 6 --warmup 1 --no-heavy --no-block --no-resident --no-cpu-baseline --allow-shared-gpu > $O/bench_2rank_forced_rccl.json 2> $O/bench_2rank_forced_rccl.err; line $O/bench_2rank_forced_rccl.json
   timeout 300 python tools/rccl_probe_check.py > $O/rccl_probe_world1.json 2> $O/rccl_probe_world1.err; cat $O/rccl_probe_world1.json
   python - $O <<'PY'
 import json, sys
@@ -147,11 +147,11 @@ config5)
 ab)
   V=${1:?env variable}; O=gpurun_out/ab_$V; mkdir -p $O
   for i in 1 2 3; do
-    timeout 300 python bench.py --no-cpu-baseline --no-heavy --no-resident --no-block --no-live-traffic --no-certify > $O/off_$i.json 2>> $O/err.txt; line $O/off_$i.json
-    env $V=1 timeout 300 python bench.py --no-cpu-baseline --no-heavy --no-resident --no-block --no-live-traffic --no-certify > $O/on_$i.json 2>> $O/err.txt; line $O/on_$i.json
+    timeout 300 python bench.py --full --no-cpu-baseline --no-heavy --no-resident --no-block --no-live-traffic --no-certify > $O/off_$i.json 2>> $O/err.txt; line $O/off_$i.json
+    env $V=1 timeout 300 python bench.py --full --no-cpu-baseline --no-heavy --no-resident --no-block --no-live-traffic --no-certify > $O/on_$i.json 2>> $O/err.txt; line $O/on_$i.json
   done
-  timeout 300 python bench.py --inflight 1 --steps 20 --no-cpu-baseline --no-heavy --no-resident --no-block --no-live-traffic --no-certify > $O/off_serial.json 2>> $O/err.txt
-  env $V=1 timeout 300 python bench.py --inflight 1 --steps 20 --no-cpu-baseline --no-heavy --no-resident --no-block --no-live-traffic --no-certify > $O/on_serial.json 2>> $O/err.txt
+  timeout 300 python bench.py --full --inflight 1 --steps 20 --no-cpu-baseline --no-heavy --no-resident --no-block --no-live-traffic --no-certify > $O/off_serial.json 2>> $O/err.txt
+  env $V=1 timeout 300 python bench.py --full --inflight 1 --steps 20 --no-cpu-baseline --no-heavy --no-resident --no-block --no-live-traffic --no-certify > $O/on_serial.json 2>> $O/err.txt
   python - $O <<'PY'
 import json, sys
 for tag in ("off", "on"):
@@ -190,7 +190,7 @@ inflight)
 torchrun2)
   O=gpurun_out/${1:-torchrun2}; mkdir -p $O      # the driver's launch shape for N > 1 (torch.distributed.run), 2 ranks sharing the one GPU
   ( time ZKH_SHARE_GPUS=1 timeout 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 \
-      bench.py --gpus 2 --steps 8 --warmup 2 > $O/bench_torchrun2.out 2> $O/err.txt; echo "rc=$?" ) 2> $O/time.txt
+      bench.py --full --gpus 2 --steps 8 --warmup 2 > $O/bench_torchrun2.out 2> $O/err.txt; echo "rc=$?" ) 2> $O/time.txt
   grep -c '^{"metric"' $O/bench_torchrun2.out; grep '^{"metric"' $O/bench_torchrun2.out | tail -1 > $O/bench_torchrun2.json; line $O/bench_torchrun2.json; grep real $O/time.txt ;;
 succinct4)
   O=gpurun_out/${1:-succinct4}; mkdir -p $O      # the N-rank shape of config 5 on ONE GPU: every rank seals + folds its aligned range natively, rank 0 joins the local roots
@@ -200,7 +200,7 @@ profiles) bash tools/collect_profiles.sh gpurun_out/${1:-prof} ;;
 big)
   O=gpurun_out/${1:-big}; mkdir -p $O
   for p in 21 22; do
-    timeout 900 python bench.py --po2 $p --steps 9 --warmup 1 --no-cpu-baseline --no-live-traffic --no-heavy --no-resident --no-block > $O/bench_po2_$p.json 2> $O/bench_po2_$p.err
+    timeout 900 python bench.py --full --po2 $p --steps 9 --warmup 1 --no-cpu-baseline --no-live-traffic --no-heavy --no-resident --no-block > $O/bench_po2_$p.json 2> $O/bench_po2_$p.err
     line $O/bench_po2_$p.json
   done ;;
 soak)
@@ -217,7 +217,7 @@ power)
   sample() { tag=$1; shift; ( timeout 240 "$@" > $O/run_$tag.txt 2>> $O/err.txt ) & pid=$!; : > $O/smi_$tag.txt
     while kill -0 $pid 2>/dev/null; do rocm-smi --showpower --showclocks 2>/dev/null | grep -E "Package Power|sclk|mclk" | tr '\n' ' ' >> $O/smi_$tag.txt; echo >> $O/smi_$tag.txt; sleep 0.4; done; }
   for m in M1 M2 M3 M4 M8; do sample $m python tools/microbench.py --only $m --reps 4000; done
-  sample bench python bench.py --steps 600 --warmup 2 --no-block --no-live-traffic --no-certify --no-cpu-baseline
+  sample bench python bench.py --full --steps 600 --warmup 2 --no-block --no-live-traffic --no-certify --no-cpu-baseline
   for tag in M1 M2 M3 M4 M8 bench; do
     echo "== $tag"; sed -E 's/.*sclk[^(]*\(([0-9]+)Mhz\).*Power \(W\): ([0-9.]+).*/\1 \2/' $O/smi_$tag.txt | awk '$2>600{n++; c[n]=$1; w[n]=$2} END{ if(!n){print "  none"; exit} asort(c); asort(w); printf "  n=%d sclk median %d MHz  power median %d W\n", n, c[int((n+1)/2)], w[int((n+1)/2)]}'
   done ;;
