@@ -211,6 +211,21 @@ const char* zkh_eval_check(zkh_ctx*, const zkh_circuit*, zkh_buf* check, const z
                            const zkh_buf* const* globals, size_t n_globals, const uint32_t poly_mix[4], size_t po2,
                            size_t steps, int use_interpreter);
 
+/* ---- CircuitHal::accumulate for arguments described as data (csrc/accumulate.hip; zeth_amd/circuits/logup.py) ----
+ * Lookup and permutation arguments as log-derivative sums: a ZKA1 blob lists terms t(r) = sign sel(r) m(r) / (alpha - (tag + beta v_0(r)
+ * + ... + beta^w v_{w-1}(r))) per accum Fp4 column; the column holds their running sum over the active rows, the blinding rows hold
+ * noise, and all columns' totals must sum to zero (one bus).  The constraints that check it are ordinary steps of the circuit's ZKC1
+ * description (emitted by the same builder), so provers and verifiers need nothing else.
+ * zkh_circuit_set_arguments validates the blob against the circuit (accum width = 4 k, alpha / beta within the mix globals, columns
+ * within their groups, tuple width 1..4, 1..3 terms per column) and keeps a copy; words == 0 removes the arguments.
+ * zkh_accumulate fills `accum` (4k x 2^po2) from the raw code and data traces and the mix globals drawn by zkh_prove_begin.  It FAILS
+ * — and leaves the accum zeroed, so no seal can be made from it — when a denominator vanishes (the error names the row and column) or
+ * when the bus does not balance (the error reports the total): an ordinary refusal of a bad witness. */
+const char* zkh_circuit_set_arguments(zkh_circuit*, const uint32_t* blob, size_t words);
+int zkh_circuit_has_arguments(const zkh_circuit*);
+const char* zkh_accumulate(zkh_ctx*, const zkh_circuit*, size_t po2, size_t zk_cycles, const uint32_t noise_key[8], const zkh_buf* code,
+                           const zkh_buf* data, const uint32_t* mix_global, zkh_buf* accum);
+
 /* ---- built-in witness generators on the device, by circuit kind (desc word 13) ----
  *   kind 1 SYN-AIR   stands in for risc0-circuit-rv32im's witgen (declared synthetic)
  *   kind 2 KECCAK-F  every 25 active rows are one real keccak-f[1600] permutation (zeth_amd/circuits/keccak_f.py; stands
@@ -386,7 +401,8 @@ typedef struct {
     const uint32_t* pub;          /* public inputs of the built-in generators (see zkh_syn_witgen), may be NULL */
     size_t n_pub;
     /* caller-produced traces instead (CPU preflight + witgen, upstream's flow): W_code x 2^po2, W_data x 2^po2 words and
-     * OUTPUT_SIZE out globals; accum comes from the session's accumulate callback (built-in for kinds 1..3) */
+     * OUTPUT_SIZE out globals; accum comes from the session's accumulate callback if one is set, else the built-in generator of
+     * kinds 1..3, else zkh_accumulate when the circuit carries arguments (zkh_circuit_set_arguments on every lane's circuit) */
     const uint32_t* host_code;
     const uint32_t* host_data;
     const uint32_t* out_global;

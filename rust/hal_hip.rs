@@ -306,6 +306,16 @@ impl HipCircuitHal {
         ffi(|| unsafe { sys::zkh_circuit_attach_code_object_part(self.circuit, image.as_ptr() as *const _, image.len(), name.as_ptr(), part, n_parts) });
         *self.kernels.borrow_mut() = unsafe { sys::zkh_circuit_compiled_parts(self.circuit) };
     }
+
+    /// The circuit's lookup / permutation arguments as a ZKA1 blob (`zeth_amd/circuits/logup.py`): `accumulate` then builds the accum
+    /// group on the device (`zkh_accumulate`).  Validated against the circuit; an empty blob removes them.
+    pub fn set_arguments(&self, blob: &[u32]) {
+        ffi(|| unsafe { sys::zkh_circuit_set_arguments(self.circuit, blob.as_ptr(), blob.len()) });
+    }
+
+    pub fn has_arguments(&self) -> bool {
+        unsafe { sys::zkh_circuit_has_arguments(self.circuit) != 0 }
+    }
 }
 
 impl Drop for HipCircuitHal {
@@ -320,6 +330,18 @@ impl CircuitHal<HipHal> for HipCircuitHal {
         let gl: Vec<*const ZkhBuf> = globals.iter().map(|b| b.raw as *const ZkhBuf).collect();
         debug_assert_eq!(check.size(), 4 * INV_RATE * steps); // CHECK_SIZE planes of 4n words: 4 x 4n
         ffi(|| unsafe { sys::zkh_eval_check(self.hal.ctx.0, self.circuit, check.raw, g.as_ptr(), g.len(), gl.as_ptr(), gl.len(), HipHal::ext_words(&poly_mix), po2, steps, 0) });
+    }
+
+    /// `CircuitHal::accumulate(ctrl, io, data, mix, accum, steps)`: for a circuit with arguments attached (`set_arguments`) the
+    /// library's built-in accumulate fills `accum` from the raw code (ctrl) and data traces and the mix globals, blinding rows from
+    /// fresh OS randomness; it panics on a refused witness (a vanishing denominator, a bus that does not balance) like every failed
+    /// HAL op.  A circuit without arguments has no accumulate here: its host supplies one (`zkh_session_set_accumulate`).
+    fn accumulate(&self, ctrl: &HipBuffer<BabyBearElem>, _io: &HipBuffer<BabyBearElem>, data: &HipBuffer<BabyBearElem>, mix: &HipBuffer<BabyBearElem>,
+                  accum: &HipBuffer<BabyBearElem>, steps: usize) {
+        assert!(self.has_arguments(), "accumulate: this circuit carries no arguments (HipCircuitHal::set_arguments)");
+        let po2 = steps.trailing_zeros() as usize;
+        let mix_words = mix.read_words(0, mix.size());
+        ffi(|| unsafe { sys::zkh_accumulate(self.hal.ctx.0, self.circuit, po2, sys::ZK_CYCLES, std::ptr::null(), ctrl.raw, data.raw, mix_words.as_ptr(), accum.raw) });
     }
 }
 

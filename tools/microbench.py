@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Per-op micro-benchmarks M1..M8 of SURVEY.md §8d (+ M9: the trace-driven witness, row f1) on one MI355X, through the C ABI (HipHal).
+"""Per-op micro-benchmarks M1..M8 of SURVEY.md §8d (+ M9: the trace-driven witness, row f1; M10: the built-in accumulate of SYN-LOOKUP's
+arguments and its share of that circuit's seal) on one MI355X, through the C ABI (HipHal).
 
 Each line of output is one JSON object: the op, its shape, the average wall time of one call (stream drained on both
 sides of `reps` back-to-back calls), its ALGORITHMIC bytes (SURVEY.md §8a "B_alg": inputs read once + outputs written
@@ -205,6 +206,32 @@ def main() -> None:
              dt, 16 * A + 4 * wd * n)
         hal.sync()
         hal.host_free(pinned)
+    if want("M10"):
+        # the built-in accumulate (zkh_accumulate) of SYN-LOOKUP (67 terms in 23 accum columns), and the seal it is part of
+        from zeth_amd.circuits import logup, syn_lookup
+        from zeth_amd.prover import Segment, SegmentProver
+        desc, blob = syn_lookup.syn_lookup()
+        a = logup.Arguments.parse(blob)
+        prover = SegmentProver(hal, desc, arguments=blob)
+        code_h, data_h, out = syn_lookup.witness(syn_lookup.FULL, args.po2, 1994, seed=10)
+        code, data = hal.alloc_elem("code", code_h.size), hal.alloc_elem("data", data_h.size)
+        code.write(code_h)
+        data.write(data_h)
+        A = n - 1994
+        seg = Segment(index=0, po2=args.po2, noise_seed=0x2E80)
+        mix = rand_fp(rng, 8)
+        accum = hal.alloc_elem("accum", 4 * a.k * n)
+        acc = lambda: hal.accumulate(prover.circuit, args.po2, 1994, 0x2E80, code, data, mix, accum)
+        dt_acc = timed(hal, acc, args.reps)
+        cols = {c for t in a.terms for c in list(t.tuple_cols) + ([t.mult] if t.mult else []) + ([(1, t.sel)] if t.sel is not None else [])}
+        line("M10", f"accumulate (SYN-LOOKUP: {len(a.terms)} terms in {a.k} accum columns)", f"{len(a.terms)} x {A} terms -> {4 * a.k} x 2^{args.po2}",
+             dt_acc, 4 * len(cols) * A + 16 * a.k * n)
+        seal = lambda: prover.seal_with_accum(seg, code, data, out, prover.args_accumulate(seg, code, data))
+        dt_seal = timed(hal, seal, args.reps)
+        line("M10s", "SYN-LOOKUP seal (prove_begin -> accumulate -> prove_finish, traces resident)", f"{sum(int(x) for x in desc[3:6])} cols x 2^{args.po2}",
+             dt_seal, 4 * sum(int(x) for x in desc[3:6]) * n)
+        print(json.dumps({"bench": "M10share", "accumulate_ms": round(dt_acc * 1e3, 3), "seal_ms": round(dt_seal * 1e3, 3),
+                          "share": round(dt_acc / dt_seal, 4)}), flush=True)
     hal.close()
 
 

@@ -1,0 +1,358 @@
+"""Lookup and permutation arguments as data: log-derivative ("LogUp") sums in the accum group (DESIGN.md §2 ARGUMENTS).
+
+One source gives two artefacts:
+  * the ordinary ZKC1 description (desc.py) whose constraints check the accum columns — the prover, the eval_check generator,
+    the bound verifier and both verifiers read it unchanged;
+  * the ZKA1 argument blob that tells the library's built-in accumulate (csrc/accumulate.hip, zkh_accumulate) how to fill those
+    columns from (code, data, mix).
+
+A TERM of accum Fp4 column c has the value on row r
+
+    t(r) = sign * sel(r) * m(r) / (alpha - (tag + beta v_0(r) + beta^2 v_1(r) + ... + beta^w v_{w-1}(r)))
+
+with alpha, beta Fp4 challenges read from the mix globals (drawn after code and data are committed), sel a code column (or 1),
+m a code / data column (or 1), v_j code / data columns at back 0 (w <= 4).  Accum column c holds the running sum over the active
+rows, S_c[r] = sum_{r' <= r} sum_{terms i of c} t_i(r'); rows [A, n) are blinding noise.  The tags make the terms one bus: all
+terms of all arguments together sum to zero, sum_c S_c[A-1] = 0.
+
+Constraints (Fp steps, Fp4 arithmetic written out as syn_air.py's ext_mul), with D = prod_i d_i over the terms of c:
+  first: S_c D - sum_i sign_i sel_i m_i prod_{l != i} d_l = 0
+  body : (S_c - S_c@1) D - (the same) = 0
+  last : sum_c S_c = 0
+The degree of a column's constraint is 1 (gate) + max(1 + t, max_i(deg sel_i + deg m_i) + t - 1) for t terms; CHECK_SIZE 16
+(4 pieces) bounds it at 5, so a column holds at most 3 terms.  The builder refuses anything above 5.
+
+ZKA1 layout (u32 words; canonical integers, not Montgomery words)::
+
+    [0] magic 'ZKA1' = 0x5a4b4131   [1] version = 1   [2] k = accum Fp4 columns   [3] alpha mix word offset
+    [4] beta mix word offset       [5] n_terms       [6..8) reserved = 0
+    terms: n_terms x 16 words, sorted by column:
+      col, neg (0: +1, 1: -1), sel (code column or NONE), m_group (NONE = constant 1, else GROUP_CODE / GROUP_DATA), m_col,
+      tag, w, 0, then w (group, column) pairs of the tuple, unused pairs 0
+"""
+from __future__ import annotations
+
+from dataclasses import dataclass
+from typing import List, Optional, Sequence, Tuple
+
+import numpy as np
+
+from .desc import GLOBAL_MIX, GROUP_ACCUM, GROUP_CODE, GROUP_DATA, P, CircuitBuilder, Fp
+
+ARGS_MAGIC = 0x5A4B4131
+ARGS_HEADER = 8
+TERM_WORDS = 16
+NONE = 0xFFFFFFFF
+MAX_DEGREE = 5
+MAX_TUPLE = 4
+NBETA = P - 11
+
+
+@dataclass(frozen=True)
+class Term:
+    col: int                                   # accum Fp4 column
+    tuple_cols: Tuple[Tuple[int, int], ...]    # (group, column) of v_0 .. v_{w-1}
+    sign: int = 1
+    sel: Optional[int] = None                  # code column, or None = 1
+    mult: Optional[Tuple[int, int]] = None     # (group, column), or None = 1
+    tag: int = 0
+
+    def degree(self, n_terms: int) -> int:
+        """degree of the numerator summand sign * sel * m * prod_{l != i} d_l"""
+        return (self.sel is not None) + (self.mult is not None) + n_terms - 1
+
+
+def column_degree(terms: Sequence[Term]) -> int:
+    """degree of the first / body constraint of a column with these terms (the gate included)"""
+    t = len(terms)
+    return 1 + max([1 + t] + [x.degree(t) for x in terms])
+
+
+@dataclass
+class Arguments:
+    """Parsed view of a ZKA1 blob."""
+    k: int
+    alpha: int
+    beta: int
+    terms: List[Term]
+
+    def blob(self) -> np.ndarray:
+        words = [ARGS_MAGIC, 1, self.k, self.alpha, self.beta, len(self.terms), 0, 0]
+        for t in sorted(self.terms, key=lambda x: x.col):
+            rec = [t.col, 0 if t.sign == 1 else 1, NONE if t.sel is None else t.sel,
+                   NONE if t.mult is None else t.mult[0], 0 if t.mult is None else t.mult[1], t.tag % P, len(t.tuple_cols), 0]
+            for g, c in t.tuple_cols:
+                rec += [g, c]
+            rec += [0] * (TERM_WORDS - len(rec))
+            words += rec
+        return np.asarray(words, dtype=np.uint32)
+
+    @staticmethod
+    def parse(blob: Sequence[int]) -> "Arguments":
+        d = [int(x) for x in np.asarray(blob, dtype=np.uint32)]
+        if len(d) < ARGS_HEADER or d[0] != ARGS_MAGIC or d[1] != 1:
+            raise ValueError("not a ZKA1 argument blob")
+        k, alpha, beta, n = d[2], d[3], d[4], d[5]
+        if len(d) != ARGS_HEADER + TERM_WORDS * n:
+            raise ValueError(f"ZKA1: {len(d)} words for {n} terms")
+        terms = []
+        for i in range(n):
+            r = d[ARGS_HEADER + TERM_WORDS * i: ARGS_HEADER + TERM_WORDS * (i + 1)]
+            w = r[6]
+            if not 1 <= w <= MAX_TUPLE:
+                raise ValueError(f"ZKA1 term {i}: tuple width {w}")
+            terms.append(Term(col=r[0], tuple_cols=tuple((r[8 + 2 * j], r[9 + 2 * j]) for j in range(w)), sign=-1 if r[1] else 1,
+                              sel=None if r[2] == NONE else r[2], mult=None if r[3] == NONE else (r[3], r[4]), tag=r[5]))
+        return Arguments(k, alpha, beta, terms)
+
+    def by_column(self) -> List[List[Term]]:
+        cols: List[List[Term]] = [[] for _ in range(self.k)]
+        for t in self.terms:
+            cols[t.col].append(t)
+        return cols
+
+
+class LogupBuilder(CircuitBuilder):
+    """CircuitBuilder that also records argument terms and emits their constraints (`arguments`)."""
+
+    def __init__(self, group_sizes, global_sizes, alpha: int = 0, beta: int = 4, kind: int = 0):
+        super().__init__(tuple(group_sizes), tuple(global_sizes), kind=kind)
+        if group_sizes[GROUP_ACCUM] % 4:
+            raise ValueError("the accum group holds Fp4 columns: its width is a multiple of 4")
+        for off in (alpha, beta):
+            if off + 4 > global_sizes[1]:
+                raise ValueError(f"mix offset {off} needs {off + 4} mix words, the circuit has {global_sizes[1]}")
+        self.alpha_off, self.beta_off = alpha, beta
+        self.terms: List[Term] = []
+
+    @property
+    def k(self) -> int:
+        return self.group_sizes[GROUP_ACCUM] // 4
+
+    def term(self, col: int, tuple_cols: Sequence[Tuple[int, int]], sign: int = 1, sel: Optional[int] = None,
+             mult: Optional[Tuple[int, int]] = None, tag: int = 0) -> Term:
+        if not 0 <= col < self.k:
+            raise ValueError(f"accum column {col} outside 0..{self.k - 1}")
+        if sign not in (1, -1):
+            raise ValueError("a term's sign is +1 or -1")
+        if not 1 <= len(tuple_cols) <= MAX_TUPLE:
+            raise ValueError(f"tuple width {len(tuple_cols)} outside 1..{MAX_TUPLE}")
+        for g, c in list(tuple_cols) + ([mult] if mult is not None else []):
+            if g not in (GROUP_CODE, GROUP_DATA) or not 0 <= c < self.group_sizes[g]:
+                raise ValueError(f"column ({g}, {c}) is not a code or data column of this circuit")
+        if sel is not None and not 0 <= sel < self.group_sizes[GROUP_CODE]:
+            raise ValueError(f"selector {sel} is not a code column")
+        t = Term(col, tuple((int(g), int(c)) for g, c in tuple_cols), sign, sel, mult, int(tag))
+        self.terms.append(t)
+        deg = column_degree([x for x in self.terms if x.col == col])
+        if deg > MAX_DEGREE:
+            self.terms.pop()
+            raise ValueError(f"accum column {col}: constraint degree {deg} exceeds {MAX_DEGREE} (at most 3 terms of single-column "
+                             f"selectors and multiplicities per column)")
+        return t
+
+    # ---- Fp4 values as 4 Fp handles (None = a zero component) ----
+    def _e_add(self, x, y):
+        return [a if b is None else b if a is None else self.add(a, b) for a, b in zip(x, y)]
+
+    def _e_sub(self, x, y):
+        return [a if b is None else self.sub(self.const(0) if a is None else a, b) for a, b in zip(x, y)]
+
+    def _e_scale(self, x, s: Fp):
+        return [None if a is None else self.mul(a, s) for a in x]
+
+    def _e_mul(self, x, y):
+        """x * y mod (X^4 + 11)"""
+        acc = [[] for _ in range(7)]
+        for i in range(4):
+            for j in range(4):
+                if x[i] is not None and y[j] is not None:
+                    acc[i + j].append(self.mul(x[i], y[j]))
+
+        def total(lst):
+            if not lst:
+                return None
+            s = lst[0]
+            for v in lst[1:]:
+                s = self.add(s, v)
+            return s
+        c = [total(a) for a in acc]
+        nb = self.const(NBETA)
+        for i in range(3):
+            if c[4 + i] is not None:
+                h = self.mul(nb, c[4 + i])
+                c[i] = h if c[i] is None else self.add(c[i], h)
+        return c[:4]
+
+    def _mix4(self, off: int):
+        return [self.get_global(GLOBAL_MIX, off + i) for i in range(4)]
+
+    def arguments(self, chain, first: Fp, body: Fp, last: Fp):
+        """emit the argument constraints onto `chain`, gated by the code selectors first / body / last; returns the chain"""
+        cols = [[t for t in self.terms if t.col == c] for c in range(self.k)]
+        for c, ts in enumerate(cols):
+            if not ts:
+                raise ValueError(f"accum column {c} has no terms")
+        alpha, beta = self._mix4(self.alpha_off), self._mix4(self.beta_off)
+        wmax = max(len(t.tuple_cols) for t in self.terms)
+        bpow = [beta]
+        for _ in range(1, wmax):
+            bpow.append(self._e_mul(bpow[-1], beta))
+        acc = lambda c, back=0: [self.get(GROUP_ACCUM, 4 * c + i, back) for i in range(4)]
+        first_inner, body_inner = self.true(), self.true()
+        for c, ts in enumerate(cols):
+            dens = []
+            for t in ts:
+                lin = [None] * 4
+                for j, (g, col) in enumerate(t.tuple_cols):
+                    lin = self._e_add(lin, self._e_scale(bpow[j], self.get(g, col)))
+                if t.tag % P:
+                    lin = self._e_add(lin, [self.const(t.tag), None, None, None])
+                dens.append(self._e_sub(alpha, lin))
+            den = dens[0]
+            for d in dens[1:]:
+                den = self._e_mul(den, d)
+            num = [None] * 4
+            for i, t in enumerate(ts):
+                s = None
+                if t.sel is not None:
+                    s = self.get(GROUP_CODE, t.sel)
+                if t.mult is not None:
+                    m = self.get(*t.mult)
+                    s = m if s is None else self.mul(s, m)
+                rest = None
+                for l, d in enumerate(dens):
+                    if l != i:
+                        rest = d if rest is None else self._e_mul(rest, d)
+                if rest is None:
+                    v = [s if s is not None else self.const(1), None, None, None]
+                else:
+                    v = rest if s is None else self._e_scale(rest, s)
+                num = self._e_add(num, v) if t.sign == 1 else self._e_sub(num, v)
+            cur, prev = acc(c), acc(c, 1)
+            f = self._e_sub(self._e_mul(cur, den), num)
+            b = self._e_sub(self._e_mul(self._e_sub(cur, prev), den), num)
+            for i in range(4):
+                first_inner = self.and_eqz(first_inner, f[i] if f[i] is not None else self.const(0))
+                body_inner = self.and_eqz(body_inner, b[i] if b[i] is not None else self.const(0))
+        chain = self.and_cond(chain, first, first_inner)
+        chain = self.and_cond(chain, body, body_inner)
+        tot = [None] * 4
+        for c in range(self.k):
+            tot = self._e_add(tot, acc(c))
+        last_inner = self.true()
+        for i in range(4):
+            last_inner = self.and_eqz(last_inner, tot[i])
+        return self.and_cond(chain, last, last_inner)
+
+    def args(self) -> Arguments:
+        return Arguments(self.k, self.alpha_off, self.beta_off, sorted(self.terms, key=lambda t: t.col))
+
+    def finish_all(self, ret) -> Tuple[np.ndarray, np.ndarray]:
+        """-> (ZKC1 description, ZKA1 argument blob)"""
+        return self.finish(ret), self.args().blob()
+
+
+# ---- host reference of the accumulate (numpy over canonical residues; the library's kernels work on Montgomery words) ----
+_R = (1 << 32) % P
+_RINV = pow(_R, -1, P)
+
+
+def _dec(a):
+    return (np.asarray(a, dtype=np.uint64) * np.uint64(_RINV)) % np.uint64(P)
+
+
+def _enc(a):
+    return ((np.asarray(a, dtype=np.uint64) % np.uint64(P)) * np.uint64(_R)) % np.uint64(P)
+
+
+def _m(a, b):
+    return (a * b) % np.uint64(P)
+
+
+def _e_mul_np(x, y):
+    c = [np.zeros_like(x[0]) for _ in range(7)]
+    for i in range(4):
+        for j in range(4):
+            c[i + j] = (c[i + j] + _m(x[i], y[j])) % np.uint64(P)
+    nb = np.uint64(NBETA)
+    return [(c[i] + _m(c[i + 4], nb)) % np.uint64(P) if i < 3 else c[3] for i in range(4)]
+
+
+def _fp_inv_np(a):
+    r = np.ones_like(a)
+    base = a.copy()
+    e = P - 2
+    while e:
+        if e & 1:
+            r = _m(r, base)
+        base = _m(base, base)
+        e >>= 1
+    return r
+
+
+def _e_inv_np(a):
+    """the tower formula of fp4_inv (fp.h), canonical residues"""
+    p = np.uint64(P)
+    beta = np.uint64(11)
+    a0, a1, a2, a3 = a
+    b0 = (_m(a0, a0) + _m(beta, (_m((2 * a1) % p, a3) + p - _m(a2, a2)) % p)) % p
+    b2 = (_m((2 * a0) % p, a2) + p - _m(a1, a1) + _m(beta, _m(a3, a3))) % p
+    ic = _fp_inv_np((_m(b0, b0) + _m(beta, _m(b2, b2))) % p)
+    b0, b2 = _m(b0, ic), _m(b2, ic)
+    neg = lambda v: (p - v) % p
+    return _e_mul_np([a0, neg(a1), a2, neg(a3)], [b0, np.zeros_like(b0), neg(b2), np.zeros_like(b0)])
+
+
+class ReferenceError(ValueError):
+    pass
+
+
+def reference_accumulate(args: Arguments, po2: int, zk_cycles: int, code, data, mix, noise=None, check_balance: bool = True):
+    """The accum trace (W_accum x 2^po2 raw Montgomery words) zkh_accumulate must produce, computed on the host.
+    code / data / mix: raw Montgomery words as the library takes them.  noise(col) -> the zk_cycles blinding words of Fp column
+    `col` (rows A..n-1), or None: zeros.  Raises ReferenceError on a vanishing denominator, and (check_balance) on a bus total
+    that is not zero; returns (accum, total) with total the 4 canonical components of sum_c S_c[A-1]."""
+    n = 1 << po2
+    A = n - zk_cycles
+    groups = {GROUP_CODE: np.asarray(code, dtype=np.uint32).reshape(-1, n), GROUP_DATA: np.asarray(data, dtype=np.uint32).reshape(-1, n)}
+    mixc = _dec(np.asarray(mix, dtype=np.uint32))
+    alpha = [np.full(A, mixc[args.alpha + i], dtype=np.uint64) for i in range(4)]
+    beta = [np.full(A, mixc[args.beta + i], dtype=np.uint64) for i in range(4)]
+    bpow = [beta]
+    for _ in range(MAX_TUPLE - 1):
+        bpow.append(_e_mul_np(bpow[-1], beta))
+    col = lambda g, c: _dec(groups[g][c, :A])
+    accum = np.zeros((4 * args.k, n), dtype=np.uint32)
+    total = [0, 0, 0, 0]
+    for c, ts in enumerate(args.by_column()):
+        s = [np.zeros(A, dtype=np.uint64) for _ in range(4)]
+        for i, t in enumerate(ts):
+            lin = [np.zeros(A, dtype=np.uint64) for _ in range(4)]
+            for j, (g, cc) in enumerate(t.tuple_cols):
+                v = col(g, cc)
+                lin = [(lin[e] + _m(bpow[j][e], v)) % np.uint64(P) for e in range(4)]
+            lin[0] = (lin[0] + np.uint64(t.tag % P)) % np.uint64(P)
+            den = [(alpha[e] + np.uint64(P) - lin[e]) % np.uint64(P) for e in range(4)]
+            zero = ~(den[0].astype(bool) | den[1].astype(bool) | den[2].astype(bool) | den[3].astype(bool))
+            if zero.any():
+                r = int(np.argmax(zero))
+                raise ReferenceError(f"denominator vanishes at row {r}, accum column {c}, term {i}")
+            inv = _e_inv_np(den)
+            f = np.ones(A, dtype=np.uint64)
+            if t.sel is not None:
+                f = _m(f, col(GROUP_CODE, t.sel))
+            if t.mult is not None:
+                f = _m(f, col(*t.mult))
+            if t.sign == -1:
+                f = (np.uint64(P) - f) % np.uint64(P)
+            s = [(s[e] + _m(inv[e], f)) % np.uint64(P) for e in range(4)]
+        for e in range(4):
+            run = np.cumsum(s[e] % np.uint64(P), dtype=np.uint64) % np.uint64(P)       # < 2^31 * 2^24: no wrap
+            accum[4 * c + e, :A] = _enc(run).astype(np.uint32)
+            total[e] = (total[e] + int(run[-1])) % P
+            if noise is not None:
+                accum[4 * c + e, A:] = np.asarray(noise(4 * c + e), dtype=np.uint32)
+    if check_balance and any(total):
+        raise ReferenceError(f"the bus does not balance: total {total}")
+    return accum.reshape(-1), total

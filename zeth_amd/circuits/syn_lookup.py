@@ -1,0 +1,154 @@
+"""SYN-LOOKUP: the declared-synthetic circuit whose accum group is a SOUND argument — range lookups and a multiset equality as
+log-derivative sums (logup.py), sealed through the library's built-in accumulate (zkh_accumulate).
+
+The shape of what a real zkVM circuit keeps in its accum group: byte / range tables and the memory argument (DESIGN.md §2
+ARGUMENTS).  Columns (n rows, A = n - zk_cycles active rows, L = limb_bits):
+  code : c0 active, c1 first, c2 body (active & !first), c3 row index, c4 last (row A-1), c5 table selector (rows < 2^L),
+         c6 table value (= row on table rows, else 0)
+  data : words w_k (n_words), then limbs b_{k,j} (n_words x n_limbs), the table multiplicity m, then n_mem (addr, val, time)
+         tuples and their permuted copies
+  accum: the argument's running sums, three terms per Fp4 column
+Constraints: w_k = sum_j b_{k,j} 2^{j L} on active rows; the argument (logup.py); SYN-AIR's selector sanity.
+Argument terms (one bus):
+  tag 0 — every limb +1 (tuple (b)); the table -m on table rows (tuple (c6), selector c5)
+  tag 1 — every memory tuple +1 (addr, val, time), its permuted copy -1
+Globals: out = 4 zero words; mix = alpha (words 0..3), beta (4..7).
+The witness comes from the host (`witness`, numpy): the upstream flow of a CPU preflight + witgen uploaded as caller traces.
+Not a shipped circuit: its control root is zkh_code_root of its code trace.
+"""
+from __future__ import annotations
+
+from typing import NamedTuple, Tuple
+
+import numpy as np
+
+from .desc import GROUP_CODE, GROUP_DATA, P
+from .logup import LogupBuilder
+
+N_CODE = 7
+MEM_W = 3
+
+
+def layout(n_words: int, n_limbs: int, n_mem: int):
+    """data column indices: (words, limbs[k][j], m, mem tuples, permuted tuples)"""
+    words = list(range(n_words))
+    limbs = [[n_words + k * n_limbs + j for j in range(n_limbs)] for k in range(n_words)]
+    m = n_words + n_words * n_limbs
+    mem = [[m + 1 + MEM_W * i + e for e in range(MEM_W)] for i in range(n_mem)]
+    perm = [[m + 1 + MEM_W * (n_mem + i) + e for e in range(MEM_W)] for i in range(n_mem)]
+    return words, limbs, m, mem, perm
+
+
+class Shape(NamedTuple):
+    n_words: int
+    n_limbs: int
+    limb_bits: int
+    n_mem: int = 1
+
+
+TINY = Shape(2, 4, 4, 1)            # 11 terms in 4 accum columns (po2 8..12)
+FULL = Shape(16, 4, 8, 1)           # 67 terms in 23 accum columns, 87 data columns (sealed at po2 20)
+
+
+def build_syn_lookup(shape: Shape = FULL) -> Tuple[np.ndarray, np.ndarray]:
+    """-> (ZKC1 description, ZKA1 argument blob)"""
+    n_words, n_limbs, limb_bits, n_mem = shape
+    words, limbs, m, mem, perm = layout(n_words, n_limbs, n_mem)
+    wd = m + 1 + 2 * MEM_W * n_mem
+    n_terms = n_words * n_limbs + 1 + 2 * n_mem
+    k = (n_terms + 2) // 3
+    b = LogupBuilder((4 * k, N_CODE, wd), (4, 8), alpha=0, beta=4)
+    code = lambda c: b.get(GROUP_CODE, c)
+    data = lambda c: b.get(GROUP_DATA, c)
+    one = b.const(1)
+    active, first, body, _rowidx, last = (code(i) for i in range(5))
+    # the terms, three per column in this order: limbs, the table, the memory pair
+    specs = [dict(tuple_cols=[(GROUP_DATA, c)], tag=0) for row in limbs for c in row]
+    specs.append(dict(tuple_cols=[(GROUP_CODE, 6)], sign=-1, sel=5, mult=(GROUP_DATA, m), tag=0))
+    for i in range(n_mem):
+        specs.append(dict(tuple_cols=[(GROUP_DATA, c) for c in mem[i]], sign=1, tag=1))
+        specs.append(dict(tuple_cols=[(GROUP_DATA, c) for c in perm[i]], sign=-1, tag=1))
+    for i, s in enumerate(specs):
+        b.term(i // 3, **s)
+    # words = sum of their limbs, on active rows
+    inner = b.true()
+    for kk in range(n_words):
+        acc = None
+        for j in range(n_limbs):
+            v = data(limbs[kk][j]) if j == 0 else b.mul(b.const(1 << (j * limb_bits)), data(limbs[kk][j]))
+            acc = v if acc is None else b.add(acc, v)
+        inner = b.and_eqz(inner, b.sub(data(words[kk]), acc))
+    chain = b.and_cond(b.true(), active, inner)
+    chain = b.arguments(chain, first, body, last)
+    chain = b.and_eqz(chain, b.mul(active, b.sub(one, active)))
+    chain = b.and_eqz(chain, b.mul(first, b.sub(one, first)))
+    chain = b.and_eqz(chain, b.sub(b.sub(active, first), body))
+    return b.finish_all(chain)
+
+
+def syn_lookup_tiny() -> Tuple[np.ndarray, np.ndarray]:
+    return build_syn_lookup(TINY)
+
+
+def syn_lookup() -> Tuple[np.ndarray, np.ndarray]:
+    return build_syn_lookup(FULL)
+
+
+def _enc(x) -> np.ndarray:
+    return ((np.asarray(x, dtype=np.uint64) % np.uint64(P)) * np.uint64((1 << 32) % P) % np.uint64(P)).astype(np.uint32)
+
+
+def witness(shape: Shape, po2: int, zk_cycles: int, seed: int = 1):
+    """-> (code, data, out_global) host arrays of raw Montgomery words: random words below min(P, 2^(n_limbs L)) split into limbs,
+    the table's multiplicities, random memory tuples and their copy sorted by (addr, time); blinding rows of data from the same
+    seeded generator"""
+    n_words, n_limbs, limb_bits, n_mem = shape
+    words, limbs, m_col, mem, perm = layout(n_words, n_limbs, n_mem)
+    wd = m_col + 1 + 2 * MEM_W * n_mem
+    n = 1 << po2
+    A = n - zk_cycles
+    T = 1 << limb_bits
+    assert A >= T, f"po2 {po2}: {A} active rows do not hold the {T}-row table"
+    rng = np.random.default_rng(seed)
+    code = np.zeros((N_CODE, n), dtype=np.uint64)
+    rows = np.arange(n, dtype=np.uint64)
+    code[0, :A] = 1
+    code[1, 0] = 1
+    code[2, 1:A] = 1
+    code[3, :A] = rows[:A]
+    code[4, A - 1] = 1
+    code[5, :T] = 1
+    code[6, :T] = rows[:T]
+    data = np.zeros((wd, n), dtype=np.uint64)
+    hi = min(P, 1 << (n_limbs * limb_bits))
+    counts = np.zeros(T, dtype=np.int64)
+    for kk in range(n_words):
+        w = rng.integers(0, hi, size=A, dtype=np.uint64)
+        data[words[kk], :A] = w
+        for j in range(n_limbs):
+            limb = (w >> np.uint64(j * limb_bits)) & np.uint64(T - 1)
+            data[limbs[kk][j], :A] = limb
+            counts += np.bincount(limb.astype(np.int64), minlength=T)
+    data[m_col, :T] = counts.astype(np.uint64)
+    for i in range(n_mem):
+        addr = rng.integers(0, 1 << 20, size=A, dtype=np.uint64)
+        val = rng.integers(0, P, size=A, dtype=np.uint64)
+        time = rng.permutation(A).astype(np.uint64)
+        order = np.lexsort((time, addr))
+        for e, v in enumerate((addr, val, time)):
+            data[mem[i][e], :A] = v
+            data[perm[i][e], :A] = v[order]
+    data[:, A:] = rng.integers(0, P, size=(wd, n - A), dtype=np.uint64)
+    return _enc(code).reshape(-1), _enc(data).reshape(-1), np.zeros(4, dtype=np.uint32)
+
+
+def corrupt_limb(shape: Shape, data, po2: int, row: int, word: int = 0) -> np.ndarray:
+    """a copy of `data` in which limb 0 of word `word` on `row` is raised by 2^L — outside the table — and the word by the same
+    amount, so that the decomposition still holds and only the lookup can object; the multiplicities are unchanged"""
+    words, limbs, _m, _mem, _perm = layout(shape.n_words, shape.n_limbs, shape.n_mem)
+    n = 1 << po2
+    d = np.array(data, dtype=np.uint32).reshape(-1, n)
+    add = (1 << shape.limb_bits) * ((1 << 32) % P) % P
+    for c in (limbs[word][0], words[word]):
+        d[c, row] = (int(d[c, row]) + add) % P
+    return d.reshape(-1)

@@ -1,0 +1,296 @@
+// accumulate.hip — the built-in CircuitHal::accumulate for circuits whose accum group is described as DATA: lookup and
+// permutation arguments as log-derivative sums (ZKA1 blob, zeth_amd/circuits/logup.py; DESIGN.md §2 ARGUMENTS).
+//
+//   t_i(r)  = sign_i sel_i(r) m_i(r) / (alpha - (tag_i + beta v_0(r) + ... + beta^w v_{w-1}(r)))        (Fp4)
+//   S_c[r]  = sum_{r' <= r} sum_{terms i of column c} t_i(r')        on the active rows [0, A); blinding noise on [A, n)
+//   bus     : sum_c S_c[A-1] = 0
+//
+// Three steps on the context stream:
+//   (a) k_args_terms: one thread owns ARGS_BATCH rows of one accum column, interleaved by the block width so that a wave's column
+//       loads are coalesced.  Per row the column's terms (at most 3) are folded into one fraction N / D; the batch's D are inverted
+//       with ONE fp4_inv (Montgomery's trick) and N / D is written in place into the column's four Fp planes of `accum`;
+//   (b) an inclusive prefix sum over the A active rows of all 4k Fp planes in one set of launches (the batched sibling of
+//       circuit.hip's k_prefix_sum_chunks / _fp / _carry), which also leaves every plane's total;
+//   (c) the blinding rows (noise_cell(GROUP_ACCUM, column, row), as k_syn_accum_store writes them).
+// The host then reads back the totals and the first vanishing denominator (one sync) and refuses the witness if either is wrong:
+// the accum is zeroed and an error names the row and column, or the bus total.
+#include "circuit.h"
+
+using namespace zkh;
+
+namespace {
+
+constexpr uint32_t ARGS_MAGIC = 0x5a4b4131u;        // 'ZKA1'
+constexpr uint32_t ARGS_HEADER = 8, TERM_WORDS = 16, MAX_TUPLE = 4, MAX_TERMS = 3, NONE = 0xffffffffu;
+constexpr uint32_t ARGS_THREADS = 256;
+// Rows per thread.  The batch keeps D, the running product before each row and N (3 Fp4 = 12 VGPRs per row) in registers, which needs
+// the batch loops fully unrolled (build.py passes a higher pragma-unroll threshold for this file; without it the arrays go to
+// scratch).  hipcc -Rpass-analysis=kernel-resource-usage, no scratch in either case: 4 rows -> 68 VGPRs = 7 waves per SIMD,
+// 6 rows -> 104 VGPRs = 4 waves, 8 rows -> 134 VGPRs = 3 waves (512 VGPRs per SIMD lane, allocated in steps of 8).  4 rows: one fp4_inv
+// (~65 Fp products) costs ~16 products per row against ~110 for the row itself at 3 terms.
+constexpr uint32_t ARGS_BATCH = 4;
+
+// one term, prepared on the host: Montgomery words, columns resolved to (group, column)
+struct ArgTerm {
+    uint32_t am[4];                 // alpha - tag (Fp4)
+    uint32_t w, neg, sel, mg, mc;   // tuple width; sign; selector code column or NONE; multiplicity group (NONE = 1) and column
+    uint32_t tg[MAX_TUPLE], tc[MAX_TUPLE];
+};
+struct ArgCols { uint32_t begin, count; };
+struct BetaPows { uint32_t b[MAX_TUPLE][4]; };      // beta^1 .. beta^4
+
+__device__ __forceinline__ const uint32_t* group_ptr(const uint32_t* code, const uint32_t* data, uint32_t g) { return g == GROUP_CODE ? code : data; }
+__device__ __forceinline__ bool fp4_is_zero(const Fp4& x) { return (x.c[0].v | x.c[1].v | x.c[2].v | x.c[3].v) == 0; }
+
+// N / D of one row: the column's terms folded as N / D + f / d = (N d + f D) / (D d); rows past A give 0 / 1.  Fixed trip counts
+// (MAX_TERMS, MAX_TUPLE) with guards, so that the batch arrays of the caller stay in registers.
+__device__ __forceinline__ void row_fraction(const uint32_t* __restrict__ code, const uint32_t* __restrict__ data, const ArgTerm* __restrict__ terms,
+                                             const ArgCols cc, const BetaPows& bp, uint32_t n, uint32_t A, uint32_t r, uint32_t c,
+                                             unsigned long long* __restrict__ bad, Fp4& D, Fp4& N) {
+    D = Fp4::one();
+    N = Fp4::zero();
+    if (r >= A) return;
+#pragma unroll
+    for (uint32_t i = 0; i < MAX_TERMS; i++) {
+        if (i < cc.count) {
+            const ArgTerm& t = terms[cc.begin + i];
+            Fp4 d(Fp::raw(t.am[0]), Fp::raw(t.am[1]), Fp::raw(t.am[2]), Fp::raw(t.am[3]));
+#pragma unroll
+            for (uint32_t e = 0; e < MAX_TUPLE; e++) {
+                if (e < t.w) {
+                    const Fp v = Fp::raw(group_ptr(code, data, t.tg[e])[(size_t)t.tc[e] * n + r]);
+                    const Fp4 b(Fp::raw(bp.b[e][0]), Fp::raw(bp.b[e][1]), Fp::raw(bp.b[e][2]), Fp::raw(bp.b[e][3]));
+                    d = d - b * v;
+                }
+            }
+            Fp f = Fp::one();
+            if (t.sel != NONE) f = Fp::raw(code[(size_t)t.sel * n + r]);
+            if (t.mg != NONE) f = f * Fp::raw(group_ptr(code, data, t.mg)[(size_t)t.mc * n + r]);
+            if (t.neg) f = -f;
+            if (fp4_is_zero(d)) atomicMin(bad, ((unsigned long long)r << 32) | (c << 2) | i);
+            if (i == 0) { N = Fp4(f); D = d; }
+            else { N = N * d + D * f; D = D * d; }
+        }
+    }
+}
+
+// (a) terms: grid (ceil(A / (ARGS_THREADS * ARGS_BATCH)), k)
+__global__ __launch_bounds__(ARGS_THREADS) void k_args_terms(uint32_t* __restrict__ accum, const uint32_t* __restrict__ code,
+                                                            const uint32_t* __restrict__ data, const ArgTerm* __restrict__ terms,
+                                                            const ArgCols* __restrict__ cols, BetaPows bp, uint32_t n, uint32_t A,
+                                                            unsigned long long* __restrict__ bad) {
+    const uint32_t c = blockIdx.y;
+    const ArgCols cc = cols[c];
+    const uint32_t base = blockIdx.x * (ARGS_THREADS * ARGS_BATCH) + threadIdx.x;
+    Fp4 D[ARGS_BATCH], Pre[ARGS_BATCH], N[ARGS_BATCH];
+    Fp4 run = Fp4::one();
+#pragma unroll
+    for (uint32_t j = 0; j < ARGS_BATCH; j++) {
+        row_fraction(code, data, terms, cc, bp, n, A, base + j * ARGS_THREADS, c, bad, D[j], N[j]);
+        Pre[j] = run;                  // product of the batch's D before row j
+        run = run * D[j];
+    }
+    Fp4 inv = fp4_inv(run);            // 1 / prod_j D_j (0 if some D_j vanished: that row is reported, the accum refused)
+#pragma unroll
+    for (uint32_t jj = 0; jj < ARGS_BATCH; jj++) {
+        const uint32_t j = ARGS_BATCH - 1 - jj;
+        const uint32_t r = base + j * ARGS_THREADS;
+        const Fp4 t = N[j] * (inv * Pre[j]);
+        inv = inv * D[j];
+        if (r < A)
+#pragma unroll
+            for (int e = 0; e < 4; e++) accum[(size_t)(4 * c + e) * n + r] = t.c[e].v;
+    }
+}
+
+// (b) batched inclusive scan over the first A words of every plane: plane = blockIdx.y, planes n words apart
+__device__ __forceinline__ uint32_t block_scan_1024(uint32_t v, uint32_t (*buf)[1024]) {
+    const uint32_t t = threadIdx.x;
+    buf[0][t] = v;
+    __syncthreads();
+    int cur = 0;
+    for (uint32_t d = 1; d < 1024; d <<= 1) {
+        uint32_t x = buf[cur][t];
+        if (t >= d) x = add_mod(x, buf[cur][t - d]);
+        buf[cur ^ 1][t] = x;
+        cur ^= 1;
+        __syncthreads();
+    }
+    return buf[cur][t];
+}
+__global__ __launch_bounds__(1024) void k_args_scan_chunks(uint32_t* accum, uint32_t n, uint32_t A, uint32_t* totals, uint32_t chunks) {
+    __shared__ uint32_t buf[2][1024];
+    uint32_t* col = accum + (size_t)blockIdx.y * n;
+    const uint32_t i = blockIdx.x * 1024 + threadIdx.x;
+    const uint32_t v = block_scan_1024(i < A ? col[i] : 0, buf);
+    if (i < A) col[i] = v;
+    if (threadIdx.x == 1023) totals[(size_t)blockIdx.y * chunks + blockIdx.x] = v;
+}
+// one workgroup per plane over its chunk totals; last[plane] = the plane's grand total S[A-1]
+__global__ __launch_bounds__(1024) void k_args_scan_totals(uint32_t* totals, uint32_t chunks, uint32_t* last) {
+    __shared__ uint32_t buf[2][1024];
+    __shared__ uint32_t carry_s;
+    uint32_t* col = totals + (size_t)blockIdx.y * chunks;
+    const uint32_t t = threadIdx.x;
+    if (t == 0) carry_s = 0;
+    __syncthreads();
+    for (uint32_t base = 0; base < chunks; base += 1024) {
+        const uint32_t i = base + t;
+        const uint32_t v = add_mod(block_scan_1024(i < chunks ? col[i] : 0, buf), carry_s);
+        if (i < chunks) col[i] = v;
+        __syncthreads();
+        if (t == 1023) carry_s = v;
+        __syncthreads();
+    }
+    if (t == 0) last[blockIdx.y] = carry_s;
+}
+__global__ __launch_bounds__(1024) void k_args_scan_carry(uint32_t* accum, uint32_t n, uint32_t A, const uint32_t* totals, uint32_t chunks) {
+    const uint32_t i = blockIdx.x * 1024 + threadIdx.x;
+    if (blockIdx.x == 0 || i >= A) return;
+    uint32_t* col = accum + (size_t)blockIdx.y * n;
+    col[i] = add_mod(col[i], totals[(size_t)blockIdx.y * chunks + blockIdx.x - 1]);
+}
+
+// (c) blinding rows [A, n) of every plane
+__global__ void k_args_blind(uint32_t* accum, uint32_t n, uint32_t A, NoiseKey nk) {
+    const uint32_t r = A + blockIdx.x * blockDim.x + threadIdx.x, col = blockIdx.y;
+    if (r >= n) return;
+    accum[(size_t)col * n + r] = noise_cell(nk, GROUP_ACCUM, col, r);
+}
+
+const char* validate_args(const zkh_circuit* c, const uint32_t* a, size_t words) {
+    ZKH_REQUIRE(words >= ARGS_HEADER && a[0] == ARGS_MAGIC && a[1] == 1, "set_arguments: not a ZKA1 (version 1) argument blob");
+    const uint32_t k = a[2], alpha = a[3], beta = a[4], n_terms = a[5];
+    ZKH_REQUIRE(words == ARGS_HEADER + (size_t)TERM_WORDS * n_terms, "set_arguments: %zu words for %u terms", words, n_terms);
+    ZKH_REQUIRE(k >= 1 && 4ull * k == c->group_size[GROUP_ACCUM], "set_arguments: %u accum Fp4 columns, the circuit's accum group is %u wide",
+                k, c->group_size[GROUP_ACCUM]);
+    const uint32_t mix = c->global_size[GLOBAL_MIX];
+    ZKH_REQUIRE((uint64_t)alpha + 4 <= mix && (uint64_t)beta + 4 <= mix, "set_arguments: alpha / beta at mix words %u / %u, the circuit has %u",
+                alpha, beta, mix);
+    std::vector<uint32_t> per_col(k, 0);
+    uint32_t prev = 0;
+    for (uint32_t i = 0; i < n_terms; i++) {
+        const uint32_t* t = a + ARGS_HEADER + (size_t)TERM_WORDS * i;
+        const uint32_t col = t[0], neg = t[1], sel = t[2], mg = t[3], mc = t[4], tag = t[5], w = t[6];
+        ZKH_REQUIRE(col < k && col >= prev, "set_arguments: term %u: accum column %u (columns 0..%u, terms sorted by column)", i, col, k - 1);
+        prev = col;
+        ZKH_REQUIRE(++per_col[col] <= MAX_TERMS, "set_arguments: accum column %u has more than %u terms (the degree bound)", col, MAX_TERMS);
+        ZKH_REQUIRE(neg <= 1 && tag < P, "set_arguments: term %u: sign word %u / tag %u", i, neg, tag);
+        ZKH_REQUIRE(sel == NONE || sel < c->group_size[GROUP_CODE], "set_arguments: term %u: selector %u is not a code column", i, sel);
+        ZKH_REQUIRE(mg == NONE || ((mg == GROUP_CODE || mg == GROUP_DATA) && mc < c->group_size[mg]),
+                    "set_arguments: term %u: multiplicity column (%u, %u) is not a code or data column", i, mg, mc);
+        ZKH_REQUIRE(w >= 1 && w <= MAX_TUPLE, "set_arguments: term %u: tuple width %u (1..%u)", i, w, MAX_TUPLE);
+        for (uint32_t e = 0; e < w; e++) {
+            const uint32_t g = t[8 + 2 * e], cc = t[9 + 2 * e];
+            ZKH_REQUIRE((g == GROUP_CODE || g == GROUP_DATA) && cc < c->group_size[g], "set_arguments: term %u: tuple column (%u, %u) is not a "
+                        "code or data column", i, g, cc);
+        }
+    }
+    for (uint32_t col = 0; col < k; col++) ZKH_REQUIRE(per_col[col] >= 1, "set_arguments: accum column %u has no terms", col);
+    return nullptr;
+}
+
+}  // namespace
+
+extern "C" const char* zkh_circuit_set_arguments(zkh_circuit* c, const uint32_t* blob, size_t words) {
+    ZKH_REQUIRE(c && (blob || !words), "set_arguments: null argument");
+    if (!words) { c->args.clear(); return nullptr; }
+    ZKH_TRY(validate_args(c, blob, words));
+    c->args.assign(blob, blob + words);
+    return nullptr;
+}
+
+extern "C" int zkh_circuit_has_arguments(const zkh_circuit* c) { return c && !c->args.empty(); }
+
+extern "C" const char* zkh_accumulate(zkh_ctx* ctx, const zkh_circuit* c, size_t po2, size_t zk_cycles, const uint32_t* noise_key,
+                                      const zkh_buf* code, const zkh_buf* data, const uint32_t* mix_global, zkh_buf* accum) {
+    ZKH_REQUIRE(ctx && c && code && data && accum && mix_global, "accumulate: null argument");
+    ZKH_REQUIRE(!c->args.empty(), "accumulate: the circuit has no arguments (zkh_circuit_set_arguments)");
+    ZKH_REQUIRE(po2 >= 1 && po2 <= 24, "accumulate: po2 %zu out of range", po2);
+    const size_t n = (size_t)1 << po2;
+    ZKH_REQUIRE(zk_cycles < n, "accumulate: zk_cycles %zu leaves no active row at po2 %zu", zk_cycles, po2);
+    const uint32_t* a = c->args.data();
+    const uint32_t k = a[2], n_terms = a[5], A = (uint32_t)(n - zk_cycles);
+    ZKH_REQUIRE(code->len == (size_t)c->group_size[GROUP_CODE] * n && data->len == (size_t)c->group_size[GROUP_DATA] * n &&
+                accum->len == (size_t)4 * k * n, "accumulate: buffer shape mismatch");
+    NoiseKey nk;
+    ZKH_TRY(resolve_noise_key(noise_key, &nk));
+    bind_thread(ctx);
+
+    // the terms in device form: alpha - tag, beta's powers, columns resolved
+    const Fp4 alpha(Fp::raw(mix_global[a[3]]), Fp::raw(mix_global[a[3] + 1]), Fp::raw(mix_global[a[3] + 2]), Fp::raw(mix_global[a[3] + 3]));
+    const Fp4 beta(Fp::raw(mix_global[a[4]]), Fp::raw(mix_global[a[4] + 1]), Fp::raw(mix_global[a[4] + 2]), Fp::raw(mix_global[a[4] + 3]));
+    BetaPows bp;
+    Fp4 pw = beta;
+    for (uint32_t e = 0; e < MAX_TUPLE; e++, pw = pw * beta)
+        for (int i = 0; i < 4; i++) bp.b[e][i] = pw.c[i].v;
+    std::vector<ArgTerm> terms(n_terms);
+    std::vector<ArgCols> cols(k, ArgCols{0, 0});
+    for (uint32_t i = 0; i < n_terms; i++) {
+        const uint32_t* t = a + ARGS_HEADER + (size_t)TERM_WORDS * i;
+        ArgTerm& d = terms[i];
+        const Fp4 am = alpha - Fp4(fp_encode(t[5]));
+        for (int e = 0; e < 4; e++) d.am[e] = am.c[e].v;
+        d.w = t[6]; d.neg = t[1]; d.sel = t[2]; d.mg = t[3]; d.mc = t[4];
+        for (uint32_t e = 0; e < MAX_TUPLE; e++) { d.tg[e] = e < d.w ? t[8 + 2 * e] : GROUP_DATA; d.tc[e] = e < d.w ? t[9 + 2 * e] : 0; }
+        if (cols[t[0]].count == 0) cols[t[0]].begin = i;
+        cols[t[0]].count++;
+    }
+    static_assert(sizeof(ArgTerm) % 4 == 0 && sizeof(ArgCols) % 4 == 0, "word records");
+    std::vector<uint32_t> table(terms.size() * (sizeof(ArgTerm) / 4) + cols.size() * (sizeof(ArgCols) / 4));
+    memcpy(table.data(), terms.data(), terms.size() * sizeof(ArgTerm));
+    memcpy(table.data() + terms.size() * (sizeof(ArgTerm) / 4), cols.data(), cols.size() * sizeof(ArgCols));
+    Tmp dtab, status, totals;
+    ZKH_TRY(zkh_copy_from(ctx, "args_terms", table.data(), table.size(), dtab.out()));
+    const uint32_t planes = 4 * k, chunks = (A + 1023) / 1024;
+    ZKH_TRY(new_buf(ctx, 2 + planes, false, status.out()));          // [0, 2): first vanishing denominator (u64 key); then the plane totals
+    ZKH_TRY(new_buf(ctx, (size_t)planes * chunks, false, totals.out()));
+    ZKH_HIP(hipMemsetAsync(status->ptr(), 0xff, 8, ctx->stream));
+    unsigned long long* bad = (unsigned long long*)status->ptr();
+    const ArgTerm* d_terms = (const ArgTerm*)dtab->ptr();
+    const ArgCols* d_cols = (const ArgCols*)(dtab->ptr() + terms.size() * (sizeof(ArgTerm) / 4));
+    {
+        // per term and row: w tuple loads + selector + multiplicity in, 16 bytes (the Fp4 term) out per column and row
+        double in_words = 0;
+        for (const ArgTerm& t : terms) in_words += t.w + (t.sel != NONE) + (t.mg != NONE);
+        ProfScope prof(ctx, "args_terms", 4.0 * in_words * A + 16.0 * k * A);
+        const unsigned bx = (unsigned)((A + ARGS_THREADS * ARGS_BATCH - 1) / (ARGS_THREADS * ARGS_BATCH));
+        k_args_terms<<<dim3(bx, k), ARGS_THREADS, 0, ctx->stream>>>(accum->ptr(), code->ptr(), data->ptr(), d_terms, d_cols, bp, (uint32_t)n, A, bad);
+        ZKH_TRY(last_launch_error("args_terms"));
+    }
+    {
+        ProfScope prof(ctx, "args_scan", 4.0 * 4 * planes * (double)A);
+        k_args_scan_chunks<<<dim3(chunks, planes), 1024, 0, ctx->stream>>>(accum->ptr(), (uint32_t)n, A, totals->ptr(), chunks);
+        k_args_scan_totals<<<dim3(1, planes), 1024, 0, ctx->stream>>>(totals->ptr(), chunks, status->ptr() + 2);
+        k_args_scan_carry<<<dim3(chunks, planes), 1024, 0, ctx->stream>>>(accum->ptr(), (uint32_t)n, A, totals->ptr(), chunks);
+        ZKH_TRY(last_launch_error("args_scan"));
+    }
+    if (n > A) {
+        ProfScope prof(ctx, "args_blind", 4.0 * planes * (double)(n - A));
+        k_args_blind<<<dim3((unsigned)((n - A + 255) / 256), planes), 256, 0, ctx->stream>>>(accum->ptr(), (uint32_t)n, A, nk);
+        ZKH_TRY(last_launch_error("args_blind"));
+    }
+    std::vector<uint32_t> st(2 + planes);
+    ZKH_TRY(zkh_read(ctx, status, st.data(), 0, st.size()));
+    unsigned long long key;
+    memcpy(&key, st.data(), 8);
+    const char* refusal = nullptr;
+    if (key != ~0ull) {
+        const uint32_t row = (uint32_t)(key >> 32), col = ((uint32_t)key) >> 2, term = key & 3;
+        refusal = make_err("accumulate: a denominator vanishes at row %u, accum column %u (Fp columns %u..%u), term %u of the column: "
+                           "the witness is refused", row, col, 4 * col, 4 * col + 3, term);
+    } else {
+        Fp4 tot = Fp4::zero();
+        for (uint32_t col = 0; col < k; col++)
+            tot += Fp4(Fp::raw(st[2 + 4 * col]), Fp::raw(st[3 + 4 * col]), Fp::raw(st[4 + 4 * col]), Fp::raw(st[5 + 4 * col]));
+        if (!(tot == Fp4::zero()))
+            refusal = make_err("accumulate: the bus does not balance: total (%u, %u, %u, %u) over the %u accum columns, not zero: the witness "
+                               "is refused", fp_decode(tot.c[0]), fp_decode(tot.c[1]), fp_decode(tot.c[2]), fp_decode(tot.c[3]), k);
+    }
+    if (refusal) {                                       // no accum: the refused trace is not left behind for a seal
+        (void)hipMemsetAsync(accum->ptr(), 0, accum->len * 4, ctx->stream);
+        (void)hipStreamSynchronize(ctx->stream);
+        return refusal;
+    }
+    return nullptr;
+}

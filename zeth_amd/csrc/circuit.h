@@ -116,6 +116,9 @@ struct zkh_circuit {
     uint32_t n_fp_slots, n_mix_slots, n_mix_pows, ret_slot;   // n_mix_slots: 16-byte slots (mix totals and Fp4-valued values)
     uint32_t* d_prog;     // device copy of prog
     uint32_t* d_taps;     // device copy of taps (group, offset, back)
+    // ZKA1 argument blob (zkh_circuit_set_arguments; zeth_amd/circuits/logup.py): what zkh_accumulate builds the accum group from.
+    // Empty = the circuit has no arguments.
+    std::vector<uint32_t> args;
 };
 
 // Circuits whose segments chain: SYN-C (kind 1, out = (post, 0, 0, 0, pre): 5 words) and SYN-S (zeth_amd/circuits/syn_air.py

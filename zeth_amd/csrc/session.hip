@@ -616,7 +616,8 @@ static const char* seal_one(zkh_session* s, Lane& l, const zkh_segment& seg, uin
         if (!err) {
             if (s->accumulate) err = s->accumulate(s->accumulate_user, l.ctx, cir, seg.po2, data, mix.data(), accum);
             else if (cir->kind >= 1 && cir->kind <= 3) err = zkh_syn_accum(l.ctx, cir, seg.po2, ZKH_ZK_CYCLES, noise, data, mix.data(), accum);
-            else err = make_err("session: circuit kind %u has no built-in accum witness generator and no accumulate callback was set", cir->kind);
+            else if (zkh_circuit_has_arguments(cir)) err = zkh_accumulate(l.ctx, cir, seg.po2, ZKH_ZK_CYCLES, noise, code, data, mix.data(), accum);
+            else err = make_err("session: circuit kind %u has no built-in accum witness generator, no arguments and no accumulate callback was set", cir->kind);
         }
         if (err) { zkh_prove_abort(job); return err; }
         return zkh_prove_finish(job, accum, seal, words);

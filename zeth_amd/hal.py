@@ -149,6 +149,9 @@ ABI = {
     "zkh_chacha_block_host": (None, [_u32p, _u32p, _i, _u32p]),
     "zkh_syn_witgen": (_err, [_vp, _vp, _sz, _sz, _u64, _u32p, _u32p, _vp, _vp, _u32p]),
     "zkh_syn_accum": (_err, [_vp, _vp, _sz, _sz, _u32p, _vp, _u32p, _vp]),
+    "zkh_circuit_set_arguments": (_err, [_vp, _u32p, _sz]),
+    "zkh_circuit_has_arguments": (_i, [_vp]),
+    "zkh_accumulate": (_err, [_vp, _vp, _sz, _sz, _u32p, _vp, _vp, _u32p, _vp]),
     "zkh_syn_chain_contributions": (_err, [_vp, _vp, C.POINTER(_u64), _u32p, _sz, _sz, _u32p]),
     "zkh_syn_preflight_ram_words": (_sz, []),
     "zkh_syn_preflight": (_err, [_u64, _sz, _sz, _u32p, _u32p, C.POINTER(C.c_double)]),
@@ -313,6 +316,14 @@ class Circuit:
 
     def compiled_parts(self) -> int:
         return int(_lib.zkh_circuit_compiled_parts(self.h))
+
+    def set_arguments(self, blob) -> None:
+        """attach a ZKA1 argument blob (circuits/logup.py): zkh_accumulate then builds this circuit's accum group; None removes it"""
+        self._args = _u32(blob) if blob is not None else np.zeros(0, np.uint32)
+        _check(_lib.zkh_circuit_set_arguments(self.h, _ptr(self._args) if self._args.size else None, self._args.size))
+
+    def has_arguments(self) -> bool:
+        return bool(_lib.zkh_circuit_has_arguments(self.h))
 
     def jit(self, use_cache: bool = True) -> None:
         """Generate + compile (hipcc --genco per part, in parallel, disk-cached) + attach the straight-line eval_check
@@ -744,6 +755,14 @@ class HipHal:
         m = _u32(mix_global)
         _k, kp = _key_ptr(noise_seed)
         _check(_lib.zkh_syn_accum(self.ctx, circuit.h, po2, zk_cycles, kp, data.h, _ptr(m), accum.h))
+
+    def accumulate(self, circuit: Circuit, po2: int, zk_cycles: int, noise_seed: int, code: Buffer, data: Buffer, mix_global,
+                   accum: Buffer) -> None:
+        """CircuitHal::accumulate for a circuit with arguments (zkh_accumulate): raises HalError if a denominator vanishes or the bus
+        does not balance (the accum is then left zeroed)"""
+        m = _u32(mix_global)
+        _k, kp = _key_ptr(noise_seed)
+        _check(_lib.zkh_accumulate(self.ctx, circuit.h, po2, zk_cycles, kp, code.h, data.h, _ptr(m), accum.h))
 
     # ---- profiling ----
     def prof_enable(self, on: bool = True) -> None:

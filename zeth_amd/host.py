@@ -681,6 +681,15 @@ class Session:
         segment like upstream's SegmentProver.  Seals are byte-identical."""
         self._hal._lib.zkh_session_set_resident_code(self.h, int(on))
 
+    def set_arguments(self, blob) -> None:
+        """attach a ZKA1 argument blob (circuits/logup.py) to every lane's circuit: segments with caller traces and no accumulate
+        callback then get their accum from zkh_accumulate"""
+        a = self._np.ascontiguousarray(blob, dtype=self._np.uint32)
+        self._args = a
+        for lane in range(int(self._hal._lib.zkh_session_lanes(self.h))):
+            c = self._hal._lib.zkh_session_circuit(self.h, lane, 0)
+            self._hal._check(self._hal._lib.zkh_circuit_set_arguments(c, self._hal._ptr(a), a.size))
+
     def _specs(self, segments: Sequence[Segment], host_traces=None):
         C, np = self._C, self._np
         arr = (self._hal.SegmentSpec * len(segments))()

@@ -116,12 +116,15 @@ class SegmentReceipt:
 class SegmentProver:
     """`SegmentProverImpl<H, C>` analogue bound to one HipHal (one GPU)."""
 
-    def __init__(self, hal: "_hal.HipHal", circuit_desc=None, resident_code_group: bool = False):
+    def __init__(self, hal: "_hal.HipHal", circuit_desc=None, resident_code_group: bool = False, arguments=None):
         """resident_code_group: keep the committed code (control) group of each segment size in HBM instead of re-committing
         it for every segment (zkh_prover_cache_code): the group is a function of (circuit, po2, zk_cycles) alone.  Off by
-        default — upstream's SegmentProver recomputes it, and so does the benchmark's headline number."""
+        default — upstream's SegmentProver recomputes it, and so does the benchmark's headline number.
+        arguments: the circuit's ZKA1 argument blob (circuits/logup.py), if its accum group is built by zkh_accumulate."""
         self.hal = hal
         self.circuit = hal.load_circuit(syn_air.syn_a() if circuit_desc is None else circuit_desc)
+        if arguments is not None:
+            self.circuit.set_arguments(arguments)
         h = C.c_void_p()
         _hal._check(_hal._lib.zkh_prover_create(hal.ctx, self.circuit.h, C.byref(h)))
         self.h = h
@@ -236,14 +239,30 @@ class SegmentProver:
             return accum
         return acc
 
+    def args_accumulate(self, seg: Segment, code, data):
+        """`accumulate` callback for a circuit with arguments (zkh_accumulate over the raw code and data traces): refuses a witness
+        whose denominators vanish or whose bus does not balance (HalError)"""
+        wa = self.group_sizes()[0]
+        if code is None:
+            raise _hal.HalError("args_accumulate: the arguments read the raw code trace; it is not held (resident code group)")
+
+        def acc(mix_global):
+            accum = self.hal.alloc_elem("accum", wa << seg.po2)
+            self.hal.accumulate(self.circuit, seg.po2, seg.zk_cycles, seg.noise_seed, code, data, mix_global, accum)
+            return accum
+        return acc
+
     def seal_host_witness(self, seg: Segment, host_code: np.ndarray, host_data: np.ndarray, out_global) -> SegmentReceipt:
         """Seal a segment whose code/data traces live in pinned HOST memory (hal.host_alloc views): enqueue both uploads
-        on the context's stream (no host sync), then run the two-halves seal.  This is the PCIe-inclusive path."""
+        on the context's stream (no host sync), then run the two-halves seal.  This is the PCIe-inclusive path.  The accum
+        comes from the built-in generator of kinds 1..3, else from zkh_accumulate when the circuit carries arguments."""
         code = self.hal.alloc_elem("code", host_code.size)
         data = self.hal.alloc_elem("data", host_data.size)
         self.hal.write_async(code, host_code)
         self.hal.write_async(data, host_data)
-        return self.seal_with_accum(seg, code, data, out_global, self.syn_accumulate(seg, data))
+        builtin = 1 <= int(self.circuit.desc[13]) <= 3
+        acc = self.args_accumulate(seg, code, data) if not builtin and self.circuit.has_arguments() else self.syn_accumulate(seg, data)
+        return self.seal_with_accum(seg, code, data, out_global, acc)
 
     def prove_segment(self, seg: Segment) -> SegmentReceipt:
         code, data, out = self.witgen(seg)
