@@ -225,6 +225,16 @@ const char* zkh_circuit_set_arguments(zkh_circuit*, const uint32_t* blob, size_t
 int zkh_circuit_has_arguments(const zkh_circuit*);
 const char* zkh_accumulate(zkh_ctx*, const zkh_circuit*, size_t po2, size_t zk_cycles, const uint32_t noise_key[8], const zkh_buf* code,
                            const zkh_buf* data, const uint32_t* mix_global, zkh_buf* accum);
+/* Derived multiplicities (ZKA1 version 2: term word 7 bit 0).  A derived term is the table side of a lookup: sign -1, its multiplicity a
+ * data column that nothing else in the blob names, every other term of its tag a lookup of sign +1.  zkh_derive_multiplicities writes
+ * that column on the active rows [0, 2^po2 - zk_cycles) of `data`: on the representative of each table key (its entry of smallest
+ * (blob term index, row)) the number of lookups of that key (the sum of their sel * m, in Fp, Montgomery form), 0 on every other
+ * active row; the blinding rows are not touched.  Keys are (tag, v_0 .. v_3) compared as field elements, the tuple zero-padded.  It
+ * FAILS and leaves `data` unchanged when a table selector is neither 0 nor 1, or when a lookup of nonzero weight has no table entry
+ * (the error names the term, tag, row and key).  Call it after the data upload and before zkh_prove_begin: the multiplicities belong
+ * to the data group.  Sessions with caller traces and SegmentProver.seal_host_witness do so when the circuit derives. */
+int zkh_circuit_derives_multiplicities(const zkh_circuit*);
+const char* zkh_derive_multiplicities(zkh_ctx*, const zkh_circuit*, size_t po2, size_t zk_cycles, const zkh_buf* code, zkh_buf* data);
 
 /* ---- built-in witness generators on the device, by circuit kind (desc word 13) ----
  *   kind 1 SYN-AIR   stands in for risc0-circuit-rv32im's witgen (declared synthetic)

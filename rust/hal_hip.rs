@@ -316,6 +316,19 @@ impl HipCircuitHal {
     pub fn has_arguments(&self) -> bool {
         unsafe { sys::zkh_circuit_has_arguments(self.circuit) != 0 }
     }
+
+    /// The arguments (a ZKA1 version-2 blob) mark a lookup table's multiplicity as derived by the library.
+    pub fn derives_multiplicities(&self) -> bool {
+        unsafe { sys::zkh_circuit_derives_multiplicities(self.circuit) != 0 }
+    }
+
+    /// Fill the derived multiplicity columns of `data` on the active rows from the raw code (ctrl) and data traces
+    /// (`zkh_derive_multiplicities`), before the data group is committed (`prove_begin`).  Panics on a refused witness (a table
+    /// selector other than 0 / 1, a lookup without a table entry), which leaves `data` unchanged, like every failed HAL op.
+    pub fn derive_multiplicities(&self, ctrl: &HipBuffer<BabyBearElem>, data: &HipBuffer<BabyBearElem>, steps: usize) {
+        let po2 = steps.trailing_zeros() as usize;
+        ffi(|| unsafe { sys::zkh_derive_multiplicities(self.hal.ctx.0, self.circuit, po2, sys::ZK_CYCLES, ctrl.raw, data.raw) });
+    }
 }
 
 impl Drop for HipCircuitHal {

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Per-op micro-benchmarks M1..M8 of SURVEY.md §8d (+ M9: the trace-driven witness, row f1; M10: the built-in accumulate of SYN-LOOKUP's
-arguments and its share of that circuit's seal) on one MI355X, through the C ABI (HipHal).
+arguments and its share of that circuit's seal; M11 / M11w: derived lookup multiplicities of SYN-LOOKUP-derived / WIDE) on one MI355X, through the C ABI (HipHal).
 
 Each line of output is one JSON object: the op, its shape, the average wall time of one call (stream drained on both
 sides of `reps` back-to-back calls), its ALGORITHMIC bytes (SURVEY.md §8a "B_alg": inputs read once + outputs written
@@ -232,6 +232,44 @@ def main() -> None:
              dt_seal, 4 * sum(int(x) for x in desc[3:6]) * n)
         print(json.dumps({"bench": "M10share", "accumulate_ms": round(dt_acc * 1e3, 3), "seal_ms": round(dt_seal * 1e3, 3),
                           "share": round(dt_acc / dt_seal, 4)}), flush=True)
+    if want("M11"):
+        # derived multiplicities (zkh_derive_multiplicities): SYN-LOOKUP-derived (64 byte-limb lookup columns into a 256-entry table, the
+        # LDS count) and WIDE (M11w: a 2^16-entry table, the global count), against the host's bincount of the same limbs
+        from zeth_amd.circuits import logup, syn_lookup
+        from zeth_amd.prover import Segment, SegmentProver
+        A = n - 1994
+        for tag, shape in (("M11", syn_lookup.FULL), ("M11w", syn_lookup.WIDE)):
+            desc, blob = syn_lookup.build_syn_lookup(shape, derive=True)
+            a = logup.Arguments.parse(blob)
+            circuit = hal.load_circuit(desc, jit=False)
+            circuit.set_arguments(blob)
+            code_h, data_h, _ = syn_lookup.witness(shape, args.po2, 1994, seed=11, count=False)
+            code, data = hal.alloc_elem("code", code_h.size), hal.alloc_elem("data", data_h.size)
+            code.write(code_h)
+            data.write(data_h)
+            dt = timed(hal, lambda: hal.derive_multiplicities(circuit, args.po2, 1994, code, data), args.reps)
+            _words, limbs, _m, _mem, _perm = syn_lookup.layout(shape.n_words, shape.n_limbs, shape.n_mem)
+            lk = [c for row in limbs for c in row]
+            T = 1 << shape.limb_bits
+            host = data_h.reshape(-1, n)
+            vals = [logup._dec(host[c, :A]).astype(np.int64) for c in lk]
+            t0 = time.perf_counter()
+            counts = np.zeros(T, np.int64)
+            for v in vals:
+                counts += np.bincount(v, minlength=T)
+            dt_host = time.perf_counter() - t0
+            # lookup columns and the table's selector + values once, the m column written once
+            line(tag, f"derive multiplicities ({len(lk)} lookup columns into a {T}-entry table)", f"{len(lk)} x {A} lookups -> 2^{args.po2}",
+                 dt, 4 * len(lk) * A + 3 * 4 * A)
+            rec = {"bench": tag + "host", "host_bincount_ms": round(dt_host * 1e3, 3), "device_ms": round(dt * 1e3, 4)}
+            if tag == "M11":
+                prover = SegmentProver(hal, desc, arguments=blob)
+                seg = Segment(index=0, po2=args.po2, noise_seed=0x2E80)
+                out = np.zeros(4, np.uint32)
+                seal = lambda: prover.seal_with_accum(seg, code, data, out, prover.args_accumulate(seg, code, data))
+                dt_seal = timed(hal, seal, args.reps)
+                rec.update(seal_ms=round(dt_seal * 1e3, 3), share=round(dt / dt_seal, 4))
+            print(json.dumps(rec), flush=True)
     hal.close()
 
 

@@ -24,11 +24,18 @@ The degree of a column's constraint is 1 (gate) + max(1 + t, max_i(deg sel_i + d
 
 ZKA1 layout (u32 words; canonical integers, not Montgomery words)::
 
-    [0] magic 'ZKA1' = 0x5a4b4131   [1] version = 1   [2] k = accum Fp4 columns   [3] alpha mix word offset
+    [0] magic 'ZKA1' = 0x5a4b4131   [1] version = 1 or 2   [2] k = accum Fp4 columns   [3] alpha mix word offset
     [4] beta mix word offset       [5] n_terms       [6..8) reserved = 0
     terms: n_terms x 16 words, sorted by column:
       col, neg (0: +1, 1: -1), sel (code column or NONE), m_group (NONE = constant 1, else GROUP_CODE / GROUP_DATA), m_col,
-      tag, w, 0, then w (group, column) pairs of the tuple, unused pairs 0
+      tag, w, flags, then w (group, column) pairs of the tuple, unused pairs 0
+    flags (word 7): version 1 writes 0 and reads nothing; version 2: bit 0 = the multiplicity is DERIVED by the library
+    (zkh_derive_multiplicities), any other bit is refused.  The builder writes version 2 only when a term is derived.
+
+A derived term is the table side of a lookup (`check_derived`): sign -1, its multiplicity a data column that no tuple and no other
+term names, and every other term of its tag a lookup of sign +1.  Its multiplicity column is then a function of the traces:
+on each table key's representative (the entry of smallest (blob term index, row)) the number of lookups of that key, 0 on the
+other active rows (`reference_multiplicities`; DESIGN.md §2 ARGUMENTS).
 """
 from __future__ import annotations
 
@@ -56,10 +63,31 @@ class Term:
     sel: Optional[int] = None                  # code column, or None = 1
     mult: Optional[Tuple[int, int]] = None     # (group, column), or None = 1
     tag: int = 0
+    derive: bool = False                       # the multiplicity is derived by the library (ZKA1 version 2)
 
     def degree(self, n_terms: int) -> int:
         """degree of the numerator summand sign * sel * m * prod_{l != i} d_l"""
         return (self.sel is not None) + (self.mult is not None) + n_terms - 1
+
+
+def check_derived(terms: Sequence[Term]) -> Optional[str]:
+    """the first derived term that breaks a rule, named by its index in `terms`, or None: (a) sign -1, (b) a data-group multiplicity,
+    (c) that column named by no tuple and no other term's multiplicity, (d) every other term of its tag of sign +1 or derived"""
+    for i, t in enumerate(terms):
+        if not t.derive:
+            continue
+        if t.sign != -1:
+            return f"term {i}: a derived multiplicity needs sign -1 (the table side of a lookup)"
+        if t.mult is None or t.mult[0] != GROUP_DATA:
+            return f"term {i}: a derived multiplicity must be a data-group column"
+        for j, u in enumerate(terms):
+            if j != i and u.mult == t.mult:
+                return f"term {i}: its derived multiplicity column (data {t.mult[1]}) is also the multiplicity of term {j}"
+            if t.mult in u.tuple_cols:
+                return f"term {i}: its derived multiplicity column (data {t.mult[1]}) is read by the tuple of term {j}"
+            if u.tag % P == t.tag % P and not u.derive and u.sign != 1:
+                return f"term {i}: term {j} of its tag {t.tag % P} has sign -1 and is not derived (the lookups of a derived tag have sign +1)"
+    return None
 
 
 def column_degree(terms: Sequence[Term]) -> int:
@@ -76,11 +104,15 @@ class Arguments:
     beta: int
     terms: List[Term]
 
+    @property
+    def version(self) -> int:
+        return 2 if any(t.derive for t in self.terms) else 1
+
     def blob(self) -> np.ndarray:
-        words = [ARGS_MAGIC, 1, self.k, self.alpha, self.beta, len(self.terms), 0, 0]
+        words = [ARGS_MAGIC, self.version, self.k, self.alpha, self.beta, len(self.terms), 0, 0]
         for t in sorted(self.terms, key=lambda x: x.col):
             rec = [t.col, 0 if t.sign == 1 else 1, NONE if t.sel is None else t.sel,
-                   NONE if t.mult is None else t.mult[0], 0 if t.mult is None else t.mult[1], t.tag % P, len(t.tuple_cols), 0]
+                   NONE if t.mult is None else t.mult[0], 0 if t.mult is None else t.mult[1], t.tag % P, len(t.tuple_cols), int(t.derive)]
             for g, c in t.tuple_cols:
                 rec += [g, c]
             rec += [0] * (TERM_WORDS - len(rec))
@@ -90,8 +122,9 @@ class Arguments:
     @staticmethod
     def parse(blob: Sequence[int]) -> "Arguments":
         d = [int(x) for x in np.asarray(blob, dtype=np.uint32)]
-        if len(d) < ARGS_HEADER or d[0] != ARGS_MAGIC or d[1] != 1:
+        if len(d) < ARGS_HEADER or d[0] != ARGS_MAGIC or d[1] not in (1, 2):
             raise ValueError("not a ZKA1 argument blob")
+        version = d[1]
         k, alpha, beta, n = d[2], d[3], d[4], d[5]
         if len(d) != ARGS_HEADER + TERM_WORDS * n:
             raise ValueError(f"ZKA1: {len(d)} words for {n} terms")
@@ -101,8 +134,14 @@ class Arguments:
             w = r[6]
             if not 1 <= w <= MAX_TUPLE:
                 raise ValueError(f"ZKA1 term {i}: tuple width {w}")
+            if version == 2 and r[7] > 1:
+                raise ValueError(f"ZKA1 term {i}: word 7 is {r[7]} (bit 0: derived multiplicity; the other bits are reserved)")
             terms.append(Term(col=r[0], tuple_cols=tuple((r[8 + 2 * j], r[9 + 2 * j]) for j in range(w)), sign=-1 if r[1] else 1,
-                              sel=None if r[2] == NONE else r[2], mult=None if r[3] == NONE else (r[3], r[4]), tag=r[5]))
+                              sel=None if r[2] == NONE else r[2], mult=None if r[3] == NONE else (r[3], r[4]), tag=r[5],
+                              derive=version == 2 and r[7] == 1))
+        problem = check_derived(terms)
+        if problem:
+            raise ValueError(f"ZKA1: {problem}")
         return Arguments(k, alpha, beta, terms)
 
     def by_column(self) -> List[List[Term]]:
@@ -130,7 +169,8 @@ class LogupBuilder(CircuitBuilder):
         return self.group_sizes[GROUP_ACCUM] // 4
 
     def term(self, col: int, tuple_cols: Sequence[Tuple[int, int]], sign: int = 1, sel: Optional[int] = None,
-             mult: Optional[Tuple[int, int]] = None, tag: int = 0) -> Term:
+             mult: Optional[Tuple[int, int]] = None, tag: int = 0, derive: bool = False) -> Term:
+        """derive: the library fills `mult` (zkh_derive_multiplicities), the table side of a lookup (`check_derived`)"""
         if not 0 <= col < self.k:
             raise ValueError(f"accum column {col} outside 0..{self.k - 1}")
         if sign not in (1, -1):
@@ -142,8 +182,12 @@ class LogupBuilder(CircuitBuilder):
                 raise ValueError(f"column ({g}, {c}) is not a code or data column of this circuit")
         if sel is not None and not 0 <= sel < self.group_sizes[GROUP_CODE]:
             raise ValueError(f"selector {sel} is not a code column")
-        t = Term(col, tuple((int(g), int(c)) for g, c in tuple_cols), sign, sel, mult, int(tag))
+        t = Term(col, tuple((int(g), int(c)) for g, c in tuple_cols), sign, sel, mult, int(tag), bool(derive))
         self.terms.append(t)
+        problem = check_derived(self.terms)
+        if problem:
+            self.terms.pop()
+            raise ValueError(problem)
         deg = column_degree([x for x in self.terms if x.col == col])
         if deg > MAX_DEGREE:
             self.terms.pop()
@@ -356,3 +400,74 @@ def reference_accumulate(args: Arguments, po2: int, zk_cycles: int, code, data, 
     if check_balance and any(total):
         raise ReferenceError(f"the bus does not balance: total {total}")
     return accum.reshape(-1), total
+
+
+def _canonical_key(terms: Sequence[Term], groups, i: int, rows) -> np.ndarray:
+    """(len(rows), 5) keys (tag, v_0 .. v_3) of term i, canonical, the tuple zero-padded"""
+    t = terms[i]
+    key = np.zeros((len(rows), 1 + MAX_TUPLE), dtype=np.uint64)
+    key[:, 0] = t.tag % P
+    for j, (g, c) in enumerate(t.tuple_cols):
+        key[:, 1 + j] = _dec(groups[g][c, rows])
+    return key
+
+
+def reference_multiplicities(args: Arguments, po2: int, zk_cycles: int, code, data) -> np.ndarray:
+    """The data trace zkh_derive_multiplicities leaves (raw Montgomery words, a copy): for each derived term D and active row r,
+    data[m_D][r] = the number of lookups (sum of sel * m in Fp) of the key of (D, r) if (D, r) is that key's representative (the table
+    entry of smallest (blob term index, row)), else 0; rows [A, n) as given.  Raises ReferenceError on a table selector other than 0 / 1
+    or on a lookup of nonzero weight whose key has no table entry."""
+    n = 1 << po2
+    A = n - zk_cycles
+    terms = Arguments.parse(args.blob()).terms                               # blob order: the term index of the representative rule
+    groups = {GROUP_CODE: np.asarray(code, dtype=np.uint32).reshape(-1, n), GROUP_DATA: np.array(data, dtype=np.uint32).reshape(-1, n)}
+    out = groups[GROUP_DATA]
+    rows = np.arange(A)
+    tags = sorted({t.tag % P for t in terms if t.derive})
+    for tag in tags:
+        derived = [i for i, t in enumerate(terms) if t.derive and t.tag % P == tag]
+        lookups = [i for i, t in enumerate(terms) if not t.derive and t.tag % P == tag]
+        keys, owner = [], []
+        for i in derived:
+            t = terms[i]
+            sel = np.ones(A, dtype=np.uint64) if t.sel is None else _dec(groups[GROUP_CODE][t.sel, :A])
+            bad = (sel != 0) & (sel != 1)
+            if bad.any():
+                r = int(np.argmax(bad))
+                raise ReferenceError(f"table term {i} (tag {tag}) has selector {int(sel[r])} at row {r}, not 0 or 1")
+            on = rows[sel == 1]
+            keys.append(_canonical_key(terms, groups, i, on))
+            owner.append(np.stack([np.full(on.size, i), on], axis=1))
+        tk, to = np.concatenate(keys), np.concatenate(owner)
+        # sort by (key, term, row): the first entry of every distinct key is its representative
+        order = np.lexsort(tuple(to[:, ::-1].T) + tuple(tk[:, ::-1].T))
+        tk, to = tk[order], to[order]
+        first = np.ones(len(tk), dtype=bool)
+        first[1:] = (tk[1:] != tk[:-1]).any(axis=1)
+        uk, uo = tk[first], to[first]
+        counts = np.zeros(len(uk), dtype=np.uint64)
+        for i in lookups:
+            t = terms[i]
+            w = np.ones(A, dtype=np.uint64)
+            if t.sel is not None:
+                w = _m(w, _dec(groups[GROUP_CODE][t.sel, :A]))
+            if t.mult is not None:
+                w = _m(w, _dec(groups[t.mult[0]][t.mult[1], :A]))
+            live = rows[w != 0]
+            lk = _canonical_key(terms, groups, i, live)
+            allk = np.concatenate([uk, lk])
+            _, inv = np.unique(allk, axis=0, return_inverse=True)
+            inv = inv.reshape(-1)
+            slot = np.full(inv.max() + 1, -1, dtype=np.int64)
+            slot[inv[:len(uk)]] = np.arange(len(uk))
+            hit = slot[inv[len(uk):]]
+            if (hit < 0).any():
+                j = int(np.argmax(hit < 0))
+                v = [int(x) for x in lk[j, 1:]]
+                raise ReferenceError(f"lookup term {i} (tag {tag}) at row {int(live[j])} has no table entry: key ({v[0]}, {v[1]}, {v[2]}, {v[3]})")
+            np.add.at(counts, hit, w[live])
+        for i in derived:
+            out[terms[i].mult[1], :A] = 0
+        mcol = np.array([terms[i].mult[1] for i in uo[:, 0]], dtype=np.int64)
+        out[mcol, uo[:, 1]] = _enc(counts % np.uint64(P)).astype(np.uint32)
+    return out.reshape(-1)

@@ -14,6 +14,9 @@ Argument terms (one bus):
   tag 1 — every memory tuple +1 (addr, val, time), its permuted copy -1
 Globals: out = 4 zero words; mix = alpha (words 0..3), beta (4..7).
 The witness comes from the host (`witness`, numpy): the upstream flow of a CPU preflight + witgen uploaded as caller traces.
+SYN-LOOKUP-derived (`syn_lookup_derived`, `build_syn_lookup(shape, derive=True)`): the same description word for word (the same
+control root), the table term marked derived in a ZKA1 version-2 blob, so the library counts m (zkh_derive_multiplicities) and
+the witness may leave it zero (`witness(count=False)`).
 Not a shipped circuit: its control root is zkh_code_root of its code trace.
 """
 from __future__ import annotations
@@ -48,10 +51,12 @@ class Shape(NamedTuple):
 
 TINY = Shape(2, 4, 4, 1)            # 11 terms in 4 accum columns (po2 8..12)
 FULL = Shape(16, 4, 8, 1)           # 67 terms in 23 accum columns, 87 data columns (sealed at po2 20)
+WIDE = Shape(2, 2, 16, 1)           # a 2^16-row table (po2 >= 17): 7 terms in 3 accum columns
 
 
-def build_syn_lookup(shape: Shape = FULL) -> Tuple[np.ndarray, np.ndarray]:
-    """-> (ZKC1 description, ZKA1 argument blob)"""
+def build_syn_lookup(shape: Shape = FULL, derive: bool = False) -> Tuple[np.ndarray, np.ndarray]:
+    """-> (ZKC1 description, ZKA1 argument blob); derive: the table term's multiplicity is derived by the library (version-2 blob,
+    the description unchanged)"""
     n_words, n_limbs, limb_bits, n_mem = shape
     words, limbs, m, mem, perm = layout(n_words, n_limbs, n_mem)
     wd = m + 1 + 2 * MEM_W * n_mem
@@ -64,7 +69,7 @@ def build_syn_lookup(shape: Shape = FULL) -> Tuple[np.ndarray, np.ndarray]:
     active, first, body, _rowidx, last = (code(i) for i in range(5))
     # the terms, three per column in this order: limbs, the table, the memory pair
     specs = [dict(tuple_cols=[(GROUP_DATA, c)], tag=0) for row in limbs for c in row]
-    specs.append(dict(tuple_cols=[(GROUP_CODE, 6)], sign=-1, sel=5, mult=(GROUP_DATA, m), tag=0))
+    specs.append(dict(tuple_cols=[(GROUP_CODE, 6)], sign=-1, sel=5, mult=(GROUP_DATA, m), tag=0, derive=derive))
     for i in range(n_mem):
         specs.append(dict(tuple_cols=[(GROUP_DATA, c) for c in mem[i]], sign=1, tag=1))
         specs.append(dict(tuple_cols=[(GROUP_DATA, c) for c in perm[i]], sign=-1, tag=1))
@@ -94,14 +99,22 @@ def syn_lookup() -> Tuple[np.ndarray, np.ndarray]:
     return build_syn_lookup(FULL)
 
 
+def syn_lookup_tiny_derived() -> Tuple[np.ndarray, np.ndarray]:
+    return build_syn_lookup(TINY, derive=True)
+
+
+def syn_lookup_derived() -> Tuple[np.ndarray, np.ndarray]:
+    return build_syn_lookup(FULL, derive=True)
+
+
 def _enc(x) -> np.ndarray:
     return ((np.asarray(x, dtype=np.uint64) % np.uint64(P)) * np.uint64((1 << 32) % P) % np.uint64(P)).astype(np.uint32)
 
 
-def witness(shape: Shape, po2: int, zk_cycles: int, seed: int = 1):
+def witness(shape: Shape, po2: int, zk_cycles: int, seed: int = 1, count: bool = True):
     """-> (code, data, out_global) host arrays of raw Montgomery words: random words below min(P, 2^(n_limbs L)) split into limbs,
-    the table's multiplicities, random memory tuples and their copy sorted by (addr, time); blinding rows of data from the same
-    seeded generator"""
+    the table's multiplicities (count=False: zero, for the library to derive), random memory tuples and their copy sorted by
+    (addr, time); blinding rows of data from the same seeded generator"""
     n_words, n_limbs, limb_bits, n_mem = shape
     words, limbs, m_col, mem, perm = layout(n_words, n_limbs, n_mem)
     wd = m_col + 1 + 2 * MEM_W * n_mem
@@ -129,7 +142,8 @@ def witness(shape: Shape, po2: int, zk_cycles: int, seed: int = 1):
             limb = (w >> np.uint64(j * limb_bits)) & np.uint64(T - 1)
             data[limbs[kk][j], :A] = limb
             counts += np.bincount(limb.astype(np.int64), minlength=T)
-    data[m_col, :T] = counts.astype(np.uint64)
+    if count:
+        data[m_col, :T] = counts.astype(np.uint64)
     for i in range(n_mem):
         addr = rng.integers(0, 1 << 20, size=A, dtype=np.uint64)
         val = rng.integers(0, P, size=A, dtype=np.uint64)

@@ -606,6 +606,8 @@ static const char* seal_one(zkh_session* s, Lane& l, const zkh_segment& seg, uin
         ZKH_REQUIRE(seg.host_code && seg.host_data && seg.out_global, "session: a segment with host traces needs host_code, host_data and out_global");
         ZKH_TRY(zkh_write(l.ctx, code, seg.host_code, 0, code->len));
         ZKH_TRY(zkh_write(l.ctx, data, seg.host_data, 0, data->len));
+        // derived lookup multiplicities belong to the data group: filled before it is committed, callback or not
+        if (zkh_circuit_derives_multiplicities(cir)) ZKH_TRY(zkh_derive_multiplicities(l.ctx, cir, seg.po2, ZKH_ZK_CYCLES, code, data));
         out_global.assign(seg.out_global, seg.out_global + out_global.size());
         *witgen_s = now_s() - t0;
         zkh_seal_job* job = nullptr;
