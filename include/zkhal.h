@@ -235,6 +235,20 @@ const char* zkh_accumulate(zkh_ctx*, const zkh_circuit*, size_t po2, size_t zk_c
  * to the data group.  Sessions with caller traces and SegmentProver.seal_host_witness do so when the circuit derives. */
 int zkh_circuit_derives_multiplicities(const zkh_circuit*);
 const char* zkh_derive_multiplicities(zkh_ctx*, const zkh_circuit*, size_t po2, size_t zk_cycles, const zkh_buf* code, zkh_buf* data);
+/* Derived sorted copies (ZKA1 version 3: term word 7 bit 1 marks a term D as the sorted copy of its source term S; bits 4..6 = nkeys
+ * (1..3), bits 8 + 2j, 9 + 2j = the tuple position of sort key j, most significant key first; bits 16..31 = the blob index of S; bits
+ * 2, 3, 7 and the positions of unused keys are reserved and refused).  D is the permuted side of a multiset equality: sign -1 against
+ * S's +1, the same tag, tuple width and selector, constant multiplicities, its tuple columns pairwise distinct data columns that nothing
+ * else in the blob names, no derived multiplicity in its tag.  With r_0 < ... < r_{m-1} the active rows (r < 2^po2 - zk_cycles) whose
+ * selector is 1 (no selector: all) and pi the STABLE permutation that sorts them by the canonical values of S's key columns
+ * (lexicographic, equal keys keep their row order), zkh_derive_sorted writes data[D.v_e][r_j] = the raw word of S.v_e at r_pi(j) for
+ * every tuple position e, 0 on the active rows whose selector is 0; the blinding rows are not touched.  The result depends on the
+ * traces alone (no atomic arrival order enters it).  It FAILS and leaves `data` unchanged when a selector is neither 0 nor 1 (the
+ * error names the term and the row).  Call it after the data upload, BEFORE zkh_derive_multiplicities (a lookup may range-check a
+ * sorted column) and before zkh_prove_begin.  Sessions with caller traces and SegmentProver.seal_host_witness do so when the circuit
+ * derives sorted copies. */
+int zkh_circuit_derives_sorted(const zkh_circuit*);
+const char* zkh_derive_sorted(zkh_ctx*, const zkh_circuit*, size_t po2, size_t zk_cycles, const zkh_buf* code, zkh_buf* data);
 
 /* ---- built-in witness generators on the device, by circuit kind (desc word 13) ----
  *   kind 1 SYN-AIR   stands in for risc0-circuit-rv32im's witgen (declared synthetic)

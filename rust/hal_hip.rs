@@ -329,6 +329,20 @@ impl HipCircuitHal {
         let po2 = steps.trailing_zeros() as usize;
         ffi(|| unsafe { sys::zkh_derive_multiplicities(self.hal.ctx.0, self.circuit, po2, sys::ZK_CYCLES, ctrl.raw, data.raw) });
     }
+
+    /// The arguments (a ZKA1 version-3 blob) mark a term as a sorted copy derived by the library.
+    pub fn derives_sorted(&self) -> bool {
+        unsafe { sys::zkh_circuit_derives_sorted(self.circuit) != 0 }
+    }
+
+    /// Fill the tuple columns of the derived sorted copies of `data` on the active rows from the raw code (ctrl) and data traces
+    /// (`zkh_derive_sorted`): each source tuple's selected rows, stably sorted by its key columns.  Call it before
+    /// `derive_multiplicities` and before the data group is committed (`prove_begin`).  Panics on a refused witness (a selector other
+    /// than 0 / 1), which leaves `data` unchanged, like every failed HAL op.
+    pub fn derive_sorted(&self, ctrl: &HipBuffer<BabyBearElem>, data: &HipBuffer<BabyBearElem>, steps: usize) {
+        let po2 = steps.trailing_zeros() as usize;
+        ffi(|| unsafe { sys::zkh_derive_sorted(self.hal.ctx.0, self.circuit, po2, sys::ZK_CYCLES, ctrl.raw, data.raw) });
+    }
 }
 
 impl Drop for HipCircuitHal {

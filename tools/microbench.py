@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Per-op micro-benchmarks M1..M8 of SURVEY.md §8d (+ M9: the trace-driven witness, row f1; M10: the built-in accumulate of SYN-LOOKUP's
-arguments and its share of that circuit's seal; M11 / M11w: derived lookup multiplicities of SYN-LOOKUP-derived / WIDE) on one MI355X, through the C ABI (HipHal).
+arguments and its share of that circuit's seal; M11 / M11w: derived lookup multiplicities of SYN-LOOKUP-derived / WIDE; M12: derived sorted copies of SYN-LOOKUP-sorted
+against the host's lexsort + upload) on one MI355X, through the C ABI (HipHal).
 
 Each line of output is one JSON object: the op, its shape, the average wall time of one call (stream drained on both
 sides of `reps` back-to-back calls), its ALGORITHMIC bytes (SURVEY.md §8a "B_alg": inputs read once + outputs written
@@ -270,6 +271,50 @@ def main() -> None:
                 dt_seal = timed(hal, seal, args.reps)
                 rec.update(seal_ms=round(dt_seal * 1e3, 3), share=round(dt / dt_seal, 4))
             print(json.dumps(rec), flush=True)
+    if want("M12"):
+        # derived sorted copies (zkh_derive_sorted) of SYN-LOOKUP-sorted: the (addr, val, time) tuple sorted by (addr, time) on the device,
+        # per step (ProfScope events) and in total, next to the seal it precedes and to what it replaces on the host: np.lexsort over the
+        # decoded keys, the gather of the three columns and their upload
+        from zeth_amd.circuits import logup, syn_lookup
+        from zeth_amd.prover import Segment, SegmentProver
+        A = n - 1994
+        shape = syn_lookup.FULL
+        desc, blob = syn_lookup.build_syn_lookup(shape, sort=True)
+        circuit = hal.load_circuit(desc, jit=False)
+        circuit.set_arguments(blob)
+        code_h, data_h, _ = syn_lookup.witness(shape, args.po2, 1994, seed=12, sort=False)
+        code, data = hal.alloc_elem("code", code_h.size), hal.alloc_elem("data", data_h.size)
+        code.write(code_h)
+        data.write(data_h)
+        derive = lambda: hal.derive_sorted(circuit, args.po2, 1994, code, data)
+        dt = timed(hal, derive, args.reps)
+        # key columns read twice (live bits, pack), 12 B of (key, row) per item, the three columns gathered and written
+        line("M12", "derive sorted copies (SYN-LOOKUP-sorted: (addr, val, time) by (addr, time))", f"{shape.n_mem} x {A} rows -> 2^{args.po2}",
+             dt, shape.n_mem * A * (4 * 2 * 2 + 12 + 4 * 2 * 3))
+        hal.prof_enable(True)
+        hal.prof_reset()
+        for _ in range(args.reps):
+            derive()
+        hal.sync()
+        steps = {r["name"]: round(r["total_ms"] / max(r["calls"], 1), 4) for r in hal.prof_get() if r["calls"] and r["name"].startswith("sort_")}
+        hal.prof_enable(False)
+        _words, _limbs, _m, mem, perm = syn_lookup.layout(shape.n_words, shape.n_limbs, shape.n_mem)
+        host = data_h.reshape(-1, n)
+        t0 = time.perf_counter()
+        addr, tm = logup._dec(host[mem[0][0], :A]), logup._dec(host[mem[0][2], :A])
+        order = np.lexsort((tm, addr))
+        cols = np.ascontiguousarray(host[mem[0], :A][:, order])
+        dt_sort = time.perf_counter() - t0
+        up = hal.alloc_elem("perm", cols.size)
+        dt_up = timed(hal, lambda: up.write(cols.reshape(-1)), args.reps)
+        prover = SegmentProver(hal, desc, arguments=blob)
+        seg = Segment(index=0, po2=args.po2, noise_seed=0x2E80)
+        out = np.zeros(4, np.uint32)
+        seal = lambda: prover.seal_with_accum(seg, code, data, out, prover.args_accumulate(seg, code, data))
+        dt_seal = timed(hal, seal, args.reps)
+        print(json.dumps({"bench": "M12share", "derive_sorted_ms": round(dt * 1e3, 4), "steps_ms": steps, "seal_ms": round(dt_seal * 1e3, 3),
+                          "share": round(dt / dt_seal, 4), "host_lexsort_ms": round(dt_sort * 1e3, 2), "host_upload_ms": round(dt_up * 1e3, 3)}),
+              flush=True)
     hal.close()
 
 

@@ -24,22 +24,31 @@ The degree of a column's constraint is 1 (gate) + max(1 + t, max_i(deg sel_i + d
 
 ZKA1 layout (u32 words; canonical integers, not Montgomery words)::
 
-    [0] magic 'ZKA1' = 0x5a4b4131   [1] version = 1 or 2   [2] k = accum Fp4 columns   [3] alpha mix word offset
+    [0] magic 'ZKA1' = 0x5a4b4131   [1] version = 1, 2 or 3   [2] k = accum Fp4 columns   [3] alpha mix word offset
     [4] beta mix word offset       [5] n_terms       [6..8) reserved = 0
     terms: n_terms x 16 words, sorted by column:
       col, neg (0: +1, 1: -1), sel (code column or NONE), m_group (NONE = constant 1, else GROUP_CODE / GROUP_DATA), m_col,
       tag, w, flags, then w (group, column) pairs of the tuple, unused pairs 0
     flags (word 7): version 1 writes 0 and reads nothing; version 2: bit 0 = the multiplicity is DERIVED by the library
     (zkh_derive_multiplicities), any other bit is refused.  The builder writes version 2 only when a term is derived.
+    Version 3: bit 0 as in version 2; bit 1 = this term D is a DERIVED SORTED COPY (zkh_derive_sorted) of its source term S, and then
+    bits 4..6 = nkeys (1..min(w, 3)), bits 8 + 2j, 9 + 2j = the tuple position of sort key j (most significant key first),
+    bits 16..31 = the blob index of S.  Without bit 1 everything above bit 0 is zero; bits 2, 3, 7 and the position fields of unused
+    keys are reserved and refused.  The builder writes version 3 only when a term is a sorted copy.
 
 A derived term is the table side of a lookup (`check_derived`): sign -1, its multiplicity a data column that no tuple and no other
 term names, and every other term of its tag a lookup of sign +1.  Its multiplicity column is then a function of the traces:
 on each table key's representative (the entry of smallest (blob term index, row)) the number of lookups of that key, 0 on the
 other active rows (`reference_multiplicities`; DESIGN.md §2 ARGUMENTS).
+
+A sorted copy D of S is the permuted side of a multiset equality (`check_sorted`): sign -1 against S's +1, the same tag, width and
+selector, constant multiplicities, and tuple columns that are data columns nothing else in the blob names.  Those columns are then
+a function of the traces: S's selected active rows, stably sorted by the canonical values of the key positions, written onto the
+same selected rows (`reference_sorted`).
 """
 from __future__ import annotations
 
-from dataclasses import dataclass
+from dataclasses import dataclass, replace
 from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -64,6 +73,17 @@ class Term:
     mult: Optional[Tuple[int, int]] = None     # (group, column), or None = 1
     tag: int = 0
     derive: bool = False                       # the multiplicity is derived by the library (ZKA1 version 2)
+    sorted_from: Optional[int] = None          # this term is the sorted copy of that term (its index in the same list; version 3)
+    sort_keys: Tuple[int, ...] = ()            # tuple positions of the sort keys, most significant first
+
+    def flags(self) -> int:
+        """word 7 of the term's record"""
+        f = int(self.derive)
+        if self.sorted_from is not None:
+            f |= 2 | len(self.sort_keys) << 4 | self.sorted_from << 16
+            for j, pos in enumerate(self.sort_keys):
+                f |= pos << (8 + 2 * j)
+        return f
 
     def degree(self, n_terms: int) -> int:
         """degree of the numerator summand sign * sel * m * prod_{l != i} d_l"""
@@ -90,6 +110,67 @@ def check_derived(terms: Sequence[Term]) -> Optional[str]:
     return None
 
 
+MAX_SORT_KEYS = 3
+
+
+def check_sorted(terms: Sequence[Term]) -> Optional[str]:
+    """the first sorted-copy term D that breaks a rule, named by its index in `terms`, or None.  With S its source: (a) D has sign -1
+    and no derived multiplicity, S is another term of sign +1 without a flag and the source of no other copy; (b) the same tag, tuple
+    width and selector, both multiplicities the constant 1; (c) D's tuple columns are pairwise distinct data columns that no other
+    tuple and no multiplicity names; (d) 1..3 key positions, distinct and below the width; (e) no derived multiplicity in D's tag"""
+    for i, t in enumerate(terms):
+        if t.sorted_from is None:
+            continue
+        s, w = t.sorted_from, len(t.tuple_cols)
+        if t.sign != -1:
+            return f"term {i}: a sorted copy needs sign -1 (the permuted side of a multiset equality)"
+        if t.derive:
+            return f"term {i}: a sorted copy cannot also have a derived multiplicity"
+        if s == i or not 0 <= s < len(terms):
+            return f"term {i}: its source term {s} is not another term of the arguments"
+        u = terms[s]
+        if u.sign != 1:
+            return f"term {i}: its source term {s} needs sign +1"
+        if u.derive or u.sorted_from is not None:
+            return f"term {i}: its source term {s} is itself derived or a sorted copy"
+        for j, x in enumerate(terms):
+            if j != i and x.sorted_from == s:
+                return f"term {i}: its source term {s} is also the source of term {j}"
+        if u.tag % P != t.tag % P or len(u.tuple_cols) != w or u.sel != t.sel:
+            return f"term {i}: its source term {s} has another tag, tuple width or selector"
+        if t.mult is not None or u.mult is not None:
+            return f"term {i}: a sorted copy and its source term {s} have the constant multiplicity 1"
+        for e, (g, c) in enumerate(t.tuple_cols):
+            if g != GROUP_DATA:
+                return f"term {i}: tuple column ({g}, {c}) of a sorted copy must be a data-group column"
+            if (g, c) in t.tuple_cols[:e]:
+                return f"term {i}: its sorted column (data {c}) appears twice in its tuple"
+            for j, x in enumerate(terms):
+                if j != i and (g, c) in x.tuple_cols:
+                    return f"term {i}: its sorted column (data {c}) is read by the tuple of term {j}"
+                if x.mult == (g, c):
+                    return f"term {i}: its sorted column (data {c}) is the multiplicity of term {j}"
+        k = t.sort_keys
+        if not 1 <= len(k) <= min(w, MAX_SORT_KEYS):
+            return f"term {i}: {len(k)} sort keys (1..{min(w, MAX_SORT_KEYS)}: at most {MAX_SORT_KEYS}, and no more than the tuple width {w})"
+        if len(set(k)) != len(k) or any(not 0 <= pos < w for pos in k):
+            return f"term {i}: its sort key positions must be distinct and below the tuple width {w}"
+        for j, x in enumerate(terms):
+            if x.derive and x.tag % P == t.tag % P:
+                return f"term {i}: term {j} of its tag {t.tag % P} has a derived multiplicity"
+    return None
+
+
+def _by_column(terms: Sequence[Term]) -> List[Term]:
+    """the terms sorted by accum column (stable: the blob order), the source indices of sorted copies following their terms"""
+    order = sorted(range(len(terms)), key=lambda i: terms[i].col)
+    if order == list(range(len(terms))):
+        return list(terms)
+    new = {old: pos for pos, old in enumerate(order)}
+    return [terms[i] if terms[i].sorted_from is None else replace(terms[i], sorted_from=new.get(terms[i].sorted_from, terms[i].sorted_from))
+            for i in order]
+
+
 def column_degree(terms: Sequence[Term]) -> int:
     """degree of the first / body constraint of a column with these terms (the gate included)"""
     t = len(terms)
@@ -106,13 +187,15 @@ class Arguments:
 
     @property
     def version(self) -> int:
+        if any(t.sorted_from is not None for t in self.terms):
+            return 3
         return 2 if any(t.derive for t in self.terms) else 1
 
     def blob(self) -> np.ndarray:
         words = [ARGS_MAGIC, self.version, self.k, self.alpha, self.beta, len(self.terms), 0, 0]
-        for t in sorted(self.terms, key=lambda x: x.col):
+        for t in _by_column(self.terms):
             rec = [t.col, 0 if t.sign == 1 else 1, NONE if t.sel is None else t.sel,
-                   NONE if t.mult is None else t.mult[0], 0 if t.mult is None else t.mult[1], t.tag % P, len(t.tuple_cols), int(t.derive)]
+                   NONE if t.mult is None else t.mult[0], 0 if t.mult is None else t.mult[1], t.tag % P, len(t.tuple_cols), t.flags()]
             for g, c in t.tuple_cols:
                 rec += [g, c]
             rec += [0] * (TERM_WORDS - len(rec))
@@ -122,7 +205,7 @@ class Arguments:
     @staticmethod
     def parse(blob: Sequence[int]) -> "Arguments":
         d = [int(x) for x in np.asarray(blob, dtype=np.uint32)]
-        if len(d) < ARGS_HEADER or d[0] != ARGS_MAGIC or d[1] not in (1, 2):
+        if len(d) < ARGS_HEADER or d[0] != ARGS_MAGIC or d[1] not in (1, 2, 3):
             raise ValueError("not a ZKA1 argument blob")
         version = d[1]
         k, alpha, beta, n = d[2], d[3], d[4], d[5]
@@ -136,10 +219,19 @@ class Arguments:
                 raise ValueError(f"ZKA1 term {i}: tuple width {w}")
             if version == 2 and r[7] > 1:
                 raise ValueError(f"ZKA1 term {i}: word 7 is {r[7]} (bit 0: derived multiplicity; the other bits are reserved)")
+            src, keys = None, ()
+            if version == 3:
+                f = r[7]
+                nkeys = f >> 4 & 7
+                if f & 0x8C or (not f & 2 and f > 1) or any(f >> (8 + 2 * j) & 3 for j in range(nkeys, 4)):
+                    raise ValueError(f"ZKA1 term {i}: word 7 is {f:#x} (bit 0: derived multiplicity; bit 1: sorted copy, with its keys in "
+                                     f"bits 4..15 and its source term in bits 16..31; the other bits are reserved)")
+                if f & 2:
+                    src, keys = f >> 16, tuple(f >> (8 + 2 * j) & 3 for j in range(nkeys))
             terms.append(Term(col=r[0], tuple_cols=tuple((r[8 + 2 * j], r[9 + 2 * j]) for j in range(w)), sign=-1 if r[1] else 1,
                               sel=None if r[2] == NONE else r[2], mult=None if r[3] == NONE else (r[3], r[4]), tag=r[5],
-                              derive=version == 2 and r[7] == 1))
-        problem = check_derived(terms)
+                              derive=version >= 2 and r[7] & 1 == 1, sorted_from=src, sort_keys=keys))
+        problem = check_sorted(terms) or check_derived(terms)
         if problem:
             raise ValueError(f"ZKA1: {problem}")
         return Arguments(k, alpha, beta, terms)
@@ -169,8 +261,11 @@ class LogupBuilder(CircuitBuilder):
         return self.group_sizes[GROUP_ACCUM] // 4
 
     def term(self, col: int, tuple_cols: Sequence[Tuple[int, int]], sign: int = 1, sel: Optional[int] = None,
-             mult: Optional[Tuple[int, int]] = None, tag: int = 0, derive: bool = False) -> Term:
-        """derive: the library fills `mult` (zkh_derive_multiplicities), the table side of a lookup (`check_derived`)"""
+             mult: Optional[Tuple[int, int]] = None, tag: int = 0, derive: bool = False, sorted_from: Optional[int] = None,
+             sort_keys: Sequence[int] = ()) -> Term:
+        """derive: the library fills `mult` (zkh_derive_multiplicities), the table side of a lookup (`check_derived`).
+        sorted_from: the library fills this term's tuple columns (zkh_derive_sorted) with the rows of term `sorted_from` (its index in
+        `self.terms`) stably sorted by the tuple positions `sort_keys`, most significant first (`check_sorted`)"""
         if not 0 <= col < self.k:
             raise ValueError(f"accum column {col} outside 0..{self.k - 1}")
         if sign not in (1, -1):
@@ -182,9 +277,14 @@ class LogupBuilder(CircuitBuilder):
                 raise ValueError(f"column ({g}, {c}) is not a code or data column of this circuit")
         if sel is not None and not 0 <= sel < self.group_sizes[GROUP_CODE]:
             raise ValueError(f"selector {sel} is not a code column")
-        t = Term(col, tuple((int(g), int(c)) for g, c in tuple_cols), sign, sel, mult, int(tag), bool(derive))
+        if sorted_from is None and len(sort_keys):
+            raise ValueError("sort_keys belong to a sorted copy (sorted_from)")
+        if sorted_from is not None and not 0 <= int(sorted_from) < 1 << 16:
+            raise ValueError(f"source term {sorted_from} outside 0..65535")
+        t = Term(col, tuple((int(g), int(c)) for g, c in tuple_cols), sign, sel, mult, int(tag), bool(derive),
+                 None if sorted_from is None else int(sorted_from), tuple(int(x) for x in sort_keys))
         self.terms.append(t)
-        problem = check_derived(self.terms)
+        problem = check_sorted(self.terms) or check_derived(self.terms)
         if problem:
             self.terms.pop()
             raise ValueError(problem)
@@ -290,7 +390,7 @@ class LogupBuilder(CircuitBuilder):
         return self.and_cond(chain, last, last_inner)
 
     def args(self) -> Arguments:
-        return Arguments(self.k, self.alpha_off, self.beta_off, sorted(self.terms, key=lambda t: t.col))
+        return Arguments(self.k, self.alpha_off, self.beta_off, _by_column(self.terms))
 
     def finish_all(self, ret) -> Tuple[np.ndarray, np.ndarray]:
         """-> (ZKC1 description, ZKA1 argument blob)"""
@@ -470,4 +570,34 @@ def reference_multiplicities(args: Arguments, po2: int, zk_cycles: int, code, da
             out[terms[i].mult[1], :A] = 0
         mcol = np.array([terms[i].mult[1] for i in uo[:, 0]], dtype=np.int64)
         out[mcol, uo[:, 1]] = _enc(counts % np.uint64(P)).astype(np.uint32)
+    return out.reshape(-1)
+
+
+def reference_sorted(args: Arguments, po2: int, zk_cycles: int, code, data) -> np.ndarray:
+    """The data trace zkh_derive_sorted leaves (raw Montgomery words, a copy).  For each sorted copy D of S: r_0 < ... < r_{m-1} the
+    active rows with selector 1 (no selector: all of them), pi the stable permutation that sorts them by the canonical values of
+    S's key columns (lexicographic in the blob's key order); data[D.v_e][r_j] = the raw word of S.v_e at r_pi(j) for every tuple
+    position e, 0 on the active rows with selector 0; rows [A, n) as given.  Raises ReferenceError on a selector other than 0 / 1."""
+    n = 1 << po2
+    A = n - zk_cycles
+    terms = Arguments.parse(args.blob()).terms
+    groups = {GROUP_CODE: np.asarray(code, dtype=np.uint32).reshape(-1, n), GROUP_DATA: np.array(data, dtype=np.uint32).reshape(-1, n)}
+    out = groups[GROUP_DATA]
+    copies = [(i, t) for i, t in enumerate(terms) if t.sorted_from is not None]
+    on = {}
+    for i, t in copies:
+        sel = np.ones(A, dtype=np.uint64) if t.sel is None else _dec(groups[GROUP_CODE][t.sel, :A])
+        bad = (sel != 0) & (sel != 1)
+        if bad.any():
+            r = int(np.argmax(bad))
+            raise ReferenceError(f"sorted-copy term {i} (tag {t.tag % P}) has selector {int(sel[r])} at row {r}, not 0 or 1")
+        on[i] = np.nonzero(sel == 1)[0]
+    for i, t in copies:
+        src, rows = terms[t.sorted_from], on[i]
+        keys = [_dec(groups[src.tuple_cols[pos][0]][src.tuple_cols[pos][1], rows]) for pos in t.sort_keys]
+        pi = np.lexsort(tuple(keys[::-1]))                                   # the last array is the primary key; stable
+        vals = [groups[g][c, rows[pi]] for g, c in src.tuple_cols]             # read before any column of D is written
+        for (_g, c), v in zip(t.tuple_cols, vals):
+            out[c, :A] = 0
+            out[c, rows] = v
     return out.reshape(-1)

@@ -17,6 +17,9 @@ The witness comes from the host (`witness`, numpy): the upstream flow of a CPU p
 SYN-LOOKUP-derived (`syn_lookup_derived`, `build_syn_lookup(shape, derive=True)`): the same description word for word (the same
 control root), the table term marked derived in a ZKA1 version-2 blob, so the library counts m (zkh_derive_multiplicities) and
 the witness may leave it zero (`witness(count=False)`).
+SYN-LOOKUP-sorted (`syn_lookup_sorted`, `build_syn_lookup(shape, sort=True)`): again the same description; every permuted copy is
+marked as the sorted copy of its memory tuple by (addr, time) in a ZKA1 version-3 blob, so the library sorts (zkh_derive_sorted) and
+the witness may leave the permuted columns zero (`witness(sort=False)`).  `derive` and `sort` combine.
 Not a shipped circuit: its control root is zkh_code_root of its code trace.
 """
 from __future__ import annotations
@@ -52,11 +55,15 @@ class Shape(NamedTuple):
 TINY = Shape(2, 4, 4, 1)            # 11 terms in 4 accum columns (po2 8..12)
 FULL = Shape(16, 4, 8, 1)           # 67 terms in 23 accum columns, 87 data columns (sealed at po2 20)
 WIDE = Shape(2, 2, 16, 1)           # a 2^16-row table (po2 >= 17): 7 terms in 3 accum columns
+MULTI = Shape(2, 4, 4, 3)           # three memory pairs: 15 terms in 5 accum columns (the batched sort)
+SORT_KEYS = (0, 2)                  # (addr, time) of a memory tuple
 
 
-def build_syn_lookup(shape: Shape = FULL, derive: bool = False) -> Tuple[np.ndarray, np.ndarray]:
+def build_syn_lookup(shape: Shape = FULL, derive: bool = False, sort: bool = False,
+                     sort_keys: Tuple[int, ...] = SORT_KEYS) -> Tuple[np.ndarray, np.ndarray]:
     """-> (ZKC1 description, ZKA1 argument blob); derive: the table term's multiplicity is derived by the library (version-2 blob,
-    the description unchanged)"""
+    the description unchanged); sort: every permuted copy is the library's sorted copy of its memory tuple by the tuple positions
+    `sort_keys` (version-3 blob, the description unchanged)"""
     n_words, n_limbs, limb_bits, n_mem = shape
     words, limbs, m, mem, perm = layout(n_words, n_limbs, n_mem)
     wd = m + 1 + 2 * MEM_W * n_mem
@@ -72,7 +79,8 @@ def build_syn_lookup(shape: Shape = FULL, derive: bool = False) -> Tuple[np.ndar
     specs.append(dict(tuple_cols=[(GROUP_CODE, 6)], sign=-1, sel=5, mult=(GROUP_DATA, m), tag=0, derive=derive))
     for i in range(n_mem):
         specs.append(dict(tuple_cols=[(GROUP_DATA, c) for c in mem[i]], sign=1, tag=1))
-        specs.append(dict(tuple_cols=[(GROUP_DATA, c) for c in perm[i]], sign=-1, tag=1))
+        copy = dict(sorted_from=len(specs) - 1, sort_keys=sort_keys) if sort else {}
+        specs.append(dict(tuple_cols=[(GROUP_DATA, c) for c in perm[i]], sign=-1, tag=1, **copy))
     for i, s in enumerate(specs):
         b.term(i // 3, **s)
     # words = sum of their limbs, on active rows
@@ -107,14 +115,24 @@ def syn_lookup_derived() -> Tuple[np.ndarray, np.ndarray]:
     return build_syn_lookup(FULL, derive=True)
 
 
+def syn_lookup_tiny_sorted() -> Tuple[np.ndarray, np.ndarray]:
+    return build_syn_lookup(TINY, sort=True)
+
+
+def syn_lookup_sorted() -> Tuple[np.ndarray, np.ndarray]:
+    return build_syn_lookup(FULL, sort=True)
+
+
 def _enc(x) -> np.ndarray:
     return ((np.asarray(x, dtype=np.uint64) % np.uint64(P)) * np.uint64((1 << 32) % P) % np.uint64(P)).astype(np.uint32)
 
 
-def witness(shape: Shape, po2: int, zk_cycles: int, seed: int = 1, count: bool = True):
+def witness(shape: Shape, po2: int, zk_cycles: int, seed: int = 1, count: bool = True, sort: bool = True, addr_range: int = 1 << 20,
+            sort_keys: Tuple[int, ...] = SORT_KEYS):
     """-> (code, data, out_global) host arrays of raw Montgomery words: random words below min(P, 2^(n_limbs L)) split into limbs,
-    the table's multiplicities (count=False: zero, for the library to derive), random memory tuples and their copy sorted by
-    (addr, time); blinding rows of data from the same seeded generator"""
+    the table's multiplicities (count=False: zero, for the library to derive), random memory tuples (addresses below `addr_range`)
+    and their copy stably sorted by the tuple positions `sort_keys`, (addr, time) (sort=False: zero, for the library to sort);
+    blinding rows of data from the same seeded generator"""
     n_words, n_limbs, limb_bits, n_mem = shape
     words, limbs, m_col, mem, perm = layout(n_words, n_limbs, n_mem)
     wd = m_col + 1 + 2 * MEM_W * n_mem
@@ -145,15 +163,23 @@ def witness(shape: Shape, po2: int, zk_cycles: int, seed: int = 1, count: bool =
     if count:
         data[m_col, :T] = counts.astype(np.uint64)
     for i in range(n_mem):
-        addr = rng.integers(0, 1 << 20, size=A, dtype=np.uint64)
+        addr = rng.integers(0, addr_range, size=A, dtype=np.uint64)
         val = rng.integers(0, P, size=A, dtype=np.uint64)
         time = rng.permutation(A).astype(np.uint64)
-        order = np.lexsort((time, addr))
-        for e, v in enumerate((addr, val, time)):
+        tup = (addr, val, time)
+        order = np.lexsort(tuple(tup[pos] for pos in sort_keys[::-1]))
+        for e, v in enumerate(tup):
             data[mem[i][e], :A] = v
-            data[perm[i][e], :A] = v[order]
+            if sort:
+                data[perm[i][e], :A] = v[order]
     data[:, A:] = rng.integers(0, P, size=(wd, n - A), dtype=np.uint64)
     return _enc(code).reshape(-1), _enc(data).reshape(-1), np.zeros(4, dtype=np.uint32)
+
+
+def witness_equal_keys(shape: Shape, po2: int, zk_cycles: int, seed: int = 1, sort: bool = True, addr_range: int = 5):
+    """the witness of `build_syn_lookup(shape, sort=True, sort_keys=(0,))`: addresses from a handful of values and the address the only
+    key, so that every key is shared by many rows of distinct (val, time) and only a STABLE sort reproduces the permuted copy"""
+    return witness(shape, po2, zk_cycles, seed=seed, sort=sort, addr_range=addr_range, sort_keys=(0,))
 
 
 def corrupt_limb(shape: Shape, data, po2: int, row: int, word: int = 0) -> np.ndarray:

@@ -161,12 +161,13 @@ __global__ void k_args_blind(uint32_t* accum, uint32_t n, uint32_t A, NoiseKey n
 // Version 2: term word 7 bit 0 = "multiplicity derived by the library" (zkh_derive_multiplicities).  A derived term is (a) of sign -1,
 // (b) with a data-group multiplicity column (c) that no tuple and no other term's multiplicity names, and (d) every other term of its
 // tag is a lookup of sign +1.  Version 1 leaves word 7 unread.
+// Version 3 adds bit 1 and its fields (validate_sorted, which has checked the word before this runs).
 const char* validate_derived(const uint32_t* a, uint32_t n_terms) {
     auto term = [&](uint32_t i) { return a + ARGS_HEADER + (size_t)TERM_WORDS * i; };
     for (uint32_t i = 0; i < n_terms; i++) {
         const uint32_t* t = term(i);
-        ZKH_REQUIRE(t[7] <= 1, "set_arguments: term %u: word 7 is %u (bit 0: derived multiplicity; the other bits are reserved)", i, t[7]);
-        if (!t[7]) continue;
+        ZKH_REQUIRE(a[1] == 3 || t[7] <= 1, "set_arguments: term %u: word 7 is %u (bit 0: derived multiplicity; the other bits are reserved)", i, t[7]);
+        if (!(t[7] & 1)) continue;
         ZKH_REQUIRE(t[1] == 1, "set_arguments: term %u: a derived multiplicity needs sign -1 (the table side of a lookup)", i);
         ZKH_REQUIRE(t[3] == GROUP_DATA, "set_arguments: term %u: a derived multiplicity must be a data-group column", i);
         for (uint32_t j = 0; j < n_terms; j++) {
@@ -176,15 +177,71 @@ const char* validate_derived(const uint32_t* a, uint32_t n_terms) {
             for (uint32_t e = 0; e < u[6]; e++)
                 ZKH_REQUIRE(!(u[8 + 2 * e] == GROUP_DATA && u[9 + 2 * e] == t[4]), "set_arguments: term %u: its derived multiplicity column "
                             "(data %u) is read by the tuple of term %u", i, t[4], j);
-            ZKH_REQUIRE(u[5] != t[5] || u[7] || u[1] == 0, "set_arguments: term %u: term %u of its tag %u has sign -1 and is not derived "
+            ZKH_REQUIRE(u[5] != t[5] || (u[7] & 1) || u[1] == 0, "set_arguments: term %u: term %u of its tag %u has sign -1 and is not derived "
                         "(the lookups of a derived tag have sign +1)", i, j, t[5]);
         }
     }
     return nullptr;
 }
 
+// Version 3: term word 7 bit 1 = "this term D is a sorted copy derived by the library" (zkh_derive_sorted, sort.hip) of its source term
+// S (bits 16..31), by nkeys (bits 4..6) tuple positions (2 bits each from bit 8, most significant key first).  (a) D has sign -1 and no
+// derived multiplicity, S is another term of sign +1 without a flag and the source of no other copy; (b) the same tag, tuple width and
+// selector, both multiplicities the constant 1; (c) D's tuple columns are pairwise distinct data columns that no other tuple and no
+// multiplicity names; (d) 1..3 key positions, distinct and below the width; (e) no derived multiplicity in D's tag.
+const char* validate_sorted(const uint32_t* a, uint32_t n_terms) {
+    auto term = [&](uint32_t i) { return a + ARGS_HEADER + (size_t)TERM_WORDS * i; };
+    constexpr uint32_t MAX_SORT_KEYS = 3;
+    for (uint32_t i = 0; i < n_terms; i++) {
+        const uint32_t* t = term(i);
+        const uint32_t f = t[7], nkeys = (f >> 4) & 7, s = f >> 16, w = t[6];
+        bool reserved = (f & 0x8c) || (!(f & 2) && f > 1);
+        for (uint32_t j = nkeys; j < 4; j++) reserved |= ((f >> (8 + 2 * j)) & 3) != 0;
+        ZKH_REQUIRE(!reserved, "set_arguments: term %u: word 7 is %#x (bit 0: derived multiplicity; bit 1: sorted copy, with its keys in "
+                    "bits 4..15 and its source term in bits 16..31; the other bits are reserved)", i, f);
+        if (!(f & 2)) continue;
+        ZKH_REQUIRE(t[1] == 1, "set_arguments: term %u: a sorted copy needs sign -1 (the permuted side of a multiset equality)", i);
+        ZKH_REQUIRE(!(f & 1), "set_arguments: term %u: a sorted copy cannot also have a derived multiplicity", i);
+        ZKH_REQUIRE(s != i && s < n_terms, "set_arguments: term %u: its source term %u is not another term of the arguments", i, s);
+        const uint32_t* u = term(s);
+        ZKH_REQUIRE(u[1] == 0, "set_arguments: term %u: its source term %u needs sign +1", i, s);
+        ZKH_REQUIRE(u[7] == 0, "set_arguments: term %u: its source term %u is itself derived or a sorted copy", i, s);
+        for (uint32_t j = 0; j < n_terms; j++)
+            ZKH_REQUIRE(j == i || !(term(j)[7] & 2) || term(j)[7] >> 16 != s, "set_arguments: term %u: its source term %u is also the source of "
+                        "term %u", i, s, j);
+        ZKH_REQUIRE(u[5] == t[5] && u[6] == w && u[2] == t[2], "set_arguments: term %u: its source term %u has another tag, tuple width or selector", i, s);
+        ZKH_REQUIRE(t[3] == NONE && u[3] == NONE, "set_arguments: term %u: a sorted copy and its source term %u have the constant multiplicity 1", i, s);
+        for (uint32_t e = 0; e < w; e++) {
+            const uint32_t g = t[8 + 2 * e], col = t[9 + 2 * e];
+            ZKH_REQUIRE(g == GROUP_DATA, "set_arguments: term %u: tuple column (%u, %u) of a sorted copy must be a data-group column", i, g, col);
+            for (uint32_t e2 = 0; e2 < e; e2++)
+                ZKH_REQUIRE(t[9 + 2 * e2] != col, "set_arguments: term %u: its sorted column (data %u) appears twice in its tuple", i, col);
+            for (uint32_t j = 0; j < n_terms; j++) {
+                const uint32_t* x = term(j);
+                for (uint32_t e2 = 0; j != i && e2 < x[6]; e2++)
+                    ZKH_REQUIRE(!(x[8 + 2 * e2] == GROUP_DATA && x[9 + 2 * e2] == col), "set_arguments: term %u: its sorted column (data %u) is "
+                                "read by the tuple of term %u", i, col, j);
+                ZKH_REQUIRE(!(x[3] == GROUP_DATA && x[4] == col), "set_arguments: term %u: its sorted column (data %u) is the multiplicity of "
+                            "term %u", i, col, j);
+            }
+        }
+        const uint32_t kmax = w < MAX_SORT_KEYS ? w : MAX_SORT_KEYS;
+        ZKH_REQUIRE(nkeys >= 1 && nkeys <= kmax, "set_arguments: term %u: %u sort keys (1..%u: at most %u, and no more than the tuple width %u)", i,
+                    nkeys, kmax, MAX_SORT_KEYS, w);
+        for (uint32_t j = 0; j < nkeys; j++) {
+            const uint32_t pos = (f >> (8 + 2 * j)) & 3;
+            bool ok = pos < w;
+            for (uint32_t j2 = 0; j2 < j; j2++) ok &= ((f >> (8 + 2 * j2)) & 3) != pos;
+            ZKH_REQUIRE(ok, "set_arguments: term %u: its sort key positions must be distinct and below the tuple width %u", i, w);
+        }
+        for (uint32_t j = 0; j < n_terms; j++)
+            ZKH_REQUIRE(!((term(j)[7] & 1) && term(j)[5] == t[5]), "set_arguments: term %u: term %u of its tag %u has a derived multiplicity", i, j, t[5]);
+    }
+    return nullptr;
+}
+
 const char* validate_args(const zkh_circuit* c, const uint32_t* a, size_t words) {
-    ZKH_REQUIRE(words >= ARGS_HEADER && a[0] == ARGS_MAGIC && (a[1] == 1 || a[1] == 2), "set_arguments: not a ZKA1 (version 1) argument blob");
+    ZKH_REQUIRE(words >= ARGS_HEADER && a[0] == ARGS_MAGIC && a[1] >= 1 && a[1] <= 3, "set_arguments: not a ZKA1 (version 1) argument blob");
     const uint32_t k = a[2], alpha = a[3], beta = a[4], n_terms = a[5];
     ZKH_REQUIRE(words == ARGS_HEADER + (size_t)TERM_WORDS * n_terms, "set_arguments: %zu words for %u terms", words, n_terms);
     ZKH_REQUIRE(k >= 1 && 4ull * k == c->group_size[GROUP_ACCUM], "set_arguments: %u accum Fp4 columns, the circuit's accum group is %u wide",
@@ -212,7 +269,8 @@ const char* validate_args(const zkh_circuit* c, const uint32_t* a, size_t words)
         }
     }
     for (uint32_t col = 0; col < k; col++) ZKH_REQUIRE(per_col[col] >= 1, "set_arguments: accum column %u has no terms", col);
-    return a[1] == 2 ? validate_derived(a, n_terms) : nullptr;
+    if (a[1] == 3) ZKH_TRY(validate_sorted(a, n_terms));
+    return a[1] >= 2 ? validate_derived(a, n_terms) : nullptr;
 }
 
 }  // namespace
@@ -475,7 +533,7 @@ __global__ __launch_bounds__(DERIVE_THREADS) void k_derive_write(const uint32_t*
 }  // namespace
 
 extern "C" int zkh_circuit_derives_multiplicities(const zkh_circuit* c) {
-    if (!c || c->args.size() < ARGS_HEADER || c->args[1] != 2) return 0;
+    if (!c || c->args.size() < ARGS_HEADER || c->args[1] < 2) return 0;
     for (uint32_t i = 0; i < c->args[5]; i++)
         if (c->args[ARGS_HEADER + (size_t)TERM_WORDS * i + 7] & 1) return 1;
     return 0;

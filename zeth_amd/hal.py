@@ -154,6 +154,8 @@ ABI = {
     "zkh_accumulate": (_err, [_vp, _vp, _sz, _sz, _u32p, _vp, _vp, _u32p, _vp]),
     "zkh_circuit_derives_multiplicities": (_i, [_vp]),
     "zkh_derive_multiplicities": (_err, [_vp, _vp, _sz, _sz, _vp, _vp]),
+    "zkh_circuit_derives_sorted": (_i, [_vp]),
+    "zkh_derive_sorted": (_err, [_vp, _vp, _sz, _sz, _vp, _vp]),
     "zkh_syn_chain_contributions": (_err, [_vp, _vp, C.POINTER(_u64), _u32p, _sz, _sz, _u32p]),
     "zkh_syn_preflight_ram_words": (_sz, []),
     "zkh_syn_preflight": (_err, [_u64, _sz, _sz, _u32p, _u32p, C.POINTER(C.c_double)]),
@@ -330,6 +332,10 @@ class Circuit:
     def derives_multiplicities(self) -> bool:
         """the arguments (ZKA1 version 2) have a term whose multiplicity the library derives (zkh_derive_multiplicities)"""
         return bool(_lib.zkh_circuit_derives_multiplicities(self.h))
+
+    def derives_sorted(self) -> bool:
+        """the arguments (ZKA1 version 3) have a term that is a sorted copy the library derives (zkh_derive_sorted)"""
+        return bool(_lib.zkh_circuit_derives_sorted(self.h))
 
     def jit(self, use_cache: bool = True) -> None:
         """Generate + compile (hipcc --genco per part, in parallel, disk-cached) + attach the straight-line eval_check
@@ -774,6 +780,11 @@ class HipHal:
         """fill the derived multiplicity columns of `data` on the active rows (zkh_derive_multiplicities): raises HalError on a table
         selector other than 0 / 1 or a lookup without a table entry (`data` is then unchanged)"""
         _check(_lib.zkh_derive_multiplicities(self.ctx, circuit.h, po2, zk_cycles, code.h, data.h))
+
+    def derive_sorted(self, circuit: Circuit, po2: int, zk_cycles: int, code: Buffer, data: Buffer) -> None:
+        """fill the tuple columns of the derived sorted copies of `data` on the active rows (zkh_derive_sorted), before
+        derive_multiplicities: raises HalError on a selector other than 0 / 1 (`data` is then unchanged)"""
+        _check(_lib.zkh_derive_sorted(self.ctx, circuit.h, po2, zk_cycles, code.h, data.h))
 
     # ---- profiling ----
     def prof_enable(self, on: bool = True) -> None:
