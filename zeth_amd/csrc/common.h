@@ -60,7 +60,7 @@ struct DeviceTables {
     uint32_t* tw_rev_lo; uint32_t* tw_rev_hi;   // same for ROU_REV[MAX_LOG_N]
     uint32_t* tile_fwd;  uint32_t* tile_rev;    // ROU_FWD[12]^j / ROU_REV[12]^j, j < 2048
     uint32_t* layer_fwd; uint32_t* layer_rev;   // per-layer: [2^(j-1) + e] = ROU[j]^e, e < 2^(j-1), j <= 12 (4096 words)
-    uint32_t* layer_fwd_plain;                  // layer_fwd out of Montgomery form (plain residues): lazy butterflies (ntt.hip)
+    uint32_t* layer_fwd_lazy;                   // layer_fwd centred, as plain residues and as Montgomery words (8192 words, ntt_lazy.h)
     uint32_t* shift_lo;  uint32_t* shift_hi;    // 3^lo, 3^(hi*4096), hi < 2^14
 };
 

@@ -7,6 +7,7 @@
 
 #include <sys/random.h>
 #include "poseidon2.h"
+#include "ntt_lazy.h"
 #include "../../include/zkh_poseidon2_consts.h"
 
 using namespace zkh;
@@ -194,8 +195,10 @@ static const char* ctx_init_tables(zkh_ctx* c) {
         }
         ZKH_TRY(upload(&c->tab.layer_fwd, lf));
         ZKH_TRY(upload(&c->tab.layer_rev, lr));
-        for (auto& w : lf) w = mont_reduce((uint64_t)w);          // word / R: the plain residue
-        ZKH_TRY(upload(&c->tab.layer_fwd_plain, lf));
+        static_assert(LAZY_TAB_LOG == LDS_TW_LOG, "the lazy table covers the per-layer tables");
+        std::vector<uint32_t> lz(LAZY_TAB_WORDS);
+        lazy_layer_table(lz.data(), lf.data());
+        ZKH_TRY(upload(&c->tab.layer_fwd_lazy, lz));
     }
     Fp three = fp_encode(3);
     ZKH_TRY(upload(&c->tab.shift_lo, powers(three, TW_SIZE)));
@@ -228,7 +231,7 @@ extern "C" void zkh_ctx_destroy(zkh_ctx* c) {
     (void)hipStreamSynchronize(c->stream);
     for (auto& kv : c->pool) (void)hipFree(kv.second);
     uint32_t* t[] = {c->tab.rc, c->tab.diag, c->tab.tw_fwd_lo, c->tab.tw_fwd_hi, c->tab.tw_rev_lo, c->tab.tw_rev_hi,
-                     c->tab.tile_fwd, c->tab.tile_rev, c->tab.shift_lo, c->tab.shift_hi, c->tab.layer_fwd, c->tab.layer_rev, c->tab.layer_fwd_plain};
+                     c->tab.tile_fwd, c->tab.tile_rev, c->tab.shift_lo, c->tab.shift_hi, c->tab.layer_fwd, c->tab.layer_rev, c->tab.layer_fwd_lazy};
     for (auto p : t) (void)hipFree(p);
     for (auto& p : c->pending) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
     for (auto ev : c->event_pool) (void)hipEventDestroy(ev);

@@ -11,6 +11,7 @@
 // unshifted coefficients ever touch HBM.
 //   HBM traffic: 8 B per element per pass (one read + one write), i.e. 16 B/elem for k <= 22, 24 B/elem up to 2^26.
 #include "common.h"
+#include "ntt_lazy.h"
 
 using namespace zkh;
 
@@ -39,7 +40,7 @@ struct PassParams {
     const uint32_t* sh_hi;
     uint32_t tiles_per_col;
     uint32_t lazy;           // forward register-radix pair (low12 + high<8|10>): see radix_layers<..., LAZY>
-    uint32_t lazy_comp;      // R^(number of lazy layers) as a Montgomery word: folded into the four-step twiddle
+    uint32_t lazy_comp;      // R^(number of lazy reductions on a path) as a Montgomery word: folded into the four-step twiddle
     uint32_t shift16[16];    // inverse last pass: n^-1 * 3^(bitrev4(k) << (log_n - 4)), k < 16 (Montgomery; 0 = unused)
 };
 
@@ -269,38 +270,19 @@ __global__ void k_bit_reverse_small(uint32_t* io, uint32_t log_n, size_t count) 
 // consecutive lanes read consecutive words.
 // =====================================================================================================
 //
-// LAZY (forward only): values are SIGNED representatives in (-P, P) and every layer divides by R = 2^32:
-//   a = (x + w y) / R,  b = (x - w y) / R   as   smont_reduce(sext(x) +- w*y)   (|x + w y| <= P + P^2 < P 2^31),
-// with w read from the PLAIN (non-Montgomery) twiddle table, so that x and the product pick up the same factor 1/R,
-// i.e. one sign extension, two v_mad_i64_i32 and two uncorrected reductions per butterfly (11.9 add-slots instead of
-// 14.1 for product + modular add + modular subtract).  The accumulated R^-layers is cancelled by one constant folded
-// into the four-step twiddle of the strided pass, whose outputs are canonicalised once.  Exact field arithmetic:
-// results are identical to the plain path.
+// LAZY (forward only): values are SIGNED representatives in (-P, P) and the layers run in PAIRS with one uncorrected
+// reduction per output per pair (ntt_lazy.h: the first layer's sums x0 +- wa x1 stay 64-bit and take the second layer's
+// product on top): 24 instructions per four elements through two layers.  Every pair divides by R = 2^32; a single
+// layer (odd expand_bits) is  smont_reduce(sext(x) +- w*y)  and divides by R as well.  The twiddles come CENTRED from the
+// lazy table: plain residues for the first layer of a pair, Montgomery words for the second.  The accumulated
+// R^-reductions is cancelled by one constant folded into the four-step twiddle of the strided pass, whose outputs are
+// canonicalised once.  Exact field arithmetic: results are identical to the plain path.
 template <int LOGR, bool INVERSE, bool BASE0, int J_LO, bool LAZY = false>
 __device__ __forceinline__ void radix_layers(uint32_t (&v)[1 << LOGR], const uint32_t* __restrict__ ltab,
                                              const uint32_t base_low, const int first_b) {
     constexpr int N = 1 << LOGR;
     if (!INVERSE && LAZY) {
-#pragma unroll
-        for (int b = 0; b < LOGR; b++) {
-            if (b < first_b) continue;
-            const uint32_t* tw = ltab + (1u << (J_LO + b - 1));
-#pragma unroll
-            for (int kk = 0; kk < (1 << b); kk++) {
-                const bool unit = BASE0 && kk == 0;
-                const int32_t w = (int32_t)(unit ? 1u : tw[base_low + ((uint32_t)kk << (J_LO - 1))]), nw = -w;   // plain residue
-#pragma unroll
-                for (int hi = 0; hi < (N >> (b + 1)); hi++) {
-                    const int k = (hi << (b + 1)) | kk;
-                    const int64_t x = (int64_t)(int32_t)v[k];
-                    const int32_t y = (int32_t)v[k + (1 << b)];
-                    // BASE0 call sites pass base_low = 0: the twiddle is wave-uniform and stays in an SGPR (the "v"
-                    // operand of mad_i64 would cost a v_mov per product)
-                    v[k] = (uint32_t)smont_reduce(BASE0 ? mad_i64_k(y, w, x) : mad_i64(y, w, x));
-                    v[k + (1 << b)] = (uint32_t)smont_reduce(BASE0 ? mad_i64_k(y, nw, x) : mad_i64(y, nw, x));
-                }
-            }
-        }
+        lazy_layers<LOGR, BASE0, J_LO>(v, ltab, base_low, first_b);     // ntt_lazy.h
     } else if (INVERSE) {
 #pragma unroll
         for (int b = LOGR - 1; b >= 0; b--) {
@@ -415,7 +397,7 @@ __global__ __launch_bounds__(256) void k_ntt_low12(PassParams p) {
         __syncthreads();
 #pragma unroll
         for (int k = 0; k < 16; k++) v[k] = lds[k * 256 + tid];
-        radix_layers<4, false, false, 9, LAZY>(v, ltab, tid, 0);                // layers 9..12 (LAZY: signed words scaled by R^-(12 - expand_bits))
+        radix_layers<4, false, false, 9, LAZY>(v, ltab, tid, 0);                // layers 9..12 (LAZY: signed words scaled by R^-(reductions so far))
 #pragma unroll
         for (int k = 0; k < 16; k++) out[base + k * 256 + tid] = v[k];
     }
@@ -459,7 +441,7 @@ __global__ __launch_bounds__(1 << RH) void k_ntt_high(PassParams p) {
     uint32_t tw[16];
     if (RH == 10) {         // m = g*16 + i*4 + k: bitrev10(m) = br2(k)*256 + br2(i)*64 + br6(g);  slot = 4*i + k
         uint32_t w0 = root(lcol * (__brev(g) >> 26));
-        if (LAZY) w0 = tmul(w0, p.lazy_comp);                // cancels the R^-layers of both lazy passes
+        if (LAZY) w0 = tmul(w0, p.lazy_comp);                // cancels the R^-reductions of both lazy passes
         const uint32_t u1 = root(lcol * 64u), v1 = root(lcol * 256u);
         const uint32_t u2 = tmul(u1, u1), u3 = tmul(u2, u1), v2 = tmul(v1, v1), v3 = tmul(v2, v1);
         const uint32_t wi[4] = {w0, tmul(w0, u2), tmul(w0, u1), tmul(w0, u3)};      // U^br2(i)
@@ -611,7 +593,10 @@ const char* run_transform(zkh_ctx* c, bool inverse, const uint32_t* in, size_t i
     // per-shape twiddle matrix, 32-byte tiles and the column-fast grid were measured slower: profiles/README.md, r03_ntt_matrix.txt,
     // r03_ntt_ab*.jsonl.  None of those variants is in the library any more.)
     const bool lazy = !inverse && npass == 2 && passes[0].R == 12 && (passes[1].R == 8 || passes[1].R == 10) && expand_bits <= 4;
-    const uint32_t lazy_comp = lazy ? fp_pow(Fp::raw(R2), passes[0].R - expand_bits + passes[1].R).v : 0;
+    // reductions on a path: the low pass's rounds of 4 layers (the first without its expand_bits skipped ones), the strided
+    // pass's rounds of 4 + 4 (+ 2) layers, one per pair of layers and one per single layer
+    const uint32_t lazy_reds = lazy ? lazy_reductions(4, expand_bits) + 2 * lazy_reductions(4, 0) + lazy_reductions(passes[1].R, 0) : 0;
+    const uint32_t lazy_comp = lazy ? fp_pow(Fp::raw(R2), lazy_reds).v : 0;
     for (size_t pi = 0; pi < npass; pi++) {
         // inverse: high bits first; forward: low bits first
         const Pass ps = inverse ? passes[npass - 1 - pi] : passes[pi];
@@ -637,7 +622,7 @@ const char* run_transform(zkh_ctx* c, bool inverse, const uint32_t* in, size_t i
         p.zk_shift = (inverse && last && zk) ? 1 : 0;
         p.lazy = lazy; p.lazy_comp = lazy_comp;
         p.tile_tw = inverse ? c->tab.tile_rev : c->tab.tile_fwd;
-        p.layer_tw = inverse ? c->tab.layer_rev : (lazy ? c->tab.layer_fwd_plain : c->tab.layer_fwd);
+        p.layer_tw = inverse ? c->tab.layer_rev : (lazy ? c->tab.layer_fwd_lazy : c->tab.layer_fwd);
         p.tw_lo = inverse ? c->tab.tw_rev_lo : c->tab.tw_fwd_lo;
         p.tw_hi = inverse ? c->tab.tw_rev_hi : c->tab.tw_fwd_hi;
         p.sh_lo = c->tab.shift_lo; p.sh_hi = c->tab.shift_hi;
