@@ -3,10 +3,15 @@
 modelled issue cycles, against the multiply floor — the evidence behind "Poseidon2 is at its instruction floor".
 
     python tools/isa_histogram.py > profiles/r03_hash_rows_isa_histogram.txt
+    python tools/isa_histogram.py --csrc <another checkout>/zeth_amd/csrc      (the same count for another tree's hash.hip)
 
 Compiles zeth_amd/csrc/hash.hip for gfx950 with the build's flags (`-S`, device only), takes the first copy of the block
 loop of k_hash_rows (interior blocks of the sponge: 16 absorbed columns, one permutation), finds its inner loops from the
-backward branches and weights them by their trip counts (4 full rounds, 7 groups of three partial rounds, 4 full rounds).
+backward branches and weights them by their trip counts (4 full rounds, 7 groups of three partial rounds, 4 full rounds, or
+3 where the last full round is peeled out of its loop and follows it as straight-line code).
+Code that a steady-state block does not run is weighted by what it is (path_weights): inside a loop of N trips the special
+cases of one trip (first / last partial group) count once per permutation; at block level the tail block's predicated loads
+and the alternative that the last block of a sponge takes count zero.
 Issue cycles per wave64 instruction from tools/ubench_valu.hip (profiles/r01_ubench_valu.txt): 32-bit multiplies,
 v_mad_*64*, fp64 and v_cvt_f64 4.0; plain add / sub / logic / shift / mov 2.5 (measured 2.46); v_min / v_add3 / v_lshl_add 4.0;
 compare-select pairs 2.1 + 2.1.
@@ -40,12 +45,106 @@ def cycles(op: str) -> float:
     return 4.0 if op.startswith(FOUR) else 2.5
 
 
+def valu_count(body, a, b):
+    return sum(1 for i in range(a, b) if body[i].startswith("\tv_"))
+
+
+def path_weights(body, labels, outer, merged, trips):
+    """weight[i] of every line of the block loop on a steady-state block.  Conditional code is found from the scalar branches:
+    (a) a forward conditional branch skips region A = (branch, target); if A ends in a forward jump, the lines from the target
+        to that jump's target are the alternative B (if / else);
+    (b) the lines between a backward conditional branch and a following backward `s_branch` to the same label run only when
+        the loop does not repeat (the compiler's place for what only the last trip does); if the two labels differ, the lines
+        between the labels and the lines after the branch are alternatives, as in (a).
+    Inside a loop of N trips: (b) and a lone A run once per permutation; of A and B the longer is the special case (once) and
+    the shorter the common one (N - 1).  At block level: (b) and an A with branches of its own (the tail block's per-column
+    loads) are not steady state (0); a plain A is."""
+    def resolve(lbl):                                   # through trampolines: a label followed only by a jump
+        for _ in range(4):
+            i = labels.get(lbl)
+            if i is None:
+                return None
+            j = i + 1
+            while j < len(body) and (not body[j].strip() or body[j].strip().startswith(";")):
+                j += 1
+            m = re.match(r"\s+s_branch\s+(\.LBB\d+_\d+)", body[j]) if j < len(body) else None
+            if not m:
+                return i
+            lbl = m.group(1)
+        return labels.get(lbl)
+    def loop_of(i):
+        for k, (a, b) in enumerate(merged):
+            if a <= i <= b:
+                return k
+        return None
+    weight = [1.0] * len(body)
+    for k, (a, b) in enumerate(merged):
+        for i in range(a, b + 1):
+            weight[i] = trips[k]
+    br = re.compile(r"\s+(s_cbranch_(?:scc|vcc)\S*|s_cbranch_exec\S*|s_branch)\s+(\.LBB\d+_\d+)")
+    i = outer[0]
+    while i <= outer[1]:
+        m = br.match(body[i])
+        if not m or not m.group(1).startswith(("s_cbranch_scc", "s_cbranch_vcc")):
+            i += 1
+            continue
+        k = loop_of(i)
+        n = trips[k] if k is not None else None
+        raw = labels.get(m.group(2))
+        if raw is not None and raw < i:                 # (b): backward conditional, then code, then a backward jump
+            j = i + 1
+            while j <= outer[1] and not br.match(body[j]) and not re.match(r"^\.LBB", body[j]):
+                j += 1
+            m2 = br.match(body[j]) if j <= outer[1] else None
+            raw2 = labels.get(m2.group(2), 1 << 30) if m2 and m2.group(1) == "s_branch" else 1 << 30
+            if raw2 == raw and valu_count(body, i + 1, j):
+                for x in range(i + 1, j):
+                    weight[x] = 1.0 if n else 0.0
+            elif raw < raw2 < i and n:                  # two alternatives: [raw, raw2) or the lines after the branch
+                long_a = valu_count(body, raw, raw2) >= valu_count(body, i + 1, j)
+                for x in range(raw, raw2):
+                    weight[x] = 1.0 if long_a else n - 1.0
+                for x in range(i + 1, j):
+                    weight[x] = n - 1.0 if long_a else 1.0
+            i += 1
+            continue
+        t = resolve(m.group(2))
+        if t is None or t <= i or t > outer[1] or (k is not None and t > merged[k][1]) or (k is None and loop_of(t - 1) is not None):
+            i += 1
+            continue
+        a_lo, a_hi = i + 1, t                           # region A = [a_lo, a_hi)
+        last = next((x for x in range(a_hi - 1, a_lo - 1, -1) if body[x].startswith("\t") and not body[x].strip().startswith(";")), None)
+        m3 = br.match(body[last]) if last is not None else None
+        b_hi = None
+        if m3 and m3.group(1) in ("s_branch", "s_cbranch_execnz", "s_cbranch_execz"):
+            t2 = resolve(m3.group(2))
+            if t2 is not None and t2 > a_hi and t2 <= (merged[k][1] if k is not None else outer[1]):
+                b_hi = t2
+        nested = any(br.match(body[x]) for x in range(a_lo, (last if m3 else a_hi)))
+        if n:
+            if b_hi is not None:
+                long_a = valu_count(body, a_lo, a_hi) >= valu_count(body, a_hi, b_hi)
+                for x in range(a_lo, a_hi):
+                    weight[x] = 1.0 if long_a else n - 1.0
+                for x in range(a_hi, b_hi):
+                    weight[x] = n - 1.0 if long_a else 1.0
+            else:
+                for x in range(a_lo, a_hi):
+                    weight[x] = 1.0
+        elif nested:
+            for x in range(a_lo, a_hi):
+                weight[x] = 0.0
+        i = (b_hi if b_hi is not None else a_hi) if (n or nested) else i + 1
+    return weight
+
+
 def main():
     sys.path.insert(0, ROOT)
     from zeth_amd import build as B
+    csrc = sys.argv[sys.argv.index("--csrc") + 1] if "--csrc" in sys.argv else B.CSRC
     with tempfile.TemporaryDirectory() as tmp:
         out = os.path.join(tmp, "hash.s")
-        cmd = [B.HIPCC, *B.FLAGS, *B.EXTRA_FLAGS.get("hash.hip", []), "--cuda-device-only", "-S", os.path.join(B.CSRC, "hash.hip"), "-o", out]
+        cmd = [B.HIPCC, *B.FLAGS, *B.EXTRA_FLAGS.get("hash.hip", []), "--cuda-device-only", "-S", os.path.join(csrc, "hash.hip"), "-o", out]
         subprocess.run(cmd, check=True, capture_output=True)
         lines = open(out).read().split("\n")
     start = next(i for i, l in enumerate(lines) if re.match(r"^_ZN\S*k_hash_rows\S*:", l))
@@ -58,8 +157,9 @@ def main():
         if m and labels.get(m.group(1), 1 << 30) < i:
             back.append((labels[m.group(1)], i))
     back.sort()
-    outer = back[0] if back else None                   # first loop nest = the interior-block loop
-    outer = max((b for b in back if b[0] <= back[0][0] + 400 and b[1] > back[0][1]), key=lambda b: b[1], default=back[0])
+    # first loop nest = the block loop: from its header to the last branch back to that header (blocks the compiler placed
+    # after that latch belong to the tail block's predicated loads and are not part of a steady-state block)
+    outer = (back[0][0], max(b[1] for b in back if b[0] == back[0][0]))
     inner = [b for b in back if outer[0] < b[0] and b[1] < outer[1]]
     # merge loops that share a region (rotated loops produce two backward branches into the same body)
     merged = []
@@ -69,10 +169,12 @@ def main():
         else:
             merged.append(b)
     kinds = ["full", "partial", "full"] if len(merged) == 3 else ["?"] * len(merged)
-    weight = [1.0] * len(body)
-    for (a, b), kind in zip(merged, kinds):
-        for i in range(a, b + 1):
-            weight[i] = TRIPS.get(kind, 1)
+    trips = [TRIPS.get(kind, 1) for kind in kinds]
+    # a peeled last full round: one more round body (hundreds of VALU instructions) between the third loop and the block loop's end
+    peeled = len(merged) == 3 and valu_count(body, merged[2][1] + 1, outer[1] + 1) > 300
+    if peeled:
+        trips[2] -= 1
+    weight = path_weights(body, labels, outer, merged, trips)
     hist = collections.Counter()
     static = collections.Counter()
     other = collections.Counter()
@@ -81,6 +183,8 @@ def main():
         if not l.startswith("\t") or not l.strip() or l.strip().startswith((".", ";")):
             continue
         op = l.strip().split()[0]
+        if weight[i] == 0:
+            continue
         if op.startswith("v_"):
             hist[op] += weight[i]
             static[op] += 1
@@ -90,7 +194,7 @@ def main():
     tot_cyc = sum(cycles(op) * n for op, n in hist.items())
     print("# k_hash_rows, steady-state absorb block = ONE Poseidon2 permutation per lane (gfx950, hipcc -O3 -enable-misched=0)")
     print(f"# block loop at asm lines {outer[0]}..{outer[1]} of the kernel; inner loops " +
-          ", ".join(f"{k} x{TRIPS.get(k, 1)} [{a}..{b}]" for (a, b), k in zip(merged, kinds)))
+          ", ".join(f"{k} x{n} [{a}..{b}]" for (a, b), k, n in zip(merged, kinds, trips)) + (" + the last full round peeled" if peeled else ""))
     print(f"# dynamic VALU instructions per wave-permutation (static count x trip counts): {total:.0f}"
           f"   (hardware: SQ_INSTS_VALU / (leaves x blocks / 64) = 6.44 k, profiles/r02_sq_counters.txt)")
     print(f"# modelled issue cycles per wave-permutation: {tot_cyc:.0f}  (1024 SIMDs: {tot_cyc / 1024:.1f} SIMD-cycles per 64 permutations)")

@@ -41,7 +41,7 @@ inline const char* make_err(const char* fmt, ...) {
         if (!(cond)) return zkh::make_err(__VA_ARGS__); \
     } while (0)
 
-constexpr int ZKH_P2_PTAB = 414;            // partial-round table, layout in poseidon2.h (P2_TAB_WORDS)
+constexpr int ZKH_P2_PTAB = 486;            // partial-round table, layout in poseidon2.h (P2_TAB_WORDS)
 constexpr int TW_BITS = 12;                 // two-level twiddle tables: w_{2^26}^(hi*4096 + lo), lo < 2^12, hi < 2^14
 constexpr int TW_SIZE = 1 << TW_BITS;
 constexpr int TW_HI_BITS = 14;              // (64 KiB per hi table: L2-resident; the index arithmetic of every kernel is unchanged)

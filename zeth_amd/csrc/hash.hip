@@ -36,24 +36,27 @@ __global__ __launch_bounds__(256, 4) void k_hash_rows(uint32_t* __restrict__ out
     for (int i = 0; i < CELLS; i++) s[i] = 0;
     const uint32_t* src = matrix + r;
     const uint32_t full = cols / RATE, tail = cols % RATE;
+    const uint32_t blocks = full + (tail || cols == 0 ? 1u : 0u);
     // No register double-buffer for the next 16 columns: the grouped partial rounds need the VGPRs, and with >= 5
     // waves per SIMD the loads of one wave hide under the permutations of the others.
-    for (uint32_t b = 0; b < full; b++) {
+    // ONE call site of the permutation serves full blocks and the tail block: interior blocks keep the capacity, the
+    // last block the digest, either one in s[16..24) (poseidon2_mix_sponge: a scalar branch around the last eight
+    // reductions).  The capacity stays a nearly centred signed word from block to block; only the digest is canonicalised.
+    for (uint32_t b = 0; b < blocks; b++) {
         const uint32_t* bsrc = src + (size_t)b * RATE * rows;
+        if (b < full) {
 #pragma unroll
-        for (int i = 0; i < RATE; i++) s[i] = bsrc[(size_t)i * rows];
-        poseidon2_mix_raw(s, rc, diag);
+            for (int i = 0; i < RATE; i++) s[i] = bsrc[(size_t)i * rows];
+        } else {
 #pragma unroll
-        for (int i = RATE; i < CELLS; i++) s[i] = p2_finish(s[i], diag);     // the capacity is all the next block keeps
+            for (int i = 0; i < RATE; i++) s[i] = (uint32_t)i < tail ? bsrc[(size_t)i * rows] : 0u;
+        }
+        poseidon2_mix_sponge(s, rc, diag, b + 1 == blocks);
+#pragma unroll
+        for (int i = RATE; i < CELLS; i++) s[i] = p2_signed(s[i]);
     }
-    if (tail || cols == 0) {
-        const uint32_t* tsrc = src + (size_t)full * RATE * rows;
 #pragma unroll
-        for (int i = 0; i < RATE; i++) s[i] = (uint32_t)i < tail ? tsrc[(size_t)i * rows] : 0u;
-        poseidon2_mix_raw(s, rc, diag);
-    }
-#pragma unroll
-    for (int i = 0; i < OUT; i++) s[i] = p2_finish(s[i], diag);
+    for (int i = 0; i < OUT; i++) s[i] = canon((int32_t)s[RATE + i]);
     uint4* o = (uint4*)(out + r * 8);
     o[0] = make_uint4(s[0], s[1], s[2], s[3]);
     o[1] = make_uint4(s[4], s[5], s[6], s[7]);
@@ -71,9 +74,9 @@ __global__ __launch_bounds__(256, 4) void k_hash_fold(uint32_t* __restrict__ io,
     s[8] = c.x; s[9] = c.y; s[10] = c.z; s[11] = c.w; s[12] = d.x; s[13] = d.y; s[14] = d.z; s[15] = d.w;
 #pragma unroll
     for (int k = RATE; k < CELLS; k++) s[k] = 0;
-    poseidon2_mix_raw(s, rc, diag);
+    poseidon2_mix_raw<0, OUT, RATE>(s, rc, diag);             // the zero capacity is not fed through the first M_ext
 #pragma unroll
-    for (int k = 0; k < OUT; k++) s[k] = p2_finish(s[k], diag);
+    for (int k = 0; k < OUT; k++) s[k] = p2_finish(s[k]);
     uint4* o = (uint4*)(io + (output_size + i) * 8);
     o[0] = make_uint4(s[0], s[1], s[2], s[3]);
     o[1] = make_uint4(s[4], s[5], s[6], s[7]);

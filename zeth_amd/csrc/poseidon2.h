@@ -12,9 +12,10 @@ constexpr int CELLS = 24, RATE = 16, OUT = 8, HALF_FULL = 4, PARTIAL = 21, ROUND
 // Partial-round table (Montgomery form): [0,24) d, [24,48) d^2, [48,72) d^3, [72] c1 = sum_{i>=1} d_i, [73] 23,
 // then the three rows again as centred two's-complement words in [74, 146); then what the lane-per-permutation
 // form below needs (scaled representations, see poseidon2_mix_raw): [146, 338) the eight full rounds' constants,
-// [338, 410) the first partial group's centred rows, [410, 413) three scale corrections.
+// [338, 410) the first partial group's centred rows, [410, 414) four scale corrections, [414, 486) the last partial
+// group's centred rows.
 constexpr int P2_TAB_SIGNED = 74, P2_TAB_FULL = P2_TAB_SIGNED + 3 * CELLS, P2_TAB_GROUP0 = P2_TAB_FULL + 2 * HALF_FULL * CELLS,
-              P2_TAB_KAPPA = P2_TAB_GROUP0 + 3 * CELLS, P2_TAB_WORDS = P2_TAB_KAPPA + 4;
+              P2_TAB_KAPPA = P2_TAB_GROUP0 + 3 * CELLS, P2_TAB_EXIT = P2_TAB_KAPPA + 4, P2_TAB_WORDS = P2_TAB_EXIT + 3 * CELLS;
 
 // (x + rc)^7.  The round-constant tables hold rc - P (in [-P, 0)), so x + rcs is already a valid signed operand in
 // [-P, P): one plain add instead of a modular add.  Four signed Montgomery products (no per-product correction) and
@@ -67,10 +68,12 @@ ZKH_HD void m_ext(uint32_t (&s)[CELLS]) {
 // canonicalisation; (2) every M_ext divides the representation by 2^32.  The state is therefore carried as
 // v = lambda_r * x with a known per-round scale (exact: M_ext is linear, x^7 turns lambda into lambda^7 / R^6), the
 // stored round constants are lambda_r * rc, and the scale is brought back to R where the partial rounds start (one
-// product for cell 0, folded into the first group's table rows for cells 1..23) and where a caller consumes cells
-// (p2_finish: one product per consumed cell).  Scales, R = 2^32:
-//   in R | F1: 1, F2: R^-7, F3: R^-56, F4: R^-399 | partial rounds: R (entry from R^-2800) | F5: R, F6: 1,
-//   F7: R^-7, F8: R^-56 | out: R^-399 (+ F64_OFF).
+// product for cell 0, folded into the first group's table rows for cells 1..23).  A full round maps lambda to
+// f(lambda) = lambda^7 / R^7, and 7 is invertible mod P - 1, so f has an inverse: the partial rounds do not EXIT at R
+// but at the sigma with f^4(sigma) = R (the last group's table rows carry mu = sigma / R, its S2 one product by mu), and
+// the permutation ends at the caller's scale: p2_finish is a subtract and a canonicalisation.  Scales, R = 2^32:
+//   in R | F1: 1, F2: R^-7, F3: R^-56, F4: R^-399 | partial rounds: R (entry from R^-2800), last group out: sigma |
+//   F5: sigma, F6: f(sigma), F7: f^2(sigma), F8: f^3(sigma) | out: R (+ F64_OFF).
 // Exact field identities throughout: digests equal the literal 29-round oracle's bit for bit (tests).
 // ---------------------------------------------------------------------------------------------------------
 constexpr uint32_t F64_OFF = 0x43380000u;                  // high word of 1.5 * 2^52
@@ -96,20 +99,36 @@ ZKH_HD void m4d(double& x0, double& x1, double& x2, double& x3) {
     const double t4 = fmad(t1, 4.0, t3), t5 = fmad(t0, 4.0, t2);
     x0 = t3 + t5; x1 = t5; x2 = t2 + t4; x3 = t4;
 }
+// One M_ext output T (an exact integer, already carrying F64_MAGIC) -> smont_reduce(T) + F64_OFF (wrapping)
+ZKH_HD uint32_t m_ext_f64_cell(double tm) {
+    const int64_t t = f64_bits(tm);
+    const int32_t m = (int32_t)((uint32_t)t * NEG_PINV);
+    return (uint32_t)((uint64_t)mad_i64_k(m, (int32_t)P, t) >> 32);
+}
+// The block products and the four column sums (each starting from F64_MAGIC) of M_ext over the LIVE leading cells; the
+// cells from LIVE on are zero and are neither read nor written.
+template <int LIVE>
+ZKH_HD void m_ext_f64_blocks(double (&d)[CELLS], double (&c)[4]) {
+    static_assert(LIVE % 4 == 0 && LIVE > 0 && LIVE <= CELLS, "whole 4-cell blocks");
+    c[0] = c[1] = c[2] = c[3] = F64_MAGIC;
+#pragma unroll
+    for (int i = 0; i < LIVE; i += 4) {
+        m4d(d[i], d[i + 1], d[i + 2], d[i + 3]);
+        c[0] += d[i]; c[1] += d[i + 1]; c[2] += d[i + 2]; c[3] += d[i + 3];
+    }
+}
+// s[DST_LO + k] = the reduced M_ext output of cell SRC_LO + k, k < N (SRC_LO and DST_LO name the same column: both = 0 mod 4)
+template <int LIVE, int SRC_LO, int DST_LO, int N>
+ZKH_HD void m_ext_f64_reduce(uint32_t (&s)[CELLS], const double (&d)[CELLS], const double (&c)[4]) {
+    static_assert(SRC_LO % 4 == 0 && DST_LO % 4 == 0 && SRC_LO + N <= CELLS && DST_LO + N <= CELLS, "column-aligned cell range");
+#pragma unroll
+    for (int k = 0; k < N; k++) s[DST_LO + k] = m_ext_f64_cell(SRC_LO + k < LIVE ? d[SRC_LO + k] + c[k % 4] : c[k % 4]);
+}
 // d: exact integers (|d_i| < P) -> s_i = smont_reduce(M_ext(d)_i) + F64_OFF (wrapping), |smont_reduce| <= P/2 + 64
 ZKH_HD void m_ext_f64(uint32_t (&s)[CELLS], double (&d)[CELLS]) {
-    double c0 = F64_MAGIC, c1 = F64_MAGIC, c2 = F64_MAGIC, c3 = F64_MAGIC;
-#pragma unroll
-    for (int i = 0; i < CELLS; i += 4) {
-        m4d(d[i], d[i + 1], d[i + 2], d[i + 3]);
-        c0 += d[i]; c1 += d[i + 1]; c2 += d[i + 2]; c3 += d[i + 3];
-    }
-#pragma unroll
-    for (int i = 0; i < CELLS; i++) {
-        const int64_t t = f64_bits(d[i] + (i % 4 == 0 ? c0 : i % 4 == 1 ? c1 : i % 4 == 2 ? c2 : c3));
-        const int32_t m = (int32_t)((uint32_t)t * NEG_PINV);
-        s[i] = (uint32_t)((uint64_t)mad_i64_k(m, (int32_t)P, t) >> 32);
-    }
+    double c[4];
+    m_ext_f64_blocks<CELLS>(d, c);
+    m_ext_f64_reduce<CELLS, 0, 0, CELLS>(s, d, c);
 }
 // t + (a mod P) for a 64-bit accumulator a = hi 2^32 + lo:  hi R + lo  (one multiply-add, one add)
 ZKH_HD uint64_t fold64(uint64_t a, uint64_t t) {
@@ -132,7 +151,18 @@ ZKH_HD int32_t sbox7_lazy(uint32_t v, uint32_t rcf) {
 // Host-side: all tables of the permutation from the canonical round constants and internal diagonal (consts.rs as data).
 inline uint32_t p2_mulm(uint32_t a, uint32_t b) { return (uint32_t)((uint64_t)a * b % P); }
 inline uint32_t p2_powm(uint32_t a, uint64_t e) { uint32_t r = 1; while (e) { if (e & 1) r = p2_mulm(r, a); a = p2_mulm(a, a); e >>= 1; } return r; }
-inline void poseidon2_partial_table(uint32_t* t, const uint32_t* rc_canonical, const uint32_t* diag_canonical) {
+// The exit scale of the partial rounds: the sigma with f^4(sigma) = R for f(lambda) = lambda^7 / R^7 (one full round).  f's
+// inverse is lambda -> (lambda R^7)^(1/7) = lambda^e R with e = 7^-1 mod (P - 1), which exists because P - 1 = 15 * 2^27.
+inline uint32_t p2_full_round_scale(uint32_t lambda) { return p2_mulm(p2_powm(lambda, 7), p2_powm(p2_powm(R1, P - 2), 7)); }
+inline uint32_t p2_exit_scale() {
+    uint64_t e = 0;
+    for (uint64_t k = 1; k < 7 && !e; k++) if ((k * (P - 1) + 1) % 7 == 0) e = (k * (P - 1) + 1) / 7;
+    uint32_t lambda = R1;
+    for (int f = 0; f < HALF_FULL; f++) lambda = p2_mulm(p2_powm(lambda, e), R1);
+    return lambda;
+}
+// Returns false (and leaves a table that must not be used) if the second half's forward scale chain does not end at R.
+inline bool poseidon2_partial_table(uint32_t* t, const uint32_t* rc_canonical, const uint32_t* diag_canonical) {
     Fp c1 = Fp::zero();
     for (int i = 0; i < CELLS; i++) {
         const Fp d = fp_encode(diag_canonical[i]);
@@ -141,10 +171,12 @@ inline void poseidon2_partial_table(uint32_t* t, const uint32_t* rc_canonical, c
     }
     t[3 * CELLS] = c1.v; t[3 * CELLS + 1] = fp_encode(23).v;
     for (int i = 0; i < 3 * CELLS; i++) t[P2_TAB_SIGNED + i] = (uint32_t)center(t[i]);
-    // scales as plain residues: lambda(k) = R^-k
+    // scales as plain residues: first half lambda(k) = R^-k; second half sigma, f(sigma), f^2(sigma), f^3(sigma), out R
     const uint32_t rinv = p2_powm(R1, P - 2);
     auto rneg = [&](uint64_t k) { return p2_powm(rinv, k); };
-    const uint32_t lam[2 * HALF_FULL] = {1u, rneg(7), rneg(56), rneg(399), R1, 1u, rneg(7), rneg(56)};
+    const uint32_t sigma = p2_exit_scale();
+    uint32_t lam[2 * HALF_FULL + 1] = {1u, rneg(7), rneg(56), rneg(399), sigma};
+    for (int f = HALF_FULL; f < 2 * HALF_FULL; f++) lam[f + 1] = p2_full_round_scale(lam[f]);
     for (int f = 0; f < 2 * HALF_FULL; f++) {
         const int round = f < HALF_FULL ? f : HALF_FULL + PARTIAL + (f - HALF_FULL);
         for (int i = 0; i < CELLS; i++) {
@@ -157,22 +189,34 @@ inline void poseidon2_partial_table(uint32_t* t, const uint32_t* rc_canonical, c
     for (int i = 0; i < 3 * CELLS; i++) t[P2_TAB_GROUP0 + i] = (uint32_t)center(p2_mulm(t[i], rho));
     t[P2_TAB_KAPPA] = (uint32_t)center(p2_mulm(rho, R1));     // cell 0 at the entry: smont(v, .) = v rho
     t[P2_TAB_KAPPA + 1] = p2_mulm(rho, R1);                   // group 0's A: mul_mod(sum v, .) = rho sum v
-    t[P2_TAB_KAPPA + 2] = (uint32_t)center(p2_powm(R1, 401)); // p2_finish: smont(v, .) = v R^400 = x R   (v = x R^-399)
-    t[P2_TAB_KAPPA + 3] = 0;
+    const uint32_t mu = p2_mulm(sigma, rinv);                 // the last group leaves its cells at sigma = mu R
+    t[P2_TAB_KAPPA + 2] = sigma;                              // last group's S2: mul_mod(S2, .) = mu S2
+    t[P2_TAB_KAPPA + 3] = p2_mulm(t[0], mu);                  // last group's d_0 mu
+    for (int i = 0; i < 3 * CELLS; i++) t[P2_TAB_EXIT + i] = (uint32_t)center(p2_mulm(t[i], mu));
+    return lam[2 * HALF_FULL] == R1;
 }
-// A cell of poseidon2_mix_raw's output -> canonical Montgomery word
-ZKH_HD uint32_t p2_finish(uint32_t v, const uint32_t* __restrict__ diag) {
-    return canon(smont((int32_t)(v - F64_OFF), (int32_t)diag[P2_TAB_KAPPA + 2]));
-}
+// A kept cell of poseidon2_mix_raw's output -> the nearly centred signed word (a valid input cell of the next permutation) ...
+ZKH_HD uint32_t p2_signed(uint32_t v) { return v - F64_OFF; }
+// ... -> the canonical Montgomery word
+ZKH_HD uint32_t p2_finish(uint32_t v) { return canon((int32_t)p2_signed(v)); }
 // rc: round constants stored as rc - P (two's complement words; the partial rounds read cell 0's); diag: the table above.
-// In: canonical Montgomery words.  Out: every cell as (x R^-399 nearly centred) + F64_OFF: p2_finish the ones you read.
-ZKH_HD void poseidon2_mix_raw(uint32_t (&s)[CELLS], const uint32_t* __restrict__ rc,
-                                                  const uint32_t* __restrict__ diag) {
+// In: Montgomery-scale words read as SIGNED, |s_i| < P: canonical words, or p2_signed() of an earlier output; the cells from
+// LIVE on are taken as zero without being read.  Out: the kept cells as (x R nearly centred, |.| <= P/2 + 64) + F64_OFF;
+// every other cell is unspecified (its last reduction is not computed).  The kept cells are
+//   SEL false: [KEEP_LO, KEEP_LO + KEEP_N), each in its own place;
+//   SEL true:  [0, KEEP_N) if `low`, else [KEEP_LO, KEEP_LO + KEEP_N), stored in s[KEEP_LO ...] either way.  `low` must be
+//              wave-uniform on the device: the two ranges share everything but the last KEEP_N reductions, which sit behind
+//              one scalar branch — a sponge with one call site keeps its capacity in interior blocks and its digest in the
+//              last one without a second copy of the permutation.
+template <int KEEP_LO, int KEEP_N, int LIVE, bool SEL>
+ZKH_HD void poseidon2_mix_core(uint32_t (&s)[CELLS], const uint32_t* __restrict__ rc, const uint32_t* __restrict__ diag, bool low) {
+    static_assert(!SEL || KEEP_LO >= KEEP_N, "the two selectable ranges do not overlap");
     const uint32_t* __restrict__ rcf = diag + P2_TAB_FULL;
-    double d[CELLS];
+    double d[CELLS], c[4];
 #pragma unroll
-    for (int i = 0; i < CELLS; i++) d[i] = (double)s[i];
-    m_ext_f64(s, d);
+    for (int i = 0; i < LIVE; i++) d[i] = (double)(int32_t)s[i];
+    m_ext_f64_blocks<LIVE>(d, c);
+    m_ext_f64_reduce<LIVE, 0, 0, CELLS>(s, d, c);
 #pragma unroll 1
     for (int r = 0; r < HALF_FULL; r++) {
 #pragma unroll
@@ -195,13 +239,19 @@ ZKH_HD void poseidon2_mix_raw(uint32_t (&s)[CELLS], const uint32_t* __restrict__
     // keeps every accumulator an unsigned word pair.
     // Group 0 reads cells at the entry scale: its rows for the terms in s_i
     // are d^k rho instead of d^k and its plain sum is multiplied by rho once (same bounds: |s_i| <= P/2 + 64 there).
+    // The last group writes cells at the exit scale sigma = mu R: the three rows of its cell update are mu d^k, and S2 is
+    // multiplied by mu once, which serves cell 0 and the accumulator start of the update alike.  (S2 must enter the update
+    // as center(mu S2) R1 with R1 < 2^28; a centred mu R as its multiplier would take the bound from P 2^27 to P^2 / 4.)
     const uint32_t* __restrict__ pc = diag;                                   // unsigned rows + c1 + 23
     const int32_t* __restrict__ pcs = (const int32_t*)(diag + P2_TAB_SIGNED); // centred d, d^2, d^3
     constexpr int64_t BIAS = (int64_t)((uint64_t)P << 32);                    // = 0 mod P; sums wrap as unsigned
     constexpr int32_t R1S = (int32_t)R1;                                      // 2^32 mod P = 268435454 < 2^28
 #pragma unroll 1
     for (int grp = 0; grp < PARTIAL / 3; grp++, round += 3) {
+        const bool last = grp == PARTIAL / 3 - 1;
         const int32_t* __restrict__ pcg = grp == 0 ? (const int32_t*)(diag + P2_TAB_GROUP0) : pcs;   // rows for terms in s_i
+        const int32_t* __restrict__ pcu = last ? (const int32_t*)(diag + P2_TAB_EXIT) : pcs;         // rows of the cell update
+        const int32_t* __restrict__ pcu3 = last ? pcu : pcg;                                         // its d^3 row
         // A: 12 + 11 terms s_i * R (|sum| <= 12 P 2^28 = 0.75 P 2^32 < bias)
         int64_t ta = BIAS, tb = BIAS;
 #pragma unroll
@@ -225,10 +275,11 @@ ZKH_HD void poseidon2_mix_raw(uint32_t (&s)[CELLS], const uint32_t* __restrict__
         }
         const uint32_t d0 = pc[0], c1 = pc[3 * CELLS], m23 = pc[3 * CELLS + 1];
         const uint32_t z0 = sbox7_rc(s[0], rc[round * CELLS]);
-        // S0 = z0 + A:  z0 R + 2 (1.75 P 2^28 + 2^32)  <  P 2^32
-        uint32_t S0 = mont_reduce(fold64((uint64_t)tb, fold64((uint64_t)ta, (uint64_t)z0 * R1)));
+        uint32_t S0;
         if (grp == 0)      // the cells came in at the entry scale: S0 = z0 + rho sum
             S0 = add_mod(z0, mul_mod(add_mod(mont_reduce_wide((uint64_t)ta), mont_reduce_wide((uint64_t)tb)), diag[P2_TAB_KAPPA + 1]));
+        else               // S0 = z0 + A:  z0 R + 2 (1.75 P 2^28 + 2^32)  <  P 2^32
+            S0 = mont_reduce(fold64((uint64_t)tb, fold64((uint64_t)ta, (uint64_t)z0 * R1)));
         const uint32_t s0a = mont_reduce_wide(((uint64_t)S0 << 32) + (uint64_t)d0 * z0);
         const uint32_t z1 = sbox7_rc(s0a, rc[(round + 1) * CELLS]);
         // S1 = z1 + 23 S0 + D1:  z1 R + m23 S0 + 6 (1.94 P 2^28 + 2^32)  <  (0.0625 + 0.47 + 0.73) P 2^32  <  2 P 2^32
@@ -242,31 +293,48 @@ ZKH_HD void poseidon2_mix_raw(uint32_t (&s)[CELLS], const uint32_t* __restrict__
         uint64_t t2 = (uint64_t)m23 * S1 + (uint64_t)c1 * S0 + (uint64_t)z2 * R1;
 #pragma unroll
         for (int c = 0; c < 6; c++) t2 = fold64(a2[c], t2);
-        const uint32_t S2 = mont_reduce_wide(t2);
-        s[0] = mont_reduce_wide(((uint64_t)S2 << 32) + (uint64_t)d0 * z2);
+        uint32_t S2 = mont_reduce_wide(t2), d0u = d0;
+        if (last) { S2 = mul_mod(S2, diag[P2_TAB_KAPPA + 2]); d0u = diag[P2_TAB_KAPPA + 3]; }      // mu S2, mu d_0
+        s[0] = mont_reduce_wide(((uint64_t)S2 << 32) + (uint64_t)d0u * z2);
         // cells 1..23: S2 rides in the accumulator as S2 R, so the signed reduction's output IS the new cell:
-        // |S2 R + d S1 + d^2 S0 + d^3 s| <= (P-1)/2 R + 2 ((P-1)/2)^2 + (P-1)(P-1)/2 = (P-1)(P + 2^27 - 2) < P 2^31.
+        // |S2 R + d S1 + d^2 S0 + d^3 s| <= (P-1)/2 R + 2 ((P-1)/2)^2 + (P-1)(P-1)/2 = (P-1)(P + 2^27 - 2) < P 2^31
+        // (the same for the last group's mu S2 and centred mu d^k).
         const int32_t S0c = center(S0), S1c = center(S1);
         const int64_t acc0 = mad_i64_k(center(S2), R1S, 0);
 #pragma unroll
         for (int i = 1; i < CELLS; i++)
-            s[i] = (uint32_t)smont_reduce(mad_i64_k((int32_t)s[i], pcg[2 * CELLS + i],
-                                                    mad_i64_k(S0c, pcs[CELLS + i], mad_i64_k(S1c, pcs[i], acc0))));   // in (-P, P)
+            s[i] = (uint32_t)smont_reduce(mad_i64_k((int32_t)s[i], pcu3[2 * CELLS + i],
+                                                    mad_i64_k(S0c, pcu[CELLS + i], mad_i64_k(S1c, pcu[i], acc0))));   // in (-P, P)
     }
 #pragma unroll
     for (int i = 1; i < CELLS; i++) s[i] = canon((int32_t)s[i]);
 #pragma unroll 1
-    for (int r = HALF_FULL; r < 2 * HALF_FULL; r++) {
+    for (int r = HALF_FULL; r < 2 * HALF_FULL - 1; r++) {
 #pragma unroll
         for (int i = 0; i < CELLS; i++) d[i] = (double)sbox7_lazy(s[i], rcf[r * CELLS + i]);
         m_ext_f64(s, d);
     }
+    // F8, peeled: every block product and column sum, but the last add and the reduction only of the cells the caller reads
+#pragma unroll
+    for (int i = 0; i < CELLS; i++) d[i] = (double)sbox7_lazy(s[i], rcf[(2 * HALF_FULL - 1) * CELLS + i]);
+    m_ext_f64_blocks<CELLS>(d, c);
+    if (SEL && low) m_ext_f64_reduce<CELLS, 0, KEEP_LO, KEEP_N>(s, d, c);
+    else            m_ext_f64_reduce<CELLS, KEEP_LO, KEEP_LO, KEEP_N>(s, d, c);
+}
+// The kept-cell forms the kernels call: cells [KEEP_LO, KEEP_LO + KEEP_N) of the output, from the LIVE leading cells of the input.
+template <int KEEP_LO = 0, int KEEP_N = CELLS, int LIVE = CELLS>
+ZKH_HD void poseidon2_mix_raw(uint32_t (&s)[CELLS], const uint32_t* __restrict__ rc, const uint32_t* __restrict__ diag) {
+    poseidon2_mix_core<KEEP_LO, KEEP_N, LIVE, false>(s, rc, diag, false);
+}
+// One sponge block: s[RATE ...] receives the capacity (cells 16..23), or in the last block the digest (cells 0..7).
+ZKH_HD void poseidon2_mix_sponge(uint32_t (&s)[CELLS], const uint32_t* __restrict__ rc, const uint32_t* __restrict__ diag, bool last_block) {
+    poseidon2_mix_core<RATE, OUT, CELLS, true>(s, rc, diag, last_block);
 }
 // The permutation on canonical Montgomery words, in and out (host sponges; kernels that read few cells use the raw form).
 ZKH_HD void poseidon2_mix(uint32_t (&s)[CELLS], const uint32_t* __restrict__ rc, const uint32_t* __restrict__ diag) {
     poseidon2_mix_raw(s, rc, diag);
 #pragma unroll
-    for (int i = 0; i < CELLS; i++) s[i] = p2_finish(s[i], diag);
+    for (int i = 0; i < CELLS; i++) s[i] = p2_finish(s[i]);
 }
 
 }  // namespace zkh

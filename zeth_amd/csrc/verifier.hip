@@ -15,9 +15,10 @@ using namespace zkh;
 namespace {
 
 struct Tables { uint32_t rc[24 * 29]; uint32_t pc[ZKH_P2_PTAB]; };
-void make_tables(Tables& t, const uint32_t* rc, const uint32_t* diag) {
+const char* make_tables(Tables& t, const uint32_t* rc, const uint32_t* diag) {
     for (int i = 0; i < 24 * 29; i++) t.rc[i] = fp_encode(rc[i]).v - P;
-    poseidon2_partial_table(t.pc, rc, diag);
+    ZKH_REQUIRE(poseidon2_partial_table(t.pc, rc, diag), "poseidon2 tables: the full rounds' scale chain does not end at R");
+    return nullptr;
 }
 struct Digest {
     uint32_t w[8];
@@ -176,7 +177,7 @@ Fp4 fold_eval(Fp4 (&v)[16], Fp4 mix, Fp inv_wk, const uint32_t (&rou_rev)[28]) {
 extern "C" const char* zkh_poseidon2_mix_host(const uint32_t* rc, const uint32_t* diag, uint32_t* states, size_t count) {
     ZKH_REQUIRE(states || !count, "poseidon2_mix_host: null states");
     std::unique_ptr<Tables> tab(new Tables());
-    make_tables(*tab, rc ? rc : ZKH_P2_ROUND_CONSTANTS, diag ? diag : ZKH_P2_M_INT_DIAG);
+    ZKH_TRY(make_tables(*tab, rc ? rc : ZKH_P2_ROUND_CONSTANTS, diag ? diag : ZKH_P2_M_INT_DIAG));
     for (size_t k = 0; k < count; k++) {
         uint32_t s[CELLS];
         for (int i = 0; i < CELLS; i++) { s[i] = states[k * CELLS + i]; ZKH_REQUIRE(s[i] < P, "poseidon2_mix_host: unreduced word"); }
@@ -192,7 +193,7 @@ extern "C" const char* zkh_receipt_claim(const zkh_circuit* c, const uint32_t* s
     const size_t out_size = c->global_size[GLOBAL_OUT];
     ZKH_REQUIRE(seal_words > out_size, "receipt_claim: seal truncated (header)");
     std::unique_ptr<Tables> tab(new Tables);
-    make_tables(*tab, rc_canonical ? rc_canonical : ZKH_P2_ROUND_CONSTANTS, diag_canonical ? diag_canonical : ZKH_P2_M_INT_DIAG);
+    ZKH_TRY(make_tables(*tab, rc_canonical ? rc_canonical : ZKH_P2_ROUND_CONSTANTS, diag_canonical ? diag_canonical : ZKH_P2_M_INT_DIAG));
     Hasher hasher{tab.get()};
     std::vector<uint32_t> in(seal, seal + out_size + 1);
     in.insert(in.end(), control_root, control_root + 8);
@@ -209,7 +210,7 @@ extern "C" const char* zkh_verify_segment(const zkh_circuit* c, const uint32_t* 
     // selectors, which switch every gated constraint off) and "prove" an arbitrary output
     ZKH_REQUIRE(control_root, "verify_segment: no control root given (the expected code commitment for this circuit and po2)");
     std::unique_ptr<Tables> tab(new Tables);
-    make_tables(*tab, rc_canonical ? rc_canonical : ZKH_P2_ROUND_CONSTANTS, diag_canonical ? diag_canonical : ZKH_P2_M_INT_DIAG);
+    ZKH_TRY(make_tables(*tab, rc_canonical ? rc_canonical : ZKH_P2_ROUND_CONSTANTS, diag_canonical ? diag_canonical : ZKH_P2_M_INT_DIAG));
     Hasher hasher{tab.get()};
     ReadIop io{seal, seal_words, 0, &hasher};
     uint32_t rou_fwd[28], rou_rev[28];
