@@ -1,4 +1,4 @@
-"""Derived lookup multiplicities (ZKA1 version 2; zeth_amd/circuits/logup.py, csrc/accumulate.hip): the builder and parser of the
+"""Derived lookup multiplicities (ZKA1 version 2; zeth_amd/circuits/logup.py, csrc/arguments.hip): the builder and parser of the
 version-2 blob, the rules a derived term must follow (in Python and in the C validator, on a GPU-less circuit), SYN-LOOKUP-derived
 against the plain circuit, and the host reference of the count.  No GPU."""
 import numpy as np

@@ -1,4 +1,4 @@
-"""Derived lookup multiplicities on the GPU (zkh_derive_multiplicities, csrc/accumulate.hip): word for word against the host reference
+"""Derived lookup multiplicities on the GPU (zkh_derive_multiplicities, csrc/multiplicities.hip): word for word against the host reference
 over random argument sets on both sides of the LDS / global count, SYN-LOOKUP-derived at po2 20 against the host count and sealed
 byte-identically to the plain circuit, the refusals (data unchanged, nothing sealed), the native session, WIDE (a 2^16-row table) and
 determinism."""

@@ -1,4 +1,4 @@
-"""Derived sorted copies (ZKA1 version 3; zeth_amd/circuits/logup.py, csrc/sort.hip, csrc/accumulate.hip's validator): the builder and
+"""Derived sorted copies (ZKA1 version 3; zeth_amd/circuits/logup.py, csrc/sort.hip, csrc/arguments.hip's validator): the builder and
 parser of the version-3 blob, the rules a sorted copy must follow (in the builder, the parser and the C validator on a GPU-less
 circuit), SYN-LOOKUP-sorted against the plain circuit, and the host reference of the sort.  No GPU."""
 import numpy as np

@@ -35,6 +35,12 @@ def _witness_parity(hal, oracle, desc, po2, zk):
     return circ, oc, (code, data, accum), (ocode, odata, oacc), (out, mix)
 
 
+def test_witness_parity_two_rounds_of_chunk_totals(hal, oracle):
+    """2^21 - 1994 active rows are 2047 prefix-sum chunks: the totals kernel runs its 1024-wide loop twice, with a carry between
+    (the smallest shape that does; the next below, po2 20, has 1023 chunks)"""
+    _witness_parity(hal, oracle, syn_air.syn_small(), 21, 1994)
+
+
 @pytest.mark.parametrize("shape,po2,zk", [("tiny", 9, 100), ("small", 12, 1994)])
 def test_witgen_and_eval_check_parity(hal, oracle, shape, po2, zk):
     desc = SHAPES[shape]()

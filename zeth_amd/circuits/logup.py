@@ -4,7 +4,7 @@ One source gives two artefacts:
   * the ordinary ZKC1 description (desc.py) whose constraints check the accum columns — the prover, the eval_check generator,
     the bound verifier and both verifiers read it unchanged;
   * the ZKA1 argument blob that tells the library's built-in accumulate (csrc/accumulate.hip, zkh_accumulate) how to fill those
-    columns from (code, data, mix).
+    columns from (code, data, mix).  csrc/arguments.hip decodes it into the mirror of `Arguments` below and checks the same rules.
 
 A TERM of accum Fp4 column c has the value on row r
 

@@ -1,0 +1,189 @@
+// arguments.hip — the ZKA1 argument blob (layout: zeth_amd/circuits/logup.py; DESIGN.md §2 ARGUMENTS): its decoding into
+// zkh::Arguments, the rules a circuit's arguments keep, and the entry points that attach them to a circuit and ask what they derive.
+// decode_arguments is the only code that knows the blob's words; everything else, here and in the consumers, reads decoded terms.
+#include "arguments.h"
+
+#include <algorithm>
+
+using namespace zkh;
+
+namespace {
+
+// Term word 7, the flags.  Version 1 leaves it unread.  Version 2: bit 0 = "multiplicity derived by the library"
+// (zkh_derive_multiplicities); every other bit is reserved.  Version 3 adds bit 1 = "this term D is a sorted copy derived by the
+// library" (zkh_derive_sorted) of its source term S (bits 16..31), by nkeys (bits 4..6) tuple positions (2 bits each from bit 8, most
+// significant key first); bits 2, 3, 7, the position fields of unused keys and, without bit 1, everything above bit 0 are reserved.
+// A reserved bit is recorded, not refused: the rules refuse it where they reach the term (flag_word_rule), after the circuit-shape checks.
+const char* decode_arguments(const uint32_t* a, size_t words, Arguments* out) {
+    ZKH_REQUIRE(words >= ARGS_HEADER && a[0] == ARGS_MAGIC && a[1] >= 1 && a[1] <= 3, "set_arguments: not a ZKA1 (version 1) argument blob");
+    const uint32_t n_terms = a[5];
+    ZKH_REQUIRE(words == ARGS_HEADER + (size_t)TERM_WORDS * n_terms, "set_arguments: %zu words for %u terms", words, n_terms);
+    out->version = a[1]; out->k = a[2]; out->alpha = a[3]; out->beta = a[4];
+    out->terms.assign(n_terms, Term{});
+    for (uint32_t i = 0; i < n_terms; i++) {
+        const uint32_t* r = a + ARGS_HEADER + (size_t)TERM_WORDS * i;
+        Term& t = out->terms[i];
+        t.col = r[0]; t.neg = r[1]; t.sel = r[2]; t.mg = r[3]; t.mc = r[4]; t.tag = r[5]; t.w = r[6];
+        for (uint32_t e = 0; e < MAX_TUPLE; e++) { t.tg[e] = r[8 + 2 * e]; t.tc[e] = r[9 + 2 * e]; }
+        const uint32_t f = t.flags = out->version >= 2 ? r[7] : 0;
+        t.derive = f & 1;
+        t.reserved = f > 1;
+        if (out->version == 3) {
+            t.sorted = f & 2;
+            t.sorted_from = f >> 16;
+            t.nkeys = (f >> 4) & 7;
+            for (uint32_t j = 0; j < 4; j++) t.key[j] = (f >> (8 + 2 * j)) & 3;
+            t.reserved = (f & 0x8c) || (!t.sorted && f > 1);
+            for (uint32_t j = t.nkeys; j < 4; j++) t.reserved |= t.key[j] != 0;
+        }
+    }
+    return nullptr;
+}
+
+const char* flag_word_rule(const Arguments& a, uint32_t i) {
+    const Term& t = a.terms[i];
+    if (!t.reserved) return nullptr;
+    if (a.version == 3)
+        return make_err("set_arguments: term %u: word 7 is %#x (bit 0: derived multiplicity; bit 1: sorted copy, with its keys in bits 4..15 "
+                        "and its source term in bits 16..31; the other bits are reserved)", i, t.flags);
+    return make_err("set_arguments: term %u: word 7 is %u (bit 0: derived multiplicity; the other bits are reserved)", i, t.flags);
+}
+
+bool in_tuple(const Term& t, uint32_t width, uint32_t g, uint32_t col) {       // (g, col) among the first `width` tuple columns of t
+    for (uint32_t e = 0; e < width; e++)
+        if (t.tg[e] == g && t.tc[e] == col) return true;
+    return false;
+}
+
+// logup.check_derived: the first derived term that breaks a rule.  A derived term is (a) of sign -1, (b) with a data-group
+// multiplicity column (c) that no tuple and no other term's multiplicity names, and (d) every other term of its tag is a lookup of
+// sign +1.
+const char* check_derived(const Arguments& a) {
+    const uint32_t n_terms = (uint32_t)a.terms.size();
+    for (uint32_t i = 0; i < n_terms; i++) {
+        const Term& t = a.terms[i];
+        ZKH_TRY(flag_word_rule(a, i));
+        if (!t.derive) continue;
+        ZKH_REQUIRE(t.neg == 1, "set_arguments: term %u: a derived multiplicity needs sign -1 (the table side of a lookup)", i);
+        ZKH_REQUIRE(t.mg == GROUP_DATA, "set_arguments: term %u: a derived multiplicity must be a data-group column", i);
+        for (uint32_t j = 0; j < n_terms; j++) {
+            const Term& u = a.terms[j];
+            ZKH_REQUIRE(j == i || !(u.mg == GROUP_DATA && u.mc == t.mc), "set_arguments: term %u: its derived multiplicity column (data %u) is "
+                        "also the multiplicity of term %u", i, t.mc, j);
+            ZKH_REQUIRE(!in_tuple(u, u.w, GROUP_DATA, t.mc), "set_arguments: term %u: its derived multiplicity column (data %u) is read by the "
+                        "tuple of term %u", i, t.mc, j);
+            ZKH_REQUIRE(u.tag != t.tag || u.derive || u.neg == 0, "set_arguments: term %u: term %u of its tag %u has sign -1 and is not derived "
+                        "(the lookups of a derived tag have sign +1)", i, j, t.tag);
+        }
+    }
+    return nullptr;
+}
+
+// logup.check_sorted: the first sorted-copy term D that breaks a rule.  With S its source: (a) D has sign -1 and no derived
+// multiplicity, S is another term of sign +1 without a flag and the source of no other copy; (b) the same tag, tuple width and
+// selector, both multiplicities the constant 1; (c) D's tuple columns are pairwise distinct data columns that no other tuple and no
+// multiplicity names; (d) 1..3 key positions, distinct and below the width; (e) no derived multiplicity in D's tag.
+const char* check_sorted(const Arguments& a) {
+    const uint32_t n_terms = (uint32_t)a.terms.size();
+    for (uint32_t i = 0; i < n_terms; i++) {
+        const Term& t = a.terms[i];
+        ZKH_TRY(flag_word_rule(a, i));
+        if (!t.sorted) continue;
+        const uint32_t s = t.sorted_from, w = t.w;
+        ZKH_REQUIRE(t.neg == 1, "set_arguments: term %u: a sorted copy needs sign -1 (the permuted side of a multiset equality)", i);
+        ZKH_REQUIRE(!t.derive, "set_arguments: term %u: a sorted copy cannot also have a derived multiplicity", i);
+        ZKH_REQUIRE(s != i && s < n_terms, "set_arguments: term %u: its source term %u is not another term of the arguments", i, s);
+        const Term& u = a.terms[s];
+        ZKH_REQUIRE(u.neg == 0, "set_arguments: term %u: its source term %u needs sign +1", i, s);
+        ZKH_REQUIRE(u.flags == 0, "set_arguments: term %u: its source term %u is itself derived or a sorted copy", i, s);
+        for (uint32_t j = 0; j < n_terms; j++)
+            ZKH_REQUIRE(j == i || !a.terms[j].sorted || a.terms[j].sorted_from != s, "set_arguments: term %u: its source term %u is also the "
+                        "source of term %u", i, s, j);
+        ZKH_REQUIRE(u.tag == t.tag && u.w == w && u.sel == t.sel, "set_arguments: term %u: its source term %u has another tag, tuple width or selector", i, s);
+        ZKH_REQUIRE(t.mg == NONE && u.mg == NONE, "set_arguments: term %u: a sorted copy and its source term %u have the constant multiplicity 1", i, s);
+        for (uint32_t e = 0; e < w; e++) {
+            const uint32_t g = t.tg[e], col = t.tc[e];
+            ZKH_REQUIRE(g == GROUP_DATA, "set_arguments: term %u: tuple column (%u, %u) of a sorted copy must be a data-group column", i, g, col);
+            ZKH_REQUIRE(!in_tuple(t, e, g, col), "set_arguments: term %u: its sorted column (data %u) appears twice in its tuple", i, col);
+            for (uint32_t j = 0; j < n_terms; j++) {
+                const Term& x = a.terms[j];
+                ZKH_REQUIRE(j == i || !in_tuple(x, x.w, g, col), "set_arguments: term %u: its sorted column (data %u) is read by the tuple of "
+                            "term %u", i, col, j);
+                ZKH_REQUIRE(!(x.mg == g && x.mc == col), "set_arguments: term %u: its sorted column (data %u) is the multiplicity of term %u", i, col, j);
+            }
+        }
+        const uint32_t kmax = w < MAX_SORT_KEYS ? w : MAX_SORT_KEYS;
+        ZKH_REQUIRE(t.nkeys >= 1 && t.nkeys <= kmax, "set_arguments: term %u: %u sort keys (1..%u: at most %u, and no more than the tuple width %u)", i,
+                    t.nkeys, kmax, MAX_SORT_KEYS, w);
+        for (uint32_t j = 0; j < t.nkeys; j++) {
+            bool ok = t.key[j] < w;
+            for (uint32_t j2 = 0; j2 < j; j2++) ok &= t.key[j2] != t.key[j];
+            ZKH_REQUIRE(ok, "set_arguments: term %u: its sort key positions must be distinct and below the tuple width %u", i, w);
+        }
+        for (uint32_t j = 0; j < n_terms; j++)
+            ZKH_REQUIRE(!(a.terms[j].derive && a.terms[j].tag == t.tag), "set_arguments: term %u: term %u of its tag %u has a derived multiplicity", i, j, t.tag);
+    }
+    return nullptr;
+}
+
+// the arguments against the circuit's shape, then the rules of sorted copies, then those of derived multiplicities
+const char* check_arguments(const zkh_circuit* c, const Arguments& a) {
+    const uint32_t k = a.k;
+    ZKH_REQUIRE(k >= 1 && 4ull * k == c->group_size[GROUP_ACCUM], "set_arguments: %u accum Fp4 columns, the circuit's accum group is %u wide",
+                k, c->group_size[GROUP_ACCUM]);
+    const uint32_t mix = c->global_size[GLOBAL_MIX];
+    ZKH_REQUIRE((uint64_t)a.alpha + 4 <= mix && (uint64_t)a.beta + 4 <= mix, "set_arguments: alpha / beta at mix words %u / %u, the circuit has %u",
+                a.alpha, a.beta, mix);
+    auto is_column = [&](uint32_t g, uint32_t col) { return (g == GROUP_CODE || g == GROUP_DATA) && col < c->group_size[g]; };
+    std::vector<uint32_t> per_col(k, 0);
+    uint32_t prev = 0;
+    for (uint32_t i = 0; i < a.terms.size(); i++) {
+        const Term& t = a.terms[i];
+        ZKH_REQUIRE(t.col < k && t.col >= prev, "set_arguments: term %u: accum column %u (columns 0..%u, terms sorted by column)", i, t.col, k - 1);
+        prev = t.col;
+        ZKH_REQUIRE(++per_col[t.col] <= MAX_TERMS, "set_arguments: accum column %u has more than %u terms (the degree bound)", t.col, MAX_TERMS);
+        ZKH_REQUIRE(t.neg <= 1 && t.tag < P, "set_arguments: term %u: sign word %u / tag %u", i, t.neg, t.tag);
+        ZKH_REQUIRE(t.sel == NONE || t.sel < c->group_size[GROUP_CODE], "set_arguments: term %u: selector %u is not a code column", i, t.sel);
+        ZKH_REQUIRE(t.mg == NONE || is_column(t.mg, t.mc), "set_arguments: term %u: multiplicity column (%u, %u) is not a code or data column", i,
+                    t.mg, t.mc);
+        ZKH_REQUIRE(t.w >= 1 && t.w <= MAX_TUPLE, "set_arguments: term %u: tuple width %u (1..%u)", i, t.w, MAX_TUPLE);
+        for (uint32_t e = 0; e < t.w; e++)
+            ZKH_REQUIRE(is_column(t.tg[e], t.tc[e]), "set_arguments: term %u: tuple column (%u, %u) is not a code or data column", i, t.tg[e], t.tc[e]);
+    }
+    for (uint32_t col = 0; col < k; col++) ZKH_REQUIRE(per_col[col] >= 1, "set_arguments: accum column %u has no terms", col);
+    if (a.version == 3) ZKH_TRY(check_sorted(a));
+    return a.version >= 2 ? check_derived(a) : nullptr;
+}
+
+}  // namespace
+
+const char* zkh::trace_rows(const char* who, const zkh_circuit* c, size_t po2, size_t zk_cycles, const zkh_buf* code, const zkh_buf* data,
+                            const zkh_buf* accum, size_t* n, uint32_t* A) {
+    ZKH_REQUIRE(po2 >= 1 && po2 <= 24, "%s: po2 %zu out of range", who, po2);
+    *n = (size_t)1 << po2;
+    ZKH_REQUIRE(zk_cycles < *n, "%s: zk_cycles %zu leaves no active row at po2 %zu", who, zk_cycles, po2);
+    *A = (uint32_t)(*n - zk_cycles);
+    ZKH_REQUIRE(code->len == (size_t)c->group_size[GROUP_CODE] * *n && data->len == (size_t)c->group_size[GROUP_DATA] * *n &&
+                (!accum || accum->len == (size_t)c->group_size[GROUP_ACCUM] * *n), "%s: buffer shape mismatch", who);
+    return nullptr;
+}
+
+extern "C" const char* zkh_circuit_set_arguments(zkh_circuit* c, const uint32_t* blob, size_t words) {
+    ZKH_REQUIRE(c && (blob || !words), "set_arguments: null argument");
+    if (!words) { c->args.reset(); return nullptr; }
+    auto a = std::make_shared<Arguments>();
+    ZKH_TRY(decode_arguments(blob, words, a.get()));
+    ZKH_TRY(check_arguments(c, *a));
+    c->args = std::move(a);
+    return nullptr;
+}
+
+extern "C" int zkh_circuit_has_arguments(const zkh_circuit* c) { return c && c->args; }
+
+extern "C" int zkh_circuit_derives_multiplicities(const zkh_circuit* c) {
+    return c && c->args && std::any_of(c->args->terms.begin(), c->args->terms.end(), [](const Term& t) { return t.derive; });
+}
+
+extern "C" int zkh_circuit_derives_sorted(const zkh_circuit* c) {
+    return c && c->args && std::any_of(c->args->terms.begin(), c->args->terms.end(), [](const Term& t) { return t.sorted; });
+}

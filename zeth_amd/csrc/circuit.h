@@ -3,6 +3,7 @@
 // (un-vendored; /root/reference/Cargo.lock:5393); blob layout: zeth_amd/circuits/desc.py.
 #pragma once
 #include <cstdint>
+#include <memory>
 #include <vector>
 
 #include "common.h"
@@ -60,6 +61,7 @@ __device__ __forceinline__ zkh::Fp4 ext_add_base(const zkh::Fp4& x, uint32_t v) 
 __device__ __forceinline__ zkh::Fp4 ext_sub_base(const zkh::Fp4& x, uint32_t v) {
     return zkh::Fp4(x.c[0] - zkh::Fp::raw(v), x.c[1], x.c[2], x.c[3]);
 }
+struct Arguments;                    // arguments.h
 typedef void (*eval_check_launch_fn)(const EvalCheckArgs&, hipStream_t);
 // A circuit's generated eval_check: n_parts kernels over disjoint constraint ranges, launched back to back on one stream;
 // part 0 writes `check`, the others add their share (circuits/codegen.py).
@@ -75,6 +77,9 @@ const CompiledEvalCheck* find_compiled_eval_check(uint64_t desc_hash);
 uint64_t desc_hash64(const uint32_t* words, size_t n);
 // inclusive prefix sum (mod P) of the first A words of a device column, in place; *last_out (device) = the grand total (circuit.hip)
 const char* prefix_sum_column(zkh_ctx* ctx, uint32_t* col, uint32_t A, uint32_t* last_out);
+// the same over `planes` columns n words apart in one set of launches; last_out[plane] = the plane's grand total; `what` names the
+// caller in a launch error
+const char* prefix_sum_planes(zkh_ctx* ctx, const char* what, uint32_t* cols, uint32_t planes, size_t n, uint32_t A, uint32_t* last_out);
 
 // device program for the generic interpreter (slots allocated on the host by liveness).  op = opcode | kind(a) << 8 |
 // kind(b) << 11 | (dst is Fp4) << 14; operand kinds: taps, constants and globals are operands, not slots, so a tap that
@@ -116,9 +121,9 @@ struct zkh_circuit {
     uint32_t n_fp_slots, n_mix_slots, n_mix_pows, ret_slot;   // n_mix_slots: 16-byte slots (mix totals and Fp4-valued values)
     uint32_t* d_prog;     // device copy of prog
     uint32_t* d_taps;     // device copy of taps (group, offset, back)
-    // ZKA1 argument blob (zkh_circuit_set_arguments; zeth_amd/circuits/logup.py): what zkh_accumulate builds the accum group from.
-    // Empty = the circuit has no arguments.
-    std::vector<uint32_t> args;
+    // the decoded ZKA1 arguments (zkh_circuit_set_arguments, arguments.hip; zeth_amd/circuits/logup.py): what zkh_accumulate builds
+    // the accum group from.  Null = the circuit has no arguments.
+    std::shared_ptr<const zkh::Arguments> args;
 };
 
 // Circuits whose segments chain: SYN-C (kind 1, out = (post, 0, 0, 0, pre): 5 words) and SYN-S (zeth_amd/circuits/syn_air.py

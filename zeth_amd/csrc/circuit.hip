@@ -6,6 +6,7 @@
 // /root/reference/crates/host/src/lib.rs:137.
 #include "circuit.h"
 #include "poseidon2.h"
+#include "scan.h"
 #include "../../include/zkh_poseidon2_consts.h"
 
 #include <algorithm>
@@ -183,55 +184,39 @@ __global__ __launch_bounds__(1024) void k_syn_chain_contrib(uint32_t* out, const
     }
     if (t == 0) out[i] = part[0];
 }
-// inclusive prefix sum (mod P) of the first A words of a column, three-level: per-1024-chunk scans + chunk totals,
-// scan of the totals (one workgroup), carry add.  (witgen, reported separately from the seal)
-__global__ __launch_bounds__(1024) void k_prefix_sum_chunks(uint32_t* col, uint32_t A, uint32_t* totals) {
+// inclusive prefix sum (mod P) of the first A words of every plane (plane = blockIdx.y, planes n words apart), three-level:
+// per-1024-chunk scans + chunk totals, scan of each plane's totals (one workgroup), carry add.
+__global__ __launch_bounds__(1024) void k_prefix_sum_chunks(uint32_t* cols, uint32_t n, uint32_t A, uint32_t* totals, uint32_t chunks) {
     __shared__ uint32_t buf[2][1024];
-    const uint32_t t = threadIdx.x, i = blockIdx.x * 1024 + t;
-    buf[0][t] = i < A ? col[i] : 0;
-    __syncthreads();
-    int cur = 0;
-    for (uint32_t d = 1; d < 1024; d <<= 1) {
-        uint32_t v = buf[cur][t];
-        if (t >= d) v = add_mod(v, buf[cur][t - d]);
-        buf[cur ^ 1][t] = v;
-        cur ^= 1;
-        __syncthreads();
-    }
-    if (i < A) col[i] = buf[cur][t];
-    if (t == 1023 && totals) totals[blockIdx.x] = buf[cur][t];
+    uint32_t* col = cols + (size_t)blockIdx.y * n;
+    const uint32_t i = blockIdx.x * 1024 + threadIdx.x;
+    const uint32_t v = block_scan<1024>(i < A ? col[i] : 0, buf, AddMod());
+    if (i < A) col[i] = v;
+    if (threadIdx.x == 1023) totals[(size_t)blockIdx.y * chunks + blockIdx.x] = v;
 }
-// single workgroup over the (<= 2^14) chunk totals; also emits the grand total = s[A-1]
-__global__ __launch_bounds__(1024) void k_prefix_sum_fp(uint32_t* col, uint32_t A, uint32_t* last_out) {
+// one workgroup per plane over its (<= 2^14) chunk totals; last[plane] = the plane's grand total s[A-1]
+__global__ __launch_bounds__(1024) void k_prefix_sum_totals(uint32_t* totals, uint32_t chunks, uint32_t* last) {
     __shared__ uint32_t buf[2][1024];
     __shared__ uint32_t carry_s;
+    uint32_t* col = totals + (size_t)blockIdx.y * chunks;
     const uint32_t t = threadIdx.x;
     if (t == 0) carry_s = 0;
     __syncthreads();
-    for (uint32_t base = 0; base < A; base += 1024) {
+    for (uint32_t base = 0; base < chunks; base += 1024) {
         const uint32_t i = base + t;
-        buf[0][t] = i < A ? col[i] : 0;
-        __syncthreads();
-        int cur = 0;
-        for (uint32_t d = 1; d < 1024; d <<= 1) {
-            uint32_t v = buf[cur][t];
-            if (t >= d) v = add_mod(v, buf[cur][t - d]);
-            buf[cur ^ 1][t] = v;
-            cur ^= 1;
-            __syncthreads();
-        }
-        const uint32_t v = add_mod(buf[cur][t], carry_s);
-        if (i < A) col[i] = v;
+        const uint32_t v = add_mod(block_scan<1024>(i < chunks ? col[i] : 0, buf, AddMod()), carry_s);
+        if (i < chunks) col[i] = v;
         __syncthreads();
         if (t == 1023) carry_s = v;
         __syncthreads();
     }
-    if (t == 0 && last_out) *last_out = carry_s;   // prefix through the last chunk
+    if (t == 0) last[blockIdx.y] = carry_s;       // prefix through the last chunk
 }
-__global__ __launch_bounds__(1024) void k_prefix_sum_carry(uint32_t* col, uint32_t A, const uint32_t* totals_scan) {
+__global__ __launch_bounds__(1024) void k_prefix_sum_carry(uint32_t* cols, uint32_t n, uint32_t A, const uint32_t* totals, uint32_t chunks) {
     const uint32_t i = blockIdx.x * 1024 + threadIdx.x;
     if (blockIdx.x == 0 || i >= A) return;
-    col[i] = add_mod(col[i], totals_scan[blockIdx.x - 1]);
+    uint32_t* col = cols + (size_t)blockIdx.y * n;
+    col[i] = add_mod(col[i], totals[(size_t)blockIdx.y * chunks + blockIdx.x - 1]);
 }
 // accum: terms[e][r] = mix_e + d_{e mod wd}[r] (active rows) or 1 (noise rows), AoS ExtElems
 __global__ void k_syn_accum_terms(uint32_t* terms, const uint32_t* data, const uint32_t* mix, uint32_t wd, uint32_t n, uint32_t A) {
@@ -839,15 +824,19 @@ static const char* p2join_check_shape(const zkh_circuit* c) {
                 c->global_size[GLOBAL_OUT] == 24, "p2join witgen: the circuit does not have P2-JOIN's shape (43 / 48 / 4 columns, 24 outputs)");
     return nullptr;
 }
-// inclusive prefix sum (mod P) of the first A words of a device column, in place; *last_out = the grand total (device word)
-const char* zkh::prefix_sum_column(zkh_ctx* ctx, uint32_t* col, uint32_t A, uint32_t* last_out) {
+// inclusive prefix sum (mod P) of the first A words of `planes` device columns n words apart, in place; last_out[plane] = the
+// plane's grand total (device words).  `what` names the caller in a launch error.
+const char* zkh::prefix_sum_planes(zkh_ctx* ctx, const char* what, uint32_t* cols, uint32_t planes, size_t n, uint32_t A, uint32_t* last_out) {
     const unsigned chunks = (A + 1023) / 1024;
     Tmp totals;
-    ZKH_TRY(new_buf(ctx, chunks, false, totals.out()));
-    k_prefix_sum_chunks<<<chunks, 1024, 0, ctx->stream>>>(col, A, totals->ptr());
-    k_prefix_sum_fp<<<1, 1024, 0, ctx->stream>>>(totals->ptr(), chunks, last_out);
-    k_prefix_sum_carry<<<chunks, 1024, 0, ctx->stream>>>(col, A, totals->ptr());
-    return last_launch_error("prefix_sum_column");
+    ZKH_TRY(new_buf(ctx, (size_t)planes * chunks, false, totals.out()));
+    k_prefix_sum_chunks<<<dim3(chunks, planes), 1024, 0, ctx->stream>>>(cols, (uint32_t)n, A, totals->ptr(), chunks);
+    k_prefix_sum_totals<<<dim3(1, planes), 1024, 0, ctx->stream>>>(totals->ptr(), chunks, last_out);
+    k_prefix_sum_carry<<<dim3(chunks, planes), 1024, 0, ctx->stream>>>(cols, (uint32_t)n, A, totals->ptr(), chunks);
+    return last_launch_error(what);
+}
+const char* zkh::prefix_sum_column(zkh_ctx* ctx, uint32_t* col, uint32_t A, uint32_t* last_out) {
+    return prefix_sum_planes(ctx, "prefix_sum_column", col, 1, 0, A, last_out);
 }
 extern "C" const char* zkh_syn_code(zkh_ctx* ctx, const zkh_circuit* c, size_t po2, size_t zk_cycles, zkh_buf* code) {
     ZKH_REQUIRE(c->kind >= 1 && c->kind <= 3, "syn_code: no built-in witness generator for circuit kind %u", c->kind);

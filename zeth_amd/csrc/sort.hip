@@ -1,4 +1,4 @@
-// sort.hip — derived sorted copies (ZKA1 version 3, term word 7 bit 1; zeth_amd/circuits/logup.py; DESIGN.md §2 ARGUMENTS): the
+// sort.hip — derived sorted copies (a term's `sorted_from`, ZKA1 version 3; zeth_amd/circuits/logup.py; DESIGN.md §2 ARGUMENTS): the
 // permuted side of a multiset equality, filled on the device.
 //
 // A pair (D, S): D the sorted copy, S its source (set_arguments has checked the rules).  r_0 < ... < r_{m-1} the active rows r < A
@@ -25,13 +25,15 @@
 //   (d) k_sort_gather : row r of rank j reads the sorted source row and copies S's tuple (coalesced writes, random reads).
 // Nothing depends on the order in which workgroups or atomics arrive (the only global atomics are OR / AND / min, which commute), and
 // no workgroup waits for another: the placement of every item is a function of the keys alone.
-#include "circuit.h"
+#include "arguments.h"
+#include "scan.h"
+
+#include <algorithm>
 
 using namespace zkh;
 
 namespace {
 
-constexpr uint32_t ARGS_HEADER = 8, TERM_WORDS = 16, MAX_TUPLE = 4, MAX_KEYS = 3, NONE = 0xffffffffu;
 constexpr uint32_t SORT_THREADS = 256, SORT_WAVES = SORT_THREADS / 64;
 // 8-bit digits: 256 counters per wave are 4 KiB of LDS for the block's four waves plus 4 KiB for their bases, far below what limits
 // occupancy, and a wave finds its lanes of equal digit with 8 ballots; 11-bit digits would save one pass in three at 8 x the LDS and
@@ -44,21 +46,13 @@ constexpr uint32_t KEYS_ROUNDS = 8;                     // k_sort_keys: rows per
 
 struct SortPair {                                       // one (D, S) as the kernels read it
     uint32_t d_term, w, nkeys, sel;                     // D's blob index; tuple width; key fields; selector code column or NONE
-    uint32_t kg[MAX_KEYS], kc[MAX_KEYS];                // S's key columns, most significant first
+    uint32_t kg[MAX_SORT_KEYS], kc[MAX_SORT_KEYS];                // S's key columns, most significant first
     uint32_t sg[MAX_TUPLE], sc[MAX_TUPLE];              // S's tuple
     uint32_t dc[MAX_TUPLE];                             // D's tuple (data columns)
 };
 // status words: [0, 2) the first bad selector (pair << 32 | row), then per pair ST_WORDS: OR[3], AND[3], m = selected rows, unused
 constexpr uint32_t ST_HEAD = 2, ST_WORDS = 8, ST_OR = 0, ST_AND = 3, ST_M = 6;
 
-__device__ __forceinline__ const uint32_t* group_ptr(const uint32_t* code, const uint32_t* data, uint32_t g) { return g == GROUP_CODE ? code : data; }
-__device__ __forceinline__ uint32_t canonical(uint32_t raw) { return fp_decode(Fp::raw(raw % P)); }
-// 0 / 1 / 2 = selector 0 / 1 / anything else (raw words compared mod P)
-__device__ __forceinline__ uint32_t sel_class(const uint32_t* code, uint32_t sel, uint32_t n, uint32_t r) {
-    if (sel == NONE) return 1;
-    const uint32_t s = code[(size_t)sel * n + r] % P;
-    return s == 0 ? 0 : s == R1 ? 1 : 2;
-}
 // the bits of v under mask, packed towards bit 0 in their order
 __device__ __forceinline__ uint32_t extract_bits(uint32_t v, uint32_t mask) {
     uint32_t out = 0, k = 0;
@@ -70,12 +64,12 @@ __device__ __forceinline__ uint32_t extract_bits(uint32_t v, uint32_t mask) {
 __global__ __launch_bounds__(SORT_THREADS) void k_sort_keys(const uint32_t* __restrict__ code, const uint32_t* __restrict__ data,
                                                            const SortPair* __restrict__ pairs, uint32_t n, uint32_t A, uint32_t groups,
                                                            uint32_t* __restrict__ selcnt, uint32_t* __restrict__ status) {
-    __shared__ uint32_t red[2 * MAX_KEYS];
+    __shared__ uint32_t red[2 * MAX_SORT_KEYS];
     const uint32_t p = blockIdx.y;
     const SortPair t = pairs[p];
-    if (threadIdx.x < 2 * MAX_KEYS) red[threadIdx.x] = threadIdx.x < MAX_KEYS ? 0u : ~0u;
+    if (threadIdx.x < 2 * MAX_SORT_KEYS) red[threadIdx.x] = threadIdx.x < MAX_SORT_KEYS ? 0u : ~0u;
     __syncthreads();
-    uint32_t vor[MAX_KEYS] = {0, 0, 0}, vand[MAX_KEYS] = {~0u, ~0u, ~0u};
+    uint32_t vor[MAX_SORT_KEYS] = {0, 0, 0}, vand[MAX_SORT_KEYS] = {~0u, ~0u, ~0u};
     for (uint32_t j = 0; j < KEYS_ROUNDS; j++) {
         const uint32_t r = (blockIdx.x * KEYS_ROUNDS + j) * SORT_THREADS + threadIdx.x;      // a wave = one 64-row group
         const uint32_t cls = r < A ? sel_class(code, t.sel, n, r) : 0;
@@ -84,9 +78,9 @@ __global__ __launch_bounds__(SORT_THREADS) void k_sort_keys(const uint32_t* __re
         if ((threadIdx.x & 63) == 0 && r < A) selcnt[(size_t)p * groups + r / 64] = __popcll(on);
         if (cls == 1) {
 #pragma unroll
-            for (uint32_t f = 0; f < MAX_KEYS; f++) {
+            for (uint32_t f = 0; f < MAX_SORT_KEYS; f++) {
                 if (f < t.nkeys) {
-                    const uint32_t v = canonical(group_ptr(code, data, t.kg[f])[(size_t)t.kc[f] * n + r]);
+                    const uint32_t v = fp_decode(Fp::raw(cell(code, data, t.kg[f], t.kc[f], n, r)));
                     vor[f] |= v;
                     vand[f] &= v;
                 }
@@ -94,14 +88,14 @@ __global__ __launch_bounds__(SORT_THREADS) void k_sort_keys(const uint32_t* __re
         }
     }
 #pragma unroll
-    for (uint32_t f = 0; f < MAX_KEYS; f++) {
+    for (uint32_t f = 0; f < MAX_SORT_KEYS; f++) {
         atomicOr(red + f, vor[f]);
-        atomicAnd(red + MAX_KEYS + f, vand[f]);
+        atomicAnd(red + MAX_SORT_KEYS + f, vand[f]);
     }
     __syncthreads();
     uint32_t* st = status + ST_HEAD + ST_WORDS * p;
-    if (threadIdx.x < MAX_KEYS) atomicOr(st + ST_OR + threadIdx.x, red[threadIdx.x]);
-    else if (threadIdx.x < 2 * MAX_KEYS) atomicAnd(st + ST_AND + threadIdx.x - MAX_KEYS, red[threadIdx.x]);
+    if (threadIdx.x < MAX_SORT_KEYS) atomicOr(st + ST_OR + threadIdx.x, red[threadIdx.x]);
+    else if (threadIdx.x < 2 * MAX_SORT_KEYS) atomicAnd(st + ST_AND + threadIdx.x - MAX_SORT_KEYS, red[threadIdx.x]);
 }
 
 // exclusive scan in place of `len` counters per segment (grid.x = segment), one workgroup per segment, each thread a contiguous chunk;
@@ -113,23 +107,14 @@ __global__ __launch_bounds__(SCAN_THREADS) void k_sort_scan(uint32_t* __restrict
     const uint32_t lo = min(t * chunk, len), hi = min(lo + chunk, len);
     uint32_t sum = 0;
     for (uint32_t i = lo; i < hi; i++) sum += seg[i];
-    buf[0][t] = sum;
-    __syncthreads();
-    int cur = 0;
-    for (uint32_t d = 1; d < SCAN_THREADS; d <<= 1) {
-        uint32_t x = buf[cur][t];
-        if (t >= d) x += buf[cur][t - d];
-        buf[cur ^ 1][t] = x;
-        cur ^= 1;
-        __syncthreads();
-    }
-    uint32_t run = buf[cur][t] - sum;
+    const uint32_t incl = block_scan<SCAN_THREADS>(sum, buf, AddWrap());
+    uint32_t run = incl - sum;
     for (uint32_t i = lo; i < hi; i++) {
         const uint32_t c = seg[i];
         seg[i] = run;
         run += c;
     }
-    if (total && t == SCAN_THREADS - 1) total[(size_t)blockIdx.x * total_stride] = buf[cur][t];
+    if (total && t == SCAN_THREADS - 1) total[(size_t)blockIdx.x * total_stride] = incl;
 }
 
 // (b) grid (ceil(A / SORT_THREADS), pairs): the packed key and the source row of every selected row, at its rank
@@ -150,12 +135,12 @@ __global__ __launch_bounds__(SORT_THREADS) void k_sort_pack(const uint32_t* __re
     unsigned long long lo = 0;
     uint32_t hi = 0;
 #pragma unroll
-    for (uint32_t f = 0; f < MAX_KEYS; f++) {
+    for (uint32_t f = 0; f < MAX_SORT_KEYS; f++) {
         if (f < t.nkeys) {
             const uint32_t live = st[ST_OR + f] & ~st[ST_AND + f];
             const uint32_t b = __popc(live);
             if (b) {                                     // (hi : lo) = (hi : lo) << b | field; b <= 31
-                const uint32_t v = extract_bits(canonical(group_ptr(code, data, t.kg[f])[(size_t)t.kc[f] * n + r]), live);
+                const uint32_t v = extract_bits(fp_decode(Fp::raw(cell(code, data, t.kg[f], t.kc[f], n, r))), live);
                 if (kWide) hi = (hi << b) | (uint32_t)(lo >> (64 - b));
                 lo = (lo << b) | v;
             }
@@ -191,35 +176,18 @@ __global__ __launch_bounds__(SORT_THREADS) void k_sort_hist(const unsigned long 
     if (h[threadIdx.x]) atomicAdd(totals + p * SORT_BINS + threadIdx.x, h[threadIdx.x]);
 }
 
-// inclusive sum over the workgroup's SORT_THREADS values
-__device__ __forceinline__ uint32_t block_scan_256(uint32_t v, uint32_t (*buf)[SORT_THREADS]) {
-    const uint32_t t = threadIdx.x;
-    buf[0][t] = v;
-    __syncthreads();
-    int cur = 0;
-#pragma unroll
-    for (uint32_t d = 1; d < SORT_THREADS; d <<= 1) {
-        uint32_t x = buf[cur][t];
-        if (t >= d) x += buf[cur][t - d];
-        buf[cur ^ 1][t] = x;
-        cur ^= 1;
-        __syncthreads();
-    }
-    return buf[cur][t];
-}
-
 // grid (SORT_BINS, pairs): hist[pair][bin][tile] := the output position of the first item of (bin, tile), in place
 __global__ __launch_bounds__(SORT_THREADS) void k_sort_offsets(uint32_t* __restrict__ hist, const uint32_t* __restrict__ totals, uint32_t tiles) {
     __shared__ uint32_t buf[2][SORT_THREADS];
     __shared__ uint32_t carry;
     const uint32_t bin = blockIdx.x, p = blockIdx.y, t = threadIdx.x;
-    const uint32_t below = block_scan_256(t < bin ? totals[p * SORT_BINS + t] : 0, buf);
+    const uint32_t below = block_scan<SORT_THREADS>(t < bin ? totals[p * SORT_BINS + t] : 0, buf, AddWrap());
     if (t == SORT_THREADS - 1) carry = below;            // the items of all smaller bins
     __syncthreads();
     uint32_t* row = hist + ((size_t)p * SORT_BINS + bin) * tiles;
     for (uint32_t t0 = 0; t0 < tiles; t0 += SORT_THREADS) {
         const uint32_t i = t0 + t, c = i < tiles ? row[i] : 0;
-        const uint32_t incl = block_scan_256(c, buf), base = carry;
+        const uint32_t incl = block_scan<SORT_THREADS>(c, buf, AddWrap()), base = carry;
         if (i < tiles) row[i] = base + incl - c;
         __syncthreads();
         if (t == SORT_THREADS - 1) carry = base + incl;
@@ -308,39 +276,25 @@ __global__ __launch_bounds__(SORT_THREADS) void k_sort_gather(const uint32_t* __
 
 }  // namespace
 
-extern "C" int zkh_circuit_derives_sorted(const zkh_circuit* c) {
-    if (!c || c->args.size() < ARGS_HEADER || c->args[1] != 3) return 0;
-    for (uint32_t i = 0; i < c->args[5]; i++)
-        if (c->args[ARGS_HEADER + (size_t)TERM_WORDS * i + 7] & 2) return 1;
-    return 0;
-}
-
 extern "C" const char* zkh_derive_sorted(zkh_ctx* ctx, const zkh_circuit* c, size_t po2, size_t zk_cycles, const zkh_buf* code, zkh_buf* data) {
     ZKH_REQUIRE(ctx && c && data, "derive_sorted: null argument");
     ZKH_REQUIRE(code, "derive_sorted: the raw code trace is required (the selectors and code-group source columns of the terms read it)");
     ZKH_REQUIRE(zkh_circuit_derives_sorted(c), "derive_sorted: the circuit's arguments derive no sorted copy (ZKA1 version 3)");
-    ZKH_REQUIRE(po2 >= 1 && po2 <= 24, "derive_sorted: po2 %zu out of range", po2);
-    const size_t n = (size_t)1 << po2;
-    ZKH_REQUIRE(zk_cycles < n, "derive_sorted: zk_cycles %zu leaves no active row at po2 %zu", zk_cycles, po2);
-    ZKH_REQUIRE(code->len == (size_t)c->group_size[GROUP_CODE] * n && data->len == (size_t)c->group_size[GROUP_DATA] * n,
-                "derive_sorted: buffer shape mismatch");
-    const uint32_t* a = c->args.data();
-    const uint32_t n_terms = a[5], A = (uint32_t)(n - zk_cycles);
+    size_t n;
+    uint32_t A;
+    ZKH_TRY(trace_rows("derive_sorted", c, po2, zk_cycles, code, data, nullptr, &n, &A));
+    const std::vector<Term>& a = c->args->terms;
     std::vector<SortPair> pairs;
-    for (uint32_t i = 0; i < n_terms; i++) {
-        const uint32_t* d = a + ARGS_HEADER + (size_t)TERM_WORDS * i;
-        if (!(d[7] & 2)) continue;
-        const uint32_t* s = a + ARGS_HEADER + (size_t)TERM_WORDS * (d[7] >> 16);
+    for (uint32_t i = 0; i < a.size(); i++) {
+        if (!a[i].sorted) continue;
+        const TermCols d = term_cols(a[i]), s = term_cols(a[a[i].sorted_from]);
         SortPair q{};
-        q.d_term = i; q.w = d[6]; q.nkeys = (d[7] >> 4) & 7; q.sel = d[2];
-        for (uint32_t f = 0; f < MAX_KEYS; f++) {
-            const uint32_t pos = f < q.nkeys ? (d[7] >> (8 + 2 * f)) & 3 : 0;
-            q.kg[f] = s[8 + 2 * pos]; q.kc[f] = s[9 + 2 * pos];
+        q.d_term = i; q.w = d.w; q.nkeys = a[i].nkeys; q.sel = d.sel;
+        for (uint32_t f = 0; f < MAX_SORT_KEYS; f++) {
+            const uint32_t pos = f < q.nkeys ? a[i].key[f] : 0;
+            q.kg[f] = s.tg[pos]; q.kc[f] = s.tc[pos];
         }
-        for (uint32_t e = 0; e < MAX_TUPLE; e++) {
-            q.sg[e] = e < q.w ? s[8 + 2 * e] : GROUP_DATA; q.sc[e] = e < q.w ? s[9 + 2 * e] : 0;
-            q.dc[e] = e < q.w ? d[9 + 2 * e] : 0;
-        }
+        for (uint32_t e = 0; e < MAX_TUPLE; e++) { q.sg[e] = s.tg[e]; q.sc[e] = s.tc[e]; q.dc[e] = d.tc[e]; }
         pairs.push_back(q);
     }
     const uint32_t np = (uint32_t)pairs.size();
@@ -355,7 +309,7 @@ extern "C" const char* zkh_derive_sorted(zkh_ctx* ctx, const zkh_circuit* c, siz
     std::vector<uint32_t> st(st_words, 0);
     st[0] = st[1] = ~0u;
     for (uint32_t p = 0; p < np; p++)
-        for (uint32_t f = 0; f < MAX_KEYS; f++) st[ST_HEAD + ST_WORDS * p + ST_AND + f] = ~0u;
+        for (uint32_t f = 0; f < MAX_SORT_KEYS; f++) st[ST_HEAD + ST_WORDS * p + ST_AND + f] = ~0u;
     ZKH_TRY(zkh_copy_from(ctx, "sort_status", st.data(), st.size(), status.out()));
     ZKH_TRY(new_buf(ctx, (size_t)np * groups, false, selcnt.out()));
     const SortPair* d_pairs = (const SortPair*)dtab->ptr();
@@ -376,7 +330,7 @@ extern "C" const char* zkh_derive_sorted(zkh_ctx* ctx, const zkh_circuit* c, siz
         uint32_t w;
         ZKH_TRY(zkh_read(ctx, code, &w, (size_t)q.sel * n + row, 1));
         return make_err("derive_sorted: sorted-copy term %u (tag %u) has selector %u at row %u, not 0 or 1: the witness is refused", q.d_term,
-                        a[ARGS_HEADER + (size_t)TERM_WORDS * q.d_term + 5], fp_decode(Fp::raw(w % P)), row);
+                        a[q.d_term].tag, fp_decode(Fp::raw(w % P)), row);
     }
     uint32_t bits = 0;                                   // the widest packed key over the pairs
     for (uint32_t p = 0; p < np; p++) {
