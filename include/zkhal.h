@@ -97,7 +97,9 @@ const char* zkh_write_async(zkh_ctx*, zkh_buf*, const uint32_t* pinned_host, siz
 /* ---- trait Hal ops (hal/mod.rs); semantics = CpuHal (hal/cpu.rs) ---- */
 /* Hal::batch_interpolate_ntt(io, count): per column inverse NTT, natural in -> bit-reversed coeffs, * n^-1 */
 const char* zkh_batch_interpolate_ntt(zkh_ctx*, zkh_buf* io, size_t count);
-/* Hal::batch_expand_into_evaluate_ntt(out, in, count, expand_bits) */
+/* Hal::batch_expand_into_evaluate_ntt(out, in, count, expand_bits): per column, bit-reversed coeffs in -> evaluations on the
+ * domain 2^expand_bits times larger.  Accepted: expand_bits in 0 .. log2(out column), with out column == in column << expand_bits;
+ * expand_bits == log2(out column) (one coefficient per column) replicates it.  Anything else is refused, `out` untouched. */
 const char* zkh_batch_expand_into_evaluate_ntt(zkh_ctx*, zkh_buf* out, const zkh_buf* in, size_t count,
                                                size_t expand_bits);
 /* Hal::batch_bit_reverse(io, count) */

@@ -27,8 +27,8 @@ struct PassParams {
     uint32_t log_n;          // transform size 2^log_n (output size)
     uint32_t L, R;           // this pass owns index bits [L, L+R)
     uint32_t log_t;          // tile width (consecutive low indices) = 2^log_t, log_t <= L
-    uint32_t expand_bits;    // forward first pass: in[i >> expand_bits], first `expand_bits` layers skipped
-    uint32_t first_layer;    // forward: first sub-layer to run in this tile (1-based), normally 1
+    uint32_t expand_bits;    // forward first pass: in[i >> expand_bits], the layers below first_layer skipped
+    uint32_t first_layer;    // forward: first sub-layer to run in this tile (1-based), normally 1; first pass: min(expand_bits, R) + 1
     uint32_t twiddle;        // 1: apply the inter-pass twiddle (pre for DIT, post for DIF)
     uint32_t scale;          // inverse last pass: multiply by n^-1 (Montgomery word) ...
     uint32_t zk_shift;       // ... and by 3^bitrev(i)
@@ -60,12 +60,16 @@ __global__ __launch_bounds__(NTT_THREADS) void k_ntt_pass(PassParams p) {
     const uint32_t* in = p.in + (size_t)col * p.in_col_stride;
     uint32_t* out = p.out + (size_t)col * p.out_col_stride;
     const uint32_t tw_shift = MAX_LOG_N - (p.L + p.R);   // w_{L+R}^e = w_26^(e << tw_shift)
+    // Expansion wider than this pass (expand_bits > R): only s = first_layer - 1 = R layers can be skipped here, and after s layers
+    // the zero-padded input holds in[i >> expand_bits] where bits [s, expand_bits) of i are zero and 0 elsewhere (a butterfly whose
+    // odd input is 0 copies the even one).  The later passes then run all of their layers.  0 whenever expand_bits <= R.
+    const uint32_t pad_mask = INVERSE ? 0u : (1u << p.expand_bits) - (1u << (p.first_layer - 1));
 
     // ---- load (+ expand, + DIT pre-twiddle) ----
     for (uint32_t e = tid; e < elems; e += NTT_THREADS) {
         const uint32_t m = e >> p.log_t, t = e & (T - 1);
         const size_t gi = base + ((size_t)m << p.L) + t;
-        uint32_t v = in[gi >> p.expand_bits];
+        uint32_t v = (gi & pad_mask) ? 0u : in[gi >> p.expand_bits];
         if (!INVERSE && p.twiddle) {
             const uint32_t r = __brev(m) >> (32 - p.R);
             const uint32_t ex = ((l0 + t) * r) << tw_shift;          // < 2^26
@@ -616,7 +620,8 @@ const char* run_transform(zkh_ctx* c, bool inverse, const uint32_t* in, size_t i
         // keep the tile <= 64 KiB
         while (p.R + p.log_t > 14 && p.log_t > 0) p.log_t--;
         p.expand_bits = (!inverse && first) ? expand_bits : 0;
-        p.first_layer = (!inverse && first) ? expand_bits + 1 : 1;
+        // the first pass skips the layers it owns; what expand_bits asks beyond them it accounts for in its load (k_ntt_pass: pad_mask)
+        p.first_layer = (!inverse && first) ? std::min(expand_bits, ps.R) + 1 : 1;
         p.twiddle = ps.L != 0;
         p.scale = (inverse && last) ? ninv.v : 0;
         p.zk_shift = (inverse && last && zk) ? 1 : 0;
@@ -714,12 +719,10 @@ extern "C" const char* zkh_batch_expand_into_evaluate_ntt(zkh_ctx* c, zkh_buf* o
     ZKH_REQUIRE(count && out->len % count == 0 && in->len % count == 0, "batch_expand_into_evaluate_ntt: sizes not multiples of count");
     const size_t n_out = out->len / count, n_in = in->len / count;
     const uint32_t log_n = log2_ceil(n_out);
-    ZKH_REQUIRE(((size_t)1 << log_n) == n_out && (n_in << expand_bits) == n_out,
-                "batch_expand_into_evaluate_ntt: out column %zu != in column %zu << %zu", n_out, n_in, expand_bits);
-    ZKH_REQUIRE(expand_bits <= log_n, "batch_expand_into_evaluate_ntt: expand_bits too large");
-    if (expand_bits == log_n) {   // degenerate: pure replication
-        return make_err("batch_expand_into_evaluate_ntt: expand_bits == log2(size) unsupported");
-    }
+    ZKH_REQUIRE(((size_t)1 << log_n) == n_out, "batch_expand_into_evaluate_ntt: column length %zu is not a power of two", n_out);
+    // expand_bits in 0..log_n; expand_bits == log_n (one coefficient per column) is replication, as upstream defines it
+    ZKH_REQUIRE(expand_bits <= log_n, "batch_expand_into_evaluate_ntt: expand_bits %zu too large for columns of %zu", expand_bits, n_out);
+    ZKH_REQUIRE((n_in << expand_bits) == n_out, "batch_expand_into_evaluate_ntt: out column %zu != in column %zu << %zu", n_out, n_in, expand_bits);
     return run_transform(c, false, in->ptr(), n_in, out->ptr(), n_out, log_n, count, (uint32_t)expand_bits, false,
                          "batch_expand_into_evaluate_ntt");
 }
