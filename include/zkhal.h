@@ -251,6 +251,34 @@ const char* zkh_derive_multiplicities(zkh_ctx*, const zkh_circuit*, size_t po2, 
  * derives sorted copies. */
 int zkh_circuit_derives_sorted(const zkh_circuit*);
 const char* zkh_derive_sorted(zkh_ctx*, const zkh_circuit*, size_t po2, size_t zk_cycles, const zkh_buf* code, zkh_buf* data);
+/* Derived columns (ZKA1 version 4: header word 6 = n_records, and n_records records of 16 words follow the terms: kind (1 = LIMBS,
+ * 2 = ORDER), L = limb bits (1..16), nl = limbs (1..8, L nl <= 32), n_src (LIMBS: 1; ORDER: 1 or 2), two (group, column) source pairs,
+ * eight destination data columns — for ORDER with two keys the flag column first, then nl <= 7 limb columns; unused words 0).  With
+ * x(c, r) the canonical value of a cell, zkh_derive_columns writes on the active rows r < 2^po2 - zk_cycles
+ *   LIMBS: dst_j[r] = Montgomery((x(src, r) >> jL) & (2^L - 1));
+ *   ORDER: zeros on row 0; for r >= 1 the limbs of d = k0[r] - k0[r-1] (one key), or with e = [k0[r] == k0[r-1]] the flag
+ *          Montgomery(e) and the limbs of d = e ? k1[r] - k1[r-1] : k0[r] - k0[r-1] - 1 (two keys);
+ * the blinding rows are not touched.  A source is a code or data column that no record writes and no derived multiplicity (records
+ * never chain); it may be a sorted copy's column.  Destinations are data columns that nothing else writes, that no record and no
+ * source term of a sorted copy reads and that no term uses as its multiplicity; lookup tuples read them freely.  It FAILS and leaves
+ * `data` unchanged — the error names the lowest (record, row) and the value — when a LIMBS value or an ORDER difference does not fit
+ * L nl bits, or when an ORDER difference is negative ("not ordered").  Call it AFTER zkh_derive_sorted (a record may read a sorted
+ * column) and BEFORE zkh_derive_multiplicities (the limbs are lookups to be counted).  Like its siblings it is an error on a circuit
+ * without records.  Sessions with caller traces and SegmentProver.seal_host_witness call the three in that order. */
+int zkh_circuit_derives_columns(const zkh_circuit*);
+const char* zkh_derive_columns(zkh_ctx*, const zkh_circuit*, size_t po2, size_t zk_cycles, const zkh_buf* code, zkh_buf* data);
+/* The data columns that zkh_derive_sorted, zkh_derive_columns and zkh_derive_multiplicities write on the active rows: their sorted
+ * union in cols[0 .. *n) (cap = room in cols; *n is set even when the call fails for lack of room).
+ * zkh_upload_data_trace copies a caller's data trace (`host`, W_data x 2^po2 words) into `data` without what the library derives:
+ * columns outside that set whole, runs of adjacent columns as one copy; the derived columns on the blinding rows [2^po2 - zk_cycles,
+ * 2^po2) only (the host still supplies those), one strided copy per run.  What it does not copy it does not write: derive before
+ * use.  pinned_async != 0: `host` lies in a zkh_host_alloc block and the copies are enqueued without a host sync (zkh_write_async);
+ * 0: any host memory, consumed before the call returns (zkh_write).
+ * zkh_ctx_h2d_bytes: the bytes this context has copied host to device since it was created (zkh_write, zkh_copy_from, zkh_write_async,
+ * zkh_upload_data_trace and the library's own uploads through them; not the tables of context and circuit set-up). */
+const char* zkh_circuit_derived_data_columns(const zkh_circuit*, uint32_t* cols, size_t cap, size_t* n);
+const char* zkh_upload_data_trace(zkh_ctx*, const zkh_circuit*, size_t po2, size_t zk_cycles, zkh_buf* data, const uint32_t* host, int pinned_async);
+size_t zkh_ctx_h2d_bytes(const zkh_ctx*);
 
 /* ---- built-in witness generators on the device, by circuit kind (desc word 13) ----
  *   kind 1 SYN-AIR   stands in for risc0-circuit-rv32im's witgen (declared synthetic)

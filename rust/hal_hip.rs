@@ -343,6 +343,36 @@ impl HipCircuitHal {
         let po2 = steps.trailing_zeros() as usize;
         ffi(|| unsafe { sys::zkh_derive_sorted(self.hal.ctx.0, self.circuit, po2, sys::ZK_CYCLES, ctrl.raw, data.raw) });
     }
+
+    /// The arguments (a ZKA1 version-4 blob) hold derived-column records (LIMBS / ORDER) that the library fills.
+    pub fn derives_columns(&self) -> bool {
+        unsafe { sys::zkh_circuit_derives_columns(self.circuit) != 0 }
+    }
+
+    /// Fill the destination columns of the derived-column records of `data` on the active rows (`zkh_derive_columns`): the limbs of a
+    /// word, or the flag and difference limbs that witness the order of sorted keys.  Call it after `derive_sorted` (a record may read
+    /// a sorted column), before `derive_multiplicities` (the limbs are lookups to be counted) and before `prove_begin`.  Panics on a
+    /// refused witness (a value that does not fit its limbs, keys that are not in order), which leaves `data` unchanged.
+    pub fn derive_columns(&self, ctrl: &HipBuffer<BabyBearElem>, data: &HipBuffer<BabyBearElem>, steps: usize) {
+        let po2 = steps.trailing_zeros() as usize;
+        ffi(|| unsafe { sys::zkh_derive_columns(self.hal.ctx.0, self.circuit, po2, sys::ZK_CYCLES, ctrl.raw, data.raw) });
+    }
+
+    /// The data columns that the three derives write on the active rows, ascending (`zkh_circuit_derived_data_columns`).
+    pub fn derived_data_columns(&self) -> Vec<u32> {
+        let mut n = 0usize;
+        let mut cols = vec![0u32; 1 << 16];
+        ffi(|| unsafe { sys::zkh_circuit_derived_data_columns(self.circuit, cols.as_mut_ptr(), cols.len(), &mut n) });
+        cols.truncate(n);
+        cols
+    }
+
+    /// Upload a caller's data trace from pinned memory without what the library derives (`zkh_upload_data_trace`): the other columns
+    /// whole, the derived ones on their blinding rows only; enqueued on the stream, no host sync.
+    pub fn upload_data_trace(&self, data: &HipBuffer<BabyBearElem>, pinned: &[u32], steps: usize) {
+        let po2 = steps.trailing_zeros() as usize;
+        ffi(|| unsafe { sys::zkh_upload_data_trace(self.hal.ctx.0, self.circuit, po2, sys::ZK_CYCLES, data.raw, pinned.as_ptr(), 1) });
+    }
 }
 
 impl Drop for HipCircuitHal {

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Per-op micro-benchmarks M1..M8 of SURVEY.md §8d (+ M9: the trace-driven witness, row f1; M10: the built-in accumulate of SYN-LOOKUP's
 arguments and its share of that circuit's seal; M11 / M11w: derived lookup multiplicities of SYN-LOOKUP-derived / WIDE; M12: derived sorted copies of SYN-LOOKUP-sorted
-against the host's lexsort + upload) on one MI355X, through the C ABI (HipHal).
+against the host's lexsort + upload; M13: derived columns — the 64 limb columns of SYN-LOOKUP FULL — next to a plain copy of the same
+bytes, and the host-witness seal with its upload) on one MI355X, through the C ABI (HipHal).
 
 Each line of output is one JSON object: the op, its shape, the average wall time of one call (stream drained on both
 sides of `reps` back-to-back calls), its ALGORITHMIC bytes (SURVEY.md §8a "B_alg": inputs read once + outputs written
@@ -315,6 +316,53 @@ def main() -> None:
         print(json.dumps({"bench": "M12share", "derive_sorted_ms": round(dt * 1e3, 4), "steps_ms": steps, "seal_ms": round(dt_seal * 1e3, 3),
                           "share": round(dt / dt_seal, 4), "host_lexsort_ms": round(dt_sort * 1e3, 2), "host_upload_ms": round(dt_up * 1e3, 3)}),
               flush=True)
+    if want("M13"):
+        # (a) derived columns (zkh_derive_columns) of SYN-LOOKUP FULL with limbs=True: 16 LIMBS records, 16 word columns read in the check
+        # pass and again in the write pass, 64 limb columns written, next to zkh_eltwise_copy_elem moving the same bytes in the same run;
+        # (b) the host-witness seal (SegmentProver.seal_host_witness from pinned memory; sort + multiplicities + limbs derived): bytes
+        # uploaded and wall-clock per seal
+        from zeth_amd.circuits import syn_lookup
+        from zeth_amd.prover import Segment, SegmentProver
+        zk = 1994
+        A = n - zk
+        shape = syn_lookup.FULL
+        desc, blob = syn_lookup.build_syn_lookup(shape, limbs=True, sort=True, derive=True)
+        circuit = hal.load_circuit(desc, jit=False)
+        circuit.set_arguments(blob)
+        code_h, data_h, out = syn_lookup.witness(shape, args.po2, zk, seed=13, sort=False, count=False, limbs=False)
+        code, data = hal.alloc_elem("code", code_h.size), hal.alloc_elem("data", data_h.size)
+        code.write(code_h)
+        data.write(data_h)
+        alg = 4 * A * shape.n_words * (2 + shape.n_limbs)
+        derive = lambda: hal.derive_columns(circuit, args.po2, zk, code, data)
+        dt = timed(hal, derive, args.reps)
+        line("M13", "derive columns (SYN-LOOKUP FULL: 16 words -> 64 limbs; check + write pass)", f"{shape.n_words} records x {A} rows -> 2^{args.po2}", dt, alg)
+        hal.prof_enable(True)
+        hal.prof_reset()
+        for _ in range(args.reps):
+            derive()
+        hal.sync()
+        steps = {r["name"]: round(r["total_ms"] / max(r["calls"], 1), 4) for r in hal.prof_get() if r["calls"] and r["name"].startswith("columns_")}
+        hal.prof_enable(False)
+        src, dst = upload(hal, rng, "m13src", alg // 8), hal.alloc_elem("m13dst", alg // 8)
+        dt_copy = timed(hal, lambda: hal.eltwise_copy_elem(dst, src), args.reps)
+        line("M13copy", "eltwise_copy_elem of the same bytes (the streaming yardstick)", f"{alg // 8} words", dt_copy, alg)
+        del src, dst
+        prover = SegmentProver(hal, desc, arguments=blob)
+        seg = Segment(index=0, po2=args.po2, noise_seed=0x2E80)
+        hcode, hdata = hal.host_alloc(code_h.size), hal.host_alloc(data_h.size)
+        hcode[:] = code_h
+        hdata[:] = data_h
+        before = hal.h2d_bytes()
+        prover.seal_host_witness(seg, hcode, hdata, out)
+        hal.sync()
+        crossed = hal.h2d_bytes() - before
+        dt_seal = timed(hal, lambda: prover.seal_host_witness(seg, hcode, hdata, out), args.reps)
+        hal.host_free(hcode)
+        hal.host_free(hdata)
+        print(json.dumps({"bench": "M13seal", "derive_columns_ms": round(dt * 1e3, 4), "steps_ms": steps, "copy_ms": round(dt_copy * 1e3, 4),
+                          "vs_copy": round(dt_copy / dt, 3), "host_witness_seal_ms": round(dt_seal * 1e3, 3), "h2d_bytes_per_seal": crossed,
+                          "full_trace_bytes": 4 * (code_h.size + data_h.size), "derived_columns": len(circuit.derived_data_columns())}), flush=True)
     hal.close()
 
 

@@ -24,8 +24,8 @@ The degree of a column's constraint is 1 (gate) + max(1 + t, max_i(deg sel_i + d
 
 ZKA1 layout (u32 words; canonical integers, not Montgomery words)::
 
-    [0] magic 'ZKA1' = 0x5a4b4131   [1] version = 1, 2 or 3   [2] k = accum Fp4 columns   [3] alpha mix word offset
-    [4] beta mix word offset       [5] n_terms       [6..8) reserved = 0
+    [0] magic 'ZKA1' = 0x5a4b4131   [1] version = 1 .. 4      [2] k = accum Fp4 columns   [3] alpha mix word offset
+    [4] beta mix word offset       [5] n_terms       [6] reserved = 0 (version 4: n_records)   [7] reserved = 0
     terms: n_terms x 16 words, sorted by column:
       col, neg (0: +1, 1: -1), sel (code column or NONE), m_group (NONE = constant 1, else GROUP_CODE / GROUP_DATA), m_col,
       tag, w, flags, then w (group, column) pairs of the tuple, unused pairs 0
@@ -35,6 +35,10 @@ ZKA1 layout (u32 words; canonical integers, not Montgomery words)::
     bits 4..6 = nkeys (1..min(w, 3)), bits 8 + 2j, 9 + 2j = the tuple position of sort key j (most significant key first),
     bits 16..31 = the blob index of S.  Without bit 1 everything above bit 0 is zero; bits 2, 3, 7 and the position fields of unused
     keys are reserved and refused.  The builder writes version 3 only when a term is a sorted copy.
+    Version 4: word 7 as in version 3; header word 6 = n_records, and n_records DERIVED-COLUMN RECORDS of 16 words follow the terms:
+      kind (1 = LIMBS, 2 = ORDER), L = limb bits (1..16), nl = limbs (1..8, L nl <= 32), n_src (LIMBS: 1; ORDER: 1 or 2),
+      two (group, column) source pairs (the unused one 0), then 8 destination data columns (ORDER with two keys: the flag column
+      first, then the nl <= 7 limb columns; unused words 0).  The builder writes version 4 only when a record exists.
 
 A derived term is the table side of a lookup (`check_derived`): sign -1, its multiplicity a data column that no tuple and no other
 term names, and every other term of its tag a lookup of sign +1.  Its multiplicity column is then a function of the traces:
@@ -45,10 +49,17 @@ A sorted copy D of S is the permuted side of a multiset equality (`check_sorted`
 selector, constant multiplicities, and tuple columns that are data columns nothing else in the blob names.  Those columns are then
 a function of the traces: S's selected active rows, stably sorted by the canonical values of the key positions, written onto the
 same selected rows (`reference_sorted`).
+
+A derived-column record (`check_columns`, zkh_derive_columns) makes data columns a function of other columns, row by row over the
+active rows (`reference_columns`).  x = the canonical value of a source cell.  LIMBS: dst_j = (x >> jL) & (2^L - 1); refused when
+x >= 2^(L nl).  ORDER over keys (k0) or (k0, k1) that are sorted: row 0 gets zeros; on row r >= 1, e = [k0 = k0@1] (two keys; the flag
+column) and d = k0 - k0@1 (one key), or e ? k1 - k1@1 : k0 - k0@1 - 1 (two keys), split into limbs like a LIMBS value; refused when
+d < 0 ("not ordered") or d >= 2^(L nl).  Sources are never destinations (records do not chain) but may be sorted-copy columns: the
+library runs sorted -> columns -> multiplicities, so that a record may read a sorted column and a lookup may count a limb.
 """
 from __future__ import annotations
 
-from dataclasses import dataclass, replace
+from dataclasses import dataclass, field, replace
 from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -161,6 +172,93 @@ def check_sorted(terms: Sequence[Term]) -> Optional[str]:
     return None
 
 
+KIND_LIMBS, KIND_ORDER = 1, 2
+RECORD_WORDS = 16
+MAX_LIMBS = 8
+MAX_ORDER_BITS = 29                            # order_constraints: keys and differences below 2^29 keep a negative difference out of range
+
+
+@dataclass(frozen=True)
+class Record:
+    """A derived-column record as the blob holds it (ZKA1 version 4): the fields are the blob's words, `check_columns` the rules"""
+    kind: int                                  # KIND_LIMBS / KIND_ORDER
+    limb_bits: int                             # L
+    nl: int                                    # limb count
+    srcs: Tuple[Tuple[int, int], ...]          # n_src (group, column) pairs
+    dsts: Tuple[int, ...]                      # data columns: (ORDER with two keys: the flag,) then the nl limbs
+    reserved: bool = False                     # a word the format reserves was not 0 (parser only)
+    n_src_word: Optional[int] = None           # the blob's n_src where it is not len(srcs) (parser only: an n_src out of range)
+
+    @property
+    def n_src(self) -> int:
+        return len(self.srcs) if self.n_src_word is None else self.n_src_word
+
+    def n_dsts(self) -> int:
+        return self.nl + (self.kind == KIND_ORDER and len(self.srcs) == 2)
+
+    def words(self) -> List[int]:
+        w = [self.kind, self.limb_bits, self.nl, len(self.srcs)]
+        for g, c in self.srcs:
+            w += [g, c]
+        w += [0] * (8 - len(w))
+        w += list(self.dsts)
+        return w + [0] * (RECORD_WORDS - len(w))
+
+
+def check_columns(terms: Sequence[Term], records: Sequence[Record], group_sizes=None) -> Optional[str]:
+    """the first record that breaks a rule, named by its index, or None.  Per record, in this order: (a) the ranges of kind, L, nl,
+    n_src and the reserved words; (b) its sources are code or data columns (of the circuit, when `group_sizes` = (accum, code, data)
+    is given), its destinations pairwise distinct data columns; (c) no source is a destination of any record (records never chain)
+    or a derived multiplicity; (d) no destination is written twice: by another record, a sorted copy or a derived multiplicity;
+    (e) no destination is read by the source term of a sorted copy (the sort runs first) or is any term's multiplicity.  Lookup
+    tuples read destinations freely."""
+    for i, r in enumerate(records):
+        if r.kind not in (KIND_LIMBS, KIND_ORDER):
+            return f"record {i}: kind {r.kind} (1 = LIMBS, 2 = ORDER)"
+        if not (1 <= r.limb_bits <= 16 and 1 <= r.nl <= MAX_LIMBS and r.limb_bits * r.nl <= 32):
+            return f"record {i}: {r.nl} limbs of {r.limb_bits} bits (1..8 limbs of 1..16 bits, at most 32 bits in all)"
+        if not 1 <= r.n_src <= (1 if r.kind == KIND_LIMBS else 2):
+            return f"record {i}: {r.n_src} sources (LIMBS: 1; ORDER: 1 or 2)"
+        if len(r.srcs) == 2 and r.nl > MAX_LIMBS - 1:
+            return f"record {i}: an ORDER record with two keys has at most {MAX_LIMBS - 1} limbs (its flag column is the first destination)"
+        if r.reserved or len(r.dsts) != r.n_dsts():
+            return f"record {i}: a reserved word is not 0 (the unused source pair and the unused destination words)"
+        for g, c in r.srcs:
+            if g not in (GROUP_CODE, GROUP_DATA) or (group_sizes is not None and not 0 <= c < group_sizes[g]):
+                return f"record {i}: source ({g}, {c}) is not a code or data column"
+        for e, c in enumerate(r.dsts):
+            if group_sizes is not None and not 0 <= c < group_sizes[GROUP_DATA]:
+                return f"record {i}: destination {c} is not a data column"
+            if c in r.dsts[:e]:
+                return f"record {i}: its destination (data {c}) appears twice"
+    for i, r in enumerate(records):
+        for g, c in r.srcs:
+            if g != GROUP_DATA:
+                continue
+            for j, x in enumerate(records):
+                if c in x.dsts:
+                    return f"record {i}: its source (data {c}) is a destination of record {j} (records never chain)"
+            for j, t in enumerate(terms):
+                if t.derive and t.mult == (g, c):
+                    return f"record {i}: its source (data {c}) is the derived multiplicity of term {j}"
+        for c in r.dsts:
+            for j, x in enumerate(records):
+                if j != i and c in x.dsts:
+                    return f"record {i}: its destination (data {c}) is also written by record {j}"
+            for j, t in enumerate(terms):
+                if t.sorted_from is not None and (GROUP_DATA, c) in t.tuple_cols:
+                    return f"record {i}: its destination (data {c}) is written by the sorted copy term {j}"
+                if t.derive and t.mult == (GROUP_DATA, c):
+                    return f"record {i}: its destination (data {c}) is the derived multiplicity of term {j}"
+            for j, t in enumerate(terms):
+                if t.sorted_from is not None and 0 <= t.sorted_from < len(terms) and (GROUP_DATA, c) in terms[t.sorted_from].tuple_cols:
+                    return f"record {i}: its destination (data {c}) is read by term {t.sorted_from}, the source of a sorted copy (the sort runs first)"
+            for j, t in enumerate(terms):
+                if t.mult == (GROUP_DATA, c):
+                    return f"record {i}: its destination (data {c}) is the multiplicity of term {j}"
+    return None
+
+
 def _by_column(terms: Sequence[Term]) -> List[Term]:
     """the terms sorted by accum column (stable: the blob order), the source indices of sorted copies following their terms"""
     order = sorted(range(len(terms)), key=lambda i: terms[i].col)
@@ -184,15 +282,18 @@ class Arguments:
     alpha: int
     beta: int
     terms: List[Term]
+    records: List[Record] = field(default_factory=list)
 
     @property
     def version(self) -> int:
+        if self.records:
+            return 4
         if any(t.sorted_from is not None for t in self.terms):
             return 3
         return 2 if any(t.derive for t in self.terms) else 1
 
     def blob(self) -> np.ndarray:
-        words = [ARGS_MAGIC, self.version, self.k, self.alpha, self.beta, len(self.terms), 0, 0]
+        words = [ARGS_MAGIC, self.version, self.k, self.alpha, self.beta, len(self.terms), len(self.records), 0]
         for t in _by_column(self.terms):
             rec = [t.col, 0 if t.sign == 1 else 1, NONE if t.sel is None else t.sel,
                    NONE if t.mult is None else t.mult[0], 0 if t.mult is None else t.mult[1], t.tag % P, len(t.tuple_cols), t.flags()]
@@ -200,17 +301,20 @@ class Arguments:
                 rec += [g, c]
             rec += [0] * (TERM_WORDS - len(rec))
             words += rec
+        for r in self.records:
+            words += r.words()
         return np.asarray(words, dtype=np.uint32)
 
     @staticmethod
     def parse(blob: Sequence[int]) -> "Arguments":
         d = [int(x) for x in np.asarray(blob, dtype=np.uint32)]
-        if len(d) < ARGS_HEADER or d[0] != ARGS_MAGIC or d[1] not in (1, 2, 3):
+        if len(d) < ARGS_HEADER or d[0] != ARGS_MAGIC or d[1] not in (1, 2, 3, 4):
             raise ValueError("not a ZKA1 argument blob")
         version = d[1]
         k, alpha, beta, n = d[2], d[3], d[4], d[5]
-        if len(d) != ARGS_HEADER + TERM_WORDS * n:
-            raise ValueError(f"ZKA1: {len(d)} words for {n} terms")
+        n_rec = d[6] if version >= 4 else 0
+        if len(d) != ARGS_HEADER + TERM_WORDS * n + RECORD_WORDS * n_rec:
+            raise ValueError(f"ZKA1: {len(d)} words for {n} terms" + (f" and {n_rec} records" if version >= 4 else ""))
         terms = []
         for i in range(n):
             r = d[ARGS_HEADER + TERM_WORDS * i: ARGS_HEADER + TERM_WORDS * (i + 1)]
@@ -220,7 +324,7 @@ class Arguments:
             if version == 2 and r[7] > 1:
                 raise ValueError(f"ZKA1 term {i}: word 7 is {r[7]} (bit 0: derived multiplicity; the other bits are reserved)")
             src, keys = None, ()
-            if version == 3:
+            if version >= 3:
                 f = r[7]
                 nkeys = f >> 4 & 7
                 if f & 0x8C or (not f & 2 and f > 1) or any(f >> (8 + 2 * j) & 3 for j in range(nkeys, 4)):
@@ -231,10 +335,23 @@ class Arguments:
             terms.append(Term(col=r[0], tuple_cols=tuple((r[8 + 2 * j], r[9 + 2 * j]) for j in range(w)), sign=-1 if r[1] else 1,
                               sel=None if r[2] == NONE else r[2], mult=None if r[3] == NONE else (r[3], r[4]), tag=r[5],
                               derive=version >= 2 and r[7] & 1 == 1, sorted_from=src, sort_keys=keys))
-        problem = check_sorted(terms) or check_derived(terms)
+        records = []
+        for i in range(n_rec):
+            at = ARGS_HEADER + TERM_WORDS * n + RECORD_WORDS * i
+            r = d[at: at + RECORD_WORDS]
+            n_src = r[3]
+            n_dst = min(8, r[2] + (r[0] == KIND_ORDER and n_src == 2))
+            reserved = any(r[4 + 2 * min(n_src, 2):8]) or any(r[8 + n_dst:])
+            records.append(Record(r[0], r[1], r[2], tuple((r[4 + 2 * j], r[5 + 2 * j]) for j in range(min(n_src, 2))), tuple(r[8: 8 + n_dst]),
+                                  reserved, None if n_src <= 2 else n_src))
+        problem = check_sorted(terms) or check_derived(terms) or check_columns(terms, records)
         if problem:
             raise ValueError(f"ZKA1: {problem}")
-        return Arguments(k, alpha, beta, terms)
+        return Arguments(k, alpha, beta, terms, records)
+
+    def plain(self) -> "Arguments":
+        """the same terms with nothing derived by the library (a version-1 blob): for a host that fills every column itself"""
+        return Arguments(self.k, self.alpha, self.beta, [replace(t, derive=False, sorted_from=None, sort_keys=()) for t in self.terms])
 
     def by_column(self) -> List[List[Term]]:
         cols: List[List[Term]] = [[] for _ in range(self.k)]
@@ -255,6 +372,7 @@ class LogupBuilder(CircuitBuilder):
                 raise ValueError(f"mix offset {off} needs {off + 4} mix words, the circuit has {global_sizes[1]}")
         self.alpha_off, self.beta_off = alpha, beta
         self.terms: List[Term] = []
+        self.records: List[Record] = []
 
     @property
     def k(self) -> int:
@@ -284,7 +402,7 @@ class LogupBuilder(CircuitBuilder):
         t = Term(col, tuple((int(g), int(c)) for g, c in tuple_cols), sign, sel, mult, int(tag), bool(derive),
                  None if sorted_from is None else int(sorted_from), tuple(int(x) for x in sort_keys))
         self.terms.append(t)
-        problem = check_sorted(self.terms) or check_derived(self.terms)
+        problem = check_sorted(self.terms) or check_derived(self.terms) or check_columns(self.terms, self.records, self.group_sizes)
         if problem:
             self.terms.pop()
             raise ValueError(problem)
@@ -294,6 +412,54 @@ class LogupBuilder(CircuitBuilder):
             raise ValueError(f"accum column {col}: constraint degree {deg} exceeds {MAX_DEGREE} (at most 3 terms of single-column "
                              f"selectors and multiplicities per column)")
         return t
+
+    def _record(self, rec: Record) -> Record:
+        self.records.append(rec)
+        problem = check_columns(self.terms, self.records, self.group_sizes)
+        if problem:
+            self.records.pop()
+            raise ValueError(problem)
+        return rec
+
+    def derive_limbs(self, src: Tuple[int, int], dsts: Sequence[int], limb_bits: int) -> Record:
+        """the library fills the data columns `dsts` (zkh_derive_columns) with the limbs of `limb_bits` bits of the (group, column)
+        `src`, least significant first (`check_columns`); a value that does not fit them refuses the witness"""
+        return self._record(Record(KIND_LIMBS, int(limb_bits), len(dsts), ((int(src[0]), int(src[1])),), tuple(int(c) for c in dsts)))
+
+    def derive_order(self, keys: Sequence[Tuple[int, int]], dsts: Sequence[int], limb_bits: int) -> Record:
+        """the library fills the data columns `dsts` with the order witness of the sorted (group, column) `keys`, one or two of them:
+        with two keys dsts[0] is the flag "same k0 as the previous row" and dsts[1:] the limbs of the ordered difference, with one key
+        dsts are the limbs (`reference_columns`); keys that are not in order refuse the witness"""
+        keys = tuple((int(g), int(c)) for g, c in keys)
+        return self._record(Record(KIND_ORDER, int(limb_bits), len(dsts) - (len(keys) == 2), keys, tuple(int(c) for c in dsts)))
+
+    def order_constraints(self, inner, record: Record):
+        """and onto `inner` (which the caller gates by its body selector) the constraints that the keys of the ORDER `record` are in
+        order on this row against the previous one: e (1 - e) = 0, e (k0 - k0@1) = 0 and
+        sum_j 2^(jL) limb_j = e (k1 - k1@1) + (1 - e) (k0 - k0@1 - 1); with one key sum_j 2^(jL) limb_j = k0 - k0@1.  Degree 3 with
+        the caller's gate.  Sound for keys below 2^29 and limbs range-checked by a lookup: L nl <= 29 keeps a negative difference,
+        P - |d| > 2^29, out of the limbs' range."""
+        if record.kind != KIND_ORDER:
+            raise ValueError("order_constraints: not an ORDER record")
+        L, nl = record.limb_bits, record.nl
+        if L * nl > MAX_ORDER_BITS:
+            raise ValueError(f"order_constraints: {nl} limbs of {L} bits exceed {MAX_ORDER_BITS} bits (a negative difference must stay out of range)")
+        two = len(record.srcs) == 2
+        limbs = record.dsts[1:] if two else record.dsts
+        total = None
+        for j, c in enumerate(limbs):
+            v = self.get(GROUP_DATA, c) if j == 0 else self.mul(self.const(1 << (j * L)), self.get(GROUP_DATA, c))
+            total = v if total is None else self.add(total, v)
+        d0 = self.sub(self.get(*record.srcs[0]), self.get(*record.srcs[0], 1))
+        if not two:
+            return self.and_eqz(inner, self.sub(total, d0))
+        one = self.const(1)
+        e = self.get(GROUP_DATA, record.dsts[0])
+        d1 = self.sub(self.get(*record.srcs[1]), self.get(*record.srcs[1], 1))
+        inner = self.and_eqz(inner, self.mul(e, self.sub(one, e)))
+        inner = self.and_eqz(inner, self.mul(e, d0))
+        want = self.add(self.mul(e, d1), self.mul(self.sub(one, e), self.sub(d0, one)))
+        return self.and_eqz(inner, self.sub(total, want))
 
     # ---- Fp4 values as 4 Fp handles (None = a zero component) ----
     def _e_add(self, x, y):
@@ -390,7 +556,7 @@ class LogupBuilder(CircuitBuilder):
         return self.and_cond(chain, last, last_inner)
 
     def args(self) -> Arguments:
-        return Arguments(self.k, self.alpha_off, self.beta_off, _by_column(self.terms))
+        return Arguments(self.k, self.alpha_off, self.beta_off, _by_column(self.terms), list(self.records))
 
     def finish_all(self, ret) -> Tuple[np.ndarray, np.ndarray]:
         """-> (ZKC1 description, ZKA1 argument blob)"""
@@ -600,4 +766,43 @@ def reference_sorted(args: Arguments, po2: int, zk_cycles: int, code, data) -> n
         for (_g, c), v in zip(t.tuple_cols, vals):
             out[c, :A] = 0
             out[c, rows] = v
+    return out.reshape(-1)
+
+
+def reference_columns(args: Arguments, po2: int, zk_cycles: int, code, data) -> np.ndarray:
+    """The data trace zkh_derive_columns leaves (raw Montgomery words, a copy): every record's destination columns on the active rows
+    (module docstring), rows [A, n) as given.  Raises ReferenceError, naming the lowest (record, row) and the offending value, on a
+    LIMBS value or an ORDER difference that does not fit the limbs and on keys that are not in order."""
+    n = 1 << po2
+    A = n - zk_cycles
+    groups = {GROUP_CODE: np.asarray(code, dtype=np.uint32).reshape(-1, n), GROUP_DATA: np.array(data, dtype=np.uint32).reshape(-1, n)}
+    out = groups[GROUP_DATA]                                                 # sources are never destinations: no record reads what another wrote
+    for i, r in enumerate(args.records):
+        L, nl, bits = r.limb_bits, r.nl, r.limb_bits * r.nl
+        k = [_dec(groups[g][c, :A]).astype(np.int64) for g, c in r.srcs]
+        flag = None
+        if r.kind == KIND_LIMBS:
+            d = k[0]
+        else:
+            d = np.zeros(A, dtype=np.int64)
+            if len(k) == 1:
+                d[1:] = k[0][1:] - k[0][:-1]
+            else:
+                flag = np.zeros(A, dtype=np.int64)
+                flag[1:] = k[0][1:] == k[0][:-1]
+                d[1:] = np.where(flag[1:] == 1, k[1][1:] - k[1][:-1], k[0][1:] - k[0][:-1] - 1)
+        bad = (d < 0) | (d >> bits != 0)
+        if bad.any():
+            row = int(np.argmax(bad))
+            v = int(d[row])
+            if r.kind == KIND_LIMBS:
+                raise ReferenceError(f"record {i} at row {row}: the value {v} does not fit {nl} limbs of {L} bits")
+            if v < 0:
+                raise ReferenceError(f"record {i} at row {row}: not ordered (difference {v})")
+            raise ReferenceError(f"record {i} at row {row}: the difference {v} does not fit {nl} limbs of {L} bits")
+        dsts = list(r.dsts)
+        if flag is not None:
+            out[dsts.pop(0), :A] = _enc(flag).astype(np.uint32)
+        for j, c in enumerate(dsts):
+            out[c, :A] = _enc((d >> (j * L)) & ((1 << L) - 1)).astype(np.uint32)
     return out.reshape(-1)

@@ -20,6 +20,14 @@ the witness may leave it zero (`witness(count=False)`).
 SYN-LOOKUP-sorted (`syn_lookup_sorted`, `build_syn_lookup(shape, sort=True)`): again the same description; every permuted copy is
 marked as the sorted copy of its memory tuple by (addr, time) in a ZKA1 version-3 blob, so the library sorts (zkh_derive_sorted) and
 the witness may leave the permuted columns zero (`witness(sort=False)`).  `derive` and `sort` combine.
+`build_syn_lookup(shape, limbs=True)`: the same description once more; every word's decomposition is a LIMBS record of a ZKA1
+version-4 blob, so the library splits the words (zkh_derive_columns) and the witness may leave the limbs zero (`witness(limbs=False)`).
+SYN-LOOKUP-ordered (`build_syn_lookup(shape, order=True)`): ANOTHER description, the one a memory argument needs.  The multiset
+equality alone lets any permutation pass for the sorted copy; here every memory pair gets, after the columns above, a flag column
+e = "same address as the previous row" and `order_limbs` limb columns of the ordered difference of the copy's (addr, time), the
+constraints that tie them to consecutive rows (logup.order_constraints) on the body rows, and the limbs as further lookups of tag 0.
+They are an ORDER record, so the library fills them (`witness(order=False)` leaves them zero).  Addresses and times stay below
+2^(order_limbs L).
 Not a shipped circuit: its control root is zkh_code_root of its code trace.
 """
 from __future__ import annotations
@@ -59,30 +67,49 @@ MULTI = Shape(2, 4, 4, 3)           # three memory pairs: 15 terms in 5 accum co
 SORT_KEYS = (0, 2)                  # (addr, time) of a memory tuple
 
 
+ORDER_LIMBS = 3
+
+
+def order_layout(n_words: int, n_limbs: int, n_mem: int, order_limbs: int = ORDER_LIMBS):
+    """data column indices of SYN-LOOKUP-ordered's additions, after `layout`'s: per memory pair [flag, limb_0 .. limb_{order_limbs-1}]"""
+    base = n_words + n_words * n_limbs + 1 + 2 * MEM_W * n_mem
+    return [[base + (1 + order_limbs) * i + e for e in range(1 + order_limbs)] for i in range(n_mem)]
+
+
 def build_syn_lookup(shape: Shape = FULL, derive: bool = False, sort: bool = False,
-                     sort_keys: Tuple[int, ...] = SORT_KEYS) -> Tuple[np.ndarray, np.ndarray]:
+                     sort_keys: Tuple[int, ...] = SORT_KEYS, limbs: bool = False, order: bool = False,
+                     order_limbs: int = ORDER_LIMBS) -> Tuple[np.ndarray, np.ndarray]:
     """-> (ZKC1 description, ZKA1 argument blob); derive: the table term's multiplicity is derived by the library (version-2 blob,
     the description unchanged); sort: every permuted copy is the library's sorted copy of its memory tuple by the tuple positions
-    `sort_keys` (version-3 blob, the description unchanged)"""
+    `sort_keys` (version-3 blob, the description unchanged); limbs: every word's limbs are a LIMBS record (version-4 blob, the
+    description unchanged); order: SYN-LOOKUP-ordered, another description (module docstring), its order columns an ORDER record over
+    the copy's (addr, time)"""
     n_words, n_limbs, limb_bits, n_mem = shape
-    words, limbs, m, mem, perm = layout(n_words, n_limbs, n_mem)
-    wd = m + 1 + 2 * MEM_W * n_mem
-    n_terms = n_words * n_limbs + 1 + 2 * n_mem
+    words, limb_cols, m, mem, perm = layout(n_words, n_limbs, n_mem)
+    ocols = order_layout(n_words, n_limbs, n_mem, order_limbs) if order else []
+    wd = m + 1 + 2 * MEM_W * n_mem + sum(len(c) for c in ocols)
+    n_terms = n_words * n_limbs + 1 + 2 * n_mem + n_mem * order_limbs * bool(order)
     k = (n_terms + 2) // 3
     b = LogupBuilder((4 * k, N_CODE, wd), (4, 8), alpha=0, beta=4)
     code = lambda c: b.get(GROUP_CODE, c)
     data = lambda c: b.get(GROUP_DATA, c)
     one = b.const(1)
     active, first, body, _rowidx, last = (code(i) for i in range(5))
-    # the terms, three per column in this order: limbs, the table, the memory pair
+    limbs_flag, limbs = limbs, limb_cols
+    # the terms, three per column in this order: limbs, the table, the memory pair (, the order limbs)
     specs = [dict(tuple_cols=[(GROUP_DATA, c)], tag=0) for row in limbs for c in row]
     specs.append(dict(tuple_cols=[(GROUP_CODE, 6)], sign=-1, sel=5, mult=(GROUP_DATA, m), tag=0, derive=derive))
     for i in range(n_mem):
         specs.append(dict(tuple_cols=[(GROUP_DATA, c) for c in mem[i]], sign=1, tag=1))
         copy = dict(sorted_from=len(specs) - 1, sort_keys=sort_keys) if sort else {}
         specs.append(dict(tuple_cols=[(GROUP_DATA, c) for c in perm[i]], sign=-1, tag=1, **copy))
+    specs += [dict(tuple_cols=[(GROUP_DATA, c)], tag=0) for cols in ocols for c in cols[1:]]
     for i, s in enumerate(specs):
         b.term(i // 3, **s)
+    if limbs_flag:
+        for kk in range(n_words):
+            b.derive_limbs((GROUP_DATA, words[kk]), limbs[kk], limb_bits)
+    records = [b.derive_order([(GROUP_DATA, perm[i][0]), (GROUP_DATA, perm[i][2])], cols, limb_bits) for i, cols in enumerate(ocols)]
     # words = sum of their limbs, on active rows
     inner = b.true()
     for kk in range(n_words):
@@ -93,6 +120,11 @@ def build_syn_lookup(shape: Shape = FULL, derive: bool = False, sort: bool = Fal
         inner = b.and_eqz(inner, b.sub(data(words[kk]), acc))
     chain = b.and_cond(b.true(), active, inner)
     chain = b.arguments(chain, first, body, last)
+    if records:
+        inner = b.true()
+        for rec in records:
+            inner = b.order_constraints(inner, rec)
+        chain = b.and_cond(chain, body, inner)
     chain = b.and_eqz(chain, b.mul(active, b.sub(one, active)))
     chain = b.and_eqz(chain, b.mul(first, b.sub(one, first)))
     chain = b.and_eqz(chain, b.sub(b.sub(active, first), body))
@@ -128,14 +160,18 @@ def _enc(x) -> np.ndarray:
 
 
 def witness(shape: Shape, po2: int, zk_cycles: int, seed: int = 1, count: bool = True, sort: bool = True, addr_range: int = 1 << 20,
-            sort_keys: Tuple[int, ...] = SORT_KEYS):
-    """-> (code, data, out_global) host arrays of raw Montgomery words: random words below min(P, 2^(n_limbs L)) split into limbs,
-    the table's multiplicities (count=False: zero, for the library to derive), random memory tuples (addresses below `addr_range`)
-    and their copy stably sorted by the tuple positions `sort_keys`, (addr, time) (sort=False: zero, for the library to sort);
-    blinding rows of data from the same seeded generator"""
+            sort_keys: Tuple[int, ...] = SORT_KEYS, limbs: bool = True, order=None, order_limbs: int = ORDER_LIMBS):
+    """-> (code, data, out_global) host arrays of raw Montgomery words: random words below min(P, 2^(n_limbs L)) split into limbs
+    (limbs=False: zero, for the library to split), the table's multiplicities (count=False: zero, for the library to derive), random
+    memory tuples (addresses below `addr_range`) and their copy stably sorted by the tuple positions `sort_keys`, (addr, time)
+    (sort=False: zero, for the library to sort); blinding rows of data from the same seeded generator.
+    order: None = the plain shape; True / False = SYN-LOOKUP-ordered's witness (`build_syn_lookup(order=True)`), its order columns
+    filled from the sorted copy (and their limbs counted in the multiplicities) / left zero for the library"""
     n_words, n_limbs, limb_bits, n_mem = shape
-    words, limbs, m_col, mem, perm = layout(n_words, n_limbs, n_mem)
-    wd = m_col + 1 + 2 * MEM_W * n_mem
+    words, limb_cols, m_col, mem, perm = layout(n_words, n_limbs, n_mem)
+    limbs_on, limbs = limbs, limb_cols
+    ocols = order_layout(n_words, n_limbs, n_mem, order_limbs) if order is not None else []
+    wd = m_col + 1 + 2 * MEM_W * n_mem + sum(len(c) for c in ocols)
     n = 1 << po2
     A = n - zk_cycles
     T = 1 << limb_bits
@@ -158,20 +194,35 @@ def witness(shape: Shape, po2: int, zk_cycles: int, seed: int = 1, count: bool =
         data[words[kk], :A] = w
         for j in range(n_limbs):
             limb = (w >> np.uint64(j * limb_bits)) & np.uint64(T - 1)
-            data[limbs[kk][j], :A] = limb
+            if limbs_on:
+                data[limbs[kk][j], :A] = limb
             counts += np.bincount(limb.astype(np.int64), minlength=T)
-    if count:
-        data[m_col, :T] = counts.astype(np.uint64)
     for i in range(n_mem):
         addr = rng.integers(0, addr_range, size=A, dtype=np.uint64)
         val = rng.integers(0, P, size=A, dtype=np.uint64)
         time = rng.permutation(A).astype(np.uint64)
         tup = (addr, val, time)
-        order = np.lexsort(tuple(tup[pos] for pos in sort_keys[::-1]))
+        by = np.lexsort(tuple(tup[pos] for pos in sort_keys[::-1]))
         for e, v in enumerate(tup):
             data[mem[i][e], :A] = v
             if sort:
-                data[perm[i][e], :A] = v[order]
+                data[perm[i][e], :A] = v[by]
+        if ocols:                                                            # the order witness of the sorted (addr, time)
+            k0, k1 = addr[by].astype(np.int64), time[by].astype(np.int64)
+            same = np.zeros(A, dtype=np.int64)
+            same[1:] = k0[1:] == k0[:-1]
+            d = np.zeros(A, dtype=np.int64)
+            d[1:] = np.where(same[1:] == 1, k1[1:] - k1[:-1], k0[1:] - k0[:-1] - 1)
+            assert (d >= 0).all() and (d >> (order_limbs * limb_bits) == 0).all(), "an ordered difference does not fit the order limbs"
+            if order:
+                data[ocols[i][0], :A] = same.astype(np.uint64)
+            for j in range(order_limbs):
+                limb = (d >> (j * limb_bits)) & (T - 1)
+                if order:
+                    data[ocols[i][1 + j], :A] = limb.astype(np.uint64)
+                counts += np.bincount(limb, minlength=T)
+    if count:
+        data[m_col, :T] = counts.astype(np.uint64)
     data[:, A:] = rng.integers(0, P, size=(wd, n - A), dtype=np.uint64)
     return _enc(code).reshape(-1), _enc(data).reshape(-1), np.zeros(4, dtype=np.uint32)
 
@@ -191,4 +242,13 @@ def corrupt_limb(shape: Shape, data, po2: int, row: int, word: int = 0) -> np.nd
     add = (1 << shape.limb_bits) * ((1 << 32) % P) % P
     for c in (limbs[word][0], words[word]):
         d[c, row] = (int(d[c, row]) + add) % P
+    return d.reshape(-1)
+
+
+def swap_sorted_rows(shape: Shape, data, po2: int, row: int, pair: int = 0) -> np.ndarray:
+    """a copy of `data` in which rows `row` and `row + 1` of the sorted copy of memory pair `pair` change places: still a permutation of
+    the memory tuples, so the bus balances, but no longer in (addr, time) order — only SYN-LOOKUP-ordered's constraints object"""
+    perm = layout(shape.n_words, shape.n_limbs, shape.n_mem)[4][pair]
+    d = np.array(data, dtype=np.uint32).reshape(-1, 1 << po2)
+    d[perm, row], d[perm, row + 1] = d[perm, row + 1].copy(), d[perm, row].copy()
     return d.reshape(-1)

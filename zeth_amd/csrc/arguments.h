@@ -1,7 +1,7 @@
 // arguments.h — lookup and permutation arguments as data (ZKA1 blob; zeth_amd/circuits/logup.py; DESIGN.md §2 ARGUMENTS): the decoded
 // form every consumer reads, and what the consumers share.  arguments.hip owns the blob format and the rules a blob must keep;
-// accumulate.hip (zkh_accumulate), multiplicities.hip (zkh_derive_multiplicities) and sort.hip (zkh_derive_sorted) read
-// zkh_circuit::args and never see a blob word.
+// accumulate.hip (zkh_accumulate), multiplicities.hip (zkh_derive_multiplicities), sort.hip (zkh_derive_sorted) and columns.hip
+// (zkh_derive_columns) read zkh_circuit::args and never see a blob word.
 #pragma once
 #include <vector>
 
@@ -12,6 +12,7 @@ namespace zkh {
 constexpr uint32_t ARGS_MAGIC = 0x5a4b4131u;        // 'ZKA1'
 constexpr uint32_t ARGS_HEADER = 8, TERM_WORDS = 16;
 constexpr uint32_t MAX_TUPLE = 4, MAX_TERMS = 3, MAX_SORT_KEYS = 3, NONE = 0xffffffffu;
+constexpr uint32_t RECORD_WORDS = 16, KIND_LIMBS = 1, KIND_ORDER = 2, MAX_LIMBS = 8;
 
 // logup.Term as the blob gives it: the fields are the blob's words, checked by the rules of arguments.hip before a circuit keeps them
 struct Term {
@@ -25,10 +26,18 @@ struct Term {
     bool sorted;                            // this term is the sorted copy of the term sorted_from (logup.Term.sorted_from is not None),
     uint32_t sorted_from, nkeys, key[4];    // by the tuple positions key[0 .. nkeys), most significant first (the rules bound nkeys)
 };
+// logup.Record, a derived-column record (version 4), as the blob gives it; the kernels of columns.hip read it in this form
+struct Record {
+    uint32_t kind, L, nl, n_src;            // KIND_LIMBS / KIND_ORDER; limb bits; limb count; sources (the rules bound them all)
+    uint32_t sg[2], sc[2];                  // the sources' (group, column), the first n_src
+    uint32_t dst[MAX_LIMBS];                // destination data columns: (ORDER with two keys: the flag,) then the nl limbs
+    uint32_t n_dst, reserved;               // destinations in use; a word the format reserves was not 0
+};
 // logup.Arguments
 struct Arguments {
     uint32_t version, k, alpha, beta;       // blob version; accum Fp4 columns; mix word offsets of the two challenges
     std::vector<Term> terms;
+    std::vector<Record> records;
 };
 
 // a term's columns as the kernels read them; unused tuple slots name (data, 0)

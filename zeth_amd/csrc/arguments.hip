@@ -1,5 +1,6 @@
 // arguments.hip — the ZKA1 argument blob (layout: zeth_amd/circuits/logup.py; DESIGN.md §2 ARGUMENTS): its decoding into
-// zkh::Arguments, the rules a circuit's arguments keep, and the entry points that attach them to a circuit and ask what they derive.
+// zkh::Arguments (terms and, from version 4, derived-column records), the rules a circuit's arguments keep (check_sorted, check_derived,
+// check_columns, in this order), and the entry points that attach them to a circuit and ask what they derive.
 // decode_arguments is the only code that knows the blob's words; everything else, here and in the consumers, reads decoded terms.
 #include "arguments.h"
 
@@ -15,9 +16,11 @@ namespace {
 // significant key first); bits 2, 3, 7, the position fields of unused keys and, without bit 1, everything above bit 0 are reserved.
 // A reserved bit is recorded, not refused: the rules refuse it where they reach the term (flag_word_rule), after the circuit-shape checks.
 const char* decode_arguments(const uint32_t* a, size_t words, Arguments* out) {
-    ZKH_REQUIRE(words >= ARGS_HEADER && a[0] == ARGS_MAGIC && a[1] >= 1 && a[1] <= 3, "set_arguments: not a ZKA1 (version 1) argument blob");
-    const uint32_t n_terms = a[5];
-    ZKH_REQUIRE(words == ARGS_HEADER + (size_t)TERM_WORDS * n_terms, "set_arguments: %zu words for %u terms", words, n_terms);
+    ZKH_REQUIRE(words >= ARGS_HEADER && a[0] == ARGS_MAGIC && a[1] >= 1 && a[1] <= 4, "set_arguments: not a ZKA1 (version 1) argument blob");
+    const uint32_t n_terms = a[5], n_records = a[1] >= 4 ? a[6] : 0;            // header word 6: the records of version 4, reserved before
+    const bool fits = words == ARGS_HEADER + (size_t)TERM_WORDS * n_terms + (size_t)RECORD_WORDS * n_records;
+    ZKH_REQUIRE(fits || a[1] < 4, "set_arguments: %zu words for %u terms and %u records", words, n_terms, n_records);
+    ZKH_REQUIRE(fits, "set_arguments: %zu words for %u terms", words, n_terms);
     out->version = a[1]; out->k = a[2]; out->alpha = a[3]; out->beta = a[4];
     out->terms.assign(n_terms, Term{});
     for (uint32_t i = 0; i < n_terms; i++) {
@@ -28,7 +31,7 @@ const char* decode_arguments(const uint32_t* a, size_t words, Arguments* out) {
         const uint32_t f = t.flags = out->version >= 2 ? r[7] : 0;
         t.derive = f & 1;
         t.reserved = f > 1;
-        if (out->version == 3) {
+        if (out->version >= 3) {
             t.sorted = f & 2;
             t.sorted_from = f >> 16;
             t.nkeys = (f >> 4) & 7;
@@ -37,13 +40,27 @@ const char* decode_arguments(const uint32_t* a, size_t words, Arguments* out) {
             for (uint32_t j = t.nkeys; j < 4; j++) t.reserved |= t.key[j] != 0;
         }
     }
+    // Derived-column records (version 4): kind, L, nl, n_src, two (group, column) source pairs, eight destination data columns.  As
+    // with the flags, a reserved word that is set is recorded here and refused by the rules (check_columns).
+    out->records.assign(n_records, Record{});
+    for (uint32_t i = 0; i < n_records; i++) {
+        const uint32_t* r = a + ARGS_HEADER + (size_t)TERM_WORDS * n_terms + (size_t)RECORD_WORDS * i;
+        Record& x = out->records[i];
+        x.kind = r[0]; x.L = r[1]; x.nl = r[2]; x.n_src = r[3];
+        for (uint32_t j = 0; j < 2; j++) { x.sg[j] = r[4 + 2 * j]; x.sc[j] = r[5 + 2 * j]; }
+        for (uint32_t j = 0; j < MAX_LIMBS; j++) x.dst[j] = r[8 + j];
+        const uint64_t nd = (uint64_t)x.nl + (x.kind == KIND_ORDER && x.n_src == 2);
+        x.n_dst = nd < MAX_LIMBS ? (uint32_t)nd : MAX_LIMBS;
+        for (uint32_t j = x.n_src < 2 ? x.n_src : 2; j < 2; j++) x.reserved |= x.sg[j] | x.sc[j];
+        for (uint32_t j = x.n_dst; j < MAX_LIMBS; j++) x.reserved |= x.dst[j];
+    }
     return nullptr;
 }
 
 const char* flag_word_rule(const Arguments& a, uint32_t i) {
     const Term& t = a.terms[i];
     if (!t.reserved) return nullptr;
-    if (a.version == 3)
+    if (a.version >= 3)
         return make_err("set_arguments: term %u: word 7 is %#x (bit 0: derived multiplicity; bit 1: sorted copy, with its keys in bits 4..15 "
                         "and its source term in bits 16..31; the other bits are reserved)", i, t.flags);
     return make_err("set_arguments: term %u: word 7 is %u (bit 0: derived multiplicity; the other bits are reserved)", i, t.flags);
@@ -126,6 +143,72 @@ const char* check_sorted(const Arguments& a) {
     return nullptr;
 }
 
+bool writes(const Record& x, uint32_t col) {                                    // data column `col` among the destinations of x
+    for (uint32_t e = 0; e < x.n_dst; e++)
+        if (x.dst[e] == col) return true;
+    return false;
+}
+
+// logup.check_columns: the first derived-column record that breaks a rule.  Per record: (a) the ranges of kind, L, nl, n_src and the
+// reserved words; (b) its sources are code or data columns of the circuit, its destinations pairwise distinct data columns; then, per
+// record again: (c) no source is a destination of any record (records never chain) or a derived multiplicity; (d) no destination is
+// written twice: by another record, a sorted copy or a derived multiplicity; (e) no destination is read by the source term of a sorted
+// copy (the sort runs first) or is any term's multiplicity.  Lookup tuples read destinations freely.
+const char* check_columns(const zkh_circuit* c, const Arguments& a) {
+    const uint32_t n_terms = (uint32_t)a.terms.size(), n_rec = (uint32_t)a.records.size();
+    for (uint32_t i = 0; i < n_rec; i++) {
+        const Record& r = a.records[i];
+        ZKH_REQUIRE(r.kind == KIND_LIMBS || r.kind == KIND_ORDER, "set_arguments: record %u: kind %u (1 = LIMBS, 2 = ORDER)", i, r.kind);
+        ZKH_REQUIRE(r.L >= 1 && r.L <= 16 && r.nl >= 1 && r.nl <= MAX_LIMBS && r.L * r.nl <= 32, "set_arguments: record %u: %u limbs of %u bits "
+                    "(1..8 limbs of 1..16 bits, at most 32 bits in all)", i, r.nl, r.L);
+        ZKH_REQUIRE(r.n_src >= 1 && r.n_src <= (r.kind == KIND_LIMBS ? 1u : 2u), "set_arguments: record %u: %u sources (LIMBS: 1; ORDER: 1 or 2)", i, r.n_src);
+        ZKH_REQUIRE(r.n_src < 2 || r.nl <= MAX_LIMBS - 1, "set_arguments: record %u: an ORDER record with two keys has at most %u limbs (its flag column is "
+                    "the first destination)", i, MAX_LIMBS - 1);
+        ZKH_REQUIRE(!r.reserved, "set_arguments: record %u: a reserved word is not 0 (the unused source pair and the unused destination words)", i);
+        for (uint32_t j = 0; j < r.n_src; j++)
+            ZKH_REQUIRE((r.sg[j] == GROUP_CODE || r.sg[j] == GROUP_DATA) && r.sc[j] < c->group_size[r.sg[j]], "set_arguments: record %u: source (%u, %u) is "
+                        "not a code or data column", i, r.sg[j], r.sc[j]);
+        for (uint32_t e = 0; e < r.n_dst; e++) {
+            ZKH_REQUIRE(r.dst[e] < c->group_size[GROUP_DATA], "set_arguments: record %u: destination %u is not a data column", i, r.dst[e]);
+            for (uint32_t e2 = 0; e2 < e; e2++)
+                ZKH_REQUIRE(r.dst[e2] != r.dst[e], "set_arguments: record %u: its destination (data %u) appears twice", i, r.dst[e]);
+        }
+    }
+    for (uint32_t i = 0; i < n_rec; i++) {
+        const Record& r = a.records[i];
+        for (uint32_t s = 0; s < r.n_src; s++) {
+            const uint32_t col = r.sc[s];
+            if (r.sg[s] != GROUP_DATA) continue;
+            for (uint32_t j = 0; j < n_rec; j++)
+                ZKH_REQUIRE(!writes(a.records[j], col), "set_arguments: record %u: its source (data %u) is a destination of record %u (records never chain)", i, col, j);
+            for (uint32_t j = 0; j < n_terms; j++)
+                ZKH_REQUIRE(!(a.terms[j].derive && a.terms[j].mg == GROUP_DATA && a.terms[j].mc == col), "set_arguments: record %u: its source (data %u) is the "
+                            "derived multiplicity of term %u", i, col, j);
+        }
+        for (uint32_t e = 0; e < r.n_dst; e++) {
+            const uint32_t col = r.dst[e];
+            for (uint32_t j = 0; j < n_rec; j++)
+                ZKH_REQUIRE(j == i || !writes(a.records[j], col), "set_arguments: record %u: its destination (data %u) is also written by record %u", i, col, j);
+            for (uint32_t j = 0; j < n_terms; j++) {
+                const Term& t = a.terms[j];
+                ZKH_REQUIRE(!(t.sorted && in_tuple(t, t.w, GROUP_DATA, col)), "set_arguments: record %u: its destination (data %u) is written by the sorted copy "
+                            "term %u", i, col, j);
+                ZKH_REQUIRE(!(t.derive && t.mg == GROUP_DATA && t.mc == col), "set_arguments: record %u: its destination (data %u) is the derived multiplicity of "
+                            "term %u", i, col, j);
+            }
+            for (uint32_t j = 0; j < n_terms; j++) {
+                const Term& t = a.terms[j];
+                ZKH_REQUIRE(!(t.sorted && in_tuple(a.terms[t.sorted_from], a.terms[t.sorted_from].w, GROUP_DATA, col)), "set_arguments: record %u: its destination "
+                            "(data %u) is read by term %u, the source of a sorted copy (the sort runs first)", i, col, t.sorted_from);
+            }
+            for (uint32_t j = 0; j < n_terms; j++)
+                ZKH_REQUIRE(!(a.terms[j].mg == GROUP_DATA && a.terms[j].mc == col), "set_arguments: record %u: its destination (data %u) is the multiplicity of term %u",
+                            i, col, j);
+        }
+    }
+    return nullptr;
+}
+
 // the arguments against the circuit's shape, then the rules of sorted copies, then those of derived multiplicities
 const char* check_arguments(const zkh_circuit* c, const Arguments& a) {
     const uint32_t k = a.k;
@@ -151,8 +234,9 @@ const char* check_arguments(const zkh_circuit* c, const Arguments& a) {
             ZKH_REQUIRE(is_column(t.tg[e], t.tc[e]), "set_arguments: term %u: tuple column (%u, %u) is not a code or data column", i, t.tg[e], t.tc[e]);
     }
     for (uint32_t col = 0; col < k; col++) ZKH_REQUIRE(per_col[col] >= 1, "set_arguments: accum column %u has no terms", col);
-    if (a.version == 3) ZKH_TRY(check_sorted(a));
-    return a.version >= 2 ? check_derived(a) : nullptr;
+    if (a.version >= 3) ZKH_TRY(check_sorted(a));
+    if (a.version >= 2) ZKH_TRY(check_derived(a));
+    return check_columns(c, a);
 }
 
 }  // namespace
@@ -186,4 +270,24 @@ extern "C" int zkh_circuit_derives_multiplicities(const zkh_circuit* c) {
 
 extern "C" int zkh_circuit_derives_sorted(const zkh_circuit* c) {
     return c && c->args && std::any_of(c->args->terms.begin(), c->args->terms.end(), [](const Term& t) { return t.sorted; });
+}
+
+extern "C" int zkh_circuit_derives_columns(const zkh_circuit* c) { return c && c->args && !c->args->records.empty(); }
+
+extern "C" const char* zkh_circuit_derived_data_columns(const zkh_circuit* c, uint32_t* cols, size_t cap, size_t* n) {
+    ZKH_REQUIRE(c && n && (cols || !cap), "derived_data_columns: null argument");
+    std::vector<uint32_t> out;
+    if (c->args) {
+        for (const Term& t : c->args->terms) {
+            if (t.derive) out.push_back(t.mc);
+            if (t.sorted) out.insert(out.end(), t.tc, t.tc + t.w);
+        }
+        for (const Record& r : c->args->records) out.insert(out.end(), r.dst, r.dst + r.n_dst);
+    }
+    std::sort(out.begin(), out.end());
+    out.erase(std::unique(out.begin(), out.end()), out.end());
+    *n = out.size();
+    ZKH_REQUIRE(out.size() <= cap, "derived_data_columns: %zu columns, room for %zu", out.size(), cap);
+    std::copy(out.begin(), out.end(), cols);
+    return nullptr;
 }

@@ -110,6 +110,7 @@ struct zkh_ctx {
     uint32_t* h_fail = nullptr;                  // pinned mirror
     bool fail_armed = false;                     // an op that may raise it was enqueued since the last check
     std::map<void*, size_t> host_blocks;         // pinned host memory handed to the caller (zkh_host_alloc): ptr -> bytes
+    size_t h2d_bytes = 0;                        // bytes copied host to device so far (zkh_ctx_h2d_bytes)
 };
 
 namespace zkh {

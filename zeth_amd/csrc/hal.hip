@@ -283,6 +283,7 @@ constexpr size_t STAGE_SLOT_WORDS = 16384, STAGE_SLOTS = 64;      // 64 x 64 KiB
 const char* h2d(zkh_ctx* c, uint32_t* dst, const uint32_t* host, size_t n) {
     if (!n) return nullptr;
     bind_thread(c);
+    c->h2d_bytes += n * 4;
     if (n <= STAGE_SLOT_WORDS) {
         ZKH_TRY(ensure_pinned(c, STAGE_SLOT_WORDS * STAGE_SLOTS));
         if (c->stage_used == STAGE_SLOTS) ZKH_TRY(sync_checked(c));
@@ -372,7 +373,54 @@ extern "C" const char* zkh_write_async(zkh_ctx* c, zkh_buf* b, const uint32_t* p
     }
     ZKH_REQUIRE(inside, "write_async: the source is not inside a zkh_host_alloc block of this context");
     if (n) ZKH_HIP(hipMemcpyAsync(b->ptr() + off, pinned_host, n * 4, hipMemcpyHostToDevice, c->stream));
+    c->h2d_bytes += n * 4;
     return nullptr;
+}
+extern "C" size_t zkh_ctx_h2d_bytes(const zkh_ctx* c) { return c ? c->h2d_bytes : 0; }
+
+// The one owner of a caller's data-trace upload (SegmentProver.seal_host_witness, the sessions' caller-trace path): what the library
+// derives (zkh_circuit_derived_data_columns) does not cross PCIe.  Columns outside that set are copied whole, a run of adjacent ones as
+// one copy; a run of derived columns is one strided copy of its blinding rows [A, n), which the host still supplies.
+extern "C" const char* zkh_upload_data_trace(zkh_ctx* c, const zkh_circuit* circuit, size_t po2, size_t zk_cycles, zkh_buf* data, const uint32_t* host,
+                                             int pinned_async) {
+    ZKH_REQUIRE(c && circuit && data && host, "upload_data_trace: null argument");
+    ZKH_REQUIRE(po2 >= 1 && po2 <= 24 && zk_cycles < ((size_t)1 << po2), "upload_data_trace: po2 %zu / zk_cycles %zu out of range", po2, zk_cycles);
+    const size_t n = (size_t)1 << po2, A = n - zk_cycles, wd = data->len / n;
+    ZKH_REQUIRE(wd * n == data->len, "upload_data_trace: a buffer of %zu words holds no whole columns of %zu rows", data->len, n);
+    std::vector<uint32_t> derived(wd);
+    size_t nd = 0;
+    ZKH_TRY(zkh_circuit_derived_data_columns(circuit, derived.data(), derived.size(), &nd));
+    std::vector<char> is_derived(wd, 0);
+    for (size_t i = 0; i < nd; i++) {
+        ZKH_REQUIRE(derived[i] < wd, "upload_data_trace: derived column %u, the buffer holds %zu columns", derived[i], wd);
+        is_derived[derived[i]] = 1;
+    }
+    bind_thread(c);
+    if (pinned_async) {
+        auto it = c->host_blocks.upper_bound((void*)host);
+        bool inside = false;
+        if (it != c->host_blocks.begin()) {
+            --it;
+            const char* base = (const char*)it->first;
+            inside = (const char*)host >= base && (const char*)(host + data->len) <= base + it->second;
+        }
+        ZKH_REQUIRE(inside, "upload_data_trace: the source is not inside a zkh_host_alloc block of this context");
+    }
+    for (size_t c0 = 0; c0 < wd;) {
+        size_t c1 = c0 + 1;
+        while (c1 < wd && is_derived[c1] == is_derived[c0]) c1++;
+        uint32_t* dst = data->ptr() + c0 * n;
+        const uint32_t* src = host + c0 * n;
+        if (!is_derived[c0]) {
+            ZKH_HIP(hipMemcpyAsync(dst, src, (c1 - c0) * n * 4, hipMemcpyHostToDevice, c->stream));
+            c->h2d_bytes += (c1 - c0) * n * 4;
+        } else if (zk_cycles) {
+            ZKH_HIP(hipMemcpy2DAsync(dst + A, n * 4, src + A, n * 4, zk_cycles * 4, c1 - c0, hipMemcpyHostToDevice, c->stream));
+            c->h2d_bytes += (c1 - c0) * zk_cycles * 4;
+        }
+        c0 = c1;
+    }
+    return pinned_async ? nullptr : sync_checked(c);    // a host pointer that is not pinned is only borrowed for the call
 }
 
 // ---- profiling ----

@@ -156,6 +156,11 @@ ABI = {
     "zkh_derive_multiplicities": (_err, [_vp, _vp, _sz, _sz, _vp, _vp]),
     "zkh_circuit_derives_sorted": (_i, [_vp]),
     "zkh_derive_sorted": (_err, [_vp, _vp, _sz, _sz, _vp, _vp]),
+    "zkh_circuit_derives_columns": (_i, [_vp]),
+    "zkh_derive_columns": (_err, [_vp, _vp, _sz, _sz, _vp, _vp]),
+    "zkh_circuit_derived_data_columns": (_err, [_vp, _u32p, _sz, C.POINTER(_sz)]),
+    "zkh_upload_data_trace": (_err, [_vp, _vp, _sz, _sz, _vp, _u32p, _i]),
+    "zkh_ctx_h2d_bytes": (_sz, [_vp]),
     "zkh_syn_chain_contributions": (_err, [_vp, _vp, C.POINTER(_u64), _u32p, _sz, _sz, _u32p]),
     "zkh_syn_preflight_ram_words": (_sz, []),
     "zkh_syn_preflight": (_err, [_u64, _sz, _sz, _u32p, _u32p, C.POINTER(C.c_double)]),
@@ -336,6 +341,17 @@ class Circuit:
     def derives_sorted(self) -> bool:
         """the arguments (ZKA1 version 3) have a term that is a sorted copy the library derives (zkh_derive_sorted)"""
         return bool(_lib.zkh_circuit_derives_sorted(self.h))
+
+    def derives_columns(self) -> bool:
+        """the arguments (ZKA1 version 4) hold derived-column records the library fills (zkh_derive_columns)"""
+        return bool(_lib.zkh_circuit_derives_columns(self.h))
+
+    def derived_data_columns(self) -> List[int]:
+        """the data columns the library's derives (sorted, columns, multiplicities) write on the active rows, ascending"""
+        cols = np.zeros(max(1, int(self.desc[5])), dtype=np.uint32)
+        n = C.c_size_t()
+        _check(_lib.zkh_circuit_derived_data_columns(self.h, _ptr(cols), cols.size, C.byref(n)))
+        return [int(x) for x in cols[: n.value]]
 
     def jit(self, use_cache: bool = True) -> None:
         """Generate + compile (hipcc --genco per part, in parallel, disk-cached) + attach the straight-line eval_check
@@ -780,6 +796,25 @@ class HipHal:
         """fill the derived multiplicity columns of `data` on the active rows (zkh_derive_multiplicities): raises HalError on a table
         selector other than 0 / 1 or a lookup without a table entry (`data` is then unchanged)"""
         _check(_lib.zkh_derive_multiplicities(self.ctx, circuit.h, po2, zk_cycles, code.h, data.h))
+
+    def derive_columns(self, circuit: Circuit, po2: int, zk_cycles: int, code: Buffer, data: Buffer) -> None:
+        """fill the destination columns of the derived-column records of `data` on the active rows (zkh_derive_columns), after
+        derive_sorted and before derive_multiplicities: raises HalError on a value that does not fit its limbs or on keys that are
+        not in order, naming the lowest (record, row) (`data` is then unchanged)"""
+        _check(_lib.zkh_derive_columns(self.ctx, circuit.h, po2, zk_cycles, code.h, data.h))
+
+    def upload_data_trace(self, circuit: Circuit, po2: int, zk_cycles: int, data: Buffer, host: np.ndarray, pinned_async: bool = True) -> None:
+        """upload a caller's data trace without what the library derives (zkh_upload_data_trace): the other columns whole, the derived
+        ones on their blinding rows only.  pinned_async: `host` is a host_alloc view and the copies are enqueued without a host sync"""
+        if host.dtype != np.uint32 or not host.flags["C_CONTIGUOUS"]:
+            raise HalError("upload_data_trace: the host trace must be a C-contiguous uint32 array")
+        if host.size != data.size():
+            raise HalError(f"upload_data_trace: a host trace of {host.size} words for a buffer of {data.size()}")
+        _check(_lib.zkh_upload_data_trace(self.ctx, circuit.h, po2, zk_cycles, data.h, host.ctypes.data_as(_u32p), int(pinned_async)))
+
+    def h2d_bytes(self) -> int:
+        """bytes this context has copied host to device so far (zkh_ctx_h2d_bytes)"""
+        return int(_lib.zkh_ctx_h2d_bytes(self.ctx))
 
     def derive_sorted(self, circuit: Circuit, po2: int, zk_cycles: int, code: Buffer, data: Buffer) -> None:
         """fill the tuple columns of the derived sorted copies of `data` on the active rows (zkh_derive_sorted), before
