@@ -267,7 +267,27 @@ const char* zkh_derive_sorted(zkh_ctx*, const zkh_circuit*, size_t po2, size_t z
  * without records.  Sessions with caller traces and SegmentProver.seal_host_witness call the three in that order. */
 int zkh_circuit_derives_columns(const zkh_circuit*);
 const char* zkh_derive_columns(zkh_ctx*, const zkh_circuit*, size_t po2, size_t zk_cycles, const zkh_buf* code, zkh_buf* data);
-/* The data columns that zkh_derive_sorted, zkh_derive_columns and zkh_derive_multiplicities write on the active rows: their sorted
+/* Linked accesses (ZKA1 version 5: a record of kind 3 = LINK takes 32 words and follows every LIMBS / ORDER record: kind, L = limb bits
+ * (1..16), nl = limbs (0..4, L nl <= 29), nc = carried columns (1..3), sel (a code column, or 0xffffffff = every active row), 0, the
+ * key's (group, column), three (group, column) pairs of the carried columns c_0 .. c_{nc-1} (c_0 is the clock), 0, 0, then from word 16
+ * the 2 + nc + nl destination data columns linked, last, prev_0 .. prev_{nc-1}, limb_0 .. limb_{nl-1}; unused words 0).  This is the
+ * witness of a memory argument without a sorted copy: every access carries the previous access to its own address.  A row
+ * r < 2^po2 - zk_cycles is an access when its selector is 1.  With x(c, r) the canonical value of a cell, K = x(key, r) and r' the
+ * greatest access below r with key K, zkh_derive_links writes on the access rows
+ *   linked[r] = Montgomery([r' exists]), last[r] = Montgomery([no access above r has key K]),
+ *   prev_j[r] = the raw word of c_j at r' (0 when not linked), limb_j[r] = Montgomery(limb j of d = x(c_0, r) - x(c_0, r') - 1) (0 when
+ *   not linked),
+ * zeros in every destination on the active rows that are no access; the blinding rows are not touched.  The result depends on the
+ * traces alone.  Sources are code or data columns that no derive writes; destinations are data columns that nothing else writes and
+ * that no record and no source term of a sorted copy reads; lookup tuples read them freely, and linked and last (only they) may be
+ * the multiplicity of a term that is not derived.  It FAILS and leaves `data` unchanged when a selector is neither 0 nor 1 (checked
+ * over all records before any clock), when d < 0 ("clock not increasing") or when d >= 2^(L nl); the error names the lowest (record,
+ * row) and the values.  Call it AFTER zkh_derive_columns and BEFORE zkh_derive_multiplicities (the limbs are lookups to be counted).
+ * Like its siblings it is an error on a circuit without LINK records.  Sessions with caller traces and
+ * SegmentProver.seal_host_witness call the four in the order sorted, columns, links, multiplicities. */
+int zkh_circuit_derives_links(const zkh_circuit*);
+const char* zkh_derive_links(zkh_ctx*, const zkh_circuit*, size_t po2, size_t zk_cycles, const zkh_buf* code, zkh_buf* data);
+/* The data columns that zkh_derive_sorted, zkh_derive_columns, zkh_derive_links and zkh_derive_multiplicities write on the active rows: their sorted
  * union in cols[0 .. *n) (cap = room in cols; *n is set even when the call fails for lack of room).
  * zkh_upload_data_trace copies a caller's data trace (`host`, W_data x 2^po2 words) into `data` without what the library derives:
  * columns outside that set whole, runs of adjacent columns as one copy; the derived columns on the blinding rows [2^po2 - zk_cycles,

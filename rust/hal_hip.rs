@@ -358,7 +358,22 @@ impl HipCircuitHal {
         ffi(|| unsafe { sys::zkh_derive_columns(self.hal.ctx.0, self.circuit, po2, sys::ZK_CYCLES, ctrl.raw, data.raw) });
     }
 
-    /// The data columns that the three derives write on the active rows, ascending (`zkh_circuit_derived_data_columns`).
+    /// The arguments (a ZKA1 version-5 blob) hold LINK records that the library fills.
+    pub fn derives_links(&self) -> bool {
+        unsafe { sys::zkh_circuit_derives_links(self.circuit) != 0 }
+    }
+
+    /// Fill the destination columns of the LINK records of `data` on the active rows (`zkh_derive_links`): every memory access gets
+    /// the previous access to its own address (linked, last, the carried values, the limbs of the clock difference).  Call it after
+    /// `derive_columns`, before `derive_multiplicities` (the limbs are lookups to be counted) and before `prove_begin`.  Panics on a
+    /// refused witness (a selector other than 0 / 1, a clock that does not increase, a difference that does not fit its limbs), which
+    /// leaves `data` unchanged.
+    pub fn derive_links(&self, ctrl: &HipBuffer<BabyBearElem>, data: &HipBuffer<BabyBearElem>, steps: usize) {
+        let po2 = steps.trailing_zeros() as usize;
+        ffi(|| unsafe { sys::zkh_derive_links(self.hal.ctx.0, self.circuit, po2, sys::ZK_CYCLES, ctrl.raw, data.raw) });
+    }
+
+    /// The data columns that the four derives write on the active rows, ascending (`zkh_circuit_derived_data_columns`).
     pub fn derived_data_columns(&self) -> Vec<u32> {
         let mut n = 0usize;
         let mut cols = vec![0u32; 1 << 16];

@@ -1,0 +1,409 @@
+"""LINK records (ZKA1 version 5; zeth_amd/circuits/logup.py, csrc/links.hip, csrc/arguments.hip's validator): the blobs of versions
+1..4 word for word what they were, the builder and parser of the version-5 blob, the rules a LINK record must follow (in the builder,
+the parser and the C validator on a GPU-less circuit, with equal messages), the host reference against a walk over the rows with a
+dictionary, and SYN-LOOKUP-linked against the oracle's row checker: the honest witness holds, a row linked forward in time fails on
+that row although the bus still balances, and a wrong previous value unbalances the bus.  No GPU."""
+import hashlib
+import re
+
+import numpy as np
+import pytest
+
+import zko
+from conftest import rand_fp
+from zeth_amd import hal as zhal
+from zeth_amd.circuits import logup, syn_lookup
+from zeth_amd.circuits.desc import GROUP_ACCUM, GROUP_CODE, GROUP_DATA
+from zeth_amd.hal import HalError
+
+P = 2013265921
+ONE = (1 << 32) % P
+TINY = syn_lookup.TINY
+NONE = logup.NONE
+_digest = lambda a: hashlib.sha256(np.ascontiguousarray(a, dtype=np.uint32).tobytes()).hexdigest()[:16]
+
+
+def _enc(x):
+    return (np.asarray(x, dtype=np.uint64) % np.uint64(P) * np.uint64(ONE) % np.uint64(P)).astype(np.uint32)
+
+
+# SYN-LOOKUP TINY as it was before version 5 existed: (version, blob digest, description digest) by build_syn_lookup's switches
+RECORDED = {
+    (): (1, "4d53ba1cd485fcbe", "0654c55c0910907a"), ("derive",): (2, "7458bf0359af39e4", "0654c55c0910907a"),
+    ("sort",): (3, "b0edc4f04cd0c1c1", "0654c55c0910907a"), ("derive", "sort"): (3, "02f530acb4c77398", "0654c55c0910907a"),
+    ("limbs",): (4, "f54a0c6c91fcbb4f", "0654c55c0910907a"), ("derive", "sort", "limbs"): (4, "bf6367e63d07176b", "0654c55c0910907a"),
+    ("order", "sort"): (4, "f9a34d18c3b00efb", "73b59d30142acb22"), ("order", "derive", "sort", "limbs"): (4, "6a441e7376d9add9", "73b59d30142acb22"),
+}
+
+
+def test_versions_1_to_4_are_byte_identical():
+    for switches, want in RECORDED.items():
+        desc, blob = syn_lookup.build_syn_lookup(TINY, **{s: True for s in switches})
+        assert (int(blob[1]), _digest(blob), _digest(desc)) == want, switches
+        assert np.array_equal(logup.Arguments.parse(blob).blob(), blob)
+    code, data, _ = syn_lookup.witness(TINY, 10, 300, seed=5)                # the default witness, too
+    assert (_digest(code), _digest(data)) == ("05d3073fd18abae7", "aa887d9a3cfaa021")
+
+
+# ---- the version-5 blob ----
+N_TERMS = 5
+REC_AT = [logup.ARGS_HEADER + 16 * N_TERMS + off for off in (0, 16, 48)]    # record 0: LIMBS (16 words); records 1, 2: LINK (32 words)
+SIZES = (8, 6, 40)
+
+
+def _term(i, w):
+    return logup.ARGS_HEADER + logup.TERM_WORDS * i + w
+
+
+def _rec(i, w):
+    return REC_AT[i] + w
+
+
+def _builder():
+    b = logup.LogupBuilder(SIZES, (4, 8))
+    b.term(0, [(GROUP_DATA, 0), (GROUP_DATA, 1)], tag=1)                                          # term 0
+    b.term(0, [(GROUP_DATA, 2), (GROUP_DATA, 3)], sign=-1, tag=1, sorted_from=0, sort_keys=(0, 1))  # term 1: sorted columns 2, 3
+    b.term(1, [(GROUP_CODE, 1)], sign=-1, mult=(GROUP_DATA, 4), tag=0, derive=True)               # term 2: derived multiplicity 4
+    r1 = b.derive_links(3, (GROUP_DATA, 8), [(GROUP_DATA, 9), (GROUP_DATA, 10)], [11, 12, 13, 14, 15, 16, 17], 8)     # record 1
+    r0 = b.derive_limbs((GROUP_CODE, 2), [5, 6, 7], 5)                                            # record 0: it goes before the LINKs
+    r2 = b.derive_links(None, (GROUP_CODE, 4), [(GROUP_DATA, 18)], [19, 20, 21], 4)               # record 2: no selector, no limbs
+    b.term(1, [(GROUP_DATA, 8), (GROUP_DATA, 14), (GROUP_DATA, 13)], sign=-1, mult=(GROUP_DATA, 11), tag=2)   # term 3: -linked (key, prev)
+    b.term(1, [(GROUP_DATA, 15)], tag=0)                                                          # term 4: a lookup reads a limb
+    return b, (r0, r1, r2)
+
+
+def _all():
+    b, _ = _builder()
+    return b.finish_all(b.arguments(b.true(), b.get(GROUP_CODE, 0), b.get(GROUP_CODE, 0), b.get(GROUP_CODE, 0)))
+
+
+def test_builder_round_trips_version_5():
+    b, (r0, r1, r2) = _builder()
+    assert b.records == [r0, r1, r2]
+    assert (r1.kind, r1.nc, r1.nl, r1.linked, r1.last, r1.prevs, r1.limbs) == (logup.KIND_LINK, 2, 3, 11, 12, (13, 14), (15, 16, 17))
+    assert (r2.nc, r2.nl, r2.sel, r2.limbs) == (1, 0, None, ())
+    a = b.args()
+    blob = a.blob()
+    assert blob[1] == 5 and blob[6] == 3 and blob[7] == 0 and blob.size == REC_AT[2] + 32
+    assert list(blob[_rec(0, 0):_rec(1, 0)]) == [1, 5, 3, 1, GROUP_CODE, 2, 0, 0, 5, 6, 7, 0, 0, 0, 0, 0]
+    assert list(blob[_rec(1, 0):_rec(2, 0)]) == [3, 8, 3, 2, 3, 0, GROUP_DATA, 8, GROUP_DATA, 9, GROUP_DATA, 10, 0, 0, 0, 0,
+                                                 11, 12, 13, 14, 15, 16, 17] + [0] * 9
+    assert list(blob[_rec(2, 0):]) == [3, 4, 0, 1, NONE, 0, GROUP_CODE, 4, GROUP_DATA, 18, 0, 0, 0, 0, 0, 0, 19, 20, 21] + [0] * 13
+    back = logup.Arguments.parse(blob)
+    assert back.version == 5 and back.records == [r0, r1, r2] and back.terms == a.terms
+    assert np.array_equal(back.blob(), blob)
+    plain = back.plain()
+    assert plain.version == 1 and not plain.records and plain.blob()[6] == 0
+    with pytest.raises(ValueError, match="167 words for 5 terms and 3 records"):
+        logup.Arguments.parse(blob[:-1])
+    v4 = blob.copy()
+    v4[1] = 4                                                                # version 4 knows no 32-word record
+    with pytest.raises(ValueError, match="168 words for 5 terms and 3 records"):
+        logup.Arguments.parse(v4)
+    # a blob without LINK records stays version 4
+    b4 = logup.LogupBuilder(SIZES, (4, 8))
+    b4.term(0, [(GROUP_DATA, 0)], tag=1)
+    b4.derive_limbs((GROUP_CODE, 2), [5, 6, 7], 5)
+    assert b4.args().blob()[1] == 4
+
+
+RANGE = r" \(1\.\.3 carried columns, 0\.\.4 limbs of 1\.\.16 bits, at most 29 bits in all\)"
+RESERVED = r"a reserved word of a LINK is not 0 \(words 5, 14, 15, the unused carried pairs and the unused destination words\)"
+# (edits of the blob of `_all()`, the message of the parser and of the C validator), in the order of the rules
+BLOB_EDITS = [
+    ([(_rec(1, 3), 0)], "record 1: a LINK of 0 carried columns and 3 limbs of 8 bits" + RANGE),
+    ([(_rec(1, 3), 4)], "record 1: a LINK of 4 carried columns and 3 limbs of 8 bits"),
+    ([(_rec(1, 1), 0)], "record 1: a LINK of 2 carried columns and 3 limbs of 0 bits"),
+    ([(_rec(1, 1), 17)], "record 1: a LINK of 2 carried columns and 3 limbs of 17 bits"),
+    ([(_rec(2, 2), 5)], "record 2: a LINK of 1 carried columns and 5 limbs of 4 bits"),
+    ([(_rec(1, 1), 10)], "record 1: a LINK of 2 carried columns and 3 limbs of 10 bits"),          # 30 bits
+    ([(_rec(1, 5), 1)], "record 1: " + RESERVED),
+    ([(_rec(1, 14), 1)], "record 1: a reserved word of a LINK is not 0"),
+    ([(_rec(1, 15), 7)], "record 1: a reserved word of a LINK is not 0"),
+    ([(_rec(1, 12), GROUP_DATA)], "record 1: a reserved word of a LINK is not 0"),               # the unused third carried pair
+    ([(_rec(2, 11), 1)], "record 2: a reserved word of a LINK is not 0"),
+    ([(_rec(1, 23), 22)], "record 1: a reserved word of a LINK is not 0"),                       # an unused destination word
+    ([(_rec(2, 31), 1)], "record 2: a reserved word of a LINK is not 0"),
+    ([(_rec(1, 2), 2)], "record 1: a reserved word of a LINK is not 0"),                         # one limb fewer: its last destination is left over
+    ([(_rec(1, 6), GROUP_ACCUM)], r"record 1: source \(0, 8\) is not a code or data column"),
+    ([(_rec(1, 10), 3)], r"record 1: source \(3, 10\) is not a code or data column"),
+    ([(_rec(1, 17), 11)], r"record 1: its destination \(data 11\) appears twice"),
+    ([(_rec(1, 7), 2)], r"record 1: its source \(data 2\) is written by the sorted copy term 1 \(a LINK reads what no derive writes\)"),
+    ([(_rec(1, 9), 5)], r"record 1: its source \(data 5\) is a destination of record 0 \(records never chain\)"),
+    ([(_rec(1, 9), 12)], r"record 1: its source \(data 12\) is a destination of record 1"),       # its own
+    ([(_rec(1, 11), 19)], r"record 1: its source \(data 19\) is a destination of record 2"),
+    ([(_rec(1, 9), 4)], r"record 1: its source \(data 4\) is the derived multiplicity of term 2"),
+    ([(_rec(1, 18), 6)], r"record 1: its destination \(data 6\) is also written by record 0"),
+    ([(_rec(2, 16), 17)], r"record 1: its destination \(data 17\) is also written by record 2"),
+    ([(_rec(1, 18), 3)], r"record 1: its destination \(data 3\) is written by the sorted copy term 1"),
+    ([(_rec(1, 18), 4)], r"record 1: its destination \(data 4\) is the derived multiplicity of term 2"),
+    ([(_rec(0, 4), GROUP_DATA), (_rec(0, 5), 12)], r"record 1: its destination \(data 12\) is read by record 0 \(the links run after the columns, and never chain\)"),
+    ([(_rec(2, 9), 16)], r"record 1: its destination \(data 16\) is read by record 2"),
+    ([(_rec(1, 18), 1)], r"record 1: its destination \(data 1\) is read by term 0, the source of a sorted copy \(the sort runs first\)"),
+    ([(_term(3, 4), 13)], r"record 1: its destination \(data 13\) is the multiplicity of term 3 \(of a LINK's destinations only linked and last may be\)"),
+    ([(_term(3, 4), 17)], r"record 1: its destination \(data 17\) is the multiplicity of term 3"),
+    ([(_term(3, 4), 21)], r"record 2: its destination \(data 21\) is the multiplicity of term 3"),
+]
+# ... and what only a validator that knows the circuit can refuse (the builder and the C validator)
+SHAPE_EDITS = [
+    ([(_rec(1, 4), 6)], "record 1: selector 6 is not a code column"),
+    ([(_rec(1, 7), 40)], r"record 1: source \(2, 40\) is not a code or data column"),
+    ([(_rec(2, 7), 6)], r"record 2: source \(1, 6\) is not a code or data column"),
+    ([(_rec(1, 20), 40)], "record 1: destination 40 is not a data column"),
+]
+# ... and what the rules allow
+GOOD_EDITS = [
+    [(_term(3, 4), 12)],                                                                         # `last` as a multiplicity
+    [(_term(3, 4), 20)],                                                                         # ... and that of the other record
+    [(_rec(1, 4), NONE)],                                                                        # no selector
+    [(_rec(1, 6), GROUP_CODE), (_rec(1, 7), 5)],                                                 # a code key
+    [(_rec(2, 9), 9)],                                                                           # two records read one source
+    [(_rec(1, 1), 9)],                                                                           # 27 bits
+    [(_term(4, 9), 13)],                                                                         # a lookup reads prev_0
+]
+
+
+def _edited(blob, edit):
+    bad = blob.copy()
+    for w, v in edit:
+        bad[w] = v
+    return bad
+
+
+def _late(blob):
+    """the same records with the LIMBS record after the first LINK record"""
+    return np.concatenate([blob[:REC_AT[0]], blob[REC_AT[1]:REC_AT[2]], blob[REC_AT[0]:REC_AT[1]], blob[REC_AT[2]:]])
+
+
+LATE = r"record 1: a LIMBS / ORDER record after the LINK record 0 \(LINK records come last\)"
+
+
+def test_parser_refuses_every_rule():
+    _, blob = _all()
+    assert blob.size == REC_AT[2] + 32 and blob[6] == 3 and blob[1] == 5
+    for edit, msg in BLOB_EDITS:
+        with pytest.raises(ValueError, match="ZKA1: " + msg):
+            logup.Arguments.parse(_edited(blob, edit))
+    with pytest.raises(ValueError, match="ZKA1: " + LATE):
+        logup.Arguments.parse(_late(blob))
+    for edit in GOOD_EDITS:
+        a = logup.Arguments.parse(_edited(blob, edit))
+        assert np.array_equal(a.blob(), _edited(blob, edit))
+    for edit, msg in SHAPE_EDITS:                                           # with the circuit's widths the same function refuses these
+        a = logup.Arguments.parse(_edited(blob, edit))
+        assert logup.check_links(a.terms, a.records) is None
+        assert re.search(msg, logup.check_links(a.terms, a.records, SIZES))
+
+
+def test_builder_refuses_and_keeps_its_state():
+    b, _ = _builder()
+    n = len(b.records)
+    with pytest.raises(ValueError, match=r"record 1: its destination \(data 17\) is also written by record 3"):
+        b.derive_links(None, (GROUP_DATA, 8), [(GROUP_DATA, 9)], [17, 23, 24], 8)
+    with pytest.raises(ValueError, match="record 3: a LINK of 1 carried columns and 2 limbs of 15 bits"):
+        b.derive_links(None, (GROUP_DATA, 8), [(GROUP_DATA, 9)], [22, 23, 24, 25, 26], 15)
+    with pytest.raises(ValueError, match="record 3: selector 6 is not a code column"):
+        b.derive_links(6, (GROUP_DATA, 8), [(GROUP_DATA, 9)], [22, 23, 24], 8)
+    with pytest.raises(ValueError, match=r"record 1: its destination \(data 13\) is the multiplicity of term 5"):
+        b.term(0, [(GROUP_DATA, 30)], sign=-1, mult=(GROUP_DATA, 13), tag=3)
+    assert len(b.records) == n and len(b.terms) == 5
+    wide = logup.Link(None, (GROUP_DATA, 8), ((GROUP_DATA, 9),), 15, 2, (22, 23, 24, 25, 26))
+    with pytest.raises(ValueError, match="link_constraints: 2 limbs of 15 bits exceed 29 bits"):
+        b.link_constraints(b.true(), wide)
+    with pytest.raises(ValueError, match="not a LINK record"):
+        b.link_constraints(b.true(), b.records[0])
+
+
+def _c_set(hc, blob):
+    b = np.ascontiguousarray(blob, dtype=np.uint32)
+    zhal._check(zhal._lib.zkh_circuit_set_arguments(hc.h, zhal._ptr(b), b.size))
+
+
+def _derived(hc):
+    cols, n = np.zeros(64, dtype=np.uint32), zhal.C.c_size_t()
+    zhal._check(zhal._lib.zkh_circuit_derived_data_columns(hc.h, zhal._ptr(cols), cols.size, zhal.C.byref(n)))
+    return [int(x) for x in cols[:n.value]]
+
+
+def test_c_validator_on_a_gpu_less_circuit_gives_the_same_messages():
+    desc, blob = _all()
+    hc = zhal.HostCircuit(desc)
+    _c_set(hc, blob)
+    assert zhal._lib.zkh_circuit_derives_links(hc.h) == 1 and zhal._lib.zkh_circuit_derives_columns(hc.h) == 1
+    assert _derived(hc) == [2, 3, 4, 5, 6, 7] + list(range(11, 18)) + [19, 20, 21]
+    for edit, msg in BLOB_EDITS + SHAPE_EDITS:
+        with pytest.raises(HalError, match="set_arguments: " + msg):
+            _c_set(hc, _edited(blob, edit))
+    with pytest.raises(HalError, match="set_arguments: " + LATE):
+        _c_set(hc, _late(blob))
+    with pytest.raises(HalError, match="167 words for 5 terms and 3 records"):
+        _c_set(hc, blob[:-1])
+    v4 = blob.copy()
+    v4[1] = 4
+    with pytest.raises(HalError, match="168 words for 5 terms and 3 records"):
+        _c_set(hc, v4)
+    assert _derived(hc)[-1] == 21                                            # a refused blob leaves the circuit's arguments as they were
+    for edit in GOOD_EDITS:
+        _c_set(hc, _edited(blob, edit))
+    _c_set(hc, logup.Arguments.parse(blob).plain().blob())
+    assert zhal._lib.zkh_circuit_derives_links(hc.h) == 0 and _derived(hc) == []
+    # versions 1 .. 4 derive no link
+    for kw in ({}, dict(derive=True), dict(sort=True), dict(limbs=True)):
+        d4, b4 = syn_lookup.build_syn_lookup(TINY, **kw)
+        h4 = zhal.HostCircuit(d4)
+        _c_set(h4, b4)
+        assert zhal._lib.zkh_circuit_derives_links(h4.h) == 0
+
+
+# ---- the reference against a walk over the rows ----
+def _walk(rec, A, code, data, n):
+    """the destinations of one LINK record over the active rows, the slow way: one access after another, the last access to every key
+    in a dictionary -> {column: A words}"""
+    groups = {GROUP_CODE: code.reshape(-1, n), GROUP_DATA: data.reshape(-1, n)}
+    rinv = pow(ONE, -1, P)
+    x = lambda gc, r: int(groups[gc[0]][gc[1], r]) % P * rinv % P
+    out = {c: np.zeros(A, dtype=np.uint32) for c in rec.dsts}
+    seen = {}
+    for r in range(A):
+        if rec.sel is not None and x((GROUP_CODE, rec.sel), r) != 1:
+            continue
+        key = x(rec.key, r)
+        out[rec.last][r] = ONE
+        if key in seen:
+            q = seen[key]
+            out[rec.last][q] = 0
+            out[rec.linked][r] = ONE
+            for c, src in zip(rec.prevs, rec.carried):
+                out[c][r] = groups[src[0]][src[1], q]
+            d = x(rec.carried[0], r) - x(rec.carried[0], q) - 1
+            assert 0 <= d < 1 << (rec.limb_bits * rec.nl)
+            for j, c in enumerate(rec.limbs):
+                out[c][r] = (d >> (j * rec.limb_bits)) % (1 << rec.limb_bits) * ONE % P
+        seen[key] = r
+    return out
+
+
+@pytest.mark.parametrize("po2,zk,seed", [(6, 3, 1), (8, 40, 2), (10, 300, 3)])
+def test_reference_links_equals_a_dictionary_walk(po2, zk, seed):
+    rng = np.random.default_rng(seed)
+    n, A = 1 << po2, (1 << po2) - zk
+    _, blob = _all()
+    args = logup.Arguments.parse(blob)
+    code, data = rand_fp(rng, SIZES[1], n), rand_fp(rng, SIZES[2], n)
+    code[3, :A] = _enc(rng.random(A) < 0.5)                                  # record 1's selector
+    data[8, :A] = _enc(rng.integers(0, 7, A))                                # its key ...
+    code[4, :A] = _enc(rng.integers(0, 1 << 31, 9)[rng.integers(0, 9, A)] % P)           # ... and record 2's
+    data[9, :A] = _enc(np.cumsum(rng.integers(1, 1 << 12, A)))               # record 1's clock: increasing, differences below 2^24
+    data[18, :A] = _enc(np.arange(A))                                        # record 2 has no limbs: the clock differs by exactly 1 ...
+    same = {}
+    for r in range(A):                                                       # ... so it counts the accesses to its key
+        k = int(code[4, r])
+        same[k] = same.get(k, -1) + 1
+        data[18, r] = _enc(same[k])
+    for col in (code[4], data[8], data[9], data[18]):                        # raw words >= P next to their residues
+        col[:A][rng.random(A) < 0.3] += np.uint32(P)
+    code, data = code.reshape(-1), data.reshape(-1)
+    got = logup.reference_links(args, po2, zk, code, data).reshape(-1, n)
+    want = data.reshape(-1, n).copy()
+    for rec in args.records[1:]:
+        for c, v in _walk(rec, A, code, data, n).items():
+            want[c, :A] = v
+    assert np.array_equal(got, want)
+    assert (got[11, :A] == ONE).sum() > A // 4 and 1 <= (got[12, :A] == ONE).sum() <= 7 and (got[19, :A] == ONE).sum() >= A - 9
+
+
+def test_reference_links_refuses_as_documented():
+    po2, zk = 8, 40
+    n, A = 1 << po2, (1 << po2) - zk
+    _, blob = _all()
+    args = logup.Arguments.parse(blob)
+    rng = np.random.default_rng(4)
+    code, data = rand_fp(rng, SIZES[1], n), rand_fp(rng, SIZES[2], n)
+    code[3, :A], code[4, :A], data[8, :A] = ONE, _enc(np.arange(A)), _enc(5)
+    data[9, :A] = _enc(10 * np.arange(A))
+    good = logup.reference_links(args, po2, zk, code.reshape(-1), data.reshape(-1))
+    assert not np.array_equal(good, data.reshape(-1))
+    bad = data.copy()
+    bad[9, 100], bad[9, 60] = _enc(3), _enc(691)
+    with pytest.raises(logup.ReferenceError, match=re.escape("record 1 at row 61: clock not increasing (610 after 691 at row 60)")):
+        logup.reference_links(args, po2, zk, code.reshape(-1), bad.reshape(-1))
+    bad[9, 60] = _enc(600)
+    with pytest.raises(logup.ReferenceError, match=re.escape("record 1 at row 100: clock not increasing (3 after 990 at row 99)")):
+        logup.reference_links(args, po2, zk, code.reshape(-1), bad.reshape(-1))
+    bad[9, 100] = _enc(990 + (1 << 24) + 1)
+    with pytest.raises(logup.ReferenceError, match=re.escape(f"record 1 at row 100: the clock difference {1 << 24} (after row 99) does not fit 3 limbs of 8 bits")):
+        logup.reference_links(args, po2, zk, code.reshape(-1), bad.reshape(-1))
+    sel = code.copy()
+    sel[3, 7], sel[3, 5] = _enc(2), _enc(9)                                  # the selector is named before the clock, whatever the row
+    with pytest.raises(logup.ReferenceError, match=re.escape("record 1 at row 5: selector 9, not 0 or 1")):
+        logup.reference_links(args, po2, zk, sel.reshape(-1), bad.reshape(-1))
+
+
+# ---- SYN-LOOKUP-linked against the oracle's row checker ----
+def _mix(seed):
+    return np.random.default_rng(seed).integers(0, P, 8, dtype=np.uint64).astype(np.uint32)
+
+
+def test_syn_lookup_linked_shape_and_switches():
+    desc, blob = syn_lookup.syn_lookup_tiny_linked()
+    a = logup.Arguments.parse(blob)
+    assert (int(desc[5]), len(a.terms), a.k, a.version, len(a.records)) == (21, 15, 5, 5, 1)
+    assert syn_lookup.link_layout(2, 4, 1) == [[11, 12, 13, 14, 15, 16, 17, 18, 19, 20]]
+    assert a.records[0] == logup.Link(None, (GROUP_DATA, 11), ((GROUP_DATA, 13), (GROUP_DATA, 12)), 4, 3, (14, 15, 17, 16, 18, 19, 20))
+    mem = [(t.sign, t.mult, tuple(c for _, c in t.tuple_cols)) for t in a.terms if t.tag == 1]
+    assert mem == [(1, None, (11, 12, 13)), (-1, (GROUP_DATA, 14), (11, 16, 17)), (-1, (GROUP_DATA, 15), (11, 12, 13))]
+    assert max(logup.column_degree(ts) for ts in a.by_column()) <= 5
+    assert not np.array_equal(desc, syn_lookup.syn_lookup_tiny()[0])
+    fdesc, fblob = syn_lookup.syn_lookup_linked()
+    assert int(fdesc[5]) == 91 and logup.Arguments.parse(fblob).version == 5
+    d2, b2 = syn_lookup.build_syn_lookup(TINY, link=True, derive=True, limbs=True)
+    assert np.array_equal(d2, desc) and np.array_equal(logup.Arguments.parse(b2).plain().blob(), a.plain().blob())
+    for kw in (dict(sort=True), dict(order=True), dict(sort=True, order=True)):
+        with pytest.raises(ValueError, match="link=True has no sorted copy"):
+            syn_lookup.build_syn_lookup(TINY, link=True, **kw)
+    po2, zk = 10, 300
+    n, A = 1 << po2, (1 << po2) - zk
+    code, full, out = syn_lookup.witness(TINY, po2, zk, seed=5, addr_range=64, link=True)
+    for off, cols in (("limbs", list(range(2, 10))), ("link", list(range(14, 21))), ("count", [10])):
+        kw = dict(link=True)
+        kw[off] = False
+        c2, d2, _ = syn_lookup.witness(TINY, po2, zk, seed=5, addr_range=64, **kw)
+        w, z = full.reshape(-1, n), d2.reshape(-1, n).copy()
+        assert np.array_equal(code, c2) and not z[cols, :A].any() and w[cols, :A].any()
+        z[cols, :A] = w[cols, :A]
+        assert np.array_equal(w, z)                                         # every other word, the blinding rows included
+
+
+@pytest.mark.parametrize("po2,zk,addr_range", [(8, 40, 16), (10, 300, 64), (12, 1994, 5)])
+def test_linked_witness_satisfies_the_oracle_and_a_forward_link_fails_on_its_row(oracle, po2, zk, addr_range):
+    desc, blob = syn_lookup.build_syn_lookup(TINY, link=True, derive=True, limbs=True)
+    args = logup.Arguments.parse(blob)
+    n, A = 1 << po2, (1 << po2) - zk
+    code, data, out = syn_lookup.witness(TINY, po2, zk, seed=po2, addr_range=addr_range, link=True)
+    _, zero, _ = syn_lookup.witness(TINY, po2, zk, seed=po2, addr_range=addr_range, link=False, count=False, limbs=False)
+    chain = logup.reference_links(args, po2, zk, code, logup.reference_columns(args, po2, zk, code, zero))
+    chain = logup.reference_multiplicities(args, po2, zk, code, chain)
+    assert np.array_equal(chain, data)                                        # columns -> links -> multiplicities = the host-made witness
+    mix = _mix(po2)
+    accum, total = logup.reference_accumulate(args, po2, zk, code, data, mix)
+    assert total == [0, 0, 0, 0]
+    oc = zko.OracleCircuit(oracle, desc)
+    assert oc.check_rows(po2, accum, code, data, out, mix) == -1
+    # a forward link: the bus still balances once the forged limbs are counted, and only the row's limb constraint objects
+    lcols = syn_lookup.link_layout(TINY.n_words, TINY.n_limbs, TINY.n_mem)[0]
+    w = data.reshape(-1, n)
+    row = next(r for r in range(A // 2, A) if (w[lcols[0], r + 1:A] == w[lcols[0], r]).any())
+    forged = syn_lookup.relink_row(TINY, data, po2, row).reshape(-1, n)
+    assert not np.array_equal(forged.reshape(-1), data)
+    forged[10, :A] = 0
+    counted = logup.Arguments.parse(syn_lookup.build_syn_lookup(TINY, link=True, derive=True)[1])
+    forged = logup.reference_multiplicities(counted, po2, zk, code, forged.reshape(-1))
+    accum, total = logup.reference_accumulate(args, po2, zk, code, forged, mix)
+    assert total == [0, 0, 0, 0]
+    assert oc.check_rows(po2, accum, code, forged, out, mix) == row
+    # a wrong previous value: every constraint of the row holds, the bus does not balance
+    wrong = data.reshape(-1, n).copy()
+    r2 = next(r for r in range(A // 3, A) if w[lcols[3], r] == ONE)
+    wrong[lcols[5], r2] = (int(wrong[lcols[5], r2]) + ONE) % P
+    with pytest.raises(logup.ReferenceError, match="the bus does not balance"):
+        logup.reference_accumulate(args, po2, zk, code, wrong.reshape(-1), mix)

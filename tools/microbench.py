@@ -2,7 +2,8 @@
 """Per-op micro-benchmarks M1..M8 of SURVEY.md §8d (+ M9: the trace-driven witness, row f1; M10: the built-in accumulate of SYN-LOOKUP's
 arguments and its share of that circuit's seal; M11 / M11w: derived lookup multiplicities of SYN-LOOKUP-derived / WIDE; M12: derived sorted copies of SYN-LOOKUP-sorted
 against the host's lexsort + upload; M13: derived columns — the 64 limb columns of SYN-LOOKUP FULL — next to a plain copy of the same
-bytes, and the host-witness seal with its upload) on one MI355X, through the C ABI (HipHal).
+bytes, and the host-witness seal with its upload; M14: linked accesses of SYN-LOOKUP-linked (zkh_derive_links) next to a plain copy of
+the same bytes, to the host's sort + gather + upload, and the host-witness seal with the derive against the host-made columns) on one MI355X, through the C ABI (HipHal).
 
 Each line of output is one JSON object: the op, its shape, the average wall time of one call (stream drained on both
 sides of `reps` back-to-back calls), its ALGORITHMIC bytes (SURVEY.md §8a "B_alg": inputs read once + outputs written
@@ -363,6 +364,73 @@ def main() -> None:
         print(json.dumps({"bench": "M13seal", "derive_columns_ms": round(dt * 1e3, 4), "steps_ms": steps, "copy_ms": round(dt_copy * 1e3, 4),
                           "vs_copy": round(dt_copy / dt, 3), "host_witness_seal_ms": round(dt_seal * 1e3, 3), "h2d_bytes_per_seal": crossed,
                           "full_trace_bytes": 4 * (code_h.size + data_h.size), "derived_columns": len(circuit.derived_data_columns())}), flush=True)
+    if want("M14"):
+        # linked accesses (zkh_derive_links) of SYN-LOOKUP-linked FULL: the accesses sorted by address, then the check and the write pass
+        # (7 destination columns), per step and in total, next to zkh_eltwise_copy_elem moving the same bytes and to the host's way:
+        # reference_links' stable sort + gather over the decoded columns and the upload of the 7 columns; then the host-witness seal with
+        # the derive against the same tree uploading the host-made columns (the flag-free blob)
+        from zeth_amd.circuits import logup, syn_lookup
+        from zeth_amd.prover import Segment, SegmentProver
+        zk = 1994
+        A = n - zk
+        shape = syn_lookup.FULL
+        desc, blob = syn_lookup.build_syn_lookup(shape, link=True)
+        largs = logup.Arguments.parse(blob)
+        circuit = hal.load_circuit(desc, jit=False)
+        circuit.set_arguments(blob)
+        code_h, full_h, out = syn_lookup.witness(shape, args.po2, zk, seed=14, link=True)
+        bare_h = full_h.reshape(-1, n).copy()
+        bare_h[circuit.derived_data_columns(), :A] = 0
+        bare_h = bare_h.reshape(-1)
+        code, data = hal.alloc_elem("code", code_h.size), hal.alloc_elem("data", bare_h.size)
+        code.write(code_h)
+        data.write(bare_h)
+        derive = lambda: hal.derive_links(circuit, args.po2, zk, code, data)
+        dt = timed(hal, derive, args.reps)
+        assert np.array_equal(data.to_vec(), full_h)
+        # the key read twice (live bits, pack) and 12 B of (key, row) per item and pass; per pass of k_links (key, row) 12 B, the clock at two
+        # rows; the write pass also reads the carried value and writes 7 columns
+        passes = 3
+        alg = A * (4 * 2 + 12 + passes * 3 * 12 + 2 * (12 + 8) + 4 + 4 * 7)
+        line("M14", "derive links (SYN-LOOKUP-linked: prev access by address; sort + check + write pass)", f"{A} accesses -> 2^{args.po2}", dt, alg)
+        hal.prof_enable(True)
+        hal.prof_reset()
+        for _ in range(args.reps):
+            derive()
+        hal.sync()
+        steps = {r["name"]: round(r["total_ms"] / max(r["calls"], 1), 4) for r in hal.prof_get()
+                 if r["calls"] and r["name"].startswith(("sort_", "links_"))}
+        hal.prof_enable(False)
+        src, dst = upload(hal, rng, "m14src", alg // 8), hal.alloc_elem("m14dst", alg // 8)
+        dt_copy = timed(hal, lambda: hal.eltwise_copy_elem(dst, src), args.reps)
+        line("M14copy", "eltwise_copy_elem of the same bytes (the streaming yardstick)", f"{alg // 8} words", dt_copy, alg)
+        del src, dst
+        t0 = time.perf_counter()
+        want_h = logup.reference_links(largs, args.po2, zk, code_h, bare_h)
+        dt_host = time.perf_counter() - t0
+        assert np.array_equal(want_h, full_h)
+        cols = np.ascontiguousarray(want_h.reshape(-1, n)[circuit.derived_data_columns(), :A])
+        up = hal.alloc_elem("links", cols.size)
+        dt_up = timed(hal, lambda: up.write(cols.reshape(-1)), args.reps)
+        seg = Segment(index=0, po2=args.po2, noise_seed=0x2E80)
+        seals = {}
+        for name, b, host in (("derive", blob, bare_h), ("host_made", largs.plain().blob(), full_h)):
+            prover = SegmentProver(hal, desc, arguments=b)
+            hcode, hdata = hal.host_alloc(code_h.size), hal.host_alloc(host.size)
+            hcode[:] = code_h
+            hdata[:] = host
+            before = hal.h2d_bytes()
+            prover.seal_host_witness(seg, hcode, hdata, out)
+            hal.sync()
+            crossed = hal.h2d_bytes() - before
+            dt_seal = timed(hal, lambda: prover.seal_host_witness(seg, hcode, hdata, out), args.reps)
+            hal.host_free(hcode)
+            hal.host_free(hdata)
+            seals[name] = {"seal_ms": round(dt_seal * 1e3, 3), "h2d_bytes_per_seal": crossed}
+        sort_ms = sum(v for k, v in steps.items() if k.startswith("sort_"))
+        print(json.dumps({"bench": "M14links", "derive_links_ms": round(dt * 1e3, 4), "steps_ms": steps, "sort_share": round(sort_ms / max(sum(steps.values()), 1e-9), 3),
+                          "copy_ms": round(dt_copy * 1e3, 4), "vs_copy": round(dt_copy / dt, 3), "host_reference_links_ms": round(dt_host * 1e3, 2),
+                          "host_upload_ms": round(dt_up * 1e3, 3), "host_witness_seal": seals}), flush=True)
     hal.close()
 
 

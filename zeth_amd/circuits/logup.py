@@ -39,6 +39,13 @@ ZKA1 layout (u32 words; canonical integers, not Montgomery words)::
       kind (1 = LIMBS, 2 = ORDER), L = limb bits (1..16), nl = limbs (1..8, L nl <= 32), n_src (LIMBS: 1; ORDER: 1 or 2),
       two (group, column) source pairs (the unused one 0), then 8 destination data columns (ORDER with two keys: the flag column
       first, then the nl <= 7 limb columns; unused words 0).  The builder writes version 4 only when a record exists.
+    Version 5: as version 4, and a record may be of kind 3 = LINK, which takes two 16-word slots (32 words; n_records counts records, not
+    slots).  LINK records come after every LIMBS / ORDER record.  Its words:
+      [0] kind = 3   [1] L = limb bits (1..16)   [2] nl = limbs (0..4, L nl <= 29)   [3] nc = carried columns (1..3)
+      [4] sel (code column or NONE)   [5] reserved = 0   [6], [7] the key's (group, column)
+      [8 + 2j], [9 + 2j] the (group, column) of carried column c_j, j < 3 (unused pairs 0)   [14], [15] reserved = 0
+      [16 ..] the 2 + nc + nl destination data columns: linked, last, prev_0 .. prev_{nc-1}, limb_0 .. limb_{nl-1}; the words after
+      them up to [31] reserved = 0.  The builder writes version 5 only when a LINK record exists.
 
 A derived term is the table side of a lookup (`check_derived`): sign -1, its multiplicity a data column that no tuple and no other
 term names, and every other term of its tag a lookup of sign +1.  Its multiplicity column is then a function of the traces:
@@ -55,7 +62,18 @@ active rows (`reference_columns`).  x = the canonical value of a source cell.  L
 x >= 2^(L nl).  ORDER over keys (k0) or (k0, k1) that are sorted: row 0 gets zeros; on row r >= 1, e = [k0 = k0@1] (two keys; the flag
 column) and d = k0 - k0@1 (one key), or e ? k1 - k1@1 : k0 - k0@1 - 1 (two keys), split into limbs like a LIMBS value; refused when
 d < 0 ("not ordered") or d >= 2^(L nl).  Sources are never destinations (records do not chain) but may be sorted-copy columns: the
-library runs sorted -> columns -> multiplicities, so that a record may read a sorted column and a lookup may count a limb.
+library runs sorted -> columns -> links -> multiplicities, so that a record may read a sorted column and a lookup may count a limb.
+
+A LINK record (`check_links`, zkh_derive_links) gives every memory access the previous access to its own address: the witness of a
+memory argument without a sorted copy.  A row r < A is an ACCESS when its selector is 1 (no selector: every active row); a selector
+other than 0 / 1 is refused.  With x(c, r) the canonical value of a cell, K = x(key, r) and r' the greatest access below r with the
+same K (`reference_links`): linked[r] = [r' exists], last[r] = [no access above r has key K] (Montgomery 0 / 1); prev_j[r] = the raw
+word of carried column c_j at r' (0 when r is not linked); limb_j[r] = limb j of d = x(c_0, r) - x(c_0, r') - 1, c_0 being the clock
+(0 when not linked), refused when d < 0 ("clock not increasing") or d >= 2^(L nl).  Active rows that are no access get zeros in every
+destination.  Selectors are checked, over all records, before any clock.  Sources are columns that no derive writes; the
+destinations are written by nothing else and read by no record and no source term of a sorted copy; lookup tuples read them freely, and
+`linked` and `last` (only they) may be the multiplicity of a term that is not derived: -linked (addr, prev) removes the old tuple from the
+bus and -last (addr, val, clock) pages the final one out.  L nl <= 29 for the reason `order_constraints` gives.
 """
 from __future__ import annotations
 
@@ -259,6 +277,129 @@ def check_columns(terms: Sequence[Term], records: Sequence[Record], group_sizes=
     return None
 
 
+KIND_LINK = 3
+LINK_WORDS = 32
+MAX_CARRIED = 3
+MAX_LINK_LIMBS = 4
+
+
+@dataclass(frozen=True)
+class Link:
+    """A LINK record as the blob holds it (ZKA1 version 5): the fields are the blob's words, `check_links` the rules"""
+    sel: Optional[int]                         # selector code column, or None = 1
+    key: Tuple[int, int]                       # (group, column) of the address
+    carried: Tuple[Tuple[int, int], ...]       # nc (group, column) pairs, c_0 the clock
+    limb_bits: int                             # L
+    nl: int                                    # limb count
+    dsts: Tuple[int, ...]                      # data columns: linked, last, prev_0 .. prev_{nc-1}, limb_0 .. limb_{nl-1}
+    reserved: bool = False                     # a word the format reserves was not 0 (parser only)
+    nc_word: Optional[int] = None              # the blob's nc where it is not len(carried) (parser only: an nc out of range)
+    kind = KIND_LINK
+
+    @property
+    def nc(self) -> int:
+        return len(self.carried) if self.nc_word is None else self.nc_word
+
+    @property
+    def srcs(self) -> Tuple[Tuple[int, int], ...]:
+        return (self.key,) + self.carried
+
+    @property
+    def linked(self) -> int:
+        return self.dsts[0]
+
+    @property
+    def last(self) -> int:
+        return self.dsts[1]
+
+    @property
+    def prevs(self) -> Tuple[int, ...]:
+        return self.dsts[2: 2 + len(self.carried)]
+
+    @property
+    def limbs(self) -> Tuple[int, ...]:
+        return self.dsts[2 + len(self.carried):]
+
+    def n_dsts(self) -> int:
+        return 2 + len(self.carried) + self.nl
+
+    def words(self) -> List[int]:
+        w = [KIND_LINK, self.limb_bits, self.nl, len(self.carried), NONE if self.sel is None else self.sel, 0, self.key[0], self.key[1]]
+        for g, c in self.carried:
+            w += [g, c]
+        w += [0] * (16 - len(w))
+        w += list(self.dsts)
+        return w + [0] * (LINK_WORDS - len(w))
+
+
+def check_links(terms: Sequence[Term], records: Sequence, group_sizes=None) -> Optional[str]:
+    """the first LINK record that breaks a rule, named by its index among all records, or None.  Per LINK record, in this order: (a) the
+    ranges of nc, L, nl and the reserved words; (b) its selector a code column, its sources code or data columns (of the circuit, when
+    `group_sizes` = (accum, code, data) is given), its destinations pairwise distinct data columns; then, per LINK record again: (c) no
+    source is written by a derive: a sorted copy's column, a destination of any record, a derived multiplicity; (d) no destination is
+    written twice: by another record, a sorted copy or a derived multiplicity; (e) no destination is read by any record, by the source
+    term of a sorted copy, or — `linked` and `last` apart — is a term's multiplicity.  Lookup tuples read destinations freely."""
+    links = [(i, r) for i, r in enumerate(records) if isinstance(r, Link)]
+    for i, r in links:
+        if not (1 <= r.nc <= MAX_CARRIED and 1 <= r.limb_bits <= 16 and 0 <= r.nl <= MAX_LINK_LIMBS and r.limb_bits * r.nl <= MAX_ORDER_BITS):
+            return (f"record {i}: a LINK of {r.nc} carried columns and {r.nl} limbs of {r.limb_bits} bits (1..{MAX_CARRIED} carried columns, "
+                    f"0..{MAX_LINK_LIMBS} limbs of 1..16 bits, at most {MAX_ORDER_BITS} bits in all)")
+        if r.reserved or len(r.dsts) != r.n_dsts():
+            return f"record {i}: a reserved word of a LINK is not 0 (words 5, 14, 15, the unused carried pairs and the unused destination words)"
+        if r.sel is not None and (r.sel >= NONE or (group_sizes is not None and not 0 <= r.sel < group_sizes[GROUP_CODE])):
+            return f"record {i}: selector {r.sel} is not a code column"
+        for g, c in r.srcs:
+            if g not in (GROUP_CODE, GROUP_DATA) or (group_sizes is not None and not 0 <= c < group_sizes[g]):
+                return f"record {i}: source ({g}, {c}) is not a code or data column"
+        for e, c in enumerate(r.dsts):
+            if group_sizes is not None and not 0 <= c < group_sizes[GROUP_DATA]:
+                return f"record {i}: destination {c} is not a data column"
+            if c in r.dsts[:e]:
+                return f"record {i}: its destination (data {c}) appears twice"
+    for i, r in links:
+        for g, c in r.srcs:
+            if g != GROUP_DATA:
+                continue
+            for j, t in enumerate(terms):
+                if t.sorted_from is not None and (g, c) in t.tuple_cols:
+                    return f"record {i}: its source (data {c}) is written by the sorted copy term {j} (a LINK reads what no derive writes)"
+            for j, x in enumerate(records):
+                if c in x.dsts:
+                    return f"record {i}: its source (data {c}) is a destination of record {j} (records never chain)"
+            for j, t in enumerate(terms):
+                if t.derive and t.mult == (g, c):
+                    return f"record {i}: its source (data {c}) is the derived multiplicity of term {j}"
+        for e, c in enumerate(r.dsts):
+            for j, x in enumerate(records):
+                if j != i and c in x.dsts:
+                    return f"record {i}: its destination (data {c}) is also written by record {j}"
+            for j, t in enumerate(terms):
+                if t.sorted_from is not None and (GROUP_DATA, c) in t.tuple_cols:
+                    return f"record {i}: its destination (data {c}) is written by the sorted copy term {j}"
+                if t.derive and t.mult == (GROUP_DATA, c):
+                    return f"record {i}: its destination (data {c}) is the derived multiplicity of term {j}"
+            for j, x in enumerate(records):
+                if (GROUP_DATA, c) in x.srcs:
+                    return f"record {i}: its destination (data {c}) is read by record {j} (the links run after the columns, and never chain)"
+            for j, t in enumerate(terms):
+                if t.sorted_from is not None and 0 <= t.sorted_from < len(terms) and (GROUP_DATA, c) in terms[t.sorted_from].tuple_cols:
+                    return f"record {i}: its destination (data {c}) is read by term {t.sorted_from}, the source of a sorted copy (the sort runs first)"
+            for j, t in enumerate(terms):
+                if e >= 2 and t.mult == (GROUP_DATA, c):
+                    return f"record {i}: its destination (data {c}) is the multiplicity of term {j} (of a LINK's destinations only linked and last may be)"
+    return None
+
+
+def _check_records(terms: Sequence[Term], records: Sequence, group_sizes=None) -> Optional[str]:
+    """check_columns over the LIMBS / ORDER records (they come first, so the indices are the blob's), then check_links"""
+    n_cols = sum(not isinstance(r, Link) for r in records)
+    for i, r in enumerate(records[:n_cols]):
+        if isinstance(r, Link):
+            j = next(j for j in range(i, len(records)) if not isinstance(records[j], Link))
+            return f"record {j}: a LIMBS / ORDER record after the LINK record {i} (LINK records come last)"
+    return check_columns(terms, records[:n_cols], group_sizes) or check_links(terms, records, group_sizes)
+
+
 def _by_column(terms: Sequence[Term]) -> List[Term]:
     """the terms sorted by accum column (stable: the blob order), the source indices of sorted copies following their terms"""
     order = sorted(range(len(terms)), key=lambda i: terms[i].col)
@@ -286,6 +427,8 @@ class Arguments:
 
     @property
     def version(self) -> int:
+        if any(isinstance(r, Link) for r in self.records):
+            return 5
         if self.records:
             return 4
         if any(t.sorted_from is not None for t in self.terms):
@@ -308,12 +451,16 @@ class Arguments:
     @staticmethod
     def parse(blob: Sequence[int]) -> "Arguments":
         d = [int(x) for x in np.asarray(blob, dtype=np.uint32)]
-        if len(d) < ARGS_HEADER or d[0] != ARGS_MAGIC or d[1] not in (1, 2, 3, 4):
+        if len(d) < ARGS_HEADER or d[0] != ARGS_MAGIC or d[1] not in (1, 2, 3, 4, 5):
             raise ValueError("not a ZKA1 argument blob")
         version = d[1]
         k, alpha, beta, n = d[2], d[3], d[4], d[5]
         n_rec = d[6] if version >= 4 else 0
-        if len(d) != ARGS_HEADER + TERM_WORDS * n + RECORD_WORDS * n_rec:
+        at, sizes = ARGS_HEADER + TERM_WORDS * n, []
+        for _ in range(n_rec):                                                # a LINK record (version 5) takes two slots
+            sizes.append(LINK_WORDS if version >= 5 and at < len(d) and d[at] == KIND_LINK else RECORD_WORDS)
+            at += sizes[-1]
+        if len(d) != at:
             raise ValueError(f"ZKA1: {len(d)} words for {n} terms" + (f" and {n_rec} records" if version >= 4 else ""))
         terms = []
         for i in range(n):
@@ -337,14 +484,21 @@ class Arguments:
                               derive=version >= 2 and r[7] & 1 == 1, sorted_from=src, sort_keys=keys))
         records = []
         for i in range(n_rec):
-            at = ARGS_HEADER + TERM_WORDS * n + RECORD_WORDS * i
-            r = d[at: at + RECORD_WORDS]
+            at = ARGS_HEADER + TERM_WORDS * n + sum(sizes[:i])
+            r = d[at: at + sizes[i]]
+            if sizes[i] == LINK_WORDS:
+                nc = min(r[3], MAX_CARRIED)
+                n_dst = min(16, 2 + nc + min(r[2], 16))
+                reserved = bool(r[5] or r[14] or r[15] or any(r[8 + 2 * nc:14]) or any(r[16 + n_dst:]))
+                records.append(Link(None if r[4] == NONE else r[4], (r[6], r[7]), tuple((r[8 + 2 * j], r[9 + 2 * j]) for j in range(nc)), r[1], r[2],
+                                    tuple(r[16: 16 + n_dst]), reserved, None if r[3] == nc else r[3]))
+                continue
             n_src = r[3]
             n_dst = min(8, r[2] + (r[0] == KIND_ORDER and n_src == 2))
             reserved = any(r[4 + 2 * min(n_src, 2):8]) or any(r[8 + n_dst:])
             records.append(Record(r[0], r[1], r[2], tuple((r[4 + 2 * j], r[5 + 2 * j]) for j in range(min(n_src, 2))), tuple(r[8: 8 + n_dst]),
                                   reserved, None if n_src <= 2 else n_src))
-        problem = check_sorted(terms) or check_derived(terms) or check_columns(terms, records)
+        problem = check_sorted(terms) or check_derived(terms) or _check_records(terms, records)
         if problem:
             raise ValueError(f"ZKA1: {problem}")
         return Arguments(k, alpha, beta, terms, records)
@@ -402,7 +556,7 @@ class LogupBuilder(CircuitBuilder):
         t = Term(col, tuple((int(g), int(c)) for g, c in tuple_cols), sign, sel, mult, int(tag), bool(derive),
                  None if sorted_from is None else int(sorted_from), tuple(int(x) for x in sort_keys))
         self.terms.append(t)
-        problem = check_sorted(self.terms) or check_derived(self.terms) or check_columns(self.terms, self.records, self.group_sizes)
+        problem = check_sorted(self.terms) or check_derived(self.terms) or _check_records(self.terms, self.records, self.group_sizes)
         if problem:
             self.terms.pop()
             raise ValueError(problem)
@@ -413,11 +567,12 @@ class LogupBuilder(CircuitBuilder):
                              f"selectors and multiplicities per column)")
         return t
 
-    def _record(self, rec: Record) -> Record:
-        self.records.append(rec)
-        problem = check_columns(self.terms, self.records, self.group_sizes)
+    def _record(self, rec):
+        at = len(self.records) if isinstance(rec, Link) else sum(not isinstance(r, Link) for r in self.records)     # LINK records come last
+        self.records.insert(at, rec)
+        problem = _check_records(self.terms, self.records, self.group_sizes)
         if problem:
-            self.records.pop()
+            self.records.pop(at)
             raise ValueError(problem)
         return rec
 
@@ -432,6 +587,34 @@ class LogupBuilder(CircuitBuilder):
         dsts are the limbs (`reference_columns`); keys that are not in order refuse the witness"""
         keys = tuple((int(g), int(c)) for g, c in keys)
         return self._record(Record(KIND_ORDER, int(limb_bits), len(dsts) - (len(keys) == 2), keys, tuple(int(c) for c in dsts)))
+
+    def derive_links(self, sel: Optional[int], key: Tuple[int, int], carried: Sequence[Tuple[int, int]], dsts: Sequence[int], limb_bits: int) -> Link:
+        """the library fills the data columns `dsts` (zkh_derive_links) = linked, last, one prev per carried column, then the limbs of
+        the clock difference, for the accesses (selector code column `sel`, None = every active row) to the address `key`; `carried`
+        are the (group, column) pairs whose value at the previous access is copied, carried[0] the clock (`reference_links`)"""
+        carried = tuple((int(g), int(c)) for g, c in carried)
+        return self._record(Link(None if sel is None else int(sel), (int(key[0]), int(key[1])), carried, int(limb_bits),
+                                 len(dsts) - 2 - len(carried), tuple(int(c) for c in dsts)))
+
+    def link_constraints(self, inner, record: Link):
+        """and onto `inner` (which the caller gates by its body selector) the constraints that tie the LINK `record`'s witness to its
+        row: linked (1 - linked) = 0, last (1 - last) = 0 and sum_j 2^(jL) limb_j = linked (c_0 - prev_0 - 1).  Degree 3 with the caller's
+        gate.  Sound for clocks below 2^29 and limbs range-checked by a lookup, as `order_constraints` is: L nl <= 29."""
+        if not isinstance(record, Link):
+            raise ValueError("link_constraints: not a LINK record")
+        L, nl = record.limb_bits, record.nl
+        if L * nl > MAX_ORDER_BITS:
+            raise ValueError(f"link_constraints: {nl} limbs of {L} bits exceed {MAX_ORDER_BITS} bits (a negative difference must stay out of range)")
+        one = self.const(1)
+        linked, last = self.get(GROUP_DATA, record.linked), self.get(GROUP_DATA, record.last)
+        inner = self.and_eqz(inner, self.mul(linked, self.sub(one, linked)))
+        inner = self.and_eqz(inner, self.mul(last, self.sub(one, last)))
+        total = self.const(0)
+        for j, c in enumerate(record.limbs):
+            v = self.get(GROUP_DATA, c) if j == 0 else self.mul(self.const(1 << (j * L)), self.get(GROUP_DATA, c))
+            total = v if j == 0 else self.add(total, v)
+        d = self.sub(self.sub(self.get(*record.carried[0]), self.get(GROUP_DATA, record.prevs[0])), one)
+        return self.and_eqz(inner, self.sub(total, self.mul(linked, d)))
 
     def order_constraints(self, inner, record: Record):
         """and onto `inner` (which the caller gates by its body selector) the constraints that the keys of the ORDER `record` are in
@@ -778,6 +961,8 @@ def reference_columns(args: Arguments, po2: int, zk_cycles: int, code, data) -> 
     groups = {GROUP_CODE: np.asarray(code, dtype=np.uint32).reshape(-1, n), GROUP_DATA: np.array(data, dtype=np.uint32).reshape(-1, n)}
     out = groups[GROUP_DATA]                                                 # sources are never destinations: no record reads what another wrote
     for i, r in enumerate(args.records):
+        if isinstance(r, Link):                                              # reference_links
+            continue
         L, nl, bits = r.limb_bits, r.nl, r.limb_bits * r.nl
         k = [_dec(groups[g][c, :A]).astype(np.int64) for g, c in r.srcs]
         flag = None
@@ -805,4 +990,60 @@ def reference_columns(args: Arguments, po2: int, zk_cycles: int, code, data) -> 
             out[dsts.pop(0), :A] = _enc(flag).astype(np.uint32)
         for j, c in enumerate(dsts):
             out[c, :A] = _enc((d >> (j * L)) & ((1 << L) - 1)).astype(np.uint32)
+    return out.reshape(-1)
+
+
+def _link_chain(key, rows):
+    """for the access rows `rows` (ascending) with canonical keys `key` (one per access): (prev, last) = the index into `rows` of the
+    previous access to the same key (-1: none), and whether no later access has it — by one stable sort, as the library does"""
+    order = np.argsort(key, kind="stable")
+    sk = key[order]
+    same = sk[1:] == sk[:-1]
+    prev = np.full(len(rows), -1, dtype=np.int64)
+    prev[order[1:][same]] = order[:-1][same]
+    last = np.ones(len(rows), dtype=bool)
+    last[order[:-1][same]] = False
+    return prev, last
+
+
+def reference_links(args: Arguments, po2: int, zk_cycles: int, code, data) -> np.ndarray:
+    """The data trace zkh_derive_links leaves (raw Montgomery words, a copy): every LINK record's destination columns on the active rows
+    (module docstring), rows [A, n) as given.  Raises ReferenceError on a selector other than 0 / 1 (the lowest (record, row) over all
+    records, before any clock is looked at), then on the lowest (record, row) whose clock difference d = c_0 - prev_0 - 1 is negative
+    ("clock not increasing") or does not fit the limbs."""
+    n = 1 << po2
+    A = n - zk_cycles
+    groups = {GROUP_CODE: np.asarray(code, dtype=np.uint32).reshape(-1, n), GROUP_DATA: np.array(data, dtype=np.uint32).reshape(-1, n)}
+    out = groups[GROUP_DATA]                                                 # sources are never destinations
+    links = [(i, r) for i, r in enumerate(args.records) if isinstance(r, Link)]
+    on = {}
+    for i, r in links:
+        sel = np.ones(A, dtype=np.uint64) if r.sel is None else _dec(groups[GROUP_CODE][r.sel, :A])
+        bad = (sel != 0) & (sel != 1)
+        if bad.any():
+            row = int(np.argmax(bad))
+            raise ReferenceError(f"record {i} at row {row}: selector {int(sel[row])}, not 0 or 1")
+        on[i] = np.nonzero(sel == 1)[0]
+    for i, r in links:
+        rows, L, nl = on[i], r.limb_bits, r.nl
+        prev, last = _link_chain(_dec(groups[r.key[0]][r.key[1], rows]), rows)
+        linked = prev >= 0
+        prow = rows[np.where(linked, prev, 0)]
+        g0, c0 = r.carried[0]
+        clock, pclock = _dec(groups[g0][c0, rows]).astype(np.int64), _dec(groups[g0][c0, prow]).astype(np.int64)
+        d = np.where(linked, clock - pclock - 1, 0)
+        bad = (d < 0) | (d >> (L * nl) != 0)
+        if bad.any():
+            j = int(np.argmax(bad))
+            if d[j] < 0:
+                raise ReferenceError(f"record {i} at row {int(rows[j])}: clock not increasing ({int(clock[j])} after {int(pclock[j])} at row {int(prow[j])})")
+            raise ReferenceError(f"record {i} at row {int(rows[j])}: the clock difference {int(d[j])} (after row {int(prow[j])}) does not fit {nl} limbs of {L} bits")
+        vals = [np.where(linked, groups[g][c, prow], 0).astype(np.uint32) for g, c in r.carried]
+        out[list(r.dsts), :A] = 0
+        out[r.linked, rows] = _enc(linked.astype(np.uint64)).astype(np.uint32)
+        out[r.last, rows] = _enc(last.astype(np.uint64)).astype(np.uint32)
+        for c, v in zip(r.prevs, vals):
+            out[c, rows] = v
+        for j, c in enumerate(r.limbs):
+            out[c, rows] = _enc((d >> (j * L)) & ((1 << L) - 1)).astype(np.uint32)
     return out.reshape(-1)

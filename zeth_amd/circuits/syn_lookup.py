@@ -28,6 +28,15 @@ e = "same address as the previous row" and `order_limbs` limb columns of the ord
 constraints that tie them to consecutive rows (logup.order_constraints) on the body rows, and the limbs as further lookups of tag 0.
 They are an ORDER record, so the library fills them (`witness(order=False)` leaves them zero).  Addresses and times stay below
 2^(order_limbs L).
+SYN-LOOKUP-linked (`syn_lookup_linked`, `build_syn_lookup(shape, link=True)`): ANOTHER description again, the memory argument without
+a sorted copy.  Every active row is an access; per memory pair the data columns are addr, val, time, linked, last, pval, ptime and
+`order_limbs` limb columns.  On the bus (tag 1) every access adds (addr, val, time), removes -linked (addr, pval, ptime) — the
+previous access to its address — and -last (addr, val, time) pages the final access of an address out; an unlinked access is the
+page-in.  The limbs of time - ptime - 1 are lookups of tag 0 and logup.link_constraints ties them to the row, so a link cannot point
+forward in time.  linked, last, pval, ptime and the limbs are a LINK record (ZKA1 version 5): the library fills them
+(zkh_derive_links; `witness(link=False)` leaves them zero).  Times are the row numbers, so differences stay below 2^(order_limbs L).
+What it leaves out: a write flag in the tuple and with it the read rule (a read returns pval), and an initial-memory table behind
+linked = 0.
 Not a shipped circuit: its control root is zkh_code_root of its code trace.
 """
 from __future__ import annotations
@@ -76,19 +85,36 @@ def order_layout(n_words: int, n_limbs: int, n_mem: int, order_limbs: int = ORDE
     return [[base + (1 + order_limbs) * i + e for e in range(1 + order_limbs)] for i in range(n_mem)]
 
 
+LINK_W = 7                          # addr, val, time, linked, last, pval, ptime
+
+
+def link_layout(n_words: int, n_limbs: int, n_mem: int, order_limbs: int = ORDER_LIMBS):
+    """data column indices of SYN-LOOKUP-linked's memory pairs, after `layout`'s m: per pair [addr, val, time, linked, last, pval, ptime,
+    limb_0 .. limb_{order_limbs-1}]"""
+    base = n_words + n_words * n_limbs + 1
+    return [[base + (LINK_W + order_limbs) * i + e for e in range(LINK_W + order_limbs)] for i in range(n_mem)]
+
+
 def build_syn_lookup(shape: Shape = FULL, derive: bool = False, sort: bool = False,
                      sort_keys: Tuple[int, ...] = SORT_KEYS, limbs: bool = False, order: bool = False,
-                     order_limbs: int = ORDER_LIMBS) -> Tuple[np.ndarray, np.ndarray]:
+                     order_limbs: int = ORDER_LIMBS, link: bool = False) -> Tuple[np.ndarray, np.ndarray]:
     """-> (ZKC1 description, ZKA1 argument blob); derive: the table term's multiplicity is derived by the library (version-2 blob,
     the description unchanged); sort: every permuted copy is the library's sorted copy of its memory tuple by the tuple positions
     `sort_keys` (version-3 blob, the description unchanged); limbs: every word's limbs are a LIMBS record (version-4 blob, the
     description unchanged); order: SYN-LOOKUP-ordered, another description (module docstring), its order columns an ORDER record over
-    the copy's (addr, time)"""
+    the copy's (addr, time); link: SYN-LOOKUP-linked, another description (module docstring), its link columns a LINK record (version-5
+    blob); it has no sorted copy, so it refuses `sort` and `order`"""
     n_words, n_limbs, limb_bits, n_mem = shape
+    if link and (sort or order):
+        raise ValueError("build_syn_lookup: link=True has no sorted copy: it does not combine with sort= / order=")
     words, limb_cols, m, mem, perm = layout(n_words, n_limbs, n_mem)
     ocols = order_layout(n_words, n_limbs, n_mem, order_limbs) if order else []
+    lcols = link_layout(n_words, n_limbs, n_mem, order_limbs) if link else []
     wd = m + 1 + 2 * MEM_W * n_mem + sum(len(c) for c in ocols)
     n_terms = n_words * n_limbs + 1 + 2 * n_mem + n_mem * order_limbs * bool(order)
+    if link:
+        wd = m + 1 + sum(len(c) for c in lcols)
+        n_terms = n_words * n_limbs + 1 + 3 * n_mem + n_mem * order_limbs
     k = (n_terms + 2) // 3
     b = LogupBuilder((4 * k, N_CODE, wd), (4, 8), alpha=0, beta=4)
     code = lambda c: b.get(GROUP_CODE, c)
@@ -99,17 +125,25 @@ def build_syn_lookup(shape: Shape = FULL, derive: bool = False, sort: bool = Fal
     # the terms, three per column in this order: limbs, the table, the memory pair (, the order limbs)
     specs = [dict(tuple_cols=[(GROUP_DATA, c)], tag=0) for row in limbs for c in row]
     specs.append(dict(tuple_cols=[(GROUP_CODE, 6)], sign=-1, sel=5, mult=(GROUP_DATA, m), tag=0, derive=derive))
-    for i in range(n_mem):
+    for i in range(n_mem if not link else 0):
         specs.append(dict(tuple_cols=[(GROUP_DATA, c) for c in mem[i]], sign=1, tag=1))
         copy = dict(sorted_from=len(specs) - 1, sort_keys=sort_keys) if sort else {}
         specs.append(dict(tuple_cols=[(GROUP_DATA, c) for c in perm[i]], sign=-1, tag=1, **copy))
+    for c_addr, c_val, c_time, c_linked, c_last, c_pval, c_ptime, *_ in lcols:
+        specs.append(dict(tuple_cols=[(GROUP_DATA, c_addr), (GROUP_DATA, c_val), (GROUP_DATA, c_time)], sign=1, tag=1))
+        specs.append(dict(tuple_cols=[(GROUP_DATA, c_addr), (GROUP_DATA, c_pval), (GROUP_DATA, c_ptime)], sign=-1, mult=(GROUP_DATA, c_linked), tag=1))
+        specs.append(dict(tuple_cols=[(GROUP_DATA, c_addr), (GROUP_DATA, c_val), (GROUP_DATA, c_time)], sign=-1, mult=(GROUP_DATA, c_last), tag=1))
     specs += [dict(tuple_cols=[(GROUP_DATA, c)], tag=0) for cols in ocols for c in cols[1:]]
+    specs += [dict(tuple_cols=[(GROUP_DATA, c)], tag=0) for cols in lcols for c in cols[LINK_W:]]
     for i, s in enumerate(specs):
         b.term(i // 3, **s)
     if limbs_flag:
         for kk in range(n_words):
             b.derive_limbs((GROUP_DATA, words[kk]), limbs[kk], limb_bits)
     records = [b.derive_order([(GROUP_DATA, perm[i][0]), (GROUP_DATA, perm[i][2])], cols, limb_bits) for i, cols in enumerate(ocols)]
+    # the clock (time) is carried first, then the value; the destinations in the LINK's order: linked, last, ptime, pval, the limbs
+    links = [b.derive_links(None, (GROUP_DATA, c[0]), [(GROUP_DATA, c[2]), (GROUP_DATA, c[1])], [c[3], c[4], c[6], c[5]] + c[LINK_W:], limb_bits)
+             for c in lcols]
     # words = sum of their limbs, on active rows
     inner = b.true()
     for kk in range(n_words):
@@ -125,6 +159,11 @@ def build_syn_lookup(shape: Shape = FULL, derive: bool = False, sort: bool = Fal
         for rec in records:
             inner = b.order_constraints(inner, rec)
         chain = b.and_cond(chain, body, inner)
+    if links:                                                                # every active row is an access, the first one included
+        inner = b.true()
+        for rec in links:
+            inner = b.link_constraints(inner, rec)
+        chain = b.and_cond(chain, active, inner)
     chain = b.and_eqz(chain, b.mul(active, b.sub(one, active)))
     chain = b.and_eqz(chain, b.mul(first, b.sub(one, first)))
     chain = b.and_eqz(chain, b.sub(b.sub(active, first), body))
@@ -155,23 +194,35 @@ def syn_lookup_sorted() -> Tuple[np.ndarray, np.ndarray]:
     return build_syn_lookup(FULL, sort=True)
 
 
+def syn_lookup_tiny_linked() -> Tuple[np.ndarray, np.ndarray]:
+    return build_syn_lookup(TINY, link=True)
+
+
+def syn_lookup_linked() -> Tuple[np.ndarray, np.ndarray]:
+    return build_syn_lookup(FULL, link=True)
+
+
 def _enc(x) -> np.ndarray:
     return ((np.asarray(x, dtype=np.uint64) % np.uint64(P)) * np.uint64((1 << 32) % P) % np.uint64(P)).astype(np.uint32)
 
 
 def witness(shape: Shape, po2: int, zk_cycles: int, seed: int = 1, count: bool = True, sort: bool = True, addr_range: int = 1 << 20,
-            sort_keys: Tuple[int, ...] = SORT_KEYS, limbs: bool = True, order=None, order_limbs: int = ORDER_LIMBS):
+            sort_keys: Tuple[int, ...] = SORT_KEYS, limbs: bool = True, order=None, order_limbs: int = ORDER_LIMBS, link=None):
     """-> (code, data, out_global) host arrays of raw Montgomery words: random words below min(P, 2^(n_limbs L)) split into limbs
     (limbs=False: zero, for the library to split), the table's multiplicities (count=False: zero, for the library to derive), random
     memory tuples (addresses below `addr_range`) and their copy stably sorted by the tuple positions `sort_keys`, (addr, time)
     (sort=False: zero, for the library to sort); blinding rows of data from the same seeded generator.
     order: None = the plain shape; True / False = SYN-LOOKUP-ordered's witness (`build_syn_lookup(order=True)`), its order columns
-    filled from the sorted copy (and their limbs counted in the multiplicities) / left zero for the library"""
+    filled from the sorted copy (and their limbs counted in the multiplicities) / left zero for the library.
+    link: None = no link; True / False = SYN-LOOKUP-linked's witness (`build_syn_lookup(link=True)`): no copy, the times are the row
+    numbers, and linked, last, pval, ptime and the limbs of time - ptime - 1 are host-made by a walk over the rows with a dictionary,
+    one access after another (and the limbs counted) / left zero for the library"""
     n_words, n_limbs, limb_bits, n_mem = shape
     words, limb_cols, m_col, mem, perm = layout(n_words, n_limbs, n_mem)
     limbs_on, limbs = limbs, limb_cols
     ocols = order_layout(n_words, n_limbs, n_mem, order_limbs) if order is not None else []
-    wd = m_col + 1 + 2 * MEM_W * n_mem + sum(len(c) for c in ocols)
+    lcols = link_layout(n_words, n_limbs, n_mem, order_limbs) if link is not None else []
+    wd = m_col + 1 + (sum(len(c) for c in lcols) if lcols else 2 * MEM_W * n_mem + sum(len(c) for c in ocols))
     n = 1 << po2
     A = n - zk_cycles
     T = 1 << limb_bits
@@ -201,6 +252,9 @@ def witness(shape: Shape, po2: int, zk_cycles: int, seed: int = 1, count: bool =
         addr = rng.integers(0, addr_range, size=A, dtype=np.uint64)
         val = rng.integers(0, P, size=A, dtype=np.uint64)
         time = rng.permutation(A).astype(np.uint64)
+        if lcols:
+            _link_witness(data, lcols[i], addr, val, A, limb_bits, order_limbs, link, counts)
+            continue
         tup = (addr, val, time)
         by = np.lexsort(tuple(tup[pos] for pos in sort_keys[::-1]))
         for e, v in enumerate(tup):
@@ -227,6 +281,33 @@ def witness(shape: Shape, po2: int, zk_cycles: int, seed: int = 1, count: bool =
     return _enc(code).reshape(-1), _enc(data).reshape(-1), np.zeros(4, dtype=np.uint32)
 
 
+def _link_witness(data, cols, addr, val, A, limb_bits, order_limbs, fill, counts):
+    """one memory pair of SYN-LOOKUP-linked: the host's way, a sequential walk with the last access of every address in a dictionary"""
+    c_addr, c_val, c_time, c_linked, c_last, c_pval, c_ptime, *c_limbs = cols
+    T = 1 << limb_bits
+    time = np.arange(A, dtype=np.uint64)
+    data[c_addr, :A], data[c_val, :A], data[c_time, :A] = addr, val, time
+    seen, prev = {}, [-1] * A
+    for r, a in enumerate(addr.tolist()):                                    # the walk: the last access to every address so far
+        prev[r] = seen.get(a, -1)
+        seen[a] = r
+    prev = np.asarray(prev, dtype=np.int64)
+    on = prev >= 0
+    q = np.where(on, prev, 0)
+    linked, last = on.astype(np.uint64), np.ones(A, dtype=np.uint64)
+    last[prev[on]] = 0
+    pval, ptime = np.where(on, val[q], 0).astype(np.uint64), np.where(on, time[q], 0).astype(np.uint64)
+    d = np.where(on, np.arange(A, dtype=np.int64) - q - 1, 0)
+    assert (d >> (order_limbs * limb_bits) == 0).all(), "a time difference does not fit the link limbs"
+    if fill:
+        data[c_linked, :A], data[c_last, :A], data[c_pval, :A], data[c_ptime, :A] = linked, last, pval, ptime
+    for j, c in enumerate(c_limbs):
+        limb = (d >> (j * limb_bits)) & (T - 1)
+        if fill:
+            data[c, :A] = limb.astype(np.uint64)
+        counts += np.bincount(limb, minlength=T)
+
+
 def witness_equal_keys(shape: Shape, po2: int, zk_cycles: int, seed: int = 1, sort: bool = True, addr_range: int = 5):
     """the witness of `build_syn_lookup(shape, sort=True, sort_keys=(0,))`: addresses from a handful of values and the address the only
     key, so that every key is shared by many rows of distinct (val, time) and only a STABLE sort reproduces the permuted copy"""
@@ -251,4 +332,35 @@ def swap_sorted_rows(shape: Shape, data, po2: int, row: int, pair: int = 0) -> n
     perm = layout(shape.n_words, shape.n_limbs, shape.n_mem)[4][pair]
     d = np.array(data, dtype=np.uint32).reshape(-1, 1 << po2)
     d[perm, row], d[perm, row + 1] = d[perm, row + 1].copy(), d[perm, row].copy()
+    return d.reshape(-1)
+
+
+def relink_row(shape: Shape, data, po2: int, row: int, pair: int = 0, order_limbs: int = ORDER_LIMBS) -> np.ndarray:
+    """a copy of SYN-LOOKUP-linked's `data` in which the access `row` points at the NEXT access to its address (row2) instead of the
+    previous one.  The other pointers move so that every tuple is still removed exactly once and the bus balances: row2 takes over
+    what `row` pointed at, and the access after row2 (row3) points at `row`; where row2 is the last one, `last` moves from row2 to
+    `row` instead.  The limbs of the rows touched are set to those of |time - ptime - 1| — in the table's range, so the lookups can be
+    answered once the multiplicities are counted again — and only logup.link_constraints on `row`, linked forward in time, objects"""
+    n = 1 << po2
+    d = np.array(data, dtype=np.uint32).reshape(-1, n)
+    c_addr, c_val, c_time, c_linked, c_last, c_pval, c_ptime, *c_limbs = link_layout(shape.n_words, shape.n_limbs, shape.n_mem, order_limbs)[pair]
+    later = row + 1 + np.nonzero((d[c_addr, row + 1:] == d[c_addr, row]) & (d[c_linked, row + 1:] != 0))[0]
+    assert later.size, f"row {row} is the last access to its address: nothing to relink it to"
+    row2 = int(later[0])
+    rinv, R = pow((1 << 32) % P, -1, P), (1 << 32) % P
+    dec = lambda c, r: int(d[c, r]) % P * rinv % P
+    old = [d[c, row].copy() for c in (c_linked, c_pval, c_ptime)]
+    d[c_linked, row], d[c_pval, row], d[c_ptime, row] = d[c_linked, row2], d[c_val, row2], d[c_time, row2]
+    d[c_linked, row2], d[c_pval, row2], d[c_ptime, row2] = old
+    touched = [row, row2]
+    if later.size > 1:
+        row3 = int(later[1])
+        d[c_pval, row3], d[c_ptime, row3] = d[c_val, row], d[c_time, row]
+        touched.append(row3)
+    else:
+        d[c_last, row], d[c_last, row2] = d[c_last, row2], d[c_last, row]
+    for r in touched:
+        diff = abs(dec(c_time, r) - dec(c_ptime, r) - 1) if dec(c_linked, r) else 0
+        for j, c in enumerate(c_limbs):
+            d[c, r] = ((diff >> (j * shape.limb_bits)) & ((1 << shape.limb_bits) - 1)) * R % P
     return d.reshape(-1)

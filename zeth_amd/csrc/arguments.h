@@ -1,7 +1,7 @@
 // arguments.h — lookup and permutation arguments as data (ZKA1 blob; zeth_amd/circuits/logup.py; DESIGN.md §2 ARGUMENTS): the decoded
 // form every consumer reads, and what the consumers share.  arguments.hip owns the blob format and the rules a blob must keep;
-// accumulate.hip (zkh_accumulate), multiplicities.hip (zkh_derive_multiplicities), sort.hip (zkh_derive_sorted) and columns.hip
-// (zkh_derive_columns) read zkh_circuit::args and never see a blob word.
+// accumulate.hip (zkh_accumulate), multiplicities.hip (zkh_derive_multiplicities), sort.hip (zkh_derive_sorted), columns.hip
+// (zkh_derive_columns) and links.hip (zkh_derive_links) read zkh_circuit::args and never see a blob word.
 #pragma once
 #include <vector>
 
@@ -13,6 +13,8 @@ constexpr uint32_t ARGS_MAGIC = 0x5a4b4131u;        // 'ZKA1'
 constexpr uint32_t ARGS_HEADER = 8, TERM_WORDS = 16;
 constexpr uint32_t MAX_TUPLE = 4, MAX_TERMS = 3, MAX_SORT_KEYS = 3, NONE = 0xffffffffu;
 constexpr uint32_t RECORD_WORDS = 16, KIND_LIMBS = 1, KIND_ORDER = 2, MAX_LIMBS = 8;
+constexpr uint32_t KIND_LINK = 3, LINK_WORDS = 32, MAX_CARRIED = 3, MAX_LINK_LIMBS = 4, MAX_LINK_DSTS = 2 + MAX_CARRIED + MAX_LINK_LIMBS;
+constexpr uint32_t MAX_ORDER_BITS = 29;             // logup.MAX_ORDER_BITS: a negative difference stays out of the limbs' range
 
 // logup.Term as the blob gives it: the fields are the blob's words, checked by the rules of arguments.hip before a circuit keeps them
 struct Term {
@@ -33,11 +35,22 @@ struct Record {
     uint32_t dst[MAX_LIMBS];                // destination data columns: (ORDER with two keys: the flag,) then the nl limbs
     uint32_t n_dst, reserved;               // destinations in use; a word the format reserves was not 0
 };
+// logup.Link, a LINK record (version 5), as the blob gives it; the kernels of links.hip read it in this form
+struct Link {
+    uint32_t index;                         // its index among all records of the blob (LINK records follow the LIMBS / ORDER ones)
+    uint32_t L, nl, nc, sel;                // limb bits; limb count; carried columns; selector code column or NONE
+    uint32_t kg, kc;                        // the key's (group, column)
+    uint32_t cg[MAX_CARRIED], cc[MAX_CARRIED];      // the carried columns, the first nc; c_0 is the clock
+    uint32_t dst[MAX_LINK_DSTS];            // destination data columns: linked, last, prev_0 .. prev_{nc-1}, limb_0 .. limb_{nl-1}
+    uint32_t n_dst, reserved;               // destinations in use; a word the format reserves was not 0
+};
 // logup.Arguments
 struct Arguments {
     uint32_t version, k, alpha, beta;       // blob version; accum Fp4 columns; mix word offsets of the two challenges
     std::vector<Term> terms;
-    std::vector<Record> records;
+    std::vector<Record> records;            // the LIMBS / ORDER records: their index here is their index in the blob
+    std::vector<Link> links;                // the LINK records
+    uint32_t late_record = NONE, late_after = 0;    // a LIMBS / ORDER record that follows a LINK record, and that LINK record (refused)
 };
 
 // a term's columns as the kernels read them; unused tuple slots name (data, 0)

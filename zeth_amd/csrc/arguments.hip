@@ -1,6 +1,6 @@
 // arguments.hip — the ZKA1 argument blob (layout: zeth_amd/circuits/logup.py; DESIGN.md §2 ARGUMENTS): its decoding into
-// zkh::Arguments (terms and, from version 4, derived-column records), the rules a circuit's arguments keep (check_sorted, check_derived,
-// check_columns, in this order), and the entry points that attach them to a circuit and ask what they derive.
+// zkh::Arguments (terms, from version 4 derived-column records, from version 5 LINK records), the rules a circuit's arguments keep
+// (check_sorted, check_derived, check_columns, check_links, in this order), and the entry points that attach them to a circuit and ask what they derive.
 // decode_arguments is the only code that knows the blob's words; everything else, here and in the consumers, reads decoded terms.
 #include "arguments.h"
 
@@ -16,9 +16,12 @@ namespace {
 // significant key first); bits 2, 3, 7, the position fields of unused keys and, without bit 1, everything above bit 0 are reserved.
 // A reserved bit is recorded, not refused: the rules refuse it where they reach the term (flag_word_rule), after the circuit-shape checks.
 const char* decode_arguments(const uint32_t* a, size_t words, Arguments* out) {
-    ZKH_REQUIRE(words >= ARGS_HEADER && a[0] == ARGS_MAGIC && a[1] >= 1 && a[1] <= 4, "set_arguments: not a ZKA1 (version 1) argument blob");
+    ZKH_REQUIRE(words >= ARGS_HEADER && a[0] == ARGS_MAGIC && a[1] >= 1 && a[1] <= 5, "set_arguments: not a ZKA1 (version 1) argument blob");
     const uint32_t n_terms = a[5], n_records = a[1] >= 4 ? a[6] : 0;            // header word 6: the records of version 4, reserved before
-    const bool fits = words == ARGS_HEADER + (size_t)TERM_WORDS * n_terms + (size_t)RECORD_WORDS * n_records;
+    const size_t rec0 = ARGS_HEADER + (size_t)TERM_WORDS * n_terms;
+    size_t end = rec0;                                                          // a LINK record (version 5) takes two slots
+    for (uint32_t i = 0; i < n_records; i++) end += a[1] >= 5 && end < words && a[end] == KIND_LINK ? LINK_WORDS : RECORD_WORDS;
+    const bool fits = words == end;
     ZKH_REQUIRE(fits || a[1] < 4, "set_arguments: %zu words for %u terms and %u records", words, n_terms, n_records);
     ZKH_REQUIRE(fits, "set_arguments: %zu words for %u terms", words, n_terms);
     out->version = a[1]; out->k = a[2]; out->alpha = a[3]; out->beta = a[4];
@@ -42,10 +45,29 @@ const char* decode_arguments(const uint32_t* a, size_t words, Arguments* out) {
     }
     // Derived-column records (version 4): kind, L, nl, n_src, two (group, column) source pairs, eight destination data columns.  As
     // with the flags, a reserved word that is set is recorded here and refused by the rules (check_columns).
-    out->records.assign(n_records, Record{});
+    // LINK records (version 5, kind 3, 32 words): L, nl, nc, sel, 0, the key's (group, column), three carried (group, column) pairs, 0, 0,
+    // then from word 16 the destinations linked, last, prev_0 .. prev_{nc-1}, limb_0 .. limb_{nl-1}, the rest 0 (check_links).
+    out->records.clear();
+    out->links.clear();
+    const uint32_t* r = a + rec0;
     for (uint32_t i = 0; i < n_records; i++) {
-        const uint32_t* r = a + ARGS_HEADER + (size_t)TERM_WORDS * n_terms + (size_t)RECORD_WORDS * i;
-        Record& x = out->records[i];
+        if (out->version >= 5 && r[0] == KIND_LINK) {
+            Link x{};
+            x.index = i; x.L = r[1]; x.nl = r[2]; x.nc = r[3]; x.sel = r[4]; x.kg = r[6]; x.kc = r[7];
+            for (uint32_t j = 0; j < MAX_CARRIED; j++) { x.cg[j] = r[8 + 2 * j]; x.cc[j] = r[9 + 2 * j]; }
+            for (uint32_t j = 0; j < MAX_LINK_DSTS; j++) x.dst[j] = r[16 + j];
+            const uint32_t nc = x.nc < MAX_CARRIED ? x.nc : MAX_CARRIED;
+            const uint64_t nd = 2ull + nc + x.nl;
+            x.n_dst = nd < MAX_LINK_DSTS ? (uint32_t)nd : MAX_LINK_DSTS;
+            x.reserved = r[5] | r[14] | r[15];
+            for (uint32_t j = nc; j < MAX_CARRIED; j++) x.reserved |= x.cg[j] | x.cc[j];
+            for (uint32_t j = 16 + x.n_dst; j < LINK_WORDS; j++) x.reserved |= r[j];
+            out->links.push_back(x);
+            r += LINK_WORDS;
+            continue;
+        }
+        if (!out->links.empty() && out->late_record == NONE) { out->late_record = i; out->late_after = out->links[0].index; }
+        Record x{};
         x.kind = r[0]; x.L = r[1]; x.nl = r[2]; x.n_src = r[3];
         for (uint32_t j = 0; j < 2; j++) { x.sg[j] = r[4 + 2 * j]; x.sc[j] = r[5 + 2 * j]; }
         for (uint32_t j = 0; j < MAX_LIMBS; j++) x.dst[j] = r[8 + j];
@@ -53,6 +75,8 @@ const char* decode_arguments(const uint32_t* a, size_t words, Arguments* out) {
         x.n_dst = nd < MAX_LIMBS ? (uint32_t)nd : MAX_LIMBS;
         for (uint32_t j = x.n_src < 2 ? x.n_src : 2; j < 2; j++) x.reserved |= x.sg[j] | x.sc[j];
         for (uint32_t j = x.n_dst; j < MAX_LIMBS; j++) x.reserved |= x.dst[j];
+        out->records.push_back(x);
+        r += RECORD_WORDS;
     }
     return nullptr;
 }
@@ -209,6 +233,96 @@ const char* check_columns(const zkh_circuit* c, const Arguments& a) {
     return nullptr;
 }
 
+bool writes(const Link& x, uint32_t col) {
+    for (uint32_t e = 0; e < x.n_dst; e++)
+        if (x.dst[e] == col) return true;
+    return false;
+}
+bool reads(const Record& x, uint32_t col) {                                     // data column `col` among the sources of x
+    for (uint32_t s = 0; s < x.n_src && s < 2; s++)
+        if (x.sg[s] == GROUP_DATA && x.sc[s] == col) return true;
+    return false;
+}
+bool reads(const Link& x, uint32_t col) {
+    if (x.kg == GROUP_DATA && x.kc == col) return true;
+    for (uint32_t s = 0; s < x.nc; s++)
+        if (x.cg[s] == GROUP_DATA && x.cc[s] == col) return true;
+    return false;
+}
+
+// logup.check_links: the first LINK record that breaks a rule, named by its index among all records.  Per LINK record: (a) the ranges of
+// nc, L, nl and the reserved words; (b) its selector a code column, its sources code or data columns, its destinations pairwise distinct
+// data columns; then, per LINK record again: (c) no source is written by a derive: a sorted copy's column, a destination of any record, a
+// derived multiplicity; (d) no destination is written twice: by another record, a sorted copy or a derived multiplicity; (e) no
+// destination is read by any record, by the source term of a sorted copy, or — linked and last apart — is a term's multiplicity.
+const char* check_links(const zkh_circuit* c, const Arguments& a) {
+    const uint32_t n_terms = (uint32_t)a.terms.size(), n_rec = (uint32_t)a.records.size();
+    for (const Link& r : a.links) {
+        const uint32_t i = r.index;
+        ZKH_REQUIRE(r.nc >= 1 && r.nc <= MAX_CARRIED && r.L >= 1 && r.L <= 16 && r.nl <= MAX_LINK_LIMBS && r.L * r.nl <= MAX_ORDER_BITS,
+                    "set_arguments: record %u: a LINK of %u carried columns and %u limbs of %u bits (1..%u carried columns, 0..%u limbs of 1..16 bits, at most "
+                    "%u bits in all)", i, r.nc, r.nl, r.L, MAX_CARRIED, MAX_LINK_LIMBS, MAX_ORDER_BITS);
+        ZKH_REQUIRE(!r.reserved, "set_arguments: record %u: a reserved word of a LINK is not 0 (words 5, 14, 15, the unused carried pairs and the unused "
+                    "destination words)", i);
+        ZKH_REQUIRE(r.sel == NONE || r.sel < c->group_size[GROUP_CODE], "set_arguments: record %u: selector %u is not a code column", i, r.sel);
+        auto is_column = [&](uint32_t g, uint32_t col) { return (g == GROUP_CODE || g == GROUP_DATA) && col < c->group_size[g]; };
+        ZKH_REQUIRE(is_column(r.kg, r.kc), "set_arguments: record %u: source (%u, %u) is not a code or data column", i, r.kg, r.kc);
+        for (uint32_t j = 0; j < r.nc; j++)
+            ZKH_REQUIRE(is_column(r.cg[j], r.cc[j]), "set_arguments: record %u: source (%u, %u) is not a code or data column", i, r.cg[j], r.cc[j]);
+        for (uint32_t e = 0; e < r.n_dst; e++) {
+            ZKH_REQUIRE(r.dst[e] < c->group_size[GROUP_DATA], "set_arguments: record %u: destination %u is not a data column", i, r.dst[e]);
+            for (uint32_t e2 = 0; e2 < e; e2++)
+                ZKH_REQUIRE(r.dst[e2] != r.dst[e], "set_arguments: record %u: its destination (data %u) appears twice", i, r.dst[e]);
+        }
+    }
+    for (const Link& r : a.links) {
+        const uint32_t i = r.index;
+        for (uint32_t s = 0; s <= r.nc; s++) {
+            const uint32_t g = s ? r.cg[s - 1] : r.kg, col = s ? r.cc[s - 1] : r.kc;
+            if (g != GROUP_DATA) continue;
+            for (uint32_t j = 0; j < n_terms; j++)
+                ZKH_REQUIRE(!(a.terms[j].sorted && in_tuple(a.terms[j], a.terms[j].w, GROUP_DATA, col)), "set_arguments: record %u: its source (data %u) is written "
+                            "by the sorted copy term %u (a LINK reads what no derive writes)", i, col, j);
+            for (uint32_t j = 0; j < n_rec; j++)
+                ZKH_REQUIRE(!writes(a.records[j], col), "set_arguments: record %u: its source (data %u) is a destination of record %u (records never chain)", i, col, j);
+            for (const Link& x : a.links)
+                ZKH_REQUIRE(!writes(x, col), "set_arguments: record %u: its source (data %u) is a destination of record %u (records never chain)", i, col, x.index);
+            for (uint32_t j = 0; j < n_terms; j++)
+                ZKH_REQUIRE(!(a.terms[j].derive && a.terms[j].mg == GROUP_DATA && a.terms[j].mc == col), "set_arguments: record %u: its source (data %u) is the "
+                            "derived multiplicity of term %u", i, col, j);
+        }
+        for (uint32_t e = 0; e < r.n_dst; e++) {
+            const uint32_t col = r.dst[e];
+            for (uint32_t j = 0; j < n_rec; j++)
+                ZKH_REQUIRE(!writes(a.records[j], col), "set_arguments: record %u: its destination (data %u) is also written by record %u", i, col, j);
+            for (const Link& x : a.links)
+                ZKH_REQUIRE(x.index == i || !writes(x, col), "set_arguments: record %u: its destination (data %u) is also written by record %u", i, col, x.index);
+            for (uint32_t j = 0; j < n_terms; j++) {
+                const Term& t = a.terms[j];
+                ZKH_REQUIRE(!(t.sorted && in_tuple(t, t.w, GROUP_DATA, col)), "set_arguments: record %u: its destination (data %u) is written by the sorted copy "
+                            "term %u", i, col, j);
+                ZKH_REQUIRE(!(t.derive && t.mg == GROUP_DATA && t.mc == col), "set_arguments: record %u: its destination (data %u) is the derived multiplicity of "
+                            "term %u", i, col, j);
+            }
+            for (uint32_t j = 0; j < n_rec; j++)
+                ZKH_REQUIRE(!reads(a.records[j], col), "set_arguments: record %u: its destination (data %u) is read by record %u (the links run after the columns, "
+                            "and never chain)", i, col, j);
+            for (const Link& x : a.links)
+                ZKH_REQUIRE(!reads(x, col), "set_arguments: record %u: its destination (data %u) is read by record %u (the links run after the columns, and never "
+                            "chain)", i, col, x.index);
+            for (uint32_t j = 0; j < n_terms; j++) {
+                const Term& t = a.terms[j];
+                ZKH_REQUIRE(!(t.sorted && in_tuple(a.terms[t.sorted_from], a.terms[t.sorted_from].w, GROUP_DATA, col)), "set_arguments: record %u: its destination "
+                            "(data %u) is read by term %u, the source of a sorted copy (the sort runs first)", i, col, t.sorted_from);
+            }
+            for (uint32_t j = 0; j < n_terms; j++)
+                ZKH_REQUIRE(e < 2 || !(a.terms[j].mg == GROUP_DATA && a.terms[j].mc == col), "set_arguments: record %u: its destination (data %u) is the multiplicity "
+                            "of term %u (of a LINK's destinations only linked and last may be)", i, col, j);
+        }
+    }
+    return nullptr;
+}
+
 // the arguments against the circuit's shape, then the rules of sorted copies, then those of derived multiplicities
 const char* check_arguments(const zkh_circuit* c, const Arguments& a) {
     const uint32_t k = a.k;
@@ -236,7 +350,10 @@ const char* check_arguments(const zkh_circuit* c, const Arguments& a) {
     for (uint32_t col = 0; col < k; col++) ZKH_REQUIRE(per_col[col] >= 1, "set_arguments: accum column %u has no terms", col);
     if (a.version >= 3) ZKH_TRY(check_sorted(a));
     if (a.version >= 2) ZKH_TRY(check_derived(a));
-    return check_columns(c, a);
+    ZKH_REQUIRE(a.late_record == NONE, "set_arguments: record %u: a LIMBS / ORDER record after the LINK record %u (LINK records come last)", a.late_record,
+                a.late_after);
+    ZKH_TRY(check_columns(c, a));
+    return check_links(c, a);
 }
 
 }  // namespace
@@ -274,6 +391,8 @@ extern "C" int zkh_circuit_derives_sorted(const zkh_circuit* c) {
 
 extern "C" int zkh_circuit_derives_columns(const zkh_circuit* c) { return c && c->args && !c->args->records.empty(); }
 
+extern "C" int zkh_circuit_derives_links(const zkh_circuit* c) { return c && c->args && !c->args->links.empty(); }
+
 extern "C" const char* zkh_circuit_derived_data_columns(const zkh_circuit* c, uint32_t* cols, size_t cap, size_t* n) {
     ZKH_REQUIRE(c && n && (cols || !cap), "derived_data_columns: null argument");
     std::vector<uint32_t> out;
@@ -283,6 +402,7 @@ extern "C" const char* zkh_circuit_derived_data_columns(const zkh_circuit* c, ui
             if (t.sorted) out.insert(out.end(), t.tc, t.tc + t.w);
         }
         for (const Record& r : c->args->records) out.insert(out.end(), r.dst, r.dst + r.n_dst);
+        for (const Link& r : c->args->links) out.insert(out.end(), r.dst, r.dst + r.n_dst);
     }
     std::sort(out.begin(), out.end());
     out.erase(std::unique(out.begin(), out.end()), out.end());

@@ -1,0 +1,37 @@
+// sort.h — the stable sort of selected trace rows by packed keys that sort.hip owns (its kernels live there and nowhere else), for
+// its two callers: zkh_derive_sorted (sort.hip) and zkh_derive_links (links.hip).
+#pragma once
+#include <vector>
+
+#include "arguments.h"
+
+namespace zkh {
+
+struct SortPair {                                       // one sort as the kernels read it (zkh_derive_sorted: a pair (D, S))
+    uint32_t d_term, w, nkeys, sel;                     // D's blob index; tuple width; key fields; selector code column or NONE
+    uint32_t kg[MAX_SORT_KEYS], kc[MAX_SORT_KEYS];      // the key columns, most significant first
+    uint32_t sg[MAX_TUPLE], sc[MAX_TUPLE];              // S's tuple
+    uint32_t dc[MAX_TUPLE];                             // D's tuple (data columns)
+};
+// status words: [0, 2) the first bad selector (pair << 32 | row), then per pair ST_WORDS: OR[3], AND[3], m = selected rows, unused
+constexpr uint32_t ST_HEAD = 2, ST_WORDS = 8, ST_OR = 0, ST_AND = 3, ST_M = 6;
+
+// What sort_rows leaves on the device, pair p at items [p A, p A + m_p): the packed keys (the live bits of the key fields: two rows have
+// equal keys exactly when their packed keys are equal) in ascending order, equal keys in row order, and the source row of each.
+struct SortedRows {
+    Tmp pairs, status, selbase;                         // the SortPair table; the status words; per 64-row group the rank of its first selected row
+    Tmp klo[2], khi[2], idx[2], hist, totals;
+    int cur = 0;                                        // which of the two item buffers holds the result
+    bool wide = false;                                  // keys of more than 64 live bits: khi holds bits 64..95
+    uint32_t groups = 0;
+    std::vector<uint32_t> st;                           // the status words as read back after the key pass
+    bool bad_selector = false;                          // a selector other than 0 / 1: the lowest (pair, row); nothing was sorted
+    uint32_t bad_pair = 0, bad_row = 0;
+    const SortPair* d_pairs() const { return (const SortPair*)pairs->ptr(); }
+    const unsigned long long* keys() const { return (const unsigned long long*)klo[cur]->ptr(); }
+    const uint32_t* rows() const { return idx[cur]->ptr(); }
+};
+// the passes (a) .. (c) of sort.hip over `pairs`, all pairs in the same launches
+const char* sort_rows(zkh_ctx* ctx, const zkh_buf* code, const zkh_buf* data, size_t n, uint32_t A, const std::vector<SortPair>& pairs, SortedRows* out);
+
+}  // namespace zkh

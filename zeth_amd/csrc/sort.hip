@@ -23,9 +23,10 @@
 //                       digit), a per-wave LDS counter carries the rank from round to round, the four waves' counts are stacked in wave
 //                       order: rank = the number of earlier items of the tile with the same digit, by construction.
 //   (d) k_sort_gather : row r of rank j reads the sorted source row and copies S's tuple (coalesced writes, random reads).
+// (a) .. (c) are `sort_rows` (sort.h), which zkh_derive_links (links.hip) calls as well: it ends with (packed key, source row) in stable order.
 // Nothing depends on the order in which workgroups or atomics arrive (the only global atomics are OR / AND / min, which commute), and
 // no workgroup waits for another: the placement of every item is a function of the keys alone.
-#include "arguments.h"
+#include "sort.h"
 #include "scan.h"
 
 #include <algorithm>
@@ -43,15 +44,6 @@ constexpr uint32_t SORT_IPT = 16, SORT_TILE = SORT_THREADS * SORT_IPT, SORT_BINS
 static_assert(SORT_BINS == SORT_THREADS, "one thread per bin in the histogram and in the stacking of the waves' counts");
 constexpr uint32_t SCAN_THREADS = 1024;
 constexpr uint32_t KEYS_ROUNDS = 8;                     // k_sort_keys: rows per thread
-
-struct SortPair {                                       // one (D, S) as the kernels read it
-    uint32_t d_term, w, nkeys, sel;                     // D's blob index; tuple width; key fields; selector code column or NONE
-    uint32_t kg[MAX_SORT_KEYS], kc[MAX_SORT_KEYS];                // S's key columns, most significant first
-    uint32_t sg[MAX_TUPLE], sc[MAX_TUPLE];              // S's tuple
-    uint32_t dc[MAX_TUPLE];                             // D's tuple (data columns)
-};
-// status words: [0, 2) the first bad selector (pair << 32 | row), then per pair ST_WORDS: OR[3], AND[3], m = selected rows, unused
-constexpr uint32_t ST_HEAD = 2, ST_WORDS = 8, ST_OR = 0, ST_AND = 3, ST_M = 6;
 
 // the bits of v under mask, packed towards bit 0 in their order
 __device__ __forceinline__ uint32_t extract_bits(uint32_t v, uint32_t mask) {
@@ -276,37 +268,16 @@ __global__ __launch_bounds__(SORT_THREADS) void k_sort_gather(const uint32_t* __
 
 }  // namespace
 
-extern "C" const char* zkh_derive_sorted(zkh_ctx* ctx, const zkh_circuit* c, size_t po2, size_t zk_cycles, const zkh_buf* code, zkh_buf* data) {
-    ZKH_REQUIRE(ctx && c && data, "derive_sorted: null argument");
-    ZKH_REQUIRE(code, "derive_sorted: the raw code trace is required (the selectors and code-group source columns of the terms read it)");
-    ZKH_REQUIRE(zkh_circuit_derives_sorted(c), "derive_sorted: the circuit's arguments derive no sorted copy (ZKA1 version 3)");
-    size_t n;
-    uint32_t A;
-    ZKH_TRY(trace_rows("derive_sorted", c, po2, zk_cycles, code, data, nullptr, &n, &A));
-    const std::vector<Term>& a = c->args->terms;
-    std::vector<SortPair> pairs;
-    for (uint32_t i = 0; i < a.size(); i++) {
-        if (!a[i].sorted) continue;
-        const TermCols d = term_cols(a[i]), s = term_cols(a[a[i].sorted_from]);
-        SortPair q{};
-        q.d_term = i; q.w = d.w; q.nkeys = a[i].nkeys; q.sel = d.sel;
-        for (uint32_t f = 0; f < MAX_SORT_KEYS; f++) {
-            const uint32_t pos = f < q.nkeys ? a[i].key[f] : 0;
-            q.kg[f] = s.tg[pos]; q.kc[f] = s.tc[pos];
-        }
-        for (uint32_t e = 0; e < MAX_TUPLE; e++) { q.sg[e] = s.tg[e]; q.sc[e] = s.tc[e]; q.dc[e] = d.tc[e]; }
-        pairs.push_back(q);
-    }
+// (a) .. (c) for both callers.  The launches, uploads and read-back of a call are a function of (pairs, A) and the live key bits alone.
+const char* zkh::sort_rows(zkh_ctx* ctx, const zkh_buf* code, const zkh_buf* data, size_t n, uint32_t A, const std::vector<SortPair>& pairs, SortedRows* out) {
     const uint32_t np = (uint32_t)pairs.size();
-    const uint32_t groups = (A + 63) / 64, tiles = (A + SORT_TILE - 1) / SORT_TILE;
-    ZKH_REQUIRE(np <= 65535, "derive_sorted: %u sorted copies in one blob (at most 65535)", np);
-    bind_thread(ctx);
-
+    const uint32_t groups = out->groups = (A + 63) / 64, tiles = (A + SORT_TILE - 1) / SORT_TILE;
     static_assert(sizeof(SortPair) % 4 == 0, "word records");
-    Tmp dtab, status, selcnt;
+    Tmp &dtab = out->pairs, &status = out->status, &selcnt = out->selbase;
     ZKH_TRY(zkh_copy_from(ctx, "sort_pairs", (const uint32_t*)pairs.data(), pairs.size() * (sizeof(SortPair) / 4), dtab.out()));
     const size_t st_words = ST_HEAD + (size_t)ST_WORDS * np;
-    std::vector<uint32_t> st(st_words, 0);
+    std::vector<uint32_t>& st = out->st;
+    st.assign(st_words, 0);
     st[0] = st[1] = ~0u;
     for (uint32_t p = 0; p < np; p++)
         for (uint32_t f = 0; f < MAX_SORT_KEYS; f++) st[ST_HEAD + ST_WORDS * p + ST_AND + f] = ~0u;
@@ -314,8 +285,8 @@ extern "C" const char* zkh_derive_sorted(zkh_ctx* ctx, const zkh_circuit* c, siz
     ZKH_TRY(new_buf(ctx, (size_t)np * groups, false, selcnt.out()));
     const SortPair* d_pairs = (const SortPair*)dtab->ptr();
     const unsigned rows_x = (unsigned)((A + SORT_THREADS - 1) / SORT_THREADS);
-    double key_words = 0, tuple_words = 0;
-    for (const SortPair& q : pairs) { key_words += q.nkeys + (q.sel != NONE); tuple_words += q.w; }
+    double key_words = 0;
+    for (const SortPair& q : pairs) key_words += q.nkeys + (q.sel != NONE);
     {
         ProfScope prof(ctx, "sort_keys", 4.0 * key_words * A);
         const unsigned bx = (unsigned)((A + SORT_THREADS * KEYS_ROUNDS - 1) / (SORT_THREADS * KEYS_ROUNDS));
@@ -325,12 +296,10 @@ extern "C" const char* zkh_derive_sorted(zkh_ctx* ctx, const zkh_circuit* c, siz
     }
     ZKH_TRY(zkh_read(ctx, status, st.data(), 0, st.size()));
     if (st[0] != ~0u || st[1] != ~0u) {
-        const SortPair& q = pairs[st[1]];
-        const uint32_t row = st[0];
-        uint32_t w;
-        ZKH_TRY(zkh_read(ctx, code, &w, (size_t)q.sel * n + row, 1));
-        return make_err("derive_sorted: sorted-copy term %u (tag %u) has selector %u at row %u, not 0 or 1: the witness is refused", q.d_term,
-                        a[q.d_term].tag, fp_decode(Fp::raw(w % P)), row);
+        out->bad_selector = true;
+        out->bad_pair = st[1];
+        out->bad_row = st[0];
+        return nullptr;
     }
     uint32_t bits = 0;                                   // the widest packed key over the pairs
     for (uint32_t p = 0; p < np; p++) {
@@ -339,10 +308,10 @@ extern "C" const char* zkh_derive_sorted(zkh_ctx* ctx, const zkh_circuit* c, siz
         for (uint32_t f = 0; f < pairs[p].nkeys; f++) b += (uint32_t)__builtin_popcount(s[ST_OR + f] & ~s[ST_AND + f]);
         bits = std::max(bits, b);
     }
-    const bool wide = bits > 64;
+    const bool wide = out->wide = bits > 64;
     const uint32_t passes = (bits + 7) / 8;
     const size_t items = (size_t)np * A;
-    Tmp klo[2], khi[2], idx[2], hist, totals;
+    Tmp (&klo)[2] = out->klo, (&khi)[2] = out->khi, (&idx)[2] = out->idx, &hist = out->hist, &totals = out->totals;
     for (int i = 0; i < (passes ? 2 : 1); i++) {
         ZKH_TRY(new_buf(ctx, 2 * items, false, klo[i].out()));
         ZKH_TRY(new_buf(ctx, wide ? items : 1, false, khi[i].out()));
@@ -382,9 +351,50 @@ extern "C" const char* zkh_derive_sorted(zkh_ctx* ctx, const zkh_circuit* c, siz
         }
         ZKH_TRY(last_launch_error("sort_passes"));
     }
+    out->cur = cur;
+    return nullptr;
+}
+
+extern "C" const char* zkh_derive_sorted(zkh_ctx* ctx, const zkh_circuit* c, size_t po2, size_t zk_cycles, const zkh_buf* code, zkh_buf* data) {
+    ZKH_REQUIRE(ctx && c && data, "derive_sorted: null argument");
+    ZKH_REQUIRE(code, "derive_sorted: the raw code trace is required (the selectors and code-group source columns of the terms read it)");
+    ZKH_REQUIRE(zkh_circuit_derives_sorted(c), "derive_sorted: the circuit's arguments derive no sorted copy (ZKA1 version 3)");
+    size_t n;
+    uint32_t A;
+    ZKH_TRY(trace_rows("derive_sorted", c, po2, zk_cycles, code, data, nullptr, &n, &A));
+    const std::vector<Term>& a = c->args->terms;
+    std::vector<SortPair> pairs;
+    for (uint32_t i = 0; i < a.size(); i++) {
+        if (!a[i].sorted) continue;
+        const TermCols d = term_cols(a[i]), s = term_cols(a[a[i].sorted_from]);
+        SortPair q{};
+        q.d_term = i; q.w = d.w; q.nkeys = a[i].nkeys; q.sel = d.sel;
+        for (uint32_t f = 0; f < MAX_SORT_KEYS; f++) {
+            const uint32_t pos = f < q.nkeys ? a[i].key[f] : 0;
+            q.kg[f] = s.tg[pos]; q.kc[f] = s.tc[pos];
+        }
+        for (uint32_t e = 0; e < MAX_TUPLE; e++) { q.sg[e] = s.tg[e]; q.sc[e] = s.tc[e]; q.dc[e] = d.tc[e]; }
+        pairs.push_back(q);
+    }
+    const uint32_t np = (uint32_t)pairs.size();
+    ZKH_REQUIRE(np <= 65535, "derive_sorted: %u sorted copies in one blob (at most 65535)", np);
+    bind_thread(ctx);
+    SortedRows sorted;
+    ZKH_TRY(sort_rows(ctx, code, data, n, A, pairs, &sorted));
+    if (sorted.bad_selector) {
+        const SortPair& q = pairs[sorted.bad_pair];
+        const uint32_t row = sorted.bad_row;
+        uint32_t w;
+        ZKH_TRY(zkh_read(ctx, code, &w, (size_t)q.sel * n + row, 1));
+        return make_err("derive_sorted: sorted-copy term %u (tag %u) has selector %u at row %u, not 0 or 1: the witness is refused", q.d_term,
+                        a[q.d_term].tag, fp_decode(Fp::raw(w % P)), row);
+    }
+    double tuple_words = 0;
+    for (const SortPair& q : pairs) tuple_words += q.w;
     {
-        ProfScope prof(ctx, "sort_gather", 4.0 * items + 8.0 * tuple_words * A);
-        k_sort_gather<<<dim3(rows_x, np), SORT_THREADS, 0, ctx->stream>>>(code->ptr(), data->ptr(), d_pairs, (uint32_t)n, A, groups, selcnt->ptr(), idx[cur]->ptr());
+        ProfScope prof(ctx, "sort_gather", 4.0 * (size_t)np * A + 8.0 * tuple_words * A);
+        k_sort_gather<<<dim3((unsigned)((A + SORT_THREADS - 1) / SORT_THREADS), np), SORT_THREADS, 0, ctx->stream>>>(
+            code->ptr(), data->ptr(), sorted.d_pairs(), (uint32_t)n, A, sorted.groups, sorted.selbase->ptr(), sorted.rows());
         ZKH_TRY(last_launch_error("sort_gather"));
     }
     // the temporaries go back to the pool on return: the stream orders their next use after these launches

@@ -158,6 +158,8 @@ ABI = {
     "zkh_derive_sorted": (_err, [_vp, _vp, _sz, _sz, _vp, _vp]),
     "zkh_circuit_derives_columns": (_i, [_vp]),
     "zkh_derive_columns": (_err, [_vp, _vp, _sz, _sz, _vp, _vp]),
+    "zkh_circuit_derives_links": (_i, [_vp]),
+    "zkh_derive_links": (_err, [_vp, _vp, _sz, _sz, _vp, _vp]),
     "zkh_circuit_derived_data_columns": (_err, [_vp, _u32p, _sz, C.POINTER(_sz)]),
     "zkh_upload_data_trace": (_err, [_vp, _vp, _sz, _sz, _vp, _u32p, _i]),
     "zkh_ctx_h2d_bytes": (_sz, [_vp]),
@@ -346,8 +348,12 @@ class Circuit:
         """the arguments (ZKA1 version 4) hold derived-column records the library fills (zkh_derive_columns)"""
         return bool(_lib.zkh_circuit_derives_columns(self.h))
 
+    def derives_links(self) -> bool:
+        """the arguments (ZKA1 version 5) hold LINK records the library fills (zkh_derive_links)"""
+        return bool(_lib.zkh_circuit_derives_links(self.h))
+
     def derived_data_columns(self) -> List[int]:
-        """the data columns the library's derives (sorted, columns, multiplicities) write on the active rows, ascending"""
+        """the data columns the library's derives (sorted, columns, links, multiplicities) write on the active rows, ascending"""
         cols = np.zeros(max(1, int(self.desc[5])), dtype=np.uint32)
         n = C.c_size_t()
         _check(_lib.zkh_circuit_derived_data_columns(self.h, _ptr(cols), cols.size, C.byref(n)))
@@ -802,6 +808,13 @@ class HipHal:
         derive_sorted and before derive_multiplicities: raises HalError on a value that does not fit its limbs or on keys that are
         not in order, naming the lowest (record, row) (`data` is then unchanged)"""
         _check(_lib.zkh_derive_columns(self.ctx, circuit.h, po2, zk_cycles, code.h, data.h))
+
+    def derive_links(self, circuit: Circuit, po2: int, zk_cycles: int, code: Buffer, data: Buffer) -> None:
+        """fill the destination columns of the LINK records of `data` on the active rows (zkh_derive_links): every access gets the
+        previous access to its own address; after derive_columns and before derive_multiplicities.  Raises HalError on a selector
+        other than 0 / 1, on a clock that does not increase or on a difference that does not fit its limbs, naming the lowest
+        (record, row) (`data` is then unchanged)"""
+        _check(_lib.zkh_derive_links(self.ctx, circuit.h, po2, zk_cycles, code.h, data.h))
 
     def upload_data_trace(self, circuit: Circuit, po2: int, zk_cycles: int, data: Buffer, host: np.ndarray, pinned_async: bool = True) -> None:
         """upload a caller's data trace without what the library derives (zkh_upload_data_trace): the other columns whole, the derived

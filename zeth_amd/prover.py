@@ -255,9 +255,9 @@ class SegmentProver:
     def seal_host_witness(self, seg: Segment, host_code: np.ndarray, host_data: np.ndarray, out_global) -> SegmentReceipt:
         """Seal a segment whose code/data traces live in pinned HOST memory (hal.host_alloc views): enqueue both uploads
         on the context's stream (no host sync), then run the two-halves seal.  This is the PCIe-inclusive path.  A circuit whose
-        arguments derive sorted copies, columns or lookup multiplicities gets them filled into the data trace first, in that order
-        (zkh_derive_sorted, zkh_derive_columns, zkh_derive_multiplicities: a record or a lookup may read a sorted column, and the
-        multiplicities count the derived limbs); of those columns only the blinding rows are uploaded (zkh_upload_data_trace).  The accum
+        arguments derive sorted copies, columns, linked accesses or lookup multiplicities gets them filled into the data trace first, in
+        that order (zkh_derive_sorted, zkh_derive_columns, zkh_derive_links, zkh_derive_multiplicities: a record or a lookup may read
+        a sorted column, and the multiplicities count the derived limbs); of those columns only the blinding rows are uploaded (zkh_upload_data_trace).  The accum
         comes from the built-in generator of kinds 1..3, else from zkh_accumulate when the circuit carries arguments."""
         code = self.hal.alloc_elem("code", host_code.size)
         data = self.hal.alloc_elem("data", host_data.size)
@@ -267,6 +267,8 @@ class SegmentProver:
             self.hal.derive_sorted(self.circuit, seg.po2, seg.zk_cycles, code, data)
         if self.circuit.derives_columns():
             self.hal.derive_columns(self.circuit, seg.po2, seg.zk_cycles, code, data)
+        if self.circuit.derives_links():
+            self.hal.derive_links(self.circuit, seg.po2, seg.zk_cycles, code, data)
         if self.circuit.derives_multiplicities():
             self.hal.derive_multiplicities(self.circuit, seg.po2, seg.zk_cycles, code, data)
         builtin = 1 <= int(self.circuit.desc[13]) <= 3
