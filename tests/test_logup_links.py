@@ -255,6 +255,19 @@ def test_c_validator_on_a_gpu_less_circuit_gives_the_same_messages():
         assert zhal._lib.zkh_circuit_derives_links(h4.h) == 0
 
 
+def test_a_count_beyond_the_blob_is_refused_without_walking_it():
+    """header word 6 (records) and word 5 (terms) far beyond the blob's 168 words: the slot walk stops at the blob's end"""
+    desc, blob = _all()
+    hc = zhal.HostCircuit(desc)
+    for word, value, msg in ((6, 0xFFFFFFFF, "168 words for 5 terms and 4294967295 records"),
+                             (5, 0x0FFFFFFF, "168 words for 268435455 terms and 3 records")):
+        bad = _edited(blob, [(word, value)])
+        with pytest.raises(ValueError, match="ZKA1: " + msg):
+            logup.Arguments.parse(bad)
+        with pytest.raises(HalError, match="set_arguments: " + msg):
+            _c_set(hc, bad)
+
+
 # ---- the reference against a walk over the rows ----
 def _walk(rec, A, code, data, n):
     """the destinations of one LINK record over the active rows, the slow way: one access after another, the last access to every key

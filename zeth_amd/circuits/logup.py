@@ -61,8 +61,7 @@ A derived-column record (`check_columns`, zkh_derive_columns) makes data columns
 active rows (`reference_columns`).  x = the canonical value of a source cell.  LIMBS: dst_j = (x >> jL) & (2^L - 1); refused when
 x >= 2^(L nl).  ORDER over keys (k0) or (k0, k1) that are sorted: row 0 gets zeros; on row r >= 1, e = [k0 = k0@1] (two keys; the flag
 column) and d = k0 - k0@1 (one key), or e ? k1 - k1@1 : k0 - k0@1 - 1 (two keys), split into limbs like a LIMBS value; refused when
-d < 0 ("not ordered") or d >= 2^(L nl).  Sources are never destinations (records do not chain) but may be sorted-copy columns: the
-library runs sorted -> columns -> links -> multiplicities, so that a record may read a sorted column and a lookup may count a limb.
+d < 0 ("not ordered") or d >= 2^(L nl).
 
 A LINK record (`check_links`, zkh_derive_links) gives every memory access the previous access to its own address: the witness of a
 memory argument without a sorted copy.  A row r < A is an ACCESS when its selector is 1 (no selector: every active row); a selector
@@ -70,15 +69,23 @@ other than 0 / 1 is refused.  With x(c, r) the canonical value of a cell, K = x(
 same K (`reference_links`): linked[r] = [r' exists], last[r] = [no access above r has key K] (Montgomery 0 / 1); prev_j[r] = the raw
 word of carried column c_j at r' (0 when r is not linked); limb_j[r] = limb j of d = x(c_0, r) - x(c_0, r') - 1, c_0 being the clock
 (0 when not linked), refused when d < 0 ("clock not increasing") or d >= 2^(L nl).  Active rows that are no access get zeros in every
-destination.  Selectors are checked, over all records, before any clock.  Sources are columns that no derive writes; the
-destinations are written by nothing else and read by no record and no source term of a sorted copy; lookup tuples read them freely, and
-`linked` and `last` (only they) may be the multiplicity of a term that is not derived: -linked (addr, prev) removes the old tuple from the
-bus and -last (addr, val, clock) pages the final one out.  L nl <= 29 for the reason `order_constraints` gives.
+destination.  Selectors are checked, over all records, before any clock.  L nl <= 29 for the reason `order_constraints` gives.
+
+WHO WRITES A DATA COLUMN (`_check_owned` behind `check_columns` and `check_links`; csrc/arguments.h says the same).  A data column
+has at most one writer, and a derive reads only what the stages before it have finished writing.  The writers: a sorted copy (its
+tuple columns), a LIMBS / ORDER record and a LINK record (their destinations), a derived multiplicity (its column); every other
+column is the host's.  The library runs one stage after the other, each over the whole trace: sorted -> columns -> links ->
+multiplicities.  Of the columns a derive writes, the sort reads none (`check_sorted`, and no record writes into a source term's
+tuple); a LIMBS / ORDER record reads a sorted copy's columns and no record's destination (records never chain); a LINK reads none;
+the multiplicities count lookup tuples, and those read every derived column freely: a lookup may count a limb.  Nothing reads a derived
+multiplicity (`check_derived`).  A term's multiplicity is the host's column or a derived one, with one exception: `linked` and
+`last` of a LINK record (only they) may be the multiplicity of a term that is not derived: -linked (addr, prev) removes the old tuple
+from the bus and -last (addr, val, clock) pages the final one out.
 """
 from __future__ import annotations
 
 from dataclasses import dataclass, field, replace
-from typing import List, Optional, Sequence, Tuple
+from typing import List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -223,58 +230,24 @@ class Record:
         return w + [0] * (RECORD_WORDS - len(w))
 
 
-def check_columns(terms: Sequence[Term], records: Sequence[Record], group_sizes=None) -> Optional[str]:
-    """the first record that breaks a rule, named by its index, or None.  Per record, in this order: (a) the ranges of kind, L, nl,
-    n_src and the reserved words; (b) its sources are code or data columns (of the circuit, when `group_sizes` = (accum, code, data)
-    is given), its destinations pairwise distinct data columns; (c) no source is a destination of any record (records never chain)
-    or a derived multiplicity; (d) no destination is written twice: by another record, a sorted copy or a derived multiplicity;
-    (e) no destination is read by the source term of a sorted copy (the sort runs first) or is any term's multiplicity.  Lookup
-    tuples read destinations freely."""
-    for i, r in enumerate(records):
-        if r.kind not in (KIND_LIMBS, KIND_ORDER):
-            return f"record {i}: kind {r.kind} (1 = LIMBS, 2 = ORDER)"
-        if not (1 <= r.limb_bits <= 16 and 1 <= r.nl <= MAX_LIMBS and r.limb_bits * r.nl <= 32):
-            return f"record {i}: {r.nl} limbs of {r.limb_bits} bits (1..8 limbs of 1..16 bits, at most 32 bits in all)"
-        if not 1 <= r.n_src <= (1 if r.kind == KIND_LIMBS else 2):
-            return f"record {i}: {r.n_src} sources (LIMBS: 1; ORDER: 1 or 2)"
-        if len(r.srcs) == 2 and r.nl > MAX_LIMBS - 1:
-            return f"record {i}: an ORDER record with two keys has at most {MAX_LIMBS - 1} limbs (its flag column is the first destination)"
-        if r.reserved or len(r.dsts) != r.n_dsts():
-            return f"record {i}: a reserved word is not 0 (the unused source pair and the unused destination words)"
-        for g, c in r.srcs:
-            if g not in (GROUP_CODE, GROUP_DATA) or (group_sizes is not None and not 0 <= c < group_sizes[g]):
-                return f"record {i}: source ({g}, {c}) is not a code or data column"
-        for e, c in enumerate(r.dsts):
-            if group_sizes is not None and not 0 <= c < group_sizes[GROUP_DATA]:
-                return f"record {i}: destination {c} is not a data column"
-            if c in r.dsts[:e]:
-                return f"record {i}: its destination (data {c}) appears twice"
-    for i, r in enumerate(records):
-        for g, c in r.srcs:
-            if g != GROUP_DATA:
-                continue
-            for j, x in enumerate(records):
-                if c in x.dsts:
-                    return f"record {i}: its source (data {c}) is a destination of record {j} (records never chain)"
-            for j, t in enumerate(terms):
-                if t.derive and t.mult == (g, c):
-                    return f"record {i}: its source (data {c}) is the derived multiplicity of term {j}"
-        for c in r.dsts:
-            for j, x in enumerate(records):
-                if j != i and c in x.dsts:
-                    return f"record {i}: its destination (data {c}) is also written by record {j}"
-            for j, t in enumerate(terms):
-                if t.sorted_from is not None and (GROUP_DATA, c) in t.tuple_cols:
-                    return f"record {i}: its destination (data {c}) is written by the sorted copy term {j}"
-                if t.derive and t.mult == (GROUP_DATA, c):
-                    return f"record {i}: its destination (data {c}) is the derived multiplicity of term {j}"
-            for j, t in enumerate(terms):
-                if t.sorted_from is not None and 0 <= t.sorted_from < len(terms) and (GROUP_DATA, c) in terms[t.sorted_from].tuple_cols:
-                    return f"record {i}: its destination (data {c}) is read by term {t.sorted_from}, the source of a sorted copy (the sort runs first)"
-            for j, t in enumerate(terms):
-                if t.mult == (GROUP_DATA, c):
-                    return f"record {i}: its destination (data {c}) is the multiplicity of term {j}"
+def _columns_clause_a(i: int, r: Record, group_sizes) -> Optional[str]:
+    if r.kind not in (KIND_LIMBS, KIND_ORDER):
+        return f"record {i}: kind {r.kind} (1 = LIMBS, 2 = ORDER)"
+    if not (1 <= r.limb_bits <= 16 and 1 <= r.nl <= MAX_LIMBS and r.limb_bits * r.nl <= 32):
+        return f"record {i}: {r.nl} limbs of {r.limb_bits} bits (1..8 limbs of 1..16 bits, at most 32 bits in all)"
+    if not 1 <= r.n_src <= (1 if r.kind == KIND_LIMBS else 2):
+        return f"record {i}: {r.n_src} sources (LIMBS: 1; ORDER: 1 or 2)"
+    if len(r.srcs) == 2 and r.nl > MAX_LIMBS - 1:
+        return f"record {i}: an ORDER record with two keys has at most {MAX_LIMBS - 1} limbs (its flag column is the first destination)"
+    if r.reserved or len(r.dsts) != r.n_dsts():
+        return f"record {i}: a reserved word is not 0 (the unused source pair and the unused destination words)"
     return None
+
+
+def check_columns(terms: Sequence[Term], records: Sequence[Record], group_sizes=None) -> Optional[str]:
+    """the first LIMBS / ORDER record that breaks a rule, named by its index in `records` (they are one another's only peers), or None:
+    (a) the ranges of kind, L, nl, n_src and the reserved words, then (b) .. (e) of `_check_owned`"""
+    return _check_owned(terms, records, False, _columns_clause_a, group_sizes)
 
 
 KIND_LINK = 3
@@ -332,61 +305,85 @@ class Link:
         return w + [0] * (LINK_WORDS - len(w))
 
 
+def _links_clause_a(i: int, r: Link, group_sizes) -> Optional[str]:
+    if not (1 <= r.nc <= MAX_CARRIED and 1 <= r.limb_bits <= 16 and 0 <= r.nl <= MAX_LINK_LIMBS and r.limb_bits * r.nl <= MAX_ORDER_BITS):
+        return (f"record {i}: a LINK of {r.nc} carried columns and {r.nl} limbs of {r.limb_bits} bits (1..{MAX_CARRIED} carried columns, "
+                f"0..{MAX_LINK_LIMBS} limbs of 1..16 bits, at most {MAX_ORDER_BITS} bits in all)")
+    if r.reserved or len(r.dsts) != r.n_dsts():
+        return f"record {i}: a reserved word of a LINK is not 0 (words 5, 14, 15, the unused carried pairs and the unused destination words)"
+    if r.sel is not None and (r.sel >= NONE or (group_sizes is not None and not 0 <= r.sel < group_sizes[GROUP_CODE])):
+        return f"record {i}: selector {r.sel} is not a code column"
+    return None
+
+
 def check_links(terms: Sequence[Term], records: Sequence, group_sizes=None) -> Optional[str]:
-    """the first LINK record that breaks a rule, named by its index among all records, or None.  Per LINK record, in this order: (a) the
-    ranges of nc, L, nl and the reserved words; (b) its selector a code column, its sources code or data columns (of the circuit, when
-    `group_sizes` = (accum, code, data) is given), its destinations pairwise distinct data columns; then, per LINK record again: (c) no
-    source is written by a derive: a sorted copy's column, a destination of any record, a derived multiplicity; (d) no destination is
-    written twice: by another record, a sorted copy or a derived multiplicity; (e) no destination is read by any record, by the source
-    term of a sorted copy, or — `linked` and `last` apart — is a term's multiplicity.  Lookup tuples read destinations freely."""
-    links = [(i, r) for i, r in enumerate(records) if isinstance(r, Link)]
-    for i, r in links:
-        if not (1 <= r.nc <= MAX_CARRIED and 1 <= r.limb_bits <= 16 and 0 <= r.nl <= MAX_LINK_LIMBS and r.limb_bits * r.nl <= MAX_ORDER_BITS):
-            return (f"record {i}: a LINK of {r.nc} carried columns and {r.nl} limbs of {r.limb_bits} bits (1..{MAX_CARRIED} carried columns, "
-                    f"0..{MAX_LINK_LIMBS} limbs of 1..16 bits, at most {MAX_ORDER_BITS} bits in all)")
-        if r.reserved or len(r.dsts) != r.n_dsts():
-            return f"record {i}: a reserved word of a LINK is not 0 (words 5, 14, 15, the unused carried pairs and the unused destination words)"
-        if r.sel is not None and (r.sel >= NONE or (group_sizes is not None and not 0 <= r.sel < group_sizes[GROUP_CODE])):
-            return f"record {i}: selector {r.sel} is not a code column"
-        for g, c in r.srcs:
+    """the first LINK record that breaks a rule, named by its index among all `records` (all of them are its peers), or None: (a) the
+    ranges of nc, L, nl, the reserved words and the selector a code column, then (b) .. (e) of `_check_owned`"""
+    return _check_owned(terms, records, True, _links_clause_a, group_sizes)
+
+
+class _Owned(NamedTuple):
+    """A record of either kind as the ownership rule sees it"""
+    index: int                                 # its index among the records
+    srcs: Tuple[Tuple[int, int], ...]          # the (group, column) pairs it reads: the data-group ones have a writer or none
+    dsts: Tuple[int, ...]                      # the data columns it writes
+    link: bool                                 # a LINK: it runs after every LIMBS / ORDER record
+
+
+def _check_owned(terms: Sequence[Term], records: Sequence, links: bool, clause_a, group_sizes=None) -> Optional[str]:
+    """The ownership rule (the module docstring) over the LINK records of `records` (`links`) or over all of them: the first that
+    breaks a clause, or None.  Per record, in this order: `clause_a`, the kind's own ranges; (b) its sources are code or data columns
+    (of the circuit, when `group_sizes` = (accum, code, data) is given), its destinations pairwise distinct data columns.  Then, per
+    record again: (c) no source is a destination of any record (records never chain) or a derived multiplicity, and a LINK's is no
+    sorted copy's column either; (d) no destination is written twice: by another record, a sorted copy or a derived multiplicity;
+    (e) no destination is read by the source term of a sorted copy (the sort runs first) or, a LINK's, by any record, and none is a
+    term's multiplicity, a LINK's `linked` and `last` apart.  Lookup tuples read destinations freely."""
+    peers = [_Owned(i, tuple(r.srcs), tuple(r.dsts), isinstance(r, Link)) for i, r in enumerate(records)]
+    mine = [v for v in peers if v.link] if links else peers
+    for i, srcs, dsts, _ in mine:
+        problem = clause_a(i, records[i], group_sizes)
+        if problem:
+            return problem
+        for g, c in srcs:
             if g not in (GROUP_CODE, GROUP_DATA) or (group_sizes is not None and not 0 <= c < group_sizes[g]):
                 return f"record {i}: source ({g}, {c}) is not a code or data column"
-        for e, c in enumerate(r.dsts):
+        for e, c in enumerate(dsts):
             if group_sizes is not None and not 0 <= c < group_sizes[GROUP_DATA]:
                 return f"record {i}: destination {c} is not a data column"
-            if c in r.dsts[:e]:
+            if c in dsts[:e]:
                 return f"record {i}: its destination (data {c}) appears twice"
-    for i, r in links:
-        for g, c in r.srcs:
+    for i, srcs, dsts, link in mine:
+        for g, c in srcs:
             if g != GROUP_DATA:
                 continue
             for j, t in enumerate(terms):
-                if t.sorted_from is not None and (g, c) in t.tuple_cols:
+                if link and t.sorted_from is not None and (g, c) in t.tuple_cols:
                     return f"record {i}: its source (data {c}) is written by the sorted copy term {j} (a LINK reads what no derive writes)"
-            for j, x in enumerate(records):
+            for x in peers:
                 if c in x.dsts:
-                    return f"record {i}: its source (data {c}) is a destination of record {j} (records never chain)"
+                    return f"record {i}: its source (data {c}) is a destination of record {x.index} (records never chain)"
             for j, t in enumerate(terms):
                 if t.derive and t.mult == (g, c):
                     return f"record {i}: its source (data {c}) is the derived multiplicity of term {j}"
-        for e, c in enumerate(r.dsts):
-            for j, x in enumerate(records):
-                if j != i and c in x.dsts:
-                    return f"record {i}: its destination (data {c}) is also written by record {j}"
+        for e, c in enumerate(dsts):
+            for x in peers:
+                if x.index != i and c in x.dsts:
+                    return f"record {i}: its destination (data {c}) is also written by record {x.index}"
             for j, t in enumerate(terms):
                 if t.sorted_from is not None and (GROUP_DATA, c) in t.tuple_cols:
                     return f"record {i}: its destination (data {c}) is written by the sorted copy term {j}"
                 if t.derive and t.mult == (GROUP_DATA, c):
                     return f"record {i}: its destination (data {c}) is the derived multiplicity of term {j}"
-            for j, x in enumerate(records):
-                if (GROUP_DATA, c) in x.srcs:
-                    return f"record {i}: its destination (data {c}) is read by record {j} (the links run after the columns, and never chain)"
-            for j, t in enumerate(terms):
+            for x in peers:
+                if link and (GROUP_DATA, c) in x.srcs:
+                    return f"record {i}: its destination (data {c}) is read by record {x.index} (the links run after the columns, and never chain)"
+            for t in terms:
                 if t.sorted_from is not None and 0 <= t.sorted_from < len(terms) and (GROUP_DATA, c) in terms[t.sorted_from].tuple_cols:
                     return f"record {i}: its destination (data {c}) is read by term {t.sorted_from}, the source of a sorted copy (the sort runs first)"
             for j, t in enumerate(terms):
-                if e >= 2 and t.mult == (GROUP_DATA, c):
-                    return f"record {i}: its destination (data {c}) is the multiplicity of term {j} (of a LINK's destinations only linked and last may be)"
+                if t.mult == (GROUP_DATA, c) and not (link and e < 2):
+                    return (f"record {i}: its destination (data {c}) is the multiplicity of term {j}"
+                            + (" (of a LINK's destinations only linked and last may be)" if link else ""))
     return None
 
 
@@ -458,6 +455,8 @@ class Arguments:
         n_rec = d[6] if version >= 4 else 0
         at, sizes = ARGS_HEADER + TERM_WORDS * n, []
         for _ in range(n_rec):                                                # a LINK record (version 5) takes two slots
+            if at > len(d):                                                   # past the blob's end: refused below, whatever n_rec says
+                break
             sizes.append(LINK_WORDS if version >= 5 and at < len(d) and d[at] == KIND_LINK else RECORD_WORDS)
             at += sizes[-1]
         if len(d) != at:

@@ -2,6 +2,18 @@
 // form every consumer reads, and what the consumers share.  arguments.hip owns the blob format and the rules a blob must keep;
 // accumulate.hip (zkh_accumulate), multiplicities.hip (zkh_derive_multiplicities), sort.hip (zkh_derive_sorted), columns.hip
 // (zkh_derive_columns) and links.hip (zkh_derive_links) read zkh_circuit::args and never see a blob word.
+//
+// WHO WRITES A DATA COLUMN (the module docstring of logup.py says the same; check_owned in arguments.hip keeps it).  A data column has at
+// most one writer, and a derive reads only what the stages before it have finished writing.  The writers: a sorted copy (its tuple
+// columns), a LIMBS / ORDER record and a LINK record (their destinations), a derived multiplicity (its column); every other column is
+// the host's.  The stages run one after the other, each over the whole trace: sorted -> columns -> links -> multiplicities.  Of the
+// columns a derive writes, the sort reads none; a LIMBS / ORDER record reads a sorted copy's columns and no record's destination
+// (records never chain); a LINK reads none; the multiplicities count lookup tuples, and those read every derived column freely.
+// Nothing reads a derived multiplicity.  A term's multiplicity is the host's column or a derived one, and of a LINK's destinations
+// linked and last (only they) may be the multiplicity of a term that is not derived.
+//
+// A derive that refuses a witness leaves `data` unchanged: its check pass reduces the lowest bad (record, row) into a BadRow, the host
+// reads that back, and only then does anything write.
 #pragma once
 #include <vector>
 
@@ -68,6 +80,49 @@ inline TermCols term_cols(const Term& t) {
 // circuit's widths at 2^po2 rows.  `who` prefixes the messages.  *n = rows, *A = active rows.
 const char* trace_rows(const char* who, const zkh_circuit* c, size_t po2, size_t zk_cycles, const zkh_buf* code, const zkh_buf* data,
                        const zkh_buf* accum, size_t* n, uint32_t* A);
+
+// the canonical value of a raw trace word (raw words >= P are legal)
+__host__ __device__ __forceinline__ uint32_t canonical(uint32_t raw) { return fp_decode(Fp::raw(raw % P)); }
+// the canonical value of the cell (g, c) at `row` of an n-row trace, read back for an error message (T: uint32_t, or wider to subtract)
+template <typename T>
+const char* read_cell(zkh_ctx* ctx, const zkh_buf* code, const zkh_buf* data, uint32_t g, uint32_t c, size_t n, uint32_t row, T* v) {
+    uint32_t w;
+    ZKH_TRY(zkh_read(ctx, g == GROUP_CODE ? code : data, &w, (size_t)c * n + row, 1));
+    *v = canonical(w);
+    return nullptr;
+}
+
+// The lowest (hi, lo) that a check pass refused, hi << 32 | lo on the device: two words, all ones = none.
+struct BadRow {
+    Tmp buf;
+    bool found = false;
+    uint32_t hi = 0, lo = 0;
+    const char* init(zkh_ctx* ctx) {
+        ZKH_TRY(new_buf(ctx, 2, false, buf.out()));
+        ZKH_HIP(hipMemsetAsync(buf->ptr(), 0xff, 8, ctx->stream));
+        return nullptr;
+    }
+    unsigned long long* ptr() const { return (unsigned long long*)buf->ptr(); }
+    const char* read(zkh_ctx* ctx) {                    // after the check pass: found, and then (hi, lo)
+        uint32_t st[2];
+        ZKH_TRY(zkh_read(ctx, buf, st, 0, 2));
+        lo = st[0]; hi = st[1];
+        found = (lo & hi) != NONE;
+        return nullptr;
+    }
+};
+// ... and its device side: this lane's refused row (NONE = none) of `record`.  Only a wave that found one reduces (the branch is
+// wave-uniform) and issues one 64-bit atomicMin.
+__device__ __forceinline__ void report_bad_row(unsigned long long* status, uint32_t record, uint32_t bad) {
+    if (__ballot(bad != NONE) != 0) {
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            const uint32_t o = __shfl_xor(bad, off, 64);
+            bad = o < bad ? o : bad;
+        }
+        if ((threadIdx.x & 63) == 0) atomicMin(status, ((unsigned long long)record << 32) | bad);
+    }
+}
 
 __device__ __forceinline__ const uint32_t* group_ptr(const uint32_t* code, const uint32_t* data, uint32_t g) { return g == GROUP_CODE ? code : data; }
 // a trace cell as its residue below P (a Montgomery word): cells are compared mod P

@@ -1,6 +1,6 @@
 // arguments.hip — the ZKA1 argument blob (layout: zeth_amd/circuits/logup.py; DESIGN.md §2 ARGUMENTS): its decoding into
 // zkh::Arguments (terms, from version 4 derived-column records, from version 5 LINK records), the rules a circuit's arguments keep
-// (check_sorted, check_derived, check_columns, check_links, in this order), and the entry points that attach them to a circuit and ask what they derive.
+// (check_sorted, check_derived, then check_owned over the LIMBS / ORDER records and over the LINK records), and the entry points that attach them to a circuit and ask what they derive.
 // decode_arguments is the only code that knows the blob's words; everything else, here and in the consumers, reads decoded terms.
 #include "arguments.h"
 
@@ -19,8 +19,8 @@ const char* decode_arguments(const uint32_t* a, size_t words, Arguments* out) {
     ZKH_REQUIRE(words >= ARGS_HEADER && a[0] == ARGS_MAGIC && a[1] >= 1 && a[1] <= 5, "set_arguments: not a ZKA1 (version 1) argument blob");
     const uint32_t n_terms = a[5], n_records = a[1] >= 4 ? a[6] : 0;            // header word 6: the records of version 4, reserved before
     const size_t rec0 = ARGS_HEADER + (size_t)TERM_WORDS * n_terms;
-    size_t end = rec0;                                                          // a LINK record (version 5) takes two slots
-    for (uint32_t i = 0; i < n_records; i++) end += a[1] >= 5 && end < words && a[end] == KIND_LINK ? LINK_WORDS : RECORD_WORDS;
+    size_t end = rec0;                                                          // a LINK record (version 5) takes two slots; past the blob's end the walk stops
+    for (uint32_t i = 0; i < n_records && end <= words; i++) end += a[1] >= 5 && end < words && a[end] == KIND_LINK ? LINK_WORDS : RECORD_WORDS;
     const bool fits = words == end;
     ZKH_REQUIRE(fits || a[1] < 4, "set_arguments: %zu words for %u terms and %u records", words, n_terms, n_records);
     ZKH_REQUIRE(fits, "set_arguments: %zu words for %u terms", words, n_terms);
@@ -44,9 +44,9 @@ const char* decode_arguments(const uint32_t* a, size_t words, Arguments* out) {
         }
     }
     // Derived-column records (version 4): kind, L, nl, n_src, two (group, column) source pairs, eight destination data columns.  As
-    // with the flags, a reserved word that is set is recorded here and refused by the rules (check_columns).
+    // with the flags, a reserved word that is set is recorded here and refused by the rules (columns_clause_a).
     // LINK records (version 5, kind 3, 32 words): L, nl, nc, sel, 0, the key's (group, column), three carried (group, column) pairs, 0, 0,
-    // then from word 16 the destinations linked, last, prev_0 .. prev_{nc-1}, limb_0 .. limb_{nl-1}, the rest 0 (check_links).
+    // then from word 16 the destinations linked, last, prev_0 .. prev_{nc-1}, limb_0 .. limb_{nl-1}, the rest 0 (links_clause_a).
     out->records.clear();
     out->links.clear();
     const uint32_t* r = a + rec0;
@@ -167,157 +167,121 @@ const char* check_sorted(const Arguments& a) {
     return nullptr;
 }
 
-bool writes(const Record& x, uint32_t col) {                                    // data column `col` among the destinations of x
-    for (uint32_t e = 0; e < x.n_dst; e++)
-        if (x.dst[e] == col) return true;
-    return false;
+bool is_column(const zkh_circuit* c, uint32_t g, uint32_t col) { return (g == GROUP_CODE || g == GROUP_DATA) && col < c->group_size[g]; }
+
+// A record of either kind as the ownership rule (arguments.h) sees it
+struct Owned {
+    uint32_t index;                                     // its index among the blob's records
+    bool link;                                          // a LINK: it runs after every LIMBS / ORDER record
+    uint32_t n_src, sg[1 + MAX_CARRIED], sc[1 + MAX_CARRIED];   // the (group, column) pairs it reads (LINK: the key, then the carried columns)
+    uint32_t n_dst, dst[MAX_LINK_DSTS];                 // the data columns it writes
+    bool writes(uint32_t col) const { return std::find(dst, dst + n_dst, col) != dst + n_dst; }
+    bool reads(uint32_t col) const {                    // data column `col` among its sources
+        for (uint32_t s = 0; s < n_src; s++)
+            if (sg[s] == GROUP_DATA && sc[s] == col) return true;
+        return false;
+    }
+};
+// the LIMBS / ORDER records, then the LINK records: the blob's order (a blob that has it otherwise is refused before anything reads this)
+std::vector<Owned> owned(const Arguments& a) {
+    std::vector<Owned> all;
+    for (const Record& r : a.records) {
+        Owned v{(uint32_t)all.size(), false, std::min(r.n_src, 2u), {}, {}, r.n_dst, {}};
+        std::copy(r.sg, r.sg + v.n_src, v.sg); std::copy(r.sc, r.sc + v.n_src, v.sc); std::copy(r.dst, r.dst + r.n_dst, v.dst);
+        all.push_back(v);
+    }
+    for (const Link& r : a.links) {
+        const uint32_t nc = std::min(r.nc, MAX_CARRIED);
+        Owned v{r.index, true, 1 + nc, {r.kg}, {r.kc}, r.n_dst, {}};
+        std::copy(r.cg, r.cg + nc, v.sg + 1); std::copy(r.cc, r.cc + nc, v.sc + 1); std::copy(r.dst, r.dst + r.n_dst, v.dst);
+        all.push_back(v);
+    }
+    return all;
 }
 
-// logup.check_columns: the first derived-column record that breaks a rule.  Per record: (a) the ranges of kind, L, nl, n_src and the
-// reserved words; (b) its sources are code or data columns of the circuit, its destinations pairwise distinct data columns; then, per
-// record again: (c) no source is a destination of any record (records never chain) or a derived multiplicity; (d) no destination is
-// written twice: by another record, a sorted copy or a derived multiplicity; (e) no destination is read by the source term of a sorted
-// copy (the sort runs first) or is any term's multiplicity.  Lookup tuples read destinations freely.
-const char* check_columns(const zkh_circuit* c, const Arguments& a) {
-    const uint32_t n_terms = (uint32_t)a.terms.size(), n_rec = (uint32_t)a.records.size();
-    for (uint32_t i = 0; i < n_rec; i++) {
-        const Record& r = a.records[i];
-        ZKH_REQUIRE(r.kind == KIND_LIMBS || r.kind == KIND_ORDER, "set_arguments: record %u: kind %u (1 = LIMBS, 2 = ORDER)", i, r.kind);
-        ZKH_REQUIRE(r.L >= 1 && r.L <= 16 && r.nl >= 1 && r.nl <= MAX_LIMBS && r.L * r.nl <= 32, "set_arguments: record %u: %u limbs of %u bits "
-                    "(1..8 limbs of 1..16 bits, at most 32 bits in all)", i, r.nl, r.L);
-        ZKH_REQUIRE(r.n_src >= 1 && r.n_src <= (r.kind == KIND_LIMBS ? 1u : 2u), "set_arguments: record %u: %u sources (LIMBS: 1; ORDER: 1 or 2)", i, r.n_src);
-        ZKH_REQUIRE(r.n_src < 2 || r.nl <= MAX_LIMBS - 1, "set_arguments: record %u: an ORDER record with two keys has at most %u limbs (its flag column is "
-                    "the first destination)", i, MAX_LIMBS - 1);
-        ZKH_REQUIRE(!r.reserved, "set_arguments: record %u: a reserved word is not 0 (the unused source pair and the unused destination words)", i);
-        for (uint32_t j = 0; j < r.n_src; j++)
-            ZKH_REQUIRE((r.sg[j] == GROUP_CODE || r.sg[j] == GROUP_DATA) && r.sc[j] < c->group_size[r.sg[j]], "set_arguments: record %u: source (%u, %u) is "
-                        "not a code or data column", i, r.sg[j], r.sc[j]);
-        for (uint32_t e = 0; e < r.n_dst; e++) {
-            ZKH_REQUIRE(r.dst[e] < c->group_size[GROUP_DATA], "set_arguments: record %u: destination %u is not a data column", i, r.dst[e]);
-            for (uint32_t e2 = 0; e2 < e; e2++)
-                ZKH_REQUIRE(r.dst[e2] != r.dst[e], "set_arguments: record %u: its destination (data %u) appears twice", i, r.dst[e]);
-        }
-    }
-    for (uint32_t i = 0; i < n_rec; i++) {
-        const Record& r = a.records[i];
-        for (uint32_t s = 0; s < r.n_src; s++) {
-            const uint32_t col = r.sc[s];
-            if (r.sg[s] != GROUP_DATA) continue;
-            for (uint32_t j = 0; j < n_rec; j++)
-                ZKH_REQUIRE(!writes(a.records[j], col), "set_arguments: record %u: its source (data %u) is a destination of record %u (records never chain)", i, col, j);
-            for (uint32_t j = 0; j < n_terms; j++)
-                ZKH_REQUIRE(!(a.terms[j].derive && a.terms[j].mg == GROUP_DATA && a.terms[j].mc == col), "set_arguments: record %u: its source (data %u) is the "
-                            "derived multiplicity of term %u", i, col, j);
-        }
-        for (uint32_t e = 0; e < r.n_dst; e++) {
-            const uint32_t col = r.dst[e];
-            for (uint32_t j = 0; j < n_rec; j++)
-                ZKH_REQUIRE(j == i || !writes(a.records[j], col), "set_arguments: record %u: its destination (data %u) is also written by record %u", i, col, j);
-            for (uint32_t j = 0; j < n_terms; j++) {
-                const Term& t = a.terms[j];
-                ZKH_REQUIRE(!(t.sorted && in_tuple(t, t.w, GROUP_DATA, col)), "set_arguments: record %u: its destination (data %u) is written by the sorted copy "
-                            "term %u", i, col, j);
-                ZKH_REQUIRE(!(t.derive && t.mg == GROUP_DATA && t.mc == col), "set_arguments: record %u: its destination (data %u) is the derived multiplicity of "
-                            "term %u", i, col, j);
-            }
-            for (uint32_t j = 0; j < n_terms; j++) {
-                const Term& t = a.terms[j];
-                ZKH_REQUIRE(!(t.sorted && in_tuple(a.terms[t.sorted_from], a.terms[t.sorted_from].w, GROUP_DATA, col)), "set_arguments: record %u: its destination "
-                            "(data %u) is read by term %u, the source of a sorted copy (the sort runs first)", i, col, t.sorted_from);
-            }
-            for (uint32_t j = 0; j < n_terms; j++)
-                ZKH_REQUIRE(!(a.terms[j].mg == GROUP_DATA && a.terms[j].mc == col), "set_arguments: record %u: its destination (data %u) is the multiplicity of term %u",
-                            i, col, j);
-        }
-    }
+// logup.check_columns' own clause (a): the ranges of kind, L, nl, n_src and the reserved words
+const char* columns_clause_a(const Record& r, uint32_t i) {
+    ZKH_REQUIRE(r.kind == KIND_LIMBS || r.kind == KIND_ORDER, "set_arguments: record %u: kind %u (1 = LIMBS, 2 = ORDER)", i, r.kind);
+    ZKH_REQUIRE(r.L >= 1 && r.L <= 16 && r.nl >= 1 && r.nl <= MAX_LIMBS && r.L * r.nl <= 32, "set_arguments: record %u: %u limbs of %u bits "
+                "(1..8 limbs of 1..16 bits, at most 32 bits in all)", i, r.nl, r.L);
+    ZKH_REQUIRE(r.n_src >= 1 && r.n_src <= (r.kind == KIND_LIMBS ? 1u : 2u), "set_arguments: record %u: %u sources (LIMBS: 1; ORDER: 1 or 2)", i, r.n_src);
+    ZKH_REQUIRE(r.n_src < 2 || r.nl <= MAX_LIMBS - 1, "set_arguments: record %u: an ORDER record with two keys has at most %u limbs (its flag column is "
+                "the first destination)", i, MAX_LIMBS - 1);
+    ZKH_REQUIRE(!r.reserved, "set_arguments: record %u: a reserved word is not 0 (the unused source pair and the unused destination words)", i);
+    return nullptr;
+}
+// logup.check_links' own clause (a): the ranges of nc, L, nl, the reserved words, and the selector a code column
+const char* links_clause_a(const zkh_circuit* c, const Link& r) {
+    const uint32_t i = r.index;
+    ZKH_REQUIRE(r.nc >= 1 && r.nc <= MAX_CARRIED && r.L >= 1 && r.L <= 16 && r.nl <= MAX_LINK_LIMBS && r.L * r.nl <= MAX_ORDER_BITS,
+                "set_arguments: record %u: a LINK of %u carried columns and %u limbs of %u bits (1..%u carried columns, 0..%u limbs of 1..16 bits, at most "
+                "%u bits in all)", i, r.nc, r.nl, r.L, MAX_CARRIED, MAX_LINK_LIMBS, MAX_ORDER_BITS);
+    ZKH_REQUIRE(!r.reserved, "set_arguments: record %u: a reserved word of a LINK is not 0 (words 5, 14, 15, the unused carried pairs and the unused "
+                "destination words)", i);
+    ZKH_REQUIRE(r.sel == NONE || r.sel < c->group_size[GROUP_CODE], "set_arguments: record %u: selector %u is not a code column", i, r.sel);
     return nullptr;
 }
 
-bool writes(const Link& x, uint32_t col) {
-    for (uint32_t e = 0; e < x.n_dst; e++)
-        if (x.dst[e] == col) return true;
-    return false;
-}
-bool reads(const Record& x, uint32_t col) {                                     // data column `col` among the sources of x
-    for (uint32_t s = 0; s < x.n_src && s < 2; s++)
-        if (x.sg[s] == GROUP_DATA && x.sc[s] == col) return true;
-    return false;
-}
-bool reads(const Link& x, uint32_t col) {
-    if (x.kg == GROUP_DATA && x.kc == col) return true;
-    for (uint32_t s = 0; s < x.nc; s++)
-        if (x.cg[s] == GROUP_DATA && x.cc[s] == col) return true;
-    return false;
-}
-
-// logup.check_links: the first LINK record that breaks a rule, named by its index among all records.  Per LINK record: (a) the ranges of
-// nc, L, nl and the reserved words; (b) its selector a code column, its sources code or data columns, its destinations pairwise distinct
-// data columns; then, per LINK record again: (c) no source is written by a derive: a sorted copy's column, a destination of any record, a
-// derived multiplicity; (d) no destination is written twice: by another record, a sorted copy or a derived multiplicity; (e) no
-// destination is read by any record, by the source term of a sorted copy, or — linked and last apart — is a term's multiplicity.
-const char* check_links(const zkh_circuit* c, const Arguments& a) {
-    const uint32_t n_terms = (uint32_t)a.terms.size(), n_rec = (uint32_t)a.records.size();
-    for (const Link& r : a.links) {
-        const uint32_t i = r.index;
-        ZKH_REQUIRE(r.nc >= 1 && r.nc <= MAX_CARRIED && r.L >= 1 && r.L <= 16 && r.nl <= MAX_LINK_LIMBS && r.L * r.nl <= MAX_ORDER_BITS,
-                    "set_arguments: record %u: a LINK of %u carried columns and %u limbs of %u bits (1..%u carried columns, 0..%u limbs of 1..16 bits, at most "
-                    "%u bits in all)", i, r.nc, r.nl, r.L, MAX_CARRIED, MAX_LINK_LIMBS, MAX_ORDER_BITS);
-        ZKH_REQUIRE(!r.reserved, "set_arguments: record %u: a reserved word of a LINK is not 0 (words 5, 14, 15, the unused carried pairs and the unused "
-                    "destination words)", i);
-        ZKH_REQUIRE(r.sel == NONE || r.sel < c->group_size[GROUP_CODE], "set_arguments: record %u: selector %u is not a code column", i, r.sel);
-        auto is_column = [&](uint32_t g, uint32_t col) { return (g == GROUP_CODE || g == GROUP_DATA) && col < c->group_size[g]; };
-        ZKH_REQUIRE(is_column(r.kg, r.kc), "set_arguments: record %u: source (%u, %u) is not a code or data column", i, r.kg, r.kc);
-        for (uint32_t j = 0; j < r.nc; j++)
-            ZKH_REQUIRE(is_column(r.cg[j], r.cc[j]), "set_arguments: record %u: source (%u, %u) is not a code or data column", i, r.cg[j], r.cc[j]);
-        for (uint32_t e = 0; e < r.n_dst; e++) {
-            ZKH_REQUIRE(r.dst[e] < c->group_size[GROUP_DATA], "set_arguments: record %u: destination %u is not a data column", i, r.dst[e]);
+// logup._check_owned, the ownership rule (arguments.h) over one kind of record: the LIMBS / ORDER records, whose peers are one another
+// (logup.check_columns), or the LINK records, whose peers are all records (logup.check_links).  The first record that breaks a clause.
+// Per record: the kind's clause (a); (b) its sources are code or data columns of the circuit, its destinations pairwise distinct data
+// columns.  Then, per record again: (c) no source is a destination of any record (records never chain) or a derived multiplicity, and a
+// LINK's is no sorted copy's column either; (d) no destination is written twice: by another record, a sorted copy or a derived
+// multiplicity; (e) no destination is read by the source term of a sorted copy (the sort runs first; check_sorted has bounded
+// sorted_from) or, a LINK's, by any record, and none is a term's multiplicity, a LINK's linked and last apart.
+const char* check_owned(const zkh_circuit* c, const Arguments& a, const std::vector<Owned>& all, bool links) {
+    const size_t n_rec = a.records.size(), lo = links ? n_rec : 0, hi = links ? all.size() : n_rec;     // the kind is [lo, hi), its peers [0, hi)
+    const uint32_t n_terms = (uint32_t)a.terms.size();
+    auto is_mult = [](const Term& t, uint32_t col) { return t.mg == GROUP_DATA && t.mc == col; };
+    for (size_t p = lo; p < hi; p++) {
+        const Owned& v = all[p];
+        const uint32_t i = v.index;
+        ZKH_TRY(links ? links_clause_a(c, a.links[p - n_rec]) : columns_clause_a(a.records[p], i));
+        for (uint32_t s = 0; s < v.n_src; s++)
+            ZKH_REQUIRE(is_column(c, v.sg[s], v.sc[s]), "set_arguments: record %u: source (%u, %u) is not a code or data column", i, v.sg[s], v.sc[s]);
+        for (uint32_t e = 0; e < v.n_dst; e++) {
+            ZKH_REQUIRE(v.dst[e] < c->group_size[GROUP_DATA], "set_arguments: record %u: destination %u is not a data column", i, v.dst[e]);
             for (uint32_t e2 = 0; e2 < e; e2++)
-                ZKH_REQUIRE(r.dst[e2] != r.dst[e], "set_arguments: record %u: its destination (data %u) appears twice", i, r.dst[e]);
+                ZKH_REQUIRE(v.dst[e2] != v.dst[e], "set_arguments: record %u: its destination (data %u) appears twice", i, v.dst[e]);
         }
     }
-    for (const Link& r : a.links) {
-        const uint32_t i = r.index;
-        for (uint32_t s = 0; s <= r.nc; s++) {
-            const uint32_t g = s ? r.cg[s - 1] : r.kg, col = s ? r.cc[s - 1] : r.kc;
-            if (g != GROUP_DATA) continue;
-            for (uint32_t j = 0; j < n_terms; j++)
+    for (size_t p = lo; p < hi; p++) {
+        const Owned& v = all[p];
+        const uint32_t i = v.index;
+        for (uint32_t s = 0; s < v.n_src; s++) {
+            const uint32_t col = v.sc[s];
+            if (v.sg[s] != GROUP_DATA) continue;
+            for (uint32_t j = 0; links && j < n_terms; j++)
                 ZKH_REQUIRE(!(a.terms[j].sorted && in_tuple(a.terms[j], a.terms[j].w, GROUP_DATA, col)), "set_arguments: record %u: its source (data %u) is written "
                             "by the sorted copy term %u (a LINK reads what no derive writes)", i, col, j);
-            for (uint32_t j = 0; j < n_rec; j++)
-                ZKH_REQUIRE(!writes(a.records[j], col), "set_arguments: record %u: its source (data %u) is a destination of record %u (records never chain)", i, col, j);
-            for (const Link& x : a.links)
-                ZKH_REQUIRE(!writes(x, col), "set_arguments: record %u: its source (data %u) is a destination of record %u (records never chain)", i, col, x.index);
+            for (size_t q = 0; q < hi; q++)
+                ZKH_REQUIRE(!all[q].writes(col), "set_arguments: record %u: its source (data %u) is a destination of record %u (records never chain)", i, col,
+                            all[q].index);
             for (uint32_t j = 0; j < n_terms; j++)
-                ZKH_REQUIRE(!(a.terms[j].derive && a.terms[j].mg == GROUP_DATA && a.terms[j].mc == col), "set_arguments: record %u: its source (data %u) is the "
-                            "derived multiplicity of term %u", i, col, j);
+                ZKH_REQUIRE(!(a.terms[j].derive && is_mult(a.terms[j], col)), "set_arguments: record %u: its source (data %u) is the derived multiplicity of term %u",
+                            i, col, j);
         }
-        for (uint32_t e = 0; e < r.n_dst; e++) {
-            const uint32_t col = r.dst[e];
-            for (uint32_t j = 0; j < n_rec; j++)
-                ZKH_REQUIRE(!writes(a.records[j], col), "set_arguments: record %u: its destination (data %u) is also written by record %u", i, col, j);
-            for (const Link& x : a.links)
-                ZKH_REQUIRE(x.index == i || !writes(x, col), "set_arguments: record %u: its destination (data %u) is also written by record %u", i, col, x.index);
+        for (uint32_t e = 0; e < v.n_dst; e++) {
+            const uint32_t col = v.dst[e];
+            for (size_t q = 0; q < hi; q++)
+                ZKH_REQUIRE(q == p || !all[q].writes(col), "set_arguments: record %u: its destination (data %u) is also written by record %u", i, col, all[q].index);
             for (uint32_t j = 0; j < n_terms; j++) {
                 const Term& t = a.terms[j];
                 ZKH_REQUIRE(!(t.sorted && in_tuple(t, t.w, GROUP_DATA, col)), "set_arguments: record %u: its destination (data %u) is written by the sorted copy "
                             "term %u", i, col, j);
-                ZKH_REQUIRE(!(t.derive && t.mg == GROUP_DATA && t.mc == col), "set_arguments: record %u: its destination (data %u) is the derived multiplicity of "
-                            "term %u", i, col, j);
+                ZKH_REQUIRE(!(t.derive && is_mult(t, col)), "set_arguments: record %u: its destination (data %u) is the derived multiplicity of term %u", i, col, j);
             }
-            for (uint32_t j = 0; j < n_rec; j++)
-                ZKH_REQUIRE(!reads(a.records[j], col), "set_arguments: record %u: its destination (data %u) is read by record %u (the links run after the columns, "
-                            "and never chain)", i, col, j);
-            for (const Link& x : a.links)
-                ZKH_REQUIRE(!reads(x, col), "set_arguments: record %u: its destination (data %u) is read by record %u (the links run after the columns, and never "
-                            "chain)", i, col, x.index);
-            for (uint32_t j = 0; j < n_terms; j++) {
-                const Term& t = a.terms[j];
+            for (size_t q = 0; links && q < hi; q++)
+                ZKH_REQUIRE(!all[q].reads(col), "set_arguments: record %u: its destination (data %u) is read by record %u (the links run after the columns, and never "
+                            "chain)", i, col, all[q].index);
+            for (const Term& t : a.terms)
                 ZKH_REQUIRE(!(t.sorted && in_tuple(a.terms[t.sorted_from], a.terms[t.sorted_from].w, GROUP_DATA, col)), "set_arguments: record %u: its destination "
                             "(data %u) is read by term %u, the source of a sorted copy (the sort runs first)", i, col, t.sorted_from);
+            for (uint32_t j = 0; j < n_terms; j++) {
+                ZKH_REQUIRE(links || !is_mult(a.terms[j], col), "set_arguments: record %u: its destination (data %u) is the multiplicity of term %u", i, col, j);
+                ZKH_REQUIRE(!links || e < 2 || !is_mult(a.terms[j], col), "set_arguments: record %u: its destination (data %u) is the multiplicity of term %u (of a "
+                            "LINK's destinations only linked and last may be)", i, col, j);
             }
-            for (uint32_t j = 0; j < n_terms; j++)
-                ZKH_REQUIRE(e < 2 || !(a.terms[j].mg == GROUP_DATA && a.terms[j].mc == col), "set_arguments: record %u: its destination (data %u) is the multiplicity "
-                            "of term %u (of a LINK's destinations only linked and last may be)", i, col, j);
         }
     }
     return nullptr;
@@ -331,7 +295,6 @@ const char* check_arguments(const zkh_circuit* c, const Arguments& a) {
     const uint32_t mix = c->global_size[GLOBAL_MIX];
     ZKH_REQUIRE((uint64_t)a.alpha + 4 <= mix && (uint64_t)a.beta + 4 <= mix, "set_arguments: alpha / beta at mix words %u / %u, the circuit has %u",
                 a.alpha, a.beta, mix);
-    auto is_column = [&](uint32_t g, uint32_t col) { return (g == GROUP_CODE || g == GROUP_DATA) && col < c->group_size[g]; };
     std::vector<uint32_t> per_col(k, 0);
     uint32_t prev = 0;
     for (uint32_t i = 0; i < a.terms.size(); i++) {
@@ -341,19 +304,20 @@ const char* check_arguments(const zkh_circuit* c, const Arguments& a) {
         ZKH_REQUIRE(++per_col[t.col] <= MAX_TERMS, "set_arguments: accum column %u has more than %u terms (the degree bound)", t.col, MAX_TERMS);
         ZKH_REQUIRE(t.neg <= 1 && t.tag < P, "set_arguments: term %u: sign word %u / tag %u", i, t.neg, t.tag);
         ZKH_REQUIRE(t.sel == NONE || t.sel < c->group_size[GROUP_CODE], "set_arguments: term %u: selector %u is not a code column", i, t.sel);
-        ZKH_REQUIRE(t.mg == NONE || is_column(t.mg, t.mc), "set_arguments: term %u: multiplicity column (%u, %u) is not a code or data column", i,
+        ZKH_REQUIRE(t.mg == NONE || is_column(c, t.mg, t.mc), "set_arguments: term %u: multiplicity column (%u, %u) is not a code or data column", i,
                     t.mg, t.mc);
         ZKH_REQUIRE(t.w >= 1 && t.w <= MAX_TUPLE, "set_arguments: term %u: tuple width %u (1..%u)", i, t.w, MAX_TUPLE);
         for (uint32_t e = 0; e < t.w; e++)
-            ZKH_REQUIRE(is_column(t.tg[e], t.tc[e]), "set_arguments: term %u: tuple column (%u, %u) is not a code or data column", i, t.tg[e], t.tc[e]);
+            ZKH_REQUIRE(is_column(c, t.tg[e], t.tc[e]), "set_arguments: term %u: tuple column (%u, %u) is not a code or data column", i, t.tg[e], t.tc[e]);
     }
     for (uint32_t col = 0; col < k; col++) ZKH_REQUIRE(per_col[col] >= 1, "set_arguments: accum column %u has no terms", col);
     if (a.version >= 3) ZKH_TRY(check_sorted(a));
     if (a.version >= 2) ZKH_TRY(check_derived(a));
     ZKH_REQUIRE(a.late_record == NONE, "set_arguments: record %u: a LIMBS / ORDER record after the LINK record %u (LINK records come last)", a.late_record,
                 a.late_after);
-    ZKH_TRY(check_columns(c, a));
-    return check_links(c, a);
+    const std::vector<Owned> all = owned(a);
+    ZKH_TRY(check_owned(c, a, all, false));
+    return check_owned(c, a, all, true);
 }
 
 }  // namespace
@@ -401,8 +365,7 @@ extern "C" const char* zkh_circuit_derived_data_columns(const zkh_circuit* c, ui
             if (t.derive) out.push_back(t.mc);
             if (t.sorted) out.insert(out.end(), t.tc, t.tc + t.w);
         }
-        for (const Record& r : c->args->records) out.insert(out.end(), r.dst, r.dst + r.n_dst);
-        for (const Link& r : c->args->links) out.insert(out.end(), r.dst, r.dst + r.n_dst);
+        for (const Owned& v : owned(*c->args)) out.insert(out.end(), v.dst, v.dst + v.n_dst);
     }
     std::sort(out.begin(), out.end());
     out.erase(std::unique(out.begin(), out.end()), out.end());

@@ -21,9 +21,6 @@ using namespace zkh;
 namespace {
 
 constexpr uint32_t COL_THREADS = 256, COL_ROWS = 4;      // rows per lane: one dwordx4 per column
-constexpr unsigned long long NO_ROW = ~0ull;
-
-__device__ __forceinline__ uint32_t canonical(uint32_t raw) { return fp_decode(Fp::raw(raw % P)); }
 
 // rows [r0, r0 + cnt) of a column as canonical values; vec: a full, aligned quad
 __device__ __forceinline__ void load_rows(const uint32_t* __restrict__ col, uint32_t r0, uint32_t cnt, bool vec, uint32_t v[COL_ROWS]) {
@@ -90,14 +87,7 @@ __global__ __launch_bounds__(COL_THREADS) void k_columns(const uint32_t* __restr
 #pragma unroll
         for (uint32_t j = COL_ROWS; j-- > 0;)
             if (j < cnt && (d[j] < 0 || (d[j] >> bits) != 0)) bad = r0 + j;
-        if (__ballot(bad != NONE) != 0) {                // wave-uniform: only a wave that found one reduces and writes
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) {
-                const uint32_t o = __shfl_xor(bad, off, 64);
-                bad = o < bad ? o : bad;
-            }
-            if ((threadIdx.x & 63) == 0) atomicMin(status, ((unsigned long long)blockIdx.y << 32) | bad);
-        }
+        report_bad_row(status, blockIdx.y, bad);
         return;
     }
     if (!cnt) return;
@@ -115,14 +105,6 @@ __global__ __launch_bounds__(COL_THREADS) void k_columns(const uint32_t* __restr
     }
 }
 
-// the canonical value of one cell, read back for an error message
-const char* read_cell(zkh_ctx* ctx, const zkh_buf* code, const zkh_buf* data, uint32_t g, uint32_t c, size_t n, uint32_t row, long long* v) {
-    uint32_t w;
-    ZKH_TRY(zkh_read(ctx, g == GROUP_CODE ? code : data, &w, (size_t)c * n + row, 1));
-    *v = fp_decode(Fp::raw(w % P));
-    return nullptr;
-}
-
 }  // namespace
 
 extern "C" const char* zkh_derive_columns(zkh_ctx* ctx, const zkh_circuit* c, size_t po2, size_t zk_cycles, const zkh_buf* code, zkh_buf* data) {
@@ -136,24 +118,22 @@ extern "C" const char* zkh_derive_columns(zkh_ctx* ctx, const zkh_circuit* c, si
     ZKH_REQUIRE(recs.size() <= 65535, "derive_columns: %zu records in one blob (at most 65535)", recs.size());
     bind_thread(ctx);
     static_assert(sizeof(Record) % 4 == 0, "word records");
-    Tmp drecs, status;
+    Tmp drecs;
+    BadRow bad;
     ZKH_TRY(zkh_copy_from(ctx, "column_records", (const uint32_t*)recs.data(), recs.size() * (sizeof(Record) / 4), drecs.out()));
-    ZKH_TRY(new_buf(ctx, 2, false, status.out()));
-    ZKH_HIP(hipMemsetAsync(status->ptr(), 0xff, 8, ctx->stream));
+    ZKH_TRY(bad.init(ctx));
     double src_words = 0, dst_words = 0;                 // per row: the sources of every record, its destinations
     for (const Record& r : recs) { src_words += r.n_src; dst_words += r.n_dst; }
     const dim3 grid((unsigned)((A + COL_THREADS * COL_ROWS - 1) / (COL_THREADS * COL_ROWS)), (unsigned)recs.size());
     const Record* d_recs = (const Record*)drecs->ptr();
-    unsigned long long* d_status = (unsigned long long*)status->ptr();
     {
         ProfScope prof(ctx, "columns_check", 4.0 * src_words * A);
-        k_columns<false><<<grid, COL_THREADS, 0, ctx->stream>>>(code->ptr(), data->ptr(), d_recs, (uint32_t)n, A, d_status);
+        k_columns<false><<<grid, COL_THREADS, 0, ctx->stream>>>(code->ptr(), data->ptr(), d_recs, (uint32_t)n, A, bad.ptr());
         ZKH_TRY(last_launch_error("columns_check"));
     }
-    uint32_t st[2];
-    ZKH_TRY(zkh_read(ctx, status, st, 0, 2));
-    if ((((unsigned long long)st[1] << 32) | st[0]) != NO_ROW) {
-        const uint32_t i = st[1], row = st[0];
+    ZKH_TRY(bad.read(ctx));
+    if (bad.found) {
+        const uint32_t i = bad.hi, row = bad.lo;
         const Record& r = recs[i];
         long long k[2] = {0, 0}, p[2] = {0, 0};
         for (uint32_t s = 0; s < r.n_src; s++) {
@@ -168,7 +148,7 @@ extern "C" const char* zkh_derive_columns(zkh_ctx* ctx, const zkh_circuit* c, si
     }
     {
         ProfScope prof(ctx, "columns_write", 4.0 * (src_words + dst_words) * A);
-        k_columns<true><<<grid, COL_THREADS, 0, ctx->stream>>>(code->ptr(), data->ptr(), d_recs, (uint32_t)n, A, d_status);
+        k_columns<true><<<grid, COL_THREADS, 0, ctx->stream>>>(code->ptr(), data->ptr(), d_recs, (uint32_t)n, A, bad.ptr());
         ZKH_TRY(last_launch_error("columns_write"));
     }
     return nullptr;

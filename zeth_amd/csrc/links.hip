@@ -26,9 +26,6 @@ using namespace zkh;
 namespace {
 
 constexpr uint32_t LINK_THREADS = 256;
-constexpr unsigned long long NO_ROW = ~0ull;
-
-__device__ __forceinline__ uint32_t canonical(uint32_t raw) { return fp_decode(Fp::raw(raw % P)); }
 
 // grid (ceil(A / LINK_THREADS), records).  kWrite = false: the check pass (bad = the lowest bad record << 32 | row, the record by its place
 // among the LINK records); kWrite = true: the write pass over a witness that passed.  The record's words are read through the uniform
@@ -62,6 +59,7 @@ __global__ __launch_bounds__(LINK_THREADS) void k_links(const uint32_t* __restri
     const uint32_t L = rec->L, nl = rec->nl;
     if (!kWrite) {
         uint32_t mine = linked && (d < 0 || (d >> (L * nl)) != 0) ? row : NONE;
+        // report_bad_row (arguments.h) written out: through the helper this kernel's argument loads are scheduled otherwise
         if (__ballot(mine != NONE) != 0) {                // wave-uniform: only a wave that found one reduces and writes
 #pragma unroll
             for (int off = 32; off > 0; off >>= 1) {
@@ -108,33 +106,31 @@ extern "C" const char* zkh_derive_links(zkh_ctx* ctx, const zkh_circuit* c, size
     ZKH_TRY(sort_rows(ctx, code, data, n, A, pairs, &sorted));
     if (sorted.bad_selector) {
         const Link& r = links[sorted.bad_pair];
-        uint32_t w;
-        ZKH_TRY(zkh_read(ctx, code, &w, (size_t)r.sel * n + sorted.bad_row, 1));
-        return make_err("derive_links: record %u at row %u: selector %u, not 0 or 1: the witness is refused", r.index, sorted.bad_row, fp_decode(Fp::raw(w % P)));
+        uint32_t sel;
+        ZKH_TRY(read_cell(ctx, code, data, GROUP_CODE, r.sel, n, sorted.bad_row, &sel));
+        return make_err("derive_links: record %u at row %u: selector %u, not 0 or 1: the witness is refused", r.index, sorted.bad_row, sel);
     }
     ZKH_REQUIRE(!sorted.wide, "derive_links: a packed key of more than 64 bits from one 31-bit field");
     static_assert(sizeof(Link) % 4 == 0, "word records");
-    Tmp drecs, status;
+    Tmp drecs;
+    BadRow bad;
     ZKH_TRY(zkh_copy_from(ctx, "link_records", (const uint32_t*)links.data(), links.size() * (sizeof(Link) / 4), drecs.out()));
-    ZKH_TRY(new_buf(ctx, 2, false, status.out()));
-    ZKH_HIP(hipMemsetAsync(status->ptr(), 0xff, 8, ctx->stream));
+    ZKH_TRY(bad.init(ctx));
     double carried = 0, dsts = 0;
     for (const Link& r : links) { carried += r.nc; dsts += r.n_dst; }
     const dim3 grid((unsigned)((A + LINK_THREADS - 1) / LINK_THREADS), nr);
     const Link* d_recs = (const Link*)drecs->ptr();
-    unsigned long long* d_bad = (unsigned long long*)status->ptr();
     {
         ProfScope prof(ctx, "links_check", 20.0 * nr * A);                   // key and row of every item; the clock at both rows
         k_links<false><<<grid, LINK_THREADS, 0, ctx->stream>>>(code->ptr(), data->ptr(), d_recs, sorted.status->ptr(), sorted.keys(), sorted.rows(),
-                                                             (uint32_t)n, A, d_bad);
+                                                             (uint32_t)n, A, bad.ptr());
         ZKH_TRY(last_launch_error("links_check"));
     }
-    uint32_t st[2];
-    ZKH_TRY(zkh_read(ctx, status, st, 0, 2));
-    if ((((unsigned long long)st[1] << 32) | st[0]) != NO_ROW) {
+    ZKH_TRY(bad.read(ctx));
+    if (bad.found) {
         // the refused access and its previous one, found on the host as the reference finds them: the key and the selector of rows [0, row]
-        const Link& r = links[st[1]];
-        const uint32_t row = st[0];
+        const Link& r = links[bad.hi];
+        const uint32_t row = bad.lo;
         std::vector<uint32_t> key(row + 1), sel(row + 1, R1);
         ZKH_TRY(zkh_read(ctx, r.kg == GROUP_CODE ? code : data, key.data(), (size_t)r.kc * n, row + 1));
         if (r.sel != NONE) ZKH_TRY(zkh_read(ctx, code, sel.data(), (size_t)r.sel * n, row + 1));
@@ -142,11 +138,10 @@ extern "C" const char* zkh_derive_links(zkh_ctx* ctx, const zkh_circuit* c, size
         for (uint32_t q = row; q-- > 0;)
             if (sel[q] % P == R1 && key[q] % P == key[row] % P) { prow = q; break; }
         ZKH_REQUIRE(prow != row, "derive_links: record %u at row %u was refused, but no earlier access has its key", r.index, row);
-        uint32_t w[2];
-        const zkh_buf* cb = r.cg[0] == GROUP_CODE ? code : data;
-        ZKH_TRY(zkh_read(ctx, cb, &w[0], (size_t)r.cc[0] * n + row, 1));
-        ZKH_TRY(zkh_read(ctx, cb, &w[1], (size_t)r.cc[0] * n + prow, 1));
-        const long long now = fp_decode(Fp::raw(w[0] % P)), before = fp_decode(Fp::raw(w[1] % P)), d = now - before - 1;
+        long long now, before;
+        ZKH_TRY(read_cell(ctx, code, data, r.cg[0], r.cc[0], n, row, &now));
+        ZKH_TRY(read_cell(ctx, code, data, r.cg[0], r.cc[0], n, prow, &before));
+        const long long d = now - before - 1;
         if (d < 0)
             return make_err("derive_links: record %u at row %u: clock not increasing (%lld after %lld at row %u): the witness is refused", r.index, row, now, before, prow);
         return make_err("derive_links: record %u at row %u: the clock difference %lld (after row %u) does not fit %u limbs of %u bits: the witness is refused",
@@ -155,7 +150,7 @@ extern "C" const char* zkh_derive_links(zkh_ctx* ctx, const zkh_circuit* c, size
     {
         ProfScope prof(ctx, "links_write", (20.0 * nr + 4.0 * carried + 4.0 * dsts) * A);
         k_links<true><<<grid, LINK_THREADS, 0, ctx->stream>>>(code->ptr(), data->ptr(), d_recs, sorted.status->ptr(), sorted.keys(), sorted.rows(),
-                                                            (uint32_t)n, A, d_bad);
+                                                            (uint32_t)n, A, bad.ptr());
         ZKH_TRY(last_launch_error("links_write"));
     }
     // the temporaries go back to the pool on return: the stream orders their next use after these launches

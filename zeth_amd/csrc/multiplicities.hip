@@ -218,10 +218,10 @@ extern "C" const char* zkh_derive_multiplicities(zkh_ctx* ctx, const zkh_circuit
     };
     uint32_t term, row;
     if (entry_of(st[2], st[3], &term, &row)) {
-        uint32_t w;
-        ZKH_TRY(zkh_read(ctx, code, &w, (size_t)a[term].sel * n + row, 1));
+        uint32_t sel;
+        ZKH_TRY(read_cell(ctx, code, data, GROUP_CODE, a[term].sel, n, row, &sel));
         return make_err("derive_multiplicities: table term %u (tag %u) has selector %u at row %u, not 0 or 1: the witness is refused", term,
-                        a[term].tag, fp_decode(Fp::raw(w % P)), row);
+                        a[term].tag, sel, row);
     }
     const uint32_t U = st[4];
     ZKH_TRY(new_buf(ctx, 2 * (size_t)std::max<uint32_t>(U, 1), true, cnt.out()));
@@ -244,10 +244,7 @@ extern "C" const char* zkh_derive_multiplicities(zkh_ctx* ctx, const zkh_circuit
     if (entry_of(st[0], st[1], &term, &row)) {
         const Term& t = a[term];
         uint32_t v[MAX_TUPLE] = {0, 0, 0, 0};
-        for (uint32_t e = 0; e < t.w; e++) {
-            ZKH_TRY(zkh_read(ctx, t.tg[e] == GROUP_CODE ? code : data, v + e, (size_t)t.tc[e] * n + row, 1));
-            v[e] = fp_decode(Fp::raw(v[e] % P));
-        }
+        for (uint32_t e = 0; e < t.w; e++) ZKH_TRY(read_cell(ctx, code, data, t.tg[e], t.tc[e], n, row, v + e));
         return make_err("derive_multiplicities: lookup term %u (tag %u) at row %u has no table entry: key (%u, %u, %u, %u): the witness is "
                         "refused", term, t.tag, row, v[0], v[1], v[2], v[3]);
     }

@@ -384,10 +384,10 @@ extern "C" const char* zkh_derive_sorted(zkh_ctx* ctx, const zkh_circuit* c, siz
     if (sorted.bad_selector) {
         const SortPair& q = pairs[sorted.bad_pair];
         const uint32_t row = sorted.bad_row;
-        uint32_t w;
-        ZKH_TRY(zkh_read(ctx, code, &w, (size_t)q.sel * n + row, 1));
+        uint32_t sel;
+        ZKH_TRY(read_cell(ctx, code, data, GROUP_CODE, q.sel, n, row, &sel));
         return make_err("derive_sorted: sorted-copy term %u (tag %u) has selector %u at row %u, not 0 or 1: the witness is refused", q.d_term,
-                        a[q.d_term].tag, fp_decode(Fp::raw(w % P)), row);
+                        a[q.d_term].tag, sel, row);
     }
     double tuple_words = 0;
     for (const SortPair& q : pairs) tuple_words += q.w;
