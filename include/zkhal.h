@@ -284,8 +284,19 @@ const char* zkh_derive_columns(zkh_ctx*, const zkh_circuit*, size_t po2, size_t 
  * over all records before any clock), when d < 0 ("clock not increasing") or when d >= 2^(L nl); the error names the lowest (record,
  * row) and the values.  Call it AFTER zkh_derive_columns and BEFORE zkh_derive_multiplicities (the limbs are lookups to be counted).
  * Like its siblings it is an error on a circuit without LINK records.  Sessions with caller traces and
- * SegmentProver.seal_host_witness call the four in the order sorted, columns, links, multiplicities. */
+ * SegmentProver.seal_host_witness call the four in the order sorted, columns, links, multiplicities.
+ * The read rule (ZKA1 version 6; versions 1..5 are word for word what they were): LINK word 5 is a flag word, bit 0 = READS, every other
+ * bit refused; with READS words 14, 15 are the (group, column) of the write flag w, a source of the record like the key and the carried
+ * columns, and nc >= 2; without READS they are 0.  Header word 7 = the number of LINK records with READS: a version-6 blob in which it
+ * is 0 is no ZKA1 blob, and one in which it is not that number is refused.  A record with READS states that a load returns the last
+ * store: on every access r, x(w, r) must be 0 or 1; a store (1) is free; a load (0) needs, for every carried column j = 1 .. nc - 1 (the
+ * clock c_0 is exempt), x(c_j, r) = x(c_j, r') when r is linked and x(c_j, r) = 0 when it is not (memory starts zeroed), compared as
+ * residues mod P.  The rule adds no destination.  zkh_derive_links FAILS and leaves `data` unchanged on the lowest (record, row) over
+ * clock and read-rule refusals together; on one row it names the write flag first, then the clock, then the read rule, lowest j first,
+ * with the value read and the value last stored and its row.  Records without READS behave as in version 5.
+ * zkh_circuit_links_check_reads: the number of LINK records with READS (0: none, or no arguments). */
 int zkh_circuit_derives_links(const zkh_circuit*);
+int zkh_circuit_links_check_reads(const zkh_circuit*);
 const char* zkh_derive_links(zkh_ctx*, const zkh_circuit*, size_t po2, size_t zk_cycles, const zkh_buf* code, zkh_buf* data);
 /* The data columns that zkh_derive_sorted, zkh_derive_columns, zkh_derive_links and zkh_derive_multiplicities write on the active rows: their sorted
  * union in cols[0 .. *n) (cap = room in cols; *n is set even when the call fails for lack of room).

@@ -363,6 +363,12 @@ impl HipCircuitHal {
         unsafe { sys::zkh_circuit_derives_links(self.circuit) != 0 }
     }
 
+    /// The LINK records with READS (a ZKA1 version-6 blob): `derive_links` then refuses a load that does not return the last store, or
+    /// 0 from an address never accessed, as well.
+    pub fn links_check_reads(&self) -> usize {
+        unsafe { sys::zkh_circuit_links_check_reads(self.circuit) as usize }
+    }
+
     /// Fill the destination columns of the LINK records of `data` on the active rows (`zkh_derive_links`): every memory access gets
     /// the previous access to its own address (linked, last, the carried values, the limbs of the clock difference).  Call it after
     /// `derive_columns`, before `derive_multiplicities` (the limbs are lookups to be counted) and before `prove_begin`.  Panics on a

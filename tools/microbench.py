@@ -3,7 +3,8 @@
 arguments and its share of that circuit's seal; M11 / M11w: derived lookup multiplicities of SYN-LOOKUP-derived / WIDE; M12: derived sorted copies of SYN-LOOKUP-sorted
 against the host's lexsort + upload; M13: derived columns — the 64 limb columns of SYN-LOOKUP FULL — next to a plain copy of the same
 bytes, and the host-witness seal with its upload; M14: linked accesses of SYN-LOOKUP-linked (zkh_derive_links) next to a plain copy of
-the same bytes, to the host's sort + gather + upload, and the host-witness seal with the derive against the host-made columns) on one MI355X, through the C ABI (HipHal).
+the same bytes, to the host's sort + gather + upload, and the host-witness seal with the derive against the host-made columns; M14r: the read rule, zkh_derive_links on SYN-LOOKUP-reads
+under its version-6 blob next to the same trace under the version-5 blob) on one MI355X, through the C ABI (HipHal).
 
 Each line of output is one JSON object: the op, its shape, the average wall time of one call (stream drained on both
 sides of `reps` back-to-back calls), its ALGORITHMIC bytes (SURVEY.md §8a "B_alg": inputs read once + outputs written
@@ -431,6 +432,47 @@ def main() -> None:
         print(json.dumps({"bench": "M14links", "derive_links_ms": round(dt * 1e3, 4), "steps_ms": steps, "sort_share": round(sort_ms / max(sum(steps.values()), 1e-9), 3),
                           "copy_ms": round(dt_copy * 1e3, 4), "vs_copy": round(dt_copy / dt, 3), "host_reference_links_ms": round(dt_host * 1e3, 2),
                           "host_upload_ms": round(dt_up * 1e3, 3), "host_witness_seal": seals}), flush=True)
+    if want("M14r"):
+        # the read rule (zkh_derive_links on SYN-LOOKUP-reads FULL, a ZKA1 version-6 blob) next to the same trace under the version-5 blob
+        # of the same arguments (the LINK record without READS): the rule adds a flag read and up to two value reads per access to the
+        # check pass, and nothing else; the check pass's share by its events
+        from dataclasses import replace
+        from zeth_amd.circuits import logup, syn_lookup
+        zk = 1994
+        A = n - zk
+        shape = syn_lookup.FULL
+        desc, blob = syn_lookup.build_syn_lookup(shape, link=True, reads=True)
+        rargs = logup.Arguments.parse(blob)
+        blob5 = logup.Arguments(rargs.k, rargs.alpha, rargs.beta, rargs.terms, [replace(r, write=None) for r in rargs.records]).blob()
+        assert int(blob[1]) == 6 and int(blob5[1]) == 5
+        code_h, full_h, _out = syn_lookup.witness(shape, args.po2, zk, seed=14, link=True, reads=True)
+        res = {}
+        for name, b in (("v6_reads", blob), ("v5", blob5)):
+            circuit = hal.load_circuit(desc, jit=False)
+            circuit.set_arguments(b)
+            assert circuit.links_check_reads() == (1 if name == "v6_reads" else 0)
+            bare_h = full_h.reshape(-1, n).copy()
+            bare_h[circuit.derived_data_columns(), :A] = 0
+            code, data = hal.alloc_elem("code", code_h.size), hal.alloc_elem("data", bare_h.size)
+            code.write(code_h)
+            data.write(bare_h.reshape(-1))
+            derive = lambda: hal.derive_links(circuit, args.po2, zk, code, data)
+            dt = timed(hal, derive, args.reps)
+            assert np.array_equal(data.to_vec(), full_h)
+            hal.prof_enable(True)
+            hal.prof_reset()
+            for _ in range(args.reps):
+                derive()
+            hal.sync()
+            steps = {r["name"]: round(r["total_ms"] / max(r["calls"], 1), 4) for r in hal.prof_get()
+                     if r["calls"] and r["name"].startswith(("sort_", "links_"))}
+            hal.prof_enable(False)
+            res[name] = {"derive_links_ms": round(dt * 1e3, 4), "steps_ms": steps,
+                         "check_share": round(steps.get("links_check", 0) / max(sum(steps.values()), 1e-9), 3)}
+            del code, data
+        print(json.dumps({"bench": "M14reads", **res, "reads_vs_v5": round(res["v6_reads"]["derive_links_ms"] / res["v5"]["derive_links_ms"], 3),
+                          "check_vs_v5": round(res["v6_reads"]["steps_ms"].get("links_check", 0) / max(res["v5"]["steps_ms"].get("links_check", 0), 1e-9), 3)}),
+              flush=True)
     hal.close()
 
 

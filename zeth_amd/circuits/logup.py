@@ -24,8 +24,9 @@ The degree of a column's constraint is 1 (gate) + max(1 + t, max_i(deg sel_i + d
 
 ZKA1 layout (u32 words; canonical integers, not Montgomery words)::
 
-    [0] magic 'ZKA1' = 0x5a4b4131   [1] version = 1 .. 4      [2] k = accum Fp4 columns   [3] alpha mix word offset
-    [4] beta mix word offset       [5] n_terms       [6] reserved = 0 (version 4: n_records)   [7] reserved = 0
+    [0] magic 'ZKA1' = 0x5a4b4131   [1] version = 1 .. 6      [2] k = accum Fp4 columns   [3] alpha mix word offset
+    [4] beta mix word offset       [5] n_terms       [6] reserved = 0 (version 4: n_records)
+    [7] reserved = 0 (version 6: the number of LINK records with READS, at least 1)
     terms: n_terms x 16 words, sorted by column:
       col, neg (0: +1, 1: -1), sel (code column or NONE), m_group (NONE = constant 1, else GROUP_CODE / GROUP_DATA), m_col,
       tag, w, flags, then w (group, column) pairs of the tuple, unused pairs 0
@@ -46,6 +47,10 @@ ZKA1 layout (u32 words; canonical integers, not Montgomery words)::
       [8 + 2j], [9 + 2j] the (group, column) of carried column c_j, j < 3 (unused pairs 0)   [14], [15] reserved = 0
       [16 ..] the 2 + nc + nl destination data columns: linked, last, prev_0 .. prev_{nc-1}, limb_0 .. limb_{nl-1}; the words after
       them up to [31] reserved = 0.  The builder writes version 5 only when a LINK record exists.
+    Version 6: as version 5, and a LINK record may carry the READ RULE.  LINK word [5] is a flag word: bit 0 = READS, every other bit
+    is refused; with READS words [14], [15] are the (group, column) of the WRITE FLAG w, without it they are 0.  READS needs nc >= 2 (a
+    clock and a value column).  Header word 7 = the number of LINK records with READS; a version-6 blob in which it is 0 is no ZKA1
+    blob, and one in which it is not that number is refused.  The builder writes version 6 only when a LINK record has READS.
 
 A derived term is the table side of a lookup (`check_derived`): sign -1, its multiplicity a data column that no tuple and no other
 term names, and every other term of its tag a lookup of sign +1.  Its multiplicity column is then a function of the traces:
@@ -70,6 +75,14 @@ same K (`reference_links`): linked[r] = [r' exists], last[r] = [no access above 
 word of carried column c_j at r' (0 when r is not linked); limb_j[r] = limb j of d = x(c_0, r) - x(c_0, r') - 1, c_0 being the clock
 (0 when not linked), refused when d < 0 ("clock not increasing") or d >= 2^(L nl).  Active rows that are no access get zeros in every
 destination.  Selectors are checked, over all records, before any clock.  L nl <= 29 for the reason `order_constraints` gives.
+
+THE READ RULE (a LINK record with READS, ZKA1 version 6): a load returns the last store.  The write flag w is a source of the record,
+a code or data column of the host's like the others.  On every access r: w(r) = x(w, r) must be 0 or 1, anything else is refused.  A
+store (w = 1) is free.  A load (w = 0) must have, for every carried column j = 1 .. nc - 1 (the clock c_0 is exempt),
+x(c_j, r) = x(c_j, r') when r is linked and x(c_j, r) = 0 when it is not: memory starts zeroed.  Values are compared as residues
+mod P (a raw word P is a zero).  The rule adds no destination.  On one row the write flag is looked at first, then the clock, then
+the read rule, lowest j first; the lowest (record, row) over all of these refusals is the one named.  Records without READS are
+what they were.
 
 WHO WRITES A DATA COLUMN (`_check_owned` behind `check_columns` and `check_links`; csrc/arguments.h says the same).  A data column
 has at most one writer, and a derive reads only what the stages before it have finished writing.  The writers: a sorted copy (its
@@ -267,6 +280,9 @@ class Link:
     dsts: Tuple[int, ...]                      # data columns: linked, last, prev_0 .. prev_{nc-1}, limb_0 .. limb_{nl-1}
     reserved: bool = False                     # a word the format reserves was not 0 (parser only)
     nc_word: Optional[int] = None              # the blob's nc where it is not len(carried) (parser only: an nc out of range)
+    write: Optional[Tuple[int, int]] = None    # READS (version 6): the (group, column) of the write flag; None = no read rule
+    flag_word: Optional[int] = None            # the blob's word 5 where it sets a bit other than READS (parser only)
+    stray_write: bool = False                  # words 14, 15 are not 0 although READS is not set (parser only, version 6)
     kind = KIND_LINK
 
     @property
@@ -275,7 +291,7 @@ class Link:
 
     @property
     def srcs(self) -> Tuple[Tuple[int, int], ...]:
-        return (self.key,) + self.carried
+        return (self.key,) + self.carried + (() if self.write is None else (self.write,))
 
     @property
     def linked(self) -> int:
@@ -297,10 +313,11 @@ class Link:
         return 2 + len(self.carried) + self.nl
 
     def words(self) -> List[int]:
-        w = [KIND_LINK, self.limb_bits, self.nl, len(self.carried), NONE if self.sel is None else self.sel, 0, self.key[0], self.key[1]]
+        w = [KIND_LINK, self.limb_bits, self.nl, len(self.carried), NONE if self.sel is None else self.sel, int(self.write is not None),
+             self.key[0], self.key[1]]
         for g, c in self.carried:
             w += [g, c]
-        w += [0] * (16 - len(w))
+        w += [0] * (14 - len(w)) + list(self.write or (0, 0))
         w += list(self.dsts)
         return w + [0] * (LINK_WORDS - len(w))
 
@@ -309,6 +326,12 @@ def _links_clause_a(i: int, r: Link, group_sizes) -> Optional[str]:
     if not (1 <= r.nc <= MAX_CARRIED and 1 <= r.limb_bits <= 16 and 0 <= r.nl <= MAX_LINK_LIMBS and r.limb_bits * r.nl <= MAX_ORDER_BITS):
         return (f"record {i}: a LINK of {r.nc} carried columns and {r.nl} limbs of {r.limb_bits} bits (1..{MAX_CARRIED} carried columns, "
                 f"0..{MAX_LINK_LIMBS} limbs of 1..16 bits, at most {MAX_ORDER_BITS} bits in all)")
+    if r.flag_word is not None:
+        return f"record {i}: word 5 of a LINK is {r.flag_word:#x} (bit 0: READS, the read rule; the other bits are reserved)"
+    if r.stray_write:
+        return f"record {i}: words 14, 15 of a LINK name a write flag, but bit 0 of word 5 (READS) is not set"
+    if r.write is not None and r.nc < 2:
+        return f"record {i}: READS needs a clock and a value column (2..{MAX_CARRIED} carried columns), this LINK carries {r.nc}"
     if r.reserved or len(r.dsts) != r.n_dsts():
         return f"record {i}: a reserved word of a LINK is not 0 (words 5, 14, 15, the unused carried pairs and the unused destination words)"
     if r.sel is not None and (r.sel >= NONE or (group_sizes is not None and not 0 <= r.sel < group_sizes[GROUP_CODE])):
@@ -318,7 +341,8 @@ def _links_clause_a(i: int, r: Link, group_sizes) -> Optional[str]:
 
 def check_links(terms: Sequence[Term], records: Sequence, group_sizes=None) -> Optional[str]:
     """the first LINK record that breaks a rule, named by its index among all `records` (all of them are its peers), or None: (a) the
-    ranges of nc, L, nl, the reserved words and the selector a code column, then (b) .. (e) of `_check_owned`"""
+    ranges of nc, L, nl, the flag word and the write flag's words (version 6), the reserved words and the selector a code column, then
+    (b) .. (e) of `_check_owned`; the write flag of a READS record is one of its sources"""
     return _check_owned(terms, records, True, _links_clause_a, group_sizes)
 
 
@@ -423,7 +447,14 @@ class Arguments:
     records: List[Record] = field(default_factory=list)
 
     @property
+    def reads(self) -> int:
+        """the LINK records with READS (header word 7 of version 6)"""
+        return sum(isinstance(r, Link) and r.write is not None for r in self.records)
+
+    @property
     def version(self) -> int:
+        if self.reads:
+            return 6
         if any(isinstance(r, Link) for r in self.records):
             return 5
         if self.records:
@@ -433,7 +464,7 @@ class Arguments:
         return 2 if any(t.derive for t in self.terms) else 1
 
     def blob(self) -> np.ndarray:
-        words = [ARGS_MAGIC, self.version, self.k, self.alpha, self.beta, len(self.terms), len(self.records), 0]
+        words = [ARGS_MAGIC, self.version, self.k, self.alpha, self.beta, len(self.terms), len(self.records), self.reads]
         for t in _by_column(self.terms):
             rec = [t.col, 0 if t.sign == 1 else 1, NONE if t.sel is None else t.sel,
                    NONE if t.mult is None else t.mult[0], 0 if t.mult is None else t.mult[1], t.tag % P, len(t.tuple_cols), t.flags()]
@@ -448,7 +479,7 @@ class Arguments:
     @staticmethod
     def parse(blob: Sequence[int]) -> "Arguments":
         d = [int(x) for x in np.asarray(blob, dtype=np.uint32)]
-        if len(d) < ARGS_HEADER or d[0] != ARGS_MAGIC or d[1] not in (1, 2, 3, 4, 5):
+        if len(d) < ARGS_HEADER or d[0] != ARGS_MAGIC or d[1] not in (1, 2, 3, 4, 5, 6) or (d[1] == 6 and d[7] == 0):
             raise ValueError("not a ZKA1 argument blob")
         version = d[1]
         k, alpha, beta, n = d[2], d[3], d[4], d[5]
@@ -488,15 +519,22 @@ class Arguments:
             if sizes[i] == LINK_WORDS:
                 nc = min(r[3], MAX_CARRIED)
                 n_dst = min(16, 2 + nc + min(r[2], 16))
-                reserved = bool(r[5] or r[14] or r[15] or any(r[8 + 2 * nc:14]) or any(r[16 + n_dst:]))
+                reserved = bool(any(r[8 + 2 * nc:14]) or any(r[16 + n_dst:]))
+                reads = version >= 6 and r[5] & 1 == 1                     # version 5 reserves words 5, 14, 15; version 6 reads them
+                if version < 6:
+                    reserved = reserved or bool(r[5] or r[14] or r[15])
                 records.append(Link(None if r[4] == NONE else r[4], (r[6], r[7]), tuple((r[8 + 2 * j], r[9 + 2 * j]) for j in range(nc)), r[1], r[2],
-                                    tuple(r[16: 16 + n_dst]), reserved, None if r[3] == nc else r[3]))
+                                    tuple(r[16: 16 + n_dst]), reserved, None if r[3] == nc else r[3], (r[14], r[15]) if reads else None,
+                                    r[5] if version >= 6 and r[5] > 1 else None, bool(version >= 6 and not reads and (r[14] or r[15]))))
                 continue
             n_src = r[3]
             n_dst = min(8, r[2] + (r[0] == KIND_ORDER and n_src == 2))
             reserved = any(r[4 + 2 * min(n_src, 2):8]) or any(r[8 + n_dst:])
             records.append(Record(r[0], r[1], r[2], tuple((r[4 + 2 * j], r[5 + 2 * j]) for j in range(min(n_src, 2))), tuple(r[8: 8 + n_dst]),
                                   reserved, None if n_src <= 2 else n_src))
+        n_reads = sum(isinstance(r, Link) and r.write is not None for r in records)
+        if version >= 6 and d[7] != n_reads:
+            raise ValueError(f"ZKA1: header word 7 is {d[7]}, the blob has {n_reads} LINK records with READS")
         problem = check_sorted(terms) or check_derived(terms) or _check_records(terms, records)
         if problem:
             raise ValueError(f"ZKA1: {problem}")
@@ -587,18 +625,25 @@ class LogupBuilder(CircuitBuilder):
         keys = tuple((int(g), int(c)) for g, c in keys)
         return self._record(Record(KIND_ORDER, int(limb_bits), len(dsts) - (len(keys) == 2), keys, tuple(int(c) for c in dsts)))
 
-    def derive_links(self, sel: Optional[int], key: Tuple[int, int], carried: Sequence[Tuple[int, int]], dsts: Sequence[int], limb_bits: int) -> Link:
+    def derive_links(self, sel: Optional[int], key: Tuple[int, int], carried: Sequence[Tuple[int, int]], dsts: Sequence[int], limb_bits: int,
+                     write: Optional[Tuple[int, int]] = None) -> Link:
         """the library fills the data columns `dsts` (zkh_derive_links) = linked, last, one prev per carried column, then the limbs of
         the clock difference, for the accesses (selector code column `sel`, None = every active row) to the address `key`; `carried`
-        are the (group, column) pairs whose value at the previous access is copied, carried[0] the clock (`reference_links`)"""
+        are the (group, column) pairs whose value at the previous access is copied, carried[0] the clock (`reference_links`).
+        write: the (group, column) of the write flag; the record then has READS (ZKA1 version 6) and a load that does not return the
+        last store, or 0 from an address never accessed, refuses the witness (the module docstring's read rule)"""
         carried = tuple((int(g), int(c)) for g, c in carried)
         return self._record(Link(None if sel is None else int(sel), (int(key[0]), int(key[1])), carried, int(limb_bits),
-                                 len(dsts) - 2 - len(carried), tuple(int(c) for c in dsts)))
+                                 len(dsts) - 2 - len(carried), tuple(int(c) for c in dsts),
+                                 write=None if write is None else (int(write[0]), int(write[1]))))
 
     def link_constraints(self, inner, record: Link):
         """and onto `inner` (which the caller gates by its body selector) the constraints that tie the LINK `record`'s witness to its
         row: linked (1 - linked) = 0, last (1 - last) = 0 and sum_j 2^(jL) limb_j = linked (c_0 - prev_0 - 1).  Degree 3 with the caller's
-        gate.  Sound for clocks below 2^29 and limbs range-checked by a lookup, as `order_constraints` is: L nl <= 29."""
+        gate.  Sound for clocks below 2^29 and limbs range-checked by a lookup, as `order_constraints` is: L nl <= 29.
+        A record with READS adds the read rule: w (1 - w) = 0 and, per value column j >= 1, (1 - w) (c_j - linked prev_j) = 0: a load
+        returns what the previous access left, or 0.  linked prev_j and not prev_j alone, so that nothing rests on the host having
+        zeroed prev_j on an unlinked row.  Degree 4 with the gate."""
         if not isinstance(record, Link):
             raise ValueError("link_constraints: not a LINK record")
         L, nl = record.limb_bits, record.nl
@@ -613,7 +658,13 @@ class LogupBuilder(CircuitBuilder):
             v = self.get(GROUP_DATA, c) if j == 0 else self.mul(self.const(1 << (j * L)), self.get(GROUP_DATA, c))
             total = v if j == 0 else self.add(total, v)
         d = self.sub(self.sub(self.get(*record.carried[0]), self.get(GROUP_DATA, record.prevs[0])), one)
-        return self.and_eqz(inner, self.sub(total, self.mul(linked, d)))
+        inner = self.and_eqz(inner, self.sub(total, self.mul(linked, d)))
+        if record.write is not None:
+            load = self.sub(one, self.get(*record.write))
+            inner = self.and_eqz(inner, self.mul(self.get(*record.write), load))
+            for src, prev in zip(record.carried[1:], record.prevs[1:]):
+                inner = self.and_eqz(inner, self.mul(load, self.sub(self.get(*src), self.mul(linked, self.get(GROUP_DATA, prev)))))
+        return inner
 
     def order_constraints(self, inner, record: Record):
         """and onto `inner` (which the caller gates by its body selector) the constraints that the keys of the ORDER `record` are in
@@ -1009,7 +1060,8 @@ def reference_links(args: Arguments, po2: int, zk_cycles: int, code, data) -> np
     """The data trace zkh_derive_links leaves (raw Montgomery words, a copy): every LINK record's destination columns on the active rows
     (module docstring), rows [A, n) as given.  Raises ReferenceError on a selector other than 0 / 1 (the lowest (record, row) over all
     records, before any clock is looked at), then on the lowest (record, row) whose clock difference d = c_0 - prev_0 - 1 is negative
-    ("clock not increasing") or does not fit the limbs."""
+    ("clock not increasing") or does not fit the limbs or, in a record with READS, whose write flag is not 0 / 1 or whose load does
+    not return the last store (0 when its address was never accessed); on one row in this order: write flag, clock, read rule."""
     n = 1 << po2
     A = n - zk_cycles
     groups = {GROUP_CODE: np.asarray(code, dtype=np.uint32).reshape(-1, n), GROUP_DATA: np.array(data, dtype=np.uint32).reshape(-1, n)}
@@ -1032,8 +1084,20 @@ def reference_links(args: Arguments, po2: int, zk_cycles: int, code, data) -> np
         clock, pclock = _dec(groups[g0][c0, rows]).astype(np.int64), _dec(groups[g0][c0, prow]).astype(np.int64)
         d = np.where(linked, clock - pclock - 1, 0)
         bad = (d < 0) | (d >> (L * nl) != 0)
+        if r.write is not None:
+            w = _dec(groups[r.write[0]][r.write[1], rows])
+            now = [_dec(groups[g][c, rows]) for g, c in r.carried]
+            before = [np.where(linked, _dec(groups[g][c, prow]), 0) for g, c in r.carried]
+            misread = [(w == 0) & (now[e] != before[e]) for e in range(1, len(r.carried))]
+            bad = bad | (w > 1) | np.logical_or.reduce(misread)
         if bad.any():
             j = int(np.argmax(bad))
+            if r.write is not None and w[j] > 1:
+                raise ReferenceError(f"record {i} at row {int(rows[j])}: write flag {int(w[j])}, not 0 or 1")
+            if r.write is not None and d[j] >= 0 and d[j] >> (L * nl) == 0:
+                e = next(e for e in range(1, len(r.carried)) if misread[e - 1][j])
+                raise ReferenceError(f"record {i} at row {int(rows[j])}: a load of carried column {e} returns {int(now[e][j])}, but " + (
+                    f"{int(before[e][j])} was last stored (row {int(prow[j])})" if linked[j] else "its address was never accessed: the value must be 0"))
             if d[j] < 0:
                 raise ReferenceError(f"record {i} at row {int(rows[j])}: clock not increasing ({int(clock[j])} after {int(pclock[j])} at row {int(prow[j])})")
             raise ReferenceError(f"record {i} at row {int(rows[j])}: the clock difference {int(d[j])} (after row {int(prow[j])}) does not fit {nl} limbs of {L} bits")

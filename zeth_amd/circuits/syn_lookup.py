@@ -35,8 +35,12 @@ previous access to its address — and -last (addr, val, time) pages the final a
 page-in.  The limbs of time - ptime - 1 are lookups of tag 0 and logup.link_constraints ties them to the row, so a link cannot point
 forward in time.  linked, last, pval, ptime and the limbs are a LINK record (ZKA1 version 5): the library fills them
 (zkh_derive_links; `witness(link=False)` leaves them zero).  Times are the row numbers, so differences stay below 2^(order_limbs L).
-What it leaves out: a write flag in the tuple and with it the read rule (a read returns pval), and an initial-memory table behind
-linked = 0.
+What it leaves out: the read rule (a load returns pval), and an initial-memory table behind linked = 0.
+SYN-LOOKUP-reads (`syn_lookup_reads`, `build_syn_lookup(shape, link=True, reads=True)`): SYN-LOOKUP-linked with the read rule.  Per
+memory pair one more data column, the write flag w (after every pair's link columns: `reads_layout`), the host's; the LINK record has
+READS (ZKA1 version 6), so zkh_derive_links refuses a load (w = 0) that does not return pval, or 0 where it is not linked, and
+logup.link_constraints adds w (1 - w) = 0 and (1 - w) (val - linked pval) = 0.  `witness(link=..., reads=True)` is a real load / store
+trace; `misread_row` forges one load so that the bus still balances.  Paging memory in and out through an image is still left out.
 Not a shipped circuit: its control root is zkh_code_root of its code trace.
 """
 from __future__ import annotations
@@ -95,16 +99,25 @@ def link_layout(n_words: int, n_limbs: int, n_mem: int, order_limbs: int = ORDER
     return [[base + (LINK_W + order_limbs) * i + e for e in range(LINK_W + order_limbs)] for i in range(n_mem)]
 
 
+def reads_layout(n_words: int, n_limbs: int, n_mem: int, order_limbs: int = ORDER_LIMBS):
+    """data column indices of SYN-LOOKUP-reads' write flags, one per memory pair, after `link_layout`'s columns"""
+    base = n_words + n_words * n_limbs + 1 + (LINK_W + order_limbs) * n_mem
+    return [base + i for i in range(n_mem)]
+
+
 def build_syn_lookup(shape: Shape = FULL, derive: bool = False, sort: bool = False,
                      sort_keys: Tuple[int, ...] = SORT_KEYS, limbs: bool = False, order: bool = False,
-                     order_limbs: int = ORDER_LIMBS, link: bool = False) -> Tuple[np.ndarray, np.ndarray]:
+                     order_limbs: int = ORDER_LIMBS, link: bool = False, reads: bool = False) -> Tuple[np.ndarray, np.ndarray]:
     """-> (ZKC1 description, ZKA1 argument blob); derive: the table term's multiplicity is derived by the library (version-2 blob,
     the description unchanged); sort: every permuted copy is the library's sorted copy of its memory tuple by the tuple positions
     `sort_keys` (version-3 blob, the description unchanged); limbs: every word's limbs are a LIMBS record (version-4 blob, the
     description unchanged); order: SYN-LOOKUP-ordered, another description (module docstring), its order columns an ORDER record over
     the copy's (addr, time); link: SYN-LOOKUP-linked, another description (module docstring), its link columns a LINK record (version-5
-    blob); it has no sorted copy, so it refuses `sort` and `order`"""
+    blob); it has no sorted copy, so it refuses `sort` and `order`; reads: SYN-LOOKUP-reads, SYN-LOOKUP-linked with a write flag per
+    memory pair and the read rule (version-6 blob, another description); it needs `link`"""
     n_words, n_limbs, limb_bits, n_mem = shape
+    if reads and not link:
+        raise ValueError("build_syn_lookup: reads=True is the read rule of the LINK records: it needs link=True")
     if link and (sort or order):
         raise ValueError("build_syn_lookup: link=True has no sorted copy: it does not combine with sort= / order=")
     words, limb_cols, m, mem, perm = layout(n_words, n_limbs, n_mem)
@@ -113,8 +126,9 @@ def build_syn_lookup(shape: Shape = FULL, derive: bool = False, sort: bool = Fal
     wd = m + 1 + 2 * MEM_W * n_mem + sum(len(c) for c in ocols)
     n_terms = n_words * n_limbs + 1 + 2 * n_mem + n_mem * order_limbs * bool(order)
     if link:
-        wd = m + 1 + sum(len(c) for c in lcols)
+        wd = m + 1 + sum(len(c) for c in lcols) + n_mem * bool(reads)
         n_terms = n_words * n_limbs + 1 + 3 * n_mem + n_mem * order_limbs
+    wcols = reads_layout(n_words, n_limbs, n_mem, order_limbs) if reads else [None] * n_mem
     k = (n_terms + 2) // 3
     b = LogupBuilder((4 * k, N_CODE, wd), (4, 8), alpha=0, beta=4)
     code = lambda c: b.get(GROUP_CODE, c)
@@ -142,8 +156,9 @@ def build_syn_lookup(shape: Shape = FULL, derive: bool = False, sort: bool = Fal
             b.derive_limbs((GROUP_DATA, words[kk]), limbs[kk], limb_bits)
     records = [b.derive_order([(GROUP_DATA, perm[i][0]), (GROUP_DATA, perm[i][2])], cols, limb_bits) for i, cols in enumerate(ocols)]
     # the clock (time) is carried first, then the value; the destinations in the LINK's order: linked, last, ptime, pval, the limbs
-    links = [b.derive_links(None, (GROUP_DATA, c[0]), [(GROUP_DATA, c[2]), (GROUP_DATA, c[1])], [c[3], c[4], c[6], c[5]] + c[LINK_W:], limb_bits)
-             for c in lcols]
+    links = [b.derive_links(None, (GROUP_DATA, c[0]), [(GROUP_DATA, c[2]), (GROUP_DATA, c[1])], [c[3], c[4], c[6], c[5]] + c[LINK_W:], limb_bits,
+                            write=None if w is None else (GROUP_DATA, w))
+             for c, w in zip(lcols, wcols)]
     # words = sum of their limbs, on active rows
     inner = b.true()
     for kk in range(n_words):
@@ -202,12 +217,21 @@ def syn_lookup_linked() -> Tuple[np.ndarray, np.ndarray]:
     return build_syn_lookup(FULL, link=True)
 
 
+def syn_lookup_tiny_reads() -> Tuple[np.ndarray, np.ndarray]:
+    return build_syn_lookup(TINY, link=True, reads=True)
+
+
+def syn_lookup_reads() -> Tuple[np.ndarray, np.ndarray]:
+    return build_syn_lookup(FULL, link=True, reads=True)
+
+
 def _enc(x) -> np.ndarray:
     return ((np.asarray(x, dtype=np.uint64) % np.uint64(P)) * np.uint64((1 << 32) % P) % np.uint64(P)).astype(np.uint32)
 
 
 def witness(shape: Shape, po2: int, zk_cycles: int, seed: int = 1, count: bool = True, sort: bool = True, addr_range: int = 1 << 20,
-            sort_keys: Tuple[int, ...] = SORT_KEYS, limbs: bool = True, order=None, order_limbs: int = ORDER_LIMBS, link=None):
+            sort_keys: Tuple[int, ...] = SORT_KEYS, limbs: bool = True, order=None, order_limbs: int = ORDER_LIMBS, link=None,
+            reads: bool = False):
     """-> (code, data, out_global) host arrays of raw Montgomery words: random words below min(P, 2^(n_limbs L)) split into limbs
     (limbs=False: zero, for the library to split), the table's multiplicities (count=False: zero, for the library to derive), random
     memory tuples (addresses below `addr_range`) and their copy stably sorted by the tuple positions `sort_keys`, (addr, time)
@@ -216,13 +240,19 @@ def witness(shape: Shape, po2: int, zk_cycles: int, seed: int = 1, count: bool =
     filled from the sorted copy (and their limbs counted in the multiplicities) / left zero for the library.
     link: None = no link; True / False = SYN-LOOKUP-linked's witness (`build_syn_lookup(link=True)`): no copy, the times are the row
     numbers, and linked, last, pval, ptime and the limbs of time - ptime - 1 are host-made by a walk over the rows with a dictionary,
-    one access after another (and the limbs counted) / left zero for the library"""
+    one access after another (and the limbs counted) / left zero for the library.
+    reads: SYN-LOOKUP-reads' witness (`build_syn_lookup(link=True, reads=True)`; it needs `link` True or False): a load / store trace.
+    Every access draws a write flag, and a load takes the value the previous access to its address left, or 0 without one; the write
+    flags are the host's column whatever `link` says"""
+    if reads and link is None:
+        raise ValueError("witness: reads=True is the read rule of the LINK records: it needs link=True or link=False")
     n_words, n_limbs, limb_bits, n_mem = shape
     words, limb_cols, m_col, mem, perm = layout(n_words, n_limbs, n_mem)
     limbs_on, limbs = limbs, limb_cols
     ocols = order_layout(n_words, n_limbs, n_mem, order_limbs) if order is not None else []
     lcols = link_layout(n_words, n_limbs, n_mem, order_limbs) if link is not None else []
-    wd = m_col + 1 + (sum(len(c) for c in lcols) if lcols else 2 * MEM_W * n_mem + sum(len(c) for c in ocols))
+    wd = m_col + 1 + (sum(len(c) for c in lcols) + n_mem * bool(reads) if lcols else 2 * MEM_W * n_mem + sum(len(c) for c in ocols))
+    wcols = reads_layout(n_words, n_limbs, n_mem, order_limbs) if reads else []
     n = 1 << po2
     A = n - zk_cycles
     T = 1 << limb_bits
@@ -252,6 +282,14 @@ def witness(shape: Shape, po2: int, zk_cycles: int, seed: int = 1, count: bool =
         addr = rng.integers(0, addr_range, size=A, dtype=np.uint64)
         val = rng.integers(0, P, size=A, dtype=np.uint64)
         time = rng.permutation(A).astype(np.uint64)
+        if wcols:                                                            # a load returns what the previous access left, or 0
+            store = rng.integers(0, 2, size=A, dtype=np.uint64)
+            held = {}
+            for r, a in enumerate(addr.tolist()):
+                if not store[r]:
+                    val[r] = held.get(a, 0)
+                held[a] = val[r]
+            data[wcols[i], :A] = store
         if lcols:
             _link_witness(data, lcols[i], addr, val, A, limb_bits, order_limbs, link, counts)
             continue
@@ -364,3 +402,26 @@ def relink_row(shape: Shape, data, po2: int, row: int, pair: int = 0, order_limb
         for j, c in enumerate(c_limbs):
             d[c, r] = ((diff >> (j * shape.limb_bits)) & ((1 << shape.limb_bits) - 1)) * R % P
     return d.reshape(-1)
+
+
+def misread_row(shape: Shape, data, po2: int, zk_cycles: int, row=None, pair: int = 0, order_limbs: int = ORDER_LIMBS):
+    """-> (a copy of SYN-LOOKUP-reads' host-made `data` in which the load at `row` returns its value plus one, row).  row = None picks a
+    load that is the last access to its address, from the middle of the trace on: its +1 and -last terms take the forged value from the
+    same row, so the bus balances as it is.  A load that has a next access gets that access's pval moved with it, and the bus balances
+    again.  No lookup reads a value, so the multiplicities are the same when they are counted again.  Only the read rule objects: on
+    `row`, and, where the next access is a load itself, on that later row as well"""
+    n = 1 << po2
+    A = n - zk_cycles
+    d = np.array(data, dtype=np.uint32).reshape(-1, n)
+    c_addr, c_val, _time, _linked, c_last, c_pval, *_ = link_layout(shape.n_words, shape.n_limbs, shape.n_mem, order_limbs)[pair]
+    c_w = reads_layout(shape.n_words, shape.n_limbs, shape.n_mem, order_limbs)[pair]
+    if row is None:
+        loads = np.nonzero((d[c_w, :A] == 0) & (d[c_last, :A] != 0))[0]
+        assert loads.size, "no load is the last access to its address"
+        row = int(loads[np.searchsorted(loads, A // 2) % loads.size])
+    assert d[c_w, row] == 0, f"row {row} is a store"
+    d[c_val, row] = (int(d[c_val, row]) + (1 << 32) % P) % P
+    later = row + 1 + np.nonzero(d[c_addr, row + 1:A] == d[c_addr, row])[0]
+    if later.size:
+        d[c_pval, int(later[0])] = d[c_val, row]
+    return d.reshape(-1), row

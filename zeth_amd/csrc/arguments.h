@@ -12,6 +12,10 @@
 // Nothing reads a derived multiplicity.  A term's multiplicity is the host's column or a derived one, and of a LINK's destinations
 // linked and last (only they) may be the multiplicity of a term that is not derived.
 //
+// THE READ RULE (a LINK record with READS, ZKA1 version 6; links.hip's header has it in full): the write flag is one more source of the
+// record, the host's column.  On an access it must be 0 or 1; a load (0) returns, in every carried column but the clock, what the
+// previous access to its address left, or 0 where there is none.  Residues mod P are compared.  The rule adds no destination.
+//
 // A derive that refuses a witness leaves `data` unchanged: its check pass reduces the lowest bad (record, row) into a BadRow, the host
 // reads that back, and only then does anything write.
 #pragma once
@@ -26,6 +30,7 @@ constexpr uint32_t ARGS_HEADER = 8, TERM_WORDS = 16;
 constexpr uint32_t MAX_TUPLE = 4, MAX_TERMS = 3, MAX_SORT_KEYS = 3, NONE = 0xffffffffu;
 constexpr uint32_t RECORD_WORDS = 16, KIND_LIMBS = 1, KIND_ORDER = 2, MAX_LIMBS = 8;
 constexpr uint32_t KIND_LINK = 3, LINK_WORDS = 32, MAX_CARRIED = 3, MAX_LINK_LIMBS = 4, MAX_LINK_DSTS = 2 + MAX_CARRIED + MAX_LINK_LIMBS;
+constexpr uint32_t LINK_READS = 1;                  // LINK word 5, bit 0 (version 6): the record carries the read rule
 constexpr uint32_t MAX_ORDER_BITS = 29;             // logup.MAX_ORDER_BITS: a negative difference stays out of the limbs' range
 
 // logup.Term as the blob gives it: the fields are the blob's words, checked by the rules of arguments.hip before a circuit keeps them
@@ -47,7 +52,7 @@ struct Record {
     uint32_t dst[MAX_LIMBS];                // destination data columns: (ORDER with two keys: the flag,) then the nl limbs
     uint32_t n_dst, reserved;               // destinations in use; a word the format reserves was not 0
 };
-// logup.Link, a LINK record (version 5), as the blob gives it; the kernels of links.hip read it in this form
+// logup.Link, a LINK record (version 5; version 6: the read rule), as the blob gives it; the kernels of links.hip read it in this form
 struct Link {
     uint32_t index;                         // its index among all records of the blob (LINK records follow the LIMBS / ORDER ones)
     uint32_t L, nl, nc, sel;                // limb bits; limb count; carried columns; selector code column or NONE
@@ -55,6 +60,7 @@ struct Link {
     uint32_t cg[MAX_CARRIED], cc[MAX_CARRIED];      // the carried columns, the first nc; c_0 is the clock
     uint32_t dst[MAX_LINK_DSTS];            // destination data columns: linked, last, prev_0 .. prev_{nc-1}, limb_0 .. limb_{nl-1}
     uint32_t n_dst, reserved;               // destinations in use; a word the format reserves was not 0
+    uint32_t flags, wg, wc;                 // version 6: word 5 (bit 0 = READS, LINK_READS) and words 14, 15, the write flag's (group, column)
 };
 // logup.Arguments
 struct Arguments {
@@ -63,6 +69,7 @@ struct Arguments {
     std::vector<Record> records;            // the LIMBS / ORDER records: their index here is their index in the blob
     std::vector<Link> links;                // the LINK records
     uint32_t late_record = NONE, late_after = 0;    // a LIMBS / ORDER record that follows a LINK record, and that LINK record (refused)
+    uint32_t reads = 0;                     // the LINK records with READS (version 6: header word 7)
 };
 
 // a term's columns as the kernels read them; unused tuple slots name (data, 0)

@@ -1,5 +1,5 @@
 // arguments.hip — the ZKA1 argument blob (layout: zeth_amd/circuits/logup.py; DESIGN.md §2 ARGUMENTS): its decoding into
-// zkh::Arguments (terms, from version 4 derived-column records, from version 5 LINK records), the rules a circuit's arguments keep
+// zkh::Arguments (terms, from version 4 derived-column records, from version 5 LINK records, from version 6 their read rule), the rules a circuit's arguments keep
 // (check_sorted, check_derived, then check_owned over the LIMBS / ORDER records and over the LINK records), and the entry points that attach them to a circuit and ask what they derive.
 // decode_arguments is the only code that knows the blob's words; everything else, here and in the consumers, reads decoded terms.
 #include "arguments.h"
@@ -16,7 +16,7 @@ namespace {
 // significant key first); bits 2, 3, 7, the position fields of unused keys and, without bit 1, everything above bit 0 are reserved.
 // A reserved bit is recorded, not refused: the rules refuse it where they reach the term (flag_word_rule), after the circuit-shape checks.
 const char* decode_arguments(const uint32_t* a, size_t words, Arguments* out) {
-    ZKH_REQUIRE(words >= ARGS_HEADER && a[0] == ARGS_MAGIC && a[1] >= 1 && a[1] <= 5, "set_arguments: not a ZKA1 (version 1) argument blob");
+    ZKH_REQUIRE(words >= ARGS_HEADER && a[0] == ARGS_MAGIC && a[1] >= 1 && a[1] <= 6 && (a[1] < 6 || a[7] != 0), "set_arguments: not a ZKA1 (version 1) argument blob");
     const uint32_t n_terms = a[5], n_records = a[1] >= 4 ? a[6] : 0;            // header word 6: the records of version 4, reserved before
     const size_t rec0 = ARGS_HEADER + (size_t)TERM_WORDS * n_terms;
     size_t end = rec0;                                                          // a LINK record (version 5) takes two slots; past the blob's end the walk stops
@@ -47,6 +47,8 @@ const char* decode_arguments(const uint32_t* a, size_t words, Arguments* out) {
     // with the flags, a reserved word that is set is recorded here and refused by the rules (columns_clause_a).
     // LINK records (version 5, kind 3, 32 words): L, nl, nc, sel, 0, the key's (group, column), three carried (group, column) pairs, 0, 0,
     // then from word 16 the destinations linked, last, prev_0 .. prev_{nc-1}, limb_0 .. limb_{nl-1}, the rest 0 (links_clause_a).
+    // Version 6: word 5 is a flag word (bit 0 = READS), words 14, 15 the write flag's (group, column) with READS and 0 without; header
+    // word 7 counts the records with READS (0 there is no ZKA1 blob: above).
     out->records.clear();
     out->links.clear();
     const uint32_t* r = a + rec0;
@@ -59,7 +61,9 @@ const char* decode_arguments(const uint32_t* a, size_t words, Arguments* out) {
             const uint32_t nc = x.nc < MAX_CARRIED ? x.nc : MAX_CARRIED;
             const uint64_t nd = 2ull + nc + x.nl;
             x.n_dst = nd < MAX_LINK_DSTS ? (uint32_t)nd : MAX_LINK_DSTS;
-            x.reserved = r[5] | r[14] | r[15];
+            if (out->version >= 6) { x.flags = r[5]; x.wg = r[14]; x.wc = r[15]; }
+            else x.reserved = r[5] | r[14] | r[15];
+            out->reads += x.flags & LINK_READS;
             for (uint32_t j = nc; j < MAX_CARRIED; j++) x.reserved |= x.cg[j] | x.cc[j];
             for (uint32_t j = 16 + x.n_dst; j < LINK_WORDS; j++) x.reserved |= r[j];
             out->links.push_back(x);
@@ -78,6 +82,7 @@ const char* decode_arguments(const uint32_t* a, size_t words, Arguments* out) {
         out->records.push_back(x);
         r += RECORD_WORDS;
     }
+    ZKH_REQUIRE(out->version < 6 || a[7] == out->reads, "set_arguments: header word 7 is %u, the blob has %u LINK records with READS", a[7], out->reads);
     return nullptr;
 }
 
@@ -173,7 +178,7 @@ bool is_column(const zkh_circuit* c, uint32_t g, uint32_t col) { return (g == GR
 struct Owned {
     uint32_t index;                                     // its index among the blob's records
     bool link;                                          // a LINK: it runs after every LIMBS / ORDER record
-    uint32_t n_src, sg[1 + MAX_CARRIED], sc[1 + MAX_CARRIED];   // the (group, column) pairs it reads (LINK: the key, then the carried columns)
+    uint32_t n_src, sg[2 + MAX_CARRIED], sc[2 + MAX_CARRIED];   // the (group, column) pairs it reads (LINK: the key, the carried columns, with READS the write flag)
     uint32_t n_dst, dst[MAX_LINK_DSTS];                 // the data columns it writes
     bool writes(uint32_t col) const { return std::find(dst, dst + n_dst, col) != dst + n_dst; }
     bool reads(uint32_t col) const {                    // data column `col` among its sources
@@ -194,6 +199,7 @@ std::vector<Owned> owned(const Arguments& a) {
         const uint32_t nc = std::min(r.nc, MAX_CARRIED);
         Owned v{r.index, true, 1 + nc, {r.kg}, {r.kc}, r.n_dst, {}};
         std::copy(r.cg, r.cg + nc, v.sg + 1); std::copy(r.cc, r.cc + nc, v.sc + 1); std::copy(r.dst, r.dst + r.n_dst, v.dst);
+        if (r.flags & LINK_READS) { v.sg[v.n_src] = r.wg; v.sc[v.n_src++] = r.wc; }
         all.push_back(v);
     }
     return all;
@@ -210,12 +216,17 @@ const char* columns_clause_a(const Record& r, uint32_t i) {
     ZKH_REQUIRE(!r.reserved, "set_arguments: record %u: a reserved word is not 0 (the unused source pair and the unused destination words)", i);
     return nullptr;
 }
-// logup.check_links' own clause (a): the ranges of nc, L, nl, the reserved words, and the selector a code column
+// logup.check_links' own clause (a): the ranges of nc, L, nl, the flag word and the write flag's words (version 6), the reserved words, and the
+// selector a code column
 const char* links_clause_a(const zkh_circuit* c, const Link& r) {
     const uint32_t i = r.index;
     ZKH_REQUIRE(r.nc >= 1 && r.nc <= MAX_CARRIED && r.L >= 1 && r.L <= 16 && r.nl <= MAX_LINK_LIMBS && r.L * r.nl <= MAX_ORDER_BITS,
                 "set_arguments: record %u: a LINK of %u carried columns and %u limbs of %u bits (1..%u carried columns, 0..%u limbs of 1..16 bits, at most "
                 "%u bits in all)", i, r.nc, r.nl, r.L, MAX_CARRIED, MAX_LINK_LIMBS, MAX_ORDER_BITS);
+    ZKH_REQUIRE(r.flags <= LINK_READS, "set_arguments: record %u: word 5 of a LINK is %#x (bit 0: READS, the read rule; the other bits are reserved)", i, r.flags);
+    ZKH_REQUIRE(r.flags || !(r.wg | r.wc), "set_arguments: record %u: words 14, 15 of a LINK name a write flag, but bit 0 of word 5 (READS) is not set", i);
+    ZKH_REQUIRE(!r.flags || r.nc >= 2, "set_arguments: record %u: READS needs a clock and a value column (2..%u carried columns), this LINK carries %u", i,
+                MAX_CARRIED, r.nc);
     ZKH_REQUIRE(!r.reserved, "set_arguments: record %u: a reserved word of a LINK is not 0 (words 5, 14, 15, the unused carried pairs and the unused "
                 "destination words)", i);
     ZKH_REQUIRE(r.sel == NONE || r.sel < c->group_size[GROUP_CODE], "set_arguments: record %u: selector %u is not a code column", i, r.sel);
@@ -356,6 +367,8 @@ extern "C" int zkh_circuit_derives_sorted(const zkh_circuit* c) {
 extern "C" int zkh_circuit_derives_columns(const zkh_circuit* c) { return c && c->args && !c->args->records.empty(); }
 
 extern "C" int zkh_circuit_derives_links(const zkh_circuit* c) { return c && c->args && !c->args->links.empty(); }
+
+extern "C" int zkh_circuit_links_check_reads(const zkh_circuit* c) { return c && c->args ? (int)c->args->reads : 0; }
 
 extern "C" const char* zkh_circuit_derived_data_columns(const zkh_circuit* c, uint32_t* cols, size_t cap, size_t* n) {
     ZKH_REQUIRE(c && n && (cols || !cap), "derived_data_columns: null argument");

@@ -159,6 +159,7 @@ ABI = {
     "zkh_circuit_derives_columns": (_i, [_vp]),
     "zkh_derive_columns": (_err, [_vp, _vp, _sz, _sz, _vp, _vp]),
     "zkh_circuit_derives_links": (_i, [_vp]),
+    "zkh_circuit_links_check_reads": (_i, [_vp]),
     "zkh_derive_links": (_err, [_vp, _vp, _sz, _sz, _vp, _vp]),
     "zkh_circuit_derived_data_columns": (_err, [_vp, _u32p, _sz, C.POINTER(_sz)]),
     "zkh_upload_data_trace": (_err, [_vp, _vp, _sz, _sz, _vp, _u32p, _i]),
@@ -351,6 +352,10 @@ class Circuit:
     def derives_links(self) -> bool:
         """the arguments (ZKA1 version 5) hold LINK records the library fills (zkh_derive_links)"""
         return bool(_lib.zkh_circuit_derives_links(self.h))
+
+    def links_check_reads(self) -> int:
+        """the LINK records with READS (ZKA1 version 6): zkh_derive_links refuses a load that does not return the last store"""
+        return int(_lib.zkh_circuit_links_check_reads(self.h))
 
     def derived_data_columns(self) -> List[int]:
         """the data columns the library's derives (sorted, columns, links, multiplicities) write on the active rows, ascending"""
