@@ -1,6 +1,6 @@
 """Seeded random shape sweep of the HAL ops against the CPU oracle (bit-exact), complementing the fixed shapes of
-test_hal_parity_gpu.py: ragged sizes, column counts around the sponge rate, sizes around the 256-wide scan blocks and
-the kernels' path switches (2^12 / 2^18 / 2^20 transforms, 2^7 / 2^15 Merkle layers).  Inputs mix uniform elements
+test_hal_parity_gpu.py: ragged sizes, column counts around the sponge rate, sizes around 2^8 and 2^16 (the scan blocks
+themselves hold 2048 ExtElems at level 0 and 2^19 at level 1: their edges are in test_poly_edges_gpu.py) and the kernels' path switches (2^12 / 2^18 / 2^20 transforms, 2^7 / 2^15 Merkle layers).  Inputs mix uniform elements
 with runs of 0 and P-1.  The seeds are fixed, so a failure reproduces.  ZKH_FUZZ_SEED_OFFSET=N shifts every seed by N: a soak
 over fresh shapes on spare GPU time (`tools/gpu.sh fuzzsoak`); unset (the suite) = offset 0."""
 import os

@@ -23,8 +23,9 @@ P = 2013265921
 
 @pytest.mark.parametrize("bitrev", [False, True])
 def test_batch_evaluate_any_runs_of_equal_columns(hal, oracle, bitrev):
-    """Taps of one register = consecutive entries with the same `which`: one block streams the column once for up to 8
-    points.  Runs of every length around that limit, interleaved with singletons, against the oracle."""
+    """Taps of one register = consecutive entries with the same `which`: one block streams the column once for up to 5
+    points.  Runs of every length around that limit, interleaved with singletons, against the oracle (runs of hundreds and
+    thousands of entries: test_poly_edges_gpu.py)."""
     rng = np.random.default_rng(77)
     po2, count = 14, 12
     n = 1 << po2

@@ -4,8 +4,10 @@
 // /root/reference/crates/host/src/lib.rs:137.
 //
 // All of these stream W x n (or combos x n) words once: HBM-bound.  The two linear recurrences (synthetic
-// division, running product) are done as three-level 256-wide block scans (up-sweep of block totals, down-sweep
-// with carries) instead of upstream's chunked sequential loops.
+// division, running product) are done as three-level block scans (up-sweep of block totals, down-sweep with carries)
+// instead of upstream's chunked sequential loops: a level-0 block holds 256 lanes x SC_E = 2048 ExtElems, levels 1 and 2
+// scan 256 block totals each, so a level-1 block covers 2^19 ExtElems and the third level works from 2^19 + 1 on
+// (limit: 2^24).
 #include <algorithm>
 
 #include "common.h"
@@ -64,8 +66,17 @@ __global__ void k_ext_scale_at(uint32_t* out, const uint32_t* __restrict__ recs,
 // with the same which[] form a run, and ONE block streams the column once for up to EV_MAXP points of the run (the other
 // blocks of the run exit at once), so DEEP evaluation reads W x n words instead of #taps x n.  (EV_MAXP is a register
 // budget: 8 accumulating points need 256 VGPRs = one wave per SIMD, which costs more bandwidth than the re-reads save.)
+//
+// Leaders of a run of ANY length (which[] is the caller's: up to n_eval equal entries).  A block finds its offset inside the run
+// by walking back at most EV_SCAN entries.  Offsets 0 .. EV_SCAN are exact, and every EV_MAXP-th of them leads.  Deeper inside a
+// run the offset is unknown and every entry looks like its neighbours, so leadership there goes by the ABSOLUTE index: entry k0
+// leads iff k0 % EV_MAXP == 0.  EV_SCAN is a multiple of EV_MAXP, so the last leader by offset (at EV_SCAN) covers offsets up to
+// EV_SCAN + 4, and an entry deeper than that has its absolute leader deeper than EV_SCAN as well: every (entry, chunk) slot of
+// `partial` is written, a column is streamed ceil(run / EV_MAXP) + 1 times at most, and the at most 4 entries that two leaders
+// cover get the same value from both (a point's partial sum does not depend on which other points share its block).
 // ---------------------------------------------------------------------------------------------------------
-constexpr int EV_PER = 64, EV_CH = TB * EV_PER, EV_MAXP = 5, EV_SCAN = 256;   // 5 = the longest back-set of a register (backs 0..4)
+constexpr int EV_PER = 64, EV_CH = TB * EV_PER, EV_MAXP = 5, EV_SCAN = 255;   // 5 = the longest back-set of a register (backs 0..4)
+static_assert(EV_SCAN % EV_MAXP == 0, "the last leader by run offset must meet the first leader by absolute index");
 
 template <int NP>
 __device__ __forceinline__ void ev_accumulate(Fp4 (&acc)[EV_MAXP], const uint32_t* __restrict__ c, size_t j0, size_t po,
@@ -160,12 +171,14 @@ __global__ __launch_bounds__(TB) void k_eval_partial(uint32_t* __restrict__ part
                                                      uint32_t n_eval) {
     __shared__ uint4 xp[EV_MAXP][EV_PER];
     __shared__ uint4 red[TB];
-    // run of this block: leader = first entry of the run, or every EV_MAXP-th entry of a longer run
+    // run of this block: leader = first entry of the run, or every EV_MAXP-th entry of a longer run (by run offset as far as the
+    // back-scan reaches, by absolute index beyond it: see above)
     const uint32_t k0 = blockIdx.y, chunk = blockIdx.x, t = threadIdx.x;
     const uint32_t col = which[k0];
     uint32_t start = k0;
     for (uint32_t back = 0; back < EV_SCAN && start > 0 && which[start - 1] == col; back++) start--;
-    if ((k0 - start) % EV_MAXP != 0) return;                  // another block of the run covers this entry
+    const bool deep = k0 - start == EV_SCAN && start > 0 && which[start - 1] == col;     // more than EV_SCAN entries into its run
+    if ((deep ? k0 : k0 - start) % EV_MAXP != 0) return;      // another block of the run covers this entry
     uint32_t np = 1;
     while (np < EV_MAXP && k0 + np < n_eval && which[k0 + np] == col) np++;
     for (uint32_t e = t; e < np * EV_PER; e += TB) xp[e / EV_PER][e % EV_PER] = tab[(size_t)(k0 + e / EV_PER) * EV_TAB + TB + e % EV_PER];
@@ -437,19 +450,21 @@ __global__ __launch_bounds__(TB) void k_combine_quotients(uint32_t* __restrict__
                                                           const uint32_t* __restrict__ n_pairs, const uint32_t* __restrict__ weights) {
     const size_t i = (size_t)blockIdx.x * TB + threadIdx.x;
     const uint32_t y = blockIdx.y;
-    if (i >= cycles) return;
-    Fp4 acc = Fp4::zero();
     const uint32_t p0 = first_pair[y], np = n_pairs[y];
+    if (i >= cycles || !np) return;                       // a combo without division points is not divided: it stays as it is
+    Fp4 acc = Fp4::zero();
     for (uint32_t p = 0; p < np; p++) acc = acc + ld_ext(q + 4 * ((size_t)(p0 + p) * cycles + i)) * ld_ext(weights + 4 * (p0 + p));
     st_ext(combos + combo_off[y] + 4 * i, acc);
 }
 // The remainders of dividing successively by (x - z_1), (x - z_2), ... are the Newton divided differences of the
-// polynomial's values at those points: r_1 = c(z_1), r_2 = (c(z_2) - c(z_1)) / (z_2 - z_1), ...  One lane per combo.
+// polynomial's values at those points: r_1 = c(z_1), r_2 = (c(z_2) - c(z_1)) / (z_2 - z_1), ...  One lane per combo (at most
+// 8 points: the caller's fast-path limit); a combo without points has no remainder slot and writes nothing.
 __global__ void k_divided_differences(uint32_t* __restrict__ rem_out, const uint32_t* __restrict__ vals, const uint32_t* __restrict__ pts,
                                       const uint32_t* __restrict__ first_pair, const uint32_t* __restrict__ n_pairs, uint32_t n_combos) {
     const uint32_t y = blockIdx.x * blockDim.x + threadIdx.x;
     if (y >= n_combos) return;
     const uint32_t p0 = first_pair[y], np = n_pairs[y];
+    if (!np) return;
     Fp4 d[8];
     for (uint32_t p = 0; p < np; p++) d[p] = ld_ext(vals + 4 * (p0 + p));
     for (uint32_t lvl = 1; lvl < np; lvl++)
