@@ -212,6 +212,24 @@ size_t zkh_circuit_compiled_parts(const zkh_circuit*);
 const char* zkh_eval_check(zkh_ctx*, const zkh_circuit*, zkh_buf* check, const zkh_buf* const* groups, size_t n_groups,
                            const zkh_buf* const* globals, size_t n_globals, const uint32_t poly_mix[4], size_t po2,
                            size_t steps, int use_interpreter);
+/* A witness checked against the circuit's own constraints, row by row, on the device (csrc/check_rows.hip; DESIGN.md §2 CHECK ROWS):
+ * which constraint a trace breaks, and on which row, before a seal is spent on it.  groups = the RAW accum, code, data traces (each
+ * W x 2^po2 words; n_groups must be 3); out_global / mix_global = host words, as zkh_accumulate takes mix.  Every constraint is
+ * evaluated exactly on every row r of the window [row_lo, row_hi) of the trace domain (no mix, no probability): a tap (g, col, back)
+ * reads row (r - back) mod 2^po2, cells and globals are read as residues (raw % P), values are Fp, and Fp4 downstream of a ConstExt.
+ * Over the mix steps F = the lowest failing and_eqz step (an index into the ZKC1 step list) or 0xffffffff:
+ *   F(true) = none; F(and_eqz(x, v)) = min(F(x), v != 0 ? this step : none); F(and_cond(x, cond, inner)) = min(F(x), cond != 0 ?
+ *   F(inner) : none); an Fp4 is non-zero when any component is.  Row r fails when F(ret) is a step.
+ * result: row = the lowest failing row of the window (-1: none failed, the other fields are then 0xffffffff, 0, zeros), step = its
+ * F(ret), failing_rows = the rows of the window that fail, value = the value that step requires to be zero on that row (canonical,
+ * decoded; a base-field value has zero upper components).  per_row (NULL, or a buffer of 2^po2 words): word r = F(ret) of row r for
+ * the rows of the window; the other words are not written.
+ * A failing row is an ANSWER: the call returns NULL either way.  It fails only for bad shapes, an empty window or one outside
+ * [0, 2^po2], a circuit loaded on another context, and a step list whose live values exceed the step interpreter's LDS. */
+typedef struct { int64_t row; uint32_t step; uint32_t failing_rows; uint32_t value[4]; } zkh_check_rows_result;
+const char* zkh_check_rows(zkh_ctx*, const zkh_circuit*, size_t po2, const zkh_buf* const* groups, size_t n_groups,
+                           const uint32_t* out_global, const uint32_t* mix_global, size_t row_lo, size_t row_hi, zkh_buf* per_row,
+                           zkh_check_rows_result* result);
 
 /* ---- CircuitHal::accumulate for arguments described as data (csrc/accumulate.hip; zeth_amd/circuits/logup.py) ----
  * Lookup and permutation arguments as log-derivative sums: a ZKA1 blob lists terms t(r) = sign sel(r) m(r) / (alpha - (tag + beta v_0(r)

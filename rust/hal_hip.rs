@@ -379,6 +379,21 @@ impl HipCircuitHal {
         ffi(|| unsafe { sys::zkh_derive_links(self.hal.ctx.0, self.circuit, po2, sys::ZK_CYCLES, ctrl.raw, data.raw) });
     }
 
+    /// Check the raw traces against the circuit's own constraints on every row of `rows` (`zkh_check_rows`): which constraint a
+    /// witness breaks, and where, before a seal is spent on it.  `out` and `mix` are the global words.  `row < 0`: no row of the window
+    /// fails; otherwise the lowest failing row, its lowest failing `and_eqz` step (an index into the ZKC1 step list), how many rows of
+    /// the window fail and the canonical value that step wants zero.  A failing row is an answer; it panics only on bad shapes, a bad
+    /// window, or a step list whose live values exceed the step interpreter's LDS.
+    pub fn check_rows(&self, accum: &HipBuffer<BabyBearElem>, ctrl: &HipBuffer<BabyBearElem>, data: &HipBuffer<BabyBearElem>, out: &[u32], mix: &[u32],
+                      steps: usize, rows: std::ops::Range<usize>, per_row: Option<&HipBuffer<u32>>) -> sys::ZkhCheckRowsResult {
+        let po2 = steps.trailing_zeros() as usize;
+        let g: [*const ZkhBuf; 3] = [accum.raw as *const ZkhBuf, ctrl.raw as *const ZkhBuf, data.raw as *const ZkhBuf];
+        let mut res = sys::ZkhCheckRowsResult { row: -1, step: u32::MAX, failing_rows: 0, value: [0; 4] };
+        ffi(|| unsafe { sys::zkh_check_rows(self.hal.ctx.0, self.circuit, po2, g.as_ptr(), 3, out.as_ptr(), mix.as_ptr(), rows.start, rows.end,
+                                            per_row.map_or(std::ptr::null_mut(), |b| b.raw), &mut res) });
+        res
+    }
+
     /// The data columns that the four derives write on the active rows, ascending (`zkh_circuit_derived_data_columns`).
     pub fn derived_data_columns(&self) -> Vec<u32> {
         let mut n = 0usize;

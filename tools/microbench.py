@@ -4,7 +4,9 @@ arguments and its share of that circuit's seal; M11 / M11w: derived lookup multi
 against the host's lexsort + upload; M13: derived columns — the 64 limb columns of SYN-LOOKUP FULL — next to a plain copy of the same
 bytes, and the host-witness seal with its upload; M14: linked accesses of SYN-LOOKUP-linked (zkh_derive_links) next to a plain copy of
 the same bytes, to the host's sort + gather + upload, and the host-witness seal with the derive against the host-made columns; M14r: the read rule, zkh_derive_links on SYN-LOOKUP-reads
-under its version-6 blob next to the same trace under the version-5 blob) on one MI355X, through the C ABI (HipHal).
+under its version-6 blob next to the same trace under the version-5 blob; M15: zkh_check_rows, the row-by-row constraint check of an honest
+SYN-A / SYN-HEAVY witness, next to zkh_eval_check on the step interpreter for the same circuit in the same run, alternating) on one
+MI355X, through the C ABI (HipHal).
 
 Each line of output is one JSON object: the op, its shape, the average wall time of one call (stream drained on both
 sides of `reps` back-to-back calls), its ALGORITHMIC bytes (SURVEY.md §8a "B_alg": inputs read once + outputs written
@@ -473,6 +475,43 @@ def main() -> None:
         print(json.dumps({"bench": "M14reads", **res, "reads_vs_v5": round(res["v6_reads"]["derive_links_ms"] / res["v5"]["derive_links_ms"], 3),
                           "check_vs_v5": round(res["v6_reads"]["steps_ms"].get("links_check", 0) / max(res["v5"]["steps_ms"].get("links_check", 0), 1e-9), 3)}),
               flush=True)
+    if want("M15"):
+        # the row-by-row constraint check (zkh_check_rows: the interpreter's program on the n rows of the trace domain, no mix arithmetic)
+        # of an honest witness of the built-in generator, next to its yardstick in the same run: zkh_eval_check on the step interpreter
+        # (use_interpreter = 1), the same program over the 4n points of the evaluation domain with Fp4 mix arithmetic.  The two are
+        # timed in alternation, `runs` windows of `reps` calls each; median and spread (min, max) of the windows.  check_rows is a
+        # whole call: its globals' upload, the pass, the read-back of the result.
+        from zeth_amd.circuits import syn_heavy
+        from zeth_amd.prover import Segment, SegmentProver
+        runs = 7
+        # (SYN-HUGE only when asked for: --only M15,M15huge)
+        circuits = [("SYN-A", syn_air.syn_a()), ("SYN-HEAVY", syn_heavy.syn_heavy())] + ([("SYN-HUGE", syn_heavy.syn_huge())] if "M15huge" in only else [])
+        for name, desc in circuits:
+            d = Desc.parse(desc)
+            prover = SegmentProver(hal, desc)
+            seg = Segment(index=0, po2=args.po2, noise_seed=0x2E80)
+            code, data, out = prover.witgen(seg)
+            mix = rand_fp(rng, d.global_sizes[1])
+            accum = prover.syn_accumulate(seg, data)(mix)
+            found = hal.check_rows(prover.circuit, args.po2, accum, code, data, out, mix)
+            assert found["row"] == -1, found                     # an honest witness: the pass alone, no second launch
+            groups = [upload(hal, rng, "m15g", wg * dom) for wg in d.group_sizes]
+            globals_ = [hal.copy_from("m15o", out), hal.copy_from("m15m", mix)]
+            check = hal.alloc_elem("m15c", 4 * dom)
+            poly_mix = rand_fp(rng, 4)
+            rows_fn = lambda: hal.check_rows(prover.circuit, args.po2, accum, code, data, out, mix)      # noqa: E731
+            eval_fn = lambda: prover.circuit.eval_check(check, groups, globals_, poly_mix, args.po2, use_interpreter=True)   # noqa: E731
+            t_rows, t_eval = [], []
+            for _ in range(runs):
+                t_rows.append(timed(hal, rows_fn, args.reps))
+                t_eval.append(timed(hal, eval_fn, args.reps))
+            spread = lambda ts: {"median_ms": round(float(np.median(ts)) * 1e3, 4), "min_ms": round(min(ts) * 1e3, 4), "max_ms": round(max(ts) * 1e3, 4)}   # noqa: E731
+            total_w = sum(d.group_sizes)
+            print(json.dumps({"bench": "M15", "circuit": name, "po2": args.po2, "steps": len(d.steps), "columns": total_w, "runs": runs, "reps": args.reps,
+                              "check_rows": spread(t_rows), "eval_check_interp": spread(t_eval),
+                              "check_rows_trace_GB": round(4 * total_w * n / 1e9, 4), "eval_check_domain_GB": round(4 * total_w * dom / 1e9, 4),
+                              "check_rows_vs_eval_check_interp": round(float(np.median(t_rows)) / float(np.median(t_eval)), 4)}), flush=True)
+            del groups, globals_, check, accum, code, data, prover
     hal.close()
 
 

@@ -84,7 +84,7 @@ const char* prefix_sum_planes(zkh_ctx* ctx, const char* what, uint32_t* cols, ui
 // device program for the generic interpreter (slots allocated on the host by liveness).  op = opcode | kind(a) << 8 |
 // kind(b) << 11 | (dst is Fp4) << 14; operand kinds: taps, constants and globals are operands, not slots, so a tap that
 // thousands of constraints read does not pin a slot for the whole program.
-struct InterpInsn { uint32_t op, dst, a, b, c, w; };   // w = index into mix_pows (ConstExt: 4th word)
+struct InterpInsn { uint32_t op, dst, a, b, c, w; };   // w = index into mix_pows (ConstExt: 4th word); and_eqz: c = its ZKC1 step index
 enum : uint32_t { OPK_FP = 0, OPK_EXT = 1, OPK_TAP = 2, OPK_CONST = 3, OPK_GLOBAL = 4 };
 
 }  // namespace zkh

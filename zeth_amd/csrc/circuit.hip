@@ -551,7 +551,8 @@ extern "C" const char* zkh_circuit_load(zkh_ctx* ctx, const uint32_t* d, size_t 
                 case OP_CONST_EXT: in.a = fp_encode(s.a).v; in.b = fp_encode(s.b).v; in.c = fp_encode(s.c).v; in.w = fp_encode(s.d).v; break;
                 case OP_ADD: case OP_SUB: case OP_MUL: in.a = operand(s.a, ka); in.b = operand(s.b, kb); break;
                 case OP_TRUE: break;
-                case OP_AND_EQZ: in.a = mix_slot[s.a]; in.b = operand(s.b, kb); in.w = mix_exp[s.a]; break;
+                // c = the step's index in the ZKC1 list: what zkh_check_rows names (check_rows.hip); k_eval_check_interp does not read it
+                case OP_AND_EQZ: in.a = mix_slot[s.a]; in.b = operand(s.b, kb); in.c = (uint32_t)i; in.w = mix_exp[s.a]; break;
                 case OP_AND_COND: in.a = mix_slot[s.a]; in.b = operand(s.b, kb); in.c = mix_slot[s.c]; in.w = mix_exp[s.a]; break;
                 }
                 in.op |= (ka << 8) | (kb << 11);

@@ -83,6 +83,11 @@ class ProfRec(C.Structure):
     _fields_ = [("name", C.c_char * 48), ("calls", C.c_uint64), ("total_ms", C.c_double), ("alg_bytes", C.c_double)]
 
 
+class CheckRowsResult(C.Structure):
+    """`zkh_check_rows_result`: what zkh_check_rows found (row -1: no row of the window fails)."""
+    _fields_ = [("row", C.c_int64), ("step", C.c_uint32), ("failing_rows", C.c_uint32), ("value", C.c_uint32 * 4)]
+
+
 ABI = {
     "zkh_free_error": (None, [_vp]),
     "zkh_version": (C.c_char_p, []),
@@ -140,6 +145,7 @@ ABI = {
     "zkh_circuit_attach_code_object_part": (_err, [_vp, C.c_char_p, _sz, C.c_char_p, _sz, _sz]),
     "zkh_circuit_compiled_parts": (_sz, [_vp]),
     "zkh_eval_check": (_err, [_vp, _vp, _vp, C.POINTER(_vp), _sz, C.POINTER(_vp), _sz, _u32p, _sz, _sz, _i]),
+    "zkh_check_rows": (_err, [_vp, _vp, _sz, C.POINTER(_vp), _sz, _u32p, _u32p, _sz, _sz, _vp, C.POINTER(CheckRowsResult)]),
     "zkh_syn_code": (_err, [_vp, _vp, _sz, _sz, _vp]),
     "zkh_sha256": (None, [C.c_char_p, _sz, C.POINTER(C.c_uint8)]),
     "zkh_session_check_termination": (_err, [_vp, C.POINTER(_u32p), C.POINTER(_sz), _sz, C.c_char_p, _sz]),
@@ -820,6 +826,22 @@ class HipHal:
         other than 0 / 1, on a clock that does not increase or on a difference that does not fit its limbs, naming the lowest
         (record, row) (`data` is then unchanged)"""
         _check(_lib.zkh_derive_links(self.ctx, circuit.h, po2, zk_cycles, code.h, data.h))
+
+    def check_rows(self, circuit: Circuit, po2: int, accum: Buffer, code: Buffer, data: Buffer, out_global, mix_global,
+                   row_lo: int = 0, row_hi: Optional[int] = None, per_row: bool = False) -> dict:
+        """the circuit's constraints evaluated exactly on every row of the window [row_lo, row_hi) of the RAW traces (zkh_check_rows;
+        the definition: circuits/check.py reference_check_rows).  -> {"row": lowest failing row or -1, "step": its lowest failing
+        and_eqz step (an index into the ZKC1 step list; explain with circuits.check.explain_step), "failing_rows", "value": the four
+        canonical words of the value that step wants zero, "per_row": None, or with per_row=True the 2^po2 words F(ret) of every
+        row, NONE = 0xffffffff outside the window and where nothing fails}.  A failing row is an answer, not an error."""
+        o, m = _u32(out_global), _u32(mix_global)
+        g = (_vp * 3)(accum.h, code.h, data.h)
+        rows = self.copy_from("check_rows_per_row", np.full(1 << po2, 0xFFFFFFFF, dtype=np.uint32)) if per_row else None
+        res = CheckRowsResult()
+        _check(_lib.zkh_check_rows(self.ctx, circuit.h, po2, g, 3, _ptr(o) if o.size else None, _ptr(m) if m.size else None, row_lo,
+                                   (1 << po2) if row_hi is None else row_hi, rows.h if rows is not None else None, C.byref(res)))
+        return {"row": int(res.row), "step": int(res.step), "failing_rows": int(res.failing_rows), "value": tuple(int(x) for x in res.value),
+                "per_row": rows.to_vec() if rows is not None else None}
 
     def upload_data_trace(self, circuit: Circuit, po2: int, zk_cycles: int, data: Buffer, host: np.ndarray, pinned_async: bool = True) -> None:
         """upload a caller's data trace without what the library derives (zkh_upload_data_trace): the other columns whole, the derived

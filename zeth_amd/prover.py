@@ -207,10 +207,27 @@ class SegmentProver:
                                                 out.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(seal_p), C.byref(n)))
         return SegmentReceipt(seal=self._take_seal(seal_p, n), index=seg.index, po2=seg.po2, output=out.copy())
 
+    def check_witness(self, seg: Segment, code, data, out_global, accum, mix_global) -> None:
+        """Check the raw traces against the circuit's own constraints on every row (zkh_check_rows): raises HalError naming the lowest
+        failing row, its lowest failing constraint step, the value that step wants zero, what it reads (circuits/check.py
+        explain_step) and how many rows fail.  Costs one pass over the trace; a seal of a bad witness costs the whole seal and names
+        neither row nor constraint."""
+        from .circuits import check as _check_rows
+        if code is None:
+            raise _hal.HalError("check_witness: the constraints read the raw code trace; it is not held (resident code group)")
+        r = self.hal.check_rows(self.circuit, seg.po2, accum, code, data, out_global, mix_global)
+        if r["row"] < 0:
+            return
+        v = r["value"]
+        value = str(v[0]) if not any(v[1:]) else "(" + ", ".join(str(x) for x in v) + ")"
+        raise _hal.HalError(f"witness: row {r['row']} fails constraint step {r['step']} (value {value}; reads "
+                            f"{_check_rows.describe_reads(self.circuit.desc, r['step'])}; {r['failing_rows']} rows fail)")
+
     def seal_with_accum(self, seg: Segment, code, data, out_global,
-                        accumulate: Callable[[np.ndarray], "_hal.Buffer"]) -> SegmentReceipt:
+                        accumulate: Callable[[np.ndarray], "_hal.Buffer"], check: bool = False) -> SegmentReceipt:
         """The same seal through the circuit-agnostic halves: zkh_prove_begin (header, code, data -> mix challenges),
-        `accumulate(mix_global) -> accum buffer` supplied by the caller (CircuitHal::accumulate), zkh_prove_finish."""
+        `accumulate(mix_global) -> accum buffer` supplied by the caller (CircuitHal::accumulate), zkh_prove_finish.
+        check: run check_witness between the accumulate and zkh_prove_finish; a witness that fails it raises, and no seal is made."""
         out = np.ascontiguousarray(out_global, dtype=np.uint32)
         wa = self.group_sizes()[0]
         job = C.c_void_p()
@@ -221,6 +238,8 @@ class SegmentProver:
             accum = accumulate(mix[: int(self.circuit.desc[8])])
             if accum.size() != wa << seg.po2:
                 raise _hal.HalError("accumulate returned a buffer of the wrong shape")
+            if check:
+                self.check_witness(seg, code, data, out, accum, mix[: int(self.circuit.desc[8])])
         except BaseException:
             _hal._lib.zkh_prove_abort(job)
             raise
@@ -252,13 +271,14 @@ class SegmentProver:
             return accum
         return acc
 
-    def seal_host_witness(self, seg: Segment, host_code: np.ndarray, host_data: np.ndarray, out_global) -> SegmentReceipt:
+    def seal_host_witness(self, seg: Segment, host_code: np.ndarray, host_data: np.ndarray, out_global, check: bool = False) -> SegmentReceipt:
         """Seal a segment whose code/data traces live in pinned HOST memory (hal.host_alloc views): enqueue both uploads
         on the context's stream (no host sync), then run the two-halves seal.  This is the PCIe-inclusive path.  A circuit whose
         arguments derive sorted copies, columns, linked accesses or lookup multiplicities gets them filled into the data trace first, in
         that order (zkh_derive_sorted, zkh_derive_columns, zkh_derive_links, zkh_derive_multiplicities: a record or a lookup may read
         a sorted column, and the multiplicities count the derived limbs); of those columns only the blinding rows are uploaded (zkh_upload_data_trace).  The accum
-        comes from the built-in generator of kinds 1..3, else from zkh_accumulate when the circuit carries arguments."""
+        comes from the built-in generator of kinds 1..3, else from zkh_accumulate when the circuit carries arguments.
+        check: check the finished witness row by row before the seal is spent on it (check_witness, seal_with_accum)."""
         code = self.hal.alloc_elem("code", host_code.size)
         data = self.hal.alloc_elem("data", host_data.size)
         self.hal.write_async(code, host_code)
@@ -273,7 +293,7 @@ class SegmentProver:
             self.hal.derive_multiplicities(self.circuit, seg.po2, seg.zk_cycles, code, data)
         builtin = 1 <= int(self.circuit.desc[13]) <= 3
         acc = self.args_accumulate(seg, code, data) if not builtin and self.circuit.has_arguments() else self.syn_accumulate(seg, data)
-        return self.seal_with_accum(seg, code, data, out_global, acc)
+        return self.seal_with_accum(seg, code, data, out_global, acc, check=check)
 
     def prove_segment(self, seg: Segment) -> SegmentReceipt:
         code, data, out = self.witgen(seg)
