@@ -230,6 +230,29 @@ typedef struct { int64_t row; uint32_t step; uint32_t failing_rows; uint32_t val
 const char* zkh_check_rows(zkh_ctx*, const zkh_circuit*, size_t po2, const zkh_buf* const* groups, size_t n_groups,
                            const uint32_t* out_global, const uint32_t* mix_global, size_t row_lo, size_t row_hi, zkh_buf* per_row,
                            zkh_check_rows_result* result);
+/* A witness's bus checked key by key on the device (csrc/bus.hip; DESIGN.md §2 CHECK BUS; host twin: circuits/logup.py reference_bus):
+ * which key does not balance, when zkh_accumulate (below) would only say "the bus does not balance".  Needs a circuit with arguments
+ * and the RAW code and data traces of 2^po2 rows, A = 2^po2 - zk_cycles active; no mix, no accum.
+ * An ENTRY is a (term i, row r < A) of non-zero weight w_i(r) = sel_i(r) m_i(r) in Fp (both read as residues, an absent one is 1: the
+ * accumulate's numerator; a selector is a field value here, nothing is refused).  Its KEY is (tag, v_0 .. v_3) as residues, the tuple
+ * zero-padded to 4 — the accumulate's denominator, so (x) and (x, 0) are one key.  net(K) = sum over K's entries of sign_i w_i(r) in
+ * Fp; K is UNBALANCED when net(K) != 0.  Distinct keys are distinct poles: the bus can balance for a mix only by chance unless every
+ * net is 0, and balances for every mix when they all are.  The representative of a key is its entry of smallest (blob term index,
+ * row) over all terms.
+ * result: term, row = the representative of the unbalanced key whose representative is smallest (-1, -1: every key balances; tag, key,
+ * net are then 0), tag, key = that key (canonical), net = its net (canonical), unbalanced_keys, distinct_keys, slots = the final size
+ * of the key table: the smallest power of two >= max(64, 2 A), doubled until it is at least twice distinct_keys.
+ * per_term (NULL, or n_terms records, n_terms the blob's): record i = what term i holds of the reported key: count of entries, their
+ * first and last row, weight = the sum of w_i(r) over them in Fp (unsigned; the sign is the term's).  A term without such an entry, and
+ * every term when nothing is unbalanced, gets count 0, rows 0xffffffff, weight 0.
+ * An unbalanced bus is an ANSWER: the call returns NULL either way.  It fails only for bad shapes, a circuit without arguments, a
+ * missing code trace, a circuit loaded on another context, more distinct keys than a table of 2^31 slots holds, and n_terms x A >= 2^33
+ * (a counter could wrap).  Reads code and data, writes neither. */
+typedef struct { int64_t row; int32_t term; uint32_t tag; uint32_t key[4]; uint32_t net; uint32_t unbalanced_keys; uint32_t distinct_keys;
+                 uint32_t slots; } zkh_check_bus_result;
+typedef struct { uint32_t count; uint32_t first_row; uint32_t last_row; uint32_t weight; } zkh_bus_term;
+const char* zkh_check_bus(zkh_ctx*, const zkh_circuit*, size_t po2, size_t zk_cycles, const zkh_buf* code, const zkh_buf* data,
+                          zkh_bus_term* per_term, size_t n_terms, zkh_check_bus_result* result);
 
 /* ---- CircuitHal::accumulate for arguments described as data (csrc/accumulate.hip; zeth_amd/circuits/logup.py) ----
  * Lookup and permutation arguments as log-derivative sums: a ZKA1 blob lists terms t(r) = sign sel(r) m(r) / (alpha - (tag + beta v_0(r)

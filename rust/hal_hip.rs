@@ -394,6 +394,21 @@ impl HipCircuitHal {
         res
     }
 
+    /// Check the bus of the circuit's arguments key by key on the raw traces (`zkh_check_bus`): which key does not balance, when
+    /// `accumulate` would only say that the bus does not.  No mix and no accum are involved.  `term < 0`: every key balances; otherwise
+    /// the representative (lowest blob term index, then row) of the unbalanced key whose representative is lowest, the key, its net in
+    /// Fp and how many of the distinct keys do not balance.  `per_term` (one record per term of the blob) receives what every term
+    /// holds of that key: entries, first and last row, weight.  An unbalanced bus is an answer; it panics only on bad shapes, a circuit
+    /// without arguments, or more keys than its table holds.
+    pub fn check_bus(&self, ctrl: &HipBuffer<BabyBearElem>, data: &HipBuffer<BabyBearElem>, steps: usize,
+                     per_term: Option<&mut [sys::ZkhBusTerm]>) -> sys::ZkhCheckBusResult {
+        let po2 = steps.trailing_zeros() as usize;
+        let mut res = sys::ZkhCheckBusResult { row: -1, term: -1, tag: 0, key: [0; 4], net: 0, unbalanced_keys: 0, distinct_keys: 0, slots: 0 };
+        let (terms, n_terms) = per_term.map_or((std::ptr::null_mut(), 0), |t| (t.as_mut_ptr(), t.len()));
+        ffi(|| unsafe { sys::zkh_check_bus(self.hal.ctx.0, self.circuit, po2, sys::ZK_CYCLES, ctrl.raw, data.raw, terms, n_terms, &mut res) });
+        res
+    }
+
     /// The data columns that the four derives write on the active rows, ascending (`zkh_circuit_derived_data_columns`).
     pub fn derived_data_columns(&self) -> Vec<u32> {
         let mut n = 0usize;

@@ -5,7 +5,9 @@ against the host's lexsort + upload; M13: derived columns — the 64 limb column
 bytes, and the host-witness seal with its upload; M14: linked accesses of SYN-LOOKUP-linked (zkh_derive_links) next to a plain copy of
 the same bytes, to the host's sort + gather + upload, and the host-witness seal with the derive against the host-made columns; M14r: the read rule, zkh_derive_links on SYN-LOOKUP-reads
 under its version-6 blob next to the same trace under the version-5 blob; M15: zkh_check_rows, the row-by-row constraint check of an honest
-SYN-A / SYN-HEAVY witness, next to zkh_eval_check on the step interpreter for the same circuit in the same run, alternating) on one
+SYN-A / SYN-HEAVY witness, next to zkh_eval_check on the step interpreter for the same circuit in the same run, alternating; M16:
+zkh_check_bus, the key-by-key bus check of the honest SYN-LOOKUP FULL witness, with and without its per-term pass, next to zkh_accumulate
+and zkh_derive_multiplicities on the same trace in the same run, alternating) on one
 MI355X, through the C ABI (HipHal).
 
 Each line of output is one JSON object: the op, its shape, the average wall time of one call (stream drained on both
@@ -512,6 +514,61 @@ def main() -> None:
                               "check_rows_trace_GB": round(4 * total_w * n / 1e9, 4), "eval_check_domain_GB": round(4 * total_w * dom / 1e9, 4),
                               "check_rows_vs_eval_check_interp": round(float(np.median(t_rows)) / float(np.median(t_eval)), 4)}), flush=True)
             del groups, globals_, check, accum, code, data, prover
+    if want("M16"):
+        # the key-by-key bus check (zkh_check_bus) of the honest SYN-LOOKUP FULL witness under its derived blob, next to its yardsticks on
+        # the same trace in the same run: zkh_accumulate (the call whose refusal it explains) and zkh_derive_multiplicities (the other
+        # keyed table over the trace).  The per-term pass runs only on an unbalanced bus: it is forced by a second data trace in which
+        # one table multiplicity is raised by one (one cell: the build and the scan cost what they cost on the honest trace).  The four
+        # are timed in alternation, `runs` windows of `reps` calls each; median and spread (min, max) of the windows.  check_bus is a
+        # whole call: its terms' upload, the table's clearing, build, scan and the read-backs.
+        from zeth_amd.circuits import logup, syn_lookup
+        runs, zk = 7, 1994
+        A = n - zk
+        shape = syn_lookup.FULL
+        desc, blob = syn_lookup.build_syn_lookup(shape, derive=True)
+        a = logup.Arguments.parse(blob)
+        circuit = hal.load_circuit(desc, jit=False)
+        circuit.set_arguments(blob)
+        code_h, data_h, _out = syn_lookup.witness(shape, args.po2, zk, seed=16)
+        m_col = syn_lookup.layout(shape.n_words, shape.n_limbs, shape.n_mem)[2]
+        forged_h = data_h.copy()
+        forged_h[m_col * n + 7] = (int(forged_h[m_col * n + 7]) + (1 << 32) % P) % P
+        code, data, forged = (hal.alloc_elem(nm, h.size) for nm, h in (("code", code_h), ("data", data_h), ("forged", forged_h)))
+        for b, h in ((code, code_h), (data, data_h), (forged, forged_h)):
+            b.write(h)
+        mix = rand_fp(rng, 8)
+        accum = hal.alloc_elem("accum", 4 * a.k * n)
+        bus_fn = lambda: hal.check_bus(circuit, args.po2, zk, code, data)                                   # noqa: E731
+        per_fn = lambda: hal.check_bus(circuit, args.po2, zk, code, forged, per_term=True)                  # noqa: E731
+        acc_fn = lambda: hal.accumulate(circuit, args.po2, zk, 0x2E80, code, data, mix, accum)              # noqa: E731
+        der_fn = lambda: hal.derive_multiplicities(circuit, args.po2, zk, code, data)                       # noqa: E731  (rewrites what is there)
+        found, named = bus_fn(), per_fn()
+        assert found["row"] == -1 and found["unbalanced_keys"] == 0, found
+        assert named["unbalanced_keys"] == 1 and named["key"] == (7, 0, 0, 0) and named["net"] == P - 1, named
+        start = logup.bus_slots(A, 0)
+        t = {"check_bus": [], "check_bus_per_term": [], "accumulate": [], "derive_multiplicities": []}
+        for _ in range(runs):
+            for name, fn in (("check_bus", bus_fn), ("accumulate", acc_fn), ("check_bus_per_term", per_fn), ("derive_multiplicities", der_fn)):
+                t[name].append(timed(hal, fn, args.reps))
+        assert np.array_equal(data.to_vec(), data_h)
+        hal.prof_enable(True)
+        hal.prof_reset()
+        for _ in range(args.reps):
+            per_fn()
+        hal.sync()
+        steps = {r["name"]: round(r["total_ms"] / max(r["calls"], 1), 4) for r in hal.prof_get() if r["calls"] and r["name"].startswith("bus_")}
+        hal.prof_enable(False)
+        spread = lambda ts: {"median_ms": round(float(np.median(ts)) * 1e3, 4), "min_ms": round(min(ts) * 1e3, 4), "max_ms": round(max(ts) * 1e3, 4)}   # noqa: E731
+        med = {k: float(np.median(v)) for k, v in t.items()}
+        print(json.dumps({"bench": "M16", "circuit": "SYN-LOOKUP FULL (derived blob)", "library": os.path.basename(os.environ.get("ZKH_LIBRARY", "") or "libzkhal_mi355x.so"),
+                          "po2": args.po2, "terms": len(a.terms), "entries": len(a.terms) * A - (A - (1 << shape.limb_bits)),
+                          "runs": runs, "reps": args.reps, **{k: spread(v) for k, v in t.items()}, "kernels_ms_per_term_call": steps,
+                          "distinct_keys": found["distinct_keys"], "slots": found["slots"], "start_slots": start,
+                          "growths": int(np.log2(found["slots"] // start)), "table_bytes": 24 * found["slots"],
+                          "check_bus_vs_accumulate": round(med["check_bus"] / med["accumulate"], 3),
+                          "check_bus_vs_derive_multiplicities": round(med["check_bus"] / med["derive_multiplicities"], 3),
+                          "per_term_vs_check_bus": round(med["check_bus_per_term"] / med["check_bus"], 3)}), flush=True)
+        del code, data, forged, accum
     hal.close()
 
 

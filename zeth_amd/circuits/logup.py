@@ -1110,3 +1110,111 @@ def reference_links(args: Arguments, po2: int, zk_cycles: int, code, data) -> np
         for j, c in enumerate(r.limbs):
             out[c, rows] = _enc((d >> (j * L)) & ((1 << L) - 1)).astype(np.uint32)
     return out.reshape(-1)
+
+
+def bus_slots(A: int, distinct_keys: int) -> int:
+    """the size zkh_check_bus's key table ends at: the smallest power of two >= max(64, 2 A), doubled until it is at least twice the
+    number of distinct keys (the table holds one slot per key and stays at most half full)"""
+    slots = 64
+    while slots < 2 * A:
+        slots <<= 1
+    while 2 * distinct_keys > slots:
+        slots <<= 1
+    return slots
+
+
+def reference_bus(args: Arguments, po2: int, zk_cycles: int, code, data) -> dict:
+    """CHECK BUS (DESIGN.md §2 ARGUMENTS), the definition zkh_check_bus computes on the device: which key of the bus does not balance.
+    No mix, no accum.  An entry is a (term i, row r < A) of non-zero weight w_i(r) = sel_i(r) m_i(r) in Fp (residues; absent = 1: the
+    numerator of the accumulate); its key is (tag, v_0 .. v_3), canonical, the tuple zero-padded (`_canonical_key`); net(K) = the sum of
+    sign_i w_i(r) over the entries of K in Fp, and K is unbalanced when net(K) != 0.  Distinct keys are distinct poles, so the bus
+    balances for every mix exactly when every net is 0.  The representative of a key is its entry of smallest (blob term index, row),
+    over all terms; the unbalanced key of smallest representative is the one reported.
+    -> {"term", "row": that representative (-1, -1: every key balances; tag, key, net are then 0), "tag", "key": 4 canonical words,
+    "net", "unbalanced_keys", "distinct_keys", "slots" (`bus_slots`), "per_term": an (n_terms, 4) int64 array, per blob term the
+    (count, first_row, last_row, weight) of its entries of the reported key, weight their sum of w_i(r) in Fp, unsigned; (0, -1, -1, 0)
+    for a term without one} — the dict of HipHal.check_bus(per_term=True)."""
+    n = 1 << po2
+    A = n - zk_cycles
+    terms = Arguments.parse(args.blob()).terms                               # blob order: the term index of the representative rule
+    groups = {GROUP_CODE: np.asarray(code, dtype=np.uint32).reshape(-1, n), GROUP_DATA: np.asarray(data, dtype=np.uint32).reshape(-1, n)}
+    rows = np.arange(A)
+    keys, who, weight, sign = [], [], [], []
+    for i, t in enumerate(terms):
+        w = np.ones(A, dtype=np.uint64)
+        if t.sel is not None:
+            w = _m(w, _dec(groups[GROUP_CODE][t.sel, :A]))
+        if t.mult is not None:
+            w = _m(w, _dec(groups[t.mult[0]][t.mult[1], :A]))
+        live = rows[w != 0]
+        keys.append(_canonical_key(terms, groups, i, live))
+        who.append((np.uint64(i) << np.uint64(32)) | live.astype(np.uint64))
+        weight.append(w[live])
+        sign.append(np.full(live.size, t.sign == -1))
+    keys, who, weight, neg = np.concatenate(keys), np.concatenate(who), np.concatenate(weight), np.concatenate(sign)
+    per_term = np.zeros((len(terms), 4), dtype=np.int64)
+    per_term[:, 1:3] = -1
+    out = {"term": -1, "row": -1, "tag": 0, "key": (0, 0, 0, 0), "net": 0, "unbalanced_keys": 0, "distinct_keys": 0,
+           "slots": bus_slots(A, 0), "per_term": per_term}
+    if not len(keys):
+        return out
+    uk, inv = np.unique(keys, axis=0, return_inverse=True)
+    inv = inv.reshape(-1)
+    total = np.zeros((2, len(uk)), dtype=np.uint64)                          # at most n_terms * A < 2^33 adds below 2^31: no wrap
+    np.add.at(total[0], inv[~neg], weight[~neg])
+    np.add.at(total[1], inv[neg], weight[neg])
+    net = (total[0] % np.uint64(P) + np.uint64(P) - total[1] % np.uint64(P)) % np.uint64(P)
+    rep = np.full(len(uk), np.iinfo(np.uint64).max, dtype=np.uint64)
+    np.minimum.at(rep, inv, who)
+    bad = np.nonzero(net != 0)[0]
+    out.update(distinct_keys=len(uk), unbalanced_keys=len(bad), slots=bus_slots(A, len(uk)))
+    if not len(bad):
+        return out
+    k = int(bad[np.argmin(rep[bad])])
+    out.update(term=int(rep[k]) >> 32, row=int(rep[k]) & 0xFFFFFFFF, tag=int(uk[k, 0]), key=tuple(int(x) for x in uk[k, 1:]), net=int(net[k]))
+    mine = inv == k
+    for i in np.unique(who[mine] >> np.uint64(32)):
+        of = mine & (who >> np.uint64(32) == i)
+        r = (who[of] & np.uint64(0xFFFFFFFF)).astype(np.int64)
+        per_term[int(i)] = (r.size, r.min(), r.max(), int(weight[of].sum() % np.uint64(P)))
+    return out
+
+
+BUS_LINE_TERMS = 8
+
+
+def describe_bus(bus: dict, args: Arguments) -> Optional[str]:
+    """the one line that words what `reference_bus` / HipHal.check_bus(per_term=True) found, None when every key balances:
+
+        bus: key (tag T; v0, v1, v2, v3) does not balance, net N: term i (+, sel code[c], m data[c]) has k entries, rows r0..r1, weight
+        w; term j (−, …) has none; U of D keys do not balance
+
+    The terms are those of the key's tag, blob indices: first the ones that hold entries of the key, the sign with fewer holders first
+    (a table before its many lookups), then the ones that hold none and whose sign no holder has (the side that is missing: the table
+    that never held the value, the store that never happened), then the other ones that hold none; each group in blob order; at most
+    BUS_LINE_TERMS terms, then "… and m more"."""
+    if bus["row"] < 0:
+        return None
+    terms = Arguments.parse(args.blob()).terms
+    table = bus["per_term"]
+    same = [i for i, t in enumerate(terms) if t.tag % P == bus["tag"]]
+    holders = [i for i in same if table[i][0]]
+    signs = {terms[i].sign for i in holders}
+    of_sign = {sg: sum(terms[j].sign == sg for j in holders) for sg in signs}
+    holders.sort(key=lambda i: (of_sign[terms[i].sign], i))
+    order = holders + [i for i in same if not table[i][0] and terms[i].sign not in signs] + \
+        [i for i in same if not table[i][0] and terms[i].sign in signs]
+    group = {GROUP_CODE: "code", GROUP_DATA: "data"}
+    parts = []
+    for i in order[:BUS_LINE_TERMS]:
+        t = terms[i]
+        what = ["+" if t.sign == 1 else "−"] + ([f"sel code[{t.sel}]"] if t.sel is not None else []) + \
+            ([f"m {group[t.mult[0]]}[{t.mult[1]}]"] if t.mult is not None else [])
+        count, first, last, weight = (int(x) for x in table[i])
+        has = f"has {count} entr{'y' if count == 1 else 'ies'}, rows {first}..{last}, weight {weight}" if count else "has none"
+        parts.append(f"term {i} ({', '.join(what)}) {has}")
+    if len(order) > BUS_LINE_TERMS:
+        parts.append(f"… and {len(order) - BUS_LINE_TERMS} more")
+    key = ", ".join(str(x) for x in bus["key"])
+    return (f"bus: key (tag {bus['tag']}; {key}) does not balance, net {bus['net']}: " + "; ".join(parts) +
+            f"; {bus['unbalanced_keys']} of {bus['distinct_keys']} keys do not balance")

@@ -18,8 +18,8 @@
 //       the adds go straight to the global counters.  The host picks the path from U, read back after the build;
 //   (c) k_derive_write: one lane per (derived term, active row) writes the count of its key on the representative, 0 elsewhere.
 // A table selector other than 0 / 1 (after the build) or a lookup of nonzero weight without a table entry (after the count) refuses
-// the witness before (c): `data` is left unchanged.
-#include "arguments.h"
+// the witness before (c): `data` is left unchanged.  The key, its hash and the probe are keytable.h's, shared with bus.hip.
+#include "keytable.h"
 
 #include <algorithm>
 
@@ -27,59 +27,9 @@ using namespace zkh;
 
 namespace {
 
-constexpr unsigned long long SLOT_EMPTY = ~0ull;
 constexpr uint32_t DERIVE_THREADS = 256;
 constexpr uint32_t LDS_KEYS = 4096;              // u64 counters per workgroup in the LDS path: 32 KiB
 constexpr uint32_t COUNT_BLOCKS = 1024;          // workgroups of the count (4 per CU); each loops over every lookup term
-
-struct KeyTerm {                                 // a derived or lookup term as the derive kernels read it
-    uint32_t tag;                                // canonical
-    TermCols c;
-};
-struct Key { uint32_t v[MAX_TUPLE]; };
-
-__device__ __forceinline__ Key read_key(const uint32_t* code, const uint32_t* data, const KeyTerm& t, uint32_t n, uint32_t r) {
-    Key k;
-#pragma unroll
-    for (uint32_t e = 0; e < MAX_TUPLE; e++) k.v[e] = e < t.c.w ? cell(code, data, t.c.tg[e], t.c.tc[e], n, r) : 0;
-    return k;
-}
-__device__ __forceinline__ uint32_t key_hash(uint32_t tag, const Key& k) {
-    uint64_t h = (tag + 1) * 0x9e3779b97f4a7c15ull;
-#pragma unroll
-    for (uint32_t e = 0; e < MAX_TUPLE; e++) {
-        h = (h ^ k.v[e]) * 0xff51afd7ed558ccdull;
-        h ^= h >> 32;
-    }
-    return (uint32_t)h;
-}
-// does the entry in a slot have the key (tag, k)?  Its key is re-read from the trace.
-__device__ __forceinline__ bool slot_has_key(const uint32_t* code, const uint32_t* data, const KeyTerm* terms, unsigned long long entry,
-                                             uint32_t tag, const Key& k, uint32_t n) {
-    const KeyTerm& o = terms[entry >> 32];
-    if (o.tag != tag) return false;
-    const Key ok = read_key(code, data, o, n, (uint32_t)entry);
-    bool eq = true;
-#pragma unroll
-    for (uint32_t e = 0; e < MAX_TUPLE; e++) eq &= ok.v[e] == k.v[e];
-    return eq;
-}
-// the slot of key (tag, k), or NONE if it has no entry (the table always has empty slots: the probe ends)
-__device__ __forceinline__ uint32_t find_slot(const uint32_t* code, const uint32_t* data, const KeyTerm* terms, const unsigned long long* slots,
-                                              uint32_t mask, uint32_t tag, const Key& k, uint32_t n) {
-    for (uint32_t s = key_hash(tag, k) & mask;; s = (s + 1) & mask) {
-        const unsigned long long cur = slots[s];
-        if (cur == SLOT_EMPTY) return NONE;
-        if (slot_has_key(code, data, terms, cur, tag, k, n)) return s;
-    }
-}
-// weight of a term's row as a canonical residue: sel * m (absent = 1)
-__device__ __forceinline__ uint32_t row_weight(const uint32_t* code, const uint32_t* data, const KeyTerm& t, uint32_t n, uint32_t r) {
-    uint32_t w = R1;                             // Montgomery words from here on
-    if (t.c.sel != NONE) w = cell(code, data, GROUP_CODE, t.c.sel, n, r);
-    if (t.c.mg != NONE) w = mul_mod(w, cell(code, data, t.c.mg, t.c.mc, n, r));
-    return fp_decode(Fp::raw(w));
-}
 
 // status words: [0, 2) the first lookup without a table entry (row << 32 | term), [2, 4) the first bad table selector (the same form),
 // [4] U = distinct keys

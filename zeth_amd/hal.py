@@ -88,6 +88,17 @@ class CheckRowsResult(C.Structure):
     _fields_ = [("row", C.c_int64), ("step", C.c_uint32), ("failing_rows", C.c_uint32), ("value", C.c_uint32 * 4)]
 
 
+class CheckBusResult(C.Structure):
+    """`zkh_check_bus_result`: what zkh_check_bus found (term, row -1: every key balances)."""
+    _fields_ = [("row", C.c_int64), ("term", C.c_int32), ("tag", C.c_uint32), ("key", C.c_uint32 * 4), ("net", C.c_uint32),
+                ("unbalanced_keys", C.c_uint32), ("distinct_keys", C.c_uint32), ("slots", C.c_uint32)]
+
+
+class BusTerm(C.Structure):
+    """`zkh_bus_term`: what one term holds of the key zkh_check_bus reports (count 0: nothing; the rows are then 0xffffffff)."""
+    _fields_ = [("count", C.c_uint32), ("first_row", C.c_uint32), ("last_row", C.c_uint32), ("weight", C.c_uint32)]
+
+
 ABI = {
     "zkh_free_error": (None, [_vp]),
     "zkh_version": (C.c_char_p, []),
@@ -146,6 +157,7 @@ ABI = {
     "zkh_circuit_compiled_parts": (_sz, [_vp]),
     "zkh_eval_check": (_err, [_vp, _vp, _vp, C.POINTER(_vp), _sz, C.POINTER(_vp), _sz, _u32p, _sz, _sz, _i]),
     "zkh_check_rows": (_err, [_vp, _vp, _sz, C.POINTER(_vp), _sz, _u32p, _u32p, _sz, _sz, _vp, C.POINTER(CheckRowsResult)]),
+    "zkh_check_bus": (_err, [_vp, _vp, _sz, _sz, _vp, _vp, C.POINTER(BusTerm), _sz, C.POINTER(CheckBusResult)]),
     "zkh_syn_code": (_err, [_vp, _vp, _sz, _sz, _vp]),
     "zkh_sha256": (None, [C.c_char_p, _sz, C.POINTER(C.c_uint8)]),
     "zkh_session_check_termination": (_err, [_vp, C.POINTER(_u32p), C.POINTER(_sz), _sz, C.c_char_p, _sz]),
@@ -842,6 +854,25 @@ class HipHal:
                                    (1 << po2) if row_hi is None else row_hi, rows.h if rows is not None else None, C.byref(res)))
         return {"row": int(res.row), "step": int(res.step), "failing_rows": int(res.failing_rows), "value": tuple(int(x) for x in res.value),
                 "per_row": rows.to_vec() if rows is not None else None}
+
+    def check_bus(self, circuit: Circuit, po2: int, zk_cycles: int, code: Buffer, data: Buffer, per_term: bool = False) -> dict:
+        """the bus of a circuit with arguments checked key by key on the RAW traces (zkh_check_bus; the definition: circuits/logup.py
+        reference_bus, which returns the same dict).  -> {"term", "row": the representative of the reported unbalanced key, or -1, -1,
+        "tag", "key": its four canonical tuple words, "net", "unbalanced_keys", "distinct_keys", "slots", "per_term": None, or with
+        per_term=True an (n_terms, 4) int64 array of (count, first_row, last_row, weight) of the reported key's entries per blob term,
+        (0, -1, -1, 0) for a term without one}.  An unbalanced bus is an answer, not an error (circuits.logup.describe_bus words it)."""
+        n_terms = int(circuit._args[5]) if getattr(circuit, "_args", None) is not None and circuit._args.size > 5 else 0
+        terms = (BusTerm * max(1, n_terms))() if per_term else None
+        res = CheckBusResult()
+        _check(_lib.zkh_check_bus(self.ctx, circuit.h, po2, zk_cycles, code.h if code is not None else None, data.h, terms, n_terms,
+                                  C.byref(res)))
+        table = None
+        if per_term:
+            table = np.array([[t.count, t.first_row if t.count else -1, t.last_row if t.count else -1, t.weight] for t in terms[:n_terms]],
+                             dtype=np.int64).reshape(n_terms, 4)
+        return {"term": int(res.term), "row": int(res.row), "tag": int(res.tag), "key": tuple(int(x) for x in res.key), "net": int(res.net),
+                "unbalanced_keys": int(res.unbalanced_keys), "distinct_keys": int(res.distinct_keys), "slots": int(res.slots),
+                "per_term": table}
 
     def upload_data_trace(self, circuit: Circuit, po2: int, zk_cycles: int, data: Buffer, host: np.ndarray, pinned_async: bool = True) -> None:
         """upload a caller's data trace without what the library derives (zkh_upload_data_trace): the other columns whole, the derived

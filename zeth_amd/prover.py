@@ -223,6 +223,18 @@ class SegmentProver:
         raise _hal.HalError(f"witness: row {r['row']} fails constraint step {r['step']} (value {value}; reads "
                             f"{_check_rows.describe_reads(self.circuit.desc, r['step'])}; {r['failing_rows']} rows fail)")
 
+    def check_bus(self, seg: Segment, code, data) -> None:
+        """Check the bus of a circuit with arguments key by key on the raw traces (zkh_check_bus; no mix, no accum, no seal): raises
+        HalError with the one line of circuits/logup.py describe_bus — the key that does not balance, its net, and what every term of
+        its tag holds of it — and returns quietly when every key balances."""
+        from .circuits import logup as _logup
+        if code is None:
+            raise _hal.HalError("check_bus: the arguments read the raw code trace; it is not held (resident code group)")
+        found = self.hal.check_bus(self.circuit, seg.po2, seg.zk_cycles, code, data, per_term=True)
+        line = _logup.describe_bus(found, _logup.Arguments.parse(self.circuit._args))
+        if line:
+            raise _hal.HalError(line)
+
     def seal_with_accum(self, seg: Segment, code, data, out_global,
                         accumulate: Callable[[np.ndarray], "_hal.Buffer"], check: bool = False) -> SegmentReceipt:
         """The same seal through the circuit-agnostic halves: zkh_prove_begin (header, code, data -> mix challenges),
@@ -258,16 +270,26 @@ class SegmentProver:
             return accum
         return acc
 
-    def args_accumulate(self, seg: Segment, code, data):
+    def args_accumulate(self, seg: Segment, code, data, check: bool = False):
         """`accumulate` callback for a circuit with arguments (zkh_accumulate over the raw code and data traces): refuses a witness
-        whose denominators vanish or whose bus does not balance (HalError)"""
+        whose denominators vanish or whose bus does not balance (HalError).  check: after a "does not balance" refusal run check_bus
+        and raise the accumulate's message followed by the bus line; a witness that is accepted costs nothing more."""
         wa = self.group_sizes()[0]
         if code is None:
             raise _hal.HalError("args_accumulate: the arguments read the raw code trace; it is not held (resident code group)")
 
         def acc(mix_global):
             accum = self.hal.alloc_elem("accum", wa << seg.po2)
-            self.hal.accumulate(self.circuit, seg.po2, seg.zk_cycles, seg.noise_seed, code, data, mix_global, accum)
+            try:
+                self.hal.accumulate(self.circuit, seg.po2, seg.zk_cycles, seg.noise_seed, code, data, mix_global, accum)
+            except _hal.HalError as refusal:
+                if not check or "does not balance" not in str(refusal):
+                    raise
+                try:
+                    self.check_bus(seg, code, data)
+                except _hal.HalError as bus:
+                    raise _hal.HalError(f"{refusal}; {bus}") from None
+                raise
             return accum
         return acc
 
@@ -278,7 +300,8 @@ class SegmentProver:
         that order (zkh_derive_sorted, zkh_derive_columns, zkh_derive_links, zkh_derive_multiplicities: a record or a lookup may read
         a sorted column, and the multiplicities count the derived limbs); of those columns only the blinding rows are uploaded (zkh_upload_data_trace).  The accum
         comes from the built-in generator of kinds 1..3, else from zkh_accumulate when the circuit carries arguments.
-        check: check the finished witness row by row before the seal is spent on it (check_witness, seal_with_accum)."""
+        check: check the finished witness row by row before the seal is spent on it (check_witness, seal_with_accum), and when
+        zkh_accumulate refuses a bus that does not balance, name the key (check_bus, args_accumulate)."""
         code = self.hal.alloc_elem("code", host_code.size)
         data = self.hal.alloc_elem("data", host_data.size)
         self.hal.write_async(code, host_code)
@@ -292,7 +315,7 @@ class SegmentProver:
         if self.circuit.derives_multiplicities():
             self.hal.derive_multiplicities(self.circuit, seg.po2, seg.zk_cycles, code, data)
         builtin = 1 <= int(self.circuit.desc[13]) <= 3
-        acc = self.args_accumulate(seg, code, data) if not builtin and self.circuit.has_arguments() else self.syn_accumulate(seg, data)
+        acc = self.args_accumulate(seg, code, data, check=check) if not builtin and self.circuit.has_arguments() else self.syn_accumulate(seg, data)
         return self.seal_with_accum(seg, code, data, out_global, acc, check=check)
 
     def prove_segment(self, seg: Segment) -> SegmentReceipt:
