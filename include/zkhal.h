@@ -274,8 +274,7 @@ const char* zkh_accumulate(zkh_ctx*, const zkh_circuit*, size_t po2, size_t zk_c
  * (blob term index, row)) the number of lookups of that key (the sum of their sel * m, in Fp, Montgomery form), 0 on every other
  * active row; the blinding rows are not touched.  Keys are (tag, v_0 .. v_3) compared as field elements, the tuple zero-padded.  It
  * FAILS and leaves `data` unchanged when a table selector is neither 0 nor 1, or when a lookup of nonzero weight has no table entry
- * (the error names the term, tag, row and key).  Call it after the data upload and before zkh_prove_begin: the multiplicities belong
- * to the data group.  Sessions with caller traces and SegmentProver.seal_host_witness do so when the circuit derives. */
+ * (the error names the term, tag, row and key).  zkh_derive_all (below) runs it in its place, last. */
 int zkh_circuit_derives_multiplicities(const zkh_circuit*);
 const char* zkh_derive_multiplicities(zkh_ctx*, const zkh_circuit*, size_t po2, size_t zk_cycles, const zkh_buf* code, zkh_buf* data);
 /* Derived sorted copies (ZKA1 version 3: term word 7 bit 1 marks a term D as the sorted copy of its source term S; bits 4..6 = nkeys
@@ -287,9 +286,7 @@ const char* zkh_derive_multiplicities(zkh_ctx*, const zkh_circuit*, size_t po2, 
  * (lexicographic, equal keys keep their row order), zkh_derive_sorted writes data[D.v_e][r_j] = the raw word of S.v_e at r_pi(j) for
  * every tuple position e, 0 on the active rows whose selector is 0; the blinding rows are not touched.  The result depends on the
  * traces alone (no atomic arrival order enters it).  It FAILS and leaves `data` unchanged when a selector is neither 0 nor 1 (the
- * error names the term and the row).  Call it after the data upload, BEFORE zkh_derive_multiplicities (a lookup may range-check a
- * sorted column) and before zkh_prove_begin.  Sessions with caller traces and SegmentProver.seal_host_witness do so when the circuit
- * derives sorted copies. */
+ * error names the term and the row).  zkh_derive_all (below) runs it in its place, first. */
 int zkh_circuit_derives_sorted(const zkh_circuit*);
 const char* zkh_derive_sorted(zkh_ctx*, const zkh_circuit*, size_t po2, size_t zk_cycles, const zkh_buf* code, zkh_buf* data);
 /* Derived columns (ZKA1 version 4: header word 6 = n_records, and n_records records of 16 words follow the terms: kind (1 = LIMBS,
@@ -303,9 +300,8 @@ const char* zkh_derive_sorted(zkh_ctx*, const zkh_circuit*, size_t po2, size_t z
  * never chain); it may be a sorted copy's column.  Destinations are data columns that nothing else writes, that no record and no
  * source term of a sorted copy reads and that no term uses as its multiplicity; lookup tuples read them freely.  It FAILS and leaves
  * `data` unchanged — the error names the lowest (record, row) and the value — when a LIMBS value or an ORDER difference does not fit
- * L nl bits, or when an ORDER difference is negative ("not ordered").  Call it AFTER zkh_derive_sorted (a record may read a sorted
- * column) and BEFORE zkh_derive_multiplicities (the limbs are lookups to be counted).  Like its siblings it is an error on a circuit
- * without records.  Sessions with caller traces and SegmentProver.seal_host_witness call the three in that order. */
+ * L nl bits, or when an ORDER difference is negative ("not ordered").  Like its siblings it is an error on a circuit without records.
+ * zkh_derive_all (below) runs it in its place, second. */
 int zkh_circuit_derives_columns(const zkh_circuit*);
 const char* zkh_derive_columns(zkh_ctx*, const zkh_circuit*, size_t po2, size_t zk_cycles, const zkh_buf* code, zkh_buf* data);
 /* Linked accesses (ZKA1 version 5: a record of kind 3 = LINK takes 32 words and follows every LIMBS / ORDER record: kind, L = limb bits
@@ -323,9 +319,8 @@ const char* zkh_derive_columns(zkh_ctx*, const zkh_circuit*, size_t po2, size_t 
  * that no record and no source term of a sorted copy reads; lookup tuples read them freely, and linked and last (only they) may be
  * the multiplicity of a term that is not derived.  It FAILS and leaves `data` unchanged when a selector is neither 0 nor 1 (checked
  * over all records before any clock), when d < 0 ("clock not increasing") or when d >= 2^(L nl); the error names the lowest (record,
- * row) and the values.  Call it AFTER zkh_derive_columns and BEFORE zkh_derive_multiplicities (the limbs are lookups to be counted).
- * Like its siblings it is an error on a circuit without LINK records.  Sessions with caller traces and
- * SegmentProver.seal_host_witness call the four in the order sorted, columns, links, multiplicities.
+ * row) and the values.  Like its siblings it is an error on a circuit without LINK records.  zkh_derive_all (below) runs it in its
+ * place, third.
  * The read rule (ZKA1 version 6; versions 1..5 are word for word what they were): LINK word 5 is a flag word, bit 0 = READS, every other
  * bit refused; with READS words 14, 15 are the (group, column) of the write flag w, a source of the record like the key and the carried
  * columns, and nc >= 2; without READS they are 0.  Header word 7 = the number of LINK records with READS: a version-6 blob in which it
@@ -339,6 +334,14 @@ const char* zkh_derive_columns(zkh_ctx*, const zkh_circuit*, size_t po2, size_t 
 int zkh_circuit_derives_links(const zkh_circuit*);
 int zkh_circuit_links_check_reads(const zkh_circuit*);
 const char* zkh_derive_links(zkh_ctx*, const zkh_circuit*, size_t po2, size_t zk_cycles, const zkh_buf* code, zkh_buf* data);
+/* Everything a circuit's arguments derive, in the one order in which it is sound: sorted copies, then columns, then links, then
+ * multiplicities (a LIMBS / ORDER record may read a sorted copy's column, and the multiplicities count the limbs that the records and
+ * the links derive).  Call it after the data upload and before zkh_prove_begin: what it writes belongs to the data group.  It runs
+ * every stage whose zkh_circuit_derives_* holds, with the arguments as given, and launches nothing of its own; a circuit without
+ * arguments, or whose arguments derive nothing, is a no-op that looks at no other argument, so the call needs no guard.  A NULL
+ * circuit is its only own error.  The first stage that fails ends the call with that stage's error; that stage has left `data` as it
+ * found it, the stages before it have written their columns. */
+const char* zkh_derive_all(zkh_ctx*, const zkh_circuit*, size_t po2, size_t zk_cycles, const zkh_buf* code, zkh_buf* data);
 /* The data columns that zkh_derive_sorted, zkh_derive_columns, zkh_derive_links and zkh_derive_multiplicities write on the active rows: their sorted
  * union in cols[0 .. *n) (cap = room in cols; *n is set even when the call fails for lack of room).
  * zkh_upload_data_trace copies a caller's data trace (`host`, W_data x 2^po2 words) into `data` without what the library derives:

@@ -322,9 +322,18 @@ impl HipCircuitHal {
         unsafe { sys::zkh_circuit_derives_multiplicities(self.circuit) != 0 }
     }
 
+    /// Fill everything the arguments derive into `data` from the raw code (ctrl) and data traces (`zkh_derive_all`), after the data
+    /// upload and before the data group is committed (`prove_begin`): the stages below in the one order in which they are sound
+    /// (sorted, columns, links, multiplicities), each only if the circuit has it; nothing to derive is a no-op.  Panics on the first
+    /// stage that refuses the witness; the stages before it have written their columns.
+    pub fn derive_all(&self, ctrl: &HipBuffer<BabyBearElem>, data: &HipBuffer<BabyBearElem>, steps: usize) {
+        let po2 = steps.trailing_zeros() as usize;
+        ffi(|| unsafe { sys::zkh_derive_all(self.hal.ctx.0, self.circuit, po2, sys::ZK_CYCLES, ctrl.raw, data.raw) });
+    }
+
     /// Fill the derived multiplicity columns of `data` on the active rows from the raw code (ctrl) and data traces
-    /// (`zkh_derive_multiplicities`), before the data group is committed (`prove_begin`).  Panics on a refused witness (a table
-    /// selector other than 0 / 1, a lookup without a table entry), which leaves `data` unchanged, like every failed HAL op.
+    /// (`zkh_derive_multiplicities`).  Panics on a refused witness (a table selector other than 0 / 1, a lookup without a table
+    /// entry), which leaves `data` unchanged, like every failed HAL op.
     pub fn derive_multiplicities(&self, ctrl: &HipBuffer<BabyBearElem>, data: &HipBuffer<BabyBearElem>, steps: usize) {
         let po2 = steps.trailing_zeros() as usize;
         ffi(|| unsafe { sys::zkh_derive_multiplicities(self.hal.ctx.0, self.circuit, po2, sys::ZK_CYCLES, ctrl.raw, data.raw) });
@@ -336,9 +345,8 @@ impl HipCircuitHal {
     }
 
     /// Fill the tuple columns of the derived sorted copies of `data` on the active rows from the raw code (ctrl) and data traces
-    /// (`zkh_derive_sorted`): each source tuple's selected rows, stably sorted by its key columns.  Call it before
-    /// `derive_multiplicities` and before the data group is committed (`prove_begin`).  Panics on a refused witness (a selector other
-    /// than 0 / 1), which leaves `data` unchanged, like every failed HAL op.
+    /// (`zkh_derive_sorted`): each source tuple's selected rows, stably sorted by its key columns.  Panics on a refused witness (a
+    /// selector other than 0 / 1), which leaves `data` unchanged, like every failed HAL op.
     pub fn derive_sorted(&self, ctrl: &HipBuffer<BabyBearElem>, data: &HipBuffer<BabyBearElem>, steps: usize) {
         let po2 = steps.trailing_zeros() as usize;
         ffi(|| unsafe { sys::zkh_derive_sorted(self.hal.ctx.0, self.circuit, po2, sys::ZK_CYCLES, ctrl.raw, data.raw) });
@@ -350,9 +358,8 @@ impl HipCircuitHal {
     }
 
     /// Fill the destination columns of the derived-column records of `data` on the active rows (`zkh_derive_columns`): the limbs of a
-    /// word, or the flag and difference limbs that witness the order of sorted keys.  Call it after `derive_sorted` (a record may read
-    /// a sorted column), before `derive_multiplicities` (the limbs are lookups to be counted) and before `prove_begin`.  Panics on a
-    /// refused witness (a value that does not fit its limbs, keys that are not in order), which leaves `data` unchanged.
+    /// word, or the flag and difference limbs that witness the order of sorted keys.  Panics on a refused witness (a value that does
+    /// not fit its limbs, keys that are not in order), which leaves `data` unchanged.
     pub fn derive_columns(&self, ctrl: &HipBuffer<BabyBearElem>, data: &HipBuffer<BabyBearElem>, steps: usize) {
         let po2 = steps.trailing_zeros() as usize;
         ffi(|| unsafe { sys::zkh_derive_columns(self.hal.ctx.0, self.circuit, po2, sys::ZK_CYCLES, ctrl.raw, data.raw) });
@@ -370,8 +377,7 @@ impl HipCircuitHal {
     }
 
     /// Fill the destination columns of the LINK records of `data` on the active rows (`zkh_derive_links`): every memory access gets
-    /// the previous access to its own address (linked, last, the carried values, the limbs of the clock difference).  Call it after
-    /// `derive_columns`, before `derive_multiplicities` (the limbs are lookups to be counted) and before `prove_begin`.  Panics on a
+    /// the previous access to its own address (linked, last, the carried values, the limbs of the clock difference).  Panics on a
     /// refused witness (a selector other than 0 / 1, a clock that does not increase, a difference that does not fit its limbs), which
     /// leaves `data` unchanged.
     pub fn derive_links(&self, ctrl: &HipBuffer<BabyBearElem>, data: &HipBuffer<BabyBearElem>, steps: usize) {

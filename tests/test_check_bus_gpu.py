@@ -16,6 +16,7 @@ import re
 import numpy as np
 import pytest
 
+from args_gpu import circuit as _circuit, seal_host as _seal_host
 import check_bus_cases as cases
 import zko
 from zeth_amd import hal as zhal
@@ -25,12 +26,6 @@ from zeth_amd.prover import Segment, SegmentProver
 
 pytestmark = pytest.mark.gpu
 NOISE = 0x0B05
-
-
-def _circuit(hal, desc, blob):
-    c = hal.load_circuit(desc, jit=False)
-    c.set_arguments(blob)
-    return c
 
 
 def _agree(hal, case, circuit=None):
@@ -121,18 +116,6 @@ def test_two_calls_agree_and_the_traces_are_not_written(hal):
 
 
 # ---- 11. the prover ----
-def _seal_host(hal, prover, seg, code, data, out, **kw):
-    hcode, hdata = hal.host_alloc(code.size), hal.host_alloc(data.size)
-    hcode[:] = code
-    hdata[:] = data
-    try:
-        return prover.seal_host_witness(seg, hcode, hdata, out, **kw)
-    finally:
-        hal.sync()
-        hal.host_free(hcode)
-        hal.host_free(hdata)
-
-
 @pytest.mark.parametrize("kind", ["corrupt_limb", "wrong_pval"])
 def test_seal_host_witness_with_check_names_the_key(hal, oracle, kind):
     """under the flag-free blob (nothing derived: the host's columns are what is sealed) the forged witness reaches the accumulate"""

@@ -15,6 +15,7 @@ import re
 import numpy as np
 import pytest
 
+from args_gpu import seal_host as _seal_host
 import check_rows_cases as cases
 import zko
 from zeth_amd.circuits import check, logup, syn_heavy, syn_random
@@ -176,18 +177,6 @@ def test_forged_syn_lookup_witnesses_word_for_word(hal, kind):
     variant, accum, code, data, out, mix, want_row, _columns = cases.lookup_forgery(kind, po2, zk)
     row, _step, _count = _agree(hal, cases.lookup_circuit(variant)[0], po2, accum, code, data, out, mix)
     assert row == want_row
-
-
-def _seal_host(hal, prover, seg, code, data, out, **kw):
-    hcode, hdata = hal.host_alloc(code.size), hal.host_alloc(data.size)
-    hcode[:] = code
-    hdata[:] = data
-    try:
-        return prover.seal_host_witness(seg, hcode, hdata, out, **kw)
-    finally:
-        hal.sync()
-        hal.host_free(hcode)
-        hal.host_free(hdata)
 
 
 @pytest.mark.parametrize("kind", ["swap_sorted_rows", "relink_row", "misread_row"])

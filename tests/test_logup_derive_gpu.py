@@ -5,6 +5,7 @@ determinism."""
 import numpy as np
 import pytest
 
+from args_gpu import enc as _enc, seal_host as _seal_host
 import zko
 from conftest import rand_fp
 from zeth_amd import hal as zhal
@@ -17,10 +18,6 @@ pytestmark = pytest.mark.gpu
 P = 2013265921
 NOISE = 0x10C1
 ONE = (1 << 32) % P
-
-
-def _enc(x):
-    return (np.asarray(x, dtype=np.uint64) % np.uint64(P) * np.uint64(ONE) % np.uint64(P)).astype(np.uint32)
 
 
 def _random_case(seed, po2, zk, big):
@@ -103,18 +100,6 @@ def _derive(hal, c, po2, zk, code, data):
     ddata.write(data)
     hal.derive_multiplicities(c, po2, zk, dcode, ddata)
     return ddata.to_vec()
-
-
-def _seal_host(hal, prover, seg, code, data, out):
-    hcode, hdata = hal.host_alloc(code.size), hal.host_alloc(data.size)
-    hcode[:] = code
-    hdata[:] = data
-    try:
-        return prover.seal_host_witness(seg, hcode, hdata, out)
-    finally:
-        hal.sync()
-        hal.host_free(hcode)
-        hal.host_free(hdata)
 
 
 GRID = [(8, 37, False), (9, 100, False), (10, 11, False), (11, 970, False), (12, 1994, False), (13, 1994, True), (14, 1994, True),

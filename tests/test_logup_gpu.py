@@ -7,6 +7,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from args_gpu import seal_host as _seal_host
 import zko
 from conftest import rand_fp
 from zeth_amd import hal as zhal
@@ -63,19 +64,6 @@ def _traces(rng, wc, wd, n):
         a[::97] = 0
         a[5::89] = P - 1
     return code, data
-
-
-def _seal_host(hal, prover, seg, code, data, out):
-    """seal_host_witness from pinned copies of the traces (zkh_write_async reads pinned memory only)"""
-    hcode, hdata = hal.host_alloc(code.size), hal.host_alloc(data.size)
-    hcode[:] = code
-    hdata[:] = data
-    try:
-        return prover.seal_host_witness(seg, hcode, hdata, out)
-    finally:
-        hal.sync()
-        hal.host_free(hcode)
-        hal.host_free(hdata)
 
 
 GRID = [(8, 37, 3), (9, 100, 5), (10, 11, 2), (11, 1994 - 1024, 7), (12, 1994, 4), (13, 1994, 9), (14, 1994, 12), (14, 3, 6)]

@@ -25,6 +25,7 @@ from dataclasses import replace
 import numpy as np
 import pytest
 
+from args_gpu import circuit as _circuit, enc as _enc, seal_host as _seal_host, upload as _upload
 import zko
 from conftest import rand_fp
 from zeth_amd.circuits import logup, syn_lookup
@@ -39,35 +40,6 @@ ONE = (1 << 32) % P
 TINY = syn_lookup.TINY
 SIZES = [(8, 40), (12, 1994), (13, 1994)]
 WC, PER_REC = 8, 13                             # code columns; data columns per record: key, clock, value, 9 destinations, the write flag
-
-
-def _enc(x):
-    return (np.asarray(x, dtype=np.uint64) % np.uint64(P) * np.uint64(ONE) % np.uint64(P)).astype(np.uint32)
-
-
-def _circuit(hal, desc, blob):
-    c = hal.load_circuit(desc, jit=False)
-    c.set_arguments(blob)
-    return c
-
-
-def _upload(hal, code, data):
-    dcode, ddata = hal.alloc_elem("code", code.size), hal.alloc_elem("data", data.size)
-    dcode.write(code)
-    ddata.write(data)
-    return dcode, ddata
-
-
-def _seal_host(hal, prover, seg, code, data, out):
-    hcode, hdata = hal.host_alloc(code.size), hal.host_alloc(data.size)
-    hcode[:] = code
-    hdata[:] = data
-    try:
-        return prover.seal_host_witness(seg, hcode, hdata, out)
-    finally:
-        hal.sync()
-        hal.host_free(hcode)
-        hal.host_free(hdata)
 
 
 def _without_reads(blob):

@@ -5,6 +5,7 @@ session, the refusals (data unchanged), and one size above 2^20 rows."""
 import numpy as np
 import pytest
 
+from args_gpu import circuit as _circuit, enc as _enc, seal_host as _seal_host
 import zko
 from conftest import rand_fp
 from zeth_amd import hal as zhal
@@ -17,10 +18,6 @@ pytestmark = pytest.mark.gpu
 P = 2013265921
 NOISE = 0x50C7
 ONE = (1 << 32) % P
-
-
-def _enc(x):
-    return (np.asarray(x, dtype=np.uint64) % np.uint64(P) * np.uint64(ONE) % np.uint64(P)).astype(np.uint32)
 
 
 def _key_values(rng, style, A):
@@ -81,24 +78,6 @@ def _derive(hal, c, po2, zk, code, data):
     ddata.write(data)
     hal.derive_sorted(c, po2, zk, dcode, ddata)
     return ddata.to_vec()
-
-
-def _seal_host(hal, prover, seg, code, data, out):
-    hcode, hdata = hal.host_alloc(code.size), hal.host_alloc(data.size)
-    hcode[:] = code
-    hdata[:] = data
-    try:
-        return prover.seal_host_witness(seg, hcode, hdata, out)
-    finally:
-        hal.sync()
-        hal.host_free(hcode)
-        hal.host_free(hdata)
-
-
-def _circuit(hal, desc, blob):
-    c = hal.load_circuit(desc, jit=False)
-    c.set_arguments(blob)
-    return c
 
 
 GRID = [(8, 37, "few"), (9, 100, "mixed"), (10, 11, "full"), (11, 970, "mixed"), (12, 1994, "few"), (13, 1994, "full"), (14, 3, "mixed"),

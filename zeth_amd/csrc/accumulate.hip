@@ -156,7 +156,7 @@ extern "C" const char* zkh_accumulate(zkh_ctx* ctx, const zkh_circuit* c, size_t
     {
         // per term and row: w tuple loads + selector + multiplicity in, 16 bytes (the Fp4 term) out per column and row
         double in_words = 0;
-        for (const ArgTerm& t : terms) in_words += t.c.w + (t.c.sel != NONE) + (t.c.mg != NONE);
+        for (const Term& t : a.terms) in_words += entry_words(t);
         ProfScope prof(ctx, "args_terms", 4.0 * in_words * A + 16.0 * k * A);
         const unsigned bx = (unsigned)((A + ARGS_THREADS * ARGS_BATCH - 1) / (ARGS_THREADS * ARGS_BATCH));
         k_args_terms<<<dim3(bx, k), ARGS_THREADS, 0, ctx->stream>>>(accum->ptr(), code->ptr(), data->ptr(), d_terms, d_cols, bp, (uint32_t)n, A, bad);

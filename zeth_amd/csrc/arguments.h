@@ -6,7 +6,8 @@
 // WHO WRITES A DATA COLUMN (the module docstring of logup.py says the same; check_owned in arguments.hip keeps it).  A data column has at
 // most one writer, and a derive reads only what the stages before it have finished writing.  The writers: a sorted copy (its tuple
 // columns), a LIMBS / ORDER record and a LINK record (their destinations), a derived multiplicity (its column); every other column is
-// the host's.  The stages run one after the other, each over the whole trace: sorted -> columns -> links -> multiplicities.  Of the
+// the host's.  The stages run one after the other, each over the whole trace: sorted -> columns -> links -> multiplicities (STAGES in
+// arguments.hip is that order in code, and zkh_derive_all runs it; no caller spells it out).  Of the
 // columns a derive writes, the sort reads none; a LIMBS / ORDER record reads a sorted copy's columns and no record's destination
 // (records never chain); a LINK reads none; the multiplicities count lookup tuples, and those read every derived column freely.
 // Nothing reads a derived multiplicity.  A term's multiplicity is the host's column or a derived one, and of a LINK's destinations
@@ -82,6 +83,8 @@ inline TermCols term_cols(const Term& t) {
     for (uint32_t e = 0; e < MAX_TUPLE; e++) { d.tg[e] = e < t.w ? t.tg[e] : GROUP_DATA; d.tc[e] = e < t.w ? t.tc[e] : 0; }
     return d;
 }
+// the words a term reads per row for its weight and tuple (selector, multiplicity, tuple columns): the ProfScope byte counts of its consumers
+inline uint32_t entry_words(const Term& t) { return t.w + (t.sel != NONE) + (t.mg != NONE); }
 
 // what the entry points over a trace share: po2 in 1..24, an active row left, the code / data (and, if given, accum) buffers of the
 // circuit's widths at 2^po2 rows.  `who` prefixes the messages.  *n = rows, *A = active rows.

@@ -370,6 +370,26 @@ extern "C" int zkh_circuit_derives_links(const zkh_circuit* c) { return c && c->
 
 extern "C" int zkh_circuit_links_check_reads(const zkh_circuit* c) { return c && c->args ? (int)c->args->reads : 0; }
 
+// THE DERIVE STAGES, IN THEIR ORDER (arguments.h, WHO WRITES A DATA COLUMN): the one statement of the order in code.  A LIMBS / ORDER
+// record may read a sorted copy's column, and the multiplicities count the limbs that the records and the links derive.
+namespace {
+using Derive = const char* (*)(zkh_ctx*, const zkh_circuit*, size_t, size_t, const zkh_buf*, zkh_buf*);
+const struct { const char* name; int (*derives)(const zkh_circuit*); Derive derive; } STAGES[] = {
+    {"sorted", zkh_circuit_derives_sorted, zkh_derive_sorted},
+    {"columns", zkh_circuit_derives_columns, zkh_derive_columns},
+    {"links", zkh_circuit_derives_links, zkh_derive_links},
+    {"multiplicities", zkh_circuit_derives_multiplicities, zkh_derive_multiplicities},
+};
+}  // namespace
+
+// every stage the circuit's arguments have, with the arguments as given: the stage's own checks and messages are the call's
+extern "C" const char* zkh_derive_all(zkh_ctx* ctx, const zkh_circuit* c, size_t po2, size_t zk_cycles, const zkh_buf* code, zkh_buf* data) {
+    ZKH_REQUIRE(c, "derive_all: null circuit");
+    for (const auto& s : STAGES)
+        if (s.derives(c)) ZKH_TRY(s.derive(ctx, c, po2, zk_cycles, code, data));
+    return nullptr;
+}
+
 extern "C" const char* zkh_circuit_derived_data_columns(const zkh_circuit* c, uint32_t* cols, size_t cap, size_t* n) {
     ZKH_REQUIRE(c && n && (cols || !cap), "derived_data_columns: null argument");
     std::vector<uint32_t> out;

@@ -209,21 +209,15 @@ extern "C" const char* zkh_check_bus(zkh_ctx* ctx, const zkh_circuit* c, size_t 
     ZKH_REQUIRE((uint64_t)n_terms * A < (1ull << 33), "check_bus: %u terms x %u rows could overflow a counter", n_terms, A);
     bind_thread(ctx);
 
-    static_assert(sizeof(KeyTerm) % 4 == 0, "word records");
-    const size_t term_words = sizeof(KeyTerm) / 4;
-    std::vector<uint32_t> table(n_terms * term_words + n_terms);
-    for (uint32_t i = 0; i < n_terms; i++) {
-        const KeyTerm t{a[i].tag, term_cols(a[i])};
-        memcpy(table.data() + i * term_words, &t, sizeof t);
-        table[n_terms * term_words + i] = a[i].neg ? 1 : 0;
-    }
+    std::vector<uint32_t> table = key_term_table(a, n_terms);         // then every term's sign
+    for (uint32_t i = 0; i < n_terms; i++) table[n_terms * KEY_TERM_WORDS + i] = a[i].neg ? 1 : 0;
     Tmp dtab, status, slots;
     ZKH_TRY(zkh_copy_from(ctx, "bus_terms", table.data(), table.size(), dtab.out()));
     ZKH_TRY(new_buf(ctx, ST_WORDS, false, status.out()));
     const KeyTerm* d_terms = (const KeyTerm*)dtab->ptr();
-    const uint32_t* d_negs = dtab->ptr() + n_terms * term_words;
+    const uint32_t* d_negs = dtab->ptr() + n_terms * KEY_TERM_WORDS;
     double in_words = 0;                                              // weight + tuple words per entry, the key re-reads not counted
-    for (const Term& t : a) in_words += t.w + (t.sel != NONE) + (t.mg != NONE);
+    for (const Term& t : a) in_words += entry_words(t);
     const unsigned rows_x = (unsigned)((A + BUS_THREADS - 1) / BUS_THREADS);
 
     uint64_t slots_n = 64;

@@ -18,6 +18,17 @@ struct KeyTerm {                                 // a term as the keyed kernels 
     TermCols c;
 };
 struct Key { uint32_t v[MAX_TUPLE]; };
+static_assert(sizeof(KeyTerm) % 4 == 0, "word records");
+constexpr size_t KEY_TERM_WORDS = sizeof(KeyTerm) / 4;
+// the circuit's terms in that form, by blob index, as words for the upload, with room for `extra` words that the caller appends
+inline std::vector<uint32_t> key_term_table(const std::vector<Term>& a, size_t extra) {
+    std::vector<uint32_t> table(a.size() * KEY_TERM_WORDS + extra);
+    for (size_t i = 0; i < a.size(); i++) {
+        const KeyTerm t{a[i].tag, term_cols(a[i])};
+        memcpy(table.data() + i * KEY_TERM_WORDS, &t, sizeof t);
+    }
+    return table;
+}
 
 __device__ __forceinline__ Key read_key(const uint32_t* code, const uint32_t* data, const KeyTerm& t, uint32_t n, uint32_t r) {
     Key k;

@@ -114,12 +114,9 @@ extern "C" const char* zkh_derive_multiplicities(zkh_ctx* ctx, const zkh_circuit
     ZKH_TRY(trace_rows("derive_multiplicities", c, po2, zk_cycles, code, data, nullptr, &n, &A));
     const std::vector<Term>& a = c->args->terms;
     const uint32_t n_terms = (uint32_t)a.size();
-    std::vector<KeyTerm> terms(n_terms);
     std::vector<uint32_t> derived, lookups;
-    for (uint32_t i = 0; i < n_terms; i++) {
-        terms[i] = KeyTerm{a[i].tag, term_cols(a[i])};
+    for (uint32_t i = 0; i < n_terms; i++)
         if (a[i].derive) derived.push_back(i);
-    }
     for (uint32_t i = 0; i < n_terms; i++)               // the lookups: the other terms of a derived term's tag
         if (!a[i].derive && std::any_of(derived.begin(), derived.end(), [&](uint32_t j) { return a[j].tag == a[i].tag; })) lookups.push_back(i);
     // counters: at most n_lookups * A adds of < 2^31 each
@@ -131,10 +128,8 @@ extern "C" const char* zkh_derive_multiplicities(zkh_ctx* ctx, const zkh_circuit
     const uint32_t mask = (uint32_t)(slots_n - 1);
     bind_thread(ctx);
 
-    static_assert(sizeof(KeyTerm) % 4 == 0, "word records");
-    std::vector<uint32_t> table(terms.size() * (sizeof(KeyTerm) / 4) + derived.size() + lookups.size());
-    memcpy(table.data(), terms.data(), terms.size() * sizeof(KeyTerm));
-    uint32_t* lists = table.data() + terms.size() * (sizeof(KeyTerm) / 4);
+    std::vector<uint32_t> table = key_term_table(a, derived.size() + lookups.size());
+    uint32_t* lists = table.data() + n_terms * KEY_TERM_WORDS;
     std::copy(derived.begin(), derived.end(), lists);
     std::copy(lookups.begin(), lookups.end(), lists + derived.size());
     Tmp dtab, status, slots, sid, cnt;
@@ -146,7 +141,7 @@ extern "C" const char* zkh_derive_multiplicities(zkh_ctx* ctx, const zkh_circuit
     ZKH_HIP(hipMemsetAsync(status->ptr() + 4, 0, 8, ctx->stream));
     ZKH_HIP(hipMemsetAsync(slots->ptr(), 0xff, 8 * slots_n, ctx->stream));
     const KeyTerm* d_terms = (const KeyTerm*)dtab->ptr();
-    const uint32_t* d_derived = dtab->ptr() + terms.size() * (sizeof(KeyTerm) / 4);
+    const uint32_t* d_derived = dtab->ptr() + n_terms * KEY_TERM_WORDS;
     const uint32_t* d_lookups = d_derived + derived.size();
     unsigned long long* d_slots = (unsigned long long*)slots->ptr();
     double key_words = 0;                                             // tuple + selector words per row of the derived terms
@@ -178,7 +173,7 @@ extern "C" const char* zkh_derive_multiplicities(zkh_ctx* ctx, const zkh_circuit
     unsigned long long* d_cnt = (unsigned long long*)cnt->ptr();
     {
         double in_words = 0;                                          // weight + tuple words per lookup row, the key re-reads not counted
-        for (uint32_t i : lookups) in_words += a[i].w + (a[i].sel != NONE) + (a[i].mg != NONE);
+        for (uint32_t i : lookups) in_words += entry_words(a[i]);
         const bool lds = U <= LDS_KEYS;
         ProfScope prof(ctx, lds ? "derive_count_lds" : "derive_count_global", 4.0 * in_words * A + 8.0 * U);
         const unsigned bx = std::min<unsigned>(rows_x, COUNT_BLOCKS);

@@ -606,12 +606,8 @@ static const char* seal_one(zkh_session* s, Lane& l, const zkh_segment& seg, uin
         ZKH_REQUIRE(seg.host_code && seg.host_data && seg.out_global, "session: a segment with host traces needs host_code, host_data and out_global");
         ZKH_TRY(zkh_write(l.ctx, code, seg.host_code, 0, code->len));
         ZKH_TRY(zkh_upload_data_trace(l.ctx, cir, seg.po2, ZKH_ZK_CYCLES, data, seg.host_data, 0));     // without what is derived below
-        // derived sorted copies, columns, linked accesses and lookup multiplicities belong to the data group: filled before it is committed, callback or
-        // not (the copies first: a record or a lookup may read a sorted column; the multiplicities last: they count the derived limbs)
-        if (zkh_circuit_derives_sorted(cir)) ZKH_TRY(zkh_derive_sorted(l.ctx, cir, seg.po2, ZKH_ZK_CYCLES, code, data));
-        if (zkh_circuit_derives_columns(cir)) ZKH_TRY(zkh_derive_columns(l.ctx, cir, seg.po2, ZKH_ZK_CYCLES, code, data));
-        if (zkh_circuit_derives_links(cir)) ZKH_TRY(zkh_derive_links(l.ctx, cir, seg.po2, ZKH_ZK_CYCLES, code, data));
-        if (zkh_circuit_derives_multiplicities(cir)) ZKH_TRY(zkh_derive_multiplicities(l.ctx, cir, seg.po2, ZKH_ZK_CYCLES, code, data));
+        // what the library derives belongs to the data group: filled before it is committed, callback or not
+        ZKH_TRY(zkh_derive_all(l.ctx, cir, seg.po2, ZKH_ZK_CYCLES, code, data));
         out_global.assign(seg.out_global, seg.out_global + out_global.size());
         *witgen_s = now_s() - t0;
         zkh_seal_job* job = nullptr;

@@ -179,6 +179,7 @@ ABI = {
     "zkh_circuit_derives_links": (_i, [_vp]),
     "zkh_circuit_links_check_reads": (_i, [_vp]),
     "zkh_derive_links": (_err, [_vp, _vp, _sz, _sz, _vp, _vp]),
+    "zkh_derive_all": (_err, [_vp, _vp, _sz, _sz, _vp, _vp]),
     "zkh_circuit_derived_data_columns": (_err, [_vp, _u32p, _sz, C.POINTER(_sz)]),
     "zkh_upload_data_trace": (_err, [_vp, _vp, _sz, _sz, _vp, _u32p, _i]),
     "zkh_ctx_h2d_bytes": (_sz, [_vp]),
@@ -821,20 +822,25 @@ class HipHal:
         _k, kp = _key_ptr(noise_seed)
         _check(_lib.zkh_accumulate(self.ctx, circuit.h, po2, zk_cycles, kp, code.h, data.h, _ptr(m), accum.h))
 
+    def derive_all(self, circuit: Circuit, po2: int, zk_cycles: int, code: Buffer, data: Buffer) -> None:
+        """fill everything the circuit's arguments derive into `data`, the stages in their order (zkh_derive_all); nothing to derive:
+        nothing done.  Raises the HalError of the first stage that refuses; the stages before it have written their columns"""
+        _check(_lib.zkh_derive_all(self.ctx, circuit.h, po2, zk_cycles, code.h, data.h))
+
     def derive_multiplicities(self, circuit: Circuit, po2: int, zk_cycles: int, code: Buffer, data: Buffer) -> None:
         """fill the derived multiplicity columns of `data` on the active rows (zkh_derive_multiplicities): raises HalError on a table
         selector other than 0 / 1 or a lookup without a table entry (`data` is then unchanged)"""
         _check(_lib.zkh_derive_multiplicities(self.ctx, circuit.h, po2, zk_cycles, code.h, data.h))
 
     def derive_columns(self, circuit: Circuit, po2: int, zk_cycles: int, code: Buffer, data: Buffer) -> None:
-        """fill the destination columns of the derived-column records of `data` on the active rows (zkh_derive_columns), after
-        derive_sorted and before derive_multiplicities: raises HalError on a value that does not fit its limbs or on keys that are
-        not in order, naming the lowest (record, row) (`data` is then unchanged)"""
+        """fill the destination columns of the derived-column records of `data` on the active rows (zkh_derive_columns): raises
+        HalError on a value that does not fit its limbs or on keys that are not in order, naming the lowest (record, row) (`data` is
+        then unchanged)"""
         _check(_lib.zkh_derive_columns(self.ctx, circuit.h, po2, zk_cycles, code.h, data.h))
 
     def derive_links(self, circuit: Circuit, po2: int, zk_cycles: int, code: Buffer, data: Buffer) -> None:
         """fill the destination columns of the LINK records of `data` on the active rows (zkh_derive_links): every access gets the
-        previous access to its own address; after derive_columns and before derive_multiplicities.  Raises HalError on a selector
+        previous access to its own address.  Raises HalError on a selector
         other than 0 / 1, on a clock that does not increase or on a difference that does not fit its limbs, naming the lowest
         (record, row) (`data` is then unchanged)"""
         _check(_lib.zkh_derive_links(self.ctx, circuit.h, po2, zk_cycles, code.h, data.h))
@@ -888,8 +894,8 @@ class HipHal:
         return int(_lib.zkh_ctx_h2d_bytes(self.ctx))
 
     def derive_sorted(self, circuit: Circuit, po2: int, zk_cycles: int, code: Buffer, data: Buffer) -> None:
-        """fill the tuple columns of the derived sorted copies of `data` on the active rows (zkh_derive_sorted), before
-        derive_multiplicities: raises HalError on a selector other than 0 / 1 (`data` is then unchanged)"""
+        """fill the tuple columns of the derived sorted copies of `data` on the active rows (zkh_derive_sorted): raises HalError on a
+        selector other than 0 / 1 (`data` is then unchanged)"""
         _check(_lib.zkh_derive_sorted(self.ctx, circuit.h, po2, zk_cycles, code.h, data.h))
 
     # ---- profiling ----

@@ -296,9 +296,8 @@ class SegmentProver:
     def seal_host_witness(self, seg: Segment, host_code: np.ndarray, host_data: np.ndarray, out_global, check: bool = False) -> SegmentReceipt:
         """Seal a segment whose code/data traces live in pinned HOST memory (hal.host_alloc views): enqueue both uploads
         on the context's stream (no host sync), then run the two-halves seal.  This is the PCIe-inclusive path.  A circuit whose
-        arguments derive sorted copies, columns, linked accesses or lookup multiplicities gets them filled into the data trace first, in
-        that order (zkh_derive_sorted, zkh_derive_columns, zkh_derive_links, zkh_derive_multiplicities: a record or a lookup may read
-        a sorted column, and the multiplicities count the derived limbs); of those columns only the blinding rows are uploaded (zkh_upload_data_trace).  The accum
+        arguments derive sorted copies, columns, linked accesses or lookup multiplicities gets them filled into the data trace first
+        (zkh_derive_all); of those columns only the blinding rows are uploaded (zkh_upload_data_trace).  The accum
         comes from the built-in generator of kinds 1..3, else from zkh_accumulate when the circuit carries arguments.
         check: check the finished witness row by row before the seal is spent on it (check_witness, seal_with_accum), and when
         zkh_accumulate refuses a bus that does not balance, name the key (check_bus, args_accumulate)."""
@@ -306,14 +305,7 @@ class SegmentProver:
         data = self.hal.alloc_elem("data", host_data.size)
         self.hal.write_async(code, host_code)
         self.hal.upload_data_trace(self.circuit, seg.po2, seg.zk_cycles, data, host_data)
-        if self.circuit.derives_sorted():
-            self.hal.derive_sorted(self.circuit, seg.po2, seg.zk_cycles, code, data)
-        if self.circuit.derives_columns():
-            self.hal.derive_columns(self.circuit, seg.po2, seg.zk_cycles, code, data)
-        if self.circuit.derives_links():
-            self.hal.derive_links(self.circuit, seg.po2, seg.zk_cycles, code, data)
-        if self.circuit.derives_multiplicities():
-            self.hal.derive_multiplicities(self.circuit, seg.po2, seg.zk_cycles, code, data)
+        self.hal.derive_all(self.circuit, seg.po2, seg.zk_cycles, code, data)
         builtin = 1 <= int(self.circuit.desc[13]) <= 3
         acc = self.args_accumulate(seg, code, data, check=check) if not builtin and self.circuit.has_arguments() else self.syn_accumulate(seg, data)
         return self.seal_with_accum(seg, code, data, out_global, acc, check=check)
