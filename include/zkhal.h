@@ -334,6 +334,32 @@ const char* zkh_derive_columns(zkh_ctx*, const zkh_circuit*, size_t po2, size_t 
 int zkh_circuit_derives_links(const zkh_circuit*);
 int zkh_circuit_links_check_reads(const zkh_circuit*);
 const char* zkh_derive_links(zkh_ctx*, const zkh_circuit*, size_t po2, size_t zk_cycles, const zkh_buf* code, zkh_buf* data);
+/* PAGING (ZKA1 version 7; versions 1..6 are word for word what they were): the arguments may hold ONE PAGES record (kind 4, 32 words, after
+ * every LINK record; header word 7 carries bit 16 beside the READS count).  Its words: kind, L = limb bits (1..16), ng = limbs (1..4,
+ * L ng <= 29), the blob index of the LINK record it pages (one with READS and nc = 2: a clock and one value column), twelve zeros, then
+ * the 5 + 2 ng destination data columns p_on, p_addr, p_in, p_out, p_time, alimb_0 .., gap_0 ...  zkh_circuit_pages: 1 with such a
+ * record, else 0.  The memory of that LINK then starts from an IMAGE, W raw Montgomery words, image[a] the word of address a (the
+ * canonical value of the key), and zkh_derive_links_paged (zkh_derive_links with that image) differs from zkh_derive_links in this:
+ *   an unlinked access r of the paged record takes the image as its previous access: prev_1[r] = the raw word image[a], prev_0[r] = 0
+ *   (clock 0 is the image's), limb_j[r] = limb j of x(clock, r) - 0 - 1; linked and last are what they were;
+ *   it FAILS, leaving `data` unchanged, also when an access has a >= W ("address A outside the image of W words"), when an unlinked
+ *   access has clock 0, when its clock - 1 does not fit the limbs, and when an unlinked load does not return image[a] (residues); on one
+ *   row the order is write flag, address, clock, read rule, and the lowest (record, row) over all refusals is the one reported;
+ *   with a_0 < .. < a_{D-1} the distinct addresses of the record's accesses it writes the page table on the active rows i < D:
+ *   p_on = Montgomery(1), p_addr = the raw key word of a_i's first access, p_in = the raw word image[a_i], p_out, p_time = the raw value
+ *   and clock words of a_i's last access, alimb_j = limb j of a_i (refused when a_i >= 2^(L ng)), gap_j = limb j of a_i - a_{i-1} - 1
+ *   (zeros on row 0); active rows [D, A) get zeros in all thirteen, rows [A, n) are never touched.
+ * One address sort serves the links and the table; the result is a function of the traces and the image alone.  zkh_derive_links and
+ * zkh_derive_all REFUSE a circuit with a PAGES record ("the arguments page memory: an image is required (zkh_derive_all_paged)"); with no
+ * PAGES record the paged entry points ignore the image (NULL or not) and are the plain ones.
+ * zkh_page_out writes the table back: image[x(p_addr, i)] = the raw word p_out[i] on every active row i with p_on = 1.  A check pass
+ * comes first and a refusal leaves the image unchanged: the lowest row whose p_on is not 0 / 1, whose address is >= W, or whose address
+ * does not follow a smaller one on a row with p_on = 1 (the table is a prefix of strictly increasing addresses, as the circuit demands:
+ * a host-made table that repeats an address is refused, not resolved).  It is a call of its own so that a refused or aborted seal never
+ * touches the image.  The image is not bound to a commitment: the verifier does not learn which image (ARGUMENTS). */
+int zkh_circuit_pages(const zkh_circuit*);
+const char* zkh_derive_links_paged(zkh_ctx*, const zkh_circuit*, size_t po2, size_t zk_cycles, const zkh_buf* code, zkh_buf* data, const zkh_buf* image);
+const char* zkh_page_out(zkh_ctx*, const zkh_circuit*, size_t po2, size_t zk_cycles, const zkh_buf* data, zkh_buf* image);
 /* Everything a circuit's arguments derive, in the one order in which it is sound: sorted copies, then columns, then links, then
  * multiplicities (a LIMBS / ORDER record may read a sorted copy's column, and the multiplicities count the limbs that the records and
  * the links derive).  Call it after the data upload and before zkh_prove_begin: what it writes belongs to the data group.  It runs
@@ -342,6 +368,9 @@ const char* zkh_derive_links(zkh_ctx*, const zkh_circuit*, size_t po2, size_t zk
  * circuit is its only own error.  The first stage that fails ends the call with that stage's error; that stage has left `data` as it
  * found it, the stages before it have written their columns. */
 const char* zkh_derive_all(zkh_ctx*, const zkh_circuit*, size_t po2, size_t zk_cycles, const zkh_buf* code, zkh_buf* data);
+/* ... and the same with the memory image that the links stage of a paging circuit reads (zkh_derive_links_paged); zkh_derive_all is this
+ * call with no image.  A paging circuit without an image is refused before any stage has written. */
+const char* zkh_derive_all_paged(zkh_ctx*, const zkh_circuit*, size_t po2, size_t zk_cycles, const zkh_buf* code, zkh_buf* data, const zkh_buf* image);
 /* The data columns that zkh_derive_sorted, zkh_derive_columns, zkh_derive_links and zkh_derive_multiplicities write on the active rows: their sorted
  * union in cols[0 .. *n) (cap = room in cols; *n is set even when the call fails for lack of room).
  * zkh_upload_data_trace copies a caller's data trace (`host`, W_data x 2^po2 words) into `data` without what the library derives:

@@ -385,6 +385,35 @@ impl HipCircuitHal {
         ffi(|| unsafe { sys::zkh_derive_links(self.hal.ctx.0, self.circuit, po2, sys::ZK_CYCLES, ctrl.raw, data.raw) });
     }
 
+    /// The arguments (a ZKA1 version-7 blob) hold a PAGES record: the memory of its LINK record starts from an image
+    /// (`derive_links_paged`, `derive_all_paged`) and `page_out` writes it back; `derive_links` and `derive_all` refuse such a circuit.
+    pub fn pages(&self) -> bool {
+        unsafe { sys::zkh_circuit_pages(self.circuit) != 0 }
+    }
+
+    /// `derive_links` from a memory image of raw Montgomery words (`zkh_derive_links_paged`): an unlinked access of the paged LINK
+    /// record takes `image[address]` as its previous access (at clock 0), and the PAGES record's page table is written.  Panics on a
+    /// refused witness as `derive_links` does, and on an address outside the image, a clock 0 or an unlinked load that does not return
+    /// the image's word; `data` is then unchanged.  Without a PAGES record the image is ignored.
+    pub fn derive_links_paged(&self, ctrl: &HipBuffer<BabyBearElem>, data: &HipBuffer<BabyBearElem>, image: &HipBuffer<BabyBearElem>, steps: usize) {
+        let po2 = steps.trailing_zeros() as usize;
+        ffi(|| unsafe { sys::zkh_derive_links_paged(self.hal.ctx.0, self.circuit, po2, sys::ZK_CYCLES, ctrl.raw, data.raw, image.raw) });
+    }
+
+    /// `derive_all` with the memory image that the links stage of a paging circuit reads (`zkh_derive_all_paged`).
+    pub fn derive_all_paged(&self, ctrl: &HipBuffer<BabyBearElem>, data: &HipBuffer<BabyBearElem>, image: &HipBuffer<BabyBearElem>, steps: usize) {
+        let po2 = steps.trailing_zeros() as usize;
+        ffi(|| unsafe { sys::zkh_derive_all_paged(self.hal.ctx.0, self.circuit, po2, sys::ZK_CYCLES, ctrl.raw, data.raw, image.raw) });
+    }
+
+    /// Write the page table of `data` back into `image` (`zkh_page_out`): `image[p_addr] = p_out` on every active row with `p_on` = 1.
+    /// A call of its own, after the seal, so that a refused or aborted seal never touches the image.  Panics, with the image unchanged,
+    /// on a `p_on` other than 0 / 1, an address outside the image, or page addresses that do not strictly increase over a prefix of rows.
+    pub fn page_out(&self, data: &HipBuffer<BabyBearElem>, image: &HipBuffer<BabyBearElem>, steps: usize) {
+        let po2 = steps.trailing_zeros() as usize;
+        ffi(|| unsafe { sys::zkh_page_out(self.hal.ctx.0, self.circuit, po2, sys::ZK_CYCLES, data.raw, image.raw) });
+    }
+
     /// Check the raw traces against the circuit's own constraints on every row of `rows` (`zkh_check_rows`): which constraint a
     /// witness breaks, and where, before a seal is spent on it.  `out` and `mix` are the global words.  `row < 0`: no row of the window
     /// fails; otherwise the lowest failing row, its lowest failing `and_eqz` step (an index into the ZKC1 step list), how many rows of

@@ -7,7 +7,9 @@ the same bytes, to the host's sort + gather + upload, and the host-witness seal 
 under its version-6 blob next to the same trace under the version-5 blob; M15: zkh_check_rows, the row-by-row constraint check of an honest
 SYN-A / SYN-HEAVY witness, next to zkh_eval_check on the step interpreter for the same circuit in the same run, alternating; M16:
 zkh_check_bus, the key-by-key bus check of the honest SYN-LOOKUP FULL witness, with and without its per-term pass, next to zkh_accumulate
-and zkh_derive_multiplicities on the same trace in the same run, alternating) on one
+and zkh_derive_multiplicities on the same trace in the same run, alternating; M17: paging, zkh_derive_links_paged on SYN-LOOKUP-paged
+under its version-7 blob next to zkh_derive_links under the version-6 blob on the same trace, and zkh_page_out next to a copy of the
+same bytes, alternating) on one
 MI355X, through the C ABI (HipHal).
 
 Each line of output is one JSON object: the op, its shape, the average wall time of one call (stream drained on both
@@ -569,6 +571,71 @@ def main() -> None:
                           "check_bus_vs_derive_multiplicities": round(med["check_bus"] / med["derive_multiplicities"], 3),
                           "per_term_vs_check_bus": round(med["check_bus_per_term"] / med["check_bus"], 3)}), flush=True)
         del code, data, forged, accum
+    if want("M17"):
+        # paging (zkh_derive_links_paged on SYN-LOOKUP-paged FULL, a ZKA1 version-7 blob) next to its yardstick in the same run:
+        # zkh_derive_links under the version-6 blob of the same arguments (the PAGES record dropped) on the same trace, code this path
+        # does not share beyond the sort.  The image is all zeros, so that the trace's first loads return 0 and the version-6 read rule
+        # accepts them too.  zkh_page_out next to zkh_eltwise_copy_elem over the bytes it moves (p_on, p_addr and p_out read, one word
+        # per page written).  Timed in alternation, `runs` windows of `reps` calls; median and spread (min, max) of the windows; then
+        # the passes by their events.
+        from zeth_amd.circuits import logup, syn_lookup
+        runs, zk = 7, 1994
+        A = n - zk
+        shape = syn_lookup.FULL
+        desc, blob = syn_lookup.build_syn_lookup(shape, link=True, reads=True, pages=True)
+        pargs = logup.Arguments.parse(blob)
+        blob6 = logup.Arguments(pargs.k, pargs.alpha, pargs.beta, pargs.terms, [r for r in pargs.records if not isinstance(r, logup.Pages)]).blob()
+        assert int(blob[1]) == 7 and int(blob6[1]) == 6
+        W = 1 << 20
+        image_h = np.zeros(W, dtype=np.uint32)
+        code_h, full_h, _out = syn_lookup.witness(shape, args.po2, zk, seed=17, link=True, reads=True, pages=True, image=image_h)
+        paged, plain = hal.load_circuit(desc, jit=False), hal.load_circuit(desc, jit=False)
+        paged.set_arguments(blob)
+        plain.set_arguments(blob6)
+        assert paged.pages() and not plain.pages()
+        bare_h = full_h.reshape(-1, n).copy()
+        bare_h[paged.derived_data_columns(), :A] = 0
+        code, data, data6, image = (hal.alloc_elem(nm, sz) for nm, sz in (("code", code_h.size), ("data", bare_h.size), ("data6", bare_h.size), ("image", W)))
+        code.write(code_h)
+        data.write(bare_h.reshape(-1))
+        data6.write(bare_h.reshape(-1))
+        image.write(image_h)
+        paged_fn = lambda: hal.derive_links_paged(paged, args.po2, zk, code, data, image)                   # noqa: E731
+        plain_fn = lambda: hal.derive_links(plain, args.po2, zk, code, data6)                               # noqa: E731
+        out_fn = lambda: hal.page_out(paged, args.po2, zk, data, image)                                     # noqa: E731  (after the first call it rewrites what is there)
+        pages = int((full_h.reshape(-1, n)[pargs.pages.p_on, :A] != 0).sum())
+        moved = 3 * A + pages                                                # words: three table columns read, one image word per page written
+        src, dst = upload(hal, rng, "m17s", moved // 2), hal.alloc_elem("m17d", moved // 2)
+        copy_fn = lambda: hal.eltwise_copy_elem(dst, src)                                                   # noqa: E731
+        paged_fn()
+        assert np.array_equal(data.to_vec(), full_h)
+        out_fn()
+        assert np.array_equal(image.to_vec(), logup.reference_page_out(pargs, args.po2, zk, full_h, image_h))
+        image.write(image_h)
+        t = {"derive_links_paged": [], "derive_links_v6": [], "page_out": [], "copy_same_bytes": []}
+        for _ in range(runs):
+            for name, fn in (("derive_links_paged", paged_fn), ("derive_links_v6", plain_fn), ("page_out", out_fn), ("copy_same_bytes", copy_fn)):
+                t[name].append(timed(hal, fn, args.reps))
+                if name == "page_out":                                       # the next window's derive starts from the first image again
+                    image.write(image_h)
+        steps = {}
+        for name, fn in (("paged", paged_fn), ("v6", plain_fn), ("page_out", out_fn)):
+            hal.prof_enable(True)
+            hal.prof_reset()
+            for _ in range(args.reps):
+                fn()
+            hal.sync()
+            steps[name] = {r["name"]: round(r["total_ms"] / max(r["calls"], 1), 4) for r in hal.prof_get()
+                           if r["calls"] and r["name"].startswith(("sort_", "links_", "pages_", "page_out_"))}
+            hal.prof_enable(False)
+            image.write(image_h)
+        spread = lambda ts: {"median_ms": round(float(np.median(ts)) * 1e3, 4), "min_ms": round(min(ts) * 1e3, 4), "max_ms": round(max(ts) * 1e3, 4)}   # noqa: E731
+        med = {k: float(np.median(v)) for k, v in t.items()}
+        print(json.dumps({"bench": "M17", "circuit": "SYN-LOOKUP-paged FULL", "po2": args.po2, "accesses": A, "pages": pages, "image_words": W, "runs": runs,
+                          "reps": args.reps, **{k: spread(v) for k, v in t.items()}, "steps_ms": steps, "page_out_words": moved,
+                          "paged_vs_v6": round(med["derive_links_paged"] / med["derive_links_v6"], 3),
+                          "page_out_vs_copy": round(med["page_out"] / med["copy_same_bytes"], 3)}), flush=True)
+        del code, data, data6, image, src, dst
     hal.close()
 
 

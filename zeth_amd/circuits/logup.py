@@ -24,9 +24,9 @@ The degree of a column's constraint is 1 (gate) + max(1 + t, max_i(deg sel_i + d
 
 ZKA1 layout (u32 words; canonical integers, not Montgomery words)::
 
-    [0] magic 'ZKA1' = 0x5a4b4131   [1] version = 1 .. 6      [2] k = accum Fp4 columns   [3] alpha mix word offset
+    [0] magic 'ZKA1' = 0x5a4b4131   [1] version = 1 .. 7      [2] k = accum Fp4 columns   [3] alpha mix word offset
     [4] beta mix word offset       [5] n_terms       [6] reserved = 0 (version 4: n_records)
-    [7] reserved = 0 (version 6: the number of LINK records with READS, at least 1)
+    [7] reserved = 0 (version 6: the number of LINK records with READS, at least 1; version 7: that number | 0x10000)
     terms: n_terms x 16 words, sorted by column:
       col, neg (0: +1, 1: -1), sel (code column or NONE), m_group (NONE = constant 1, else GROUP_CODE / GROUP_DATA), m_col,
       tag, w, flags, then w (group, column) pairs of the tuple, unused pairs 0
@@ -51,6 +51,13 @@ ZKA1 layout (u32 words; canonical integers, not Montgomery words)::
     is refused; with READS words [14], [15] are the (group, column) of the WRITE FLAG w, without it they are 0.  READS needs nc >= 2 (a
     clock and a value column).  Header word 7 = the number of LINK records with READS; a version-6 blob in which it is 0 is no ZKA1
     blob, and one in which it is not that number is refused.  The builder writes version 6 only when a LINK record has READS.
+
+    Version 7: as version 6, and the blob holds ONE record of kind 4 = PAGES (32 words), after every LINK record:
+      [0] kind = 4   [1] L = limb bits (1..16)   [2] ng = limbs (1..4, L ng <= 29)   [3] the blob record index of the LINK record it pages
+      [4 .. 15] reserved = 0   [16 ..] the 5 + 2 ng destination data columns p_on, p_addr, p_in, p_out, p_time, alimb_0 .. alimb_{ng-1},
+      gap_0 .. gap_{ng-1}; the words after them reserved = 0.  The LINK it names has READS and nc = 2 (a clock and one value column); its own
+      32 words are what version 6 writes.  Header word 7 = (the READS count) | 0x10000: a version-7 blob without bit 16 is no ZKA1 blob, bit
+      16 without a PAGES record is refused.  The builder writes version 7 only when a PAGES record exists (`derive_pages`).
 
 A derived term is the table side of a lookup (`check_derived`): sign -1, its multiplicity a data column that no tuple and no other
 term names, and every other term of its tag a lookup of sign +1.  Its multiplicity column is then a function of the traces:
@@ -84,6 +91,22 @@ mod P (a raw word P is a zero).  The rule adds no destination.  On one row the w
 the read rule, lowest j first; the lowest (record, row) over all of these refusals is the one named.  Records without READS are
 what they were.
 
+PAGING (the PAGES record, ZKA1 version 7; `check_pages`, `reference_links(..., image)`, zkh_derive_links_paged): the memory of the paged
+LINK record starts from an IMAGE of W raw Montgomery words, image[a] the word of address a = x(key, r); a >= W is refused ("address A
+outside the image of W words").  An UNLINKED access r of the paged record takes the image as its previous access: prev_1[r] = the raw
+word image[a] (a copy, as prev always is), prev_0[r] = 0 (clock 0 is the image's), the limbs those of d = x(clock, r) - 0 - 1; a clock 0 is
+refused ("clock 0 is the image's"), a d that does not fit by the range refusal, and an unlinked load must return image[a] (residues)
+where it had to return 0.  linked and last keep their meaning; linked accesses and the other LINK records are what they were.  On one
+row the order is write flag, address, clock, read rule.  THE PAGE TABLE: a_0 < .. < a_{D-1} the distinct addresses of the record's
+accesses; on the active rows i < D p_on = Montgomery(1), p_addr = the raw key word of a_i's first access, p_in = the raw word
+image[a_i], p_out / p_time = the raw value / clock word of a_i's last access, alimb_j = limb j of a_i (refused under the PAGES record's
+index when a_i >= 2^(L ng)), gap_j = limb j of a_i - a_{i-1} - 1 (zeros on row 0); active rows [D, A) get zeros in all destinations, rows
+[A, n) are never touched; D <= A always fits.  A refusal leaves the data unchanged; the lowest (record, row) over all refusals is named.
+PAGE-OUT (`reference_page_out`, zkh_page_out): image[x(p_addr, i)] = p_out[i] on every active row with p_on = 1; refused, with the image
+unchanged, on the lowest row whose p_on is not 0 / 1, whose address is >= W or does not follow a smaller one on a row with p_on = 1 (a
+table that repeats an address is REFUSED, not resolved: the rows with p_on = 1 are a prefix of strictly increasing addresses).
+Left out: the image is not bound to a commitment, sessions do not thread one, and a blob pages one memory of one value word per address.
+
 WHO WRITES A DATA COLUMN (`_check_owned` behind `check_columns` and `check_links`; csrc/arguments.h says the same).  A data column
 has at most one writer, and a derive reads only what the stages before it have finished writing.  The writers: a sorted copy (its
 tuple columns), a LIMBS / ORDER record and a LINK record (their destinations), a derived multiplicity (its column); every other
@@ -93,7 +116,8 @@ tuple); a LIMBS / ORDER record reads a sorted copy's columns and no record's des
 the multiplicities count lookup tuples, and those read every derived column freely: a lookup may count a limb.  Nothing reads a derived
 multiplicity (`check_derived`).  A term's multiplicity is the host's column or a derived one, with one exception: `linked` and
 `last` of a LINK record (only they) may be the multiplicity of a term that is not derived: -linked (addr, prev) removes the old tuple
-from the bus and -last (addr, val, clock) pages the final one out.
+from the bus and -last (addr, val, clock) pages the final one out.  The PAGES record is one more writer of the links stage: it reads what
+its LINK reads, and of its destinations p_on (only it) may be such a multiplicity.
 """
 from __future__ import annotations
 
@@ -260,7 +284,7 @@ def _columns_clause_a(i: int, r: Record, group_sizes) -> Optional[str]:
 def check_columns(terms: Sequence[Term], records: Sequence[Record], group_sizes=None) -> Optional[str]:
     """the first LIMBS / ORDER record that breaks a rule, named by its index in `records` (they are one another's only peers), or None:
     (a) the ranges of kind, L, nl, n_src and the reserved words, then (b) .. (e) of `_check_owned`"""
-    return _check_owned(terms, records, False, _columns_clause_a, group_sizes)
+    return _check_owned(terms, records, None, _columns_clause_a, group_sizes)
 
 
 KIND_LINK = 3
@@ -343,7 +367,61 @@ def check_links(terms: Sequence[Term], records: Sequence, group_sizes=None) -> O
     """the first LINK record that breaks a rule, named by its index among all `records` (all of them are its peers), or None: (a) the
     ranges of nc, L, nl, the flag word and the write flag's words (version 6), the reserved words and the selector a code column, then
     (b) .. (e) of `_check_owned`; the write flag of a READS record is one of its sources"""
-    return _check_owned(terms, records, True, _links_clause_a, group_sizes)
+    return _check_owned(terms, records, Link, _links_clause_a, group_sizes)
+
+
+KIND_PAGES = 4
+PAGES_WORDS = 32
+MAX_PAGE_LIMBS = 4
+PAGES_BIT = 0x10000                            # header word 7, bit 16 (version 7): the blob has a PAGES record
+
+
+@dataclass(frozen=True)
+class Pages:
+    """A PAGES record as the blob holds it (ZKA1 version 7): the fields are the blob's words, `check_pages` the rules"""
+    limb_bits: int                             # L
+    ng: int                                    # limbs of a page address and of a gap
+    link: int                                  # the blob record index of the LINK record it pages
+    dsts: Tuple[int, ...]                      # data columns: p_on, p_addr, p_in, p_out, p_time, alimb_0 .. alimb_{ng-1}, gap_0 .. gap_{ng-1}
+    reserved: bool = False                     # a word the format reserves was not 0 (parser only)
+    kind = KIND_PAGES
+
+    p_on = property(lambda self: self.dsts[0])
+    p_addr = property(lambda self: self.dsts[1])
+    p_in = property(lambda self: self.dsts[2])
+    p_out = property(lambda self: self.dsts[3])
+    p_time = property(lambda self: self.dsts[4])
+    alimbs = property(lambda self: self.dsts[5: 5 + self.ng])
+    gaps = property(lambda self: self.dsts[5 + self.ng:])
+
+    def n_dsts(self) -> int:
+        return 5 + 2 * self.ng
+
+    def words(self) -> List[int]:
+        w = [KIND_PAGES, self.limb_bits, self.ng, self.link] + [0] * 12 + list(self.dsts)
+        return w + [0] * (PAGES_WORDS - len(w))
+
+
+def _paged_link(records: Sequence, r: "Pages") -> Optional[Link]:
+    """the LINK record that the PAGES record `r` names, where it is one the rules allow: READS, a clock and one value column"""
+    t = records[r.link] if 0 <= r.link < len(records) else None
+    return t if isinstance(t, Link) and t.write is not None and t.nc == 2 and len(t.carried) == 2 else None
+
+
+def check_pages(terms: Sequence[Term], records: Sequence, group_sizes=None) -> Optional[str]:
+    """the PAGES record that breaks a rule, named by its index among all `records` (all of them are its peers), or None: (a) the ranges
+    of L and ng, the reserved words, and its target a LINK record with READS and nc = 2; then (b) .. (e) of `_check_owned`, its sources
+    being its LINK's and p_on the one destination that may be a multiplicity"""
+    def clause_a(i, r, _sizes):
+        if not (1 <= r.limb_bits <= 16 and 1 <= r.ng <= MAX_PAGE_LIMBS and r.limb_bits * r.ng <= MAX_ORDER_BITS):
+            return (f"record {i}: a PAGES record of {r.ng} limbs of {r.limb_bits} bits (1..{MAX_PAGE_LIMBS} limbs of 1..16 bits, at most "
+                    f"{MAX_ORDER_BITS} bits in all)")
+        if r.reserved or len(r.dsts) != r.n_dsts():
+            return f"record {i}: a reserved word of a PAGES record is not 0 (words 4..15 and the unused destination words)"
+        if _paged_link(records, r) is None:
+            return f"record {i}: a PAGES record pages record {r.link}, which is no LINK record with READS and two carried columns (a clock and one value)"
+        return None
+    return _check_owned(terms, records, Pages, clause_a, group_sizes)
 
 
 class _Owned(NamedTuple):
@@ -351,20 +429,27 @@ class _Owned(NamedTuple):
     index: int                                 # its index among the records
     srcs: Tuple[Tuple[int, int], ...]          # the (group, column) pairs it reads: the data-group ones have a writer or none
     dsts: Tuple[int, ...]                      # the data columns it writes
-    link: bool                                 # a LINK: it runs after every LIMBS / ORDER record
+    link: bool                                 # a LINK or the PAGES record: it runs after every LIMBS / ORDER record
+    free: int = 0                              # its first `free` destinations may be the multiplicity of a term that is not derived
 
 
-def _check_owned(terms: Sequence[Term], records: Sequence, links: bool, clause_a, group_sizes=None) -> Optional[str]:
-    """The ownership rule (the module docstring) over the LINK records of `records` (`links`) or over all of them: the first that
-    breaks a clause, or None.  Per record, in this order: `clause_a`, the kind's own ranges; (b) its sources are code or data columns
+def _check_owned(terms: Sequence[Term], records: Sequence, of, clause_a, group_sizes=None) -> Optional[str]:
+    """The ownership rule (the module docstring) over the records of `records` of the class `of` (Link, Pages; None: all of them): the
+    first that breaks a clause, or None.  Per record, in this order: `clause_a`, the kind's own ranges; (b) its sources are code or data columns
     (of the circuit, when `group_sizes` = (accum, code, data) is given), its destinations pairwise distinct data columns.  Then, per
     record again: (c) no source is a destination of any record (records never chain) or a derived multiplicity, and a LINK's is no
     sorted copy's column either; (d) no destination is written twice: by another record, a sorted copy or a derived multiplicity;
     (e) no destination is read by the source term of a sorted copy (the sort runs first) or, a LINK's, by any record, and none is a
-    term's multiplicity, a LINK's `linked` and `last` apart.  Lookup tuples read destinations freely."""
-    peers = [_Owned(i, tuple(r.srcs), tuple(r.dsts), isinstance(r, Link)) for i, r in enumerate(records)]
-    mine = [v for v in peers if v.link] if links else peers
-    for i, srcs, dsts, _ in mine:
+    term's multiplicity, a LINK's `linked` and `last` and a PAGES record's `p_on` apart.  A PAGES record reads what its LINK reads.
+    Lookup tuples read destinations freely."""
+    def view(i, r):
+        if isinstance(r, Pages):
+            t = _paged_link(records, r)
+            return _Owned(i, () if t is None else tuple(t.srcs), tuple(r.dsts), True, 1)
+        return _Owned(i, tuple(r.srcs), tuple(r.dsts), isinstance(r, Link), 2 if isinstance(r, Link) else 0)
+    peers = [view(i, r) for i, r in enumerate(records)]
+    mine = peers if of is None else [v for v in peers if isinstance(records[v.index], of)]
+    for i, srcs, dsts, _, _ in mine:
         problem = clause_a(i, records[i], group_sizes)
         if problem:
             return problem
@@ -376,7 +461,7 @@ def _check_owned(terms: Sequence[Term], records: Sequence, links: bool, clause_a
                 return f"record {i}: destination {c} is not a data column"
             if c in dsts[:e]:
                 return f"record {i}: its destination (data {c}) appears twice"
-    for i, srcs, dsts, link in mine:
+    for i, srcs, dsts, link, free in mine:
         for g, c in srcs:
             if g != GROUP_DATA:
                 continue
@@ -405,20 +490,28 @@ def _check_owned(terms: Sequence[Term], records: Sequence, links: bool, clause_a
                 if t.sorted_from is not None and 0 <= t.sorted_from < len(terms) and (GROUP_DATA, c) in terms[t.sorted_from].tuple_cols:
                     return f"record {i}: its destination (data {c}) is read by term {t.sorted_from}, the source of a sorted copy (the sort runs first)"
             for j, t in enumerate(terms):
-                if t.mult == (GROUP_DATA, c) and not (link and e < 2):
+                if t.mult == (GROUP_DATA, c) and e >= free:
                     return (f"record {i}: its destination (data {c}) is the multiplicity of term {j}"
-                            + (" (of a LINK's destinations only linked and last may be)" if link else ""))
+                            + ((" (of a LINK's destinations only linked and last may be)" if free == 2 else
+                                " (of a PAGES record's destinations only p_on may be)") if link else ""))
     return None
 
 
 def _check_records(terms: Sequence[Term], records: Sequence, group_sizes=None) -> Optional[str]:
-    """check_columns over the LIMBS / ORDER records (they come first, so the indices are the blob's), then check_links"""
-    n_cols = sum(not isinstance(r, Link) for r in records)
+    """check_columns over the LIMBS / ORDER records (they come first, so the indices are the blob's), then check_links, then (version 7)
+    check_pages over the one PAGES record, which comes last"""
+    pages = [i for i, r in enumerate(records) if isinstance(r, Pages)]
+    if pages and pages[0] != len(records) - 1:
+        j = pages[0] + 1
+        if isinstance(records[j], Pages):
+            return f"record {j}: a second PAGES record (record {pages[0]} is one: a blob pages one memory)"
+        return f"record {j}: a record after the PAGES record {pages[0]} (the PAGES record comes last)"
+    n_cols = sum(isinstance(r, Record) for r in records)
     for i, r in enumerate(records[:n_cols]):
         if isinstance(r, Link):
-            j = next(j for j in range(i, len(records)) if not isinstance(records[j], Link))
+            j = next(j for j in range(i, len(records)) if isinstance(records[j], Record))
             return f"record {j}: a LIMBS / ORDER record after the LINK record {i} (LINK records come last)"
-    return check_columns(terms, records[:n_cols], group_sizes) or check_links(terms, records, group_sizes)
+    return check_columns(terms, records[:n_cols], group_sizes) or check_links(terms, records, group_sizes) or check_pages(terms, records, group_sizes)
 
 
 def _by_column(terms: Sequence[Term]) -> List[Term]:
@@ -452,7 +545,14 @@ class Arguments:
         return sum(isinstance(r, Link) and r.write is not None for r in self.records)
 
     @property
+    def pages(self) -> Optional["Pages"]:
+        """the PAGES record (version 7: bit 16 of header word 7), or None"""
+        return next((r for r in self.records if isinstance(r, Pages)), None)
+
+    @property
     def version(self) -> int:
+        if self.pages is not None:
+            return 7
         if self.reads:
             return 6
         if any(isinstance(r, Link) for r in self.records):
@@ -464,7 +564,8 @@ class Arguments:
         return 2 if any(t.derive for t in self.terms) else 1
 
     def blob(self) -> np.ndarray:
-        words = [ARGS_MAGIC, self.version, self.k, self.alpha, self.beta, len(self.terms), len(self.records), self.reads]
+        words = [ARGS_MAGIC, self.version, self.k, self.alpha, self.beta, len(self.terms), len(self.records),
+                 self.reads | (PAGES_BIT if self.pages is not None else 0)]
         for t in _by_column(self.terms):
             rec = [t.col, 0 if t.sign == 1 else 1, NONE if t.sel is None else t.sel,
                    NONE if t.mult is None else t.mult[0], 0 if t.mult is None else t.mult[1], t.tag % P, len(t.tuple_cols), t.flags()]
@@ -479,7 +580,8 @@ class Arguments:
     @staticmethod
     def parse(blob: Sequence[int]) -> "Arguments":
         d = [int(x) for x in np.asarray(blob, dtype=np.uint32)]
-        if len(d) < ARGS_HEADER or d[0] != ARGS_MAGIC or d[1] not in (1, 2, 3, 4, 5, 6) or (d[1] == 6 and d[7] == 0):
+        if len(d) < ARGS_HEADER or d[0] != ARGS_MAGIC or d[1] not in (1, 2, 3, 4, 5, 6, 7) or (d[1] == 6 and d[7] == 0) or \
+                (d[1] == 7 and not d[7] & PAGES_BIT):
             raise ValueError("not a ZKA1 argument blob")
         version = d[1]
         k, alpha, beta, n = d[2], d[3], d[4], d[5]
@@ -488,7 +590,8 @@ class Arguments:
         for _ in range(n_rec):                                                # a LINK record (version 5) takes two slots
             if at > len(d):                                                   # past the blob's end: refused below, whatever n_rec says
                 break
-            sizes.append(LINK_WORDS if version >= 5 and at < len(d) and d[at] == KIND_LINK else RECORD_WORDS)
+            wide = at < len(d) and ((version >= 5 and d[at] == KIND_LINK) or (version >= 7 and d[at] == KIND_PAGES))
+            sizes.append(LINK_WORDS if wide else RECORD_WORDS)
             at += sizes[-1]
         if len(d) != at:
             raise ValueError(f"ZKA1: {len(d)} words for {n} terms" + (f" and {n_rec} records" if version >= 4 else ""))
@@ -516,6 +619,10 @@ class Arguments:
         for i in range(n_rec):
             at = ARGS_HEADER + TERM_WORDS * n + sum(sizes[:i])
             r = d[at: at + sizes[i]]
+            if sizes[i] == PAGES_WORDS and r[0] == KIND_PAGES:
+                n_dst = min(16, 5 + 2 * min(r[2], 8))
+                records.append(Pages(r[1], r[2], r[3], tuple(r[16: 16 + n_dst]), bool(any(r[4:16]) or any(r[16 + n_dst:]))))
+                continue
             if sizes[i] == LINK_WORDS:
                 nc = min(r[3], MAX_CARRIED)
                 n_dst = min(16, 2 + nc + min(r[2], 16))
@@ -533,8 +640,11 @@ class Arguments:
             records.append(Record(r[0], r[1], r[2], tuple((r[4 + 2 * j], r[5 + 2 * j]) for j in range(min(n_src, 2))), tuple(r[8: 8 + n_dst]),
                                   reserved, None if n_src <= 2 else n_src))
         n_reads = sum(isinstance(r, Link) and r.write is not None for r in records)
-        if version >= 6 and d[7] != n_reads:
-            raise ValueError(f"ZKA1: header word 7 is {d[7]}, the blob has {n_reads} LINK records with READS")
+        word7 = d[7] ^ PAGES_BIT if version >= 7 else d[7]                     # version 7: bit 16 says PAGES, the rest counts as before
+        if version >= 6 and word7 != n_reads:
+            raise ValueError(f"ZKA1: header word 7 is {word7}, the blob has {n_reads} LINK records with READS")
+        if version >= 7 and not any(isinstance(r, Pages) for r in records):
+            raise ValueError("ZKA1: header word 7 has bit 16 (PAGES), but the blob has no PAGES record")
         problem = check_sorted(terms) or check_derived(terms) or _check_records(terms, records)
         if problem:
             raise ValueError(f"ZKA1: {problem}")
@@ -605,11 +715,14 @@ class LogupBuilder(CircuitBuilder):
         return t
 
     def _record(self, rec):
-        at = len(self.records) if isinstance(rec, Link) else sum(not isinstance(r, Link) for r in self.records)     # LINK records come last
+        # LIMBS / ORDER records, then LINK records, then the PAGES record, which names its LINK by index: that index moves with the LINK
+        before = list(self.records)
+        at = len(before) if isinstance(rec, Pages) else sum(isinstance(r, Record) or (isinstance(rec, Link) and isinstance(r, Link)) for r in before)
+        self.records = [replace(r, link=r.link + 1) if isinstance(r, Pages) and r.link >= at else r for r in before]
         self.records.insert(at, rec)
         problem = _check_records(self.terms, self.records, self.group_sizes)
         if problem:
-            self.records.pop(at)
+            self.records = before
             raise ValueError(problem)
         return rec
 
@@ -637,13 +750,61 @@ class LogupBuilder(CircuitBuilder):
                                  len(dsts) - 2 - len(carried), tuple(int(c) for c in dsts),
                                  write=None if write is None else (int(write[0]), int(write[1]))))
 
+    def derive_pages(self, link_record: Link, dsts: Sequence[int], limb_bits: int) -> Pages:
+        """the memory of the LINK record `link_record` (one of this builder's, with READS and a clock and one value column) is PAGED
+        (ZKA1 version 7): its first access to an address takes the word of an image as its previous access, at clock 0, and the
+        library fills the data columns `dsts` = p_on, p_addr, p_in, p_out, p_time, alimb_0 .., gap_0 .. (5 + 2 ng of them) with the page
+        table: the distinct addresses in order, each with the image's word and what its last access left (`reference_links` with an
+        image; zkh_derive_links_paged)"""
+        at = next((i for i, r in enumerate(self.records) if r is link_record), None)
+        if at is None:
+            at = self.records.index(link_record) if link_record in self.records else -1
+        if at < 0:
+            raise ValueError("derive_pages: the LINK record is not one of this builder's")
+        if len(dsts) < 7 or (len(dsts) - 5) % 2:
+            raise ValueError(f"derive_pages: {len(dsts)} destinations (5 + 2 ng: p_on, p_addr, p_in, p_out, p_time, ng address limbs, ng gap limbs)")
+        return self._record(Pages(int(limb_bits), (len(dsts) - 5) // 2, at, tuple(int(c) for c in dsts)))
+
+    def paged(self, record: Link) -> Optional[Pages]:
+        """the PAGES record that pages the LINK `record`, or None"""
+        return next((r for r in self.records if isinstance(r, Pages) and 0 <= r.link < len(self.records) and self.records[r.link] == record), None)
+
+    def _limb_sum(self, cols, L):
+        total = None
+        for j, c in enumerate(cols):
+            v = self.get(GROUP_DATA, c) if j == 0 else self.mul(self.const(1 << (j * L)), self.get(GROUP_DATA, c))
+            total = v if total is None else self.add(total, v)
+        return total
+
+    def page_constraints(self, inner, body_inner, record: Pages):
+        """and onto `inner` (which the caller gates by its active selector) p_on (1 - p_on) = 0 and sum_j 2^(jL) alimb_j = p_addr, and onto
+        `body_inner` (gated by the body selector: every active row but the first) p_on (1 - p_on@1) = 0, so that p_on is a prefix, and
+        p_on (p_addr - p_addr@1 - 1 - sum_j 2^(jL) gap_j) = 0 -> (inner, body_inner).  Degree 3 with the gates.  Range-checked address
+        limbs and range-checked gaps (lookups, L ng <= 29 as in `order_constraints`) make the page addresses strictly increasing, hence
+        distinct: no address is paged in twice, and memory cannot fork."""
+        if not isinstance(record, Pages):
+            raise ValueError("page_constraints: not a PAGES record")
+        L = record.limb_bits
+        if L * record.ng > MAX_ORDER_BITS:
+            raise ValueError(f"page_constraints: {record.ng} limbs of {L} bits exceed {MAX_ORDER_BITS} bits (a negative gap must stay out of range)")
+        one = self.const(1)
+        on, addr = self.get(GROUP_DATA, record.p_on), self.get(GROUP_DATA, record.p_addr)
+        inner = self.and_eqz(inner, self.mul(on, self.sub(one, on)))
+        inner = self.and_eqz(inner, self.sub(self._limb_sum(record.alimbs, L), addr))
+        body_inner = self.and_eqz(body_inner, self.mul(on, self.sub(one, self.get(GROUP_DATA, record.p_on, 1))))
+        gap = self.sub(self.sub(self.sub(addr, self.get(GROUP_DATA, record.p_addr, 1)), one), self._limb_sum(record.gaps, L))
+        body_inner = self.and_eqz(body_inner, self.mul(on, gap))
+        return inner, body_inner
+
     def link_constraints(self, inner, record: Link):
         """and onto `inner` (which the caller gates by its body selector) the constraints that tie the LINK `record`'s witness to its
         row: linked (1 - linked) = 0, last (1 - last) = 0 and sum_j 2^(jL) limb_j = linked (c_0 - prev_0 - 1).  Degree 3 with the caller's
         gate.  Sound for clocks below 2^29 and limbs range-checked by a lookup, as `order_constraints` is: L nl <= 29.
         A record with READS adds the read rule: w (1 - w) = 0 and, per value column j >= 1, (1 - w) (c_j - linked prev_j) = 0: a load
         returns what the previous access left, or 0.  linked prev_j and not prev_j alone, so that nothing rests on the host having
-        zeroed prev_j on an unlinked row.  Degree 4 with the gate."""
+        zeroed prev_j on an unlinked row.  Degree 4 with the gate.
+        A PAGED record (`derive_pages`): linked, last and w are 0 / 1, and UNGATED sum_j 2^(jL) limb_j = c_0 - prev_0 - 1 and
+        (1 - w) (c_1 - prev_1) = 0: the first access to an address has the image's word at clock 0 as its previous access."""
         if not isinstance(record, Link):
             raise ValueError("link_constraints: not a LINK record")
         L, nl = record.limb_bits, record.nl
@@ -653,6 +814,12 @@ class LogupBuilder(CircuitBuilder):
         linked, last = self.get(GROUP_DATA, record.linked), self.get(GROUP_DATA, record.last)
         inner = self.and_eqz(inner, self.mul(linked, self.sub(one, linked)))
         inner = self.and_eqz(inner, self.mul(last, self.sub(one, last)))
+        if self.paged(record) is not None:                                   # an unlinked access has the image as its previous one: nothing is gated
+            w = self.get(*record.write)
+            inner = self.and_eqz(inner, self.mul(w, self.sub(one, w)))
+            d = self.sub(self.sub(self.get(*record.carried[0]), self.get(GROUP_DATA, record.prevs[0])), one)
+            inner = self.and_eqz(inner, self.sub(self._limb_sum(record.limbs, L), d))
+            return self.and_eqz(inner, self.mul(self.sub(one, w), self.sub(self.get(*record.carried[1]), self.get(GROUP_DATA, record.prevs[1]))))
         total = self.const(0)
         for j, c in enumerate(record.limbs):
             v = self.get(GROUP_DATA, c) if j == 0 else self.mul(self.const(1 << (j * L)), self.get(GROUP_DATA, c))
@@ -1011,7 +1178,7 @@ def reference_columns(args: Arguments, po2: int, zk_cycles: int, code, data) -> 
     groups = {GROUP_CODE: np.asarray(code, dtype=np.uint32).reshape(-1, n), GROUP_DATA: np.array(data, dtype=np.uint32).reshape(-1, n)}
     out = groups[GROUP_DATA]                                                 # sources are never destinations: no record reads what another wrote
     for i, r in enumerate(args.records):
-        if isinstance(r, Link):                                              # reference_links
+        if not isinstance(r, Record):                                        # reference_links
             continue
         L, nl, bits = r.limb_bits, r.nl, r.limb_bits * r.nl
         k = [_dec(groups[g][c, :A]).astype(np.int64) for g, c in r.srcs]
@@ -1056,17 +1223,31 @@ def _link_chain(key, rows):
     return prev, last
 
 
-def reference_links(args: Arguments, po2: int, zk_cycles: int, code, data) -> np.ndarray:
+PAGES_NEED_IMAGE = "the arguments page memory: an image is required (zkh_derive_all_paged)"
+
+
+def reference_links(args: Arguments, po2: int, zk_cycles: int, code, data, image=None) -> np.ndarray:
     """The data trace zkh_derive_links leaves (raw Montgomery words, a copy): every LINK record's destination columns on the active rows
     (module docstring), rows [A, n) as given.  Raises ReferenceError on a selector other than 0 / 1 (the lowest (record, row) over all
     records, before any clock is looked at), then on the lowest (record, row) whose clock difference d = c_0 - prev_0 - 1 is negative
     ("clock not increasing") or does not fit the limbs or, in a record with READS, whose write flag is not 0 / 1 or whose load does
-    not return the last store (0 when its address was never accessed); on one row in this order: write flag, clock, read rule."""
+    not return the last store (0 when its address was never accessed); on one row in this order: write flag, clock, read rule.
+    image: the W raw Montgomery words of the memory image, needed exactly when the arguments hold a PAGES record (ZKA1 version 7;
+    zkh_derive_links_paged).  The paged LINK record then takes, for an unlinked access to address a (the canonical value of its key),
+    the image as the previous access — prev_1 = the raw word image[a], prev_0 = 0, the limbs those of d = clock - 0 - 1 — refuses an
+    address >= W, a clock 0 ("clock 0 is the image's") and an unlinked load whose residue is not image[a]'s (on one row: write flag,
+    address, clock, read rule), and the PAGES record's destinations get the page table (module docstring, PAGING)."""
     n = 1 << po2
     A = n - zk_cycles
     groups = {GROUP_CODE: np.asarray(code, dtype=np.uint32).reshape(-1, n), GROUP_DATA: np.array(data, dtype=np.uint32).reshape(-1, n)}
     out = groups[GROUP_DATA]                                                 # sources are never destinations
     links = [(i, r) for i, r in enumerate(args.records) if isinstance(r, Link)]
+    pages = args.pages
+    if pages is not None and image is None:
+        raise ReferenceError(PAGES_NEED_IMAGE)
+    if pages is not None:
+        image = np.asarray(image, dtype=np.uint32).reshape(-1)
+        W = image.size
     on = {}
     for i, r in links:
         sel = np.ones(A, dtype=np.uint64) if r.sel is None else _dec(groups[GROUP_CODE][r.sel, :A])
@@ -1075,41 +1256,111 @@ def reference_links(args: Arguments, po2: int, zk_cycles: int, code, data) -> np
             row = int(np.argmax(bad))
             raise ReferenceError(f"record {i} at row {row}: selector {int(sel[row])}, not 0 or 1")
         on[i] = np.nonzero(sel == 1)[0]
+    writes, late = [], None                                                  # (columns, rows, words): nothing is written before every record passed
     for i, r in links:
         rows, L, nl = on[i], r.limb_bits, r.nl
-        prev, last = _link_chain(_dec(groups[r.key[0]][r.key[1], rows]), rows)
+        paged = pages is not None and pages.link == i
+        addr = _dec(groups[r.key[0]][r.key[1], rows]).astype(np.int64)
+        prev, last = _link_chain(addr, rows)
         linked = prev >= 0
-        prow = rows[np.where(linked, prev, 0)]
+        prow = rows[np.where(linked, prev, 0)] if rows.size else rows
         g0, c0 = r.carried[0]
         clock, pclock = _dec(groups[g0][c0, rows]).astype(np.int64), _dec(groups[g0][c0, prow]).astype(np.int64)
-        d = np.where(linked, clock - pclock - 1, 0)
+        d = np.where(linked, clock - pclock - 1, clock - 1 if paged else 0)
         bad = (d < 0) | (d >> (L * nl) != 0)
+        if paged:
+            outside = addr >= W
+            word = image[np.where(outside, 0, addr)] if W else np.zeros(rows.size, dtype=np.uint32)      # the image's word of an unlinked access
+            bad = bad | outside
         if r.write is not None:
             w = _dec(groups[r.write[0]][r.write[1], rows])
             now = [_dec(groups[g][c, rows]) for g, c in r.carried]
-            before = [np.where(linked, _dec(groups[g][c, prow]), 0) for g, c in r.carried]
+            before = [np.where(linked, _dec(groups[g][c, prow]), _dec(word) if paged and e == 1 else 0) for e, (g, c) in enumerate(r.carried)]
             misread = [(w == 0) & (now[e] != before[e]) for e in range(1, len(r.carried))]
             bad = bad | (w > 1) | np.logical_or.reduce(misread)
         if bad.any():
             j = int(np.argmax(bad))
+            at = f"record {i} at row {int(rows[j])}"
             if r.write is not None and w[j] > 1:
-                raise ReferenceError(f"record {i} at row {int(rows[j])}: write flag {int(w[j])}, not 0 or 1")
+                raise ReferenceError(f"{at}: write flag {int(w[j])}, not 0 or 1")
+            if paged and outside[j]:
+                raise ReferenceError(f"{at}: address {int(addr[j])} outside the image of {W} words")
+            if paged and not linked[j] and clock[j] == 0:
+                raise ReferenceError(f"{at}: clock 0 is the image's")
             if r.write is not None and d[j] >= 0 and d[j] >> (L * nl) == 0:
                 e = next(e for e in range(1, len(r.carried)) if misread[e - 1][j])
-                raise ReferenceError(f"record {i} at row {int(rows[j])}: a load of carried column {e} returns {int(now[e][j])}, but " + (
-                    f"{int(before[e][j])} was last stored (row {int(prow[j])})" if linked[j] else "its address was never accessed: the value must be 0"))
+                raise ReferenceError(f"{at}: a load of carried column {e} returns {int(now[e][j])}, but " + (
+                    f"{int(before[e][j])} was last stored (row {int(prow[j])})" if linked[j] else
+                    f"the image holds {int(before[e][j])} at its address {int(addr[j])}" if paged else "its address was never accessed: the value must be 0"))
             if d[j] < 0:
-                raise ReferenceError(f"record {i} at row {int(rows[j])}: clock not increasing ({int(clock[j])} after {int(pclock[j])} at row {int(prow[j])})")
-            raise ReferenceError(f"record {i} at row {int(rows[j])}: the clock difference {int(d[j])} (after row {int(prow[j])}) does not fit {nl} limbs of {L} bits")
-        vals = [np.where(linked, groups[g][c, prow], 0).astype(np.uint32) for g, c in r.carried]
-        out[list(r.dsts), :A] = 0
-        out[r.linked, rows] = _enc(linked.astype(np.uint64)).astype(np.uint32)
-        out[r.last, rows] = _enc(last.astype(np.uint64)).astype(np.uint32)
-        for c, v in zip(r.prevs, vals):
-            out[c, rows] = v
-        for j, c in enumerate(r.limbs):
-            out[c, rows] = _enc((d >> (j * L)) & ((1 << L) - 1)).astype(np.uint32)
+                raise ReferenceError(f"{at}: clock not increasing ({int(clock[j])} after {int(pclock[j])} at row {int(prow[j])})")
+            after = f"after row {int(prow[j])}" if linked[j] else "after the image"
+            raise ReferenceError(f"{at}: the clock difference {int(d[j])} ({after}) does not fit {nl} limbs of {L} bits")
+        vals = [np.where(linked, groups[g][c, prow], word if paged and e == 1 else 0).astype(np.uint32) for e, (g, c) in enumerate(r.carried)]
+        writes.append((list(r.dsts), slice(0, A), 0))
+        writes.append((r.linked, rows, _enc(linked.astype(np.uint64)).astype(np.uint32)))
+        writes.append((r.last, rows, _enc(last.astype(np.uint64)).astype(np.uint32)))
+        writes += [(c, rows, v) for c, v in zip(r.prevs, vals)]
+        writes += [(c, rows, _enc((d >> (j * L)) & ((1 << L) - 1)).astype(np.uint32)) for j, c in enumerate(r.limbs)]
+        if paged:                                                            # the page table: the distinct addresses in order
+            first, final = rows[~linked], rows[last]                         # the first and the last access of every address ...
+            first, final = first[np.argsort(addr[~linked], kind="stable")], final[np.argsort(addr[last], kind="stable")]       # ... by address
+            a = np.sort(addr[~linked])
+            D, Lp, ng = a.size, pages.limb_bits, pages.ng
+            wide = a >> (Lp * ng) != 0
+            if wide.any():
+                j = int(np.argmin(np.where(wide, first, A)))                 # the PAGES record comes last: any LINK's refusal goes first
+                late = f"record {args.records.index(pages)} at row {int(first[j])}: address {int(a[j])} does not fit {ng} limbs of {Lp} bits"
+                continue
+            gap = np.zeros(D, dtype=np.int64)
+            gap[1:] = a[1:] - a[:-1] - 1
+            top = slice(0, D)
+            writes.append((list(pages.dsts), slice(0, A), 0))
+            writes.append((pages.p_on, top, np.uint32(_R)))
+            writes.append((pages.p_addr, top, groups[r.key[0]][r.key[1], first]))
+            writes.append((pages.p_in, top, image[a]))
+            writes.append((pages.p_out, top, groups[r.carried[1][0]][r.carried[1][1], final]))
+            writes.append((pages.p_time, top, groups[g0][c0, final]))
+            for j in range(ng):
+                writes.append((pages.alimbs[j], top, _enc((a >> (j * Lp)) & ((1 << Lp) - 1)).astype(np.uint32)))
+                writes.append((pages.gaps[j], top, _enc((gap >> (j * Lp)) & ((1 << Lp) - 1)).astype(np.uint32)))
+    if late:
+        raise ReferenceError(late)
+    for cols, rows, words in writes:
+        out[cols, rows] = words
     return out.reshape(-1)
+
+
+def reference_page_out(args: Arguments, po2: int, zk_cycles: int, data, image) -> np.ndarray:
+    """The image zkh_page_out leaves (raw Montgomery words, a copy): image[x(p_addr, i)] = the raw word p_out[i] on every active row i
+    with p_on = 1 of the PAGES record's table in `data`.  Raises ReferenceError, with the image unchanged, on the lowest row whose
+    p_on is not 0 / 1, whose address is outside the image or, the table being the host's own, whose address does not follow a smaller
+    one: the page addresses of rows 0 .. D - 1 strictly increase and p_on is 1 exactly there, as the circuit demands, so no address
+    is written twice (a repeated address is REFUSED, not resolved).  On one row in this order."""
+    n = 1 << po2
+    A = n - zk_cycles
+    pages = args.pages
+    if pages is None:
+        raise ReferenceError("the arguments hold no PAGES record (ZKA1 version 7)")
+    i = args.records.index(pages)
+    d = np.asarray(data, dtype=np.uint32).reshape(-1, n)
+    out = np.array(image, dtype=np.uint32).reshape(-1)
+    W = out.size
+    on, addr = _dec(d[pages.p_on, :A]).astype(np.int64), _dec(d[pages.p_addr, :A]).astype(np.int64)
+    pon, paddr = np.concatenate([[1], on[:-1]]), np.concatenate([[-1], addr[:-1]])
+    live = on == 1
+    follows = (pon == 1) & (paddr < addr)
+    bad = (on > 1) | (live & ((addr >= W) | ~follows))
+    if bad.any():
+        r = int(np.argmax(bad))
+        at = f"record {i} at row {r}"
+        if on[r] > 1:
+            raise ReferenceError(f"{at}: p_on {int(on[r])}, not 0 or 1")
+        if addr[r] >= W:
+            raise ReferenceError(f"{at}: address {int(addr[r])} outside the image of {W} words")
+        raise ReferenceError(f"{at}: page address {int(addr[r])} does not follow a smaller one (row {r - 1}: p_on {int(pon[r])}, address {int(paddr[r])})")
+    out[addr[live]] = d[pages.p_out, :A][live]
+    return out
 
 
 def bus_slots(A: int, distinct_keys: int) -> int:

@@ -40,7 +40,17 @@ SYN-LOOKUP-reads (`syn_lookup_reads`, `build_syn_lookup(shape, link=True, reads=
 memory pair one more data column, the write flag w (after every pair's link columns: `reads_layout`), the host's; the LINK record has
 READS (ZKA1 version 6), so zkh_derive_links refuses a load (w = 0) that does not return pval, or 0 where it is not linked, and
 logup.link_constraints adds w (1 - w) = 0 and (1 - w) (val - linked pval) = 0.  `witness(link=..., reads=True)` is a real load / store
-trace; `misread_row` forges one load so that the bus still balances.  Paging memory in and out through an image is still left out.
+trace; `misread_row` forges one load so that the bus still balances.
+SYN-LOOKUP-paged (`syn_lookup_paged`, `build_syn_lookup(shape, link=True, reads=True, pages=True)`; one memory pair): SYN-LOOKUP-reads
+whose memory is paged in from an image and out again.  After the write flag come the page table's columns (`pages_layout`): p_on, p_addr,
+p_in, p_out, p_time and `order_limbs` limbs each of the page address and of the gap to the page before.  On the bus (tag 1): every access
+adds (addr, val, time) and removes (addr, pval, ptime), UNGATED: the first access to an address removes (addr, image word, 0), which the
+page table put there with +p_on (p_addr, p_in) — a width-2 tuple, the key (addr, val, 0) — and -p_on (p_addr, p_out, p_time) pages the
+final tuple of every address out.  Nothing uses linked or last as a multiplicity.  The link limbs, the address limbs and the gap limbs are
+lookups of tag 0; logup.link_constraints (paged) and logup.page_constraints tie them to the rows, so the page addresses strictly increase
+and no address is paged in twice.  The link columns are the LINK record's, the table a PAGES record's (ZKA1 version 7): the library fills
+both from the image (zkh_derive_links_paged; `witness(link=False, pages=False)` leaves them zero).  Times are row + 1 (clock 0 is the
+image's), so the limbs must cover A: 2^(order_limbs L) > A.  `fork_page` forges a table that pages one address in twice.
 Not a shipped circuit: its control root is zkh_code_root of its code trace.
 """
 from __future__ import annotations
@@ -105,17 +115,32 @@ def reads_layout(n_words: int, n_limbs: int, n_mem: int, order_limbs: int = ORDE
     return [base + i for i in range(n_mem)]
 
 
+PAGE_W = 5                          # p_on, p_addr, p_in, p_out, p_time
+
+
+def pages_layout(n_words: int, n_limbs: int, n_mem: int = 1, order_limbs: int = ORDER_LIMBS):
+    """data column indices of SYN-LOOKUP-paged's page table, after `reads_layout`'s write flag: [p_on, p_addr, p_in, p_out, p_time,
+    alimb_0 .. alimb_{order_limbs-1}, gap_0 .. gap_{order_limbs-1}]"""
+    base = n_words + n_words * n_limbs + 1 + (LINK_W + order_limbs) * n_mem + n_mem
+    return [base + e for e in range(PAGE_W + 2 * order_limbs)]
+
+
 def build_syn_lookup(shape: Shape = FULL, derive: bool = False, sort: bool = False,
                      sort_keys: Tuple[int, ...] = SORT_KEYS, limbs: bool = False, order: bool = False,
-                     order_limbs: int = ORDER_LIMBS, link: bool = False, reads: bool = False) -> Tuple[np.ndarray, np.ndarray]:
+                     order_limbs: int = ORDER_LIMBS, link: bool = False, reads: bool = False, pages: bool = False) -> Tuple[np.ndarray, np.ndarray]:
     """-> (ZKC1 description, ZKA1 argument blob); derive: the table term's multiplicity is derived by the library (version-2 blob,
     the description unchanged); sort: every permuted copy is the library's sorted copy of its memory tuple by the tuple positions
     `sort_keys` (version-3 blob, the description unchanged); limbs: every word's limbs are a LIMBS record (version-4 blob, the
     description unchanged); order: SYN-LOOKUP-ordered, another description (module docstring), its order columns an ORDER record over
     the copy's (addr, time); link: SYN-LOOKUP-linked, another description (module docstring), its link columns a LINK record (version-5
     blob); it has no sorted copy, so it refuses `sort` and `order`; reads: SYN-LOOKUP-reads, SYN-LOOKUP-linked with a write flag per
-    memory pair and the read rule (version-6 blob, another description); it needs `link`"""
+    memory pair and the read rule (version-6 blob, another description); it needs `link`; pages: SYN-LOOKUP-paged, SYN-LOOKUP-reads
+    with its one memory paged in from an image and out again (version-7 blob, another description); it needs `link`, `reads` and n_mem = 1"""
     n_words, n_limbs, limb_bits, n_mem = shape
+    if pages and not (link and reads):
+        raise ValueError("build_syn_lookup: pages=True pages the memory of a LINK record with the read rule: it needs link=True, reads=True")
+    if pages and n_mem != 1:
+        raise ValueError(f"build_syn_lookup: pages=True pages one memory: n_mem is {n_mem}")
     if reads and not link:
         raise ValueError("build_syn_lookup: reads=True is the read rule of the LINK records: it needs link=True")
     if link and (sort or order):
@@ -129,6 +154,10 @@ def build_syn_lookup(shape: Shape = FULL, derive: bool = False, sort: bool = Fal
         wd = m + 1 + sum(len(c) for c in lcols) + n_mem * bool(reads)
         n_terms = n_words * n_limbs + 1 + 3 * n_mem + n_mem * order_limbs
     wcols = reads_layout(n_words, n_limbs, n_mem, order_limbs) if reads else [None] * n_mem
+    pcols = pages_layout(n_words, n_limbs, n_mem, order_limbs) if pages else []
+    if pages:
+        wd += len(pcols)
+        n_terms += 1 + 2 * order_limbs
     k = (n_terms + 2) // 3
     b = LogupBuilder((4 * k, N_CODE, wd), (4, 8), alpha=0, beta=4)
     code = lambda c: b.get(GROUP_CODE, c)
@@ -143,12 +172,18 @@ def build_syn_lookup(shape: Shape = FULL, derive: bool = False, sort: bool = Fal
         specs.append(dict(tuple_cols=[(GROUP_DATA, c) for c in mem[i]], sign=1, tag=1))
         copy = dict(sorted_from=len(specs) - 1, sort_keys=sort_keys) if sort else {}
         specs.append(dict(tuple_cols=[(GROUP_DATA, c) for c in perm[i]], sign=-1, tag=1, **copy))
-    for c_addr, c_val, c_time, c_linked, c_last, c_pval, c_ptime, *_ in lcols:
+    for c_addr, c_val, c_time, c_linked, c_last, c_pval, c_ptime, *_ in lcols if pages else []:
+        specs.append(dict(tuple_cols=[(GROUP_DATA, c_addr), (GROUP_DATA, c_val), (GROUP_DATA, c_time)], sign=1, tag=1))
+        specs.append(dict(tuple_cols=[(GROUP_DATA, c_addr), (GROUP_DATA, c_pval), (GROUP_DATA, c_ptime)], sign=-1, tag=1))
+        specs.append(dict(tuple_cols=[(GROUP_DATA, pcols[1]), (GROUP_DATA, pcols[2])], sign=1, mult=(GROUP_DATA, pcols[0]), tag=1))
+        specs.append(dict(tuple_cols=[(GROUP_DATA, pcols[1]), (GROUP_DATA, pcols[3]), (GROUP_DATA, pcols[4])], sign=-1, mult=(GROUP_DATA, pcols[0]), tag=1))
+    for c_addr, c_val, c_time, c_linked, c_last, c_pval, c_ptime, *_ in [] if pages else lcols:
         specs.append(dict(tuple_cols=[(GROUP_DATA, c_addr), (GROUP_DATA, c_val), (GROUP_DATA, c_time)], sign=1, tag=1))
         specs.append(dict(tuple_cols=[(GROUP_DATA, c_addr), (GROUP_DATA, c_pval), (GROUP_DATA, c_ptime)], sign=-1, mult=(GROUP_DATA, c_linked), tag=1))
         specs.append(dict(tuple_cols=[(GROUP_DATA, c_addr), (GROUP_DATA, c_val), (GROUP_DATA, c_time)], sign=-1, mult=(GROUP_DATA, c_last), tag=1))
     specs += [dict(tuple_cols=[(GROUP_DATA, c)], tag=0) for cols in ocols for c in cols[1:]]
     specs += [dict(tuple_cols=[(GROUP_DATA, c)], tag=0) for cols in lcols for c in cols[LINK_W:]]
+    specs += [dict(tuple_cols=[(GROUP_DATA, c)], tag=0) for c in pcols[PAGE_W:]]
     for i, s in enumerate(specs):
         b.term(i // 3, **s)
     if limbs_flag:
@@ -159,6 +194,7 @@ def build_syn_lookup(shape: Shape = FULL, derive: bool = False, sort: bool = Fal
     links = [b.derive_links(None, (GROUP_DATA, c[0]), [(GROUP_DATA, c[2]), (GROUP_DATA, c[1])], [c[3], c[4], c[6], c[5]] + c[LINK_W:], limb_bits,
                             write=None if w is None else (GROUP_DATA, w))
              for c, w in zip(lcols, wcols)]
+    table = b.derive_pages(links[0], pcols, limb_bits) if pages else None
     # words = sum of their limbs, on active rows
     inner = b.true()
     for kk in range(n_words):
@@ -178,7 +214,11 @@ def build_syn_lookup(shape: Shape = FULL, derive: bool = False, sort: bool = Fal
         inner = b.true()
         for rec in links:
             inner = b.link_constraints(inner, rec)
+        if table is not None:
+            inner, body_inner = b.page_constraints(inner, b.true(), table)
         chain = b.and_cond(chain, active, inner)
+        if table is not None:
+            chain = b.and_cond(chain, body, body_inner)
     chain = b.and_eqz(chain, b.mul(active, b.sub(one, active)))
     chain = b.and_eqz(chain, b.mul(first, b.sub(one, first)))
     chain = b.and_eqz(chain, b.sub(b.sub(active, first), body))
@@ -225,13 +265,21 @@ def syn_lookup_reads() -> Tuple[np.ndarray, np.ndarray]:
     return build_syn_lookup(FULL, link=True, reads=True)
 
 
+def syn_lookup_tiny_paged() -> Tuple[np.ndarray, np.ndarray]:
+    return build_syn_lookup(TINY, link=True, reads=True, pages=True)
+
+
+def syn_lookup_paged() -> Tuple[np.ndarray, np.ndarray]:
+    return build_syn_lookup(FULL, link=True, reads=True, pages=True)
+
+
 def _enc(x) -> np.ndarray:
     return ((np.asarray(x, dtype=np.uint64) % np.uint64(P)) * np.uint64((1 << 32) % P) % np.uint64(P)).astype(np.uint32)
 
 
 def witness(shape: Shape, po2: int, zk_cycles: int, seed: int = 1, count: bool = True, sort: bool = True, addr_range: int = 1 << 20,
             sort_keys: Tuple[int, ...] = SORT_KEYS, limbs: bool = True, order=None, order_limbs: int = ORDER_LIMBS, link=None,
-            reads: bool = False):
+            reads: bool = False, pages=None, image=None):
     """-> (code, data, out_global) host arrays of raw Montgomery words: random words below min(P, 2^(n_limbs L)) split into limbs
     (limbs=False: zero, for the library to split), the table's multiplicities (count=False: zero, for the library to derive), random
     memory tuples (addresses below `addr_range`) and their copy stably sorted by the tuple positions `sort_keys`, (addr, time)
@@ -243,7 +291,14 @@ def witness(shape: Shape, po2: int, zk_cycles: int, seed: int = 1, count: bool =
     one access after another (and the limbs counted) / left zero for the library.
     reads: SYN-LOOKUP-reads' witness (`build_syn_lookup(link=True, reads=True)`; it needs `link` True or False): a load / store trace.
     Every access draws a write flag, and a load takes the value the previous access to its address left, or 0 without one; the write
-    flags are the host's column whatever `link` says"""
+    flags are the host's column whatever `link` says.
+    pages: None = no paging; True / False = SYN-LOOKUP-paged's witness (`build_syn_lookup(link=True, reads=True, pages=True)`; it needs
+    `link`, `reads` and `image`, the W raw Montgomery words of the memory image, each below P): the times are row + 1, the addresses
+    below min(addr_range, W), a load takes the last store or else the image's word, an access without a previous one has (pval, ptime) =
+    (image word, 0) and the limbs of time - 1, and the page table is host-made by a walk over the sorted distinct addresses (its limbs
+    counted) / left zero for the library"""
+    if pages is not None and (link is None or not reads or image is None):
+        raise ValueError("witness: pages= pages the memory of the LINK record with the read rule: it needs link=, reads=True and image=")
     if reads and link is None:
         raise ValueError("witness: reads=True is the read rule of the LINK records: it needs link=True or link=False")
     n_words, n_limbs, limb_bits, n_mem = shape
@@ -253,9 +308,18 @@ def witness(shape: Shape, po2: int, zk_cycles: int, seed: int = 1, count: bool =
     lcols = link_layout(n_words, n_limbs, n_mem, order_limbs) if link is not None else []
     wd = m_col + 1 + (sum(len(c) for c in lcols) + n_mem * bool(reads) if lcols else 2 * MEM_W * n_mem + sum(len(c) for c in ocols))
     wcols = reads_layout(n_words, n_limbs, n_mem, order_limbs) if reads else []
+    pcols = pages_layout(n_words, n_limbs, n_mem, order_limbs) if pages is not None else []
+    wd += len(pcols)
     n = 1 << po2
     A = n - zk_cycles
     T = 1 << limb_bits
+    if pcols:
+        assert n_mem == 1, "one memory is paged"
+        image = np.asarray(image, dtype=np.uint32).reshape(-1)
+        assert (image < P).all(), "the witness holds canonical Montgomery words: an image word >= P has no host-made twin"
+        assert A < 1 << (order_limbs * limb_bits), f"times reach {A}: they do not fit {order_limbs} limbs of {limb_bits} bits"
+        held0 = (image.astype(np.uint64) * np.uint64(pow((1 << 32) % P, -1, P)) % np.uint64(P)).tolist()     # the image, canonical
+        addr_range = min(addr_range, image.size, 1 << (order_limbs * limb_bits))
     assert A >= T, f"po2 {po2}: {A} active rows do not hold the {T}-row table"
     rng = np.random.default_rng(seed)
     code = np.zeros((N_CODE, n), dtype=np.uint64)
@@ -287,9 +351,12 @@ def witness(shape: Shape, po2: int, zk_cycles: int, seed: int = 1, count: bool =
             held = {}
             for r, a in enumerate(addr.tolist()):
                 if not store[r]:
-                    val[r] = held.get(a, 0)
+                    val[r] = held.get(a, held0[a] if pcols else 0)
                 held[a] = val[r]
             data[wcols[i], :A] = store
+        if pcols:
+            _paged_witness(data, lcols[i], pcols, addr, val, held0, A, limb_bits, order_limbs, link, pages, counts)
+            continue
         if lcols:
             _link_witness(data, lcols[i], addr, val, A, limb_bits, order_limbs, link, counts)
             continue
@@ -344,6 +411,79 @@ def _link_witness(data, cols, addr, val, A, limb_bits, order_limbs, fill, counts
         if fill:
             data[c, :A] = limb.astype(np.uint64)
         counts += np.bincount(limb, minlength=T)
+
+
+def _paged_witness(data, cols, pcols, addr, val, image, A, limb_bits, order_limbs, fill, fill_pages, counts):
+    """the memory pair of SYN-LOOKUP-paged: `_link_witness` with times row + 1 and the image (canonical words) behind every first access,
+    and the page table from a walk over the distinct addresses in order"""
+    c_addr, c_val, c_time, c_linked, c_last, c_pval, c_ptime, *c_limbs = cols
+    T = 1 << limb_bits
+    time = np.arange(1, A + 1, dtype=np.uint64)
+    data[c_addr, :A], data[c_val, :A], data[c_time, :A] = addr, val, time
+    seen, first, prev = {}, {}, [-1] * A
+    for r, a in enumerate(addr.tolist()):
+        prev[r] = seen.get(a, -1)
+        first.setdefault(a, r)
+        seen[a] = r
+    prev = np.asarray(prev, dtype=np.int64)
+    on = prev >= 0
+    q = np.where(on, prev, 0)
+    linked, last = on.astype(np.uint64), np.ones(A, dtype=np.uint64)
+    last[prev[on]] = 0
+    img = np.asarray(image, dtype=np.uint64)
+    pval, ptime = np.where(on, val[q], img[addr.astype(np.int64)]).astype(np.uint64), np.where(on, time[q], 0).astype(np.uint64)
+    d = time.astype(np.int64) - ptime.astype(np.int64) - 1
+    assert (d >> (order_limbs * limb_bits) == 0).all(), "a time difference does not fit the link limbs"
+    if fill:
+        data[c_linked, :A], data[c_last, :A], data[c_pval, :A], data[c_ptime, :A] = linked, last, pval, ptime
+    for j, c in enumerate(c_limbs):
+        limb = (d >> (j * limb_bits)) & (T - 1)
+        if fill:
+            data[c, :A] = limb.astype(np.uint64)
+        counts += np.bincount(limb, minlength=T)
+    below = -1
+    for i, a in enumerate(sorted(seen)):                                     # the page table: one row per distinct address, in order
+        gap = a - below - 1 if i else 0
+        row = [1, a, image[a], int(val[seen[a]]), int(time[seen[a]])] + [(a >> (j * limb_bits)) & (T - 1) for j in range(order_limbs)] + \
+            [(gap >> (j * limb_bits)) & (T - 1) for j in range(order_limbs)]
+        assert a >> (order_limbs * limb_bits) == 0
+        if fill_pages:
+            data[pcols, i] = row
+        for v in row[PAGE_W:]:
+            counts[v] += 1
+        below = a
+    counts[0] += 2 * order_limbs * (A - len(seen))                           # the rows below the table look their zero limbs up as well
+
+
+def fork_page(shape: Shape, data, po2: int, zk_cycles: int, image, order_limbs: int = ORDER_LIMBS):
+    """-> (a copy of SYN-LOOKUP-paged's host-made `data` in which one address is paged in TWICE, the row of the second page).  A store r
+    that is linked (it has an earlier access to its address a) is cut loose: it takes (image[a], 0) as its previous access, as a first
+    access would, with the limbs of time - 1.  The tuple its earlier access left is then paged out by a second table row for a, put
+    right after a's own (the rows below move down by one; the limbs are a's, the gap limbs zeros, which the table holds): + p_on
+    (a, image[a]) twice against the two removals, and the bus balances.  The multiplicities have to be counted again.  Only
+    logup.page_constraints objects, on the second row: its address does not exceed the one before."""
+    n = 1 << po2
+    A = n - zk_cycles
+    d = np.array(data, dtype=np.uint32).reshape(-1, n)
+    image = np.asarray(image, dtype=np.uint32).reshape(-1)
+    c_addr, c_val, c_time, c_linked, c_last, c_pval, c_ptime, *c_limbs = link_layout(shape.n_words, shape.n_limbs, shape.n_mem, order_limbs)[0]
+    c_w = reads_layout(shape.n_words, shape.n_limbs, shape.n_mem, order_limbs)[0]
+    pcols = pages_layout(shape.n_words, shape.n_limbs, shape.n_mem, order_limbs)
+    R, T = (1 << 32) % P, 1 << shape.limb_bits
+    rinv = pow(R, -1, P)
+    dec = lambda v: int(v) % P * rinv % P
+    D = int((d[pcols[0], :A] != 0).sum())
+    assert D < A, "the table has no free row"
+    r = next(r for r in range(A // 2, A) if d[c_w, r] != 0 and d[c_linked, r] != 0)      # a linked store
+    a = dec(d[c_addr, r])
+    i = next(i for i in range(D) if dec(d[pcols[1], i]) == a)
+    second = [R, d[c_addr, r], image[a], d[c_pval, r], d[c_ptime, r]] + [d[pcols[PAGE_W + j], i] for j in range(order_limbs)] + [0] * order_limbs
+    d[pcols, i + 2:D + 1] = d[pcols, i + 1:D].copy()
+    d[pcols, i + 1] = second
+    d[c_pval, r], d[c_ptime, r] = image[a], 0
+    for j, c in enumerate(c_limbs):
+        d[c, r] = ((dec(d[c_time, r]) - 1) >> (j * shape.limb_bits)) % T * R % P
+    return d.reshape(-1), i + 1
 
 
 def witness_equal_keys(shape: Shape, po2: int, zk_cycles: int, seed: int = 1, sort: bool = True, addr_range: int = 5):

@@ -1,7 +1,7 @@
 // arguments.h — lookup and permutation arguments as data (ZKA1 blob; zeth_amd/circuits/logup.py; DESIGN.md §2 ARGUMENTS): the decoded
 // form every consumer reads, and what the consumers share.  arguments.hip owns the blob format and the rules a blob must keep;
 // accumulate.hip (zkh_accumulate), multiplicities.hip (zkh_derive_multiplicities), sort.hip (zkh_derive_sorted), columns.hip
-// (zkh_derive_columns) and links.hip (zkh_derive_links) read zkh_circuit::args and never see a blob word.
+// (zkh_derive_columns) and links.hip (zkh_derive_links, zkh_derive_links_paged, zkh_page_out) read zkh_circuit::args and never see a blob word.
 //
 // WHO WRITES A DATA COLUMN (the module docstring of logup.py says the same; check_owned in arguments.hip keeps it).  A data column has at
 // most one writer, and a derive reads only what the stages before it have finished writing.  The writers: a sorted copy (its tuple
@@ -11,7 +11,8 @@
 // columns a derive writes, the sort reads none; a LIMBS / ORDER record reads a sorted copy's columns and no record's destination
 // (records never chain); a LINK reads none; the multiplicities count lookup tuples, and those read every derived column freely.
 // Nothing reads a derived multiplicity.  A term's multiplicity is the host's column or a derived one, and of a LINK's destinations
-// linked and last (only they) may be the multiplicity of a term that is not derived.
+// linked and last (only they) may be the multiplicity of a term that is not derived.  The PAGES record (version 7) is one more writer of
+// the links stage: it reads what the LINK it pages reads, writes the page table, and of its destinations p_on may be such a multiplicity.
 //
 // THE READ RULE (a LINK record with READS, ZKA1 version 6; links.hip's header has it in full): the write flag is one more source of the
 // record, the host's column.  On an access it must be 0 or 1; a load (0) returns, in every carried column but the clock, what the
@@ -32,6 +33,8 @@ constexpr uint32_t MAX_TUPLE = 4, MAX_TERMS = 3, MAX_SORT_KEYS = 3, NONE = 0xfff
 constexpr uint32_t RECORD_WORDS = 16, KIND_LIMBS = 1, KIND_ORDER = 2, MAX_LIMBS = 8;
 constexpr uint32_t KIND_LINK = 3, LINK_WORDS = 32, MAX_CARRIED = 3, MAX_LINK_LIMBS = 4, MAX_LINK_DSTS = 2 + MAX_CARRIED + MAX_LINK_LIMBS;
 constexpr uint32_t LINK_READS = 1;                  // LINK word 5, bit 0 (version 6): the record carries the read rule
+constexpr uint32_t KIND_PAGES = 4, PAGES_WORDS = 32, MAX_PAGE_LIMBS = 4, MAX_PAGE_DSTS = 5 + 2 * MAX_PAGE_LIMBS;   // a PAGES record (version 7)
+constexpr uint32_t PAGES_BIT = 0x10000;             // header word 7, bit 16 (version 7): the blob has a PAGES record
 constexpr uint32_t MAX_ORDER_BITS = 29;             // logup.MAX_ORDER_BITS: a negative difference stays out of the limbs' range
 
 // logup.Term as the blob gives it: the fields are the blob's words, checked by the rules of arguments.hip before a circuit keeps them
@@ -63,6 +66,14 @@ struct Link {
     uint32_t n_dst, reserved;               // destinations in use; a word the format reserves was not 0
     uint32_t flags, wg, wc;                 // version 6: word 5 (bit 0 = READS, LINK_READS) and words 14, 15, the write flag's (group, column)
 };
+// logup.Pages, the PAGES record (version 7), as the blob gives it; the paged kernels of links.hip read it in this form
+struct Pages {
+    uint32_t index;                         // its index among all records of the blob (it comes last)
+    uint32_t L, ng, link;                   // limb bits; limbs of an address and of a gap; the blob record index of the LINK it pages
+    uint32_t dst[MAX_PAGE_DSTS];            // destination data columns: p_on, p_addr, p_in, p_out, p_time, alimb_0 .., gap_0 ..
+    uint32_t n_dst, reserved;               // destinations in use; a word the format reserves was not 0
+};
+enum { PG_ON = 0, PG_ADDR = 1, PG_IN = 2, PG_OUT = 3, PG_TIME = 4, PG_LIMBS = 5 };      // the places of Pages::dst
 // logup.Arguments
 struct Arguments {
     uint32_t version, k, alpha, beta;       // blob version; accum Fp4 columns; mix word offsets of the two challenges
@@ -71,6 +82,14 @@ struct Arguments {
     std::vector<Link> links;                // the LINK records
     uint32_t late_record = NONE, late_after = 0;    // a LIMBS / ORDER record that follows a LINK record, and that LINK record (refused)
     uint32_t reads = 0;                     // the LINK records with READS (version 6: header word 7)
+    std::vector<Pages> pages;               // the PAGES record (version 7; the rules allow one)
+    uint32_t after_pages = NONE;            // a record that follows the first PAGES record (refused)
+    bool second_pages = false;              // ... and it is a PAGES record itself
+    int paged_link() const {                // the place among `links` of the LINK that the PAGES record names, -1: none (or no such LINK)
+        for (size_t p = 0; !pages.empty() && p < links.size(); p++)
+            if (links[p].index == pages[0].link) return (int)p;
+        return -1;
+    }
 };
 
 // a term's columns as the kernels read them; unused tuple slots name (data, 0)

@@ -1,6 +1,7 @@
 // arguments.hip — the ZKA1 argument blob (layout: zeth_amd/circuits/logup.py; DESIGN.md §2 ARGUMENTS): its decoding into
-// zkh::Arguments (terms, from version 4 derived-column records, from version 5 LINK records, from version 6 their read rule), the rules a circuit's arguments keep
-// (check_sorted, check_derived, then check_owned over the LIMBS / ORDER records and over the LINK records), and the entry points that attach them to a circuit and ask what they derive.
+// zkh::Arguments (terms, from version 4 derived-column records, from version 5 LINK records, from version 6 their read rule, from version 7 the PAGES
+// record), the rules a circuit's arguments keep (check_sorted, check_derived, then check_owned over the LIMBS / ORDER records, over the LINK records
+// and over the PAGES record), and the entry points that attach them to a circuit and ask what they derive.
 // decode_arguments is the only code that knows the blob's words; everything else, here and in the consumers, reads decoded terms.
 #include "arguments.h"
 
@@ -16,11 +17,13 @@ namespace {
 // significant key first); bits 2, 3, 7, the position fields of unused keys and, without bit 1, everything above bit 0 are reserved.
 // A reserved bit is recorded, not refused: the rules refuse it where they reach the term (flag_word_rule), after the circuit-shape checks.
 const char* decode_arguments(const uint32_t* a, size_t words, Arguments* out) {
-    ZKH_REQUIRE(words >= ARGS_HEADER && a[0] == ARGS_MAGIC && a[1] >= 1 && a[1] <= 6 && (a[1] < 6 || a[7] != 0), "set_arguments: not a ZKA1 (version 1) argument blob");
+    ZKH_REQUIRE(words >= ARGS_HEADER && a[0] == ARGS_MAGIC && a[1] >= 1 && a[1] <= 7 && (a[1] != 6 || a[7] != 0) && (a[1] != 7 || (a[7] & PAGES_BIT)),
+                "set_arguments: not a ZKA1 (version 1) argument blob");
     const uint32_t n_terms = a[5], n_records = a[1] >= 4 ? a[6] : 0;            // header word 6: the records of version 4, reserved before
     const size_t rec0 = ARGS_HEADER + (size_t)TERM_WORDS * n_terms;
     size_t end = rec0;                                                          // a LINK record (version 5) takes two slots; past the blob's end the walk stops
-    for (uint32_t i = 0; i < n_records && end <= words; i++) end += a[1] >= 5 && end < words && a[end] == KIND_LINK ? LINK_WORDS : RECORD_WORDS;
+    for (uint32_t i = 0; i < n_records && end <= words; i++)                    // ... and so does the PAGES record (version 7)
+        end += end < words && ((a[1] >= 5 && a[end] == KIND_LINK) || (a[1] >= 7 && a[end] == KIND_PAGES)) ? LINK_WORDS : RECORD_WORDS;
     const bool fits = words == end;
     ZKH_REQUIRE(fits || a[1] < 4, "set_arguments: %zu words for %u terms and %u records", words, n_terms, n_records);
     ZKH_REQUIRE(fits, "set_arguments: %zu words for %u terms", words, n_terms);
@@ -49,10 +52,27 @@ const char* decode_arguments(const uint32_t* a, size_t words, Arguments* out) {
     // then from word 16 the destinations linked, last, prev_0 .. prev_{nc-1}, limb_0 .. limb_{nl-1}, the rest 0 (links_clause_a).
     // Version 6: word 5 is a flag word (bit 0 = READS), words 14, 15 the write flag's (group, column) with READS and 0 without; header
     // word 7 counts the records with READS (0 there is no ZKA1 blob: above).
+    // The PAGES record (version 7, kind 4, 32 words): L, ng, the blob index of its LINK, words 4 .. 15 reserved, then from word 16 the
+    // destinations p_on, p_addr, p_in, p_out, p_time, alimb_0 .. alimb_{ng-1}, gap_0 .. gap_{ng-1}, the rest 0 (pages_clause_a).  Header
+    // word 7 carries bit 16 beside the READS count.
     out->records.clear();
     out->links.clear();
+    out->pages.clear();
     const uint32_t* r = a + rec0;
     for (uint32_t i = 0; i < n_records; i++) {
+        if (!out->pages.empty() && out->after_pages == NONE) { out->after_pages = i; out->second_pages = out->version >= 7 && r[0] == KIND_PAGES; }
+        if (out->version >= 7 && r[0] == KIND_PAGES) {
+            Pages x{};
+            x.index = i; x.L = r[1]; x.ng = r[2]; x.link = r[3];
+            const uint32_t nd = 5 + 2 * (x.ng < 8 ? x.ng : 8);
+            x.n_dst = nd < MAX_PAGE_DSTS ? nd : MAX_PAGE_DSTS;
+            for (uint32_t j = 0; j < x.n_dst; j++) x.dst[j] = r[16 + j];
+            for (uint32_t j = 4; j < 16; j++) x.reserved |= r[j];
+            for (uint32_t j = 16 + (nd < 16 ? nd : 16); j < PAGES_WORDS; j++) x.reserved |= r[j];
+            out->pages.push_back(x);
+            r += PAGES_WORDS;
+            continue;
+        }
         if (out->version >= 5 && r[0] == KIND_LINK) {
             Link x{};
             x.index = i; x.L = r[1]; x.nl = r[2]; x.nc = r[3]; x.sel = r[4]; x.kg = r[6]; x.kc = r[7];
@@ -82,7 +102,9 @@ const char* decode_arguments(const uint32_t* a, size_t words, Arguments* out) {
         out->records.push_back(x);
         r += RECORD_WORDS;
     }
-    ZKH_REQUIRE(out->version < 6 || a[7] == out->reads, "set_arguments: header word 7 is %u, the blob has %u LINK records with READS", a[7], out->reads);
+    const uint32_t word7 = out->version >= 7 ? a[7] ^ PAGES_BIT : a[7];          // version 7: bit 16 says PAGES, the rest counts as before
+    ZKH_REQUIRE(out->version < 6 || word7 == out->reads, "set_arguments: header word 7 is %u, the blob has %u LINK records with READS", word7, out->reads);
+    ZKH_REQUIRE(out->version < 7 || !out->pages.empty(), "set_arguments: header word 7 has bit 16 (PAGES), but the blob has no PAGES record");
     return nullptr;
 }
 
@@ -177,9 +199,10 @@ bool is_column(const zkh_circuit* c, uint32_t g, uint32_t col) { return (g == GR
 // A record of either kind as the ownership rule (arguments.h) sees it
 struct Owned {
     uint32_t index;                                     // its index among the blob's records
-    bool link;                                          // a LINK: it runs after every LIMBS / ORDER record
+    bool link;                                          // a LINK or the PAGES record: it runs after every LIMBS / ORDER record
     uint32_t n_src, sg[2 + MAX_CARRIED], sc[2 + MAX_CARRIED];   // the (group, column) pairs it reads (LINK: the key, the carried columns, with READS the write flag)
-    uint32_t n_dst, dst[MAX_LINK_DSTS];                 // the data columns it writes
+    uint32_t n_dst, dst[MAX_PAGE_DSTS];                 // the data columns it writes
+    uint32_t free;                                      // its first `free` destinations may be the multiplicity of a term that is not derived
     bool writes(uint32_t col) const { return std::find(dst, dst + n_dst, col) != dst + n_dst; }
     bool reads(uint32_t col) const {                    // data column `col` among its sources
         for (uint32_t s = 0; s < n_src; s++)
@@ -187,19 +210,36 @@ struct Owned {
         return false;
     }
 };
-// the LIMBS / ORDER records, then the LINK records: the blob's order (a blob that has it otherwise is refused before anything reads this)
+// the LINK that a PAGES record names, where it is one the rules allow: READS, a clock and one value column
+const Link* paged_link(const Arguments& a, const Pages& g) {
+    for (const Link& r : a.links)
+        if (r.index == g.link) return (r.flags & LINK_READS) && r.nc == 2 ? &r : nullptr;
+    return nullptr;
+}
+static_assert(MAX_PAGE_DSTS >= MAX_LINK_DSTS && MAX_PAGE_DSTS >= MAX_LIMBS, "Owned::dst holds any record's destinations");
+// the LIMBS / ORDER records, then the LINK records, then the PAGES record: the blob's order (a blob that has it otherwise is refused before anything reads this)
 std::vector<Owned> owned(const Arguments& a) {
     std::vector<Owned> all;
     for (const Record& r : a.records) {
-        Owned v{(uint32_t)all.size(), false, std::min(r.n_src, 2u), {}, {}, r.n_dst, {}};
+        Owned v{(uint32_t)all.size(), false, std::min(r.n_src, 2u), {}, {}, r.n_dst, {}, 0};
         std::copy(r.sg, r.sg + v.n_src, v.sg); std::copy(r.sc, r.sc + v.n_src, v.sc); std::copy(r.dst, r.dst + r.n_dst, v.dst);
         all.push_back(v);
     }
     for (const Link& r : a.links) {
         const uint32_t nc = std::min(r.nc, MAX_CARRIED);
-        Owned v{r.index, true, 1 + nc, {r.kg}, {r.kc}, r.n_dst, {}};
+        Owned v{r.index, true, 1 + nc, {r.kg}, {r.kc}, r.n_dst, {}, 2};
         std::copy(r.cg, r.cg + nc, v.sg + 1); std::copy(r.cc, r.cc + nc, v.sc + 1); std::copy(r.dst, r.dst + r.n_dst, v.dst);
         if (r.flags & LINK_READS) { v.sg[v.n_src] = r.wg; v.sc[v.n_src++] = r.wc; }
+        all.push_back(v);
+    }
+    const size_t n_rec = a.records.size();
+    for (const Pages& g : a.pages) {                    // it reads what its LINK reads
+        Owned v{g.index, true, 0, {}, {}, g.n_dst, {}, 1};
+        if (const Link* t = paged_link(a, g)) {
+            const Owned& l = all[n_rec + (t - a.links.data())];
+            v.n_src = l.n_src; std::copy(l.sg, l.sg + l.n_src, v.sg); std::copy(l.sc, l.sc + l.n_src, v.sc);
+        }
+        std::copy(g.dst, g.dst + g.n_dst, v.dst);
         all.push_back(v);
     }
     return all;
@@ -233,21 +273,37 @@ const char* links_clause_a(const zkh_circuit* c, const Link& r) {
     return nullptr;
 }
 
+// logup.check_pages' own clause (a): the ranges of L and ng, the reserved words, and the target a LINK with READS and nc = 2
+const char* pages_clause_a(const Arguments& a, const Pages& g) {
+    const uint32_t i = g.index;
+    ZKH_REQUIRE(g.L >= 1 && g.L <= 16 && g.ng >= 1 && g.ng <= MAX_PAGE_LIMBS && g.L * g.ng <= MAX_ORDER_BITS, "set_arguments: record %u: a PAGES record of %u limbs "
+                "of %u bits (1..%u limbs of 1..16 bits, at most %u bits in all)", i, g.ng, g.L, MAX_PAGE_LIMBS, MAX_ORDER_BITS);
+    ZKH_REQUIRE(!g.reserved, "set_arguments: record %u: a reserved word of a PAGES record is not 0 (words 4..15 and the unused destination words)", i);
+    ZKH_REQUIRE(paged_link(a, g), "set_arguments: record %u: a PAGES record pages record %u, which is no LINK record with READS and two carried columns (a clock "
+                "and one value)", i, g.link);
+    return nullptr;
+}
+
 // logup._check_owned, the ownership rule (arguments.h) over one kind of record: the LIMBS / ORDER records, whose peers are one another
-// (logup.check_columns), or the LINK records, whose peers are all records (logup.check_links).  The first record that breaks a clause.
+// (logup.check_columns), the LINK records (kind 1) or the PAGES record (kind 2), whose peers are all records (logup.check_links,
+// logup.check_pages).  The first record that breaks a clause.
 // Per record: the kind's clause (a); (b) its sources are code or data columns of the circuit, its destinations pairwise distinct data
 // columns.  Then, per record again: (c) no source is a destination of any record (records never chain) or a derived multiplicity, and a
 // LINK's is no sorted copy's column either; (d) no destination is written twice: by another record, a sorted copy or a derived
 // multiplicity; (e) no destination is read by the source term of a sorted copy (the sort runs first; check_sorted has bounded
-// sorted_from) or, a LINK's, by any record, and none is a term's multiplicity, a LINK's linked and last apart.
-const char* check_owned(const zkh_circuit* c, const Arguments& a, const std::vector<Owned>& all, bool links) {
-    const size_t n_rec = a.records.size(), lo = links ? n_rec : 0, hi = links ? all.size() : n_rec;     // the kind is [lo, hi), its peers [0, hi)
+// sorted_from) or, a LINK's or the PAGES record's, by any record, and none is a term's multiplicity, a LINK's linked and last and a PAGES
+// record's p_on apart.  kind: 0 = LIMBS / ORDER, 1 = LINK, 2 = PAGES.
+const char* check_owned(const zkh_circuit* c, const Arguments& a, const std::vector<Owned>& all, int kind) {
+    const bool links = kind != 0;                       // a LINK or the PAGES record
+    const size_t n_rec = a.records.size(), n_link = n_rec + a.links.size();
+    const size_t lo = kind == 0 ? 0 : kind == 1 ? n_rec : n_link, top = kind == 0 ? n_rec : kind == 1 ? n_link : all.size();   // the kind is [lo, top) ...
+    const size_t hi = links ? all.size() : n_rec;       // ... its peers [0, hi)
     const uint32_t n_terms = (uint32_t)a.terms.size();
     auto is_mult = [](const Term& t, uint32_t col) { return t.mg == GROUP_DATA && t.mc == col; };
-    for (size_t p = lo; p < hi; p++) {
+    for (size_t p = lo; p < top; p++) {
         const Owned& v = all[p];
         const uint32_t i = v.index;
-        ZKH_TRY(links ? links_clause_a(c, a.links[p - n_rec]) : columns_clause_a(a.records[p], i));
+        ZKH_TRY(kind == 2 ? pages_clause_a(a, a.pages[p - n_link]) : links ? links_clause_a(c, a.links[p - n_rec]) : columns_clause_a(a.records[p], i));
         for (uint32_t s = 0; s < v.n_src; s++)
             ZKH_REQUIRE(is_column(c, v.sg[s], v.sc[s]), "set_arguments: record %u: source (%u, %u) is not a code or data column", i, v.sg[s], v.sc[s]);
         for (uint32_t e = 0; e < v.n_dst; e++) {
@@ -256,7 +312,7 @@ const char* check_owned(const zkh_circuit* c, const Arguments& a, const std::vec
                 ZKH_REQUIRE(v.dst[e2] != v.dst[e], "set_arguments: record %u: its destination (data %u) appears twice", i, v.dst[e]);
         }
     }
-    for (size_t p = lo; p < hi; p++) {
+    for (size_t p = lo; p < top; p++) {
         const Owned& v = all[p];
         const uint32_t i = v.index;
         for (uint32_t s = 0; s < v.n_src; s++) {
@@ -290,8 +346,10 @@ const char* check_owned(const zkh_circuit* c, const Arguments& a, const std::vec
                             "(data %u) is read by term %u, the source of a sorted copy (the sort runs first)", i, col, t.sorted_from);
             for (uint32_t j = 0; j < n_terms; j++) {
                 ZKH_REQUIRE(links || !is_mult(a.terms[j], col), "set_arguments: record %u: its destination (data %u) is the multiplicity of term %u", i, col, j);
-                ZKH_REQUIRE(!links || e < 2 || !is_mult(a.terms[j], col), "set_arguments: record %u: its destination (data %u) is the multiplicity of term %u (of a "
+                ZKH_REQUIRE(kind != 1 || e < v.free || !is_mult(a.terms[j], col), "set_arguments: record %u: its destination (data %u) is the multiplicity of term %u (of a "
                             "LINK's destinations only linked and last may be)", i, col, j);
+                ZKH_REQUIRE(kind != 2 || e < v.free || !is_mult(a.terms[j], col), "set_arguments: record %u: its destination (data %u) is the multiplicity of term %u (of a "
+                            "PAGES record's destinations only p_on may be)", i, col, j);
             }
         }
     }
@@ -324,11 +382,16 @@ const char* check_arguments(const zkh_circuit* c, const Arguments& a) {
     for (uint32_t col = 0; col < k; col++) ZKH_REQUIRE(per_col[col] >= 1, "set_arguments: accum column %u has no terms", col);
     if (a.version >= 3) ZKH_TRY(check_sorted(a));
     if (a.version >= 2) ZKH_TRY(check_derived(a));
+    if (a.after_pages != NONE) {
+        ZKH_REQUIRE(!a.second_pages, "set_arguments: record %u: a second PAGES record (record %u is one: a blob pages one memory)", a.after_pages, a.pages[0].index);
+        return make_err("set_arguments: record %u: a record after the PAGES record %u (the PAGES record comes last)", a.after_pages, a.pages[0].index);
+    }
     ZKH_REQUIRE(a.late_record == NONE, "set_arguments: record %u: a LIMBS / ORDER record after the LINK record %u (LINK records come last)", a.late_record,
                 a.late_after);
     const std::vector<Owned> all = owned(a);
-    ZKH_TRY(check_owned(c, a, all, false));
-    return check_owned(c, a, all, true);
+    ZKH_TRY(check_owned(c, a, all, 0));
+    ZKH_TRY(check_owned(c, a, all, 1));
+    return check_owned(c, a, all, 2);
 }
 
 }  // namespace
@@ -370,24 +433,37 @@ extern "C" int zkh_circuit_derives_links(const zkh_circuit* c) { return c && c->
 
 extern "C" int zkh_circuit_links_check_reads(const zkh_circuit* c) { return c && c->args ? (int)c->args->reads : 0; }
 
+extern "C" int zkh_circuit_pages(const zkh_circuit* c) { return c && c->args && !c->args->pages.empty(); }
+
 // THE DERIVE STAGES, IN THEIR ORDER (arguments.h, WHO WRITES A DATA COLUMN): the one statement of the order in code.  A LIMBS / ORDER
 // record may read a sorted copy's column, and the multiplicities count the limbs that the records and the links derive.
 namespace {
-using Derive = const char* (*)(zkh_ctx*, const zkh_circuit*, size_t, size_t, const zkh_buf*, zkh_buf*);
+using Derive = const char* (*)(zkh_ctx*, const zkh_circuit*, size_t, size_t, const zkh_buf*, zkh_buf*, const zkh_buf*);
+template <const char* (*F)(zkh_ctx*, const zkh_circuit*, size_t, size_t, const zkh_buf*, zkh_buf*)>
+const char* no_image(zkh_ctx* ctx, const zkh_circuit* c, size_t po2, size_t zk_cycles, const zkh_buf* code, zkh_buf* data, const zkh_buf*) {
+    return F(ctx, c, po2, zk_cycles, code, data);
+}
 const struct { const char* name; int (*derives)(const zkh_circuit*); Derive derive; } STAGES[] = {
-    {"sorted", zkh_circuit_derives_sorted, zkh_derive_sorted},
-    {"columns", zkh_circuit_derives_columns, zkh_derive_columns},
-    {"links", zkh_circuit_derives_links, zkh_derive_links},
-    {"multiplicities", zkh_circuit_derives_multiplicities, zkh_derive_multiplicities},
+    {"sorted", zkh_circuit_derives_sorted, no_image<zkh_derive_sorted>},
+    {"columns", zkh_circuit_derives_columns, no_image<zkh_derive_columns>},
+    {"links", zkh_circuit_derives_links, zkh_derive_links_paged},           // the one stage that reads the memory image (a PAGES record)
+    {"multiplicities", zkh_circuit_derives_multiplicities, no_image<zkh_derive_multiplicities>},
 };
 }  // namespace
 
-// every stage the circuit's arguments have, with the arguments as given: the stage's own checks and messages are the call's
-extern "C" const char* zkh_derive_all(zkh_ctx* ctx, const zkh_circuit* c, size_t po2, size_t zk_cycles, const zkh_buf* code, zkh_buf* data) {
+// every stage the circuit's arguments have, with the arguments as given: the stage's own checks and messages are the call's.  A circuit
+// whose arguments page memory is refused without an image before any stage writes.
+extern "C" const char* zkh_derive_all_paged(zkh_ctx* ctx, const zkh_circuit* c, size_t po2, size_t zk_cycles, const zkh_buf* code, zkh_buf* data,
+                                            const zkh_buf* image) {
     ZKH_REQUIRE(c, "derive_all: null circuit");
+    ZKH_REQUIRE(image || !zkh_circuit_pages(c), "derive_all: the arguments page memory: an image is required (zkh_derive_all_paged)");
     for (const auto& s : STAGES)
-        if (s.derives(c)) ZKH_TRY(s.derive(ctx, c, po2, zk_cycles, code, data));
+        if (s.derives(c)) ZKH_TRY(s.derive(ctx, c, po2, zk_cycles, code, data, image));
     return nullptr;
+}
+
+extern "C" const char* zkh_derive_all(zkh_ctx* ctx, const zkh_circuit* c, size_t po2, size_t zk_cycles, const zkh_buf* code, zkh_buf* data) {
+    return zkh_derive_all_paged(ctx, c, po2, zk_cycles, code, data, nullptr);
 }
 
 extern "C" const char* zkh_circuit_derived_data_columns(const zkh_circuit* c, uint32_t* cols, size_t cap, size_t* n) {

@@ -26,6 +26,30 @@
 // stores, and zeros on the active rows that are no access, coalesced), so a refusal leaves `data` unchanged.  Sources are never
 // destinations (set_arguments), so both passes see the same sources and no lane reads what another writes.  Selectors are refused by
 // the sort's key pass, over all records, before any clock is read.
+//
+// PAGING (a PAGES record, ZKA1 version 7; `reference_links(..., image)`): the memory of ONE record, the paged one (READS, nc = 2: a clock and
+// one value), starts from an image of W raw Montgomery words, image[a] the word of address a = x(key, r); a >= W is refused ("address A
+// outside the image of W words").  An UNLINKED access r of the paged record takes the image as its previous access: prev_1[r] = the raw word
+// image[a] (a copy), prev_0[r] = 0 (clock 0 is the image's), the limbs those of d = x(clock, r) - 0 - 1; "clock 0 is the image's" refuses a
+// clock 0, the range refusal a d that does not fit, and an unlinked load must return image[a] (residues) where it had to return 0.  linked
+// and last keep their meaning; linked accesses and the other records are untouched.  On one row the order is write flag, address, clock, read
+// rule.  THE PAGE TABLE: a_0 < .. < a_{D-1} the distinct addresses of the record's accesses; on the active rows i < D p_on = Montgomery(1),
+// p_addr = the raw key word of a_i's first access, p_in = the raw word image[a_i], p_out / p_time = the raw value / clock word of a_i's last
+// access, alimb_j = limb j of a_i (refused, under the PAGES record's index, when a_i >= 2^(L ng)), gap_j = limb j of a_i - a_{i-1} - 1 (zeros
+// on row 0); active rows [D, A) get zeros in all destinations, rows [A, n) are never touched.  PAGE-OUT (zkh_page_out,
+// `reference_page_out`): image[x(p_addr, i)] = p_out[i] on every active row with p_on = 1, after a check pass that refuses, with the image
+// unchanged, the lowest row whose p_on is not 0 / 1, whose address is >= W or does not follow a smaller one on a row with p_on = 1: a table
+// that repeats an address is REFUSED, so the scatter never writes one word twice.
+//
+// The paged passes reuse the one sort.  Position t of the paged record is a HEAD when the packed key at t - 1 differs (the first access of
+// its address) and a TAIL when the one at t + 1 does: neighbouring packed keys, coalesced.  An inclusive scan of the head flags over the m
+// sorted positions gives every position its page index + 1: k_page_heads scans inside a workgroup (scan.h's block_scan) and leaves the
+// workgroup's total, k_page_carry — ONE workgroup, so none waits for another — turns the totals into exclusive carries and leaves D; the
+// consumers add carry[workgroup] to the local index.  k_links_paged is k_links with the image: its check pass adds the image reads and
+// the new refusals to the same wave minimum and the same atomicMin; its write pass also fills the table — head lanes p_on, p_addr, p_in,
+// alimb and gap (the previous address re-read from the trace at rows[t - 1]: packed keys drop bits and are no addresses), tail lanes
+// p_out and p_time, lanes D <= t < A zeros (coalesced).  No atomic but that min: the result is a function of the traces and the image.
+#include "scan.h"
 #include "sort.h"
 
 using namespace zkh;
@@ -105,18 +129,179 @@ __global__ __launch_bounds__(LINK_THREADS) void k_links(const uint32_t* __restri
         data[(size_t)rec->dst[2 + nc + j] * n + row] = fp_encode((uint32_t)((unsigned long long)d >> (j * L)) & mask).v;
 }
 
+
+// ---- paging ----
+constexpr uint32_t PG_TOTAL = 0;                        // word 0 of the carry buffer: D, the pages; the workgroups' carries follow from word 1
+
+// grid ceil(m_max / LINK_THREADS) over the sorted positions of the paged record (its place p among the LINK records): local[t] = the heads
+// among the positions of t's workgroup up to t, sums[1 + workgroup] = the workgroup's heads
+__global__ __launch_bounds__(LINK_THREADS) void k_page_heads(const uint32_t* __restrict__ status, const unsigned long long* __restrict__ keys, uint32_t p, uint32_t A,
+                                                             uint32_t* __restrict__ local, uint32_t* __restrict__ sums) {
+    __shared__ uint32_t buf[2][LINK_THREADS];
+    const uint32_t m = status[ST_HEAD + ST_WORDS * p + ST_M];
+    const uint32_t t = blockIdx.x * LINK_THREADS + threadIdx.x;
+    const size_t base = (size_t)p * A;
+    const uint32_t head = t < m && (t == 0 || keys[base + t - 1] != keys[base + t]);
+    const uint32_t incl = block_scan<LINK_THREADS>(head, buf, AddWrap());
+    if (t < m) local[t] = incl;
+    if (threadIdx.x == LINK_THREADS - 1) sums[1 + blockIdx.x] = incl;
+}
+
+// one workgroup: sums[1 + b] = the heads of the workgroups below b (their exclusive scan, in place), sums[PG_TOTAL] = D.  Thread t scans
+// the chunk of `per` consecutive workgroups [t per, (t + 1) per).
+__global__ __launch_bounds__(LINK_THREADS) void k_page_carry(uint32_t* __restrict__ sums, uint32_t nb, uint32_t per) {
+    __shared__ uint32_t buf[2][LINK_THREADS];
+    const uint32_t lo = threadIdx.x * per, hi = lo + per < nb ? lo + per : nb;
+    uint32_t mine = 0;
+    for (uint32_t b = lo; b < hi; b++) mine += sums[1 + b];
+    const uint32_t incl = block_scan<LINK_THREADS>(mine, buf, AddWrap());
+    uint32_t run = incl - mine;
+    for (uint32_t b = lo; b < hi; b++) {
+        const uint32_t v = sums[1 + b];
+        sums[1 + b] = run;
+        run += v;
+    }
+    if (threadIdx.x == LINK_THREADS - 1) sums[PG_TOTAL] = incl;
+}
+
+// k_links over a blob with a PAGES record `pg` that pages the record at place `paged`: grid (ceil(A / LINK_THREADS), records), both passes
+// as k_links', every record with the read rule where it has READS.  Whether blockIdx.y is the paged record is uniform: a scalar branch.
+// bad: the lowest (place << 32 | row), the PAGES record's own refusal under the place `records` (it comes after every LINK).
+template <bool kWrite>
+__global__ __launch_bounds__(LINK_THREADS) void k_links_paged(const uint32_t* __restrict__ code, uint32_t* data, const Link* __restrict__ links,
+                                                              const uint32_t* __restrict__ status, const unsigned long long* __restrict__ keys,
+                                                              const uint32_t* __restrict__ rows, uint32_t n, uint32_t A, unsigned long long* __restrict__ bad,
+                                                              const Pages* __restrict__ pg, uint32_t paged, const uint32_t* __restrict__ image, uint32_t W,
+                                                              const uint32_t* __restrict__ local, const uint32_t* __restrict__ sums) {
+    const uint32_t p = blockIdx.y;
+    const Link* __restrict__ rec = links + p;
+    const bool pages = p == paged;
+    const uint32_t m = status[ST_HEAD + ST_WORDS * p + ST_M];
+    const uint32_t t = blockIdx.x * LINK_THREADS + threadIdx.x;
+    const size_t base = (size_t)p * A;
+    const bool access = t < m;
+    uint32_t row = 0, prow = 0;
+    bool linked = false, last = false;
+    if (access) {
+        const unsigned long long key = keys[base + t];
+        row = rows[base + t];
+        if (t) {
+            linked = keys[base + t - 1] == key;
+            prow = rows[base + t - 1];                    // linked: the previous access; a head of the paged record: the last access of the address below
+        }
+        last = t + 1 >= m || keys[base + t + 1] != key;
+    }
+    const uint32_t* clock = group_ptr(code, data, rec->cg[0]) + (size_t)rec->cc[0] * n;
+    const uint32_t* keycol = group_ptr(code, data, rec->kg) + (size_t)rec->kc * n;
+    long long d = 0;
+    uint32_t addr = 0, word = 0;                          // the paged record's access: its address and, in range, the image's word
+    bool inside = true;
+    if (linked) d = (long long)canonical(clock[row]) - canonical(clock[prow]) - 1;
+    if (pages && access) {
+        addr = canonical(keycol[row]);
+        inside = addr < W;
+        if (inside) word = image[addr];
+        if (!linked) d = (long long)canonical(clock[row]) - 1;      // clock 0 is the image's: d = -1 refuses it
+    }
+    const uint32_t L = rec->L, nl = rec->nl;
+    if (!kWrite) {
+        uint32_t mine = (linked || (pages && access)) && (d < 0 || (d >> (L * nl)) != 0) ? row : NONE;
+        if (!inside) mine = row;
+        if ((rec->flags & LINK_READS) && access) {
+            const uint32_t w = cell(code, data, rec->wg, rec->wc, n, row);
+            bool ok = w == 0 || w == R1;
+            if (w == 0) {                                 // a load: the previous access's values; unlinked: 0, or the image's word (residues)
+                const uint32_t nc = rec->nc;
+                for (uint32_t j = 1; j < nc; j++) {
+                    const uint32_t* col = group_ptr(code, data, rec->cg[j]) + (size_t)rec->cc[j] * n;
+                    ok &= col[row] % P == (linked ? col[prow] % P : pages ? word % P : 0);
+                }
+            }
+            if (!ok) mine = row;
+        }
+        report_bad_row(bad, p, mine);
+        if (pages) report_bad_row(bad, gridDim.y, access && (addr >> (pg->L * pg->ng)) != 0 ? row : NONE);     // an address the limbs do not hold
+        return;
+    }
+    const uint32_t nc = rec->nc, n_dst = rec->n_dst;
+    if (rec->sel != NONE && t < A && sel_class(code, rec->sel, n, t) != 1)
+        for (uint32_t e = 0; e < n_dst; e++) data[(size_t)rec->dst[e] * n + t] = 0;
+    if (pages) {
+        const uint32_t D = sums[PG_TOTAL];
+        if (t >= D && t < A)                              // the rows below the table, coalesced
+            for (uint32_t e = 0; e < pg->n_dst; e++) data[(size_t)pg->dst[e] * n + t] = 0;
+        if (access && (!linked || last)) {
+            const uint32_t i = local[t] + sums[1 + blockIdx.x] - 1;      // the page of t's address: the heads up to t, less one
+            const uint32_t Lp = pg->L, ng = pg->ng, maskp = (1u << Lp) - 1;
+            if (!linked) {                                // the head: the first access of the address
+                data[(size_t)pg->dst[PG_ON] * n + i] = R1;
+                data[(size_t)pg->dst[PG_ADDR] * n + i] = keycol[row];
+                data[(size_t)pg->dst[PG_IN] * n + i] = word;
+                const uint32_t gap = t ? addr - canonical(keycol[prow]) - 1 : 0;
+                for (uint32_t j = 0; j < ng; j++) {
+                    data[(size_t)pg->dst[PG_LIMBS + j] * n + i] = fp_encode((addr >> (j * Lp)) & maskp).v;
+                    data[(size_t)pg->dst[PG_LIMBS + ng + j] * n + i] = fp_encode((gap >> (j * Lp)) & maskp).v;
+                }
+            }
+            if (last) {                                   // the tail: the last access of the address
+                data[(size_t)pg->dst[PG_OUT] * n + i] = group_ptr(code, data, rec->cg[1])[(size_t)rec->cc[1] * n + row];
+                data[(size_t)pg->dst[PG_TIME] * n + i] = clock[row];
+            }
+        }
+    }
+    if (!access) return;
+    const bool from_image = pages && !linked;
+    data[(size_t)rec->dst[0] * n + row] = linked ? R1 : 0;
+    data[(size_t)rec->dst[1] * n + row] = last ? R1 : 0;
+    for (uint32_t j = 0; j < nc; j++)
+        data[(size_t)rec->dst[2 + j] * n + row] = linked ? group_ptr(code, data, rec->cg[j])[(size_t)rec->cc[j] * n + prow] : from_image && j == 1 ? word : 0;
+    const uint32_t mask = (1u << L) - 1;                  // L <= 16
+    for (uint32_t j = 0; j < nl; j++)
+        data[(size_t)rec->dst[2 + nc + j] * n + row] = fp_encode((uint32_t)((unsigned long long)d >> (j * L)) & mask).v;
+}
+
+// zkh_page_out's two passes over the active rows of the page table: kWrite = false reduces the lowest refused row into `bad` (under 0),
+// kWrite = true scatters p_out into the image (addresses checked distinct and inside: no word is written twice)
+template <bool kWrite>
+__global__ __launch_bounds__(LINK_THREADS) void k_page_out(const uint32_t* __restrict__ data, const Pages* __restrict__ pg, uint32_t n, uint32_t A, uint32_t* image,
+                                                           uint32_t W, unsigned long long* __restrict__ bad) {
+    const uint32_t t = blockIdx.x * LINK_THREADS + threadIdx.x;
+    const uint32_t* on = data + (size_t)pg->dst[PG_ON] * n;
+    const uint32_t* addrs = data + (size_t)pg->dst[PG_ADDR] * n;
+    uint32_t mine = NONE;
+    if (t < A) {
+        const uint32_t v = on[t] % P, a = canonical(addrs[t]);
+        if (!kWrite) {
+            bool ok = v == 0 || v == R1;
+            if (v == R1) ok = a < W && (t == 0 || (on[t - 1] % P == R1 && canonical(addrs[t - 1]) < a));
+            if (!ok) mine = t;
+        } else if (v == R1 && a < W) {
+            image[a] = data[(size_t)pg->dst[PG_OUT] * n + t];
+        }
+    }
+    if (!kWrite) report_bad_row(bad, 0, mine);
+}
 }  // namespace
 
-extern "C" const char* zkh_derive_links(zkh_ctx* ctx, const zkh_circuit* c, size_t po2, size_t zk_cycles, const zkh_buf* code, zkh_buf* data) {
+namespace {
+
+// zkh_derive_links (image = NULL) and zkh_derive_links_paged: one sort, the check pass, one read-back, the write pass.  With a PAGES record
+// both passes are k_links_paged's and the page scan runs between the sort and the check.
+const char* derive_links(zkh_ctx* ctx, const zkh_circuit* c, size_t po2, size_t zk_cycles, const zkh_buf* code, zkh_buf* data, const zkh_buf* image) {
     ZKH_REQUIRE(ctx && c && data, "derive_links: null argument");
     ZKH_REQUIRE(code, "derive_links: the raw code trace is required (the selectors and code-group source columns of the records read it)");
     ZKH_REQUIRE(zkh_circuit_derives_links(c), "derive_links: the circuit's arguments hold no LINK record (ZKA1 version 5)");
+    const bool paging = !c->args->pages.empty();
+    ZKH_REQUIRE(image || !paging, "derive_links: the arguments page memory: an image is required (zkh_derive_all_paged)");
     size_t n;
     uint32_t A;
     ZKH_TRY(trace_rows("derive_links", c, po2, zk_cycles, code, data, nullptr, &n, &A));
     const std::vector<Link>& links = c->args->links;
     const uint32_t nr = (uint32_t)links.size();
     ZKH_REQUIRE(nr <= 65535, "derive_links: %u LINK records in one blob (at most 65535)", nr);
+    ZKH_REQUIRE(!paging || image->len <= 0xffffffffull, "derive_links: an image of %zu words (at most 2^32 - 1)", paging ? image->len : 0);
+    const int paged = paging ? c->args->paged_link() : -1;
+    ZKH_REQUIRE(!paging || paged >= 0, "derive_links: the PAGES record names no LINK record");    // set_arguments has refused such a blob
     std::vector<SortPair> pairs(nr, SortPair{});
     for (uint32_t p = 0; p < nr; p++) {                 // the accesses of a record sorted by their key alone: the sort is stable
         pairs[p].d_term = links[p].index; pairs[p].nkeys = 1; pairs[p].sel = links[p].sel;
@@ -133,29 +318,55 @@ extern "C" const char* zkh_derive_links(zkh_ctx* ctx, const zkh_circuit* c, size
         return make_err("derive_links: record %u at row %u: selector %u, not 0 or 1: the witness is refused", r.index, sorted.bad_row, sel);
     }
     ZKH_REQUIRE(!sorted.wide, "derive_links: a packed key of more than 64 bits from one 31-bit field");
-    static_assert(sizeof(Link) % 4 == 0, "word records");
-    Tmp drecs;
+    static_assert(sizeof(Link) % 4 == 0 && sizeof(Pages) % 4 == 0, "word records");
+    Tmp drecs, dpages, local, sums;
     BadRow bad;
     ZKH_TRY(zkh_copy_from(ctx, "link_records", (const uint32_t*)links.data(), links.size() * (sizeof(Link) / 4), drecs.out()));
     ZKH_TRY(bad.init(ctx));
     double carried = 0, dsts = 0;
     for (const Link& r : links) { carried += r.nc; dsts += r.n_dst; }
-    const dim3 grid((unsigned)((A + LINK_THREADS - 1) / LINK_THREADS), nr);
+    const uint32_t nb = (A + LINK_THREADS - 1) / LINK_THREADS;
+    const dim3 grid(nb, nr);
     const bool reads = c->args->reads != 0;             // a record has READS: the check pass with the read rule, over all records
     const Link* d_recs = (const Link*)drecs->ptr();
+    const Pages* d_pg = nullptr;
+    const uint32_t W = paging ? (uint32_t)image->len : 0;
+    if (paging) {                                       // every sorted position of the paged record gets its page: a two-level scan of the head flags
+        const Pages& g = c->args->pages[0];
+        ZKH_TRY(zkh_copy_from(ctx, "pages_record", (const uint32_t*)&g, sizeof(Pages) / 4, dpages.out()));
+        d_pg = (const Pages*)dpages->ptr();
+        ZKH_TRY(new_buf(ctx, A, false, local.out()));
+        ZKH_TRY(new_buf(ctx, 1 + (size_t)nb, false, sums.out()));
+        ProfScope prof(ctx, "pages_scan", 12.0 * A + 8.0 * nb);            // the keys of every position, its index, the workgroups' totals twice
+        k_page_heads<<<nb, LINK_THREADS, 0, ctx->stream>>>(sorted.status->ptr(), sorted.keys(), (uint32_t)paged, A, local->ptr(), sums->ptr());
+        ZKH_TRY(last_launch_error("pages_heads"));
+        k_page_carry<<<1, LINK_THREADS, 0, ctx->stream>>>(sums->ptr(), nb, (nb + LINK_THREADS - 1) / LINK_THREADS);
+        ZKH_TRY(last_launch_error("pages_carry"));
+    }
     {
         double cells = 0;                                 // with READS: the write flag and, at most, the value cells at both rows
         for (const Link& r : links) cells += r.flags & LINK_READS ? 1 + 2 * (r.nc - 1) : 0;
-        ProfScope prof(ctx, "links_check", (20.0 * nr + 4.0 * cells) * A);   // key and row of every item; the clock at both rows
-        (reads ? k_links<false, true> : k_links<false, false>)<<<grid, LINK_THREADS, 0, ctx->stream>>>(code->ptr(), data->ptr(), d_recs, sorted.status->ptr(),
-                                                                                                       sorted.keys(), sorted.rows(), (uint32_t)n, A, bad.ptr());
+        ProfScope prof(ctx, "links_check", (20.0 * nr + 4.0 * cells + (paging ? 8.0 : 0.0)) * A);   // key and row of every item; the clock at both rows; paged: the key and the image's word
+        if (paging)
+            k_links_paged<false><<<grid, LINK_THREADS, 0, ctx->stream>>>(code->ptr(), data->ptr(), d_recs, sorted.status->ptr(), sorted.keys(), sorted.rows(), (uint32_t)n, A,
+                                                                         bad.ptr(), d_pg, (uint32_t)paged, image->ptr(), W, local->ptr(), sums->ptr());
+        else
+            (reads ? k_links<false, true> : k_links<false, false>)<<<grid, LINK_THREADS, 0, ctx->stream>>>(code->ptr(), data->ptr(), d_recs, sorted.status->ptr(),
+                                                                                                           sorted.keys(), sorted.rows(), (uint32_t)n, A, bad.ptr());
         ZKH_TRY(last_launch_error("links_check"));
     }
     ZKH_TRY(bad.read(ctx));
+    if (bad.found && bad.hi >= nr) {                    // the PAGES record's own refusal: an address that its limbs do not hold
+        const Pages& g = c->args->pages[0];
+        uint32_t a;
+        ZKH_TRY(read_cell(ctx, code, data, links[paged].kg, links[paged].kc, n, bad.lo, &a));
+        return make_err("derive_links: record %u at row %u: address %u does not fit %u limbs of %u bits: the witness is refused", g.index, bad.lo, a, g.ng, g.L);
+    }
     if (bad.found) {
         // the refused access and its previous one, found on the host as the reference finds them: the key and the selector of rows [0, row]
         const Link& r = links[bad.hi];
         const uint32_t row = bad.lo;
+        const bool pages = (int)bad.hi == paged;
         std::vector<uint32_t> key(row + 1), sel(row + 1, R1);
         ZKH_TRY(zkh_read(ctx, r.kg == GROUP_CODE ? code : data, key.data(), (size_t)r.kc * n, row + 1));
         if (r.sel != NONE) ZKH_TRY(zkh_read(ctx, code, sel.data(), (size_t)r.sel * n, row + 1));
@@ -168,36 +379,111 @@ extern "C" const char* zkh_derive_links(zkh_ctx* ctx, const zkh_circuit* c, size
             ZKH_TRY(read_cell(ctx, code, data, r.wg, r.wc, n, row, &w));
             if (w > 1) return make_err("derive_links: record %u at row %u: write flag %u, not 0 or 1: the witness is refused", r.index, row, w);
         }
-        if (linked) {
-            long long now, before;
+        const uint32_t addr = canonical(key[row]);
+        uint32_t word = 0;                                // paged: the image's word at the address, canonical
+        if (pages) {
+            if (addr >= W) return make_err("derive_links: record %u at row %u: address %u outside the image of %u words: the witness is refused", r.index, row, addr, W);
+            ZKH_TRY(zkh_read(ctx, image, &word, addr, 1));
+            word = canonical(word);
+        }
+        if (linked || pages) {
+            long long now, before = 0;
             ZKH_TRY(read_cell(ctx, code, data, r.cg[0], r.cc[0], n, row, &now));
-            ZKH_TRY(read_cell(ctx, code, data, r.cg[0], r.cc[0], n, prow, &before));
+            if (linked) ZKH_TRY(read_cell(ctx, code, data, r.cg[0], r.cc[0], n, prow, &before));
+            if (!linked && now == 0) return make_err("derive_links: record %u at row %u: clock 0 is the image's: the witness is refused", r.index, row);
             const long long d = now - before - 1;
             if (d < 0)
                 return make_err("derive_links: record %u at row %u: clock not increasing (%lld after %lld at row %u): the witness is refused", r.index, row, now, before, prow);
-            if ((d >> (r.L * r.nl)) != 0)
+            if ((d >> (r.L * r.nl)) != 0 && linked)
                 return make_err("derive_links: record %u at row %u: the clock difference %lld (after row %u) does not fit %u limbs of %u bits: the witness is refused",
                                 r.index, row, d, prow, r.nl, r.L);
+            if ((d >> (r.L * r.nl)) != 0)
+                return make_err("derive_links: record %u at row %u: the clock difference %lld (after the image) does not fit %u limbs of %u bits: the witness is refused",
+                                r.index, row, d, r.nl, r.L);
         }
         for (uint32_t j = 1; (r.flags & LINK_READS) && j < r.nc; j++) {     // a load (the write flag is 0, or something above was named)
-            uint32_t now, before = 0;
+            uint32_t now, before = pages ? word : 0;
             ZKH_TRY(read_cell(ctx, code, data, r.cg[j], r.cc[j], n, row, &now));
             if (linked) ZKH_TRY(read_cell(ctx, code, data, r.cg[j], r.cc[j], n, prow, &before));
             if (now == before) continue;
             if (linked)
                 return make_err("derive_links: record %u at row %u: a load of carried column %u returns %u, but %u was last stored (row %u): the witness is refused",
                                 r.index, row, j, now, before, prow);
+            if (pages)
+                return make_err("derive_links: record %u at row %u: a load of carried column %u returns %u, but the image holds %u at its address %u: the witness is "
+                                "refused", r.index, row, j, now, before, addr);
             return make_err("derive_links: record %u at row %u: a load of carried column %u returns %u, but its address was never accessed: the value must be 0: "
                             "the witness is refused", r.index, row, j, now);
         }
         return make_err("derive_links: record %u at row %u was refused, but the host finds no rule it breaks", r.index, row);
     }
     {
-        ProfScope prof(ctx, "links_write", (20.0 * nr + 4.0 * carried + 4.0 * dsts) * A);
-        k_links<true, false><<<grid, LINK_THREADS, 0, ctx->stream>>>(code->ptr(), data->ptr(), d_recs, sorted.status->ptr(), sorted.keys(), sorted.rows(),
-                                                                   (uint32_t)n, A, bad.ptr());
+        const Pages* g = paging ? &c->args->pages[0] : nullptr;
+        ProfScope prof(ctx, "links_write", (20.0 * nr + 4.0 * carried + 4.0 * dsts + (paging ? 12.0 + 4.0 * g->n_dst : 0.0)) * A);
+        if (paging)
+            k_links_paged<true><<<grid, LINK_THREADS, 0, ctx->stream>>>(code->ptr(), data->ptr(), d_recs, sorted.status->ptr(), sorted.keys(), sorted.rows(), (uint32_t)n, A,
+                                                                        bad.ptr(), d_pg, (uint32_t)paged, image->ptr(), W, local->ptr(), sums->ptr());
+        else
+            k_links<true, false><<<grid, LINK_THREADS, 0, ctx->stream>>>(code->ptr(), data->ptr(), d_recs, sorted.status->ptr(), sorted.keys(), sorted.rows(),
+                                                                       (uint32_t)n, A, bad.ptr());
         ZKH_TRY(last_launch_error("links_write"));
     }
     // the temporaries go back to the pool on return: the stream orders their next use after these launches
+    return nullptr;
+}
+
+}  // namespace
+
+extern "C" const char* zkh_derive_links(zkh_ctx* ctx, const zkh_circuit* c, size_t po2, size_t zk_cycles, const zkh_buf* code, zkh_buf* data) {
+    return derive_links(ctx, c, po2, zk_cycles, code, data, nullptr);
+}
+
+extern "C" const char* zkh_derive_links_paged(zkh_ctx* ctx, const zkh_circuit* c, size_t po2, size_t zk_cycles, const zkh_buf* code, zkh_buf* data,
+                                              const zkh_buf* image) {
+    return derive_links(ctx, c, po2, zk_cycles, code, data, image);
+}
+
+extern "C" const char* zkh_page_out(zkh_ctx* ctx, const zkh_circuit* c, size_t po2, size_t zk_cycles, const zkh_buf* data, zkh_buf* image) {
+    ZKH_REQUIRE(ctx && c && data && image, "page_out: null argument");
+    ZKH_REQUIRE(zkh_circuit_pages(c), "page_out: the circuit's arguments hold no PAGES record (ZKA1 version 7)");
+    ZKH_REQUIRE(po2 >= 1 && po2 <= 24, "page_out: po2 %zu out of range", po2);
+    const size_t n = (size_t)1 << po2;
+    ZKH_REQUIRE(zk_cycles < n, "page_out: zk_cycles %zu leaves no active row at po2 %zu", zk_cycles, po2);
+    const uint32_t A = (uint32_t)(n - zk_cycles);
+    ZKH_REQUIRE(data->len == (size_t)c->group_size[GROUP_DATA] * n, "page_out: buffer shape mismatch");
+    ZKH_REQUIRE(image->len <= 0xffffffffull, "page_out: an image of %zu words (at most 2^32 - 1)", image->len);
+    const Pages& g = c->args->pages[0];
+    const uint32_t W = (uint32_t)image->len;
+    bind_thread(ctx);
+    Tmp dpages;
+    BadRow bad;
+    ZKH_TRY(zkh_copy_from(ctx, "pages_record", (const uint32_t*)&g, sizeof(Pages) / 4, dpages.out()));
+    ZKH_TRY(bad.init(ctx));
+    const uint32_t nb = (A + LINK_THREADS - 1) / LINK_THREADS;
+    {
+        ProfScope prof(ctx, "page_out_check", 8.0 * A);
+        k_page_out<false><<<nb, LINK_THREADS, 0, ctx->stream>>>(data->ptr(), (const Pages*)dpages->ptr(), (uint32_t)n, A, image->ptr(), W, bad.ptr());
+        ZKH_TRY(last_launch_error("page_out_check"));
+    }
+    ZKH_TRY(bad.read(ctx));
+    if (bad.found) {
+        const uint32_t row = bad.lo;
+        uint32_t on, a, pon = 1, pa = 0;
+        ZKH_TRY(read_cell(ctx, data, data, GROUP_DATA, g.dst[PG_ON], n, row, &on));
+        ZKH_TRY(read_cell(ctx, data, data, GROUP_DATA, g.dst[PG_ADDR], n, row, &a));
+        if (on > 1) return make_err("page_out: record %u at row %u: p_on %u, not 0 or 1: the image is unchanged", g.index, row, on);
+        if (a >= W) return make_err("page_out: record %u at row %u: address %u outside the image of %u words: the image is unchanged", g.index, row, a, W);
+        if (row) {
+            ZKH_TRY(read_cell(ctx, data, data, GROUP_DATA, g.dst[PG_ON], n, row - 1, &pon));
+            ZKH_TRY(read_cell(ctx, data, data, GROUP_DATA, g.dst[PG_ADDR], n, row - 1, &pa));
+        }
+        return make_err("page_out: record %u at row %u: page address %u does not follow a smaller one (row %u: p_on %u, address %u): the image is unchanged", g.index, row,
+                        a, row - 1, pon, pa);
+    }
+    {
+        ProfScope prof(ctx, "page_out_write", 16.0 * A);
+        k_page_out<true><<<nb, LINK_THREADS, 0, ctx->stream>>>(data->ptr(), (const Pages*)dpages->ptr(), (uint32_t)n, A, image->ptr(), W, bad.ptr());
+        ZKH_TRY(last_launch_error("page_out_write"));
+    }
     return nullptr;
 }

@@ -180,6 +180,10 @@ ABI = {
     "zkh_circuit_links_check_reads": (_i, [_vp]),
     "zkh_derive_links": (_err, [_vp, _vp, _sz, _sz, _vp, _vp]),
     "zkh_derive_all": (_err, [_vp, _vp, _sz, _sz, _vp, _vp]),
+    "zkh_circuit_pages": (_i, [_vp]),
+    "zkh_derive_links_paged": (_err, [_vp, _vp, _sz, _sz, _vp, _vp, _vp]),
+    "zkh_derive_all_paged": (_err, [_vp, _vp, _sz, _sz, _vp, _vp, _vp]),
+    "zkh_page_out": (_err, [_vp, _vp, _sz, _sz, _vp, _vp]),
     "zkh_circuit_derived_data_columns": (_err, [_vp, _u32p, _sz, C.POINTER(_sz)]),
     "zkh_upload_data_trace": (_err, [_vp, _vp, _sz, _sz, _vp, _u32p, _i]),
     "zkh_ctx_h2d_bytes": (_sz, [_vp]),
@@ -375,6 +379,11 @@ class Circuit:
     def links_check_reads(self) -> int:
         """the LINK records with READS (ZKA1 version 6): zkh_derive_links refuses a load that does not return the last store"""
         return int(_lib.zkh_circuit_links_check_reads(self.h))
+
+    def pages(self) -> bool:
+        """the arguments (ZKA1 version 7) hold a PAGES record: the memory of its LINK starts from an image (derive_links_paged,
+        derive_all_paged) and page_out writes it back; derive_links and derive_all refuse such a circuit"""
+        return bool(_lib.zkh_circuit_pages(self.h))
 
     def derived_data_columns(self) -> List[int]:
         """the data columns the library's derives (sorted, columns, links, multiplicities) write on the active rows, ascending"""
@@ -826,6 +835,24 @@ class HipHal:
         """fill everything the circuit's arguments derive into `data`, the stages in their order (zkh_derive_all); nothing to derive:
         nothing done.  Raises the HalError of the first stage that refuses; the stages before it have written their columns"""
         _check(_lib.zkh_derive_all(self.ctx, circuit.h, po2, zk_cycles, code.h, data.h))
+
+    def derive_all_paged(self, circuit: Circuit, po2: int, zk_cycles: int, code: Buffer, data: Buffer, image: Optional[Buffer]) -> None:
+        """derive_all with the memory image (a Buffer of W raw Montgomery words, or None) that the links stage of a paging circuit reads
+        (zkh_derive_all_paged); a paging circuit without an image is refused before any stage writes"""
+        _check(_lib.zkh_derive_all_paged(self.ctx, circuit.h, po2, zk_cycles, code.h, data.h, None if image is None else image.h))
+
+    def derive_links_paged(self, circuit: Circuit, po2: int, zk_cycles: int, code: Buffer, data: Buffer, image: Optional[Buffer]) -> None:
+        """derive_links from a memory image (zkh_derive_links_paged): an unlinked access of the paged LINK record takes image[address] as
+        its previous access, and the PAGES record's page table is written.  Raises HalError as derive_links does, and on an address
+        outside the image, a clock 0 and an unlinked load that does not return the image's word (`data` is then unchanged).  Without a
+        PAGES record the image is ignored"""
+        _check(_lib.zkh_derive_links_paged(self.ctx, circuit.h, po2, zk_cycles, code.h, data.h, None if image is None else image.h))
+
+    def page_out(self, circuit: Circuit, po2: int, zk_cycles: int, data: Buffer, image: Buffer) -> None:
+        """write the page table of `data` back into `image`: image[p_addr] = p_out on every active row with p_on = 1 (zkh_page_out).
+        Raises HalError, with the image unchanged, on a p_on other than 0 / 1, an address outside the image, or page addresses that
+        do not strictly increase over a prefix of rows"""
+        _check(_lib.zkh_page_out(self.ctx, circuit.h, po2, zk_cycles, data.h, image.h))
 
     def derive_multiplicities(self, circuit: Circuit, po2: int, zk_cycles: int, code: Buffer, data: Buffer) -> None:
         """fill the derived multiplicity columns of `data` on the active rows (zkh_derive_multiplicities): raises HalError on a table

@@ -293,22 +293,34 @@ class SegmentProver:
             return accum
         return acc
 
-    def seal_host_witness(self, seg: Segment, host_code: np.ndarray, host_data: np.ndarray, out_global, check: bool = False) -> SegmentReceipt:
+    def seal_host_witness(self, seg: Segment, host_code: np.ndarray, host_data: np.ndarray, out_global, check: bool = False,
+                          image=None, page_out: bool = False) -> SegmentReceipt:
         """Seal a segment whose code/data traces live in pinned HOST memory (hal.host_alloc views): enqueue both uploads
         on the context's stream (no host sync), then run the two-halves seal.  This is the PCIe-inclusive path.  A circuit whose
         arguments derive sorted copies, columns, linked accesses or lookup multiplicities gets them filled into the data trace first
         (zkh_derive_all); of those columns only the blinding rows are uploaded (zkh_upload_data_trace).  The accum
         comes from the built-in generator of kinds 1..3, else from zkh_accumulate when the circuit carries arguments.
         check: check the finished witness row by row before the seal is spent on it (check_witness, seal_with_accum), and when
-        zkh_accumulate refuses a bus that does not balance, name the key (check_bus, args_accumulate)."""
+        zkh_accumulate refuses a bus that does not balance, name the key (check_bus, args_accumulate).
+        image: the memory image (a device Buffer of raw Montgomery words) that a circuit whose arguments page memory starts from
+        (zkh_derive_all_paged).  The derive only reads it.  page_out: after the seal has succeeded, write the segment's memory back
+        into `image` (`page_out`), so that the next segment starts from it; a refused or failed seal leaves the image as it was."""
         code = self.hal.alloc_elem("code", host_code.size)
         data = self.hal.alloc_elem("data", host_data.size)
         self.hal.write_async(code, host_code)
         self.hal.upload_data_trace(self.circuit, seg.po2, seg.zk_cycles, data, host_data)
-        self.hal.derive_all(self.circuit, seg.po2, seg.zk_cycles, code, data)
+        self.hal.derive_all_paged(self.circuit, seg.po2, seg.zk_cycles, code, data, image)
         builtin = 1 <= int(self.circuit.desc[13]) <= 3
         acc = self.args_accumulate(seg, code, data, check=check) if not builtin and self.circuit.has_arguments() else self.syn_accumulate(seg, data)
-        return self.seal_with_accum(seg, code, data, out_global, acc, check=check)
+        receipt = self.seal_with_accum(seg, code, data, out_global, acc, check=check)
+        if page_out:
+            self.page_out(seg, data, image)
+        return receipt
+
+    def page_out(self, seg: Segment, data, image) -> None:
+        """write the page table of the segment's derived data trace (a device Buffer) back into the memory image: image[p_addr] = p_out
+        on the rows with p_on = 1 (zkh_page_out).  A call of its own, after the seal: a refused witness never touches the image."""
+        self.hal.page_out(self.circuit, seg.po2, seg.zk_cycles, data, image)
 
     def prove_segment(self, seg: Segment) -> SegmentReceipt:
         code, data, out = self.witgen(seg)
