@@ -9,12 +9,10 @@ the sparse upload.
 Mutants these cases catch (never committed): taking prev from sorted position j + 1 instead of j - 1 fails every case with a linked
 access (`equal`, `range5`, ...); treating the first item of a 4096-item sort tile as unlinked fails `equal` at po2 13, where sorted
 position 4096 continues the one chain."""
-import re
-
 import numpy as np
 import pytest
 
-from args_gpu import circuit as _circuit, enc as _enc, seal_host as _seal_host, upload as _upload
+from args_gpu import circuit as _circuit, enc as _enc, links_refused, profiled, seal_host as _seal_host, upload as _upload
 import zko
 from conftest import rand_fp
 from zeth_amd import hal as zhal
@@ -112,11 +110,7 @@ def test_links_match_the_reference(hal, po2, zk):
         else:
             assert linked > A // 8 and last >= 3
         dcode, ddata = _upload(hal, code, data)
-        hal.prof_enable(True)
-        hal.prof_reset()
-        hal.derive_links(c, po2, zk, dcode, ddata)
-        prof = {r["name"]: r for r in hal.prof_get() if r["calls"]}
-        hal.prof_enable(False)
+        prof = profiled(hal, lambda: hal.derive_links(c, po2, zk, dcode, ddata))
         assert {"sort_keys", "sort_pack", "links_check", "links_write"} <= set(prof), set(prof)
         if kind == "spread31":                                               # bits 0 and 30 are live, 25 or more in all: four digit passes
             k = logup._dec(data.reshape(-1, n)[0, :A]).astype(np.int64)
@@ -212,23 +206,13 @@ def test_syn_lookup_linked_full_at_po2_20(hal, oracle):
 
 
 # ---- refusals ----
-def _refused(hal, desc, blob, po2, zk, code, data, out, want_msg):
-    """derive_links refuses with the reference's words and leaves the data as it was; nothing is sealed from that witness"""
-    with pytest.raises(logup.ReferenceError, match=re.escape(want_msg)):
-        logup.reference_links(logup.Arguments.parse(blob), po2, zk, code, data)
-    c = _circuit(hal, desc, blob)
-    dcode, ddata = _upload(hal, code, data)
-    with pytest.raises(HalError, match=re.escape(want_msg)):
-        hal.derive_links(c, po2, zk, dcode, ddata)
-    assert np.array_equal(ddata.to_vec(), data)
-    with pytest.raises(HalError, match=re.escape(want_msg)):
-        _seal_host(hal, SegmentProver(hal, desc, arguments=blob), Segment(index=0, po2=po2, zk_cycles=zk, noise_seed=NOISE), code, data, out)
+def _refused(hal, desc, blob, po2, zk, code, data, want_msg):
+    links_refused(hal, desc, blob, po2, zk, code, data, want_msg, seal=True)
 
 
 def test_refusals_name_the_lowest_record_and_row_and_leave_data_unchanged(hal):
     po2, zk = 10, 300
     n, A = 1 << po2, (1 << po2) - zk
-    out = np.zeros(4, dtype=np.uint32)
     desc, blob, code, data = _case("two", 9, po2, zk)                        # record 0: selector code 3, clock data 1, L nl = 24 bits
     args = logup.Arguments.parse(blob)
     c2, d2 = code.reshape(-1, n).copy(), data.reshape(-1, n).copy()
@@ -239,19 +223,19 @@ def test_refusals_name_the_lowest_record_and_row_and_leave_data_unchanged(hal):
     chain = [r for r in on0 if k0[r] == k0[on0[5]]]                          # the accesses of record 0 to one address, in row order
     assert len(chain) >= 4
     d2[1, chain[2]] = d2[1, chain[0]]                                        # the clock of the third = the clock of the first
-    _refused(hal, desc, blob, po2, zk, c2.reshape(-1), d2.reshape(-1), out, f"record 1 at row 650: selector {P - 1}, not 0 or 1")
+    _refused(hal, desc, blob, po2, zk, c2, d2, f"record 1 at row 650: selector {P - 1}, not 0 or 1")
     c2[4, 650] = c2[4, 700] = 0
     t0, t1 = int(logup._dec(d2[1, chain[0]])), int(logup._dec(d2[1, chain[1]]))
     msg = f"record 0 at row {chain[2]}: clock not increasing ({t0} after {t1} at row {chain[1]})"
     d2[PER_REC + 1, :A] = d2[PER_REC + 1, ::-1][n - A:]                      # record 1's clocks reversed: bad too, but record 0 is named
-    _refused(hal, desc, blob, po2, zk, c2.reshape(-1), d2.reshape(-1), out, msg)
+    _refused(hal, desc, blob, po2, zk, c2, d2, msg)
     # of two bad rows of one record the lower; a clock equal to the previous one is d = -1
     d2[1, chain[3]] = d2[1, chain[2]]
-    _refused(hal, desc, blob, po2, zk, c2.reshape(-1), d2.reshape(-1), out, msg)
+    _refused(hal, desc, blob, po2, zk, c2, d2, msg)
     # in order, but too wide: 2^24 + 1 after the previous clock
     d3 = data.reshape(-1, n).copy()
     d3[1, chain[1]] = _enc(t0 + (1 << 24) + 1)
-    _refused(hal, desc, blob, po2, zk, code, d3.reshape(-1), out,
+    _refused(hal, desc, blob, po2, zk, code, d3,
              f"record 0 at row {chain[1]}: the clock difference {1 << 24} (after row {chain[0]}) does not fit 3 limbs of 8 bits")
     d3[1, chain[1]] = _enc(t0 + (1 << 24))                                   # the widest that fits: its successor is then behind it
     with pytest.raises(HalError, match=f"record 0 at row {chain[2]}: clock not increasing"):

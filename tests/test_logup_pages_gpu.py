@@ -4,7 +4,8 @@ from an image and goes back into it.  Hand-built load / store traces (pages_case
 one address for every access (D = 1, head and tail 6197 positions apart), all distinct (D = m: every position both head and tail, every
 load answered by the image), five addresses, a sparse selector (D < m < A: both zeroing paths), the addresses 0 and W - 1, raw words >= P
 in key, clock, value and image next to their residues, and a second LINK record that is not paged: the data equals the host reference
-word for word.  The refusals carry the reference's text and leave `data` unchanged; page-out equals `reference_page_out`, a second segment
+word for word, and so does a derive at po2 19, the smallest size at which a thread of the carry scan owns two counters.
+The refusals carry the reference's text and leave `data` unchanged; page-out equals `reference_page_out`, a second segment
 derived from that image equals the walk over both segments, and a refused page-out leaves the image unchanged.  SYN-LOOKUP-paged seals
 byte-identically to the host-made witness under the plain blob, and a forked page yields no accepted seal.
 
@@ -23,7 +24,7 @@ import numpy as np
 import pytest
 
 import pages_cases as pc
-from args_gpu import circuit as _circuit, seal_host as _seal_host, upload as _upload
+from args_gpu import circuit as _circuit, image_buf as _image, links_refused, profiled, seal_host as _seal_host, upload as _upload
 import zko
 from zeth_amd.circuits import logup, syn_lookup
 from zeth_amd.hal import HalError
@@ -35,12 +36,6 @@ NOISE = 0x0C06
 ONE = (1 << 32) % P
 TINY = syn_lookup.TINY
 SIZES = [(8, 40), (12, 1994), (13, 1994)]
-
-
-def _image(hal, image):
-    buf = hal.alloc_elem("image", image.size)
-    buf.write(np.ascontiguousarray(image, dtype=np.uint32))
-    return buf
 
 
 @pytest.mark.parametrize("po2,zk", SIZES)
@@ -68,11 +63,7 @@ def test_pages_match_the_reference(hal, po2, zk):
             assert (image >= P).sum() > image.size // 6 and (d0[pc.KEY, :A] >= P).any() and (d0[pc.CLOCK, :A] >= P).any() and (d0[pc.VALUE, :A] >= P).any()
         dcode, ddata = _upload(hal, code, data)
         dimage = _image(hal, image)
-        hal.prof_enable(True)
-        hal.prof_reset()
-        hal.derive_links_paged(c, po2, zk, dcode, ddata, dimage)
-        prof = {r["name"]: r for r in hal.prof_get() if r["calls"]}
-        hal.prof_enable(False)
+        prof = profiled(hal, lambda: hal.derive_links_paged(c, po2, zk, dcode, ddata, dimage))
         assert {"sort_keys", "sort_pack", "pages_scan", "links_check", "links_write"} <= set(prof), set(prof)
         got = ddata.to_vec()
         bad = np.nonzero(got != want)[0]
@@ -83,6 +74,30 @@ def test_pages_match_the_reference(hal, po2, zk):
         ddata.write(data)                                                    # the stage table hands the image to the links stage
         hal.derive_all_paged(c, po2, zk, dcode, ddata, dimage)
         assert np.array_equal(ddata.to_vec(), want)
+
+
+@pytest.mark.parametrize("kind", ["distinct", "sparse"])
+def test_the_carry_scan_with_two_counters_per_thread(hal, kind):
+    """po2 19 is the smallest size at which a thread of the carry scan owns more than one counter: 2041 workgroups of 256 positions
+    under 1024 threads.  `distinct`: every workgroup's total is 256, so a dropped or shifted carry moves every page; `sparse`: 40
+    pages, most totals 0"""
+    po2, zk = 19, 1994
+    n, A = 1 << po2, (1 << po2) - zk
+    assert (A + 255) // 256 == 2041 > 1024
+    desc, blob, code, data, image = pc.case(kind, 19, po2, zk)
+    args = logup.Arguments.parse(blob)
+    code, data = code.reshape(-1), data.reshape(-1)
+    want = logup.reference_links(args, po2, zk, code, data, image=image)
+    D, m = int((want.reshape(-1, n)[pc.P_ON, :A] == ONE).sum()), pc.accesses(code.reshape(-1, n), data.reshape(-1, n), A, kind).size
+    assert (D, m) == (A, A) if kind == "distinct" else D == 40 and A // 4 < m < A // 3, (D, m)
+    dcode, ddata = _upload(hal, code, data)
+    dimage = _image(hal, image)
+    hal.derive_links_paged(_circuit(hal, desc, blob), po2, zk, dcode, ddata, dimage)
+    got = ddata.to_vec()
+    bad = np.nonzero(got != want)[0]
+    assert bad.size == 0, f"{kind}: {bad.size} words differ, first at column {bad[0] // n}, row {bad[0] % n}"
+    assert np.array_equal(got.reshape(-1, n)[:, A:], data.reshape(-1, n)[:, A:])                 # the blinding rows were not written
+    assert np.array_equal(dimage.to_vec(), image)
 
 
 def test_without_a_pages_record_the_paged_calls_are_the_plain_ones(hal):
@@ -115,19 +130,6 @@ def test_without_a_pages_record_the_paged_calls_are_the_plain_ones(hal):
 
 
 # ---- refusals ----
-def _refused(hal, desc, blob, po2, zk, code, data, image, want_msg):
-    """derive_links_paged refuses with the reference's words and leaves the data and the image as they were"""
-    code, data = np.ascontiguousarray(code).reshape(-1), np.ascontiguousarray(data).reshape(-1)
-    with pytest.raises(logup.ReferenceError, match="^" + re.escape(want_msg) + "$"):
-        logup.reference_links(logup.Arguments.parse(blob), po2, zk, code, data, image=image)
-    c = _circuit(hal, desc, blob)
-    dcode, ddata = _upload(hal, code, data)
-    dimage = _image(hal, image)
-    with pytest.raises(HalError, match=re.escape("derive_links: " + want_msg + ": the witness is refused")):
-        hal.derive_links_paged(c, po2, zk, dcode, ddata, dimage)
-    assert np.array_equal(ddata.to_vec(), data) and np.array_equal(dimage.to_vec(), image)
-
-
 def _first_access(data, A, nth):
     """the row of the nth first access (in row order) of the paged record of a case without a selector, and its address"""
     seen, found = set(), []
@@ -172,7 +174,7 @@ def test_a_paged_refusal_carries_the_reference_text(hal, what):
         blob = short.blob()
         r = min(q for q in range(A) if x(data[pc.KEY, q]) >= 16)
         msg = f"record 2 at row {r}: address {x(data[pc.KEY, r])} does not fit 2 limbs of 2 bits"
-    _refused(hal, desc, blob, po2, zk, code, data, image, msg)
+    links_refused(hal, desc, blob, po2, zk, code, data, msg, image=image)
 
 
 def test_a_paging_circuit_needs_an_image(hal):

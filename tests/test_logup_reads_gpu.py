@@ -25,7 +25,7 @@ from dataclasses import replace
 import numpy as np
 import pytest
 
-from args_gpu import circuit as _circuit, enc as _enc, seal_host as _seal_host, upload as _upload
+from args_gpu import circuit as _circuit, enc as _enc, links_refused, profiled, seal_host as _seal_host, upload as _upload
 import zko
 from conftest import rand_fp
 from zeth_amd.circuits import logup, syn_lookup
@@ -133,11 +133,7 @@ def test_reads_match_the_reference(hal, po2, zk):
         else:
             assert (load & linked).sum() > sel.sum() // 4
         dcode, ddata = _upload(hal, code, data)
-        hal.prof_enable(True)
-        hal.prof_reset()
-        hal.derive_links(c, po2, zk, dcode, ddata)
-        prof = {r["name"]: r for r in hal.prof_get() if r["calls"]}
-        hal.prof_enable(False)
+        prof = profiled(hal, lambda: hal.derive_links(c, po2, zk, dcode, ddata))
         assert {"sort_keys", "sort_pack", "links_check", "links_write"} <= set(prof), set(prof)
         got = ddata.to_vec()
         bad = np.nonzero(got != want)[0]
@@ -154,19 +150,7 @@ def test_reads_match_the_reference(hal, po2, zk):
 
 # ---- refusals ----
 def _refused(hal, desc, blob, po2, zk, code, data, want_msg, seal=True):
-    """derive_links refuses with the reference's words and leaves the data as it was; nothing is sealed from that witness"""
-    code, data = np.ascontiguousarray(code).reshape(-1), np.ascontiguousarray(data).reshape(-1)
-    with pytest.raises(logup.ReferenceError, match="^" + re.escape(want_msg) + "$"):
-        logup.reference_links(logup.Arguments.parse(blob), po2, zk, code, data)
-    c = _circuit(hal, desc, blob)
-    dcode, ddata = _upload(hal, code, data)
-    with pytest.raises(HalError, match=re.escape("derive_links: " + want_msg + ": the witness is refused")):
-        hal.derive_links(c, po2, zk, dcode, ddata)
-    assert np.array_equal(ddata.to_vec(), data)
-    if seal:
-        with pytest.raises(HalError, match=re.escape(want_msg)):
-            _seal_host(hal, SegmentProver(hal, desc, arguments=blob), Segment(index=0, po2=po2, zk_cycles=zk, noise_seed=NOISE), code, data,
-                       np.zeros(4, dtype=np.uint32))
+    links_refused(hal, desc, blob, po2, zk, code, data, want_msg, seal=seal)
 
 
 def _store_then_bad_load(data, row, value=4242):

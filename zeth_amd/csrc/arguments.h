@@ -105,7 +105,7 @@ inline TermCols term_cols(const Term& t) {
 // the words a term reads per row for its weight and tuple (selector, multiplicity, tuple columns): the ProfScope byte counts of its consumers
 inline uint32_t entry_words(const Term& t) { return t.w + (t.sel != NONE) + (t.mg != NONE); }
 
-// what the entry points over a trace share: po2 in 1..24, an active row left, the code / data (and, if given, accum) buffers of the
+// what the entry points over a trace share: po2 in 1..24, an active row left, the data (and, if given, code and accum) buffers of the
 // circuit's widths at 2^po2 rows.  `who` prefixes the messages.  *n = rows, *A = active rows.
 const char* trace_rows(const char* who, const zkh_circuit* c, size_t po2, size_t zk_cycles, const zkh_buf* code, const zkh_buf* data,
                        const zkh_buf* accum, size_t* n, uint32_t* A);

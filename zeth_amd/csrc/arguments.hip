@@ -402,7 +402,7 @@ const char* zkh::trace_rows(const char* who, const zkh_circuit* c, size_t po2, s
     *n = (size_t)1 << po2;
     ZKH_REQUIRE(zk_cycles < *n, "%s: zk_cycles %zu leaves no active row at po2 %zu", who, zk_cycles, po2);
     *A = (uint32_t)(*n - zk_cycles);
-    ZKH_REQUIRE(code->len == (size_t)c->group_size[GROUP_CODE] * *n && data->len == (size_t)c->group_size[GROUP_DATA] * *n &&
+    ZKH_REQUIRE((!code || code->len == (size_t)c->group_size[GROUP_CODE] * *n) && data->len == (size_t)c->group_size[GROUP_DATA] * *n &&
                 (!accum || accum->len == (size_t)c->group_size[GROUP_ACCUM] * *n), "%s: buffer shape mismatch", who);
     return nullptr;
 }

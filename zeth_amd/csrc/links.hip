@@ -41,13 +41,14 @@
 // unchanged, the lowest row whose p_on is not 0 / 1, whose address is >= W or does not follow a smaller one on a row with p_on = 1: a table
 // that repeats an address is REFUSED, so the scatter never writes one word twice.
 //
-// The paged passes reuse the one sort.  Position t of the paged record is a HEAD when the packed key at t - 1 differs (the first access of
-// its address) and a TAIL when the one at t + 1 does: neighbouring packed keys, coalesced.  An inclusive scan of the head flags over the m
+// The paged passes reuse the one sort, and they are the same kernel (k_links<.., kPaged>: one body for the link semantics and the read rule;
+// the plain passes compile the paging out).  Position t of the paged record is a HEAD when the packed key at t - 1 differs (the first access
+// of its address) and a TAIL when the one at t + 1 does: neighbouring packed keys, coalesced.  An inclusive scan of the head flags over the m
 // sorted positions gives every position its page index + 1: k_page_heads scans inside a workgroup (scan.h's block_scan) and leaves the
-// workgroup's total, k_page_carry — ONE workgroup, so none waits for another — turns the totals into exclusive carries and leaves D; the
-// consumers add carry[workgroup] to the local index.  k_links_paged is k_links with the image: its check pass adds the image reads and
-// the new refusals to the same wave minimum and the same atomicMin; its write pass also fills the table — head lanes p_on, p_addr, p_in,
-// alimb and gap (the previous address re-read from the trace at rows[t - 1]: packed keys drop bits and are no addresses), tail lanes
+// workgroup's total, the sort's counter scan (sort.h scan_counters, ONE workgroup, so none waits for another) turns the totals into
+// exclusive carries and leaves D; the consumers add carry[workgroup] to the local index.  The paged check pass adds the image reads and
+// the new refusals to the same wave minimum and the same atomicMin; the paged write pass also fills the table — head lanes p_on, p_addr,
+// p_in, alimb and gap (the previous address re-read from the trace at rows[t - 1]: packed keys drop bits and are no addresses), tail lanes
 // p_out and p_time, lanes D <= t < A zeros (coalesced).  No atomic but that min: the result is a function of the traces and the image.
 #include "scan.h"
 #include "sort.h"
@@ -58,80 +59,17 @@ namespace {
 
 constexpr uint32_t LINK_THREADS = 256;
 
-// grid (ceil(A / LINK_THREADS), records).  kWrite = false: the check pass (bad = the lowest bad record << 32 | row, the record by its place
-// among the LINK records); kWrite = true: the write pass over a witness that passed.  kReads: the check pass of a blob in which a
-// record has READS; the flag is uniform per record, so the branch is scalar, and which rule a row broke the host finds out by reading
-// its few cells back.  The record's words are read through the uniform pointer (scalar loads): nothing is indexed in registers.
-template <bool kWrite, bool kReads>
-__global__ __launch_bounds__(LINK_THREADS) void k_links(const uint32_t* __restrict__ code, uint32_t* data, const Link* __restrict__ links,
-                                                        const uint32_t* __restrict__ status, const unsigned long long* __restrict__ keys,
-                                                        const uint32_t* __restrict__ rows, uint32_t n, uint32_t A, unsigned long long* __restrict__ bad) {
-    const uint32_t p = blockIdx.y;
-    const Link* __restrict__ rec = links + p;
-    const uint32_t m = status[ST_HEAD + ST_WORDS * p + ST_M];                 // the record's accesses: m <= A
-    const uint32_t t = blockIdx.x * LINK_THREADS + threadIdx.x;             // a sorted position (t < m) and, in the write pass, a row (t < A)
-    const size_t base = (size_t)p * A;
-    const bool access = t < m;
-    uint32_t row = 0, prow = 0;
-    bool linked = false, last = false;
-    if (access) {
-        const unsigned long long key = keys[base + t];
-        row = rows[base + t];
-        if (t) {
-            linked = keys[base + t - 1] == key;
-            prow = rows[base + t - 1];
-        }
-        last = t + 1 >= m || keys[base + t + 1] != key;
-    }
-    long long d = 0;
-    if (linked) {
-        const uint32_t* clock = group_ptr(code, data, rec->cg[0]) + (size_t)rec->cc[0] * n;
-        d = (long long)canonical(clock[row]) - canonical(clock[prow]) - 1;
-    }
-    const uint32_t L = rec->L, nl = rec->nl;
-    if (!kWrite) {
-        uint32_t mine = linked && (d < 0 || (d >> (L * nl)) != 0) ? row : NONE;
-        if constexpr (kReads) {
-            if ((rec->flags & LINK_READS) && access) {
-                const uint32_t w = cell(code, data, rec->wg, rec->wc, n, row);
-                bool ok = w == 0 || w == R1;
-                if (w == 0) {                             // a load: every value column equals the previous access's, or 0 without one
-                    const uint32_t nc = rec->nc;
-                    for (uint32_t j = 1; j < nc; j++) {
-                        const uint32_t* col = group_ptr(code, data, rec->cg[j]) + (size_t)rec->cc[j] * n;
-                        ok &= col[row] % P == (linked ? col[prow] % P : 0);
-                    }
-                }
-                if (!ok) mine = row;
-            }
-        }
-        // report_bad_row (arguments.h) written out: through the helper this kernel's argument loads are scheduled otherwise
-        if (__ballot(mine != NONE) != 0) {                // wave-uniform: only a wave that found one reduces and writes
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) {
-                const uint32_t o = __shfl_xor(mine, off, 64);
-                mine = o < mine ? o : mine;
-            }
-            if ((threadIdx.x & 63) == 0) atomicMin(bad, ((unsigned long long)p << 32) | mine);
-        }
-        return;
-    }
-    const uint32_t nc = rec->nc, n_dst = rec->n_dst;
-    if (rec->sel != NONE && t < A && sel_class(code, rec->sel, n, t) != 1)
-        for (uint32_t e = 0; e < n_dst; e++) data[(size_t)rec->dst[e] * n + t] = 0;
-    if (!access) return;
-    data[(size_t)rec->dst[0] * n + row] = linked ? R1 : 0;
-    data[(size_t)rec->dst[1] * n + row] = last ? R1 : 0;
-    for (uint32_t j = 0; j < nc; j++)
-        data[(size_t)rec->dst[2 + j] * n + row] = linked ? group_ptr(code, data, rec->cg[j])[(size_t)rec->cc[j] * n + prow] : 0;
-    const uint32_t mask = (1u << L) - 1;                  // L <= 16
-    for (uint32_t j = 0; j < nl; j++)
-        data[(size_t)rec->dst[2 + nc + j] * n + row] = fp_encode((uint32_t)((unsigned long long)d >> (j * L)) & mask).v;
-}
-
-
 // ---- paging ----
 constexpr uint32_t PG_TOTAL = 0;                        // word 0 of the carry buffer: D, the pages; the workgroups' carries follow from word 1
+
+// what the paged passes of k_links read on top of the plain ones'; the plain passes get a zeroed one and read none of it
+struct Paging {
+    const Pages* pg;                                    // the PAGES record
+    uint32_t paged;                                     // the place among the LINK records of the record it pages
+    const uint32_t* image;
+    uint32_t W;                                         // the image's words
+    const uint32_t *local, *sums;                       // the page scan: k_page_heads' local indices; D and the workgroups' carries
+};
 
 // grid ceil(m_max / LINK_THREADS) over the sorted positions of the paged record (its place p among the LINK records): local[t] = the heads
 // among the positions of t's workgroup up to t, sums[1 + workgroup] = the workgroup's heads
@@ -147,37 +85,23 @@ __global__ __launch_bounds__(LINK_THREADS) void k_page_heads(const uint32_t* __r
     if (threadIdx.x == LINK_THREADS - 1) sums[1 + blockIdx.x] = incl;
 }
 
-// one workgroup: sums[1 + b] = the heads of the workgroups below b (their exclusive scan, in place), sums[PG_TOTAL] = D.  Thread t scans
-// the chunk of `per` consecutive workgroups [t per, (t + 1) per).
-__global__ __launch_bounds__(LINK_THREADS) void k_page_carry(uint32_t* __restrict__ sums, uint32_t nb, uint32_t per) {
-    __shared__ uint32_t buf[2][LINK_THREADS];
-    const uint32_t lo = threadIdx.x * per, hi = lo + per < nb ? lo + per : nb;
-    uint32_t mine = 0;
-    for (uint32_t b = lo; b < hi; b++) mine += sums[1 + b];
-    const uint32_t incl = block_scan<LINK_THREADS>(mine, buf, AddWrap());
-    uint32_t run = incl - mine;
-    for (uint32_t b = lo; b < hi; b++) {
-        const uint32_t v = sums[1 + b];
-        sums[1 + b] = run;
-        run += v;
-    }
-    if (threadIdx.x == LINK_THREADS - 1) sums[PG_TOTAL] = incl;
-}
-
-// k_links over a blob with a PAGES record `pg` that pages the record at place `paged`: grid (ceil(A / LINK_THREADS), records), both passes
-// as k_links', every record with the read rule where it has READS.  Whether blockIdx.y is the paged record is uniform: a scalar branch.
-// bad: the lowest (place << 32 | row), the PAGES record's own refusal under the place `records` (it comes after every LINK).
-template <bool kWrite>
-__global__ __launch_bounds__(LINK_THREADS) void k_links_paged(const uint32_t* __restrict__ code, uint32_t* data, const Link* __restrict__ links,
-                                                              const uint32_t* __restrict__ status, const unsigned long long* __restrict__ keys,
-                                                              const uint32_t* __restrict__ rows, uint32_t n, uint32_t A, unsigned long long* __restrict__ bad,
-                                                              const Pages* __restrict__ pg, uint32_t paged, const uint32_t* __restrict__ image, uint32_t W,
-                                                              const uint32_t* __restrict__ local, const uint32_t* __restrict__ sums) {
+// grid (ceil(A / LINK_THREADS), records).  kWrite = false: the check pass (bad = the lowest bad record << 32 | row, the record by its place
+// among the LINK records; the PAGES record's own refusal under the place `records`: it comes after every LINK); kWrite = true: the write
+// pass over a witness that passed.  kReads: the check pass of a blob in which a record has READS; the flag is uniform per record, so the
+// branch is scalar, and which rule a row broke the host finds out by reading its few cells back.  kPaged: the blob has a PAGES record, and
+// `pages` says whether blockIdx.y is the record it pages (uniform: a scalar branch); without kPaged `pages` is the constant false, `word`
+// the constant 0, and nothing of `pa` is read.  The record's words are read through the uniform pointer (scalar loads): nothing is indexed
+// in registers.
+template <bool kWrite, bool kReads, bool kPaged>
+__global__ __launch_bounds__(LINK_THREADS) void k_links(const uint32_t* __restrict__ code, uint32_t* data, const Link* __restrict__ links,
+                                                        const uint32_t* __restrict__ status, const unsigned long long* __restrict__ keys,
+                                                        const uint32_t* __restrict__ rows, uint32_t n, uint32_t A, unsigned long long* __restrict__ bad,
+                                                        const Paging pa) {
     const uint32_t p = blockIdx.y;
     const Link* __restrict__ rec = links + p;
-    const bool pages = p == paged;
-    const uint32_t m = status[ST_HEAD + ST_WORDS * p + ST_M];
-    const uint32_t t = blockIdx.x * LINK_THREADS + threadIdx.x;
+    const bool pages = kPaged && p == pa.paged;
+    const uint32_t m = status[ST_HEAD + ST_WORDS * p + ST_M];                 // the record's accesses: m <= A
+    const uint32_t t = blockIdx.x * LINK_THREADS + threadIdx.x;             // a sorted position (t < m) and, in the write pass, a row (t < A)
     const size_t base = (size_t)p * A;
     const bool access = t < m;
     uint32_t row = 0, prow = 0;
@@ -191,49 +115,62 @@ __global__ __launch_bounds__(LINK_THREADS) void k_links_paged(const uint32_t* __
         }
         last = t + 1 >= m || keys[base + t + 1] != key;
     }
-    const uint32_t* clock = group_ptr(code, data, rec->cg[0]) + (size_t)rec->cc[0] * n;
-    const uint32_t* keycol = group_ptr(code, data, rec->kg) + (size_t)rec->kc * n;
+    const bool from_image = pages && access && !linked;  // an unlinked access of the paged record: the image is its previous access, at clock 0
     long long d = 0;
+    if (linked || from_image) {
+        const uint32_t* clock = group_ptr(code, data, rec->cg[0]) + (size_t)rec->cc[0] * n;
+        d = (long long)canonical(clock[row]) - (linked ? canonical(clock[prow]) : 0) - 1;       // clock 0 is the image's: d = -1 refuses it
+    }
     uint32_t addr = 0, word = 0;                          // the paged record's access: its address and, in range, the image's word
     bool inside = true;
-    if (linked) d = (long long)canonical(clock[row]) - canonical(clock[prow]) - 1;
     if (pages && access) {
-        addr = canonical(keycol[row]);
-        inside = addr < W;
-        if (inside) word = image[addr];
-        if (!linked) d = (long long)canonical(clock[row]) - 1;      // clock 0 is the image's: d = -1 refuses it
+        addr = canonical(group_ptr(code, data, rec->kg)[(size_t)rec->kc * n + row]);
+        inside = addr < pa.W;
+        if (inside) word = pa.image[addr];
     }
     const uint32_t L = rec->L, nl = rec->nl;
     if (!kWrite) {
-        uint32_t mine = (linked || (pages && access)) && (d < 0 || (d >> (L * nl)) != 0) ? row : NONE;
+        uint32_t mine = (linked || from_image) && (d < 0 || (d >> (L * nl)) != 0) ? row : NONE;
         if (!inside) mine = row;
-        if ((rec->flags & LINK_READS) && access) {
-            const uint32_t w = cell(code, data, rec->wg, rec->wc, n, row);
-            bool ok = w == 0 || w == R1;
-            if (w == 0) {                                 // a load: the previous access's values; unlinked: 0, or the image's word (residues)
-                const uint32_t nc = rec->nc;
-                for (uint32_t j = 1; j < nc; j++) {
-                    const uint32_t* col = group_ptr(code, data, rec->cg[j]) + (size_t)rec->cc[j] * n;
-                    ok &= col[row] % P == (linked ? col[prow] % P : pages ? word % P : 0);
+        if constexpr (kReads) {
+            if ((rec->flags & LINK_READS) && access) {
+                const uint32_t w = cell(code, data, rec->wg, rec->wc, n, row);
+                bool ok = w == 0 || w == R1;
+                if (w == 0) {                             // a load: every value column equals the previous access's; without one 0, or the image's word
+                    const uint32_t nc = rec->nc;
+                    for (uint32_t j = 1; j < nc; j++) {
+                        const uint32_t* col = group_ptr(code, data, rec->cg[j]) + (size_t)rec->cc[j] * n;
+                        ok &= col[row] % P == (linked ? col[prow] % P : word % P);
+                    }
                 }
+                if (!ok) mine = row;
             }
-            if (!ok) mine = row;
         }
-        report_bad_row(bad, p, mine);
-        if (pages) report_bad_row(bad, gridDim.y, access && (addr >> (pg->L * pg->ng)) != 0 ? row : NONE);     // an address the limbs do not hold
+        // report_bad_row (arguments.h) written out: through the helper this kernel's argument loads are scheduled otherwise
+        if (__ballot(mine != NONE) != 0) {                // wave-uniform: only a wave that found one reduces and writes
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) {
+                const uint32_t o = __shfl_xor(mine, off, 64);
+                mine = o < mine ? o : mine;
+            }
+            if ((threadIdx.x & 63) == 0) atomicMin(bad, ((unsigned long long)p << 32) | mine);
+        }
+        if (pages) report_bad_row(bad, gridDim.y, access && (addr >> (pa.pg->L * pa.pg->ng)) != 0 ? row : NONE);     // an address the limbs do not hold
         return;
     }
     const uint32_t nc = rec->nc, n_dst = rec->n_dst;
     if (rec->sel != NONE && t < A && sel_class(code, rec->sel, n, t) != 1)
         for (uint32_t e = 0; e < n_dst; e++) data[(size_t)rec->dst[e] * n + t] = 0;
-    if (pages) {
-        const uint32_t D = sums[PG_TOTAL];
+    if (pages) {                                          // the page table
+        const Pages* __restrict__ pg = pa.pg;
+        const uint32_t D = pa.sums[PG_TOTAL];
         if (t >= D && t < A)                              // the rows below the table, coalesced
             for (uint32_t e = 0; e < pg->n_dst; e++) data[(size_t)pg->dst[e] * n + t] = 0;
         if (access && (!linked || last)) {
-            const uint32_t i = local[t] + sums[1 + blockIdx.x] - 1;      // the page of t's address: the heads up to t, less one
+            const uint32_t i = pa.local[t] + pa.sums[1 + blockIdx.x] - 1;      // the page of t's address: the heads up to t, less one
             const uint32_t Lp = pg->L, ng = pg->ng, maskp = (1u << Lp) - 1;
             if (!linked) {                                // the head: the first access of the address
+                const uint32_t* keycol = group_ptr(code, data, rec->kg) + (size_t)rec->kc * n;
                 data[(size_t)pg->dst[PG_ON] * n + i] = R1;
                 data[(size_t)pg->dst[PG_ADDR] * n + i] = keycol[row];
                 data[(size_t)pg->dst[PG_IN] * n + i] = word;
@@ -245,16 +182,15 @@ __global__ __launch_bounds__(LINK_THREADS) void k_links_paged(const uint32_t* __
             }
             if (last) {                                   // the tail: the last access of the address
                 data[(size_t)pg->dst[PG_OUT] * n + i] = group_ptr(code, data, rec->cg[1])[(size_t)rec->cc[1] * n + row];
-                data[(size_t)pg->dst[PG_TIME] * n + i] = clock[row];
+                data[(size_t)pg->dst[PG_TIME] * n + i] = group_ptr(code, data, rec->cg[0])[(size_t)rec->cc[0] * n + row];
             }
         }
     }
     if (!access) return;
-    const bool from_image = pages && !linked;
     data[(size_t)rec->dst[0] * n + row] = linked ? R1 : 0;
     data[(size_t)rec->dst[1] * n + row] = last ? R1 : 0;
-    for (uint32_t j = 0; j < nc; j++)
-        data[(size_t)rec->dst[2 + j] * n + row] = linked ? group_ptr(code, data, rec->cg[j])[(size_t)rec->cc[j] * n + prow] : from_image && j == 1 ? word : 0;
+    for (uint32_t j = 0; j < nc; j++)                     // the previous access's cells; an unlinked access: 0, and the image's word for the paged value
+        data[(size_t)rec->dst[2 + j] * n + row] = linked ? group_ptr(code, data, rec->cg[j])[(size_t)rec->cc[j] * n + prow] : j == 1 ? word : 0;
     const uint32_t mask = (1u << L) - 1;                  // L <= 16
     for (uint32_t j = 0; j < nl; j++)
         data[(size_t)rec->dst[2 + nc + j] * n + row] = fp_encode((uint32_t)((unsigned long long)d >> (j * L)) & mask).v;
@@ -281,12 +217,64 @@ __global__ __launch_bounds__(LINK_THREADS) void k_page_out(const uint32_t* __res
     }
     if (!kWrite) report_bad_row(bad, 0, mine);
 }
-}  // namespace
 
-namespace {
+// Which rule the refused access `row` of the LINK record r broke, as the reference names it (pages: r is the paged record, and `image` its
+// image): the access and its previous one are found on the host as the reference finds them, from the key and the selector of rows [0, row].
+const char* refusal(zkh_ctx* ctx, const zkh_buf* code, const zkh_buf* data, size_t n, const Link& r, uint32_t row, bool pages, const zkh_buf* image) {
+    std::vector<uint32_t> key(row + 1), sel(row + 1, R1);
+    ZKH_TRY(zkh_read(ctx, r.kg == GROUP_CODE ? code : data, key.data(), (size_t)r.kc * n, row + 1));
+    if (r.sel != NONE) ZKH_TRY(zkh_read(ctx, code, sel.data(), (size_t)r.sel * n, row + 1));
+    uint32_t prow = row;                                  // prow == row: no earlier access has its key (unlinked)
+    for (uint32_t q = row; q-- > 0;)
+        if (sel[q] % P == R1 && key[q] % P == key[row] % P) { prow = q; break; }
+    const bool linked = prow != row;
+    if (r.flags & LINK_READS) {
+        uint32_t w;
+        ZKH_TRY(read_cell(ctx, code, data, r.wg, r.wc, n, row, &w));
+        if (w > 1) return make_err("derive_links: record %u at row %u: write flag %u, not 0 or 1: the witness is refused", r.index, row, w);
+    }
+    const uint32_t addr = canonical(key[row]);
+    uint32_t word = 0;                                    // paged: the image's word at the address, canonical
+    if (pages) {
+        const uint32_t W = (uint32_t)image->len;
+        if (addr >= W) return make_err("derive_links: record %u at row %u: address %u outside the image of %u words: the witness is refused", r.index, row, addr, W);
+        ZKH_TRY(zkh_read(ctx, image, &word, addr, 1));
+        word = canonical(word);
+    }
+    if (linked || pages) {
+        long long now, before = 0;
+        ZKH_TRY(read_cell(ctx, code, data, r.cg[0], r.cc[0], n, row, &now));
+        if (linked) ZKH_TRY(read_cell(ctx, code, data, r.cg[0], r.cc[0], n, prow, &before));
+        if (!linked && now == 0) return make_err("derive_links: record %u at row %u: clock 0 is the image's: the witness is refused", r.index, row);
+        const long long d = now - before - 1;
+        if (d < 0)
+            return make_err("derive_links: record %u at row %u: clock not increasing (%lld after %lld at row %u): the witness is refused", r.index, row, now, before, prow);
+        if ((d >> (r.L * r.nl)) != 0 && linked)
+            return make_err("derive_links: record %u at row %u: the clock difference %lld (after row %u) does not fit %u limbs of %u bits: the witness is refused",
+                            r.index, row, d, prow, r.nl, r.L);
+        if ((d >> (r.L * r.nl)) != 0)
+            return make_err("derive_links: record %u at row %u: the clock difference %lld (after the image) does not fit %u limbs of %u bits: the witness is refused",
+                            r.index, row, d, r.nl, r.L);
+    }
+    for (uint32_t j = 1; (r.flags & LINK_READS) && j < r.nc; j++) {     // a load (the write flag is 0, or something above was named)
+        uint32_t now, before = pages ? word : 0;
+        ZKH_TRY(read_cell(ctx, code, data, r.cg[j], r.cc[j], n, row, &now));
+        if (linked) ZKH_TRY(read_cell(ctx, code, data, r.cg[j], r.cc[j], n, prow, &before));
+        if (now == before) continue;
+        if (linked)
+            return make_err("derive_links: record %u at row %u: a load of carried column %u returns %u, but %u was last stored (row %u): the witness is refused",
+                            r.index, row, j, now, before, prow);
+        if (pages)
+            return make_err("derive_links: record %u at row %u: a load of carried column %u returns %u, but the image holds %u at its address %u: the witness is "
+                            "refused", r.index, row, j, now, before, addr);
+        return make_err("derive_links: record %u at row %u: a load of carried column %u returns %u, but its address was never accessed: the value must be 0: "
+                        "the witness is refused", r.index, row, j, now);
+    }
+    return make_err("derive_links: record %u at row %u was refused, but the host finds no rule it breaks", r.index, row);
+}
 
 // zkh_derive_links (image = NULL) and zkh_derive_links_paged: one sort, the check pass, one read-back, the write pass.  With a PAGES record
-// both passes are k_links_paged's and the page scan runs between the sort and the check.
+// both passes are k_links' paged ones and the page scan runs between the sort and the check.
 const char* derive_links(zkh_ctx* ctx, const zkh_circuit* c, size_t po2, size_t zk_cycles, const zkh_buf* code, zkh_buf* data, const zkh_buf* image) {
     ZKH_REQUIRE(ctx && c && data, "derive_links: null argument");
     ZKH_REQUIRE(code, "derive_links: the raw code trace is required (the selectors and code-group source columns of the records read it)");
@@ -326,33 +314,29 @@ const char* derive_links(zkh_ctx* ctx, const zkh_circuit* c, size_t po2, size_t 
     double carried = 0, dsts = 0;
     for (const Link& r : links) { carried += r.nc; dsts += r.n_dst; }
     const uint32_t nb = (A + LINK_THREADS - 1) / LINK_THREADS;
-    const dim3 grid(nb, nr);
     const bool reads = c->args->reads != 0;             // a record has READS: the check pass with the read rule, over all records
-    const Link* d_recs = (const Link*)drecs->ptr();
-    const Pages* d_pg = nullptr;
-    const uint32_t W = paging ? (uint32_t)image->len : 0;
+    Paging pa{};
     if (paging) {                                       // every sorted position of the paged record gets its page: a two-level scan of the head flags
         const Pages& g = c->args->pages[0];
         ZKH_TRY(zkh_copy_from(ctx, "pages_record", (const uint32_t*)&g, sizeof(Pages) / 4, dpages.out()));
-        d_pg = (const Pages*)dpages->ptr();
         ZKH_TRY(new_buf(ctx, A, false, local.out()));
         ZKH_TRY(new_buf(ctx, 1 + (size_t)nb, false, sums.out()));
+        pa = Paging{(const Pages*)dpages->ptr(), (uint32_t)paged, image->ptr(), (uint32_t)image->len, local->ptr(), sums->ptr()};
         ProfScope prof(ctx, "pages_scan", 12.0 * A + 8.0 * nb);            // the keys of every position, its index, the workgroups' totals twice
         k_page_heads<<<nb, LINK_THREADS, 0, ctx->stream>>>(sorted.status->ptr(), sorted.keys(), (uint32_t)paged, A, local->ptr(), sums->ptr());
         ZKH_TRY(last_launch_error("pages_heads"));
-        k_page_carry<<<1, LINK_THREADS, 0, ctx->stream>>>(sums->ptr(), nb, (nb + LINK_THREADS - 1) / LINK_THREADS);
+        scan_counters(ctx, sums->ptr() + 1, 1, nb, sums->ptr() + PG_TOTAL, 0);      // the totals become the workgroups' carries, their sum D
         ZKH_TRY(last_launch_error("pages_carry"));
     }
+    auto pass = [&](auto* kernel) {
+        kernel<<<dim3(nb, nr), LINK_THREADS, 0, ctx->stream>>>(code->ptr(), data->ptr(), (const Link*)drecs->ptr(), sorted.status->ptr(), sorted.keys(), sorted.rows(),
+                                                              (uint32_t)n, A, bad.ptr(), pa);
+    };
     {
         double cells = 0;                                 // with READS: the write flag and, at most, the value cells at both rows
         for (const Link& r : links) cells += r.flags & LINK_READS ? 1 + 2 * (r.nc - 1) : 0;
         ProfScope prof(ctx, "links_check", (20.0 * nr + 4.0 * cells + (paging ? 8.0 : 0.0)) * A);   // key and row of every item; the clock at both rows; paged: the key and the image's word
-        if (paging)
-            k_links_paged<false><<<grid, LINK_THREADS, 0, ctx->stream>>>(code->ptr(), data->ptr(), d_recs, sorted.status->ptr(), sorted.keys(), sorted.rows(), (uint32_t)n, A,
-                                                                         bad.ptr(), d_pg, (uint32_t)paged, image->ptr(), W, local->ptr(), sums->ptr());
-        else
-            (reads ? k_links<false, true> : k_links<false, false>)<<<grid, LINK_THREADS, 0, ctx->stream>>>(code->ptr(), data->ptr(), d_recs, sorted.status->ptr(),
-                                                                                                           sorted.keys(), sorted.rows(), (uint32_t)n, A, bad.ptr());
+        pass(paging ? k_links<false, true, true> : reads ? k_links<false, true, false> : k_links<false, false, false>);
         ZKH_TRY(last_launch_error("links_check"));
     }
     ZKH_TRY(bad.read(ctx));
@@ -362,70 +346,10 @@ const char* derive_links(zkh_ctx* ctx, const zkh_circuit* c, size_t po2, size_t 
         ZKH_TRY(read_cell(ctx, code, data, links[paged].kg, links[paged].kc, n, bad.lo, &a));
         return make_err("derive_links: record %u at row %u: address %u does not fit %u limbs of %u bits: the witness is refused", g.index, bad.lo, a, g.ng, g.L);
     }
-    if (bad.found) {
-        // the refused access and its previous one, found on the host as the reference finds them: the key and the selector of rows [0, row]
-        const Link& r = links[bad.hi];
-        const uint32_t row = bad.lo;
-        const bool pages = (int)bad.hi == paged;
-        std::vector<uint32_t> key(row + 1), sel(row + 1, R1);
-        ZKH_TRY(zkh_read(ctx, r.kg == GROUP_CODE ? code : data, key.data(), (size_t)r.kc * n, row + 1));
-        if (r.sel != NONE) ZKH_TRY(zkh_read(ctx, code, sel.data(), (size_t)r.sel * n, row + 1));
-        uint32_t prow = row;                              // prow == row: no earlier access has its key (unlinked)
-        for (uint32_t q = row; q-- > 0;)
-            if (sel[q] % P == R1 && key[q] % P == key[row] % P) { prow = q; break; }
-        const bool linked = prow != row;
-        if (r.flags & LINK_READS) {
-            uint32_t w;
-            ZKH_TRY(read_cell(ctx, code, data, r.wg, r.wc, n, row, &w));
-            if (w > 1) return make_err("derive_links: record %u at row %u: write flag %u, not 0 or 1: the witness is refused", r.index, row, w);
-        }
-        const uint32_t addr = canonical(key[row]);
-        uint32_t word = 0;                                // paged: the image's word at the address, canonical
-        if (pages) {
-            if (addr >= W) return make_err("derive_links: record %u at row %u: address %u outside the image of %u words: the witness is refused", r.index, row, addr, W);
-            ZKH_TRY(zkh_read(ctx, image, &word, addr, 1));
-            word = canonical(word);
-        }
-        if (linked || pages) {
-            long long now, before = 0;
-            ZKH_TRY(read_cell(ctx, code, data, r.cg[0], r.cc[0], n, row, &now));
-            if (linked) ZKH_TRY(read_cell(ctx, code, data, r.cg[0], r.cc[0], n, prow, &before));
-            if (!linked && now == 0) return make_err("derive_links: record %u at row %u: clock 0 is the image's: the witness is refused", r.index, row);
-            const long long d = now - before - 1;
-            if (d < 0)
-                return make_err("derive_links: record %u at row %u: clock not increasing (%lld after %lld at row %u): the witness is refused", r.index, row, now, before, prow);
-            if ((d >> (r.L * r.nl)) != 0 && linked)
-                return make_err("derive_links: record %u at row %u: the clock difference %lld (after row %u) does not fit %u limbs of %u bits: the witness is refused",
-                                r.index, row, d, prow, r.nl, r.L);
-            if ((d >> (r.L * r.nl)) != 0)
-                return make_err("derive_links: record %u at row %u: the clock difference %lld (after the image) does not fit %u limbs of %u bits: the witness is refused",
-                                r.index, row, d, r.nl, r.L);
-        }
-        for (uint32_t j = 1; (r.flags & LINK_READS) && j < r.nc; j++) {     // a load (the write flag is 0, or something above was named)
-            uint32_t now, before = pages ? word : 0;
-            ZKH_TRY(read_cell(ctx, code, data, r.cg[j], r.cc[j], n, row, &now));
-            if (linked) ZKH_TRY(read_cell(ctx, code, data, r.cg[j], r.cc[j], n, prow, &before));
-            if (now == before) continue;
-            if (linked)
-                return make_err("derive_links: record %u at row %u: a load of carried column %u returns %u, but %u was last stored (row %u): the witness is refused",
-                                r.index, row, j, now, before, prow);
-            if (pages)
-                return make_err("derive_links: record %u at row %u: a load of carried column %u returns %u, but the image holds %u at its address %u: the witness is "
-                                "refused", r.index, row, j, now, before, addr);
-            return make_err("derive_links: record %u at row %u: a load of carried column %u returns %u, but its address was never accessed: the value must be 0: "
-                            "the witness is refused", r.index, row, j, now);
-        }
-        return make_err("derive_links: record %u at row %u was refused, but the host finds no rule it breaks", r.index, row);
-    }
+    if (bad.found) return refusal(ctx, code, data, n, links[bad.hi], bad.lo, (int)bad.hi == paged, image);
     {
-        const Pages* g = paging ? &c->args->pages[0] : nullptr;
-        ProfScope prof(ctx, "links_write", (20.0 * nr + 4.0 * carried + 4.0 * dsts + (paging ? 12.0 + 4.0 * g->n_dst : 0.0)) * A);
-        if (paging)
-            k_links_paged<true><<<grid, LINK_THREADS, 0, ctx->stream>>>(code->ptr(), data->ptr(), d_recs, sorted.status->ptr(), sorted.keys(), sorted.rows(), (uint32_t)n, A,
-                                                                        bad.ptr(), d_pg, (uint32_t)paged, image->ptr(), W, local->ptr(), sums->ptr());
-        else
-            k_links<true, false><<<grid, LINK_THREADS, 0, ctx->stream>>>(code->ptr(), data->ptr(), d_recs, sorted.status->ptr(), sorted.keys(), sorted.rows(),
-                                                                       (uint32_t)n, A, bad.ptr());
+        ProfScope prof(ctx, "links_write", (20.0 * nr + 4.0 * carried + 4.0 * dsts + (paging ? 12.0 + 4.0 * c->args->pages[0].n_dst : 0.0)) * A);
+        pass(paging ? k_links<true, false, true> : k_links<true, false, false>);
         ZKH_TRY(last_launch_error("links_write"));
     }
     // the temporaries go back to the pool on return: the stream orders their next use after these launches
@@ -446,11 +370,9 @@ extern "C" const char* zkh_derive_links_paged(zkh_ctx* ctx, const zkh_circuit* c
 extern "C" const char* zkh_page_out(zkh_ctx* ctx, const zkh_circuit* c, size_t po2, size_t zk_cycles, const zkh_buf* data, zkh_buf* image) {
     ZKH_REQUIRE(ctx && c && data && image, "page_out: null argument");
     ZKH_REQUIRE(zkh_circuit_pages(c), "page_out: the circuit's arguments hold no PAGES record (ZKA1 version 7)");
-    ZKH_REQUIRE(po2 >= 1 && po2 <= 24, "page_out: po2 %zu out of range", po2);
-    const size_t n = (size_t)1 << po2;
-    ZKH_REQUIRE(zk_cycles < n, "page_out: zk_cycles %zu leaves no active row at po2 %zu", zk_cycles, po2);
-    const uint32_t A = (uint32_t)(n - zk_cycles);
-    ZKH_REQUIRE(data->len == (size_t)c->group_size[GROUP_DATA] * n, "page_out: buffer shape mismatch");
+    size_t n;
+    uint32_t A;
+    ZKH_TRY(trace_rows("page_out", c, po2, zk_cycles, nullptr, data, nullptr, &n, &A));
     ZKH_REQUIRE(image->len <= 0xffffffffull, "page_out: an image of %zu words (at most 2^32 - 1)", image->len);
     const Pages& g = c->args->pages[0];
     const uint32_t W = (uint32_t)image->len;

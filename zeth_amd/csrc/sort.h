@@ -1,5 +1,6 @@
 // sort.h — the stable sort of selected trace rows by packed keys that sort.hip owns (its kernels live there and nowhere else), for
-// its two callers: zkh_derive_sorted (sort.hip) and zkh_derive_links (links.hip).
+// its two callers: zkh_derive_sorted (sort.hip) and zkh_derive_links (links.hip), and the counter scan inside it, which the page scan of
+// links.hip launches as well.
 #pragma once
 #include <vector>
 
@@ -33,5 +34,9 @@ struct SortedRows {
 };
 // the passes (a) .. (c) of sort.hip over `pairs`, all pairs in the same launches
 const char* sort_rows(zkh_ctx* ctx, const zkh_buf* code, const zkh_buf* data, size_t n, uint32_t A, const std::vector<SortPair>& pairs, SortedRows* out);
+
+// the exclusive scan, in place, of `segments` runs of `len` counters each at v (k_sort_scan: one workgroup per run, none waits for another);
+// with `total`, the sum of run s goes to total[s * total_stride].  A plain launch on the context's stream.
+void scan_counters(zkh_ctx* ctx, uint32_t* v, uint32_t segments, uint32_t len, uint32_t* total, uint32_t total_stride);
 
 }  // namespace zkh

@@ -268,6 +268,10 @@ __global__ __launch_bounds__(SORT_THREADS) void k_sort_gather(const uint32_t* __
 
 }  // namespace
 
+void zkh::scan_counters(zkh_ctx* ctx, uint32_t* v, uint32_t segments, uint32_t len, uint32_t* total, uint32_t total_stride) {
+    k_sort_scan<<<segments, SCAN_THREADS, 0, ctx->stream>>>(v, len, total, total_stride);
+}
+
 // (a) .. (c) for both callers.  The launches, uploads and read-back of a call are a function of (pairs, A) and the live key bits alone.
 const char* zkh::sort_rows(zkh_ctx* ctx, const zkh_buf* code, const zkh_buf* data, size_t n, uint32_t A, const std::vector<SortPair>& pairs, SortedRows* out) {
     const uint32_t np = (uint32_t)pairs.size();
@@ -291,7 +295,7 @@ const char* zkh::sort_rows(zkh_ctx* ctx, const zkh_buf* code, const zkh_buf* dat
         ProfScope prof(ctx, "sort_keys", 4.0 * key_words * A);
         const unsigned bx = (unsigned)((A + SORT_THREADS * KEYS_ROUNDS - 1) / (SORT_THREADS * KEYS_ROUNDS));
         k_sort_keys<<<dim3(bx, np), SORT_THREADS, 0, ctx->stream>>>(code->ptr(), data->ptr(), d_pairs, (uint32_t)n, A, groups, selcnt->ptr(), status->ptr());
-        k_sort_scan<<<np, SCAN_THREADS, 0, ctx->stream>>>(selcnt->ptr(), groups, status->ptr() + ST_HEAD + ST_M, ST_WORDS);
+        scan_counters(ctx, selcnt->ptr(), np, groups, status->ptr() + ST_HEAD + ST_M, ST_WORDS);
         ZKH_TRY(last_launch_error("sort_keys"));
     }
     ZKH_TRY(zkh_read(ctx, status, st.data(), 0, st.size()));
