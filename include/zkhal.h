@@ -356,10 +356,31 @@ const char* zkh_derive_links(zkh_ctx*, const zkh_circuit*, size_t po2, size_t zk
  * comes first and a refusal leaves the image unchanged: the lowest row whose p_on is not 0 / 1, whose address is >= W, or whose address
  * does not follow a smaller one on a row with p_on = 1 (the table is a prefix of strictly increasing addresses, as the circuit demands:
  * a host-made table that repeats an address is refused, not resolved).  It is a call of its own so that a refused or aborted seal never
- * touches the image.  The image is not bound to a commitment: the verifier does not learn which image (ARGUMENTS). */
+ * touches the image.  The prover can commit to the image (below); no circuit checks p_in / p_out against that commitment yet, so the
+ * verifier does not learn which image (ARGUMENTS). */
 int zkh_circuit_pages(const zkh_circuit*);
 const char* zkh_derive_links_paged(zkh_ctx*, const zkh_circuit*, size_t po2, size_t zk_cycles, const zkh_buf* code, zkh_buf* data, const zkh_buf* image);
 const char* zkh_page_out(zkh_ctx*, const zkh_circuit*, size_t po2, size_t zk_cycles, const zkh_buf* data, zkh_buf* image);
+/* THE IMAGE'S COMMITMENT: a Merkle root that the prover keeps current from segment to segment.  An image is W >= 1 raw Montgomery words,
+ * W <= 2^32 - 1, as zkh_page_out takes it.  The commitment is a function of the RESIDUES, not of the raw words: image[a] and
+ * image[a] + P are one memory and give one root.  L = the smallest power of two >= ceil(W / 8).  The tree is 2 L digests in heap order,
+ * 16 L words, digest i at words [8 i, 8 i + 8): the `nodes` layout of zkh_merkle_fold_all(nodes, rows = L) and zkh_merkle_open.
+ *   digest 0 is eight zero words;
+ *   leaf digest L + j, word k, is image[8 j + k] % P for 8 j + k < W and 0 past the end of the image, in the last partial leaf and in
+ *   every padding leaf alike: a leaf is eight memory words verbatim, not a hash;
+ *   node i, 1 <= i < L, is hash_pair(node 2 i, node 2 i + 1): the Poseidon2 of zkh_hash_fold, the one operation P2-JOIN constrains;
+ *   the root is digest 1 (for L = 1 it is the leaf).
+ * zkh_image_tree_words: 16 L, and 0 for W = 0.  zkh_image_commit writes the whole tree of `image` into `nodes`: one pass for digest 0
+ * and the leaf layer, the layers above as zkh_merkle_fold_all builds them.  It FAILS on W = 0, on W > 2^32 - 1 and on a `nodes` that is
+ * not exactly zkh_image_tree_words(W) words.
+ * zkh_page_out_tree is zkh_page_out followed by the update of `nodes`, as one call: the same check pass, the same refusals with the same
+ * messages (image and nodes then unchanged; a wrong-sized `nodes` is refused before anything is written), the same scatter; then, with D
+ * the rows of the table, the dirty leaves are rewritten from the image and only the nodes on the paths of the paged words are hashed
+ * again, so that `nodes` equals, word for word, what zkh_image_commit writes for the new image.  `nodes` must hold the tree of `image`
+ * as it was before the call.  D = 0 leaves `nodes` as it is.  No atomics: `nodes` is a function of the image alone. */
+size_t zkh_image_tree_words(size_t image_words);
+const char* zkh_image_commit(zkh_ctx*, const zkh_buf* image, zkh_buf* nodes);
+const char* zkh_page_out_tree(zkh_ctx*, const zkh_circuit*, size_t po2, size_t zk_cycles, const zkh_buf* data, zkh_buf* image, zkh_buf* nodes);
 /* Everything a circuit's arguments derive, in the one order in which it is sound: sorted copies, then columns, then links, then
  * multiplicities (a LIMBS / ORDER record may read a sorted copy's column, and the multiplicities count the limbs that the records and
  * the links derive).  Call it after the data upload and before zkh_prove_begin: what it writes belongs to the data group.  It runs

@@ -414,6 +414,27 @@ impl HipCircuitHal {
         ffi(|| unsafe { sys::zkh_page_out(self.hal.ctx.0, self.circuit, po2, sys::ZK_CYCLES, data.raw, image.raw) });
     }
 
+    /// The words of the committed tree of an image of `image_words` words (`zkh_image_tree_words`): 16 L, L the smallest power of two
+    /// >= ceil(W / 8); 0 for an empty image.
+    pub fn image_tree_words(image_words: usize) -> usize {
+        unsafe { sys::zkh_image_tree_words(image_words) }
+    }
+
+    /// Commit to a memory image (`zkh_image_commit`): `nodes` (exactly `image_tree_words` words) becomes 2 L digests in heap order, the
+    /// leaves the image's residues mod P eight at a time and zero-padded, every node above `hash_pair` of its two children, the root
+    /// digest 1.  Panics on an empty image or a `nodes` of another size.
+    pub fn image_commit(&self, image: &HipBuffer<BabyBearElem>, nodes: &HipBuffer<BabyBearElem>) {
+        ffi(|| unsafe { sys::zkh_image_commit(self.hal.ctx.0, image.raw, nodes.raw) });
+    }
+
+    /// `page_out`, and `nodes` (the committed tree of `image` before the call) brought up to the new image by hashing only the paths of
+    /// the paged words again (`zkh_page_out_tree`): afterwards `nodes` is word for word what `image_commit` writes for the new image.
+    /// Panics as `page_out` does, and on a `nodes` of the wrong size; image and nodes are then unchanged.
+    pub fn page_out_tree(&self, data: &HipBuffer<BabyBearElem>, image: &HipBuffer<BabyBearElem>, nodes: &HipBuffer<BabyBearElem>, steps: usize) {
+        let po2 = steps.trailing_zeros() as usize;
+        ffi(|| unsafe { sys::zkh_page_out_tree(self.hal.ctx.0, self.circuit, po2, sys::ZK_CYCLES, data.raw, image.raw, nodes.raw) });
+    }
+
     /// Check the raw traces against the circuit's own constraints on every row of `rows` (`zkh_check_rows`): which constraint a
     /// witness breaks, and where, before a seal is spent on it.  `out` and `mix` are the global words.  `row < 0`: no row of the window
     /// fails; otherwise the lowest failing row, its lowest failing `and_eqz` step (an index into the ZKC1 step list), how many rows of

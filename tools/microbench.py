@@ -9,7 +9,9 @@ SYN-A / SYN-HEAVY witness, next to zkh_eval_check on the step interpreter for th
 zkh_check_bus, the key-by-key bus check of the honest SYN-LOOKUP FULL witness, with and without its per-term pass, next to zkh_accumulate
 and zkh_derive_multiplicities on the same trace in the same run, alternating; M17: paging, zkh_derive_links_paged on SYN-LOOKUP-paged
 under its version-7 blob next to zkh_derive_links under the version-6 blob on the same trace, and zkh_page_out next to a copy of the
-same bytes, alternating) on one
+same bytes, alternating; M18: the committed image, zkh_page_out_tree (the page-out with the incremental update of the image's Merkle
+tree) next to zkh_page_out followed by zkh_image_commit (the full rebuild), for the derive's own page table, a hand-made table of as many
+pages spread over the whole image and a sparse one of 4096 pages, at two image sizes, alternating) on one
 MI355X, through the C ABI (HipHal).
 
 Each line of output is one JSON object: the op, its shape, the average wall time of one call (stream drained on both
@@ -636,6 +638,81 @@ def main() -> None:
                           "paged_vs_v6": round(med["derive_links_paged"] / med["derive_links_v6"], 3),
                           "page_out_vs_copy": round(med["page_out"] / med["copy_same_bytes"], 3)}), flush=True)
         del code, data, data6, image, src, dst
+    if want("M18"):
+        # the committed image: zkh_page_out_tree (page-out + the incremental update of the tree: only the paths of the paged words are
+        # hashed again) next to its yardstick in the same run, zkh_page_out followed by zkh_image_commit (the rebuild with the fold
+        # kernels the library already had), each into its own image and nodes.  SYN-LOOKUP-paged FULL at M17's image size (2^20 words)
+        # and at 2^26 words.  Tables: `derive`, the page table that zkh_derive_links_paged leaves (its addresses lie below 2^20 at
+        # either image size); `spread`, a hand-made table of as many pages at random addresses over the whole image (zkh_page_out
+        # reads p_on, p_addr and p_out alone); `sparse`, a hand-made one of 4096 pages.  Timed in alternation, `runs` windows of `reps`
+        # calls; median and spread (min, max) of the windows; then the stages by their events.  After the first call a page-out
+        # rewrites what is there and the update hashes the same paths again: every call does the same work.
+        from zeth_amd.circuits import logup, syn_lookup
+        runs, zk = 7, 1994
+        A = n - zk
+        shape = syn_lookup.FULL
+        desc, blob = syn_lookup.build_syn_lookup(shape, link=True, reads=True, pages=True)
+        pargs = logup.Arguments.parse(blob)
+        pg = pargs.pages
+        code_h, full_h, _out = syn_lookup.witness(shape, args.po2, zk, seed=17, link=True, reads=True, pages=True, image=np.zeros(1 << 20, dtype=np.uint32))
+        paged = hal.load_circuit(desc, jit=False)
+        paged.set_arguments(blob)
+        full = full_h.reshape(-1, n)
+        pages = int((full[pg.p_on, :A] != 0).sum())
+        one = np.uint32((1 << 32) % P)
+        enc = lambda x: (np.asarray(x, dtype=np.uint64) * np.uint64(one) % np.uint64(P)).astype(np.uint32)   # noqa: E731
+        spread = lambda ts: {"median_ms": round(float(np.median(ts)) * 1e3, 4), "min_ms": round(min(ts) * 1e3, 4), "max_ms": round(max(ts) * 1e3, 4)}   # noqa: E731
+        data = hal.alloc_elem("m18d", full_h.size)
+        for W in (1 << 20, 1 << 26):
+            for table in ("derive", "spread", "sparse"):
+                if table == "derive":
+                    D = pages
+                    data.write(full_h)
+                else:
+                    D = pages if table == "spread" else 4096
+                    hand = np.zeros_like(full)
+                    hand[pg.p_on, :D], hand[pg.p_out, :D] = one, rand_fp(rng, D)
+                    if W <= 1 << 22:
+                        addrs = rng.choice(W, D, replace=False)
+                    else:                                                    # (no permutation of 2^26 words: distinct draws, D of them at random)
+                        addrs = np.unique(rng.integers(0, W, D + D // 8))
+                        addrs = addrs[rng.choice(addrs.size, D, replace=False)]
+                    hand[pg.p_addr, :D] = enc(np.sort(addrs))
+                    data.write(hand.reshape(-1))
+                    del hand
+                image_h = rand_fp(rng, W)
+                images = [hal.alloc_elem("m18i", W) for _ in range(2)]
+                for im in images:
+                    im.write(image_h)
+                nodes = [hal.image_commit(im) for im in images]
+                tree_fn = lambda: hal.page_out_tree(paged, args.po2, zk, data, images[0], nodes[0])            # noqa: E731
+                yard_fn = lambda: (hal.page_out(paged, args.po2, zk, data, images[1]), hal.image_commit(images[1], nodes[1]))   # noqa: E731
+                tree_fn()
+                yard_fn()
+                assert np.array_equal(images[0].to_vec(), images[1].to_vec()) and not np.array_equal(images[0].to_vec(), image_h)
+                assert np.array_equal(nodes[0].to_vec(), nodes[1].to_vec())
+                t = {"page_out_tree": [], "page_out_then_commit": []}
+                for _ in range(runs):
+                    for name, fn in (("page_out_tree", tree_fn), ("page_out_then_commit", yard_fn)):
+                        t[name].append(timed(hal, fn, args.reps))
+                steps = {}
+                for name, fn in (("page_out_tree", tree_fn), ("page_out_then_commit", yard_fn)):
+                    hal.prof_enable(True)
+                    hal.prof_reset()
+                    for _ in range(args.reps):
+                        fn()
+                    hal.sync()
+                    steps[name] = {r["name"]: {"calls_per_call": r["calls"] // args.reps, "ms_per_call": round(r["total_ms"] / args.reps, 4)} for r in hal.prof_get()
+                                   if r["calls"] and r["name"].startswith(("page_out_", "image_", "hash_fold"))}
+                    hal.prof_enable(False)
+                assert np.array_equal(nodes[0].to_vec(), nodes[1].to_vec())
+                med = {k: float(np.median(v)) for k, v in t.items()}
+                print(json.dumps({"bench": "M18", "circuit": "SYN-LOOKUP-paged FULL", "library": os.path.basename(os.environ.get("ZKH_LIBRARY", "") or "libzkhal_mi355x.so"),
+                                  "po2": args.po2, "table": table, "pages": D, "image_words": W, "leaves": logup.image_tree_leaves(W), "runs": runs,
+                                  "reps": args.reps, **{k: spread(v) for k, v in t.items()}, "steps": steps,
+                                  "tree_vs_rebuild": round(med["page_out_tree"] / med["page_out_then_commit"], 3)}), flush=True)
+                del images, nodes
+        del data
     hal.close()
 
 

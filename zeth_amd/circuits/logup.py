@@ -105,7 +105,14 @@ index when a_i >= 2^(L ng)), gap_j = limb j of a_i - a_{i-1} - 1 (zeros on row 0
 PAGE-OUT (`reference_page_out`, zkh_page_out): image[x(p_addr, i)] = p_out[i] on every active row with p_on = 1; refused, with the image
 unchanged, on the lowest row whose p_on is not 0 / 1, whose address is >= W or does not follow a smaller one on a row with p_on = 1 (a
 table that repeats an address is REFUSED, not resolved: the rows with p_on = 1 are a prefix of strictly increasing addresses).
-Left out: the image is not bound to a commitment, sessions do not thread one, and a blob pages one memory of one value word per address.
+THE IMAGE'S COMMITMENT (`reference_image_tree`, `reference_image_root`; zkh_image_commit, zkh_page_out_tree): a Merkle tree over the
+image's RESIDUES (image[a] and image[a] + P are one memory and give one root).  L = the smallest power of two >= ceil(W / 8); 2 L digests
+in heap order, digest 0 eight zeros; leaf L + j, word k = image[8 j + k] % P for 8 j + k < W, else 0: eight memory words verbatim, not a
+hash; node i (1 <= i < L) = hash_pair(node 2 i, node 2 i + 1), the operation P2-JOIN constrains; the root is digest 1.
+zkh_page_out_tree is the page-out followed by the update of the nodes on the paged words' paths: afterwards the nodes are those of a
+fresh commit of the new image.
+Left out: no circuit checks p_in / p_out against those roots and they are not in `out` (the verifier does not learn which image), sessions
+do not thread an image, and a blob pages one memory of one value word per address.
 
 WHO WRITES A DATA COLUMN (`_check_owned` behind `check_columns` and `check_links`; csrc/arguments.h says the same).  A data column
 has at most one writer, and a derive reads only what the stages before it have finished writing.  The writers: a sorted copy (its
@@ -1361,6 +1368,50 @@ def reference_page_out(args: Arguments, po2: int, zk_cycles: int, data, image) -
         raise ReferenceError(f"{at}: page address {int(addr[r])} does not follow a smaller one (row {r - 1}: p_on {int(pon[r])}, address {int(paddr[r])})")
     out[addr[live]] = d[pages.p_out, :A][live]
     return out
+
+
+def image_tree_leaves(image_words: int) -> int:
+    """L of an image of W >= 1 words: the smallest power of two >= ceil(W / 8)"""
+    L = 1
+    while 8 * L < image_words:
+        L <<= 1
+    return L
+
+
+def _hash_pairs(left, right) -> np.ndarray:
+    """hash_pair of k pairs of digests, (k, 8) each, as ONE batch through the library's host permutation (zkh_poseidon2_mix_host)"""
+    import ctypes as C
+    from .. import hal as _hal
+    _hal.load_library()
+    st = np.zeros((len(left), 24), dtype=np.uint32)
+    st[:, :8], st[:, 8:16] = left, right
+    _hal._check(_hal._lib.zkh_poseidon2_mix_host(None, None, st.ctypes.data_as(C.POINTER(C.c_uint32)), len(left)))
+    return st[:, :8].copy()
+
+
+def reference_image_tree(image) -> np.ndarray:
+    """THE IMAGE'S COMMITMENT (zkh_image_commit, zkh_page_out_tree; include/zkhal.h): the (2 L, 8) array of digests in heap order over an
+    image of W >= 1 raw Montgomery words, W <= 2^32 - 1.  A function of the residues: image[a] and image[a] + P are one memory and give
+    one tree.  L = the smallest power of two >= ceil(W / 8); digest 0 is eight zeros; leaf L + j, word k, is image[8 j + k] % P for
+    8 j + k < W and 0 past the end of the image (the last partial leaf and every padding leaf): eight memory words verbatim, not a hash;
+    node i, 1 <= i < L, is hash_pair(node 2 i, node 2 i + 1), the operation P2-JOIN constrains; the root is digest 1 (L = 1: the leaf)."""
+    words = np.asarray(image, dtype=np.uint32).reshape(-1)
+    W = words.size
+    if not 1 <= W <= 0xffffffff:
+        raise ReferenceError(f"an image of {W} words (1 .. 2^32 - 1)")
+    L = image_tree_leaves(W)
+    nodes = np.zeros((2 * L, 8), dtype=np.uint32)
+    nodes[L:].reshape(-1)[:W] = words % np.uint32(P)
+    width = L // 2
+    while width:
+        nodes[width:2 * width] = _hash_pairs(nodes[2 * width:4 * width:2], nodes[2 * width + 1:4 * width:2])
+        width //= 2
+    return nodes
+
+
+def reference_image_root(image) -> np.ndarray:
+    """the root of `reference_image_tree`: digest 1, 8 words"""
+    return reference_image_tree(image)[1].copy()
 
 
 def bus_slots(A: int, distinct_keys: int) -> int:

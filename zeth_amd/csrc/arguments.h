@@ -1,7 +1,7 @@
 // arguments.h — lookup and permutation arguments as data (ZKA1 blob; zeth_amd/circuits/logup.py; DESIGN.md §2 ARGUMENTS): the decoded
 // form every consumer reads, and what the consumers share.  arguments.hip owns the blob format and the rules a blob must keep;
 // accumulate.hip (zkh_accumulate), multiplicities.hip (zkh_derive_multiplicities), sort.hip (zkh_derive_sorted), columns.hip
-// (zkh_derive_columns) and links.hip (zkh_derive_links, zkh_derive_links_paged, zkh_page_out) read zkh_circuit::args and never see a blob word.
+// (zkh_derive_columns) and links.hip (zkh_derive_links, zkh_derive_links_paged, zkh_page_out, zkh_page_out_tree) read zkh_circuit::args and never see a blob word.
 //
 // WHO WRITES A DATA COLUMN (the module docstring of logup.py says the same; check_owned in arguments.hip keeps it).  A data column has at
 // most one writer, and a derive reads only what the stages before it have finished writing.  The writers: a sorted copy (its tuple
@@ -121,21 +121,23 @@ const char* read_cell(zkh_ctx* ctx, const zkh_buf* code, const zkh_buf* data, ui
     return nullptr;
 }
 
-// The lowest (hi, lo) that a check pass refused, hi << 32 | lo on the device: two words, all ones = none.
+// The lowest (hi, lo) that a check pass refused, hi << 32 | lo on the device: two words, all ones = none.  A third word, `extra`, comes
+// back with them for a check pass that has one more thing to tell (zkh_page_out: the last row of its table); it starts as all ones too.
 struct BadRow {
     Tmp buf;
     bool found = false;
-    uint32_t hi = 0, lo = 0;
+    uint32_t hi = 0, lo = 0, extra = NONE;
     const char* init(zkh_ctx* ctx) {
-        ZKH_TRY(new_buf(ctx, 2, false, buf.out()));
-        ZKH_HIP(hipMemsetAsync(buf->ptr(), 0xff, 8, ctx->stream));
+        ZKH_TRY(new_buf(ctx, 4, false, buf.out()));             // three words in use
+        ZKH_HIP(hipMemsetAsync(buf->ptr(), 0xff, 12, ctx->stream));
         return nullptr;
     }
     unsigned long long* ptr() const { return (unsigned long long*)buf->ptr(); }
-    const char* read(zkh_ctx* ctx) {                    // after the check pass: found, and then (hi, lo)
-        uint32_t st[2];
-        ZKH_TRY(zkh_read(ctx, buf, st, 0, 2));
-        lo = st[0]; hi = st[1];
+    uint32_t* extra_ptr() const { return buf->ptr() + 2; }
+    const char* read(zkh_ctx* ctx) {                    // after the check pass: found, and then (hi, lo); extra
+        uint32_t st[3];
+        ZKH_TRY(zkh_read(ctx, buf, st, 0, 3));
+        lo = st[0]; hi = st[1]; extra = st[2];
         found = (lo & hi) != NONE;
         return nullptr;
     }

@@ -13,6 +13,7 @@
 // the headroom a 31-bit prime denies a 32-bit word), partial rounds three at a time with unreduced weighted sums:
 // 6.4 k VALU instructions per 64 permutations.
 #include "common.h"
+#include "image_tree.h"
 #include "poseidon2.h"
 #include "poseidon2_wide.h"
 
@@ -62,11 +63,9 @@ __global__ __launch_bounds__(256, 4) void k_hash_rows(uint32_t* __restrict__ out
     o[1] = make_uint4(s[4], s[5], s[6], s[7]);
 }
 
-// Hal::hash_fold — one lane per parent: io[out+i] = H(io[in+2i] || io[in+2i+1])
-__global__ __launch_bounds__(256, 4) void k_hash_fold(uint32_t* __restrict__ io, size_t input_size, size_t output_size,
-                                                   const uint32_t* __restrict__ rc, const uint32_t* __restrict__ diag) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= output_size) return;
+// one lane folds one parent of the layer of `output_size` parents: io[out+i] = H(io[in+2i] || io[in+2i+1])
+__device__ __forceinline__ void fold_one(uint32_t* __restrict__ io, size_t input_size, size_t output_size, size_t i,
+                                         const uint32_t* __restrict__ rc, const uint32_t* __restrict__ diag) {
     const uint4* src = (const uint4*)(io + (input_size + 2 * i) * 8);
     uint32_t s[CELLS];
     const uint4 a = src[0], b = src[1], c = src[2], d = src[3];
@@ -80,6 +79,23 @@ __global__ __launch_bounds__(256, 4) void k_hash_fold(uint32_t* __restrict__ io,
     uint4* o = (uint4*)(io + (output_size + i) * 8);
     o[0] = make_uint4(s[0], s[1], s[2], s[3]);
     o[1] = make_uint4(s[4], s[5], s[6], s[7]);
+}
+// Hal::hash_fold — one lane per parent
+__global__ __launch_bounds__(256, 4) void k_hash_fold(uint32_t* __restrict__ io, size_t input_size, size_t output_size,
+                                                   const uint32_t* __restrict__ rc, const uint32_t* __restrict__ diag) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= output_size) return;
+    fold_one(io, input_size, output_size, i, rc, diag);
+}
+// The image tree's update (image.hip): the same fold over a LIST of parents of the layer of `width` parents, lane t the parent list[t],
+// t < *count (the count is the device's: the compaction that made the list left it).  The lanes are dense: a wave runs a permutation
+// only for parents that are dirty, but for the last wave of the list.  Every parent is in the list once: no node is written twice.
+__global__ __launch_bounds__(256, 4) void k_hash_fold_list(uint32_t* __restrict__ io, size_t width, const uint32_t* __restrict__ list,
+                                                        const uint32_t* __restrict__ count, const uint32_t* __restrict__ rc,
+                                                        const uint32_t* __restrict__ diag) {
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= *count) return;
+    fold_one(io, 2 * width, width, list[t], rc, diag);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -106,7 +122,7 @@ __device__ __forceinline__ void wide_fold_one(uint32_t* __restrict__ io, size_t 
     wide_permute(c, j, rcs, pc);
     if (live && j < 2) *(uint4*)(io + (output_size + parent) * 8 + 4 * j) = make_uint4(c[0], c[1], c[2], c[3]);
 }
-constexpr int WIDE_LOG = 15;      // layers with <= 2^15 parents use the 8-lane permutation
+// (WIDE_LOG, image_tree.h: layers with <= 2^15 parents use the 8-lane permutation)
 constexpr int TAIL_LOG = 7;       // a 1024-lane workgroup = 2^7 eight-lane groups; the last 8 layers (<= 2^7 parents) are one launch
 // Middle of the tree: workgroup b owns the 128 consecutive parents [128 b, 128 b + 128) of the layer with `first_parents`
 // parents and the `levels` - 1 layers above them (64, 32, ... parents of its own subtree), so the layers with
@@ -187,7 +203,6 @@ extern "C" const char* zkh_hash_fold(zkh_ctx* c, zkh_buf* io, size_t input_size,
                                                                              c->tab.diag);
     return last_launch_error("hash_fold");
 }
-static const char* merkle_fold_from(zkh_ctx* c, zkh_buf* nodes, size_t first_layer);
 extern "C" const char* zkh_merkle_fold_all(zkh_ctx* c, zkh_buf* nodes, size_t rows) {
     ZKH_REQUIRE(nodes->len == rows * 16 && rows && (rows & (rows - 1)) == 0, "merkle_fold_all: nodes must hold 2*rows digests");
     return merkle_fold_from(c, nodes, rows);
@@ -204,7 +219,7 @@ extern "C" const char* zkh_merkle_build(zkh_ctx* c, zkh_buf* nodes, const zkh_bu
     ZKH_TRY(err);
     return merkle_fold_from(c, nodes, rows);
 }
-static const char* merkle_fold_from(zkh_ctx* c, zkh_buf* nodes, size_t first_layer) {
+const char* zkh::merkle_fold_from(zkh_ctx* c, zkh_buf* nodes, size_t first_layer) {
     for (size_t layer = first_layer; layer >= 2; layer /= 2) {       // layer = current input width, layer/2 parents
         const size_t parents = layer / 2;
         if (parents > ((size_t)1 << WIDE_LOG)) {
@@ -225,4 +240,10 @@ static const char* merkle_fold_from(zkh_ctx* c, zkh_buf* nodes, size_t first_lay
         }
     }
     return nullptr;
+}
+const char* zkh::hash_fold_listed(zkh_ctx* c, zkh_buf* nodes, size_t width, const uint32_t* list, const uint32_t* count, uint32_t bound) {
+    ZKH_REQUIRE(bound && bound <= width && 32 * width <= nodes->len, "hash_fold_listed: %u parents of %zu in %zu words", bound, width, nodes->len);
+    ProfScope prof(c, "image_sparse", 100.0 * bound);
+    k_hash_fold_list<<<(bound + 255) / 256, 256, 0, c->stream>>>(nodes->ptr(), width, list, count, c->tab.rc, c->tab.diag);
+    return last_launch_error("image_sparse");
 }

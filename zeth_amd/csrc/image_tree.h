@@ -1,0 +1,29 @@
+// image_tree.h — the committed memory image (include/zkhal.h "THE IMAGE'S COMMITMENT"; DESIGN.md §2 ARGUMENTS): what image.hip,
+// hash.hip and links.hip share.  image.hip owns the leaf layer and the lists of dirty nodes, hash.hip every permutation (its build
+// flags), links.hip the page-out that drives the update.
+#pragma once
+#include "common.h"
+
+namespace zkh {
+
+constexpr int WIDE_LOG = 15;      // tree layers with <= 2^15 parents use hash.hip's 8-lane permutation; the image update lists no such layer
+
+// L of an image of W >= 1 words: the smallest power of two >= ceil(W / 8); the tree is 2 L digests, 16 L words
+inline size_t image_leaves(size_t W) {
+    size_t L = 1;
+    while (L * 8 < W) L <<= 1;
+    return L;
+}
+
+// hash.hip: every layer above the one of `first_layer` digests (a power of two; 1: nothing), the widest with one lane per parent, the
+// narrow ones with the 8-lane kernels
+const char* merkle_fold_from(zkh_ctx* c, zkh_buf* nodes, size_t first_layer);
+// hash.hip: the parents list[0 .. *count) of the layer of `width` parents, one lane per listed parent, nothing else of the layer touched.
+// `bound` >= *count sizes the grid (the count lives on the device); every list[t] < width.  Profiler scope image_sparse.
+const char* hash_fold_listed(zkh_ctx* c, zkh_buf* nodes, size_t width, const uint32_t* list, const uint32_t* count, uint32_t bound);
+
+// image.hip: after a page-out has scattered into `image`: `addrs` is the page table's address column (raw words), its rows [0, D) strictly
+// increasing addresses below image->len; `nodes` becomes what zkh_image_commit writes for the new image.  D = 0: nothing is launched.
+const char* image_tree_update(zkh_ctx* c, const uint32_t* addrs, uint32_t D, const zkh_buf* image, zkh_buf* nodes);
+
+}  // namespace zkh

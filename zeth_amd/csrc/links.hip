@@ -36,7 +36,7 @@
 // rule.  THE PAGE TABLE: a_0 < .. < a_{D-1} the distinct addresses of the record's accesses; on the active rows i < D p_on = Montgomery(1),
 // p_addr = the raw key word of a_i's first access, p_in = the raw word image[a_i], p_out / p_time = the raw value / clock word of a_i's last
 // access, alimb_j = limb j of a_i (refused, under the PAGES record's index, when a_i >= 2^(L ng)), gap_j = limb j of a_i - a_{i-1} - 1 (zeros
-// on row 0); active rows [D, A) get zeros in all destinations, rows [A, n) are never touched.  PAGE-OUT (zkh_page_out,
+// on row 0); active rows [D, A) get zeros in all destinations, rows [A, n) are never touched.  PAGE-OUT (zkh_page_out, zkh_page_out_tree,
 // `reference_page_out`): image[x(p_addr, i)] = p_out[i] on every active row with p_on = 1, after a check pass that refuses, with the image
 // unchanged, the lowest row whose p_on is not 0 / 1, whose address is >= W or does not follow a smaller one on a row with p_on = 1: a table
 // that repeats an address is REFUSED, so the scatter never writes one word twice.
@@ -50,6 +50,7 @@
 // the new refusals to the same wave minimum and the same atomicMin; the paged write pass also fills the table — head lanes p_on, p_addr,
 // p_in, alimb and gap (the previous address re-read from the trace at rows[t - 1]: packed keys drop bits and are no addresses), tail lanes
 // p_out and p_time, lanes D <= t < A zeros (coalesced).  No atomic but that min: the result is a function of the traces and the image.
+#include "image_tree.h"
 #include "scan.h"
 #include "sort.h"
 
@@ -197,10 +198,12 @@ __global__ __launch_bounds__(LINK_THREADS) void k_links(const uint32_t* __restri
 }
 
 // zkh_page_out's two passes over the active rows of the page table: kWrite = false reduces the lowest refused row into `bad` (under 0),
+// and the row with p_on = 1 that has none after it leaves its index in `last` (in a table that passes the rows with p_on = 1 are a prefix
+// [0, D): that is row D - 1, one lane, a plain store; no such row: `last` keeps its all ones, D = 0);
 // kWrite = true scatters p_out into the image (addresses checked distinct and inside: no word is written twice)
 template <bool kWrite>
 __global__ __launch_bounds__(LINK_THREADS) void k_page_out(const uint32_t* __restrict__ data, const Pages* __restrict__ pg, uint32_t n, uint32_t A, uint32_t* image,
-                                                           uint32_t W, unsigned long long* __restrict__ bad) {
+                                                           uint32_t W, unsigned long long* __restrict__ bad, uint32_t* __restrict__ last) {
     const uint32_t t = blockIdx.x * LINK_THREADS + threadIdx.x;
     const uint32_t* on = data + (size_t)pg->dst[PG_ON] * n;
     const uint32_t* addrs = data + (size_t)pg->dst[PG_ADDR] * n;
@@ -211,6 +214,7 @@ __global__ __launch_bounds__(LINK_THREADS) void k_page_out(const uint32_t* __res
             bool ok = v == 0 || v == R1;
             if (v == R1) ok = a < W && (t == 0 || (on[t - 1] % P == R1 && canonical(addrs[t - 1]) < a));
             if (!ok) mine = t;
+            if (v == R1 && (t + 1 == A || on[t + 1] % P != R1)) *last = t;
         } else if (v == R1 && a < W) {
             image[a] = data[(size_t)pg->dst[PG_OUT] * n + t];
         }
@@ -367,13 +371,18 @@ extern "C" const char* zkh_derive_links_paged(zkh_ctx* ctx, const zkh_circuit* c
     return derive_links(ctx, c, po2, zk_cycles, code, data, image);
 }
 
-extern "C" const char* zkh_page_out(zkh_ctx* ctx, const zkh_circuit* c, size_t po2, size_t zk_cycles, const zkh_buf* data, zkh_buf* image) {
-    ZKH_REQUIRE(ctx && c && data && image, "page_out: null argument");
+namespace {
+// zkh_page_out (nodes = NULL) and zkh_page_out_tree: the check pass, one read-back (the refused row; D), the scatter, and with `nodes`
+// the update of the image's tree (image.hip) over the table's D addresses
+const char* page_out(zkh_ctx* ctx, const zkh_circuit* c, size_t po2, size_t zk_cycles, const zkh_buf* data, zkh_buf* image, zkh_buf* nodes) {
     ZKH_REQUIRE(zkh_circuit_pages(c), "page_out: the circuit's arguments hold no PAGES record (ZKA1 version 7)");
     size_t n;
     uint32_t A;
     ZKH_TRY(trace_rows("page_out", c, po2, zk_cycles, nullptr, data, nullptr, &n, &A));
     ZKH_REQUIRE(image->len <= 0xffffffffull, "page_out: an image of %zu words (at most 2^32 - 1)", image->len);
+    ZKH_REQUIRE(!nodes || (image->len && nodes->len == zkh_image_tree_words(image->len)),
+                "page_out: nodes of %zu words; an image of %zu words has a tree of %zu (zkh_image_tree_words): the image is unchanged", nodes ? nodes->len : 0,
+                image->len, zkh_image_tree_words(image->len));
     const Pages& g = c->args->pages[0];
     const uint32_t W = (uint32_t)image->len;
     bind_thread(ctx);
@@ -384,7 +393,7 @@ extern "C" const char* zkh_page_out(zkh_ctx* ctx, const zkh_circuit* c, size_t p
     const uint32_t nb = (A + LINK_THREADS - 1) / LINK_THREADS;
     {
         ProfScope prof(ctx, "page_out_check", 8.0 * A);
-        k_page_out<false><<<nb, LINK_THREADS, 0, ctx->stream>>>(data->ptr(), (const Pages*)dpages->ptr(), (uint32_t)n, A, image->ptr(), W, bad.ptr());
+        k_page_out<false><<<nb, LINK_THREADS, 0, ctx->stream>>>(data->ptr(), (const Pages*)dpages->ptr(), (uint32_t)n, A, image->ptr(), W, bad.ptr(), bad.extra_ptr());
         ZKH_TRY(last_launch_error("page_out_check"));
     }
     ZKH_TRY(bad.read(ctx));
@@ -404,8 +413,22 @@ extern "C" const char* zkh_page_out(zkh_ctx* ctx, const zkh_circuit* c, size_t p
     }
     {
         ProfScope prof(ctx, "page_out_write", 16.0 * A);
-        k_page_out<true><<<nb, LINK_THREADS, 0, ctx->stream>>>(data->ptr(), (const Pages*)dpages->ptr(), (uint32_t)n, A, image->ptr(), W, bad.ptr());
+        k_page_out<true><<<nb, LINK_THREADS, 0, ctx->stream>>>(data->ptr(), (const Pages*)dpages->ptr(), (uint32_t)n, A, image->ptr(), W, bad.ptr(), bad.extra_ptr());
         ZKH_TRY(last_launch_error("page_out_write"));
     }
-    return nullptr;
+    if (!nodes) return nullptr;
+    const uint32_t D = bad.extra + 1;                   // the table passed: its rows are [0, D), and row D - 1 left its index (none: all ones, D = 0)
+    ZKH_REQUIRE(D <= A, "page_out: the check pass left %u pages on %u active rows", D, A);
+    return image_tree_update(ctx, data->ptr() + (size_t)g.dst[PG_ADDR] * n, D, image, nodes);
+}
+}  // namespace
+
+extern "C" const char* zkh_page_out(zkh_ctx* ctx, const zkh_circuit* c, size_t po2, size_t zk_cycles, const zkh_buf* data, zkh_buf* image) {
+    ZKH_REQUIRE(ctx && c && data && image, "page_out: null argument");
+    return page_out(ctx, c, po2, zk_cycles, data, image, nullptr);
+}
+
+extern "C" const char* zkh_page_out_tree(zkh_ctx* ctx, const zkh_circuit* c, size_t po2, size_t zk_cycles, const zkh_buf* data, zkh_buf* image, zkh_buf* nodes) {
+    ZKH_REQUIRE(ctx && c && data && image && nodes, "page_out: null argument");
+    return page_out(ctx, c, po2, zk_cycles, data, image, nodes);
 }

@@ -184,6 +184,9 @@ ABI = {
     "zkh_derive_links_paged": (_err, [_vp, _vp, _sz, _sz, _vp, _vp, _vp]),
     "zkh_derive_all_paged": (_err, [_vp, _vp, _sz, _sz, _vp, _vp, _vp]),
     "zkh_page_out": (_err, [_vp, _vp, _sz, _sz, _vp, _vp]),
+    "zkh_image_tree_words": (_sz, [_sz]),
+    "zkh_image_commit": (_err, [_vp, _vp, _vp]),
+    "zkh_page_out_tree": (_err, [_vp, _vp, _sz, _sz, _vp, _vp, _vp]),
     "zkh_circuit_derived_data_columns": (_err, [_vp, _u32p, _sz, C.POINTER(_sz)]),
     "zkh_upload_data_trace": (_err, [_vp, _vp, _sz, _sz, _vp, _u32p, _i]),
     "zkh_ctx_h2d_bytes": (_sz, [_vp]),
@@ -853,6 +856,33 @@ class HipHal:
         Raises HalError, with the image unchanged, on a p_on other than 0 / 1, an address outside the image, or page addresses that
         do not strictly increase over a prefix of rows"""
         _check(_lib.zkh_page_out(self.ctx, circuit.h, po2, zk_cycles, data.h, image.h))
+
+    def image_tree_words(self, image_words: int) -> int:
+        """the words of the committed tree of an image of `image_words` words: 16 L, L the smallest power of two >= ceil(W / 8); 0 for 0
+        (zkh_image_tree_words; the commitment: `logup.reference_image_tree`)"""
+        return int(_lib.zkh_image_tree_words(image_words))
+
+    def image_commit(self, image: Buffer, nodes: Optional[Buffer] = None) -> Buffer:
+        """the committed tree of `image` (a Buffer of W raw Montgomery words), built on the device (zkh_image_commit): 2 L digests in heap
+        order, the leaves the image's residues eight at a time, zero-padded, every node above hash_pair of its two children; the root is
+        digest 1 (`image_root`).  nodes: a Buffer of image_tree_words(W) words to build it in (default: a new one).  Raises HalError on
+        an empty image and on a `nodes` of another size"""
+        if nodes is None:
+            nodes = self.alloc("image_nodes", self.image_tree_words(image.size()) or 16)
+        _check(_lib.zkh_image_commit(self.ctx, image.h, nodes.h))
+        return nodes
+
+    def page_out_tree(self, circuit: Circuit, po2: int, zk_cycles: int, data: Buffer, image: Buffer, nodes: Buffer) -> None:
+        """page_out, and `nodes` (the committed tree of `image` before the call) brought up to the new image by hashing only the paths
+        of the paged words again (zkh_page_out_tree): afterwards `nodes` is, word for word, what image_commit gives for the new image.
+        Raises HalError as page_out does, and on a `nodes` that is not image_tree_words(W) words; image and nodes are then unchanged"""
+        _check(_lib.zkh_page_out_tree(self.ctx, circuit.h, po2, zk_cycles, data.h, image.h, nodes.h))
+
+    def image_root(self, nodes: Buffer) -> np.ndarray:
+        """the root of a committed tree: digest 1 of `nodes`, 8 words"""
+        out = np.empty(DIGEST_WORDS, dtype=np.uint32)
+        _check(_lib.zkh_read(self.ctx, nodes.h, _ptr(out), DIGEST_WORDS, DIGEST_WORDS))
+        return out
 
     def derive_multiplicities(self, circuit: Circuit, po2: int, zk_cycles: int, code: Buffer, data: Buffer) -> None:
         """fill the derived multiplicity columns of `data` on the active rows (zkh_derive_multiplicities): raises HalError on a table

@@ -294,7 +294,7 @@ class SegmentProver:
         return acc
 
     def seal_host_witness(self, seg: Segment, host_code: np.ndarray, host_data: np.ndarray, out_global, check: bool = False,
-                          image=None, page_out: bool = False) -> SegmentReceipt:
+                          image=None, page_out: bool = False, tree=None) -> SegmentReceipt:
         """Seal a segment whose code/data traces live in pinned HOST memory (hal.host_alloc views): enqueue both uploads
         on the context's stream (no host sync), then run the two-halves seal.  This is the PCIe-inclusive path.  A circuit whose
         arguments derive sorted copies, columns, linked accesses or lookup multiplicities gets them filled into the data trace first
@@ -304,7 +304,8 @@ class SegmentProver:
         zkh_accumulate refuses a bus that does not balance, name the key (check_bus, args_accumulate).
         image: the memory image (a device Buffer of raw Montgomery words) that a circuit whose arguments page memory starts from
         (zkh_derive_all_paged).  The derive only reads it.  page_out: after the seal has succeeded, write the segment's memory back
-        into `image` (`page_out`), so that the next segment starts from it; a refused or failed seal leaves the image as it was."""
+        into `image` (`page_out`), so that the next segment starts from it; a refused or failed seal leaves the image as it was.
+        tree: the committed tree of `image` (hal.image_commit); the page-out then keeps it current (zkh_page_out_tree)."""
         code = self.hal.alloc_elem("code", host_code.size)
         data = self.hal.alloc_elem("data", host_data.size)
         self.hal.write_async(code, host_code)
@@ -314,13 +315,18 @@ class SegmentProver:
         acc = self.args_accumulate(seg, code, data, check=check) if not builtin and self.circuit.has_arguments() else self.syn_accumulate(seg, data)
         receipt = self.seal_with_accum(seg, code, data, out_global, acc, check=check)
         if page_out:
-            self.page_out(seg, data, image)
+            self.page_out(seg, data, image, tree=tree)
         return receipt
 
-    def page_out(self, seg: Segment, data, image) -> None:
+    def page_out(self, seg: Segment, data, image, tree=None) -> None:
         """write the page table of the segment's derived data trace (a device Buffer) back into the memory image: image[p_addr] = p_out
-        on the rows with p_on = 1 (zkh_page_out).  A call of its own, after the seal: a refused witness never touches the image."""
-        self.hal.page_out(self.circuit, seg.po2, seg.zk_cycles, data, image)
+        on the rows with p_on = 1 (zkh_page_out).  A call of its own, after the seal: a refused witness never touches the image.
+        tree: the image's committed tree (hal.image_commit of the image as it is now), brought up to the new image in the same call
+        (zkh_page_out_tree): its root is the commitment the next segment starts from."""
+        if tree is None:
+            self.hal.page_out(self.circuit, seg.po2, seg.zk_cycles, data, image)
+        else:
+            self.hal.page_out_tree(self.circuit, seg.po2, seg.zk_cycles, data, image, tree)
 
     def prove_segment(self, seg: Segment) -> SegmentReceipt:
         code, data, out = self.witgen(seg)
