@@ -356,8 +356,8 @@ const char* zkh_derive_links(zkh_ctx*, const zkh_circuit*, size_t po2, size_t zk
  * comes first and a refusal leaves the image unchanged: the lowest row whose p_on is not 0 / 1, whose address is >= W, or whose address
  * does not follow a smaller one on a row with p_on = 1 (the table is a prefix of strictly increasing addresses, as the circuit demands:
  * a host-made table that repeats an address is refused, not resolved).  It is a call of its own so that a refused or aborted seal never
- * touches the image.  The prover can commit to the image (below); no circuit checks p_in / p_out against that commitment yet, so the
- * verifier does not learn which image (ARGUMENTS). */
+ * touches the image.  The prover can commit to the image and prove a page-out between two roots (below); no circuit checks p_in /
+ * p_out against that commitment yet, so the verifier does not learn which image (ARGUMENTS). */
 int zkh_circuit_pages(const zkh_circuit*);
 const char* zkh_derive_links_paged(zkh_ctx*, const zkh_circuit*, size_t po2, size_t zk_cycles, const zkh_buf* code, zkh_buf* data, const zkh_buf* image);
 const char* zkh_page_out(zkh_ctx*, const zkh_circuit*, size_t po2, size_t zk_cycles, const zkh_buf* data, zkh_buf* image);
@@ -381,6 +381,46 @@ const char* zkh_page_out(zkh_ctx*, const zkh_circuit*, size_t po2, size_t zk_cyc
 size_t zkh_image_tree_words(size_t image_words);
 const char* zkh_image_commit(zkh_ctx*, const zkh_buf* image, zkh_buf* nodes);
 const char* zkh_page_out_tree(zkh_ctx*, const zkh_circuit*, size_t po2, size_t zk_cycles, const zkh_buf* data, zkh_buf* image, zkh_buf* nodes);
+/* THE UPDATE'S PROOF, ZKU1: what takes a holder of root_before to root_after without the image.  W, L, `nodes` and "residue" are as
+ * above.  h = log2 L.  Layer k, 0 <= k <= h, is the layer of width w = L >> k: heap indices [w, 2 w); k = 0 is the leaf layer.  A valid
+ * page table has rows [0, D) with strictly increasing addresses a_i < W (what zkh_page_out's check pass establishes).
+ *   S_0 = the distinct a_i >> 3, increasing; M = |S_0|.   S_{k+1} = the distinct x >> 1 for x in S_k.
+ *   C_k, k < h: the clean siblings of layer k, { x ^ 1 : x in S_k, x ^ 1 not in S_k }, increasing; c_k = |C_k|.
+ * A clean sibling is the same digest in the tree before and after the page-out, so one proof serves both roots.  A padding leaf can be a
+ * clean sibling.  Digest 0 is never read.  The proof is a run of 32-bit words:
+ *   word 0                 0x5a4b5531 ('ZKU1', written as ARGS_MAGIC is)
+ *   words 1 .. 4           W, D, M, h
+ *   words 5 .. 5 + h - 1   c_0 .. c_{h-1}
+ *   then 3 D words         row i: a_i as an integer (the canonical value of p_addr), p_in[i] % P, p_out[i] % P (the residues of the raw
+ *                          words: the space the tree lives in)
+ *   then 8 M words         the leaves S_0, in order, as `nodes` holds them BEFORE the page-out
+ *   then 8 sum c_k words   for k = 0 .. h - 1 in that order, the digests of C_k in increasing index
+ * Its length is 5 + h + 3 D + 8 M + 8 sum c_k.  D = 0 gives the header alone, L = 1 no sibling section.  zkh_image_proof_words(W, D) is
+ * the bound 5 + h + 3 D + 8 min(D, L) + 8 sum_{k<h} min(D, L >> (k + 1)): a clean sibling shares its pair with a dirty node, so c_k is at
+ * most D and at most the number of pairs.  The bound is reached for D = 1 and for W <= 8.
+ * zkh_page_out_proof writes the proof of the page table of `data` into `proof`.  It only READS data, image and nodes, `nodes` being the
+ * tree of `image` as it is: call it BEFORE zkh_page_out_tree (the old leaves are taken from `nodes`).  The check pass is zkh_page_out's,
+ * with the same three refusals and the same text after "page_out_proof: " (nothing is written, so no "the image is unchanged"), and one
+ * more, tested after them on a row: p_in[i] % P is not the word the tree holds ("record R at row r: p_in X at address A, the tree holds
+ * Y").  A `nodes` that is not zkh_image_tree_words(W) words is refused before any launch, and so is, after the check pass has given D, a
+ * `proof` shorter than zkh_image_proof_words(W, D).  After a refusal the contents of `proof` are unspecified; words past the proof's
+ * length are never written.  No atomics, no read-back after the check pass: the proof is a function of data and nodes alone.
+ * zkh_image_proof_verify is HOST ONLY (no context, no GPU): the walk from `proof` and root_before to root_after, hashing through the
+ * permutation of zkh_poseidon2_mix_host.
+ *   The header is checked against the length; every word of the table's in / out, of the leaves and of the siblings must be < P; the
+ *   addresses must increase and lie below W, and lie in M leaves.  Every in_i must equal word a_i & 7 of its old leaf; the new leaves are
+ *   the old ones with out_i put in.  On layer k the walk goes through S_k in order: a node whose sibling is the next item pairs with it,
+ *   any other takes the next digest of C_k, on the left when the node's index is odd; hash_pair of the old children and of the new ones
+ *   give the parent's two digests.  Exactly c_k digests must be taken.  At the top the old digest must equal root_before; the new one is
+ *   root_after (L = 1: the leaf is the root; D = 0: root_before).  Zero padding past W is not checked: root_before is the authority.
+ * It FAILS with one message per cause, naming what and where: bad magic; an h that is not W's; a length other than what the header
+ * describes; a word >= P (its offset); row i whose address does not follow a smaller one or lies outside the image; an M other than the
+ * table's; row i whose `in` differs from its leaf's word; layer k with more or fewer siblings than the walk takes; "the proof opens root
+ * .., not root_before".  root_after is written only on success. */
+size_t zkh_image_proof_words(size_t image_words, size_t pages);
+const char* zkh_page_out_proof(zkh_ctx*, const zkh_circuit*, size_t po2, size_t zk_cycles, const zkh_buf* data, const zkh_buf* image, const zkh_buf* nodes,
+                               zkh_buf* proof);
+const char* zkh_image_proof_verify(const uint32_t* proof, size_t words, const uint32_t root_before[8], uint32_t root_after[8]);
 /* Everything a circuit's arguments derive, in the one order in which it is sound: sorted copies, then columns, then links, then
  * multiplicities (a LIMBS / ORDER record may read a sorted copy's column, and the multiplicities count the limbs that the records and
  * the links derive).  Call it after the data upload and before zkh_prove_begin: what it writes belongs to the data group.  It runs

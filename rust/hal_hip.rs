@@ -435,6 +435,30 @@ impl HipCircuitHal {
         ffi(|| unsafe { sys::zkh_page_out_tree(self.hal.ctx.0, self.circuit, po2, sys::ZK_CYCLES, data.raw, image.raw, nodes.raw) });
     }
 
+    /// The bound on the words of a ZKU1 proof of `pages` pages over an image of `image_words` words (`zkh_image_proof_words`).
+    pub fn image_proof_words(image_words: usize, pages: usize) -> usize {
+        unsafe { sys::zkh_image_proof_words(image_words, pages) }
+    }
+
+    /// The ZKU1 proof of the page-out of `data`'s page table (`zkh_page_out_proof`): the table's rows, the old leaves they touch and the
+    /// clean sibling digests of every layer, from which the root of `nodes` and the root after the page-out both follow.  Only reads
+    /// `data`, `image` and `nodes` (the committed tree of `image` as it is): call it before `page_out_tree`.  `proof` holds at least
+    /// `image_proof_words(W, pages)` words; the proof's own length follows from its header.  Panics as `page_out` does, when a `p_in` is
+    /// not the word the tree holds, and on a `nodes` or `proof` of the wrong size.
+    pub fn page_out_proof(&self, data: &HipBuffer<BabyBearElem>, image: &HipBuffer<BabyBearElem>, nodes: &HipBuffer<BabyBearElem>, proof: &HipBuffer<u32>,
+                          steps: usize) {
+        let po2 = steps.trailing_zeros() as usize;
+        ffi(|| unsafe { sys::zkh_page_out_proof(self.hal.ctx.0, self.circuit, po2, sys::ZK_CYCLES, data.raw, image.raw, nodes.raw, proof.raw) });
+    }
+
+    /// Walk a ZKU1 proof from `root_before` to the root after the page-out (`zkh_image_proof_verify`): host only, no GPU.  Panics with
+    /// one message per cause when the proof is refused.
+    pub fn image_proof_verify(proof: &[u32], root_before: &[u32; 8]) -> [u32; 8] {
+        let mut after = [0u32; 8];
+        ffi(|| unsafe { sys::zkh_image_proof_verify(proof.as_ptr(), proof.len(), root_before.as_ptr(), after.as_mut_ptr()) });
+        after
+    }
+
     /// Check the raw traces against the circuit's own constraints on every row of `rows` (`zkh_check_rows`): which constraint a
     /// witness breaks, and where, before a seal is spent on it.  `out` and `mix` are the global words.  `row < 0`: no row of the window
     /// fails; otherwise the lowest failing row, its lowest failing `and_eqz` step (an index into the ZKC1 step list), how many rows of

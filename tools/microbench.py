@@ -11,7 +11,8 @@ and zkh_derive_multiplicities on the same trace in the same run, alternating; M1
 under its version-7 blob next to zkh_derive_links under the version-6 blob on the same trace, and zkh_page_out next to a copy of the
 same bytes, alternating; M18: the committed image, zkh_page_out_tree (the page-out with the incremental update of the image's Merkle
 tree) next to zkh_page_out followed by zkh_image_commit (the full rebuild), for the derive's own page table, a hand-made table of as many
-pages spread over the whole image and a sparse one of 4096 pages, at two image sizes, alternating) on one
+pages spread over the whole image and a sparse one of 4096 pages, at two image sizes, alternating; M19: the update's proof,
+zkh_page_out_proof next to zkh_page_out_tree on M18's tables and image sizes, alternating, with the proof's size) on one
 MI355X, through the C ABI (HipHal).
 
 Each line of output is one JSON object: the op, its shape, the average wall time of one call (stream drained on both
@@ -712,6 +713,92 @@ def main() -> None:
                                   "reps": args.reps, **{k: spread(v) for k, v in t.items()}, "steps": steps,
                                   "tree_vs_rebuild": round(med["page_out_tree"] / med["page_out_then_commit"], 3)}), flush=True)
                 del images, nodes
+        del data
+    if want("M19"):
+        # the update's proof: zkh_page_out_proof (the ZKU1 proof of a page-out, built from the tree as it is: the table, the old leaves,
+        # the clean siblings of every layer; it hashes nothing) next to its yardstick in the same run, zkh_page_out_tree (the page-out
+        # and the incremental update: unchanged code), each on its own image and nodes.  M18's setup: SYN-LOOKUP-paged FULL, the tables
+        # `derive`, `spread` and `sparse`, 2^20 and 2^26 image words; p_in is set to the image's word, which the proof's check pass
+        # demands.  The proof's call goes through the C ABI directly: HipHal.page_out_proof would read the proof back.  Timed in
+        # alternation, `runs` windows of `reps` calls; median and spread (min, max) of the windows; then the stages by their events.
+        # The sparse table's proof is walked on the host (zkh_image_proof_verify) to the root the update leaves.
+        from zeth_amd import hal as zhal
+        from zeth_amd.circuits import logup, syn_lookup
+        runs, zk = 7, 1994
+        A = n - zk
+        shape = syn_lookup.FULL
+        desc, blob = syn_lookup.build_syn_lookup(shape, link=True, reads=True, pages=True)
+        pargs = logup.Arguments.parse(blob)
+        pg = pargs.pages
+        code_h, full_h, _out = syn_lookup.witness(shape, args.po2, zk, seed=17, link=True, reads=True, pages=True, image=np.zeros(1 << 20, dtype=np.uint32))
+        paged = hal.load_circuit(desc, jit=False)
+        paged.set_arguments(blob)
+        full = full_h.reshape(-1, n)
+        pages = int((full[pg.p_on, :A] != 0).sum())
+        one = np.uint32((1 << 32) % P)
+        rinv = pow(int(one), -1, P)
+        enc = lambda x: (np.asarray(x, dtype=np.uint64) * np.uint64(one) % np.uint64(P)).astype(np.uint32)   # noqa: E731
+        spread = lambda ts: {"median_ms": round(float(np.median(ts)) * 1e3, 4), "min_ms": round(min(ts) * 1e3, 4), "max_ms": round(max(ts) * 1e3, 4)}   # noqa: E731
+        data = hal.alloc_elem("m19d", full_h.size)
+        for W in (1 << 20, 1 << 26):
+            for table in ("derive", "spread", "sparse"):
+                image_h = rand_fp(rng, W)
+                hand = full.copy() if table == "derive" else np.zeros_like(full)
+                if table == "derive":
+                    D = pages
+                    addrs = (hand[pg.p_addr, :D].astype(np.uint64) * np.uint64(rinv) % np.uint64(P)).astype(np.int64)
+                else:
+                    D = pages if table == "spread" else 4096
+                    hand[pg.p_on, :D], hand[pg.p_out, :D] = one, rand_fp(rng, D)
+                    if W <= 1 << 22:
+                        addrs = rng.choice(W, D, replace=False)
+                    else:                                                    # (no permutation of 2^26 words: distinct draws, D of them at random)
+                        addrs = np.unique(rng.integers(0, W, D + D // 8))
+                        addrs = addrs[rng.choice(addrs.size, D, replace=False)]
+                    addrs = np.sort(addrs).astype(np.int64)
+                    hand[pg.p_addr, :D] = enc(addrs)
+                hand[pg.p_in, :D] = image_h[addrs]
+                data.write(hand.reshape(-1))
+                del hand
+                images = [hal.alloc_elem("m19i", W) for _ in range(2)]
+                for im in images:
+                    im.write(image_h)
+                nodes = [hal.image_commit(im) for im in images]
+                root0 = hal.image_root(nodes[0])
+                buf = hal.alloc("m19p", hal.image_proof_words(W, A))
+                proof_fn = lambda: zhal._check(zhal._lib.zkh_page_out_proof(hal.ctx, paged.h, args.po2, zk, data.h, images[0].h, nodes[0].h, buf.h))   # noqa: E731
+                tree_fn = lambda: hal.page_out_tree(paged, args.po2, zk, data, images[1], nodes[1])            # noqa: E731
+                words = hal.page_out_proof(paged, args.po2, zk, data, images[0], nodes[0], proof=buf)
+                tree_fn()
+                assert int(words[2]) == D and np.array_equal(nodes[0].to_vec()[8:16], root0)
+                walked = None
+                if table == "sparse":
+                    walked = bool(np.array_equal(zhal.image_proof_verify(words, root0), hal.image_root(nodes[1])))
+                    assert walked
+                t = {"page_out_proof": [], "page_out_tree": []}
+                for _ in range(runs):
+                    for name, fn in (("page_out_proof", proof_fn), ("page_out_tree", tree_fn)):
+                        t[name].append(timed(hal, fn, args.reps))
+                steps = {}
+                for name, fn in (("page_out_proof", proof_fn), ("page_out_tree", tree_fn)):
+                    hal.prof_enable(True)
+                    hal.prof_reset()
+                    for _ in range(args.reps):
+                        fn()
+                    hal.sync()
+                    steps[name] = {r["name"]: {"calls_per_call": r["calls"] // args.reps, "ms_per_call": round(r["total_ms"] / args.reps, 4)} for r in hal.prof_get()
+                                   if r["calls"] and r["name"].startswith(("page_out_", "proof_", "image_", "hash_fold"))}
+                    hal.prof_enable(False)
+                assert np.array_equal(buf.slice(0, words.size).to_vec(), words)
+                h = int(words[4])
+                med = {k: float(np.median(v)) for k, v in t.items()}
+                print(json.dumps({"bench": "M19", "circuit": "SYN-LOOKUP-paged FULL", "library": os.path.basename(os.environ.get("ZKH_LIBRARY", "") or "libzkhal_mi355x.so"),
+                                  "po2": args.po2, "table": table, "pages": D, "image_words": W, "leaves": logup.image_tree_leaves(W), "dirty_leaves": int(words[3]),
+                                  "clean_siblings": [int(x) for x in words[5:5 + h]], "proof_bytes": 4 * int(words.size),
+                                  "bound_bytes": 4 * hal.image_proof_words(W, D), "walked_on_the_host": walked, "runs": runs, "reps": args.reps,
+                                  **{k: spread(v) for k, v in t.items()}, "steps": steps,
+                                  "proof_vs_tree": round(med["page_out_proof"] / med["page_out_tree"], 3)}), flush=True)
+                del images, nodes, buf
         del data
     hal.close()
 

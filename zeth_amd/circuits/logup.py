@@ -111,8 +111,12 @@ in heap order, digest 0 eight zeros; leaf L + j, word k = image[8 j + k] % P for
 hash; node i (1 <= i < L) = hash_pair(node 2 i, node 2 i + 1), the operation P2-JOIN constrains; the root is digest 1.
 zkh_page_out_tree is the page-out followed by the update of the nodes on the paged words' paths: afterwards the nodes are those of a
 fresh commit of the new image.
-Left out: no circuit checks p_in / p_out against those roots and they are not in `out` (the verifier does not learn which image), sessions
-do not thread an image, and a blob pages one memory of one value word per address.
+THE UPDATE'S PROOF, ZKU1 (`reference_page_out_proof`, `check_page_out_proof`; zkh_page_out_proof, zkh_image_proof_verify; the format in
+full: include/zkhal.h): the page table's (address, in, out) rows, the old leaves they touch and the clean sibling digests of every layer,
+from which root_before and root_after both follow by one hash_pair per dirty node: who holds root_before and the proof reaches
+root_after without the image.
+Left out: no circuit checks p_in / p_out against those roots yet (the in-circuit path check consumes exactly this proof's digests) and
+they are not in `out`, sessions do not thread an image, and a blob pages one memory of one value word per address.
 
 WHO WRITES A DATA COLUMN (`_check_owned` behind `check_columns` and `check_links`; csrc/arguments.h says the same).  A data column
 has at most one writer, and a derive reads only what the stages before it have finished writing.  The writers: a sorted copy (its
@@ -1344,29 +1348,11 @@ def reference_page_out(args: Arguments, po2: int, zk_cycles: int, data, image) -
     p_on is not 0 / 1, whose address is outside the image or, the table being the host's own, whose address does not follow a smaller
     one: the page addresses of rows 0 .. D - 1 strictly increase and p_on is 1 exactly there, as the circuit demands, so no address
     is written twice (a repeated address is REFUSED, not resolved).  On one row in this order."""
-    n = 1 << po2
-    A = n - zk_cycles
-    pages = args.pages
-    if pages is None:
-        raise ReferenceError("the arguments hold no PAGES record (ZKA1 version 7)")
-    i = args.records.index(pages)
-    d = np.asarray(data, dtype=np.uint32).reshape(-1, n)
     out = np.array(image, dtype=np.uint32).reshape(-1)
-    W = out.size
-    on, addr = _dec(d[pages.p_on, :A]).astype(np.int64), _dec(d[pages.p_addr, :A]).astype(np.int64)
-    pon, paddr = np.concatenate([[1], on[:-1]]), np.concatenate([[-1], addr[:-1]])
-    live = on == 1
-    follows = (pon == 1) & (paddr < addr)
-    bad = (on > 1) | (live & ((addr >= W) | ~follows))
-    if bad.any():
-        r = int(np.argmax(bad))
-        at = f"record {i} at row {r}"
-        if on[r] > 1:
-            raise ReferenceError(f"{at}: p_on {int(on[r])}, not 0 or 1")
-        if addr[r] >= W:
-            raise ReferenceError(f"{at}: address {int(addr[r])} outside the image of {W} words")
-        raise ReferenceError(f"{at}: page address {int(addr[r])} does not follow a smaller one (row {r - 1}: p_on {int(pon[r])}, address {int(paddr[r])})")
-    out[addr[live]] = d[pages.p_out, :A][live]
+    d, live = _page_table(args, po2, zk_cycles, data, out.size)
+    A = (1 << po2) - zk_cycles
+    pages = args.pages
+    out[_dec(d[pages.p_addr, :A][live]).astype(np.int64)] = d[pages.p_out, :A][live]
     return out
 
 
@@ -1412,6 +1398,173 @@ def reference_image_tree(image) -> np.ndarray:
 def reference_image_root(image) -> np.ndarray:
     """the root of `reference_image_tree`: digest 1, 8 words"""
     return reference_image_tree(image)[1].copy()
+
+
+PROOF_MAGIC = 0x5A4B5531                        # 'ZKU1'
+PROOF_HEADER = 5
+
+
+def _tree_height(image_words: int) -> int:
+    return image_tree_leaves(image_words).bit_length() - 1
+
+
+def image_proof_words(image_words: int, pages: int) -> int:
+    """zkh_image_proof_words: the bound 5 + h + 3 D + 8 min(D, L) + 8 sum_{k<h} min(D, L >> (k + 1)) on the words of a ZKU1 proof of D
+    pages over an image of W words (a clean sibling shares its pair with a dirty node: c_k is at most D and at most the pairs)"""
+    L, D = image_tree_leaves(image_words), int(pages)
+    h = L.bit_length() - 1
+    return PROOF_HEADER + h + 3 * D + 8 * min(D, L) + 8 * sum(min(D, L >> (k + 1)) for k in range(h))
+
+
+def _page_table(args: Arguments, po2: int, zk_cycles: int, data, W: int, leaves=None):
+    """the check pass of the page-out family -> (d, live): the data trace as (columns, n) and the mask of the table's rows over the
+    active ones; raises ReferenceError on the lowest refused row.  leaves: the tree's leaf layer as flat words (the proof's fourth
+    refusal: p_in is not the word the tree holds)"""
+    n = 1 << po2
+    A = n - zk_cycles
+    pages = args.pages
+    if pages is None:
+        raise ReferenceError("the arguments hold no PAGES record (ZKA1 version 7)")
+    i = args.records.index(pages)
+    d = np.asarray(data, dtype=np.uint32).reshape(-1, n)
+    on, addr = _dec(d[pages.p_on, :A]).astype(np.int64), _dec(d[pages.p_addr, :A]).astype(np.int64)
+    pon, paddr = np.concatenate([[1], on[:-1]]), np.concatenate([[-1], addr[:-1]])
+    live = on == 1
+    follows = (pon == 1) & (paddr < addr)
+    bad = (on > 1) | (live & ((addr >= W) | ~follows))
+    if leaves is not None:
+        held = leaves[np.where(live & (addr < W), addr, 0)]
+        bad |= live & (d[pages.p_in, :A] % np.uint32(P) != held)
+    if bad.any():
+        r = int(np.argmax(bad))
+        at = f"record {i} at row {r}"
+        if on[r] > 1:
+            raise ReferenceError(f"{at}: p_on {int(on[r])}, not 0 or 1")
+        if addr[r] >= W:
+            raise ReferenceError(f"{at}: address {int(addr[r])} outside the image of {W} words")
+        if not follows[r]:
+            raise ReferenceError(f"{at}: page address {int(addr[r])} does not follow a smaller one (row {r - 1}: p_on {int(pon[r])}, address {int(paddr[r])})")
+        raise ReferenceError(f"{at}: p_in {int(_dec(d[pages.p_in, r]))} at address {int(addr[r])}, the tree holds {int(_dec(held[r]))}")
+    return d, live
+
+
+def reference_page_out_proof(args: Arguments, po2: int, zk_cycles: int, data, image_words: int, nodes) -> np.ndarray:
+    """The ZKU1 proof zkh_page_out_proof writes (include/zkhal.h "THE UPDATE'S PROOF"), word for word: the page table of `data` over an
+    image of `image_words` words whose committed tree is `nodes` (`reference_image_tree`, before the page-out).  It hashes nothing:
+    every digest is read from `nodes`.  Raises ReferenceError on the lowest refused row as `reference_page_out` does and, after its
+    three refusals on a row, when p_in % P is not the word the tree holds; and on a `nodes` of another size."""
+    W = int(image_words)
+    L = image_tree_leaves(W)
+    nodes = np.asarray(nodes, dtype=np.uint32).reshape(-1)
+    if not W or nodes.size != 16 * L:
+        raise ReferenceError(f"nodes of {nodes.size} words; an image of {W} words has a tree of {16 * L if W else 0} (zkh_image_tree_words)")
+    nodes = nodes.reshape(-1, 8)
+    d, live = _page_table(args, po2, zk_cycles, data, W, leaves=nodes[L:].reshape(-1))
+    A = (1 << po2) - zk_cycles
+    pages = args.pages
+    a = _dec(d[pages.p_addr, :A][live]).astype(np.int64)
+    h = L.bit_length() - 1
+    table = np.stack([a.astype(np.uint32), d[pages.p_in, :A][live] % np.uint32(P), d[pages.p_out, :A][live] % np.uint32(P)], axis=1)
+    S = np.unique(a >> 3)
+    counts, sections = [], [nodes[L + S].reshape(-1)]
+    for k in range(h):
+        clean = (S ^ 1)[~np.isin(S ^ 1, S)]
+        counts.append(clean.size)
+        sections.append(nodes[(L >> k) + clean].reshape(-1))
+        S = np.unique(S >> 1)
+    header = np.array([PROOF_MAGIC, W, a.size, sections[0].size // 8, h] + counts, dtype=np.uint32)
+    return np.concatenate([header, table.reshape(-1)] + sections).astype(np.uint32)
+
+
+def _digest_hex(d) -> str:
+    return " ".join(f"{int(w):08x}" for w in d)
+
+
+def check_page_out_proof(proof, root_before) -> np.ndarray:
+    """zkh_image_proof_verify in numpy, one `_hash_pairs` batch per layer: the walk from a ZKU1 proof and root_before to root_after (8
+    words), with nothing else in hand.  Raises ReferenceError with the C verifier's message (after its "image_proof_verify: ")."""
+    pf = np.asarray(proof, dtype=np.uint32).reshape(-1)
+    rb = np.asarray(root_before, dtype=np.uint32).reshape(-1)
+    if pf.size < PROOF_HEADER:
+        raise ReferenceError(f"a proof of {pf.size} words: the header alone has {PROOF_HEADER}")
+    magic, W, D, M, h = (int(x) for x in pf[:PROOF_HEADER])
+    if magic != PROOF_MAGIC:
+        raise ReferenceError(f"bad magic 0x{magic:08x} (ZKU1 is 0x{PROOF_MAGIC:08x})")
+    if h != _tree_height(W):
+        raise ReferenceError(f"h {h}, but an image of {W} words has h {_tree_height(W)}")
+    if pf.size < PROOF_HEADER + h:
+        raise ReferenceError(f"a proof of {pf.size} words, but the header describes at least {PROOF_HEADER + h}")
+    c = [int(x) for x in pf[PROOF_HEADER:PROOF_HEADER + h]]
+    want = PROOF_HEADER + h + 3 * D + 8 * M + 8 * sum(c)
+    if pf.size != want:
+        raise ReferenceError(f"a proof of {pf.size} words, but the header describes {want}")
+    t0 = PROOF_HEADER + h
+    l0 = t0 + 3 * D
+    s0 = l0 + 8 * M
+    table = pf[t0:l0].reshape(-1, 3)
+    unreduced = pf >= P
+    unreduced[:t0] = False
+    unreduced[t0:l0:3] = False                                               # the addresses are integers
+    if unreduced.any():
+        at = int(np.argmax(unreduced))
+        raise ReferenceError(f"word {at} is {int(pf[at])}, not below P")
+    if rb.size != 8 or (rb >= P).any():
+        raise ReferenceError("root_before is not 8 words below P")
+    if D == 0:
+        if M:
+            raise ReferenceError(f"M {M}, but the table's rows lie in 0 leaves")
+        for k in range(h):
+            if c[k]:
+                raise ReferenceError(f"layer {k}: {c[k]} siblings, but the walk takes 0")
+        return rb.copy()
+    a = table[:, 0].astype(np.int64)
+    below = np.concatenate([[-1], a[:-1]])
+    bad = (a >= W) | (a <= below)
+    if bad.any():
+        r = int(np.argmax(bad))
+        if a[r] >= W:
+            raise ReferenceError(f"row {r}: address {int(a[r])} outside the image of {W} words")
+        raise ReferenceError(f"row {r}: address {int(a[r])} does not follow a smaller one (row {r - 1}: address {int(below[r])})")
+    S, rank = np.unique(a >> 3, return_inverse=True)
+    if S.size != M:
+        raise ReferenceError(f"M {M}, but the table's rows lie in {S.size} leaves")
+    old = pf[l0:s0].reshape(-1, 8).copy()
+    held = old[rank, a & 7]
+    if (held != table[:, 1]).any():
+        r = int(np.argmax(held != table[:, 1]))
+        raise ReferenceError(f"row {r}: in {int(table[r, 1])} at address {int(a[r])}, but its leaf holds {int(held[r])}")
+    new = old.copy()
+    new[rank, a & 7] = table[:, 2]
+    at = s0
+    for k in range(h):
+        m = S.size
+        nxt = np.concatenate([S[1:], [-1]])
+        prv = np.concatenate([[-1], S[:-1]])
+        first = (S & 1 == 0) & (nxt == S + 1)                                # an even node whose sibling is the next item
+        second = (S & 1 == 1) & (prv == S - 1)
+        lone = ~(first | second)
+        take = int(lone.sum())
+        if take != c[k]:
+            raise ReferenceError(f"layer {k}: {c[k]} siblings, but the walk takes {take}")
+        sib = pf[at:at + 8 * take].reshape(-1, 8)
+        at += 8 * take
+        heads = ~second
+        parents = int(heads.sum())
+        lo, ln, ro, rn = (np.zeros((parents, 8), dtype=np.uint32) for _ in range(4))
+        slot = np.cumsum(heads) - 1                                          # the parent's rank of every item
+        left, right = S & 1 == 0, S & 1 == 1
+        lo[slot[left]], ln[slot[left]] = old[left], new[left]
+        ro[slot[right]], rn[slot[right]] = old[right], new[right]
+        lone_left = lone & left                                              # the node is the left child: its sibling goes right
+        ro[slot[lone_left]] = rn[slot[lone_left]] = sib[(np.cumsum(lone) - 1)[lone_left]]
+        lone_right = lone & right
+        lo[slot[lone_right]] = ln[slot[lone_right]] = sib[(np.cumsum(lone) - 1)[lone_right]]
+        both = _hash_pairs(np.concatenate([lo, ln]), np.concatenate([ro, rn]))
+        old, new = both[:parents], both[parents:]
+        S = S[heads] >> 1
+    if not np.array_equal(old[0], rb):
+        raise ReferenceError(f"the proof opens root {_digest_hex(old[0])}, not root_before")
+    return new[0].copy()
 
 
 def bus_slots(A: int, distinct_keys: int) -> int:

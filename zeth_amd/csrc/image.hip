@@ -28,6 +28,9 @@
 #include "scan.h"
 #include "sort.h"
 
+#include <cstring>
+#include <vector>
+
 using namespace zkh;
 
 namespace {
@@ -71,19 +74,20 @@ __global__ __launch_bounds__(IMG_THREADS) void k_image_dirty_leaves(const uint32
 
 // The dirty parent that item t of the layer below names.  kTable: the items are the table's rows, a row's parent on the widest parent
 // layer is its address >> 4; else the items are the list of the layer below, and a node's parent is its index >> 1.
-template <bool kTable>
-__device__ __forceinline__ uint32_t parent_of(const uint32_t* __restrict__ src, uint32_t t) { return kTable ? canonical(src[t]) >> 4 : src[t] >> 1; }
+// kShift: what a table row's address is shifted by: 4 names its parent on the widest parent layer, 3 its leaf (the proof's first list).
+template <bool kTable, int kShift = 4>
+__device__ __forceinline__ uint32_t parent_of(const uint32_t* __restrict__ src, uint32_t t) { return kTable ? canonical(src[t]) >> kShift : src[t] >> 1; }
 
 // grid ceil(bound / IMG_THREADS) over the items [0, m) of the layer below, m = *count (kTable: the host's D, count = NULL): local[t] = the
 // heads among the items of t's workgroup up to t (a head: its parent differs from the item before's), sums[1 + workgroup] = the
 // workgroup's heads.  Workgroups past m leave a total of 0.
-template <bool kTable>
+template <bool kTable, int kShift = 4>
 __global__ __launch_bounds__(IMG_THREADS) void k_image_heads(const uint32_t* __restrict__ src, const uint32_t* __restrict__ count, uint32_t D,
                                                              uint32_t* __restrict__ local, uint32_t* __restrict__ sums) {
     __shared__ uint32_t buf[2][IMG_THREADS];
     const uint32_t m = kTable ? D : *count;
     const uint32_t t = blockIdx.x * IMG_THREADS + threadIdx.x;
-    const uint32_t head = t < m && (t == 0 || parent_of<kTable>(src, t - 1) != parent_of<kTable>(src, t));
+    const uint32_t head = t < m && (t == 0 || parent_of<kTable, kShift>(src, t - 1) != parent_of<kTable, kShift>(src, t));
     const uint32_t incl = block_scan<IMG_THREADS>(head, buf, AddWrap());
     if (t < m) local[t] = incl;
     if (threadIdx.x == IMG_THREADS - 1) sums[1 + blockIdx.x] = incl;
@@ -100,7 +104,205 @@ __global__ __launch_bounds__(IMG_THREADS) void k_image_compact(const uint32_t* _
     if (t == 0 || parent_of<kTable>(src, t - 1) != v) list[local[t] + sums[1 + blockIdx.x] - 1] = v;
 }
 
+// ---- THE UPDATE'S PROOF (include/zkhal.h; the header comment of zkh::image_proof_build below) ----
+constexpr uint32_t PROOF_MAGIC = 0x5a4b5531;            // 'ZKU1'
+constexpr uint32_t PROOF_HEADER = 5;
+// A layer whose list holds at most 2^PROOF_TOP_LOG items for certain (min(D, its nodes): the bound only falls on the way up) is walked,
+// with every layer above it, by ONE workgroup in one launch (k_proof_top): the list fits its lanes, and a layer costs barriers instead
+// of three launches.  Measured (DESIGN.md §2 ARGUMENTS, M19): a layer of three launches takes 12 us whatever its list holds up to 2^19
+// items (16 us with 6 x 10^5 digests to copy), a layer inside the top kernel 1.8 us; so the top starts as low as its lanes allow.
+constexpr int PROOF_TOP_LOG = 10;
+constexpr uint32_t TOP_THREADS = 1u << PROOF_TOP_LOG;
+// the counts on the device, three words per layer k: the items of S_k, c_k, and the word of `proof` where C_k's digests start
+enum { PM_ITEMS = 0, PM_CLEAN = 1, PM_OFF = 2, PM_WORDS = 3 };
+
+// A digest from `nodes` (16-byte aligned: two 16-byte loads) to the proof (word aligned: its sections start where the counts put them)
+__device__ __forceinline__ void copy_digest(const uint32_t* __restrict__ from, uint32_t* __restrict__ to) {
+    const uint4 a = ((const uint4*)from)[0], b = ((const uint4*)from)[1];
+    to[0] = a.x; to[1] = a.y; to[2] = a.z; to[3] = a.w;
+    to[4] = b.x; to[5] = b.y; to[6] = b.z; to[7] = b.w;
+}
+
+// The two flags of item t of a sorted list S_k of m node indices, given its neighbours (NONE past either end): bit 0 "my sibling is not
+// my neighbour in the list" (its digest is a clean sibling), bit 16 "my parent differs from the item before's" (a head of S_{k+1}).
+__device__ __forceinline__ uint32_t proof_flags(uint32_t before, uint32_t x, uint32_t after) {
+    const bool paired = x & 1 ? before == x - 1 : after == x + 1;          // before / after = NONE never match: x < 2^29
+    const bool head = before == NONE || (before >> 1) != (x >> 1);
+    return (paired ? 0u : 1u) | (head ? 0x10000u : 0u);
+}
+
+// grid ceil(D / IMG_THREADS): row i of the table as three words (the address as an integer, the residues of p_in and p_out); lane 0
+// the header's words that the host knows
+__global__ __launch_bounds__(IMG_THREADS) void k_proof_table(const uint32_t* __restrict__ addrs, const uint32_t* __restrict__ in, const uint32_t* __restrict__ out,
+                                                             uint32_t D, uint32_t W, uint32_t h, uint32_t* __restrict__ proof) {
+    const uint32_t t = blockIdx.x * IMG_THREADS + threadIdx.x;
+    if (t >= D) return;
+    uint32_t* row = proof + PROOF_HEADER + h + 3 * (size_t)t;
+    row[0] = canonical(addrs[t]);
+    row[1] = in[t] % P;
+    row[2] = out[t] % P;
+    if (t == 0) { proof[0] = PROOF_MAGIC; proof[1] = W; proof[2] = D; proof[4] = h; }
+}
+
+// After k_image_heads<true, 3> and its counter scan (meta[PM_ITEMS] = M): every row that is the first of its leaf writes the leaf's
+// index at its rank into `list` (S_0) and copies the leaf, as `nodes` holds it, to the proof's leaf section at that rank.  Lane 0 writes
+// M to the header and the word where the sibling digests start.
+__global__ __launch_bounds__(IMG_THREADS) void k_proof_leaves(const uint32_t* __restrict__ addrs, uint32_t D, const uint32_t* __restrict__ local,
+                                                              const uint32_t* __restrict__ sums, const uint32_t* __restrict__ nodes, size_t L, uint32_t h,
+                                                              uint32_t* __restrict__ list, uint32_t* __restrict__ meta, uint32_t* __restrict__ proof) {
+    const uint32_t t = blockIdx.x * IMG_THREADS + threadIdx.x;
+    if (t >= D) return;
+    const size_t leaves0 = PROOF_HEADER + h + 3 * (size_t)D;
+    if (t == 0) {
+        const uint32_t M = meta[PM_ITEMS];
+        proof[3] = M;
+        meta[PM_OFF] = (uint32_t)(leaves0 + 8 * (size_t)M);
+    }
+    const uint32_t leaf = canonical(addrs[t]) >> 3;
+    if (t && (canonical(addrs[t - 1]) >> 3) == leaf) return;
+    const uint32_t rank = local[t] + sums[1 + blockIdx.x] - 1;
+    list[rank] = leaf;
+    copy_digest(nodes + (L + leaf) * 8, proof + leaves0 + 8 * (size_t)rank);
+}
+
+// One layer below the top kernel's, three launches.  First, grid ceil(bound / IMG_THREADS) over the items [0, m) of S_k,
+// m = meta[PM_ITEMS]: both flags of every item, scanned in the workgroup as one packed word (a workgroup's counts are <= 256: 16 bits
+// each), local[t] = the packed inclusive counts, the workgroup's totals to its place in the two runs of `sums` ([0, nb) clean, [nb, 2 nb) heads).
+__global__ __launch_bounds__(IMG_THREADS) void k_proof_flags(const uint32_t* __restrict__ list, const uint32_t* __restrict__ meta, uint32_t* __restrict__ local,
+                                                             uint32_t* __restrict__ sums, uint32_t nb) {
+    __shared__ uint32_t buf[2][IMG_THREADS];
+    const uint32_t m = meta[PM_ITEMS];
+    const uint32_t t = blockIdx.x * IMG_THREADS + threadIdx.x;
+    uint32_t f = 0;
+    if (t < m) f = proof_flags(t ? list[t - 1] : NONE, list[t], t + 1 < m ? list[t + 1] : NONE);
+    const uint32_t incl = block_scan<IMG_THREADS>(f, buf, AddWrap());
+    if (t < m) local[t] = incl;
+    if (threadIdx.x == IMG_THREADS - 1) { sums[blockIdx.x] = incl & 0xffff; sums[nb + blockIdx.x] = incl >> 16; }
+}
+// ... then the counter scan over both runs (c_k to meta[PM_CLEAN], the items of S_{k+1} to the next layer's meta[PM_ITEMS]), then: an
+// item whose sibling is clean copies that digest from `nodes` to the proof at its rank, a head writes its parent into `next` at its
+// rank.  Lane 0 writes c_k to the header and the next layer's offset.  `width` = the nodes of layer k.
+__global__ __launch_bounds__(IMG_THREADS) void k_proof_gather(const uint32_t* __restrict__ list, uint32_t* __restrict__ meta, const uint32_t* __restrict__ local,
+                                                              const uint32_t* __restrict__ sums, uint32_t nb, const uint32_t* __restrict__ nodes, size_t width,
+                                                              uint32_t k, uint32_t* __restrict__ next, uint32_t* __restrict__ proof) {
+    const uint32_t m = meta[PM_ITEMS], off = meta[PM_OFF];
+    const uint32_t t = blockIdx.x * IMG_THREADS + threadIdx.x;
+    if (t >= m) return;
+    if (t == 0) {
+        const uint32_t c = meta[PM_CLEAN];
+        proof[PROOF_HEADER + k] = c;
+        meta[PM_WORDS + PM_OFF] = off + 8 * c;
+    }
+    const uint32_t x = list[t];
+    const uint32_t f = proof_flags(t ? list[t - 1] : NONE, x, t + 1 < m ? list[t + 1] : NONE);
+    const uint32_t ranks = local[t];
+    if (f & 1) copy_digest(nodes + (width + (x ^ 1)) * 8, proof + off + 8 * (size_t)((ranks & 0xffff) + sums[blockIdx.x] - 1));
+    if (f >> 16) next[(ranks >> 16) + sums[nb + blockIdx.x] - 1] = x >> 1;
+}
+
+// The narrow top: ONE workgroup walks every layer k0 <= k < h (S_k0 and so every list above it fits its lanes), the list in
+// LDS: flag, scan, gather, parents, a barrier between the layers.  meta: layer k0's three words.
+__global__ __launch_bounds__(TOP_THREADS) void k_proof_top(const uint32_t* __restrict__ list, const uint32_t* __restrict__ meta, const uint32_t* __restrict__ nodes,
+                                                           size_t L, uint32_t k0, uint32_t h, uint32_t* __restrict__ proof) {
+    __shared__ uint32_t items[2][TOP_THREADS];
+    __shared__ uint32_t buf[2][TOP_THREADS];
+    __shared__ uint32_t totals;
+    const uint32_t t = threadIdx.x;
+    uint32_t m = meta[PM_ITEMS], off = meta[PM_OFF];
+    if (t < m) items[0][t] = list[t];
+    __syncthreads();
+    int cur = 0;
+    for (uint32_t k = k0; k < h; k++, cur ^= 1) {
+        const uint32_t x = t < m ? items[cur][t] : 0;
+        uint32_t f = 0;
+        if (t < m) f = proof_flags(t ? items[cur][t - 1] : NONE, x, t + 1 < m ? items[cur][t + 1] : NONE);
+        const uint32_t incl = block_scan<TOP_THREADS>(f, buf, AddWrap());
+        if (t == TOP_THREADS - 1) totals = incl;
+        __syncthreads();
+        const uint32_t c = totals & 0xffff;
+        if (f & 1) copy_digest(nodes + ((L >> k) + (x ^ 1)) * 8, proof + off + 8 * (size_t)((incl & 0xffff) - 1));
+        if (f >> 16) items[cur ^ 1][(incl >> 16) - 1] = x >> 1;
+        if (t == 0) proof[PROOF_HEADER + k] = c;
+        m = totals >> 16;
+        off += 8 * c;
+        __syncthreads();
+    }
+}
+
 }  // namespace
+
+// THE UPDATE'S PROOF on the device (zkh_page_out_proof, links.hip -> image_proof_build), after the check pass: the table's rows [0, D)
+// hold strictly increasing addresses a_i < W and p_in is what the tree holds.  `nodes` is only read.
+//   proof_table  : the header's W, D, h and the 3 D table words, one pass over D lanes;
+//   proof_leaves : S_0 = the adjacent-unique of a_i >> 3, flag / scan / compact as image_list does for a_i >> 4 (k_image_heads with the
+//                  shift 3, the counter scan, k_proof_leaves): a head lane copies its 32-byte leaf to its rank; M and the siblings'
+//                  first word are written from the count;
+//   proof_layer  : per layer whose list may hold more than 2^PROOF_TOP_LOG items (min(D, its nodes)): k_proof_flags, ONE counter scan
+//                  over two runs, k_proof_gather;
+//   proof_top    : every layer from the first whose list cannot, in one launch of one workgroup.  L = 1 has no layer.
+// No atomics and no read-back: every count stays on the device (`meta`), every section's offset comes from counts an earlier launch
+// (or, in the top, an earlier barrier) wrote, every word of the proof is written by one lane.  The grids are sized by the bounds
+// min(D, the layer's nodes); lanes past the count leave.
+const char* zkh::image_proof_build(zkh_ctx* ctx, const uint32_t* addrs, const uint32_t* in, const uint32_t* out, uint32_t D, size_t image_words,
+                                   const zkh_buf* nodes, zkh_buf* proof) {
+    const size_t L = image_leaves(image_words);
+    const uint32_t W = (uint32_t)image_words;
+    uint32_t h = 0;
+    while (((size_t)1 << h) < L) h++;
+    if (!D) {                                           // the header alone: nothing to launch
+        std::vector<uint32_t> header(PROOF_HEADER + h, 0);
+        header[0] = PROOF_MAGIC; header[1] = W; header[4] = h;
+        return zkh_write(ctx, proof, header.data(), 0, header.size());
+    }
+    const uint32_t nb0 = (D + IMG_THREADS - 1) / IMG_THREADS;
+    Tmp lists[2], local, sums, meta;
+    for (int i = 0; i < 2; i++) ZKH_TRY(new_buf(ctx, D, false, lists[i].out()));
+    ZKH_TRY(new_buf(ctx, D, false, local.out()));
+    ZKH_TRY(new_buf(ctx, 1 + 2 * (size_t)nb0, false, sums.out()));
+    ZKH_TRY(new_buf(ctx, PM_WORDS * ((size_t)h + 2), false, meta.out()));
+    {
+        ProfScope prof(ctx, "proof_table", 24.0 * D);
+        k_proof_table<<<nb0, IMG_THREADS, 0, ctx->stream>>>(addrs, in, out, D, W, h, proof->ptr());
+        ZKH_TRY(last_launch_error("proof_table"));
+    }
+    {
+        ProfScope prof(ctx, "proof_leaves", 16.0 * D + 8.0 * nb0 + 68.0 * (D < L ? D : L));
+        k_image_heads<true, 3><<<nb0, IMG_THREADS, 0, ctx->stream>>>(addrs, nullptr, D, local->ptr(), sums->ptr());
+        ZKH_TRY(last_launch_error("proof_heads"));
+        scan_counters(ctx, sums->ptr() + 1, 1, nb0, meta->ptr() + PM_ITEMS, 0);
+        ZKH_TRY(last_launch_error("proof_carry"));
+        k_proof_leaves<<<nb0, IMG_THREADS, 0, ctx->stream>>>(addrs, D, local->ptr(), sums->ptr(), nodes->ptr(), L, h, lists[0]->ptr(), meta->ptr(), proof->ptr());
+        ZKH_TRY(last_launch_error("proof_leaves"));
+    }
+    uint32_t k0 = 0;                                    // layers [0, k0): S_k may hold more items than the top kernel has lanes
+    while (k0 < h && (D < (L >> k0) ? D : (L >> k0)) > TOP_THREADS) k0++;
+    int cur = 0;
+    for (uint32_t k = 0; k < k0; k++, cur ^= 1) {
+        const size_t width = L >> k;
+        const uint32_t items = (uint32_t)(D < width ? D : width);
+        const uint32_t nb = (items + IMG_THREADS - 1) / IMG_THREADS;
+        uint32_t* mk = meta->ptr() + PM_WORDS * (size_t)k;
+        ProfScope prof(ctx, "proof_layer", 20.0 * items + 16.0 * nb + 64.0 * (items < width / 2 ? items : width / 2));
+        k_proof_flags<<<nb, IMG_THREADS, 0, ctx->stream>>>(lists[cur]->ptr(), mk, local->ptr(), sums->ptr(), nb);
+        ZKH_TRY(last_launch_error("proof_flags"));
+        scan_counters(ctx, sums->ptr(), 2, nb, mk + PM_CLEAN, PM_WORDS - PM_CLEAN + PM_ITEMS);
+        ZKH_TRY(last_launch_error("proof_carry"));
+        k_proof_gather<<<nb, IMG_THREADS, 0, ctx->stream>>>(lists[cur]->ptr(), mk, local->ptr(), sums->ptr(), nb, nodes->ptr(), width, k, lists[cur ^ 1]->ptr(),
+                                                            proof->ptr());
+        ZKH_TRY(last_launch_error("proof_gather"));
+    }
+    if (k0 < h) {
+        const size_t width = L >> k0;
+        const size_t items = D < width ? D : width;
+        double digests = 0;                             // at most min(items, the layer's pairs) clean siblings per layer
+        for (uint32_t k = k0; k < h; k++) digests += (double)(items < (L >> k) / 2 ? items : (L >> k) / 2);
+        ProfScope prof(ctx, "proof_top", 4.0 * items + 64.0 * digests);
+        k_proof_top<<<1, TOP_THREADS, 0, ctx->stream>>>(lists[cur]->ptr(), meta->ptr() + PM_WORDS * (size_t)k0, nodes->ptr(), L, k0, h, proof->ptr());
+        ZKH_TRY(last_launch_error("proof_top"));
+    }
+    // the temporaries go back to the pool on return: the stream orders their next use after these launches
+    return nullptr;
+}
 
 const char* zkh::image_tree_update(zkh_ctx* ctx, const uint32_t* addrs, uint32_t D, const zkh_buf* image, zkh_buf* nodes) {
     const size_t L = image_leaves(image->len);
@@ -165,4 +367,96 @@ extern "C" const char* zkh_image_commit(zkh_ctx* ctx, const zkh_buf* image, zkh_
         ZKH_TRY(last_launch_error("image_leaves"));
     }
     return merkle_fold_from(ctx, nodes, L);
+}
+
+extern "C" size_t zkh_image_proof_words(size_t image_words, size_t pages) {
+    const size_t L = image_leaves(image_words), D = pages;
+    size_t words = PROOF_HEADER + 3 * D + 8 * (D < L ? D : L);
+    for (size_t w = L; w > 1; w >>= 1) words += 1 + 8 * (D < w / 2 ? D : w / 2);
+    return words;
+}
+
+// The walk of include/zkhal.h "THE UPDATE'S PROOF" on the host: no context, no GPU; every layer is one batch through the permutation
+// zkh_poseidon2_mix_host uses, the old children first, the new ones after them.
+extern "C" const char* zkh_image_proof_verify(const uint32_t* proof, size_t words, const uint32_t root_before[8], uint32_t root_after[8]) {
+    ZKH_REQUIRE(proof && root_before && root_after, "image_proof_verify: null argument");
+    ZKH_REQUIRE(words >= PROOF_HEADER, "image_proof_verify: a proof of %zu words: the header alone has %u", words, PROOF_HEADER);
+    const uint32_t W = proof[1], D = proof[2], M = proof[3], h = proof[4];
+    ZKH_REQUIRE(proof[0] == PROOF_MAGIC, "image_proof_verify: bad magic 0x%08x (ZKU1 is 0x%08x)", proof[0], PROOF_MAGIC);
+    uint32_t hw = 0;
+    while (((size_t)1 << hw) < image_leaves(W)) hw++;
+    ZKH_REQUIRE(h == hw, "image_proof_verify: h %u, but an image of %u words has h %u", h, W, hw);
+    ZKH_REQUIRE(words >= PROOF_HEADER + h, "image_proof_verify: a proof of %zu words, but the header describes at least %u", words, PROOF_HEADER + h);
+    const uint32_t* c = proof + PROOF_HEADER;
+    unsigned long long want = PROOF_HEADER + h + 3ull * D + 8ull * M;
+    for (uint32_t k = 0; k < h; k++) want += 8ull * c[k];
+    ZKH_REQUIRE(words == want, "image_proof_verify: a proof of %zu words, but the header describes %llu", words, want);
+    const size_t t0 = PROOF_HEADER + h, l0 = t0 + 3 * (size_t)D, s0 = l0 + 8 * (size_t)M;
+    for (size_t i = t0; i < words; i++)
+        ZKH_REQUIRE(proof[i] < P || (i < l0 && (i - t0) % 3 == 0), "image_proof_verify: word %zu is %u, not below P", i, proof[i]);
+    for (int j = 0; j < 8; j++) ZKH_REQUIRE(root_before[j] < P, "image_proof_verify: root_before is not 8 words below P");
+    if (!D) {
+        ZKH_REQUIRE(!M, "image_proof_verify: M %u, but the table's rows lie in 0 leaves", M);
+        for (uint32_t k = 0; k < h; k++) ZKH_REQUIRE(!c[k], "image_proof_verify: layer %u: %u siblings, but the walk takes 0", k, c[k]);
+        memmove(root_after, root_before, 32);
+        return nullptr;
+    }
+    const uint32_t* table = proof + t0;
+    std::vector<uint32_t> S, rank(D);                   // the dirty nodes of the layer in hand; every row's leaf among S_0
+    for (uint32_t i = 0; i < D; i++) {
+        const uint32_t a = table[3 * (size_t)i];
+        ZKH_REQUIRE(a < W, "image_proof_verify: row %u: address %u outside the image of %u words", i, a, W);
+        ZKH_REQUIRE(!i || table[3 * (size_t)(i - 1)] < a, "image_proof_verify: row %u: address %u does not follow a smaller one (row %u: address %u)", i, a, i - 1,
+                    i ? table[3 * (size_t)(i - 1)] : 0);
+        if (S.empty() || S.back() != a >> 3) S.push_back(a >> 3);
+        rank[i] = (uint32_t)S.size() - 1;
+    }
+    ZKH_REQUIRE(S.size() == M, "image_proof_verify: M %u, but the table's rows lie in %zu leaves", M, S.size());
+    // the digests of the layer in hand, 16 words per item: the old one, then the new one
+    std::vector<uint32_t> cur(16 * (size_t)M), st;
+    for (size_t j = 0; j < M; j++) {
+        memcpy(&cur[16 * j], proof + l0 + 8 * j, 32);
+        memcpy(&cur[16 * j + 8], proof + l0 + 8 * j, 32);
+    }
+    for (uint32_t i = 0; i < D; i++) {
+        const uint32_t a = table[3 * (size_t)i], held = cur[16 * (size_t)rank[i] + (a & 7)];
+        ZKH_REQUIRE(held == table[3 * (size_t)i + 1], "image_proof_verify: row %u: in %u at address %u, but its leaf holds %u", i, table[3 * (size_t)i + 1], a, held);
+        cur[16 * (size_t)rank[i] + 8 + (a & 7)] = table[3 * (size_t)i + 2];
+    }
+    size_t at = s0;
+    for (uint32_t k = 0; k < h; k++) {
+        const size_t m = S.size();
+        uint32_t take = 0;
+        for (size_t j = 0; j < m; j++) take += !(S[j] & 1 ? j && S[j - 1] == S[j] - 1 : j + 1 < m && S[j + 1] == S[j] + 1);
+        ZKH_REQUIRE(take == c[k], "image_proof_verify: layer %u: %u siblings, but the walk takes %u", k, c[k], take);
+        std::vector<uint32_t> up;
+        st.clear();                                     // per parent two states of 24 words: (old left, old right, 0), (new left, new right, 0)
+        for (size_t j = 0; j < m; j++) {
+            const uint32_t x = S[j];
+            const bool pair = !(x & 1) && j + 1 < m && S[j + 1] == x + 1;
+            const uint32_t* left[2] = {&cur[16 * j], &cur[16 * j + 8]};
+            const uint32_t* right[2] = {left[0], left[1]};
+            if (pair) { right[0] = &cur[16 * (j + 1)]; right[1] = &cur[16 * (j + 1) + 8]; }
+            else if (x & 1) { left[0] = left[1] = proof + at; at += 8; }
+            else { right[0] = right[1] = proof + at; at += 8; }
+            for (int v = 0; v < 2; v++) {
+                st.insert(st.end(), left[v], left[v] + 8);
+                st.insert(st.end(), right[v], right[v] + 8);
+                st.insert(st.end(), 8, 0u);
+            }
+            up.push_back(x >> 1);
+            j += pair;
+        }
+        ZKH_TRY(zkh_poseidon2_mix_host(nullptr, nullptr, st.data(), st.size() / 24));
+        cur.resize(16 * up.size());
+        for (size_t j = 0; j < up.size(); j++) {
+            memcpy(&cur[16 * j], &st[48 * j], 32);
+            memcpy(&cur[16 * j + 8], &st[48 * j + 24], 32);
+        }
+        S.swap(up);
+    }
+    ZKH_REQUIRE(!memcmp(cur.data(), root_before, 32), "image_proof_verify: the proof opens root %08x %08x %08x %08x %08x %08x %08x %08x, not root_before", cur[0], cur[1],
+                cur[2], cur[3], cur[4], cur[5], cur[6], cur[7]);
+    memcpy(root_after, &cur[8], 32);
+    return nullptr;
 }

@@ -26,4 +26,10 @@ const char* hash_fold_listed(zkh_ctx* c, zkh_buf* nodes, size_t width, const uin
 // increasing addresses below image->len; `nodes` becomes what zkh_image_commit writes for the new image.  D = 0: nothing is launched.
 const char* image_tree_update(zkh_ctx* c, const uint32_t* addrs, uint32_t D, const zkh_buf* image, zkh_buf* nodes);
 
+// image.hip: THE UPDATE'S PROOF (include/zkhal.h), after the proof's check pass: `addrs`, `in`, `out` are the page table's p_addr, p_in
+// and p_out columns (raw words), their rows [0, D) strictly increasing addresses below `image_words`, `nodes` the tree of the image
+// before the page-out (only read), `proof` at least zkh_image_proof_words(image_words, D) words.
+const char* image_proof_build(zkh_ctx* c, const uint32_t* addrs, const uint32_t* in, const uint32_t* out, uint32_t D, size_t image_words, const zkh_buf* nodes,
+                              zkh_buf* proof);
+
 }  // namespace zkh

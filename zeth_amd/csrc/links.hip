@@ -200,8 +200,10 @@ __global__ __launch_bounds__(LINK_THREADS) void k_links(const uint32_t* __restri
 // zkh_page_out's two passes over the active rows of the page table: kWrite = false reduces the lowest refused row into `bad` (under 0),
 // and the row with p_on = 1 that has none after it leaves its index in `last` (in a table that passes the rows with p_on = 1 are a prefix
 // [0, D): that is row D - 1, one lane, a plain store; no such row: `last` keeps its all ones, D = 0);
-// kWrite = true scatters p_out into the image (addresses checked distinct and inside: no word is written twice)
-template <bool kWrite>
+// kWrite = true scatters p_out into the image (addresses checked distinct and inside: no word is written twice).
+// kProof (zkh_page_out_proof's check pass): `image` is the LEAF LAYER of the image's tree, the residue of word a at image[a], and a row
+// that passes the three rules is refused when p_in % P is not that word.
+template <bool kWrite, bool kProof = false>
 __global__ __launch_bounds__(LINK_THREADS) void k_page_out(const uint32_t* __restrict__ data, const Pages* __restrict__ pg, uint32_t n, uint32_t A, uint32_t* image,
                                                            uint32_t W, unsigned long long* __restrict__ bad, uint32_t* __restrict__ last) {
     const uint32_t t = blockIdx.x * LINK_THREADS + threadIdx.x;
@@ -213,6 +215,7 @@ __global__ __launch_bounds__(LINK_THREADS) void k_page_out(const uint32_t* __res
         if (!kWrite) {
             bool ok = v == 0 || v == R1;
             if (v == R1) ok = a < W && (t == 0 || (on[t - 1] % P == R1 && canonical(addrs[t - 1]) < a));
+            if (kProof && ok && v == R1) ok = data[(size_t)pg->dst[PG_IN] * n + t] % P == image[a];
             if (!ok) mine = t;
             if (v == R1 && (t + 1 == A || on[t + 1] % P != R1)) *last = t;
         } else if (v == R1 && a < W) {
@@ -372,6 +375,27 @@ extern "C" const char* zkh_derive_links_paged(zkh_ctx* ctx, const zkh_circuit* c
 }
 
 namespace {
+// Which rule the refused row of the page table broke, as the reference names it: `who` and `tail` frame the text.  nodes: the proof's
+// check pass, whose fourth rule is that p_in is the word the tree holds.
+const char* page_refusal(zkh_ctx* ctx, const char* who, const char* tail, const Pages& g, const zkh_buf* data, size_t n, uint32_t row, uint32_t W, const zkh_buf* nodes) {
+    uint32_t on, a, pon = 1, pa = 0;
+    ZKH_TRY(read_cell(ctx, data, data, GROUP_DATA, g.dst[PG_ON], n, row, &on));
+    ZKH_TRY(read_cell(ctx, data, data, GROUP_DATA, g.dst[PG_ADDR], n, row, &a));
+    if (on > 1) return make_err("%s: record %u at row %u: p_on %u, not 0 or 1%s", who, g.index, row, on, tail);
+    if (a >= W) return make_err("%s: record %u at row %u: address %u outside the image of %u words%s", who, g.index, row, a, W, tail);
+    if (row) {
+        ZKH_TRY(read_cell(ctx, data, data, GROUP_DATA, g.dst[PG_ON], n, row - 1, &pon));
+        ZKH_TRY(read_cell(ctx, data, data, GROUP_DATA, g.dst[PG_ADDR], n, row - 1, &pa));
+    }
+    if (!nodes || (row && (pon != 1 || pa >= a)))
+        return make_err("%s: record %u at row %u: page address %u does not follow a smaller one (row %u: p_on %u, address %u)%s", who, g.index, row, a, row - 1, pon, pa,
+                        tail);
+    uint32_t in, held;
+    ZKH_TRY(read_cell(ctx, data, data, GROUP_DATA, g.dst[PG_IN], n, row, &in));
+    ZKH_TRY(zkh_read(ctx, nodes, &held, nodes->len / 2 + a, 1));
+    return make_err("%s: record %u at row %u: p_in %u at address %u, the tree holds %u%s", who, g.index, row, in, a, canonical(held), tail);
+}
+
 // zkh_page_out (nodes = NULL) and zkh_page_out_tree: the check pass, one read-back (the refused row; D), the scatter, and with `nodes`
 // the update of the image's tree (image.hip) over the table's D addresses
 const char* page_out(zkh_ctx* ctx, const zkh_circuit* c, size_t po2, size_t zk_cycles, const zkh_buf* data, zkh_buf* image, zkh_buf* nodes) {
@@ -397,20 +421,7 @@ const char* page_out(zkh_ctx* ctx, const zkh_circuit* c, size_t po2, size_t zk_c
         ZKH_TRY(last_launch_error("page_out_check"));
     }
     ZKH_TRY(bad.read(ctx));
-    if (bad.found) {
-        const uint32_t row = bad.lo;
-        uint32_t on, a, pon = 1, pa = 0;
-        ZKH_TRY(read_cell(ctx, data, data, GROUP_DATA, g.dst[PG_ON], n, row, &on));
-        ZKH_TRY(read_cell(ctx, data, data, GROUP_DATA, g.dst[PG_ADDR], n, row, &a));
-        if (on > 1) return make_err("page_out: record %u at row %u: p_on %u, not 0 or 1: the image is unchanged", g.index, row, on);
-        if (a >= W) return make_err("page_out: record %u at row %u: address %u outside the image of %u words: the image is unchanged", g.index, row, a, W);
-        if (row) {
-            ZKH_TRY(read_cell(ctx, data, data, GROUP_DATA, g.dst[PG_ON], n, row - 1, &pon));
-            ZKH_TRY(read_cell(ctx, data, data, GROUP_DATA, g.dst[PG_ADDR], n, row - 1, &pa));
-        }
-        return make_err("page_out: record %u at row %u: page address %u does not follow a smaller one (row %u: p_on %u, address %u): the image is unchanged", g.index, row,
-                        a, row - 1, pon, pa);
-    }
+    if (bad.found) return page_refusal(ctx, "page_out", ": the image is unchanged", g, data, n, bad.lo, W, nullptr);
     {
         ProfScope prof(ctx, "page_out_write", 16.0 * A);
         k_page_out<true><<<nb, LINK_THREADS, 0, ctx->stream>>>(data->ptr(), (const Pages*)dpages->ptr(), (uint32_t)n, A, image->ptr(), W, bad.ptr(), bad.extra_ptr());
@@ -421,7 +432,48 @@ const char* page_out(zkh_ctx* ctx, const zkh_circuit* c, size_t po2, size_t zk_c
     ZKH_REQUIRE(D <= A, "page_out: the check pass left %u pages on %u active rows", D, A);
     return image_tree_update(ctx, data->ptr() + (size_t)g.dst[PG_ADDR] * n, D, image, nodes);
 }
+
+// zkh_page_out_proof: the check pass with the fourth rule, one read-back (the refused row; D), then the proof from `nodes` (image.hip)
+const char* page_out_proof(zkh_ctx* ctx, const zkh_circuit* c, size_t po2, size_t zk_cycles, const zkh_buf* data, const zkh_buf* image, const zkh_buf* nodes,
+                           zkh_buf* proof) {
+    ZKH_REQUIRE(zkh_circuit_pages(c), "page_out_proof: the circuit's arguments hold no PAGES record (ZKA1 version 7)");
+    size_t n;
+    uint32_t A;
+    ZKH_TRY(trace_rows("page_out_proof", c, po2, zk_cycles, nullptr, data, nullptr, &n, &A));
+    ZKH_REQUIRE(image->len <= 0xffffffffull, "page_out_proof: an image of %zu words (at most 2^32 - 1)", image->len);
+    ZKH_REQUIRE(image->len && nodes->len == zkh_image_tree_words(image->len), "page_out_proof: nodes of %zu words; an image of %zu words has a tree of %zu (zkh_image_tree_words)",
+                nodes->len, image->len, zkh_image_tree_words(image->len));
+    const Pages& g = c->args->pages[0];
+    const uint32_t W = (uint32_t)image->len;
+    bind_thread(ctx);
+    Tmp dpages;
+    BadRow bad;
+    ZKH_TRY(zkh_copy_from(ctx, "pages_record", (const uint32_t*)&g, sizeof(Pages) / 4, dpages.out()));
+    ZKH_TRY(bad.init(ctx));
+    const uint32_t nb = (A + LINK_THREADS - 1) / LINK_THREADS;
+    {
+        ProfScope prof(ctx, "page_out_check", 16.0 * A);            // p_on and p_addr; p_in and the tree's word
+        k_page_out<false, true><<<nb, LINK_THREADS, 0, ctx->stream>>>(data->ptr(), (const Pages*)dpages->ptr(), (uint32_t)n, A, nodes->ptr() + nodes->len / 2, W, bad.ptr(),
+                                                                      bad.extra_ptr());
+        ZKH_TRY(last_launch_error("page_out_check"));
+    }
+    ZKH_TRY(bad.read(ctx));
+    if (bad.found) return page_refusal(ctx, "page_out_proof", "", g, data, n, bad.lo, W, nodes);
+    const uint32_t D = bad.extra + 1;                   // as in page_out: the table's rows are [0, D)
+    ZKH_REQUIRE(D <= A, "page_out_proof: the check pass left %u pages on %u active rows", D, A);
+    const size_t bound = zkh_image_proof_words(W, D);
+    ZKH_REQUIRE(proof->len >= bound && bound <= 0xffffffffull, "page_out_proof: a proof buffer of %zu words; %u pages over an image of %u words take up to %zu (zkh_image_proof_words)",
+                proof->len, D, W, bound);
+    const uint32_t* cols = data->ptr();
+    return image_proof_build(ctx, cols + (size_t)g.dst[PG_ADDR] * n, cols + (size_t)g.dst[PG_IN] * n, cols + (size_t)g.dst[PG_OUT] * n, D, image->len, nodes, proof);
+}
 }  // namespace
+
+extern "C" const char* zkh_page_out_proof(zkh_ctx* ctx, const zkh_circuit* c, size_t po2, size_t zk_cycles, const zkh_buf* data, const zkh_buf* image,
+                                          const zkh_buf* nodes, zkh_buf* proof) {
+    ZKH_REQUIRE(ctx && c && data && image && nodes && proof, "page_out_proof: null argument");
+    return page_out_proof(ctx, c, po2, zk_cycles, data, image, nodes, proof);
+}
 
 extern "C" const char* zkh_page_out(zkh_ctx* ctx, const zkh_circuit* c, size_t po2, size_t zk_cycles, const zkh_buf* data, zkh_buf* image) {
     ZKH_REQUIRE(ctx && c && data && image, "page_out: null argument");

@@ -187,6 +187,9 @@ ABI = {
     "zkh_image_tree_words": (_sz, [_sz]),
     "zkh_image_commit": (_err, [_vp, _vp, _vp]),
     "zkh_page_out_tree": (_err, [_vp, _vp, _sz, _sz, _vp, _vp, _vp]),
+    "zkh_image_proof_words": (_sz, [_sz, _sz]),
+    "zkh_page_out_proof": (_err, [_vp, _vp, _sz, _sz, _vp, _vp, _vp, _vp]),
+    "zkh_image_proof_verify": (_err, [_u32p, _sz, _u32p, _u32p]),
     "zkh_circuit_derived_data_columns": (_err, [_vp, _u32p, _sz, C.POINTER(_sz)]),
     "zkh_upload_data_trace": (_err, [_vp, _vp, _sz, _sz, _vp, _u32p, _i]),
     "zkh_ctx_h2d_bytes": (_sz, [_vp]),
@@ -288,6 +291,18 @@ def _u32(a) -> np.ndarray:
 
 def _ptr(a: np.ndarray):
     return a.ctypes.data_as(_u32p)
+
+
+def image_proof_verify(proof, root_before) -> np.ndarray:
+    """root_after from a ZKU1 proof (HipHal.page_out_proof) and root_before, on the host alone: no HipHal, no GPU
+    (zkh_image_proof_verify; include/zkhal.h "THE UPDATE'S PROOF"; the numpy twin is logup.check_page_out_proof).  Raises HalError with
+    one message per cause; nothing is returned then"""
+    lib = load_library()
+    words, before, after = _u32(proof).reshape(-1), _u32(root_before).reshape(-1), np.empty(DIGEST_WORDS, dtype=np.uint32)
+    if before.size != DIGEST_WORDS:
+        raise HalError(f"image_proof_verify: root_before of {before.size} words")
+    _check(lib.zkh_image_proof_verify(_ptr(words), words.size, _ptr(before), _ptr(after)))
+    return after
 
 
 class Buffer:
@@ -877,6 +892,24 @@ class HipHal:
         of the paged words again (zkh_page_out_tree): afterwards `nodes` is, word for word, what image_commit gives for the new image.
         Raises HalError as page_out does, and on a `nodes` that is not image_tree_words(W) words; image and nodes are then unchanged"""
         _check(_lib.zkh_page_out_tree(self.ctx, circuit.h, po2, zk_cycles, data.h, image.h, nodes.h))
+
+    def image_proof_words(self, image_words: int, pages: int) -> int:
+        """the bound on the words of a ZKU1 proof of `pages` pages over an image of `image_words` words (zkh_image_proof_words)"""
+        return int(_lib.zkh_image_proof_words(image_words, pages))
+
+    def page_out_proof(self, circuit: Circuit, po2: int, zk_cycles: int, data: Buffer, image: Buffer, nodes: Buffer, proof: Optional[Buffer] = None) -> np.ndarray:
+        """the ZKU1 proof of the page-out of `data`'s page table (zkh_page_out_proof; include/zkhal.h "THE UPDATE'S PROOF"): what takes a
+        holder of the root of `nodes` to the root after the page-out (`image_proof_verify`).  Only reads data, image and nodes, `nodes`
+        the committed tree of `image` as it is: call it before page_out_tree.  proof: a Buffer to build it in (default: a new one of
+        image_proof_words(W, the active rows) words).  Returns exactly the proof's words.  Raises HalError as page_out does, when a
+        p_in is not the word the tree holds, and on a `nodes` or `proof` of the wrong size"""
+        if proof is None:
+            proof = self.alloc("image_proof", self.image_proof_words(image.size(), (1 << po2) - zk_cycles))
+        _check(_lib.zkh_page_out_proof(self.ctx, circuit.h, po2, zk_cycles, data.h, image.h, nodes.h, proof.h))
+        h = proof.get_at(4)
+        header = proof.slice(0, 5 + h).to_vec()
+        words = 5 + h + 3 * int(header[2]) + 8 * int(header[3]) + 8 * int(header[5:].astype(np.uint64).sum())
+        return proof.slice(0, words).to_vec()
 
     def image_root(self, nodes: Buffer) -> np.ndarray:
         """the root of a committed tree: digest 1 of `nodes`, 8 words"""

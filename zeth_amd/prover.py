@@ -318,15 +318,21 @@ class SegmentProver:
             self.page_out(seg, data, image, tree=tree)
         return receipt
 
-    def page_out(self, seg: Segment, data, image, tree=None) -> None:
+    def page_out(self, seg: Segment, data, image, tree=None, proof: bool = False):
         """write the page table of the segment's derived data trace (a device Buffer) back into the memory image: image[p_addr] = p_out
         on the rows with p_on = 1 (zkh_page_out).  A call of its own, after the seal: a refused witness never touches the image.
         tree: the image's committed tree (hal.image_commit of the image as it is now), brought up to the new image in the same call
-        (zkh_page_out_tree): its root is the commitment the next segment starts from."""
+        (zkh_page_out_tree): its root is the commitment the next segment starts from.
+        proof: with a tree, build the update's ZKU1 proof first (zkh_page_out_proof, from the tree as it is) and return its words:
+        hal.image_proof_verify(proof, the old root) gives the new root without the image.  Otherwise None is returned."""
+        if proof and tree is None:
+            raise _hal.HalError("page_out: proof=True needs the image's committed tree (tree=hal.image_commit(image))")
         if tree is None:
             self.hal.page_out(self.circuit, seg.po2, seg.zk_cycles, data, image)
-        else:
-            self.hal.page_out_tree(self.circuit, seg.po2, seg.zk_cycles, data, image, tree)
+            return None
+        words = self.hal.page_out_proof(self.circuit, seg.po2, seg.zk_cycles, data, image, tree) if proof else None
+        self.hal.page_out_tree(self.circuit, seg.po2, seg.zk_cycles, data, image, tree)
+        return words
 
     def prove_segment(self, seg: Segment) -> SegmentReceipt:
         code, data, out = self.witgen(seg)
