@@ -416,11 +416,24 @@ const char* zkh_page_out_tree(zkh_ctx*, const zkh_circuit*, size_t po2, size_t z
  * It FAILS with one message per cause, naming what and where: bad magic; an h that is not W's; a length other than what the header
  * describes; a word >= P (its offset); row i whose address does not follow a smaller one or lies outside the image; an M other than the
  * table's; row i whose `in` differs from its leaf's word; layer k with more or fewer siblings than the walk takes; "the proof opens root
- * .., not root_before".  root_after is written only on success. */
+ * .., not root_before".  root_after is written only on success.
+ * zkh_image_proof_walk is the same walk ON THE DEVICE, for a rank that has a GPU but not the image, and for the prover checking the
+ * proof it is about to ship: `proof` is a device buffer whose first `words` words are the proof (words <= the buffer's size, words <=
+ * 2^32 - 1: refused before anything is read; the rest of the buffer is never read, so the buffer zkh_page_out_proof wrote goes in as it
+ * is with the proof's own length).  `proof` is only read; root_before and root_after are host pointers.  For every (proof, root_before)
+ * the call and zkh_image_proof_verify either both succeed with the same root_after or both fail with the same message after
+ * "image_proof_walk: " / "image_proof_verify: ", the cause reported being the first in the host verifier's order when several apply.
+ * One read-back fetches the header (5 + h words, at most 34), which is checked against the length by the code zkh_image_proof_verify
+ * uses; everything after it is enqueued without synchronisation (per layer: the two flags of every item, one counter scan, the
+ * parents, one Poseidon2 lane per hash_pair); one read-back fetches a 32-word record: the lowest index of every cause (atomicMin:
+ * the result does not depend on arrival order; there are no other atomics), the values its message prints, both top digests.  No
+ * kernel reads a proof word at or past `words` whatever the proof holds: a stage does nothing when an earlier refusal removes its
+ * precondition.  Scratch comes from the context's pool, a small multiple of the proof's own size.  D = 0 launches nothing. */
 size_t zkh_image_proof_words(size_t image_words, size_t pages);
 const char* zkh_page_out_proof(zkh_ctx*, const zkh_circuit*, size_t po2, size_t zk_cycles, const zkh_buf* data, const zkh_buf* image, const zkh_buf* nodes,
                                zkh_buf* proof);
 const char* zkh_image_proof_verify(const uint32_t* proof, size_t words, const uint32_t root_before[8], uint32_t root_after[8]);
+const char* zkh_image_proof_walk(zkh_ctx*, const zkh_buf* proof, size_t words, const uint32_t root_before[8], uint32_t root_after[8]);
 /* Everything a circuit's arguments derive, in the one order in which it is sound: sorted copies, then columns, then links, then
  * multiplicities (a LIMBS / ORDER record may read a sorted copy's column, and the multiplicities count the limbs that the records and
  * the links derive).  Call it after the data upload and before zkh_prove_begin: what it writes belongs to the data group.  It runs

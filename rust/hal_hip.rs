@@ -459,6 +459,15 @@ impl HipCircuitHal {
         after
     }
 
+    /// The same walk on the device (`zkh_image_proof_walk`): the first `words` words of the device buffer `proof` are the ZKU1 proof
+    /// (the buffer `page_out_proof` wrote goes in as it is, with the proof's own length); the buffer is only read.  The same root, and
+    /// the same message per cause, as `image_proof_verify` gives on the host.
+    pub fn image_proof_walk(&self, proof: &HipBuffer<u32>, words: usize, root_before: &[u32; 8]) -> [u32; 8] {
+        let mut after = [0u32; 8];
+        ffi(|| unsafe { sys::zkh_image_proof_walk(self.hal.ctx.0, proof.raw, words, root_before.as_ptr(), after.as_mut_ptr()) });
+        after
+    }
+
     /// Check the raw traces against the circuit's own constraints on every row of `rows` (`zkh_check_rows`): which constraint a
     /// witness breaks, and where, before a seal is spent on it.  `out` and `mix` are the global words.  `row < 0`: no row of the window
     /// fails; otherwise the lowest failing row, its lowest failing `and_eqz` step (an index into the ZKC1 step list), how many rows of

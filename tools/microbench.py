@@ -12,8 +12,9 @@ under its version-7 blob next to zkh_derive_links under the version-6 blob on th
 same bytes, alternating; M18: the committed image, zkh_page_out_tree (the page-out with the incremental update of the image's Merkle
 tree) next to zkh_page_out followed by zkh_image_commit (the full rebuild), for the derive's own page table, a hand-made table of as many
 pages spread over the whole image and a sparse one of 4096 pages, at two image sizes, alternating; M19: the update's proof,
-zkh_page_out_proof next to zkh_page_out_tree on M18's tables and image sizes, alternating, with the proof's size) on one
-MI355X, through the C ABI (HipHal).
+zkh_page_out_proof next to zkh_page_out_tree on M18's tables and image sizes, alternating, with the proof's size; M20: the walk of
+that proof on the device, zkh_image_proof_walk next to the host walk of the downloaded proof (zkh_image_proof_verify), the download and
+zkh_page_out_tree, alternating, with the number of permutations) on one MI355X, through the C ABI (HipHal).
 
 Each line of output is one JSON object: the op, its shape, the average wall time of one call (stream drained on both
 sides of `reps` back-to-back calls), its ALGORITHMIC bytes (SURVEY.md §8a "B_alg": inputs read once + outputs written
@@ -798,6 +799,99 @@ def main() -> None:
                                   "bound_bytes": 4 * hal.image_proof_words(W, D), "walked_on_the_host": walked, "runs": runs, "reps": args.reps,
                                   **{k: spread(v) for k, v in t.items()}, "steps": steps,
                                   "proof_vs_tree": round(med["page_out_proof"] / med["page_out_tree"], 3)}), flush=True)
+                del images, nodes, buf
+        del data
+    if want("M20"):
+        # the walk of the update's proof on the device: zkh_image_proof_walk on the buffer zkh_page_out_proof wrote (through the C ABI,
+        # the proof's own length) next to its yardstick, zkh_image_proof_verify on the downloaded proof (the parent's host walk), the
+        # download timed on its own, and next to zkh_page_out_tree (the update of the same paths: one permutation per dirty node where
+        # the walk runs two).  M18 / M19's setup: SYN-LOOKUP-paged FULL, the tables `derive`, `spread` and `sparse`, 2^20 and 2^26 image
+        # words.  Timed in alternation, `runs` windows of `reps` calls of the device calls and ONE host walk per window; median and
+        # spread (min, max) of the windows; then the walk's stages by their events.  Every layer of the walk is its own four launches
+        # (the narrow-layer variant that was built); permutations = 2 sum |S_{k+1}|, from the proof's counts.
+        from zeth_amd import hal as zhal
+        from zeth_amd.circuits import logup, syn_lookup
+        runs, zk = 7, 1994
+        A = n - zk
+        shape = syn_lookup.FULL
+        desc, blob = syn_lookup.build_syn_lookup(shape, link=True, reads=True, pages=True)
+        pargs = logup.Arguments.parse(blob)
+        pg = pargs.pages
+        code_h, full_h, _out = syn_lookup.witness(shape, args.po2, zk, seed=17, link=True, reads=True, pages=True, image=np.zeros(1 << 20, dtype=np.uint32))
+        paged = hal.load_circuit(desc, jit=False)
+        paged.set_arguments(blob)
+        full = full_h.reshape(-1, n)
+        pages = int((full[pg.p_on, :A] != 0).sum())
+        one = np.uint32((1 << 32) % P)
+        rinv = pow(int(one), -1, P)
+        enc = lambda x: (np.asarray(x, dtype=np.uint64) * np.uint64(one) % np.uint64(P)).astype(np.uint32)   # noqa: E731
+        spread = lambda ts: {"median_ms": round(float(np.median(ts)) * 1e3, 4), "min_ms": round(min(ts) * 1e3, 4), "max_ms": round(max(ts) * 1e3, 4)}   # noqa: E731
+        data = hal.alloc_elem("m20d", full_h.size)
+        u32p = zhal._u32p
+        for W in (1 << 20, 1 << 26):
+            for table in ("derive", "spread", "sparse"):
+                image_h = rand_fp(rng, W)
+                hand = full.copy() if table == "derive" else np.zeros_like(full)
+                if table == "derive":
+                    D = pages
+                    addrs = (hand[pg.p_addr, :D].astype(np.uint64) * np.uint64(rinv) % np.uint64(P)).astype(np.int64)
+                else:
+                    D = pages if table == "spread" else 4096
+                    hand[pg.p_on, :D], hand[pg.p_out, :D] = one, rand_fp(rng, D)
+                    if W <= 1 << 22:
+                        addrs = rng.choice(W, D, replace=False)
+                    else:
+                        addrs = np.unique(rng.integers(0, W, D + D // 8))
+                        addrs = addrs[rng.choice(addrs.size, D, replace=False)]
+                    addrs = np.sort(addrs).astype(np.int64)
+                    hand[pg.p_addr, :D] = enc(addrs)
+                hand[pg.p_in, :D] = image_h[addrs]
+                data.write(hand.reshape(-1))
+                del hand
+                images = [hal.alloc_elem("m20i", W) for _ in range(2)]
+                for im in images:
+                    im.write(image_h)
+                nodes = [hal.image_commit(im) for im in images]
+                root0 = hal.image_root(nodes[0])
+                buf = hal.alloc("m20p", hal.image_proof_words(W, A))
+                words = hal.page_out_proof(paged, args.po2, zk, data, images[0], nodes[0], proof=buf)
+                tree_fn = lambda: hal.page_out_tree(paged, args.po2, zk, data, images[1], nodes[1])            # noqa: E731
+                tree_fn()
+                root1 = hal.image_root(nodes[1])
+                after = np.empty(8, dtype=np.uint32)
+                walk_fn = lambda: zhal._check(zhal._lib.zkh_image_proof_walk(hal.ctx, buf.h, words.size, root0.ctypes.data_as(u32p), after.ctypes.data_as(u32p)))   # noqa: E731
+                walk_fn()
+                assert np.array_equal(after, root1), "the walk does not reach the root the update leaves"
+                host = np.empty(words.size, dtype=np.uint32)
+                down_fn = lambda: zhal._check(zhal._lib.zkh_read(hal.ctx, buf.h, host.ctypes.data_as(u32p), 0, host.size))      # noqa: E731
+                t = {"image_proof_walk": [], "page_out_tree": [], "download": [], "image_proof_verify": []}
+                for _ in range(runs):
+                    for name, fn in (("image_proof_walk", walk_fn), ("page_out_tree", tree_fn), ("download", down_fn)):
+                        t[name].append(timed(hal, fn, args.reps))
+                    t0 = time.perf_counter()
+                    assert np.array_equal(zhal.image_proof_verify(host, root0), root1)
+                    t["image_proof_verify"].append(time.perf_counter() - t0)
+                hal.prof_enable(True)
+                hal.prof_reset()
+                for _ in range(args.reps):
+                    walk_fn()
+                hal.sync()
+                steps = {r["name"]: {"calls_per_call": r["calls"] // args.reps, "ms_per_call": round(r["total_ms"] / args.reps, 4)} for r in hal.prof_get()
+                         if r["calls"] and r["name"].startswith("walk_")}
+                hal.prof_enable(False)
+                assert np.array_equal(buf.slice(0, words.size).to_vec(), words)
+                h = int(words[4])
+                items, perms = int(words[3]), 0
+                for k in range(h):                                           # |S_{k+1}| = c_k + (|S_k| - c_k) / 2
+                    items = int(words[5 + k]) + (items - int(words[5 + k])) // 2
+                    perms += 2 * items
+                med = {k: float(np.median(v)) for k, v in t.items()}
+                print(json.dumps({"bench": "M20", "circuit": "SYN-LOOKUP-paged FULL", "library": os.path.basename(os.environ.get("ZKH_LIBRARY", "") or "libzkhal_mi355x.so"),
+                                  "po2": args.po2, "table": table, "pages": D, "image_words": W, "leaves": logup.image_tree_leaves(W), "layers": h,
+                                  "dirty_leaves": int(words[3]), "proof_bytes": 4 * int(words.size), "permutations": perms, "narrow_layers": "one launch set per layer",
+                                  "runs": runs, "reps": args.reps, **{k: spread(v) for k, v in t.items()}, "steps": steps,
+                                  "walk_vs_download_and_host_walk": round(med["image_proof_walk"] / (med["download"] + med["image_proof_verify"]), 5),
+                                  "walk_vs_tree": round(med["image_proof_walk"] / med["page_out_tree"], 3)}), flush=True)
                 del images, nodes, buf
         del data
     hal.close()

@@ -115,6 +115,11 @@ THE UPDATE'S PROOF, ZKU1 (`reference_page_out_proof`, `check_page_out_proof`; zk
 full: include/zkhal.h): the page table's (address, in, out) rows, the old leaves they touch and the clean sibling digests of every layer,
 from which root_before and root_after both follow by one hash_pair per dirty node: who holds root_before and the proof reaches
 root_after without the image.
+THE WALK has two homes with one verdict: zkh_image_proof_verify on the host (`check_page_out_proof` is its numpy twin) and
+zkh_image_proof_walk on the device, from the buffer zkh_page_out_proof wrote and the proof's own length (HipHal.image_proof_walk;
+SegmentProver.page_out(..., proof=True, walk=True) checks the proof it returns against the tree's root after the page-out).  For every
+(proof, root_before) both succeed with the same root_after or fail with the same message after their prefixes; the host verifier's
+order of causes decides when several apply, and this module's `check_page_out_proof` states that order.
 Left out: no circuit checks p_in / p_out against those roots yet (the in-circuit path check consumes exactly this proof's digests) and
 they are not in `out`, sessions do not thread an image, and a blob pages one memory of one value word per address.
 

@@ -97,6 +97,35 @@ __global__ __launch_bounds__(256, 4) void k_hash_fold_list(uint32_t* __restrict_
     if (t >= *count) return;
     fold_one(io, 2 * width, width, list[t], rc, diag);
 }
+// The walk of a ZKU1 proof (image.hip, zkh_image_proof_walk): layer k's parents [0, *count), TWO lanes per parent, lane parity 0 the
+// hash_pair of the old children, 1 of the new ones, so a lane holds one permutation as in k_hash_fold.  Parent r's first child is item
+// from[r] of the layer's list, its digests at cur[16 item, +16) (old, new); the other child is the item after it (sib[r] = NONE), or the
+// clean sibling at rank sib[r] of the proof's section C_k (word *off; word aligned), the same for old and new, on the left when the
+// item's index is odd.  The parent's digests go to next[16 r, +16).  Lanes past the count leave: a refusal leaves a count of 0.
+__global__ __launch_bounds__(256, 4) void k_hash_walk(const uint32_t* __restrict__ list, const uint32_t* __restrict__ from, const uint32_t* __restrict__ sib,
+                                                   const uint32_t* __restrict__ count, const uint32_t* __restrict__ proof, const uint32_t* __restrict__ off,
+                                                   const uint32_t* __restrict__ cur, uint32_t* __restrict__ next, const uint32_t* __restrict__ rc,
+                                                   const uint32_t* __restrict__ diag) {
+    const uint32_t lane = blockIdx.x * blockDim.x + threadIdx.x, r = lane >> 1, v = lane & 1;
+    if (r >= *count) return;
+    const uint32_t item = from[r], clean = sib[r];
+    const uint32_t* mine = cur + 16 * (size_t)item + 8 * v;
+    const uint32_t* other = clean == 0xffffffffu ? mine + 16 : proof + *off + 8 * (size_t)clean;
+    const bool odd = clean != 0xffffffffu && (list[item] & 1);
+    const uint32_t* left = odd ? other : mine;
+    const uint32_t* right = odd ? mine : other;
+    uint32_t s[CELLS];
+#pragma unroll
+    for (int k = 0; k < 8; k++) { s[k] = left[k]; s[8 + k] = right[k]; }
+#pragma unroll
+    for (int k = RATE; k < CELLS; k++) s[k] = 0;
+    poseidon2_mix_raw<0, OUT, RATE>(s, rc, diag);             // as fold_one: the zero capacity is not fed through the first M_ext
+#pragma unroll
+    for (int k = 0; k < OUT; k++) s[k] = p2_finish(s[k]);
+    uint4* o = (uint4*)(next + 16 * (size_t)r + 8 * v);
+    o[0] = make_uint4(s[0], s[1], s[2], s[3]);
+    o[1] = make_uint4(s[4], s[5], s[6], s[7]);
+}
 
 // ---------------------------------------------------------------------------------------------------------
 // Wavefront-cooperative permutation for the narrow layers of a tree.  With one lane per permutation a layer
@@ -246,4 +275,11 @@ const char* zkh::hash_fold_listed(zkh_ctx* c, zkh_buf* nodes, size_t width, cons
     ProfScope prof(c, "image_sparse", 100.0 * bound);
     k_hash_fold_list<<<(bound + 255) / 256, 256, 0, c->stream>>>(nodes->ptr(), width, list, count, c->tab.rc, c->tab.diag);
     return last_launch_error("image_sparse");
+}
+const char* zkh::hash_walk_layer(zkh_ctx* c, const uint32_t* list, const uint32_t* from, const uint32_t* sib, const uint32_t* count, const uint32_t* proof,
+                                 const uint32_t* off, const uint32_t* cur, uint32_t* next, uint32_t bound) {
+    ZKH_REQUIRE(bound && bound <= 0x7fffffffu, "hash_walk_layer: %u parents", bound);
+    ProfScope prof(c, "walk_hash", 200.0 * bound);
+    k_hash_walk<<<(unsigned)((2 * (size_t)bound + 255) / 256), 256, 0, c->stream>>>(list, from, sib, count, proof, off, cur, next, c->tab.rc, c->tab.diag);
+    return last_launch_error("walk_hash");
 }

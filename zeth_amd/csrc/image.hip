@@ -376,28 +376,65 @@ extern "C" size_t zkh_image_proof_words(size_t image_words, size_t pages) {
     return words;
 }
 
+// ---- THE UPDATE'S PROOF, WALKED (zkh_image_proof_verify on the host, zkh_image_proof_walk on the device) ----
+// One source for every refusal of the two walks: `who` is the call's name, the text after it is the same for both.
+namespace {
+
+const char* refuse_word(const char* who, size_t i, uint32_t v) { return make_err("%s: word %zu is %u, not below P", who, i, v); }
+const char* refuse_root_range(const char* who) { return make_err("%s: root_before is not 8 words below P", who); }
+const char* refuse_leaves(const char* who, uint32_t M, size_t leaves) { return make_err("%s: M %u, but the table's rows lie in %zu leaves", who, M, leaves); }
+const char* refuse_layer(const char* who, uint32_t k, uint32_t c, uint32_t take) { return make_err("%s: layer %u: %u siblings, but the walk takes %u", who, k, c, take); }
+const char* refuse_outside(const char* who, uint32_t i, uint32_t a, uint32_t W) { return make_err("%s: row %u: address %u outside the image of %u words", who, i, a, W); }
+const char* refuse_order(const char* who, uint32_t i, uint32_t a, uint32_t before) {
+    return make_err("%s: row %u: address %u does not follow a smaller one (row %u: address %u)", who, i, a, i - 1, before);
+}
+const char* refuse_in(const char* who, uint32_t i, uint32_t in, uint32_t a, uint32_t held) {
+    return make_err("%s: row %u: in %u at address %u, but its leaf holds %u", who, i, in, a, held);
+}
+const char* refuse_root(const char* who, const uint32_t* top) {
+    return make_err("%s: the proof opens root %08x %08x %08x %08x %08x %08x %08x %08x, not root_before", who, top[0], top[1], top[2], top[3], top[4], top[5], top[6], top[7]);
+}
+
+// The header against the length.  `head` holds the proof's first min(words, PROOF_HEADER + 29) words: enough, since the counts c_k are
+// read only once h has been found to be W's, and that is at most 29.
+const char* proof_header(const char* who, const uint32_t* head, size_t words) {
+    ZKH_REQUIRE(words >= PROOF_HEADER, "%s: a proof of %zu words: the header alone has %u", who, words, PROOF_HEADER);
+    const uint32_t W = head[1], D = head[2], M = head[3], h = head[4];
+    ZKH_REQUIRE(head[0] == PROOF_MAGIC, "%s: bad magic 0x%08x (ZKU1 is 0x%08x)", who, head[0], PROOF_MAGIC);
+    uint32_t hw = 0;
+    while (((size_t)1 << hw) < image_leaves(W)) hw++;
+    ZKH_REQUIRE(h == hw, "%s: h %u, but an image of %u words has h %u", who, h, W, hw);
+    ZKH_REQUIRE(words >= PROOF_HEADER + h, "%s: a proof of %zu words, but the header describes at least %u", who, words, PROOF_HEADER + h);
+    unsigned long long want = PROOF_HEADER + h + 3ull * D + 8ull * M;
+    for (uint32_t k = 0; k < h; k++) want += 8ull * head[PROOF_HEADER + k];
+    ZKH_REQUIRE(words == want, "%s: a proof of %zu words, but the header describes %llu", who, words, want);
+    return nullptr;
+}
+// D = 0 after the header, the words and root_before have passed: the header must describe nothing
+const char* proof_empty(const char* who, const uint32_t* head) {
+    if (head[3]) return refuse_leaves(who, head[3], 0);
+    for (uint32_t k = 0; k < head[4]; k++)
+        if (head[PROOF_HEADER + k]) return refuse_layer(who, k, head[PROOF_HEADER + k], 0);
+    return nullptr;
+}
+
+}  // namespace
+
 // The walk of include/zkhal.h "THE UPDATE'S PROOF" on the host: no context, no GPU; every layer is one batch through the permutation
 // zkh_poseidon2_mix_host uses, the old children first, the new ones after them.
 extern "C" const char* zkh_image_proof_verify(const uint32_t* proof, size_t words, const uint32_t root_before[8], uint32_t root_after[8]) {
-    ZKH_REQUIRE(proof && root_before && root_after, "image_proof_verify: null argument");
-    ZKH_REQUIRE(words >= PROOF_HEADER, "image_proof_verify: a proof of %zu words: the header alone has %u", words, PROOF_HEADER);
+    static const char who[] = "image_proof_verify";
+    ZKH_REQUIRE(proof && root_before && root_after, "%s: null argument", who);
+    ZKH_TRY(proof_header(who, proof, words));
     const uint32_t W = proof[1], D = proof[2], M = proof[3], h = proof[4];
-    ZKH_REQUIRE(proof[0] == PROOF_MAGIC, "image_proof_verify: bad magic 0x%08x (ZKU1 is 0x%08x)", proof[0], PROOF_MAGIC);
-    uint32_t hw = 0;
-    while (((size_t)1 << hw) < image_leaves(W)) hw++;
-    ZKH_REQUIRE(h == hw, "image_proof_verify: h %u, but an image of %u words has h %u", h, W, hw);
-    ZKH_REQUIRE(words >= PROOF_HEADER + h, "image_proof_verify: a proof of %zu words, but the header describes at least %u", words, PROOF_HEADER + h);
     const uint32_t* c = proof + PROOF_HEADER;
-    unsigned long long want = PROOF_HEADER + h + 3ull * D + 8ull * M;
-    for (uint32_t k = 0; k < h; k++) want += 8ull * c[k];
-    ZKH_REQUIRE(words == want, "image_proof_verify: a proof of %zu words, but the header describes %llu", words, want);
     const size_t t0 = PROOF_HEADER + h, l0 = t0 + 3 * (size_t)D, s0 = l0 + 8 * (size_t)M;
     for (size_t i = t0; i < words; i++)
-        ZKH_REQUIRE(proof[i] < P || (i < l0 && (i - t0) % 3 == 0), "image_proof_verify: word %zu is %u, not below P", i, proof[i]);
-    for (int j = 0; j < 8; j++) ZKH_REQUIRE(root_before[j] < P, "image_proof_verify: root_before is not 8 words below P");
+        if (!(proof[i] < P || (i < l0 && (i - t0) % 3 == 0))) return refuse_word(who, i, proof[i]);
+    for (int j = 0; j < 8; j++)
+        if (root_before[j] >= P) return refuse_root_range(who);
     if (!D) {
-        ZKH_REQUIRE(!M, "image_proof_verify: M %u, but the table's rows lie in 0 leaves", M);
-        for (uint32_t k = 0; k < h; k++) ZKH_REQUIRE(!c[k], "image_proof_verify: layer %u: %u siblings, but the walk takes 0", k, c[k]);
+        ZKH_TRY(proof_empty(who, proof));
         memmove(root_after, root_before, 32);
         return nullptr;
     }
@@ -405,13 +442,12 @@ extern "C" const char* zkh_image_proof_verify(const uint32_t* proof, size_t word
     std::vector<uint32_t> S, rank(D);                   // the dirty nodes of the layer in hand; every row's leaf among S_0
     for (uint32_t i = 0; i < D; i++) {
         const uint32_t a = table[3 * (size_t)i];
-        ZKH_REQUIRE(a < W, "image_proof_verify: row %u: address %u outside the image of %u words", i, a, W);
-        ZKH_REQUIRE(!i || table[3 * (size_t)(i - 1)] < a, "image_proof_verify: row %u: address %u does not follow a smaller one (row %u: address %u)", i, a, i - 1,
-                    i ? table[3 * (size_t)(i - 1)] : 0);
+        if (a >= W) return refuse_outside(who, i, a, W);
+        if (i && table[3 * (size_t)(i - 1)] >= a) return refuse_order(who, i, a, table[3 * (size_t)(i - 1)]);
         if (S.empty() || S.back() != a >> 3) S.push_back(a >> 3);
         rank[i] = (uint32_t)S.size() - 1;
     }
-    ZKH_REQUIRE(S.size() == M, "image_proof_verify: M %u, but the table's rows lie in %zu leaves", M, S.size());
+    if (S.size() != M) return refuse_leaves(who, M, S.size());
     // the digests of the layer in hand, 16 words per item: the old one, then the new one
     std::vector<uint32_t> cur(16 * (size_t)M), st;
     for (size_t j = 0; j < M; j++) {
@@ -420,7 +456,7 @@ extern "C" const char* zkh_image_proof_verify(const uint32_t* proof, size_t word
     }
     for (uint32_t i = 0; i < D; i++) {
         const uint32_t a = table[3 * (size_t)i], held = cur[16 * (size_t)rank[i] + (a & 7)];
-        ZKH_REQUIRE(held == table[3 * (size_t)i + 1], "image_proof_verify: row %u: in %u at address %u, but its leaf holds %u", i, table[3 * (size_t)i + 1], a, held);
+        if (held != table[3 * (size_t)i + 1]) return refuse_in(who, i, table[3 * (size_t)i + 1], a, held);
         cur[16 * (size_t)rank[i] + 8 + (a & 7)] = table[3 * (size_t)i + 2];
     }
     size_t at = s0;
@@ -428,7 +464,7 @@ extern "C" const char* zkh_image_proof_verify(const uint32_t* proof, size_t word
         const size_t m = S.size();
         uint32_t take = 0;
         for (size_t j = 0; j < m; j++) take += !(S[j] & 1 ? j && S[j - 1] == S[j] - 1 : j + 1 < m && S[j + 1] == S[j] + 1);
-        ZKH_REQUIRE(take == c[k], "image_proof_verify: layer %u: %u siblings, but the walk takes %u", k, c[k], take);
+        if (take != c[k]) return refuse_layer(who, k, c[k], take);
         std::vector<uint32_t> up;
         st.clear();                                     // per parent two states of 24 words: (old left, old right, 0), (new left, new right, 0)
         for (size_t j = 0; j < m; j++) {
@@ -455,8 +491,267 @@ extern "C" const char* zkh_image_proof_verify(const uint32_t* proof, size_t word
         }
         S.swap(up);
     }
-    ZKH_REQUIRE(!memcmp(cur.data(), root_before, 32), "image_proof_verify: the proof opens root %08x %08x %08x %08x %08x %08x %08x %08x, not root_before", cur[0], cur[1],
-                cur[2], cur[3], cur[4], cur[5], cur[6], cur[7]);
+    if (memcmp(cur.data(), root_before, 32)) return refuse_root(who, cur.data());
     memcpy(root_after, &cur[8], 32);
+    return nullptr;
+}
+
+// THE WALK ON THE DEVICE (zkh_image_proof_walk): what zkh_image_proof_verify computes, from a proof that sits in device memory.
+//
+// SAFETY AGAINST ANY INPUT.  The proof is hostile until shown otherwise, and nothing below may read a proof word at or past `words`,
+// or a scratch item past its count, whatever the proof holds.  The reasoning, stage by stage:
+//   header     : the host reads min(words, 5 + 29) words once and runs proof_header on them: after it, h is W's (<= 29),
+//                words = 5 + h + 3 D + 8 M + 8 sum c_k exactly, so the table [t0, l0), the leaves [l0, s0) and the siblings [s0, words) are
+//                sections of the proof, and 3 D + 8 M <= words: the scratch, sized by min(D, M, L), is a small multiple of the proof.
+//   walk_check : k_walk_range reads the words [t0, words), k_walk_rows the address words t0 + 3 i, i < D: inside the table.  They
+//                gate nothing and are gated by nothing; each leaves the LOWEST index it refuses (atomicMin), so the result does
+//                not depend on the order in which lanes arrive.  The counter scan leaves the number of distinct leaves in the record.
+//   walk_leaves: gated on what the launches BEFORE it left (a word >= P, a refused row, a count of leaves other than M).  No leaf is
+//                read before M has been found to be the table's count ON THE DEVICE: a rank is then below M and the leaf inside
+//                [l0, s0); with a wrong M a rank could run into the siblings or past the proof.  Lane 0 hands layer 0 its count: M, or
+//                0 when the gate is shut, so that every later stage has nothing to do.  The gate does not include the stage's own
+//                refusal (an `in` that differs): lanes that saw it early would leave, and the lowest row would depend on timing.
+//   walk_layer : k_proof_flags reads list[0, m), m the count the stage before left (<= the list's size by the above).  k_walk_parents
+//                is gated on every earlier refusal AND on the layer's taken-count being c_k; lane 0 hands the next layer |S_{k+1}|, or 0
+//                when the gate is shut.  hash.hip's k_hash_walk runs one lane per permutation of the parents below that count, so
+//                it does nothing after a refusal, and its sibling ranks are below take = c_k: the reads stay inside C_k's section,
+//                which ends at or before `words` because the length was what the header describes.  With take > c_k and no gate a
+//                lane would read past the section.
+//   walk_top   : copies the two top digests into the record only when the last count is 1, and the values a message prints (read at
+//                indices the check stages refused, which they had read themselves).
+// The only atomics are the atomicMin's on the record; every scratch word has one writer (a leaf's two digests: the lane of the leaf's
+// first row; a parent's digest: the lane of that permutation; lists and ranks: the head lanes, as in image_proof_build); a launch reads
+// what earlier launches wrote, in stream order.  Two calls give the same record.
+//
+// NARROW LAYERS.  Every layer is its own four launches (flags, the counter scan, parents, hash) whatever its list holds: the simplest
+// of the three candidates (one launch per layer; one workgroup walking the narrow layers with barriers; hash.hip's 8-lane permutation),
+// and the only one built.  No constant switches a code path but the workgroup size.  What it reads: DESIGN.md §2 ARGUMENTS, M20.
+namespace {
+
+// the result record, 32 words.  Two 64-bit keys (index << 32 | the value the message prints), then words.
+enum {
+    WR_RANGE = 0,       // 64 bits: the lowest word >= P and the word
+    WR_IN = 2,          // 64 bits: the lowest row whose `in` differs and what its leaf holds
+    WR_ROW = 4,         // the lowest refused row
+    WR_COUNT = 5,       // the distinct leaves of the table
+    WR_LAYER = 6, WR_LAYER_C = 7, WR_LAYER_TAKE = 8,    // the lowest layer whose taken-count is not c_k, c_k, the count
+    WR_ROW_A = 9, WR_ROW_BEFORE = 10,                   // the refused row's address and the one before it
+    WR_IN_IN = 11, WR_IN_A = 12,                        // that row's `in` and address
+    WR_TOP_ITEMS = 13,  // the items of the top layer (1 after a walk that went through)
+    WR_DIGESTS = 16,    // the old and the new top digest
+    WR_WORDS = 32
+};
+// per layer on the device: the items of S_k, the word where C_k starts, and the two totals of the layer's counter scan
+enum { WM_ITEMS = 0, WM_OFF = 1, WM_TAKE = 2, WM_HEADS = 3, WM_WORDS = 4 };
+static_assert(WM_ITEMS == PM_ITEMS, "k_proof_flags reads the layer's count at PM_ITEMS");
+
+__device__ __forceinline__ void lowest(unsigned long long* slot, uint32_t index, uint32_t value) {
+    const unsigned long long key = ((unsigned long long)index << 32) | value;
+    if (key < *(volatile unsigned long long*)slot) atomicMin(slot, key);       // entries only decrease
+}
+__device__ __forceinline__ bool clean64(const uint32_t* st, int at) { return (st[at] & st[at + 1]) == NONE; }
+
+// grid ceil((words - t0) / IMG_THREADS): every word of the table's in / out, of the leaves and of the siblings is below P
+__global__ __launch_bounds__(IMG_THREADS) void k_walk_range(const uint32_t* __restrict__ proof, size_t t0, size_t l0, size_t words, uint32_t* __restrict__ st) {
+    const size_t i = t0 + (size_t)blockIdx.x * IMG_THREADS + threadIdx.x;
+    if (i >= words) return;
+    const uint32_t v = proof[i];
+    if (v >= P && !(i < l0 && (i - t0) % 3 == 0)) lowest((unsigned long long*)(st + WR_RANGE), (uint32_t)i, v);
+}
+
+// grid ceil(D / IMG_THREADS) over the rows of the proof's table (stride 3, addresses as integers): the lowest row whose address lies
+// outside the image or does not follow a smaller one; and what k_image_heads<true, 3> leaves for a raw column: local[t] = the heads
+// (rows whose leaf differs from the row before's) of t's workgroup up to t, sums[1 + workgroup] its total.
+__global__ __launch_bounds__(IMG_THREADS) void k_walk_rows(const uint32_t* __restrict__ table, uint32_t D, uint32_t W, uint32_t* __restrict__ local,
+                                                           uint32_t* __restrict__ sums, uint32_t* __restrict__ st) {
+    __shared__ uint32_t buf[2][IMG_THREADS];
+    const uint32_t t = blockIdx.x * IMG_THREADS + threadIdx.x;
+    const uint32_t a = t < D ? table[3 * (size_t)t] : 0, before = t && t < D ? table[3 * (size_t)(t - 1)] : 0;
+    if (t < D && (a >= W || (t && before >= a))) atomicMin(st + WR_ROW, t);
+    const uint32_t head = t < D && (t == 0 || (before >> 3) != (a >> 3));
+    const uint32_t incl = block_scan<IMG_THREADS>(head, buf, AddWrap());
+    if (t < D) local[t] = incl;
+    if (threadIdx.x == IMG_THREADS - 1) sums[1 + blockIdx.x] = incl;
+}
+
+// grid ceil(D / IMG_THREADS), after the counter scan (st[WR_COUNT]).  The lane of a leaf's first row owns the leaf: its index to
+// list[rank], the old digest (the proof's leaf) and the new one (the rows' `out` put in) to dig[16 rank, +16), every `in` of the leaf's
+// rows (at most 8, consecutive) compared with the old word.  Lane 0 hands layer 0 its count and the siblings' first word.
+__global__ __launch_bounds__(IMG_THREADS) void k_walk_leaves(const uint32_t* __restrict__ proof, uint32_t t0, uint32_t D, uint32_t M, const uint32_t* __restrict__ local,
+                                                             const uint32_t* __restrict__ sums, uint32_t* __restrict__ st, uint32_t* __restrict__ list,
+                                                             uint32_t* __restrict__ dig, uint32_t* __restrict__ meta) {
+    const uint32_t t = blockIdx.x * IMG_THREADS + threadIdx.x;
+    const size_t l0 = (size_t)t0 + 3 * (size_t)D;
+    const bool ok = clean64(st, WR_RANGE) && st[WR_ROW] == NONE && st[WR_COUNT] == M;
+    if (t == 0) { meta[WM_ITEMS] = ok ? M : 0; meta[WM_OFF] = (uint32_t)(l0 + 8 * (size_t)M); }
+    if (t >= D || !ok) return;
+    const uint32_t* table = proof + t0;
+    const uint32_t leaf = table[3 * (size_t)t] >> 3;
+    if (t && (table[3 * (size_t)(t - 1)] >> 3) == leaf) return;
+    const uint32_t rank = local[t] + sums[1 + blockIdx.x] - 1;         // < M: the count is M
+    list[rank] = leaf;
+    const uint32_t* from = proof + l0 + 8 * (size_t)rank;
+    uint32_t o[8], n[8];
+#pragma unroll
+    for (int j = 0; j < 8; j++) o[j] = n[j] = from[j];
+    uint32_t bad = NONE, held = 0;
+    for (uint32_t u = t; u < D && u - t < 8; u++) {
+        const uint32_t* row = table + 3 * (size_t)u;
+        const uint32_t a = row[0];
+        if ((a >> 3) != leaf) break;
+        uint32_t was = 0;
+#pragma unroll
+        for (int j = 0; j < 8; j++)
+            if ((a & 7) == (uint32_t)j) { was = o[j]; n[j] = row[2]; }
+        if (was != row[1] && bad == NONE) { bad = u; held = was; }
+    }
+    if (bad != NONE) lowest((unsigned long long*)(st + WR_IN), bad, held);
+    uint4* d = (uint4*)(dig + 16 * (size_t)rank);
+    d[0] = make_uint4(o[0], o[1], o[2], o[3]); d[1] = make_uint4(o[4], o[5], o[6], o[7]);
+    d[2] = make_uint4(n[0], n[1], n[2], n[3]); d[3] = make_uint4(n[4], n[5], n[6], n[7]);
+}
+
+// grid ceil(bound / IMG_THREADS) over the items of S_k, after k_proof_flags and the counter scan over its two runs (meta[WM_TAKE], the
+// siblings the walk takes; meta[WM_HEADS] = |S_{k+1}|).  Gated on every earlier refusal and on take = c_k.  A head writes, at its
+// parent's rank: the parent's index (next), its own item (from) and the rank of the clean sibling it takes, NONE when it pairs with
+// the item after it (sib).  Lane 0 hands the next layer its count (0: the gate is shut) and the word where C_{k+1} starts, and records
+// the layer when its count is the first that differs.
+__global__ __launch_bounds__(IMG_THREADS) void k_walk_parents(const uint32_t* __restrict__ list, uint32_t* __restrict__ meta, const uint32_t* __restrict__ local,
+                                                              const uint32_t* __restrict__ sums, uint32_t nb, uint32_t k, const uint32_t* __restrict__ proof,
+                                                              uint32_t* __restrict__ st, uint32_t* __restrict__ next, uint32_t* __restrict__ from, uint32_t* __restrict__ sib) {
+    const uint32_t m = meta[WM_ITEMS], take = meta[WM_TAKE], c = proof[PROOF_HEADER + k];
+    const uint32_t t = blockIdx.x * IMG_THREADS + threadIdx.x;
+    const bool before = clean64(st, WR_RANGE) && clean64(st, WR_IN) && st[WR_ROW] == NONE, ok = before && take == c;
+    if (t == 0) {
+        meta[WM_WORDS + WM_ITEMS] = ok ? meta[WM_HEADS] : 0;
+        meta[WM_WORDS + WM_OFF] = meta[WM_OFF] + 8 * c;
+        if (before && m && take != c && st[WR_LAYER] == NONE) { st[WR_LAYER] = k; st[WR_LAYER_C] = c; st[WR_LAYER_TAKE] = take; }
+    }
+    if (t >= m || !ok) return;
+    const uint32_t x = list[t];
+    const uint32_t f = proof_flags(t ? list[t - 1] : NONE, x, t + 1 < m ? list[t + 1] : NONE);
+    if (!(f >> 16)) return;
+    const uint32_t ranks = local[t], r = (ranks >> 16) + sums[nb + blockIdx.x] - 1;
+    next[r] = x >> 1;
+    from[r] = t;
+    sib[r] = f & 1 ? (ranks & 0xffff) + sums[blockIdx.x] - 1 : NONE;
+}
+
+// one workgroup of 64: the top digests when the walk went through (items = the count of the top layer), and the values the messages of
+// a refused row and of a differing `in` print
+__global__ __launch_bounds__(64) void k_walk_top(const uint32_t* __restrict__ proof, uint32_t t0, const uint32_t* __restrict__ items, const uint32_t* __restrict__ dig,
+                                                 uint32_t* __restrict__ st) {
+    const uint32_t t = threadIdx.x, n = *items;
+    if (t < 16 && n == 1) st[WR_DIGESTS + t] = dig[t];
+    if (t == 16) st[WR_TOP_ITEMS] = n;
+    if (t == 17 && st[WR_ROW] != NONE) {
+        const uint32_t i = st[WR_ROW];
+        st[WR_ROW_A] = proof[t0 + 3 * (size_t)i];
+        st[WR_ROW_BEFORE] = i ? proof[t0 + 3 * (size_t)(i - 1)] : 0;
+    }
+    if (t == 18 && !clean64(st, WR_IN)) {
+        const uint32_t i = st[WR_IN + 1];
+        st[WR_IN_A] = proof[t0 + 3 * (size_t)i];
+        st[WR_IN_IN] = proof[t0 + 3 * (size_t)i + 1];
+    }
+}
+
+}  // namespace
+
+extern "C" const char* zkh_image_proof_walk(zkh_ctx* ctx, const zkh_buf* proof, size_t words, const uint32_t root_before[8], uint32_t root_after[8]) {
+    static const char who[] = "image_proof_walk";
+    ZKH_REQUIRE(ctx && proof && root_before && root_after, "%s: null argument", who);
+    ZKH_REQUIRE(words <= proof->len, "%s: a proof of %zu words in a buffer of %zu", who, words, proof->len);
+    ZKH_REQUIRE(words <= 0xffffffffull, "%s: a proof of %zu words (at most 2^32 - 1)", who, words);
+    bind_thread(ctx);
+    uint32_t head[PROOF_HEADER + 29] = {0};
+    ZKH_TRY(zkh_read(ctx, proof, head, 0, words < PROOF_HEADER + 29 ? words : PROOF_HEADER + 29));
+    ZKH_TRY(proof_header(who, head, words));
+    const uint32_t W = head[1], D = head[2], M = head[3], h = head[4];
+    const size_t L = image_leaves(W), t0 = PROOF_HEADER + h, l0 = t0 + 3 * (size_t)D;
+    bool root_ok = true;
+    for (int j = 0; j < 8; j++) root_ok = root_ok && root_before[j] < P;
+    if (words == t0) {                                  // D = 0 and nothing after the header: nothing to launch
+        if (!root_ok) return refuse_root_range(who);
+        memmove(root_after, root_before, 32);
+        return nullptr;
+    }
+    uint32_t rec[WR_WORDS] = {0};
+    rec[WR_RANGE] = rec[WR_RANGE + 1] = rec[WR_IN] = rec[WR_IN + 1] = rec[WR_ROW] = rec[WR_LAYER] = NONE;
+    Tmp st;
+    ZKH_TRY(zkh_copy_from(ctx, "walk_record", rec, WR_WORDS, st.out()));
+    const uint32_t* pw = proof->ptr();
+    // the scratch: the items of any layer are at most min(D, M, L) once the leaf stage's gate has passed, and nothing runs when it has not
+    size_t items0 = D < M ? D : M;
+    if (L < items0) items0 = L;
+    if (!items0) items0 = 1;                            // M = 0 on a table with rows: the gate stays shut, the stages still report
+    const bool rows = D && root_ok;                     // a root_before that is not below P: only a word >= P is reported before it
+    const uint32_t nb0 = (D + IMG_THREADS - 1) / IMG_THREADS;
+    Tmp lists[2], local, sums, meta, from, sib, dig[2];
+    {
+        ProfScope prof(ctx, "walk_check", 4.0 * (words - t0) + (rows ? 12.0 * D + 8.0 * nb0 : 0.0));
+        k_walk_range<<<(unsigned)((words - t0 + IMG_THREADS - 1) / IMG_THREADS), IMG_THREADS, 0, ctx->stream>>>(pw, t0, l0, words, st->ptr());
+        ZKH_TRY(last_launch_error("walk_range"));
+        if (rows) {
+            ZKH_TRY(new_buf(ctx, D, false, local.out()));
+            ZKH_TRY(new_buf(ctx, 1 + 2 * (size_t)nb0, false, sums.out()));
+            k_walk_rows<<<nb0, IMG_THREADS, 0, ctx->stream>>>(pw + t0, D, W, local->ptr(), sums->ptr(), st->ptr());
+            ZKH_TRY(last_launch_error("walk_rows"));
+            scan_counters(ctx, sums->ptr() + 1, 1, nb0, st->ptr() + WR_COUNT, 0);
+            ZKH_TRY(last_launch_error("walk_carry"));
+        }
+    }
+    if (rows) {
+        for (int i = 0; i < 2; i++) {
+            ZKH_TRY(new_buf(ctx, items0, false, lists[i].out()));
+            ZKH_TRY(new_buf(ctx, 16 * items0, false, dig[i].out()));
+        }
+        ZKH_TRY(new_buf(ctx, items0, false, from.out()));
+        ZKH_TRY(new_buf(ctx, items0, false, sib.out()));
+        ZKH_TRY(new_buf(ctx, WM_WORDS * ((size_t)h + 2), false, meta.out()));
+        {
+            ProfScope prof(ctx, "walk_leaves", 20.0 * D + 100.0 * items0);
+            k_walk_leaves<<<nb0, IMG_THREADS, 0, ctx->stream>>>(pw, (uint32_t)t0, D, M, local->ptr(), sums->ptr(), st->ptr(), lists[0]->ptr(), dig[0]->ptr(), meta->ptr());
+            ZKH_TRY(last_launch_error("walk_leaves"));
+        }
+        int cur = 0;
+        for (uint32_t k = 0; k < h; k++, cur ^= 1) {
+            const size_t width = L >> k;
+            const uint32_t items = (uint32_t)(items0 < width ? items0 : width), parents = (uint32_t)(items0 < width / 2 ? items0 : width / 2);
+            const uint32_t nb = (items + IMG_THREADS - 1) / IMG_THREADS;
+            uint32_t* mk = meta->ptr() + WM_WORDS * (size_t)k;
+            {
+                ProfScope prof(ctx, "walk_layer", 24.0 * items + 16.0 * nb + 12.0 * parents);
+                k_proof_flags<<<nb, IMG_THREADS, 0, ctx->stream>>>(lists[cur]->ptr(), mk, local->ptr(), sums->ptr(), nb);
+                ZKH_TRY(last_launch_error("walk_flags"));
+                scan_counters(ctx, sums->ptr(), 2, nb, mk + WM_TAKE, 1);
+                ZKH_TRY(last_launch_error("walk_carry"));
+                k_walk_parents<<<nb, IMG_THREADS, 0, ctx->stream>>>(lists[cur]->ptr(), mk, local->ptr(), sums->ptr(), nb, k, pw, st->ptr(), lists[cur ^ 1]->ptr(), from->ptr(),
+                                                                    sib->ptr());
+                ZKH_TRY(last_launch_error("walk_parents"));
+            }
+            ZKH_TRY(hash_walk_layer(ctx, lists[cur]->ptr(), from->ptr(), sib->ptr(), mk + WM_WORDS + WM_ITEMS, pw, mk + WM_OFF, dig[cur]->ptr(), dig[cur ^ 1]->ptr(), parents));
+        }
+        {
+            ProfScope prof(ctx, "walk_top", 128.0);
+            k_walk_top<<<1, 64, 0, ctx->stream>>>(pw, (uint32_t)t0, meta->ptr() + WM_WORDS * (size_t)h + WM_ITEMS, dig[cur]->ptr(), st->ptr());
+            ZKH_TRY(last_launch_error("walk_top"));
+        }
+    }
+    ZKH_TRY(zkh_read(ctx, st.b, rec, 0, WR_WORDS));
+    // the causes in the host verifier's order
+    if (!((rec[WR_RANGE] & rec[WR_RANGE + 1]) == NONE)) return refuse_word(who, rec[WR_RANGE + 1], rec[WR_RANGE]);
+    if (!root_ok) return refuse_root_range(who);
+    if (!D) return proof_empty(who, head);              // words past the header: M or a c_k is not 0
+    if (rec[WR_ROW] != NONE) {
+        const uint32_t i = rec[WR_ROW], a = rec[WR_ROW_A];
+        return a >= W ? refuse_outside(who, i, a, W) : refuse_order(who, i, a, rec[WR_ROW_BEFORE]);
+    }
+    if (rec[WR_COUNT] != M) return refuse_leaves(who, M, rec[WR_COUNT]);
+    if (!((rec[WR_IN] & rec[WR_IN + 1]) == NONE)) return refuse_in(who, rec[WR_IN + 1], rec[WR_IN_IN], rec[WR_IN_A], rec[WR_IN]);
+    if (rec[WR_LAYER] != NONE) return refuse_layer(who, rec[WR_LAYER], rec[WR_LAYER_C], rec[WR_LAYER_TAKE]);
+    ZKH_REQUIRE(rec[WR_TOP_ITEMS] == 1, "%s: the walk ended on %u nodes (a fault of the walk, not of the proof)", who, rec[WR_TOP_ITEMS]);
+    if (memcmp(rec + WR_DIGESTS, root_before, 32)) return refuse_root(who, rec + WR_DIGESTS);
+    memcpy(root_after, rec + WR_DIGESTS + 8, 32);
     return nullptr;
 }

@@ -21,6 +21,12 @@ const char* merkle_fold_from(zkh_ctx* c, zkh_buf* nodes, size_t first_layer);
 // hash.hip: the parents list[0 .. *count) of the layer of `width` parents, one lane per listed parent, nothing else of the layer touched.
 // `bound` >= *count sizes the grid (the count lives on the device); every list[t] < width.  Profiler scope image_sparse.
 const char* hash_fold_listed(zkh_ctx* c, zkh_buf* nodes, size_t width, const uint32_t* list, const uint32_t* count, uint32_t bound);
+// hash.hip: one layer of the walk of a ZKU1 proof (image.hip, zkh_image_proof_walk): the parents [0, *count) of the layer, two lanes
+// each (hash_pair of the old children, of the new ones).  Parent r's children: item from[r] of `list` with its two digests at
+// cur[16 item, +16), and the item after it (sib[r] = all ones) or the clean sibling at rank sib[r] of the proof's section at word *off.
+// The two digests of parent r go to next[16 r, +16).  `bound` >= *count sizes the grid.  Profiler scope walk_hash.
+const char* hash_walk_layer(zkh_ctx* c, const uint32_t* list, const uint32_t* from, const uint32_t* sib, const uint32_t* count, const uint32_t* proof,
+                            const uint32_t* off, const uint32_t* cur, uint32_t* next, uint32_t bound);
 
 // image.hip: after a page-out has scattered into `image`: `addrs` is the page table's address column (raw words), its rows [0, D) strictly
 // increasing addresses below image->len; `nodes` becomes what zkh_image_commit writes for the new image.  D = 0: nothing is launched.

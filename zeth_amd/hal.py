@@ -190,6 +190,7 @@ ABI = {
     "zkh_image_proof_words": (_sz, [_sz, _sz]),
     "zkh_page_out_proof": (_err, [_vp, _vp, _sz, _sz, _vp, _vp, _vp, _vp]),
     "zkh_image_proof_verify": (_err, [_u32p, _sz, _u32p, _u32p]),
+    "zkh_image_proof_walk": (_err, [_vp, _vp, _sz, _u32p, _u32p]),
     "zkh_circuit_derived_data_columns": (_err, [_vp, _u32p, _sz, C.POINTER(_sz)]),
     "zkh_upload_data_trace": (_err, [_vp, _vp, _sz, _sz, _vp, _u32p, _i]),
     "zkh_ctx_h2d_bytes": (_sz, [_vp]),
@@ -910,6 +911,26 @@ class HipHal:
         header = proof.slice(0, 5 + h).to_vec()
         words = 5 + h + 3 * int(header[2]) + 8 * int(header[3]) + 8 * int(header[5:].astype(np.uint64).sum())
         return proof.slice(0, words).to_vec()
+
+    def image_proof_walk(self, proof, root_before, words: Optional[int] = None) -> np.ndarray:
+        """root_after from a ZKU1 proof and root_before, walked on the device (zkh_image_proof_walk): the same verdict, root and message
+        (after "image_proof_walk: ") as `image_proof_verify` gives on the host.  proof: a Buffer whose first `words` words are the proof
+        (default: all of it; the buffer page_out_proof built in goes in with the proof's own length), or an array, which is uploaded.
+        The buffer is only read.  Raises HalError with one message per cause; nothing is returned then"""
+        before, after = _u32(root_before).reshape(-1), np.empty(DIGEST_WORDS, dtype=np.uint32)
+        if before.size != DIGEST_WORDS:
+            raise HalError(f"image_proof_walk: root_before of {before.size} words")
+        if not isinstance(proof, Buffer):
+            host = _u32(proof).reshape(-1)
+            proof = self.alloc("image_proof", max(host.size, 1))
+            if host.size:
+                _check(_lib.zkh_write(self.ctx, proof.h, _ptr(host), 0, host.size))
+            if words is None:
+                words = host.size
+        if words is None:
+            words = proof.size()
+        _check(_lib.zkh_image_proof_walk(self.ctx, proof.h, words, _ptr(before), _ptr(after)))
+        return after
 
     def image_root(self, nodes: Buffer) -> np.ndarray:
         """the root of a committed tree: digest 1 of `nodes`, 8 words"""

@@ -318,20 +318,35 @@ class SegmentProver:
             self.page_out(seg, data, image, tree=tree)
         return receipt
 
-    def page_out(self, seg: Segment, data, image, tree=None, proof: bool = False):
+    def page_out(self, seg: Segment, data, image, tree=None, proof: bool = False, walk: bool = False):
         """write the page table of the segment's derived data trace (a device Buffer) back into the memory image: image[p_addr] = p_out
         on the rows with p_on = 1 (zkh_page_out).  A call of its own, after the seal: a refused witness never touches the image.
         tree: the image's committed tree (hal.image_commit of the image as it is now), brought up to the new image in the same call
         (zkh_page_out_tree): its root is the commitment the next segment starts from.
         proof: with a tree, build the update's ZKU1 proof first (zkh_page_out_proof, from the tree as it is) and return its words:
-        hal.image_proof_verify(proof, the old root) gives the new root without the image.  Otherwise None is returned."""
+        hal.image_proof_verify(proof, the old root) gives the new root without the image.  Otherwise None is returned.
+        walk: with proof, the prover checks what it ships: the proof is walked on the device (zkh_image_proof_walk) from the tree's
+        root as it is, and after the page-out the walked root must be the tree's; HalError, naming both roots, if it is not."""
         if proof and tree is None:
             raise _hal.HalError("page_out: proof=True needs the image's committed tree (tree=hal.image_commit(image))")
+        if walk and not proof:
+            raise _hal.HalError("page_out: walk=True needs proof=True (the walk is of the proof)")
         if tree is None:
             self.hal.page_out(self.circuit, seg.po2, seg.zk_cycles, data, image)
             return None
-        words = self.hal.page_out_proof(self.circuit, seg.po2, seg.zk_cycles, data, image, tree) if proof else None
+        words = walked = None
+        if proof and walk:
+            buf = self.hal.alloc("image_proof", self.hal.image_proof_words(image.size(), (1 << seg.po2) - seg.zk_cycles))
+            words = self.hal.page_out_proof(self.circuit, seg.po2, seg.zk_cycles, data, image, tree, proof=buf)
+            walked = self.hal.image_proof_walk(buf, self.hal.image_root(tree), words=words.size)
+        elif proof:
+            words = self.hal.page_out_proof(self.circuit, seg.po2, seg.zk_cycles, data, image, tree)
         self.hal.page_out_tree(self.circuit, seg.po2, seg.zk_cycles, data, image, tree)
+        if walked is not None:
+            root = self.hal.image_root(tree)
+            if not np.array_equal(walked, root):
+                fmt = lambda r: " ".join(f"{int(w):08x}" for w in r)
+                raise _hal.HalError(f"page_out: the proof walks to root {fmt(walked)}, but the tree's root after the page-out is {fmt(root)}")
         return words
 
     def prove_segment(self, seg: Segment) -> SegmentReceipt:
