@@ -356,8 +356,9 @@ const char* zkh_derive_links(zkh_ctx*, const zkh_circuit*, size_t po2, size_t zk
  * comes first and a refusal leaves the image unchanged: the lowest row whose p_on is not 0 / 1, whose address is >= W, or whose address
  * does not follow a smaller one on a row with p_on = 1 (the table is a prefix of strictly increasing addresses, as the circuit demands:
  * a host-made table that repeats an address is refused, not resolved).  It is a call of its own so that a refused or aborted seal never
- * touches the image.  The prover can commit to the image and prove a page-out between two roots (below); no circuit checks p_in /
- * p_out against that commitment yet, so the verifier does not learn which image (ARGUMENTS). */
+ * touches the image.  The prover can commit to the image, prove a page-out between two roots and seal that step (below: P2-PAGE); no
+ * circuit ties p_in / p_out of a paging segment's OWN seal to that commitment yet, so the verifier of that seal does not learn which
+ * image (ARGUMENTS). */
 int zkh_circuit_pages(const zkh_circuit*);
 const char* zkh_derive_links_paged(zkh_ctx*, const zkh_circuit*, size_t po2, size_t zk_cycles, const zkh_buf* code, zkh_buf* data, const zkh_buf* image);
 const char* zkh_page_out(zkh_ctx*, const zkh_circuit*, size_t po2, size_t zk_cycles, const zkh_buf* data, zkh_buf* image);
@@ -434,6 +435,29 @@ const char* zkh_page_out_proof(zkh_ctx*, const zkh_circuit*, size_t po2, size_t 
                                zkh_buf* proof);
 const char* zkh_image_proof_verify(const uint32_t* proof, size_t words, const uint32_t root_before[8], uint32_t root_after[8]);
 const char* zkh_image_proof_walk(zkh_ctx*, const zkh_buf* proof, size_t words, const uint32_t root_before[8], uint32_t root_after[8]);
+/* P2-PAGE (circuit kind 5, zeth_amd/circuits/p2_page.py; csrc/page_circuit.hip): the circuit that consumes a ZKU1 proof's table.  Its
+ * seal proves "D single-word updates, applied one after the other, take root_before to root_after": out = root_before (8) ‖ root_after
+ * (8).  Every update is one Merkle path of h = log2 L blocks of 31 rows (P2-JOIN's rows), the old path and the new one side by side;
+ * N = ((2^po2 - zk_cycles) / 31) / h paths fit a trace, the slots past D are no-op updates of address 0.  It does NOT constrain that
+ * the addresses increase, nor that the table is the page table of a paging segment's seal.  W > 8 (a path is at least one hash_pair)
+ * and h <= 27 (the address is rebuilt in the field).
+ * zkh_page_circuit_code writes the code group, a function of (po2, zk_cycles, h of `image_words`): what the control root commits to.
+ * zkh_page_circuit_witgen writes the data group and out_roots = digest 1 of both trees.  `proof` is a device buffer whose first
+ * `proof_words` words are a ZKU1 proof as zkh_page_out_proof left it; only its header (one read-back, checked as zkh_image_proof_walk
+ * checks it) and its 3 D table words are read.  `nodes_before` / `nodes_after`: the tree before and after zkh_page_out_tree, each
+ * exactly zkh_image_tree_words(W) words.  `code`: this (po2, zk_cycles, h)'s code group, only read.  noise_key: as zkh_syn_witgen's.
+ * The generator reads the memory that update i opens from the two trees (`nodes_after` below a_i, `nodes_before` from a_i on: the
+ * addresses increase), so every path is independent; it TRUSTS that the table matches the trees (zkh_image_proof_walk is the check
+ * for that, and a table that does not gives a witness that zkh_check_rows refuses), but never reads outside `nodes_*` whatever the
+ * table holds: a check pass comes first and no path is walked after a refusal.
+ * It FAILS, after "page_circuit_witgen: ", one message per cause, in this order and before any launch: the circuit does not have
+ * P2-PAGE's shape; buffer shape mismatch; the proof's header (zkh_image_proof_verify's messages); W <= 8; nodes of another size; D > N
+ * (naming D, N, h and po2).  After the launches, from one read-back: the code group was not built for this h; row i whose address lies
+ * outside the image or does not follow a smaller one (`data` is then unspecified).  The accum group is zkh_syn_accum's (P2-JOIN's
+ * argument: one running product of mix + data column 0); the seal goes through zkh_prove_begin / zkh_prove_finish. */
+const char* zkh_page_circuit_code(zkh_ctx*, const zkh_circuit*, size_t po2, size_t zk_cycles, size_t image_words, zkh_buf* code);
+const char* zkh_page_circuit_witgen(zkh_ctx*, const zkh_circuit*, size_t po2, size_t zk_cycles, const zkh_buf* code, const zkh_buf* proof, size_t proof_words,
+                                    const zkh_buf* nodes_before, const zkh_buf* nodes_after, zkh_buf* data, uint32_t out_roots[16], const uint32_t noise_key[8]);
 /* Everything a circuit's arguments derive, in the one order in which it is sound: sorted copies, then columns, then links, then
  * multiplicities (a LIMBS / ORDER record may read a sorted copy's column, and the multiplicities count the limbs that the records and
  * the links derive).  Call it after the data upload and before zkh_prove_begin: what it writes belongs to the data group.  It runs
@@ -466,7 +490,9 @@ size_t zkh_ctx_h2d_bytes(const zkh_ctx*);
  *                    and out_global receives its output state as 100 16-bit limbs (lane l, limb j at 4 l + j).
  *   kind 3 P2-JOIN   every 31 active rows are one Poseidon2 permutation; block 0 = hash_pair(left, right) (zeth_amd/circuits/
  *                    p2_join.py; stands in for the in-circuit hashing of risc0-circuit-recursion 4.0.2, Cargo.lock:5305).
- *                    `pub` = the two child claims (16 words, required); out_global = parent (8) ‖ left (8) ‖ right (8). */
+ *                    `pub` = the two child claims (16 words, required); out_global = parent (8) ‖ left (8) ‖ right (8).
+ *   kind 5 P2-PAGE   has a generator of its own, zkh_page_circuit_code / zkh_page_circuit_witgen above (its inputs are a proof and
+ *                    two trees, not a seed); zkh_syn_accum builds its accum group, which is P2-JOIN's. */
 /* BLINDING ROWS.  The last zk_cycles rows of every data / accum column are zero-knowledge blinding noise.  Upstream draws each
  * cell from the OS RNG (`Elem::random(&mut rng)`); here the randomness enters once per call as a 256-bit key — `noise_key`, 8
  * words — and every cell is ChaCha12(key; counter = (row, column), nonce = (group, "ZKN1")) folded mod P the way upstream's

@@ -468,6 +468,29 @@ impl HipCircuitHal {
         after
     }
 
+    /// The code group of P2-PAGE, the circuit that seals a page-out from root to root (`zkh_page_circuit_code`): a function of the trace's
+    /// size and of the tree height of an image of `image_words` words.  `self` holds the P2-PAGE description.  Panics on a circuit of
+    /// another shape, on `image_words <= 8`, and on a trace without room for one path.
+    pub fn page_circuit_code(&self, image_words: usize, code: &HipBuffer<BabyBearElem>, steps: usize) {
+        let po2 = steps.trailing_zeros() as usize;
+        ffi(|| unsafe { sys::zkh_page_circuit_code(self.hal.ctx.0, self.circuit, po2, sys::ZK_CYCLES, image_words, code.raw) });
+    }
+
+    /// The data group of P2-PAGE for the page-out a ZKU1 proof describes (`zkh_page_circuit_witgen`) and the `out` globals, root_before
+    /// then root_after.  Only the header and the table of the first `words` words of `proof` are read; `nodes_before` / `nodes_after`
+    /// are the committed tree before and after `page_out_tree`; `code` is `page_circuit_code` of the same image size.  `noise_key`:
+    /// the 256-bit key of the blinding rows, `None` for fresh OS randomness.  Panics with one message per cause: a proof header that
+    /// does not fit, more updates than the trace has paths, trees of another size, a code group of another tree height, an address
+    /// outside the image or out of order.
+    pub fn page_circuit_witgen(&self, code: &HipBuffer<BabyBearElem>, proof: &HipBuffer<u32>, words: usize, nodes_before: &HipBuffer<BabyBearElem>,
+                               nodes_after: &HipBuffer<BabyBearElem>, data: &HipBuffer<BabyBearElem>, steps: usize, noise_key: Option<&[u32; 8]>) -> [u32; 16] {
+        let po2 = steps.trailing_zeros() as usize;
+        let mut roots = [0u32; 16];
+        ffi(|| unsafe { sys::zkh_page_circuit_witgen(self.hal.ctx.0, self.circuit, po2, sys::ZK_CYCLES, code.raw, proof.raw, words, nodes_before.raw, nodes_after.raw,
+                                                     data.raw, roots.as_mut_ptr(), noise_key.map_or(std::ptr::null(), |k| k.as_ptr())) });
+        roots
+    }
+
     /// Check the raw traces against the circuit's own constraints on every row of `rows` (`zkh_check_rows`): which constraint a
     /// witness breaks, and where, before a seal is spent on it.  `out` and `mix` are the global words.  `row < 0`: no row of the window
     /// fails; otherwise the lowest failing row, its lowest failing `and_eqz` step (an index into the ZKC1 step list), how many rows of

@@ -14,7 +14,8 @@ tree) next to zkh_page_out followed by zkh_image_commit (the full rebuild), for 
 pages spread over the whole image and a sparse one of 4096 pages, at two image sizes, alternating; M19: the update's proof,
 zkh_page_out_proof next to zkh_page_out_tree on M18's tables and image sizes, alternating, with the proof's size; M20: the walk of
 that proof on the device, zkh_image_proof_walk next to the host walk of the downloaded proof (zkh_image_proof_verify), the download and
-zkh_page_out_tree, alternating, with the number of permutations) on one MI355X, through the C ABI (HipHal).
+zkh_page_out_tree, alternating, with the number of permutations; M21: P2-PAGE's witness, zkh_page_circuit_witgen with full slots at
+h = 17 and h = 23 next to zkh_syn_witgen of P2-JOIN at the same po2, alternating, with both calls' stages) on one MI355X, through the C ABI (HipHal).
 
 Each line of output is one JSON object: the op, its shape, the average wall time of one call (stream drained on both
 sides of `reps` back-to-back calls), its ALGORITHMIC bytes (SURVEY.md §8a "B_alg": inputs read once + outputs written
@@ -894,6 +895,74 @@ def main() -> None:
                                   "walk_vs_tree": round(med["image_proof_walk"] / med["page_out_tree"], 3)}), flush=True)
                 del images, nodes, buf
         del data
+    if want("M21"):
+        # P2-PAGE's witness: zkh_page_circuit_witgen (csrc/page_circuit.hip: two permutations per row, one lane per (path, old / new)
+        # walking its h blocks in turn) with every path slot full, at h = 17 (2^20 image words) and h = 23 (2^26), next to its yardstick
+        # in the same run, zkh_syn_witgen of P2-JOIN at the same po2 (one permutation per row at half the width, one lane per block;
+        # that call also writes its code group, so the kernels' own events are reported too).  Timed in alternation, `runs` windows of
+        # `reps` calls; median and spread (min, max) of the windows; then both calls' stages by their events.  The generator reads the
+        # proof's header and table only, so the proof here is exactly that: a ZKU1 header that describes no leaves and no siblings, and
+        # the table.  per_block_ratio = (page_paths per block of two permutations) / (p2join_blocks per block of one).
+        from zeth_amd import hal as zhal
+        from zeth_amd.circuits import p2_join, p2_page
+        runs, zk = 7, 1994
+        spread = lambda ts: {"median_ms": round(float(np.median(ts)) * 1e3, 4), "min_ms": round(min(ts) * 1e3, 4), "max_ms": round(max(ts) * 1e3, 4)}   # noqa: E731
+        join, page = hal.load_circuit(p2_join.p2_join_circuit()), hal.load_circuit(p2_page.p2_page_circuit())
+        K = (n - zk) // 31
+        jcode, jdata = hal.alloc_elem("m21jc", p2_join.WC * n), hal.alloc_elem("m21jd", p2_join.WD * n)
+        kids = rand_fp(rng, 16)
+        join_fn = lambda: hal.syn_witgen(join, args.po2, zk, 0, 0x2E80, jcode, jdata, pub=kids)               # noqa: E731
+        pdata = hal.alloc_elem("m21pd", p2_page.WD * n)
+        u32p = zhal._u32p
+        key = zhal.noise_key(0x2E80)
+        for W in (1 << 20, 1 << 26):
+            h = p2_page.tree_height(W)
+            N = p2_page.slots(args.po2, zk, h)
+            image_h = rand_fp(rng, W)
+            addrs = np.unique(rng.integers(0, W, N + N // 8))
+            addrs = np.sort(addrs[rng.choice(addrs.size, N, replace=False)]).astype(np.int64)
+            outs = rand_fp(rng, N)
+            table = np.stack([addrs.astype(np.uint32), image_h[addrs], outs], axis=1).reshape(-1)
+            proof_h = np.concatenate([np.array([0x5A4B5531, W, N, 0, h] + [0] * h, dtype=np.uint32), table])
+            image = hal.alloc_elem("m21i", W)
+            image.write(image_h)
+            before = hal.image_commit(image)
+            image_h[addrs] = outs
+            image.write(image_h)
+            after = hal.image_commit(image)
+            del image
+            proof = hal.copy_from("m21p", proof_h)
+            pcode = hal.page_circuit_code(page, args.po2, zk, W)
+            roots = np.zeros(16, dtype=np.uint32)
+            page_fn = lambda: zhal._check(zhal._lib.zkh_page_circuit_witgen(hal.ctx, page.h, args.po2, zk, pcode.h, proof.h, proof_h.size, before.h, after.h, pdata.h,   # noqa: E731
+                                                                            roots.ctypes.data_as(u32p), key.ctypes.data_as(u32p)))
+            page_fn()
+            assert np.array_equal(roots[:8], hal.image_root(before)) and np.array_equal(roots[8:], hal.image_root(after))
+            top = 31 * h * N - 1                                             # the last path's output row holds root_after on its new side
+            got = np.array([pdata.get_at((p2_page.D_SN + j) * n + top) for j in range(8)], dtype=np.uint32)
+            assert np.array_equal(got, roots[8:]), "the last path does not end on the root of the tree after the page-out"
+            t = {"page_circuit_witgen": [], "p2join_syn_witgen": []}
+            for _ in range(runs):
+                for name, fn in (("page_circuit_witgen", page_fn), ("p2join_syn_witgen", join_fn)):
+                    t[name].append(timed(hal, fn, args.reps))
+            steps = {}
+            for fn in (page_fn, join_fn):
+                hal.prof_enable(True)
+                hal.prof_reset()
+                for _ in range(args.reps):
+                    fn()
+                hal.sync()
+                steps.update({r["name"]: {"calls_per_call": r["calls"] // args.reps, "ms_per_call": round(r["total_ms"] / args.reps, 4)} for r in hal.prof_get()
+                              if r["calls"] and r["name"].startswith(("page_", "p2join_"))})
+                hal.prof_enable(False)
+            med = {k: float(np.median(v)) for k, v in t.items()}
+            print(json.dumps({"bench": "M21", "library": os.path.basename(os.environ.get("ZKH_LIBRARY", "") or "libzkhal_mi355x.so"), "po2": args.po2,
+                              "image_words": W, "layers": h, "slots": N, "page_blocks": h * N, "join_blocks": K, "lanes": 2 * N, "runs": runs, "reps": args.reps,
+                              **{k: spread(v) for k, v in t.items()}, "steps": steps,
+                              "call_ratio": round(med["page_circuit_witgen"] / med["p2join_syn_witgen"], 3),
+                              "per_block_ratio": round((steps["page_paths"]["ms_per_call"] / (h * N)) / (steps["p2join_blocks"]["ms_per_call"] / K), 3)}), flush=True)
+            del before, after, proof, pcode
+        del jcode, jdata, pdata
     hal.close()
 
 

@@ -1326,6 +1326,8 @@ def shipped() -> Dict[str, np.ndarray]:
         SHIPPED["p2_join"] = p2_join.p2_join_circuit()
         from . import recursion
         SHIPPED["recursion"] = recursion.recursion_circuit()
+        from . import p2_page
+        SHIPPED["p2_page"] = p2_page.p2_page_circuit()
     return SHIPPED
 
 

@@ -5,6 +5,7 @@
 // risc0_zkp::hal::CircuitHal (risc0-zkp 3.0.2 src/hal/mod.rs).  Reached from
 // /root/reference/crates/host/src/lib.rs:137.
 #include "circuit.h"
+#include "p2_rows.h"
 #include "poseidon2.h"
 #include "scan.h"
 #include "../../include/zkh_poseidon2_consts.h"
@@ -342,16 +343,7 @@ KeccakTables keccak_tables() {
 // two child claims into the parent claim, the other blocks hash (parent ‖ public sibling words).  Stands in for the in-circuit
 // hashing of risc0-circuit-recursion 4.0.2 (un-vendored: /root/reference/Cargo.lock:5305).  A literal round-by-round
 // permutation (the trace needs every intermediate state); tab = Montgomery words of rc[24 * 29] then diag[24].
-constexpr uint32_t PJ_T = 24, PJ_HALF = 4, PJ_RP = 21, PJ_ROUNDS = 29, PJ_BLOCK = 31;
-__device__ __forceinline__ bool pj_is_full(uint32_t rnd) { return rnd < PJ_HALF || rnd >= PJ_HALF + PJ_RP; }
-__device__ void pj_m_ext(uint32_t (&c)[PJ_T]) {
-    uint32_t sums[4] = {0, 0, 0, 0};
-    for (uint32_t b = 0; b < PJ_T; b += 4) {
-        m4(c[b], c[b + 1], c[b + 2], c[b + 3]);
-        for (uint32_t i = 0; i < 4; i++) sums[i] = add_mod(sums[i], c[b + i]);
-    }
-    for (uint32_t k = 0; k < PJ_T; k++) c[k] = add_mod(c[k], sums[k & 3]);
-}
+// (PJ_*, pj_is_full, pj_m_ext: p2_rows.h, shared with the P2-PAGE generator of page_circuit.hip)
 __global__ void k_p2join_code(uint32_t* code, uint32_t n, uint32_t A, uint32_t K, const uint32_t* __restrict__ tab) {
     const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x, col = blockIdx.y;
     if (r >= n) return;
@@ -814,11 +806,11 @@ static const char* keccak_check_shape(const zkh_circuit* c) {
                 c->global_size[GLOBAL_OUT] == 200, "keccak witgen: the circuit does not have KECCAK-F's shape (15 / 3840 / 4 columns, 200 outputs)");
     return nullptr;
 }
-static const char* p2join_tables(zkh_ctx* ctx, Tmp& tab) {          // Montgomery words of the SHIPPED tables: rc[24 * 29] then diag[24]
+const char* zkh::p2_rows_tables(zkh_ctx* ctx, Tmp& tab) {           // Montgomery words of the SHIPPED tables: rc[24 * 29] then diag[24]
     std::vector<uint32_t> t(PJ_T * PJ_ROUNDS + PJ_T);
     for (uint32_t i = 0; i < PJ_T * PJ_ROUNDS; i++) t[i] = fp_encode(ZKH_P2_ROUND_CONSTANTS[i]).v;
     for (uint32_t i = 0; i < PJ_T; i++) t[PJ_T * PJ_ROUNDS + i] = fp_encode(ZKH_P2_M_INT_DIAG[i]).v;
-    return zkh_copy_from(ctx, "p2join_tables", t.data(), t.size(), tab.out());
+    return zkh_copy_from(ctx, "p2_rows_tables", t.data(), t.size(), tab.out());
 }
 static const char* p2join_check_shape(const zkh_circuit* c) {
     ZKH_REQUIRE(c->group_size[GROUP_CODE] == 43 && c->group_size[GROUP_DATA] == 2 * PJ_T && c->group_size[GROUP_ACCUM] == 4 &&
@@ -854,7 +846,7 @@ extern "C" const char* zkh_syn_code(zkh_ctx* ctx, const zkh_circuit* c, size_t p
     if (c->kind == 3) {
         ZKH_TRY(p2join_check_shape(c));
         Tmp tab;
-        ZKH_TRY(p2join_tables(ctx, tab));
+        ZKH_TRY(p2_rows_tables(ctx, tab));
         ProfScope prof(ctx, "p2join_code", 4.0 * wc * n);
         k_p2join_code<<<dim3((unsigned)((n + 255) / 256), wc), 256, 0, ctx->stream>>>(code->ptr(), (uint32_t)n, A, A / PJ_BLOCK, tab->ptr());
         return last_launch_error("p2join_code");
@@ -881,7 +873,7 @@ extern "C" const char* zkh_syn_witgen(zkh_ctx* ctx, const zkh_circuit* c, size_t
         ZKH_REQUIRE(K > 0, "p2join witgen: no room for a permutation (31 rows) in %u active rows", A);
         ZKH_TRY(zkh_syn_code(ctx, c, po2, zk_cycles, code));
         Tmp tab, kids, parent;
-        ZKH_TRY(p2join_tables(ctx, tab));
+        ZKH_TRY(p2_rows_tables(ctx, tab));
         ZKH_TRY(zkh_copy_from(ctx, "children", pub, 16, kids.out()));
         ZKH_TRY(new_buf(ctx, 8, false, parent.out()));
         {
@@ -959,7 +951,8 @@ extern "C" const char* zkh_syn_chain_contributions(zkh_ctx* ctx, const zkh_circu
 }
 extern "C" const char* zkh_syn_accum(zkh_ctx* ctx, const zkh_circuit* c, size_t po2, size_t zk_cycles, const uint32_t* noise_key,
                                      const zkh_buf* data, const uint32_t* mix_global, zkh_buf* accum) {
-    ZKH_REQUIRE(c->kind >= 1 && c->kind <= 3, "syn_accum: no built-in accum witness generator for circuit kind %u", c->kind);
+    // kind 5 (P2-PAGE, page_circuit.hip) carries P2-JOIN's argument: one running product of (mix + data column 0)
+    ZKH_REQUIRE((c->kind >= 1 && c->kind <= 3) || c->kind == 5, "syn_accum: no built-in accum witness generator for circuit kind %u", c->kind);
     NoiseKey nk;
     ZKH_TRY(resolve_noise_key(noise_key, &nk));
     const size_t n = (size_t)1 << po2;

@@ -420,6 +420,8 @@ const char* proof_empty(const char* who, const uint32_t* head) {
 
 }  // namespace
 
+const char* zkh::image_proof_header(const char* who, const uint32_t* head, size_t words) { return proof_header(who, head, words); }
+
 // The walk of include/zkhal.h "THE UPDATE'S PROOF" on the host: no context, no GPU; every layer is one batch through the permutation
 // zkh_poseidon2_mix_host uses, the old children first, the new ones after them.
 extern "C" const char* zkh_image_proof_verify(const uint32_t* proof, size_t words, const uint32_t root_before[8], uint32_t root_after[8]) {

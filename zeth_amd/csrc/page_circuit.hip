@@ -1,0 +1,288 @@
+// page_circuit.hip — the witness of P2-PAGE (zeth_amd/circuits/p2_page.py; include/zkhal.h "P2-PAGE"; DESIGN.md §2 ARGUMENTS): a
+// page-out of the committed memory image as a trace, D single-word updates applied one after the other from root_before to
+// root_after, every update one Merkle path of h blocks of 31 rows, the old path and the new one side by side in every row.
+//
+// THE TWO-TREE SHORTCUT.  Update i opens its word under the tree as updates 0 .. i - 1 have left it, so the paths form a chain.  The
+// generator does not walk that chain: it holds the tree BEFORE the page-out and the tree AFTER it, and the table's addresses strictly
+// increase.  So the memory update i opens is `nodes_after` at every address below a_i and `nodes_before` from a_i on: updates before
+// i wrote only below a_i, and nothing above a_i has been written yet.  A subtree that lies wholly on one side of a_i is therefore a
+// node of one of the two trees as it stands:
+//   leaf block : each of the 16 words of the pair of leaves comes from `nodes_after` when its address is below a_i (new side: at or
+//                below a_i), else from `nodes_before`;
+//   block t>=1 : the sibling is a left one (all its addresses below a_i) from `nodes_after`, or a right one from `nodes_before`;
+//   the on-path digests come from the lane's own permutation chain.
+// Every path is then independent of every other.  The slots D .. N - 1 are no-op updates of address 0 under the tree after the
+// page-out.  The Python yardstick (p2_page.reference_page_trace) applies the updates one at a time to one tree and shares nothing
+// with this.
+//
+// KERNELS.  k_page_check: ONE workgroup; the lowest row of the table whose address is outside the image or does not follow a smaller
+// one (an LDS minimum, no atomics), whether the code group was built for this h, and digest 1 of both trees, into a record of 24 words.
+// k_page_paths: one lane per (slot, old / new) walks its h blocks with the literal permutation of k_p2join_blocks; it returns at once
+// when the record holds a refusal, so no address at or past W ever indexes `nodes_*`.  k_page_book: one lane per (row, bookkeeping
+// column); `cur` of slot s > 0 is read from the output row the path kernel wrote for slot s - 1.  k_page_tail: zero rows, then the
+// blinding rows.  No atomics, every cell has one writer; one read-back fetches the record at the end.
+#include "circuit.h"
+#include "image_tree.h"
+#include "p2_rows.h"
+
+using namespace zkh;
+
+namespace {
+
+constexpr uint32_t PG_WC = 39, PG_WD = 125, PG_OUT = 16, PG_MAX_H = 27;
+// code columns (p2_page.py C_*)
+enum : uint32_t { PC_LIN = 3, PC_FULLR, PC_PARTR, PC_LF, PC_LP, PC_LEAF_IN, PC_NODE_IN, PC_PATH_FIRST, PC_TOP_OUT, PC_LAST_TOP, PC_CARRY, PC_POW, PC_RC };
+// data columns (p2_page.py D_*)
+enum : uint32_t { PD_SO = 0, PD_QO = 24, PD_SN = 48, PD_QN = 72, PD_E = 96, PD_B = 112, PD_ADDR = 113, PD_W_IN = 114, PD_W_OUT = 115, PD_ACC = 116, PD_CUR = 117 };
+// the record: the lowest refused row (NONE: none), its address, the address before it, whether the code group is this h's, both roots
+enum : uint32_t { PR_ROW = 0, PR_A = 1, PR_BEFORE = 2, PR_CODE_OK = 3, PR_ROOTS = 8, PR_WORDS = 24 };
+constexpr uint32_t NONE = 0xffffffffu;
+constexpr uint32_t PG_THREADS = 256;
+
+__device__ __forceinline__ uint32_t encode(uint32_t x) { return mul_mod(R2, x); }       // x < P
+
+__global__ void k_page_code(uint32_t* code, uint32_t n, uint32_t A, uint32_t h, uint32_t N, const uint32_t* __restrict__ tab) {
+    const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x, col = blockIdx.y;
+    if (r >= n) return;
+    uint32_t v = 0;
+    const bool in_paths = r < PJ_BLOCK * h * N;
+    const uint32_t k = r % PJ_BLOCK, blk = r / PJ_BLOCK, t = blk % h, s = blk / h;
+    const bool round_row = in_paths && k >= 1 && k <= PJ_ROUNDS;
+    const bool full = round_row && pj_is_full(k - 1), part = round_row && !pj_is_full(k - 1);
+    const bool top = in_paths && k == PJ_BLOCK - 1 && t == h - 1;
+    switch (col) {
+    case 0: v = r < A ? R1 : 0; break;
+    case 1: v = r == 0 ? R1 : 0; break;
+    case 2: v = (r > 0 && r < A) ? R1 : 0; break;
+    case PC_LIN: v = (in_paths && k == 1) ? R1 : 0; break;
+    case PC_FULLR: v = full ? R1 : 0; break;
+    case PC_PARTR: v = part ? R1 : 0; break;
+    case PC_LF: v = (in_paths && k >= 2 && pj_is_full(k - 2)) ? R1 : 0; break;
+    case PC_LP: v = (in_paths && k >= 2 && !pj_is_full(k - 2)) ? R1 : 0; break;
+    case PC_LEAF_IN: v = (in_paths && k == 0 && t == 0) ? R1 : 0; break;
+    case PC_NODE_IN: v = (in_paths && k == 0 && t > 0) ? R1 : 0; break;
+    case PC_PATH_FIRST: v = (in_paths && k == 0 && t == 0 && s > 0) ? R1 : 0; break;
+    case PC_TOP_OUT: v = top ? R1 : 0; break;
+    case PC_LAST_TOP: v = (top && s == N - 1) ? R1 : 0; break;
+    case PC_CARRY: v = (in_paths && (k > 0 || t > 0)) ? R1 : 0; break;
+    case PC_POW: v = (in_paths && k == 0 && t > 0) ? encode(1u << (3 + t)) : 0; break;
+    default: if (full || (part && col == PC_RC)) v = tab[(k - 1) * PJ_T + (col - PC_RC)];
+    }
+    code[(size_t)col * n + r] = v;
+}
+
+// ONE workgroup over the table's D rows (stride 3, the address first).  No kernel reads `nodes_*` at an address of the table before
+// this record says that every address is below W.
+__global__ __launch_bounds__(PG_THREADS) void k_page_check(const uint32_t* __restrict__ table, uint32_t D, uint32_t W, const uint32_t* __restrict__ code, uint32_t n,
+                                                           uint32_t h, const uint32_t* __restrict__ nodes_before, const uint32_t* __restrict__ nodes_after,
+                                                           uint32_t* __restrict__ rec) {
+    __shared__ uint32_t low[PG_THREADS];
+    const uint32_t t = threadIdx.x;
+    uint32_t bad = NONE;
+    for (uint32_t i = t; i < D && bad == NONE; i += PG_THREADS) {
+        const uint32_t a = table[3 * (size_t)i];
+        if (a >= W || (i && table[3 * (size_t)(i - 1)] >= a)) bad = i;
+    }
+    low[t] = bad;
+    __syncthreads();
+    for (uint32_t s = PG_THREADS / 2; s; s >>= 1) {
+        if (t < s) low[t] = low[t] < low[t + s] ? low[t] : low[t + s];
+        __syncthreads();
+    }
+    if (t == 0) {
+        const uint32_t i = low[0];
+        rec[PR_ROW] = i;
+        rec[PR_A] = i != NONE ? table[3 * (size_t)i] : 0;
+        rec[PR_BEFORE] = i != NONE && i ? table[3 * (size_t)(i - 1)] : 0;
+        // a code group of another h' has its first top_out row at 31 h' - 1 and 2^(3 + t) on the input row of its blocks t = block % h'
+        const bool top = code[(size_t)PC_TOP_OUT * n + PJ_BLOCK * h - 1] == R1;
+        const bool pow = h == 1 || code[(size_t)PC_POW * n + PJ_BLOCK * (h - 1)] == encode(1u << (2 + h));
+        rec[PR_CODE_OK] = top && pow;
+    }
+    if (t >= 8 && t < 16) rec[t] = nodes_before[t];                   // digest 1 = words [8, 16)
+    if (t >= 16 && t < 24) rec[t] = nodes_after[t - 8];
+}
+
+// One lane per (slot, side): side 0 the old path, 1 the new one.  L = the tree's leaves (2^h), words of layer t's node x at
+// 8 ((L >> t) + x); the leaf layer is the memory itself at words [8 L, 16 L).
+__global__ __launch_bounds__(64) void k_page_paths(uint32_t* __restrict__ data, uint32_t n, uint32_t h, uint32_t N, const uint32_t* __restrict__ table, uint32_t D,
+                                                   const uint32_t* __restrict__ nodes_before, const uint32_t* __restrict__ nodes_after, size_t L,
+                                                   const uint32_t* __restrict__ rec, const uint32_t* __restrict__ tab) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= 2 * N || rec[PR_ROW] != NONE) return;
+    const uint32_t slot = i >> 1, side = i & 1;
+    const bool real = slot < D;
+    const uint32_t a = real ? table[3 * (size_t)slot] : 0;             // < W <= 8 L: the record holds no refusal
+    const uint32_t* before = real ? nodes_before : nodes_after;        // a no-op opens the tree after the page-out
+    const uint32_t s_col = side ? PD_SN : PD_SO, q_col = side ? PD_QN : PD_QO;
+    const uint32_t* diag = tab + PJ_T * PJ_ROUNDS;
+    uint32_t s[PJ_T];
+    for (uint32_t t = 0; t < h; t++) {
+        const size_t r0 = (size_t)PJ_BLOCK * ((size_t)slot * h + t);
+        if (t == 0) {
+            const uint32_t x0 = a & ~15u;                              // the pair of leaves: 16 words, all below 8 L (L >= 2)
+            for (uint32_t j = 0; j < 16; j++) {
+                const uint32_t x = x0 + j;
+                const bool done = side ? x <= a : x < a;
+                s[j] = (done ? nodes_after : before)[8 * L + x];
+            }
+        } else {
+            const uint32_t x = a >> (3 + t);                           // the on-path node of layer t, the lane's own digest in s[0, 8)
+            const bool right = x & 1;
+            const uint32_t* sib = (right ? nodes_after : before) + 8 * ((L >> t) + (x ^ 1));
+            for (uint32_t j = 0; j < 8; j++) {
+                const uint32_t own = s[j], other = sib[j];
+                s[j] = right ? other : own;
+                s[8 + j] = right ? own : other;
+            }
+        }
+        for (uint32_t j = 16; j < PJ_T; j++) s[j] = 0;
+        for (uint32_t j = 0; j < PJ_T; j++) { data[(size_t)(s_col + j) * n + r0] = s[j]; data[(size_t)(q_col + j) * n + r0] = 0; }
+        pj_m_ext(s);
+        // the round loop of k_p2join_blocks (circuit.hip) on this side's columns
+        for (uint32_t rnd = 0; rnd < PJ_ROUNDS; rnd++) {
+            const size_t r = r0 + 1 + rnd;
+            for (uint32_t j = 0; j < PJ_T; j++) data[(size_t)(s_col + j) * n + r] = s[j];
+            if (pj_is_full(rnd)) {
+                for (uint32_t j = 0; j < PJ_T; j++) {
+                    const uint32_t u = add_mod(s[j], tab[rnd * PJ_T + j]);
+                    const uint32_t q = mul_mod(mul_mod(u, u), u);
+                    data[(size_t)(q_col + j) * n + r] = q;
+                    s[j] = mul_mod(mul_mod(q, q), u);
+                }
+                pj_m_ext(s);
+            } else {
+                const uint32_t u = add_mod(s[0], tab[rnd * PJ_T]);
+                const uint32_t q = mul_mod(mul_mod(u, u), u);
+                data[(size_t)q_col * n + r] = q;
+                for (uint32_t j = 1; j < PJ_T; j++) data[(size_t)(q_col + j) * n + r] = 0;
+                const uint32_t x7 = mul_mod(mul_mod(q, q), u);
+                uint32_t tot = x7;
+                for (uint32_t j = 1; j < PJ_T; j++) tot = add_mod(tot, s[j]);
+                s[0] = add_mod(tot, mul_mod(diag[0], x7));
+                for (uint32_t j = 1; j < PJ_T; j++) s[j] = add_mod(tot, mul_mod(diag[j], s[j]));
+            }
+        }
+        const size_t rl = r0 + PJ_BLOCK - 1;
+        for (uint32_t j = 0; j < PJ_T; j++) { data[(size_t)(s_col + j) * n + rl] = s[j]; data[(size_t)(q_col + j) * n + rl] = 0; }
+    }
+}
+
+// grid (ceil(31 h N / 256), 29): the bookkeeping columns e, b, addr, w_in, w_out, acc, cur of the rows of the paths, after k_page_paths
+__global__ __launch_bounds__(PG_THREADS) void k_page_book(uint32_t* __restrict__ data, uint32_t n, uint32_t h, uint32_t N, const uint32_t* __restrict__ table, uint32_t D,
+                                                          const uint32_t* __restrict__ nodes_before, const uint32_t* __restrict__ nodes_after, size_t L,
+                                                          const uint32_t* __restrict__ rec) {
+    const uint32_t r = blockIdx.x * PG_THREADS + threadIdx.x, col = PD_E + blockIdx.y;
+    if (r >= PJ_BLOCK * h * N || rec[PR_ROW] != NONE) return;
+    const uint32_t k = r % PJ_BLOCK, blk = r / PJ_BLOCK, t = blk % h, slot = blk / h;
+    const bool real = slot < D;
+    const uint32_t a = real ? table[3 * (size_t)slot] : 0;
+    uint32_t v = 0;
+    if (col < PD_B) v = (k == 0 && t == 0 && (a & 15) == col - PD_E) ? R1 : 0;
+    else if (col == PD_B) v = (k == 0 && t > 0 && ((a >> (3 + t)) & 1)) ? R1 : 0;
+    else if (col == PD_ADDR) v = encode(a);
+    else if (col == PD_W_IN) v = real ? table[3 * (size_t)slot + 1] : nodes_after[8 * L];
+    else if (col == PD_W_OUT) v = real ? table[3 * (size_t)slot + 2] : nodes_after[8 * L];
+    else if (col == PD_ACC) v = encode(a & ((1u << (4 + t)) - 1));
+    else v = slot ? data[(size_t)(PD_SN + col - PD_CUR) * n + (size_t)PJ_BLOCK * h * slot - 1] : nodes_before[8 + col - PD_CUR];
+    data[(size_t)col * n + r] = v;
+}
+
+// rows past the last path: zero while active, blinding noise after
+__global__ void k_page_tail(uint32_t* data, uint32_t n, uint32_t A, uint32_t first_row, NoiseKey nk) {
+    const uint32_t r = first_row + blockIdx.x * blockDim.x + threadIdx.x, col = blockIdx.y;
+    if (r >= n) return;
+    data[(size_t)col * n + r] = r < A ? 0u : noise_cell(nk, GROUP_DATA, col, r);
+}
+
+// the checks the two entry points share.  First the circuit's shape and the trace's size ...
+const char* page_circuit_shape(const char* who, const zkh_circuit* c, size_t po2, size_t zk_cycles) {
+    ZKH_REQUIRE(c->kind == 5 && c->group_size[GROUP_CODE] == PG_WC && c->group_size[GROUP_DATA] == PG_WD && c->group_size[GROUP_ACCUM] == 4 &&
+                c->global_size[GLOBAL_OUT] == PG_OUT, "%s: the circuit does not have P2-PAGE's shape (kind 5, 39 / 125 / 4 columns, 16 outputs)", who);
+    ZKH_REQUIRE(po2 >= 1 && po2 <= 30 && ((size_t)1 << po2) > zk_cycles + 1, "%s: po2 %zu out of range for %zu zk_cycles", who, po2, zk_cycles);
+    return nullptr;
+}
+// ... then the image's -> A, h, N
+const char* page_image_shape(const char* who, size_t po2, size_t zk_cycles, size_t W, uint32_t* A_out, uint32_t* h_out, uint32_t* N_out) {
+    ZKH_REQUIRE(W > 8, "%s: an image of %zu words has a single leaf (W > 8: a path is at least one hash_pair)", who, W);
+    uint32_t h = 0;
+    while (((size_t)1 << h) < image_leaves(W)) h++;
+    ZKH_REQUIRE(h <= PG_MAX_H, "%s: an image of %zu words has h %u; the address is rebuilt in the field, which takes h <= %u", who, W, h, PG_MAX_H);
+    *A_out = (uint32_t)(((size_t)1 << po2) - zk_cycles);
+    *h_out = h;
+    *N_out = *A_out / PJ_BLOCK / h;
+    ZKH_REQUIRE(*N_out >= 1, "%s: no room for a path of h %u blocks of 31 rows in %u active rows (po2 %zu)", who, h, *A_out, po2);
+    return nullptr;
+}
+
+}  // namespace
+
+extern "C" const char* zkh_page_circuit_code(zkh_ctx* ctx, const zkh_circuit* c, size_t po2, size_t zk_cycles, size_t image_words, zkh_buf* code) {
+    static const char who[] = "page_circuit_code";
+    ZKH_REQUIRE(ctx && c && code, "%s: null argument", who);
+    ZKH_TRY(page_circuit_shape(who, c, po2, zk_cycles));
+    const size_t n = (size_t)1 << po2;
+    ZKH_REQUIRE(code->len == (size_t)PG_WC * n, "%s: buffer shape mismatch", who);
+    uint32_t A, h, N;
+    ZKH_TRY(page_image_shape(who, po2, zk_cycles, image_words, &A, &h, &N));
+    Tmp tab;
+    ZKH_TRY(p2_rows_tables(ctx, tab));
+    ProfScope prof(ctx, "page_code", 4.0 * PG_WC * n);
+    k_page_code<<<dim3((unsigned)((n + 255) / 256), PG_WC), 256, 0, ctx->stream>>>(code->ptr(), (uint32_t)n, A, h, N, tab->ptr());
+    return last_launch_error("page_code");
+}
+
+extern "C" const char* zkh_page_circuit_witgen(zkh_ctx* ctx, const zkh_circuit* c, size_t po2, size_t zk_cycles, const zkh_buf* code, const zkh_buf* proof,
+                                               size_t proof_words, const zkh_buf* nodes_before, const zkh_buf* nodes_after, zkh_buf* data,
+                                               uint32_t out_roots[16], const uint32_t* noise_key) {
+    static const char who[] = "page_circuit_witgen";
+    ZKH_REQUIRE(ctx && c && code && proof && nodes_before && nodes_after && data && out_roots, "%s: null argument", who);
+    ZKH_TRY(page_circuit_shape(who, c, po2, zk_cycles));
+    const size_t n = (size_t)1 << po2;
+    ZKH_REQUIRE(code->len == (size_t)PG_WC * n && data->len == (size_t)PG_WD * n, "%s: buffer shape mismatch (the code group is an input of this generator)", who);
+    ZKH_REQUIRE(proof_words <= proof->len && proof_words <= 0xffffffffull, "%s: a proof of %zu words in a buffer of %zu", who, proof_words, proof->len);
+    NoiseKey nk;
+    ZKH_TRY(resolve_noise_key(noise_key, &nk));
+    bind_thread(ctx);
+    uint32_t head[PROOF_HEAD_MAX] = {0};
+    ZKH_TRY(zkh_read(ctx, proof, head, 0, proof_words < PROOF_HEAD_MAX ? proof_words : PROOF_HEAD_MAX));
+    ZKH_TRY(image_proof_header(who, head, proof_words));
+    const uint32_t W = head[1], D = head[2];
+    uint32_t A, h, N;
+    ZKH_TRY(page_image_shape(who, po2, zk_cycles, W, &A, &h, &N));
+    const size_t L = image_leaves(W);
+    ZKH_REQUIRE(nodes_before->len == 16 * L && nodes_after->len == 16 * L, "%s: nodes of %zu and %zu words; an image of %u words has a tree of %zu (zkh_image_tree_words)",
+                who, nodes_before->len, nodes_after->len, W, 16 * L);
+    ZKH_REQUIRE(D <= N, "%s: D %u updates, but h %u at po2 %zu leaves N %u path slots", who, D, h, po2, N);
+    const uint32_t* table = proof->ptr() + 5 + h;                     // 3 D words inside the proof: its length is what the header describes
+    Tmp tab, rec;
+    ZKH_TRY(p2_rows_tables(ctx, tab));
+    ZKH_TRY(new_buf(ctx, PR_WORDS, false, rec.out()));
+    const uint32_t rows = PJ_BLOCK * h * N;
+    {
+        ProfScope prof(ctx, "page_check", 12.0 * D + 4.0 * PR_WORDS);
+        k_page_check<<<1, PG_THREADS, 0, ctx->stream>>>(table, D, W, code->ptr(), (uint32_t)n, h, nodes_before->ptr(), nodes_after->ptr(), rec->ptr());
+        ZKH_TRY(last_launch_error("page_check"));
+    }
+    {
+        ProfScope prof(ctx, "page_paths", 4.0 * 96 * rows);
+        k_page_paths<<<(2 * N + 63) / 64, 64, 0, ctx->stream>>>(data->ptr(), (uint32_t)n, h, N, table, D, nodes_before->ptr(), nodes_after->ptr(), L, rec->ptr(), tab->ptr());
+        ZKH_TRY(last_launch_error("page_paths"));
+    }
+    {
+        ProfScope prof(ctx, "page_book", 4.0 * (PG_WD - PD_E) * rows + 4.0 * PG_WD * (n - rows));
+        k_page_book<<<dim3((rows + PG_THREADS - 1) / PG_THREADS, PG_WD - PD_E), PG_THREADS, 0, ctx->stream>>>(data->ptr(), (uint32_t)n, h, N, table, D, nodes_before->ptr(),
+                                                                                                               nodes_after->ptr(), L, rec->ptr());
+        if (rows < n) k_page_tail<<<dim3((unsigned)((n - rows + 255) / 256), PG_WD), 256, 0, ctx->stream>>>(data->ptr(), (uint32_t)n, A, rows, nk);
+        ZKH_TRY(last_launch_error("page_book"));
+    }
+    uint32_t r[PR_WORDS];
+    ZKH_TRY(zkh_read(ctx, rec, r, 0, PR_WORDS));
+    ZKH_REQUIRE(r[PR_CODE_OK], "%s: the code group was not built for h %u (zkh_page_circuit_code with this image's size)", who, h);
+    if (r[PR_ROW] != NONE) {
+        if (r[PR_A] >= W) return make_err("%s: row %u: address %u outside the image of %u words", who, r[PR_ROW], r[PR_A], W);
+        return make_err("%s: row %u: address %u does not follow a smaller one (row %u: address %u)", who, r[PR_ROW], r[PR_A], r[PR_ROW] - 1, r[PR_BEFORE]);
+    }
+    memcpy(out_roots, r + PR_ROOTS, 4 * PG_OUT);
+    return nullptr;
+}

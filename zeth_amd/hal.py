@@ -191,6 +191,8 @@ ABI = {
     "zkh_page_out_proof": (_err, [_vp, _vp, _sz, _sz, _vp, _vp, _vp, _vp]),
     "zkh_image_proof_verify": (_err, [_u32p, _sz, _u32p, _u32p]),
     "zkh_image_proof_walk": (_err, [_vp, _vp, _sz, _u32p, _u32p]),
+    "zkh_page_circuit_code": (_err, [_vp, _vp, _sz, _sz, _sz, _vp]),
+    "zkh_page_circuit_witgen": (_err, [_vp, _vp, _sz, _sz, _vp, _vp, _sz, _vp, _vp, _vp, _u32p, _u32p]),
     "zkh_circuit_derived_data_columns": (_err, [_vp, _u32p, _sz, C.POINTER(_sz)]),
     "zkh_upload_data_trace": (_err, [_vp, _vp, _sz, _sz, _vp, _u32p, _i]),
     "zkh_ctx_h2d_bytes": (_sz, [_vp]),
@@ -936,6 +938,28 @@ class HipHal:
         """the root of a committed tree: digest 1 of `nodes`, 8 words"""
         out = np.empty(DIGEST_WORDS, dtype=np.uint32)
         _check(_lib.zkh_read(self.ctx, nodes.h, _ptr(out), DIGEST_WORDS, DIGEST_WORDS))
+        return out
+
+    def page_circuit_code(self, circuit: Circuit, po2: int, zk_cycles: int, image_words: int, code: Optional[Buffer] = None) -> Buffer:
+        """the code group of P2-PAGE (circuits/p2_page.py) for (po2, zk_cycles, the tree height of an image of `image_words` words)
+        (zkh_page_circuit_code; the host twin: p2_page.reference_page_code).  code: a Buffer of 39 x 2^po2 words to write (default: a
+        new one).  Raises HalError on a circuit of another shape, W <= 8, h > 27 and a trace without room for one path"""
+        if code is None:
+            code = self.alloc_elem("code", int(circuit.desc[4]) << po2)
+        _check(_lib.zkh_page_circuit_code(self.ctx, circuit.h, po2, zk_cycles, image_words, code.h))
+        return code
+
+    def page_circuit_witgen(self, circuit: Circuit, po2: int, zk_cycles: int, code: Buffer, proof: Buffer, proof_words: int, nodes_before: Buffer,
+                            nodes_after: Buffer, data: Buffer, noise_seed: int) -> np.ndarray:
+        """the data group of P2-PAGE for the page-out a ZKU1 proof describes (zkh_page_circuit_witgen; the host twin:
+        p2_page.reference_page_trace) -> the out globals, root_before ‖ root_after (16 words).  proof: a Buffer whose first
+        `proof_words` words are the proof (only its header and table are read); nodes_before / nodes_after: the committed tree before
+        and after page_out_tree; code: page_circuit_code of the same (po2, zk_cycles, image size).  Raises HalError with one message
+        per cause (include/zkhal.h "P2-PAGE"); `data` is unspecified then"""
+        out = np.zeros(2 * DIGEST_WORDS, dtype=np.uint32)
+        _k, kp = _key_ptr(noise_seed)
+        _check(_lib.zkh_page_circuit_witgen(self.ctx, circuit.h, po2, zk_cycles, code.h, proof.h, proof_words, nodes_before.h, nodes_after.h, data.h,
+                                            _ptr(out), kp))
         return out
 
     def derive_multiplicities(self, circuit: Circuit, po2: int, zk_cycles: int, code: Buffer, data: Buffer) -> None:

@@ -318,7 +318,7 @@ class SegmentProver:
             self.page_out(seg, data, image, tree=tree)
         return receipt
 
-    def page_out(self, seg: Segment, data, image, tree=None, proof: bool = False, walk: bool = False):
+    def page_out(self, seg: Segment, data, image, tree=None, proof: bool = False, walk: bool = False, keep_before: bool = False):
         """write the page table of the segment's derived data trace (a device Buffer) back into the memory image: image[p_addr] = p_out
         on the rows with p_on = 1 (zkh_page_out).  A call of its own, after the seal: a refused witness never touches the image.
         tree: the image's committed tree (hal.image_commit of the image as it is now), brought up to the new image in the same call
@@ -326,7 +326,11 @@ class SegmentProver:
         proof: with a tree, build the update's ZKU1 proof first (zkh_page_out_proof, from the tree as it is) and return its words:
         hal.image_proof_verify(proof, the old root) gives the new root without the image.  Otherwise None is returned.
         walk: with proof, the prover checks what it ships: the proof is walked on the device (zkh_image_proof_walk) from the tree's
-        root as it is, and after the page-out the walked root must be the tree's; HalError, naming both roots, if it is not."""
+        root as it is, and after the page-out the walked root must be the tree's; HalError, naming both roots, if it is not.
+        keep_before: with proof, the tree is copied (zkh_eltwise_copy_elem) before the update and (words, the copy) is returned: the
+        two trees and the proof are what a P2-PAGE prover's `seal_page_out` takes."""
+        if keep_before and not proof:
+            raise _hal.HalError("page_out: keep_before=True needs proof=True (the copy goes with the proof)")
         if proof and tree is None:
             raise _hal.HalError("page_out: proof=True needs the image's committed tree (tree=hal.image_commit(image))")
         if walk and not proof:
@@ -341,13 +345,37 @@ class SegmentProver:
             walked = self.hal.image_proof_walk(buf, self.hal.image_root(tree), words=words.size)
         elif proof:
             words = self.hal.page_out_proof(self.circuit, seg.po2, seg.zk_cycles, data, image, tree)
+        before = None
+        if keep_before:
+            before = self.hal.alloc("image_nodes_before", tree.size())
+            self.hal.eltwise_copy_elem(before, tree)
         self.hal.page_out_tree(self.circuit, seg.po2, seg.zk_cycles, data, image, tree)
         if walked is not None:
             root = self.hal.image_root(tree)
             if not np.array_equal(walked, root):
                 fmt = lambda r: " ".join(f"{int(w):08x}" for w in r)
                 raise _hal.HalError(f"page_out: the proof walks to root {fmt(walked)}, but the tree's root after the page-out is {fmt(root)}")
-        return words
+        return (words, before) if keep_before else words
+
+    def seal_page_out(self, seg: Segment, proof, proof_words: int, nodes_before, nodes_after, check: bool = False) -> SegmentReceipt:
+        """Seal a page-out from root to root with P2-PAGE (this prover's circuit: circuits/p2_page.py): the code group for the image's
+        tree height, the witness of the ZKU1 proof's table between the two trees (zkh_page_circuit_code / _witgen), P2-JOIN's accum
+        and the two-halves seal.  proof: a device Buffer whose first `proof_words` words are the proof, or the proof's words (uploaded);
+        nodes_before / nodes_after: the committed tree before and after the page-out (`page_out(..., proof=True, keep_before=True)`).
+        The receipt's output is root_before ‖ root_after; `control_root` is the committed code group's root, which depends on the
+        tree height as well as on po2.  check: check the witness row by row first (check_witness); a table that does not match
+        the trees is named there."""
+        if not isinstance(proof, _hal.Buffer):
+            proof = self.hal.copy_from("image_proof", np.ascontiguousarray(proof, dtype=np.uint32).reshape(-1))
+        header = proof.slice(0, min(2, proof.size())).to_vec()
+        W = int(header[1]) if header.size > 1 else 0
+        wa, wc, wd = self.group_sizes()
+        code = self.hal.page_circuit_code(self.circuit, seg.po2, seg.zk_cycles, W)
+        data = self.hal.alloc_elem("data", wd << seg.po2)
+        out = self.hal.page_circuit_witgen(self.circuit, seg.po2, seg.zk_cycles, code, proof, proof_words, nodes_before, nodes_after, data, seg.noise_seed)
+        receipt = self.seal_with_accum(seg, code, data, out, self.syn_accumulate(seg, data), check=check)
+        receipt.control_root = self.code_root(code, seg.po2)
+        return receipt
 
     def prove_segment(self, seg: Segment) -> SegmentReceipt:
         code, data, out = self.witgen(seg)
