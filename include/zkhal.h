@@ -454,10 +454,28 @@ const char* zkh_image_proof_walk(zkh_ctx*, const zkh_buf* proof, size_t words, c
  * P2-PAGE's shape; buffer shape mismatch; the proof's header (zkh_image_proof_verify's messages); W <= 8; nodes of another size; D > N
  * (naming D, N, h and po2).  After the launches, from one read-back: the code group was not built for this h; row i whose address lies
  * outside the image or does not follow a smaller one (`data` is then unspecified).  The accum group is zkh_syn_accum's (P2-JOIN's
- * argument: one running product of mix + data column 0); the seal goes through zkh_prove_begin / zkh_prove_finish. */
+ * argument: one running product of mix + data column 0); the seal goes through zkh_prove_begin / zkh_prove_finish.
+ * PARTS: a table of D > N rows is sealed as a chain.  A PART is the run of updates [first, first + count) of one table, count =
+ * min(N, D - first); its trace is the circuit's as it stands, slot s holding update first + s and the slots count .. N - 1 the usual
+ * no-ops (only the last part has any, so they still open the tree after the whole page-out); its out is (the root before update
+ * `first`) ‖ (the root after update first + count - 1).  Part p + 1 opens the root part p left: the verifier of the chain checks that
+ * link, the first root and every seal, all against ONE control root.  The circuit, the code group and the accum are untouched.
+ * zkh_page_circuit_witgen_part is zkh_page_circuit_witgen for the part at `first`: the same operands (both trees are the WHOLE
+ * page-out's, whichever part is laid out: the memory an update opens is chosen by its address, so the parts are independent and can be
+ * generated in any order), the same refusals in the same order with the same text after "page_circuit_witgen_part: ", but no D > N
+ * refusal, and in its place "first F, but the table has D rows" for first >= D (first = D = 0 is the empty table's one part).  The
+ * check pass still covers the whole table and names a refused row by its index in the table.  For first > 0 the root before the part
+ * is computed on the device (h hash_pairs: the new path of update first - 1); still one read-back, no atomics.
+ * zkh_page_circuit_witgen is the part at first = 0 behind its D <= N refusal, word for word.
+ * zkh_page_circuit_slots is HOST ONLY (no context, no GPU): N for (po2, zk_cycles, an image of `image_words` words), or 0 where
+ * zkh_page_circuit_code refuses the shape.  The parts of a table of D rows start at 0, N, 2 N, ... below D (D = 0: one part at 0). */
 const char* zkh_page_circuit_code(zkh_ctx*, const zkh_circuit*, size_t po2, size_t zk_cycles, size_t image_words, zkh_buf* code);
 const char* zkh_page_circuit_witgen(zkh_ctx*, const zkh_circuit*, size_t po2, size_t zk_cycles, const zkh_buf* code, const zkh_buf* proof, size_t proof_words,
                                     const zkh_buf* nodes_before, const zkh_buf* nodes_after, zkh_buf* data, uint32_t out_roots[16], const uint32_t noise_key[8]);
+const char* zkh_page_circuit_witgen_part(zkh_ctx*, const zkh_circuit*, size_t po2, size_t zk_cycles, const zkh_buf* code, const zkh_buf* proof, size_t proof_words,
+                                         const zkh_buf* nodes_before, const zkh_buf* nodes_after, size_t first, zkh_buf* data, uint32_t out_roots[16],
+                                         const uint32_t noise_key[8]);
+size_t zkh_page_circuit_slots(size_t po2, size_t zk_cycles, size_t image_words);
 /* Everything a circuit's arguments derive, in the one order in which it is sound: sorted copies, then columns, then links, then
  * multiplicities (a LIMBS / ORDER record may read a sorted copy's column, and the multiplicities count the limbs that the records and
  * the links derive).  Call it after the data upload and before zkh_prove_begin: what it writes belongs to the data group.  It runs

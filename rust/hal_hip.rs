@@ -491,6 +491,28 @@ impl HipCircuitHal {
         roots
     }
 
+    /// N, the path slots of a P2-PAGE trace of `steps` rows over an image of `image_words` words (`zkh_page_circuit_slots`): host only, no
+    /// GPU; 0 where `page_circuit_code` refuses the shape.  A table of D rows is sealed as the parts that start at 0, N, 2 N, ... below
+    /// D (D = 0: one part at 0).
+    pub fn page_circuit_slots(image_words: usize, steps: usize) -> usize {
+        unsafe { sys::zkh_page_circuit_slots(steps.trailing_zeros() as usize, sys::ZK_CYCLES, image_words) }
+    }
+
+    /// The data group of P2-PAGE for ONE PART of a page-out (`zkh_page_circuit_witgen_part`): the updates `first .. first + min(N, D -
+    /// first)` of the proof's table, and the `out` globals, the root before update `first` then the root after the part's last update.
+    /// The other operands are `page_circuit_witgen`'s; both trees are the whole page-out's for every part, so the parts can be generated
+    /// in any order.  Part p + 1 opens the root part p left.  Panics as `page_circuit_witgen` does, but on `first >= D` (unless both
+    /// are 0) where that refuses more updates than the trace has paths.
+    pub fn page_circuit_witgen_part(&self, code: &HipBuffer<BabyBearElem>, proof: &HipBuffer<u32>, words: usize, nodes_before: &HipBuffer<BabyBearElem>,
+                                    nodes_after: &HipBuffer<BabyBearElem>, first: usize, data: &HipBuffer<BabyBearElem>, steps: usize,
+                                    noise_key: Option<&[u32; 8]>) -> [u32; 16] {
+        let po2 = steps.trailing_zeros() as usize;
+        let mut roots = [0u32; 16];
+        ffi(|| unsafe { sys::zkh_page_circuit_witgen_part(self.hal.ctx.0, self.circuit, po2, sys::ZK_CYCLES, code.raw, proof.raw, words, nodes_before.raw,
+                                                          nodes_after.raw, first, data.raw, roots.as_mut_ptr(), noise_key.map_or(std::ptr::null(), |k| k.as_ptr())) });
+        roots
+    }
+
     /// Check the raw traces against the circuit's own constraints on every row of `rows` (`zkh_check_rows`): which constraint a
     /// witness breaks, and where, before a seal is spent on it.  `out` and `mix` are the global words.  `row < 0`: no row of the window
     /// fails; otherwise the lowest failing row, its lowest failing `and_eqz` step (an index into the ZKC1 step list), how many rows of

@@ -15,7 +15,9 @@ pages spread over the whole image and a sparse one of 4096 pages, at two image s
 zkh_page_out_proof next to zkh_page_out_tree on M18's tables and image sizes, alternating, with the proof's size; M20: the walk of
 that proof on the device, zkh_image_proof_walk next to the host walk of the downloaded proof (zkh_image_proof_verify), the download and
 zkh_page_out_tree, alternating, with the number of permutations; M21: P2-PAGE's witness, zkh_page_circuit_witgen with full slots at
-h = 17 and h = 23 next to zkh_syn_witgen of P2-JOIN at the same po2, alternating, with both calls' stages) on one MI355X, through the C ABI (HipHal).
+h = 17 and h = 23 next to zkh_syn_witgen of P2-JOIN at the same po2, alternating, with both calls' stages; M22: P2-PAGE's parts,
+zkh_page_circuit_witgen_part on a table of 4 N rows at first = 0, N, 2 N, 3 N next to zkh_page_circuit_witgen on its first N rows,
+alternating, with every call's stages) on one MI355X, through the C ABI (HipHal).
 
 Each line of output is one JSON object: the op, its shape, the average wall time of one call (stream drained on both
 sides of `reps` back-to-back calls), its ALGORITHMIC bytes (SURVEY.md §8a "B_alg": inputs read once + outputs written
@@ -963,6 +965,77 @@ def main() -> None:
                               "per_block_ratio": round((steps["page_paths"]["ms_per_call"] / (h * N)) / (steps["p2join_blocks"]["ms_per_call"] / K), 3)}), flush=True)
             del before, after, proof, pcode
         del jcode, jdata, pdata
+    if want("M22"):
+        # P2-PAGE's parts: zkh_page_circuit_witgen_part on a table of 4 N rows at first = 0, N, 2 N, 3 N (every slot full; the parts after
+        # the first walk the root before them, k_page_root: h hash_pairs in one lane after the paths; the parts before the last copy the
+        # root they leave out of the rows), next to zkh_page_circuit_witgen on the table's first N rows between the trees of THAT
+        # page-out.  M21's setup and windows: `runs` alternating windows of `reps` calls, median and spread, then every call's stages by
+        # their events.  The parts' roots must chain from the tree before to the tree after, and part 0 must leave the root of the N-row
+        # page-out's tree.
+        from zeth_amd import hal as zhal
+        from zeth_amd.circuits import p2_page
+        runs, zk = 7, 1994
+        spread = lambda ts: {"median_ms": round(float(np.median(ts)) * 1e3, 4), "min_ms": round(min(ts) * 1e3, 4), "max_ms": round(max(ts) * 1e3, 4)}   # noqa: E731
+        page = hal.load_circuit(p2_page.p2_page_circuit())
+        pdata = hal.alloc_elem("m22pd", p2_page.WD * n)
+        u32p = zhal._u32p
+        key = zhal.noise_key(0x2E80)
+        for W in (1 << 20, 1 << 26):
+            h = p2_page.tree_height(W)
+            N = p2_page.slots(args.po2, zk, h)
+            assert int(zhal._lib.zkh_page_circuit_slots(args.po2, zk, W)) == N
+            D = 4 * N
+            image_h = rand_fp(rng, W)
+            addrs = np.unique(rng.integers(0, W, D + D // 8))
+            addrs = np.sort(addrs[rng.choice(addrs.size, D, replace=False)]).astype(np.int64)
+            outs = rand_fp(rng, D)
+            table = np.stack([addrs.astype(np.uint32), image_h[addrs], outs], axis=1).reshape(-1)
+            head = lambda rows: np.array([0x5A4B5531, W, rows, 0, h] + [0] * h, dtype=np.uint32)   # noqa: E731
+            proof_h, proof1_h = np.concatenate([head(D), table]), np.concatenate([head(N), table[:3 * N]])
+            image = hal.alloc_elem("m22i", W)
+            image.write(image_h)
+            before = hal.image_commit(image)
+            image_h[addrs[:N]] = outs[:N]
+            image.write(image_h)
+            after1 = hal.image_commit(image)
+            image_h[addrs] = outs
+            image.write(image_h)
+            after = hal.image_commit(image)
+            del image
+            proof, proof1 = hal.copy_from("m22p", proof_h), hal.copy_from("m22p1", proof1_h)
+            pcode = hal.page_circuit_code(page, args.po2, zk, W)
+            roots = np.zeros(16, dtype=np.uint32)
+            whole_fn = lambda: zhal._check(zhal._lib.zkh_page_circuit_witgen(hal.ctx, page.h, args.po2, zk, pcode.h, proof1.h, proof1_h.size, before.h, after1.h, pdata.h,   # noqa: E731
+                                                                             roots.ctypes.data_as(u32p), key.ctypes.data_as(u32p)))
+            part_fn = lambda first: lambda: zhal._check(zhal._lib.zkh_page_circuit_witgen_part(hal.ctx, page.h, args.po2, zk, pcode.h, proof.h, proof_h.size, before.h,   # noqa: E731
+                                                                                               after.h, first, pdata.h, roots.ctypes.data_as(u32p), key.ctypes.data_as(u32p)))
+            fns = [("page_circuit_witgen", whole_fn)] + [(f"part_first_{p}N", part_fn(p * N)) for p in range(4)]
+            chain = []
+            for name, fn in fns:
+                fn()
+                chain.append(roots.copy())
+            assert np.array_equal(chain[0][:8], hal.image_root(before)) and np.array_equal(chain[0][8:], hal.image_root(after1))
+            assert np.array_equal(chain[1], chain[0]), "part 0 of the long table does not leave the root of the N-row page-out"
+            assert all(np.array_equal(chain[p][8:], chain[p + 1][:8]) for p in range(1, 4)) and np.array_equal(chain[4][8:], hal.image_root(after))
+            t = {name: [] for name, _ in fns}
+            for _ in range(runs):
+                for name, fn in fns:
+                    t[name].append(timed(hal, fn, args.reps))
+            steps = {}
+            for name, fn in fns:
+                hal.prof_enable(True)
+                hal.prof_reset()
+                for _ in range(args.reps):
+                    fn()
+                hal.sync()
+                steps[name] = {r["name"]: {"calls_per_call": r["calls"] // args.reps, "ms_per_call": round(r["total_ms"] / args.reps, 4)} for r in hal.prof_get()
+                               if r["calls"] and r["name"].startswith("page_")}
+                hal.prof_enable(False)
+            print(json.dumps({"bench": "M22", "library": os.path.basename(os.environ.get("ZKH_LIBRARY", "") or "libzkhal_mi355x.so"), "po2": args.po2,
+                              "image_words": W, "layers": h, "slots": N, "table_rows": D, "runs": runs, "reps": args.reps,
+                              **{k: spread(v) for k, v in t.items()}, "steps": steps}), flush=True)
+            del before, after, after1, proof, proof1, pcode
+        del pdata
     hal.close()
 
 

@@ -28,6 +28,9 @@ address 0 (in = out = the word held there): real paths that satisfy every constr
   accum: P2-JOIN's argument verbatim, one Fp4 running product of (mix + data column 0) (data column 0 is S_old[0]).
 Globals: out = root_before (8) ‖ root_after (8);  mix = 4 words.
 The address is rebuilt in the field, so 2^(3 + h) must stay below P: h <= MAX_H = 27 (images of at most 2^30 words).
+
+A table of D > N rows is sealed as a chain of PARTS (`parts`, `reference_page_part`; DESIGN.md "PARTS"): the same circuit on the run of
+updates [first, first + min(N, D - first)), out = the root before update `first` ‖ the root after the run's last update.
 """
 from __future__ import annotations
 
@@ -352,6 +355,29 @@ def reference_page_trace(po2: int, zk_cycles: int, W: int, table: Sequence[Tuple
         if d_old != cur or d_new != nodes[1]:
             raise AssertionError(f"slot {s}: the paths' top digests are not the tree's roots")
     return data, np.asarray(root_before, dtype=np.uint32), np.asarray(nodes[1], dtype=np.uint32)
+
+
+def parts(po2: int, zk_cycles: int, W: int, D: int) -> List[Tuple[int, int]]:
+    """The plan of a page-out of D rows over an image of W words as a chain of P2-PAGE traces: [(first, count), ...], part p the updates
+    [first, first + count) with count = min(N, D - first), so only the last part has no-op slots.  D = 0 is the one part (0, 0)."""
+    N = slots(po2, zk_cycles, tree_height(W)) if W > 8 else 0
+    if N < 1:
+        raise ValueError(f"no path slot for an image of {W} words at po2 {po2} with {zk_cycles} zk_cycles")
+    return [(first, min(N, D - first)) for first in range(0, D, N)] or [(0, 0)]
+
+
+def reference_page_part(po2: int, zk_cycles: int, W: int, table: Sequence[Tuple[int, int, int]], image_before, first: int):
+    """-> (data, root_before, root_after) of the part of `table` that starts at update `first`, as reference_page_trace gives them: the
+    updates [0, first) are applied to a copy of the image in plain numpy, and the rows [first, first + N) are then a whole table over
+    that image.  No tree code of its own: the yardstick of zkh_page_circuit_witgen_part, which reads both trees of the WHOLE page-out."""
+    D = len(table)
+    if not (0 <= first < D or first == D == 0):
+        raise ValueError(f"first {first}, but the table has {D} rows")
+    image = np.array(image_before, dtype=np.uint32).reshape(-1)
+    for a, _, w_out in table[:first]:
+        image[int(a)] = int(w_out)
+    N = slots(po2, zk_cycles, tree_height(W))
+    return reference_page_trace(po2, zk_cycles, W, table[first:first + N], image)
 
 
 if __name__ == "__main__":      # python -m zeth_amd.circuits.p2_page out.desc   (blob for non-Python hosts)

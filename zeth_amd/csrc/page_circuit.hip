@@ -15,12 +15,22 @@
 // page-out.  The Python yardstick (p2_page.reference_page_trace) applies the updates one at a time to one tree and shares nothing
 // with this.
 //
+// PARTS.  A table of D > N rows is sealed as a chain of parts (zkh_page_circuit_witgen_part): the part at `first` lays out the updates
+// [first, first + count), count = min(N, D - first), slot s holding update first + s.  The memory an update opens is chosen by its
+// ADDRESS alone, so a part reads the same two trees as the whole table would and needs no tree of its own; what it does need is the
+// root its first path opens, the tree with the updates [0, first) applied.  That root is the top of the NEW path of update first - 1
+// under the same shortcut: k_page_root walks it, h hash_pairs in one lane, and writes no rows.  Only the last part has slots left
+// over, so a no-op still opens the tree after the whole page-out.  The root a part that is not the last leaves is the top of its slot
+// N - 1's new path, which k_page_root copies out of the rows.
+//
 // KERNELS.  k_page_check: ONE workgroup; the lowest row of the table whose address is outside the image or does not follow a smaller
 // one (an LDS minimum, no atomics), whether the code group was built for this h, and digest 1 of both trees, into a record of 24 words.
 // k_page_paths: one lane per (slot, old / new) walks its h blocks with the literal permutation of k_p2join_blocks; it returns at once
-// when the record holds a refusal, so no address at or past W ever indexes `nodes_*`.  k_page_book: one lane per (row, bookkeeping
-// column); `cur` of slot s > 0 is read from the output row the path kernel wrote for slot s - 1.  k_page_tail: zero rows, then the
-// blinding rows.  No atomics, every cell has one writer; one read-back fetches the record at the end.
+// when the record holds a refusal, so no address at or past W ever indexes `nodes_*`.  k_page_root (parts only: first > 0, or a part
+// that is not the last): the record's roots that k_page_check does not own.  k_page_book: one lane per (row, bookkeeping column);
+// `cur` of slot 0 is the record's first root, of slot s > 0 it is read from the output row the path kernel wrote for slot s - 1.
+// k_page_tail: zero rows, then the blinding rows.  No atomics, every cell (of the record too) has one writer; one read-back fetches
+// the record at the end.
 #include "circuit.h"
 #include "image_tree.h"
 #include "p2_rows.h"
@@ -35,6 +45,7 @@ enum : uint32_t { PC_LIN = 3, PC_FULLR, PC_PARTR, PC_LF, PC_LP, PC_LEAF_IN, PC_N
 // data columns (p2_page.py D_*)
 enum : uint32_t { PD_SO = 0, PD_QO = 24, PD_SN = 48, PD_QN = 72, PD_E = 96, PD_B = 112, PD_ADDR = 113, PD_W_IN = 114, PD_W_OUT = 115, PD_ACC = 116, PD_CUR = 117 };
 // the record: the lowest refused row (NONE: none), its address, the address before it, whether the code group is this h's, both roots
+// (the one the trace's first path opens, the one its last path leaves)
 enum : uint32_t { PR_ROW = 0, PR_A = 1, PR_BEFORE = 2, PR_CODE_OK = 3, PR_ROOTS = 8, PR_WORDS = 24 };
 constexpr uint32_t NONE = 0xffffffffu;
 constexpr uint32_t PG_THREADS = 256;
@@ -71,11 +82,12 @@ __global__ void k_page_code(uint32_t* code, uint32_t n, uint32_t A, uint32_t h, 
     code[(size_t)col * n + r] = v;
 }
 
-// ONE workgroup over the table's D rows (stride 3, the address first).  No kernel reads `nodes_*` at an address of the table before
-// this record says that every address is below W.
+// ONE workgroup over the table's D rows (stride 3, the address first): the WHOLE table, whichever part is laid out.  No kernel reads
+// `nodes_*` at an address of the table before this record says that every address is below W.  The roots: digest 1 of the tree before
+// when the part starts the table (first = 0), of the tree after when it ends it (D - first <= N); k_page_root owns the others.
 __global__ __launch_bounds__(PG_THREADS) void k_page_check(const uint32_t* __restrict__ table, uint32_t D, uint32_t W, const uint32_t* __restrict__ code, uint32_t n,
-                                                           uint32_t h, const uint32_t* __restrict__ nodes_before, const uint32_t* __restrict__ nodes_after,
-                                                           uint32_t* __restrict__ rec) {
+                                                           uint32_t h, uint32_t N, uint32_t first, const uint32_t* __restrict__ nodes_before,
+                                                           const uint32_t* __restrict__ nodes_after, uint32_t* __restrict__ rec) {
     __shared__ uint32_t low[PG_THREADS];
     const uint32_t t = threadIdx.x;
     uint32_t bad = NONE;
@@ -99,20 +111,21 @@ __global__ __launch_bounds__(PG_THREADS) void k_page_check(const uint32_t* __res
         const bool pow = h == 1 || code[(size_t)PC_POW * n + PJ_BLOCK * (h - 1)] == encode(1u << (2 + h));
         rec[PR_CODE_OK] = top && pow;
     }
-    if (t >= 8 && t < 16) rec[t] = nodes_before[t];                   // digest 1 = words [8, 16)
-    if (t >= 16 && t < 24) rec[t] = nodes_after[t - 8];
+    if (t >= 8 && t < 16 && first == 0) rec[t] = nodes_before[t];     // digest 1 = words [8, 16)
+    if (t >= 16 && t < 24 && D - first <= N) rec[t] = nodes_after[t - 8];
 }
 
-// One lane per (slot, side): side 0 the old path, 1 the new one.  L = the tree's leaves (2^h), words of layer t's node x at
-// 8 ((L >> t) + x); the leaf layer is the memory itself at words [8 L, 16 L).
+// One lane per (slot, side): side 0 the old path, 1 the new one.  Slot s holds the table's row first + s (first < D < 2^31, s < N <
+// 2^26: the sum does not wrap).  L = the tree's leaves (2^h), words of layer t's node x at 8 ((L >> t) + x); the leaf layer is the
+// memory itself at words [8 L, 16 L).
 __global__ __launch_bounds__(64) void k_page_paths(uint32_t* __restrict__ data, uint32_t n, uint32_t h, uint32_t N, const uint32_t* __restrict__ table, uint32_t D,
-                                                   const uint32_t* __restrict__ nodes_before, const uint32_t* __restrict__ nodes_after, size_t L,
+                                                   uint32_t first, const uint32_t* __restrict__ nodes_before, const uint32_t* __restrict__ nodes_after, size_t L,
                                                    const uint32_t* __restrict__ rec, const uint32_t* __restrict__ tab) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= 2 * N || rec[PR_ROW] != NONE) return;
     const uint32_t slot = i >> 1, side = i & 1;
-    const bool real = slot < D;
-    const uint32_t a = real ? table[3 * (size_t)slot] : 0;             // < W <= 8 L: the record holds no refusal
+    const bool real = first + slot < D;
+    const uint32_t a = real ? table[3 * (size_t)(first + slot)] : 0;   // < W <= 8 L: the record holds no refusal
     const uint32_t* before = real ? nodes_before : nodes_after;        // a no-op opens the tree after the page-out
     const uint32_t s_col = side ? PD_SN : PD_SO, q_col = side ? PD_QN : PD_QO;
     const uint32_t* diag = tab + PJ_T * PJ_ROUNDS;
@@ -168,23 +181,65 @@ __global__ __launch_bounds__(64) void k_page_paths(uint32_t* __restrict__ data, 
     }
 }
 
+// ONE wave, after k_page_paths, launched only for a part that does not start the table or does not end it: the roots of the record
+// that are not digest 1 of a tree.  Lane 0, first > 0: the root BEFORE the part = the tree with the updates [0, first) applied = the
+// top of the new path of update first - 1, walked as k_page_paths walks a new side (the update's own word and everything below it from
+// `nodes_after`, everything above from `nodes_before`) but as h bare hash_pairs (k_hash_walk's lane body, hash.hip): no rows.  Lanes
+// 8 .. 15, a part that is not the last: the root AFTER it, the output row of slot N - 1's new path.  It returns at once on a refusal,
+// as the path kernel does; `rec` is read and written here (distinct cells), hence no __restrict__ on it.
+__global__ __launch_bounds__(64) void k_page_root(const uint32_t* __restrict__ data, uint32_t n, uint32_t h, uint32_t N, const uint32_t* __restrict__ table, uint32_t D,
+                                                  uint32_t first, const uint32_t* __restrict__ nodes_before, const uint32_t* __restrict__ nodes_after, size_t L,
+                                                  uint32_t* rec, const uint32_t* __restrict__ rc, const uint32_t* __restrict__ diag) {
+    const uint32_t lane = threadIdx.x;
+    if (rec[PR_ROW] != NONE) return;
+    if (lane >= 8 && lane < 16 && D - first > N) rec[PR_ROOTS + lane] = data[(size_t)(PD_SN + lane - 8) * n + (size_t)PJ_BLOCK * h * N - 1];
+    if (lane != 0 || first == 0) return;
+    const uint32_t a = table[3 * (size_t)(first - 1)];                 // < W <= 8 L: the record holds no refusal
+    uint32_t s[CELLS];
+    for (uint32_t t = 0; t < h; t++) {
+        if (t == 0) {
+            const uint32_t x0 = a & ~15u;
+#pragma unroll
+            for (uint32_t j = 0; j < 16; j++) s[j] = (x0 + j <= a ? nodes_after : nodes_before)[8 * L + x0 + j];
+        } else {
+            const uint32_t x = a >> (3 + t);
+            const bool right = x & 1;
+            const uint32_t* sib = (right ? nodes_after : nodes_before) + 8 * ((L >> t) + (x ^ 1));
+#pragma unroll
+            for (uint32_t j = 0; j < 8; j++) {
+                const uint32_t own = s[j], other = sib[j];
+                s[j] = right ? other : own;
+                s[8 + j] = right ? own : other;
+            }
+        }
+#pragma unroll
+        for (int j = RATE; j < CELLS; j++) s[j] = 0;
+        poseidon2_mix_raw<0, OUT, RATE>(s, rc, diag);
+#pragma unroll
+        for (int j = 0; j < OUT; j++) s[j] = p2_finish(s[j]);
+    }
+#pragma unroll
+    for (uint32_t j = 0; j < 8; j++) rec[PR_ROOTS + j] = s[j];
+}
+
 // grid (ceil(31 h N / 256), 29): the bookkeeping columns e, b, addr, w_in, w_out, acc, cur of the rows of the paths, after k_page_paths
+// (and k_page_root, where it runs: `cur` of slot 0 is the record's first root)
 __global__ __launch_bounds__(PG_THREADS) void k_page_book(uint32_t* __restrict__ data, uint32_t n, uint32_t h, uint32_t N, const uint32_t* __restrict__ table, uint32_t D,
-                                                          const uint32_t* __restrict__ nodes_before, const uint32_t* __restrict__ nodes_after, size_t L,
-                                                          const uint32_t* __restrict__ rec) {
+                                                          uint32_t first, const uint32_t* __restrict__ nodes_after, size_t L, const uint32_t* __restrict__ rec) {
     const uint32_t r = blockIdx.x * PG_THREADS + threadIdx.x, col = PD_E + blockIdx.y;
     if (r >= PJ_BLOCK * h * N || rec[PR_ROW] != NONE) return;
     const uint32_t k = r % PJ_BLOCK, blk = r / PJ_BLOCK, t = blk % h, slot = blk / h;
-    const bool real = slot < D;
-    const uint32_t a = real ? table[3 * (size_t)slot] : 0;
+    const bool real = first + slot < D;
+    const size_t row = (size_t)first + slot;
+    const uint32_t a = real ? table[3 * row] : 0;
     uint32_t v = 0;
     if (col < PD_B) v = (k == 0 && t == 0 && (a & 15) == col - PD_E) ? R1 : 0;
     else if (col == PD_B) v = (k == 0 && t > 0 && ((a >> (3 + t)) & 1)) ? R1 : 0;
     else if (col == PD_ADDR) v = encode(a);
-    else if (col == PD_W_IN) v = real ? table[3 * (size_t)slot + 1] : nodes_after[8 * L];
-    else if (col == PD_W_OUT) v = real ? table[3 * (size_t)slot + 2] : nodes_after[8 * L];
+    else if (col == PD_W_IN) v = real ? table[3 * row + 1] : nodes_after[8 * L];
+    else if (col == PD_W_OUT) v = real ? table[3 * row + 2] : nodes_after[8 * L];
     else if (col == PD_ACC) v = encode(a & ((1u << (4 + t)) - 1));
-    else v = slot ? data[(size_t)(PD_SN + col - PD_CUR) * n + (size_t)PJ_BLOCK * h * slot - 1] : nodes_before[8 + col - PD_CUR];
+    else v = slot ? data[(size_t)(PD_SN + col - PD_CUR) * n + (size_t)PJ_BLOCK * h * slot - 1] : rec[PR_ROOTS + col - PD_CUR];
     data[(size_t)col * n + r] = v;
 }
 
@@ -195,11 +250,12 @@ __global__ void k_page_tail(uint32_t* data, uint32_t n, uint32_t A, uint32_t fir
     data[(size_t)col * n + r] = r < A ? 0u : noise_cell(nk, GROUP_DATA, col, r);
 }
 
-// the checks the two entry points share.  First the circuit's shape and the trace's size ...
+// the checks the entry points share.  First the circuit's shape and the trace's size ...
+inline bool page_po2_ok(size_t po2, size_t zk_cycles) { return po2 >= 1 && po2 <= 30 && ((size_t)1 << po2) > zk_cycles + 1; }
 const char* page_circuit_shape(const char* who, const zkh_circuit* c, size_t po2, size_t zk_cycles) {
     ZKH_REQUIRE(c->kind == 5 && c->group_size[GROUP_CODE] == PG_WC && c->group_size[GROUP_DATA] == PG_WD && c->group_size[GROUP_ACCUM] == 4 &&
                 c->global_size[GLOBAL_OUT] == PG_OUT, "%s: the circuit does not have P2-PAGE's shape (kind 5, 39 / 125 / 4 columns, 16 outputs)", who);
-    ZKH_REQUIRE(po2 >= 1 && po2 <= 30 && ((size_t)1 << po2) > zk_cycles + 1, "%s: po2 %zu out of range for %zu zk_cycles", who, po2, zk_cycles);
+    ZKH_REQUIRE(page_po2_ok(po2, zk_cycles), "%s: po2 %zu out of range for %zu zk_cycles", who, po2, zk_cycles);
     return nullptr;
 }
 // ... then the image's -> A, h, N
@@ -212,6 +268,71 @@ const char* page_image_shape(const char* who, size_t po2, size_t zk_cycles, size
     *h_out = h;
     *N_out = *A_out / PJ_BLOCK / h;
     ZKH_REQUIRE(*N_out >= 1, "%s: no room for a path of h %u blocks of 31 rows in %u active rows (po2 %zu)", who, h, *A_out, po2);
+    return nullptr;
+}
+
+// Both generators.  `whole`: zkh_page_circuit_witgen, the table as one trace (first = 0, D <= N or refused); else the part at `first`.
+const char* page_witgen(const char* who, bool whole, zkh_ctx* ctx, const zkh_circuit* c, size_t po2, size_t zk_cycles, const zkh_buf* code, const zkh_buf* proof,
+                        size_t proof_words, const zkh_buf* nodes_before, const zkh_buf* nodes_after, size_t first_row, zkh_buf* data, uint32_t* out_roots,
+                        const uint32_t* noise_key) {
+    ZKH_REQUIRE(ctx && c && code && proof && nodes_before && nodes_after && data && out_roots, "%s: null argument", who);
+    ZKH_TRY(page_circuit_shape(who, c, po2, zk_cycles));
+    const size_t n = (size_t)1 << po2;
+    ZKH_REQUIRE(code->len == (size_t)PG_WC * n && data->len == (size_t)PG_WD * n, "%s: buffer shape mismatch (the code group is an input of this generator)", who);
+    ZKH_REQUIRE(proof_words <= proof->len && proof_words <= 0xffffffffull, "%s: a proof of %zu words in a buffer of %zu", who, proof_words, proof->len);
+    NoiseKey nk;
+    ZKH_TRY(resolve_noise_key(noise_key, &nk));
+    bind_thread(ctx);
+    uint32_t head[PROOF_HEAD_MAX] = {0};
+    ZKH_TRY(zkh_read(ctx, proof, head, 0, proof_words < PROOF_HEAD_MAX ? proof_words : PROOF_HEAD_MAX));
+    ZKH_TRY(image_proof_header(who, head, proof_words));
+    const uint32_t W = head[1], D = head[2];
+    uint32_t A, h, N;
+    ZKH_TRY(page_image_shape(who, po2, zk_cycles, W, &A, &h, &N));
+    const size_t L = image_leaves(W);
+    ZKH_REQUIRE(nodes_before->len == 16 * L && nodes_after->len == 16 * L, "%s: nodes of %zu and %zu words; an image of %u words has a tree of %zu (zkh_image_tree_words)",
+                who, nodes_before->len, nodes_after->len, W, 16 * L);
+    if (whole) ZKH_REQUIRE(D <= N, "%s: D %u updates, but h %u at po2 %zu leaves N %u path slots", who, D, h, po2, N);
+    else ZKH_REQUIRE(first_row < D || (first_row == 0 && D == 0), "%s: first %zu, but the table has %u rows", who, first_row, D);
+    const uint32_t first = (uint32_t)first_row;                       // < D, and 3 D words fit the proof: D < 2^31
+    const bool own_roots = first || D - first > N;                    // a root of this part is not digest 1 of a tree: k_page_root
+    const uint32_t* table = proof->ptr() + 5 + h;                     // 3 D words inside the proof: its length is what the header describes
+    Tmp tab, rec;
+    ZKH_TRY(p2_rows_tables(ctx, tab));
+    ZKH_TRY(new_buf(ctx, PR_WORDS, false, rec.out()));
+    const uint32_t rows = PJ_BLOCK * h * N;
+    {
+        ProfScope prof(ctx, "page_check", 12.0 * D + 4.0 * PR_WORDS);
+        k_page_check<<<1, PG_THREADS, 0, ctx->stream>>>(table, D, W, code->ptr(), (uint32_t)n, h, N, first, nodes_before->ptr(), nodes_after->ptr(), rec->ptr());
+        ZKH_TRY(last_launch_error("page_check"));
+    }
+    {
+        ProfScope prof(ctx, "page_paths", 4.0 * 96 * rows);
+        k_page_paths<<<(2 * N + 63) / 64, 64, 0, ctx->stream>>>(data->ptr(), (uint32_t)n, h, N, table, D, first, nodes_before->ptr(), nodes_after->ptr(), L, rec->ptr(),
+                                                                tab->ptr());
+        ZKH_TRY(last_launch_error("page_paths"));
+    }
+    if (own_roots) {
+        ProfScope prof(ctx, "page_root", 4.0 * 16 * h);
+        k_page_root<<<1, 64, 0, ctx->stream>>>(data->ptr(), (uint32_t)n, h, N, table, D, first, nodes_before->ptr(), nodes_after->ptr(), L, rec->ptr(), ctx->tab.rc,
+                                               ctx->tab.diag);
+        ZKH_TRY(last_launch_error("page_root"));
+    }
+    {
+        ProfScope prof(ctx, "page_book", 4.0 * (PG_WD - PD_E) * rows + 4.0 * PG_WD * (n - rows));
+        k_page_book<<<dim3((rows + PG_THREADS - 1) / PG_THREADS, PG_WD - PD_E), PG_THREADS, 0, ctx->stream>>>(data->ptr(), (uint32_t)n, h, N, table, D, first,
+                                                                                                               nodes_after->ptr(), L, rec->ptr());
+        if (rows < n) k_page_tail<<<dim3((unsigned)((n - rows + 255) / 256), PG_WD), 256, 0, ctx->stream>>>(data->ptr(), (uint32_t)n, A, rows, nk);
+        ZKH_TRY(last_launch_error("page_book"));
+    }
+    uint32_t r[PR_WORDS];
+    ZKH_TRY(zkh_read(ctx, rec, r, 0, PR_WORDS));
+    ZKH_REQUIRE(r[PR_CODE_OK], "%s: the code group was not built for h %u (zkh_page_circuit_code with this image's size)", who, h);
+    if (r[PR_ROW] != NONE) {
+        if (r[PR_A] >= W) return make_err("%s: row %u: address %u outside the image of %u words", who, r[PR_ROW], r[PR_A], W);
+        return make_err("%s: row %u: address %u does not follow a smaller one (row %u: address %u)", who, r[PR_ROW], r[PR_A], r[PR_ROW] - 1, r[PR_BEFORE]);
+    }
+    memcpy(out_roots, r + PR_ROOTS, 4 * PG_OUT);
     return nullptr;
 }
 
@@ -232,57 +353,21 @@ extern "C" const char* zkh_page_circuit_code(zkh_ctx* ctx, const zkh_circuit* c,
     return last_launch_error("page_code");
 }
 
+// HOST ONLY: N of (po2, zk_cycles, an image of `image_words` words), 0 where zkh_page_circuit_code refuses the shape
+extern "C" size_t zkh_page_circuit_slots(size_t po2, size_t zk_cycles, size_t image_words) {
+    uint32_t A, h, N;
+    return page_po2_ok(po2, zk_cycles) && !page_image_shape("page_circuit_slots", po2, zk_cycles, image_words, &A, &h, &N) ? N : 0;
+}
+
 extern "C" const char* zkh_page_circuit_witgen(zkh_ctx* ctx, const zkh_circuit* c, size_t po2, size_t zk_cycles, const zkh_buf* code, const zkh_buf* proof,
                                                size_t proof_words, const zkh_buf* nodes_before, const zkh_buf* nodes_after, zkh_buf* data,
                                                uint32_t out_roots[16], const uint32_t* noise_key) {
-    static const char who[] = "page_circuit_witgen";
-    ZKH_REQUIRE(ctx && c && code && proof && nodes_before && nodes_after && data && out_roots, "%s: null argument", who);
-    ZKH_TRY(page_circuit_shape(who, c, po2, zk_cycles));
-    const size_t n = (size_t)1 << po2;
-    ZKH_REQUIRE(code->len == (size_t)PG_WC * n && data->len == (size_t)PG_WD * n, "%s: buffer shape mismatch (the code group is an input of this generator)", who);
-    ZKH_REQUIRE(proof_words <= proof->len && proof_words <= 0xffffffffull, "%s: a proof of %zu words in a buffer of %zu", who, proof_words, proof->len);
-    NoiseKey nk;
-    ZKH_TRY(resolve_noise_key(noise_key, &nk));
-    bind_thread(ctx);
-    uint32_t head[PROOF_HEAD_MAX] = {0};
-    ZKH_TRY(zkh_read(ctx, proof, head, 0, proof_words < PROOF_HEAD_MAX ? proof_words : PROOF_HEAD_MAX));
-    ZKH_TRY(image_proof_header(who, head, proof_words));
-    const uint32_t W = head[1], D = head[2];
-    uint32_t A, h, N;
-    ZKH_TRY(page_image_shape(who, po2, zk_cycles, W, &A, &h, &N));
-    const size_t L = image_leaves(W);
-    ZKH_REQUIRE(nodes_before->len == 16 * L && nodes_after->len == 16 * L, "%s: nodes of %zu and %zu words; an image of %u words has a tree of %zu (zkh_image_tree_words)",
-                who, nodes_before->len, nodes_after->len, W, 16 * L);
-    ZKH_REQUIRE(D <= N, "%s: D %u updates, but h %u at po2 %zu leaves N %u path slots", who, D, h, po2, N);
-    const uint32_t* table = proof->ptr() + 5 + h;                     // 3 D words inside the proof: its length is what the header describes
-    Tmp tab, rec;
-    ZKH_TRY(p2_rows_tables(ctx, tab));
-    ZKH_TRY(new_buf(ctx, PR_WORDS, false, rec.out()));
-    const uint32_t rows = PJ_BLOCK * h * N;
-    {
-        ProfScope prof(ctx, "page_check", 12.0 * D + 4.0 * PR_WORDS);
-        k_page_check<<<1, PG_THREADS, 0, ctx->stream>>>(table, D, W, code->ptr(), (uint32_t)n, h, nodes_before->ptr(), nodes_after->ptr(), rec->ptr());
-        ZKH_TRY(last_launch_error("page_check"));
-    }
-    {
-        ProfScope prof(ctx, "page_paths", 4.0 * 96 * rows);
-        k_page_paths<<<(2 * N + 63) / 64, 64, 0, ctx->stream>>>(data->ptr(), (uint32_t)n, h, N, table, D, nodes_before->ptr(), nodes_after->ptr(), L, rec->ptr(), tab->ptr());
-        ZKH_TRY(last_launch_error("page_paths"));
-    }
-    {
-        ProfScope prof(ctx, "page_book", 4.0 * (PG_WD - PD_E) * rows + 4.0 * PG_WD * (n - rows));
-        k_page_book<<<dim3((rows + PG_THREADS - 1) / PG_THREADS, PG_WD - PD_E), PG_THREADS, 0, ctx->stream>>>(data->ptr(), (uint32_t)n, h, N, table, D, nodes_before->ptr(),
-                                                                                                               nodes_after->ptr(), L, rec->ptr());
-        if (rows < n) k_page_tail<<<dim3((unsigned)((n - rows + 255) / 256), PG_WD), 256, 0, ctx->stream>>>(data->ptr(), (uint32_t)n, A, rows, nk);
-        ZKH_TRY(last_launch_error("page_book"));
-    }
-    uint32_t r[PR_WORDS];
-    ZKH_TRY(zkh_read(ctx, rec, r, 0, PR_WORDS));
-    ZKH_REQUIRE(r[PR_CODE_OK], "%s: the code group was not built for h %u (zkh_page_circuit_code with this image's size)", who, h);
-    if (r[PR_ROW] != NONE) {
-        if (r[PR_A] >= W) return make_err("%s: row %u: address %u outside the image of %u words", who, r[PR_ROW], r[PR_A], W);
-        return make_err("%s: row %u: address %u does not follow a smaller one (row %u: address %u)", who, r[PR_ROW], r[PR_A], r[PR_ROW] - 1, r[PR_BEFORE]);
-    }
-    memcpy(out_roots, r + PR_ROOTS, 4 * PG_OUT);
-    return nullptr;
+    return page_witgen("page_circuit_witgen", true, ctx, c, po2, zk_cycles, code, proof, proof_words, nodes_before, nodes_after, 0, data, out_roots, noise_key);
+}
+
+extern "C" const char* zkh_page_circuit_witgen_part(zkh_ctx* ctx, const zkh_circuit* c, size_t po2, size_t zk_cycles, const zkh_buf* code, const zkh_buf* proof,
+                                                    size_t proof_words, const zkh_buf* nodes_before, const zkh_buf* nodes_after, size_t first, zkh_buf* data,
+                                                    uint32_t out_roots[16], const uint32_t* noise_key) {
+    return page_witgen("page_circuit_witgen_part", false, ctx, c, po2, zk_cycles, code, proof, proof_words, nodes_before, nodes_after, first, data, out_roots,
+                       noise_key);
 }

@@ -193,6 +193,8 @@ ABI = {
     "zkh_image_proof_walk": (_err, [_vp, _vp, _sz, _u32p, _u32p]),
     "zkh_page_circuit_code": (_err, [_vp, _vp, _sz, _sz, _sz, _vp]),
     "zkh_page_circuit_witgen": (_err, [_vp, _vp, _sz, _sz, _vp, _vp, _sz, _vp, _vp, _vp, _u32p, _u32p]),
+    "zkh_page_circuit_witgen_part": (_err, [_vp, _vp, _sz, _sz, _vp, _vp, _sz, _vp, _vp, _sz, _vp, _u32p, _u32p]),
+    "zkh_page_circuit_slots": (_sz, [_sz, _sz, _sz]),
     "zkh_circuit_derived_data_columns": (_err, [_vp, _u32p, _sz, C.POINTER(_sz)]),
     "zkh_upload_data_trace": (_err, [_vp, _vp, _sz, _sz, _vp, _u32p, _i]),
     "zkh_ctx_h2d_bytes": (_sz, [_vp]),
@@ -960,6 +962,24 @@ class HipHal:
         _k, kp = _key_ptr(noise_seed)
         _check(_lib.zkh_page_circuit_witgen(self.ctx, circuit.h, po2, zk_cycles, code.h, proof.h, proof_words, nodes_before.h, nodes_after.h, data.h,
                                             _ptr(out), kp))
+        return out
+
+    def page_circuit_slots(self, po2: int, zk_cycles: int, image_words: int) -> int:
+        """N, the path slots of a P2-PAGE trace of 2^po2 rows over an image of `image_words` words, 0 where page_circuit_code refuses the
+        shape (zkh_page_circuit_slots: host only; the Python twin is p2_page.slots, the plan of the parts p2_page.parts)"""
+        return int(_lib.zkh_page_circuit_slots(po2, zk_cycles, image_words))
+
+    def page_circuit_witgen_part(self, circuit: Circuit, po2: int, zk_cycles: int, code: Buffer, proof: Buffer, proof_words: int, nodes_before: Buffer,
+                                 nodes_after: Buffer, first: int, data: Buffer, noise_seed: int) -> np.ndarray:
+        """the data group of P2-PAGE for ONE PART of the page-out a ZKU1 proof describes: the updates [first, first + min(N, D - first)) of
+        its table (zkh_page_circuit_witgen_part; the host twin: p2_page.reference_page_part) -> the out globals, the root before
+        update `first` ‖ the root after the part's last update (16 words).  Every other operand is page_circuit_witgen's, and both trees
+        are the whole page-out's whichever part is laid out.  A table of any size is refused only for first >= D (first = D = 0 is
+        the empty table's one part); the other refusals are page_circuit_witgen's after "page_circuit_witgen_part: " """
+        out = np.zeros(2 * DIGEST_WORDS, dtype=np.uint32)
+        _k, kp = _key_ptr(noise_seed)
+        _check(_lib.zkh_page_circuit_witgen_part(self.ctx, circuit.h, po2, zk_cycles, code.h, proof.h, proof_words, nodes_before.h, nodes_after.h, first,
+                                                 data.h, _ptr(out), kp))
         return out
 
     def derive_multiplicities(self, circuit: Circuit, po2: int, zk_cycles: int, code: Buffer, data: Buffer) -> None:

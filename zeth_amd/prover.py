@@ -377,9 +377,67 @@ class SegmentProver:
         receipt.control_root = self.code_root(code, seg.po2)
         return receipt
 
+    def seal_page_out_parts(self, segs, proof, proof_words: int, nodes_before, nodes_after, check: bool = False) -> list:
+        """Seal a page-out of ANY size with P2-PAGE as a chain of parts (circuits/p2_page.py `parts`): part p lays out the updates
+        [first, first + count) of the ZKU1 proof's table (zkh_page_circuit_witgen_part), and its receipt's output is the root before
+        update `first` ‖ the root after the part's last update, so part p + 1 opens the root part p left (`verify_page_out_chain`).
+        segs: one Segment per part, all of one (po2, zk_cycles), each with its own noise seed; HalError if their number is not the
+        plan's.  The other operands are seal_page_out's; both trees are the WHOLE page-out's for every part, so the parts could be
+        sealed in any order, or on several ranks.  The code group and its control root are built once and the data buffer is reused.
+        -> the receipts, in the order of the parts."""
+        from .circuits import p2_page
+        segs = list(segs)
+        if not segs:
+            raise _hal.HalError("seal_page_out_parts: no segment")
+        po2, zk = segs[0].po2, segs[0].zk_cycles
+        if any((s.po2, s.zk_cycles) != (po2, zk) for s in segs):
+            raise _hal.HalError("seal_page_out_parts: the parts share one code group: every segment must have the same (po2, zk_cycles)")
+        if not isinstance(proof, _hal.Buffer):
+            proof = self.hal.copy_from("image_proof", np.ascontiguousarray(proof, dtype=np.uint32).reshape(-1))
+        header = proof.slice(0, min(3, proof.size())).to_vec()
+        W, D = (int(header[1]), int(header[2])) if header.size > 2 else (0, 0)
+        wa, wc, wd = self.group_sizes()
+        code = self.hal.page_circuit_code(self.circuit, po2, zk, W)            # refuses a shape without a path slot
+        plan = p2_page.parts(po2, zk, W, D)
+        if len(segs) != len(plan):
+            raise _hal.HalError(f"seal_page_out_parts: {len(segs)} segments, but a table of {D} rows takes {len(plan)} parts of "
+                                f"{self.hal.page_circuit_slots(po2, zk, W)} slots at po2 {po2}")
+        control_root = self.code_root(code, po2)
+        data = self.hal.alloc_elem("data", wd << po2)
+        receipts = []
+        for seg, (first, _count) in zip(segs, plan):
+            out = self.hal.page_circuit_witgen_part(self.circuit, po2, zk, code, proof, proof_words, nodes_before, nodes_after, first, data, seg.noise_seed)
+            receipt = self.seal_with_accum(seg, code, data, out, self.syn_accumulate(seg, data), check=check)
+            receipt.control_root = control_root.copy()
+            receipts.append(receipt)
+        return receipts
+
     def prove_segment(self, seg: Segment) -> SegmentReceipt:
         code, data, out = self.witgen(seg)
         return self.seal(seg, code, data, out)
+
+
+def verify_page_out_chain(receipts, control_root, root_before=None) -> Tuple[np.ndarray, np.ndarray]:
+    """Verify the chain of P2-PAGE seals of one page-out (SegmentProver.seal_page_out_parts), HOST ONLY -> (root_before, root_after) of
+    the whole page-out.  Every seal is verified against P2-PAGE's description and `control_root` (the code group's: one for all
+    parts); part p + 1 must open the root part p left; with a `root_before`, part 0 must open it.  Raises HalError on a seal the
+    verifier rejects, on a chain that does not link, on another first root, and on an empty list."""
+    from .circuits import p2_page
+    receipts = list(receipts)
+    if not receipts:
+        raise _hal.HalError("verify_page_out_chain: no receipt (a page-out of no rows still has one part)")
+    hc = _hal.HostCircuit(p2_page.p2_page_circuit())
+    fmt = lambda r: " ".join(f"{int(w):08x}" for w in r)
+    roots = []
+    for r in receipts:
+        hc.verify_segment(r.seal, control_root)
+        roots.append((np.array(r.seal[:8], dtype=np.uint32), np.array(r.seal[8:16], dtype=np.uint32)))
+    if root_before is not None and not np.array_equal(roots[0][0], np.asarray(root_before, dtype=np.uint32)):
+        raise _hal.HalError(f"verify_page_out_chain: part 0 opens root {fmt(roots[0][0])}, not root_before {fmt(root_before)}")
+    for p in range(len(roots) - 1):
+        if not np.array_equal(roots[p + 1][0], roots[p][1]):
+            raise _hal.HalError(f"verify_page_out_chain: part {p + 1} opens root {fmt(roots[p + 1][0])}, but part {p} left root {fmt(roots[p][1])}")
+    return roots[0][0], roots[-1][1]
 
 
 def _generate_control_roots(po2s=range(13, 25)) -> None:
