@@ -439,7 +439,7 @@ const char* zkh_image_proof_walk(zkh_ctx*, const zkh_buf* proof, size_t words, c
  * seal proves "D single-word updates, applied one after the other, take root_before to root_after": out = root_before (8) ‖ root_after
  * (8).  Every update is one Merkle path of h = log2 L blocks of 31 rows (P2-JOIN's rows), the old path and the new one side by side;
  * N = ((2^po2 - zk_cycles) / 31) / h paths fit a trace, the slots past D are no-op updates of address 0.  It does NOT constrain that
- * the addresses increase, nor that the table is the page table of a paging segment's seal.  W > 8 (a path is at least one hash_pair)
+ * the addresses increase (P2-PAGE-ordered, below, does), nor that the table is the page table of a paging segment's seal.  W > 8 (a path is at least one hash_pair)
  * and h <= 27 (the address is rebuilt in the field).
  * zkh_page_circuit_code writes the code group, a function of (po2, zk_cycles, h of `image_words`): what the control root commits to.
  * zkh_page_circuit_witgen writes the data group and out_roots = digest 1 of both trees.  `proof` is a device buffer whose first
@@ -476,6 +476,30 @@ const char* zkh_page_circuit_witgen_part(zkh_ctx*, const zkh_circuit*, size_t po
                                          const zkh_buf* nodes_before, const zkh_buf* nodes_after, size_t first, zkh_buf* data, uint32_t out_roots[16],
                                          const uint32_t noise_key[8]);
 size_t zkh_page_circuit_slots(size_t po2, size_t zk_cycles, size_t image_words);
+/* P2-PAGE-ordered (circuit kind 6, zeth_amd/circuits/p2_page_ordered.py; csrc/page_circuit.hip): P2-PAGE plus the constraint that the
+ * addresses strictly increase.  Its seal proves "the LIVE updates of the part have strictly increasing addresses, all at or above lo;
+ * hi is one more than the last of them, or lo if there is none; those updates, in that order, take root_before to root_after": out =
+ * root_before (8) ‖ root_after (8) ‖ lo ‖ hi (18 words; lo and hi are field elements as the trace holds them, Montgomery words, which
+ * the verifier decodes).  A chain whose part 0 has lo = 0 and whose part p + 1 starts at the root and the hi part p left seals a SET of
+ * addresses, each written once, in order.  The trace is P2-PAGE's in a wider buffer: data columns 0 .. 124 and code columns 0 .. 38
+ * are P2-PAGE's, written by the same kernels; data 125 live (1 on a real update's path, 0 on a no-op's), 126 lo (one more than the last
+ * live address before the slot, in this part or an earlier one; 0 if none), 127 gbit / 128 gacc (the gap addr - lo one bit per row on
+ * rows 1 .. 29 of a path's block 0, and its running sum); code 39 gsel, 40 gpow, 41 gend (those rows, 2^(k - 1) on them, the last of
+ * them).  Still NOT constrained: that the table is the page table of a paging segment's seal.
+ * h <= 26 (images of at most 2^29 words), one less than P2-PAGE: the gap is decomposed into 29 bits, and addr = lo + gap is an integer
+ * equation only while lo + gap < 2^30 < P.  N, the parts' plan and W > 8 are P2-PAGE's (zkh_page_circuit_slots).
+ * zkh_page_ordered_code: zkh_page_circuit_code's operands, `code` of 42 x 2^po2 words.
+ * zkh_page_ordered_witgen: zkh_page_circuit_witgen_part's operands, `first` included, `data` of 129 x 2^po2 words, out[18]; first = 0
+ * with D <= N is the single-seal case.  One more kernel after P2-PAGE's, one lane per (path row, new column); still one read-back, no
+ * atomics.  The refusals are zkh_page_circuit_witgen_part's, in the same order with the same text, after "page_ordered_code: " /
+ * "page_ordered_witgen: ", but "the circuit does not have P2-PAGE-ordered's shape (kind 6, 42 / 129 / 4 columns, 18 outputs)", and after
+ * P2-PAGE's h <= 27 refusal "an image of W words has h 27; the gap between two addresses is decomposed into 29 bits, which takes
+ * addresses below 2^29: h <= 26".  A table whose addresses do not increase is the check pass's refusal as before: no path and no new
+ * column is written after it.  The accum group is zkh_syn_accum's, as for kind 5. */
+const char* zkh_page_ordered_code(zkh_ctx*, const zkh_circuit*, size_t po2, size_t zk_cycles, size_t image_words, zkh_buf* code);
+const char* zkh_page_ordered_witgen(zkh_ctx*, const zkh_circuit*, size_t po2, size_t zk_cycles, const zkh_buf* code, const zkh_buf* proof, size_t proof_words,
+                                    const zkh_buf* nodes_before, const zkh_buf* nodes_after, size_t first, zkh_buf* data, uint32_t out[18],
+                                    const uint32_t noise_key[8]);
 /* Everything a circuit's arguments derive, in the one order in which it is sound: sorted copies, then columns, then links, then
  * multiplicities (a LIMBS / ORDER record may read a sorted copy's column, and the multiplicities count the limbs that the records and
  * the links derive).  Call it after the data upload and before zkh_prove_begin: what it writes belongs to the data group.  It runs
@@ -510,7 +534,8 @@ size_t zkh_ctx_h2d_bytes(const zkh_ctx*);
  *                    p2_join.py; stands in for the in-circuit hashing of risc0-circuit-recursion 4.0.2, Cargo.lock:5305).
  *                    `pub` = the two child claims (16 words, required); out_global = parent (8) ‖ left (8) ‖ right (8).
  *   kind 5 P2-PAGE   has a generator of its own, zkh_page_circuit_code / zkh_page_circuit_witgen above (its inputs are a proof and
- *                    two trees, not a seed); zkh_syn_accum builds its accum group, which is P2-JOIN's. */
+ *                    two trees, not a seed); zkh_syn_accum builds its accum group, which is P2-JOIN's.
+ *   kind 6 P2-PAGE-ordered  likewise: zkh_page_ordered_code / zkh_page_ordered_witgen above, and zkh_syn_accum. */
 /* BLINDING ROWS.  The last zk_cycles rows of every data / accum column are zero-knowledge blinding noise.  Upstream draws each
  * cell from the OS RNG (`Elem::random(&mut rng)`); here the randomness enters once per call as a 256-bit key — `noise_key`, 8
  * words — and every cell is ChaCha12(key; counter = (row, column), nonce = (group, "ZKN1")) folded mod P the way upstream's

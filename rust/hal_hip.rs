@@ -513,6 +513,29 @@ impl HipCircuitHal {
         roots
     }
 
+    /// The code group of P2-PAGE-ordered, P2-PAGE plus the constraint that the addresses strictly increase (`zkh_page_ordered_code`):
+    /// P2-PAGE's 39 columns, then gsel, gpow, gend.  `self` holds the P2-PAGE-ordered description; `code` has 42 columns.  Panics as
+    /// `page_circuit_code` does, and on an image of more than 2^29 words (h > 26: the gap between two addresses has 29 bits).
+    pub fn page_ordered_code(&self, image_words: usize, code: &HipBuffer<BabyBearElem>, steps: usize) {
+        let po2 = steps.trailing_zeros() as usize;
+        ffi(|| unsafe { sys::zkh_page_ordered_code(self.hal.ctx.0, self.circuit, po2, sys::ZK_CYCLES, image_words, code.raw) });
+    }
+
+    /// The data group of P2-PAGE-ordered for the part at `first` of a page-out (`zkh_page_ordered_witgen`), and the `out` globals: the
+    /// root before update `first`, the root after the part's last update, then lo and hi as the trace holds them (Montgomery words): the
+    /// part's live addresses strictly increase from lo on, and hi is one more than the last of them.  The operands are
+    /// `page_circuit_witgen_part`'s, `data` has 129 columns; `first = 0` with D <= N is the single-seal case.  Part p + 1 opens the
+    /// root and starts at the hi part p left.  Panics as `page_circuit_witgen_part` does.
+    pub fn page_ordered_witgen(&self, code: &HipBuffer<BabyBearElem>, proof: &HipBuffer<u32>, words: usize, nodes_before: &HipBuffer<BabyBearElem>,
+                               nodes_after: &HipBuffer<BabyBearElem>, first: usize, data: &HipBuffer<BabyBearElem>, steps: usize,
+                               noise_key: Option<&[u32; 8]>) -> [u32; 18] {
+        let po2 = steps.trailing_zeros() as usize;
+        let mut out = [0u32; 18];
+        ffi(|| unsafe { sys::zkh_page_ordered_witgen(self.hal.ctx.0, self.circuit, po2, sys::ZK_CYCLES, code.raw, proof.raw, words, nodes_before.raw,
+                                                     nodes_after.raw, first, data.raw, out.as_mut_ptr(), noise_key.map_or(std::ptr::null(), |k| k.as_ptr())) });
+        out
+    }
+
     /// Check the raw traces against the circuit's own constraints on every row of `rows` (`zkh_check_rows`): which constraint a
     /// witness breaks, and where, before a seal is spent on it.  `out` and `mix` are the global words.  `row < 0`: no row of the window
     /// fails; otherwise the lowest failing row, its lowest failing `and_eqz` step (an index into the ZKC1 step list), how many rows of

@@ -17,7 +17,9 @@ that proof on the device, zkh_image_proof_walk next to the host walk of the down
 zkh_page_out_tree, alternating, with the number of permutations; M21: P2-PAGE's witness, zkh_page_circuit_witgen with full slots at
 h = 17 and h = 23 next to zkh_syn_witgen of P2-JOIN at the same po2, alternating, with both calls' stages; M22: P2-PAGE's parts,
 zkh_page_circuit_witgen_part on a table of 4 N rows at first = 0, N, 2 N, 3 N next to zkh_page_circuit_witgen on its first N rows,
-alternating, with every call's stages) on one MI355X, through the C ABI (HipHal).
+alternating, with every call's stages; M23: P2-PAGE-ordered, zkh_page_ordered_witgen next to zkh_page_circuit_witgen_part at first = 0 and
+first = N of one table, and the seal of a part under both circuits, alternating, with every witness call's stages) on one MI355X, through
+the C ABI (HipHal).
 
 Each line of output is one JSON object: the op, its shape, the average wall time of one call (stream drained on both
 sides of `reps` back-to-back calls), its ALGORITHMIC bytes (SURVEY.md §8a "B_alg": inputs read once + outputs written
@@ -1036,6 +1038,87 @@ def main() -> None:
                               **{k: spread(v) for k, v in t.items()}, "steps": steps}), flush=True)
             del before, after, after1, proof, proof1, pcode
         del pdata
+    if want("M23"):
+        # P2-PAGE-ordered: zkh_page_ordered_witgen next to zkh_page_circuit_witgen_part on one table of 2 N rows (every slot full) at
+        # first = 0 and first = N, and the seal of the part at 0 under both circuits (zkh_prove_begin / zkh_syn_accum /
+        # zkh_prove_finish: 42 + 129 = 171 code and data columns against 39 + 125 = 164, 4 accum columns under both).  M21's windows: `runs`
+        # alternating windows of `reps` calls, median and spread, then every witness call's stages by their events; page_order is the
+        # one stage the ordered call adds.  Both calls must give the same roots, and the ordered parts' lo / hi must chain.
+        from zeth_amd import hal as zhal
+        from zeth_amd.circuits import p2_page, p2_page_ordered
+        from zeth_amd.prover import Segment, SegmentProver
+        runs, zk = 7, 1994
+        spread = lambda ts: {"median_ms": round(float(np.median(ts)) * 1e3, 4), "min_ms": round(min(ts) * 1e3, 4), "max_ms": round(max(ts) * 1e3, 4)}   # noqa: E731
+        provers = {"page": SegmentProver(hal, p2_page.p2_page_circuit()), "ordered": SegmentProver(hal, p2_page_ordered.p2_page_ordered_circuit())}
+        datas = {"page": hal.alloc_elem("m23pd", p2_page.WD * n), "ordered": hal.alloc_elem("m23od", p2_page_ordered.WD * n)}
+        u32p = zhal._u32p
+        key = zhal.noise_key(0x2E80)
+        for W in (1 << 20, 1 << 26):
+            h = p2_page.tree_height(W)
+            N = p2_page.slots(args.po2, zk, h)
+            D = 2 * N
+            image_h = rand_fp(rng, W)
+            addrs = np.unique(rng.integers(0, W, D + D // 8))
+            addrs = np.sort(addrs[rng.choice(addrs.size, D, replace=False)]).astype(np.int64)
+            outs = rand_fp(rng, D)
+            table = np.stack([addrs.astype(np.uint32), image_h[addrs], outs], axis=1).reshape(-1)
+            proof_h = np.concatenate([np.array([0x5A4B5531, W, D, 0, h] + [0] * h, dtype=np.uint32), table])
+            image = hal.alloc_elem("m23i", W)
+            image.write(image_h)
+            before = hal.image_commit(image)
+            image_h[addrs] = outs
+            image.write(image_h)
+            after = hal.image_commit(image)
+            del image
+            proof = hal.copy_from("m23p", proof_h)
+            codes = {"page": hal.page_circuit_code(provers["page"].circuit, args.po2, zk, W), "ordered": hal.page_ordered_code(provers["ordered"].circuit, args.po2, zk, W)}
+            outs16, outs18 = np.zeros(16, dtype=np.uint32), np.zeros(18, dtype=np.uint32)
+            page_fn = lambda first: lambda: zhal._check(zhal._lib.zkh_page_circuit_witgen_part(hal.ctx, provers["page"].circuit.h, args.po2, zk, codes["page"].h, proof.h,   # noqa: E731
+                                                                                               proof_h.size, before.h, after.h, first, datas["page"].h,
+                                                                                               outs16.ctypes.data_as(u32p), key.ctypes.data_as(u32p)))
+            ordered_fn = lambda first: lambda: zhal._check(zhal._lib.zkh_page_ordered_witgen(hal.ctx, provers["ordered"].circuit.h, args.po2, zk, codes["ordered"].h, proof.h,   # noqa: E731
+                                                                                             proof_h.size, before.h, after.h, first, datas["ordered"].h,
+                                                                                             outs18.ctypes.data_as(u32p), key.ctypes.data_as(u32p)))
+            fns = [(f"{name}_first_{p}N", mk(p * N)) for p in range(2) for name, mk in (("page_circuit_witgen_part", page_fn), ("page_ordered_witgen", ordered_fn))]
+            bounds = []
+            for p in (1, 0):                                                 # the part at 0 last: its witness is the one sealed below
+                page_fn(p * N)()
+                ordered_fn(p * N)()
+                assert np.array_equal(outs18[:16], outs16), "the ordered call's roots are not P2-PAGE's"
+                bounds.append((p2_page_ordered.decode(outs18[16]), p2_page_ordered.decode(outs18[17])))
+            assert bounds[1] == (0, int(addrs[N - 1]) + 1) and bounds[0] == (bounds[1][1], int(addrs[D - 1]) + 1)
+            seg = Segment(index=0, po2=args.po2, zk_cycles=zk, noise_seed=0x2E80)
+            seal_fn = lambda name, out: lambda: provers[name].seal_with_accum(seg, codes[name], datas[name], out, provers[name].syn_accumulate(seg, datas[name]))   # noqa: E731
+            seals = [("seal_page", seal_fn("page", outs16.copy())), ("seal_ordered", seal_fn("ordered", outs18.copy()))]
+            t = {name: [] for name, _ in fns + seals}
+            for _ in range(runs):
+                for name, fn in fns:
+                    t[name].append(timed(hal, fn, args.reps))
+            steps = {}
+            for name, fn in fns:
+                hal.prof_enable(True)
+                hal.prof_reset()
+                for _ in range(args.reps):
+                    fn()
+                hal.sync()
+                steps[name] = {r["name"]: {"calls_per_call": r["calls"] // args.reps, "ms_per_call": round(r["total_ms"] / args.reps, 4)} for r in hal.prof_get()
+                               if r["calls"] and r["name"].startswith("page_")}
+                hal.prof_enable(False)
+            page_fn(0)()                                                     # the witnesses of the part at 0 again, for the seals
+            ordered_fn(0)()
+            for _ in range(runs):
+                for name, fn in seals:
+                    t[name].append(timed(hal, fn, args.reps))
+            med = {k: float(np.median(v)) for k, v in t.items()}
+            print(json.dumps({"bench": "M23", "library": os.path.basename(os.environ.get("ZKH_LIBRARY", "") or "libzkhal_mi355x.so"), "po2": args.po2,
+                              "image_words": W, "layers": h, "slots": N, "table_rows": D, "runs": runs, "reps": args.reps,
+                              **{k: spread(v) for k, v in t.items()}, "steps": steps,
+                              "ordered_minus_page_ms": {f"first_{p}N": round((med[f"page_ordered_witgen_first_{p}N"] - med[f"page_circuit_witgen_part_first_{p}N"]) * 1e3, 4)
+                                                        for p in range(2)},
+                              "seal_ratio": round(med["seal_ordered"] / med["seal_page"], 4), "code_and_data_columns": {"page": 39 + 125, "ordered": 42 + 129}}),
+                  flush=True)
+            del before, after, proof, codes
+        del datas
     hal.close()
 
 

@@ -1328,6 +1328,8 @@ def shipped() -> Dict[str, np.ndarray]:
         SHIPPED["recursion"] = recursion.recursion_circuit()
         from . import p2_page
         SHIPPED["p2_page"] = p2_page.p2_page_circuit()
+        from . import p2_page_ordered
+        SHIPPED["p2_page_ordered"] = p2_page_ordered.p2_page_ordered_circuit()
     return SHIPPED
 
 

@@ -5,8 +5,9 @@ current root and replaces it with out_i, which gives the next root; the last roo
 include/zkhal.h "THE IMAGE'S COMMITMENT": leaves are eight words verbatim, a node is `hash_pair` of its children, h = log2 L.  Words
 are residues, as Montgomery words in the trace: the space the tree lives in.
 
-NOT constrained here: that the addresses strictly increase, and that the rows (a_i, in_i, out_i) are the page table of a particular
-paging segment's seal.  This circuit proves "D single-word updates take root_before to root_after" and nothing else.
+NOT constrained here: that the addresses strictly increase (P2-PAGE-ordered, p2_page_ordered.py, is this circuit plus that), and that
+the rows (a_i, in_i, out_i) are the page table of a particular paging segment's seal.  This circuit proves "D single-word updates take
+root_before to root_after" and nothing else.
 
 Trace (A = n - zk_cycles active rows, blocks of 31 rows with P2-JOIN's row roles k = 0 .. 30, K = A // 31 blocks).  A PATH is h
 consecutive blocks, so there are N = K // h path slots; h >= 1 is a parameter of the code group as (po2, zk_cycles) are.  Block 0 of a
@@ -65,8 +66,11 @@ def slots(po2: int, zk_cycles: int, h: int) -> int:
     return (((1 << po2) - zk_cycles) // BLOCK_ROWS) // h
 
 
-def build_p2_page() -> np.ndarray:
-    b = CircuitBuilder((WA, WC, WD), (OUT_WORDS, WA), kind=KIND_P2_PAGE)
+def build_page(kind: int, sizes: Tuple[int, int, int], out_words: int, after_roots=None):
+    """-> (blob, families): P2-PAGE's constraint text over a circuit of `sizes` (accum, code, data) columns and `out_words` outputs.
+    after_roots(b, chain, gated, env) -> chain emits one more family, named by after_roots.family, between `roots` and `accum`
+    (p2_page_ordered.py); without it this is P2-PAGE word for word."""
+    b = CircuitBuilder(sizes, (out_words, WA), kind=kind)
     code = lambda c, back=0: b.get(GROUP_CODE, c, back)
     dat = lambda c, back=0: b.get(GROUP_DATA, c, back)
     acc4 = lambda c, back=0: b.get(GROUP_ACCUM, c, back)
@@ -174,6 +178,10 @@ def build_p2_page() -> np.ndarray:
     chain = gated(chain, code(C_PATH_FIRST), [b.sub(cur[j], Sn(j, 1)) for j in range(8)])
     chain = gated(chain, code(C_LAST_TOP), [b.sub(Sn(j), out(8 + j)) for j in range(8)])
     family("roots", start)
+    if after_roots is not None:
+        start = len(b.steps)
+        chain = after_roots(b, chain, gated, dict(code=code, dat=dat, out=out, one=one, first=first, leaf_in=leaf_in, addr=addr, w_in=w_in, w_out=w_out))
+        family(after_roots.family, start)
 
     # 7. accum: one Fp4 running product of (mix + data column 0), and the selector sanity, as in P2-JOIN
     start = len(b.steps)
@@ -194,8 +202,13 @@ def build_p2_page() -> np.ndarray:
     chain = b.and_eqz(chain, b.mul(first, b.sub(one, first)))
     chain = b.and_eqz(chain, b.sub(b.sub(active, first), body))
     family("sanity", start)
+    return b.finish(chain), families
+
+
+def build_p2_page() -> np.ndarray:
+    blob, families = build_page(KIND_P2_PAGE, (WA, WC, WD), OUT_WORDS)
     FAMILIES[:] = families
-    return b.finish(chain)
+    return blob
 
 
 _cached = None

@@ -951,8 +951,8 @@ extern "C" const char* zkh_syn_chain_contributions(zkh_ctx* ctx, const zkh_circu
 }
 extern "C" const char* zkh_syn_accum(zkh_ctx* ctx, const zkh_circuit* c, size_t po2, size_t zk_cycles, const uint32_t* noise_key,
                                      const zkh_buf* data, const uint32_t* mix_global, zkh_buf* accum) {
-    // kind 5 (P2-PAGE, page_circuit.hip) carries P2-JOIN's argument: one running product of (mix + data column 0)
-    ZKH_REQUIRE((c->kind >= 1 && c->kind <= 3) || c->kind == 5, "syn_accum: no built-in accum witness generator for circuit kind %u", c->kind);
+    // kinds 5 and 6 (P2-PAGE and P2-PAGE-ordered, page_circuit.hip) carry P2-JOIN's argument: one running product of (mix + data column 0)
+    ZKH_REQUIRE((c->kind >= 1 && c->kind <= 3) || c->kind == 5 || c->kind == 6, "syn_accum: no built-in accum witness generator for circuit kind %u", c->kind);
     NoiseKey nk;
     ZKH_TRY(resolve_noise_key(noise_key, &nk));
     const size_t n = (size_t)1 << po2;

@@ -31,6 +31,12 @@
 // `cur` of slot 0 is the record's first root, of slot s > 0 it is read from the output row the path kernel wrote for slot s - 1.
 // k_page_tail: zero rows, then the blinding rows.  No atomics, every cell (of the record too) has one writer; one read-back fetches
 // the record at the end.
+//
+// P2-PAGE-ORDERED (zeth_amd/circuits/p2_page_ordered.py; include/zkhal.h "P2-PAGE-ordered"): the same trace in a wider buffer, columns
+// 0 .. 124 of the data group and 0 .. 38 of the code group written by the kernels above as they stand (every one of them strides by n,
+// and the tail's width is a grid dimension), then the columns live, lo, gbit, gacc by k_page_order and gsel, gpow, gend by
+// k_page_order_code.  The order the circuit constrains is the one the two-tree shortcut already relies on and k_page_check already
+// refuses a table without: lo of a slot is one more than the address of the table's row before it, and the gap to it is >= 0.
 #include "circuit.h"
 #include "image_tree.h"
 #include "p2_rows.h"
@@ -40,13 +46,21 @@ using namespace zkh;
 namespace {
 
 constexpr uint32_t PG_WC = 39, PG_WD = 125, PG_OUT = 16, PG_MAX_H = 27;
+// P2-PAGE-ordered (p2_page_ordered.py): three more code columns, four more data columns, out = the roots ‖ lo ‖ hi; the gap between two
+// addresses is decomposed into 29 bits, which takes addr < 2^29: h <= 26
+constexpr uint32_t PO_WC = 42, PO_WD = 129, PO_OUT = 18, PO_MAX_H = 26, PO_GAP_BITS = 29;
+enum : uint32_t { PC_GSEL = 39, PC_GPOW = 40, PC_GEND = 41 };
+enum : uint32_t { PD_LIVE = 125, PD_LO = 126, PD_GBIT = 127, PD_GACC = 128 };
+// the shape of the circuit an entry point serves
+struct PageShape { const char* name; uint32_t kind, wc, wd, out, max_h; };
+constexpr PageShape PAGE = {"P2-PAGE", 5, PG_WC, PG_WD, PG_OUT, PG_MAX_H}, ORDERED = {"P2-PAGE-ordered", 6, PO_WC, PO_WD, PO_OUT, PO_MAX_H};
 // code columns (p2_page.py C_*)
 enum : uint32_t { PC_LIN = 3, PC_FULLR, PC_PARTR, PC_LF, PC_LP, PC_LEAF_IN, PC_NODE_IN, PC_PATH_FIRST, PC_TOP_OUT, PC_LAST_TOP, PC_CARRY, PC_POW, PC_RC };
 // data columns (p2_page.py D_*)
 enum : uint32_t { PD_SO = 0, PD_QO = 24, PD_SN = 48, PD_QN = 72, PD_E = 96, PD_B = 112, PD_ADDR = 113, PD_W_IN = 114, PD_W_OUT = 115, PD_ACC = 116, PD_CUR = 117 };
 // the record: the lowest refused row (NONE: none), its address, the address before it, whether the code group is this h's, both roots
-// (the one the trace's first path opens, the one its last path leaves)
-enum : uint32_t { PR_ROW = 0, PR_A = 1, PR_BEFORE = 2, PR_CODE_OK = 3, PR_ROOTS = 8, PR_WORDS = 24 };
+// (the one the trace's first path opens, the one its last path leaves); P2-PAGE-ordered: lo and hi as the trace holds them (k_page_order)
+enum : uint32_t { PR_ROW = 0, PR_A = 1, PR_BEFORE = 2, PR_CODE_OK = 3, PR_LO = 4, PR_HI = 5, PR_ROOTS = 8, PR_WORDS = 24 };
 constexpr uint32_t NONE = 0xffffffffu;
 constexpr uint32_t PG_THREADS = 256;
 
@@ -79,6 +93,19 @@ __global__ void k_page_code(uint32_t* code, uint32_t n, uint32_t A, uint32_t h, 
     case PC_POW: v = (in_paths && k == 0 && t > 0) ? encode(1u << (3 + t)) : 0; break;
     default: if (full || (part && col == PC_RC)) v = tab[(k - 1) * PJ_T + (col - PC_RC)];
     }
+    code[(size_t)col * n + r] = v;
+}
+
+// P2-PAGE-ordered's code columns gsel, gpow, gend: grid (ceil(n / 256), 3), after k_page_code has written columns 0 .. 38
+__global__ void k_page_order_code(uint32_t* code, uint32_t n, uint32_t h, uint32_t N) {
+    const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x, col = PC_GSEL + blockIdx.y;
+    if (r >= n) return;
+    const uint32_t k = r % PJ_BLOCK, t = (r / PJ_BLOCK) % h;
+    const bool bits = r < PJ_BLOCK * h * N && t == 0 && k >= 1 && k <= PO_GAP_BITS;       // rows 1 .. 29 of a path's block 0
+    uint32_t v = 0;
+    if (col == PC_GSEL) v = bits ? R1 : 0;
+    else if (col == PC_GPOW) v = bits ? encode(1u << (k - 1)) : 0;
+    else v = (bits && k == PO_GAP_BITS) ? R1 : 0;
     code[(size_t)col * n + r] = v;
 }
 
@@ -243,6 +270,34 @@ __global__ __launch_bounds__(PG_THREADS) void k_page_book(uint32_t* __restrict__
     data[(size_t)col * n + r] = v;
 }
 
+// P2-PAGE-ordered, grid (ceil(31 h N / 256), 4): the columns live, lo, gbit, gacc of the rows of the paths, one lane per (row, column),
+// stores coalesced along the rows as k_page_book's.  The record holds no refusal here, so the table's addresses strictly increase below
+// W <= 2^29: lo <= 2^29 and the gap a - lo of a live slot is in [0, 2^29).  lo of a slot is one more than the address of the table's row
+// before it (a dead slot: before the table's end), 0 where there is none; a dead slot's gap counts as 0.  The lane of slot 0's first
+// row and `lo` writes out[16] into the record, the lane of the last path's top row and `lo` writes out[17] = hi: one writer per cell.
+// `rec` is read and written here (distinct cells), hence no __restrict__ on it.
+__global__ __launch_bounds__(PG_THREADS) void k_page_order(uint32_t* __restrict__ data, uint32_t n, uint32_t h, uint32_t N, const uint32_t* __restrict__ table, uint32_t D,
+                                                           uint32_t first, uint32_t* rec) {
+    const uint32_t r = blockIdx.x * PG_THREADS + threadIdx.x, col = PD_LIVE + blockIdx.y, rows = PJ_BLOCK * h * N;
+    if (r >= rows || rec[PR_ROW] != NONE) return;
+    const uint32_t k = r % PJ_BLOCK, blk = r / PJ_BLOCK, t = blk % h, slot = blk / h;
+    const size_t row = (size_t)first + slot;
+    const bool live = row < D;
+    const size_t before = live ? row : D;                              // the table's rows before this slot
+    const uint32_t a = live ? table[3 * row] : 0;
+    const uint32_t lo = before ? table[3 * (before - 1)] + 1 : 0;
+    const uint32_t g = live ? a - lo : 0;
+    const bool bits = t == 0 && k >= 1 && k <= PO_GAP_BITS;
+    uint32_t v;
+    if (col == PD_LIVE) v = live ? R1 : 0;
+    else if (col == PD_LO) v = encode(lo);
+    else if (col == PD_GBIT) v = (bits && ((g >> (k - 1)) & 1)) ? R1 : 0;
+    else v = bits ? encode(g & ((1u << k) - 1)) : 0;
+    data[(size_t)col * n + r] = v;
+    if (col == PD_LO && r == 0) rec[PR_LO] = v;
+    if (col == PD_LO && r == rows - 1) rec[PR_HI] = encode(live ? a + 1 : lo);
+}
+
 // rows past the last path: zero while active, blinding noise after
 __global__ void k_page_tail(uint32_t* data, uint32_t n, uint32_t A, uint32_t first_row, NoiseKey nk) {
     const uint32_t r = first_row + blockIdx.x * blockDim.x + threadIdx.x, col = blockIdx.y;
@@ -252,18 +307,21 @@ __global__ void k_page_tail(uint32_t* data, uint32_t n, uint32_t A, uint32_t fir
 
 // the checks the entry points share.  First the circuit's shape and the trace's size ...
 inline bool page_po2_ok(size_t po2, size_t zk_cycles) { return po2 >= 1 && po2 <= 30 && ((size_t)1 << po2) > zk_cycles + 1; }
-const char* page_circuit_shape(const char* who, const zkh_circuit* c, size_t po2, size_t zk_cycles) {
-    ZKH_REQUIRE(c->kind == 5 && c->group_size[GROUP_CODE] == PG_WC && c->group_size[GROUP_DATA] == PG_WD && c->group_size[GROUP_ACCUM] == 4 &&
-                c->global_size[GLOBAL_OUT] == PG_OUT, "%s: the circuit does not have P2-PAGE's shape (kind 5, 39 / 125 / 4 columns, 16 outputs)", who);
+const char* page_circuit_shape(const char* who, const PageShape& sh, const zkh_circuit* c, size_t po2, size_t zk_cycles) {
+    ZKH_REQUIRE(c->kind == sh.kind && c->group_size[GROUP_CODE] == sh.wc && c->group_size[GROUP_DATA] == sh.wd && c->group_size[GROUP_ACCUM] == 4 &&
+                c->global_size[GLOBAL_OUT] == sh.out, "%s: the circuit does not have %s's shape (kind %u, %u / %u / 4 columns, %u outputs)", who, sh.name, sh.kind,
+                sh.wc, sh.wd, sh.out);
     ZKH_REQUIRE(page_po2_ok(po2, zk_cycles), "%s: po2 %zu out of range for %zu zk_cycles", who, po2, zk_cycles);
     return nullptr;
 }
 // ... then the image's -> A, h, N
-const char* page_image_shape(const char* who, size_t po2, size_t zk_cycles, size_t W, uint32_t* A_out, uint32_t* h_out, uint32_t* N_out) {
+const char* page_image_shape(const char* who, const PageShape& sh, size_t po2, size_t zk_cycles, size_t W, uint32_t* A_out, uint32_t* h_out, uint32_t* N_out) {
     ZKH_REQUIRE(W > 8, "%s: an image of %zu words has a single leaf (W > 8: a path is at least one hash_pair)", who, W);
     uint32_t h = 0;
     while (((size_t)1 << h) < image_leaves(W)) h++;
     ZKH_REQUIRE(h <= PG_MAX_H, "%s: an image of %zu words has h %u; the address is rebuilt in the field, which takes h <= %u", who, W, h, PG_MAX_H);
+    ZKH_REQUIRE(h <= sh.max_h, "%s: an image of %zu words has h %u; the gap between two addresses is decomposed into %u bits, which takes addresses below 2^%u: h <= %u",
+                who, W, h, PO_GAP_BITS, PO_GAP_BITS, sh.max_h);
     *A_out = (uint32_t)(((size_t)1 << po2) - zk_cycles);
     *h_out = h;
     *N_out = *A_out / PJ_BLOCK / h;
@@ -272,13 +330,13 @@ const char* page_image_shape(const char* who, size_t po2, size_t zk_cycles, size
 }
 
 // Both generators.  `whole`: zkh_page_circuit_witgen, the table as one trace (first = 0, D <= N or refused); else the part at `first`.
-const char* page_witgen(const char* who, bool whole, zkh_ctx* ctx, const zkh_circuit* c, size_t po2, size_t zk_cycles, const zkh_buf* code, const zkh_buf* proof,
+const char* page_witgen(const char* who, const PageShape& sh, bool whole, zkh_ctx* ctx, const zkh_circuit* c, size_t po2, size_t zk_cycles, const zkh_buf* code, const zkh_buf* proof,
                         size_t proof_words, const zkh_buf* nodes_before, const zkh_buf* nodes_after, size_t first_row, zkh_buf* data, uint32_t* out_roots,
                         const uint32_t* noise_key) {
     ZKH_REQUIRE(ctx && c && code && proof && nodes_before && nodes_after && data && out_roots, "%s: null argument", who);
-    ZKH_TRY(page_circuit_shape(who, c, po2, zk_cycles));
+    ZKH_TRY(page_circuit_shape(who, sh, c, po2, zk_cycles));
     const size_t n = (size_t)1 << po2;
-    ZKH_REQUIRE(code->len == (size_t)PG_WC * n && data->len == (size_t)PG_WD * n, "%s: buffer shape mismatch (the code group is an input of this generator)", who);
+    ZKH_REQUIRE(code->len == (size_t)sh.wc * n && data->len == (size_t)sh.wd * n, "%s: buffer shape mismatch (the code group is an input of this generator)", who);
     ZKH_REQUIRE(proof_words <= proof->len && proof_words <= 0xffffffffull, "%s: a proof of %zu words in a buffer of %zu", who, proof_words, proof->len);
     NoiseKey nk;
     ZKH_TRY(resolve_noise_key(noise_key, &nk));
@@ -288,7 +346,7 @@ const char* page_witgen(const char* who, bool whole, zkh_ctx* ctx, const zkh_cir
     ZKH_TRY(image_proof_header(who, head, proof_words));
     const uint32_t W = head[1], D = head[2];
     uint32_t A, h, N;
-    ZKH_TRY(page_image_shape(who, po2, zk_cycles, W, &A, &h, &N));
+    ZKH_TRY(page_image_shape(who, sh, po2, zk_cycles, W, &A, &h, &N));
     const size_t L = image_leaves(W);
     ZKH_REQUIRE(nodes_before->len == 16 * L && nodes_after->len == 16 * L, "%s: nodes of %zu and %zu words; an image of %u words has a tree of %zu (zkh_image_tree_words)",
                 who, nodes_before->len, nodes_after->len, W, 16 * L);
@@ -319,11 +377,16 @@ const char* page_witgen(const char* who, bool whole, zkh_ctx* ctx, const zkh_cir
         ZKH_TRY(last_launch_error("page_root"));
     }
     {
-        ProfScope prof(ctx, "page_book", 4.0 * (PG_WD - PD_E) * rows + 4.0 * PG_WD * (n - rows));
+        ProfScope prof(ctx, "page_book", 4.0 * (PG_WD - PD_E) * rows + 4.0 * sh.wd * (n - rows));
         k_page_book<<<dim3((rows + PG_THREADS - 1) / PG_THREADS, PG_WD - PD_E), PG_THREADS, 0, ctx->stream>>>(data->ptr(), (uint32_t)n, h, N, table, D, first,
                                                                                                                nodes_after->ptr(), L, rec->ptr());
-        if (rows < n) k_page_tail<<<dim3((unsigned)((n - rows + 255) / 256), PG_WD), 256, 0, ctx->stream>>>(data->ptr(), (uint32_t)n, A, rows, nk);
+        if (rows < n) k_page_tail<<<dim3((unsigned)((n - rows + 255) / 256), sh.wd), 256, 0, ctx->stream>>>(data->ptr(), (uint32_t)n, A, rows, nk);
         ZKH_TRY(last_launch_error("page_book"));
+    }
+    if (sh.wd == PO_WD) {
+        ProfScope prof(ctx, "page_order", 4.0 * (PO_WD - PD_LIVE) * rows);
+        k_page_order<<<dim3((rows + PG_THREADS - 1) / PG_THREADS, PO_WD - PD_LIVE), PG_THREADS, 0, ctx->stream>>>(data->ptr(), (uint32_t)n, h, N, table, D, first, rec->ptr());
+        ZKH_TRY(last_launch_error("page_order"));
     }
     uint32_t r[PR_WORDS];
     ZKH_TRY(zkh_read(ctx, rec, r, 0, PR_WORDS));
@@ -333,41 +396,59 @@ const char* page_witgen(const char* who, bool whole, zkh_ctx* ctx, const zkh_cir
         return make_err("%s: row %u: address %u does not follow a smaller one (row %u: address %u)", who, r[PR_ROW], r[PR_A], r[PR_ROW] - 1, r[PR_BEFORE]);
     }
     memcpy(out_roots, r + PR_ROOTS, 4 * PG_OUT);
+    if (sh.out == PO_OUT) { out_roots[16] = r[PR_LO]; out_roots[17] = r[PR_HI]; }
     return nullptr;
+}
+
+// Both code groups: P2-PAGE's 39 columns, and behind them P2-PAGE-ordered's three
+const char* page_code(const char* who, const PageShape& sh, zkh_ctx* ctx, const zkh_circuit* c, size_t po2, size_t zk_cycles, size_t image_words, zkh_buf* code) {
+    ZKH_REQUIRE(ctx && c && code, "%s: null argument", who);
+    ZKH_TRY(page_circuit_shape(who, sh, c, po2, zk_cycles));
+    const size_t n = (size_t)1 << po2;
+    ZKH_REQUIRE(code->len == (size_t)sh.wc * n, "%s: buffer shape mismatch", who);
+    uint32_t A, h, N;
+    ZKH_TRY(page_image_shape(who, sh, po2, zk_cycles, image_words, &A, &h, &N));
+    Tmp tab;
+    ZKH_TRY(p2_rows_tables(ctx, tab));
+    ProfScope prof(ctx, "page_code", 4.0 * sh.wc * n);
+    k_page_code<<<dim3((unsigned)((n + 255) / 256), PG_WC), 256, 0, ctx->stream>>>(code->ptr(), (uint32_t)n, A, h, N, tab->ptr());
+    if (sh.wc == PO_WC) k_page_order_code<<<dim3((unsigned)((n + 255) / 256), PO_WC - PG_WC), 256, 0, ctx->stream>>>(code->ptr(), (uint32_t)n, h, N);
+    return last_launch_error("page_code");
 }
 
 }  // namespace
 
 extern "C" const char* zkh_page_circuit_code(zkh_ctx* ctx, const zkh_circuit* c, size_t po2, size_t zk_cycles, size_t image_words, zkh_buf* code) {
-    static const char who[] = "page_circuit_code";
-    ZKH_REQUIRE(ctx && c && code, "%s: null argument", who);
-    ZKH_TRY(page_circuit_shape(who, c, po2, zk_cycles));
-    const size_t n = (size_t)1 << po2;
-    ZKH_REQUIRE(code->len == (size_t)PG_WC * n, "%s: buffer shape mismatch", who);
-    uint32_t A, h, N;
-    ZKH_TRY(page_image_shape(who, po2, zk_cycles, image_words, &A, &h, &N));
-    Tmp tab;
-    ZKH_TRY(p2_rows_tables(ctx, tab));
-    ProfScope prof(ctx, "page_code", 4.0 * PG_WC * n);
-    k_page_code<<<dim3((unsigned)((n + 255) / 256), PG_WC), 256, 0, ctx->stream>>>(code->ptr(), (uint32_t)n, A, h, N, tab->ptr());
-    return last_launch_error("page_code");
+    return page_code("page_circuit_code", PAGE, ctx, c, po2, zk_cycles, image_words, code);
 }
 
 // HOST ONLY: N of (po2, zk_cycles, an image of `image_words` words), 0 where zkh_page_circuit_code refuses the shape
 extern "C" size_t zkh_page_circuit_slots(size_t po2, size_t zk_cycles, size_t image_words) {
     uint32_t A, h, N;
-    return page_po2_ok(po2, zk_cycles) && !page_image_shape("page_circuit_slots", po2, zk_cycles, image_words, &A, &h, &N) ? N : 0;
+    return page_po2_ok(po2, zk_cycles) && !page_image_shape("page_circuit_slots", PAGE, po2, zk_cycles, image_words, &A, &h, &N) ? N : 0;
 }
 
 extern "C" const char* zkh_page_circuit_witgen(zkh_ctx* ctx, const zkh_circuit* c, size_t po2, size_t zk_cycles, const zkh_buf* code, const zkh_buf* proof,
                                                size_t proof_words, const zkh_buf* nodes_before, const zkh_buf* nodes_after, zkh_buf* data,
                                                uint32_t out_roots[16], const uint32_t* noise_key) {
-    return page_witgen("page_circuit_witgen", true, ctx, c, po2, zk_cycles, code, proof, proof_words, nodes_before, nodes_after, 0, data, out_roots, noise_key);
+    return page_witgen("page_circuit_witgen", PAGE, true, ctx, c, po2, zk_cycles, code, proof, proof_words, nodes_before, nodes_after, 0, data, out_roots, noise_key);
 }
 
 extern "C" const char* zkh_page_circuit_witgen_part(zkh_ctx* ctx, const zkh_circuit* c, size_t po2, size_t zk_cycles, const zkh_buf* code, const zkh_buf* proof,
                                                     size_t proof_words, const zkh_buf* nodes_before, const zkh_buf* nodes_after, size_t first, zkh_buf* data,
                                                     uint32_t out_roots[16], const uint32_t* noise_key) {
-    return page_witgen("page_circuit_witgen_part", false, ctx, c, po2, zk_cycles, code, proof, proof_words, nodes_before, nodes_after, first, data, out_roots,
+    return page_witgen("page_circuit_witgen_part", PAGE, false, ctx, c, po2, zk_cycles, code, proof, proof_words, nodes_before, nodes_after, first, data, out_roots,
+                       noise_key);
+}
+
+// P2-PAGE-ordered (zeth_amd/circuits/p2_page_ordered.py): the same two calls on the wider circuit
+extern "C" const char* zkh_page_ordered_code(zkh_ctx* ctx, const zkh_circuit* c, size_t po2, size_t zk_cycles, size_t image_words, zkh_buf* code) {
+    return page_code("page_ordered_code", ORDERED, ctx, c, po2, zk_cycles, image_words, code);
+}
+
+extern "C" const char* zkh_page_ordered_witgen(zkh_ctx* ctx, const zkh_circuit* c, size_t po2, size_t zk_cycles, const zkh_buf* code, const zkh_buf* proof,
+                                               size_t proof_words, const zkh_buf* nodes_before, const zkh_buf* nodes_after, size_t first, zkh_buf* data,
+                                               uint32_t out[18], const uint32_t* noise_key) {
+    return page_witgen("page_ordered_witgen", ORDERED, false, ctx, c, po2, zk_cycles, code, proof, proof_words, nodes_before, nodes_after, first, data, out,
                        noise_key);
 }

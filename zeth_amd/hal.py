@@ -195,6 +195,8 @@ ABI = {
     "zkh_page_circuit_witgen": (_err, [_vp, _vp, _sz, _sz, _vp, _vp, _sz, _vp, _vp, _vp, _u32p, _u32p]),
     "zkh_page_circuit_witgen_part": (_err, [_vp, _vp, _sz, _sz, _vp, _vp, _sz, _vp, _vp, _sz, _vp, _u32p, _u32p]),
     "zkh_page_circuit_slots": (_sz, [_sz, _sz, _sz]),
+    "zkh_page_ordered_code": (_err, [_vp, _vp, _sz, _sz, _sz, _vp]),
+    "zkh_page_ordered_witgen": (_err, [_vp, _vp, _sz, _sz, _vp, _vp, _sz, _vp, _vp, _sz, _vp, _u32p, _u32p]),
     "zkh_circuit_derived_data_columns": (_err, [_vp, _u32p, _sz, C.POINTER(_sz)]),
     "zkh_upload_data_trace": (_err, [_vp, _vp, _sz, _sz, _vp, _u32p, _i]),
     "zkh_ctx_h2d_bytes": (_sz, [_vp]),
@@ -980,6 +982,28 @@ class HipHal:
         _k, kp = _key_ptr(noise_seed)
         _check(_lib.zkh_page_circuit_witgen_part(self.ctx, circuit.h, po2, zk_cycles, code.h, proof.h, proof_words, nodes_before.h, nodes_after.h, first,
                                                  data.h, _ptr(out), kp))
+        return out
+
+    def page_ordered_code(self, circuit: Circuit, po2: int, zk_cycles: int, image_words: int, code: Optional[Buffer] = None) -> Buffer:
+        """the code group of P2-PAGE-ordered (circuits/p2_page_ordered.py) for (po2, zk_cycles, the tree height of an image of
+        `image_words` words) (zkh_page_ordered_code; the host twin: p2_page_ordered.reference_ordered_code).  code: a Buffer of 42 x
+        2^po2 words to write (default: a new one).  Raises HalError as page_circuit_code does, and on h > 26"""
+        if code is None:
+            code = self.alloc_elem("code", int(circuit.desc[4]) << po2)
+        _check(_lib.zkh_page_ordered_code(self.ctx, circuit.h, po2, zk_cycles, image_words, code.h))
+        return code
+
+    def page_ordered_witgen(self, circuit: Circuit, po2: int, zk_cycles: int, code: Buffer, proof: Buffer, proof_words: int, nodes_before: Buffer,
+                            nodes_after: Buffer, first: int, data: Buffer, noise_seed: int) -> np.ndarray:
+        """the data group of P2-PAGE-ordered for the part at `first` of the page-out a ZKU1 proof describes (zkh_page_ordered_witgen;
+        the host twin: p2_page_ordered.reference_ordered_part) -> the out globals, root_before ‖ root_after ‖ lo ‖ hi (18 words: lo
+        and hi as the trace holds them, p2_page_ordered.decode).  The operands are page_circuit_witgen_part's, `data` of 129 x 2^po2
+        words; first = 0 with D <= N is the single-seal case.  Raises HalError with one message per cause (include/zkhal.h
+        "P2-PAGE-ordered"); `data` is unspecified then"""
+        out = np.zeros(2 * DIGEST_WORDS + 2, dtype=np.uint32)
+        _k, kp = _key_ptr(noise_seed)
+        _check(_lib.zkh_page_ordered_witgen(self.ctx, circuit.h, po2, zk_cycles, code.h, proof.h, proof_words, nodes_before.h, nodes_after.h, first,
+                                            data.h, _ptr(out), kp))
         return out
 
     def derive_multiplicities(self, circuit: Circuit, po2: int, zk_cycles: int, code: Buffer, data: Buffer) -> None:

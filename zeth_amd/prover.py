@@ -412,6 +412,39 @@ class SegmentProver:
             receipts.append(receipt)
         return receipts
 
+    def seal_page_out_ordered(self, segs, proof, proof_words: int, nodes_before, nodes_after, check: bool = False) -> list:
+        """Seal a page-out of any size with P2-PAGE-ordered (this prover's circuit: circuits/p2_page_ordered.py) as a chain of parts:
+        seal_page_out_parts with the order of the addresses constrained.  Part p's receipt's output is root_before ‖ root_after ‖ lo ‖
+        hi of its run of updates (zkh_page_ordered_witgen), so part p + 1 opens the root and starts at the `hi` part p left
+        (`verify_page_ordered_chain`).  The operands and the plan (p2_page.parts) are seal_page_out_parts'; one code group, one
+        control root, one data buffer.  -> the receipts, in the order of the parts."""
+        from .circuits import p2_page
+        segs = list(segs)
+        if not segs:
+            raise _hal.HalError("seal_page_out_ordered: no segment")
+        po2, zk = segs[0].po2, segs[0].zk_cycles
+        if any((s.po2, s.zk_cycles) != (po2, zk) for s in segs):
+            raise _hal.HalError("seal_page_out_ordered: the parts share one code group: every segment must have the same (po2, zk_cycles)")
+        if not isinstance(proof, _hal.Buffer):
+            proof = self.hal.copy_from("image_proof", np.ascontiguousarray(proof, dtype=np.uint32).reshape(-1))
+        header = proof.slice(0, min(3, proof.size())).to_vec()
+        W, D = (int(header[1]), int(header[2])) if header.size > 2 else (0, 0)
+        wa, wc, wd = self.group_sizes()
+        code = self.hal.page_ordered_code(self.circuit, po2, zk, W)            # refuses a shape without a path slot, and h > 26
+        plan = p2_page.parts(po2, zk, W, D)
+        if len(segs) != len(plan):
+            raise _hal.HalError(f"seal_page_out_ordered: {len(segs)} segments, but a table of {D} rows takes {len(plan)} parts of "
+                                f"{self.hal.page_circuit_slots(po2, zk, W)} slots at po2 {po2}")
+        control_root = self.code_root(code, po2)
+        data = self.hal.alloc_elem("data", wd << po2)
+        receipts = []
+        for seg, (first, _count) in zip(segs, plan):
+            out = self.hal.page_ordered_witgen(self.circuit, po2, zk, code, proof, proof_words, nodes_before, nodes_after, first, data, seg.noise_seed)
+            receipt = self.seal_with_accum(seg, code, data, out, self.syn_accumulate(seg, data), check=check)
+            receipt.control_root = control_root.copy()
+            receipts.append(receipt)
+        return receipts
+
     def prove_segment(self, seg: Segment) -> SegmentReceipt:
         code, data, out = self.witgen(seg)
         return self.seal(seg, code, data, out)
@@ -438,6 +471,38 @@ def verify_page_out_chain(receipts, control_root, root_before=None) -> Tuple[np.
         if not np.array_equal(roots[p + 1][0], roots[p][1]):
             raise _hal.HalError(f"verify_page_out_chain: part {p + 1} opens root {fmt(roots[p + 1][0])}, but part {p} left root {fmt(roots[p][1])}")
     return roots[0][0], roots[-1][1]
+
+
+def verify_page_ordered_chain(receipts, control_root, root_before=None) -> Tuple[np.ndarray, np.ndarray, int]:
+    """Verify the chain of P2-PAGE-ordered seals of one page-out (SegmentProver.seal_page_out_ordered), HOST ONLY -> (root_before,
+    root_after, hi) of the whole page-out: its live updates have strictly increasing addresses, the last of them hi - 1 (hi = 0: none).
+    Every seal is verified against P2-PAGE-ordered's description and `control_root` (one for all parts); every lo and hi must decode
+    to at most 2^29 (what the circuit's 29-bit gaps are sound for); part 0 must have lo = 0; part p + 1 must open the root part p left
+    and start at the hi part p left; with a `root_before`, part 0 must open it.  Raises HalError, one message per cause."""
+    from .circuits import p2_page_ordered as po
+    receipts = list(receipts)
+    if not receipts:
+        raise _hal.HalError("verify_page_ordered_chain: no receipt (a page-out of no rows still has one part)")
+    hc = _hal.HostCircuit(po.p2_page_ordered_circuit())
+    fmt = lambda r: " ".join(f"{int(w):08x}" for w in r)
+    parts = []
+    for p, r in enumerate(receipts):
+        hc.verify_segment(r.seal, control_root)
+        lo, hi = po.decode(r.seal[po.OUT_LO]), po.decode(r.seal[po.OUT_HI])
+        for name, v in (("lo", lo), ("hi", hi)):
+            if v > 1 << po.GAP_BITS:
+                raise _hal.HalError(f"verify_page_ordered_chain: part {p}: {name} {v} is above 2^{po.GAP_BITS}, the bound the order check is sound for")
+        parts.append((np.array(r.seal[:8], dtype=np.uint32), np.array(r.seal[8:16], dtype=np.uint32), lo, hi))
+    if parts[0][2] != 0:
+        raise _hal.HalError(f"verify_page_ordered_chain: part 0 starts at lo {parts[0][2]}, not 0: addresses below it are not covered")
+    if root_before is not None and not np.array_equal(parts[0][0], np.asarray(root_before, dtype=np.uint32)):
+        raise _hal.HalError(f"verify_page_ordered_chain: part 0 opens root {fmt(parts[0][0])}, not root_before {fmt(root_before)}")
+    for p in range(len(parts) - 1):
+        if not np.array_equal(parts[p + 1][0], parts[p][1]):
+            raise _hal.HalError(f"verify_page_ordered_chain: part {p + 1} opens root {fmt(parts[p + 1][0])}, but part {p} left root {fmt(parts[p][1])}")
+        if parts[p + 1][2] != parts[p][3]:
+            raise _hal.HalError(f"verify_page_ordered_chain: part {p + 1} starts at lo {parts[p + 1][2]}, but part {p} left hi {parts[p][3]}")
+    return parts[0][0], parts[-1][1], parts[-1][3]
 
 
 def _generate_control_roots(po2s=range(13, 25)) -> None:
