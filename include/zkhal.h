@@ -500,6 +500,37 @@ const char* zkh_page_ordered_code(zkh_ctx*, const zkh_circuit*, size_t po2, size
 const char* zkh_page_ordered_witgen(zkh_ctx*, const zkh_circuit*, size_t po2, size_t zk_cycles, const zkh_buf* code, const zkh_buf* proof, size_t proof_words,
                                     const zkh_buf* nodes_before, const zkh_buf* nodes_after, size_t first, zkh_buf* data, uint32_t out[18],
                                     const uint32_t noise_key[8]);
+/* P2-TREE (circuit kind 7, zeth_amd/circuits/p2_tree.py; csrc/page_tree.hip): a page-out sealed by its DIRTY NODES instead of one path
+ * per word.  Its seal proves "a set of pairs of leaves (16 words each), in strictly increasing order, is replaced, and the replacement
+ * takes root_before to root_after": out = root_before (8) ‖ root_after (8) ‖ lo ‖ hi (18 words), lo and hi bounding the HEAP IDS of
+ * the part's pair blocks (a pair of leaves q of a tree of L = 2^h leaves has id L/2 + q) as P2-PAGE-ordered's bound addresses.  A chain
+ * whose part 0 has lo = 2^(h-1), whose part p + 1 opens the root and starts at the hi part p left, and whose last hi is at most 2^h
+ * seals a page-out of any size; the verifier is told h.  The trace is B = (2^po2 - zk_cycles) / 31 blocks of P2-JOIN's 31 rows, one
+ * tree node each, old and new permutation side by side; a parent reads its children over a bus in the accum group (24 columns), which
+ * zkh_accumulate fills from the circuit's ZKA1 arguments (zkh_circuit_set_arguments with p2_tree.arguments()): zkh_syn_accum does not
+ * serve kind 7.  The columns, the constraints and why the bus forces a tree: p2_tree.py.  Still NOT constrained: which words of a pair
+ * changed, and that the table is the page table of a paging segment's seal.  W > 16, h = 2 .. 27, B >= h.
+ * zkh_page_tree_code: `code` of 41 x 2^po2 words, a function of (po2, zk_cycles) alone: one control root for every image size.
+ * zkh_page_tree_plan (HOST ONLY): the parts of a table with the addresses addrs[0 .. D) (strictly increasing, below image_words), greedy:
+ * a part takes whole pairs of leaves while its nodes stay at most B, its first pair costing h nodes and every later one bit_length(pair
+ * index xor the one before).  parts[2 p], parts[2 p + 1] = (first, count) of part p for p < parts_cap; *n_parts is the number of parts
+ * whatever parts_cap is (D = 0: the one part (0, 0)).  The addresses are the host's: one read-back of D words; planning on the device
+ * is out of scope.
+ * zkh_page_tree_witgen: zkh_page_ordered_witgen's operands with the part as (first, count), `data` of 106 x 2^po2 words, out[18].  Both
+ * trees are the WHOLE page-out's for every part.  One read-back at the end, no atomics, one writer per cell.  Refusals after
+ * "page_tree_witgen: " (the shape ones also after "page_tree_code: " / "page_tree_plan: "): "the circuit does not have P2-TREE's shape
+ * (kind 7, 41 / 106 / 24 columns, 18 outputs)"; "an image of W words has a single pair of leaves (W > 16: ...)"; "no room for the h H
+ * nodes of one path in B block slots"; the proof header's and the tree buffers' as zkh_page_circuit_witgen; "the part [F, E) of a table
+ * of D rows"; then, from the check pass over the whole table and before any tree is indexed: "row R: address A outside the image of W
+ * words", "row R: address A does not follow a smaller one (row R-1: address A')", "the part [F, E) splits a pair of leaves: rows R-1
+ * and R write the same 16 words", "the part [F, E) has N dirty nodes, but po2 P leaves B block slots".  A table that does not match
+ * the trees is not refused here: its bus does not balance, zkh_accumulate refuses it and zkh_check_bus names the key. */
+const char* zkh_page_tree_code(zkh_ctx*, const zkh_circuit*, size_t po2, size_t zk_cycles, zkh_buf* code);
+const char* zkh_page_tree_plan(size_t po2, size_t zk_cycles, size_t image_words, const uint32_t* addrs, size_t D, size_t* parts, size_t parts_cap,
+                               size_t* n_parts);
+const char* zkh_page_tree_witgen(zkh_ctx*, const zkh_circuit*, size_t po2, size_t zk_cycles, const zkh_buf* code, const zkh_buf* proof, size_t proof_words,
+                                 const zkh_buf* nodes_before, const zkh_buf* nodes_after, size_t first, size_t count, zkh_buf* data, uint32_t out[18],
+                                 const uint32_t noise_key[8]);
 /* Everything a circuit's arguments derive, in the one order in which it is sound: sorted copies, then columns, then links, then
  * multiplicities (a LIMBS / ORDER record may read a sorted copy's column, and the multiplicities count the limbs that the records and
  * the links derive).  Call it after the data upload and before zkh_prove_begin: what it writes belongs to the data group.  It runs
@@ -535,7 +566,8 @@ size_t zkh_ctx_h2d_bytes(const zkh_ctx*);
  *                    `pub` = the two child claims (16 words, required); out_global = parent (8) ‖ left (8) ‖ right (8).
  *   kind 5 P2-PAGE   has a generator of its own, zkh_page_circuit_code / zkh_page_circuit_witgen above (its inputs are a proof and
  *                    two trees, not a seed); zkh_syn_accum builds its accum group, which is P2-JOIN's.
- *   kind 6 P2-PAGE-ordered  likewise: zkh_page_ordered_code / zkh_page_ordered_witgen above, and zkh_syn_accum. */
+ *   kind 6 P2-PAGE-ordered  likewise: zkh_page_ordered_code / zkh_page_ordered_witgen above, and zkh_syn_accum.
+ *   kind 7 P2-TREE   zkh_page_tree_code / zkh_page_tree_witgen above; its accum group is a bus: zkh_accumulate, not zkh_syn_accum. */
 /* BLINDING ROWS.  The last zk_cycles rows of every data / accum column are zero-knowledge blinding noise.  Upstream draws each
  * cell from the OS RNG (`Elem::random(&mut rng)`); here the randomness enters once per call as a 256-bit key — `noise_key`, 8
  * words — and every cell is ChaCha12(key; counter = (row, column), nonce = (group, "ZKN1")) folded mod P the way upstream's

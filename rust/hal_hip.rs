@@ -536,6 +536,37 @@ impl HipCircuitHal {
         out
     }
 
+    /// The code group of P2-TREE, a page-out sealed by its dirty nodes (`zkh_page_tree_code`): 41 columns, a function of the trace's
+    /// size alone, so one control root serves every image size.  `self` holds the P2-TREE description with its ZKA1 arguments set.
+    pub fn page_tree_code(&self, code: &HipBuffer<BabyBearElem>, steps: usize) {
+        let po2 = steps.trailing_zeros() as usize;
+        ffi(|| unsafe { sys::zkh_page_tree_code(self.hal.ctx.0, self.circuit, po2, sys::ZK_CYCLES, code.raw) });
+    }
+
+    /// The parts `(first, count)` of a page-out with the addresses `addrs` (strictly increasing, below `image_words`) as P2-TREE traces
+    /// (`zkh_page_tree_plan`, host only): whole pairs of leaves while a part's dirty nodes fit the trace's block slots.
+    pub fn page_tree_plan(image_words: usize, addrs: &[u32], steps: usize) -> Vec<(usize, usize)> {
+        let po2 = steps.trailing_zeros() as usize;
+        let cap = addrs.len().max(1);
+        let (mut parts, mut n) = (vec![0usize; 2 * cap], 0usize);
+        ffi(|| unsafe { sys::zkh_page_tree_plan(po2, sys::ZK_CYCLES, image_words, addrs.as_ptr(), addrs.len(), parts.as_mut_ptr(), cap, &mut n) });
+        (0..n).map(|p| (parts[2 * p], parts[2 * p + 1])).collect()
+    }
+
+    /// The data group of P2-TREE for the part `[first, first + count)` of a page-out (`zkh_page_tree_witgen`), and the `out` globals:
+    /// the root before the part, the root after it, then lo and hi (Montgomery words) bounding the heap ids of its pair blocks.  The
+    /// other operands are `page_ordered_witgen`'s, `data` has 106 columns; the accum group comes from `zkh_accumulate`.  Part p + 1
+    /// opens the root and starts at the hi part p left; part 0 starts at 2^(h-1).  Panics on the refusals include/zkhal.h lists.
+    pub fn page_tree_witgen(&self, code: &HipBuffer<BabyBearElem>, proof: &HipBuffer<u32>, words: usize, nodes_before: &HipBuffer<BabyBearElem>,
+                            nodes_after: &HipBuffer<BabyBearElem>, first: usize, count: usize, data: &HipBuffer<BabyBearElem>, steps: usize,
+                            noise_key: Option<&[u32; 8]>) -> [u32; 18] {
+        let po2 = steps.trailing_zeros() as usize;
+        let mut out = [0u32; 18];
+        ffi(|| unsafe { sys::zkh_page_tree_witgen(self.hal.ctx.0, self.circuit, po2, sys::ZK_CYCLES, code.raw, proof.raw, words, nodes_before.raw,
+                                                  nodes_after.raw, first, count, data.raw, out.as_mut_ptr(), noise_key.map_or(std::ptr::null(), |k| k.as_ptr())) });
+        out
+    }
+
     /// Check the raw traces against the circuit's own constraints on every row of `rows` (`zkh_check_rows`): which constraint a
     /// witness breaks, and where, before a seal is spent on it.  `out` and `mix` are the global words.  `row < 0`: no row of the window
     /// fails; otherwise the lowest failing row, its lowest failing `and_eqz` step (an index into the ZKC1 step list), how many rows of

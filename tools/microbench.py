@@ -18,7 +18,9 @@ zkh_page_out_tree, alternating, with the number of permutations; M21: P2-PAGE's 
 h = 17 and h = 23 next to zkh_syn_witgen of P2-JOIN at the same po2, alternating, with both calls' stages; M22: P2-PAGE's parts,
 zkh_page_circuit_witgen_part on a table of 4 N rows at first = 0, N, 2 N, 3 N next to zkh_page_circuit_witgen on its first N rows,
 alternating, with every call's stages; M23: P2-PAGE-ordered, zkh_page_ordered_witgen next to zkh_page_circuit_witgen_part at first = 0 and
-first = N of one table, and the seal of a part under both circuits, alternating, with every witness call's stages) on one MI355X, through
+first = N of one table, and the seal of a part under both circuits, alternating, with every witness call's stages; M24: P2-TREE, the
+parts of one page-out of 662 267 addresses under p2_tree's plan and under P2-PAGE's, zkh_page_tree_witgen next to
+zkh_page_ordered_witgen and the seal of a part under both circuits, alternating, with every witness call's stages) on one MI355X, through
 the C ABI (HipHal).
 
 Each line of output is one JSON object: the op, its shape, the average wall time of one call (stream drained on both
@@ -1116,6 +1118,91 @@ def main() -> None:
                               "ordered_minus_page_ms": {f"first_{p}N": round((med[f"page_ordered_witgen_first_{p}N"] - med[f"page_circuit_witgen_part_first_{p}N"]) * 1e3, 4)
                                                         for p in range(2)},
                               "seal_ratio": round(med["seal_ordered"] / med["seal_page"], 4), "code_and_data_columns": {"page": 39 + 125, "ordered": 42 + 129}}),
+                  flush=True)
+            del before, after, proof, codes
+        del datas
+    if want("M24"):
+        # P2-TREE: one page-out of 662 267 random addresses (the paging segment's own table at po2 20) planned and sealed by dirty nodes
+        # next to P2-PAGE-ordered's paths: the parts under both plans, zkh_page_tree_witgen (part 0 and the middle part) next to
+        # zkh_page_ordered_witgen (first = 0) in M23's windows with every call's stages by their events, and the seal of part 0 under both
+        # circuits (41 + 106 code and data columns and 24 accum columns through zkh_accumulate against 42 + 129 and 4 through zkh_syn_accum).
+        # Both chains must start from the same root; no threshold on any time.
+        from zeth_amd import hal as zhal
+        from zeth_amd.circuits import p2_page, p2_page_ordered, p2_tree
+        from zeth_amd.prover import Segment, SegmentProver
+        runs, zk, D = 7, 1994, 662267
+        spread = lambda ts: {"median_ms": round(float(np.median(ts)) * 1e3, 4), "min_ms": round(min(ts) * 1e3, 4), "max_ms": round(max(ts) * 1e3, 4)}   # noqa: E731
+        provers = {"tree": SegmentProver(hal, p2_tree.p2_tree_circuit(), arguments=p2_tree.arguments()),
+                   "ordered": SegmentProver(hal, p2_page_ordered.p2_page_ordered_circuit())}
+        datas = {"tree": hal.alloc_elem("m24td", p2_tree.WD * n), "ordered": hal.alloc_elem("m24od", p2_page_ordered.WD * n)}
+        u32p = zhal._u32p
+        key = zhal.noise_key(0x2E80)
+        for W in (1 << 20, 1 << 26):
+            h = p2_page.tree_height(W)
+            image_h = rand_fp(rng, W)
+            addrs = np.sort(rng.choice(W, D, replace=False)).astype(np.int64)
+            outs = rand_fp(rng, D)
+            table = np.stack([addrs.astype(np.uint32), image_h[addrs], outs], axis=1).reshape(-1)
+            proof_h = np.concatenate([np.array([0x5A4B5531, W, D, 0, h] + [0] * h, dtype=np.uint32), table])
+            image = hal.alloc_elem("m24i", W)
+            image.write(image_h)
+            before = hal.image_commit(image)
+            image_h[addrs] = outs
+            image.write(image_h)
+            after = hal.image_commit(image)
+            del image
+            proof = hal.copy_from("m24p", proof_h)
+            t0 = time.perf_counter()
+            plan = hal.page_tree_plan(args.po2, zk, W, addrs)
+            plan_ms = (time.perf_counter() - t0) * 1e3
+            ordered_plan = p2_page.parts(args.po2, zk, W, D)
+            codes = {"tree": hal.page_tree_code(provers["tree"].circuit, args.po2, zk), "ordered": hal.page_ordered_code(provers["ordered"].circuit, args.po2, zk, W)}
+            out_t, out_o = np.zeros(18, dtype=np.uint32), np.zeros(18, dtype=np.uint32)
+            tree_fn = lambda part: lambda: zhal._check(zhal._lib.zkh_page_tree_witgen(hal.ctx, provers["tree"].circuit.h, args.po2, zk, codes["tree"].h, proof.h,   # noqa: E731
+                                                                                      proof_h.size, before.h, after.h, part[0], part[1], datas["tree"].h,
+                                                                                      out_t.ctypes.data_as(u32p), key.ctypes.data_as(u32p)))
+            ordered_fn = lambda first: lambda: zhal._check(zhal._lib.zkh_page_ordered_witgen(hal.ctx, provers["ordered"].circuit.h, args.po2, zk, codes["ordered"].h, proof.h,   # noqa: E731
+                                                                                             proof_h.size, before.h, after.h, first, datas["ordered"].h,
+                                                                                             out_o.ctypes.data_as(u32p), key.ctypes.data_as(u32p)))
+            mid = len(plan) // 2
+            fns = [("page_tree_witgen_part_0", tree_fn(plan[0])), ("page_ordered_witgen_first_0", ordered_fn(0)), (f"page_tree_witgen_part_{mid}", tree_fn(plan[mid]))]
+            tree_fn(plan[0])()
+            ordered_fn(0)()
+            assert np.array_equal(out_t[:8], out_o[:8]), "the two chains do not start from the same root"
+            assert p2_tree.decode(out_t[16]) == 1 << (h - 1) and p2_tree.decode(out_t[17]) == (1 << (h - 1)) + (int(addrs[plan[0][1] - 1]) >> 4) + 1
+            seg = Segment(index=0, po2=args.po2, zk_cycles=zk, noise_seed=0x2E80)
+            seals = [("seal_tree", lambda: provers["tree"].seal_with_accum(seg, codes["tree"], datas["tree"], out_t.copy(),
+                                                                           provers["tree"].args_accumulate(seg, codes["tree"], datas["tree"]))),
+                     ("seal_ordered", lambda: provers["ordered"].seal_with_accum(seg, codes["ordered"], datas["ordered"], out_o.copy(),
+                                                                                 provers["ordered"].syn_accumulate(seg, datas["ordered"])))]
+            t = {name: [] for name, _ in fns + seals}
+            for _ in range(runs):
+                for name, fn in fns:
+                    t[name].append(timed(hal, fn, args.reps))
+            steps = {}
+            for name, fn in fns:
+                hal.prof_enable(True)
+                hal.prof_reset()
+                for _ in range(args.reps):
+                    fn()
+                hal.sync()
+                steps[name] = {r["name"]: {"calls_per_call": r["calls"] // args.reps, "ms_per_call": round(r["total_ms"] / args.reps, 4)} for r in hal.prof_get()
+                               if r["calls"] and r["name"].startswith(("page_", "tree_"))}
+                hal.prof_enable(False)
+            tree_fn(plan[0])()                                               # the witnesses of part 0 again, for the seals
+            ordered_fn(0)()
+            for _ in range(runs):
+                for name, fn in seals:
+                    t[name].append(timed(hal, fn, args.reps))
+            med = {k: float(np.median(v)) for k, v in t.items()}
+            print(json.dumps({"bench": "M24", "library": os.path.basename(os.environ.get("ZKH_LIBRARY", "") or "libzkhal_mi355x.so"), "po2": args.po2,
+                              "image_words": W, "layers": h, "table_rows": D, "block_slots": p2_tree.block_slots(args.po2, zk),
+                              "path_slots": p2_page.slots(args.po2, zk, h), "parts": {"tree": len(plan), "ordered": len(ordered_plan)},
+                              "tree_part_rows": {"min": min(c for _, c in plan), "max": max(c for _, c in plan)}, "plan_host_ms": round(plan_ms, 3),
+                              "runs": runs, "reps": args.reps, **{k: spread(v) for k, v in t.items()}, "steps": steps,
+                              "seal_ratio_tree_over_ordered": round(med["seal_tree"] / med["seal_ordered"], 4),
+                              "columns": {"tree": {"code": p2_tree.WC, "data": p2_tree.WD, "accum": p2_tree.WA},
+                                          "ordered": {"code": p2_page_ordered.WC, "data": p2_page_ordered.WD, "accum": p2_page_ordered.WA}}}),
                   flush=True)
             del before, after, proof, codes
         del datas

@@ -66,19 +66,12 @@ def slots(po2: int, zk_cycles: int, h: int) -> int:
     return (((1 << po2) - zk_cycles) // BLOCK_ROWS) // h
 
 
-def build_page(kind: int, sizes: Tuple[int, int, int], out_words: int, after_roots=None):
-    """-> (blob, families): P2-PAGE's constraint text over a circuit of `sizes` (accum, code, data) columns and `out_words` outputs.
-    after_roots(b, chain, gated, env) -> chain emits one more family, named by after_roots.family, between `roots` and `accum`
-    (p2_page_ordered.py); without it this is P2-PAGE word for word."""
-    b = CircuitBuilder(sizes, (out_words, WA), kind=kind)
-    code = lambda c, back=0: b.get(GROUP_CODE, c, back)
-    dat = lambda c, back=0: b.get(GROUP_DATA, c, back)
-    acc4 = lambda c, back=0: b.get(GROUP_ACCUM, c, back)
-    out = lambda i: b.get_global(GLOBAL_OUT, i)
-    one = b.const(1)
-    active, first, body = code(0), code(1), code(2)
-    cst = {v: b.const(v) for v in (2, 3, 4, 5, 6, 7)}
-    families = []
+def emit_rounds(b, chain, gated, code, dat, cst, sides, cols, input_rows):
+    """The `rounds` family P2-PAGE, P2-PAGE-ordered and P2-TREE (p2_tree.py) share, emitted onto `chain`: P2-JOIN's round constraints
+    on every (S, Q) pair of `sides` (data column offsets), and the capacity cells S[16 .. 24) zero where the selector `input_rows()`
+    (built after the round constraints, as the builders always did) is set.  cols = the code columns (lin, fullr, partr, lf, lp, rc);
+    cst = the constants 2 .. 7 as handles; gated(chain, selector, constraints) -> chain."""
+    c_lin, c_fullr, c_partr, c_lf, c_lp, c_rc = cols
 
     def times(c, x):
         return x if c == 1 else b.mul(cst[c], x)
@@ -99,6 +92,45 @@ def build_page(kind: int, sizes: Tuple[int, int, int], out_words: int, after_roo
             tot.append(e)
         return [b.add(y[k], tot[k % 4]) for k in range(T)]
 
+    diag = [b.const(d) for d in DIAG]
+    cube = lambda x: b.mul(b.mul(x, x), x)
+    cap = []
+    for s0, q0 in sides:
+        S = lambda j, back=0, s0=s0: dat(s0 + j, back)
+        Q = lambda j, back=0, q0=q0: dat(q0 + j, back)
+        u = [b.add(S(j), code(c_rc + j)) for j in range(T)]
+        chain = gated(chain, code(c_fullr), [b.sub(Q(j), cube(u[j])) for j in range(T)])
+        chain = gated(chain, code(c_partr), [b.sub(Q(0), cube(u[0]))])
+        prev = [S(j, 1) for j in range(T)]
+        chain = gated(chain, code(c_lin), [b.sub(S(k), e) for k, e in enumerate(lin_m_ext(prev))])
+        x7 = [b.mul(b.mul(Q(j, 1), Q(j, 1)), b.add(S(j, 1), code(c_rc + j, 1))) for j in range(T)]
+        chain = gated(chain, code(c_lf), [b.sub(S(k), e) for k, e in enumerate(lin_m_ext(x7))])
+        tot = x7[0]
+        for j in range(1, T):
+            tot = b.add(tot, prev[j])
+        chain = gated(chain, code(c_lp), [b.sub(S(0), b.add(tot, b.mul(diag[0], x7[0])))]
+                      + [b.sub(S(j), b.add(tot, b.mul(diag[j], prev[j]))) for j in range(1, T)])
+        cap += [S(16 + i) for i in range(8)]
+    return gated(chain, input_rows(), cap)
+
+
+def build_page(kind: int, sizes: Tuple[int, int, int], out_words: int, after_roots=None):
+    """-> (blob, families): P2-PAGE's constraint text over a circuit of `sizes` (accum, code, data) columns and `out_words` outputs.
+    after_roots(b, chain, gated, env) -> chain emits one more family, named by after_roots.family, between `roots` and `accum`
+    (p2_page_ordered.py); without it this is P2-PAGE word for word."""
+    b = CircuitBuilder(sizes, (out_words, WA), kind=kind)
+    code = lambda c, back=0: b.get(GROUP_CODE, c, back)
+    dat = lambda c, back=0: b.get(GROUP_DATA, c, back)
+    acc4 = lambda c, back=0: b.get(GROUP_ACCUM, c, back)
+    out = lambda i: b.get_global(GLOBAL_OUT, i)
+    one = b.const(1)
+    active, first, body = code(0), code(1), code(2)
+    cst = {v: b.const(v) for v in (2, 3, 4, 5, 6, 7)}
+    families = []
+
+    def times(c, x):
+        return x if c == 1 else b.mul(cst[c], x)
+
     def total(xs):
         e = xs[0]
         for x in xs[1:]:
@@ -118,26 +150,8 @@ def build_page(kind: int, sizes: Tuple[int, int, int], out_words: int, after_roo
     leaf_in, node_in = code(C_LEAF_IN), code(C_NODE_IN)
     # 1. rounds: P2-JOIN's constraints on both permutations; the capacity cells are zero on every input row
     start = len(b.steps)
-    diag = [b.const(d) for d in DIAG]
-    cube = lambda x: b.mul(b.mul(x, x), x)
-    cap = []
-    for s0, q0 in ((D_SO, D_QO), (D_SN, D_QN)):
-        S = lambda j, back=0, s0=s0: dat(s0 + j, back)
-        Q = lambda j, back=0, q0=q0: dat(q0 + j, back)
-        u = [b.add(S(j), code(C_RC + j)) for j in range(T)]
-        chain = gated(chain, code(C_FULLR), [b.sub(Q(j), cube(u[j])) for j in range(T)])
-        chain = gated(chain, code(C_PARTR), [b.sub(Q(0), cube(u[0]))])
-        prev = [S(j, 1) for j in range(T)]
-        chain = gated(chain, code(C_LIN), [b.sub(S(k), e) for k, e in enumerate(lin_m_ext(prev))])
-        x7 = [b.mul(b.mul(Q(j, 1), Q(j, 1)), b.add(S(j, 1), code(C_RC + j, 1))) for j in range(T)]
-        chain = gated(chain, code(C_LF), [b.sub(S(k), e) for k, e in enumerate(lin_m_ext(x7))])
-        tot = x7[0]
-        for j in range(1, T):
-            tot = b.add(tot, prev[j])
-        chain = gated(chain, code(C_LP), [b.sub(S(0), b.add(tot, b.mul(diag[0], x7[0])))]
-                      + [b.sub(S(j), b.add(tot, b.mul(diag[j], prev[j]))) for j in range(1, T)])
-        cap += [S(16 + i) for i in range(8)]
-    chain = gated(chain, b.add(leaf_in, node_in), cap)
+    chain = emit_rounds(b, chain, gated, code, dat, cst, ((D_SO, D_QO), (D_SN, D_QN)), (C_LIN, C_FULLR, C_PARTR, C_LF, C_LP, C_RC),
+                        lambda: b.add(leaf_in, node_in))
     family("rounds", start)
 
     So = lambda j, back=0: dat(D_SO + j, back)

@@ -22,5 +22,8 @@ static __device__ void pj_m_ext(uint32_t (&c)[PJ_T]) {
 
 // circuit.hip: the SHIPPED round constants and diagonal as Montgomery words on the device, rc[24 * 29] then diag[24]: the `tab` of both generators
 const char* p2_rows_tables(zkh_ctx* ctx, Tmp& tab);
+// page_circuit.hip: k_page_tail over the rows [first_row, n) of the `wd` columns of a data group: zero while active, blinding noise
+// after.  What the generators of P2-PAGE and of P2-TREE (page_tree.hip) share for the rows past their last block.
+const char* page_tail_rows(zkh_ctx* ctx, zkh_buf* data, uint32_t wd, size_t n, uint32_t A, uint32_t first_row, const NoiseKey& nk);
 
 }  // namespace zkh

@@ -418,6 +418,12 @@ const char* page_code(const char* who, const PageShape& sh, zkh_ctx* ctx, const 
 
 }  // namespace
 
+// p2_rows.h: the tail kernel for another generator's data group (page_tree.hip)
+const char* zkh::page_tail_rows(zkh_ctx* ctx, zkh_buf* data, uint32_t wd, size_t n, uint32_t A, uint32_t first_row, const NoiseKey& nk) {
+    k_page_tail<<<dim3((unsigned)((n - first_row + 255) / 256), wd), 256, 0, ctx->stream>>>(data->ptr(), (uint32_t)n, A, first_row, nk);
+    return last_launch_error("page_tail");
+}
+
 extern "C" const char* zkh_page_circuit_code(zkh_ctx* ctx, const zkh_circuit* c, size_t po2, size_t zk_cycles, size_t image_words, zkh_buf* code) {
     return page_code("page_circuit_code", PAGE, ctx, c, po2, zk_cycles, image_words, code);
 }

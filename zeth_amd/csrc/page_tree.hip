@@ -1,0 +1,458 @@
+// page_tree.hip — the witness of P2-TREE (zeth_amd/circuits/p2_tree.py; include/zkhal.h "P2-TREE"; DESIGN.md §2 ARGUMENTS): a page-out
+// of the committed memory image sealed by its DIRTY NODES.  B = A / 31 block slots of P2-JOIN's 31 rows, the old and the new
+// permutation side by side; a block computes one node of the tree, its id is the node's heap index (image_tree.h), and parents read
+// their children over the circuit's bus, wherever they lie in the trace.
+//
+// SOURCES BY ADDRESS ALONE (the proof: DESIGN.md, next to THE TWO-TREE SHORTCUT).  A part replaces the updates [first, first + count) of
+// the table; a_f and a_l are its first and last address.  Every part reads the two trees of the WHOLE page-out.  Old side: what the
+// updates [0, first) left; new side: what [0, first + count) left.  The table increases, so a memory word x is `nodes_after`'s on the
+// old side when x < a_f (new side: x <= a_l), else `nodes_before`'s; nodes are aligned intervals, so a child node that does not hold
+// a_f (a_l) lies wholly on one side of it and is a node of one of the two trees as it stands: `nodes_after` below, `nodes_before`
+// above.  The one child per layer that holds a_f (a_l) is neither: it comes from the EDGE CHAIN, a_f's old path (a_l's new path) walked
+// as h bare hash_pairs by k_tree_edges.  Every block is then independent of every other.  An empty part (the table has no row) is the
+// root block over the tree as it stands.
+//
+// KERNELS.  k_tree_check: ONE workgroup; k_page_check's refusals over the whole table, a part that splits a pair of leaves, the part's
+// node and pair counts (LDS sums, no atomics).  Every other kernel returns at once when the record holds a refusal, so no address at
+// or past W ever indexes `nodes_*` and no slot past B is written.  k_tree_edges: one wave, lane 0 the old chain, lane 1 the new one.
+// k_tree_place: ONE workgroup, one lane per update, 256 at a time: the slot list (p2_tree.py slot order) by two block scans with a
+// carry.  k_tree_blocks: one lane per (slot, side), the literal round loop of k_p2join_blocks.  k_tree_book: one lane per (row,
+// bookkeeping column).  The tail rows are page_circuit.hip's (page_tail_rows).  One writer per cell (of the record and the slot list
+// too), one read-back of the record at the end.
+#include "circuit.h"
+#include "image_tree.h"
+#include "p2_rows.h"
+#include "scan.h"
+
+using namespace zkh;
+
+namespace {
+
+constexpr uint32_t PT_KIND = 7, PT_WC = 41, PT_WD = 106, PT_WA = 24, PT_OUT = 18, PT_MIN_H = 2, PT_MAX_H = 27, PT_GAP_BITS = 29;
+// code columns (p2_tree.py C_*)
+enum : uint32_t { TC_LIN = 3, TC_FULLR, TC_PARTR, TC_LF, TC_LP, TC_IN_ROW, TC_OUT_ROW, TC_BLOCK_FIRST, TC_CARRY, TC_LAST_TOP, TC_GSEL, TC_GPOW, TC_GEND, TC_RC, TC_LAST = 40 };
+// data columns (p2_tree.py D_*)
+enum : uint32_t { TD_SO = 0, TD_QO = 24, TD_SN = 48, TD_QN = 72, TD_ID = 96, TD_IDL, TD_IDR, TD_LEAF, TD_UP, TD_DL, TD_DR, TD_LO, TD_GBIT, TD_GACC };
+// the record: k_page_check's refusal (row, its address, the one before), the row at which the part splits a pair of leaves, the part's
+// nodes (saturated) and pairs, lo and hi as the trace holds them, whether anything is refused, both roots, both edge chains (h digests
+// each: step t's is the node of layer t + 1)
+enum : uint32_t { TR_ROW = 0, TR_A, TR_BEFORE, TR_SPLIT, TR_NODES, TR_PAIRS, TR_LO, TR_HI, TR_REFUSED, TR_ROOTS = 16, TR_EDGES = 32, TR_WORDS = TR_EDGES + 16 * PT_MAX_H };
+constexpr uint32_t NONE = 0xffffffffu;
+constexpr uint32_t PT_THREADS = 256;
+
+__device__ __forceinline__ uint32_t encode(uint32_t x) { return mul_mod(R2, x); }       // x < P
+__device__ __forceinline__ uint32_t bit_length(uint32_t x) { return 32u - (uint32_t)__clz((int)x); }   // __clz(0) = 32
+// the nodes update i of the part starts: all h of its path when it is the part's first, else those below the fork from the update before
+__device__ __forceinline__ uint32_t started(const uint32_t* __restrict__ table, uint32_t first, uint32_t i, uint32_t h) {
+    if (i == 0) return h;
+    return bit_length((table[3 * (size_t)(first + i)] >> 4) ^ (table[3 * (size_t)(first + i - 1)] >> 4));
+}
+
+// grid (ceil(n / 256), 41): a function of (po2, zk_cycles) alone
+__global__ void k_tree_code(uint32_t* code, uint32_t n, uint32_t A, uint32_t B, const uint32_t* __restrict__ tab) {
+    const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x, col = blockIdx.y;
+    if (r >= n) return;
+    uint32_t v = 0;
+    const bool in_blocks = r < PJ_BLOCK * B;
+    const uint32_t k = r % PJ_BLOCK, slot = r / PJ_BLOCK;
+    const bool round_row = in_blocks && k >= 1 && k <= PJ_ROUNDS;
+    const bool full = round_row && pj_is_full(k - 1), part = round_row && !pj_is_full(k - 1);
+    switch (col) {
+    case 0: v = r < A ? R1 : 0; break;
+    case 1: v = r == 0 ? R1 : 0; break;
+    case 2: v = (r > 0 && r < A) ? R1 : 0; break;
+    case TC_LIN: v = (in_blocks && k == 1) ? R1 : 0; break;
+    case TC_FULLR: v = full ? R1 : 0; break;
+    case TC_PARTR: v = part ? R1 : 0; break;
+    case TC_LF: v = (in_blocks && k >= 2 && pj_is_full(k - 2)) ? R1 : 0; break;
+    case TC_LP: v = (in_blocks && k >= 2 && !pj_is_full(k - 2)) ? R1 : 0; break;
+    case TC_IN_ROW: v = (in_blocks && k == 0) ? R1 : 0; break;
+    case TC_OUT_ROW: v = (in_blocks && k == PJ_BLOCK - 1) ? R1 : 0; break;
+    case TC_BLOCK_FIRST: v = (in_blocks && k == 0 && slot > 0) ? R1 : 0; break;
+    case TC_CARRY: v = (in_blocks && k > 0) ? R1 : 0; break;
+    case TC_LAST_TOP: v = (in_blocks && k == PJ_BLOCK - 1 && slot == B - 1) ? R1 : 0; break;
+    case TC_GSEL: v = round_row ? R1 : 0; break;                       // rows 1 .. 29: the 29 gap bits
+    case TC_GPOW: v = round_row ? encode(1u << (k - 1)) : 0; break;
+    case TC_GEND: v = (round_row && k == PT_GAP_BITS) ? R1 : 0; break;
+    case TC_LAST: v = r == A - 1 ? R1 : 0; break;
+    default: if (full || (part && col == TC_RC)) v = tab[(k - 1) * PJ_T + (col - TC_RC)];
+    }
+    code[(size_t)col * n + r] = v;
+}
+
+// ONE workgroup over the table's D rows (stride 3, the address first): the WHOLE table, whichever part is laid out, then the part
+// [first, first + count) (inside the table: the host has checked it)
+__global__ __launch_bounds__(PT_THREADS) void k_tree_check(const uint32_t* __restrict__ table, uint32_t D, uint32_t W, uint32_t h, uint32_t B, uint32_t first,
+                                                           uint32_t count, uint32_t* __restrict__ rec) {
+    __shared__ uint32_t low[PT_THREADS], pairs[PT_THREADS];
+    __shared__ unsigned long long nodes[PT_THREADS];
+    const uint32_t t = threadIdx.x;
+    uint32_t bad = NONE;
+    for (uint32_t i = t; i < D && bad == NONE; i += PT_THREADS) {
+        const uint32_t a = table[3 * (size_t)i];
+        if (a >= W || (i && table[3 * (size_t)(i - 1)] >= a)) bad = i;
+    }
+    unsigned long long sum = 0;
+    uint32_t fresh = 0;
+    for (uint32_t i = t; i < count; i += PT_THREADS) {
+        const uint32_t c = started(table, first, i, h);
+        sum += c;
+        fresh += c != 0;
+    }
+    low[t] = bad; nodes[t] = sum; pairs[t] = fresh;
+    __syncthreads();
+    for (uint32_t s = PT_THREADS / 2; s; s >>= 1) {
+        if (t < s) {
+            low[t] = low[t] < low[t + s] ? low[t] : low[t + s];
+            nodes[t] += nodes[t + s];
+            pairs[t] += pairs[t + s];
+        }
+        __syncthreads();
+    }
+    if (t == 0) {
+        const uint32_t i = low[0], end = first + count;
+        uint32_t split = NONE;
+        if (end && end < D && table[3 * (size_t)(end - 1)] >> 4 == table[3 * (size_t)end] >> 4) split = end;
+        if (first && first < D && table[3 * (size_t)(first - 1)] >> 4 == table[3 * (size_t)first] >> 4) split = first;
+        const unsigned long long total = count ? nodes[0] : 1;          // an empty part is the root block alone
+        rec[TR_ROW] = i;
+        rec[TR_A] = i != NONE ? table[3 * (size_t)i] : 0;
+        rec[TR_BEFORE] = i != NONE && i ? table[3 * (size_t)(i - 1)] : 0;
+        rec[TR_SPLIT] = split;
+        rec[TR_NODES] = total > 0xfffffffeull ? 0xfffffffeu : (uint32_t)total;
+        rec[TR_PAIRS] = pairs[0];
+        rec[TR_REFUSED] = i != NONE || split != NONE || total > B;
+    }
+}
+
+// ONE wave.  Lane 0: a_f's OLD path, lane 1: a_l's NEW path, each h bare hash_pairs (k_page_root's lane body, page_circuit.hip) whose
+// digests go into the record; the tops are the part's two roots.  An empty part: both roots are digest 1 of the tree as it stands.
+__global__ __launch_bounds__(64) void k_tree_edges(uint32_t h, const uint32_t* __restrict__ table, uint32_t first, uint32_t count, const uint32_t* __restrict__ nodes_before,
+                                                   const uint32_t* __restrict__ nodes_after, size_t L, uint32_t* rec, const uint32_t* __restrict__ rc,
+                                                   const uint32_t* __restrict__ diag) {
+    const uint32_t lane = threadIdx.x;
+    if (rec[TR_REFUSED]) return;
+    if (count == 0) {
+        if (lane < 16) rec[TR_ROOTS + lane] = nodes_after[8 + (lane & 7)];
+        return;
+    }
+    if (lane >= 2) return;
+    const uint32_t side = lane;
+    const uint32_t a = table[3 * (size_t)(side ? first + count - 1 : first)];      // < W <= 8 L: the record holds no refusal
+    uint32_t s[CELLS];
+    for (uint32_t t = 0; t < h; t++) {
+        if (t == 0) {
+            const uint32_t x0 = a & ~15u;
+#pragma unroll
+            for (uint32_t j = 0; j < 16; j++) {
+                const bool done = side ? x0 + j <= a : x0 + j < a;
+                s[j] = (done ? nodes_after : nodes_before)[8 * L + x0 + j];
+            }
+        } else {
+            const uint32_t x = a >> (3 + t);
+            const bool right = x & 1;
+            const uint32_t* sib = (right ? nodes_after : nodes_before) + 8 * ((L >> t) + (x ^ 1));
+#pragma unroll
+            for (uint32_t j = 0; j < 8; j++) {
+                const uint32_t own = s[j], other = sib[j];
+                s[j] = right ? other : own;
+                s[8 + j] = right ? own : other;
+            }
+        }
+#pragma unroll
+        for (int j = RATE; j < CELLS; j++) s[j] = 0;
+        poseidon2_mix_raw<0, OUT, RATE>(s, rc, diag);
+#pragma unroll
+        for (int j = 0; j < OUT; j++) s[j] = p2_finish(s[j]);
+#pragma unroll
+        for (uint32_t j = 0; j < 8; j++) rec[TR_EDGES + 8 * (side * h + t) + j] = s[j];
+    }
+#pragma unroll
+    for (uint32_t j = 0; j < 8; j++) rec[TR_ROOTS + 8 * side + j] = s[j];
+}
+
+// ONE workgroup, one lane per update of the part, 256 updates at a time.  An update that opens a new pair of leaves q takes the next
+// pair slot (a scan of the "new pair" flags) and writes the ids of the nodes it starts above the pair, bottom up, behind the pair slots
+// (a scan of their numbers); the root is not among them: it is slot B - 1.  The record's node count has passed the check, so every
+// slot written is below B - 1.  The dead slots and the root slot are written by the lanes' first loop: one writer per slot.
+__global__ __launch_bounds__(PT_THREADS) void k_tree_place(uint32_t* __restrict__ ids, uint32_t B, uint32_t h, const uint32_t* __restrict__ table, uint32_t first,
+                                                           uint32_t count, const uint32_t* __restrict__ rec) {
+    __shared__ uint32_t buf[2][PT_THREADS];
+    __shared__ uint32_t tot[2];
+    const uint32_t t = threadIdx.x;
+    if (rec[TR_REFUSED]) return;
+    const uint32_t live = rec[TR_NODES] - 1, m = rec[TR_PAIRS], half = 1u << (h - 1);       // live slots but the root: [0, live)
+    for (uint32_t s = live + t; s < B; s += PT_THREADS) ids[s] = s == B - 1 ? 1u : 0u;
+    uint32_t pair_base = 0, over_base = m;
+    for (uint32_t i0 = 0; i0 < count; i0 += PT_THREADS) {
+        const uint32_t i = i0 + t;
+        const uint32_t c = i < count ? started(table, first, i, h) : 0;
+        const uint32_t above = c ? (c < h - 1 ? c : h - 1) - 1 : 0;                        // t = 1 .. min(c, h - 1) - 1
+        const uint32_t p_incl = block_scan<PT_THREADS>(c ? 1u : 0u, buf, AddWrap());
+        const uint32_t o_incl = block_scan<PT_THREADS>(above, buf, AddWrap());
+        if (t == PT_THREADS - 1) { tot[0] = p_incl; tot[1] = o_incl; }
+        __syncthreads();
+        if (c) {
+            const uint32_t id = half + (table[3 * (size_t)(first + i)] >> 4);
+            ids[pair_base + p_incl - 1] = id;
+            const uint32_t at = over_base + o_incl - above;
+            for (uint32_t k = 1; k <= above; k++) ids[at + k - 1] = id >> k;
+        }
+        pair_base += tot[0];
+        over_base += tot[1];
+        __syncthreads();
+    }
+}
+
+// One lane per (slot, side): side 0 the old permutation, 1 the new one.  The 16 input words by the address rule at the top of this
+// file, then the round loop of k_p2join_blocks (circuit.hip) on this side's columns.  A dead slot (id 0) hashes zeros.
+__global__ __launch_bounds__(64) void k_tree_blocks(uint32_t* __restrict__ data, uint32_t n, uint32_t h, uint32_t B, const uint32_t* __restrict__ ids,
+                                                    const uint32_t* __restrict__ table, uint32_t first, uint32_t count, const uint32_t* __restrict__ nodes_before,
+                                                    const uint32_t* __restrict__ nodes_after, size_t L, const uint32_t* __restrict__ rec, const uint32_t* __restrict__ tab) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= 2 * B || rec[TR_REFUSED]) return;
+    const uint32_t slot = i >> 1, side = i & 1, id = ids[slot];
+    const uint32_t s_col = side ? TD_SN : TD_SO, q_col = side ? TD_QN : TD_QO;
+    const uint32_t* diag = tab + PJ_T * PJ_ROUNDS;
+    uint32_t s[PJ_T];
+    for (uint32_t j = 0; j < PJ_T; j++) s[j] = 0;
+    if (id && count == 0) {                                                // the root block over the tree as it stands
+        for (uint32_t j = 0; j < 16; j++) s[j] = nodes_after[16 * (size_t)id + j];
+    } else if (id) {
+        // the part's edge: its first address on the old side (words below it are written), its last on the new side (words up to it are)
+        const uint32_t a = table[3 * (size_t)(side ? first + count - 1 : first)];
+        if (id >= L / 2) {                                                 // a pair block: 16 memory words
+            const uint32_t x0 = (id - (uint32_t)(L / 2)) << 4;
+            for (uint32_t j = 0; j < 16; j++) {
+                const uint32_t x = x0 + j;
+                const bool done = side ? x <= a : x < a;
+                s[j] = (done ? nodes_after : nodes_before)[8 * L + x];
+            }
+        } else {                                                           // children 2 id, 2 id + 1: nodes of layer t >= 1
+            const uint32_t t = h - bit_length(id);
+            const uint32_t on_edge = a >> (3 + t);                         // the node of layer t that holds the edge address
+            for (uint32_t c = 0; c < 2; c++) {
+                const size_t child = 2 * (size_t)id + c;
+                const uint32_t x = (uint32_t)(child - (L >> t));
+                const uint32_t* src = x == on_edge ? rec + TR_EDGES + 8 * (side * h + t - 1) : (x < on_edge ? nodes_after : nodes_before) + 8 * child;
+                for (uint32_t j = 0; j < 8; j++) s[8 * c + j] = src[j];
+            }
+        }
+    }
+    const size_t r0 = (size_t)PJ_BLOCK * slot;
+    for (uint32_t j = 0; j < PJ_T; j++) { data[(size_t)(s_col + j) * n + r0] = s[j]; data[(size_t)(q_col + j) * n + r0] = 0; }
+    pj_m_ext(s);
+    for (uint32_t rnd = 0; rnd < PJ_ROUNDS; rnd++) {
+        const size_t r = r0 + 1 + rnd;
+        for (uint32_t j = 0; j < PJ_T; j++) data[(size_t)(s_col + j) * n + r] = s[j];
+        if (pj_is_full(rnd)) {
+            for (uint32_t j = 0; j < PJ_T; j++) {
+                const uint32_t u = add_mod(s[j], tab[rnd * PJ_T + j]);
+                const uint32_t q = mul_mod(mul_mod(u, u), u);
+                data[(size_t)(q_col + j) * n + r] = q;
+                s[j] = mul_mod(mul_mod(q, q), u);
+            }
+            pj_m_ext(s);
+        } else {
+            const uint32_t u = add_mod(s[0], tab[rnd * PJ_T]);
+            const uint32_t q = mul_mod(mul_mod(u, u), u);
+            data[(size_t)q_col * n + r] = q;
+            for (uint32_t j = 1; j < PJ_T; j++) data[(size_t)(q_col + j) * n + r] = 0;
+            const uint32_t x7 = mul_mod(mul_mod(q, q), u);
+            uint32_t tot = x7;
+            for (uint32_t j = 1; j < PJ_T; j++) tot = add_mod(tot, s[j]);
+            s[0] = add_mod(tot, mul_mod(diag[0], x7));
+            for (uint32_t j = 1; j < PJ_T; j++) s[j] = add_mod(tot, mul_mod(diag[j], s[j]));
+        }
+    }
+    const size_t rl = r0 + PJ_BLOCK - 1;
+    for (uint32_t j = 0; j < PJ_T; j++) { data[(size_t)(s_col + j) * n + rl] = s[j]; data[(size_t)(q_col + j) * n + rl] = 0; }
+}
+
+// whether an address of the part lies in [x, y): a binary search of its `count` increasing addresses
+__device__ __forceinline__ bool part_touches(const uint32_t* __restrict__ table, uint32_t first, uint32_t count, uint32_t x, uint32_t y) {
+    uint32_t lo = 0, hi = count;
+    while (lo < hi) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        if (table[3 * (size_t)(first + mid)] < x) lo = mid + 1; else hi = mid;
+    }
+    return lo < count && table[3 * (size_t)(first + lo)] < y;
+}
+
+// grid (ceil(31 B / 256), 10): the bookkeeping columns id .. gacc of the rows of the blocks, stores coalesced along the rows.  The lane
+// of row 0 and `lo` writes out[16] into the record, the lane of the root block's last row and `lo` writes out[17] = hi (the root block
+// is no pair block, and lo behind the pair blocks is one more than the last of them).  `rec` is read and written here (distinct cells).
+__global__ __launch_bounds__(PT_THREADS) void k_tree_book(uint32_t* __restrict__ data, uint32_t n, uint32_t h, uint32_t B, const uint32_t* __restrict__ ids,
+                                                          const uint32_t* __restrict__ table, uint32_t first, uint32_t count, uint32_t* rec) {
+    const uint32_t r = blockIdx.x * PT_THREADS + threadIdx.x, col = TD_ID + blockIdx.y, rows = PJ_BLOCK * B;
+    if (r >= rows || rec[TR_REFUSED]) return;
+    const uint32_t k = r % PJ_BLOCK, slot = r / PJ_BLOCK, id = ids[slot], half = 1u << (h - 1), m = rec[TR_PAIRS];
+    const bool leaf = id >= half;
+    uint32_t v = 0;
+    if (col == TD_ID) v = encode(id);
+    else if (col == TD_IDL) v = encode(2 * id);
+    else if (col == TD_IDR) v = encode(2 * id + 1);
+    else if (col == TD_LEAF) v = leaf ? R1 : 0;
+    else if (col == TD_UP) v = id > 1 ? R1 : 0;
+    else if (col == TD_DL || col == TD_DR) {
+        if (id && !leaf && count) {
+            const uint32_t t = h - bit_length(id);                         // the children are nodes of layer t >= 1: 2^(3 + t) words each
+            const uint32_t x = (2 * id + (col == TD_DR)) - (1u << (h - t));
+            v = part_touches(table, first, count, x << (3 + t), (x + 1) << (3 + t)) ? R1 : 0;
+        }
+    } else {
+        const uint32_t base = first ? half + (table[3 * (size_t)(first - 1)] >> 4) + 1 : half;
+        const uint32_t lo = leaf ? (slot ? ids[slot - 1] + 1 : base) : (m ? ids[m - 1] + 1 : base);
+        const uint32_t g = leaf ? id - lo : 0;
+        if (col == TD_LO) {
+            v = encode(lo);
+            if (r == 0) rec[TR_LO] = v;
+            if (r == rows - 1) rec[TR_HI] = v;
+        } else if (col == TD_GBIT) v = (k >= 1 && k <= PT_GAP_BITS && ((g >> (k - 1)) & 1)) ? R1 : 0;
+        else v = k == 0 ? 0 : encode(k <= PT_GAP_BITS ? g & ((1u << k) - 1) : g);
+    }
+    data[(size_t)col * n + r] = v;
+}
+
+inline bool tree_po2_ok(size_t po2, size_t zk_cycles) { return po2 >= 1 && po2 <= 30 && ((size_t)1 << po2) > zk_cycles + 1; }
+
+const char* tree_circuit_shape(const char* who, const zkh_circuit* c, size_t po2, size_t zk_cycles) {
+    ZKH_REQUIRE(c->kind == PT_KIND && c->group_size[GROUP_CODE] == PT_WC && c->group_size[GROUP_DATA] == PT_WD && c->group_size[GROUP_ACCUM] == PT_WA &&
+                c->global_size[GLOBAL_OUT] == PT_OUT, "%s: the circuit does not have P2-TREE's shape (kind %u, %u / %u / %u columns, %u outputs)", who, PT_KIND, PT_WC,
+                PT_WD, PT_WA, PT_OUT);
+    ZKH_REQUIRE(tree_po2_ok(po2, zk_cycles), "%s: po2 %zu out of range for %zu zk_cycles", who, po2, zk_cycles);
+    return nullptr;
+}
+
+// the image's shape -> h, B
+const char* tree_image_shape(const char* who, size_t po2, size_t zk_cycles, size_t W, uint32_t* h_out, uint32_t* B_out) {
+    ZKH_REQUIRE(W > 16, "%s: an image of %zu words has a single pair of leaves (W > 16: the root block is not a pair block)", who, W);
+    uint32_t h = 0;
+    while (((size_t)1 << h) < image_leaves(W)) h++;
+    ZKH_REQUIRE(h >= PT_MIN_H && h <= PT_MAX_H, "%s: an image of %zu words has h %u (%u .. %u: ids and gaps stay below 2^%u)", who, W, h, PT_MIN_H, PT_MAX_H, PT_GAP_BITS);
+    *h_out = h;
+    *B_out = (uint32_t)((((size_t)1 << po2) - zk_cycles) / PJ_BLOCK);
+    ZKH_REQUIRE(*B_out >= h, "%s: no room for the h %u nodes of one path in %u block slots (po2 %zu, %zu zk_cycles)", who, h, *B_out, po2, zk_cycles);
+    return nullptr;
+}
+
+}  // namespace
+
+extern "C" const char* zkh_page_tree_code(zkh_ctx* ctx, const zkh_circuit* c, size_t po2, size_t zk_cycles, zkh_buf* code) {
+    const char* who = "page_tree_code";
+    ZKH_REQUIRE(ctx && c && code, "%s: null argument", who);
+    ZKH_TRY(tree_circuit_shape(who, c, po2, zk_cycles));
+    const size_t n = (size_t)1 << po2;
+    ZKH_REQUIRE(code->len == (size_t)PT_WC * n, "%s: buffer shape mismatch", who);
+    const uint32_t A = (uint32_t)(n - zk_cycles), B = A / PJ_BLOCK;
+    Tmp tab;
+    ZKH_TRY(p2_rows_tables(ctx, tab));
+    ProfScope prof(ctx, "tree_code", 4.0 * PT_WC * n);
+    k_tree_code<<<dim3((unsigned)((n + 255) / 256), PT_WC), 256, 0, ctx->stream>>>(code->ptr(), (uint32_t)n, A, B, tab->ptr());
+    return last_launch_error("tree_code");
+}
+
+// HOST ONLY: the plan of p2_tree.parts over a host array of the table's addresses
+extern "C" const char* zkh_page_tree_plan(size_t po2, size_t zk_cycles, size_t image_words, const uint32_t* addrs, size_t D, size_t* parts, size_t parts_cap,
+                                          size_t* n_parts) {
+    const char* who = "page_tree_plan";
+    ZKH_REQUIRE((addrs || D == 0) && (parts || parts_cap == 0) && n_parts, "%s: null argument", who);
+    ZKH_REQUIRE(tree_po2_ok(po2, zk_cycles), "%s: po2 %zu out of range for %zu zk_cycles", who, po2, zk_cycles);
+    uint32_t h, B;
+    ZKH_TRY(tree_image_shape(who, po2, zk_cycles, image_words, &h, &B));
+    size_t count = 0, first = 0, nodes = 0;
+    auto emit = [&](size_t from, size_t to) {
+        if (count < parts_cap) { parts[2 * count] = from; parts[2 * count + 1] = to - from; }
+        count++;
+    };
+    bool any = false;
+    uint32_t before = 0;
+    for (size_t i = 0; i < D; i++) {
+        ZKH_REQUIRE(addrs[i] < image_words && (i == 0 || addrs[i - 1] < addrs[i]), "%s: row %zu: address %u does not follow a smaller one below %zu", who, i, addrs[i],
+                    image_words);
+        const uint32_t q = addrs[i] >> 4;
+        if (any && q == before) continue;
+        uint32_t cost = any ? 32u - (uint32_t)__builtin_clz(q ^ before) : h;
+        if (nodes + cost > B) { emit(first, i); first = i; nodes = 0; cost = h; }
+        nodes += cost;
+        before = q;
+        any = true;
+    }
+    emit(first, D);
+    *n_parts = count;
+    return nullptr;
+}
+
+extern "C" const char* zkh_page_tree_witgen(zkh_ctx* ctx, const zkh_circuit* c, size_t po2, size_t zk_cycles, const zkh_buf* code, const zkh_buf* proof,
+                                            size_t proof_words, const zkh_buf* nodes_before, const zkh_buf* nodes_after, size_t first_row, size_t count_rows,
+                                            zkh_buf* data, uint32_t out[18], const uint32_t* noise_key) {
+    const char* who = "page_tree_witgen";
+    ZKH_REQUIRE(ctx && c && code && proof && nodes_before && nodes_after && data && out, "%s: null argument", who);
+    ZKH_TRY(tree_circuit_shape(who, c, po2, zk_cycles));
+    const size_t n = (size_t)1 << po2;
+    ZKH_REQUIRE(code->len == (size_t)PT_WC * n && data->len == (size_t)PT_WD * n, "%s: buffer shape mismatch", who);
+    ZKH_REQUIRE(proof_words <= proof->len && proof_words <= 0xffffffffull, "%s: a proof of %zu words in a buffer of %zu", who, proof_words, proof->len);
+    NoiseKey nk;
+    ZKH_TRY(resolve_noise_key(noise_key, &nk));
+    bind_thread(ctx);
+    uint32_t head[PROOF_HEAD_MAX] = {0};
+    ZKH_TRY(zkh_read(ctx, proof, head, 0, proof_words < PROOF_HEAD_MAX ? proof_words : PROOF_HEAD_MAX));
+    ZKH_TRY(image_proof_header(who, head, proof_words));
+    const uint32_t W = head[1], D = head[2];
+    uint32_t h, B;
+    ZKH_TRY(tree_image_shape(who, po2, zk_cycles, W, &h, &B));
+    const size_t L = image_leaves(W);
+    ZKH_REQUIRE(nodes_before->len == 16 * L && nodes_after->len == 16 * L, "%s: nodes of %zu and %zu words; an image of %u words has a tree of %zu (zkh_image_tree_words)",
+                who, nodes_before->len, nodes_after->len, W, 16 * L);
+    ZKH_REQUIRE(first_row <= D && count_rows <= D - first_row && (count_rows || D == 0), "%s: the part [%zu, %zu) of a table of %u rows (an empty part only of an empty table)",
+                who, first_row, first_row + count_rows, D);
+    const uint32_t first = (uint32_t)first_row, count = (uint32_t)count_rows;     // 3 D words fit the proof: D < 2^31
+    const uint32_t A = (uint32_t)(n - zk_cycles), rows = PJ_BLOCK * B;
+    const uint32_t* table = proof->ptr() + 5 + h;                      // 3 D words inside the proof: its length is what the header describes
+    Tmp tab, rec, ids;
+    ZKH_TRY(p2_rows_tables(ctx, tab));
+    ZKH_TRY(new_buf(ctx, TR_WORDS, false, rec.out()));
+    ZKH_TRY(new_buf(ctx, B, false, ids.out()));
+    {
+        ProfScope prof(ctx, "tree_check", 12.0 * D + 12.0 * count);
+        k_tree_check<<<1, PT_THREADS, 0, ctx->stream>>>(table, D, W, h, B, first, count, rec->ptr());
+        ZKH_TRY(last_launch_error("tree_check"));
+    }
+    {
+        ProfScope prof(ctx, "tree_edges", 4.0 * 32 * h);
+        k_tree_edges<<<1, 64, 0, ctx->stream>>>(h, table, first, count, nodes_before->ptr(), nodes_after->ptr(), L, rec->ptr(), ctx->tab.rc, ctx->tab.diag);
+        ZKH_TRY(last_launch_error("tree_edges"));
+    }
+    {
+        ProfScope prof(ctx, "tree_place", 12.0 * count + 4.0 * B);
+        k_tree_place<<<1, PT_THREADS, 0, ctx->stream>>>(ids->ptr(), B, h, table, first, count, rec->ptr());
+        ZKH_TRY(last_launch_error("tree_place"));
+    }
+    {
+        ProfScope prof(ctx, "tree_blocks", 4.0 * 96 * rows);
+        k_tree_blocks<<<(2 * B + 63) / 64, 64, 0, ctx->stream>>>(data->ptr(), (uint32_t)n, h, B, ids->ptr(), table, first, count, nodes_before->ptr(),
+                                                                 nodes_after->ptr(), L, rec->ptr(), tab->ptr());
+        ZKH_TRY(last_launch_error("tree_blocks"));
+    }
+    {
+        ProfScope prof(ctx, "tree_book", 4.0 * (PT_WD - TD_ID) * rows + 4.0 * PT_WD * (n - rows));
+        k_tree_book<<<dim3((rows + PT_THREADS - 1) / PT_THREADS, PT_WD - TD_ID), PT_THREADS, 0, ctx->stream>>>(data->ptr(), (uint32_t)n, h, B, ids->ptr(), table, first,
+                                                                                                               count, rec->ptr());
+        ZKH_TRY(last_launch_error("tree_book"));
+        if (rows < n) ZKH_TRY(page_tail_rows(ctx, data, PT_WD, n, A, rows, nk));
+    }
+    uint32_t r[TR_ROOTS + 16];
+    ZKH_TRY(zkh_read(ctx, rec, r, 0, TR_ROOTS + 16));
+    if (r[TR_ROW] != NONE) {
+        if (r[TR_A] >= W) return make_err("%s: row %u: address %u outside the image of %u words", who, r[TR_ROW], r[TR_A], W);
+        return make_err("%s: row %u: address %u does not follow a smaller one (row %u: address %u)", who, r[TR_ROW], r[TR_A], r[TR_ROW] - 1, r[TR_BEFORE]);
+    }
+    ZKH_REQUIRE(r[TR_SPLIT] == NONE, "%s: the part [%u, %u) splits a pair of leaves: rows %u and %u write the same 16 words (zkh_page_tree_plan)", who, first,
+                first + count, r[TR_SPLIT] - 1, r[TR_SPLIT]);
+    ZKH_REQUIRE(r[TR_NODES] <= B, "%s: the part [%u, %u) has %u%s dirty nodes, but po2 %zu leaves %u block slots (zkh_page_tree_plan)", who, first, first + count,
+                r[TR_NODES], r[TR_NODES] == 0xfffffffeu ? " or more" : "", po2, B);
+    memcpy(out, r + TR_ROOTS, 4 * 16);
+    out[16] = r[TR_LO];
+    out[17] = r[TR_HI];
+    return nullptr;
+}

@@ -197,6 +197,9 @@ ABI = {
     "zkh_page_circuit_slots": (_sz, [_sz, _sz, _sz]),
     "zkh_page_ordered_code": (_err, [_vp, _vp, _sz, _sz, _sz, _vp]),
     "zkh_page_ordered_witgen": (_err, [_vp, _vp, _sz, _sz, _vp, _vp, _sz, _vp, _vp, _sz, _vp, _u32p, _u32p]),
+    "zkh_page_tree_code": (_err, [_vp, _vp, _sz, _sz, _vp]),
+    "zkh_page_tree_plan": (_err, [_sz, _sz, _sz, _u32p, _sz, C.POINTER(C.c_size_t), _sz, C.POINTER(C.c_size_t)]),
+    "zkh_page_tree_witgen": (_err, [_vp, _vp, _sz, _sz, _vp, _vp, _sz, _vp, _vp, _sz, _sz, _vp, _u32p, _u32p]),
     "zkh_circuit_derived_data_columns": (_err, [_vp, _u32p, _sz, C.POINTER(_sz)]),
     "zkh_upload_data_trace": (_err, [_vp, _vp, _sz, _sz, _vp, _u32p, _i]),
     "zkh_ctx_h2d_bytes": (_sz, [_vp]),
@@ -616,6 +619,19 @@ def placement_slot(device: int, devices: Sequence[int]):
     return same.index(device), len(same)
 
 
+def page_tree_plan(po2: int, zk_cycles: int, image_words: int, addrs) -> list:
+    """the parts [(first, count), ...] of a page-out with the addresses `addrs` (host words, strictly increasing) as P2-TREE traces
+    (zkh_page_tree_plan: host only, no GPU; the Python twin is circuits/p2_tree.py `parts`).  Raises HalError on W <= 16, on B < h and
+    on addresses that do not increase below `image_words`"""
+    load_library()
+    addrs = np.ascontiguousarray(addrs, dtype=np.uint32).reshape(-1)
+    cap = max(1, addrs.size)
+    parts = (C.c_size_t * (2 * cap))()
+    n = C.c_size_t()
+    _check(_lib.zkh_page_tree_plan(po2, zk_cycles, image_words, _ptr(addrs), addrs.size, parts, cap, C.byref(n)))
+    return [(int(parts[2 * p]), int(parts[2 * p + 1])) for p in range(n.value)]
+
+
 class HipHal:
     """`impl Hal for HipHal` — one MI355X, one HIP stream, one driving thread."""
 
@@ -1004,6 +1020,31 @@ class HipHal:
         _k, kp = _key_ptr(noise_seed)
         _check(_lib.zkh_page_ordered_witgen(self.ctx, circuit.h, po2, zk_cycles, code.h, proof.h, proof_words, nodes_before.h, nodes_after.h, first,
                                             data.h, _ptr(out), kp))
+        return out
+
+    def page_tree_code(self, circuit: Circuit, po2: int, zk_cycles: int, code: Optional[Buffer] = None) -> Buffer:
+        """the code group of P2-TREE (circuits/p2_tree.py) for (po2, zk_cycles): it does not depend on the image (zkh_page_tree_code; the
+        host twin: p2_tree.reference_tree_code).  code: a Buffer of 41 x 2^po2 words to write (default: a new one)"""
+        if code is None:
+            code = self.alloc_elem("code", int(circuit.desc[4]) << po2)
+        _check(_lib.zkh_page_tree_code(self.ctx, circuit.h, po2, zk_cycles, code.h))
+        return code
+
+    def page_tree_plan(self, po2: int, zk_cycles: int, image_words: int, addrs) -> list:
+        """the module's page_tree_plan (host only: it needs no context)"""
+        return page_tree_plan(po2, zk_cycles, image_words, addrs)
+
+    def page_tree_witgen(self, circuit: Circuit, po2: int, zk_cycles: int, code: Buffer, proof: Buffer, proof_words: int, nodes_before: Buffer,
+                         nodes_after: Buffer, first: int, count: int, data: Buffer, noise_seed: int) -> np.ndarray:
+        """the data group of P2-TREE for the part [first, first + count) of the page-out a ZKU1 proof describes (zkh_page_tree_witgen; the
+        host twin: p2_tree.reference_tree_part) -> the out globals, root_before ‖ root_after ‖ lo ‖ hi (18 words: lo and hi bound the
+        heap ids of the part's pair blocks, p2_tree.decode).  The other operands are page_ordered_witgen's, `data` of 106 x 2^po2
+        words, both trees the whole page-out's; the part is one of page_tree_plan's.  Raises HalError with one message per cause
+        (include/zkhal.h "P2-TREE"); `data` is unspecified then"""
+        out = np.zeros(2 * DIGEST_WORDS + 2, dtype=np.uint32)
+        _k, kp = _key_ptr(noise_seed)
+        _check(_lib.zkh_page_tree_witgen(self.ctx, circuit.h, po2, zk_cycles, code.h, proof.h, proof_words, nodes_before.h, nodes_after.h, first, count,
+                                         data.h, _ptr(out), kp))
         return out
 
     def derive_multiplicities(self, circuit: Circuit, po2: int, zk_cycles: int, code: Buffer, data: Buffer) -> None:

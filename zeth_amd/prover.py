@@ -445,6 +445,45 @@ class SegmentProver:
             receipts.append(receipt)
         return receipts
 
+    def seal_page_out_tree(self, segs, proof, proof_words: int, nodes_before, nodes_after, check: bool = False) -> list:
+        """Seal a page-out of any size with P2-TREE (this prover's circuit: circuits/p2_tree.py, built with arguments=p2_tree.arguments())
+        as a chain of parts: one block per DIRTY NODE of the tree instead of one path per word.  Part p's receipt's output is
+        root_before ‖ root_after ‖ lo ‖ hi of its run of pairs of leaves (zkh_page_tree_witgen), so part p + 1 opens the root and
+        starts at the `hi` part p left (`verify_page_tree_chain`).  The plan is zkh_page_tree_plan's over the table's addresses, read
+        back once (D words).  The accum group is the circuit's bus (args_accumulate): a table that does not match the trees is refused
+        there, and check=True names the key.  The other operands are seal_page_out_parts'; one code group, one control root (it does
+        not depend on the image's size), one data buffer.  -> the receipts, in the order of the parts."""
+        segs = list(segs)
+        if not segs:
+            raise _hal.HalError("seal_page_out_tree: no segment")
+        po2, zk = segs[0].po2, segs[0].zk_cycles
+        if any((s.po2, s.zk_cycles) != (po2, zk) for s in segs):
+            raise _hal.HalError("seal_page_out_tree: the parts share one code group: every segment must have the same (po2, zk_cycles)")
+        if not self.circuit.has_arguments():
+            raise _hal.HalError("seal_page_out_tree: the prover was built without P2-TREE's arguments (arguments=p2_tree.arguments())")
+        if not isinstance(proof, _hal.Buffer):
+            proof = self.hal.copy_from("image_proof", np.ascontiguousarray(proof, dtype=np.uint32).reshape(-1))
+        header = proof.slice(0, min(5, proof.size())).to_vec()
+        W, D, h = (int(header[1]), int(header[2]), int(header[4])) if header.size > 4 else (0, 0, 0)
+        if 5 + h + 3 * D > min(proof_words, proof.size()):
+            raise _hal.HalError(f"seal_page_out_tree: a proof of {proof_words} words does not hold its header and a table of {D} rows")
+        addrs = proof.slice(5 + h, 3 * D).to_vec()[::3] if D else np.zeros(0, dtype=np.uint32)
+        plan = self.hal.page_tree_plan(po2, zk, W, addrs)                      # refuses W <= 16, B < h, addresses out of order
+        if len(segs) != len(plan):
+            raise _hal.HalError(f"seal_page_out_tree: {len(segs)} segments, but a table of {D} rows takes {len(plan)} parts of "
+                                f"{((1 << po2) - zk) // 31} block slots at po2 {po2}")
+        wa, wc, wd = self.group_sizes()
+        code = self.hal.page_tree_code(self.circuit, po2, zk)
+        control_root = self.code_root(code, po2)
+        data = self.hal.alloc_elem("data", wd << po2)
+        receipts = []
+        for seg, (first, count) in zip(segs, plan):
+            out = self.hal.page_tree_witgen(self.circuit, po2, zk, code, proof, proof_words, nodes_before, nodes_after, first, count, data, seg.noise_seed)
+            receipt = self.seal_with_accum(seg, code, data, out, self.args_accumulate(seg, code, data, check=check), check=check)
+            receipt.control_root = control_root.copy()
+            receipts.append(receipt)
+        return receipts
+
     def prove_segment(self, seg: Segment) -> SegmentReceipt:
         code, data, out = self.witgen(seg)
         return self.seal(seg, code, data, out)
@@ -503,6 +542,55 @@ def verify_page_ordered_chain(receipts, control_root, root_before=None) -> Tuple
         if parts[p + 1][2] != parts[p][3]:
             raise _hal.HalError(f"verify_page_ordered_chain: part {p + 1} starts at lo {parts[p + 1][2]}, but part {p} left hi {parts[p][3]}")
     return parts[0][0], parts[-1][1], parts[-1][3]
+
+
+def link_page_tree_chain(outs, h: int, root_before=None) -> Tuple[np.ndarray, np.ndarray, int]:
+    """What verify_page_tree_chain checks of the parts' `out` words (18 each) once every seal is verified -> (root_before, root_after,
+    hi).  Every lo and hi must decode to at most 2^29; part 0 must have lo = 2^(h-1), the id of the first pair of leaves; part p + 1
+    must open the root part p left and start at the hi part p left; the last hi must be at most 2^h, so every pair block's id lies in
+    [2^(h-1), 2^h): h - 1 levels below the root; with a `root_before`, part 0 must open it.  Raises HalError, one message per cause."""
+    from .circuits import p2_tree as pt
+    who = "verify_page_tree_chain"
+    if not pt.MIN_H <= h <= pt.MAX_H:
+        raise _hal.HalError(f"{who}: h {h} ({pt.MIN_H} .. {pt.MAX_H})")
+    fmt = lambda r: " ".join(f"{int(w):08x}" for w in r)
+    parts = []
+    for p, out in enumerate(outs):
+        out = np.asarray(out, dtype=np.uint32)
+        lo, hi = pt.decode(out[pt.OUT_LO]), pt.decode(out[pt.OUT_HI])
+        for name, v in (("lo", lo), ("hi", hi)):
+            if v > 1 << pt.GAP_BITS:
+                raise _hal.HalError(f"{who}: part {p}: {name} {v} is above 2^{pt.GAP_BITS}, the bound the order check is sound for")
+        parts.append((out[:8].copy(), out[8:16].copy(), lo, hi))
+    if not parts:
+        raise _hal.HalError(f"{who}: no receipt (a page-out of no rows still has one part)")
+    if parts[0][2] != 1 << (h - 1):
+        raise _hal.HalError(f"{who}: part 0 starts at lo {parts[0][2]}, not 2^{h - 1} = {1 << (h - 1)}, the id of the first pair of leaves of a tree of height {h}")
+    if root_before is not None and not np.array_equal(parts[0][0], np.asarray(root_before, dtype=np.uint32)):
+        raise _hal.HalError(f"{who}: part 0 opens root {fmt(parts[0][0])}, not root_before {fmt(root_before)}")
+    for p in range(len(parts) - 1):
+        if not np.array_equal(parts[p + 1][0], parts[p][1]):
+            raise _hal.HalError(f"{who}: part {p + 1} opens root {fmt(parts[p + 1][0])}, but part {p} left root {fmt(parts[p][1])}")
+        if parts[p + 1][2] != parts[p][3]:
+            raise _hal.HalError(f"{who}: part {p + 1} starts at lo {parts[p + 1][2]}, but part {p} left hi {parts[p][3]}")
+    if parts[-1][3] > 1 << h:
+        raise _hal.HalError(f"{who}: the last part leaves hi {parts[-1][3]}, above 2^{h} = {1 << h}: a pair block outside a tree of height {h}")
+    return parts[0][0], parts[-1][1], parts[-1][3]
+
+
+def verify_page_tree_chain(receipts, control_root, h: int, root_before=None) -> Tuple[np.ndarray, np.ndarray, int]:
+    """Verify the chain of P2-TREE seals of one page-out (SegmentProver.seal_page_out_tree), HOST ONLY -> (root_before, root_after, hi)
+    of the whole page-out.  Every seal is verified against P2-TREE's description and `control_root` (one per (po2, zk_cycles), for
+    every image size); then the parts' outputs must link (`link_page_tree_chain`): the verifier is told h, the height of the image's
+    tree.  Raises HalError on a seal the verifier rejects, and one message per cause on a chain that does not link."""
+    from .circuits import p2_tree as pt
+    receipts = list(receipts)
+    if not receipts:
+        raise _hal.HalError("verify_page_tree_chain: no receipt (a page-out of no rows still has one part)")
+    hc = _hal.HostCircuit(pt.p2_tree_circuit())
+    for r in receipts:
+        hc.verify_segment(r.seal, control_root)
+    return link_page_tree_chain([r.seal[:pt.OUT_WORDS] for r in receipts], h, root_before)
 
 
 def _generate_control_roots(po2s=range(13, 25)) -> None:
