@@ -35,17 +35,21 @@ updates [first, first + min(N, D - first)), out = the root before update `first`
 """
 from __future__ import annotations
 
+import functools
 from typing import List, Sequence, Tuple
 
 import numpy as np
 
-from .desc import (GLOBAL_MIX, GLOBAL_OUT, GROUP_ACCUM, GROUP_CODE, GROUP_DATA, OP_ADD, OP_AND_EQZ, OP_CONST, OP_CONST_EXT, OP_GET,
-                   OP_GET_GLOBAL, OP_MUL, OP_SUB, OP_TRUE, P, Circuit, CircuitBuilder)
-from .p2_join import BLOCK_ROWS, DIAG, M4, NBETA, R, RC, RINV, T, block_rows, hash_pair_words, round_kind
+from . import p2_blocks
+from .desc import (GLOBAL_OUT, GROUP_CODE, GROUP_DATA, OP_ADD, OP_AND_EQZ, OP_CONST, OP_CONST_EXT, OP_GET, OP_GET_GLOBAL, OP_MUL, OP_SUB, OP_TRUE, P, Circuit,
+                   CircuitBuilder)
+from .p2_blocks import enc, gated, tree_height  # noqa: F401  (tree_height: what callers of this module size an image with)
+from .p2_join import BLOCK_ROWS, R, RINV, T, block_rows, hash_pair_words
 
 KIND_P2_PAGE = 5
 WC, WD, WA, OUT_WORDS = 39, 125, 4, 16
 C_LIN, C_FULLR, C_PARTR, C_LF, C_LP, C_LEAF_IN, C_NODE_IN, C_PATH_FIRST, C_TOP_OUT, C_LAST_TOP, C_CARRY, C_POW, C_RC = range(3, 16)
+ROUND_COLS = (C_LIN, C_FULLR, C_PARTR, C_LF, C_LP, C_RC)
 D_SO, D_QO, D_SN, D_QN, D_E, D_B, D_ADDR, D_W_IN, D_W_OUT, D_ACC, D_CUR = 0, 24, 48, 72, 96, 112, 113, 114, 115, 116, 117
 MAX_H = 27
 
@@ -53,80 +57,23 @@ MAX_H = 27
 FAMILIES: List[Tuple[str, int, int]] = []
 
 
-def tree_height(image_words: int) -> int:
-    """h = log2 L of an image of W words, L the smallest power of two >= ceil(W / 8)"""
-    L = 1
-    while 8 * L < image_words:
-        L <<= 1
-    return L.bit_length() - 1
-
-
 def slots(po2: int, zk_cycles: int, h: int) -> int:
     """N: the path slots of a trace of 2^po2 rows"""
     return (((1 << po2) - zk_cycles) // BLOCK_ROWS) // h
 
 
-def emit_rounds(b, chain, gated, code, dat, cst, sides, cols, input_rows):
-    """The `rounds` family P2-PAGE, P2-PAGE-ordered and P2-TREE (p2_tree.py) share, emitted onto `chain`: P2-JOIN's round constraints
-    on every (S, Q) pair of `sides` (data column offsets), and the capacity cells S[16 .. 24) zero where the selector `input_rows()`
-    (built after the round constraints, as the builders always did) is set.  cols = the code columns (lin, fullr, partr, lf, lp, rc);
-    cst = the constants 2 .. 7 as handles; gated(chain, selector, constraints) -> chain."""
-    c_lin, c_fullr, c_partr, c_lf, c_lp, c_rc = cols
-
-    def times(c, x):
-        return x if c == 1 else b.mul(cst[c], x)
-
-    def lin_m_ext(x):                                  # the 24 x 24 external matrix as expressions over 24 values
-        y = []
-        for blk in range(0, T, 4):
-            for i in range(4):
-                e = times(M4[i][0], x[blk])
-                for j in range(1, 4):
-                    e = b.add(e, times(M4[i][j], x[blk + j]))
-                y.append(e)
-        tot = []
-        for i in range(4):
-            e = y[i]
-            for blk in range(4, T, 4):
-                e = b.add(e, y[blk + i])
-            tot.append(e)
-        return [b.add(y[k], tot[k % 4]) for k in range(T)]
-
-    diag = [b.const(d) for d in DIAG]
-    cube = lambda x: b.mul(b.mul(x, x), x)
-    cap = []
-    for s0, q0 in sides:
-        S = lambda j, back=0, s0=s0: dat(s0 + j, back)
-        Q = lambda j, back=0, q0=q0: dat(q0 + j, back)
-        u = [b.add(S(j), code(c_rc + j)) for j in range(T)]
-        chain = gated(chain, code(c_fullr), [b.sub(Q(j), cube(u[j])) for j in range(T)])
-        chain = gated(chain, code(c_partr), [b.sub(Q(0), cube(u[0]))])
-        prev = [S(j, 1) for j in range(T)]
-        chain = gated(chain, code(c_lin), [b.sub(S(k), e) for k, e in enumerate(lin_m_ext(prev))])
-        x7 = [b.mul(b.mul(Q(j, 1), Q(j, 1)), b.add(S(j, 1), code(c_rc + j, 1))) for j in range(T)]
-        chain = gated(chain, code(c_lf), [b.sub(S(k), e) for k, e in enumerate(lin_m_ext(x7))])
-        tot = x7[0]
-        for j in range(1, T):
-            tot = b.add(tot, prev[j])
-        chain = gated(chain, code(c_lp), [b.sub(S(0), b.add(tot, b.mul(diag[0], x7[0])))]
-                      + [b.sub(S(j), b.add(tot, b.mul(diag[j], prev[j]))) for j in range(1, T)])
-        cap += [S(16 + i) for i in range(8)]
-    return gated(chain, input_rows(), cap)
-
-
 def build_page(kind: int, sizes: Tuple[int, int, int], out_words: int, after_roots=None):
     """-> (blob, families): P2-PAGE's constraint text over a circuit of `sizes` (accum, code, data) columns and `out_words` outputs.
-    after_roots(b, chain, gated, env) -> chain emits one more family, named by after_roots.family, between `roots` and `accum`
+    after_roots = (name, emit): emit(b, chain) -> chain emits one more family, `name`, between `roots` and `accum`
     (p2_page_ordered.py); without it this is P2-PAGE word for word."""
     b = CircuitBuilder(sizes, (out_words, WA), kind=kind)
     code = lambda c, back=0: b.get(GROUP_CODE, c, back)
     dat = lambda c, back=0: b.get(GROUP_DATA, c, back)
-    acc4 = lambda c, back=0: b.get(GROUP_ACCUM, c, back)
     out = lambda i: b.get_global(GLOBAL_OUT, i)
     one = b.const(1)
     active, first, body = code(0), code(1), code(2)
     cst = {v: b.const(v) for v in (2, 3, 4, 5, 6, 7)}
-    families = []
+    families, family = p2_blocks.family_log(b)
 
     def times(c, x):
         return x if c == 1 else b.mul(cst[c], x)
@@ -137,21 +84,11 @@ def build_page(kind: int, sizes: Tuple[int, int, int], out_words: int, after_roo
             e = b.add(e, x)
         return e
 
-    def gated(chain, sel, constraints):
-        inner = b.true()
-        for c in constraints:
-            inner = b.and_eqz(inner, c)
-        return b.and_cond(chain, sel, inner)
-
-    def family(name, start):
-        families.append((name, start, len(b.steps)))
-
     chain = b.true()
     leaf_in, node_in = code(C_LEAF_IN), code(C_NODE_IN)
     # 1. rounds: P2-JOIN's constraints on both permutations; the capacity cells are zero on every input row
     start = len(b.steps)
-    chain = emit_rounds(b, chain, gated, code, dat, cst, ((D_SO, D_QO), (D_SN, D_QN)), (C_LIN, C_FULLR, C_PARTR, C_LF, C_LP, C_RC),
-                        lambda: b.add(leaf_in, node_in))
+    chain = p2_blocks.emit_rounds(b, chain, code, dat, cst, ((D_SO, D_QO), (D_SN, D_QN)), ROUND_COLS, lambda: b.add(leaf_in, node_in))
     family("rounds", start)
 
     So = lambda j, back=0: dat(D_SO + j, back)
@@ -161,7 +98,7 @@ def build_page(kind: int, sizes: Tuple[int, int, int], out_words: int, after_roo
     cur = [dat(D_CUR + j) for j in range(8)]
     # 2. leaf_in: the word a & 15 of the pair of leaves is w_in on the old side, w_out on the new one; every other word is shared
     start = len(b.steps)
-    chain = gated(chain, leaf_in,
+    chain = gated(b, chain, leaf_in,
                   [b.mul(e[j], b.sub(one, e[j])) for j in range(16)] + [b.sub(total(e), one)]
                   + [b.mul(b.sub(one, e[j]), b.sub(So(j), Sn(j))) for j in range(16)]
                   + [b.sub(total([b.mul(e[j], So(j)) for j in range(16)]), w_in), b.sub(total([b.mul(e[j], Sn(j)) for j in range(16)]), w_out),
@@ -175,73 +112,51 @@ def build_page(kind: int, sizes: Tuple[int, int, int], out_words: int, after_roo
         cons += [b.add(b.mul(nb, b.sub(X(j), X(j, 1))), b.mul(bit, b.sub(X(8 + j), X(j, 1)))) for j in range(8)]
     cons += [b.add(b.mul(nb, b.sub(So(8 + j), Sn(8 + j))), b.mul(bit, b.sub(So(j), Sn(j)))) for j in range(8)]
     cons += [b.sub(acc, b.add(dat(D_ACC, 1), b.mul(code(C_POW), bit)))]
-    chain = gated(chain, node_in, cons)
+    chain = gated(b, chain, node_in, cons)
     family("node_in", start)
     # 4. carry: what is constant along a path; acc moves on node_in rows only
     start = len(b.steps)
-    chain = gated(chain, code(C_CARRY), [b.sub(dat(c), dat(c, 1)) for c in [D_ADDR, D_W_IN, D_W_OUT] + [D_CUR + j for j in range(8)]])
-    chain = gated(chain, b.sub(code(C_CARRY), node_in), [b.sub(acc, dat(D_ACC, 1))])
+    chain = gated(b, chain, code(C_CARRY), [b.sub(dat(c), dat(c, 1)) for c in [D_ADDR, D_W_IN, D_W_OUT] + [D_CUR + j for j in range(8)]])
+    chain = gated(b, chain, b.sub(code(C_CARRY), node_in), [b.sub(acc, dat(D_ACC, 1))])
     family("carry", start)
     # 5. top_out: the old path ends on the root in hand, at the address it claims
     start = len(b.steps)
-    chain = gated(chain, code(C_TOP_OUT), [b.sub(So(j), cur[j]) for j in range(8)] + [b.sub(acc, addr)])
+    chain = gated(b, chain, code(C_TOP_OUT), [b.sub(So(j), cur[j]) for j in range(8)] + [b.sub(acc, addr)])
     family("top_out", start)
     # 6. roots: the first path opens root_before, every later one the new root of the path before it, the last leaves root_after
     start = len(b.steps)
-    chain = gated(chain, first, [b.sub(cur[j], out(j)) for j in range(8)])
-    chain = gated(chain, code(C_PATH_FIRST), [b.sub(cur[j], Sn(j, 1)) for j in range(8)])
-    chain = gated(chain, code(C_LAST_TOP), [b.sub(Sn(j), out(8 + j)) for j in range(8)])
+    chain = gated(b, chain, first, [b.sub(cur[j], out(j)) for j in range(8)])
+    chain = gated(b, chain, code(C_PATH_FIRST), [b.sub(cur[j], Sn(j, 1)) for j in range(8)])
+    chain = gated(b, chain, code(C_LAST_TOP), [b.sub(Sn(j), out(8 + j)) for j in range(8)])
     family("roots", start)
     if after_roots is not None:
         start = len(b.steps)
-        chain = after_roots(b, chain, gated, dict(code=code, dat=dat, out=out, one=one, first=first, leaf_in=leaf_in, addr=addr, w_in=w_in, w_out=w_out))
-        family(after_roots.family, start)
-
+        chain = after_roots[1](b, chain)
+        family(after_roots[0], start)
     # 7. accum: one Fp4 running product of (mix + data column 0), and the selector sanity, as in P2-JOIN
     start = len(b.steps)
-    nbeta = b.const(NBETA)
-    m = [b.get_global(GLOBAL_MIX, i) for i in range(4)]
-    term = [b.add(m[0], So(0)), m[1], m[2], m[3]]
-    chain = gated(chain, first, [b.sub(acc4(i), term[i]) for i in range(4)])
-    pa = [acc4(i, 1) for i in range(4)]
-    mm = lambda i, j: b.mul(pa[i], term[j])
-    pr = [b.add(mm(0, 0), b.mul(nbeta, b.add(b.add(mm(1, 3), mm(2, 2)), mm(3, 1)))),
-          b.add(b.add(mm(0, 1), mm(1, 0)), b.mul(nbeta, b.add(mm(2, 3), mm(3, 2)))),
-          b.add(b.add(b.add(mm(0, 2), mm(1, 1)), mm(2, 0)), b.mul(nbeta, mm(3, 3))),
-          b.add(b.add(mm(0, 3), mm(1, 2)), b.add(mm(2, 1), mm(3, 0)))]
-    chain = gated(chain, body, [b.sub(acc4(i), pr[i]) for i in range(4)])
+    chain = p2_blocks.running_product(b, chain, first, body, So(0))
     family("accum", start)
     start = len(b.steps)
-    chain = b.and_eqz(chain, b.mul(active, b.sub(one, active)))
-    chain = b.and_eqz(chain, b.mul(first, b.sub(one, first)))
-    chain = b.and_eqz(chain, b.sub(b.sub(active, first), body))
+    chain = p2_blocks.sanity(b, chain, active, first, body)
     family("sanity", start)
     return b.finish(chain), families
 
 
+@functools.lru_cache(maxsize=None)
 def build_p2_page() -> np.ndarray:
-    blob, families = build_page(KIND_P2_PAGE, (WA, WC, WD), OUT_WORDS)
-    FAMILIES[:] = families
+    blob, FAMILIES[:] = build_page(KIND_P2_PAGE, (WA, WC, WD), OUT_WORDS)
     return blob
 
 
-_cached = None
-
-
 def p2_page_circuit() -> np.ndarray:
-    global _cached
-    if _cached is None:
-        _cached = build_p2_page()
-    return _cached.copy()
+    return build_p2_page().copy()
 
 
 def family_of(step: int) -> str:
     """the constraint family (rounds, leaf_in, node_in, carry, top_out, roots, accum, sanity) of a step of the description"""
-    p2_page_circuit()
-    for name, lo, hi in FAMILIES:
-        if lo <= step < hi:
-            return name
-    raise ValueError(f"step {step} is outside the description")
+    build_p2_page()
+    return p2_blocks.family_of(FAMILIES, step)
 
 
 def constraint_degrees(desc) -> List[int]:
@@ -266,42 +181,22 @@ def constraint_degrees(desc) -> List[int]:
 
 
 # ------------------------------------------------------------------------------------------------ host twins
-def _enc(x: int) -> int:
-    return x % P * R % P
-
-
 def reference_page_code(po2: int, zk_cycles: int, h: int) -> np.ndarray:
     """The code group zkh_page_circuit_code writes, (39, 2^po2) Montgomery words: a function of (po2, zk_cycles, h)."""
     if not 1 <= h <= MAX_H:
         raise ValueError(f"h {h} (1 .. {MAX_H})")
-    n = 1 << po2
-    A = n - zk_cycles
     N = slots(po2, zk_cycles, h)
-    code = np.zeros((WC, n), dtype=np.uint32)
-    code[0, :A] = R
-    code[1, 0] = R
-    code[2, 1:A] = R
+    code = p2_blocks.reference_round_code(WC, po2, zk_cycles, h * N, ROUND_COLS)
     for r in range(BLOCK_ROWS * h * N):
         k, blk = r % BLOCK_ROWS, r // BLOCK_ROWS
         t, s = blk % h, blk // h
-        kind = round_kind(k)
-        if k == 1:
-            code[C_LIN, r] = R
-        if kind == "full":
-            code[C_FULLR, r] = R
-            code[C_RC:C_RC + T, r] = [_enc(v) for v in RC[(k - 1) * T:k * T]]
-        if kind == "partial":
-            code[C_PARTR, r] = R
-            code[C_RC, r] = _enc(RC[(k - 1) * T])
-        if k >= 2:
-            code[C_LF if round_kind(k - 1) == "full" else C_LP, r] = R
         if k == 0 and t == 0:
             code[C_LEAF_IN, r] = R
             if s:
                 code[C_PATH_FIRST, r] = R
         if k == 0 and t:
             code[C_NODE_IN, r] = R
-            code[C_POW, r] = _enc(1 << (3 + t))
+            code[C_POW, r] = enc(1 << (3 + t))
         if k == BLOCK_ROWS - 1 and t == h - 1:
             code[C_TOP_OUT, r] = R
             if s == N - 1:
@@ -363,14 +258,14 @@ def reference_page_trace(po2: int, zk_cycles: int, W: int, table: Sequence[Tuple
                 r = r0 + BLOCK_ROWS * t + k
                 for base, v in ((D_SO, ro[k][0]), (D_QO, ro[k][1]), (D_SN, rn[k][0]), (D_QN, rn[k][1])):
                     data[base:base + T, r] = [x * R % P for x in v]
-                data[D_ACC, r] = _enc(a % (1 << (4 + t)))
+                data[D_ACC, r] = enc(a % (1 << (4 + t)))
             if t == 0:
                 data[D_E + (a & 15), r0] = R
             else:
                 data[D_B, r0 + BLOCK_ROWS * t] = R * ((a >> (3 + t)) & 1)
             d_old, d_new = ([x * R % P for x in rows[-1][0][:8]] for rows in (ro, rn))
         rows = slice(r0, r0 + BLOCK_ROWS * h)
-        data[D_ADDR, rows], data[D_W_IN, rows], data[D_W_OUT, rows] = _enc(a), w_in, w_out
+        data[D_ADDR, rows], data[D_W_IN, rows], data[D_W_OUT, rows] = enc(a), w_in, w_out
         for j in range(8):
             data[D_CUR + j, rows] = cur[j]
         # the plain tree takes the update on its own: the leaf's word, then hash_pair up the path

@@ -39,71 +39,63 @@ NOT constrained here: that the rows (a_i, in_i, out_i) are the page table of a p
 """
 from __future__ import annotations
 
+import functools
 from typing import List, Sequence, Tuple
 
 import numpy as np
 
-from . import p2_page
-from .desc import P
+from . import p2_blocks, p2_page
+from .desc import GLOBAL_OUT, GROUP_CODE, GROUP_DATA
+from .p2_blocks import GAP_BITS, decode, enc, gated, tree_height  # noqa: F401  (decode: what the chain verifier reads out[16], out[17] with)
 from .p2_join import BLOCK_ROWS, R
-from .p2_page import D_ADDR, _enc, slots, tree_height
+from .p2_page import D_ADDR, D_W_IN, D_W_OUT, slots
 
 KIND_P2_PAGE_ORDERED = 6
 WC, WD, WA, OUT_WORDS = 42, 129, 4, 18
 C_GSEL, C_GPOW, C_GEND = 39, 40, 41
 D_LIVE, D_LO, D_GBIT, D_GACC = 125, 126, 127, 128
 OUT_LO, OUT_HI = 16, 17
-GAP_BITS = 29
 MAX_H = 26
 
 # the constraint families, in the order the description emits them: (name, first step, end step) over the ZKC1 step list
 FAMILIES: List[Tuple[str, int, int]] = []
 
 
-def _order(b, chain, gated, env):
-    """the `order` family, after P2-PAGE's `roots`"""
-    code, dat, out, one = env["code"], env["dat"], env["out"], env["one"]
-    addr, w_in, w_out = env["addr"], env["w_in"], env["w_out"]
+def _order(b, chain):
+    """the `order` family, after P2-PAGE's `roots` (every tap of P2-PAGE's it names has been emitted there).  P2-TREE's `order` states
+    the same gap decomposition over (leaf, id) but emits it in another order: the two are not shared (p2_blocks.py)."""
+    code = lambda c, back=0: b.get(GROUP_CODE, c, back)
+    dat = lambda c, back=0: b.get(GROUP_DATA, c, back)
+    out = lambda i: b.get_global(GLOBAL_OUT, i)
+    one, addr, w_in, w_out = b.const(1), dat(D_ADDR), dat(D_W_IN), dat(D_W_OUT)
     live, lo, gbit, gacc = dat(D_LIVE), dat(D_LO), dat(D_GBIT), dat(D_GACC)
     dead = b.sub(one, live)
-    chain = gated(chain, env["leaf_in"], [b.mul(live, dead), b.mul(dead, b.sub(w_in, w_out)), gacc])
-    chain = gated(chain, code(p2_page.C_CARRY), [b.sub(live, dat(D_LIVE, 1)), b.sub(lo, dat(D_LO, 1))])
-    chain = gated(chain, code(C_GSEL), [b.mul(gbit, b.sub(one, gbit)), b.sub(gacc, b.add(dat(D_GACC, 1), b.mul(code(C_GPOW), gbit)))])
-    chain = gated(chain, code(C_GEND), [b.mul(live, b.sub(b.sub(addr, lo), gacc))])
-    chain = gated(chain, env["first"], [b.sub(lo, out(OUT_LO))])
+    chain = gated(b, chain, code(p2_page.C_LEAF_IN), [b.mul(live, dead), b.mul(dead, b.sub(w_in, w_out)), gacc])
+    chain = gated(b, chain, code(p2_page.C_CARRY), [b.sub(live, dat(D_LIVE, 1)), b.sub(lo, dat(D_LO, 1))])
+    chain = gated(b, chain, code(C_GSEL), [b.mul(gbit, b.sub(one, gbit)), b.sub(gacc, b.add(dat(D_GACC, 1), b.mul(code(C_GPOW), gbit)))])
+    chain = gated(b, chain, code(C_GEND), [b.mul(live, b.sub(b.sub(addr, lo), gacc))])
+    chain = gated(b, chain, code(1), [b.sub(lo, out(OUT_LO))])
     live_b, dead_b = dat(D_LIVE, 1), b.sub(one, dat(D_LIVE, 1))
-    chain = gated(chain, code(p2_page.C_PATH_FIRST),
+    chain = gated(b, chain, code(p2_page.C_PATH_FIRST),
                   [b.mul(live, dead_b), b.sub(lo, b.add(b.mul(live_b, b.add(dat(D_ADDR, 1), one)), b.mul(dead_b, dat(D_LO, 1))))])
-    chain = gated(chain, code(p2_page.C_LAST_TOP), [b.sub(out(OUT_HI), b.add(b.mul(live, b.add(addr, one)), b.mul(dead, lo)))])
+    chain = gated(b, chain, code(p2_page.C_LAST_TOP), [b.sub(out(OUT_HI), b.add(b.mul(live, b.add(addr, one)), b.mul(dead, lo)))])
     return chain
 
 
-_order.family = "order"
-
-
+@functools.lru_cache(maxsize=None)
 def build_p2_page_ordered() -> np.ndarray:
-    blob, families = p2_page.build_page(KIND_P2_PAGE_ORDERED, (WA, WC, WD), OUT_WORDS, after_roots=_order)
-    FAMILIES[:] = families
+    blob, FAMILIES[:] = p2_page.build_page(KIND_P2_PAGE_ORDERED, (WA, WC, WD), OUT_WORDS, after_roots=("order", _order))
     return blob
 
 
-_cached = None
-
-
 def p2_page_ordered_circuit() -> np.ndarray:
-    global _cached
-    if _cached is None:
-        _cached = build_p2_page_ordered()
-    return _cached.copy()
+    return build_p2_page_ordered().copy()
 
 
 def family_of(step: int) -> str:
     """the constraint family (P2-PAGE's, with `order` after `roots`) of a step of the description"""
-    p2_page_ordered_circuit()
-    for name, lo, hi in FAMILIES:
-        if lo <= step < hi:
-            return name
-    raise ValueError(f"step {step} is outside the description")
+    build_p2_page_ordered()
+    return p2_blocks.family_of(FAMILIES, step)
 
 
 # ------------------------------------------------------------------------------------------------ host twins
@@ -118,7 +110,7 @@ def reference_ordered_code(po2: int, zk_cycles: int, h: int) -> np.ndarray:
     for s in range(slots(po2, zk_cycles, h)):
         r0 = path * s
         code[C_GSEL, r0 + 1:r0 + 1 + GAP_BITS] = R
-        code[C_GPOW, r0 + 1:r0 + 1 + GAP_BITS] = [_enc(1 << k) for k in range(GAP_BITS)]
+        code[C_GPOW, r0 + 1:r0 + 1 + GAP_BITS] = [enc(1 << k) for k in range(GAP_BITS)]
         code[C_GEND, r0 + GAP_BITS] = R
     return code
 
@@ -143,10 +135,8 @@ def order_columns(po2: int, zk_cycles: int, h: int, addrs: Sequence[int], first:
             raise ValueError(f"row {row}: address {a} does not follow {lo - 1} by a gap of {GAP_BITS} bits")
         r0 = path * s
         cols[0, r0:r0 + path] = R * live
-        cols[1, r0:r0 + path] = _enc(lo)
-        for k in range(1, GAP_BITS + 1):
-            cols[2, r0 + k] = R * ((g >> (k - 1)) & 1)
-            cols[3, r0 + k] = _enc(g % (1 << k))
+        cols[1, r0:r0 + path] = enc(lo)
+        cols[2, r0 + 1:r0 + 1 + GAP_BITS], cols[3, r0 + 1:r0 + 1 + GAP_BITS] = p2_blocks.gap_columns(g)
         if s == 0:
             out_lo = lo
         hi = a + 1 if live else lo
@@ -163,13 +153,8 @@ def reference_ordered_part(po2: int, zk_cycles: int, W: int, table: Sequence[Tup
     page, root_before, root_after = p2_page.reference_page_part(po2, zk_cycles, W, table, image_before, first)
     cols, lo, hi = order_columns(po2, zk_cycles, h, [int(row[0]) for row in table], first)
     data = np.concatenate([page, cols])
-    out = np.concatenate([root_before, root_after, [_enc(lo), _enc(hi)]]).astype(np.uint32)
+    out = np.concatenate([root_before, root_after, [enc(lo), enc(hi)]]).astype(np.uint32)
     return data, out
-
-
-def decode(word: int) -> int:
-    """the integer a Montgomery word of the trace (out[16], out[17]) stands for"""
-    return int(word) % P * p2_page.RINV % P
 
 
 if __name__ == "__main__":      # python -m zeth_amd.circuits.p2_page_ordered out.desc   (blob for non-Python hosts)

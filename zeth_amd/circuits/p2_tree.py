@@ -31,7 +31,7 @@ Slot order: the pair blocks first, in increasing id; then the other live blocks:
 sides, every flag zero, id 0, so idr = 1; lo carried); the root block is always slot B - 1.  Rows past 31 B are zero.
 
 Constraint families (`FAMILIES`, `family_of`; every one of degree <= 3 before its selector, backs 0 and 1):
-  rounds  P2-PAGE's (p2_page.emit_rounds) on both permutations; the capacity cells are zero on in_row
+  rounds  P2-PAGE's (p2_blocks.emit_rounds) on both permutations; the capacity cells are zero on in_row
   in_row  leaf, up, dl, dr boolean; idl = 2 id, idr = 2 id + 1; leaf dl = leaf dr = 0; (1 - leaf)(1 - dl)(S_old[j] - S_new[j]) = 0 for
           j < 8 and the same with dr for j in 8 .. 15: a clean child is ONE sibling serving both sides
   carry   id, idl, idr, leaf, up, dl, dr, lo are constant along a block; gacc too, except on gsel rows; gbit = 0 on the output row
@@ -44,7 +44,7 @@ Constraint families (`FAMILIES`, `family_of`; every one of degree <= 3 before it
           of the output row.  Left consumer: +1, in_row, dl, key idl, S_old[0..8), S_new[0..8) of the input row.  Right consumer: +1,
           in_row, dr, key idr, S_old[8..16), S_new[8..16).  The three terms of a tag share one accum column.  No records: nothing is
           derived.
-  sanity  as in P2-PAGE
+  sanity  P2-PAGE's (p2_blocks.sanity)
 
 WHY THE BUS FORCES A TREE.  Every produced tuple must be consumed by a block whose id is the producer's id >> 1, on the matching side
 (the key is idl or idr of the consumer).  The only block that produces nothing is the root slot (up = 0 there, and id = 1).  A second
@@ -65,20 +65,20 @@ from typing import List, Sequence, Tuple
 
 import numpy as np
 
-from . import p2_page
+from . import p2_blocks
 from .desc import GLOBAL_OUT, GROUP_CODE, GROUP_DATA, P
 from .logup import LogupBuilder
-from .p2_join import BLOCK_ROWS, R, RC, RINV, T, block_rows, round_kind
-from .p2_page import _enc, tree_height
+from .p2_blocks import GAP_BITS, decode, enc, gated, tree_height  # noqa: F401  (decode: what the chain verifier reads out[16], out[17] with)
+from .p2_join import BLOCK_ROWS, R, RINV, T, block_rows
 
 KIND_P2_TREE = 7
 WC, WD, WA, OUT_WORDS, MIX_WORDS = 41, 106, 24, 18, 8
 (C_LIN, C_FULLR, C_PARTR, C_LF, C_LP, C_IN_ROW, C_OUT_ROW, C_BLOCK_FIRST, C_CARRY, C_LAST_TOP, C_GSEL, C_GPOW, C_GEND, C_RC) = range(3, 17)
 C_LAST = 40
+ROUND_COLS = (C_LIN, C_FULLR, C_PARTR, C_LF, C_LP, C_RC)
 D_SO, D_QO, D_SN, D_QN = 0, 24, 48, 72
 D_ID, D_IDL, D_IDR, D_LEAF, D_UP, D_DL, D_DR, D_LO, D_GBIT, D_GACC = range(96, 106)
 OUT_LO, OUT_HI = 16, 17
-GAP_BITS = 29
 MIN_H, MAX_H = 2, 27
 
 # the constraint families, in the order the description emits them: (name, first step, end step) over the ZKC1 step list
@@ -90,6 +90,7 @@ def block_slots(po2: int, zk_cycles: int) -> int:
     return ((1 << po2) - zk_cycles) // BLOCK_ROWS
 
 
+@functools.lru_cache(maxsize=None)
 def build_p2_tree() -> Tuple[np.ndarray, np.ndarray]:
     """-> (ZKC1 description, ZKA1 argument blob)"""
     b = LogupBuilder((WA, WC, WD), (OUT_WORDS, MIX_WORDS), alpha=0, beta=4, kind=KIND_P2_TREE)
@@ -99,21 +100,12 @@ def build_p2_tree() -> Tuple[np.ndarray, np.ndarray]:
     one = b.const(1)
     active, first, body = code(0), code(1), code(2)
     cst = {v: b.const(v) for v in (2, 3, 4, 5, 6, 7)}
-    families = []
-
-    def gated(chain, sel, constraints):
-        inner = b.true()
-        for c in constraints:
-            inner = b.and_eqz(inner, c)
-        return b.and_cond(chain, sel, inner)
-
-    def family(name, start):
-        families.append((name, start, len(b.steps)))
+    families, family = p2_blocks.family_log(b)
 
     chain = b.true()
     in_row = code(C_IN_ROW)
     start = len(b.steps)
-    chain = p2_page.emit_rounds(b, chain, gated, code, dat, cst, ((D_SO, D_QO), (D_SN, D_QN)), (C_LIN, C_FULLR, C_PARTR, C_LF, C_LP, C_RC), lambda: in_row)
+    chain = p2_blocks.emit_rounds(b, chain, code, dat, cst, ((D_SO, D_QO), (D_SN, D_QN)), ROUND_COLS, lambda: in_row)
     family("rounds", start)
 
     So = lambda j, back=0: dat(D_SO + j, back)
@@ -126,27 +118,27 @@ def build_p2_tree() -> Tuple[np.ndarray, np.ndarray]:
     for side, lo_j in ((dl, 0), (dr, 8)):
         clean = b.mul(inner_node, b.sub(one, side))
         cons += [b.mul(clean, b.sub(So(lo_j + j), Sn(lo_j + j))) for j in range(8)]
-    chain = gated(chain, in_row, cons)
+    chain = gated(b, chain, in_row, cons)
     family("in_row", start)
 
     start = len(b.steps)
-    chain = gated(chain, code(C_CARRY), [b.sub(dat(c), dat(c, 1)) for c in range(D_ID, D_LO + 1)])
-    chain = gated(chain, b.sub(code(C_CARRY), code(C_GSEL)), [b.sub(gacc, dat(D_GACC, 1)), gbit])
+    chain = gated(b, chain, code(C_CARRY), [b.sub(dat(c), dat(c, 1)) for c in range(D_ID, D_LO + 1)])
+    chain = gated(b, chain, b.sub(code(C_CARRY), code(C_GSEL)), [b.sub(gacc, dat(D_GACC, 1)), gbit])
     family("carry", start)
 
     start = len(b.steps)
-    chain = gated(chain, in_row, [gbit, gacc])
-    chain = gated(chain, code(C_GSEL), [b.mul(gbit, b.sub(one, gbit)), b.sub(gacc, b.add(dat(D_GACC, 1), b.mul(code(C_GPOW), gbit)))])
-    chain = gated(chain, code(C_GEND), [b.mul(leaf, b.sub(b.sub(ident, lo), gacc))])
+    chain = gated(b, chain, in_row, [gbit, gacc])
+    chain = gated(b, chain, code(C_GSEL), [b.mul(gbit, b.sub(one, gbit)), b.sub(gacc, b.add(dat(D_GACC, 1), b.mul(code(C_GPOW), gbit)))])
+    chain = gated(b, chain, code(C_GEND), [b.mul(leaf, b.sub(b.sub(ident, lo), gacc))])
     leaf_b, inner_b = dat(D_LEAF, 1), b.sub(one, dat(D_LEAF, 1))
-    chain = gated(chain, code(C_BLOCK_FIRST),
+    chain = gated(b, chain, code(C_BLOCK_FIRST),
                   [b.mul(leaf, inner_b), b.sub(lo, b.add(b.mul(leaf_b, b.add(dat(D_ID, 1), one)), b.mul(inner_b, dat(D_LO, 1))))])
-    chain = gated(chain, first, [b.sub(lo, out(OUT_LO))])
-    chain = gated(chain, code(C_LAST_TOP), [b.sub(out(OUT_HI), b.add(b.mul(leaf, b.add(ident, one)), b.mul(inner_node, lo)))])
+    chain = gated(b, chain, first, [b.sub(lo, out(OUT_LO))])
+    chain = gated(b, chain, code(C_LAST_TOP), [b.sub(out(OUT_HI), b.add(b.mul(leaf, b.add(ident, one)), b.mul(inner_node, lo)))])
     family("order", start)
 
     start = len(b.steps)
-    chain = gated(chain, code(C_LAST_TOP), [b.sub(ident, one), up] + [b.sub(So(j), out(j)) for j in range(8)] + [b.sub(Sn(j), out(8 + j)) for j in range(8)])
+    chain = gated(b, chain, code(C_LAST_TOP), [b.sub(ident, one), up] + [b.sub(So(j), out(j)) for j in range(8)] + [b.sub(Sn(j), out(8 + j)) for j in range(8)])
     family("root", start)
 
     # the bus: three terms per tag, one accum column per tag
@@ -157,9 +149,7 @@ def build_p2_tree() -> Tuple[np.ndarray, np.ndarray]:
     family("bus", start)
 
     start = len(b.steps)
-    chain = b.and_eqz(chain, b.mul(active, b.sub(one, active)))
-    chain = b.and_eqz(chain, b.mul(first, b.sub(one, first)))
-    chain = b.and_eqz(chain, b.sub(b.sub(active, first), body))
+    chain = p2_blocks.sanity(b, chain, active, first, body)
     family("sanity", start)
     FAMILIES[:] = families
     return b.finish_all(chain)
@@ -177,76 +167,37 @@ def bus_terms() -> List[dict]:
     return terms
 
 
-_cached = None
-
-
-def _built():
-    global _cached
-    if _cached is None:
-        _cached = build_p2_tree()
-    return _cached
-
-
 def p2_tree_circuit() -> np.ndarray:
-    return _built()[0].copy()
+    return build_p2_tree()[0].copy()
 
 
 def arguments() -> np.ndarray:
     """the ZKA1 blob of the bus: what SegmentProver(hal, p2_tree_circuit(), arguments=arguments()) hands zkh_accumulate"""
-    return _built()[1].copy()
+    return build_p2_tree()[1].copy()
 
 
 def family_of(step: int) -> str:
     """the constraint family (rounds, in_row, carry, order, root, bus, sanity) of a step of the description"""
-    _built()
-    for name, lo, hi in FAMILIES:
-        if lo <= step < hi:
-            return name
-    raise ValueError(f"step {step} is outside the description")
-
-
-def decode(word: int) -> int:
-    """the integer a Montgomery word of the trace (out[16], out[17]) stands for"""
-    return int(word) % P * RINV % P
+    build_p2_tree()
+    return p2_blocks.family_of(FAMILIES, step)
 
 
 # ------------------------------------------------------------------------------------------------ host twins
 def reference_tree_code(po2: int, zk_cycles: int) -> np.ndarray:
     """The code group zkh_page_tree_code writes, (41, 2^po2) Montgomery words: a function of (po2, zk_cycles) alone."""
-    n = 1 << po2
-    A = n - zk_cycles
     B = block_slots(po2, zk_cycles)
-    code = np.zeros((WC, n), dtype=np.uint32)
-    code[0, :A] = R
-    code[1, 0] = R
-    code[2, 1:A] = R
-    code[C_LAST, A - 1] = R
-    for k in range(BLOCK_ROWS):
-        rows = slice(k, BLOCK_ROWS * B, BLOCK_ROWS)
-        kind = round_kind(k)
-        if k == 1:
-            code[C_LIN, rows] = R
-        if kind == "full":
-            code[C_FULLR, rows] = R
-            for j in range(T):
-                code[C_RC + j, rows] = _enc(RC[(k - 1) * T + j])
-        if kind == "partial":
-            code[C_PARTR, rows] = R
-            code[C_RC, rows] = _enc(RC[(k - 1) * T])
-        if k >= 2:
-            code[C_LF if round_kind(k - 1) == "full" else C_LP, rows] = R
-        if k == 0:
-            code[C_IN_ROW, rows] = R
-            code[C_BLOCK_FIRST, BLOCK_ROWS::BLOCK_ROWS][:max(B - 1, 0)] = R
-        if k == BLOCK_ROWS - 1:
-            code[C_OUT_ROW, rows] = R
-        if k:
-            code[C_CARRY, rows] = R
-        if 1 <= k <= GAP_BITS:
-            code[C_GSEL, rows] = R
-            code[C_GPOW, rows] = _enc(1 << (k - 1))
-        if k == GAP_BITS:
-            code[C_GEND, rows] = R
+    code = p2_blocks.reference_round_code(WC, po2, zk_cycles, B, ROUND_COLS)
+    code[C_LAST, (1 << po2) - zk_cycles - 1] = R
+    rows = lambda k: slice(k, BLOCK_ROWS * B, BLOCK_ROWS)
+    code[C_IN_ROW, rows(0)] = R
+    code[C_BLOCK_FIRST, BLOCK_ROWS::BLOCK_ROWS][:max(B - 1, 0)] = R
+    code[C_OUT_ROW, rows(BLOCK_ROWS - 1)] = R
+    for k in range(1, BLOCK_ROWS):
+        code[C_CARRY, rows(k)] = R
+    for k in range(1, GAP_BITS + 1):
+        code[C_GSEL, rows(k)] = R
+        code[C_GPOW, rows(k)] = enc(1 << (k - 1))
+    code[C_GEND, rows(GAP_BITS)] = R
     if B:
         code[C_LAST_TOP, BLOCK_ROWS * B - 1] = R
     return code
@@ -350,21 +301,19 @@ def reference_tree_part(po2: int, zk_cycles: int, W: int, table: Sequence[Tuple[
         if not 0 <= g < 1 << GAP_BITS:
             raise ValueError(f"slot {slot}: id {i} does not follow {lo - 1} by a gap of {GAP_BITS} bits")
         r0 = BLOCK_ROWS * slot
-        data[D_ID, rows], data[D_IDL, rows], data[D_IDR, rows] = _enc(i), _enc(2 * i), _enc(2 * i + 1)
+        data[D_ID, rows], data[D_IDL, rows], data[D_IDR, rows] = enc(i), enc(2 * i), enc(2 * i + 1)
         data[D_LEAF, rows], data[D_UP, rows] = R * leaf, R * (i > 1)
         data[D_DL, rows], data[D_DR, rows] = R * (0 < i < half and 2 * i in live), R * (0 < i < half and 2 * i + 1 in live)
-        data[D_LO, rows] = _enc(lo)
-        for k in range(1, GAP_BITS + 1):
-            data[D_GBIT, r0 + k] = R * ((g >> (k - 1)) & 1)
-            data[D_GACC, r0 + k] = _enc(g % (1 << k))
-        data[D_GACC, r0 + BLOCK_ROWS - 1] = _enc(g)
-    out = np.concatenate([old[1], new[1], [_enc(base), _enc(hi)]]).astype(np.uint32)
+        data[D_LO, rows] = enc(lo)
+        data[D_GBIT, r0 + 1:r0 + 1 + GAP_BITS], data[D_GACC, r0 + 1:r0 + 1 + GAP_BITS] = p2_blocks.gap_columns(g)
+        data[D_GACC, r0 + BLOCK_ROWS - 1] = enc(g)
+    out = np.concatenate([old[1], new[1], [enc(base), enc(hi)]]).astype(np.uint32)
     return data, out
 
 
 if __name__ == "__main__":      # python -m zeth_amd.circuits.p2_tree out.desc out.args   (blobs for non-Python hosts)
     import sys
-    desc, args = _built()
+    desc, args = build_p2_tree()
     np.asarray(desc, dtype="<u4").tofile(sys.argv[1])
     print(f"{sys.argv[1]}: {desc.size} words")
     if len(sys.argv) > 2:

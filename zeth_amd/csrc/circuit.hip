@@ -343,7 +343,8 @@ KeccakTables keccak_tables() {
 // two child claims into the parent claim, the other blocks hash (parent ‖ public sibling words).  Stands in for the in-circuit
 // hashing of risc0-circuit-recursion 4.0.2 (un-vendored: /root/reference/Cargo.lock:5305).  A literal round-by-round
 // permutation (the trace needs every intermediate state); tab = Montgomery words of rc[24 * 29] then diag[24].
-// (PJ_*, pj_is_full, pj_m_ext: p2_rows.h, shared with the P2-PAGE generator of page_circuit.hip)
+// (PJ_*, pj_is_full, pj_m_ext: p2_rows.h, shared with the generators of page_circuit.hip and page_tree.hip.  These two kernels keep
+// their switch and their round loop written out, where those call pj_code_cell and pj_block_rows: p2_rows.h says why.)
 __global__ void k_p2join_code(uint32_t* code, uint32_t n, uint32_t A, uint32_t K, const uint32_t* __restrict__ tab) {
     const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x, col = blockIdx.y;
     if (r >= n) return;
@@ -413,12 +414,6 @@ __global__ void k_p2join_blocks(uint32_t* data, const uint32_t* __restrict__ cod
     const size_t rl = r0 + PJ_BLOCK - 1;
     for (uint32_t j = 0; j < PJ_T; j++) { data[(size_t)j * n + rl] = s[j]; data[(size_t)(PJ_T + j) * n + rl] = 0; }
     if (p == 0) for (uint32_t j = 0; j < 8; j++) parent[j] = s[j];
-}
-// rows past the last block: zero while active, blinding noise after
-__global__ void k_p2join_tail(uint32_t* data, uint32_t n, uint32_t A, uint32_t first_row, NoiseKey nk) {
-    const uint32_t r = first_row + blockIdx.x * blockDim.x + threadIdx.x, col = blockIdx.y;
-    if (r >= n) return;
-    data[(size_t)col * n + r] = r < A ? 0u : noise_cell(nk, GROUP_DATA, col, r);
 }
 
 }  // namespace
@@ -812,6 +807,15 @@ const char* zkh::p2_rows_tables(zkh_ctx* ctx, Tmp& tab) {           // Montgomer
     for (uint32_t i = 0; i < PJ_T; i++) t[PJ_T * PJ_ROUNDS + i] = fp_encode(ZKH_P2_M_INT_DIAG[i]).v;
     return zkh_copy_from(ctx, "p2_rows_tables", t.data(), t.size(), tab.out());
 }
+// rows past the last block of a P2-JOIN, P2-PAGE or P2-TREE trace: zero while active, blinding noise after
+static __global__ void k_rows_tail(uint32_t* data, uint32_t n, uint32_t A, uint32_t first_row, NoiseKey nk) {
+    const uint32_t r = first_row + blockIdx.x * blockDim.x + threadIdx.x, col = blockIdx.y;
+    if (r >= n) return;
+    data[(size_t)col * n + r] = r < A ? 0u : noise_cell(nk, GROUP_DATA, col, r);
+}
+void zkh::p2_rows_tail(zkh_ctx* ctx, zkh_buf* data, uint32_t wd, size_t n, uint32_t A, uint32_t first_row, const NoiseKey& nk) {
+    k_rows_tail<<<dim3((unsigned)((n - first_row + 255) / 256), wd), 256, 0, ctx->stream>>>(data->ptr(), (uint32_t)n, A, first_row, nk);
+}
 static const char* p2join_check_shape(const zkh_circuit* c) {
     ZKH_REQUIRE(c->group_size[GROUP_CODE] == 43 && c->group_size[GROUP_DATA] == 2 * PJ_T && c->group_size[GROUP_ACCUM] == 4 &&
                 c->global_size[GLOBAL_OUT] == 24, "p2join witgen: the circuit does not have P2-JOIN's shape (43 / 48 / 4 columns, 24 outputs)");
@@ -881,7 +885,7 @@ extern "C" const char* zkh_syn_witgen(zkh_ctx* ctx, const zkh_circuit* c, size_t
             k_p2join_blocks<<<1, 64, 0, ctx->stream>>>(data->ptr(), code->ptr(), (uint32_t)n, 0, 1, kids->ptr(), parent->ptr(), tab->ptr());
             if (K > 1) k_p2join_blocks<<<(K - 1 + 63) / 64, 64, 0, ctx->stream>>>(data->ptr(), code->ptr(), (uint32_t)n, 1, K - 1, kids->ptr(), parent->ptr(), tab->ptr());
             const uint32_t first = PJ_BLOCK * K;
-            if (first < n) k_p2join_tail<<<dim3((unsigned)((n - first + 255) / 256), wd), 256, 0, ctx->stream>>>(data->ptr(), (uint32_t)n, A, first, nk);
+            if (first < n) p2_rows_tail(ctx, data, wd, n, A, first, nk);
         }
         ZKH_TRY(last_launch_error("p2join_witgen"));
         memcpy(out_global + 8, pub, 64);

@@ -14,6 +14,12 @@ inline size_t image_leaves(size_t W) {
     while (L * 8 < W) L <<= 1;
     return L;
 }
+// h = log2 L: the hash_pairs of a path from a leaf to the root
+inline uint32_t image_height(size_t W) {
+    uint32_t h = 0;
+    while (((size_t)1 << h) < image_leaves(W)) h++;
+    return h;
+}
 
 // hash.hip: every layer above the one of `first_layer` digests (a power of two; 1: nothing), the widest with one lane per parent, the
 // narrow ones with the 8-lane kernels

@@ -25,20 +25,18 @@
 //
 // KERNELS.  k_page_check: ONE workgroup; the lowest row of the table whose address is outside the image or does not follow a smaller
 // one (an LDS minimum, no atomics), whether the code group was built for this h, and digest 1 of both trees, into a record of 24 words.
-// k_page_paths: one lane per (slot, old / new) walks its h blocks with the literal permutation of k_p2join_blocks; it returns at once
+// k_page_paths: one lane per (slot, old / new) walks its h blocks, every block by pj_block_rows (p2_rows.h); it returns at once
 // when the record holds a refusal, so no address at or past W ever indexes `nodes_*`.  k_page_root (parts only: first > 0, or a part
 // that is not the last): the record's roots that k_page_check does not own.  k_page_book: one lane per (row, bookkeeping column);
 // `cur` of slot 0 is the record's first root, of slot s > 0 it is read from the output row the path kernel wrote for slot s - 1.
-// k_page_tail: zero rows, then the blinding rows.  No atomics, every cell (of the record too) has one writer; one read-back fetches
-// the record at the end.
+// k_rows_tail (circuit.hip, p2_rows_tail): zero rows, then the blinding rows.  No atomics, every cell (of the record too) has one
+// writer; one read-back fetches the record at the end.
 //
 // P2-PAGE-ORDERED (zeth_amd/circuits/p2_page_ordered.py; include/zkhal.h "P2-PAGE-ordered"): the same trace in a wider buffer, columns
 // 0 .. 124 of the data group and 0 .. 38 of the code group written by the kernels above as they stand (every one of them strides by n,
 // and the tail's width is a grid dimension), then the columns live, lo, gbit, gacc by k_page_order and gsel, gpow, gend by
 // k_page_order_code.  The order the circuit constrains is the one the two-tree shortcut already relies on and k_page_check already
 // refuses a table without: lo of a slot is one more than the address of the table's row before it, and the gap to it is >= 0.
-#include "circuit.h"
-#include "image_tree.h"
 #include "p2_rows.h"
 
 using namespace zkh;
@@ -51,20 +49,17 @@ constexpr uint32_t PG_WC = 39, PG_WD = 125, PG_OUT = 16, PG_MAX_H = 27;
 constexpr uint32_t PO_WC = 42, PO_WD = 129, PO_OUT = 18, PO_MAX_H = 26, PO_GAP_BITS = 29;
 enum : uint32_t { PC_GSEL = 39, PC_GPOW = 40, PC_GEND = 41 };
 enum : uint32_t { PD_LIVE = 125, PD_LO = 126, PD_GBIT = 127, PD_GACC = 128 };
-// the shape of the circuit an entry point serves
-struct PageShape { const char* name; uint32_t kind, wc, wd, out, max_h; };
-constexpr PageShape PAGE = {"P2-PAGE", 5, PG_WC, PG_WD, PG_OUT, PG_MAX_H}, ORDERED = {"P2-PAGE-ordered", 6, PO_WC, PO_WD, PO_OUT, PO_MAX_H};
+// the shape of the circuit an entry point serves (p2_rows.h PageShape)
+constexpr PageShape PAGE = {"P2-PAGE", 5, PG_WC, PG_WD, 4, PG_OUT, PG_MAX_H, " (the code group is an input of this generator)"},
+                    ORDERED = {"P2-PAGE-ordered", 6, PO_WC, PO_WD, 4, PO_OUT, PO_MAX_H, " (the code group is an input of this generator)"};
 // code columns (p2_page.py C_*)
 enum : uint32_t { PC_LIN = 3, PC_FULLR, PC_PARTR, PC_LF, PC_LP, PC_LEAF_IN, PC_NODE_IN, PC_PATH_FIRST, PC_TOP_OUT, PC_LAST_TOP, PC_CARRY, PC_POW, PC_RC };
 // data columns (p2_page.py D_*)
 enum : uint32_t { PD_SO = 0, PD_QO = 24, PD_SN = 48, PD_QN = 72, PD_E = 96, PD_B = 112, PD_ADDR = 113, PD_W_IN = 114, PD_W_OUT = 115, PD_ACC = 116, PD_CUR = 117 };
-// the record: the lowest refused row (NONE: none), its address, the address before it, whether the code group is this h's, both roots
+// the record: the lowest refused row (PJ_NONE: none), its address, the address before it, whether the code group is this h's, both roots
 // (the one the trace's first path opens, the one its last path leaves); P2-PAGE-ordered: lo and hi as the trace holds them (k_page_order)
-enum : uint32_t { PR_ROW = 0, PR_A = 1, PR_BEFORE = 2, PR_CODE_OK = 3, PR_LO = 4, PR_HI = 5, PR_ROOTS = 8, PR_WORDS = 24 };
-constexpr uint32_t NONE = 0xffffffffu;
+enum : uint32_t { PR_ROW = TABLE_ROW, PR_CODE_OK = 3, PR_LO = 4, PR_HI = 5, PR_ROOTS = 8, PR_WORDS = 24 };
 constexpr uint32_t PG_THREADS = 256;
-
-__device__ __forceinline__ uint32_t encode(uint32_t x) { return mul_mod(R2, x); }       // x < P
 
 __global__ void k_page_code(uint32_t* code, uint32_t n, uint32_t A, uint32_t h, uint32_t N, const uint32_t* __restrict__ tab) {
     const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x, col = blockIdx.y;
@@ -72,26 +67,16 @@ __global__ void k_page_code(uint32_t* code, uint32_t n, uint32_t A, uint32_t h, 
     uint32_t v = 0;
     const bool in_paths = r < PJ_BLOCK * h * N;
     const uint32_t k = r % PJ_BLOCK, blk = r / PJ_BLOCK, t = blk % h, s = blk / h;
-    const bool round_row = in_paths && k >= 1 && k <= PJ_ROUNDS;
-    const bool full = round_row && pj_is_full(k - 1), part = round_row && !pj_is_full(k - 1);
     const bool top = in_paths && k == PJ_BLOCK - 1 && t == h - 1;
     switch (col) {
-    case 0: v = r < A ? R1 : 0; break;
-    case 1: v = r == 0 ? R1 : 0; break;
-    case 2: v = (r > 0 && r < A) ? R1 : 0; break;
-    case PC_LIN: v = (in_paths && k == 1) ? R1 : 0; break;
-    case PC_FULLR: v = full ? R1 : 0; break;
-    case PC_PARTR: v = part ? R1 : 0; break;
-    case PC_LF: v = (in_paths && k >= 2 && pj_is_full(k - 2)) ? R1 : 0; break;
-    case PC_LP: v = (in_paths && k >= 2 && !pj_is_full(k - 2)) ? R1 : 0; break;
     case PC_LEAF_IN: v = (in_paths && k == 0 && t == 0) ? R1 : 0; break;
     case PC_NODE_IN: v = (in_paths && k == 0 && t > 0) ? R1 : 0; break;
     case PC_PATH_FIRST: v = (in_paths && k == 0 && t == 0 && s > 0) ? R1 : 0; break;
     case PC_TOP_OUT: v = top ? R1 : 0; break;
     case PC_LAST_TOP: v = (top && s == N - 1) ? R1 : 0; break;
     case PC_CARRY: v = (in_paths && (k > 0 || t > 0)) ? R1 : 0; break;
-    case PC_POW: v = (in_paths && k == 0 && t > 0) ? encode(1u << (3 + t)) : 0; break;
-    default: if (full || (part && col == PC_RC)) v = tab[(k - 1) * PJ_T + (col - PC_RC)];
+    case PC_POW: v = (in_paths && k == 0 && t > 0) ? pj_encode(1u << (3 + t)) : 0; break;
+    default: v = pj_code_cell(col < PC_RC ? col : PJ_RC0 + col - PC_RC, r, A, k, in_paths, tab);     // columns 0 .. 7 are their roles
     }
     code[(size_t)col * n + r] = v;
 }
@@ -104,7 +89,7 @@ __global__ void k_page_order_code(uint32_t* code, uint32_t n, uint32_t h, uint32
     const bool bits = r < PJ_BLOCK * h * N && t == 0 && k >= 1 && k <= PO_GAP_BITS;       // rows 1 .. 29 of a path's block 0
     uint32_t v = 0;
     if (col == PC_GSEL) v = bits ? R1 : 0;
-    else if (col == PC_GPOW) v = bits ? encode(1u << (k - 1)) : 0;
+    else if (col == PC_GPOW) v = bits ? pj_encode(1u << (k - 1)) : 0;
     else v = (bits && k == PO_GAP_BITS) ? R1 : 0;
     code[(size_t)col * n + r] = v;
 }
@@ -117,25 +102,11 @@ __global__ __launch_bounds__(PG_THREADS) void k_page_check(const uint32_t* __res
                                                            const uint32_t* __restrict__ nodes_after, uint32_t* __restrict__ rec) {
     __shared__ uint32_t low[PG_THREADS];
     const uint32_t t = threadIdx.x;
-    uint32_t bad = NONE;
-    for (uint32_t i = t; i < D && bad == NONE; i += PG_THREADS) {
-        const uint32_t a = table[3 * (size_t)i];
-        if (a >= W || (i && table[3 * (size_t)(i - 1)] >= a)) bad = i;
-    }
-    low[t] = bad;
-    __syncthreads();
-    for (uint32_t s = PG_THREADS / 2; s; s >>= 1) {
-        if (t < s) low[t] = low[t] < low[t + s] ? low[t] : low[t + s];
-        __syncthreads();
-    }
+    pj_table_lowest<PG_THREADS>(pj_table_scan<PG_THREADS>(table, D, W), table, low, rec, [](uint32_t, uint32_t) {});
     if (t == 0) {
-        const uint32_t i = low[0];
-        rec[PR_ROW] = i;
-        rec[PR_A] = i != NONE ? table[3 * (size_t)i] : 0;
-        rec[PR_BEFORE] = i != NONE && i ? table[3 * (size_t)(i - 1)] : 0;
         // a code group of another h' has its first top_out row at 31 h' - 1 and 2^(3 + t) on the input row of its blocks t = block % h'
         const bool top = code[(size_t)PC_TOP_OUT * n + PJ_BLOCK * h - 1] == R1;
-        const bool pow = h == 1 || code[(size_t)PC_POW * n + PJ_BLOCK * (h - 1)] == encode(1u << (2 + h));
+        const bool pow = h == 1 || code[(size_t)PC_POW * n + PJ_BLOCK * (h - 1)] == pj_encode(1u << (2 + h));
         rec[PR_CODE_OK] = top && pow;
     }
     if (t >= 8 && t < 16 && first == 0) rec[t] = nodes_before[t];     // digest 1 = words [8, 16)
@@ -143,102 +114,42 @@ __global__ __launch_bounds__(PG_THREADS) void k_page_check(const uint32_t* __res
 }
 
 // One lane per (slot, side): side 0 the old path, 1 the new one.  Slot s holds the table's row first + s (first < D < 2^31, s < N <
-// 2^26: the sum does not wrap).  L = the tree's leaves (2^h), words of layer t's node x at 8 ((L >> t) + x); the leaf layer is the
-// memory itself at words [8 L, 16 L).
+// 2^26: the sum does not wrap).  The sources of its h blocks by the address rule (p2_rows.h), the rows by pj_block_rows.
 __global__ __launch_bounds__(64) void k_page_paths(uint32_t* __restrict__ data, uint32_t n, uint32_t h, uint32_t N, const uint32_t* __restrict__ table, uint32_t D,
                                                    uint32_t first, const uint32_t* __restrict__ nodes_before, const uint32_t* __restrict__ nodes_after, size_t L,
                                                    const uint32_t* __restrict__ rec, const uint32_t* __restrict__ tab) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= 2 * N || rec[PR_ROW] != NONE) return;
+    if (i >= 2 * N || rec[PR_ROW] != PJ_NONE) return;
     const uint32_t slot = i >> 1, side = i & 1;
     const bool real = first + slot < D;
     const uint32_t a = real ? table[3 * (size_t)(first + slot)] : 0;   // < W <= 8 L: the record holds no refusal
-    const uint32_t* before = real ? nodes_before : nodes_after;        // a no-op opens the tree after the page-out
-    const uint32_t s_col = side ? PD_SN : PD_SO, q_col = side ? PD_QN : PD_QO;
-    const uint32_t* diag = tab + PJ_T * PJ_ROUNDS;
+    const uint32_t* open = real ? nodes_before : nodes_after;          // a no-op opens the tree after the page-out
     uint32_t s[PJ_T];
     for (uint32_t t = 0; t < h; t++) {
-        const size_t r0 = (size_t)PJ_BLOCK * ((size_t)slot * h + t);
-        if (t == 0) {
-            const uint32_t x0 = a & ~15u;                              // the pair of leaves: 16 words, all below 8 L (L >= 2)
-            for (uint32_t j = 0; j < 16; j++) {
-                const uint32_t x = x0 + j;
-                const bool done = side ? x <= a : x < a;
-                s[j] = (done ? nodes_after : before)[8 * L + x];
-            }
-        } else {
-            const uint32_t x = a >> (3 + t);                           // the on-path node of layer t, the lane's own digest in s[0, 8)
-            const bool right = x & 1;
-            const uint32_t* sib = (right ? nodes_after : before) + 8 * ((L >> t) + (x ^ 1));
-            for (uint32_t j = 0; j < 8; j++) {
-                const uint32_t own = s[j], other = sib[j];
-                s[j] = right ? other : own;
-                s[8 + j] = right ? own : other;
-            }
-        }
+        if (t == 0) pj_pair_words(s, a & ~15u, a, side, open, nodes_after, L);
+        else pj_join_sibling(s, t, a, open, nodes_after, L);           // the lane's own digest is in s[0, 8)
         for (uint32_t j = 16; j < PJ_T; j++) s[j] = 0;
-        for (uint32_t j = 0; j < PJ_T; j++) { data[(size_t)(s_col + j) * n + r0] = s[j]; data[(size_t)(q_col + j) * n + r0] = 0; }
-        pj_m_ext(s);
-        // the round loop of k_p2join_blocks (circuit.hip) on this side's columns
-        for (uint32_t rnd = 0; rnd < PJ_ROUNDS; rnd++) {
-            const size_t r = r0 + 1 + rnd;
-            for (uint32_t j = 0; j < PJ_T; j++) data[(size_t)(s_col + j) * n + r] = s[j];
-            if (pj_is_full(rnd)) {
-                for (uint32_t j = 0; j < PJ_T; j++) {
-                    const uint32_t u = add_mod(s[j], tab[rnd * PJ_T + j]);
-                    const uint32_t q = mul_mod(mul_mod(u, u), u);
-                    data[(size_t)(q_col + j) * n + r] = q;
-                    s[j] = mul_mod(mul_mod(q, q), u);
-                }
-                pj_m_ext(s);
-            } else {
-                const uint32_t u = add_mod(s[0], tab[rnd * PJ_T]);
-                const uint32_t q = mul_mod(mul_mod(u, u), u);
-                data[(size_t)q_col * n + r] = q;
-                for (uint32_t j = 1; j < PJ_T; j++) data[(size_t)(q_col + j) * n + r] = 0;
-                const uint32_t x7 = mul_mod(mul_mod(q, q), u);
-                uint32_t tot = x7;
-                for (uint32_t j = 1; j < PJ_T; j++) tot = add_mod(tot, s[j]);
-                s[0] = add_mod(tot, mul_mod(diag[0], x7));
-                for (uint32_t j = 1; j < PJ_T; j++) s[j] = add_mod(tot, mul_mod(diag[j], s[j]));
-            }
-        }
-        const size_t rl = r0 + PJ_BLOCK - 1;
-        for (uint32_t j = 0; j < PJ_T; j++) { data[(size_t)(s_col + j) * n + rl] = s[j]; data[(size_t)(q_col + j) * n + rl] = 0; }
+        pj_block_rows(data, n, (size_t)PJ_BLOCK * ((size_t)slot * h + t), side ? PD_SN : PD_SO, side ? PD_QN : PD_QO, s, tab);
     }
 }
 
 // ONE wave, after k_page_paths, launched only for a part that does not start the table or does not end it: the roots of the record
 // that are not digest 1 of a tree.  Lane 0, first > 0: the root BEFORE the part = the tree with the updates [0, first) applied = the
-// top of the new path of update first - 1, walked as k_page_paths walks a new side (the update's own word and everything below it from
-// `nodes_after`, everything above from `nodes_before`) but as h bare hash_pairs (k_hash_walk's lane body, hash.hip): no rows.  Lanes
-// 8 .. 15, a part that is not the last: the root AFTER it, the output row of slot N - 1's new path.  It returns at once on a refusal,
-// as the path kernel does; `rec` is read and written here (distinct cells), hence no __restrict__ on it.
+// top of the new path of update first - 1, walked as k_page_paths walks a new side but as h bare hash_pairs: no rows.  Lanes 8 .. 15, a
+// part that is not the last: the root AFTER it, the output row of slot N - 1's new path.  It returns at once on a refusal, as the
+// path kernel does; `rec` is read and written here (distinct cells), hence no __restrict__ on it.
 __global__ __launch_bounds__(64) void k_page_root(const uint32_t* __restrict__ data, uint32_t n, uint32_t h, uint32_t N, const uint32_t* __restrict__ table, uint32_t D,
                                                   uint32_t first, const uint32_t* __restrict__ nodes_before, const uint32_t* __restrict__ nodes_after, size_t L,
                                                   uint32_t* rec, const uint32_t* __restrict__ rc, const uint32_t* __restrict__ diag) {
     const uint32_t lane = threadIdx.x;
-    if (rec[PR_ROW] != NONE) return;
+    if (rec[PR_ROW] != PJ_NONE) return;
     if (lane >= 8 && lane < 16 && D - first > N) rec[PR_ROOTS + lane] = data[(size_t)(PD_SN + lane - 8) * n + (size_t)PJ_BLOCK * h * N - 1];
     if (lane != 0 || first == 0) return;
     const uint32_t a = table[3 * (size_t)(first - 1)];                 // < W <= 8 L: the record holds no refusal
     uint32_t s[CELLS];
     for (uint32_t t = 0; t < h; t++) {
-        if (t == 0) {
-            const uint32_t x0 = a & ~15u;
-#pragma unroll
-            for (uint32_t j = 0; j < 16; j++) s[j] = (x0 + j <= a ? nodes_after : nodes_before)[8 * L + x0 + j];
-        } else {
-            const uint32_t x = a >> (3 + t);
-            const bool right = x & 1;
-            const uint32_t* sib = (right ? nodes_after : nodes_before) + 8 * ((L >> t) + (x ^ 1));
-#pragma unroll
-            for (uint32_t j = 0; j < 8; j++) {
-                const uint32_t own = s[j], other = sib[j];
-                s[j] = right ? other : own;
-                s[8 + j] = right ? own : other;
-            }
-        }
+        if (t == 0) pj_pair_words(s, a & ~15u, a, true, nodes_before, nodes_after, L);
+        else pj_join_sibling(s, t, a, nodes_before, nodes_after, L);
 #pragma unroll
         for (int j = RATE; j < CELLS; j++) s[j] = 0;
         poseidon2_mix_raw<0, OUT, RATE>(s, rc, diag);
@@ -254,7 +165,7 @@ __global__ __launch_bounds__(64) void k_page_root(const uint32_t* __restrict__ d
 __global__ __launch_bounds__(PG_THREADS) void k_page_book(uint32_t* __restrict__ data, uint32_t n, uint32_t h, uint32_t N, const uint32_t* __restrict__ table, uint32_t D,
                                                           uint32_t first, const uint32_t* __restrict__ nodes_after, size_t L, const uint32_t* __restrict__ rec) {
     const uint32_t r = blockIdx.x * PG_THREADS + threadIdx.x, col = PD_E + blockIdx.y;
-    if (r >= PJ_BLOCK * h * N || rec[PR_ROW] != NONE) return;
+    if (r >= PJ_BLOCK * h * N || rec[PR_ROW] != PJ_NONE) return;
     const uint32_t k = r % PJ_BLOCK, blk = r / PJ_BLOCK, t = blk % h, slot = blk / h;
     const bool real = first + slot < D;
     const size_t row = (size_t)first + slot;
@@ -262,10 +173,10 @@ __global__ __launch_bounds__(PG_THREADS) void k_page_book(uint32_t* __restrict__
     uint32_t v = 0;
     if (col < PD_B) v = (k == 0 && t == 0 && (a & 15) == col - PD_E) ? R1 : 0;
     else if (col == PD_B) v = (k == 0 && t > 0 && ((a >> (3 + t)) & 1)) ? R1 : 0;
-    else if (col == PD_ADDR) v = encode(a);
+    else if (col == PD_ADDR) v = pj_encode(a);
     else if (col == PD_W_IN) v = real ? table[3 * row + 1] : nodes_after[8 * L];
     else if (col == PD_W_OUT) v = real ? table[3 * row + 2] : nodes_after[8 * L];
-    else if (col == PD_ACC) v = encode(a & ((1u << (4 + t)) - 1));
+    else if (col == PD_ACC) v = pj_encode(a & ((1u << (4 + t)) - 1));
     else v = slot ? data[(size_t)(PD_SN + col - PD_CUR) * n + (size_t)PJ_BLOCK * h * slot - 1] : rec[PR_ROOTS + col - PD_CUR];
     data[(size_t)col * n + r] = v;
 }
@@ -279,7 +190,7 @@ __global__ __launch_bounds__(PG_THREADS) void k_page_book(uint32_t* __restrict__
 __global__ __launch_bounds__(PG_THREADS) void k_page_order(uint32_t* __restrict__ data, uint32_t n, uint32_t h, uint32_t N, const uint32_t* __restrict__ table, uint32_t D,
                                                            uint32_t first, uint32_t* rec) {
     const uint32_t r = blockIdx.x * PG_THREADS + threadIdx.x, col = PD_LIVE + blockIdx.y, rows = PJ_BLOCK * h * N;
-    if (r >= rows || rec[PR_ROW] != NONE) return;
+    if (r >= rows || rec[PR_ROW] != PJ_NONE) return;
     const uint32_t k = r % PJ_BLOCK, blk = r / PJ_BLOCK, t = blk % h, slot = blk / h;
     const size_t row = (size_t)first + slot;
     const bool live = row < D;
@@ -290,35 +201,18 @@ __global__ __launch_bounds__(PG_THREADS) void k_page_order(uint32_t* __restrict_
     const bool bits = t == 0 && k >= 1 && k <= PO_GAP_BITS;
     uint32_t v;
     if (col == PD_LIVE) v = live ? R1 : 0;
-    else if (col == PD_LO) v = encode(lo);
+    else if (col == PD_LO) v = pj_encode(lo);
     else if (col == PD_GBIT) v = (bits && ((g >> (k - 1)) & 1)) ? R1 : 0;
-    else v = bits ? encode(g & ((1u << k) - 1)) : 0;
+    else v = bits ? pj_encode(g & ((1u << k) - 1)) : 0;
     data[(size_t)col * n + r] = v;
     if (col == PD_LO && r == 0) rec[PR_LO] = v;
-    if (col == PD_LO && r == rows - 1) rec[PR_HI] = encode(live ? a + 1 : lo);
+    if (col == PD_LO && r == rows - 1) rec[PR_HI] = pj_encode(live ? a + 1 : lo);
 }
 
-// rows past the last path: zero while active, blinding noise after
-__global__ void k_page_tail(uint32_t* data, uint32_t n, uint32_t A, uint32_t first_row, NoiseKey nk) {
-    const uint32_t r = first_row + blockIdx.x * blockDim.x + threadIdx.x, col = blockIdx.y;
-    if (r >= n) return;
-    data[(size_t)col * n + r] = r < A ? 0u : noise_cell(nk, GROUP_DATA, col, r);
-}
-
-// the checks the entry points share.  First the circuit's shape and the trace's size ...
-inline bool page_po2_ok(size_t po2, size_t zk_cycles) { return po2 >= 1 && po2 <= 30 && ((size_t)1 << po2) > zk_cycles + 1; }
-const char* page_circuit_shape(const char* who, const PageShape& sh, const zkh_circuit* c, size_t po2, size_t zk_cycles) {
-    ZKH_REQUIRE(c->kind == sh.kind && c->group_size[GROUP_CODE] == sh.wc && c->group_size[GROUP_DATA] == sh.wd && c->group_size[GROUP_ACCUM] == 4 &&
-                c->global_size[GLOBAL_OUT] == sh.out, "%s: the circuit does not have %s's shape (kind %u, %u / %u / 4 columns, %u outputs)", who, sh.name, sh.kind,
-                sh.wc, sh.wd, sh.out);
-    ZKH_REQUIRE(page_po2_ok(po2, zk_cycles), "%s: po2 %zu out of range for %zu zk_cycles", who, po2, zk_cycles);
-    return nullptr;
-}
-// ... then the image's -> A, h, N
+// the image's shape, after the circuit's (p2_rows.h page_circuit_shape) -> A, h, N
 const char* page_image_shape(const char* who, const PageShape& sh, size_t po2, size_t zk_cycles, size_t W, uint32_t* A_out, uint32_t* h_out, uint32_t* N_out) {
     ZKH_REQUIRE(W > 8, "%s: an image of %zu words has a single leaf (W > 8: a path is at least one hash_pair)", who, W);
-    uint32_t h = 0;
-    while (((size_t)1 << h) < image_leaves(W)) h++;
+    const uint32_t h = image_height(W);
     ZKH_REQUIRE(h <= PG_MAX_H, "%s: an image of %zu words has h %u; the address is rebuilt in the field, which takes h <= %u", who, W, h, PG_MAX_H);
     ZKH_REQUIRE(h <= sh.max_h, "%s: an image of %zu words has h %u; the gap between two addresses is decomposed into %u bits, which takes addresses below 2^%u: h <= %u",
                 who, W, h, PO_GAP_BITS, PO_GAP_BITS, sh.max_h);
@@ -333,28 +227,17 @@ const char* page_image_shape(const char* who, const PageShape& sh, size_t po2, s
 const char* page_witgen(const char* who, const PageShape& sh, bool whole, zkh_ctx* ctx, const zkh_circuit* c, size_t po2, size_t zk_cycles, const zkh_buf* code, const zkh_buf* proof,
                         size_t proof_words, const zkh_buf* nodes_before, const zkh_buf* nodes_after, size_t first_row, zkh_buf* data, uint32_t* out_roots,
                         const uint32_t* noise_key) {
-    ZKH_REQUIRE(ctx && c && code && proof && nodes_before && nodes_after && data && out_roots, "%s: null argument", who);
-    ZKH_TRY(page_circuit_shape(who, sh, c, po2, zk_cycles));
-    const size_t n = (size_t)1 << po2;
-    ZKH_REQUIRE(code->len == (size_t)sh.wc * n && data->len == (size_t)sh.wd * n, "%s: buffer shape mismatch (the code group is an input of this generator)", who);
-    ZKH_REQUIRE(proof_words <= proof->len && proof_words <= 0xffffffffull, "%s: a proof of %zu words in a buffer of %zu", who, proof_words, proof->len);
-    NoiseKey nk;
-    ZKH_TRY(resolve_noise_key(noise_key, &nk));
-    bind_thread(ctx);
-    uint32_t head[PROOF_HEAD_MAX] = {0};
-    ZKH_TRY(zkh_read(ctx, proof, head, 0, proof_words < PROOF_HEAD_MAX ? proof_words : PROOF_HEAD_MAX));
-    ZKH_TRY(image_proof_header(who, head, proof_words));
-    const uint32_t W = head[1], D = head[2];
     uint32_t A, h, N;
-    ZKH_TRY(page_image_shape(who, sh, po2, zk_cycles, W, &A, &h, &N));
-    const size_t L = image_leaves(W);
-    ZKH_REQUIRE(nodes_before->len == 16 * L && nodes_after->len == 16 * L, "%s: nodes of %zu and %zu words; an image of %u words has a tree of %zu (zkh_image_tree_words)",
-                who, nodes_before->len, nodes_after->len, W, 16 * L);
+    PageOpen o;
+    ZKH_TRY(page_open(who, sh, ctx, c, po2, zk_cycles, code, proof, proof_words, nodes_before, nodes_after, data, out_roots, noise_key,
+                      [&](size_t W) { return page_image_shape(who, sh, po2, zk_cycles, W, &A, &h, &N); }, &o));
+    const size_t n = o.n, L = o.L;
+    const uint32_t W = o.W, D = o.D, *table = o.table;
+    const NoiseKey& nk = o.nk;
     if (whole) ZKH_REQUIRE(D <= N, "%s: D %u updates, but h %u at po2 %zu leaves N %u path slots", who, D, h, po2, N);
     else ZKH_REQUIRE(first_row < D || (first_row == 0 && D == 0), "%s: first %zu, but the table has %u rows", who, first_row, D);
     const uint32_t first = (uint32_t)first_row;                       // < D, and 3 D words fit the proof: D < 2^31
     const bool own_roots = first || D - first > N;                    // a root of this part is not digest 1 of a tree: k_page_root
-    const uint32_t* table = proof->ptr() + 5 + h;                     // 3 D words inside the proof: its length is what the header describes
     Tmp tab, rec;
     ZKH_TRY(p2_rows_tables(ctx, tab));
     ZKH_TRY(new_buf(ctx, PR_WORDS, false, rec.out()));
@@ -380,7 +263,7 @@ const char* page_witgen(const char* who, const PageShape& sh, bool whole, zkh_ct
         ProfScope prof(ctx, "page_book", 4.0 * (PG_WD - PD_E) * rows + 4.0 * sh.wd * (n - rows));
         k_page_book<<<dim3((rows + PG_THREADS - 1) / PG_THREADS, PG_WD - PD_E), PG_THREADS, 0, ctx->stream>>>(data->ptr(), (uint32_t)n, h, N, table, D, first,
                                                                                                                nodes_after->ptr(), L, rec->ptr());
-        if (rows < n) k_page_tail<<<dim3((unsigned)((n - rows + 255) / 256), sh.wd), 256, 0, ctx->stream>>>(data->ptr(), (uint32_t)n, A, rows, nk);
+        if (rows < n) p2_rows_tail(ctx, data, sh.wd, n, A, rows, nk);
         ZKH_TRY(last_launch_error("page_book"));
     }
     if (sh.wd == PO_WD) {
@@ -391,10 +274,7 @@ const char* page_witgen(const char* who, const PageShape& sh, bool whole, zkh_ct
     uint32_t r[PR_WORDS];
     ZKH_TRY(zkh_read(ctx, rec, r, 0, PR_WORDS));
     ZKH_REQUIRE(r[PR_CODE_OK], "%s: the code group was not built for h %u (zkh_page_circuit_code with this image's size)", who, h);
-    if (r[PR_ROW] != NONE) {
-        if (r[PR_A] >= W) return make_err("%s: row %u: address %u outside the image of %u words", who, r[PR_ROW], r[PR_A], W);
-        return make_err("%s: row %u: address %u does not follow a smaller one (row %u: address %u)", who, r[PR_ROW], r[PR_A], r[PR_ROW] - 1, r[PR_BEFORE]);
-    }
+    ZKH_TRY(table_refusal(who, r, W));
     memcpy(out_roots, r + PR_ROOTS, 4 * PG_OUT);
     if (sh.out == PO_OUT) { out_roots[16] = r[PR_LO]; out_roots[17] = r[PR_HI]; }
     return nullptr;
@@ -417,12 +297,6 @@ const char* page_code(const char* who, const PageShape& sh, zkh_ctx* ctx, const 
 }
 
 }  // namespace
-
-// p2_rows.h: the tail kernel for another generator's data group (page_tree.hip)
-const char* zkh::page_tail_rows(zkh_ctx* ctx, zkh_buf* data, uint32_t wd, size_t n, uint32_t A, uint32_t first_row, const NoiseKey& nk) {
-    k_page_tail<<<dim3((unsigned)((n - first_row + 255) / 256), wd), 256, 0, ctx->stream>>>(data->ptr(), (uint32_t)n, A, first_row, nk);
-    return last_launch_error("page_tail");
-}
 
 extern "C" const char* zkh_page_circuit_code(zkh_ctx* ctx, const zkh_circuit* c, size_t po2, size_t zk_cycles, size_t image_words, zkh_buf* code) {
     return page_code("page_circuit_code", PAGE, ctx, c, po2, zk_cycles, image_words, code);

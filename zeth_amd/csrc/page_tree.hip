@@ -17,10 +17,8 @@
 // or past W ever indexes `nodes_*` and no slot past B is written.  k_tree_edges: one wave, lane 0 the old chain, lane 1 the new one.
 // k_tree_place: ONE workgroup, one lane per update, 256 at a time: the slot list (p2_tree.py slot order) by two block scans with a
 // carry.  k_tree_blocks: one lane per (slot, side), the literal round loop of k_p2join_blocks.  k_tree_book: one lane per (row,
-// bookkeeping column).  The tail rows are page_circuit.hip's (page_tail_rows).  One writer per cell (of the record and the slot list
+// bookkeeping column).  The tail rows are k_rows_tail's (circuit.hip, p2_rows_tail).  One writer per cell (of the record and the slot list
 // too), one read-back of the record at the end.
-#include "circuit.h"
-#include "image_tree.h"
 #include "p2_rows.h"
 #include "scan.h"
 
@@ -29,6 +27,7 @@ using namespace zkh;
 namespace {
 
 constexpr uint32_t PT_KIND = 7, PT_WC = 41, PT_WD = 106, PT_WA = 24, PT_OUT = 18, PT_MIN_H = 2, PT_MAX_H = 27, PT_GAP_BITS = 29;
+constexpr PageShape TREE = {"P2-TREE", PT_KIND, PT_WC, PT_WD, PT_WA, PT_OUT, PT_MAX_H, ""};     // p2_rows.h
 // code columns (p2_tree.py C_*)
 enum : uint32_t { TC_LIN = 3, TC_FULLR, TC_PARTR, TC_LF, TC_LP, TC_IN_ROW, TC_OUT_ROW, TC_BLOCK_FIRST, TC_CARRY, TC_LAST_TOP, TC_GSEL, TC_GPOW, TC_GEND, TC_RC, TC_LAST = 40 };
 // data columns (p2_tree.py D_*)
@@ -37,10 +36,8 @@ enum : uint32_t { TD_SO = 0, TD_QO = 24, TD_SN = 48, TD_QN = 72, TD_ID = 96, TD_
 // nodes (saturated) and pairs, lo and hi as the trace holds them, whether anything is refused, both roots, both edge chains (h digests
 // each: step t's is the node of layer t + 1)
 enum : uint32_t { TR_ROW = 0, TR_A, TR_BEFORE, TR_SPLIT, TR_NODES, TR_PAIRS, TR_LO, TR_HI, TR_REFUSED, TR_ROOTS = 16, TR_EDGES = 32, TR_WORDS = TR_EDGES + 16 * PT_MAX_H };
-constexpr uint32_t NONE = 0xffffffffu;
 constexpr uint32_t PT_THREADS = 256;
 
-__device__ __forceinline__ uint32_t encode(uint32_t x) { return mul_mod(R2, x); }       // x < P
 __device__ __forceinline__ uint32_t bit_length(uint32_t x) { return 32u - (uint32_t)__clz((int)x); }   // __clz(0) = 32
 // the nodes update i of the part starts: all h of its path when it is the part's first, else those below the fork from the update before
 __device__ __forceinline__ uint32_t started(const uint32_t* __restrict__ table, uint32_t first, uint32_t i, uint32_t h) {
@@ -56,26 +53,17 @@ __global__ void k_tree_code(uint32_t* code, uint32_t n, uint32_t A, uint32_t B, 
     const bool in_blocks = r < PJ_BLOCK * B;
     const uint32_t k = r % PJ_BLOCK, slot = r / PJ_BLOCK;
     const bool round_row = in_blocks && k >= 1 && k <= PJ_ROUNDS;
-    const bool full = round_row && pj_is_full(k - 1), part = round_row && !pj_is_full(k - 1);
     switch (col) {
-    case 0: v = r < A ? R1 : 0; break;
-    case 1: v = r == 0 ? R1 : 0; break;
-    case 2: v = (r > 0 && r < A) ? R1 : 0; break;
-    case TC_LIN: v = (in_blocks && k == 1) ? R1 : 0; break;
-    case TC_FULLR: v = full ? R1 : 0; break;
-    case TC_PARTR: v = part ? R1 : 0; break;
-    case TC_LF: v = (in_blocks && k >= 2 && pj_is_full(k - 2)) ? R1 : 0; break;
-    case TC_LP: v = (in_blocks && k >= 2 && !pj_is_full(k - 2)) ? R1 : 0; break;
     case TC_IN_ROW: v = (in_blocks && k == 0) ? R1 : 0; break;
     case TC_OUT_ROW: v = (in_blocks && k == PJ_BLOCK - 1) ? R1 : 0; break;
     case TC_BLOCK_FIRST: v = (in_blocks && k == 0 && slot > 0) ? R1 : 0; break;
     case TC_CARRY: v = (in_blocks && k > 0) ? R1 : 0; break;
     case TC_LAST_TOP: v = (in_blocks && k == PJ_BLOCK - 1 && slot == B - 1) ? R1 : 0; break;
     case TC_GSEL: v = round_row ? R1 : 0; break;                       // rows 1 .. 29: the 29 gap bits
-    case TC_GPOW: v = round_row ? encode(1u << (k - 1)) : 0; break;
+    case TC_GPOW: v = round_row ? pj_encode(1u << (k - 1)) : 0; break;
     case TC_GEND: v = (round_row && k == PT_GAP_BITS) ? R1 : 0; break;
     case TC_LAST: v = r == A - 1 ? R1 : 0; break;
-    default: if (full || (part && col == TC_RC)) v = tab[(k - 1) * PJ_T + (col - TC_RC)];
+    default: v = pj_code_cell(col < TC_RC ? col : PJ_RC0 + col - TC_RC, r, A, k, in_blocks, tab);    // columns 0 .. 7 are their roles
     }
     code[(size_t)col * n + r] = v;
 }
@@ -87,46 +75,31 @@ __global__ __launch_bounds__(PT_THREADS) void k_tree_check(const uint32_t* __res
     __shared__ uint32_t low[PT_THREADS], pairs[PT_THREADS];
     __shared__ unsigned long long nodes[PT_THREADS];
     const uint32_t t = threadIdx.x;
-    uint32_t bad = NONE;
-    for (uint32_t i = t; i < D && bad == NONE; i += PT_THREADS) {
-        const uint32_t a = table[3 * (size_t)i];
-        if (a >= W || (i && table[3 * (size_t)(i - 1)] >= a)) bad = i;
-    }
+    const uint32_t bad = pj_table_scan<PT_THREADS>(table, D, W);
     unsigned long long sum = 0;
     uint32_t fresh = 0;
-    for (uint32_t i = t; i < count; i += PT_THREADS) {
-        const uint32_t c = started(table, first, i, h);
+    for (uint32_t u = t; u < count; u += PT_THREADS) {
+        const uint32_t c = started(table, first, u, h);
         sum += c;
         fresh += c != 0;
     }
-    low[t] = bad; nodes[t] = sum; pairs[t] = fresh;
-    __syncthreads();
-    for (uint32_t s = PT_THREADS / 2; s; s >>= 1) {
-        if (t < s) {
-            low[t] = low[t] < low[t + s] ? low[t] : low[t + s];
-            nodes[t] += nodes[t + s];
-            pairs[t] += pairs[t + s];
-        }
-        __syncthreads();
-    }
+    nodes[t] = sum; pairs[t] = fresh;
+    const uint32_t i = pj_table_lowest<PT_THREADS>(bad, table, low, rec, [&](uint32_t t, uint32_t s) { nodes[t] += nodes[t + s]; pairs[t] += pairs[t + s]; });
     if (t == 0) {
-        const uint32_t i = low[0], end = first + count;
-        uint32_t split = NONE;
+        const uint32_t end = first + count;
+        uint32_t split = PJ_NONE;
         if (end && end < D && table[3 * (size_t)(end - 1)] >> 4 == table[3 * (size_t)end] >> 4) split = end;
         if (first && first < D && table[3 * (size_t)(first - 1)] >> 4 == table[3 * (size_t)first] >> 4) split = first;
         const unsigned long long total = count ? nodes[0] : 1;          // an empty part is the root block alone
-        rec[TR_ROW] = i;
-        rec[TR_A] = i != NONE ? table[3 * (size_t)i] : 0;
-        rec[TR_BEFORE] = i != NONE && i ? table[3 * (size_t)(i - 1)] : 0;
         rec[TR_SPLIT] = split;
         rec[TR_NODES] = total > 0xfffffffeull ? 0xfffffffeu : (uint32_t)total;
         rec[TR_PAIRS] = pairs[0];
-        rec[TR_REFUSED] = i != NONE || split != NONE || total > B;
+        rec[TR_REFUSED] = i != PJ_NONE || split != PJ_NONE || total > B;
     }
 }
 
-// ONE wave.  Lane 0: a_f's OLD path, lane 1: a_l's NEW path, each h bare hash_pairs (k_page_root's lane body, page_circuit.hip) whose
-// digests go into the record; the tops are the part's two roots.  An empty part: both roots are digest 1 of the tree as it stands.
+// ONE wave.  Lane 0: a_f's OLD path, lane 1: a_l's NEW path, each h bare hash_pairs (as k_page_root's lane 0) whose digests go into
+// the record; the tops are the part's two roots.  An empty part: both roots are digest 1 of the tree as it stands.
 __global__ __launch_bounds__(64) void k_tree_edges(uint32_t h, const uint32_t* __restrict__ table, uint32_t first, uint32_t count, const uint32_t* __restrict__ nodes_before,
                                                    const uint32_t* __restrict__ nodes_after, size_t L, uint32_t* rec, const uint32_t* __restrict__ rc,
                                                    const uint32_t* __restrict__ diag) {
@@ -140,6 +113,8 @@ __global__ __launch_bounds__(64) void k_tree_edges(uint32_t h, const uint32_t* _
     const uint32_t side = lane;
     const uint32_t a = table[3 * (size_t)(side ? first + count - 1 : first)];      // < W <= 8 L: the record holds no refusal
     uint32_t s[CELLS];
+    // the address rule written out, not p2_rows.h's pj_pair_words and pj_join_sibling: through them this one-lane kernel measured 4 to
+    // 7 % slower (M24, medians of six runs: 0.342 against 0.329 ms at h = 17, 0.474 against 0.442 ms at h = 23)
     for (uint32_t t = 0; t < h; t++) {
         if (t == 0) {
             const uint32_t x0 = a & ~15u;
@@ -205,7 +180,9 @@ __global__ __launch_bounds__(PT_THREADS) void k_tree_place(uint32_t* __restrict_
 }
 
 // One lane per (slot, side): side 0 the old permutation, 1 the new one.  The 16 input words by the address rule at the top of this
-// file, then the round loop of k_p2join_blocks (circuit.hip) on this side's columns.  A dead slot (id 0) hashes zeros.
+// file, then the round loop of k_p2join_blocks (circuit.hip) on this side's columns.  A dead slot (id 0) hashes zeros.  Written out,
+// not through p2_rows.h's pj_pair_words, pj_node_beside and pj_block_rows: through them this kernel measured 2 % slower on every
+// row of M24 (medians of five runs: 1.341 against 1.311 ms, 1.343 against 1.321, 1.333 against 1.314, 1.341 against 1.319).
 __global__ __launch_bounds__(64) void k_tree_blocks(uint32_t* __restrict__ data, uint32_t n, uint32_t h, uint32_t B, const uint32_t* __restrict__ ids,
                                                     const uint32_t* __restrict__ table, uint32_t first, uint32_t count, const uint32_t* __restrict__ nodes_before,
                                                     const uint32_t* __restrict__ nodes_after, size_t L, const uint32_t* __restrict__ rec, const uint32_t* __restrict__ tab) {
@@ -289,9 +266,9 @@ __global__ __launch_bounds__(PT_THREADS) void k_tree_book(uint32_t* __restrict__
     const uint32_t k = r % PJ_BLOCK, slot = r / PJ_BLOCK, id = ids[slot], half = 1u << (h - 1), m = rec[TR_PAIRS];
     const bool leaf = id >= half;
     uint32_t v = 0;
-    if (col == TD_ID) v = encode(id);
-    else if (col == TD_IDL) v = encode(2 * id);
-    else if (col == TD_IDR) v = encode(2 * id + 1);
+    if (col == TD_ID) v = pj_encode(id);
+    else if (col == TD_IDL) v = pj_encode(2 * id);
+    else if (col == TD_IDR) v = pj_encode(2 * id + 1);
     else if (col == TD_LEAF) v = leaf ? R1 : 0;
     else if (col == TD_UP) v = id > 1 ? R1 : 0;
     else if (col == TD_DL || col == TD_DR) {
@@ -305,30 +282,19 @@ __global__ __launch_bounds__(PT_THREADS) void k_tree_book(uint32_t* __restrict__
         const uint32_t lo = leaf ? (slot ? ids[slot - 1] + 1 : base) : (m ? ids[m - 1] + 1 : base);
         const uint32_t g = leaf ? id - lo : 0;
         if (col == TD_LO) {
-            v = encode(lo);
+            v = pj_encode(lo);
             if (r == 0) rec[TR_LO] = v;
             if (r == rows - 1) rec[TR_HI] = v;
         } else if (col == TD_GBIT) v = (k >= 1 && k <= PT_GAP_BITS && ((g >> (k - 1)) & 1)) ? R1 : 0;
-        else v = k == 0 ? 0 : encode(k <= PT_GAP_BITS ? g & ((1u << k) - 1) : g);
+        else v = k == 0 ? 0 : pj_encode(k <= PT_GAP_BITS ? g & ((1u << k) - 1) : g);
     }
     data[(size_t)col * n + r] = v;
-}
-
-inline bool tree_po2_ok(size_t po2, size_t zk_cycles) { return po2 >= 1 && po2 <= 30 && ((size_t)1 << po2) > zk_cycles + 1; }
-
-const char* tree_circuit_shape(const char* who, const zkh_circuit* c, size_t po2, size_t zk_cycles) {
-    ZKH_REQUIRE(c->kind == PT_KIND && c->group_size[GROUP_CODE] == PT_WC && c->group_size[GROUP_DATA] == PT_WD && c->group_size[GROUP_ACCUM] == PT_WA &&
-                c->global_size[GLOBAL_OUT] == PT_OUT, "%s: the circuit does not have P2-TREE's shape (kind %u, %u / %u / %u columns, %u outputs)", who, PT_KIND, PT_WC,
-                PT_WD, PT_WA, PT_OUT);
-    ZKH_REQUIRE(tree_po2_ok(po2, zk_cycles), "%s: po2 %zu out of range for %zu zk_cycles", who, po2, zk_cycles);
-    return nullptr;
 }
 
 // the image's shape -> h, B
 const char* tree_image_shape(const char* who, size_t po2, size_t zk_cycles, size_t W, uint32_t* h_out, uint32_t* B_out) {
     ZKH_REQUIRE(W > 16, "%s: an image of %zu words has a single pair of leaves (W > 16: the root block is not a pair block)", who, W);
-    uint32_t h = 0;
-    while (((size_t)1 << h) < image_leaves(W)) h++;
+    const uint32_t h = image_height(W);
     ZKH_REQUIRE(h >= PT_MIN_H && h <= PT_MAX_H, "%s: an image of %zu words has h %u (%u .. %u: ids and gaps stay below 2^%u)", who, W, h, PT_MIN_H, PT_MAX_H, PT_GAP_BITS);
     *h_out = h;
     *B_out = (uint32_t)((((size_t)1 << po2) - zk_cycles) / PJ_BLOCK);
@@ -341,7 +307,7 @@ const char* tree_image_shape(const char* who, size_t po2, size_t zk_cycles, size
 extern "C" const char* zkh_page_tree_code(zkh_ctx* ctx, const zkh_circuit* c, size_t po2, size_t zk_cycles, zkh_buf* code) {
     const char* who = "page_tree_code";
     ZKH_REQUIRE(ctx && c && code, "%s: null argument", who);
-    ZKH_TRY(tree_circuit_shape(who, c, po2, zk_cycles));
+    ZKH_TRY(page_circuit_shape(who, TREE, c, po2, zk_cycles));
     const size_t n = (size_t)1 << po2;
     ZKH_REQUIRE(code->len == (size_t)PT_WC * n, "%s: buffer shape mismatch", who);
     const uint32_t A = (uint32_t)(n - zk_cycles), B = A / PJ_BLOCK;
@@ -357,7 +323,7 @@ extern "C" const char* zkh_page_tree_plan(size_t po2, size_t zk_cycles, size_t i
                                           size_t* n_parts) {
     const char* who = "page_tree_plan";
     ZKH_REQUIRE((addrs || D == 0) && (parts || parts_cap == 0) && n_parts, "%s: null argument", who);
-    ZKH_REQUIRE(tree_po2_ok(po2, zk_cycles), "%s: po2 %zu out of range for %zu zk_cycles", who, po2, zk_cycles);
+    ZKH_REQUIRE(page_po2_ok(po2, zk_cycles), "%s: po2 %zu out of range for %zu zk_cycles", who, po2, zk_cycles);
     uint32_t h, B;
     ZKH_TRY(tree_image_shape(who, po2, zk_cycles, image_words, &h, &B));
     size_t count = 0, first = 0, nodes = 0;
@@ -387,28 +353,17 @@ extern "C" const char* zkh_page_tree_witgen(zkh_ctx* ctx, const zkh_circuit* c, 
                                             size_t proof_words, const zkh_buf* nodes_before, const zkh_buf* nodes_after, size_t first_row, size_t count_rows,
                                             zkh_buf* data, uint32_t out[18], const uint32_t* noise_key) {
     const char* who = "page_tree_witgen";
-    ZKH_REQUIRE(ctx && c && code && proof && nodes_before && nodes_after && data && out, "%s: null argument", who);
-    ZKH_TRY(tree_circuit_shape(who, c, po2, zk_cycles));
-    const size_t n = (size_t)1 << po2;
-    ZKH_REQUIRE(code->len == (size_t)PT_WC * n && data->len == (size_t)PT_WD * n, "%s: buffer shape mismatch", who);
-    ZKH_REQUIRE(proof_words <= proof->len && proof_words <= 0xffffffffull, "%s: a proof of %zu words in a buffer of %zu", who, proof_words, proof->len);
-    NoiseKey nk;
-    ZKH_TRY(resolve_noise_key(noise_key, &nk));
-    bind_thread(ctx);
-    uint32_t head[PROOF_HEAD_MAX] = {0};
-    ZKH_TRY(zkh_read(ctx, proof, head, 0, proof_words < PROOF_HEAD_MAX ? proof_words : PROOF_HEAD_MAX));
-    ZKH_TRY(image_proof_header(who, head, proof_words));
-    const uint32_t W = head[1], D = head[2];
     uint32_t h, B;
-    ZKH_TRY(tree_image_shape(who, po2, zk_cycles, W, &h, &B));
-    const size_t L = image_leaves(W);
-    ZKH_REQUIRE(nodes_before->len == 16 * L && nodes_after->len == 16 * L, "%s: nodes of %zu and %zu words; an image of %u words has a tree of %zu (zkh_image_tree_words)",
-                who, nodes_before->len, nodes_after->len, W, 16 * L);
+    PageOpen o;
+    ZKH_TRY(page_open(who, TREE, ctx, c, po2, zk_cycles, code, proof, proof_words, nodes_before, nodes_after, data, out, noise_key,
+                      [&](size_t W) { return tree_image_shape(who, po2, zk_cycles, W, &h, &B); }, &o));
+    const size_t n = o.n, L = o.L;
+    const uint32_t W = o.W, D = o.D, *table = o.table;
+    const NoiseKey& nk = o.nk;
     ZKH_REQUIRE(first_row <= D && count_rows <= D - first_row && (count_rows || D == 0), "%s: the part [%zu, %zu) of a table of %u rows (an empty part only of an empty table)",
                 who, first_row, first_row + count_rows, D);
     const uint32_t first = (uint32_t)first_row, count = (uint32_t)count_rows;     // 3 D words fit the proof: D < 2^31
     const uint32_t A = (uint32_t)(n - zk_cycles), rows = PJ_BLOCK * B;
-    const uint32_t* table = proof->ptr() + 5 + h;                      // 3 D words inside the proof: its length is what the header describes
     Tmp tab, rec, ids;
     ZKH_TRY(p2_rows_tables(ctx, tab));
     ZKH_TRY(new_buf(ctx, TR_WORDS, false, rec.out()));
@@ -439,15 +394,15 @@ extern "C" const char* zkh_page_tree_witgen(zkh_ctx* ctx, const zkh_circuit* c, 
         k_tree_book<<<dim3((rows + PT_THREADS - 1) / PT_THREADS, PT_WD - TD_ID), PT_THREADS, 0, ctx->stream>>>(data->ptr(), (uint32_t)n, h, B, ids->ptr(), table, first,
                                                                                                                count, rec->ptr());
         ZKH_TRY(last_launch_error("tree_book"));
-        if (rows < n) ZKH_TRY(page_tail_rows(ctx, data, PT_WD, n, A, rows, nk));
+        if (rows < n) {
+            p2_rows_tail(ctx, data, PT_WD, n, A, rows, nk);
+            ZKH_TRY(last_launch_error("page_tail"));
+        }
     }
     uint32_t r[TR_ROOTS + 16];
     ZKH_TRY(zkh_read(ctx, rec, r, 0, TR_ROOTS + 16));
-    if (r[TR_ROW] != NONE) {
-        if (r[TR_A] >= W) return make_err("%s: row %u: address %u outside the image of %u words", who, r[TR_ROW], r[TR_A], W);
-        return make_err("%s: row %u: address %u does not follow a smaller one (row %u: address %u)", who, r[TR_ROW], r[TR_A], r[TR_ROW] - 1, r[TR_BEFORE]);
-    }
-    ZKH_REQUIRE(r[TR_SPLIT] == NONE, "%s: the part [%u, %u) splits a pair of leaves: rows %u and %u write the same 16 words (zkh_page_tree_plan)", who, first,
+    ZKH_TRY(table_refusal(who, r, W));
+    ZKH_REQUIRE(r[TR_SPLIT] == PJ_NONE, "%s: the part [%u, %u) splits a pair of leaves: rows %u and %u write the same 16 words (zkh_page_tree_plan)", who, first,
                 first + count, r[TR_SPLIT] - 1, r[TR_SPLIT]);
     ZKH_REQUIRE(r[TR_NODES] <= B, "%s: the part [%u, %u) has %u%s dirty nodes, but po2 %zu leaves %u block slots (zkh_page_tree_plan)", who, first, first + count,
                 r[TR_NODES], r[TR_NODES] == 0xfffffffeu ? " or more" : "", po2, B);

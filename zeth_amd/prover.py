@@ -377,73 +377,70 @@ class SegmentProver:
         receipt.control_root = self.code_root(code, seg.po2)
         return receipt
 
+    def _seal_page_chain(self, who: str, segs, proof, proof_words: int, nodes_before, nodes_after, check: bool, open_chain, witgen, accum) -> list:
+        """Seal a page-out as a chain of parts: what seal_page_out_parts, seal_page_out_ordered and seal_page_out_tree share.  segs: one
+        Segment per part, all of one (po2, zk_cycles), each with its own noise seed; HalError if their number is not the plan's.
+        open_chain(proof, po2, zk, fit) -> (the code group, the plan: per part the witness call's own operands), made in the order in
+        which the kind's code call and plan refuse, with fit(plan, D, room) called where the kind compares the plan with the segments
+        (D: the table's rows; room: what a part holds, in words for the message).  witgen: the hal's witness call;
+        accum(seg, code, data) -> the accum group.  Both trees are the WHOLE page-out's for every part, so the parts could be sealed
+        in any order, or on several ranks.  The code group and its control root are built once and the data buffer is reused.
+        -> the receipts, in the order of the parts."""
+        segs = list(segs)
+        if not segs:
+            raise _hal.HalError(f"{who}: no segment")
+        po2, zk = segs[0].po2, segs[0].zk_cycles
+        if any((s.po2, s.zk_cycles) != (po2, zk) for s in segs):
+            raise _hal.HalError(f"{who}: the parts share one code group: every segment must have the same (po2, zk_cycles)")
+        if not isinstance(proof, _hal.Buffer):
+            proof = self.hal.copy_from("image_proof", np.ascontiguousarray(proof, dtype=np.uint32).reshape(-1))
+
+        def fit(plan, D, room):
+            if len(segs) != len(plan):
+                raise _hal.HalError(f"{who}: {len(segs)} segments, but a table of {D} rows takes {len(plan)} parts of {room} at po2 {po2}")
+
+        code, plan = open_chain(proof, po2, zk, fit)
+        control_root = self.code_root(code, po2)
+        data = self.hal.alloc_elem("data", self.group_sizes()[2] << po2)
+        receipts = []
+        for seg, part in zip(segs, plan):
+            out = witgen(self.circuit, po2, zk, code, proof, proof_words, nodes_before, nodes_after, *part, data, seg.noise_seed)
+            receipt = self.seal_with_accum(seg, code, data, out, accum(seg, code, data), check=check)
+            receipt.control_root = control_root.copy()
+            receipts.append(receipt)
+        return receipts
+
+    def _open_path_chain(self, code_call):
+        """open_chain of the circuits that lay out one path per update: the plan is p2_page.parts, a part's operand its first update"""
+        def open_chain(proof, po2, zk, fit):
+            from .circuits import p2_page
+            header = proof.slice(0, min(3, proof.size())).to_vec()
+            W, D = (int(header[1]), int(header[2])) if header.size > 2 else (0, 0)
+            code = code_call(self.circuit, po2, zk, W)                         # refuses a shape without a path slot (P2-PAGE-ordered: and h > 26)
+            plan = [(first,) for first, _count in p2_page.parts(po2, zk, W, D)]
+            fit(plan, D, f"{self.hal.page_circuit_slots(po2, zk, W)} slots")
+            return code, plan
+        return open_chain
+
     def seal_page_out_parts(self, segs, proof, proof_words: int, nodes_before, nodes_after, check: bool = False) -> list:
         """Seal a page-out of ANY size with P2-PAGE as a chain of parts (circuits/p2_page.py `parts`): part p lays out the updates
         [first, first + count) of the ZKU1 proof's table (zkh_page_circuit_witgen_part), and its receipt's output is the root before
         update `first` ‖ the root after the part's last update, so part p + 1 opens the root part p left (`verify_page_out_chain`).
-        segs: one Segment per part, all of one (po2, zk_cycles), each with its own noise seed; HalError if their number is not the
-        plan's.  The other operands are seal_page_out's; both trees are the WHOLE page-out's for every part, so the parts could be
-        sealed in any order, or on several ranks.  The code group and its control root are built once and the data buffer is reused.
-        -> the receipts, in the order of the parts."""
-        from .circuits import p2_page
-        segs = list(segs)
-        if not segs:
-            raise _hal.HalError("seal_page_out_parts: no segment")
-        po2, zk = segs[0].po2, segs[0].zk_cycles
-        if any((s.po2, s.zk_cycles) != (po2, zk) for s in segs):
-            raise _hal.HalError("seal_page_out_parts: the parts share one code group: every segment must have the same (po2, zk_cycles)")
-        if not isinstance(proof, _hal.Buffer):
-            proof = self.hal.copy_from("image_proof", np.ascontiguousarray(proof, dtype=np.uint32).reshape(-1))
-        header = proof.slice(0, min(3, proof.size())).to_vec()
-        W, D = (int(header[1]), int(header[2])) if header.size > 2 else (0, 0)
-        wa, wc, wd = self.group_sizes()
-        code = self.hal.page_circuit_code(self.circuit, po2, zk, W)            # refuses a shape without a path slot
-        plan = p2_page.parts(po2, zk, W, D)
-        if len(segs) != len(plan):
-            raise _hal.HalError(f"seal_page_out_parts: {len(segs)} segments, but a table of {D} rows takes {len(plan)} parts of "
-                                f"{self.hal.page_circuit_slots(po2, zk, W)} slots at po2 {po2}")
-        control_root = self.code_root(code, po2)
-        data = self.hal.alloc_elem("data", wd << po2)
-        receipts = []
-        for seg, (first, _count) in zip(segs, plan):
-            out = self.hal.page_circuit_witgen_part(self.circuit, po2, zk, code, proof, proof_words, nodes_before, nodes_after, first, data, seg.noise_seed)
-            receipt = self.seal_with_accum(seg, code, data, out, self.syn_accumulate(seg, data), check=check)
-            receipt.control_root = control_root.copy()
-            receipts.append(receipt)
-        return receipts
+        segs: one Segment per part (_seal_page_chain); the other operands are seal_page_out's.  -> the receipts, in the order of the
+        parts."""
+        return self._seal_page_chain("seal_page_out_parts", segs, proof, proof_words, nodes_before, nodes_after, check,
+                                     self._open_path_chain(self.hal.page_circuit_code), self.hal.page_circuit_witgen_part,
+                                     lambda seg, code, data: self.syn_accumulate(seg, data))
 
     def seal_page_out_ordered(self, segs, proof, proof_words: int, nodes_before, nodes_after, check: bool = False) -> list:
         """Seal a page-out of any size with P2-PAGE-ordered (this prover's circuit: circuits/p2_page_ordered.py) as a chain of parts:
         seal_page_out_parts with the order of the addresses constrained.  Part p's receipt's output is root_before ‖ root_after ‖ lo ‖
         hi of its run of updates (zkh_page_ordered_witgen), so part p + 1 opens the root and starts at the `hi` part p left
-        (`verify_page_ordered_chain`).  The operands and the plan (p2_page.parts) are seal_page_out_parts'; one code group, one
-        control root, one data buffer.  -> the receipts, in the order of the parts."""
-        from .circuits import p2_page
-        segs = list(segs)
-        if not segs:
-            raise _hal.HalError("seal_page_out_ordered: no segment")
-        po2, zk = segs[0].po2, segs[0].zk_cycles
-        if any((s.po2, s.zk_cycles) != (po2, zk) for s in segs):
-            raise _hal.HalError("seal_page_out_ordered: the parts share one code group: every segment must have the same (po2, zk_cycles)")
-        if not isinstance(proof, _hal.Buffer):
-            proof = self.hal.copy_from("image_proof", np.ascontiguousarray(proof, dtype=np.uint32).reshape(-1))
-        header = proof.slice(0, min(3, proof.size())).to_vec()
-        W, D = (int(header[1]), int(header[2])) if header.size > 2 else (0, 0)
-        wa, wc, wd = self.group_sizes()
-        code = self.hal.page_ordered_code(self.circuit, po2, zk, W)            # refuses a shape without a path slot, and h > 26
-        plan = p2_page.parts(po2, zk, W, D)
-        if len(segs) != len(plan):
-            raise _hal.HalError(f"seal_page_out_ordered: {len(segs)} segments, but a table of {D} rows takes {len(plan)} parts of "
-                                f"{self.hal.page_circuit_slots(po2, zk, W)} slots at po2 {po2}")
-        control_root = self.code_root(code, po2)
-        data = self.hal.alloc_elem("data", wd << po2)
-        receipts = []
-        for seg, (first, _count) in zip(segs, plan):
-            out = self.hal.page_ordered_witgen(self.circuit, po2, zk, code, proof, proof_words, nodes_before, nodes_after, first, data, seg.noise_seed)
-            receipt = self.seal_with_accum(seg, code, data, out, self.syn_accumulate(seg, data), check=check)
-            receipt.control_root = control_root.copy()
-            receipts.append(receipt)
-        return receipts
+        (`verify_page_ordered_chain`).  The operands and the plan (p2_page.parts) are seal_page_out_parts'.  -> the receipts, in the
+        order of the parts."""
+        return self._seal_page_chain("seal_page_out_ordered", segs, proof, proof_words, nodes_before, nodes_after, check,
+                                     self._open_path_chain(self.hal.page_ordered_code), self.hal.page_ordered_witgen,
+                                     lambda seg, code, data: self.syn_accumulate(seg, data))
 
     def seal_page_out_tree(self, segs, proof, proof_words: int, nodes_before, nodes_after, check: bool = False) -> list:
         """Seal a page-out of any size with P2-TREE (this prover's circuit: circuits/p2_tree.py, built with arguments=p2_tree.arguments())
@@ -451,42 +448,71 @@ class SegmentProver:
         root_before ‖ root_after ‖ lo ‖ hi of its run of pairs of leaves (zkh_page_tree_witgen), so part p + 1 opens the root and
         starts at the `hi` part p left (`verify_page_tree_chain`).  The plan is zkh_page_tree_plan's over the table's addresses, read
         back once (D words).  The accum group is the circuit's bus (args_accumulate): a table that does not match the trees is refused
-        there, and check=True names the key.  The other operands are seal_page_out_parts'; one code group, one control root (it does
-        not depend on the image's size), one data buffer.  -> the receipts, in the order of the parts."""
-        segs = list(segs)
-        if not segs:
-            raise _hal.HalError("seal_page_out_tree: no segment")
-        po2, zk = segs[0].po2, segs[0].zk_cycles
-        if any((s.po2, s.zk_cycles) != (po2, zk) for s in segs):
-            raise _hal.HalError("seal_page_out_tree: the parts share one code group: every segment must have the same (po2, zk_cycles)")
-        if not self.circuit.has_arguments():
-            raise _hal.HalError("seal_page_out_tree: the prover was built without P2-TREE's arguments (arguments=p2_tree.arguments())")
-        if not isinstance(proof, _hal.Buffer):
-            proof = self.hal.copy_from("image_proof", np.ascontiguousarray(proof, dtype=np.uint32).reshape(-1))
-        header = proof.slice(0, min(5, proof.size())).to_vec()
-        W, D, h = (int(header[1]), int(header[2]), int(header[4])) if header.size > 4 else (0, 0, 0)
-        if 5 + h + 3 * D > min(proof_words, proof.size()):
-            raise _hal.HalError(f"seal_page_out_tree: a proof of {proof_words} words does not hold its header and a table of {D} rows")
-        addrs = proof.slice(5 + h, 3 * D).to_vec()[::3] if D else np.zeros(0, dtype=np.uint32)
-        plan = self.hal.page_tree_plan(po2, zk, W, addrs)                      # refuses W <= 16, B < h, addresses out of order
-        if len(segs) != len(plan):
-            raise _hal.HalError(f"seal_page_out_tree: {len(segs)} segments, but a table of {D} rows takes {len(plan)} parts of "
-                                f"{((1 << po2) - zk) // 31} block slots at po2 {po2}")
-        wa, wc, wd = self.group_sizes()
-        code = self.hal.page_tree_code(self.circuit, po2, zk)
-        control_root = self.code_root(code, po2)
-        data = self.hal.alloc_elem("data", wd << po2)
-        receipts = []
-        for seg, (first, count) in zip(segs, plan):
-            out = self.hal.page_tree_witgen(self.circuit, po2, zk, code, proof, proof_words, nodes_before, nodes_after, first, count, data, seg.noise_seed)
-            receipt = self.seal_with_accum(seg, code, data, out, self.args_accumulate(seg, code, data, check=check), check=check)
-            receipt.control_root = control_root.copy()
-            receipts.append(receipt)
-        return receipts
+        there, and check=True names the key.  The other operands are seal_page_out_parts'; the control root does not depend on the
+        image's size.  -> the receipts, in the order of the parts."""
+        who = "seal_page_out_tree"
+
+        def open_chain(proof, po2, zk, fit):
+            if not self.circuit.has_arguments():
+                raise _hal.HalError(f"{who}: the prover was built without P2-TREE's arguments (arguments=p2_tree.arguments())")
+            header = proof.slice(0, min(5, proof.size())).to_vec()
+            W, D, h = (int(header[1]), int(header[2]), int(header[4])) if header.size > 4 else (0, 0, 0)
+            if 5 + h + 3 * D > min(proof_words, proof.size()):
+                raise _hal.HalError(f"{who}: a proof of {proof_words} words does not hold its header and a table of {D} rows")
+            addrs = proof.slice(5 + h, 3 * D).to_vec()[::3] if D else np.zeros(0, dtype=np.uint32)
+            plan = self.hal.page_tree_plan(po2, zk, W, addrs)                  # refuses W <= 16, B < h, addresses out of order
+            fit(plan, D, f"{((1 << po2) - zk) // 31} block slots")
+            return self.hal.page_tree_code(self.circuit, po2, zk), plan
+
+        return self._seal_page_chain(who, segs, proof, proof_words, nodes_before, nodes_after, check, open_chain, self.hal.page_tree_witgen,
+                                     lambda seg, code, data: self.args_accumulate(seg, code, data, check=check))
+
 
     def prove_segment(self, seg: Segment) -> SegmentReceipt:
         code, data, out = self.witgen(seg)
         return self.seal(seg, code, data, out)
+
+
+def link_page_parts(who: str, parts, root_before=None, first_lo=None, last_hi=None) -> tuple:
+    """The links of a chain of page-out seals, HOST ONLY: what verify_page_out_chain, verify_page_ordered_chain and
+    link_page_tree_chain check once a seal is verified -> (root_before, root_after) of the whole page-out, and hi where the parts have
+    one.  parts: per part (the root it opens, the root it leaves) or (…, lo, hi), lo and hi as integers; an iterator is consumed part
+    by part, so a caller may verify each seal as it hands it over.  who: the prefix of every message.  Part p + 1 must open the root
+    part p left; with a `root_before`, part 0 must open it.  Parts with lo and hi: every lo and hi must be at most 2^29 (what the
+    circuits' 29-bit gaps are sound for); part p + 1 must start at the hi part p left; first_lo = (the lo part 0 must have, the words
+    that say why); last_hi, if given = (the bound of the last hi, the words that say why).  Raises HalError, one message per cause."""
+    from .circuits.p2_blocks import GAP_BITS
+    fmt = lambda r: " ".join(f"{int(w):08x}" for w in r)
+    chain = []
+    for p, part in enumerate(parts):
+        for name, v in zip(("lo", "hi"), part[2:]):
+            if v > 1 << GAP_BITS:
+                raise _hal.HalError(f"{who}: part {p}: {name} {v} is above 2^{GAP_BITS}, the bound the order check is sound for")
+        chain.append((np.array(part[0], dtype=np.uint32), np.array(part[1], dtype=np.uint32)) + tuple(part[2:]))
+    if not chain:
+        raise _hal.HalError(f"{who}: no receipt (a page-out of no rows still has one part)")
+    ordered = len(chain[0]) > 2
+    if ordered and chain[0][2] != first_lo[0]:
+        raise _hal.HalError(f"{who}: part 0 starts at lo {chain[0][2]}, not {first_lo[1]}")
+    if root_before is not None and not np.array_equal(chain[0][0], np.asarray(root_before, dtype=np.uint32)):
+        raise _hal.HalError(f"{who}: part 0 opens root {fmt(chain[0][0])}, not root_before {fmt(root_before)}")
+    for p in range(len(chain) - 1):
+        if not np.array_equal(chain[p + 1][0], chain[p][1]):
+            raise _hal.HalError(f"{who}: part {p + 1} opens root {fmt(chain[p + 1][0])}, but part {p} left root {fmt(chain[p][1])}")
+        if ordered and chain[p + 1][2] != chain[p][3]:
+            raise _hal.HalError(f"{who}: part {p + 1} starts at lo {chain[p + 1][2]}, but part {p} left hi {chain[p][3]}")
+    if ordered and last_hi is not None and chain[-1][3] > last_hi[0]:
+        raise _hal.HalError(f"{who}: the last part leaves hi {chain[-1][3]}, above {last_hi[1]}")
+    return (chain[0][0], chain[-1][1]) + chain[-1][3:]
+
+
+def _verified_parts(receipts, desc, control_root, decode=None):
+    """per receipt, once its seal is verified against the description desc() and `control_root`: the operands of link_page_parts"""
+    hc = None
+    for r in receipts:
+        hc = hc or _hal.HostCircuit(desc())
+        hc.verify_segment(r.seal, control_root)
+        yield (r.seal[:8], r.seal[8:16]) + ((decode(r.seal[16]), decode(r.seal[17])) if decode else ())
 
 
 def verify_page_out_chain(receipts, control_root, root_before=None) -> Tuple[np.ndarray, np.ndarray]:
@@ -495,21 +521,7 @@ def verify_page_out_chain(receipts, control_root, root_before=None) -> Tuple[np.
     parts); part p + 1 must open the root part p left; with a `root_before`, part 0 must open it.  Raises HalError on a seal the
     verifier rejects, on a chain that does not link, on another first root, and on an empty list."""
     from .circuits import p2_page
-    receipts = list(receipts)
-    if not receipts:
-        raise _hal.HalError("verify_page_out_chain: no receipt (a page-out of no rows still has one part)")
-    hc = _hal.HostCircuit(p2_page.p2_page_circuit())
-    fmt = lambda r: " ".join(f"{int(w):08x}" for w in r)
-    roots = []
-    for r in receipts:
-        hc.verify_segment(r.seal, control_root)
-        roots.append((np.array(r.seal[:8], dtype=np.uint32), np.array(r.seal[8:16], dtype=np.uint32)))
-    if root_before is not None and not np.array_equal(roots[0][0], np.asarray(root_before, dtype=np.uint32)):
-        raise _hal.HalError(f"verify_page_out_chain: part 0 opens root {fmt(roots[0][0])}, not root_before {fmt(root_before)}")
-    for p in range(len(roots) - 1):
-        if not np.array_equal(roots[p + 1][0], roots[p][1]):
-            raise _hal.HalError(f"verify_page_out_chain: part {p + 1} opens root {fmt(roots[p + 1][0])}, but part {p} left root {fmt(roots[p][1])}")
-    return roots[0][0], roots[-1][1]
+    return link_page_parts("verify_page_out_chain", _verified_parts(receipts, p2_page.p2_page_circuit, control_root), root_before)
 
 
 def verify_page_ordered_chain(receipts, control_root, root_before=None) -> Tuple[np.ndarray, np.ndarray, int]:
@@ -519,29 +531,8 @@ def verify_page_ordered_chain(receipts, control_root, root_before=None) -> Tuple
     to at most 2^29 (what the circuit's 29-bit gaps are sound for); part 0 must have lo = 0; part p + 1 must open the root part p left
     and start at the hi part p left; with a `root_before`, part 0 must open it.  Raises HalError, one message per cause."""
     from .circuits import p2_page_ordered as po
-    receipts = list(receipts)
-    if not receipts:
-        raise _hal.HalError("verify_page_ordered_chain: no receipt (a page-out of no rows still has one part)")
-    hc = _hal.HostCircuit(po.p2_page_ordered_circuit())
-    fmt = lambda r: " ".join(f"{int(w):08x}" for w in r)
-    parts = []
-    for p, r in enumerate(receipts):
-        hc.verify_segment(r.seal, control_root)
-        lo, hi = po.decode(r.seal[po.OUT_LO]), po.decode(r.seal[po.OUT_HI])
-        for name, v in (("lo", lo), ("hi", hi)):
-            if v > 1 << po.GAP_BITS:
-                raise _hal.HalError(f"verify_page_ordered_chain: part {p}: {name} {v} is above 2^{po.GAP_BITS}, the bound the order check is sound for")
-        parts.append((np.array(r.seal[:8], dtype=np.uint32), np.array(r.seal[8:16], dtype=np.uint32), lo, hi))
-    if parts[0][2] != 0:
-        raise _hal.HalError(f"verify_page_ordered_chain: part 0 starts at lo {parts[0][2]}, not 0: addresses below it are not covered")
-    if root_before is not None and not np.array_equal(parts[0][0], np.asarray(root_before, dtype=np.uint32)):
-        raise _hal.HalError(f"verify_page_ordered_chain: part 0 opens root {fmt(parts[0][0])}, not root_before {fmt(root_before)}")
-    for p in range(len(parts) - 1):
-        if not np.array_equal(parts[p + 1][0], parts[p][1]):
-            raise _hal.HalError(f"verify_page_ordered_chain: part {p + 1} opens root {fmt(parts[p + 1][0])}, but part {p} left root {fmt(parts[p][1])}")
-        if parts[p + 1][2] != parts[p][3]:
-            raise _hal.HalError(f"verify_page_ordered_chain: part {p + 1} starts at lo {parts[p + 1][2]}, but part {p} left hi {parts[p][3]}")
-    return parts[0][0], parts[-1][1], parts[-1][3]
+    return link_page_parts("verify_page_ordered_chain", _verified_parts(receipts, po.p2_page_ordered_circuit, control_root, po.decode), root_before,
+                           first_lo=(0, "0: addresses below it are not covered"))
 
 
 def link_page_tree_chain(outs, h: int, root_before=None) -> Tuple[np.ndarray, np.ndarray, int]:
@@ -553,29 +544,9 @@ def link_page_tree_chain(outs, h: int, root_before=None) -> Tuple[np.ndarray, np
     who = "verify_page_tree_chain"
     if not pt.MIN_H <= h <= pt.MAX_H:
         raise _hal.HalError(f"{who}: h {h} ({pt.MIN_H} .. {pt.MAX_H})")
-    fmt = lambda r: " ".join(f"{int(w):08x}" for w in r)
-    parts = []
-    for p, out in enumerate(outs):
-        out = np.asarray(out, dtype=np.uint32)
-        lo, hi = pt.decode(out[pt.OUT_LO]), pt.decode(out[pt.OUT_HI])
-        for name, v in (("lo", lo), ("hi", hi)):
-            if v > 1 << pt.GAP_BITS:
-                raise _hal.HalError(f"{who}: part {p}: {name} {v} is above 2^{pt.GAP_BITS}, the bound the order check is sound for")
-        parts.append((out[:8].copy(), out[8:16].copy(), lo, hi))
-    if not parts:
-        raise _hal.HalError(f"{who}: no receipt (a page-out of no rows still has one part)")
-    if parts[0][2] != 1 << (h - 1):
-        raise _hal.HalError(f"{who}: part 0 starts at lo {parts[0][2]}, not 2^{h - 1} = {1 << (h - 1)}, the id of the first pair of leaves of a tree of height {h}")
-    if root_before is not None and not np.array_equal(parts[0][0], np.asarray(root_before, dtype=np.uint32)):
-        raise _hal.HalError(f"{who}: part 0 opens root {fmt(parts[0][0])}, not root_before {fmt(root_before)}")
-    for p in range(len(parts) - 1):
-        if not np.array_equal(parts[p + 1][0], parts[p][1]):
-            raise _hal.HalError(f"{who}: part {p + 1} opens root {fmt(parts[p + 1][0])}, but part {p} left root {fmt(parts[p][1])}")
-        if parts[p + 1][2] != parts[p][3]:
-            raise _hal.HalError(f"{who}: part {p + 1} starts at lo {parts[p + 1][2]}, but part {p} left hi {parts[p][3]}")
-    if parts[-1][3] > 1 << h:
-        raise _hal.HalError(f"{who}: the last part leaves hi {parts[-1][3]}, above 2^{h} = {1 << h}: a pair block outside a tree of height {h}")
-    return parts[0][0], parts[-1][1], parts[-1][3]
+    parts = ((out[:8], out[8:16], pt.decode(out[pt.OUT_LO]), pt.decode(out[pt.OUT_HI])) for out in outs)
+    return link_page_parts(who, parts, root_before, first_lo=(1 << (h - 1), f"2^{h - 1} = {1 << (h - 1)}, the id of the first pair of leaves of a tree of height {h}"),
+                           last_hi=(1 << h, f"2^{h} = {1 << h}: a pair block outside a tree of height {h}"))
 
 
 def verify_page_tree_chain(receipts, control_root, h: int, root_before=None) -> Tuple[np.ndarray, np.ndarray, int]:
