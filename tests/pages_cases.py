@@ -1,6 +1,8 @@
 """What the paging tests share (tests/test_logup_pages.py, tests/test_logup_pages_gpu.py; imported the way args_gpu is): hand-built load /
 store traces over a memory image under one paged LINK record and its PAGES record (ZKA1 version 7), as test_logup_reads_gpu.py's `_case`
-builds them for the read rule."""
+builds them for the read rule.  And the SEAM TABLES (seam_table) of the page-out's proof, walk and tree update (tests/test_image_proof.py,
+test_image_proof_gpu.py, test_image_walk_gpu.py, test_image_tree_gpu.py): hand-made page tables that put a head decision of the
+compactions on the seam between two workgroups of 256 lanes."""
 import numpy as np
 
 from conftest import rand_fp
@@ -140,3 +142,31 @@ def walk(code, data, image, A, kind, memory=None):
             out[GAP0 + j][i] = (gap >> (8 * j)) % 256 * ONE % P
         below = a
     return out, {a: v[0] for a, v in mem.items()}
+
+
+SEAM_TABLES = ["seam_leaf", "seam_pair", "seam_new"]
+SEAM_ROWS = [256, 257, 513]                     # the table ends on the seam; one row past it; a second seam under random rows
+
+
+def seam_table(what, D, W, rng):
+    """-> D sorted, distinct addresses below W (an image of at least 512 leaves), random except around rows 255 and 256: the last lane of
+    workgroup 0 and lane 0 of workgroup 1 of every kernel that takes a row per lane, 256 lanes a workgroup.  `seam_leaf`: the two rows
+    are words 3 and 4 of one leaf (lane 0 of workgroup 1 is no head of the leaf list); `seam_pair`: they lie in the leaves 2 q and
+    2 q + 1 (a head of the leaf list, no head of the parents'); `seam_new`: in the leaves 2 q + 1 and 2 q + 2, under different parents
+    (a head of both).  Rows [0, 255) lie in distinct leaves, so row 256's leaf is item 255 or 256 of the leaf list as well."""
+    assert what in SEAM_TABLES and D >= 256
+    above = max(D - 257, 0)                                                  # the random rows past row 256
+    j = int(rng.integers(256, (W + 7) // 8 - 3 - (above + 7) // 8))          # row 255's leaf: 255 leaves below it, room above row 256's
+    if what == "seam_leaf":
+        lo, hi = 8 * j + 3, 8 * j + 4
+    else:
+        j = j & ~1 if what == "seam_pair" else j | 1
+        lo, hi = 8 * j + int(rng.integers(0, 8)), 8 * (j + 1) + int(rng.integers(0, 8))
+    below = 8 * np.sort(rng.choice(j, 255, replace=False)).astype(np.int64) + rng.integers(0, 8, 255)
+    after = hi + 1 + np.sort(rng.choice(W - hi - 1, above, replace=False)).astype(np.int64)
+    addrs = np.concatenate([below, [lo, hi], after]).astype(np.int64)[:D]
+    assert len(addrs) == D and (np.diff(addrs) > 0).all() and addrs[-1] < W and addrs[255] == lo and len(np.unique(addrs[:256] >> 3)) == 256
+    if D > 256:
+        same_leaf, same_parent = (lo >> 3) == (hi >> 3), (lo >> 4) == (hi >> 4)
+        assert addrs[256] == hi and (same_leaf, same_parent) == {"seam_leaf": (True, True), "seam_pair": (False, True), "seam_new": (False, False)}[what]
+    return addrs

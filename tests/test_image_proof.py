@@ -102,6 +102,23 @@ def test_both_verifiers_reach_the_root_of_the_paged_out_image(args, W, what):
     assert np.array_equal(_both(proof, nodes[1]), logup.reference_image_tree(after)[1])
 
 
+@pytest.mark.parametrize("D", pc.SEAM_ROWS)
+@pytest.mark.parametrize("what", pc.SEAM_TABLES)
+def test_both_verifiers_walk_the_seam_tables(args, what, D):
+    """rows 255 and 256 on the seam between two workgroups of the device's kernels (pages_cases.seam_table), W = 4096 (L = 512, h = 9):
+    the proofs the GPU modules compare against pass both host verifiers first"""
+    W = 4096
+    rng = np.random.default_rng(D + len(what))
+    image = _words(rng, W, big=True)
+    addrs = pc.seam_table(what, D, W, rng)
+    out = _words(rng, D, big=True)
+    nodes = logup.reference_image_tree(image)
+    proof = logup.reference_page_out_proof(args, PO2, 0, _table(image, addrs, out), W, nodes)
+    assert list(proof[1:5]) == [W, D, len(np.unique(addrs >> 3)), 9]
+    image[addrs] = out
+    assert np.array_equal(_both(proof, nodes[1]), logup.reference_image_root(image))
+
+
 def test_raw_words_above_p_give_the_proof_of_their_residues(args):
     W = 1000
     image, addrs, out, nodes, proof, after = _case(args, W, "five", seed=7, big=True)

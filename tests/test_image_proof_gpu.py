@@ -1,11 +1,12 @@
-"""The update's proof on the GPU (zkh_page_out_proof; csrc/image.hip, the check pass of csrc/links.hip): the ZKU1 proof built on the
+"""The update's proof on the GPU (zkh_page_out_proof; csrc/image.hip, the check pass of csrc/page_out.hip): the ZKU1 proof built on the
 device equals logup.reference_page_out_proof word for word, the reference reading the `nodes` that the device committed; the call leaves
 data, image and nodes as they were, writes no word past the proof's length, and the host verifier (zkh_image_proof_verify) walks the
 proof from the root before to the root that zkh_page_out_tree leaves.
 
 Through the real derive: every kind of pages_cases at two sizes.  Hand-made tables (p_on, p_addr, p_in = the image's word, p_out) over the
 image of 2^22 - 3 words (L = 2^19: for more than 1024 rows nine layers of three launches each, then the top kernel), over 8189 words (L = 2^10: the whole tree
-inside the top kernel), over 9 words (h = 1) and 8 words (L = 1: no layer).
+inside the top kernel), over 9 words (h = 1) and 8 words (L = 1: no layer); and the seam tables of pages_cases over 4096 words (L = 512), whose
+rows 255 and 256 put a head decision of the leaf compaction on the seam between two workgroups.
 
 Mutants these cases are meant to catch:
   * a carry dropped at a scan-workgroup boundary, in either run of the packed scan: `spread` and `twins` on the big image (24 workgroups);
@@ -100,7 +101,7 @@ def images(hal):
     """W -> (image, nodes): a third of the words raw words >= P, the nodes committed on the device and read back once; the tests upload
     their own copies"""
     out = {}
-    for W in (BIG_W, 8189, 9, 8):
+    for W in (BIG_W, 8189, 4096, 9, 8):
         image = _words(np.random.default_rng(W), W)
         out[W] = (image, hal.image_commit(_image(hal, image)).to_vec())
     return out
@@ -114,8 +115,10 @@ def _table(po2, image, addrs, out):
     return data.reshape(-1)
 
 
-def _addresses(what, W, A, rng):
+def _addresses(what, W, A, rng, rows=None):
     L = logup.image_tree_leaves(W)
+    if what in pc.SEAM_TABLES:
+        return pc.seam_table(what, rows, W, rng)
     if what == "spread":
         return np.sort(rng.choice(W, min(A, 3 * W // 4), replace=False)).astype(np.int64)
     if what == "twins":                                                      # 8 j and 8 j + 7 of the leaves 2 q and 2 q + 1
@@ -132,11 +135,11 @@ def _addresses(what, W, A, rng):
     return 8 * np.arange(L, dtype=np.int64)
 
 
-def _run_table(hal, images, W, what, po2, zk, seed=5, walk=True):
+def _run_table(hal, images, W, what, po2, zk, seed=5, walk=True, rows=None):
     image0, nodes0 = images[W]
     A = (1 << po2) - zk
     rng = np.random.default_rng(seed)
-    addrs = _addresses(what, W, A, rng)
+    addrs = _addresses(what, W, A, rng, rows)
     D = len(addrs)
     assert D <= A and (D < 2 or (np.diff(addrs) > 0).all()) and (D == 0 or addrs[-1] < W)
     out = _words(rng, D)
@@ -201,6 +204,17 @@ def test_a_tree_inside_the_top_kernel(hal, images, what):
         assert c == [2] * 9 + [0]
     if what == "one":
         assert c == [1] * 10
+
+
+@pytest.mark.parametrize("D", pc.SEAM_ROWS)
+@pytest.mark.parametrize("what", pc.SEAM_TABLES)
+def test_a_head_on_the_seam_of_two_workgroups(hal, images, what, D):
+    """rows 255 and 256 share a leaf, lie in sibling leaves, or lie under different parents: lane 0 of the second workgroup is no head
+    of the leaf list, or one; 984 active rows"""
+    proof, prof, c = _run_table(hal, images, 4096, what, 10, 40, seed=D, rows=D)
+    assert [int(x) for x in proof[1:3]] == [4096, D] and int(proof[4]) == 9 and {"proof_table", "proof_leaves", "proof_top"} <= set(prof)
+    if D == 257:                                                             # the two rows of the seam: one leaf, or two
+        assert int(proof[3]) == (256 if what == "seam_leaf" else 257)
 
 
 @pytest.mark.parametrize("W", [9, 8])

@@ -7,7 +7,8 @@ Commit: W = 1, 7, 8, 9 (one leaf, a partial leaf, two leaves), 650 and 1000 (par
 the root).  Page-out through the real derive: every kind of pages_cases at two sizes, and a second segment from the paged-out image.
 The listed route: hand-made page tables (zkh_page_out reads p_on, p_addr and p_out alone) over the image of 2^22 - 3 words, whose
 parent layers of 2^18, 2^17 and 2^16 nodes lie above the width the 8-lane kernels rebuild densely; po2 13 with 1994 blinding rows gives
-6198 table rows, past one 4096-item tile and past 24 scan workgroups.
+6198 table rows, past one 4096-item tile and past 24 scan workgroups.  The seam tables of pages_cases put rows 255 and 256, the two
+sides of the seam between two scan workgroups, into one leaf, into sibling leaves and under different parents.
 
 Mutants these cases are meant to catch (the case named is the one whose reference words the mutant cannot produce):
   * raw words hashed instead of residues: `big` of test_commit_matches_the_reference; `spread` and `twins` (a third of the image and of
@@ -176,8 +177,10 @@ def _table(po2, addrs, out):
     return data.reshape(-1)
 
 
-def _addresses(what, A, rng):
+def _addresses(what, A, rng, rows=None):
     L = 1 << 19
+    if what in pc.SEAM_TABLES:
+        return pc.seam_table(what, rows, BIG_W, rng)
     if what == "spread":
         return np.sort(rng.choice(BIG_W, A, replace=False)).astype(np.int64)
     if what == "twins":                                                      # 8 j and 8 j + 7 of the leaves 2 q and 2 q + 1, A // 4 pairs of leaves
@@ -194,11 +197,11 @@ def _addresses(what, A, rng):
     return 8 * np.arange(L, dtype=np.int64)
 
 
-def _run_table(hal, big, what, po2, zk, seed=5):
+def _run_table(hal, big, what, po2, zk, seed=5, rows=None):
     image0, nodes0 = big
     A = (1 << po2) - zk
     rng = np.random.default_rng(seed)
-    addrs = _addresses(what, A, rng)
+    addrs = _addresses(what, A, rng, rows)
     D = len(addrs)
     assert D <= A and (D < 2 or (np.diff(addrs) > 0).all()) and (D == 0 or addrs[-1] < BIG_W)
     out = _words(rng, D)
@@ -229,6 +232,15 @@ def test_a_hand_made_table_leaves_the_nodes_of_a_fresh_commit(hal, big, what):
     if what in ("spread", "edges"):                                          # no threshold sends these to the dense path
         assert "image_list" in prof and prof["image_sparse"]["calls"] >= 2, prof
         assert D == {"spread": 6198, "edges": 2}[what]
+
+
+@pytest.mark.parametrize("D", pc.SEAM_ROWS)
+@pytest.mark.parametrize("what", pc.SEAM_TABLES)
+def test_a_head_on_the_seam_of_two_workgroups(hal, big, what, D):
+    """lane 0 of the second scan workgroup is no head of the first list of dirty parents (rows 255 and 256 in one leaf or in sibling
+    leaves), or it is one (different parents): the listed route still leaves the nodes of a fresh commit"""
+    prof, got, rows = _run_table(hal, big, what, 10, 40, seed=D, rows=D)
+    assert rows == D and "image_list" in prof and not np.array_equal(got[8:16], big[1][8:16])
 
 
 def test_every_leaf_dirty(hal, big):

@@ -9,6 +9,7 @@ Shapes: W in {1, 7, 8, 9, 650, 1025} (L = 1: the leaf is the root; h = 1; partia
 W = 2^17 + 5 (ceil(W / 8) = 2^14 + 1, so L = 2^15 and h = 15: lists of many workgroups).  Every layer takes the same four launches whatever its list holds, so the only
 constant that switches a path is the workgroup size, 256: of the items of a list (flags, parents) and of the hashing lanes, two per
 parent (128 parents).  Lists of 127 .. 129 and 255 .. 257 items that keep their count over many layers stand on both sides of each.
+The seam tables of pages_cases (W = 4096) put a head decision of the row kernel, and of the flags of layer 0, on lane 0 of the second workgroup.
 
 Mutants these cases are meant to catch: a carry dropped between scan workgroups (spread, twins, all at the big shape); the sibling on
 the wrong side of an odd node, or taken when both children are dirty (twins, all, edges); old and new digests swapped or the new leaf
@@ -212,6 +213,24 @@ def test_layers_of_many_workgroups(hal, args, big, what):
     after = image.copy()
     after[addrs] = out
     assert msg is None and np.array_equal(root, hal.image_root(hal.image_commit(_image(hal, after))))
+
+
+@pytest.mark.parametrize("D", pc.SEAM_ROWS)
+@pytest.mark.parametrize("what", pc.SEAM_TABLES)
+def test_a_head_on_the_seam_of_two_workgroups(hal, args, what, D):
+    """rows 255 and 256 share a leaf, lie in sibling leaves, or lie under different parents (pages_cases.seam_table): the walk returns the
+    host verifier's root_after, which is the root of the paged-out image"""
+    W, po2, zk = 4096, 10, 40
+    rng = np.random.default_rng(D + len(what))
+    image = _words(rng, W, big=True)
+    addrs = pc.seam_table(what, D, W, rng)
+    out = _words(rng, D, big=True)
+    nodes = logup.reference_image_tree(image)
+    proof = logup.reference_page_out_proof(args, po2, zk, _table(image, addrs, out, po2), W, nodes)
+    assert [int(x) for x in proof[1:3]] == [W, D] and int(proof[4]) == 9
+    msg, root = _agree(hal, proof, nodes[1])
+    image[addrs] = out
+    assert msg is None and np.array_equal(root, logup.reference_image_root(image))
 
 
 # ---- 3. a device-built proof, and the prover ----

@@ -1,4 +1,4 @@
-"""Paging on the GPU (zkh_derive_links_paged, zkh_page_out, zkh_derive_all_paged; csrc/links.hip): the memory of a LINK record starts
+"""Paging on the GPU (zkh_derive_links_paged, zkh_page_out, zkh_derive_all_paged; csrc/links.hip, the page-out in csrc/page_out.hip): the memory of a LINK record starts
 from an image and goes back into it.  Hand-built load / store traces (pages_cases.case) at three sizes (A = 216: no multiple of a wave;
 2102; 6198: past one 4096-item sort tile and past one scan workgroup) over the key patterns that can break the page scan and the table —
 one address for every access (D = 1, head and tail 6197 positions apart), all distinct (D = m: every position both head and tail, every

@@ -1,7 +1,8 @@
 // arguments.h — lookup and permutation arguments as data (ZKA1 blob; zeth_amd/circuits/logup.py; DESIGN.md §2 ARGUMENTS): the decoded
 // form every consumer reads, and what the consumers share.  arguments.hip owns the blob format and the rules a blob must keep;
 // accumulate.hip (zkh_accumulate), multiplicities.hip (zkh_derive_multiplicities), sort.hip (zkh_derive_sorted), columns.hip
-// (zkh_derive_columns) and links.hip (zkh_derive_links, zkh_derive_links_paged, zkh_page_out, zkh_page_out_tree) read zkh_circuit::args and never see a blob word.
+// (zkh_derive_columns), links.hip (zkh_derive_links, zkh_derive_links_paged) and page_out.hip (zkh_page_out, zkh_page_out_tree,
+// zkh_page_out_proof) read zkh_circuit::args and never see a blob word.
 //
 // WHO WRITES A DATA COLUMN (the module docstring of logup.py says the same; check_owned in arguments.hip keeps it).  A data column has at
 // most one writer, and a derive reads only what the stages before it have finished writing.  The writers: a sorted copy (its tuple
@@ -66,7 +67,7 @@ struct Link {
     uint32_t n_dst, reserved;               // destinations in use; a word the format reserves was not 0
     uint32_t flags, wg, wc;                 // version 6: word 5 (bit 0 = READS, LINK_READS) and words 14, 15, the write flag's (group, column)
 };
-// logup.Pages, the PAGES record (version 7), as the blob gives it; the paged kernels of links.hip read it in this form
+// logup.Pages, the PAGES record (version 7), as the blob gives it; the paged kernels of links.hip and the page-out of page_out.hip read it in this form
 struct Pages {
     uint32_t index;                         // its index among all records of the blob (it comes last)
     uint32_t L, ng, link;                   // limb bits; limbs of an address and of a gap; the blob record index of the LINK it pages

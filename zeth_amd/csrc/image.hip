@@ -1,6 +1,6 @@
 // image.hip — the committed memory image (include/zkhal.h "THE IMAGE'S COMMITMENT"; zeth_amd/circuits/logup.py `reference_image_tree`;
 // DESIGN.md §2 ARGUMENTS): a Merkle tree over the residues of an image of W raw Montgomery words, built on the device
-// (zkh_image_commit) and kept current by a page-out (zkh_page_out_tree, links.hip -> image_tree_update).
+// (zkh_image_commit) and kept current by a page-out (zkh_page_out_tree, page_out.hip -> image_tree_update).
 //
 // L = the smallest power of two >= ceil(W / 8).  `nodes` is 2 L digests in heap order (digest i at words [8 i, 8 i + 8)): digest 0 eight
 // zeros; leaf L + j, word k = image[8 j + k] % P where 8 j + k < W, else 0 (a leaf is eight memory words verbatim, no hash); node i
@@ -13,10 +13,9 @@
 //   image_leaves : lane i < D whose leaf differs from the row below's rewrites the whole leaf from the image (residues, zero padding);
 //   then per layer of `width` parents, from the widest (L / 2) up, while the layer is LISTED:
 //   image_list   : the layer's dirty parents = the adjacent-unique of (the layer below's list >> 1); the first list comes from the table
-//                  (a_i >> 4).  Flag, scan, scatter as the page scan of links.hip does: k_image_heads flags a lane whose key differs from
-//                  the one before and scans the flags in its workgroup (scan.h), the sort's counter scan (sort.h scan_counters, ONE
-//                  workgroup) turns the workgroups' totals into carries and leaves the count, k_image_compact writes the heads' keys at
-//                  their ranks.  The count stays on the device: the grids are sized by its bound min(D, width) and lanes past it leave.
+//                  (a_i >> 4).  Flag, scan, scatter as the page scan of links.hip does: k_image_heads runs the heads stage (scan.h
+//                  scan_heads) on "my key differs from the one before", the sort's counter scan leaves the count, k_image_compact writes the
+//                  heads' keys at their ranks.  The count stays on the device: the grids are sized by its bound min(D, width), lanes past it leave.
 //   image_sparse : hash.hip's k_hash_fold_list, one lane per listed parent: dense lanes, a permutation per dirty parent and no other.
 //   A layer is listed when D + 2^16 <= width (listed(): a function of (D, width) alone, the constant measured; since D only grows
 //   against width on the way up, the listed layers are the lowest ones).  From the first layer that is not, merkle_fold_from rebuilds
@@ -27,6 +26,7 @@
 #include "image_tree.h"
 #include "scan.h"
 #include "sort.h"
+#include "zku1.h"
 
 #include <cstring>
 #include <vector>
@@ -78,9 +78,8 @@ __global__ __launch_bounds__(IMG_THREADS) void k_image_dirty_leaves(const uint32
 template <bool kTable, int kShift = 4>
 __device__ __forceinline__ uint32_t parent_of(const uint32_t* __restrict__ src, uint32_t t) { return kTable ? canonical(src[t]) >> kShift : src[t] >> 1; }
 
-// grid ceil(bound / IMG_THREADS) over the items [0, m) of the layer below, m = *count (kTable: the host's D, count = NULL): local[t] = the
-// heads among the items of t's workgroup up to t (a head: its parent differs from the item before's), sums[1 + workgroup] = the
-// workgroup's heads.  Workgroups past m leave a total of 0.
+// grid ceil(bound / IMG_THREADS) over the items [0, m) of the layer below, m = *count (kTable: the host's D, count = NULL): the heads stage,
+// a head being an item whose parent differs from the item before's; the totals from sums[1].  Workgroups past m leave a total of 0.
 template <bool kTable, int kShift = 4>
 __global__ __launch_bounds__(IMG_THREADS) void k_image_heads(const uint32_t* __restrict__ src, const uint32_t* __restrict__ count, uint32_t D,
                                                              uint32_t* __restrict__ local, uint32_t* __restrict__ sums) {
@@ -88,9 +87,7 @@ __global__ __launch_bounds__(IMG_THREADS) void k_image_heads(const uint32_t* __r
     const uint32_t m = kTable ? D : *count;
     const uint32_t t = blockIdx.x * IMG_THREADS + threadIdx.x;
     const uint32_t head = t < m && (t == 0 || parent_of<kTable, kShift>(src, t - 1) != parent_of<kTable, kShift>(src, t));
-    const uint32_t incl = block_scan<IMG_THREADS>(head, buf, AddWrap());
-    if (t < m) local[t] = incl;
-    if (threadIdx.x == IMG_THREADS - 1) sums[1 + blockIdx.x] = incl;
+    scan_heads<IMG_THREADS>(head, t, m, buf, local, sums + 1);
 }
 // ... and after the counter scan (sums[1 + workgroup] = the heads of the workgroups before it): every head writes its parent at its rank.
 // `count` is the count k_image_heads read: the layer below's, in the other counter run than `sums` (whose word 0 is now this layer's).
@@ -101,12 +98,10 @@ __global__ __launch_bounds__(IMG_THREADS) void k_image_compact(const uint32_t* _
     const uint32_t t = blockIdx.x * IMG_THREADS + threadIdx.x;
     if (t >= m) return;
     const uint32_t v = parent_of<kTable>(src, t);
-    if (t == 0 || parent_of<kTable>(src, t - 1) != v) list[local[t] + sums[1 + blockIdx.x] - 1] = v;
+    if (t == 0 || parent_of<kTable>(src, t - 1) != v) list[head_rank(local, sums + 1, t)] = v;
 }
 
-// ---- THE UPDATE'S PROOF (include/zkhal.h; the header comment of zkh::image_proof_build below) ----
-constexpr uint32_t PROOF_MAGIC = 0x5a4b5531;            // 'ZKU1'
-constexpr uint32_t PROOF_HEADER = 5;
+// ---- THE UPDATE'S PROOF (include/zkhal.h; the header comment of zkh::image_proof_build below; its layout: zku1.h) ----
 // A layer whose list holds at most 2^PROOF_TOP_LOG items for certain (min(D, its nodes): the bound only falls on the way up) is walked,
 // with every layer above it, by ONE workgroup in one launch (k_proof_top): the list fits its lanes, and a layer costs barriers instead
 // of three launches.  Measured (DESIGN.md §2 ARGUMENTS, M19): a layer of three launches takes 12 us whatever its list holds up to 2^19
@@ -137,11 +132,11 @@ __global__ __launch_bounds__(IMG_THREADS) void k_proof_table(const uint32_t* __r
                                                              uint32_t D, uint32_t W, uint32_t h, uint32_t* __restrict__ proof) {
     const uint32_t t = blockIdx.x * IMG_THREADS + threadIdx.x;
     if (t >= D) return;
-    uint32_t* row = proof + PROOF_HEADER + h + 3 * (size_t)t;
-    row[0] = canonical(addrs[t]);
-    row[1] = in[t] % P;
-    row[2] = out[t] % P;
-    if (t == 0) { proof[0] = PROOF_MAGIC; proof[1] = W; proof[2] = D; proof[4] = h; }
+    uint32_t* row = table_row(proof + proof_table_at(h), t);
+    row[ROW_ADDR] = canonical(addrs[t]);
+    row[ROW_IN] = in[t] % P;
+    row[ROW_OUT] = out[t] % P;
+    if (t == 0) { proof[0] = PROOF_MAGIC; proof[PROOF_W] = W; proof[PROOF_D] = D; proof[PROOF_H] = h; }
 }
 
 // After k_image_heads<true, 3> and its counter scan (meta[PM_ITEMS] = M): every row that is the first of its leaf writes the leaf's
@@ -152,15 +147,15 @@ __global__ __launch_bounds__(IMG_THREADS) void k_proof_leaves(const uint32_t* __
                                                               uint32_t* __restrict__ list, uint32_t* __restrict__ meta, uint32_t* __restrict__ proof) {
     const uint32_t t = blockIdx.x * IMG_THREADS + threadIdx.x;
     if (t >= D) return;
-    const size_t leaves0 = PROOF_HEADER + h + 3 * (size_t)D;
+    const size_t leaves0 = proof_leaves_at(h, D);
     if (t == 0) {
         const uint32_t M = meta[PM_ITEMS];
-        proof[3] = M;
+        proof[PROOF_M] = M;
         meta[PM_OFF] = (uint32_t)(leaves0 + 8 * (size_t)M);
     }
     const uint32_t leaf = canonical(addrs[t]) >> 3;
     if (t && (canonical(addrs[t - 1]) >> 3) == leaf) return;
-    const uint32_t rank = local[t] + sums[1 + blockIdx.x] - 1;
+    const uint32_t rank = head_rank(local, sums + 1, t);
     list[rank] = leaf;
     copy_digest(nodes + (L + leaf) * 8, proof + leaves0 + 8 * (size_t)rank);
 }
@@ -231,7 +226,7 @@ __global__ __launch_bounds__(TOP_THREADS) void k_proof_top(const uint32_t* __res
 
 }  // namespace
 
-// THE UPDATE'S PROOF on the device (zkh_page_out_proof, links.hip -> image_proof_build), after the check pass: the table's rows [0, D)
+// THE UPDATE'S PROOF on the device (zkh_page_out_proof, page_out.hip -> image_proof_build), after the check pass: the table's rows [0, D)
 // hold strictly increasing addresses a_i < W and p_in is what the tree holds.  `nodes` is only read.
 //   proof_table  : the header's W, D, h and the 3 D table words, one pass over D lanes;
 //   proof_leaves : S_0 = the adjacent-unique of a_i >> 3, flag / scan / compact as image_list does for a_i >> 4 (k_image_heads with the
@@ -247,11 +242,10 @@ const char* zkh::image_proof_build(zkh_ctx* ctx, const uint32_t* addrs, const ui
                                    const zkh_buf* nodes, zkh_buf* proof) {
     const size_t L = image_leaves(image_words);
     const uint32_t W = (uint32_t)image_words;
-    uint32_t h = 0;
-    while (((size_t)1 << h) < L) h++;
+    const uint32_t h = image_height(image_words);
     if (!D) {                                           // the header alone: nothing to launch
         std::vector<uint32_t> header(PROOF_HEADER + h, 0);
-        header[0] = PROOF_MAGIC; header[1] = W; header[4] = h;
+        header[0] = PROOF_MAGIC; header[PROOF_W] = W; header[PROOF_H] = h;
         return zkh_write(ctx, proof, header.data(), 0, header.size());
     }
     const uint32_t nb0 = (D + IMG_THREADS - 1) / IMG_THREADS;
@@ -371,23 +365,20 @@ extern "C" const char* zkh_image_commit(zkh_ctx* ctx, const zkh_buf* image, zkh_
 
 extern "C" size_t zkh_image_proof_words(size_t image_words, size_t pages) {
     const size_t L = image_leaves(image_words), D = pages;
-    size_t words = PROOF_HEADER + 3 * D + 8 * (D < L ? D : L);
+    size_t words = PROOF_HEADER + PROOF_ROW * D + 8 * (D < L ? D : L);
     for (size_t w = L; w > 1; w >>= 1) words += 1 + 8 * (D < w / 2 ? D : w / 2);
     return words;
 }
 
 // ---- THE UPDATE'S PROOF, WALKED (zkh_image_proof_verify on the host, zkh_image_proof_walk on the device) ----
-// One source for every refusal of the two walks: `who` is the call's name, the text after it is the same for both.
+// One source for every refusal of the two walks: `who` is the call's name, the text after it is the same for both (the header's
+// and the table's refusals are zku1.h's: the page-out circuits share them).
 namespace {
 
 const char* refuse_word(const char* who, size_t i, uint32_t v) { return make_err("%s: word %zu is %u, not below P", who, i, v); }
 const char* refuse_root_range(const char* who) { return make_err("%s: root_before is not 8 words below P", who); }
 const char* refuse_leaves(const char* who, uint32_t M, size_t leaves) { return make_err("%s: M %u, but the table's rows lie in %zu leaves", who, M, leaves); }
 const char* refuse_layer(const char* who, uint32_t k, uint32_t c, uint32_t take) { return make_err("%s: layer %u: %u siblings, but the walk takes %u", who, k, c, take); }
-const char* refuse_outside(const char* who, uint32_t i, uint32_t a, uint32_t W) { return make_err("%s: row %u: address %u outside the image of %u words", who, i, a, W); }
-const char* refuse_order(const char* who, uint32_t i, uint32_t a, uint32_t before) {
-    return make_err("%s: row %u: address %u does not follow a smaller one (row %u: address %u)", who, i, a, i - 1, before);
-}
 const char* refuse_in(const char* who, uint32_t i, uint32_t in, uint32_t a, uint32_t held) {
     return make_err("%s: row %u: in %u at address %u, but its leaf holds %u", who, i, in, a, held);
 }
@@ -395,44 +386,28 @@ const char* refuse_root(const char* who, const uint32_t* top) {
     return make_err("%s: the proof opens root %08x %08x %08x %08x %08x %08x %08x %08x, not root_before", who, top[0], top[1], top[2], top[3], top[4], top[5], top[6], top[7]);
 }
 
-// The header against the length.  `head` holds the proof's first min(words, PROOF_HEADER + 29) words: enough, since the counts c_k are
-// read only once h has been found to be W's, and that is at most 29.
-const char* proof_header(const char* who, const uint32_t* head, size_t words) {
-    ZKH_REQUIRE(words >= PROOF_HEADER, "%s: a proof of %zu words: the header alone has %u", who, words, PROOF_HEADER);
-    const uint32_t W = head[1], D = head[2], M = head[3], h = head[4];
-    ZKH_REQUIRE(head[0] == PROOF_MAGIC, "%s: bad magic 0x%08x (ZKU1 is 0x%08x)", who, head[0], PROOF_MAGIC);
-    uint32_t hw = 0;
-    while (((size_t)1 << hw) < image_leaves(W)) hw++;
-    ZKH_REQUIRE(h == hw, "%s: h %u, but an image of %u words has h %u", who, h, W, hw);
-    ZKH_REQUIRE(words >= PROOF_HEADER + h, "%s: a proof of %zu words, but the header describes at least %u", who, words, PROOF_HEADER + h);
-    unsigned long long want = PROOF_HEADER + h + 3ull * D + 8ull * M;
-    for (uint32_t k = 0; k < h; k++) want += 8ull * head[PROOF_HEADER + k];
-    ZKH_REQUIRE(words == want, "%s: a proof of %zu words, but the header describes %llu", who, words, want);
-    return nullptr;
-}
 // D = 0 after the header, the words and root_before have passed: the header must describe nothing
 const char* proof_empty(const char* who, const uint32_t* head) {
-    if (head[3]) return refuse_leaves(who, head[3], 0);
-    for (uint32_t k = 0; k < head[4]; k++)
+    if (head[PROOF_M]) return refuse_leaves(who, head[PROOF_M], 0);
+    for (uint32_t k = 0; k < head[PROOF_H]; k++)
         if (head[PROOF_HEADER + k]) return refuse_layer(who, k, head[PROOF_HEADER + k], 0);
     return nullptr;
 }
 
 }  // namespace
 
-const char* zkh::image_proof_header(const char* who, const uint32_t* head, size_t words) { return proof_header(who, head, words); }
-
 // The walk of include/zkhal.h "THE UPDATE'S PROOF" on the host: no context, no GPU; every layer is one batch through the permutation
 // zkh_poseidon2_mix_host uses, the old children first, the new ones after them.
 extern "C" const char* zkh_image_proof_verify(const uint32_t* proof, size_t words, const uint32_t root_before[8], uint32_t root_after[8]) {
     static const char who[] = "image_proof_verify";
     ZKH_REQUIRE(proof && root_before && root_after, "%s: null argument", who);
-    ZKH_TRY(proof_header(who, proof, words));
-    const uint32_t W = proof[1], D = proof[2], M = proof[3], h = proof[4];
+    ZKH_TRY(image_proof_header(who, proof, words));
+    const ProofShape ps = proof_shape(proof);
+    const uint32_t W = ps.W, D = ps.D, M = ps.M, h = ps.h;
     const uint32_t* c = proof + PROOF_HEADER;
-    const size_t t0 = PROOF_HEADER + h, l0 = t0 + 3 * (size_t)D, s0 = l0 + 8 * (size_t)M;
+    const size_t t0 = ps.table, l0 = ps.leaves, s0 = ps.siblings;
     for (size_t i = t0; i < words; i++)
-        if (!(proof[i] < P || (i < l0 && (i - t0) % 3 == 0))) return refuse_word(who, i, proof[i]);
+        if (!(proof[i] < P || proof_word_is_address(i, t0, l0))) return refuse_word(who, i, proof[i]);
     for (int j = 0; j < 8; j++)
         if (root_before[j] >= P) return refuse_root_range(who);
     if (!D) {
@@ -443,9 +418,8 @@ extern "C" const char* zkh_image_proof_verify(const uint32_t* proof, size_t word
     const uint32_t* table = proof + t0;
     std::vector<uint32_t> S, rank(D);                   // the dirty nodes of the layer in hand; every row's leaf among S_0
     for (uint32_t i = 0; i < D; i++) {
-        const uint32_t a = table[3 * (size_t)i];
-        if (a >= W) return refuse_outside(who, i, a, W);
-        if (i && table[3 * (size_t)(i - 1)] >= a) return refuse_order(who, i, a, table[3 * (size_t)(i - 1)]);
+        const uint32_t a = table_addr(table, i), before = i ? table_addr(table, i - 1) : 0;
+        if (table_row_refused(i, a, before, W)) return refuse_row(who, i, a, before, W);
         if (S.empty() || S.back() != a >> 3) S.push_back(a >> 3);
         rank[i] = (uint32_t)S.size() - 1;
     }
@@ -457,9 +431,9 @@ extern "C" const char* zkh_image_proof_verify(const uint32_t* proof, size_t word
         memcpy(&cur[16 * j + 8], proof + l0 + 8 * j, 32);
     }
     for (uint32_t i = 0; i < D; i++) {
-        const uint32_t a = table[3 * (size_t)i], held = cur[16 * (size_t)rank[i] + (a & 7)];
-        if (held != table[3 * (size_t)i + 1]) return refuse_in(who, i, table[3 * (size_t)i + 1], a, held);
-        cur[16 * (size_t)rank[i] + 8 + (a & 7)] = table[3 * (size_t)i + 2];
+        const uint32_t a = table_addr(table, i), held = cur[16 * (size_t)rank[i] + (a & 7)];
+        if (held != table_in(table, i)) return refuse_in(who, i, table_in(table, i), a, held);
+        cur[16 * (size_t)rank[i] + 8 + (a & 7)] = table_out(table, i);
     }
     size_t at = s0;
     for (uint32_t k = 0; k < h; k++) {
@@ -502,8 +476,8 @@ extern "C" const char* zkh_image_proof_verify(const uint32_t* proof, size_t word
 //
 // SAFETY AGAINST ANY INPUT.  The proof is hostile until shown otherwise, and nothing below may read a proof word at or past `words`,
 // or a scratch item past its count, whatever the proof holds.  The reasoning, stage by stage:
-//   header     : the host reads min(words, 5 + 29) words once and runs proof_header on them: after it, h is W's (<= 29),
-//                words = 5 + h + 3 D + 8 M + 8 sum c_k exactly, so the table [t0, l0), the leaves [l0, s0) and the siblings [s0, words) are
+//   header     : the host reads min(words, PROOF_HEAD_MAX) words once and runs image_proof_header (zku1.h) on them: after it, h is W's (<= 29),
+//                words = t0 + 3 D + 8 M + 8 sum c_k exactly, so the table [t0, l0), the leaves [l0, s0) and the siblings [s0, words) are
 //                sections of the proof, and 3 D + 8 M <= words: the scratch, sized by min(D, M, L), is a small multiple of the proof.
 //   walk_check : k_walk_range reads the words [t0, words), k_walk_rows the address words t0 + 3 i, i < D: inside the table.  They
 //                gate nothing and are gated by nothing; each leaves the LOWEST index it refuses (atomicMin), so the result does
@@ -558,7 +532,7 @@ __global__ __launch_bounds__(IMG_THREADS) void k_walk_range(const uint32_t* __re
     const size_t i = t0 + (size_t)blockIdx.x * IMG_THREADS + threadIdx.x;
     if (i >= words) return;
     const uint32_t v = proof[i];
-    if (v >= P && !(i < l0 && (i - t0) % 3 == 0)) lowest((unsigned long long*)(st + WR_RANGE), (uint32_t)i, v);
+    if (v >= P && !proof_word_is_address(i, t0, l0)) lowest((unsigned long long*)(st + WR_RANGE), (uint32_t)i, v);
 }
 
 // grid ceil(D / IMG_THREADS) over the rows of the proof's table (stride 3, addresses as integers): the lowest row whose address lies
@@ -568,12 +542,10 @@ __global__ __launch_bounds__(IMG_THREADS) void k_walk_rows(const uint32_t* __res
                                                            uint32_t* __restrict__ sums, uint32_t* __restrict__ st) {
     __shared__ uint32_t buf[2][IMG_THREADS];
     const uint32_t t = blockIdx.x * IMG_THREADS + threadIdx.x;
-    const uint32_t a = t < D ? table[3 * (size_t)t] : 0, before = t && t < D ? table[3 * (size_t)(t - 1)] : 0;
-    if (t < D && (a >= W || (t && before >= a))) atomicMin(st + WR_ROW, t);
+    const uint32_t a = t < D ? table_addr(table, t) : 0, before = t && t < D ? table_addr(table, t - 1) : 0;
+    if (t < D && table_row_refused(t, a, before, W)) atomicMin(st + WR_ROW, t);
     const uint32_t head = t < D && (t == 0 || (before >> 3) != (a >> 3));
-    const uint32_t incl = block_scan<IMG_THREADS>(head, buf, AddWrap());
-    if (t < D) local[t] = incl;
-    if (threadIdx.x == IMG_THREADS - 1) sums[1 + blockIdx.x] = incl;
+    scan_heads<IMG_THREADS>(head, t, D, buf, local, sums + 1);
 }
 
 // grid ceil(D / IMG_THREADS), after the counter scan (st[WR_COUNT]).  The lane of a leaf's first row owns the leaf: its index to
@@ -583,14 +555,14 @@ __global__ __launch_bounds__(IMG_THREADS) void k_walk_leaves(const uint32_t* __r
                                                              const uint32_t* __restrict__ sums, uint32_t* __restrict__ st, uint32_t* __restrict__ list,
                                                              uint32_t* __restrict__ dig, uint32_t* __restrict__ meta) {
     const uint32_t t = blockIdx.x * IMG_THREADS + threadIdx.x;
-    const size_t l0 = (size_t)t0 + 3 * (size_t)D;
+    const size_t l0 = (size_t)t0 + PROOF_ROW * (size_t)D;
     const bool ok = clean64(st, WR_RANGE) && st[WR_ROW] == NONE && st[WR_COUNT] == M;
     if (t == 0) { meta[WM_ITEMS] = ok ? M : 0; meta[WM_OFF] = (uint32_t)(l0 + 8 * (size_t)M); }
     if (t >= D || !ok) return;
     const uint32_t* table = proof + t0;
-    const uint32_t leaf = table[3 * (size_t)t] >> 3;
-    if (t && (table[3 * (size_t)(t - 1)] >> 3) == leaf) return;
-    const uint32_t rank = local[t] + sums[1 + blockIdx.x] - 1;         // < M: the count is M
+    const uint32_t leaf = table_addr(table, t) >> 3;
+    if (t && (table_addr(table, t - 1) >> 3) == leaf) return;
+    const uint32_t rank = head_rank(local, sums + 1, t);         // < M: the count is M
     list[rank] = leaf;
     const uint32_t* from = proof + l0 + 8 * (size_t)rank;
     uint32_t o[8], n[8];
@@ -598,14 +570,14 @@ __global__ __launch_bounds__(IMG_THREADS) void k_walk_leaves(const uint32_t* __r
     for (int j = 0; j < 8; j++) o[j] = n[j] = from[j];
     uint32_t bad = NONE, held = 0;
     for (uint32_t u = t; u < D && u - t < 8; u++) {
-        const uint32_t* row = table + 3 * (size_t)u;
-        const uint32_t a = row[0];
+        const uint32_t* row = table_row(table, u);
+        const uint32_t a = row[ROW_ADDR];
         if ((a >> 3) != leaf) break;
         uint32_t was = 0;
 #pragma unroll
         for (int j = 0; j < 8; j++)
-            if ((a & 7) == (uint32_t)j) { was = o[j]; n[j] = row[2]; }
-        if (was != row[1] && bad == NONE) { bad = u; held = was; }
+            if ((a & 7) == (uint32_t)j) { was = o[j]; n[j] = row[ROW_OUT]; }
+        if (was != row[ROW_IN] && bad == NONE) { bad = u; held = was; }
     }
     if (bad != NONE) lowest((unsigned long long*)(st + WR_IN), bad, held);
     uint4* d = (uint4*)(dig + 16 * (size_t)rank);
@@ -648,13 +620,13 @@ __global__ __launch_bounds__(64) void k_walk_top(const uint32_t* __restrict__ pr
     if (t == 16) st[WR_TOP_ITEMS] = n;
     if (t == 17 && st[WR_ROW] != NONE) {
         const uint32_t i = st[WR_ROW];
-        st[WR_ROW_A] = proof[t0 + 3 * (size_t)i];
-        st[WR_ROW_BEFORE] = i ? proof[t0 + 3 * (size_t)(i - 1)] : 0;
+        st[WR_ROW_A] = table_addr(proof + t0, i);
+        st[WR_ROW_BEFORE] = i ? table_addr(proof + t0, i - 1) : 0;
     }
     if (t == 18 && !clean64(st, WR_IN)) {
         const uint32_t i = st[WR_IN + 1];
-        st[WR_IN_A] = proof[t0 + 3 * (size_t)i];
-        st[WR_IN_IN] = proof[t0 + 3 * (size_t)i + 1];
+        st[WR_IN_A] = table_addr(proof + t0, i);
+        st[WR_IN_IN] = table_in(proof + t0, i);
     }
 }
 
@@ -666,11 +638,12 @@ extern "C" const char* zkh_image_proof_walk(zkh_ctx* ctx, const zkh_buf* proof, 
     ZKH_REQUIRE(words <= proof->len, "%s: a proof of %zu words in a buffer of %zu", who, words, proof->len);
     ZKH_REQUIRE(words <= 0xffffffffull, "%s: a proof of %zu words (at most 2^32 - 1)", who, words);
     bind_thread(ctx);
-    uint32_t head[PROOF_HEADER + 29] = {0};
-    ZKH_TRY(zkh_read(ctx, proof, head, 0, words < PROOF_HEADER + 29 ? words : PROOF_HEADER + 29));
-    ZKH_TRY(proof_header(who, head, words));
-    const uint32_t W = head[1], D = head[2], M = head[3], h = head[4];
-    const size_t L = image_leaves(W), t0 = PROOF_HEADER + h, l0 = t0 + 3 * (size_t)D;
+    uint32_t head[PROOF_HEAD_MAX] = {0};
+    ZKH_TRY(zkh_read(ctx, proof, head, 0, words < PROOF_HEAD_MAX ? words : PROOF_HEAD_MAX));
+    ZKH_TRY(image_proof_header(who, head, words));
+    const ProofShape ps = proof_shape(head);
+    const uint32_t W = ps.W, D = ps.D, M = ps.M, h = ps.h;
+    const size_t L = image_leaves(W), t0 = ps.table, l0 = ps.leaves;
     bool root_ok = true;
     for (int j = 0; j < 8; j++) root_ok = root_ok && root_before[j] < P;
     if (words == t0) {                                  // D = 0 and nothing after the header: nothing to launch
@@ -745,10 +718,7 @@ extern "C" const char* zkh_image_proof_walk(zkh_ctx* ctx, const zkh_buf* proof, 
     if (!((rec[WR_RANGE] & rec[WR_RANGE + 1]) == NONE)) return refuse_word(who, rec[WR_RANGE + 1], rec[WR_RANGE]);
     if (!root_ok) return refuse_root_range(who);
     if (!D) return proof_empty(who, head);              // words past the header: M or a c_k is not 0
-    if (rec[WR_ROW] != NONE) {
-        const uint32_t i = rec[WR_ROW], a = rec[WR_ROW_A];
-        return a >= W ? refuse_outside(who, i, a, W) : refuse_order(who, i, a, rec[WR_ROW_BEFORE]);
-    }
+    if (rec[WR_ROW] != NONE) return refuse_row(who, rec[WR_ROW], rec[WR_ROW_A], rec[WR_ROW_BEFORE], W);
     if (rec[WR_COUNT] != M) return refuse_leaves(who, M, rec[WR_COUNT]);
     if (!((rec[WR_IN] & rec[WR_IN + 1]) == NONE)) return refuse_in(who, rec[WR_IN + 1], rec[WR_IN_IN], rec[WR_IN_A], rec[WR_IN]);
     if (rec[WR_LAYER] != NONE) return refuse_layer(who, rec[WR_LAYER], rec[WR_LAYER_C], rec[WR_LAYER_TAKE]);

@@ -1,6 +1,6 @@
 // image_tree.h — the committed memory image (include/zkhal.h "THE IMAGE'S COMMITMENT"; DESIGN.md §2 ARGUMENTS): what image.hip,
-// hash.hip and links.hip share.  image.hip owns the leaf layer and the lists of dirty nodes, hash.hip every permutation (its build
-// flags), links.hip the page-out that drives the update.
+// hash.hip and page_out.hip share.  image.hip owns the leaf layer and the lists of dirty nodes, hash.hip every permutation (its build
+// flags), page_out.hip the page-out that drives the update and the proof, zku1.h the proof's layout.
 #pragma once
 #include "common.h"
 
@@ -43,11 +43,6 @@ const char* image_tree_update(zkh_ctx* c, const uint32_t* addrs, uint32_t D, con
 // before the page-out (only read), `proof` at least zkh_image_proof_words(image_words, D) words.
 const char* image_proof_build(zkh_ctx* c, const uint32_t* addrs, const uint32_t* in, const uint32_t* out, uint32_t D, size_t image_words, const zkh_buf* nodes,
                               zkh_buf* proof);
-
-// image.hip: the header of a ZKU1 proof against the proof's length, with the messages of zkh_image_proof_verify after "`who`: ".  `head`
-// holds the proof's first min(words, PROOF_HEAD_MAX) words: the header is 5 + h words and an h that passes is at most 29.  After it
-// W = head[1], D = head[2], h = head[4] is W's, and the 3 D table words start at word 5 + h inside the proof.
-constexpr uint32_t PROOF_HEAD_MAX = 5 + 29;
-const char* image_proof_header(const char* who, const uint32_t* head, size_t words);
+// The proof's layout, its header's check and its table's rule are zku1.h's.
 
 }  // namespace zkh

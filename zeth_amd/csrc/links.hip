@@ -36,21 +36,17 @@
 // rule.  THE PAGE TABLE: a_0 < .. < a_{D-1} the distinct addresses of the record's accesses; on the active rows i < D p_on = Montgomery(1),
 // p_addr = the raw key word of a_i's first access, p_in = the raw word image[a_i], p_out / p_time = the raw value / clock word of a_i's last
 // access, alimb_j = limb j of a_i (refused, under the PAGES record's index, when a_i >= 2^(L ng)), gap_j = limb j of a_i - a_{i-1} - 1 (zeros
-// on row 0); active rows [D, A) get zeros in all destinations, rows [A, n) are never touched.  PAGE-OUT (zkh_page_out, zkh_page_out_tree,
-// `reference_page_out`): image[x(p_addr, i)] = p_out[i] on every active row with p_on = 1, after a check pass that refuses, with the image
-// unchanged, the lowest row whose p_on is not 0 / 1, whose address is >= W or does not follow a smaller one on a row with p_on = 1: a table
-// that repeats an address is REFUSED, so the scatter never writes one word twice.
+// on row 0); active rows [D, A) get zeros in all destinations, rows [A, n) are never touched.  Writing the table back into the image,
+// the page-out, has a file of its own.
 //
 // The paged passes reuse the one sort, and they are the same kernel (k_links<.., kPaged>: one body for the link semantics and the read rule;
 // the plain passes compile the paging out).  Position t of the paged record is a HEAD when the packed key at t - 1 differs (the first access
 // of its address) and a TAIL when the one at t + 1 does: neighbouring packed keys, coalesced.  An inclusive scan of the head flags over the m
-// sorted positions gives every position its page index + 1: k_page_heads scans inside a workgroup (scan.h's block_scan) and leaves the
-// workgroup's total, the sort's counter scan (sort.h scan_counters, ONE workgroup, so none waits for another) turns the totals into
-// exclusive carries and leaves D; the consumers add carry[workgroup] to the local index.  The paged check pass adds the image reads and
+// sorted positions gives every position its page index + 1: k_page_heads is the heads stage (scan.h scan_heads), the sort's counter scan
+// (sort.h scan_counters, ONE workgroup, so none waits for another) leaves the carries and D, head_rank is the index.  The paged check pass adds the image reads and
 // the new refusals to the same wave minimum and the same atomicMin; the paged write pass also fills the table — head lanes p_on, p_addr,
 // p_in, alimb and gap (the previous address re-read from the trace at rows[t - 1]: packed keys drop bits and are no addresses), tail lanes
 // p_out and p_time, lanes D <= t < A zeros (coalesced).  No atomic but that min: the result is a function of the traces and the image.
-#include "image_tree.h"
 #include "scan.h"
 #include "sort.h"
 
@@ -72,8 +68,7 @@ struct Paging {
     const uint32_t *local, *sums;                       // the page scan: k_page_heads' local indices; D and the workgroups' carries
 };
 
-// grid ceil(m_max / LINK_THREADS) over the sorted positions of the paged record (its place p among the LINK records): local[t] = the heads
-// among the positions of t's workgroup up to t, sums[1 + workgroup] = the workgroup's heads
+// grid ceil(m_max / LINK_THREADS) over the sorted positions of the paged record (its place p among the LINK records): the heads stage
 __global__ __launch_bounds__(LINK_THREADS) void k_page_heads(const uint32_t* __restrict__ status, const unsigned long long* __restrict__ keys, uint32_t p, uint32_t A,
                                                              uint32_t* __restrict__ local, uint32_t* __restrict__ sums) {
     __shared__ uint32_t buf[2][LINK_THREADS];
@@ -81,9 +76,7 @@ __global__ __launch_bounds__(LINK_THREADS) void k_page_heads(const uint32_t* __r
     const uint32_t t = blockIdx.x * LINK_THREADS + threadIdx.x;
     const size_t base = (size_t)p * A;
     const uint32_t head = t < m && (t == 0 || keys[base + t - 1] != keys[base + t]);
-    const uint32_t incl = block_scan<LINK_THREADS>(head, buf, AddWrap());
-    if (t < m) local[t] = incl;
-    if (threadIdx.x == LINK_THREADS - 1) sums[1 + blockIdx.x] = incl;
+    scan_heads<LINK_THREADS>(head, t, m, buf, local, sums + 1);
 }
 
 // grid (ceil(A / LINK_THREADS), records).  kWrite = false: the check pass (bad = the lowest bad record << 32 | row, the record by its place
@@ -168,7 +161,7 @@ __global__ __launch_bounds__(LINK_THREADS) void k_links(const uint32_t* __restri
         if (t >= D && t < A)                              // the rows below the table, coalesced
             for (uint32_t e = 0; e < pg->n_dst; e++) data[(size_t)pg->dst[e] * n + t] = 0;
         if (access && (!linked || last)) {
-            const uint32_t i = pa.local[t] + pa.sums[1 + blockIdx.x] - 1;      // the page of t's address: the heads up to t, less one
+            const uint32_t i = head_rank(pa.local, pa.sums + 1, t);            // the page of t's address: the heads up to t, less one
             const uint32_t Lp = pg->L, ng = pg->ng, maskp = (1u << Lp) - 1;
             if (!linked) {                                // the head: the first access of the address
                 const uint32_t* keycol = group_ptr(code, data, rec->kg) + (size_t)rec->kc * n;
@@ -195,34 +188,6 @@ __global__ __launch_bounds__(LINK_THREADS) void k_links(const uint32_t* __restri
     const uint32_t mask = (1u << L) - 1;                  // L <= 16
     for (uint32_t j = 0; j < nl; j++)
         data[(size_t)rec->dst[2 + nc + j] * n + row] = fp_encode((uint32_t)((unsigned long long)d >> (j * L)) & mask).v;
-}
-
-// zkh_page_out's two passes over the active rows of the page table: kWrite = false reduces the lowest refused row into `bad` (under 0),
-// and the row with p_on = 1 that has none after it leaves its index in `last` (in a table that passes the rows with p_on = 1 are a prefix
-// [0, D): that is row D - 1, one lane, a plain store; no such row: `last` keeps its all ones, D = 0);
-// kWrite = true scatters p_out into the image (addresses checked distinct and inside: no word is written twice).
-// kProof (zkh_page_out_proof's check pass): `image` is the LEAF LAYER of the image's tree, the residue of word a at image[a], and a row
-// that passes the three rules is refused when p_in % P is not that word.
-template <bool kWrite, bool kProof = false>
-__global__ __launch_bounds__(LINK_THREADS) void k_page_out(const uint32_t* __restrict__ data, const Pages* __restrict__ pg, uint32_t n, uint32_t A, uint32_t* image,
-                                                           uint32_t W, unsigned long long* __restrict__ bad, uint32_t* __restrict__ last) {
-    const uint32_t t = blockIdx.x * LINK_THREADS + threadIdx.x;
-    const uint32_t* on = data + (size_t)pg->dst[PG_ON] * n;
-    const uint32_t* addrs = data + (size_t)pg->dst[PG_ADDR] * n;
-    uint32_t mine = NONE;
-    if (t < A) {
-        const uint32_t v = on[t] % P, a = canonical(addrs[t]);
-        if (!kWrite) {
-            bool ok = v == 0 || v == R1;
-            if (v == R1) ok = a < W && (t == 0 || (on[t - 1] % P == R1 && canonical(addrs[t - 1]) < a));
-            if (kProof && ok && v == R1) ok = data[(size_t)pg->dst[PG_IN] * n + t] % P == image[a];
-            if (!ok) mine = t;
-            if (v == R1 && (t + 1 == A || on[t + 1] % P != R1)) *last = t;
-        } else if (v == R1 && a < W) {
-            image[a] = data[(size_t)pg->dst[PG_OUT] * n + t];
-        }
-    }
-    if (!kWrite) report_bad_row(bad, 0, mine);
 }
 
 // Which rule the refused access `row` of the LINK record r broke, as the reference names it (pages: r is the paged record, and `image` its
@@ -372,115 +337,4 @@ extern "C" const char* zkh_derive_links(zkh_ctx* ctx, const zkh_circuit* c, size
 extern "C" const char* zkh_derive_links_paged(zkh_ctx* ctx, const zkh_circuit* c, size_t po2, size_t zk_cycles, const zkh_buf* code, zkh_buf* data,
                                               const zkh_buf* image) {
     return derive_links(ctx, c, po2, zk_cycles, code, data, image);
-}
-
-namespace {
-// Which rule the refused row of the page table broke, as the reference names it: `who` and `tail` frame the text.  nodes: the proof's
-// check pass, whose fourth rule is that p_in is the word the tree holds.
-const char* page_refusal(zkh_ctx* ctx, const char* who, const char* tail, const Pages& g, const zkh_buf* data, size_t n, uint32_t row, uint32_t W, const zkh_buf* nodes) {
-    uint32_t on, a, pon = 1, pa = 0;
-    ZKH_TRY(read_cell(ctx, data, data, GROUP_DATA, g.dst[PG_ON], n, row, &on));
-    ZKH_TRY(read_cell(ctx, data, data, GROUP_DATA, g.dst[PG_ADDR], n, row, &a));
-    if (on > 1) return make_err("%s: record %u at row %u: p_on %u, not 0 or 1%s", who, g.index, row, on, tail);
-    if (a >= W) return make_err("%s: record %u at row %u: address %u outside the image of %u words%s", who, g.index, row, a, W, tail);
-    if (row) {
-        ZKH_TRY(read_cell(ctx, data, data, GROUP_DATA, g.dst[PG_ON], n, row - 1, &pon));
-        ZKH_TRY(read_cell(ctx, data, data, GROUP_DATA, g.dst[PG_ADDR], n, row - 1, &pa));
-    }
-    if (!nodes || (row && (pon != 1 || pa >= a)))
-        return make_err("%s: record %u at row %u: page address %u does not follow a smaller one (row %u: p_on %u, address %u)%s", who, g.index, row, a, row - 1, pon, pa,
-                        tail);
-    uint32_t in, held;
-    ZKH_TRY(read_cell(ctx, data, data, GROUP_DATA, g.dst[PG_IN], n, row, &in));
-    ZKH_TRY(zkh_read(ctx, nodes, &held, nodes->len / 2 + a, 1));
-    return make_err("%s: record %u at row %u: p_in %u at address %u, the tree holds %u%s", who, g.index, row, in, a, canonical(held), tail);
-}
-
-// zkh_page_out (nodes = NULL) and zkh_page_out_tree: the check pass, one read-back (the refused row; D), the scatter, and with `nodes`
-// the update of the image's tree (image.hip) over the table's D addresses
-const char* page_out(zkh_ctx* ctx, const zkh_circuit* c, size_t po2, size_t zk_cycles, const zkh_buf* data, zkh_buf* image, zkh_buf* nodes) {
-    ZKH_REQUIRE(zkh_circuit_pages(c), "page_out: the circuit's arguments hold no PAGES record (ZKA1 version 7)");
-    size_t n;
-    uint32_t A;
-    ZKH_TRY(trace_rows("page_out", c, po2, zk_cycles, nullptr, data, nullptr, &n, &A));
-    ZKH_REQUIRE(image->len <= 0xffffffffull, "page_out: an image of %zu words (at most 2^32 - 1)", image->len);
-    ZKH_REQUIRE(!nodes || (image->len && nodes->len == zkh_image_tree_words(image->len)),
-                "page_out: nodes of %zu words; an image of %zu words has a tree of %zu (zkh_image_tree_words): the image is unchanged", nodes ? nodes->len : 0,
-                image->len, zkh_image_tree_words(image->len));
-    const Pages& g = c->args->pages[0];
-    const uint32_t W = (uint32_t)image->len;
-    bind_thread(ctx);
-    Tmp dpages;
-    BadRow bad;
-    ZKH_TRY(zkh_copy_from(ctx, "pages_record", (const uint32_t*)&g, sizeof(Pages) / 4, dpages.out()));
-    ZKH_TRY(bad.init(ctx));
-    const uint32_t nb = (A + LINK_THREADS - 1) / LINK_THREADS;
-    {
-        ProfScope prof(ctx, "page_out_check", 8.0 * A);
-        k_page_out<false><<<nb, LINK_THREADS, 0, ctx->stream>>>(data->ptr(), (const Pages*)dpages->ptr(), (uint32_t)n, A, image->ptr(), W, bad.ptr(), bad.extra_ptr());
-        ZKH_TRY(last_launch_error("page_out_check"));
-    }
-    ZKH_TRY(bad.read(ctx));
-    if (bad.found) return page_refusal(ctx, "page_out", ": the image is unchanged", g, data, n, bad.lo, W, nullptr);
-    {
-        ProfScope prof(ctx, "page_out_write", 16.0 * A);
-        k_page_out<true><<<nb, LINK_THREADS, 0, ctx->stream>>>(data->ptr(), (const Pages*)dpages->ptr(), (uint32_t)n, A, image->ptr(), W, bad.ptr(), bad.extra_ptr());
-        ZKH_TRY(last_launch_error("page_out_write"));
-    }
-    if (!nodes) return nullptr;
-    const uint32_t D = bad.extra + 1;                   // the table passed: its rows are [0, D), and row D - 1 left its index (none: all ones, D = 0)
-    ZKH_REQUIRE(D <= A, "page_out: the check pass left %u pages on %u active rows", D, A);
-    return image_tree_update(ctx, data->ptr() + (size_t)g.dst[PG_ADDR] * n, D, image, nodes);
-}
-
-// zkh_page_out_proof: the check pass with the fourth rule, one read-back (the refused row; D), then the proof from `nodes` (image.hip)
-const char* page_out_proof(zkh_ctx* ctx, const zkh_circuit* c, size_t po2, size_t zk_cycles, const zkh_buf* data, const zkh_buf* image, const zkh_buf* nodes,
-                           zkh_buf* proof) {
-    ZKH_REQUIRE(zkh_circuit_pages(c), "page_out_proof: the circuit's arguments hold no PAGES record (ZKA1 version 7)");
-    size_t n;
-    uint32_t A;
-    ZKH_TRY(trace_rows("page_out_proof", c, po2, zk_cycles, nullptr, data, nullptr, &n, &A));
-    ZKH_REQUIRE(image->len <= 0xffffffffull, "page_out_proof: an image of %zu words (at most 2^32 - 1)", image->len);
-    ZKH_REQUIRE(image->len && nodes->len == zkh_image_tree_words(image->len), "page_out_proof: nodes of %zu words; an image of %zu words has a tree of %zu (zkh_image_tree_words)",
-                nodes->len, image->len, zkh_image_tree_words(image->len));
-    const Pages& g = c->args->pages[0];
-    const uint32_t W = (uint32_t)image->len;
-    bind_thread(ctx);
-    Tmp dpages;
-    BadRow bad;
-    ZKH_TRY(zkh_copy_from(ctx, "pages_record", (const uint32_t*)&g, sizeof(Pages) / 4, dpages.out()));
-    ZKH_TRY(bad.init(ctx));
-    const uint32_t nb = (A + LINK_THREADS - 1) / LINK_THREADS;
-    {
-        ProfScope prof(ctx, "page_out_check", 16.0 * A);            // p_on and p_addr; p_in and the tree's word
-        k_page_out<false, true><<<nb, LINK_THREADS, 0, ctx->stream>>>(data->ptr(), (const Pages*)dpages->ptr(), (uint32_t)n, A, nodes->ptr() + nodes->len / 2, W, bad.ptr(),
-                                                                      bad.extra_ptr());
-        ZKH_TRY(last_launch_error("page_out_check"));
-    }
-    ZKH_TRY(bad.read(ctx));
-    if (bad.found) return page_refusal(ctx, "page_out_proof", "", g, data, n, bad.lo, W, nodes);
-    const uint32_t D = bad.extra + 1;                   // as in page_out: the table's rows are [0, D)
-    ZKH_REQUIRE(D <= A, "page_out_proof: the check pass left %u pages on %u active rows", D, A);
-    const size_t bound = zkh_image_proof_words(W, D);
-    ZKH_REQUIRE(proof->len >= bound && bound <= 0xffffffffull, "page_out_proof: a proof buffer of %zu words; %u pages over an image of %u words take up to %zu (zkh_image_proof_words)",
-                proof->len, D, W, bound);
-    const uint32_t* cols = data->ptr();
-    return image_proof_build(ctx, cols + (size_t)g.dst[PG_ADDR] * n, cols + (size_t)g.dst[PG_IN] * n, cols + (size_t)g.dst[PG_OUT] * n, D, image->len, nodes, proof);
-}
-}  // namespace
-
-extern "C" const char* zkh_page_out_proof(zkh_ctx* ctx, const zkh_circuit* c, size_t po2, size_t zk_cycles, const zkh_buf* data, const zkh_buf* image,
-                                          const zkh_buf* nodes, zkh_buf* proof) {
-    ZKH_REQUIRE(ctx && c && data && image && nodes && proof, "page_out_proof: null argument");
-    return page_out_proof(ctx, c, po2, zk_cycles, data, image, nodes, proof);
-}
-
-extern "C" const char* zkh_page_out(zkh_ctx* ctx, const zkh_circuit* c, size_t po2, size_t zk_cycles, const zkh_buf* data, zkh_buf* image) {
-    ZKH_REQUIRE(ctx && c && data && image, "page_out: null argument");
-    return page_out(ctx, c, po2, zk_cycles, data, image, nullptr);
-}
-
-extern "C" const char* zkh_page_out_tree(zkh_ctx* ctx, const zkh_circuit* c, size_t po2, size_t zk_cycles, const zkh_buf* data, zkh_buf* image, zkh_buf* nodes) {
-    ZKH_REQUIRE(ctx && c && data && image && nodes, "page_out: null argument");
-    return page_out(ctx, c, po2, zk_cycles, data, image, nodes);
 }

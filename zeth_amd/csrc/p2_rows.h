@@ -14,7 +14,7 @@
 // table_refusal) and the opening of their entry points (page_open).  The tail rows of all three are k_rows_tail's (p2_rows_tail).
 #pragma once
 #include "circuit.h"
-#include "image_tree.h"
+#include "zku1.h"
 #include "poseidon2.h"
 
 namespace zkh {
@@ -121,16 +121,15 @@ static __device__ __forceinline__ void pj_join_sibling(uint32_t* s, uint32_t t, 
 // against 0.442 ms at h = 23), so it keeps the rule written out; k_page_root walks with the two helpers above.  pj_node_beside has
 // pj_join_sibling as its one caller since k_tree_blocks went back to its own text.
 
-// ---- THE TABLE'S CHECK.  Block-wide, THREADS lanes: the lowest row of the table's D rows (stride 3, the address first) whose address
-// is outside the image of W words or does not follow a smaller one, PJ_NONE if there is none.  In two steps, so that a kernel can read
+// ---- THE TABLE'S CHECK.  Block-wide, THREADS lanes: the lowest row of the table's D rows that the table's rule refuses (zku1.h
+// table_row_refused: an address outside the image of W words, or one that does not follow a smaller one), PJ_NONE if there is none.  In two steps, so that a kernel can read
 // the table for sums of its own in between (k_tree_check: what it reads last is what the next kernel finds in the cache).
 // pj_table_scan: the lowest such row among the lane's own, i = lane, lane + THREADS, ...
 template <uint32_t THREADS>
 static __device__ __forceinline__ uint32_t pj_table_scan(const uint32_t* __restrict__ table, uint32_t D, uint32_t W) {
     uint32_t bad = PJ_NONE;
     for (uint32_t i = threadIdx.x; i < D && bad == PJ_NONE; i += THREADS) {
-        const uint32_t a = table[3 * (size_t)i];
-        if (a >= W || (i && table[3 * (size_t)(i - 1)] >= a)) bad = i;
+        if (table_row_refused(i, table_addr(table, i), i ? table_addr(table, i - 1) : 0, W)) bad = i;
     }
     return bad;
 }
@@ -153,16 +152,14 @@ static __device__ __forceinline__ uint32_t pj_table_lowest(uint32_t bad, const u
     const uint32_t i = low[0];
     if (t == 0) {
         rec[TABLE_ROW] = i;
-        rec[TABLE_A] = i != PJ_NONE ? table[3 * (size_t)i] : 0;
-        rec[TABLE_BEFORE] = i != PJ_NONE && i ? table[3 * (size_t)(i - 1)] : 0;
+        rec[TABLE_A] = i != PJ_NONE ? table_addr(table, i) : 0;
+        rec[TABLE_BEFORE] = i != PJ_NONE && i ? table_addr(table, i - 1) : 0;
     }
     return i;
 }
 // HOST: the refusal the record's words 0 .. 2 stand for, after "`who`: "; nullptr if no row is refused
 inline const char* table_refusal(const char* who, const uint32_t* r, uint32_t W) {
-    if (r[TABLE_ROW] == PJ_NONE) return nullptr;
-    if (r[TABLE_A] >= W) return make_err("%s: row %u: address %u outside the image of %u words", who, r[TABLE_ROW], r[TABLE_A], W);
-    return make_err("%s: row %u: address %u does not follow a smaller one (row %u: address %u)", who, r[TABLE_ROW], r[TABLE_A], r[TABLE_ROW] - 1, r[TABLE_BEFORE]);
+    return r[TABLE_ROW] == PJ_NONE ? nullptr : refuse_row(who, r[TABLE_ROW], r[TABLE_A], r[TABLE_BEFORE], W);
 }
 
 // ---- HOST: what the entry points share
@@ -201,14 +198,15 @@ const char* page_open(const char* who, const PageShape& sh, zkh_ctx* ctx, const 
     uint32_t head[PROOF_HEAD_MAX] = {0};
     ZKH_TRY(zkh_read(ctx, proof, head, 0, proof_words < PROOF_HEAD_MAX ? proof_words : PROOF_HEAD_MAX));
     ZKH_TRY(image_proof_header(who, head, proof_words));
-    o->W = head[1];
-    o->D = head[2];
+    const ProofShape ps = proof_shape(head);
+    o->W = ps.W;
+    o->D = ps.D;
     ZKH_TRY(image_shape(o->W));
-    o->h = image_height(o->W);
+    o->h = ps.h;                                        // the header passed: h is W's
     o->L = image_leaves(o->W);
     ZKH_REQUIRE(nodes_before->len == 16 * o->L && nodes_after->len == 16 * o->L, "%s: nodes of %zu and %zu words; an image of %u words has a tree of %zu (zkh_image_tree_words)",
                 who, nodes_before->len, nodes_after->len, o->W, 16 * o->L);
-    o->table = proof->ptr() + 5 + o->h;
+    o->table = proof->ptr() + ps.table;
     return nullptr;
 }
 

@@ -122,7 +122,7 @@ __global__ __launch_bounds__(64) void k_page_paths(uint32_t* __restrict__ data, 
     if (i >= 2 * N || rec[PR_ROW] != PJ_NONE) return;
     const uint32_t slot = i >> 1, side = i & 1;
     const bool real = first + slot < D;
-    const uint32_t a = real ? table[3 * (size_t)(first + slot)] : 0;   // < W <= 8 L: the record holds no refusal
+    const uint32_t a = real ? table_addr(table, first + slot) : 0;   // < W <= 8 L: the record holds no refusal
     const uint32_t* open = real ? nodes_before : nodes_after;          // a no-op opens the tree after the page-out
     uint32_t s[PJ_T];
     for (uint32_t t = 0; t < h; t++) {
@@ -145,7 +145,7 @@ __global__ __launch_bounds__(64) void k_page_root(const uint32_t* __restrict__ d
     if (rec[PR_ROW] != PJ_NONE) return;
     if (lane >= 8 && lane < 16 && D - first > N) rec[PR_ROOTS + lane] = data[(size_t)(PD_SN + lane - 8) * n + (size_t)PJ_BLOCK * h * N - 1];
     if (lane != 0 || first == 0) return;
-    const uint32_t a = table[3 * (size_t)(first - 1)];                 // < W <= 8 L: the record holds no refusal
+    const uint32_t a = table_addr(table, first - 1);                 // < W <= 8 L: the record holds no refusal
     uint32_t s[CELLS];
     for (uint32_t t = 0; t < h; t++) {
         if (t == 0) pj_pair_words(s, a & ~15u, a, true, nodes_before, nodes_after, L);
@@ -169,13 +169,13 @@ __global__ __launch_bounds__(PG_THREADS) void k_page_book(uint32_t* __restrict__
     const uint32_t k = r % PJ_BLOCK, blk = r / PJ_BLOCK, t = blk % h, slot = blk / h;
     const bool real = first + slot < D;
     const size_t row = (size_t)first + slot;
-    const uint32_t a = real ? table[3 * row] : 0;
+    const uint32_t a = real ? table_addr(table, row) : 0;
     uint32_t v = 0;
     if (col < PD_B) v = (k == 0 && t == 0 && (a & 15) == col - PD_E) ? R1 : 0;
     else if (col == PD_B) v = (k == 0 && t > 0 && ((a >> (3 + t)) & 1)) ? R1 : 0;
     else if (col == PD_ADDR) v = pj_encode(a);
-    else if (col == PD_W_IN) v = real ? table[3 * row + 1] : nodes_after[8 * L];
-    else if (col == PD_W_OUT) v = real ? table[3 * row + 2] : nodes_after[8 * L];
+    else if (col == PD_W_IN) v = real ? table_row(table, row)[ROW_IN] : nodes_after[8 * L];
+    else if (col == PD_W_OUT) v = real ? table_row(table, row)[ROW_OUT] : nodes_after[8 * L];
     else if (col == PD_ACC) v = pj_encode(a & ((1u << (4 + t)) - 1));
     else v = slot ? data[(size_t)(PD_SN + col - PD_CUR) * n + (size_t)PJ_BLOCK * h * slot - 1] : rec[PR_ROOTS + col - PD_CUR];
     data[(size_t)col * n + r] = v;
@@ -195,8 +195,8 @@ __global__ __launch_bounds__(PG_THREADS) void k_page_order(uint32_t* __restrict_
     const size_t row = (size_t)first + slot;
     const bool live = row < D;
     const size_t before = live ? row : D;                              // the table's rows before this slot
-    const uint32_t a = live ? table[3 * row] : 0;
-    const uint32_t lo = before ? table[3 * (before - 1)] + 1 : 0;
+    const uint32_t a = live ? table_addr(table, row) : 0;
+    const uint32_t lo = before ? table_addr(table, before - 1) + 1 : 0;
     const uint32_t g = live ? a - lo : 0;
     const bool bits = t == 0 && k >= 1 && k <= PO_GAP_BITS;
     uint32_t v;

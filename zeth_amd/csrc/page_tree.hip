@@ -42,7 +42,7 @@ __device__ __forceinline__ uint32_t bit_length(uint32_t x) { return 32u - (uint3
 // the nodes update i of the part starts: all h of its path when it is the part's first, else those below the fork from the update before
 __device__ __forceinline__ uint32_t started(const uint32_t* __restrict__ table, uint32_t first, uint32_t i, uint32_t h) {
     if (i == 0) return h;
-    return bit_length((table[3 * (size_t)(first + i)] >> 4) ^ (table[3 * (size_t)(first + i - 1)] >> 4));
+    return bit_length((table_addr(table, first + i) >> 4) ^ (table_addr(table, first + i - 1) >> 4));
 }
 
 // grid (ceil(n / 256), 41): a function of (po2, zk_cycles) alone
@@ -88,8 +88,8 @@ __global__ __launch_bounds__(PT_THREADS) void k_tree_check(const uint32_t* __res
     if (t == 0) {
         const uint32_t end = first + count;
         uint32_t split = PJ_NONE;
-        if (end && end < D && table[3 * (size_t)(end - 1)] >> 4 == table[3 * (size_t)end] >> 4) split = end;
-        if (first && first < D && table[3 * (size_t)(first - 1)] >> 4 == table[3 * (size_t)first] >> 4) split = first;
+        if (end && end < D && table_addr(table, end - 1) >> 4 == table_addr(table, end) >> 4) split = end;
+        if (first && first < D && table_addr(table, first - 1) >> 4 == table_addr(table, first) >> 4) split = first;
         const unsigned long long total = count ? nodes[0] : 1;          // an empty part is the root block alone
         rec[TR_SPLIT] = split;
         rec[TR_NODES] = total > 0xfffffffeull ? 0xfffffffeu : (uint32_t)total;
@@ -111,7 +111,7 @@ __global__ __launch_bounds__(64) void k_tree_edges(uint32_t h, const uint32_t* _
     }
     if (lane >= 2) return;
     const uint32_t side = lane;
-    const uint32_t a = table[3 * (size_t)(side ? first + count - 1 : first)];      // < W <= 8 L: the record holds no refusal
+    const uint32_t a = table_addr(table, side ? first + count - 1 : first);      // < W <= 8 L: the record holds no refusal
     uint32_t s[CELLS];
     // the address rule written out, not p2_rows.h's pj_pair_words and pj_join_sibling: through them this one-lane kernel measured 4 to
     // 7 % slower (M24, medians of six runs: 0.342 against 0.329 ms at h = 17, 0.474 against 0.442 ms at h = 23)
@@ -168,7 +168,7 @@ __global__ __launch_bounds__(PT_THREADS) void k_tree_place(uint32_t* __restrict_
         if (t == PT_THREADS - 1) { tot[0] = p_incl; tot[1] = o_incl; }
         __syncthreads();
         if (c) {
-            const uint32_t id = half + (table[3 * (size_t)(first + i)] >> 4);
+            const uint32_t id = half + (table_addr(table, first + i) >> 4);
             ids[pair_base + p_incl - 1] = id;
             const uint32_t at = over_base + o_incl - above;
             for (uint32_t k = 1; k <= above; k++) ids[at + k - 1] = id >> k;
@@ -197,7 +197,7 @@ __global__ __launch_bounds__(64) void k_tree_blocks(uint32_t* __restrict__ data,
         for (uint32_t j = 0; j < 16; j++) s[j] = nodes_after[16 * (size_t)id + j];
     } else if (id) {
         // the part's edge: its first address on the old side (words below it are written), its last on the new side (words up to it are)
-        const uint32_t a = table[3 * (size_t)(side ? first + count - 1 : first)];
+        const uint32_t a = table_addr(table, side ? first + count - 1 : first);
         if (id >= L / 2) {                                                 // a pair block: 16 memory words
             const uint32_t x0 = (id - (uint32_t)(L / 2)) << 4;
             for (uint32_t j = 0; j < 16; j++) {
@@ -251,9 +251,9 @@ __device__ __forceinline__ bool part_touches(const uint32_t* __restrict__ table,
     uint32_t lo = 0, hi = count;
     while (lo < hi) {
         const uint32_t mid = lo + (hi - lo) / 2;
-        if (table[3 * (size_t)(first + mid)] < x) lo = mid + 1; else hi = mid;
+        if (table_addr(table, first + mid) < x) lo = mid + 1; else hi = mid;
     }
-    return lo < count && table[3 * (size_t)(first + lo)] < y;
+    return lo < count && table_addr(table, first + lo) < y;
 }
 
 // grid (ceil(31 B / 256), 10): the bookkeeping columns id .. gacc of the rows of the blocks, stores coalesced along the rows.  The lane
@@ -278,7 +278,7 @@ __global__ __launch_bounds__(PT_THREADS) void k_tree_book(uint32_t* __restrict__
             v = part_touches(table, first, count, x << (3 + t), (x + 1) << (3 + t)) ? R1 : 0;
         }
     } else {
-        const uint32_t base = first ? half + (table[3 * (size_t)(first - 1)] >> 4) + 1 : half;
+        const uint32_t base = first ? half + (table_addr(table, first - 1) >> 4) + 1 : half;
         const uint32_t lo = leaf ? (slot ? ids[slot - 1] + 1 : base) : (m ? ids[m - 1] + 1 : base);
         const uint32_t g = leaf ? id - lo : 0;
         if (col == TD_LO) {

@@ -27,4 +27,15 @@ __device__ __forceinline__ uint32_t block_scan(uint32_t v, uint32_t (*buf)[THREA
     return buf[cur][t];
 }
 
+// THE HEADS STAGE of a compaction over m items, item t on lane threadIdx.x of its workgroup (t >= m: `head` is 0): local[t] = the heads
+// among the items of t's workgroup up to t, sums[blockIdx.x] = the workgroup's heads.  The counter scan (sort.h scan_counters) turns `sums`
+// into the heads of the workgroups before each one; then head_rank, given the same `sums`, is the rank of the head at item t.
+template <uint32_t THREADS>
+__device__ __forceinline__ void scan_heads(uint32_t head, uint32_t t, uint32_t m, uint32_t (*buf)[THREADS], uint32_t* __restrict__ local, uint32_t* __restrict__ sums) {
+    const uint32_t incl = block_scan<THREADS>(head, buf, AddWrap());
+    if (t < m) local[t] = incl;
+    if (threadIdx.x == THREADS - 1) sums[blockIdx.x] = incl;
+}
+__device__ __forceinline__ uint32_t head_rank(const uint32_t* __restrict__ local, const uint32_t* __restrict__ sums, uint32_t t) { return local[t] + sums[blockIdx.x] - 1; }
+
 }  // namespace zkh

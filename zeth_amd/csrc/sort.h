@@ -1,6 +1,6 @@
 // sort.h — the stable sort of selected trace rows by packed keys that sort.hip owns (its kernels live there and nowhere else), for
-// its two callers: zkh_derive_sorted (sort.hip) and zkh_derive_links (links.hip), and the counter scan inside it, which the page scan of
-// links.hip launches as well.
+// its two callers: zkh_derive_sorted (sort.hip) and zkh_derive_links (links.hip), and the counter scan inside it, which every compaction
+// launches as well after its heads stage (scan.h scan_heads): the page scan of links.hip, the lists and the proof of image.hip.
 #pragma once
 #include <vector>
 
