@@ -514,8 +514,19 @@ const char* zkh_page_ordered_witgen(zkh_ctx*, const zkh_circuit*, size_t po2, si
  * zkh_page_tree_plan (HOST ONLY): the parts of a table with the addresses addrs[0 .. D) (strictly increasing, below image_words), greedy:
  * a part takes whole pairs of leaves while its nodes stay at most B, its first pair costing h nodes and every later one bit_length(pair
  * index xor the one before).  parts[2 p], parts[2 p + 1] = (first, count) of part p for p < parts_cap; *n_parts is the number of parts
- * whatever parts_cap is (D = 0: the one part (0, 0)).  The addresses are the host's: one read-back of D words; planning on the device
- * is out of scope.
+ * whatever parts_cap is (D = 0: the one part (0, 0)).  The addresses are the host's: a host that holds no copy of the table plans with
+ * zkh_page_tree_plan_device.
+ * zkh_page_tree_plan_device: the same plan over a table where it lies on the device: the words of `table` from `table_at` on are D rows
+ * of a ZKU1 table (stride 3, the address first; for a proof table_at = 5 + h), in any buffer, with no proof needed around them.  The plan
+ * as a prefix sum and a search (DESIGN.md "THE PLAN AS A SCAN"): a costs pass of 256 rows a workgroup, a scan of the workgroups' sums,
+ * one wave that walks from part to part; no atomics, one writer per cell.  parts, parts_cap and n_parts as zkh_page_tree_plan's; nodes
+ * (may be NULL): nodes[p] = the dirty nodes of part p (at most B), for p < parts_cap.  What is read back is the record and the parts
+ * written, never a word per row.  Refusals after "page_tree_plan_device: ", in this order: "null argument"; "po2 P out of range for Z
+ * zk_cycles"; the image's shape as zkh_page_tree_plan; "a table of D rows of 3 words at word T does not fit a buffer of N words"; "a
+ * table of D rows (at most 1073741824: ...)" (no table of more rows increases below the 2^30 words of the largest image); then the
+ * LOWEST row of the whole table that breaks the table's rule, in zkh_page_tree_witgen's words: "row R: address A outside the image of
+ * W words" or "row R: address A does not follow a smaller one (row R-1: address A')".  On a refusal nothing is written, *n_parts
+ * included.
  * zkh_page_tree_witgen: zkh_page_ordered_witgen's operands with the part as (first, count), `data` of 106 x 2^po2 words, out[18].  Both
  * trees are the WHOLE page-out's for every part.  One read-back at the end, no atomics, one writer per cell.  Refusals after
  * "page_tree_witgen: " (the shape ones also after "page_tree_code: " / "page_tree_plan: "): "the circuit does not have P2-TREE's shape
@@ -528,6 +539,8 @@ const char* zkh_page_ordered_witgen(zkh_ctx*, const zkh_circuit*, size_t po2, si
 const char* zkh_page_tree_code(zkh_ctx*, const zkh_circuit*, size_t po2, size_t zk_cycles, zkh_buf* code);
 const char* zkh_page_tree_plan(size_t po2, size_t zk_cycles, size_t image_words, const uint32_t* addrs, size_t D, size_t* parts, size_t parts_cap,
                                size_t* n_parts);
+const char* zkh_page_tree_plan_device(zkh_ctx*, size_t po2, size_t zk_cycles, size_t image_words, const zkh_buf* table, size_t table_at, size_t D, size_t* parts,
+                                      size_t parts_cap, size_t* n_parts, uint32_t* nodes);
 const char* zkh_page_tree_witgen(zkh_ctx*, const zkh_circuit*, size_t po2, size_t zk_cycles, const zkh_buf* code, const zkh_buf* proof, size_t proof_words,
                                  const zkh_buf* nodes_before, const zkh_buf* nodes_after, size_t first, size_t count, zkh_buf* data, uint32_t out[18],
                                  const uint32_t noise_key[8]);

@@ -553,6 +553,19 @@ impl HipCircuitHal {
         (0..n).map(|p| (parts[2 * p], parts[2 * p + 1])).collect()
     }
 
+    /// `page_tree_plan` over a table that lies on the device (`zkh_page_tree_plan_device`): the words of `table` from `table_at` on are
+    /// `rows` rows of a ZKU1 table (for a proof `table_at = 5 + h`).  Returns the parts and the dirty nodes of each; no word per row
+    /// comes back to the host, so this host needs no copy of the table.  Panics on the refusals include/zkhal.h lists.
+    pub fn page_tree_plan_device(&self, image_words: usize, table: &HipBuffer<u32>, table_at: usize, rows: usize, steps: usize) -> (Vec<(usize, usize)>, Vec<u32>) {
+        let po2 = steps.trailing_zeros() as usize;
+        let cap = rows.max(1);
+        let (mut parts, mut nodes, mut n) = (vec![0usize; 2 * cap], vec![0u32; cap], 0usize);
+        ffi(|| unsafe { sys::zkh_page_tree_plan_device(self.hal.ctx.0, po2, sys::ZK_CYCLES, image_words, table.raw, table_at, rows, parts.as_mut_ptr(), cap, &mut n,
+                                                       nodes.as_mut_ptr()) });
+        nodes.truncate(n);
+        ((0..n).map(|p| (parts[2 * p], parts[2 * p + 1])).collect(), nodes)
+    }
+
     /// The data group of P2-TREE for the part `[first, first + count)` of a page-out (`zkh_page_tree_witgen`), and the `out` globals:
     /// the root before the part, the root after it, then lo and hi (Montgomery words) bounding the heap ids of its pair blocks.  The
     /// other operands are `page_ordered_witgen`'s, `data` has 106 columns; the accum group comes from `zkh_accumulate`.  Part p + 1

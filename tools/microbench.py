@@ -20,7 +20,8 @@ zkh_page_circuit_witgen_part on a table of 4 N rows at first = 0, N, 2 N, 3 N ne
 alternating, with every call's stages; M23: P2-PAGE-ordered, zkh_page_ordered_witgen next to zkh_page_circuit_witgen_part at first = 0 and
 first = N of one table, and the seal of a part under both circuits, alternating, with every witness call's stages; M24: P2-TREE, the
 parts of one page-out of 662 267 addresses under p2_tree's plan and under P2-PAGE's, zkh_page_tree_witgen next to
-zkh_page_ordered_witgen and the seal of a part under both circuits, alternating, with every witness call's stages) on one MI355X, through
+zkh_page_ordered_witgen and the seal of a part under both circuits, alternating, with every witness call's stages; M25: P2-TREE's plan
+of M24's table by zkh_page_tree_plan_device next to the read-back of the table and zkh_page_tree_plan, alternating) on one MI355X, through
 the C ABI (HipHal).
 
 Each line of output is one JSON object: the op, its shape, the average wall time of one call (stream drained on both
@@ -1206,6 +1207,57 @@ def main() -> None:
                   flush=True)
             del before, after, proof, codes
         del datas
+    if want("M25"):
+        # P2-TREE's plan where the table lies: M24's table (the same draws in the same order, so `--only M25` plans the addresses `--only
+        # M24` seals) planned by the parent's path, the read-back of the table and zkh_page_tree_plan over every third word, and by
+        # zkh_page_tree_plan_device, in one run, alternating, M24's windows; the device call's three stages by their events.  The
+        # yardstick is the parent's path in this run.  Both plans must be the same; no threshold on any time.
+        import ctypes as C
+        from zeth_amd import hal as zhal
+        from zeth_amd.circuits import p2_page, p2_tree
+        runs, zk, D, cap = 7, 1994, 662267, 4096
+        spread = lambda ts: {"median_ms": round(float(np.median(ts)) * 1e3, 4), "min_ms": round(min(ts) * 1e3, 4), "max_ms": round(max(ts) * 1e3, 4)}   # noqa: E731
+        for W in (1 << 20, 1 << 26):
+            h = p2_page.tree_height(W)
+            image_h = rand_fp(rng, W)
+            addrs = np.sort(rng.choice(W, D, replace=False)).astype(np.int64)
+            outs = rand_fp(rng, D)
+            table = np.stack([addrs.astype(np.uint32), image_h[addrs], outs], axis=1).reshape(-1)
+            del image_h
+            proof = hal.copy_from("m25p", np.concatenate([np.array([0x5A4B5531, W, D, 0, h] + [0] * h, dtype=np.uint32), table]))
+            parts = {k: (C.c_size_t * (2 * cap))() for k in ("host", "device")}
+            count = {k: C.c_size_t() for k in parts}
+            got = {}
+            read_back = lambda: got.__setitem__("addrs", np.ascontiguousarray(proof.slice(5 + h, 3 * D).to_vec()[::3]))   # noqa: E731
+            host_plan = lambda: zhal._check(zhal._lib.zkh_page_tree_plan(args.po2, zk, W, zhal._ptr(got["addrs"]), D, parts["host"], cap,   # noqa: E731
+                                                                         C.byref(count["host"])))
+            parent = lambda: got.__setitem__("plan", hal.page_tree_plan(args.po2, zk, W, proof.slice(5 + h, 3 * D).to_vec()[::3]))   # noqa: E731
+            device = lambda: zhal._check(zhal._lib.zkh_page_tree_plan_device(hal.ctx, args.po2, zk, W, proof.h, 5 + h, D, parts["device"], cap,   # noqa: E731
+                                                                             C.byref(count["device"]), None))
+            wrapper = lambda: got.__setitem__("device_plan", hal.page_tree_plan_device(args.po2, zk, W, proof, 5 + h, D))   # noqa: E731
+            fns = [("parent_path_read_back_and_plan", parent), ("plan_device_call", device), ("read_back_alone", read_back), ("host_plan_alone", host_plan),
+                   ("plan_device_python_wrapper", wrapper)]
+            t = {name: [] for name, _ in fns}
+            for _ in range(runs):
+                for name, fn in fns:
+                    t[name].append(timed(hal, fn, args.reps))
+            assert got["plan"] == got["device_plan"] == p2_tree.parts_by_scan(args.po2, zk, W, addrs), "the device plan is not the host plan"
+            assert count["host"].value == count["device"].value == len(got["plan"]) and list(parts["host"]) == list(parts["device"])
+            hal.prof_enable(True)
+            hal.prof_reset()
+            for _ in range(args.reps):
+                device()
+            hal.sync()
+            stages = {r["name"]: {"calls_per_call": r["calls"] // args.reps, "ms_per_call": round(r["total_ms"] / args.reps, 4)} for r in hal.prof_get()
+                      if r["calls"] and r["name"].startswith("tree_plan_")}
+            hal.prof_enable(False)
+            med = {k: float(np.median(v)) for k, v in t.items()}
+            print(json.dumps({"bench": "M25", "library": os.path.basename(os.environ.get("ZKH_LIBRARY", "") or "libzkhal_mi355x.so"), "po2": args.po2,
+                              "image_words": W, "layers": h, "table_rows": D, "block_slots": p2_tree.block_slots(args.po2, zk), "parts": len(got["plan"]),
+                              "workgroups": -(-D // 256), "runs": runs, "reps": args.reps, **{k: spread(v) for k, v in t.items()}, "stages": stages,
+                              "device_over_parent": round(med["plan_device_call"] / med["parent_path_read_back_and_plan"], 4)}),
+                  flush=True)
+            del proof
     hal.close()
 
 

@@ -221,11 +221,8 @@ def slot_ids(h: int, B: int, pairs: Sequence[int]) -> List[int]:
     return ids + [0] * (B - 1 - len(ids)) + [1]
 
 
-def parts(po2: int, zk_cycles: int, W: int, addrs: Sequence[int]) -> List[Tuple[int, int]]:
-    """The plan of a page-out with the addresses `addrs` (strictly increasing, below W) as a chain of P2-TREE traces: [(first, count)],
-    part p the updates [first, first + count).  Greedy: a part takes whole pairs of leaves while its node count stays at most B; its
-    first pair costs h nodes, every later one bit_length(pair index xor the pair index before).  No address: the one part (0, 0).
-    zkh_page_tree_plan is the same plan in C."""
+def plan_shape(po2: int, zk_cycles: int, W: int) -> Tuple[int, int]:
+    """(h, B) of a plan, or the ValueError of a shape no plan exists for"""
     if W <= 16:
         raise ValueError(f"an image of {W} words has a single pair of leaves (W > 16)")
     h, B = tree_height(W), block_slots(po2, zk_cycles)
@@ -233,6 +230,15 @@ def parts(po2: int, zk_cycles: int, W: int, addrs: Sequence[int]) -> List[Tuple[
         raise ValueError(f"an image of {W} words has h {h} ({MIN_H} .. {MAX_H})")
     if B < h:
         raise ValueError(f"no room for the h {h} nodes of one path in {B} block slots (po2 {po2}, {zk_cycles} zk_cycles)")
+    return h, B
+
+
+def parts(po2: int, zk_cycles: int, W: int, addrs: Sequence[int]) -> List[Tuple[int, int]]:
+    """The plan of a page-out with the addresses `addrs` (strictly increasing, below W) as a chain of P2-TREE traces: [(first, count)],
+    part p the updates [first, first + count).  Greedy: a part takes whole pairs of leaves while its node count stays at most B; its
+    first pair costs h nodes, every later one bit_length(pair index xor the pair index before).  No address: the one part (0, 0).
+    zkh_page_tree_plan is the same plan in C."""
+    h, B = plan_shape(po2, zk_cycles, W)
     plan, first, nodes, before = [], 0, 0, None
     for i, a in enumerate(addrs):
         q = int(a) >> 4
@@ -245,6 +251,37 @@ def parts(po2: int, zk_cycles: int, W: int, addrs: Sequence[int]) -> List[Tuple[
         nodes += cost
         before = q
     return plan + [(first, len(addrs) - first)] if len(addrs) else [(0, 0)]
+
+
+def cost_sums(addrs: Sequence[int]) -> np.ndarray:
+    """S of the plan as a scan (DESIGN.md "THE PLAN AS A SCAN"): S[i] = c_0 + .. + c_i with c_0 = 0 and c_i = bit_length(q_i xor
+    q_{i-1}) for the pair indices q = a >> 4, which is 0 where row i stays in row i - 1's pair of leaves"""
+    q = np.asarray(addrs, dtype=np.int64).reshape(-1) >> 4
+    c = np.zeros(q.size, dtype=np.int64)
+    if q.size > 1:
+        c[1:] = np.frexp((q[1:] ^ q[:-1]).astype(np.float64))[1]             # bit_length of an integer below 2^53; frexp(0) has exponent 0
+    return np.cumsum(c)
+
+
+def parts_by_scan(po2: int, zk_cycles: int, W: int, addrs: Sequence[int]) -> List[Tuple[int, int]]:
+    """`parts` as a prefix sum and a search, the formulation zkh_page_tree_plan_device runs on the GPU: a part that starts at row f
+    holds h + S[i] - S[f] nodes after row i, so the next part starts at the first i with S[i] > S[f] + B - h (S rises only where a
+    new pair starts, so the search lands on one), and D ends the last part.  The same ValueErrors as `parts`."""
+    h, B = plan_shape(po2, zk_cycles, W)
+    S = cost_sums(addrs)
+    D, plan, f = S.size, [], 0
+    while f < D:
+        nxt = int(np.searchsorted(S, S[f] + B - h, side="right"))            # the first i with S[i] > S[f] + B - h, D if there is none
+        plan.append((f, nxt - f))
+        f = nxt
+    return plan or [(0, 0)]
+
+
+def part_nodes(h: int, addrs: Sequence[int], plan: Sequence[Tuple[int, int]]) -> List[int]:
+    """the dirty nodes of every part of `plan` over the table's addresses, from the same S: h + S[first + count - 1] - S[first]; the
+    empty part of an empty table is the root block alone"""
+    S = cost_sums(addrs)
+    return [h + int(S[first + count - 1] - S[first]) if count else 1 for first, count in plan]
 
 
 @functools.lru_cache(maxsize=4096)

@@ -18,7 +18,10 @@
 // k_tree_place: ONE workgroup, one lane per update, 256 at a time: the slot list (p2_tree.py slot order) by two block scans with a
 // carry.  k_tree_blocks: one lane per (slot, side), the literal round loop of k_p2join_blocks.  k_tree_book: one lane per (row,
 // bookkeeping column).  The tail rows are k_rows_tail's (circuit.hip, p2_rows_tail).  One writer per cell (of the record and the slot list
-// too), one read-back of the record at the end.
+// too), one read-back of the record at the end.  The plan of the parts, on the host (zkh_page_tree_plan) and over the table where it
+// lies (zkh_page_tree_plan_device: k_plan_costs, k_plan_scan, k_plan_walk, many workgroups), is described above those kernels.
+#include <vector>
+
 #include "p2_rows.h"
 #include "scan.h"
 
@@ -291,6 +294,109 @@ __global__ __launch_bounds__(PT_THREADS) void k_tree_book(uint32_t* __restrict__
     data[(size_t)col * n + r] = v;
 }
 
+// ---- THE PLAN ON THE DEVICE (zkh_page_tree_plan_device; DESIGN.md "THE PLAN AS A SCAN").  Row i costs c_i = bit_length(q_i xor q_{i-1})
+// for the pair indices q = a >> 4 (c_0 = 0; 0 inside a pair), S_i = c_0 + .. + c_i, and the part that starts at row f ends before the first
+// row i with S_i > S_f + B - h.  S_i = base[i / 256] + local[i]: k_plan_costs leaves the locals and every workgroup's sum, k_plan_scan
+// turns the sums into the bases (base[nb] is S_{D-1}), k_plan_walk follows f.  32 bits hold every S that is read: a table that passes
+// the table's rule starts every node of the tree of pairs at most once, so S_{D-1} < 2^h <= 2^27, and the sums of a table that does not
+// pass are never read (they may wrap).  The record: the table's refusal in words 0 .. 2 (p2_rows.h TABLE_*), the number of parts, then
+// per part written (first, count, nodes).
+constexpr uint32_t PLAN_MAX_ROWS = 1u << 30;              // the words of the largest image (h = 27): no longer table can increase below W
+enum : uint32_t { PL_PARTS = 3, PL_WORDS = 4, PL_PART = 3, PL_EAGER = 20 };     // PL_EAGER: the parts the first read-back brings along
+struct MinOf { __device__ __forceinline__ uint32_t operator()(uint32_t a, uint32_t b) const { return a < b ? a : b; } };
+
+// grid ceil(D / 256), one lane per row: the row's cost into the workgroup's scan (scan_heads, with costs for heads: local[i] and
+// sums[workgroup]) and the workgroup's lowest refused row, PJ_NONE if it has none, into low[workgroup] (a min scan, no atomics)
+__global__ __launch_bounds__(PT_THREADS) void k_plan_costs(const uint32_t* __restrict__ table, uint32_t D, uint32_t W, uint32_t* __restrict__ local,
+                                                           uint32_t* __restrict__ sums, uint32_t* __restrict__ low) {
+    __shared__ uint32_t buf[2][PT_THREADS];
+    const uint32_t i = blockIdx.x * PT_THREADS + threadIdx.x;
+    uint32_t c = 0, bad = PJ_NONE;
+    if (i < D) {
+        const uint32_t a = table_addr(table, i), before = i ? table_addr(table, i - 1) : 0;
+        if (table_row_refused(i, a, before, W)) bad = i;
+        if (i) c = bit_length((a >> 4) ^ (before >> 4));
+    }
+    scan_heads<PT_THREADS>(c, i, D, buf, local, sums);
+    const uint32_t lowest = block_scan<PT_THREADS>(bad, buf, MinOf());
+    if (threadIdx.x == PT_THREADS - 1) low[blockIdx.x] = lowest;
+}
+
+// ONE workgroup, k_sort_scan's shape (a contiguous chunk of the nb workgroups per lane): the exclusive scan of `sums` in place with
+// the total behind it (sums[nb]), and the minimum of `low` riding along: the lowest refused row of the whole table into the record,
+// as pj_table_lowest leaves it
+__global__ __launch_bounds__(PT_THREADS) void k_plan_scan(uint32_t* __restrict__ sums, const uint32_t* __restrict__ low, uint32_t nb, const uint32_t* __restrict__ table,
+                                                          uint32_t* __restrict__ rec) {
+    __shared__ uint32_t buf[2][PT_THREADS];
+    const uint32_t t = threadIdx.x, chunk = (nb + PT_THREADS - 1) / PT_THREADS;
+    const uint32_t lo = min(t * chunk, nb), hi = min(lo + chunk, nb);
+    uint32_t sum = 0, bad = PJ_NONE;
+    for (uint32_t b = lo; b < hi; b++) {
+        sum += sums[b];
+        bad = MinOf()(bad, low[b]);
+    }
+    const uint32_t incl = block_scan<PT_THREADS>(sum, buf, AddWrap());
+    const uint32_t lowest = block_scan<PT_THREADS>(bad, buf, MinOf());
+    uint32_t run = incl - sum;
+    for (uint32_t b = lo; b < hi; b++) {
+        const uint32_t c = sums[b];
+        sums[b] = run;
+        run += c;
+    }
+    if (t == PT_THREADS - 1) {
+        sums[nb] = incl;
+        rec[TABLE_ROW] = lowest;
+        rec[TABLE_A] = lowest != PJ_NONE ? table_addr(table, lowest) : 0;
+        rec[TABLE_BEFORE] = lowest != PJ_NONE && lowest ? table_addr(table, lowest - 1) : 0;
+    }
+}
+
+// ONE wave follows f_0 = 0, f_{k+1} = the first row i with S_i > S_{f_k} + B - h (D if there is none); the lanes search together.
+// First for the workgroup that holds i, the first b with base[b + 1] > limit: 64 probes a round over [lo, hi], of which hi is known to
+// pass (64-ary: two rounds for 4096 workgroups); then among that workgroup's 256 locals, four loads a lane.  S does not fall and
+// limit >= S_f (B >= h), so i > f: the walk ends after at most D parts.  Lane 0 writes the parts below `slots` and, last, their number.
+__global__ __launch_bounds__(64) void k_plan_walk(const uint32_t* __restrict__ local, const uint32_t* __restrict__ base, uint32_t nb, uint32_t D, uint32_t h, uint32_t B,
+                                                  uint32_t slots, uint32_t* __restrict__ rec) {
+    if (rec[TABLE_ROW] != PJ_NONE) return;
+    const uint32_t lane = threadIdx.x, total = base[nb];
+    uint32_t f = 0, k = 0;
+    while (f < D) {
+        const uint32_t s_f = base[f / PT_THREADS] + local[f], limit = s_f + (B - h);
+        uint32_t next = D;
+        if (total > limit) {
+            uint32_t lo = f / PT_THREADS, hi = nb - 1;
+            while (lo < hi) {
+                const uint32_t step = (hi - lo) / 64 + 1, p = lo + lane * step + step - 1;      // lane 63's probe is at or past hi
+                const uint32_t j = (uint32_t)__ffsll((long long)__ballot(p >= hi || base[p + 1] > limit)) - 1;
+                hi = min(lo + j * step + step - 1, hi);
+                lo += j * step;
+            }
+            const uint32_t row0 = lo * PT_THREADS, s0 = base[lo];
+            uint32_t s[PT_THREADS / 64];
+#pragma unroll
+            for (uint32_t j = 0; j < PT_THREADS / 64; j++) {
+                const uint32_t i = row0 + 64 * j + lane;
+                s[j] = i < D ? s0 + local[i] : 0;                                                // 0 never passes a limit
+            }
+#pragma unroll
+            for (uint32_t j = PT_THREADS / 64; j-- > 0;) {
+                const unsigned long long over = __ballot(s[j] > limit);
+                if (over) next = row0 + 64 * j + (uint32_t)__ffsll((long long)over) - 1;
+            }
+        }
+        const uint32_t s_last = next < D ? base[(next - 1) / PT_THREADS] + local[next - 1] : total;
+        if (lane == 0 && k < slots) {
+            uint32_t* part = rec + PL_WORDS + PL_PART * (size_t)k;
+            part[0] = f;
+            part[1] = next - f;
+            part[2] = h + s_last - s_f;
+        }
+        k++;
+        f = next;
+    }
+    if (lane == 0) rec[PL_PARTS] = k;
+}
+
 // the image's shape -> h, B
 const char* tree_image_shape(const char* who, size_t po2, size_t zk_cycles, size_t W, uint32_t* h_out, uint32_t* B_out) {
     ZKH_REQUIRE(W > 16, "%s: an image of %zu words has a single pair of leaves (W > 16: the root block is not a pair block)", who, W);
@@ -345,6 +451,67 @@ extern "C" const char* zkh_page_tree_plan(size_t po2, size_t zk_cycles, size_t i
         any = true;
     }
     emit(first, D);
+    *n_parts = count;
+    return nullptr;
+}
+
+// The same plan over a table that lies on the device (stride 3 from word `table_at` of `table` on, as in a ZKU1 proof): three launches,
+// and what comes back is the record and the parts written, never a word per row.  nodes[k]: part k's dirty nodes, under the same cap.
+extern "C" const char* zkh_page_tree_plan_device(zkh_ctx* ctx, size_t po2, size_t zk_cycles, size_t image_words, const zkh_buf* table, size_t table_at, size_t D,
+                                                 size_t* parts, size_t parts_cap, size_t* n_parts, uint32_t* nodes) {
+    const char* who = "page_tree_plan_device";
+    ZKH_REQUIRE(ctx && table && (parts || parts_cap == 0) && n_parts, "%s: null argument", who);
+    ZKH_REQUIRE(page_po2_ok(po2, zk_cycles), "%s: po2 %zu out of range for %zu zk_cycles", who, po2, zk_cycles);
+    uint32_t h, B;
+    ZKH_TRY(tree_image_shape(who, po2, zk_cycles, image_words, &h, &B));
+    ZKH_REQUIRE(table_at <= table->len && D <= (table->len - table_at) / PROOF_ROW, "%s: a table of %zu rows of %u words at word %zu does not fit a buffer of %zu words", who,
+                D, PROOF_ROW, table_at, table->len);
+    ZKH_REQUIRE(D <= PLAN_MAX_ROWS, "%s: a table of %zu rows (at most %u: the words of the largest image, and what keeps the sums of the costs in 32 bits)", who, D,
+                PLAN_MAX_ROWS);
+    if (D == 0) {                                       // the one empty part, the root block alone: nothing to launch
+        if (parts_cap) { parts[0] = parts[1] = 0; if (nodes) nodes[0] = 1; }
+        *n_parts = 1;
+        return nullptr;
+    }
+    const uint32_t rows = (uint32_t)D, W = (uint32_t)image_words, nb = (rows + PT_THREADS - 1) / PT_THREADS;      // h <= 27: W <= 2^30
+    const uint32_t slots = (uint32_t)(parts_cap < D ? parts_cap : D);                                              // a part has a row: at most D parts
+    const uint32_t* rows_at = table->ptr() + table_at;
+    bind_thread(ctx);
+    Tmp local, sums, rec;
+    ZKH_TRY(new_buf(ctx, rows, false, local.out()));
+    ZKH_TRY(new_buf(ctx, 2 * (size_t)nb + 1, false, sums.out()));       // the nb sums, their total, then the nb lowest refused rows
+    ZKH_TRY(new_buf(ctx, PL_WORDS + PL_PART * (size_t)slots, false, rec.out()));
+    uint32_t* low = sums->ptr() + nb + 1;
+    {
+        ProfScope prof(ctx, "tree_plan_costs", 16.0 * rows + 8.0 * nb);
+        k_plan_costs<<<nb, PT_THREADS, 0, ctx->stream>>>(rows_at, rows, W, local->ptr(), sums->ptr(), low);
+        ZKH_TRY(last_launch_error("tree_plan_costs"));
+    }
+    {
+        ProfScope prof(ctx, "tree_plan_scan", 12.0 * nb);
+        k_plan_scan<<<1, PT_THREADS, 0, ctx->stream>>>(sums->ptr(), low, nb, rows_at, rec->ptr());
+        ZKH_TRY(last_launch_error("tree_plan_scan"));
+    }
+    {
+        ProfScope prof(ctx, "tree_plan_walk", 4.0 * PL_PART * slots);
+        k_plan_walk<<<1, 64, 0, ctx->stream>>>(local->ptr(), sums->ptr(), nb, rows, h, B, slots, rec->ptr());
+        ZKH_TRY(last_launch_error("tree_plan_walk"));
+    }
+    const uint32_t eager = slots < PL_EAGER ? slots : PL_EAGER;
+    std::vector<uint32_t> r(PL_WORDS + PL_PART * (size_t)eager);
+    ZKH_TRY(zkh_read(ctx, rec.b, r.data(), 0, r.size()));
+    ZKH_TRY(table_refusal(who, r.data(), W));
+    const uint32_t count = r[PL_PARTS], written = count < slots ? count : slots;
+    if (written > eager) {                              // a long plan: the parts written, in a second read-back
+        r.resize(PL_WORDS + PL_PART * (size_t)written);
+        ZKH_TRY(zkh_read(ctx, rec.b, r.data() + PL_WORDS, PL_WORDS, PL_PART * (size_t)written));
+    }
+    for (uint32_t k = 0; k < written; k++) {
+        const uint32_t* part = r.data() + PL_WORDS + PL_PART * (size_t)k;
+        parts[2 * k] = part[0];
+        parts[2 * k + 1] = part[1];
+        if (nodes) nodes[k] = part[2];
+    }
     *n_parts = count;
     return nullptr;
 }

@@ -199,6 +199,7 @@ ABI = {
     "zkh_page_ordered_witgen": (_err, [_vp, _vp, _sz, _sz, _vp, _vp, _sz, _vp, _vp, _sz, _vp, _u32p, _u32p]),
     "zkh_page_tree_code": (_err, [_vp, _vp, _sz, _sz, _vp]),
     "zkh_page_tree_plan": (_err, [_sz, _sz, _sz, _u32p, _sz, C.POINTER(C.c_size_t), _sz, C.POINTER(C.c_size_t)]),
+    "zkh_page_tree_plan_device": (_err, [_vp, _sz, _sz, _sz, _vp, _sz, _sz, C.POINTER(C.c_size_t), _sz, C.POINTER(C.c_size_t), _u32p]),
     "zkh_page_tree_witgen": (_err, [_vp, _vp, _sz, _sz, _vp, _vp, _sz, _vp, _vp, _sz, _sz, _vp, _u32p, _u32p]),
     "zkh_circuit_derived_data_columns": (_err, [_vp, _u32p, _sz, C.POINTER(_sz)]),
     "zkh_upload_data_trace": (_err, [_vp, _vp, _sz, _sz, _vp, _u32p, _i]),
@@ -1033,6 +1034,23 @@ class HipHal:
     def page_tree_plan(self, po2: int, zk_cycles: int, image_words: int, addrs) -> list:
         """the module's page_tree_plan (host only: it needs no context)"""
         return page_tree_plan(po2, zk_cycles, image_words, addrs)
+
+    def page_tree_plan_device(self, po2: int, zk_cycles: int, image_words: int, table: Buffer, table_at: int, D: int, nodes: bool = False):
+        """page_tree_plan over a table that lies on the device (zkh_page_tree_plan_device; the numpy twin is p2_tree.parts_by_scan): the
+        words of `table` from `table_at` on are D rows of a ZKU1 table (stride 3, the address first; for a proof table_at = 5 + h).
+        -> the parts [(first, count), ...]; with nodes=True (plan, the dirty nodes of every part: p2_tree.part_nodes).  Nothing per row
+        comes back to the host.  Raises HalError as page_tree_plan does on the shape, on rows that do not fit the buffer, and with the
+        witness generator's message for the lowest row whose address does not follow a smaller one below `image_words`"""
+        who = "page_tree_plan_device"
+        if not isinstance(table, Buffer):
+            raise HalError(f"{who}: the table is a {type(table).__name__}, not a device Buffer (a host array is page_tree_plan's)")
+        if min(po2, zk_cycles, image_words, table_at, D) < 0:
+            raise HalError(f"{who}: negative argument (po2 {po2}, zk_cycles {zk_cycles}, image_words {image_words}, table_at {table_at}, D {D})")
+        cap = max(1, D)
+        parts, n, counts = (C.c_size_t * (2 * cap))(), C.c_size_t(), np.zeros(cap if nodes else 0, dtype=np.uint32)
+        _check(_lib.zkh_page_tree_plan_device(self.ctx, po2, zk_cycles, image_words, table.h, table_at, D, parts, cap, C.byref(n), _ptr(counts) if nodes else None))
+        plan = [(int(parts[2 * p]), int(parts[2 * p + 1])) for p in range(n.value)]
+        return (plan, [int(c) for c in counts[:n.value]]) if nodes else plan
 
     def page_tree_witgen(self, circuit: Circuit, po2: int, zk_cycles: int, code: Buffer, proof: Buffer, proof_words: int, nodes_before: Buffer,
                          nodes_after: Buffer, first: int, count: int, data: Buffer, noise_seed: int) -> np.ndarray:

@@ -442,15 +442,18 @@ class SegmentProver:
                                      self._open_path_chain(self.hal.page_ordered_code), self.hal.page_ordered_witgen,
                                      lambda seg, code, data: self.syn_accumulate(seg, data))
 
-    def seal_page_out_tree(self, segs, proof, proof_words: int, nodes_before, nodes_after, check: bool = False) -> list:
+    def seal_page_out_tree(self, segs, proof, proof_words: int, nodes_before, nodes_after, check: bool = False, plan: str = "host") -> list:
         """Seal a page-out of any size with P2-TREE (this prover's circuit: circuits/p2_tree.py, built with arguments=p2_tree.arguments())
         as a chain of parts: one block per DIRTY NODE of the tree instead of one path per word.  Part p's receipt's output is
         root_before ‖ root_after ‖ lo ‖ hi of its run of pairs of leaves (zkh_page_tree_witgen), so part p + 1 opens the root and
         starts at the `hi` part p left (`verify_page_tree_chain`).  The plan is zkh_page_tree_plan's over the table's addresses, read
         back once (D words).  The accum group is the circuit's bus (args_accumulate): a table that does not match the trees is refused
         there, and check=True names the key.  The other operands are seal_page_out_parts'; the control root does not depend on the
-        image's size.  -> the receipts, in the order of the parts."""
-        who = "seal_page_out_tree"
+        image's size.  plan="device" plans where the table lies (zkh_page_tree_plan_device over (proof, 5 + h, D)): only the header is
+        read back; the parts, and so the receipts, are the same.  -> the receipts, in the order of the parts."""
+        who, where = "seal_page_out_tree", plan
+        if where not in ("host", "device"):
+            raise _hal.HalError(f'{who}: plan="{where}" (the plan is made on the "host" or on the "device")')
 
         def open_chain(proof, po2, zk, fit):
             if not self.circuit.has_arguments():
@@ -459,8 +462,11 @@ class SegmentProver:
             W, D, h = (int(header[1]), int(header[2]), int(header[4])) if header.size > 4 else (0, 0, 0)
             if 5 + h + 3 * D > min(proof_words, proof.size()):
                 raise _hal.HalError(f"{who}: a proof of {proof_words} words does not hold its header and a table of {D} rows")
-            addrs = proof.slice(5 + h, 3 * D).to_vec()[::3] if D else np.zeros(0, dtype=np.uint32)
-            plan = self.hal.page_tree_plan(po2, zk, W, addrs)                  # refuses W <= 16, B < h, addresses out of order
+            if where == "device":                                              # the table stays where zkh_page_out_proof left it
+                plan = self.hal.page_tree_plan_device(po2, zk, W, proof, 5 + h, D)
+            else:
+                addrs = proof.slice(5 + h, 3 * D).to_vec()[::3] if D else np.zeros(0, dtype=np.uint32)
+                plan = self.hal.page_tree_plan(po2, zk, W, addrs)              # refuses W <= 16, B < h, addresses out of order
             fit(plan, D, f"{((1 << po2) - zk) // 31} block slots")
             return self.hal.page_tree_code(self.circuit, po2, zk), plan
 
