@@ -167,6 +167,10 @@ const char* zkh_combos_divide_all(zkh_ctx*, zkh_buf* combos, size_t cycles, size
 const char* zkh_eltwise_add_elem(zkh_ctx*, zkh_buf* out, const zkh_buf* a, const zkh_buf* b);
 const char* zkh_eltwise_copy_elem(zkh_ctx*, zkh_buf* out, const zkh_buf* in);
 const char* zkh_eltwise_zeroize_elem(zkh_ctx*, zkh_buf* io);   /* INVALID (0xffffffff) -> 0 */
+/* io[i] = io[i] % P in place, for any 32-bit words: where a caller's trace, whose raw words >= P are legal for the entry points that
+ * take arguments as data (zkh_derive_*, zkh_check_rows, zkh_check_bus, zkh_accumulate, the image calls), becomes the reduced words
+ * that every Hal-level op and zkh_prove_begin expect (below).  No upstream counterpart: upstream's Elem is reduced by construction. */
+const char* zkh_reduce_elem(zkh_ctx*, zkh_buf* io);
 const char* zkh_eltwise_sum_extelem(zkh_ctx*, zkh_buf* out_elem, const zkh_buf* in_ext);
 /* Hal::fri_fold(output, input, mix) */
 const char* zkh_fri_fold(zkh_ctx*, zkh_buf* out, const zkh_buf* in, const uint32_t mix[4]);
@@ -646,7 +650,12 @@ typedef struct zkh_seal_job zkh_seal_job;
  * zkh_prover_cache_code commits `code` once for this po2 (replacing an earlier entry); afterwards zkh_prove_begin /
  * zkh_prove_segment accept code == NULL for that po2 and share the resident group read-only.  Seals are byte-identical
  * to the ones made from the same code trace.  The caller vouches that the trace is the circuit's code trace for that
- * size (the verifier still checks the root against the control root).  zkh_prover_drop_code_cache releases the entries. */
+ * size (the verifier still checks the root against the control root).  zkh_prover_drop_code_cache releases the entries.
+ * REDUCED WORDS IN.  zkh_prove_begin, zkh_prove_segment, zkh_prover_cache_code and zkh_code_root take device-resident traces of
+ * reduced words (< P), like the Hal-level ops they drive (the NTTs, hash_rows, hash_fold, the eltwise ops): a raw word >= P is not
+ * refused, it seals to something no verifier accepts.  A caller whose traces may hold such words (the entry points over arguments
+ * as data read a cell as its residue, and the derives copy raw words) calls zkh_reduce_elem on code and data after zkh_derive_all
+ * and before zkh_prove_begin, as zkh_session_prove does for a segment with host traces. */
 const char* zkh_prover_cache_code(zkh_prover*, size_t po2, const zkh_buf* code);
 void zkh_prover_drop_code_cache(zkh_prover*);
 /* Root of the resident code group of this size.  The entry is keyed by po2 alone although a code trace also depends on

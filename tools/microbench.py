@@ -21,8 +21,8 @@ alternating, with every call's stages; M23: P2-PAGE-ordered, zkh_page_ordered_wi
 first = N of one table, and the seal of a part under both circuits, alternating, with every witness call's stages; M24: P2-TREE, the
 parts of one page-out of 662 267 addresses under p2_tree's plan and under P2-PAGE's, zkh_page_tree_witgen next to
 zkh_page_ordered_witgen and the seal of a part under both circuits, alternating, with every witness call's stages; M25: P2-TREE's plan
-of M24's table by zkh_page_tree_plan_device next to the read-back of the table and zkh_page_tree_plan, alternating) on one MI355X, through
-the C ABI (HipHal).
+of M24's table by zkh_page_tree_plan_device next to the read-back of the table and zkh_page_tree_plan, alternating; M26: zkh_reduce_elem
+at SYN-A's code and data widths next to zkh_eltwise_copy_elem over the same bytes, alternating) on one MI355X, through the C ABI (HipHal).
 
 Each line of output is one JSON object: the op, its shape, the average wall time of one call (stream drained on both
 sides of `reps` back-to-back calls), its ALGORITHMIC bytes (SURVEY.md §8a "B_alg": inputs read once + outputs written
@@ -1258,6 +1258,33 @@ def main() -> None:
                               "device_over_parent": round(med["plan_device_call"] / med["parent_path_read_back_and_plan"], 4)}),
                   flush=True)
             del proof
+    if want("M26"):
+        # zkh_reduce_elem (w := w % P in place; the caller-trace seal paths run it on code and data between zkh_derive_all and the
+        # accumulate) at SYN-A's widths next to zkh_eltwise_copy_elem moving the same bytes (one read and one write per word), in one
+        # run, alternating windows.  About 30 % of the words are >= P; the kernel's time does not depend on it, the result is checked.
+        from zeth_amd.circuits import syn_air
+        runs = 7
+        spread = lambda ts: {"median_ms": round(float(np.median(ts)) * 1e3, 4), "min_ms": round(min(ts) * 1e3, 4), "max_ms": round(max(ts) * 1e3, 4)}   # noqa: E731
+        desc = syn_air.syn_a()
+        for group, width in (("code", int(desc[4])), ("data", int(desc[5]))):
+            words = width * n
+            src = upload(hal, rng, "m26s", words)
+            head = src.slice(0, 1 << 20).to_vec()
+            raised = np.where((rng.random(head.size) < 0.3) & (head < (1 << 32) - P), head + np.uint32(P), head).astype(np.uint32)
+            src.write(raised, 0)
+            dst = hal.alloc_elem("m26d", words)
+            t = {"reduce_elem": [], "eltwise_copy_elem": []}
+            for _ in range(runs):
+                t["reduce_elem"].append(timed(hal, lambda: hal.reduce_elem(src), args.reps))
+                t["eltwise_copy_elem"].append(timed(hal, lambda: hal.eltwise_copy_elem(dst, src), args.reps))
+            assert np.array_equal(src.slice(0, 1 << 20).to_vec(), head), "reduce_elem did not give w % P"
+            med = {k: float(np.median(v)) for k, v in t.items()}
+            print(json.dumps({"bench": "M26", "library": os.path.basename(os.environ.get("ZKH_LIBRARY", "") or "libzkhal_mi355x.so"), "po2": args.po2,
+                              "group": group, "columns": width, "alg_GB": round(8 * words / 1e9, 4), "runs": runs, "reps": args.reps,
+                              **{k: spread(v) for k, v in t.items()}, "reduce_GB_per_s": round(8 * words / med["reduce_elem"] / 1e9, 1),
+                              "copy_GB_per_s": round(8 * words / med["eltwise_copy_elem"] / 1e9, 1),
+                              "reduce_over_copy": round(med["reduce_elem"] / med["eltwise_copy_elem"], 4)}), flush=True)
+            del src, dst
     hal.close()
 
 

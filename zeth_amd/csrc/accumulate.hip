@@ -39,7 +39,8 @@ struct BetaPows { uint32_t b[MAX_TUPLE][4]; };      // beta^1 .. beta^4
 
 __device__ __forceinline__ bool fp4_is_zero(const Fp4& x) { return (x.c[0].v | x.c[1].v | x.c[2].v | x.c[3].v) == 0; }
 
-// N / D of one row: the column's terms folded as N / D + f / d = (N d + f D) / (D d); rows past A give 0 / 1.  Fixed trip counts
+// N / D of one row: the column's terms folded as N / D + f / d = (N d + f D) / (D d); rows past A give 0 / 1.  Every cell is read as
+// its residue (cell(): raw words >= P are legal, and neither -f nor a product takes one).  Fixed trip counts
 // (MAX_TERMS, MAX_TUPLE) with guards, so that the batch arrays of the caller stay in registers.
 __device__ __forceinline__ void row_fraction(const uint32_t* __restrict__ code, const uint32_t* __restrict__ data, const ArgTerm* __restrict__ terms,
                                              const ArgCols cc, const BetaPows& bp, uint32_t n, uint32_t A, uint32_t r, uint32_t c,
@@ -55,14 +56,14 @@ __device__ __forceinline__ void row_fraction(const uint32_t* __restrict__ code, 
 #pragma unroll
             for (uint32_t e = 0; e < MAX_TUPLE; e++) {
                 if (e < t.c.w) {
-                    const Fp v = Fp::raw(group_ptr(code, data, t.c.tg[e])[(size_t)t.c.tc[e] * n + r]);
+                    const Fp v = Fp::raw(cell(code, data, t.c.tg[e], t.c.tc[e], n, r));
                     const Fp4 b(Fp::raw(bp.b[e][0]), Fp::raw(bp.b[e][1]), Fp::raw(bp.b[e][2]), Fp::raw(bp.b[e][3]));
                     d = d - b * v;
                 }
             }
             Fp f = Fp::one();
-            if (t.c.sel != NONE) f = Fp::raw(code[(size_t)t.c.sel * n + r]);
-            if (t.c.mg != NONE) f = f * Fp::raw(group_ptr(code, data, t.c.mg)[(size_t)t.c.mc * n + r]);
+            if (t.c.sel != NONE) f = Fp::raw(cell(code, data, GROUP_CODE, t.c.sel, n, r));
+            if (t.c.mg != NONE) f = f * Fp::raw(cell(code, data, t.c.mg, t.c.mc, n, r));
             if (t.neg) f = -f;
             if (fp4_is_zero(d)) atomicMin(bad, ((unsigned long long)r << 32) | (c << 2) | i);
             if (i == 0) { N = Fp4(f); D = d; }

@@ -456,6 +456,26 @@ __global__ void k_copy(uint32_t* out, const uint32_t* in, size_t n) {
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) out[i] = in[i];
 }
+// w % P for any 32-bit word: 2^32 < 3 P, so two conditional subtractions
+__device__ __forceinline__ uint32_t reduce_word(uint32_t w) {
+    w = w >= P ? w - P : w;
+    return w >= P ? w - P : w;
+}
+// io[i] %= P.  `head` words (0..3) lie before the first 16-byte boundary of the view; the body is read and written as uint4, one lane
+// per 16 bytes; the head and the tail (0..3 words each) go to the first lanes of the grid, which is never empty.
+__global__ void k_reduce(uint32_t* io, size_t n, size_t head) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const size_t quads = (n - head) / 4;
+    if (i < quads) {
+        uint4* p = (uint4*)(io + head) + i;
+        uint4 v = *p;
+        v.x = reduce_word(v.x); v.y = reduce_word(v.y); v.z = reduce_word(v.z); v.w = reduce_word(v.w);
+        *p = v;
+    }
+    if (i < head) io[i] = reduce_word(io[i]);
+    const size_t t = head + 4 * quads + i;
+    if (i < 3 && t < n) io[t] = reduce_word(io[t]);
+}
 __global__ void k_zeroize(uint32_t* io, size_t n) {
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n && io[i] == INVALID) io[i] = 0;
@@ -607,6 +627,17 @@ extern "C" const char* zkh_eltwise_copy_elem(zkh_ctx* c, zkh_buf* out, const zkh
     ProfScope ps(c, "eltwise_copy_elem", 8.0 * out->len);
     k_copy<<<blocks_for(out->len), TB, 0, c->stream>>>(out->ptr(), in->ptr(), out->len);
     return last_launch_error("eltwise_copy_elem");
+}
+extern "C" const char* zkh_reduce_elem(zkh_ctx* c, zkh_buf* io) {
+    ZKH_REQUIRE(c && io, "reduce_elem: null argument");
+    if (!io->len) return nullptr;
+    const size_t n = io->len;
+    size_t head = ((16 - ((uintptr_t)io->ptr() & 15)) & 15) / 4;
+    if (head > n) head = n;
+    const size_t quads = (n - head) / 4;
+    ProfScope ps(c, "reduce_elem", 8.0 * n);
+    k_reduce<<<blocks_for(quads ? quads : 1), TB, 0, c->stream>>>(io->ptr(), n, head);
+    return last_launch_error("reduce_elem");
 }
 extern "C" const char* zkh_eltwise_zeroize_elem(zkh_ctx* c, zkh_buf* io) {
     if (!io->len) return nullptr;

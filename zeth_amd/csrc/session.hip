@@ -608,6 +608,9 @@ static const char* seal_one(zkh_session* s, Lane& l, const zkh_segment& seg, uin
         ZKH_TRY(zkh_upload_data_trace(l.ctx, cir, seg.po2, ZKH_ZK_CYCLES, data, seg.host_data, 0));     // without what is derived below
         // what the library derives belongs to the data group: filled before it is committed, callback or not
         ZKH_TRY(zkh_derive_all(l.ctx, cir, seg.po2, ZKH_ZK_CYCLES, code, data));
+        // a caller's raw words >= P (and the derives' copies of them) end here: the seal takes reduced words
+        ZKH_TRY(zkh_reduce_elem(l.ctx, code));
+        ZKH_TRY(zkh_reduce_elem(l.ctx, data));
         out_global.assign(seg.out_global, seg.out_global + out_global.size());
         *witgen_s = now_s() - t0;
         zkh_seal_job* job = nullptr;

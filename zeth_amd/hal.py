@@ -143,6 +143,7 @@ ABI = {
     "zkh_eltwise_add_elem": (_err, [_vp, _vp, _vp, _vp]),
     "zkh_eltwise_copy_elem": (_err, [_vp, _vp, _vp]),
     "zkh_eltwise_zeroize_elem": (_err, [_vp, _vp]),
+    "zkh_reduce_elem": (_err, [_vp, _vp]),
     "zkh_eltwise_sum_extelem": (_err, [_vp, _vp, _vp]),
     "zkh_fri_fold": (_err, [_vp, _vp, _vp, _u32p]),
     "zkh_gather_sample": (_err, [_vp, _vp, _vp, _sz, _sz, _sz]),
@@ -782,6 +783,10 @@ class HipHal:
 
     def eltwise_zeroize_elem(self, io: Buffer) -> None:
         _check(_lib.zkh_eltwise_zeroize_elem(self.ctx, io.h))
+
+    def reduce_elem(self, io: Buffer) -> None:
+        """io[i] %= P in place (zkh_reduce_elem): a caller's trace of raw words becomes the reduced words that prove_begin takes"""
+        _check(_lib.zkh_reduce_elem(self.ctx, io.h))
 
     def eltwise_sum_extelem(self, out: Buffer, inp: Buffer) -> None:
         _check(_lib.zkh_eltwise_sum_extelem(self.ctx, out.h, inp.h))

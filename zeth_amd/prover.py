@@ -298,7 +298,9 @@ class SegmentProver:
         """Seal a segment whose code/data traces live in pinned HOST memory (hal.host_alloc views): enqueue both uploads
         on the context's stream (no host sync), then run the two-halves seal.  This is the PCIe-inclusive path.  A circuit whose
         arguments derive sorted copies, columns, linked accesses or lookup multiplicities gets them filled into the data trace first
-        (zkh_derive_all); of those columns only the blinding rows are uploaded (zkh_upload_data_trace).  The accum
+        (zkh_derive_all); of those columns only the blinding rows are uploaded (zkh_upload_data_trace).  The traces may hold raw words
+        >= P (a cell is read as its residue): after the derives both are reduced in place (zkh_reduce_elem), so the seal is a function
+        of the residues.  The accum
         comes from the built-in generator of kinds 1..3, else from zkh_accumulate when the circuit carries arguments.
         check: check the finished witness row by row before the seal is spent on it (check_witness, seal_with_accum), and when
         zkh_accumulate refuses a bus that does not balance, name the key (check_bus, args_accumulate).
@@ -311,7 +313,9 @@ class SegmentProver:
         self.hal.write_async(code, host_code)
         self.hal.upload_data_trace(self.circuit, seg.po2, seg.zk_cycles, data, host_data)
         self.hal.derive_all_paged(self.circuit, seg.po2, seg.zk_cycles, code, data, image)
-        builtin = 1 <= int(self.circuit.desc[13]) <= 3
+        self.hal.reduce_elem(code)           # raw words >= P end here: the accumulate reads residues, the seal takes reduced words
+        self.hal.reduce_elem(data)
+        builtin =1 <= int(self.circuit.desc[13]) <= 3
         acc = self.args_accumulate(seg, code, data, check=check) if not builtin and self.circuit.has_arguments() else self.syn_accumulate(seg, data)
         receipt = self.seal_with_accum(seg, code, data, out_global, acc, check=check)
         if page_out:
