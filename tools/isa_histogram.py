@@ -4,11 +4,16 @@ modelled issue cycles, against the multiply floor — the evidence behind "Posei
 
     python tools/isa_histogram.py > profiles/r03_hash_rows_isa_histogram.txt
     python tools/isa_histogram.py --csrc <another checkout>/zeth_amd/csrc      (the same count for another tree's hash.hip)
+    python tools/isa_histogram.py --kernel fold                                 (k_hash_fold: one permutation, no block loop)
+    python tools/isa_histogram.py --grouped                                     (the instantiation with the grouped partial rounds)
 
 Compiles zeth_amd/csrc/hash.hip for gfx950 with the build's flags (`-S`, device only), takes the first copy of the block
 loop of k_hash_rows (interior blocks of the sponge: 16 absorbed columns, one permutation), finds its inner loops from the
 backward branches and weights them by their trip counts (4 full rounds, 7 groups of three partial rounds, 4 full rounds, or
-3 where the last full round is peeled out of its loop and follows it as straight-line code).
+3 where the last full round is peeled out of its loop and follows it as straight-line code).  Where the partial rounds run as
+matrix products (poseidon2_linear.h) there are two inner loops, the full rounds', and the section between them is straight-line
+code that runs once per permutation; v_mfma_* instructions are counted apart from the VALU (another pipe) with their passes,
+and the half-wave swaps (v_permlane32_swap) are modelled at 4.0 cycles like the other two-register instructions.
 Code that a steady-state block does not run is weighted by what it is (path_weights): inside a loop of N trips the special
 cases of one trip (first / last partial group) count once per permutation; at block level the tail block's predicated loads
 and the alternative that the last block of a sponge takes count zero.
@@ -27,7 +32,8 @@ import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FOUR = ("v_mul_lo", "v_mul_hi", "v_mad_u64", "v_mad_i64", "v_add_f64", "v_fma_f64", "v_mul_f64", "v_cvt_f64", "v_min_u32", "v_max",
-        "v_add3", "v_lshl_add", "v_lshl_or", "v_and_or")
+        "v_add3", "v_lshl_add", "v_lshl_or", "v_and_or", "v_permlane32_swap")
+MFMA_PASSES = {"v_mfma_i32_32x32x32_i8": 16}     # 4 cycles per pass on the matrix pipe
 TRIPS = {"full": 4, "partial": 7}
 CLASSES = [
     ("s-box + reduction multiplies (v_mad_i64_i32, v_mad_u64_u32)", ("v_mad_i64", "v_mad_u64")),
@@ -37,6 +43,7 @@ CLASSES = [
     ("round-constant / plain adds, subs (v_add_u32, v_sub_u32, v_add_co ...)", ("v_add_u32", "v_sub_u32", "v_subrev_u32", "v_add_co", "v_addc", "v_sub_co", "v_subrev_co", "v_subb")),
     ("select / min (modular corrections, canonicalisation)", ("v_cndmask", "v_min_u32", "v_max")),
     ("64-bit shift-adds (v_lshl_add_u64: unreduced sum folds)", ("v_lshl_add", "v_lshlrev_b64", "v_lshrrev_b64", "v_ashrrev_i64")),
+    ("half-wave swaps (v_permlane32_swap: B operands, accumulator gather)", ("v_permlane32_swap",)),
     ("moves, logic, shifts (v_mov, v_and, v_or, v_xor, v_ashrrev, v_lshl ...)", ("v_mov", "v_and", "v_or", "v_xor", "v_ashrrev", "v_lshlrev", "v_lshrrev", "v_bfe", "v_perm", "v_readlane", "v_writelane", "v_readfirstlane", "v_accvgpr")),
 ]
 
@@ -46,7 +53,7 @@ def cycles(op: str) -> float:
 
 
 def valu_count(body, a, b):
-    return sum(1 for i in range(a, b) if body[i].startswith("\tv_"))
+    return sum(1 for i in range(a, b) if body[i].startswith("\tv_") and not body[i].startswith("\tv_mfma"))
 
 
 def path_weights(body, labels, outer, merged, trips):
@@ -147,7 +154,10 @@ def main():
         cmd = [B.HIPCC, *B.FLAGS, *B.EXTRA_FLAGS.get("hash.hip", []), "--cuda-device-only", "-S", os.path.join(csrc, "hash.hip"), "-o", out]
         subprocess.run(cmd, check=True, capture_output=True)
         lines = open(out).read().split("\n")
-    start = next(i for i, l in enumerate(lines) if re.match(r"^_ZN\S*k_hash_rows\S*:", l))
+    kernel = sys.argv[sys.argv.index("--kernel") + 1] if "--kernel" in sys.argv else "rows"
+    heads = [i for i, l in enumerate(lines) if re.match(r"^_ZN\S*k_hash_%s(I\S*Ev|E)\S*:" % kernel, l)]
+    want = "ILb0E" if "--grouped" in sys.argv else "ILb1E"           # templated on the linear partial rounds where that path exists
+    start = next((i for i in heads if want in lines[i]), heads[0])
     end = next(i for i in range(start, len(lines)) if lines[i].startswith(".Lfunc_end"))
     body = lines[start + 1:end]
     labels = {m.group(1): i for i, l in enumerate(body) if (m := re.match(r"^(\.LBB\d+_\d+):", l))}
@@ -159,7 +169,10 @@ def main():
     back.sort()
     # first loop nest = the block loop: from its header to the last branch back to that header (blocks the compiler placed
     # after that latch belong to the tail block's predicated loads and are not part of a steady-state block)
-    outer = (back[0][0], max(b[1] for b in back if b[0] == back[0][0]))
+    if kernel == "rows":
+        outer = (back[0][0], max(b[1] for b in back if b[0] == back[0][0]))
+    else:                                               # no block loop: the whole kernel is one permutation
+        outer = (0, len(body) - 1)
     inner = [b for b in back if outer[0] < b[0] and b[1] < outer[1]]
     # merge loops that share a region (rotated loops produce two backward branches into the same body)
     merged = []
@@ -168,16 +181,17 @@ def main():
             merged[-1] = (min(merged[-1][0], b[0]), max(merged[-1][1], b[1]))
         else:
             merged.append(b)
-    kinds = ["full", "partial", "full"] if len(merged) == 3 else ["?"] * len(merged)
+    kinds = ["full", "partial", "full"] if len(merged) == 3 else ["full", "full"] if len(merged) == 2 else ["?"] * len(merged)
     trips = [TRIPS.get(kind, 1) for kind in kinds]
-    # a peeled last full round: one more round body (hundreds of VALU instructions) between the third loop and the block loop's end
-    peeled = len(merged) == 3 and valu_count(body, merged[2][1] + 1, outer[1] + 1) > 300
+    # a peeled last full round: one more round body (hundreds of VALU instructions) between the last loop and the block loop's end
+    peeled = len(merged) in (2, 3) and valu_count(body, merged[-1][1] + 1, outer[1] + 1) > 300
     if peeled:
-        trips[2] -= 1
+        trips[-1] -= 1
     weight = path_weights(body, labels, outer, merged, trips)
     hist = collections.Counter()
     static = collections.Counter()
     other = collections.Counter()
+    mfma = collections.Counter()
     for i in range(outer[0], outer[1] + 1):
         l = body[i]
         if not l.startswith("\t") or not l.strip() or l.strip().startswith((".", ";")):
@@ -185,19 +199,26 @@ def main():
         op = l.strip().split()[0]
         if weight[i] == 0:
             continue
-        if op.startswith("v_"):
+        if op.startswith("v_mfma"):
+            mfma[op.replace("_e64", "")] += weight[i]
+        elif op.startswith("v_"):
             hist[op] += weight[i]
             static[op] += 1
         else:
             other[op.split("_")[0] + "_" + op.split("_")[1] if "_" in op else op] += weight[i]
     total = sum(hist.values())
     tot_cyc = sum(cycles(op) * n for op, n in hist.items())
-    print("# k_hash_rows, steady-state absorb block = ONE Poseidon2 permutation per lane (gfx950, hipcc -O3 -enable-misched=0)")
+    print(f"# {lines[start].rstrip(':')}")
+    print("# k_hash_%s, %s = ONE Poseidon2 permutation per lane (gfx950, hipcc -O3 -enable-misched=0)" %
+          (kernel, "steady-state absorb block" if kernel == "rows" else "the whole kernel"))
     print(f"# block loop at asm lines {outer[0]}..{outer[1]} of the kernel; inner loops " +
           ", ".join(f"{k} x{n} [{a}..{b}]" for (a, b), k, n in zip(merged, kinds, trips)) + (" + the last full round peeled" if peeled else ""))
     print(f"# dynamic VALU instructions per wave-permutation (static count x trip counts): {total:.0f}"
           f"   (hardware: SQ_INSTS_VALU / (leaves x blocks / 64) = 6.44 k, profiles/r02_sq_counters.txt)")
     print(f"# modelled issue cycles per wave-permutation: {tot_cyc:.0f}  (1024 SIMDs: {tot_cyc / 1024:.1f} SIMD-cycles per 64 permutations)")
+    if mfma:
+        print("# matrix pipe (not VALU): " + ", ".join(f"{n:.0f} x {op} = {n * MFMA_PASSES.get(op, 16) * 4:.0f} cycles" for op, n in mfma.items()) +
+              f"; straight-line VALU between the loops: {valu_count(body, merged[0][1] + 1, merged[1][0]) if len(merged) == 2 else 0}")
     print("#")
     print(f"# {'class':82s} {'instr':>7s} {'share':>6s} {'cycles':>8s} {'share':>6s}")
     seen = set()

@@ -42,6 +42,7 @@ inline const char* make_err(const char* fmt, ...) {
     } while (0)
 
 constexpr int ZKH_P2_PTAB = 486;            // partial-round table, layout in poseidon2.h (P2_TAB_WORDS)
+constexpr int ZKH_P2_LIN = 7318;            // the partial rounds as digit matrices, layout in poseidon2_linear.h (LIN_WORDS)
 constexpr int TW_BITS = 12;                 // two-level twiddle tables: w_{2^26}^(hi*4096 + lo), lo < 2^12, hi < 2^14
 constexpr int TW_SIZE = 1 << TW_BITS;
 constexpr int TW_HI_BITS = 14;              // (64 KiB per hi table: L2-resident; the index arithmetic of every kernel is unchanged)
@@ -55,6 +56,7 @@ struct DeviceTables {
     // Poseidon2 (Montgomery form)
     uint32_t* rc;        // 24*29
     uint32_t* diag;      // ZKH_P2_PTAB words: partial-round table
+    uint32_t* lin;       // ZKH_P2_LIN words: the partial rounds' affine map (k_hash_rows, k_hash_fold)
     // twiddles, Montgomery form
     uint32_t* tw_fwd_lo; uint32_t* tw_fwd_hi;   // w^lo, w^(hi*4096), w = ROU_FWD[MAX_LOG_N]
     uint32_t* tw_rev_lo; uint32_t* tw_rev_hi;   // same for ROU_REV[MAX_LOG_N]
@@ -94,7 +96,8 @@ struct zkh_ctx {
     zkh::DeviceTables tab;
     uint32_t rou_fwd[28], rou_rev[28];          // host copies (Montgomery)
     uint32_t h_rc[24 * 29], h_diag[zkh::ZKH_P2_PTAB]; // host copies of the Poseidon2 tables (rc - P; partial-round table)
-    std::multimap<size_t, void*> pool;          // stream-ordered free list (single in-order stream)
+    bool lin_ok = false;                        // tab.lin holds a table its builder accepted (poseidon2_linear.h)
+    std::multimap<size_t, void*> pool;         // stream-ordered free list (single in-order stream)
     size_t pool_bytes = 0, live_bytes = 0, peak_bytes = 0;
     bool prof = false;
     std::vector<zkh::ProfPending> pending;

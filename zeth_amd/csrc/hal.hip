@@ -140,14 +140,17 @@ static std::vector<uint32_t> powers(Fp base, size_t n) {
 
 extern "C" const char* zkh_poseidon2_set_constants(zkh_ctx* c, const uint32_t* rc, const uint32_t* diag) {
     bind_thread(c);
-    std::vector<uint32_t> r(24 * 29), d(ZKH_P2_PTAB);
+    std::vector<uint32_t> r(24 * 29), d(ZKH_P2_PTAB), l(ZKH_P2_LIN);
     for (int i = 0; i < 24 * 29; i++) r[i] = fp_encode(rc[i]).v - P;   // stored as rc - P: see poseidon2.h sbox7_rc
     ZKH_REQUIRE(poseidon2_partial_table(d.data(), rc, diag), "poseidon2_set_constants: the full rounds' scale chain does not end at R");
+    // a table whose digits leave their bounds is refused: hash_rows / hash_fold then run the grouped partial rounds with these constants
+    c->lin_ok = poseidon2_linear_table(l.data(), d.data(), rc, diag);
     memcpy(c->h_rc, r.data(), sizeof c->h_rc);
     memcpy(c->h_diag, d.data(), sizeof c->h_diag);
     ZKH_HIP(hipStreamSynchronize(c->stream));
     ZKH_HIP(hipMemcpy(c->tab.rc, r.data(), r.size() * 4, hipMemcpyHostToDevice));
     ZKH_HIP(hipMemcpy(c->tab.diag, d.data(), d.size() * 4, hipMemcpyHostToDevice));
+    ZKH_HIP(hipMemcpy(c->tab.lin, l.data(), l.size() * 4, hipMemcpyHostToDevice));
     return nullptr;
 }
 
@@ -205,6 +208,7 @@ static const char* ctx_init_tables(zkh_ctx* c) {
     ZKH_TRY(upload(&c->tab.shift_hi, powers(fp_pow(three, TW_SIZE), TW_HI_SIZE)));
     ZKH_TRY(upload(&c->tab.rc, std::vector<uint32_t>(24 * 29)));
     ZKH_TRY(upload(&c->tab.diag, std::vector<uint32_t>(ZKH_P2_PTAB)));
+    ZKH_TRY(upload(&c->tab.lin, std::vector<uint32_t>(ZKH_P2_LIN)));
     ZKH_TRY(zkh_poseidon2_set_constants(c, ZKH_P2_ROUND_CONSTANTS, ZKH_P2_M_INT_DIAG));
     ZKH_TRY(ntt_device_init(c));
     ZKH_HIP(hipMalloc((void**)&c->d_fail, 8));
@@ -230,7 +234,7 @@ extern "C" void zkh_ctx_destroy(zkh_ctx* c) {
     (void)hipSetDevice(c->device);
     (void)hipStreamSynchronize(c->stream);
     for (auto& kv : c->pool) (void)hipFree(kv.second);
-    uint32_t* t[] = {c->tab.rc, c->tab.diag, c->tab.tw_fwd_lo, c->tab.tw_fwd_hi, c->tab.tw_rev_lo, c->tab.tw_rev_hi,
+    uint32_t* t[] = {c->tab.rc, c->tab.diag, c->tab.lin, c->tab.tw_fwd_lo, c->tab.tw_fwd_hi, c->tab.tw_rev_lo, c->tab.tw_rev_hi,
                      c->tab.tile_fwd, c->tab.tile_rev, c->tab.shift_lo, c->tab.shift_hi, c->tab.layer_fwd, c->tab.layer_rev, c->tab.layer_fwd_lazy};
     for (auto p : t) (void)hipFree(p);
     for (auto& p : c->pending) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }

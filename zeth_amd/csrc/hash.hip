@@ -3,15 +3,19 @@
 // src/core/hash/poseidon2/mod.rs; un-vendored: /root/reference/Cargo.lock:5393).  Reached from
 // /root/reference/crates/host/src/lib.rs:137 (MerkleTreeProver::new inside Prover::commit_group).
 //
-// This is 31-bit modular integer work: no MFMA.  One lane owns one sponge; the 24-word state lives in VGPRs for
+// This is 31-bit modular integer work: a product of two VARIABLES has no use for the matrix cores.  A constant matrix
+// applied to 64 states at once has: in k_hash_rows and k_hash_fold the linear part of the 21 partial rounds is two int8
+// digit products on v_mfma_i32_32x32x32_i8 (poseidon2_linear.h; 54 MFMAs per wave-permutation, on a pipe of their own), and
+// only the serial cell-0 chain of those rounds stays on the VALU.  Every other caller keeps the grouped partial rounds.
+// One lane owns one sponge; the 24-word state lives in VGPRs for
 // the whole permutation (all cell loops are fully unrolled, round constants arrive through scalar loads), rows
 // are read column-major so a wave's 64 lanes read 64 consecutive words per column; four resident workgroups per CU
 // hide the column loads behind other waves' permutations (no software prefetch: it only cost VGPRs).  VALU-bound
 // by construction (~1356 Montgomery products per 64 absorbed bytes); the HBM side only has to keep up with
 // 16*W*n bytes per tree.  The permutation is poseidon2.h's lane-per-permutation form: signed Montgomery s-boxes with
 // no canonicalisation, M_ext on exact doubles (v_add_f64 / v_fma_f64 issue at the rate of a 32-bit multiply and have
-// the headroom a 31-bit prime denies a 32-bit word), partial rounds three at a time with unreduced weighted sums:
-// 6.4 k VALU instructions per 64 permutations.
+// the headroom a 31-bit prime denies a 32-bit word); partial rounds three at a time with unreduced weighted sums
+// (6.4 k VALU instructions per 64 permutations) or, in the two kernels above, as matrix products (5.0 k).
 #include "common.h"
 #include "image_tree.h"
 #include "poseidon2.h"
@@ -21,25 +25,33 @@ using namespace zkh;
 
 // common.h sizes the host / device / verifier copies of the partial-round table by hand; poseidon2.h lays the table out.
 static_assert(zkh::ZKH_P2_PTAB == zkh::P2_TAB_WORDS, "common.h ZKH_P2_PTAB must equal poseidon2.h P2_TAB_WORDS");
+static_assert(zkh::ZKH_P2_LIN == zkh::LIN_WORDS, "common.h ZKH_P2_LIN must equal poseidon2_linear.h LIN_WORDS");
 
 namespace {
 
 // Hal::hash_rows — one lane per leaf.
 // (register budgets for 2, 3 or 4 workgroups per CU compile to the same speed; capping residency at 2 or 3 workgroups
 // with LDS padding is 5 % slower alone and 5 % slower with three seals in flight: no SMT-style gain from leaving room)
+// LINEAR (lin: poseidon2_linear.h's table): the partial rounds run as int8 matrix products, wave-wide, so no lane leaves before the
+// last permutation: a lane past the end hashes the last row again and only its store is predicated.  Without it (a table the
+// builder refused) the grouped form runs.
+template <bool LINEAR>
 __global__ __launch_bounds__(256, 4) void k_hash_rows(uint32_t* __restrict__ out, const uint32_t* __restrict__ matrix,
                                                    size_t rows, uint32_t cols, const uint32_t* __restrict__ rc,
-                                                   const uint32_t* __restrict__ diag) {
-    const size_t r = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= rows) return;
+                                                   const uint32_t* __restrict__ diag, const uint32_t* __restrict__ lin) {
+    const size_t lane_row = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const bool live = lane_row < rows;
+    if (!LINEAR && !live) return;
+    const size_t r = live ? lane_row : rows - 1;
     uint32_t s[CELLS];
 #pragma unroll
     for (int i = 0; i < CELLS; i++) s[i] = 0;
     const uint32_t* src = matrix + r;
     const uint32_t full = cols / RATE, tail = cols % RATE;
     const uint32_t blocks = full + (tail || cols == 0 ? 1u : 0u);
-    // No register double-buffer for the next 16 columns: the grouped partial rounds need the VGPRs, and with >= 5
-    // waves per SIMD the loads of one wave hide under the permutations of the others.
+    // No register double-buffer for the next 16 columns: the partial rounds need the VGPRs (127 with the matrix products'
+    // operands and accumulators, 88 in the grouped form), and with 4 or 5 waves per SIMD the loads of one wave hide under
+    // the permutations of the others.
     // ONE call site of the permutation serves full blocks and the tail block: interior blocks keep the capacity, the
     // last block the digest, either one in s[16..24) (poseidon2_mix_sponge: a scalar branch around the last eight
     // reductions).  The capacity stays a nearly centred signed word from block to block; only the digest is canonicalised.
@@ -52,20 +64,27 @@ __global__ __launch_bounds__(256, 4) void k_hash_rows(uint32_t* __restrict__ out
 #pragma unroll
             for (int i = 0; i < RATE; i++) s[i] = (uint32_t)i < tail ? bsrc[(size_t)i * rows] : 0u;
         }
-        poseidon2_mix_sponge(s, rc, diag, b + 1 == blocks);
+        const uint32_t* lin_here = lin;
+        asm volatile("" : "+s"(lin_here));       // the table's 200 scalar words are loaded where they are used, not hoisted out of this loop and spilled
+        if (LINEAR) poseidon2_mix_sponge_linear(s, diag, lin_here, b + 1 == blocks);
+        else        poseidon2_mix_sponge(s, rc, diag, b + 1 == blocks);
 #pragma unroll
         for (int i = RATE; i < CELLS; i++) s[i] = p2_signed(s[i]);
     }
 #pragma unroll
     for (int i = 0; i < OUT; i++) s[i] = canon((int32_t)s[RATE + i]);
+    if (!live) return;
     uint4* o = (uint4*)(out + r * 8);
     o[0] = make_uint4(s[0], s[1], s[2], s[3]);
     o[1] = make_uint4(s[4], s[5], s[6], s[7]);
 }
 
 // one lane folds one parent of the layer of `output_size` parents: io[out+i] = H(io[in+2i] || io[in+2i+1])
+// (LINEAR: as in k_hash_rows; `store` predicates the write of a lane that only keeps its wave whole)
+template <bool LINEAR = false>
 __device__ __forceinline__ void fold_one(uint32_t* __restrict__ io, size_t input_size, size_t output_size, size_t i,
-                                         const uint32_t* __restrict__ rc, const uint32_t* __restrict__ diag) {
+                                         const uint32_t* __restrict__ rc, const uint32_t* __restrict__ diag,
+                                         const uint32_t* __restrict__ lin = nullptr, bool store = true) {
     const uint4* src = (const uint4*)(io + (input_size + 2 * i) * 8);
     uint32_t s[CELLS];
     const uint4 a = src[0], b = src[1], c = src[2], d = src[3];
@@ -73,19 +92,24 @@ __device__ __forceinline__ void fold_one(uint32_t* __restrict__ io, size_t input
     s[8] = c.x; s[9] = c.y; s[10] = c.z; s[11] = c.w; s[12] = d.x; s[13] = d.y; s[14] = d.z; s[15] = d.w;
 #pragma unroll
     for (int k = RATE; k < CELLS; k++) s[k] = 0;
-    poseidon2_mix_raw<0, OUT, RATE>(s, rc, diag);             // the zero capacity is not fed through the first M_ext
+    if (LINEAR) poseidon2_mix_raw_linear<0, OUT, RATE>(s, diag, lin);
+    else        poseidon2_mix_raw<0, OUT, RATE>(s, rc, diag);  // the zero capacity is not fed through the first M_ext
 #pragma unroll
     for (int k = 0; k < OUT; k++) s[k] = p2_finish(s[k]);
+    if (!store) return;
     uint4* o = (uint4*)(io + (output_size + i) * 8);
     o[0] = make_uint4(s[0], s[1], s[2], s[3]);
     o[1] = make_uint4(s[4], s[5], s[6], s[7]);
 }
 // Hal::hash_fold — one lane per parent
+template <bool LINEAR>
 __global__ __launch_bounds__(256, 4) void k_hash_fold(uint32_t* __restrict__ io, size_t input_size, size_t output_size,
-                                                   const uint32_t* __restrict__ rc, const uint32_t* __restrict__ diag) {
+                                                   const uint32_t* __restrict__ rc, const uint32_t* __restrict__ diag,
+                                                   const uint32_t* __restrict__ lin) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= output_size) return;
-    fold_one(io, input_size, output_size, i, rc, diag);
+    const bool live = i < output_size;
+    if (!LINEAR && !live) return;
+    fold_one<LINEAR>(io, input_size, output_size, live ? i : output_size - 1, rc, diag, lin, live);
 }
 // The image tree's update (image.hip): the same fold over a LIST of parents of the layer of `width` parents, lane t the parent list[t],
 // t < *count (the count is the device's: the compaction that made the list left it).  The lanes are dense: a wave runs a permutation
@@ -204,8 +228,39 @@ __global__ __launch_bounds__(256) void k_poseidon2_mix(uint32_t* __restrict__ io
     for (int q = 0; q < CELLS / 4; q++) p[q] = make_uint4(s[4 * q], s[4 * q + 1], s[4 * q + 2], s[4 * q + 3]);
 }
 
+// Test hook: ONE tile product of poseidon2_linear.h through the helpers the kernels use.  a: a 32 x 32 int8 matrix, row-major;
+// b: lane l's own eight words (the bytes k = 0..31 of column l); out[32 l + 4 o + (0, 1)] = (lo, hi) of output o (rows lin_row(o, 0..3)) of column l, gathered by the swaps (8 o < 32: 16 words used).
+__global__ __launch_bounds__(64) void k_lin_tile(const uint32_t* __restrict__ a, const uint32_t* __restrict__ b, uint32_t* __restrict__ out) {
+#if defined(__HIP_DEVICE_COMPILE__)               // (the matrix helpers exist in the device pass only)
+    const uint32_t lane = threadIdx.x;
+    uint32_t v[8];
+#pragma unroll
+    for (int q = 0; q < 8; q++) v[q] = b[8 * lane + q];
+    lin_operands(v);
+    const lin_v4 af = ((const lin_v4*)a)[2 * (lane & 31) + (lane >> 5)];      // row lane & 31, bytes 16 (lane >> 5) + 0..15
+    lin_v16 c0 = {0}, c1 = {0};
+    c0 = __builtin_amdgcn_mfma_i32_32x32x32_i8(af, lin_b(v, 0, 0), c0, 0, 0, 0);
+    c1 = __builtin_amdgcn_mfma_i32_32x32x32_i8(af, lin_b(v, 0, 1), c1, 0, 0, 0);
+    // lin_gather2 with the weights (1, 0) and then (0, 1) returns lo = r_0 + (r_1 << 8) and hi = r_2 + (r_3 << 8) of two outputs
+#pragma unroll
+    for (int g = 0; g < 4; g++) {
+        int64_t lo0, lo1, hi0, hi1;
+        lin_gather2(lo0, lo1, c0, c1, g, 1, 0);
+        lin_gather2(hi0, hi1, c0, c1, g, 0, 1);
+        out[32 * lane + 8 * g] = (uint32_t)lo0; out[32 * lane + 8 * g + 1] = (uint32_t)hi0;
+        out[32 * lane + 8 * g + 4] = (uint32_t)lo1; out[32 * lane + 8 * g + 5] = (uint32_t)hi1;
+    }
+#endif
+}
+
 }  // namespace
 
+extern "C" const char* zkh_test_lin_tile(zkh_ctx* c, const zkh_buf* a, const zkh_buf* b, zkh_buf* out) {
+    ZKH_REQUIRE(a && b && out && a->len == 256 && b->len == 512 && out->len == 2048, "test_lin_tile: a 256, b 512, out 2048 words");
+    bind_thread(c);
+    k_lin_tile<<<1, 64, 0, c->stream>>>(a->ptr(), b->ptr(), out->ptr());
+    return last_launch_error("test_lin_tile");
+}
 extern "C" const char* zkh_poseidon2_mix(zkh_ctx* c, zkh_buf* states, size_t count) {
     ZKH_REQUIRE(states && states->len == count * CELLS, "poseidon2_mix: buffer is not count x 24 words");
     if (!count) return nullptr;
@@ -219,8 +274,9 @@ extern "C" const char* zkh_hash_rows(zkh_ctx* c, zkh_buf* out, const zkh_buf* ma
     ZKH_REQUIRE(matrix->len % rows == 0, "hash_rows: matrix size %zu not a multiple of rows %zu", matrix->len, rows);
     const size_t cols = matrix->len / rows;
     ProfScope prof(c, "hash_rows", 4.0 * matrix->len + 32.0 * rows);
-    k_hash_rows<<<(unsigned)((rows + 255) / 256), 256, 0, c->stream>>>(out->ptr(), matrix->ptr(), rows, (uint32_t)cols,
-                                                                      c->tab.rc, c->tab.diag);
+    const dim3 grid((unsigned)((rows + 255) / 256));
+    if (c->lin_ok) k_hash_rows<true><<<grid, 256, 0, c->stream>>>(out->ptr(), matrix->ptr(), rows, (uint32_t)cols, c->tab.rc, c->tab.diag, c->tab.lin);
+    else           k_hash_rows<false><<<grid, 256, 0, c->stream>>>(out->ptr(), matrix->ptr(), rows, (uint32_t)cols, c->tab.rc, c->tab.diag, c->tab.lin);
     return last_launch_error("hash_rows");
 }
 extern "C" const char* zkh_hash_fold(zkh_ctx* c, zkh_buf* io, size_t input_size, size_t output_size) {
@@ -228,8 +284,9 @@ extern "C" const char* zkh_hash_fold(zkh_ctx* c, zkh_buf* io, size_t input_size,
     ZKH_REQUIRE((input_size + 2 * output_size) * 8 <= io->len && output_size * 2 <= input_size, "hash_fold: ranges out of bounds");
     if (!output_size) return nullptr;
     ProfScope prof(c, "hash_fold", 96.0 * output_size);
-    k_hash_fold<<<(unsigned)((output_size + 255) / 256), 256, 0, c->stream>>>(io->ptr(), input_size, output_size, c->tab.rc,
-                                                                             c->tab.diag);
+    const dim3 grid((unsigned)((output_size + 255) / 256));
+    if (c->lin_ok) k_hash_fold<true><<<grid, 256, 0, c->stream>>>(io->ptr(), input_size, output_size, c->tab.rc, c->tab.diag, c->tab.lin);
+    else           k_hash_fold<false><<<grid, 256, 0, c->stream>>>(io->ptr(), input_size, output_size, c->tab.rc, c->tab.diag, c->tab.lin);
     return last_launch_error("hash_fold");
 }
 extern "C" const char* zkh_merkle_fold_all(zkh_ctx* c, zkh_buf* nodes, size_t rows) {

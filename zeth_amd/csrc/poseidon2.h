@@ -195,6 +195,10 @@ inline bool poseidon2_partial_table(uint32_t* t, const uint32_t* rc_canonical, c
     for (int i = 0; i < 3 * CELLS; i++) t[P2_TAB_EXIT + i] = (uint32_t)center(p2_mulm(t[i], mu));
     return lam[2 * HALF_FULL] == R1;
 }
+}  // namespace zkh
+#define ZKH_POSEIDON2_H_PARTS
+#include "poseidon2_linear.h"   // the partial rounds as one affine map on the matrix cores (k_hash_rows, k_hash_fold)
+namespace zkh {
 // A kept cell of poseidon2_mix_raw's output -> the nearly centred signed word (a valid input cell of the next permutation) ...
 ZKH_HD uint32_t p2_signed(uint32_t v) { return v - F64_OFF; }
 // ... -> the canonical Montgomery word
@@ -208,10 +212,15 @@ ZKH_HD uint32_t p2_finish(uint32_t v) { return canon((int32_t)p2_signed(v)); }
 //              wave-uniform on the device: the two ranges share everything but the last KEEP_N reductions, which sit behind
 //              one scalar branch — a sponge with one call site keeps its capacity in interior blocks and its digest in the
 //              last one without a second copy of the permutation.
-template <int KEEP_LO, int KEEP_N, int LIVE, bool SEL>
-ZKH_HD void poseidon2_mix_core(uint32_t (&s)[CELLS], const uint32_t* __restrict__ rc, const uint32_t* __restrict__ diag, bool low) {
+// LINEAR: the 21 partial rounds run as poseidon2_linear.h's affine map (lin: its table) instead of the grouped form below; the
+// second half's full rounds then read lin's constant rows (the fifth round's constants sit in the map).  On the device a whole
+// wave must then run the permutation together.
+template <int KEEP_LO, int KEEP_N, int LIVE, bool SEL, bool LINEAR = false>
+ZKH_HD void poseidon2_mix_core(uint32_t (&s)[CELLS], const uint32_t* __restrict__ rc, const uint32_t* __restrict__ diag, bool low,
+                               const uint32_t* __restrict__ lin = nullptr) {
     static_assert(!SEL || KEEP_LO >= KEEP_N, "the two selectable ranges do not overlap");
     const uint32_t* __restrict__ rcf = diag + P2_TAB_FULL;
+    const uint32_t* __restrict__ rcf2 = LINEAR ? lin + LIN_RCF : rcf;          // rows of the second half
     double d[CELLS], c[4];
 #pragma unroll
     for (int i = 0; i < LIVE; i++) d[i] = (double)(int32_t)s[i];
@@ -223,6 +232,9 @@ ZKH_HD void poseidon2_mix_core(uint32_t (&s)[CELLS], const uint32_t* __restrict_
         for (int i = 0; i < CELLS; i++) d[i] = (double)sbox7_lazy(s[i], rcf[r * CELLS + i]);
         m_ext_f64(s, d);
     }
+    if constexpr (LINEAR) {
+        poseidon2_partial_linear(s, lin);
+    } else {
     // back to scale R for the partial rounds: cell 0 by one product, cells 1..23 through group 0's table rows
     s[0] = canon(smont((int32_t)(s[0] - F64_OFF), (int32_t)diag[P2_TAB_KAPPA]));
 #pragma unroll
@@ -308,15 +320,16 @@ ZKH_HD void poseidon2_mix_core(uint32_t (&s)[CELLS], const uint32_t* __restrict_
     }
 #pragma unroll
     for (int i = 1; i < CELLS; i++) s[i] = canon((int32_t)s[i]);
+    }
 #pragma unroll 1
     for (int r = HALF_FULL; r < 2 * HALF_FULL - 1; r++) {
 #pragma unroll
-        for (int i = 0; i < CELLS; i++) d[i] = (double)sbox7_lazy(s[i], rcf[r * CELLS + i]);
+        for (int i = 0; i < CELLS; i++) d[i] = (double)sbox7_lazy(s[i], rcf2[r * CELLS + i]);
         m_ext_f64(s, d);
     }
     // F8, peeled: every block product and column sum, but the last add and the reduction only of the cells the caller reads
 #pragma unroll
-    for (int i = 0; i < CELLS; i++) d[i] = (double)sbox7_lazy(s[i], rcf[(2 * HALF_FULL - 1) * CELLS + i]);
+    for (int i = 0; i < CELLS; i++) d[i] = (double)sbox7_lazy(s[i], rcf2[(2 * HALF_FULL - 1) * CELLS + i]);
     m_ext_f64_blocks<CELLS>(d, c);
     if (SEL && low) m_ext_f64_reduce<CELLS, 0, KEEP_LO, KEEP_N>(s, d, c);
     else            m_ext_f64_reduce<CELLS, KEEP_LO, KEEP_LO, KEEP_N>(s, d, c);
@@ -329,6 +342,14 @@ ZKH_HD void poseidon2_mix_raw(uint32_t (&s)[CELLS], const uint32_t* __restrict__
 // One sponge block: s[RATE ...] receives the capacity (cells 16..23), or in the last block the digest (cells 0..7).
 ZKH_HD void poseidon2_mix_sponge(uint32_t (&s)[CELLS], const uint32_t* __restrict__ rc, const uint32_t* __restrict__ diag, bool last_block) {
     poseidon2_mix_core<RATE, OUT, CELLS, true>(s, rc, diag, last_block);
+}
+// The same two through the linear partial rounds (k_hash_rows, k_hash_fold; on the host: the model of what they compute)
+template <int KEEP_LO = 0, int KEEP_N = CELLS, int LIVE = CELLS>
+ZKH_HD void poseidon2_mix_raw_linear(uint32_t (&s)[CELLS], const uint32_t* __restrict__ diag, const uint32_t* __restrict__ lin) {
+    poseidon2_mix_core<KEEP_LO, KEEP_N, LIVE, false, true>(s, nullptr, diag, false, lin);
+}
+ZKH_HD void poseidon2_mix_sponge_linear(uint32_t (&s)[CELLS], const uint32_t* __restrict__ diag, const uint32_t* __restrict__ lin, bool last_block) {
+    poseidon2_mix_core<RATE, OUT, CELLS, true, true>(s, nullptr, diag, last_block, lin);
 }
 // The permutation on canonical Montgomery words, in and out (host sponges; kernels that read few cells use the raw form).
 ZKH_HD void poseidon2_mix(uint32_t (&s)[CELLS], const uint32_t* __restrict__ rc, const uint32_t* __restrict__ diag) {
