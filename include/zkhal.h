@@ -272,6 +272,27 @@ const char* zkh_circuit_set_arguments(zkh_circuit*, const uint32_t* blob, size_t
 int zkh_circuit_has_arguments(const zkh_circuit*);
 const char* zkh_accumulate(zkh_ctx*, const zkh_circuit*, size_t po2, size_t zk_cycles, const uint32_t noise_key[8], const zkh_buf* code,
                            const zkh_buf* data, const uint32_t* mix_global, zkh_buf* accum);
+/* THE OPEN BUS (ZKA1 version 8: version 7's layout and, after every other record, ONE record of kind 5 = OPEN, 16 words: kind, the open
+ * tag, the `out` word offsets of alpha, beta and the total (4 words each, disjoint, inside `out`), the circuit's `out` words, the rest
+ * reserved; header words 3, 4 repeat the offsets of alpha and beta; header word 7 carries bit 17, and bit 16 exactly when the blob holds a
+ * PAGES record).  A bus ACROSS seals (DESIGN.md §2 "THE TIE"): the constraints read alpha and beta from `out`, the terms of the open tag are
+ * answered by another seal, and the bus closes on the four `out` words of the total instead of zero.
+ * zkh_circuit_open_bus: 1 when the circuit's arguments are open, and then where[4] (if given) = the open tag and the three offsets; else 0.
+ * zkh_accumulate_open is zkh_accumulate's pass with `challenge` = alpha (4 words) ‖ beta (4 words), reduced Montgomery words, where the
+ * mix globals were.  It refuses a vanishing denominator as zkh_accumulate does; a total that is not zero is no refusal: total[4] = the
+ * sum of the accum columns' last active row, 4 reduced Montgomery words, which the caller states in `out` next to the challenge.
+ * zkh_accumulate refuses an open blob and zkh_accumulate_open a closed one; zkh_check_bus skips the keys of the open tag. */
+int zkh_circuit_open_bus(const zkh_circuit*, uint32_t where[4]);
+const char* zkh_accumulate_open(zkh_ctx*, const zkh_circuit*, size_t po2, size_t zk_cycles, const uint32_t noise_key[8], const zkh_buf* code,
+                                const zkh_buf* data, const uint32_t challenge[8], zkh_buf* accum, uint32_t total[4]);
+/* THE TABLE'S FINGERPRINT (csrc/tie.hip; host twin: circuits/logup.py table_fingerprint): total[4] = the sum over the D rows (a, in, out)
+ * of the table at word `table_at` of `table` (three words a row as a ZKU1 proof holds them: the address an integer, in and out
+ * Montgomery words; zkh_page_out_proof leaves it at word 5 + h) of 1 / (alpha - (2 + beta a + beta^2 in + beta^3 out)) in Fp4, as 4
+ * reduced Montgomery words; challenge = alpha ‖ beta as zkh_accumulate_open takes it.  It is the open total of the tied paging segment
+ * whose page table this is, and minus the sum of the totals of the P2-PAGE-tied parts of its page-out.  D = 0 gives zero without a
+ * launch.  It FAILS when the table does not lie in the buffer, when D >= 2^31, and when a denominator vanishes: the error names the
+ * lowest such row.  Two launches, one read-back of 5 words; reads the table, writes nothing of the caller's. */
+const char* zkh_table_fingerprint(zkh_ctx*, const zkh_buf* table, size_t table_at, size_t D, const uint32_t challenge[8], uint32_t total[4]);
 /* Derived multiplicities (ZKA1 version 2: term word 7 bit 0).  A derived term is the table side of a lookup: sign -1, its multiplicity a
  * data column that nothing else in the blob names, every other term of its tag a lookup of sign +1.  zkh_derive_multiplicities writes
  * that column on the active rows [0, 2^po2 - zk_cycles) of `data`: on the representative of each table key (its entry of smallest
@@ -489,7 +510,7 @@ size_t zkh_page_circuit_slots(size_t po2, size_t zk_cycles, size_t image_words);
  * are P2-PAGE's, written by the same kernels; data 125 live (1 on a real update's path, 0 on a no-op's), 126 lo (one more than the last
  * live address before the slot, in this part or an earlier one; 0 if none), 127 gbit / 128 gacc (the gap addr - lo one bit per row on
  * rows 1 .. 29 of a path's block 0, and its running sum); code 39 gsel, 40 gpow, 41 gend (those rows, 2^(k - 1) on them, the last of
- * them).  Still NOT constrained: that the table is the page table of a paging segment's seal.
+ * them).  Still NOT constrained: that the table is the page table of a paging segment's seal (P2-PAGE-tied, below, adds that).
  * h <= 26 (images of at most 2^29 words), one less than P2-PAGE: the gap is decomposed into 29 bits, and addr = lo + gap is an integer
  * equation only while lo + gap < 2^30 < P.  N, the parts' plan and W > 8 are P2-PAGE's (zkh_page_circuit_slots).
  * zkh_page_ordered_code: zkh_page_circuit_code's operands, `code` of 42 x 2^po2 words.
@@ -499,7 +520,10 @@ size_t zkh_page_circuit_slots(size_t po2, size_t zk_cycles, size_t image_words);
  * "page_ordered_witgen: ", but "the circuit does not have P2-PAGE-ordered's shape (kind 6, 42 / 129 / 4 columns, 18 outputs)", and after
  * P2-PAGE's h <= 27 refusal "an image of W words has h 27; the gap between two addresses is decomposed into 29 bits, which takes
  * addresses below 2^29: h <= 26".  A table whose addresses do not increase is the check pass's refusal as before: no path and no new
- * column is written after it.  The accum group is zkh_syn_accum's, as for kind 5. */
+ * column is written after it.  The accum group is zkh_syn_accum's, as for kind 5.
+ * P2-PAGE-tied (circuit kind 8, zeth_amd/circuits/p2_page_tied.py; DESIGN.md §2 "THE TIE"): P2-PAGE-ordered's code and data groups column
+ * for column, so both calls serve it as they stand (they tell the circuit by its kind, and then ask for 30 outputs); out = these 18 words
+ * ‖ alpha ‖ beta ‖ F, of which the witness call writes the 18.  Its accum group is an open bus: zkh_accumulate_open, not zkh_syn_accum. */
 const char* zkh_page_ordered_code(zkh_ctx*, const zkh_circuit*, size_t po2, size_t zk_cycles, size_t image_words, zkh_buf* code);
 const char* zkh_page_ordered_witgen(zkh_ctx*, const zkh_circuit*, size_t po2, size_t zk_cycles, const zkh_buf* code, const zkh_buf* proof, size_t proof_words,
                                     const zkh_buf* nodes_before, const zkh_buf* nodes_after, size_t first, zkh_buf* data, uint32_t out[18],
@@ -668,6 +692,10 @@ void zkh_prove_abort(zkh_seal_job*);
 /* Control root = Merkle root of the committed code group (the control-ID analogue: risc0-zkp verify/mod.rs check_code).
  * zkh_code_root commits a caller-supplied code trace; zkh_syn_control_root generates SYN-AIR's for (po2, zk_cycles). */
 const char* zkh_code_root(zkh_prover*, const zkh_buf* code, size_t po2, uint32_t root[8]);
+/* zkh_data_root commits a data trace as zkh_prove_begin will: the root the seal of this trace carries, known before the seal is made
+ * (the shared challenge of a tied group hashes the data roots of all its seals: zkh_tie_challenge).  zkh_prove_begin commits the group
+ * again. */
+const char* zkh_data_root(zkh_prover*, size_t po2, const zkh_buf* data, uint32_t root[8]);
 const char* zkh_syn_control_root(zkh_prover*, size_t po2, size_t zk_cycles, uint32_t root[8]);
 
 /* ---- verifier: risc0_zkp::verify::verify — what `receipt.verify(image_id)` (cli.rs:103) runs per segment ----
@@ -675,6 +703,13 @@ const char* zkh_syn_control_root(zkh_prover*, size_t po2, size_t zk_cycles, uint
  * control_root: the expected code commitment for (circuit, po2) — REQUIRED (check_code: a seal whose code group is
  * anything else, e.g. all-zero selectors, is rejected).  rc / diag: canonical Poseidon2 tables (24*29 / 24 words) or
  * NULL for the shipped ones.  NULL = seal accepted. */
+/* THE TIE, HOST ONLY.  zkh_seal_data_root: the root of the data group a seal commits to, folded from the top layer the seal carries as
+ * zkh_verify_segment folds it; it reads the header and the two tree tops only, so verify the seal first.
+ * zkh_tie_challenge: challenge[8] = alpha ‖ beta of a tied group from its n data roots in order (the segment's, then the parts'): the hash
+ * suite's digest of ('ZKT1', n, the roots) seeds a fresh transcript generator, and eight random elements follow.  Prover and verifier
+ * call this one function. */
+const char* zkh_seal_data_root(const zkh_circuit*, const uint32_t* seal, size_t seal_words, uint32_t root[8]);
+const char* zkh_tie_challenge(const uint32_t* roots, size_t n, uint32_t challenge[8]);
 const char* zkh_verify_segment(const zkh_circuit*, const uint32_t* seal, size_t seal_words, const uint32_t control_root[8],
                                const uint32_t* rc, const uint32_t* diag);
 

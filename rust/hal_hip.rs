@@ -610,6 +610,31 @@ impl HipCircuitHal {
         res
     }
 
+    /// `(open tag, out offsets of alpha, beta, the total)` of arguments that are an OPEN bus (ZKA1 version 8; `zkh_circuit_open_bus`):
+    /// a bus across seals, whose challenges and total are words of `out`.  `None`: the bus closes on zero inside the seal.
+    pub fn open_bus(&self) -> Option<[u32; 4]> {
+        let mut wh = [0u32; 4];
+        if unsafe { sys::zkh_circuit_open_bus(self.circuit, wh.as_mut_ptr()) } != 0 { Some(wh) } else { None }
+    }
+
+    /// `accumulate` for an OPEN bus (`zkh_accumulate_open`): `challenge` = alpha ‖ beta where the mix globals were; returns the bus
+    /// total, which the seal states in `out` behind the challenge.  It panics on a vanishing denominator and on a closed blob.
+    pub fn accumulate_open(&self, ctrl: &HipBuffer<BabyBearElem>, data: &HipBuffer<BabyBearElem>, challenge: &[u32; 8], accum: &HipBuffer<BabyBearElem>,
+                           steps: usize) -> [u32; 4] {
+        let po2 = steps.trailing_zeros() as usize;
+        let mut total = [0u32; 4];
+        ffi(|| unsafe { sys::zkh_accumulate_open(self.hal.ctx.0, self.circuit, po2, sys::ZK_CYCLES, std::ptr::null(), ctrl.raw, data.raw, challenge.as_ptr(), accum.raw,
+                                                 total.as_mut_ptr()) });
+        total
+    }
+
+    /// The root of the data group a seal of this circuit commits to, read out of the seal (`zkh_seal_data_root`; host only).
+    pub fn seal_data_root(&self, seal: &[u32]) -> [u32; 8] {
+        let mut root = [0u32; 8];
+        ffi(|| unsafe { sys::zkh_seal_data_root(self.circuit, seal.as_ptr(), seal.len(), root.as_mut_ptr()) });
+        root
+    }
+
     /// The data columns that the four derives write on the active rows, ascending (`zkh_circuit_derived_data_columns`).
     pub fn derived_data_columns(&self) -> Vec<u32> {
         let mut n = 0usize;
@@ -652,6 +677,29 @@ impl CircuitHal<HipHal> for HipCircuitHal {
         let mix_words = mix.read_words(0, mix.size());
         ffi(|| unsafe { sys::zkh_accumulate(self.hal.ctx.0, self.circuit, po2, sys::ZK_CYCLES, std::ptr::null(), ctrl.raw, data.raw, mix_words.as_ptr(), accum.raw) });
     }
+}
+
+/// THE TIE: the fingerprint of the `rows` table rows at word `table_at` of `table`, where `zkh_page_out_proof` left them,
+/// under `challenge` = alpha ‖ beta (`zkh_table_fingerprint`): what the open total of the tied segment must be.
+pub fn table_fingerprint(hal: &HipHal, table: &HipBuffer<BabyBearElem>, table_at: usize, rows: usize, challenge: &[u32; 8]) -> [u32; 4] {
+    let mut total = [0u32; 4];
+    ffi(|| unsafe { sys::zkh_table_fingerprint(hal.ctx.0, table.raw, table_at, rows, challenge.as_ptr(), total.as_mut_ptr()) });
+    total
+}
+
+/// The root a seal of `data` will carry for its data group, before the seal is made (`zkh_data_root`).
+pub fn data_root(prover: *mut sys::ZkhProver, po2: usize, data: &HipBuffer<BabyBearElem>) -> [u32; 8] {
+    let mut root = [0u32; 8];
+    ffi(|| unsafe { sys::zkh_data_root(prover, po2, data.raw, root.as_mut_ptr()) });
+    root
+}
+
+/// alpha ‖ beta of a tied group from its data roots in order, the segment's first (`zkh_tie_challenge`; host only): prover and
+/// verifier call the same function.
+pub fn tie_challenge(roots: &[[u32; 8]]) -> [u32; 8] {
+    let mut challenge = [0u32; 8];
+    ffi(|| unsafe { sys::zkh_tie_challenge(roots.as_ptr() as *const u32, roots.len(), challenge.as_mut_ptr()) });
+    challenge
 }
 
 /// `SegmentProver::prove` in the two halves upstream drives `Prover` in, for hosts that would rather hand the library whole

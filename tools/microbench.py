@@ -22,7 +22,8 @@ first = N of one table, and the seal of a part under both circuits, alternating,
 parts of one page-out of 662 267 addresses under p2_tree's plan and under P2-PAGE's, zkh_page_tree_witgen next to
 zkh_page_ordered_witgen and the seal of a part under both circuits, alternating, with every witness call's stages; M25: P2-TREE's plan
 of M24's table by zkh_page_tree_plan_device next to the read-back of the table and zkh_page_tree_plan, alternating; M26: zkh_reduce_elem
-at SYN-A's code and data widths next to zkh_eltwise_copy_elem over the same bytes, alternating) on one MI355X, through the C ABI (HipHal).
+at SYN-A's code and data widths next to zkh_eltwise_copy_elem over the same bytes, alternating; M27: the tie, zkh_data_root of a P2-PAGE-tied
+part next to its seal, zkh_accumulate_open next to zkh_accumulate, zkh_table_fingerprint next to a copy of the same bytes, alternating) on one MI355X, through the C ABI (HipHal).
 
 Each line of output is one JSON object: the op, its shape, the average wall time of one call (stream drained on both
 sides of `reps` back-to-back calls), its ALGORITHMIC bytes (SURVEY.md §8a "B_alg": inputs read once + outputs written
@@ -1285,6 +1286,87 @@ def main() -> None:
                               "copy_GB_per_s": round(8 * words / med["eltwise_copy_elem"] / 1e9, 1),
                               "reduce_over_copy": round(med["reduce_elem"] / med["eltwise_copy_elem"], 4)}), flush=True)
             del src, dst
+    if want("M27"):
+        # THE TIE: what a tied group costs beside what its seals cost anyway, on M24's table (662 267 random addresses over an
+        # image of 2^20 words), in one run, alternating windows, median and spread.  zkh_data_root of a P2-PAGE-tied part (pass one commits
+        # every part's data group once more) next to the seal of that part; zkh_accumulate_open on SYN-LOOKUP-tied FULL next to
+        # zkh_accumulate on SYN-LOOKUP-paged's blob over the same traces (the parent's yardstick: one term more, and the total returned);
+        # zkh_table_fingerprint over the table next to zkh_eltwise_copy_elem over the same bytes.  No threshold on any time.
+        from zeth_amd import hal as zhal
+        from zeth_amd.circuits import logup, p2_page, p2_page_tied, syn_lookup
+        from zeth_amd.prover import Segment, SegmentProver
+        runs, zk, D, W = 7, 1994, 662267, 1 << 20
+        spread = lambda ts: {"median_ms": round(float(np.median(ts)) * 1e3, 4), "min_ms": round(min(ts) * 1e3, 4), "max_ms": round(max(ts) * 1e3, 4)}   # noqa: E731
+        h = p2_page.tree_height(W)
+        image_h = rand_fp(rng, W)
+        addrs = np.sort(rng.choice(W, D, replace=False)).astype(np.int64)
+        outs = rand_fp(rng, D)
+        table = np.stack([addrs.astype(np.uint32), image_h[addrs], outs], axis=1).reshape(-1)
+        proof_h = np.concatenate([np.array([0x5A4B5531, W, D, 0, h] + [0] * h, dtype=np.uint32), table])
+        image = hal.alloc_elem("m27i", W)
+        image.write(image_h)
+        before = hal.image_commit(image)
+        image_h[addrs] = outs
+        image.write(image_h)
+        after = hal.image_commit(image)
+        del image
+        proof = hal.copy_from("m27p", proof_h)
+        challenge = zhal.tie_challenge(rand_fp(rng, 16))
+        t, got = {}, {}
+        # (a) the data root of a part next to its seal
+        page = SegmentProver(hal, p2_page_tied.p2_page_tied_circuit(), arguments=p2_page_tied.arguments())
+        seg = Segment(index=0, po2=args.po2, zk_cycles=zk, noise_seed=0x2E80)
+        code = hal.page_ordered_code(page.circuit, args.po2, zk, W)
+        data = hal.alloc_elem("m27d", p2_page_tied.WD * n)
+        prefix = hal.page_ordered_witgen(page.circuit, args.po2, zk, code, proof, proof_h.size, before, after, 0, data, seg.noise_seed)
+        accum = hal.alloc_elem("m27a", p2_page_tied.WA * n)
+
+        def seal_part():
+            total = got["part_total"] = hal.accumulate_open(page.circuit, args.po2, zk, seg.noise_seed, code, data, challenge, accum)
+            return page.seal_with_accum(seg, code, data, np.concatenate([prefix, challenge, total]), lambda _mix: accum)
+        fns = [("data_root_part", lambda: page.data_root(data, args.po2)), ("seal_part", seal_part)]
+        # (c) the fingerprint next to a copy of the same bytes
+        rows = hal.copy_from("m27t", table)
+        rows_copy = hal.alloc_elem("m27c", table.size)
+        fns += [("table_fingerprint", lambda: got.__setitem__("f", hal.table_fingerprint(proof, 5 + h, D, challenge))),
+                ("eltwise_copy_elem_same_bytes", lambda: hal.eltwise_copy_elem(rows_copy, rows))]
+        for name, _ in fns:
+            t[name] = []
+        for _ in range(runs):
+            for name, fn in fns:
+                t[name].append(timed(hal, fn, args.reps))
+        slots = p2_page.slots(args.po2, zk, h)
+        part_rows = hal.table_fingerprint(proof, 5 + h, min(slots, D), challenge).astype(np.uint64)
+        assert not ((part_rows + got["part_total"]) % np.uint64(P)).any(), "part 0's open total is not minus the fingerprint of its rows"
+        del code, data, accum, rows, rows_copy, before, after, proof
+        # (b) the open accumulate next to the closed one, SYN-LOOKUP FULL over one pair of traces
+        shape = syn_lookup.FULL
+        code_h, full_h, _out = syn_lookup.witness(shape, args.po2, zk, seed=17, link=True, reads=True, pages=True, image=np.zeros(1 << 20, dtype=np.uint32))
+        circuits = {}
+        for name, tied in (("paged", False), ("tied", True)):
+            desc, blob = syn_lookup.build_syn_lookup(shape, link=True, reads=True, pages=True, tied=tied)
+            circuits[name] = hal.load_circuit(desc, jit=False)
+            circuits[name].set_arguments(blob)
+        k = {name: len(logup.Arguments.parse(c._args).by_column()) for name, c in circuits.items()}
+        dcode, ddata = hal.copy_from("m27sc", code_h), hal.copy_from("m27sd", full_h)
+        accums = {name: hal.alloc_elem("m27sa", 4 * k[name] * n) for name in circuits}
+        mix = rand_fp(rng, 8)
+        acc = [("accumulate_paged", lambda: hal.accumulate(circuits["paged"], args.po2, zk, 0x2E80, dcode, ddata, mix, accums["paged"])),
+               ("accumulate_open_tied", lambda: got.__setitem__("total", hal.accumulate_open(circuits["tied"], args.po2, zk, 0x2E80, dcode, ddata, challenge, accums["tied"])))]
+        for name, _ in acc:
+            t[name] = []
+        for _ in range(runs):
+            for name, fn in acc:
+                t[name].append(timed(hal, fn, args.reps))
+        assert got["total"].any(), "the tied segment's open total is zero"
+        med = {name: float(np.median(v)) for name, v in t.items()}
+        print(json.dumps({"bench": "M27", "library": os.path.basename(os.environ.get("ZKH_LIBRARY", "") or "libzkhal_mi355x.so"), "po2": args.po2,
+                          "image_words": W, "layers": h, "table_rows": D, "path_slots": slots, "runs": runs, "reps": args.reps,
+                          **{name: spread(v) for name, v in t.items()}, "accum_columns": k,
+                          "data_root_over_seal": round(med["data_root_part"] / med["seal_part"], 4),
+                          "open_over_closed": round(med["accumulate_open_tied"] / med["accumulate_paged"], 4),
+                          "fingerprint_over_copy": round(med["table_fingerprint"] / med["eltwise_copy_elem_same_bytes"], 4),
+                          "fingerprint_rows_per_us": round(D / med["table_fingerprint"] / 1e6, 1)}), flush=True)
     hal.close()
 
 

@@ -19,14 +19,15 @@ ROOT = os.path.dirname(HERE)
 VARIANT = os.environ.get("ZKH_BUILD_VARIANT", "")
 LIB = os.path.join(ROOT, ".variants", f"libzkhal_{VARIANT}.so") if VARIANT else os.path.join(HERE, "libzkhal_mi355x.so")
 OBJ_DIR = os.path.join(ROOT, ".variants", f"_obj_{VARIANT}") if VARIANT else os.path.join(HERE, "csrc", "_obj")
-SOURCES = ["hal.hip", "ntt.hip", "hash.hip", "poly.hip", "circuit.hip", "prover.hip", "verifier.hip", "session.hip", "recursion.hip", "topology.hip", "preflight.hip", "rec_builder.hip", "arguments.hip", "accumulate.hip", "multiplicities.hip", "sort.hip", "columns.hip", "links.hip", "page_out.hip", "image.hip", "page_circuit.hip", "page_tree.hip", "check_rows.hip", "bus.hip"]   # + generated eval_check units
+SOURCES = ["hal.hip", "ntt.hip", "hash.hip", "poly.hip", "circuit.hip", "prover.hip", "verifier.hip", "session.hip", "recursion.hip", "topology.hip", "preflight.hip", "rec_builder.hip", "arguments.hip", "accumulate.hip", "multiplicities.hip", "sort.hip", "columns.hip", "links.hip", "page_out.hip", "image.hip", "page_circuit.hip", "page_tree.hip", "check_rows.hip", "bus.hip", "tie.hip"]   # + generated eval_check units
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-comment", "-Wno-unused-result"] + os.environ.get("ZKH_BUILD_FLAGS", "").split()
 # hash.hip: the unrolled Poseidon2 source order already interleaves 24 independent cells; LLVM's machine scheduler
 # re-interleaves it up to the register budget (126 VGPRs instead of 86) for no measurable gain on MI355X (hash_rows
 # M3 9.55 vs 9.59 ms): the source order is kept for the smaller footprint.
 # accumulate.hip: the batch loops of k_args_terms must unroll fully to keep their arrays in registers (scratch otherwise).
-EXTRA_FLAGS = {"hash.hip": ["-mllvm", "-enable-misched=0"], "accumulate.hip": ["-mllvm", "-pragma-unroll-threshold=200000"]}
+EXTRA_FLAGS = {"hash.hip": ["-mllvm", "-enable-misched=0"], "accumulate.hip": ["-mllvm", "-pragma-unroll-threshold=200000"],
+               "tie.hip": ["-mllvm", "-pragma-unroll-threshold=200000"]}       # k_tie_rows batches as k_args_terms does
 
 
 def _extra(src: str) -> list:

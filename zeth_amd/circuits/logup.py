@@ -59,6 +59,20 @@ ZKA1 layout (u32 words; canonical integers, not Montgomery words)::
       32 words are what version 6 writes.  Header word 7 = (the READS count) | 0x10000: a version-7 blob without bit 16 is no ZKA1 blob, bit
       16 without a PAGES record is refused.  The builder writes version 7 only when a PAGES record exists (`derive_pages`).
 
+    Version 8: version 7's layout, and the blob ends on ONE record of kind 5 = OPEN (16 words), after every other record:
+      [0] kind = 5   [1] the open tag   [2], [3], [4] the `out` word offsets of alpha, beta and the total (4 words each, pairwise
+      disjoint)   [5] the circuit's `out` words   [6 .. 15] reserved = 0.  Header words 3, 4 repeat the offsets of alpha and beta: they
+      are `out` offsets, not mix offsets.  Header word 7 = (the READS count) | 0x10000 exactly when the blob holds a PAGES record | 0x20000:
+      a version-8 blob without bit 17 is no ZKA1 blob, bit 17 without an OPEN record is refused; neither a READS count nor a PAGES record
+      is required.  The builder writes version 8 only when an OPEN record exists.
+
+THE OPEN BUS (the OPEN record; `LogupBuilder(..., open_bus=...)`, zkh_accumulate_open; DESIGN.md §2 "THE TIE"): a bus across seals.  The
+challenges are words of `out` (a hash of the data roots of every seal of the group, drawn after all of them are committed:
+prover.seal_tied), every term reads them there, and the `last` constraint closes on sum_c S_c = out[total .. total + 4) instead of
+zero.  The terms of the open tag are the ones another seal answers: they are no lookups of this seal, so no derived multiplicity and
+no sorted copy has that tag, and a bus check (`reference_bus`, zkh_check_bus) skips its keys.  Every other term nets to zero inside
+the seal, so the total is the sum of the open tag's terms: `table_fingerprint` of the rows they carry.
+
 A derived term is the table side of a lookup (`check_derived`): sign -1, its multiplicity a data column that no tuple and no other
 term names, and every other term of its tag a lookup of sign +1.  Its multiplicity column is then a function of the traces:
 on each table key's representative (the entry of smallest (blob term index, row)) the number of lookups of that key, 0 on the
@@ -120,8 +134,8 @@ zkh_image_proof_walk on the device, from the buffer zkh_page_out_proof wrote and
 SegmentProver.page_out(..., proof=True, walk=True) checks the proof it returns against the tree's root after the page-out).  For every
 (proof, root_before) both succeed with the same root_after or fail with the same message after their prefixes; the host verifier's
 order of causes decides when several apply, and this module's `check_page_out_proof` states that order.
-Left out: no circuit checks p_in / p_out against those roots yet (the in-circuit path check consumes exactly this proof's digests) and
-they are not in `out`, sessions do not thread an image, and a blob pages one memory of one value word per address.
+Left out: sessions do not thread an image, and a blob pages one memory of one value word per address.  The circuits that check p_in /
+p_out against those roots are the page-out circuits (p2_page.py and after it), and THE OPEN BUS below ties their rows to this table.
 
 WHO WRITES A DATA COLUMN (`_check_owned` behind `check_columns` and `check_links`; csrc/arguments.h says the same).  A data column
 has at most one writer, and a derive reads only what the stages before it have finished writing.  The writers: a sorted copy (its
@@ -142,7 +156,7 @@ from typing import List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 
-from .desc import GLOBAL_MIX, GROUP_ACCUM, GROUP_CODE, GROUP_DATA, P, CircuitBuilder, Fp
+from .desc import GLOBAL_MIX, GLOBAL_OUT, GROUP_ACCUM, GROUP_CODE, GROUP_DATA, P, CircuitBuilder, Fp
 
 ARGS_MAGIC = 0x5A4B4131
 ARGS_HEADER = 8
@@ -440,6 +454,60 @@ def check_pages(terms: Sequence[Term], records: Sequence, group_sizes=None) -> O
     return _check_owned(terms, records, Pages, clause_a, group_sizes)
 
 
+KIND_OPEN = 5
+OPEN_WORDS = 16
+OPEN_BIT = 0x20000                             # header word 7, bit 17 (version 8): the blob has an OPEN record
+
+
+@dataclass(frozen=True)
+class Open:
+    """The OPEN record as the blob holds it (ZKA1 version 8): the fields are the blob's words, `check_open` the rules"""
+    tag: int                                   # the terms of this tag are answered by another seal
+    alpha: int                                 # `out` word offsets: the two challenges and the bus total, 4 words each
+    beta: int
+    total: int
+    out_words: int                             # the circuit's `out` words
+    reserved: bool = False                     # a word the format reserves was not 0 (parser only)
+    kind = KIND_OPEN
+
+    def words(self) -> List[int]:
+        w = [KIND_OPEN, self.tag % P, self.alpha, self.beta, self.total, self.out_words]
+        return w + [0] * (OPEN_WORDS - len(w))
+
+
+def check_open(terms: Sequence[Term], records: Sequence, header=None) -> Optional[str]:
+    """the OPEN record that breaks a rule, named by its index among all `records`, or None: it is the last record and the only one of
+    its kind; its reserved words are 0; its tag is below P, some term carries it, and none of them is derived or a sorted copy; alpha,
+    beta and the total are three disjoint runs of 4 words inside `out`.  header = the blob's (alpha, beta) words, which repeat them."""
+    at = [i for i, r in enumerate(records) if isinstance(r, Open)]
+    if not at:
+        return None
+    i, r = at[0], records[at[0]]
+    if len(at) > 1:
+        return f"record {at[1]}: a second OPEN record (record {i} is one: a seal closes on one total)"
+    if i != len(records) - 1:
+        return f"record {i + 1}: a record after the OPEN record {i} (the OPEN record comes last)"
+    if r.reserved:
+        return f"record {i}: a reserved word of the OPEN record is not 0 (words 6..15)"
+    if r.tag >= P:
+        return f"record {i}: the open tag {r.tag} is not below P"
+    for name, off in (("alpha", r.alpha), ("beta", r.beta), ("the total", r.total)):
+        if off + 4 > r.out_words:
+            return f"record {i}: {name} at out words {off}..{off + 3}, the circuit has {r.out_words}"
+    runs = sorted((r.alpha, r.beta, r.total))
+    if runs[0] + 4 > runs[1] or runs[1] + 4 > runs[2]:
+        return f"record {i}: alpha, beta and the total overlap in out (words {r.alpha}, {r.beta}, {r.total}: 4 words each)"
+    if header is not None and tuple(header) != (r.alpha, r.beta):
+        return f"record {i}: header words 3, 4 are {header[0]}, {header[1]}, the OPEN record's alpha, beta are {r.alpha}, {r.beta}"
+    mine = [j for j, t in enumerate(terms) if t.tag % P == r.tag]
+    if not mine:
+        return f"record {i}: no term has the open tag {r.tag}"
+    for j in mine:
+        if terms[j].derive or terms[j].sorted_from is not None:
+            return f"record {i}: term {j} of the open tag {r.tag} is derived or a sorted copy (another seal answers the open tag)"
+    return None
+
+
 class _Owned(NamedTuple):
     """A record of either kind as the ownership rule sees it"""
     index: int                                 # its index among the records
@@ -515,7 +583,11 @@ def _check_owned(terms: Sequence[Term], records: Sequence, of, clause_a, group_s
 
 def _check_records(terms: Sequence[Term], records: Sequence, group_sizes=None) -> Optional[str]:
     """check_columns over the LIMBS / ORDER records (they come first, so the indices are the blob's), then check_links, then (version 7)
-    check_pages over the one PAGES record, which comes last"""
+    check_pages over the one PAGES record, which comes last; the OPEN record (version 8) comes after all of them (`check_open`)"""
+    problem = check_open(terms, records)
+    if problem:
+        return problem
+    records = [r for r in records if not isinstance(r, Open)]
     pages = [i for i, r in enumerate(records) if isinstance(r, Pages)]
     if pages and pages[0] != len(records) - 1:
         j = pages[0] + 1
@@ -566,7 +638,14 @@ class Arguments:
         return next((r for r in self.records if isinstance(r, Pages)), None)
 
     @property
+    def open(self) -> Optional["Open"]:
+        """the OPEN record (version 8), or None: the bus closes on zero and the challenges are mix words"""
+        return next((r for r in self.records if isinstance(r, Open)), None)
+
+    @property
     def version(self) -> int:
+        if self.open is not None:
+            return 8
         if self.pages is not None:
             return 7
         if self.reads:
@@ -581,7 +660,7 @@ class Arguments:
 
     def blob(self) -> np.ndarray:
         words = [ARGS_MAGIC, self.version, self.k, self.alpha, self.beta, len(self.terms), len(self.records),
-                 self.reads | (PAGES_BIT if self.pages is not None else 0)]
+                 self.reads | (PAGES_BIT if self.pages is not None else 0) | (OPEN_BIT if self.open is not None else 0)]
         for t in _by_column(self.terms):
             rec = [t.col, 0 if t.sign == 1 else 1, NONE if t.sel is None else t.sel,
                    NONE if t.mult is None else t.mult[0], 0 if t.mult is None else t.mult[1], t.tag % P, len(t.tuple_cols), t.flags()]
@@ -596,8 +675,8 @@ class Arguments:
     @staticmethod
     def parse(blob: Sequence[int]) -> "Arguments":
         d = [int(x) for x in np.asarray(blob, dtype=np.uint32)]
-        if len(d) < ARGS_HEADER or d[0] != ARGS_MAGIC or d[1] not in (1, 2, 3, 4, 5, 6, 7) or (d[1] == 6 and d[7] == 0) or \
-                (d[1] == 7 and not d[7] & PAGES_BIT):
+        if len(d) < ARGS_HEADER or d[0] != ARGS_MAGIC or d[1] not in (1, 2, 3, 4, 5, 6, 7, 8) or (d[1] == 6 and d[7] == 0) or \
+                (d[1] == 7 and not d[7] & PAGES_BIT) or (d[1] == 8 and not d[7] & OPEN_BIT):
             raise ValueError("not a ZKA1 argument blob")
         version = d[1]
         k, alpha, beta, n = d[2], d[3], d[4], d[5]
@@ -635,6 +714,9 @@ class Arguments:
         for i in range(n_rec):
             at = ARGS_HEADER + TERM_WORDS * n + sum(sizes[:i])
             r = d[at: at + sizes[i]]
+            if version >= 8 and r[0] == KIND_OPEN:
+                records.append(Open(r[1], r[2], r[3], r[4], r[5], bool(any(r[6:]))))
+                continue
             if sizes[i] == PAGES_WORDS and r[0] == KIND_PAGES:
                 n_dst = min(16, 5 + 2 * min(r[2], 8))
                 records.append(Pages(r[1], r[2], r[3], tuple(r[16: 16 + n_dst]), bool(any(r[4:16]) or any(r[16 + n_dst:]))))
@@ -656,12 +738,19 @@ class Arguments:
             records.append(Record(r[0], r[1], r[2], tuple((r[4 + 2 * j], r[5 + 2 * j]) for j in range(min(n_src, 2))), tuple(r[8: 8 + n_dst]),
                                   reserved, None if n_src <= 2 else n_src))
         n_reads = sum(isinstance(r, Link) and r.write is not None for r in records)
-        word7 = d[7] ^ PAGES_BIT if version >= 7 else d[7]                     # version 7: bit 16 says PAGES, the rest counts as before
+        has_pages = any(isinstance(r, Pages) for r in records)
+        word7 = d[7] ^ PAGES_BIT if version == 7 or (version >= 8 and d[7] & PAGES_BIT) else d[7]     # bit 16 says PAGES, the rest counts as before
+        if version >= 8:
+            word7 ^= OPEN_BIT                                                # bit 17 says OPEN
         if version >= 6 and word7 != n_reads:
             raise ValueError(f"ZKA1: header word 7 is {word7}, the blob has {n_reads} LINK records with READS")
-        if version >= 7 and not any(isinstance(r, Pages) for r in records):
+        if version >= 7 and d[7] & PAGES_BIT and not has_pages:
             raise ValueError("ZKA1: header word 7 has bit 16 (PAGES), but the blob has no PAGES record")
-        problem = check_sorted(terms) or check_derived(terms) or _check_records(terms, records)
+        if version >= 8 and has_pages and not d[7] & PAGES_BIT:
+            raise ValueError("ZKA1: the blob has a PAGES record, but header word 7 lacks bit 16 (PAGES)")
+        if version >= 8 and not any(isinstance(r, Open) for r in records):
+            raise ValueError("ZKA1: header word 7 has bit 17 (OPEN), but the blob has no OPEN record")
+        problem = check_sorted(terms) or check_derived(terms) or check_open(terms, records, (alpha, beta)) or _check_records(terms, records)
         if problem:
             raise ValueError(f"ZKA1: {problem}")
         return Arguments(k, alpha, beta, terms, records)
@@ -680,16 +769,25 @@ class Arguments:
 class LogupBuilder(CircuitBuilder):
     """CircuitBuilder that also records argument terms and emits their constraints (`arguments`)."""
 
-    def __init__(self, group_sizes, global_sizes, alpha: int = 0, beta: int = 4, kind: int = 0):
+    def __init__(self, group_sizes, global_sizes, alpha: int = 0, beta: int = 4, kind: int = 0, open_bus: Optional[Tuple[int, int]] = None):
+        """open_bus = (tag, total): the OPEN mode (the module docstring's open bus).  alpha and beta are then `out` word offsets, every
+        term reads the challenges there, the terms of `tag` are answered by another seal and `arguments` closes the bus on the four
+        `out` words at `total`.  The blob gets an OPEN record (ZKA1 version 8)."""
         super().__init__(tuple(group_sizes), tuple(global_sizes), kind=kind)
         if group_sizes[GROUP_ACCUM] % 4:
             raise ValueError("the accum group holds Fp4 columns: its width is a multiple of 4")
         for off in (alpha, beta):
-            if off + 4 > global_sizes[1]:
+            if open_bus is None and off + 4 > global_sizes[1]:
                 raise ValueError(f"mix offset {off} needs {off + 4} mix words, the circuit has {global_sizes[1]}")
         self.alpha_off, self.beta_off = alpha, beta
         self.terms: List[Term] = []
         self.records: List[Record] = []
+        self.open: Optional[Open] = None
+        if open_bus is not None:
+            self.open = Open(int(open_bus[0]), int(alpha), int(beta), int(open_bus[1]), int(global_sizes[0]))
+            problem = check_open([Term(0, ((GROUP_DATA, 0),), tag=self.open.tag)], [self.open])     # the offsets; the terms come later
+            if problem:
+                raise ValueError(problem)
 
     @property
     def k(self) -> int:
@@ -911,7 +1009,8 @@ class LogupBuilder(CircuitBuilder):
         return c[:4]
 
     def _mix4(self, off: int):
-        return [self.get_global(GLOBAL_MIX, off + i) for i in range(4)]
+        """a challenge: four mix words, or in the open mode four `out` words"""
+        return [self.get_global(GLOBAL_MIX if self.open is None else GLOBAL_OUT, off + i) for i in range(4)]
 
     def arguments(self, chain, first: Fp, body: Fp, last: Fp):
         """emit the argument constraints onto `chain`, gated by the code selectors first / body / last; returns the chain"""
@@ -967,12 +1066,18 @@ class LogupBuilder(CircuitBuilder):
         for c in range(self.k):
             tot = self._e_add(tot, acc(c))
         last_inner = self.true()
+        if self.open is not None:                                            # the closing step: sum_c S_c = the total the seal states in `out`
+            tot = self._e_sub(tot, self._mix4(self.open.total))
         for i in range(4):
             last_inner = self.and_eqz(last_inner, tot[i])
         return self.and_cond(chain, last, last_inner)
 
     def args(self) -> Arguments:
-        return Arguments(self.k, self.alpha_off, self.beta_off, _by_column(self.terms), list(self.records))
+        args = Arguments(self.k, self.alpha_off, self.beta_off, _by_column(self.terms), list(self.records) + ([self.open] if self.open is not None else []))
+        problem = check_open(args.terms, args.records)
+        if problem:
+            raise ValueError(problem)
+        return args
 
     def finish_all(self, ret) -> Tuple[np.ndarray, np.ndarray]:
         """-> (ZKC1 description, ZKA1 argument blob)"""
@@ -1038,13 +1143,18 @@ def reference_accumulate(args: Arguments, po2: int, zk_cycles: int, code, data, 
     """The accum trace (W_accum x 2^po2 raw Montgomery words) zkh_accumulate must produce, computed on the host.
     code / data / mix: raw Montgomery words as the library takes them.  noise(col) -> the zk_cycles blinding words of Fp column
     `col` (rows A..n-1), or None: zeros.  Raises ReferenceError on a vanishing denominator, and (check_balance) on a bus total
-    that is not zero; returns (accum, total) with total the 4 canonical components of sum_c S_c[A-1]."""
+    that is not zero; returns (accum, total) with total the 4 canonical components of sum_c S_c[A-1].
+    OPEN arguments (zkh_accumulate_open): `mix` is the challenge, alpha (4 words) then beta (4 words), whatever the offsets say; a
+    total that is not zero is no refusal: it is what the call is for, and the seal states it in `out`."""
     n = 1 << po2
     A = n - zk_cycles
     groups = {GROUP_CODE: np.asarray(code, dtype=np.uint32).reshape(-1, n), GROUP_DATA: np.asarray(data, dtype=np.uint32).reshape(-1, n)}
     mixc = _dec(np.asarray(mix, dtype=np.uint32))
-    alpha = [np.full(A, mixc[args.alpha + i], dtype=np.uint64) for i in range(4)]
-    beta = [np.full(A, mixc[args.beta + i], dtype=np.uint64) for i in range(4)]
+    is_open = args.open is not None
+    if is_open and mixc.size != 8:
+        raise ReferenceError(f"a challenge of {mixc.size} words (alpha and beta: 8)")
+    alpha = [np.full(A, mixc[(0 if is_open else args.alpha) + i], dtype=np.uint64) for i in range(4)]
+    beta = [np.full(A, mixc[(4 if is_open else args.beta) + i], dtype=np.uint64) for i in range(4)]
     bpow = [beta]
     for _ in range(MAX_TUPLE - 1):
         bpow.append(_e_mul_np(bpow[-1], beta))
@@ -1079,7 +1189,7 @@ def reference_accumulate(args: Arguments, po2: int, zk_cycles: int, code, data, 
             total[e] = (total[e] + int(run[-1])) % P
             if noise is not None:
                 accum[4 * c + e, A:] = np.asarray(noise(4 * c + e), dtype=np.uint32)
-    if check_balance and any(total):
+    if check_balance and not is_open and any(total):
         raise ReferenceError(f"the bus does not balance: total {total}")
     return accum.reshape(-1), total
 
@@ -1601,6 +1711,8 @@ def reference_bus(args: Arguments, po2: int, zk_cycles: int, code, data) -> dict
     rows = np.arange(A)
     keys, who, weight, sign = [], [], [], []
     for i, t in enumerate(terms):
+        if args.open is not None and t.tag % P == args.open.tag:              # another seal answers the open tag: its keys are no part of this check
+            continue
         w = np.ones(A, dtype=np.uint64)
         if t.sel is not None:
             w = _m(w, _dec(groups[GROUP_CODE][t.sel, :A]))
@@ -1641,6 +1753,45 @@ def reference_bus(args: Arguments, po2: int, zk_cycles: int, code, data) -> dict
 
 
 BUS_LINE_TERMS = 8
+TIE_TAG = 2                                     # the tag of a table row (addr, in, out) on the bus across a paging segment's seal and its page-out chain
+
+
+def _f4_mul(x, y):
+    c = [0] * 7
+    for i in range(4):
+        for j in range(4):
+            c[i + j] += x[i] * y[j]
+    return [(c[i] + (c[i + 4] * NBETA if i < 3 else 0)) % P for i in range(4)]
+
+
+def _f4_inv(a):
+    """1 / a in Fp4 = Fp[x] / (x^4 + 11): a * a' lies in Fp[x^2] for a'(x) = a(-x), and that quadratic element is inverted by its norm"""
+    conj = [a[0], -a[1] % P, a[2], -a[3] % P]
+    q = _f4_mul(a, conj)                                                     # (q0, 0, q2, 0)
+    norm = (q[0] * q[0] + 11 * q[2] * q[2]) % P
+    inv = pow(norm, P - 2, P)
+    return _f4_mul(conj, [q[0] * inv % P, 0, -q[2] * inv % P, 0])
+
+
+def table_fingerprint(table, alpha, beta, tag: int = TIE_TAG) -> np.ndarray:
+    """THE TABLE'S FINGERPRINT (zkh_table_fingerprint): sum_i 1 / (alpha - (tag + beta a_i + beta^2 in_i + beta^3 out_i)) in Fp4 over the rows
+    (a_i, in_i, out_i) of a page table, in plain Python integers.  table: rows as a ZKU1 proof holds them, the address an integer, in and
+    out Montgomery words; alpha, beta: 4 Montgomery words each, as `out` holds them.  -> the sum as 4 Montgomery words.  It is what the
+    open total of a tied paging segment must be, and minus what the totals of its page-out parts add up to.  Raises ReferenceError,
+    naming the lowest row, on a denominator that vanishes."""
+    dec = lambda w: int(w) % P * _RINV % P
+    al, be = [dec(w) for w in alpha], [dec(w) for w in beta]
+    b2 = _f4_mul(be, be)
+    b3 = _f4_mul(b2, be)
+    total = [0, 0, 0, 0]
+    for i, (a, w_in, w_out) in enumerate(np.asarray(table, dtype=np.uint64).reshape(-1, 3).tolist()):
+        a, vi, vo = a % P, dec(w_in), dec(w_out)
+        den = [(al[e] - (be[e] * a + b2[e] * vi + b3[e] * vo) - (tag % P if e == 0 else 0)) % P for e in range(4)]
+        if not any(den):
+            raise ReferenceError(f"table_fingerprint: the denominator of row {i} vanishes")
+        inv = _f4_inv(den)
+        total = [(total[e] + inv[e]) % P for e in range(4)]
+    return np.asarray([t * _R % P for t in total], dtype=np.uint32)
 
 
 def describe_bus(bus: dict, args: Arguments) -> Optional[str]:

@@ -6,7 +6,8 @@ include/zkhal.h "THE IMAGE'S COMMITMENT": leaves are eight words verbatim, a nod
 are residues, as Montgomery words in the trace: the space the tree lives in.
 
 NOT constrained here: that the addresses strictly increase (P2-PAGE-ordered, p2_page_ordered.py, is this circuit plus that), and that
-the rows (a_i, in_i, out_i) are the page table of a particular paging segment's seal.  This circuit proves "D single-word updates take
+the rows (a_i, in_i, out_i) are the page table of a particular paging segment's seal (P2-PAGE-tied, p2_page_tied.py, is P2-PAGE-ordered
+plus that).  This circuit proves "D single-word updates take
 root_before to root_after" and nothing else.
 
 Trace (A = n - zk_cycles active rows, blocks of 31 rows with P2-JOIN's row roles k = 0 .. 30, K = A // 31 blocks).  A PATH is h
@@ -62,11 +63,13 @@ def slots(po2: int, zk_cycles: int, h: int) -> int:
     return (((1 << po2) - zk_cycles) // BLOCK_ROWS) // h
 
 
-def build_page(kind: int, sizes: Tuple[int, int, int], out_words: int, after_roots=None):
+def build_page(kind: int, sizes: Tuple[int, int, int], out_words: int, after_roots=None, builder=None, accum=None):
     """-> (blob, families): P2-PAGE's constraint text over a circuit of `sizes` (accum, code, data) columns and `out_words` outputs.
     after_roots = (name, emit): emit(b, chain) -> chain emits one more family, `name`, between `roots` and `accum`
-    (p2_page_ordered.py); without it this is P2-PAGE word for word."""
-    b = CircuitBuilder(sizes, (out_words, WA), kind=kind)
+    (p2_page_ordered.py); without it this is P2-PAGE word for word.  builder: the CircuitBuilder to emit into, one of these sizes
+    that the caller made (p2_page_tied.py: a LogupBuilder, which also holds the argument's terms); accum(b, chain, first, body) ->
+    chain emits the `accum` family in place of the running product."""
+    b = CircuitBuilder(sizes, (out_words, WA), kind=kind) if builder is None else builder
     code = lambda c, back=0: b.get(GROUP_CODE, c, back)
     dat = lambda c, back=0: b.get(GROUP_DATA, c, back)
     out = lambda i: b.get_global(GLOBAL_OUT, i)
@@ -135,7 +138,7 @@ def build_page(kind: int, sizes: Tuple[int, int, int], out_words: int, after_roo
         family(after_roots[0], start)
     # 7. accum: one Fp4 running product of (mix + data column 0), and the selector sanity, as in P2-JOIN
     start = len(b.steps)
-    chain = p2_blocks.running_product(b, chain, first, body, So(0))
+    chain = p2_blocks.running_product(b, chain, first, body, So(0)) if accum is None else accum(b, chain, first, body)
     family("accum", start)
     start = len(b.steps)
     chain = p2_blocks.sanity(b, chain, active, first, body)

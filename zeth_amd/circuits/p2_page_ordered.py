@@ -35,7 +35,8 @@ induction from a checked out[16] (lo is out[16], an earlier address plus one, or
 lo + gacc < 2^30 < P, so the field equation addr = lo + gacc is an integer one and gives addr >= lo; every honest gap fits 29 bits.
 MAX_H is therefore 26 (images of up to 2^29 words), one less than P2-PAGE's.
 
-NOT constrained here: that the rows (a_i, in_i, out_i) are the page table of a particular paging segment's seal.
+NOT constrained here: that the rows (a_i, in_i, out_i) are the page table of a particular paging segment's seal.  P2-PAGE-tied
+(p2_page_tied.py) is this circuit with its live rows on a bus shared with that seal.
 """
 from __future__ import annotations
 

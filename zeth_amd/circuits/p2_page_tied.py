@@ -1,0 +1,97 @@
+"""P2-PAGE-tied: P2-PAGE-ordered (p2_page_ordered.py) whose live rows are tied to a paging segment's page table (DESIGN.md §2 ARGUMENTS,
+"THE TIE").
+
+Statement: P2-PAGE-ordered's (the live updates of the part have strictly increasing addresses at or above `lo`, and take `root_before`
+to `root_after`), AND the sum over the live updates of -1 / (alpha - (2 + beta a + beta^2 in + beta^3 out)) is F, with alpha, beta and F
+words of `out`.  A group verifier (prover.verify_tied) checks that every seal of the group states one alpha ‖ beta, that it is the hash
+of the group's data roots (so it was drawn after every trace was fixed), and that F of the segment's seal (SYN-LOOKUP-tied: + its page
+table's rows) and the F of the parts add up to zero: the parts' live rows are then the segment's page table, as a multiset, and the
+chain's order makes them its rows in order.
+
+The trace is P2-PAGE-ordered's: code columns 0 .. 41 and data columns 0 .. 128 have the same meaning and the same constraints (one
+constraint text: p2_page.build_page with p2_page_ordered._order), so zkh_page_ordered_code and zkh_page_ordered_witgen serve this
+circuit as they stand.  What differs is the accum group and `out`:
+
+  accum (4 columns = one Fp4 column): the OPEN bus (logup.py "THE OPEN BUS"; ZKA1 version 8) with one term, through logup.LogupBuilder in
+      place of P2-PAGE's running product:  -live (addr, w_in, w_out), tag 2, on the leaf_in row of each slot (selector leaf_in,
+      multiplicity live).  A dead slot adds nothing.  The bus closes on the last path's top row (selector last_top): the active rows past
+      it hold no leaf_in row, so the running sum there is the sum over the whole trace.  zkh_accumulate_open fills it.
+  out (30 words): P2-PAGE-ordered's 18 ‖ alpha (4) ‖ beta (4) ‖ F (4).
+Globals: mix = 4 words, which no constraint reads.
+
+NOT constrained here: nothing about the segment; the group verifier holds the other half.
+"""
+from __future__ import annotations
+
+import functools
+from typing import List, Sequence, Tuple
+
+import numpy as np
+
+from . import p2_blocks, p2_page, p2_page_ordered
+from .desc import GROUP_CODE, GROUP_DATA
+from .logup import TIE_TAG, Arguments, LogupBuilder, reference_accumulate, _enc
+from .p2_page import C_LAST_TOP, C_LEAF_IN, D_ADDR, D_W_IN, D_W_OUT
+from .p2_page_ordered import D_LIVE, MAX_H, WC, WD, decode, slots  # noqa: F401  (the shape is P2-PAGE-ordered's; callers size and decode with these)
+
+KIND_P2_PAGE_TIED = 8
+WA, OUT_WORDS = 4, 30
+OUT_ALPHA, OUT_BETA, OUT_TOTAL = 18, 22, 26
+PREFIX_WORDS = p2_page_ordered.OUT_WORDS        # what the witness generator returns: root_before ‖ root_after ‖ lo ‖ hi
+
+# the constraint families, in the order the description emits them: (name, first step, end step) over the ZKC1 step list
+FAMILIES: List[Tuple[str, int, int]] = []
+
+
+def _bus(b, chain, first, body):
+    """the `accum` family: the one term, and the argument's constraints closing on last_top"""
+    b.term(0, [(GROUP_DATA, D_ADDR), (GROUP_DATA, D_W_IN), (GROUP_DATA, D_W_OUT)], sign=-1, sel=C_LEAF_IN, mult=(GROUP_DATA, D_LIVE), tag=TIE_TAG)
+    return b.arguments(chain, first, body, b.get(GROUP_CODE, C_LAST_TOP))
+
+
+@functools.lru_cache(maxsize=None)
+def build_p2_page_tied() -> Tuple[np.ndarray, np.ndarray]:
+    """-> (ZKC1 description, ZKA1 argument blob)"""
+    b = LogupBuilder((WA, WC, WD), (OUT_WORDS, p2_page.WA), alpha=OUT_ALPHA, beta=OUT_BETA, kind=KIND_P2_PAGE_TIED, open_bus=(TIE_TAG, OUT_TOTAL))
+    desc, FAMILIES[:] = p2_page.build_page(KIND_P2_PAGE_TIED, (WA, WC, WD), OUT_WORDS, after_roots=("order", p2_page_ordered._order), builder=b, accum=_bus)
+    return desc, b.args().blob()
+
+
+def p2_page_tied_circuit() -> np.ndarray:
+    return build_p2_page_tied()[0].copy()
+
+
+def arguments() -> np.ndarray:
+    """the ZKA1 blob of the open bus: what SegmentProver(hal, p2_page_tied_circuit(), arguments=arguments()) hands zkh_accumulate_open"""
+    return build_p2_page_tied()[1].copy()
+
+
+def family_of(step: int) -> str:
+    """the constraint family (P2-PAGE-ordered's, `accum` being the open bus) of a step of the description"""
+    build_p2_page_tied()
+    return p2_blocks.family_of(FAMILIES, step)
+
+
+# ------------------------------------------------------------------------------------------------ host twins
+def reference_tied_part(po2: int, zk_cycles: int, W: int, table: Sequence[Tuple[int, int, int]], image_before, first: int, challenge):
+    """-> (data, accum, out) of the part of `table` that starts at update `first`, under the challenge alpha ‖ beta (8 Montgomery words): the
+    active rows of the data trace, (129, A) Montgomery words (p2_page_ordered.reference_ordered_part's); the accum trace zkh_accumulate_open
+    must produce over the full 2^po2 rows with zero blinding rows, (4, 2^po2); out = root_before ‖ root_after ‖ lo ‖ hi ‖ alpha ‖ beta ‖ F
+    (30 words)."""
+    n = 1 << po2
+    A = n - zk_cycles
+    data, prefix = p2_page_ordered.reference_ordered_part(po2, zk_cycles, W, table, image_before, first)
+    full = np.zeros((WD, n), dtype=np.uint32)
+    full[:, :A] = data
+    code = p2_page_ordered.reference_ordered_code(po2, zk_cycles, p2_blocks.tree_height(W))
+    challenge = np.asarray(challenge, dtype=np.uint32).reshape(8)
+    accum, total = reference_accumulate(Arguments.parse(arguments()), po2, zk_cycles, code, full, challenge)
+    out = np.concatenate([prefix, challenge, _enc(np.asarray(total, dtype=np.uint64)).astype(np.uint32)]).astype(np.uint32)
+    return data, accum.reshape(WA, n), out
+
+
+if __name__ == "__main__":      # python -m zeth_amd.circuits.p2_page_tied out.desc   (blob for non-Python hosts)
+    import sys
+    blob = p2_page_tied_circuit()
+    np.asarray(blob, dtype="<u4").tofile(sys.argv[1])
+    print(f"{sys.argv[1]}: {blob.size} words")

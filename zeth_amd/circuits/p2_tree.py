@@ -55,7 +55,8 @@ inside [2^(h-1), 2^h), so a pair block sits h - 1 levels below the root, and lea
 both halves: they are no-ops.  (A block with up = 0 that is not the root slot is cut off from the tree: nothing reads it.)
 
 NOT constrained here: which words of a pair changed, and that the updates are the page table of a particular paging segment's seal
-(a pair block's input row holds the 16 old and the 16 new words of its addresses, which is what that tie will read).
+(p2_page_tied.py ties P2-PAGE-ordered's rows to it over a bus across seals; a pair block's input row holds the 16 old and the 16 new
+words of its addresses, and once it constrains which of them changed, this circuit plugs into the same bus).
 Not a shipped circuit: it is loaded the way SYN-LOOKUP is, and its control root is zkh_code_root of its code group.
 """
 from __future__ import annotations

@@ -51,6 +51,11 @@ lookups of tag 0; logup.link_constraints (paged) and logup.page_constraints tie 
 and no address is paged in twice.  The link columns are the LINK record's, the table a PAGES record's (ZKA1 version 7): the library fills
 both from the image (zkh_derive_links_paged; `witness(link=False, pages=False)` leaves them zero).  Times are row + 1 (clock 0 is the
 image's), so the limbs must cover A: 2^(order_limbs L) > A.  `fork_page` forges a table that pages one address in twice.
+SYN-LOOKUP-tied (`syn_lookup_tied`, `build_syn_lookup(shape, link=True, reads=True, pages=True, tied=True)`): SYN-LOOKUP-paged on the
+OPEN bus (logup.py, "THE OPEN BUS"; ZKA1 version 8), ANOTHER description with its own control root.  One more term, the last one:
++p_on (p_addr, p_in, p_out) of tag 2 (logup.TIE_TAG), the page table's rows put on the bus that the seals of its page-out chain
+(p2_page_tied.py) take them off.  out = SYN-LOOKUP-paged's 4 words ‖ alpha ‖ beta ‖ F (16 words): every term reads the two challenges
+from `out`, and the `last` constraint closes on F = logup.table_fingerprint of the page table.  The witness is SYN-LOOKUP-paged's.
 Not a shipped circuit: its control root is zkh_code_root of its code trace.
 """
 from __future__ import annotations
@@ -60,7 +65,7 @@ from typing import NamedTuple, Tuple
 import numpy as np
 
 from .desc import GROUP_CODE, GROUP_DATA, P
-from .logup import LogupBuilder
+from .logup import TIE_TAG, LogupBuilder
 
 N_CODE = 7
 MEM_W = 3
@@ -116,6 +121,7 @@ def reads_layout(n_words: int, n_limbs: int, n_mem: int, order_limbs: int = ORDE
 
 
 PAGE_W = 5                          # p_on, p_addr, p_in, p_out, p_time
+TIED_OUT, OUT_ALPHA, OUT_BETA, OUT_TOTAL = 16, 4, 8, 12      # SYN-LOOKUP-tied's out: 4 zero words ‖ alpha ‖ beta ‖ F
 
 
 def pages_layout(n_words: int, n_limbs: int, n_mem: int = 1, order_limbs: int = ORDER_LIMBS):
@@ -127,7 +133,8 @@ def pages_layout(n_words: int, n_limbs: int, n_mem: int = 1, order_limbs: int = 
 
 def build_syn_lookup(shape: Shape = FULL, derive: bool = False, sort: bool = False,
                      sort_keys: Tuple[int, ...] = SORT_KEYS, limbs: bool = False, order: bool = False,
-                     order_limbs: int = ORDER_LIMBS, link: bool = False, reads: bool = False, pages: bool = False) -> Tuple[np.ndarray, np.ndarray]:
+                     order_limbs: int = ORDER_LIMBS, link: bool = False, reads: bool = False, pages: bool = False,
+                     tied: bool = False) -> Tuple[np.ndarray, np.ndarray]:
     """-> (ZKC1 description, ZKA1 argument blob); derive: the table term's multiplicity is derived by the library (version-2 blob,
     the description unchanged); sort: every permuted copy is the library's sorted copy of its memory tuple by the tuple positions
     `sort_keys` (version-3 blob, the description unchanged); limbs: every word's limbs are a LIMBS record (version-4 blob, the
@@ -135,8 +142,11 @@ def build_syn_lookup(shape: Shape = FULL, derive: bool = False, sort: bool = Fal
     the copy's (addr, time); link: SYN-LOOKUP-linked, another description (module docstring), its link columns a LINK record (version-5
     blob); it has no sorted copy, so it refuses `sort` and `order`; reads: SYN-LOOKUP-reads, SYN-LOOKUP-linked with a write flag per
     memory pair and the read rule (version-6 blob, another description); it needs `link`; pages: SYN-LOOKUP-paged, SYN-LOOKUP-reads
-    with its one memory paged in from an image and out again (version-7 blob, another description); it needs `link`, `reads` and n_mem = 1"""
+    with its one memory paged in from an image and out again (version-7 blob, another description); it needs `link`, `reads` and n_mem = 1; tied: SYN-LOOKUP-tied, SYN-LOOKUP-paged on the open bus with
+    the page table's rows as one more term (version-8 blob, another description, 16 `out` words); it needs `pages`"""
     n_words, n_limbs, limb_bits, n_mem = shape
+    if tied and not pages:
+        raise ValueError("build_syn_lookup: tied=True ties the page table of a paged memory to its page-out: it needs pages=True")
     if pages and not (link and reads):
         raise ValueError("build_syn_lookup: pages=True pages the memory of a LINK record with the read rule: it needs link=True, reads=True")
     if pages and n_mem != 1:
@@ -157,9 +167,12 @@ def build_syn_lookup(shape: Shape = FULL, derive: bool = False, sort: bool = Fal
     pcols = pages_layout(n_words, n_limbs, n_mem, order_limbs) if pages else []
     if pages:
         wd += len(pcols)
-        n_terms += 1 + 2 * order_limbs
+        n_terms += 1 + 2 * order_limbs + bool(tied)
     k = (n_terms + 2) // 3
-    b = LogupBuilder((4 * k, N_CODE, wd), (4, 8), alpha=0, beta=4)
+    if tied:
+        b = LogupBuilder((4 * k, N_CODE, wd), (TIED_OUT, 8), alpha=OUT_ALPHA, beta=OUT_BETA, open_bus=(TIE_TAG, OUT_TOTAL))
+    else:
+        b = LogupBuilder((4 * k, N_CODE, wd), (4, 8), alpha=0, beta=4)
     code = lambda c: b.get(GROUP_CODE, c)
     data = lambda c: b.get(GROUP_DATA, c)
     one = b.const(1)
@@ -184,6 +197,8 @@ def build_syn_lookup(shape: Shape = FULL, derive: bool = False, sort: bool = Fal
     specs += [dict(tuple_cols=[(GROUP_DATA, c)], tag=0) for cols in ocols for c in cols[1:]]
     specs += [dict(tuple_cols=[(GROUP_DATA, c)], tag=0) for cols in lcols for c in cols[LINK_W:]]
     specs += [dict(tuple_cols=[(GROUP_DATA, c)], tag=0) for c in pcols[PAGE_W:]]
+    if tied:                                                                 # the table's rows, for the page-out chain to take off the bus
+        specs.append(dict(tuple_cols=[(GROUP_DATA, pcols[1]), (GROUP_DATA, pcols[2]), (GROUP_DATA, pcols[3])], sign=1, mult=(GROUP_DATA, pcols[0]), tag=TIE_TAG))
     for i, s in enumerate(specs):
         b.term(i // 3, **s)
     if limbs_flag:
@@ -271,6 +286,14 @@ def syn_lookup_tiny_paged() -> Tuple[np.ndarray, np.ndarray]:
 
 def syn_lookup_paged() -> Tuple[np.ndarray, np.ndarray]:
     return build_syn_lookup(FULL, link=True, reads=True, pages=True)
+
+
+def syn_lookup_tiny_tied() -> Tuple[np.ndarray, np.ndarray]:
+    return build_syn_lookup(TINY, link=True, reads=True, pages=True, tied=True)
+
+
+def syn_lookup_tied() -> Tuple[np.ndarray, np.ndarray]:
+    return build_syn_lookup(FULL, link=True, reads=True, pages=True, tied=True)
 
 
 def _enc(x) -> np.ndarray:

@@ -14,6 +14,10 @@
 //   (c) the blinding rows (noise_cell(GROUP_ACCUM, column, row), as k_syn_accum_store writes them).
 // The host then reads back the totals and the first vanishing denominator (one sync) and refuses the witness if either is wrong:
 // the accum is zeroed and an error names the row and column, or the bus total.
+//
+// THE OPEN BUS (zkh_accumulate_open; a ZKA1 version-8 blob with an OPEN record): the same pass with the challenge alpha ‖ beta given by the
+// caller (the seal states it in `out`, where the constraints read it) and the total RETURNED instead of compared with zero: the terms of
+// the open tag are answered by another seal.  One body, `accumulate`, serves both calls.
 #include "arguments.h"
 
 using namespace zkh;
@@ -108,15 +112,13 @@ __global__ void k_args_blind(uint32_t* accum, uint32_t n, uint32_t A, NoiseKey n
     accum[(size_t)col * n + r] = noise_cell(nk, GROUP_ACCUM, col, r);
 }
 
-}  // namespace
-
-extern "C" const char* zkh_accumulate(zkh_ctx* ctx, const zkh_circuit* c, size_t po2, size_t zk_cycles, const uint32_t* noise_key,
-                                      const zkh_buf* code, const zkh_buf* data, const uint32_t* mix_global, zkh_buf* accum) {
-    ZKH_REQUIRE(ctx && c && code && data && accum && mix_global, "accumulate: null argument");
-    ZKH_REQUIRE(c->args, "accumulate: the circuit has no arguments (zkh_circuit_set_arguments)");
+// both calls: alpha, beta = the two challenges as 4 Montgomery words each; total = NULL: the bus must close on zero (zkh_accumulate), else
+// the 4 Montgomery words of sum_c S_c[A-1] are returned there (zkh_accumulate_open)
+const char* accumulate(const char* who, zkh_ctx* ctx, const zkh_circuit* c, size_t po2, size_t zk_cycles, const uint32_t* noise_key, const zkh_buf* code,
+                       const zkh_buf* data, const uint32_t* alpha_words, const uint32_t* beta_words, zkh_buf* accum, uint32_t* total) {
     size_t n;
     uint32_t A;
-    ZKH_TRY(trace_rows("accumulate", c, po2, zk_cycles, code, data, accum, &n, &A));
+    ZKH_TRY(trace_rows(who, c, po2, zk_cycles, code, data, accum, &n, &A));
     const Arguments& a = *c->args;
     const uint32_t k = a.k, n_terms = (uint32_t)a.terms.size();
     NoiseKey nk;
@@ -124,8 +126,8 @@ extern "C" const char* zkh_accumulate(zkh_ctx* ctx, const zkh_circuit* c, size_t
     bind_thread(ctx);
 
     // the terms in device form: alpha - tag, beta's powers, columns resolved
-    auto challenge = [&](uint32_t at) { return Fp4(Fp::raw(mix_global[at]), Fp::raw(mix_global[at + 1]), Fp::raw(mix_global[at + 2]), Fp::raw(mix_global[at + 3])); };
-    const Fp4 alpha = challenge(a.alpha), beta = challenge(a.beta);
+    auto challenge = [](const uint32_t* w) { return Fp4(Fp::raw(w[0]), Fp::raw(w[1]), Fp::raw(w[2]), Fp::raw(w[3])); };
+    const Fp4 alpha = challenge(alpha_words), beta = challenge(beta_words);
     BetaPows bp;
     Fp4 pw = beta;
     for (uint32_t e = 0; e < MAX_TUPLE; e++, pw = pw * beta)
@@ -179,13 +181,15 @@ extern "C" const char* zkh_accumulate(zkh_ctx* ctx, const zkh_circuit* c, size_t
     const char* refusal = nullptr;
     if (key != ~0ull) {
         const uint32_t row = (uint32_t)(key >> 32), col = ((uint32_t)key) >> 2, term = key & 3;
-        refusal = make_err("accumulate: a denominator vanishes at row %u, accum column %u (Fp columns %u..%u), term %u of the column: "
-                           "the witness is refused", row, col, 4 * col, 4 * col + 3, term);
+        refusal = make_err("%s: a denominator vanishes at row %u, accum column %u (Fp columns %u..%u), term %u of the column: "
+                           "the witness is refused", who, row, col, 4 * col, 4 * col + 3, term);
     } else {
         Fp4 tot = Fp4::zero();
         for (uint32_t col = 0; col < k; col++)
             tot += Fp4(Fp::raw(st[2 + 4 * col]), Fp::raw(st[3 + 4 * col]), Fp::raw(st[4 + 4 * col]), Fp::raw(st[5 + 4 * col]));
-        if (!(tot == Fp4::zero()))
+        if (total)
+            for (int e = 0; e < 4; e++) total[e] = tot.c[e].v % P;
+        else if (!(tot == Fp4::zero()))
             refusal = make_err("accumulate: the bus does not balance: total (%u, %u, %u, %u) over the %u accum columns, not zero: the witness "
                                "is refused", fp_decode(tot.c[0]), fp_decode(tot.c[1]), fp_decode(tot.c[2]), fp_decode(tot.c[3]), k);
     }
@@ -195,4 +199,23 @@ extern "C" const char* zkh_accumulate(zkh_ctx* ctx, const zkh_circuit* c, size_t
         return refusal;
     }
     return nullptr;
+}
+
+}  // namespace
+
+extern "C" const char* zkh_accumulate(zkh_ctx* ctx, const zkh_circuit* c, size_t po2, size_t zk_cycles, const uint32_t* noise_key,
+                                      const zkh_buf* code, const zkh_buf* data, const uint32_t* mix_global, zkh_buf* accum) {
+    ZKH_REQUIRE(ctx && c && code && data && accum && mix_global, "accumulate: null argument");
+    ZKH_REQUIRE(c->args, "accumulate: the circuit has no arguments (zkh_circuit_set_arguments)");
+    ZKH_REQUIRE(!c->args->is_open(), "accumulate: the arguments are an open bus (ZKA1 version 8): its total is not zero but a word of `out` (zkh_accumulate_open)");
+    return accumulate("accumulate", ctx, c, po2, zk_cycles, noise_key, code, data, mix_global + c->args->alpha, mix_global + c->args->beta, accum, nullptr);
+}
+
+extern "C" const char* zkh_accumulate_open(zkh_ctx* ctx, const zkh_circuit* c, size_t po2, size_t zk_cycles, const uint32_t* noise_key, const zkh_buf* code,
+                                           const zkh_buf* data, const uint32_t* challenge, zkh_buf* accum, uint32_t total[4]) {
+    ZKH_REQUIRE(ctx && c && code && data && accum && challenge && total, "accumulate_open: null argument");
+    ZKH_REQUIRE(c->args, "accumulate_open: the circuit has no arguments (zkh_circuit_set_arguments)");
+    ZKH_REQUIRE(c->args->is_open(), "accumulate_open: the arguments are a closed bus (no OPEN record): its total must be zero (zkh_accumulate)");
+    for (int e = 0; e < 8; e++) ZKH_REQUIRE(challenge[e] < P, "accumulate_open: challenge word %d is not a reduced element", e);
+    return accumulate("accumulate_open", ctx, c, po2, zk_cycles, noise_key, code, data, challenge, challenge + 4, accum, total);
 }

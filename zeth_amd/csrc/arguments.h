@@ -36,6 +36,8 @@ constexpr uint32_t KIND_LINK = 3, LINK_WORDS = 32, MAX_CARRIED = 3, MAX_LINK_LIM
 constexpr uint32_t LINK_READS = 1;                  // LINK word 5, bit 0 (version 6): the record carries the read rule
 constexpr uint32_t KIND_PAGES = 4, PAGES_WORDS = 32, MAX_PAGE_LIMBS = 4, MAX_PAGE_DSTS = 5 + 2 * MAX_PAGE_LIMBS;   // a PAGES record (version 7)
 constexpr uint32_t PAGES_BIT = 0x10000;             // header word 7, bit 16 (version 7): the blob has a PAGES record
+constexpr uint32_t OPEN_BIT = 0x20000;              // header word 7, bit 17 (version 8): the blob has an OPEN record
+constexpr uint32_t KIND_OPEN = 5, OPEN_WORDS = 16;  // the OPEN record (version 8): the bus closes on `out` words, not on zero
 constexpr uint32_t MAX_ORDER_BITS = 29;             // logup.MAX_ORDER_BITS: a negative difference stays out of the limbs' range
 
 // logup.Term as the blob gives it: the fields are the blob's words, checked by the rules of arguments.hip before a circuit keeps them
@@ -74,10 +76,17 @@ struct Pages {
     uint32_t dst[MAX_PAGE_DSTS];            // destination data columns: p_on, p_addr, p_in, p_out, p_time, alimb_0 .., gap_0 ..
     uint32_t n_dst, reserved;               // destinations in use; a word the format reserves was not 0
 };
+// logup.Open, the OPEN record (version 8), as the blob gives it: the terms of `tag` are answered by another seal, the challenges and the
+// bus total are words of `out` (accumulate.hip zkh_accumulate_open; bus.hip skips the tag's keys)
+struct Open {
+    uint32_t index;                         // its index among all records of the blob (it comes last)
+    uint32_t tag, alpha, beta, total;       // the open tag; the `out` word offsets of alpha, beta and the total (4 words each)
+    uint32_t out_words, reserved;           // the circuit's `out` words; a word the format reserves was not 0
+};
 enum { PG_ON = 0, PG_ADDR = 1, PG_IN = 2, PG_OUT = 3, PG_TIME = 4, PG_LIMBS = 5 };      // the places of Pages::dst
 // logup.Arguments
 struct Arguments {
-    uint32_t version, k, alpha, beta;       // blob version; accum Fp4 columns; mix word offsets of the two challenges
+    uint32_t version, k, alpha, beta;       // blob version; accum Fp4 columns; mix word offsets of the two challenges (OPEN: `out` offsets)
     std::vector<Term> terms;
     std::vector<Record> records;            // the LIMBS / ORDER records: their index here is their index in the blob
     std::vector<Link> links;                // the LINK records
@@ -86,6 +95,11 @@ struct Arguments {
     std::vector<Pages> pages;               // the PAGES record (version 7; the rules allow one)
     uint32_t after_pages = NONE;            // a record that follows the first PAGES record (refused)
     bool second_pages = false;              // ... and it is a PAGES record itself
+    std::vector<Open> open;                 // the OPEN record (version 8; the rules allow one, the last record)
+    uint32_t after_open = NONE;             // a record that follows the first OPEN record (refused)
+    bool second_open = false;               // ... and it is an OPEN record itself
+    bool is_open() const { return !open.empty(); }
+    bool open_tag(uint32_t tag) const { return !open.empty() && open[0].tag == tag; }
     int paged_link() const {                // the place among `links` of the LINK that the PAGES record names, -1: none (or no such LINK)
         for (size_t p = 0; !pages.empty() && p < links.size(); p++)
             if (links[p].index == pages[0].link) return (int)p;

@@ -1,6 +1,6 @@
 // arguments.hip — the ZKA1 argument blob (layout: zeth_amd/circuits/logup.py; DESIGN.md §2 ARGUMENTS): its decoding into
 // zkh::Arguments (terms, from version 4 derived-column records, from version 5 LINK records, from version 6 their read rule, from version 7 the PAGES
-// record), the rules a circuit's arguments keep (check_sorted, check_derived, then check_owned over the LIMBS / ORDER records, over the LINK records
+// record, from version 8 the OPEN record), the rules a circuit's arguments keep (check_sorted, check_derived, then check_owned over the LIMBS / ORDER records, over the LINK records
 // and over the PAGES record), and the entry points that attach them to a circuit and ask what they derive.
 // decode_arguments is the only code that knows the blob's words; everything else, here and in the consumers, reads decoded terms.
 #include "arguments.h"
@@ -17,7 +17,7 @@ namespace {
 // significant key first); bits 2, 3, 7, the position fields of unused keys and, without bit 1, everything above bit 0 are reserved.
 // A reserved bit is recorded, not refused: the rules refuse it where they reach the term (flag_word_rule), after the circuit-shape checks.
 const char* decode_arguments(const uint32_t* a, size_t words, Arguments* out) {
-    ZKH_REQUIRE(words >= ARGS_HEADER && a[0] == ARGS_MAGIC && a[1] >= 1 && a[1] <= 7 && (a[1] != 6 || a[7] != 0) && (a[1] != 7 || (a[7] & PAGES_BIT)),
+    ZKH_REQUIRE(words >= ARGS_HEADER && a[0] == ARGS_MAGIC && a[1] >= 1 && a[1] <= 8 && (a[1] != 6 || a[7] != 0) && (a[1] != 7 || (a[7] & PAGES_BIT)) && (a[1] != 8 || (a[7] & OPEN_BIT)),
                 "set_arguments: not a ZKA1 (version 1) argument blob");
     const uint32_t n_terms = a[5], n_records = a[1] >= 4 ? a[6] : 0;            // header word 6: the records of version 4, reserved before
     const size_t rec0 = ARGS_HEADER + (size_t)TERM_WORDS * n_terms;
@@ -55,11 +55,24 @@ const char* decode_arguments(const uint32_t* a, size_t words, Arguments* out) {
     // The PAGES record (version 7, kind 4, 32 words): L, ng, the blob index of its LINK, words 4 .. 15 reserved, then from word 16 the
     // destinations p_on, p_addr, p_in, p_out, p_time, alimb_0 .. alimb_{ng-1}, gap_0 .. gap_{ng-1}, the rest 0 (pages_clause_a).  Header
     // word 7 carries bit 16 beside the READS count.
+    // The OPEN record (version 8, kind 5, 16 words), after every other record: the open tag, the `out` offsets of alpha, beta and the total, the
+    // circuit's `out` words, words 6 .. 15 reserved (open_rule).  Header words 3, 4 repeat alpha and beta; header word 7 carries bit 17 beside
+    // the READS count and, exactly when the blob holds a PAGES record, bit 16.
     out->records.clear();
     out->links.clear();
     out->pages.clear();
+    out->open.clear();
     const uint32_t* r = a + rec0;
     for (uint32_t i = 0; i < n_records; i++) {
+        if (!out->open.empty() && out->after_open == NONE) { out->after_open = i; out->second_open = r[0] == KIND_OPEN; }
+        if (out->version >= 8 && r[0] == KIND_OPEN) {
+            Open x{};
+            x.index = i; x.tag = r[1]; x.alpha = r[2]; x.beta = r[3]; x.total = r[4]; x.out_words = r[5];
+            for (uint32_t j = 6; j < OPEN_WORDS; j++) x.reserved |= r[j];
+            out->open.push_back(x);
+            r += OPEN_WORDS;
+            continue;
+        }
         if (!out->pages.empty() && out->after_pages == NONE) { out->after_pages = i; out->second_pages = out->version >= 7 && r[0] == KIND_PAGES; }
         if (out->version >= 7 && r[0] == KIND_PAGES) {
             Pages x{};
@@ -102,9 +115,12 @@ const char* decode_arguments(const uint32_t* a, size_t words, Arguments* out) {
         out->records.push_back(x);
         r += RECORD_WORDS;
     }
-    const uint32_t word7 = out->version >= 7 ? a[7] ^ PAGES_BIT : a[7];          // version 7: bit 16 says PAGES, the rest counts as before
+    const bool paged = out->version == 7 || (out->version >= 8 && (a[7] & PAGES_BIT));
+    const uint32_t word7 = (paged ? a[7] ^ PAGES_BIT : a[7]) ^ (out->version >= 8 ? OPEN_BIT : 0);     // bit 16 says PAGES, bit 17 OPEN, the rest counts as before
     ZKH_REQUIRE(out->version < 6 || word7 == out->reads, "set_arguments: header word 7 is %u, the blob has %u LINK records with READS", word7, out->reads);
-    ZKH_REQUIRE(out->version < 7 || !out->pages.empty(), "set_arguments: header word 7 has bit 16 (PAGES), but the blob has no PAGES record");
+    ZKH_REQUIRE(!paged || !out->pages.empty(), "set_arguments: header word 7 has bit 16 (PAGES), but the blob has no PAGES record");
+    ZKH_REQUIRE(out->version < 8 || paged || out->pages.empty(), "set_arguments: the blob has a PAGES record, but header word 7 lacks bit 16 (PAGES)");
+    ZKH_REQUIRE(out->version < 8 || !out->open.empty(), "set_arguments: header word 7 has bit 17 (OPEN), but the blob has no OPEN record");
     return nullptr;
 }
 
@@ -356,13 +372,50 @@ const char* check_owned(const zkh_circuit* c, const Arguments& a, const std::vec
     return nullptr;
 }
 
+// logup.check_open: the OPEN record is the last record and the only one of its kind; its reserved words are 0; its tag is below P, some term
+// carries it and none of them is derived or a sorted copy; alpha, beta and the total are three disjoint runs of 4 words inside the circuit's
+// `out`; header words 3, 4 repeat alpha and beta
+const char* open_rule(const zkh_circuit* c, const Arguments& a) {
+    if (a.open.empty()) return nullptr;
+    const Open& o = a.open[0];
+    const uint32_t i = o.index;
+    if (a.after_open != NONE) {
+        ZKH_REQUIRE(!a.second_open, "set_arguments: record %u: a second OPEN record (record %u is one: a seal closes on one total)", a.after_open, i);
+        return make_err("set_arguments: record %u: a record after the OPEN record %u (the OPEN record comes last)", a.after_open, i);
+    }
+    ZKH_REQUIRE(!o.reserved, "set_arguments: record %u: a reserved word of the OPEN record is not 0 (words 6..15)", i);
+    ZKH_REQUIRE(o.tag < P, "set_arguments: record %u: the open tag %u is not below P", i, o.tag);
+    ZKH_REQUIRE(o.out_words == c->global_size[GLOBAL_OUT], "set_arguments: record %u: the OPEN record is of a circuit with %u out words, this one has %u", i,
+                o.out_words, c->global_size[GLOBAL_OUT]);
+    const uint32_t off[3] = {o.alpha, o.beta, o.total};
+    const char* name[3] = {"alpha", "beta", "the total"};
+    for (int e = 0; e < 3; e++)
+        ZKH_REQUIRE((uint64_t)off[e] + 4 <= o.out_words, "set_arguments: record %u: %s at out words %u..%u, the circuit has %u", i, name[e], off[e], off[e] + 3,
+                    o.out_words);
+    for (int e = 0; e < 3; e++)
+        for (int f = 0; f < e; f++)
+            ZKH_REQUIRE(off[e] + 4 <= off[f] || off[f] + 4 <= off[e], "set_arguments: record %u: alpha, beta and the total overlap in out (words %u, %u, %u: 4 words each)",
+                        i, o.alpha, o.beta, o.total);
+    ZKH_REQUIRE(a.alpha == o.alpha && a.beta == o.beta, "set_arguments: record %u: header words 3, 4 are %u, %u, the OPEN record's alpha, beta are %u, %u", i,
+                a.alpha, a.beta, o.alpha, o.beta);
+    bool any = false;
+    for (uint32_t j = 0; j < a.terms.size(); j++) {
+        if (a.terms[j].tag != o.tag) continue;
+        any = true;
+        ZKH_REQUIRE(!a.terms[j].derive && !a.terms[j].sorted, "set_arguments: record %u: term %u of the open tag %u is derived or a sorted copy (another seal answers "
+                    "the open tag)", i, j, o.tag);
+    }
+    ZKH_REQUIRE(any, "set_arguments: record %u: no term has the open tag %u", i, o.tag);
+    return nullptr;
+}
+
 // the arguments against the circuit's shape, then the rules of sorted copies, then those of derived multiplicities
 const char* check_arguments(const zkh_circuit* c, const Arguments& a) {
     const uint32_t k = a.k;
     ZKH_REQUIRE(k >= 1 && 4ull * k == c->group_size[GROUP_ACCUM], "set_arguments: %u accum Fp4 columns, the circuit's accum group is %u wide",
                 k, c->group_size[GROUP_ACCUM]);
     const uint32_t mix = c->global_size[GLOBAL_MIX];
-    ZKH_REQUIRE((uint64_t)a.alpha + 4 <= mix && (uint64_t)a.beta + 4 <= mix, "set_arguments: alpha / beta at mix words %u / %u, the circuit has %u",
+    ZKH_REQUIRE(a.is_open() || ((uint64_t)a.alpha + 4 <= mix && (uint64_t)a.beta + 4 <= mix), "set_arguments: alpha / beta at mix words %u / %u, the circuit has %u",
                 a.alpha, a.beta, mix);
     std::vector<uint32_t> per_col(k, 0);
     uint32_t prev = 0;
@@ -382,6 +435,7 @@ const char* check_arguments(const zkh_circuit* c, const Arguments& a) {
     for (uint32_t col = 0; col < k; col++) ZKH_REQUIRE(per_col[col] >= 1, "set_arguments: accum column %u has no terms", col);
     if (a.version >= 3) ZKH_TRY(check_sorted(a));
     if (a.version >= 2) ZKH_TRY(check_derived(a));
+    ZKH_TRY(open_rule(c, a));
     if (a.after_pages != NONE) {
         ZKH_REQUIRE(!a.second_pages, "set_arguments: record %u: a second PAGES record (record %u is one: a blob pages one memory)", a.after_pages, a.pages[0].index);
         return make_err("set_arguments: record %u: a record after the PAGES record %u (the PAGES record comes last)", a.after_pages, a.pages[0].index);
@@ -434,6 +488,13 @@ extern "C" int zkh_circuit_derives_links(const zkh_circuit* c) { return c && c->
 extern "C" int zkh_circuit_links_check_reads(const zkh_circuit* c) { return c && c->args ? (int)c->args->reads : 0; }
 
 extern "C" int zkh_circuit_pages(const zkh_circuit* c) { return c && c->args && !c->args->pages.empty(); }
+
+extern "C" int zkh_circuit_open_bus(const zkh_circuit* c, uint32_t where[4]) {
+    if (!c || !c->args || !c->args->is_open()) return 0;
+    const Open& o = c->args->open[0];
+    if (where) { where[0] = o.tag; where[1] = o.alpha; where[2] = o.beta; where[3] = o.total; }
+    return 1;
+}
 
 // THE DERIVE STAGES, IN THEIR ORDER (arguments.h, WHO WRITES A DATA COLUMN): the one statement of the order in code.  A LIMBS / ORDER
 // record may read a sorted copy's column, and the multiplicities count the limbs that the records and the links derive.

@@ -101,6 +101,7 @@ __device__ __forceinline__ void add_combined(unsigned long long* cnt, uint32_t s
 }
 
 // grid (x, y): the workgroups of one y take the terms y, y + gridDim.y, ...; rows in strides of gridDim.x workgroups
+constexpr uint32_t BUS_SKIP = 2;                // in place of a term's sign: the term is of the open tag of an OPEN record (ZKA1 version 8) and holds no entry here
 __global__ __launch_bounds__(BUS_THREADS) void k_bus_build(const uint32_t* __restrict__ code, const uint32_t* __restrict__ data,
                                                            const KeyTerm* __restrict__ terms, const uint32_t* __restrict__ negs,
                                                            uint32_t n_terms, unsigned long long* slots, unsigned long long* cnt, uint32_t mask,
@@ -108,6 +109,7 @@ __global__ __launch_bounds__(BUS_THREADS) void k_bus_build(const uint32_t* __res
     for (uint32_t ti = blockIdx.y; ti < n_terms; ti += gridDim.y) {
         const KeyTerm t = terms[ti];
         const uint32_t neg = negs[ti];
+        if (neg == BUS_SKIP) continue;                                   // a term of the open tag: another seal answers its keys (workgroup-uniform)
         for (uint32_t base = blockIdx.x * BUS_THREADS; base < A; base += gridDim.x * BUS_THREADS) {     // the same trips for every lane
             const uint32_t r = base + threadIdx.x;
             uint32_t s = NONE, w = 0;
@@ -210,7 +212,7 @@ extern "C" const char* zkh_check_bus(zkh_ctx* ctx, const zkh_circuit* c, size_t 
     bind_thread(ctx);
 
     std::vector<uint32_t> table = key_term_table(a, n_terms);         // then every term's sign
-    for (uint32_t i = 0; i < n_terms; i++) table[n_terms * KEY_TERM_WORDS + i] = a[i].neg ? 1 : 0;
+    for (uint32_t i = 0; i < n_terms; i++) table[n_terms * KEY_TERM_WORDS + i] = c->args->open_tag(a[i].tag) ? BUS_SKIP : a[i].neg ? 1 : 0;
     Tmp dtab, status, slots;
     ZKH_TRY(zkh_copy_from(ctx, "bus_terms", table.data(), table.size(), dtab.out()));
     ZKH_TRY(new_buf(ctx, ST_WORDS, false, status.out()));

@@ -51,7 +51,12 @@ enum : uint32_t { PC_GSEL = 39, PC_GPOW = 40, PC_GEND = 41 };
 enum : uint32_t { PD_LIVE = 125, PD_LO = 126, PD_GBIT = 127, PD_GACC = 128 };
 // the shape of the circuit an entry point serves (p2_rows.h PageShape)
 constexpr PageShape PAGE = {"P2-PAGE", 5, PG_WC, PG_WD, 4, PG_OUT, PG_MAX_H, " (the code group is an input of this generator)"},
-                    ORDERED = {"P2-PAGE-ordered", 6, PO_WC, PO_WD, 4, PO_OUT, PO_MAX_H, " (the code group is an input of this generator)"};
+                    ORDERED = {"P2-PAGE-ordered", 6, PO_WC, PO_WD, 4, PO_OUT, PO_MAX_H, " (the code group is an input of this generator)"},
+                    // P2-PAGE-tied (p2_page_tied.py): P2-PAGE-ordered's code and data groups column for column, so both of its calls serve it; its out
+                    // is those 18 words ‖ alpha ‖ beta ‖ F, of which the generator writes the 18
+                    TIED = {"P2-PAGE-tied", 8, PO_WC, PO_WD, 4, 30, PO_MAX_H, " (the code group is an input of this generator)"};
+// the shape the P2-PAGE-ordered calls serve: the circuit's own kind decides
+inline const PageShape& ordered_shape(const zkh_circuit* c) { return c && c->kind == TIED.kind ? TIED : ORDERED; }
 // code columns (p2_page.py C_*)
 enum : uint32_t { PC_LIN = 3, PC_FULLR, PC_PARTR, PC_LF, PC_LP, PC_LEAF_IN, PC_NODE_IN, PC_PATH_FIRST, PC_TOP_OUT, PC_LAST_TOP, PC_CARRY, PC_POW, PC_RC };
 // data columns (p2_page.py D_*)
@@ -276,7 +281,7 @@ const char* page_witgen(const char* who, const PageShape& sh, bool whole, zkh_ct
     ZKH_REQUIRE(r[PR_CODE_OK], "%s: the code group was not built for h %u (zkh_page_circuit_code with this image's size)", who, h);
     ZKH_TRY(table_refusal(who, r, W));
     memcpy(out_roots, r + PR_ROOTS, 4 * PG_OUT);
-    if (sh.out == PO_OUT) { out_roots[16] = r[PR_LO]; out_roots[17] = r[PR_HI]; }
+    if (sh.wd == PO_WD) { out_roots[16] = r[PR_LO]; out_roots[17] = r[PR_HI]; }
     return nullptr;
 }
 
@@ -323,12 +328,12 @@ extern "C" const char* zkh_page_circuit_witgen_part(zkh_ctx* ctx, const zkh_circ
 
 // P2-PAGE-ordered (zeth_amd/circuits/p2_page_ordered.py): the same two calls on the wider circuit
 extern "C" const char* zkh_page_ordered_code(zkh_ctx* ctx, const zkh_circuit* c, size_t po2, size_t zk_cycles, size_t image_words, zkh_buf* code) {
-    return page_code("page_ordered_code", ORDERED, ctx, c, po2, zk_cycles, image_words, code);
+    return page_code("page_ordered_code", ordered_shape(c), ctx, c, po2, zk_cycles, image_words, code);
 }
 
 extern "C" const char* zkh_page_ordered_witgen(zkh_ctx* ctx, const zkh_circuit* c, size_t po2, size_t zk_cycles, const zkh_buf* code, const zkh_buf* proof,
                                                size_t proof_words, const zkh_buf* nodes_before, const zkh_buf* nodes_after, size_t first, zkh_buf* data,
                                                uint32_t out[18], const uint32_t* noise_key) {
-    return page_witgen("page_ordered_witgen", ORDERED, false, ctx, c, po2, zk_cycles, code, proof, proof_words, nodes_before, nodes_after, first, data, out,
+    return page_witgen("page_ordered_witgen", ordered_shape(c), false, ctx, c, po2, zk_cycles, code, proof, proof_words, nodes_before, nodes_after, first, data, out,
                        noise_key);
 }

@@ -339,6 +339,18 @@ extern "C" const char* zkh_code_root(zkh_prover* pr, const zkh_buf* code, size_t
     memcpy(root, pg.merkle.root(), 32);
     return nullptr;
 }
+// Its sibling for the data group: the root a seal of this data trace carries (zkh_seal_data_root reads it out of the seal), before any seal
+// is made.  The roots of a tied group's data traces are what its shared challenge is drawn from (zkh_tie_challenge).  zkh_prove_begin
+// commits the data group again: a begin that takes a held commitment is not part of this.
+extern "C" const char* zkh_data_root(zkh_prover* pr, size_t po2, const zkh_buf* data, uint32_t root[8]) {
+    ZKH_REQUIRE(pr && data && root, "data_root: null argument");
+    ZKH_REQUIRE(po2 >= 1 && po2 + 2 <= (size_t)MAX_LOG_N, "data_root: po2 %zu out of range", po2);
+    PolyGroup pg;
+    ZKH_TRY(commit_group_enqueue(pr->ctx, pg, data, pr->circuit->group_size[GROUP_DATA], (size_t)1 << po2));
+    ZKH_TRY(pg.merkle.fetch_top(pr->ctx));
+    memcpy(root, pg.merkle.root(), 32);
+    return nullptr;
+}
 extern "C" const char* zkh_syn_control_root(zkh_prover* pr, size_t po2, size_t zk_cycles, uint32_t root[8]) {
     ZKH_REQUIRE(pr && root, "syn_control_root: null argument");
     ZKH_REQUIRE(po2 >= 1 && po2 + 2 <= (size_t)MAX_LOG_N && ((size_t)1 << po2) > zk_cycles + 1, "syn_control_root: po2 %zu out of range", po2);

@@ -349,6 +349,48 @@ extern "C" const char* zkh_verify_segment(const zkh_circuit* c, const uint32_t* 
     return nullptr;
 }
 
+// ---- THE TIE: what a group verifier reads out of seals that share a bus, HOST ONLY ----
+// The root of the data group a seal commits to, folded from the top layer the seal carries exactly as zkh_verify_segment folds it (and
+// commits it to the transcript).  It reads the header and the two tree tops, nothing else: a seal that has not been verified proves
+// nothing about the root, so verify it first.
+extern "C" const char* zkh_seal_data_root(const zkh_circuit* c, const uint32_t* seal, size_t seal_words, uint32_t root[8]) {
+    ZKH_REQUIRE(c && seal && root, "seal_data_root: null argument");
+    std::unique_ptr<Tables> tab(new Tables);
+    ZKH_TRY(make_tables(*tab, ZKH_P2_ROUND_CONSTANTS, ZKH_P2_M_INT_DIAG));
+    Hasher hasher{tab.get()};
+    ReadIop io{seal, seal_words, 0, &hasher};
+    const size_t out_size = c->global_size[GLOBAL_OUT];
+    const uint32_t* head = io.read(out_size + 1);
+    ZKH_REQUIRE(head && reduced(head, out_size + 1), "seal_data_root: seal truncated or unreduced (header)");
+    const uint32_t po2 = fp_decode(Fp::raw(head[out_size]));
+    ZKH_REQUIRE(po2 >= 1 && po2 <= 24, "seal_data_root: bad po2 %u", po2);
+    const size_t domain = ((size_t)1 << po2) * ZKH_INV_RATE;
+    TreeVerifier code, data;
+    const char* e;
+    if ((e = code.init(io, domain, c->group_size[GROUP_CODE])) || (e = data.init(io, domain, c->group_size[GROUP_DATA])))
+        return make_err("seal_data_root: %s", e);
+    ZKH_REQUIRE(reduced(data.top[1].w, 8), "seal_data_root: unreduced root");
+    memcpy(root, data.top[1].w, 32);
+    return nullptr;
+}
+// The shared challenge alpha ‖ beta of a tied group: the hash suite's digest of (the domain word 'ZKT1', n, the n data roots in order: the
+// segment's, then the parts') seeds a fresh transcript generator, and eight random elements follow.  A function of the roots alone, so
+// the prover (which holds the traces) and the verifier (which reads the roots out of the seals) call this one function.
+extern "C" const char* zkh_tie_challenge(const uint32_t* roots, size_t n, uint32_t challenge[8]) {
+    ZKH_REQUIRE(roots && challenge, "tie_challenge: null argument");
+    ZKH_REQUIRE(n >= 1 && n < P, "tie_challenge: %zu roots (at least the segment's)", n);
+    ZKH_REQUIRE(reduced(roots, 8 * n), "tie_challenge: a root word is not a reduced element");
+    std::unique_ptr<Tables> tab(new Tables);
+    ZKH_TRY(make_tables(*tab, ZKH_P2_ROUND_CONSTANTS, ZKH_P2_M_INT_DIAG));
+    Hasher hasher{tab.get()};
+    std::vector<uint32_t> in{0x5a4b5431u, (uint32_t)n};
+    in.insert(in.end(), roots, roots + 8 * n);
+    ReadIop io{nullptr, 0, 0, &hasher};
+    io.commit(hasher.elems(in.data(), in.size()));
+    for (int i = 0; i < 8; i++) challenge[i] = io.elem();
+    return nullptr;
+}
+
 // =====================================================================================================
 // Receipt container — a versioned, self-describing envelope around a seal (row f3 groundwork).
 // Upstream ships `SegmentReceipt{seal, index, hashfn, claim, verifier_parameters}` bincode-encoded inside `ProveInfo`

@@ -9,7 +9,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
-from typing import List, Optional, Sequence
+from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -171,6 +171,9 @@ ABI = {
     "zkh_circuit_set_arguments": (_err, [_vp, _u32p, _sz]),
     "zkh_circuit_has_arguments": (_i, [_vp]),
     "zkh_accumulate": (_err, [_vp, _vp, _sz, _sz, _u32p, _vp, _vp, _u32p, _vp]),
+    "zkh_circuit_open_bus": (_i, [_vp, _u32p]),
+    "zkh_accumulate_open": (_err, [_vp, _vp, _sz, _sz, _u32p, _vp, _vp, _u32p, _vp, _u32p]),
+    "zkh_table_fingerprint": (_err, [_vp, _vp, _sz, _sz, _u32p, _u32p]),
     "zkh_circuit_derives_multiplicities": (_i, [_vp]),
     "zkh_derive_multiplicities": (_err, [_vp, _vp, _sz, _sz, _vp, _vp]),
     "zkh_circuit_derives_sorted": (_i, [_vp]),
@@ -222,7 +225,10 @@ ABI = {
     "zkh_prove_finish": (_err, [_vp, _vp, C.POINTER(_u32p), C.POINTER(_sz)]),
     "zkh_prove_abort": (None, [_vp]),
     "zkh_code_root": (_err, [_vp, _vp, _sz, _u32p]),
+    "zkh_data_root": (_err, [_vp, _sz, _vp, _u32p]),
     "zkh_syn_control_root": (_err, [_vp, _sz, _sz, _u32p]),
+    "zkh_seal_data_root": (_err, [_vp, _u32p, _sz, _u32p]),
+    "zkh_tie_challenge": (_err, [_u32p, _sz, _u32p]),
     "zkh_verify_segment": (_err, [_vp, _u32p, _sz, _u32p, _u32p, _u32p]),
     "zkh_receipt_claim": (_err, [_vp, _u32p, _sz, _u32p, _u32p, _u32p, _u32p]),
     "zkh_receipt_encode": (_err, [_vp, _u32p, _sz, _u32, _u32p, C.POINTER(_u32p), C.POINTER(_sz)]),
@@ -315,6 +321,17 @@ def image_proof_verify(proof, root_before) -> np.ndarray:
         raise HalError(f"image_proof_verify: root_before of {before.size} words")
     _check(lib.zkh_image_proof_verify(_ptr(words), words.size, _ptr(before), _ptr(after)))
     return after
+
+
+def tie_challenge(roots) -> np.ndarray:
+    """alpha ‖ beta (8 Montgomery words) of a tied group from its data roots in order, the segment's first and then the parts', on the host
+    alone (zkh_tie_challenge): the one function the prover and the verifier of a tied group both call"""
+    lib = load_library()
+    r, out = _u32(roots).reshape(-1), np.zeros(8, dtype=np.uint32)
+    if not r.size or r.size % DIGEST_WORDS:
+        raise HalError(f"tie_challenge: roots of {r.size} words (one or more digests of {DIGEST_WORDS})")
+    _check(lib.zkh_tie_challenge(_ptr(r), r.size // DIGEST_WORDS, _ptr(out)))
+    return out
 
 
 class Buffer:
@@ -415,6 +432,11 @@ class Circuit:
         derive_all_paged) and page_out writes it back; derive_links and derive_all refuse such a circuit"""
         return bool(_lib.zkh_circuit_pages(self.h))
 
+    def open_bus(self) -> Optional[Tuple[int, int, int, int]]:
+        """(the open tag, the `out` offsets of alpha, beta and the total) of arguments that are an OPEN bus (ZKA1 version 8), else None"""
+        where = np.zeros(4, dtype=np.uint32)
+        return tuple(int(x) for x in where) if _lib.zkh_circuit_open_bus(self.h, _ptr(where)) else None
+
     def derived_data_columns(self) -> List[int]:
         """the data columns the library's derives (sorted, columns, links, multiplicities) write on the active rows, ascending"""
         cols = np.zeros(max(1, int(self.desc[5])), dtype=np.uint32)
@@ -498,6 +520,13 @@ class HostCircuit:
         r = _ptr(_u32(rc)) if rc is not None else None
         d = _ptr(_u32(diag)) if diag is not None else None
         _check(_lib.zkh_receipt_claim(self.h, _ptr(s), s.size, _ptr(cr), r, d, _ptr(out)))
+        return out
+
+    def seal_data_root(self, seal) -> np.ndarray:
+        """the root (8 words) of the data group a seal of this circuit commits to, folded from the top layer the seal carries as the
+        verifier folds it (zkh_seal_data_root).  It proves nothing about a seal that has not been verified."""
+        s, out = _u32(seal), np.zeros(8, dtype=np.uint32)
+        _check(_lib.zkh_seal_data_root(self.h, _ptr(s), s.size, _ptr(out)))
         return out
 
 
@@ -877,6 +906,29 @@ class HipHal:
         m = _u32(mix_global)
         _k, kp = _key_ptr(noise_seed)
         _check(_lib.zkh_accumulate(self.ctx, circuit.h, po2, zk_cycles, kp, code.h, data.h, _ptr(m), accum.h))
+
+    def accumulate_open(self, circuit: Circuit, po2: int, zk_cycles: int, noise_seed: int, code: Buffer, data: Buffer, challenge,
+                        accum: Buffer) -> np.ndarray:
+        """accumulate for a circuit whose arguments are an OPEN bus (zkh_accumulate_open; ZKA1 version 8): challenge = alpha ‖ beta (8
+        reduced Montgomery words) where the mix globals were -> the bus total, 4 Montgomery words, which the seal states in `out`.
+        Raises HalError if a denominator vanishes (the accum is then left zeroed), or on a closed blob"""
+        ch, total = _u32(challenge), np.zeros(4, dtype=np.uint32)
+        if ch.size != 8:
+            raise HalError(f"accumulate_open: a challenge of {ch.size} words (alpha and beta: 8)")
+        _k, kp = _key_ptr(noise_seed)
+        _check(_lib.zkh_accumulate_open(self.ctx, circuit.h, po2, zk_cycles, kp, code.h, data.h, _ptr(ch), accum.h, _ptr(total)))
+        return total
+
+    def table_fingerprint(self, table: Buffer, table_at: int, rows: int, challenge) -> np.ndarray:
+        """the fingerprint (4 Montgomery words) of the `rows` table rows (address, in, out) at word `table_at` of `table`, where
+        zkh_page_out_proof left them (word 5 + h of the proof), under challenge = alpha ‖ beta (zkh_table_fingerprint; host twin:
+        circuits/logup.py table_fingerprint): what a tied segment's open total must be.  Raises HalError, naming the lowest row, if a
+        denominator vanishes"""
+        ch, total = _u32(challenge), np.zeros(4, dtype=np.uint32)
+        if ch.size != 8:
+            raise HalError(f"table_fingerprint: a challenge of {ch.size} words (alpha and beta: 8)")
+        _check(_lib.zkh_table_fingerprint(self.ctx, table.h, table_at, rows, _ptr(ch), _ptr(total)))
+        return total
 
     def derive_all(self, circuit: Circuit, po2: int, zk_cycles: int, code: Buffer, data: Buffer) -> None:
         """fill everything the circuit's arguments derive into `data`, the stages in their order (zkh_derive_all); nothing to derive:

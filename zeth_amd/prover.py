@@ -159,6 +159,12 @@ class SegmentProver:
         _hal._check(_hal._lib.zkh_code_root(self.h, code.h, po2, root.ctypes.data_as(C.POINTER(C.c_uint32))))
         return root
 
+    def data_root(self, data, po2: int) -> np.ndarray:
+        """the root a seal of the data trace `data` will carry for its data group (zkh_data_root), before the seal is made"""
+        root = np.zeros(8, dtype=np.uint32)
+        _hal._check(_hal._lib.zkh_data_root(self.h, po2, data.h, root.ctypes.data_as(C.POINTER(C.c_uint32))))
+        return root
+
     def witgen(self, seg: Segment):
         """Witness generation (code + data traces resident in HBM) — reported separately from the seal."""
         wa, wc, wd = self.group_sizes()
@@ -572,6 +578,124 @@ def verify_page_tree_chain(receipts, control_root, h: int, root_before=None) -> 
     for r in receipts:
         hc.verify_segment(r.seal, control_root)
     return link_page_tree_chain([r.seal[:pt.OUT_WORDS] for r in receipts], h, root_before)
+
+
+TIE_WORDS = 12                                  # alpha (4) ‖ beta (4) ‖ F (4): the last words of `out` of every seal of a tied group
+
+
+def _fmt_words(w) -> str:
+    return " ".join(f"{int(x):08x}" for x in w)
+
+
+def seal_tied(seg_prover: SegmentProver, seg: Segment, code, data, out_prefix, page_prover: SegmentProver, page_segs, proof, proof_words: int,
+              nodes_before, nodes_after, check: bool = False, check_table: bool = True):
+    """Seal a paging segment and the page-out of its memory as ONE tied group (DESIGN.md §2 "THE TIE") -> (the segment's receipt, [the
+    parts' receipts]): the seals share a bus under a challenge drawn from all their data roots, and `verify_tied` accepts them only
+    together.  seg_prover: a prover of an open-bus paging circuit (SYN-LOOKUP-tied, built with its arguments); code, data: the segment's
+    traces on the device, derived and reduced (what seal_host_witness hands its accumulate); out_prefix: the segment's `out` words before
+    alpha.  page_prover: a prover of P2-PAGE-tied with p2_page_tied.arguments(); page_segs, proof, proof_words, nodes_before, nodes_after:
+    seal_page_out_ordered's operands.  Two passes, so that one part's traces are held at a time:
+      1. the roots: the segment's data root (zkh_data_root); per part the witness, its data root, and the buffer is reused; the
+         challenge alpha ‖ beta = hal.tie_challenge(the roots, the segment's first).
+      between, with check_table: the segment's open total must be hal.table_fingerprint of the proof's table under that challenge, else
+         HalError "the proof's table is not the segment's page table": no part is sealed on a table that cannot cancel.
+      2. the segment and then every part: the part's witness again (the same noise key gives the same trace, hence the same root),
+         accumulate_open, out = prefix ‖ challenge ‖ total, zkh_prove_begin, with `check` check_witness, zkh_prove_finish.
+    Every receipt carries its code group's root as `control_root`."""
+    from .circuits import p2_page_tied as pt
+    who = "seal_tied"
+    hal = seg_prover.hal
+    for name, p in (("segment", seg_prover), ("page-out", page_prover)):
+        if p.circuit.open_bus() is None:
+            raise _hal.HalError(f"{who}: the {name} prover's circuit has no open bus (its arguments hold no OPEN record)")
+    page_segs = list(page_segs)
+    if not page_segs:
+        raise _hal.HalError(f"{who}: no segment for the page-out (a page-out of no rows still has one part)")
+    po2, zk = page_segs[0].po2, page_segs[0].zk_cycles
+    if any((s.po2, s.zk_cycles) != (po2, zk) for s in page_segs):
+        raise _hal.HalError(f"{who}: the parts share one code group: every segment must have the same (po2, zk_cycles)")
+    if not isinstance(proof, _hal.Buffer):
+        proof = hal.copy_from("image_proof", np.ascontiguousarray(proof, dtype=np.uint32).reshape(-1))
+
+    def fit(plan, D, room):
+        if len(page_segs) != len(plan):
+            raise _hal.HalError(f"{who}: {len(page_segs)} segments, but a table of {D} rows takes {len(plan)} parts of {room} at po2 {po2}")
+
+    page_code, plan = page_prover._open_path_chain(hal.page_ordered_code)(proof, po2, zk, fit)
+    head = proof.slice(0, 5).to_vec()
+    rows, table_at = int(head[2]), 5 + int(head[4])
+    page_data = hal.alloc_elem("data", page_prover.group_sizes()[2] << po2)
+
+    def part_witness(s, part):
+        return hal.page_ordered_witgen(page_prover.circuit, po2, zk, page_code, proof, proof_words, nodes_before, nodes_after, *part, page_data, s.noise_seed)
+
+    # pass one: the data roots, the segment's first
+    roots = [seg_prover.data_root(data, seg.po2)]
+    for s, part in zip(page_segs, plan):
+        part_witness(s, part)
+        roots.append(page_prover.data_root(page_data, po2))
+    challenge = _hal.tie_challenge(np.concatenate(roots))
+
+    def open_seal(prover, s, code, data, prefix, control_root):
+        accum = hal.alloc_elem("accum", prover.group_sizes()[0] << s.po2)
+        total = hal.accumulate_open(prover.circuit, s.po2, s.zk_cycles, s.noise_seed, code, data, challenge, accum)
+        out = np.concatenate([np.asarray(prefix, dtype=np.uint32).reshape(-1), challenge, total]).astype(np.uint32)
+        if out.size != prover.out_size():
+            raise _hal.HalError(f"{who}: {out.size} out words (a prefix of {out.size - TIE_WORDS}, alpha, beta, the total), the circuit has {prover.out_size()}")
+        return accum, total, out, control_root
+
+    seg_accum, seg_total, seg_out, _ = open_seal(seg_prover, seg, code, data, out_prefix, None)
+    if check_table:
+        want = hal.table_fingerprint(proof, table_at, rows, challenge)
+        if not np.array_equal(seg_total, want):
+            raise _hal.HalError(f"{who}: the proof's table is not the segment's page table: the segment's open total is {_fmt_words(seg_total)}, "
+                                f"the fingerprint of the proof's {rows} rows is {_fmt_words(want)}")
+    # pass two: the seals
+    seg_receipt = seg_prover.seal_with_accum(seg, code, data, seg_out, lambda _mix: seg_accum, check=check)
+    seg_receipt.control_root = seg_prover.code_root(code, seg.po2)
+    del seg_accum
+    page_root = page_prover.code_root(page_code, po2)
+    receipts = []
+    for s, part in zip(page_segs, plan):
+        prefix = part_witness(s, part)
+        accum, _total, out, _ = open_seal(page_prover, s, page_code, page_data, prefix[:pt.PREFIX_WORDS], None)
+        receipt = page_prover.seal_with_accum(s, page_code, page_data, out, lambda _mix, accum=accum: accum, check=check)
+        receipt.control_root = page_root.copy()
+        receipts.append(receipt)
+    return seg_receipt, receipts
+
+
+def verify_tied(seg_receipt, seg_circuit, seg_control_root, part_receipts, page_control_root, root_before=None) -> Tuple[np.ndarray, np.ndarray, int]:
+    """Verify a tied group (`seal_tied`), HOST ONLY -> (root_before, root_after, hi): the page table of the segment `seg_receipt` seals,
+    applied in order to the image under root_before, leaves root_after, its last address hi - 1 (hi = 0: the segment touched no memory).
+    seg_circuit: the segment circuit's description (its `out` ends on alpha ‖ beta ‖ F, as every tied circuit's does); the parts are
+    P2-PAGE-tied's.  On top of the ordered chain (`link_page_parts`, as verify_page_ordered_chain) it makes the four checks of the design:
+    every seal verifies against its control root; every seal states the challenge that `hal.tie_challenge` gives for the data roots read
+    out of the seals themselves, the segment's first (one comparison per seal: they then all state the same one); the totals F of all
+    seals add up to zero in Fp4.  Raises HalError, one line per cause, naming the seal and the two values that differ."""
+    from .circuits import p2_page_tied as pt
+    who = "verify_tied"
+    part_receipts = list(part_receipts)
+    seg_hc = _hal.HostCircuit(np.asarray(seg_circuit, dtype=np.uint32))
+    seg_out_size = int(np.asarray(seg_circuit, dtype=np.uint32)[7])
+    if seg_out_size < TIE_WORDS:
+        raise _hal.HalError(f"{who}: the segment circuit has {seg_out_size} out words: no room for alpha, beta and the total")
+    seg_hc.verify_segment(seg_receipt.seal, seg_control_root)
+    linked = link_page_parts(who, _verified_parts(part_receipts, pt.p2_page_tied_circuit, page_control_root, pt.decode), root_before,
+                             first_lo=(0, "0: addresses below it are not covered"))
+    page_hc = _hal.HostCircuit(pt.p2_page_tied_circuit())
+    seals = [("the segment", seg_hc, seg_receipt.seal, seg_out_size)] + [(f"part {p}", page_hc, r.seal, pt.OUT_WORDS) for p, r in enumerate(part_receipts)]
+    want = _hal.tie_challenge(np.concatenate([hc.seal_data_root(seal) for _, hc, seal, _ in seals]))
+    total = np.zeros(4, dtype=np.uint64)
+    for name, _, seal, out_size in seals[1:] + seals[:1]:                     # a part that was swapped in is named before the segment
+        stated = np.asarray(seal[out_size - TIE_WORDS:out_size - 4], dtype=np.uint32)
+        if not np.array_equal(stated, want):
+            raise _hal.HalError(f"{who}: {name}: its challenge {_fmt_words(stated)} is not the one the data roots give, {_fmt_words(want)}")
+        total = (total + np.asarray(seal[out_size - 4:out_size], dtype=np.uint64)) % np.uint64(_hal.P)
+    if total.any():
+        raise _hal.HalError(f"{who}: the totals do not cancel: the segment's F plus the parts' is {_fmt_words(total)}, not zero: the parts' rows are not "
+                            f"the segment's page table")
+    return linked
 
 
 def _generate_control_roots(po2s=range(13, 25)) -> None:
