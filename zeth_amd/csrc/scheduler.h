@@ -2,7 +2,9 @@
 //
 // zkh_session_prove (session.hip) is `ProverServer::prove_session` + the lift / join tree of `ProverImpl::{lift, join}` (risc0-zkvm
 // 3.0.3, un-vendored: /root/reference/Cargo.lock:5418) behind `default_prover().prove(env, elf)`
-// (/root/reference/crates/host/src/lib.rs:137).  Its worker threads do the GPU work; WHAT they do next is decided here:
+// (/root/reference/crates/host/src/lib.rs:137).  Its worker threads (ProveRun::worker: seal_step, node_step) do the GPU work; what a
+// fold node reads and publishes is claims.h (the same fold shape as the plan below: tests/cpp/claims_test.cpp holds the two to
+// each other); WHAT the threads do next is decided here:
 //   * FoldPlan — which recursion program proves which node, fixed before anything runs (zeth_amd/recursion.py fold_plan: the first
 //     level pairs the segments — one lift2 per pair where the program set has it for EVERY pair, else a lift per segment and joins —
 //     every level above takes three nodes per proof: join3 where a program exists for their sizes, else join(join(a, b), c); a

@@ -8,6 +8,14 @@
 // device; segments are independent, so here segment i goes to whichever lane is free next (one shared work
 // index over all lanes of all devices: round-robin with work stealing for the short tail), with NO exchange between devices.
 // Host code only (threads + the C ABI of this library); one lane = one zkh_ctx (device + stream) + circuit + prover.
+//
+// Three parts, two of them plain C++ that is unit-tested without a GPU:
+//   * scheduler.h — the fold plan and the scheduling state machine (WHAT a lane does next);
+//   * claims.h    — the claim rules (what a lift / join / union / resolve node reads and publishes, the fold shapes, the
+//                   allowed-programs tree): the prover and the verifiers below take them from there, with hash_pair_host;
+//   * this file   — the GPU work and the threads.  zkh_session_prove is a ProveRun taken through its stages in order:
+//                   chain_public_inputs, plan_fold, start_scheduler, prepare_preflight, run_lanes (worker / producer threads; a
+//                   worker's steps are seal_step and node_step, a node is run_node), write_statistics, join_tree (P2-JOIN).
 #include <algorithm>
 #include <array>
 #include <atomic>
@@ -16,6 +24,7 @@
 #include <deque>
 #include <memory>
 #include <mutex>
+#include <optional>
 #include <string>
 #include <thread>
 #include <vector>
@@ -23,9 +32,11 @@
 #include <sys/random.h>
 
 #include "circuit.h"
+#include "claims.h"
 #include "scheduler.h"
 
 using namespace zkh;
+using claims::NodeClaim;
 
 namespace {
 
@@ -70,7 +81,19 @@ struct ErrorSlot {
         return true;
     }
     bool any() { std::lock_guard<std::mutex> lk(lock); return !first.empty(); }
+    std::string get() { std::lock_guard<std::mutex> lk(lock); return first; }
 };
+
+struct SealFree { void operator()(uint32_t* p) const { zkh_free_seal(p); } };
+using SealPtr = std::unique_ptr<uint32_t, SealFree>;                   // a malloc'd seal and its owner
+struct CircuitFree { void operator()(zkh_circuit* c) const { zkh_circuit_destroy(c); } };
+using CircuitPtr = std::unique_ptr<zkh_circuit, CircuitFree>;
+const char* load_host_circuit(const std::vector<uint32_t>& desc, CircuitPtr* out) {     // host-only (no context): verification, claims
+    zkh_circuit* c = nullptr;
+    ZKH_TRY(zkh_circuit_load(nullptr, desc.data(), desc.size(), &c));
+    out->reset(c);
+    return nullptr;
+}
 
 }  // namespace
 
@@ -79,7 +102,7 @@ struct zkh_session {
     std::vector<uint32_t> desc, join_desc, rec_desc;
     std::vector<RecKind> rec_kinds;
     std::vector<std::vector<uint32_t>> rec_roots;                 // control root of program i
-    std::vector<std::vector<std::vector<uint32_t>>> allowed;       // levels of the allowed-programs tree (8 leaves)
+    claims::Levels allowed;                                       // levels of the allowed-programs tree (claims.h allowed_levels)
     std::vector<Lane> lanes;
     std::vector<Lane> fold_lanes;        // extra contexts that only lift / join (zkh_session_set_recursion): the fold packs the GPU with more lanes than the seals need
     std::vector<Lane*> rec_lanes;        // lanes + fold_lanes
@@ -155,96 +178,50 @@ extern "C" void zkh_session_set_accumulate(zkh_session* s, zkh_accumulate_fn fn,
     if (s) { s->accumulate = fn; s->accumulate_user = user; }
 }
 
-static const char* hash_pair_host(const uint32_t* a, const uint32_t* b, uint32_t out[8]) {
+// ---- the claim rules live in claims.h; what this file adds is the pair hash (the library's host permutation), the library's
+// error convention, and the claims of SEGMENT seals (which need the circuit) ----
+static std::string hash_pair_host(const uint32_t* a, const uint32_t* b, uint32_t out[8]) {
     uint32_t st[24] = {0};
     memcpy(st, a, 32); memcpy(st + 8, b, 32);
-    ZKH_TRY(zkh_poseidon2_mix_host(nullptr, nullptr, st, 1));
+    if (const char* e = zkh_poseidon2_mix_host(nullptr, nullptr, st, 1)) { const std::string msg(e); zkh_free_error(e); return msg; }
     memcpy(out, st, 32);
-    return nullptr;
+    return "";
 }
-constexpr size_t REC_ALLOWED = 16, REC_DEPTH = 4;                   // zeth_amd/circuits/rec_verify.py ALLOWED_DEPTH
+static const claims::PairHash HASH_PAIR = hash_pair_host;
+constexpr size_t REC_ALLOWED = claims::ALLOWED;
+static const char* claim_err(const std::string& e) { return e.empty() ? nullptr : make_err("%s", e.c_str()); }      // claims.h "" / message -> NULL / heap string
 
-// claim' = hash_pair(core, (pre, post, 0, 0, 0, 0, 0, 0)): what every recursion receipt publishes (circuits/rec_verify.py _wrap) — its
-// core claim bound to the state range [pre, post] it covers.  A join opens both children's claim' in-circuit and asserts
-// post(left) = pre(right); the opening (core, pre, post) travels next to a receipt as witness for its parent, never trusted.
-struct NodeClaim { uint32_t core[8] = {0}; uint32_t pre = 0, post = 0; };
-static const char* wrap_claim(const NodeClaim& c, uint32_t out[8]) {
-    const uint32_t st[8] = {c.pre, c.post, 0, 0, 0, 0, 0, 0};
-    return hash_pair_host(c.core, st, out);
-}
 // (receipt claim, pre, post) of a segment seal: SYN-C circuits (kind 1, five outputs) carry their state in out[4] / out[0]
-static const char* leaf_claim(const zkh_circuit* c, const uint32_t* seal, size_t words, const uint32_t* control_root, NodeClaim* out) {
-    ZKH_TRY(zkh_receipt_claim(c, seal, words, control_root, nullptr, nullptr, out->core));
+static void leaf_state(const zkh_circuit* c, const uint32_t* seal, NodeClaim* out) {
     const bool chained = circuit_has_state(c);
     out->pre = chained ? seal[4] : 0; out->post = chained ? seal[0] : 0;
+}
+static const char* leaf_claim(const zkh_circuit* c, const uint32_t* seal, size_t words, const uint32_t* control_root, NodeClaim* out) {
+    ZKH_TRY(zkh_receipt_claim(c, seal, words, control_root, nullptr, nullptr, out->core));
+    leaf_state(c, seal, out);
     return nullptr;
 }
-// parent of two nodes: core = hash_pair(claim'_l, claim'_r), state range = [pre_l, post_r]; the children must chain
-static const char* parent_claim(const NodeClaim& l, const NodeClaim& r, NodeClaim* out) {
-    ZKH_REQUIRE(l.post == r.pre, "claim tree: two neighbouring nodes do not chain (post(l) != pre(r)): no join has a witness for them");
-    uint32_t cl[8], cr[8];
-    ZKH_TRY(wrap_claim(l, cl)); ZKH_TRY(wrap_claim(r, cr));
-    ZKH_TRY(hash_pair_host(cl, cr, out->core));
-    out->pre = l.pre; out->post = r.post;
-    return nullptr;
+// a lifted assumption receipt publishes wrap(receipt claim, 0, 0)
+static const char* lifted_claim(const uint32_t* receipt_claim, claims::Digest* out) {
+    NodeClaim nd;
+    memcpy(nd.core, receipt_claim, 32);
+    return claim_err(claims::wrap(HASH_PAIR, nd, out->data()));
 }
-
-// the fold plan's shape over claim nodes (zeth_amd/recursion.py fold_plan): the first level pairs, every level above takes three at
-// a time (a group of three is join(join(a, b), c)), a remainder of two is a join, of one moves up
-static const char* fold_claim_nodes(std::vector<NodeClaim> nodes, NodeClaim* root) {
-    ZKH_REQUIRE(!nodes.empty(), "claim tree: no leaves");
-    for (size_t group = 2; nodes.size() > 1; group = 3) {
-        std::vector<NodeClaim> up;
-        size_t k = 0;
-        for (; k + group <= nodes.size(); k += group) {
-            NodeClaim nd;
-            ZKH_TRY(parent_claim(nodes[k], nodes[k + 1], &nd));
-            if (group == 3) { const NodeClaim ab = nd; ZKH_TRY(parent_claim(ab, nodes[k + 2], &nd)); }
-            up.push_back(nd);
-        }
-        if (nodes.size() - k == 2) { NodeClaim nd; ZKH_TRY(parent_claim(nodes[k], nodes[k + 1], &nd)); up.push_back(nd); }
-        else if (nodes.size() - k == 1) up.push_back(nodes[k]);
-        nodes.swap(up);
-    }
-    *root = nodes[0];
-    return nullptr;
+// verify one seal under one control root; a refusal is prefixed with whose seal it was
+static const char* verify_under(const zkh_circuit* c, const uint32_t* seal, size_t words, const uint32_t* control_root, const std::string& what) {
+    const char* e = zkh_verify_segment(c, seal, words, control_root, nullptr, nullptr);
+    if (!e) return nullptr;
+    const char* out = make_err("%s: %s", what.c_str(), e);
+    zkh_free_error(e);
+    return out;
 }
 
 // `receipt.verify` for a SUCCINCT receipt, on the host alone (no GPU, no session): what zeth_amd/recursion.py RecReceipt.verify does.
-// union(l, r): wrap(hash_pair(lo, hi), 0, 0) with (lo, hi) the two claim' sorted by their canonical words, lexicographically
-// (zeth_amd/recursion.py union_node; ProverServer::union, risc0-zkvm 3.0.3: the UnionClaim keeps left <= right)
-static const char* union_claim(const uint32_t* l, const uint32_t* r, uint32_t out[8]) {
-    bool swap = false;
-    for (int i = 0; i < 8; i++) {
-        const uint32_t a = fp_decode(Fp::raw(l[i])), b = fp_decode(Fp::raw(r[i]));
-        if (a != b) { swap = b < a; break; }
-    }
-    NodeClaim nd;
-    ZKH_TRY(hash_pair_host(swap ? r : l, swap ? l : r, nd.core));
-    return wrap_claim(nd, out);
-}
-// the union tree over assumption claim' (zeth_amd/recursion.py union_claims): neighbours pairwise, level by level, an odd one moves up
-static const char* union_tree(std::vector<std::array<uint32_t, 8>> level, uint32_t out[8]) {
-    ZKH_REQUIRE(!level.empty(), "union tree: no assumption claims");
-    while (level.size() > 1) {
-        std::vector<std::array<uint32_t, 8>> up;
-        for (size_t k = 0; k + 1 < level.size(); k += 2) {
-            std::array<uint32_t, 8> u;
-            ZKH_TRY(union_claim(level[k].data(), level[k + 1].data(), u.data()));
-            up.push_back(u);
-        }
-        if (level.size() % 2) up.push_back(level.back());
-        level.swap(up);
-    }
-    memcpy(out, level[0].data(), 32);
-    return nullptr;
-}
-
 static const char* succinct_verify_impl(const uint32_t* root_seal, size_t root_words, const uint32_t* allowed_roots, size_t n_allowed,
                                         size_t root_program, const uint32_t* leaves, size_t n_leaves, size_t ranks,
                                         const uint32_t* assumptions, size_t n_assumptions) {
     ZKH_REQUIRE(root_seal && allowed_roots && (leaves || !n_leaves) && (assumptions || !n_assumptions), "succinct_verify: null argument");
-    ZKH_REQUIRE(n_allowed >= 1 && n_allowed <= REC_ALLOWED && root_program < n_allowed, "succinct_verify: the receipt's program is not in the allowed set");
+    ZKH_REQUIRE(n_allowed >= 1 && n_allowed <= claims::ALLOWED && root_program < n_allowed, "succinct_verify: the receipt's program is not in the allowed set");
     ZKH_REQUIRE(n_leaves + n_assumptions >= 1, "succinct_verify: neither leaves nor assumptions");
     ZKH_REQUIRE(ranks >= 1 && n_leaves % ranks == 0 && (n_leaves || ranks == 1), "succinct_verify: %zu leaves do not split into %zu equal ranges", n_leaves, ranks);
     ZKH_REQUIRE(root_words > 16, "succinct_verify: not a recursion seal");
@@ -252,55 +229,21 @@ static const char* succinct_verify_impl(const uint32_t* root_seal, size_t root_w
     const uint32_t* rdesc = nullptr;
     size_t rdesc_words = 0;
     ZKH_TRY(zkh_shipped_circuit_desc("recursion", &rdesc, &rdesc_words));
-    zkh_circuit* rc = nullptr;
-    ZKH_TRY(zkh_circuit_load(nullptr, rdesc, rdesc_words, &rc));
-    std::unique_ptr<zkh_circuit, void (*)(zkh_circuit*)> hold(rc, zkh_circuit_destroy);
-    if (const char* e = zkh_verify_segment(rc, root_seal, root_words, allowed_roots + 8 * root_program, nullptr, nullptr)) {
-        const char* out = make_err("succinct_verify: root receipt: %s", e);
-        zkh_free_error(e);
-        return out;
-    }
+    CircuitPtr rc;
+    ZKH_TRY(load_host_circuit(std::vector<uint32_t>(rdesc, rdesc + rdesc_words), &rc));
+    ZKH_TRY(verify_under(rc.get(), root_seal, root_words, allowed_roots + 8 * root_program, "succinct_verify: root receipt"));
     // 2) the allowed-programs root the receipt carries is the root of THIS set (16 leaves, zero padded)
-    std::vector<std::vector<uint32_t>> level(REC_ALLOWED, std::vector<uint32_t>(8, 0));
-    for (size_t i = 0; i < n_allowed; i++) level[i].assign(allowed_roots + 8 * i, allowed_roots + 8 * i + 8);
-    while (level.size() > 1) {
-        std::vector<std::vector<uint32_t>> up(level.size() / 2, std::vector<uint32_t>(8));
-        for (size_t k = 0; k < up.size(); k++) ZKH_TRY(hash_pair_host(level[2 * k].data(), level[2 * k + 1].data(), up[k].data()));
-        level.swap(up);
-    }
-    ZKH_REQUIRE(memcmp(root_seal + 8, level[0].data(), 32) == 0, "succinct_verify: the receipt was produced under another allowed-programs root");
-    // 3) its claim is the root of the leaves' claim tree: `ranks` contiguous equal ranges folded on their own, their roots folded again
+    claims::Levels allowed;
+    ZKH_TRY(claim_err(claims::allowed_levels(HASH_PAIR, allowed_roots, n_allowed, &allowed)));
+    ZKH_REQUIRE(memcmp(root_seal + 8, allowed.back()[0].data(), 32) == 0, "succinct_verify: the receipt was produced under another allowed-programs root");
+    // 3) its claim is the root of the leaves' claim tree (`ranks` contiguous equal ranges folded on their own, their roots folded
+    //    again), resolved against the assumptions' union tree when there are any
     std::vector<NodeClaim> nodes(n_leaves);
     for (size_t i = 0; i < n_leaves; i++) { memcpy(nodes[i].core, leaves + 10 * i, 32); nodes[i].pre = leaves[10 * i + 8]; nodes[i].post = leaves[10 * i + 9]; }
-    if (ranks > 1) {
-        const size_t per = n_leaves / ranks;
-        std::vector<NodeClaim> tops(ranks);
-        for (size_t r = 0; r < ranks; r++) ZKH_TRY(fold_claim_nodes(std::vector<NodeClaim>(nodes.begin() + r * per, nodes.begin() + (r + 1) * per), &tops[r]));
-        nodes.swap(tops);
-    }
-    uint32_t want[8], assumed[8];
-    if (n_assumptions) {                  // a lifted assumption receipt publishes wrap(receipt claim, 0, 0)
-        std::vector<std::array<uint32_t, 8>> lifted(n_assumptions);
-        for (size_t i = 0; i < n_assumptions; i++) {
-            NodeClaim nd;
-            memcpy(nd.core, assumptions + 8 * i, 32);
-            ZKH_TRY(wrap_claim(nd, lifted[i].data()));
-        }
-        ZKH_TRY(union_tree(lifted, assumed));
-    }
-    if (n_leaves) {
-        NodeClaim top;
-        ZKH_TRY(fold_claim_nodes(nodes, &top));
-        ZKH_TRY(wrap_claim(top, want));
-        if (n_assumptions) {              // resolve(cond, assum): the session's state range over hash_pair(claim'_cond, claim'_assum)
-            NodeClaim res;
-            ZKH_TRY(hash_pair_host(want, assumed, res.core));
-            res.pre = top.pre; res.post = top.post;
-            ZKH_TRY(wrap_claim(res, want));
-        }
-    } else {
-        memcpy(want, assumed, 32);
-    }
+    std::vector<claims::Digest> lifted(n_assumptions);
+    for (size_t i = 0; i < n_assumptions; i++) ZKH_TRY(lifted_claim(assumptions + 8 * i, &lifted[i]));
+    uint32_t want[8];
+    ZKH_TRY(claim_err(claims::session_root_claim(HASH_PAIR, nodes, ranks, lifted, want)));
     ZKH_REQUIRE(memcmp(root_seal, want, 32) == 0, n_assumptions ? "succinct_verify: the receipt's claim is not the resolved root of the leaves' claim tree and the assumptions' union tree"
                                                                 : "succinct_verify: the receipt's claim is not the root of the leaves' claim tree");
     return nullptr;
@@ -364,15 +307,10 @@ extern "C" const char* zkh_session_set_recursion(zkh_session* s, const uint32_t*
         REC_TRY(zkh_rec_program_info(loaded[0].programs[i], root.data(), nullptr));
         rec_roots.push_back(root);
     }
-    std::vector<std::vector<uint32_t>> level(rec_roots);
-    level.resize(REC_ALLOWED, std::vector<uint32_t>(8, 0));
-    std::vector<std::vector<std::vector<uint32_t>>> allowed(1, level);
-    while (level.size() > 1) {
-        std::vector<std::vector<uint32_t>> up(level.size() / 2, std::vector<uint32_t>(8));
-        for (size_t k = 0; k < up.size(); k++) REC_TRY(hash_pair_host(level[2 * k].data(), level[2 * k + 1].data(), up[k].data()));
-        allowed.push_back(up);
-        level.swap(up);
-    }
+    std::vector<uint32_t> flat_roots;
+    for (const auto& r : rec_roots) flat_roots.insert(flat_roots.end(), r.begin(), r.end());
+    claims::Levels allowed;
+    REC_TRY(claim_err(claims::allowed_levels(HASH_PAIR, flat_roots.data(), rec_roots.size(), &allowed)));
 #undef REC_TRY
     // ---- commit (nothing below can fail) ----
     s->rec_desc.assign(rec_desc, rec_desc + rec_desc_words);
@@ -392,18 +330,14 @@ extern "C" const char* zkh_session_set_assumptions(zkh_session* s, const uint32_
     if (!n) { s->assum_desc.clear(); s->assum_seals.clear(); s->assum_po2.clear(); s->assum_roots.clear(); s->assum_claims.clear(); return nullptr; }
     ZKH_REQUIRE(desc && desc_words >= 16 && seals && seal_words && po2s && control_roots, "session_set_assumptions: null argument");
     // every receipt is verified HERE, on the host, against the control root it is handed with: what the lifts then prove in-circuit
-    zkh_circuit* hc = nullptr;
-    ZKH_TRY(zkh_circuit_load(nullptr, desc, desc_words, &hc));
-    std::unique_ptr<zkh_circuit, void (*)(zkh_circuit*)> hold(hc, zkh_circuit_destroy);
+    CircuitPtr hold;
+    ZKH_TRY(load_host_circuit(std::vector<uint32_t>(desc, desc + desc_words), &hold));
+    const zkh_circuit* hc = hold.get();
     ZKH_REQUIRE(!circuit_has_state(hc), "session_set_assumptions: an assumption circuit has no state words (its claim' is wrap(claim, 0, 0))");
     std::vector<uint32_t> claims(8 * n);
     for (size_t i = 0; i < n; i++) {
         ZKH_REQUIRE(seals[i] && po2s[i] >= 4 && po2s[i] <= 24, "session_set_assumptions: assumption %zu: bad seal / po2", i);
-        if (const char* e = zkh_verify_segment(hc, seals[i], seal_words[i], control_roots + 8 * i, nullptr, nullptr)) {
-            const char* out = make_err("session_set_assumptions: assumption receipt %zu: %s", i, e);
-            zkh_free_error(e);
-            return out;
-        }
+        ZKH_TRY(verify_under(hc, seals[i], seal_words[i], control_roots + 8 * i, "session_set_assumptions: assumption receipt " + std::to_string(i)));
         ZKH_TRY(zkh_receipt_claim(hc, seals[i], seal_words[i], control_roots + 8 * i, nullptr, nullptr, &claims[8 * i]));
     }
     s->assum_claims = std::move(claims);
@@ -588,118 +522,180 @@ extern "C" const char* zkh_session_build_recursion(zkh_session* s, const uint32_
     return zkh_session_set_recursion(s, rdesc, rdesc_words, ptrs.data(), words.data(), kinds.data(), built.size());
 }
 
-// one segment on one lane: built-in witness generator, or the caller's traces through prove_begin / accumulate / prove_finish
-// records / ram: this segment's preflight output in pinned memory (witness source 1), or NULL: run the preflight here (a retry)
-static const char* seal_one(zkh_session* s, Lane& l, const zkh_segment& seg, uint32_t** seal, size_t* words, double* witgen_s,
-                            const uint32_t* records = nullptr, const uint32_t* ram = nullptr, double* preflight_cpu_s = nullptr, double* trace_bytes = nullptr) {
-    const zkh_circuit* cir = l.circuit;
-    const size_t n = (size_t)1 << seg.po2;
-    NoiseKey nk;                                   // this segment's blinding key: the caller's, or (all-zero) 256 fresh bits from the OS
-    ZKH_TRY(resolve_noise_key(seg.noise_key, &nk));
-    const uint32_t* noise = nk.k;
-    Tmp code, data;
-    ZKH_TRY(zkh_alloc(l.ctx, "code", (size_t)cir->group_size[GROUP_CODE] * n, 0, code.out()));
-    ZKH_TRY(zkh_alloc(l.ctx, "data", (size_t)cir->group_size[GROUP_DATA] * n, 0, data.out()));
-    std::vector<uint32_t> out_global(cir->global_size[GLOBAL_OUT]);
-    const double t0 = now_s();
-    if (seg.host_code || seg.host_data) {
-        ZKH_REQUIRE(seg.host_code && seg.host_data && seg.out_global, "session: a segment with host traces needs host_code, host_data and out_global");
-        ZKH_TRY(zkh_write(l.ctx, code, seg.host_code, 0, code->len));
-        ZKH_TRY(zkh_upload_data_trace(l.ctx, cir, seg.po2, ZKH_ZK_CYCLES, data, seg.host_data, 0));     // without what is derived below
-        // what the library derives belongs to the data group: filled before it is committed, callback or not
-        ZKH_TRY(zkh_derive_all(l.ctx, cir, seg.po2, ZKH_ZK_CYCLES, code, data));
-        // a caller's raw words >= P (and the derives' copies of them) end here: the seal takes reduced words
-        ZKH_TRY(zkh_reduce_elem(l.ctx, code));
-        ZKH_TRY(zkh_reduce_elem(l.ctx, data));
-        out_global.assign(seg.out_global, seg.out_global + out_global.size());
-        *witgen_s = now_s() - t0;
-        zkh_seal_job* job = nullptr;
-        std::vector<uint32_t> mix(cir->global_size[GLOBAL_MIX] ? cir->global_size[GLOBAL_MIX] : 1);
-        ZKH_TRY(zkh_prove_begin(l.prover, seg.po2, code, data, out_global.data(), &job, mix.data()));
-        Tmp accum;
-        const char* err = zkh_alloc(l.ctx, "accum", (size_t)cir->group_size[GROUP_ACCUM] * n, 0, accum.out());
-        if (!err) {
-            if (s->accumulate) err = s->accumulate(s->accumulate_user, l.ctx, cir, seg.po2, data, mix.data(), accum);
-            else if (cir->kind >= 1 && cir->kind <= 3) err = zkh_syn_accum(l.ctx, cir, seg.po2, ZKH_ZK_CYCLES, noise, data, mix.data(), accum);
-            else if (zkh_circuit_has_arguments(cir)) err = zkh_accumulate(l.ctx, cir, seg.po2, ZKH_ZK_CYCLES, noise, code, data, mix.data(), accum);
-            else err = make_err("session: circuit kind %u has no built-in accum witness generator, no arguments and no accumulate callback was set", cir->kind);
-        }
-        if (err) { zkh_prove_abort(job); return err; }
-        return zkh_prove_finish(job, accum, seal, words);
+// control root of the leaf circuit per segment size (po2 -> root): filled through leaf_control_root (lane 0's GPU for the built-in
+// circuits) on ONE thread, read without a lock once threads run
+struct ControlRoots {
+    std::vector<std::pair<uint32_t, claims::Digest>> roots;
+    const uint32_t* find(uint32_t po2) const {
+        for (const auto& r : roots) if (r.first == po2) return r.second.data();
+        return nullptr;
     }
+    const char* add(zkh_session* s, const zkh_segment& seg) {          // a size already known costs nothing
+        if (find(seg.po2)) return nullptr;
+        claims::Digest cr;
+        ZKH_TRY(leaf_control_root(s, seg, cr.data()));
+        roots.emplace_back(seg.po2, cr);
+        return nullptr;
+    }
+};
+
+// ---- one segment on one lane: the caller's traces through prove_begin / accumulate / prove_finish, or a built-in witness
+// generator through zkh_prove_segment.  seal_one allocates what both need. ----
+struct SegmentTraces { NoiseKey nk; Tmp code, data; std::vector<uint32_t> out_global; double t0 = 0; };
+struct Prepared { const uint32_t* records = nullptr; const uint32_t* ram = nullptr; };   // a producer's preflight output in pinned memory (witness source 1)
+struct SealCost { double witgen_s = 0, preflight_cpu_s = 0, trace_bytes = 0; };
+
+static const char* seal_host_traces(zkh_session* s, Lane& l, const zkh_segment& seg, SegmentTraces& t, uint32_t** seal, size_t* words, SealCost* cost) {
+    const zkh_circuit* cir = l.circuit;
+    ZKH_REQUIRE(seg.host_code && seg.host_data && seg.out_global, "session: a segment with host traces needs host_code, host_data and out_global");
+    ZKH_TRY(zkh_write(l.ctx, t.code, seg.host_code, 0, t.code->len));
+    ZKH_TRY(zkh_upload_data_trace(l.ctx, cir, seg.po2, ZKH_ZK_CYCLES, t.data, seg.host_data, 0));     // without what is derived below
+    // what the library derives belongs to the data group: filled before it is committed, callback or not
+    ZKH_TRY(zkh_derive_all(l.ctx, cir, seg.po2, ZKH_ZK_CYCLES, t.code, t.data));
+    // a caller's raw words >= P (and the derives' copies of them) end here: the seal takes reduced words
+    ZKH_TRY(zkh_reduce_elem(l.ctx, t.code));
+    ZKH_TRY(zkh_reduce_elem(l.ctx, t.data));
+    t.out_global.assign(seg.out_global, seg.out_global + t.out_global.size());
+    cost->witgen_s = now_s() - t.t0;
+    zkh_seal_job* job = nullptr;
+    std::vector<uint32_t> mix(cir->global_size[GLOBAL_MIX] ? cir->global_size[GLOBAL_MIX] : 1);
+    ZKH_TRY(zkh_prove_begin(l.prover, seg.po2, t.code, t.data, t.out_global.data(), &job, mix.data()));
+    Tmp accum;
+    const char* err = zkh_alloc(l.ctx, "accum", (size_t)cir->group_size[GROUP_ACCUM] << seg.po2, 0, accum.out());
+    if (!err) {
+        if (s->accumulate) err = s->accumulate(s->accumulate_user, l.ctx, cir, seg.po2, t.data, mix.data(), accum);
+        else if (cir->kind >= 1 && cir->kind <= 3) err = zkh_syn_accum(l.ctx, cir, seg.po2, ZKH_ZK_CYCLES, t.nk.k, t.data, mix.data(), accum);
+        else if (zkh_circuit_has_arguments(cir)) err = zkh_accumulate(l.ctx, cir, seg.po2, ZKH_ZK_CYCLES, t.nk.k, t.code, t.data, mix.data(), accum);
+        else err = make_err("session: circuit kind %u has no built-in accum witness generator, no arguments and no accumulate callback was set", cir->kind);
+    }
+    if (err) { zkh_prove_abort(job); return err; }
+    return zkh_prove_finish(job, accum, seal, words);
+}
+
+// pre: this segment's preflight output (witness source 1), or empty: run the preflight here (a retry)
+static const char* seal_generated(zkh_session* s, Lane& l, const zkh_segment& seg, const Prepared& pre, SegmentTraces& t, uint32_t** seal, size_t* words,
+                                  SealCost* cost) {
+    const zkh_circuit* cir = l.circuit;
     ZKH_REQUIRE(cir->kind >= 1 && cir->kind <= 3, "session: circuit kind %u has no built-in witness generator: supply host traces", cir->kind);
     // The code (control) group of a built-in circuit is a function of (circuit, po2) alone: commit it once per lane and size and
     // keep the committed form in HBM (seals are byte-identical to the recomputing prover's).  Upstream's
     // SegmentProver re-commits it per segment; zkh_session_set_resident_code(s, 0) does the same.
     if (s->resident_code && cir->kind <= 2) {
         if (std::find(l.resident_po2.begin(), l.resident_po2.end(), seg.po2) == l.resident_po2.end()) {
-            ZKH_TRY(zkh_syn_code(l.ctx, cir, seg.po2, ZKH_ZK_CYCLES, code));
-            ZKH_TRY(zkh_prover_cache_code(l.prover, seg.po2, code));
+            ZKH_TRY(zkh_syn_code(l.ctx, cir, seg.po2, ZKH_ZK_CYCLES, t.code));
+            ZKH_TRY(zkh_prover_cache_code(l.prover, seg.po2, t.code));
             l.resident_po2.push_back(seg.po2);
         }
-        code.out();                                                  // the trace itself is not needed again
+        t.code.out();                                                // the trace itself is not needed again
     }
-    zkh_buf* code_arg = code ? (zkh_buf*)code : nullptr;
+    zkh_buf* code_arg = t.code ? (zkh_buf*)t.code : nullptr;
+    const uint32_t* noise = t.nk.k;
     if (s->witness_source == 1 && cir->kind == 1) {
         // trace-driven: the compact per-cycle records (16 bytes per cycle) go up from pinned memory, the row fill expands them
-        const size_t A = n - ZKH_ZK_CYCLES;
+        const size_t A = ((size_t)1 << seg.po2) - ZKH_ZK_CYCLES;
         std::vector<uint32_t> inline_records, inline_ram;
-        if (!records) {                                               // no producer ran ahead for this one (a retry): preflight here
+        if (!pre.records) {                                           // no producer ran ahead for this one (a retry): preflight here
             inline_records.resize(4 * A); inline_ram.resize(zkh_syn_preflight_ram_words());
             double cpu = 0;
             ZKH_TRY(zkh_syn_preflight(seg.seed, seg.po2, ZKH_ZK_CYCLES, inline_records.data(), inline_ram.data(), &cpu));
-            if (preflight_cpu_s) *preflight_cpu_s += cpu;
+            cost->preflight_cpu_s += cpu;
         }
         Tmp recs;
         ZKH_TRY(zkh_alloc(l.ctx, "records", 4 * A, 0, recs.out()));
-        if (records) ZKH_TRY(zkh_write_async(l.ctx, recs, records, 0, 4 * A));
+        if (pre.records) ZKH_TRY(zkh_write_async(l.ctx, recs, pre.records, 0, 4 * A));
         else ZKH_TRY(zkh_write(l.ctx, recs, inline_records.data(), 0, 4 * A));
-        if (trace_bytes) *trace_bytes += 16.0 * A + 4.0 * zkh_syn_preflight_ram_words() + 4.0 * out_global.size();
-        ZKH_TRY(zkh_syn_witgen_trace(l.ctx, cir, seg.po2, ZKH_ZK_CYCLES, noise, recs, records ? ram : inline_ram.data(), code_arg, data, out_global.data()));
+        cost->trace_bytes += 16.0 * A + 4.0 * zkh_syn_preflight_ram_words() + 4.0 * t.out_global.size();
+        ZKH_TRY(zkh_syn_witgen_trace(l.ctx, cir, seg.po2, ZKH_ZK_CYCLES, noise, recs, pre.records ? pre.ram : inline_ram.data(), code_arg, t.data, t.out_global.data()));
     } else {
-        ZKH_TRY(zkh_syn_witgen(l.ctx, cir, seg.po2, ZKH_ZK_CYCLES, seg.seed, noise, seg.n_pub ? seg.pub : nullptr, code_arg, data, out_global.data()));
+        ZKH_TRY(zkh_syn_witgen(l.ctx, cir, seg.po2, ZKH_ZK_CYCLES, seg.seed, noise, seg.n_pub ? seg.pub : nullptr, code_arg, t.data, t.out_global.data()));
     }
-    *witgen_s = now_s() - t0;
-    return zkh_prove_segment(l.prover, seg.po2, ZKH_ZK_CYCLES, noise, code_arg, data, out_global.data(), seal, words);
+    cost->witgen_s = now_s() - t.t0;
+    return zkh_prove_segment(l.prover, seg.po2, ZKH_ZK_CYCLES, noise, code_arg, t.data, t.out_global.data(), seal, words);
 }
 
-extern "C" const char* zkh_session_prove(zkh_session* s, const zkh_segment* segs, size_t n, int join_tree, size_t join_po2, const uint32_t* join_noise_key,
-                                         zkh_prove_info* info) {
-    ZKH_REQUIRE(s && segs && n && info, "session_prove: bad argument");
-    ZKH_REQUIRE(join_tree != 1 || !s->join_desc.empty(), "session_prove: the session was created without a join circuit");
-    ZKH_REQUIRE(join_tree != 2 || !s->rec_kinds.empty(), "session_prove: join_tree 2 needs zkh_session_set_recursion");
-    memset(info, 0, sizeof *info);
-    info->n_segments = n;
-    info->seals = (uint32_t**)calloc(n, sizeof(uint32_t*));
-    info->seal_words = (size_t*)calloc(n, sizeof(size_t));
-    if (!info->seals || !info->seal_words) {
-        free(info->seals); free(info->seal_words);
-        memset(info, 0, sizeof *info);
-        return make_err("session_prove: out of host memory for %zu receipts", n);
-    }
-    const bool fold = join_tree == 2;
-    if (join_tree == 1 && !s->assum_po2.empty()) {
-        zkh_prove_info_free(info);
-        return make_err("session_prove: the session has assumption receipts: they are united and resolved by the RECURSION programs (join_tree 2), the P2-JOIN tree has no such node");
-    }
-    const bool streamed = fold && s->streamed_fold;
-    info->streamed = streamed;
-    constexpr size_t NONE = (size_t)-1;
-    // ---- chained session: the executor's pass.  Every segment's pre-state is fixed BEFORE any segment is proven (one launch over
-    // all segments), so the provers stay independent; the pre-state becomes the segment's public input ----
+static const char* seal_one(zkh_session* s, Lane& l, const zkh_segment& seg, const Prepared& pre, uint32_t** seal, size_t* words, SealCost* cost) {
+    const zkh_circuit* cir = l.circuit;
+    const size_t n = (size_t)1 << seg.po2;
+    SegmentTraces t;
+    ZKH_TRY(resolve_noise_key(seg.noise_key, &t.nk));     // this segment's blinding key: the caller's, or (all-zero) 256 fresh bits from the OS
+    ZKH_TRY(zkh_alloc(l.ctx, "code", (size_t)cir->group_size[GROUP_CODE] * n, 0, t.code.out()));
+    ZKH_TRY(zkh_alloc(l.ctx, "data", (size_t)cir->group_size[GROUP_DATA] * n, 0, t.data.out()));
+    t.out_global.resize(cir->global_size[GLOBAL_OUT]);
+    t.t0 = now_s();
+    if (seg.host_code || seg.host_data) return seal_host_traces(s, l, seg, t, seal, words, cost);
+    return seal_generated(s, l, seg, pre, t, seal, words, cost);
+}
+
+namespace {
+
+// Fault injection (tests of the retry path): ZKH_FAULT_SEGMENT=<i> fails the FIRST attempt at segment i, ZKH_FAULT_SEGMENT_ALWAYS=<i>
+// every attempt.  Armed only by a value that parses STRICTLY as a decimal index (an empty or stray variable arms nothing: atol("")
+// was 0 = segment 0) and only together with ZKH_TEST_HOOKS=1, which no deployment sets.
+long fault_index(const char* name) {
+    const char* v = getenv(name);
+    const char* armed = getenv("ZKH_TEST_HOOKS");
+    if (!v || !*v || !armed || strcmp(armed, "1") != 0) return -1;
+    char* end = nullptr;
+    const long k = strtol(v, &end, 10);
+    return (end && *end == 0 && k >= 0) ? k : -1;
+}
+
+const char* node_name(const sched::PlanNode& nd) {
+    const uint32_t k = nd.kind;
+    return k == 1 ? "join" : k == 3 ? "join3" : k == 2 ? "lift2" : k == 4 ? "union (of two assumption receipts)" : k == 5 ? "resolve (the session's root against its assumptions)"
+           : nd.family == 1 ? "lift (of an assumption receipt)" : "lift";
+}
+
+// frees the caller's zkh_prove_info on every exit of zkh_session_prove but the successful one
+struct InfoGuard {
+    zkh_prove_info* info;
+    ~InfoGuard() { if (info) zkh_prove_info_free(info); }
+    void keep() { info = nullptr; }
+};
+
+struct NodeData { SealPtr seal; size_t words = 0; NodeClaim claim; };     // what a proven node leaves for its parent
+struct Ready { size_t seg; uint32_t* slot; };
+struct LaneQ { std::deque<Ready> ready; std::vector<uint32_t*> free_slots; size_t producers_active = 0; bool accepting = true; };
+struct Busy { double wit = 0, seal = 0, fold = 0; };                      // one worker's seconds, added to the run's sums when it leaves
+
+// One call of zkh_session_prove: the state its threads share, and its stages in the order the call takes them.
+// Lock discipline: every Scheduler method, every LaneQ and every sum below is touched with m held; GPU work runs with it released.
+struct ProveRun {
+    zkh_session* const s;
+    const zkh_segment* segs;             // the segments as proven (a chained session: with their public inputs)
+    const size_t n;
+    zkh_prove_info* const info;
+    const uint32_t* const join_noise_key;
+    const bool fold, streamed, use_pre;
     std::vector<zkh_segment> chained_segs;
     std::vector<uint32_t> pre_states;
-    if (s->chained) {
+    sched::FoldPlan fplan;
+    std::vector<NodeData> ndata;
+    ControlRoots leaf_roots;             // (the lifts' claims are computed against them)
+    ErrorSlot errs;
+    std::mutex m;
+    std::condition_variable cv;
+    std::optional<sched::Scheduler> sc;
+    long fault_seg = -1, fault_always = -1;
+    std::vector<LaneQ> laneq;
+    double t0 = 0, t_end = 0;
+    double wit_sum = 0, seal_sum = 0, fold_busy = 0, pre_cpu_sum = 0, trace_bytes_sum = 0;
+
+    ProveRun(zkh_session* s_, const zkh_segment* segs_, size_t n_, int join_tree, const uint32_t* key, zkh_prove_info* info_)
+        : s(s_), segs(segs_), n(n_), info(info_), join_noise_key(key), fold(join_tree == 2), streamed(fold && s_->streamed_fold),
+          use_pre(s_->witness_source == 1 && s_->lanes[0].circuit->kind == 1), laneq(s_->lanes.size()) {}
+
+    // ---- chained session: the executor's pass.  Every segment's pre-state is fixed BEFORE any segment is proven (one launch over
+    // all segments), so the provers stay independent; the pre-state becomes the segment's public input ----
+    const char* chain_public_inputs() {
+        if (!s->chained) return nullptr;
         std::vector<uint64_t> seeds(n);
         std::vector<uint32_t> po2s(n), contrib(n);
         for (size_t i = 0; i < n; i++) {
-            if (segs[i].host_code || segs[i].host_data) { zkh_prove_info_free(info); return make_err("session_prove: a chained session takes segments described by their seed"); }
+            ZKH_REQUIRE(!segs[i].host_code && !segs[i].host_data, "session_prove: a chained session takes segments described by their seed");
             seeds[i] = segs[i].seed; po2s[i] = segs[i].po2;
         }
-        if (const char* e = zkh_syn_chain_contributions(s->lanes[0].ctx, s->lanes[0].circuit, seeds.data(), po2s.data(), n, ZKH_ZK_CYCLES, contrib.data())) {
-            zkh_prove_info_free(info);
-            return e;
-        }
+        ZKH_TRY(zkh_syn_chain_contributions(s->lanes[0].ctx, s->lanes[0].circuit, seeds.data(), po2s.data(), n, ZKH_ZK_CYCLES, contrib.data()));
         // SYN-C: one public word per segment (the pre-state).  SYN-S: 19 — pre-state, the exit code pair (SystemSplit (2, 0) for
         // every segment but the last, Halted(0) (0, 0) for the last) and the 16 limbs of SHA-256(journal), zero except in the last
         // segment; the journal of a session is its final state word (canonical residue, 4 bytes little-endian).
@@ -722,6 +718,7 @@ extern "C" const char* zkh_session_prove(zkh_session* s, const zkh_segment* segs
         chained_segs.assign(segs, segs + n);
         for (size_t i = 0; i < n; i++) { chained_segs[i].pub = &pre_states[i * pw]; chained_segs[i].n_pub = pw; }
         segs = chained_segs.data();
+        return nullptr;
     }
 
     // ---- the fold plan (join_tree 2), fixed before anything runs: the bottom level turns segment receipts into recursion
@@ -729,14 +726,10 @@ extern "C" const char* zkh_session_prove(zkh_session* s, const zkh_segment* segs
     // fused), else every segment is lifted on its own and the first level above pairs the lifts — and every level above THAT takes
     // three nodes at a time (zeth_amd/recursion.py fold_plan: one join3 where the program set has it for their sizes, else
     // join(join(a, b), c), the same node either way), a remainder of two is a join, of one moves up unchanged.  A node's program
-    // follows from its children's sizes, so a missing program is reported here, not after the leaves are sealed. ----
-    // (the plan itself and the scheduling state machine: scheduler.h — plain C++, unit-tested without a GPU)
-
-    sched::FoldPlan fplan;
-    std::vector<sched::PlanNode>& plan = fplan.nodes;
-    struct NodeData { uint32_t* seal = nullptr; size_t words = 0; NodeClaim claim; };     // what a proven node leaves for its parent
-    std::vector<NodeData> ndata;
-    if (fold) {
+    // follows from its children's sizes, so a missing program is reported here, not after the leaves are sealed.
+    // (the plan itself and the scheduling state machine: scheduler.h — plain C++, unit-tested without a GPU) ----
+    const char* plan_fold() {
+        if (!fold) return nullptr;
         std::vector<uint32_t> seg_po2(n);
         for (size_t i = 0; i < n; i++) seg_po2[i] = segs[i].po2;
         const std::string perr = sched::build_fold_plan(
@@ -748,37 +741,12 @@ extern "C" const char* zkh_session_prove(zkh_session* s, const zkh_segment* segs
             },
             [&](uint32_t program) { uint32_t inf[8] = {0}; (void)zkh_rec_program_info(s->lanes[0].programs[program], nullptr, inf); return inf[0]; },
             &fplan, s->assum_po2);
-        if (!perr.empty()) { zkh_prove_info_free(info); return make_err("session_prove: %s", perr.c_str()); }
-        ndata.resize(plan.size());
-    }
-    const size_t n_bottom = fplan.n_bottom, root_node = fplan.root;
-    std::unique_ptr<zkh_circuit, void (*)(zkh_circuit*)> assum_circuit(nullptr, zkh_circuit_destroy);      // host-only: the assumption receipts' claims
-    if (fold && !s->assum_po2.empty()) {
-        zkh_circuit* ac = nullptr;
-        if (const char* e = zkh_circuit_load(nullptr, s->assum_desc.data(), s->assum_desc.size(), &ac)) { zkh_prove_info_free(info); return e; }
-        assum_circuit.reset(ac);
-    }
-    // control root of the leaf circuit per segment size (the lifts' claims are computed against it): before any thread starts
-    std::vector<std::pair<uint32_t, std::vector<uint32_t>>> fold_leaf_roots;
-    auto leaf_root_of = [&](uint32_t po2) -> const uint32_t* {
-        for (auto& r : fold_leaf_roots) if (r.first == po2) return r.second.data();
+        ZKH_REQUIRE(perr.empty(), "session_prove: %s", perr.c_str());
+        ndata.resize(fplan.nodes.size());
+        // control root of the leaf circuit per segment size: before any thread starts
+        for (size_t i = 0; i < n; i++) ZKH_TRY(leaf_roots.add(s, segs[i]));
         return nullptr;
-    };
-    if (fold)
-        for (size_t i = 0; i < n; i++)
-            if (!leaf_root_of(segs[i].po2)) {
-                std::vector<uint32_t> cr(8);
-                if (const char* e = leaf_control_root(s, segs[i], cr.data())) { zkh_prove_info_free(info); return e; }
-                fold_leaf_roots.emplace_back(segs[i].po2, cr);
-            }
-    auto path_of = [&](uint32_t program, std::vector<uint32_t>& out) {      // per level: the direction bit as an element, the sibling
-        size_t idx = program;
-        for (size_t l = 0; l < REC_DEPTH; l++) {
-            out.push_back(fp_encode((uint32_t)(idx & 1)).v);
-            out.insert(out.end(), s->allowed[l][idx ^ 1].begin(), s->allowed[l][idx ^ 1].end());
-            idx >>= 1;
-        }
-    };
+    }
 
     // ---- one scheduler for the whole call.  Sealing lanes pull segments from one index (round-robin with work stealing over all
     // lanes of all devices; a segment whose seal fails is handed to ANOTHER lane before the session gives up: ZKH_SEGMENT_RETRIES,
@@ -786,123 +754,27 @@ extern "C" const char* zkh_session_prove(zkh_session* s, const zkh_segment* segs
     // free — the fold-only lanes while segments are still being sealed (the witness schedule of a lift / join is a 300-level
     // latency chain that fills the gaps the VALU-bound seals leave), every lane once the segments are done: upstream's
     // join-as-you-go.  zkh_session_set_streamed_fold(s, 0) holds the fold back until the last segment is sealed (two phases). ----
-    ErrorSlot errs;
-    std::mutex m;
-    std::condition_variable cv;
-    const char* renv = getenv("ZKH_SEGMENT_RETRIES");
-    sched::Scheduler sc(n, s->lanes.size(), fold ? &fplan : nullptr, streamed, renv ? atoi(renv) : 1);
-    // Fault injection (tests of the retry path): ZKH_FAULT_SEGMENT=<i> fails the FIRST attempt at segment i, ZKH_FAULT_SEGMENT_ALWAYS=<i>
-    // every attempt.  Armed only by a value that parses STRICTLY as a decimal index (an empty or stray variable arms nothing: atol("")
-    // was 0 = segment 0) and only together with ZKH_TEST_HOOKS=1, which no deployment sets.
-    auto fault_index = [](const char* name) -> long {
-        const char* v = getenv(name);
-        const char* armed = getenv("ZKH_TEST_HOOKS");
-        if (!v || !*v || !armed || strcmp(armed, "1") != 0) return -1;
-        char* end = nullptr;
-        const long k = strtol(v, &end, 10);
-        return (end && *end == 0 && k >= 0) ? k : -1;
-    };
-    const long fault_seg = fault_index("ZKH_FAULT_SEGMENT"), fault_always = fault_index("ZKH_FAULT_SEGMENT_ALWAYS");
-    const double t0 = now_s();
+    void start_scheduler() {
+        const char* renv = getenv("ZKH_SEGMENT_RETRIES");
+        sc.emplace(n, s->lanes.size(), fold ? &fplan : nullptr, streamed, renv ? atoi(renv) : 1);
+        fault_seg = fault_index("ZKH_FAULT_SEGMENT"); fault_always = fault_index("ZKH_FAULT_SEGMENT_ALWAYS");
+        t0 = now_s();
+    }
+    bool finished() { return errs.any() || sc->finished(); }                                  // call with m held
 
-    auto finished = [&] { return errs.any() || sc.finished(); };                              // call with m held
-    auto run_node = [&](Lane* l, size_t id, std::vector<uint32_t>& in) -> const char* {
-        const sched::PlanNode& nd = plan[id];
-        NodeData& me = ndata[id];
-        in.clear();
-        const std::vector<uint32_t>& A = s->allowed.back()[0];
-        if (nd.kind == 1 || nd.kind == 3) {
-            // per child: seal, membership path, then the opening of its claim' (core, pre, post) — all checked in-circuit
-            const size_t ch3[3] = {nd.a, nd.b, nd.kind == 3 ? nd.c : NONE};
-            for (size_t ch : ch3) {
-                if (ch == NONE) continue;
-                in.insert(in.end(), ndata[ch].seal, ndata[ch].seal + ndata[ch].words);
-                path_of(plan[ch].program, in);
-                in.insert(in.end(), ndata[ch].claim.core, ndata[ch].claim.core + 8);
-                in.push_back(ndata[ch].claim.pre); in.push_back(ndata[ch].claim.post);
-            }
-            ZKH_TRY(parent_claim(ndata[nd.a].claim, ndata[nd.b].claim, &me.claim));
-            if (nd.kind == 3) { const NodeClaim ab = me.claim; ZKH_TRY(parent_claim(ab, ndata[nd.c].claim, &me.claim)); }     // join3 = join(join(a, b), c)
-        } else if (nd.kind == 4) {
-            // union: per child its seal and membership path, then the swap bit — (lo, hi) = the two claim' sorted by canonical words
-            uint32_t ca[8], cb[8];
-            ZKH_TRY(wrap_claim(ndata[nd.a].claim, ca)); ZKH_TRY(wrap_claim(ndata[nd.b].claim, cb));
-            bool swap = false;
-            for (int i = 0; i < 8; i++) {
-                const uint32_t x = fp_decode(Fp::raw(ca[i])), y = fp_decode(Fp::raw(cb[i]));
-                if (x != y) { swap = y < x; break; }
-            }
-            for (size_t ch : {nd.a, nd.b}) {
-                in.insert(in.end(), ndata[ch].seal, ndata[ch].seal + ndata[ch].words);
-                path_of(plan[ch].program, in);
-            }
-            in.push_back(fp_encode(swap ? 1u : 0u).v);
-            ZKH_TRY(hash_pair_host(swap ? cb : ca, swap ? ca : cb, me.claim.core));
-            me.claim.pre = me.claim.post = 0;
-        } else if (nd.kind == 5) {
-            // resolve: the conditional receipt (the session's root: seal, path, the opening of its claim'), then the assumption receipt
-            const NodeData& cond = ndata[nd.a];
-            const NodeData& assum = ndata[nd.b];
-            in.insert(in.end(), cond.seal, cond.seal + cond.words);
-            path_of(plan[nd.a].program, in);
-            in.insert(in.end(), cond.claim.core, cond.claim.core + 8);
-            in.push_back(cond.claim.pre); in.push_back(cond.claim.post);
-            in.insert(in.end(), assum.seal, assum.seal + assum.words);
-            path_of(plan[nd.b].program, in);
-            uint32_t cc[8], ca[8];
-            ZKH_TRY(wrap_claim(cond.claim, cc)); ZKH_TRY(wrap_claim(assum.claim, ca));
-            ZKH_TRY(hash_pair_host(cc, ca, me.claim.core));
-            me.claim.pre = cond.claim.pre; me.claim.post = cond.claim.post;
-        } else if (nd.kind == 0 && nd.family == 1) {
-            // the lift of an assumption receipt: its seal, then A; claim = its receipt claim, no state
-            const std::vector<uint32_t>& seal = s->assum_seals[nd.a];
-            in.assign(seal.begin(), seal.end());
-            ZKH_TRY(zkh_receipt_claim(assum_circuit.get(), seal.data(), seal.size(), s->assum_roots[nd.a].data(), nullptr, nullptr, me.claim.core));
-            me.claim.pre = me.claim.post = 0;
-            in.insert(in.end(), A.begin(), A.end());
-        } else {
-            const zkh_circuit* lc = s->lanes[0].circuit;
-            in.assign(info->seals[nd.a], info->seals[nd.a] + info->seal_words[nd.a]);
-            NodeClaim ca;
-            ZKH_TRY(leaf_claim(lc, info->seals[nd.a], info->seal_words[nd.a], leaf_root_of(segs[nd.a].po2), &ca));
-            if (nd.kind == 2) {
-                in.insert(in.end(), info->seals[nd.b], info->seals[nd.b] + info->seal_words[nd.b]);
-                NodeClaim cb;
-                ZKH_TRY(leaf_claim(lc, info->seals[nd.b], info->seal_words[nd.b], leaf_root_of(segs[nd.b].po2), &cb));
-                ZKH_TRY(parent_claim(ca, cb, &me.claim));
-            } else {
-                me.claim = ca;
-            }
-            in.insert(in.end(), A.begin(), A.end());
-        }
-        ZKH_TRY(zkh_rec_prove(l->programs[nd.program], in.data(), in.size(), join_noise_key, nullptr, &me.seal, &me.words));    // NULL: a fresh OS key per proof
-        if (nd.kind == 1 || nd.kind >= 3) {                    // children are not kept: the verifier needs the root only
-            for (size_t ch : {nd.a, nd.b, nd.kind == 3 ? nd.c : NONE})
-                if (ch != NONE) { zkh_free_seal(ndata[ch].seal); ndata[ch].seal = nullptr; }
-        }
-        return nullptr;
-    };
-    double wit_sum = 0, seal_sum = 0, fold_busy = 0, pre_cpu_sum = 0, trace_bytes_sum = 0;
     // ---- witness source 1: the sequential host preflight runs AHEAD of the seals.  Every sealing lane has its own producer threads
     // (zkh_session_set_witness_source: default 2 — one preflight of a po2-20 segment is ~70 ms of one core, a lane seals one every
     // ~70 ms) and a pool of pinned record slots (producers + 1): a producer takes the next segment index, replays its cycles into a
     // free slot, and queues (segment, slot) for its lane, which uploads the 16 bytes per cycle and row-fills on the GPU.  The
     // producers are what pull the work index; a lane seals what its producers hand it. ----
-    const bool use_pre = s->witness_source == 1 && s->lanes[0].circuit->kind == 1;
-    struct Ready { size_t seg; uint32_t* slot; };
-    struct LaneQ { std::deque<Ready> ready; std::vector<uint32_t*> free_slots; size_t producers_active = 0; bool accepting = true; };
-    std::vector<LaneQ> laneq(s->lanes.size());
-    const size_t ram_words = zkh_syn_preflight_ram_words();
-    if (use_pre) {
+    const char* prepare_preflight() {
+        if (!use_pre) return nullptr;
         uint32_t max_po2 = 0;
         for (size_t i = 0; i < n; i++) {
-            if (segs[i].host_code || segs[i].host_data || segs[i].n_pub) {       // (info's arrays are allocated: every early return frees them)
-                zkh_prove_info_free(info);
-                return make_err("session_prove: witness source 1 takes segments described by their seed only");
-            }
+            ZKH_REQUIRE(!segs[i].host_code && !segs[i].host_data && !segs[i].n_pub, "session_prove: witness source 1 takes segments described by their seed only");
             max_po2 = std::max(max_po2, segs[i].po2);
         }
-        const size_t slot_words = ((size_t)4 << max_po2) + ram_words;          // records, then the RAM image
+        const size_t slot_words = ((size_t)4 << max_po2) + zkh_syn_preflight_ram_words();          // records, then the RAM image
         for (size_t k = 0; k < s->lanes.size(); k++) {
             Lane& l = s->lanes[k];
             if (l.record_slot_words < slot_words) {                             // (main thread: nobody else touches the contexts yet)
@@ -911,23 +783,24 @@ extern "C" const char* zkh_session_prove(zkh_session* s, const zkh_segment* segs
             }
             while (l.record_slots.size() < s->producers_per_lane + 1) {
                 uint32_t* p = nullptr;
-                if (const char* e = zkh_host_alloc(l.ctx, slot_words, &p)) { zkh_prove_info_free(info); return e; }
+                ZKH_TRY(zkh_host_alloc(l.ctx, slot_words, &p));
                 l.record_slots.push_back(p);
             }
             l.record_slot_words = slot_words;
             laneq[k].free_slots = l.record_slots;
             laneq[k].producers_active = s->producers_per_lane;
         }
+        return nullptr;
     }
-    auto producer = [&](size_t lane_idx) {
+    void producer(size_t lane_idx) {
         LaneQ& q = laneq[lane_idx];
         const Lane& l = s->lanes[lane_idx];
         { const char* e = zkh_bind_thread_to_device(l.device, 0, 1, nullptr, nullptr); if (e) zkh_free_error(e); }      // (ZKH_AFFINITY=off: a no-op)
         std::unique_lock<std::mutex> lk(m);
         for (;;) {
-            cv.wait(lk, [&] { return errs.any() || !q.accepting || !sc.indices_left() || !q.free_slots.empty(); });
-            if (errs.any() || !q.accepting || !sc.indices_left()) break;
-            const size_t i = sc.claim_index();
+            cv.wait(lk, [&] { return errs.any() || !q.accepting || !sc->indices_left() || !q.free_slots.empty(); });
+            if (errs.any() || !q.accepting || !sc->indices_left()) break;
+            const size_t i = sc->claim_index();
             uint32_t* slot = q.free_slots.back();
             q.free_slots.pop_back();
             lk.unlock();
@@ -937,333 +810,342 @@ extern "C" const char* zkh_session_prove(zkh_session* s, const zkh_segment* segs
             pre_cpu_sum += cpu;
             if (err) { errs.set(err, "preflight"); q.free_slots.push_back(slot); break; }
             if (q.accepting) q.ready.push_back(Ready{i, slot});
-            else { q.free_slots.push_back(slot); sc.requeue(i); }     // the lane stopped sealing meanwhile: anyone may take it
+            else { q.free_slots.push_back(slot); sc->requeue(i); }     // the lane stopped sealing meanwhile: anyone may take it
             cv.notify_all();
         }
         q.producers_active--;
         lk.unlock();
         cv.notify_all();
-    };
-    auto worker = [&](Lane* l, bool can_seal) {
+    }
+
+    // A fold node: look up the children, take the witness words and the node's claim from claims.h, prove, release the children's seals
+    const char* run_node(Lane* l, size_t id, std::vector<uint32_t>& in) {
+        const sched::PlanNode& nd = fplan.nodes[id];
+        NodeData& me = ndata[id];
+        const size_t ids[3] = {nd.a, nd.b, nd.c}, n_ch = nd.kind == 0 ? 1 : nd.kind == 3 ? 3 : 2;
+        const bool of_nodes = nd.kind == 1 || nd.kind >= 3;                // else a lift / lift2: the children are seals of another circuit
+        claims::Child ch[3];
+        for (size_t k = 0; k < n_ch; k++) {
+            const size_t c = ids[k];
+            if (of_nodes) {
+                ch[k].seal = ndata[c].seal.get(); ch[k].words = ndata[c].words; ch[k].program = fplan.nodes[c].program; ch[k].claim = ndata[c].claim;
+            } else if (nd.family == 1) {                                   // an assumption receipt: its receipt claim, no state
+                ch[k].seal = s->assum_seals[c].data(); ch[k].words = s->assum_seals[c].size();
+                memcpy(ch[k].claim.core, &s->assum_claims[8 * c], 32);
+            } else {
+                ch[k].seal = info->seals[c]; ch[k].words = info->seal_words[c];
+                ZKH_TRY(leaf_claim(s->lanes[0].circuit, info->seals[c], info->seal_words[c], leaf_roots.find(segs[c].po2), &ch[k].claim));
+            }
+        }
+        ZKH_TRY(claim_err(claims::node_witness(HASH_PAIR, nd.kind, ch, n_ch, s->allowed, in, &me.claim)));
+        uint32_t* seal = nullptr;
+        const char* err = zkh_rec_prove(l->programs[nd.program], in.data(), in.size(), join_noise_key, nullptr, &seal, &me.words);    // NULL: a fresh OS key per proof
+        me.seal.reset(seal);
+        if (!err && of_nodes) for (size_t k = 0; k < n_ch; k++) ndata[ids[k]].seal.reset();     // children are not kept: the verifier needs the root only
+        return err;
+    }
+
+    // One segment on this lane.  m is held on entry and on return and released around the GPU work; false: the run has failed.
+    bool seal_step(Lane* l, size_t lane_idx, size_t seg, uint32_t* slot, bool* can_seal, Busy* busy, std::unique_lock<std::mutex>& lk) {
+        lk.unlock();
+        SealCost cost;
+        const double ts = now_s();
+        const char* err = nullptr;
+        if ((long)seg == fault_always || ((long)seg == fault_seg && sc->attempts(seg) == 0)) err = make_err("injected fault (ZKH_FAULT_SEGMENT)");
+        else err = seal_one(s, *l, segs[seg], Prepared{slot, slot ? slot + ((size_t)4 << segs[seg].po2) : nullptr}, &info->seals[seg], &info->seal_words[seg], &cost);
+        const double te = now_s();
+        lk.lock();
+        pre_cpu_sum += cost.preflight_cpu_s; trace_bytes_sum += cost.trace_bytes;
+        if (slot) {
+            // a successful seal ended with a host sync, so the upload from this pinned slot is done; a FAILED one may have returned
+            // with the async H2D still in flight: drain the lane's stream before a producer may overwrite the slot
+            if (err) { lk.unlock(); if (const char* se = zkh_sync(l->ctx)) zkh_free_error(se); lk.lock(); }
+            laneq[lane_idx].free_slots.push_back(slot); cv.notify_all();
+        }
+        if (!err) {
+            busy->wit += cost.witgen_s; busy->seal += te - ts - cost.witgen_s;
+            sc->on_seal_done(seg, lane_idx, now_s());
+            cv.notify_all();
+            return true;
+        }
+        const sched::Scheduler::Failure f = sc->on_seal_failed(seg, lane_idx, now_s());      // hand it to another lane / device, or give up
+        if (f == sched::Scheduler::Failure::Fatal) {
+            char what[64];
+            snprintf(what, sizeof what, "segment %zu (after %d attempt(s))", seg, sc->attempts(seg));
+            errs.set(err, what);
+            cv.notify_all();
+            return false;
+        }
+        zkh_free_error(err);
+        zkh_free_seal(info->seals[seg]); info->seals[seg] = nullptr; info->seal_words[seg] = 0;
+        if (f == sched::Scheduler::Failure::RetryAndRetireLane) {        // two failures in a row: this lane stops taking segments
+            *can_seal = false;
+            if (use_pre) {                            // what its producers already prepared goes to the other lanes
+                LaneQ& q = laneq[lane_idx];
+                q.accepting = false;
+                for (auto& r : q.ready) { q.free_slots.push_back(r.slot); sc->requeue(r.seg); }
+                q.ready.clear();
+            }
+        }
+        cv.notify_all();
+        return true;
+    }
+    // One fold node on this lane, under the same lock contract
+    bool node_step(Lane* l, size_t id, std::vector<uint32_t>& in, Busy* busy, std::unique_lock<std::mutex>& lk) {
+        lk.unlock();
+        const double ts = now_s();
+        const char* err = run_node(l, id, in);
+        const double te = now_s();
+        lk.lock();
+        busy->fold += te - ts;
+        if (err) errs.set(err, node_name(fplan.nodes[id]));
+        else sc->on_node_done(id, now_s());
+        cv.notify_all();
+        return !err;
+    }
+    void worker(Lane* l, bool can_seal) {
         const size_t lane_idx = can_seal ? (size_t)(l - s->lanes.data()) : sched::NONE;
         { const char* e = zkh_bind_thread_to_device(l->device, 0, 1, nullptr, nullptr); if (e) zkh_free_error(e); }
         std::vector<uint32_t> in;
-        double wit = 0, seal_t = 0, fold_t = 0;
+        Busy busy;
         std::unique_lock<std::mutex> lk(m);
-        for (;;) {
-            if (finished()) break;
+        while (!finished()) {
             // 1) a segment (scheduler.h take_segment: retries first, then the next index — or, with the host-preflight pipeline, what
             //    this lane's producers have prepared)
-            size_t seg = NONE;
+            size_t seg = sched::NONE;
             uint32_t* slot = nullptr;
             if (can_seal) {
-                seg = sc.take_segment(lane_idx, now_s(), !use_pre).index;
-                if (seg == NONE && use_pre) {
+                seg = sc->take_segment(lane_idx, now_s(), !use_pre).index;
+                if (seg == sched::NONE && use_pre) {
                     LaneQ& q = laneq[lane_idx];
                     if (!q.ready.empty()) { seg = q.ready.front().seg; slot = q.ready.front().slot; q.ready.pop_front(); }
                 }
             }
-            if (seg != NONE) {
-                lk.unlock();
-                double w = 0, pcpu = 0, tbytes = 0;
-                const double ts = now_s();
-                const char* err = nullptr;
-                if ((long)seg == fault_always || ((long)seg == fault_seg && sc.attempts(seg) == 0)) err = make_err("injected fault (ZKH_FAULT_SEGMENT)");
-                else err = seal_one(s, *l, segs[seg], &info->seals[seg], &info->seal_words[seg], &w, slot, slot ? slot + ((size_t)4 << segs[seg].po2) : nullptr, &pcpu, &tbytes);
-                const double te = now_s();
-                lk.lock();
-                pre_cpu_sum += pcpu; trace_bytes_sum += tbytes;
-                if (slot) {
-                    // a successful seal ended with a host sync, so the upload from this pinned slot is done; a FAILED one may have returned
-                    // with the async H2D still in flight: drain the lane's stream before a producer may overwrite the slot
-                    if (err) { lk.unlock(); if (const char* se = zkh_sync(l->ctx)) zkh_free_error(se); lk.lock(); }
-                    laneq[lane_idx].free_slots.push_back(slot); cv.notify_all();
-                }
-                if (err) {
-                    const sched::Scheduler::Failure f = sc.on_seal_failed(seg, lane_idx, now_s());      // hand it to another lane / device, or give up
-                    if (f != sched::Scheduler::Failure::Fatal) {
-                        zkh_free_error(err);
-                        zkh_free_seal(info->seals[seg]); info->seals[seg] = nullptr; info->seal_words[seg] = 0;
-                        if (f == sched::Scheduler::Failure::RetryAndRetireLane) {        // two failures in a row: this lane stops taking segments
-                            can_seal = false;
-                            if (use_pre) {                            // what its producers already prepared goes to the other lanes
-                                LaneQ& q = laneq[lane_idx];
-                                q.accepting = false;
-                                for (auto& r : q.ready) { q.free_slots.push_back(r.slot); sc.requeue(r.seg); }
-                                q.ready.clear();
-                            }
-                        }
-                        cv.notify_all();
-                        continue;
-                    }
-                    char what[64];
-                    snprintf(what, sizeof what, "segment %zu (after %d attempt(s))", seg, sc.attempts(seg));
-                    errs.set(err, what);
-                    cv.notify_all();
-                    break;
-                }
-                wit += w; seal_t += te - ts - w;
-                sc.on_seal_done(seg, lane_idx, now_s());
-                cv.notify_all();
+            if (seg != sched::NONE) {
+                if (!seal_step(l, lane_idx, seg, slot, &can_seal, &busy, lk)) break;
                 continue;
             }
             // 2) a fold node (streamed: any time; two phases: once every segment is sealed)
-            const sched::Scheduler::Work nw = sc.take_node();
+            const sched::Scheduler::Work nw = sc->take_node();
             if (nw.kind == sched::Scheduler::Kind::Node) {
-                const size_t id = nw.index;
-                lk.unlock();
-                const double ts = now_s();
-                const char* err = run_node(l, id, in);
-                const double te = now_s();
-                lk.lock();
-                fold_t += te - ts;
-                if (err) {
-                    const uint32_t k = plan[id].kind;
-                    errs.set(err, k == 1 ? "join" : k == 3 ? "join3" : k == 2 ? "lift2" : k == 4 ? "union (of two assumption receipts)" : k == 5 ? "resolve (the session's root against its assumptions)"
-                             : plan[id].family == 1 ? "lift (of an assumption receipt)" : "lift");
-                    cv.notify_all();
-                    break;
-                }
-                sc.on_node_done(id, now_s());
-                cv.notify_all();
+                if (!node_step(l, nw.index, in, &busy, lk)) break;
                 continue;
             }
             // 3) nothing to do right now (a retry entry held back for another lane wakes us after 20 ms; producers, finished seals and
             //    finished fold nodes notify)
-            if (can_seal && sc.retries_waiting()) cv.wait_for(lk, std::chrono::milliseconds(20));
+            if (can_seal && sc->retries_waiting()) cv.wait_for(lk, std::chrono::milliseconds(20));
             else cv.wait(lk);
         }
-        sc.lane_leaves(can_seal);
-        wit_sum += wit; seal_sum += seal_t; fold_busy += fold_t;
+        sc->lane_leaves(can_seal);
+        wit_sum += busy.wit; seal_sum += busy.seal; fold_busy += busy.fold;
         lk.unlock();
         cv.notify_all();
         (void)zkh_sync(l->ctx);
-    };
-    {
-        std::vector<std::thread> th;
-        for (auto& lane : s->lanes) th.emplace_back(worker, &lane, true);
-        if (fold) for (auto& lane : s->fold_lanes) th.emplace_back(worker, &lane, false);
-        if (use_pre) for (size_t k = 0; k < s->lanes.size(); k++) for (size_t p = 0; p < s->producers_per_lane; p++) th.emplace_back(producer, k);
-        for (auto& t : th) t.join();
     }
-    const double t_end = now_s();
-    info->witgen_s_sum = wit_sum; info->seal_s_sum = seal_sum; info->fold_busy_s_sum = fold_busy; info->n_retries = sc.n_retries;
-    info->preflight_cpu_s_sum = pre_cpu_sum; info->trace_bytes = trace_bytes_sum;
-    info->leaves_s = (sc.t_leaves_done ? sc.t_leaves_done : t_end) - t0;
-    if (fold) {
+    // one worker per sealing lane, one per fold lane when folding, producers_per_lane producers per lane with witness source 1
+    void run_lanes() {
+        std::vector<std::thread> th;
+        for (auto& lane : s->lanes) th.emplace_back([this, l = &lane] { worker(l, true); });
+        if (fold) for (auto& lane : s->fold_lanes) th.emplace_back([this, l = &lane] { worker(l, false); });
+        if (use_pre) for (size_t k = 0; k < s->lanes.size(); k++) for (size_t p = 0; p < s->producers_per_lane; p++) th.emplace_back([this, k] { producer(k); });
+        for (auto& t : th) t.join();
+        t_end = now_s();
+    }
+
+    void write_statistics() {
+        info->witgen_s_sum = wit_sum; info->seal_s_sum = seal_sum; info->fold_busy_s_sum = fold_busy; info->n_retries = sc->n_retries;
+        info->preflight_cpu_s_sum = pre_cpu_sum; info->trace_bytes = trace_bytes_sum;
+        info->leaves_s = (sc->t_leaves_done ? sc->t_leaves_done : t_end) - t0;
+        if (!fold) return;
         // bottom level = lifts (or lift2 per pair); with the streamed fold these overlap the leaf phase: lift_s / join_s are what the
         // fold still took AFTER the last segment was sealed (bottom level, then joins); two phases: the two phases' durations
-        const double tb = std::max(sc.t_bottom_done ? sc.t_bottom_done : t_end, t0 + info->leaves_s);
-        info->n_lifts = n_bottom + fplan.n_assumptions;          // the bottom level + a lift per assumption receipt
-        info->n_joins = plan.size() - info->n_lifts;             // joins / join3s, unions, the resolve
+        const double tb = std::max(sc->t_bottom_done ? sc->t_bottom_done : t_end, t0 + info->leaves_s);
+        info->n_lifts = fplan.n_bottom + fplan.n_assumptions;          // the bottom level + a lift per assumption receipt
+        info->n_joins = fplan.nodes.size() - info->n_lifts;            // joins / join3s, unions, the resolve
         info->lift_s = tb - (t0 + info->leaves_s);
         info->join_s = t_end - tb;
         info->fold_tail_s = t_end - (t0 + info->leaves_s);
-        if (!errs.any()) {
-            NodeData& r = ndata[root_node];
-            info->root_seal = r.seal; info->root_seal_words = r.words; info->root_program = plan[root_node].program;
-            memcpy(info->root_core, r.claim.core, 32); info->root_pre = r.claim.pre; info->root_post = r.claim.post;
-            r.seal = nullptr;
-        }
-        for (auto& nd : ndata) zkh_free_seal(nd.seal);
     }
-    if (join_tree == 1 && n > 1 && !errs.any()) {
+    void move_root_into_info() {            // every other node seal goes with the run
+        NodeData& r = ndata[fplan.root];
+        info->root_seal = r.seal.release(); info->root_seal_words = r.words; info->root_program = fplan.nodes[fplan.root].program;
+        memcpy(info->root_core, r.claim.core, 32); info->root_pre = r.claim.pre; info->root_post = r.claim.post;
+    }
+
+    // ---- the P2-JOIN tree (join_tree 1), after the lanes: claims.h pair_fold gives the shape, a level's joins are proven on one
+    // thread per lane; joins below the root are not kept (the verifier does not need them) ----
+    std::string join_level(size_t join_po2, const std::vector<claims::Digest>& level, std::vector<claims::Digest>& up) {
+        const size_t pairs = up.size();
+        std::vector<SealPtr> seals(pairs);
+        std::vector<size_t> words(pairs, 0);
+        std::atomic<size_t> idx{0};
+        std::vector<std::thread> th;
+        for (auto& lane : s->lanes)
+            th.emplace_back([&, l = &lane] {
+                const zkh_circuit* jc = l->join_circuit;
+                const size_t jn = (size_t)1 << join_po2;
+                Tmp code, data;
+                if (errs.set(zkh_alloc(l->ctx, "code", (size_t)jc->group_size[GROUP_CODE] * jn, 0, code.out()), "join alloc") ||
+                    errs.set(zkh_alloc(l->ctx, "data", (size_t)jc->group_size[GROUP_DATA] * jn, 0, data.out()), "join alloc")) return;
+                uint32_t pub[16], outg[24];
+                for (;;) {
+                    const size_t k = idx.fetch_add(1);
+                    if (k >= pairs || errs.any()) break;
+                    memcpy(pub, level[2 * k].data(), 32);
+                    memcpy(pub + 8, level[2 * k + 1].data(), 32);
+                    NoiseKey jk;
+                    if (errs.set(resolve_noise_key(join_noise_key, &jk), "join noise")) break;
+                    uint32_t* seal = nullptr;
+                    const bool failed = errs.set(zkh_syn_witgen(l->ctx, jc, join_po2, ZKH_ZK_CYCLES, 0, jk.k, pub, code, data, outg), "join witgen") ||
+                                        errs.set(zkh_prove_segment(l->join_prover, join_po2, ZKH_ZK_CYCLES, jk.k, code, data, outg, &seal, &words[k]), "join seal");
+                    seals[k].reset(seal);
+                    if (failed) break;
+                    memcpy(up[k].data(), seal, 32);
+                }
+                (void)zkh_sync(l->ctx);
+            });
+        for (auto& t : th) t.join();
+        if (errs.any()) return errs.get();
+        info->n_joins += pairs;
+        if (level.size() == 2) { info->root_seal = seals[0].release(); info->root_seal_words = words[0]; }
+        return "";
+    }
+    void join_tree(size_t join_po2) {
         const double tj = now_s();
-        std::vector<std::vector<uint32_t>> claims(n, std::vector<uint32_t>(8));
-        std::vector<std::pair<uint32_t, std::vector<uint32_t>>> roots;          // (po2, control root) of the leaf circuit
+        std::vector<claims::Digest> leaf_claims(n), root;
+        ControlRoots roots;
         for (size_t i = 0; i < n && !errs.any(); i++) {
-            const uint32_t po2 = segs[i].po2;
-            const std::vector<uint32_t>* root = nullptr;
-            for (auto& r : roots) if (r.first == po2) root = &r.second;
-            if (!root) {
-                std::vector<uint32_t> cr(8);
-                if (errs.set(leaf_control_root(s, segs[i], cr.data()), "control root")) break;
-                roots.emplace_back(po2, cr);
-                root = &roots.back().second;
-            }
-            errs.set(zkh_receipt_claim(s->lanes[0].circuit, info->seals[i], info->seal_words[i], root->data(), nullptr, nullptr, claims[i].data()), "receipt_claim");
+            if (errs.set(roots.add(s, segs[i]), "control root")) break;
+            errs.set(zkh_receipt_claim(s->lanes[0].circuit, info->seals[i], info->seal_words[i], roots.find(segs[i].po2), nullptr, nullptr, leaf_claims[i].data()), "receipt_claim");
         }
-        while (claims.size() > 1 && !errs.any()) {
-            const size_t pairs = claims.size() / 2;
-            std::vector<std::vector<uint32_t>> up(pairs, std::vector<uint32_t>(8));
-            std::vector<uint32_t*> seals(pairs, nullptr);
-            std::vector<size_t> words(pairs, 0);
-            std::atomic<size_t> idx{0};
-            std::vector<std::thread> th;
-            for (auto& lane : s->lanes)
-                th.emplace_back([&, l = &lane] {
-                    const zkh_circuit* jc = l->join_circuit;
-                    const size_t jn = (size_t)1 << join_po2;
-                    Tmp code, data;
-                    if (errs.set(zkh_alloc(l->ctx, "code", (size_t)jc->group_size[GROUP_CODE] * jn, 0, code.out()), "join alloc") ||
-                        errs.set(zkh_alloc(l->ctx, "data", (size_t)jc->group_size[GROUP_DATA] * jn, 0, data.out()), "join alloc")) return;
-                    uint32_t pub[16], outg[24];
-                    for (;;) {
-                        const size_t k = idx.fetch_add(1);
-                        if (k >= pairs || errs.any()) break;
-                        memcpy(pub, claims[2 * k].data(), 32);
-                        memcpy(pub + 8, claims[2 * k + 1].data(), 32);
-                        NoiseKey jk;
-                        if (errs.set(resolve_noise_key(join_noise_key, &jk), "join noise")) break;
-                        const uint32_t* noise = jk.k;
-                        if (errs.set(zkh_syn_witgen(l->ctx, jc, join_po2, ZKH_ZK_CYCLES, 0, noise, pub, code, data, outg), "join witgen") ||
-                            errs.set(zkh_prove_segment(l->join_prover, join_po2, ZKH_ZK_CYCLES, noise, code, data, outg, &seals[k], &words[k]), "join seal")) break;
-                        memcpy(up[k].data(), seals[k], 32);
-                    }
-                    (void)zkh_sync(l->ctx);
-                });
-            for (auto& t : th) t.join();
-            if (!errs.any()) {
-                info->n_joins += pairs;
-                if (claims.size() == 2) { info->root_seal = seals[0]; info->root_seal_words = words[0]; seals[0] = nullptr; }
-            }
-            for (auto p : seals) zkh_free_seal(p);            // joins below the root are not kept: the verifier does not need them
-            if (claims.size() % 2) up.push_back(claims.back());
-            claims.swap(up);
-        }
+        if (!errs.any())          // (a failed level is in errs: the string only stops the fold)
+            (void)claims::pair_fold(leaf_claims, 1, [&](const std::vector<claims::Digest>& level, std::vector<claims::Digest>& up) { return join_level(join_po2, level, up); }, &root);
         info->join_s = now_s() - tj;
     }
-    info->wall_s = now_s() - t0;
-    if (errs.any()) {
-        zkh_prove_info_free(info);
-        return make_err("session_prove: %s", errs.first.c_str());
-    }
+};
+
+}  // namespace
+
+extern "C" const char* zkh_session_prove(zkh_session* s, const zkh_segment* segs, size_t n, int join_tree, size_t join_po2, const uint32_t* join_noise_key,
+                                         zkh_prove_info* info) {
+    ZKH_REQUIRE(s && segs && n && info, "session_prove: bad argument");
+    ZKH_REQUIRE(join_tree != 1 || !s->join_desc.empty(), "session_prove: the session was created without a join circuit");
+    ZKH_REQUIRE(join_tree != 2 || !s->rec_kinds.empty(), "session_prove: join_tree 2 needs zkh_session_set_recursion");
+    memset(info, 0, sizeof *info);
+    InfoGuard guard{info};                   // from here on every return but the last leaves *info zeroed and owning nothing
+    info->n_segments = n;
+    info->seals = (uint32_t**)calloc(n, sizeof(uint32_t*));
+    info->seal_words = (size_t*)calloc(n, sizeof(size_t));
+    ZKH_REQUIRE(info->seals && info->seal_words, "session_prove: out of host memory for %zu receipts", n);
+    ZKH_REQUIRE(join_tree != 1 || s->assum_po2.empty(), "session_prove: the session has assumption receipts: they are united and resolved by the RECURSION programs (join_tree 2), the P2-JOIN tree has no such node");
+    ProveRun run(s, segs, n, join_tree, join_noise_key, info);
+    info->streamed = run.streamed;
+    ZKH_TRY(run.chain_public_inputs());
+    ZKH_TRY(run.plan_fold());
+    run.start_scheduler();
+    ZKH_TRY(run.prepare_preflight());
+    run.run_lanes();
+    run.write_statistics();
+    if (run.fold && !run.errs.any()) run.move_root_into_info();
+    if (join_tree == 1 && n > 1 && !run.errs.any()) run.join_tree(join_po2);
+    info->wall_s = now_s() - run.t0;
+    if (run.errs.any()) return make_err("session_prove: %s", run.errs.first.c_str());
+    guard.keep();
     return nullptr;
 }
 
 // receipt.verify for what zkh_session_prove returned: every leaf seal against the control root of its size, and — when a root
-// receipt is present — the root seal against the join circuit's control root plus the claim tree recomputed on the host.
-// Host arithmetic only, except that the control roots of the built-in circuits are computed on lane 0 (a deployment ships them).
-extern "C" const char* zkh_session_verify(zkh_session* s, const zkh_segment* segs, const zkh_prove_info* info, size_t join_po2) {
-    ZKH_REQUIRE(s && segs && info && info->n_segments, "session_verify: bad argument");
-    zkh_circuit* hc = nullptr;
-    ZKH_TRY(zkh_circuit_load(nullptr, s->desc.data(), s->desc.size(), &hc));
-    std::unique_ptr<zkh_circuit, void (*)(zkh_circuit*)> hold(hc, zkh_circuit_destroy);
-    std::vector<std::pair<uint32_t, std::vector<uint32_t>>> roots;
-    std::vector<std::vector<uint32_t>> claims(info->n_segments, std::vector<uint32_t>(8));
-    for (size_t i = 0; i < info->n_segments; i++) {          // the control root of every segment size first (lane 0's GPU for built-in circuits)
-        bool have = false;
-        for (auto& r : roots) have = have || r.first == segs[i].po2;
-        if (!have) {
-            std::vector<uint32_t> cr(8);
-            ZKH_TRY(leaf_control_root(s, segs[i], cr.data()));
-            roots.emplace_back(segs[i].po2, cr);
-        }
-    }
-    {
-        // the segment seals are independent and the verifier is pure host arithmetic on read-only data: spread them over host
-        // threads (upstream verifies them in a loop; 1024 seals x 7 ms is 7 s on one core)
-        ErrorSlot verrs;
-        std::atomic<size_t> next{0};
-        const size_t n_threads = std::max<size_t>(1, std::min<size_t>({(size_t)std::thread::hardware_concurrency(), (size_t)16, info->n_segments}));
-        std::vector<std::thread> th;
-        for (size_t t = 0; t < n_threads; t++)
-            th.emplace_back([&] {
-                for (;;) {
-                    const size_t i = next.fetch_add(1);
-                    if (i >= info->n_segments || verrs.any()) return;
-                    const uint32_t* root = nullptr;
-                    for (auto& r : roots) if (r.first == segs[i].po2) root = r.second.data();
-                    char what[48];
-                    snprintf(what, sizeof what, "segment %zu", i);
-                    if (verrs.set(zkh_verify_segment(hc, info->seals[i], info->seal_words[i], root, nullptr, nullptr), what)) return;
-                    if (verrs.set(zkh_receipt_claim(hc, info->seals[i], info->seal_words[i], root, nullptr, nullptr, claims[i].data()), what)) return;
-                }
-            });
-        for (auto& t : th) t.join();
-        if (verrs.any()) return make_err("session_verify: %s", verrs.first.c_str());
-    }
-    if (s->chained) {          // continuity (CompositeReceipt::verify_integrity): pre == prev.post, read from the verified seals' `out` words
-        uint32_t prev = fp_encode(s->initial_state).v;
-        for (size_t i = 0; i < info->n_segments; i++) {
-            ZKH_REQUIRE(info->seal_words[i] > 5 && info->seals[i][4] == prev, "session_verify: the session is not continuous: segment %zu does not start from its predecessor's post-state", i);
-            prev = info->seals[i][0];
-        }
-        // SYN-S: the session TERMINATES here — every segment but the last says SystemSplit, the last Halted(0) and carries the digest
-        // of the journal (= the final state word): a receipt with trailing segments cut off ends in a SystemSplit and is refused
-        if (circuit_is_session(s->lanes[0].circuit)) {
-            std::vector<const uint32_t*> seals(info->n_segments);
-            for (size_t i = 0; i < info->n_segments; i++) {
-                ZKH_REQUIRE(info->seal_words[i] > SESSION_OUT_WORDS, "session_verify: segment %zu: seal too short", i);
-                seals[i] = info->seals[i];
+// receipt is present — the root seal against the join circuit's control root plus the claim tree recomputed on the host
+// (claims.h).  Host arithmetic only, except that the control roots of the built-in circuits are computed on lane 0 (a deployment
+// ships them).
+// the segment seals are independent and the verifier is pure host arithmetic on read-only data: spread them over host
+// threads (upstream verifies them in a loop; 1024 seals x 7 ms is 7 s on one core)
+static const char* verify_leaves(const zkh_circuit* hc, const zkh_segment* segs, const zkh_prove_info* info, const ControlRoots& roots,
+                                 std::vector<claims::Digest>& leaf_claims) {
+    ErrorSlot verrs;
+    std::atomic<size_t> next{0};
+    const size_t n_threads = std::max<size_t>(1, std::min<size_t>({(size_t)std::thread::hardware_concurrency(), (size_t)16, info->n_segments}));
+    std::vector<std::thread> th;
+    for (size_t t = 0; t < n_threads; t++)
+        th.emplace_back([&] {
+            for (;;) {
+                const size_t i = next.fetch_add(1);
+                if (i >= info->n_segments || verrs.any()) return;
+                const uint32_t* root = roots.find(segs[i].po2);
+                char what[48];
+                snprintf(what, sizeof what, "segment %zu", i);
+                if (verrs.set(zkh_verify_segment(hc, info->seals[i], info->seal_words[i], root, nullptr, nullptr), what)) return;
+                if (verrs.set(zkh_receipt_claim(hc, info->seals[i], info->seal_words[i], root, nullptr, nullptr, leaf_claims[i].data()), what)) return;
             }
-            uint32_t ad[8];
-            ZKH_TRY(check_session_termination(seals.data(), info->n_segments, s->journal_ptr(), s->journal.size(), s->assumptions_digest(ad)));
-        }
+        });
+    for (auto& t : th) t.join();
+    ZKH_REQUIRE(!verrs.any(), "session_verify: %s", verrs.first.c_str());
+    return nullptr;
+}
+// continuity (CompositeReceipt::verify_integrity): pre == prev.post, read from the verified seals' `out` words
+static const char* verify_continuity(zkh_session* s, const zkh_prove_info* info) {
+    uint32_t prev = fp_encode(s->initial_state).v;
+    for (size_t i = 0; i < info->n_segments; i++) {
+        ZKH_REQUIRE(info->seal_words[i] > 5 && info->seals[i][4] == prev, "session_verify: the session is not continuous: segment %zu does not start from its predecessor's post-state", i);
+        prev = info->seals[i][0];
     }
-    if (!info->root_seal) return nullptr;
-    if (info->n_lifts) {
-        // a RECURSION root: ONE seal under a program of the allowed set, out = claim tree root ‖ allowed-programs root
-        ZKH_REQUIRE(!s->rec_kinds.empty() && info->root_program < s->rec_roots.size(), "session_verify: a recursion root without the session's programs");
-        zkh_circuit* rc = nullptr;
-        ZKH_TRY(zkh_circuit_load(nullptr, s->rec_desc.data(), s->rec_desc.size(), &rc));
-        std::unique_ptr<zkh_circuit, void (*)(zkh_circuit*)> rhold(rc, zkh_circuit_destroy);
-        if (const char* e = zkh_verify_segment(rc, info->root_seal, info->root_seal_words, s->rec_roots[info->root_program].data(), nullptr, nullptr)) {
-            const char* out = make_err("session_verify: root receipt: %s", e);
-            zkh_free_error(e);
-            return out;
-        }
-        // the claim tree over the leaves (receipt claim + state words of every VERIFIED segment seal), as the lift2 / join programs
-        // build it in-circuit: parent core = hash_pair(claim'_l, claim'_r), state range [pre_l, post_r], and neighbours must chain
-        std::vector<NodeClaim> nodes(info->n_segments);
-        for (size_t i = 0; i < info->n_segments; i++) {
-            memcpy(nodes[i].core, claims[i].data(), 32);
-            const bool chained = circuit_has_state(hc);
-            nodes[i].pre = chained ? info->seals[i][4] : 0; nodes[i].post = chained ? info->seals[i][0] : 0;
-        }
-        // ... in the shape of the fold plan (fold_claim_nodes: pairs, then three at a time)
-        NodeClaim top;
-        ZKH_TRY(fold_claim_nodes(nodes, &top));
-        uint32_t want[8];
-        ZKH_TRY(wrap_claim(top, want));
-        if (!s->assum_seals.empty()) {
-            // the session was RESOLVED against its assumption receipts (verified when they were handed over): the union tree over their
-            // lifted claims, then claim' = wrap(hash_pair(claim' of the join tree, claim' of the union tree), pre, post of the session)
-            zkh_circuit* ac = nullptr;
-            ZKH_TRY(zkh_circuit_load(nullptr, s->assum_desc.data(), s->assum_desc.size(), &ac));
-            std::unique_ptr<zkh_circuit, void (*)(zkh_circuit*)> ahold(ac, zkh_circuit_destroy);
-            std::vector<std::array<uint32_t, 8>> lifted(s->assum_seals.size());
-            for (size_t i = 0; i < lifted.size(); i++) {
-                NodeClaim nd;
-                ZKH_TRY(zkh_receipt_claim(ac, s->assum_seals[i].data(), s->assum_seals[i].size(), s->assum_roots[i].data(), nullptr, nullptr, nd.core));
-                ZKH_TRY(wrap_claim(nd, lifted[i].data()));
-            }
-            uint32_t assumed[8];
-            ZKH_TRY(union_tree(lifted, assumed));
-            NodeClaim res;
-            ZKH_TRY(hash_pair_host(want, assumed, res.core));
-            res.pre = top.pre; res.post = top.post;
-            ZKH_TRY(wrap_claim(res, want));
-        }
-        ZKH_REQUIRE(info->root_seal_words > 16 && memcmp(info->root_seal, want, 32) == 0,
-                    s->assum_seals.empty() ? "session_verify: the root receipt does not commit to the claim tree of these segments"
-                                           : "session_verify: the root receipt does not commit to the claim tree of these segments resolved against the session's assumption receipts");
-        ZKH_REQUIRE(memcmp(info->root_seal + 8, s->allowed.back()[0].data(), 32) == 0, "session_verify: the root receipt was produced under another allowed-programs root");
-        return nullptr;
+    // SYN-S: the session TERMINATES here — every segment but the last says SystemSplit, the last Halted(0) and carries the digest
+    // of the journal (= the final state word): a receipt with trailing segments cut off ends in a SystemSplit and is refused
+    if (!circuit_is_session(s->lanes[0].circuit)) return nullptr;
+    std::vector<const uint32_t*> seals(info->n_segments);
+    for (size_t i = 0; i < info->n_segments; i++) {
+        ZKH_REQUIRE(info->seal_words[i] > SESSION_OUT_WORDS, "session_verify: segment %zu: seal too short", i);
+        seals[i] = info->seals[i];
     }
+    uint32_t ad[8];
+    return check_session_termination(seals.data(), info->n_segments, s->journal_ptr(), s->journal.size(), s->assumptions_digest(ad));
+}
+// a RECURSION root: ONE seal under a program of the allowed set, out = claim tree root ‖ allowed-programs root
+static const char* verify_recursion_root(zkh_session* s, const zkh_circuit* hc, const zkh_prove_info* info, const std::vector<claims::Digest>& leaf_claims) {
+    ZKH_REQUIRE(!s->rec_kinds.empty() && info->root_program < s->rec_roots.size(), "session_verify: a recursion root without the session's programs");
+    CircuitPtr rc;
+    ZKH_TRY(load_host_circuit(s->rec_desc, &rc));
+    ZKH_TRY(verify_under(rc.get(), info->root_seal, info->root_seal_words, s->rec_roots[info->root_program].data(), "session_verify: root receipt"));
+    // the claim tree over the leaves (receipt claim + state words of every VERIFIED segment seal), as the lift2 / join programs
+    // build it in-circuit, in the shape of the fold plan; a session with assumption receipts (verified when they were handed over)
+    // was RESOLVED against the union tree over their lifted claims
+    std::vector<NodeClaim> nodes(info->n_segments);
+    for (size_t i = 0; i < info->n_segments; i++) { memcpy(nodes[i].core, leaf_claims[i].data(), 32); leaf_state(hc, info->seals[i], &nodes[i]); }
+    std::vector<claims::Digest> lifted(s->assum_seals.size());
+    for (size_t i = 0; i < lifted.size(); i++) ZKH_TRY(lifted_claim(&s->assum_claims[8 * i], &lifted[i]));
+    uint32_t want[8];
+    ZKH_TRY(claim_err(claims::session_root_claim(HASH_PAIR, nodes, 1, lifted, want)));
+    ZKH_REQUIRE(info->root_seal_words > 16 && memcmp(info->root_seal, want, 32) == 0,
+                s->assum_seals.empty() ? "session_verify: the root receipt does not commit to the claim tree of these segments"
+                                       : "session_verify: the root receipt does not commit to the claim tree of these segments resolved against the session's assumption receipts");
+    ZKH_REQUIRE(memcmp(info->root_seal + 8, s->allowed.back()[0].data(), 32) == 0, "session_verify: the root receipt was produced under another allowed-programs root");
+    return nullptr;
+}
+// a P2-JOIN root: its public inputs are the two children of the root of the pairwise claim tree
+static const char* verify_join_root(zkh_session* s, const zkh_prove_info* info, size_t join_po2, const std::vector<claims::Digest>& leaf_claims) {
     ZKH_REQUIRE(!s->join_desc.empty() && info->n_segments > 1, "session_verify: a root receipt without a join circuit");
-    zkh_circuit* jc = nullptr;
-    ZKH_TRY(zkh_circuit_load(nullptr, s->join_desc.data(), s->join_desc.size(), &jc));
-    std::unique_ptr<zkh_circuit, void (*)(zkh_circuit*)> jhold(jc, zkh_circuit_destroy);
+    CircuitPtr jc;
+    ZKH_TRY(load_host_circuit(s->join_desc, &jc));
     uint32_t jroot[8];
     ZKH_TRY(zkh_syn_control_root(s->lanes[0].join_prover, join_po2, ZKH_ZK_CYCLES, jroot));
-    if (const char* e = zkh_verify_segment(jc, info->root_seal, info->root_seal_words, jroot, nullptr, nullptr)) {
-        const char* out = make_err("session_verify: root receipt: %s", e);
-        zkh_free_error(e);
-        return out;
-    }
-    while (claims.size() > 2) {
-        std::vector<std::vector<uint32_t>> up(claims.size() / 2, std::vector<uint32_t>(8));
-        for (size_t k = 0; k < up.size(); k++) {
-            uint32_t st[24] = {0};
-            memcpy(st, claims[2 * k].data(), 32); memcpy(st + 8, claims[2 * k + 1].data(), 32);
-            ZKH_TRY(zkh_poseidon2_mix_host(nullptr, nullptr, st, 1));
-            memcpy(up[k].data(), st, 32);
-        }
-        if (claims.size() % 2) up.push_back(claims.back());
-        claims.swap(up);
-    }
-    ZKH_REQUIRE(info->root_seal_words > 24 && memcmp(info->root_seal + 8, claims[0].data(), 32) == 0 && memcmp(info->root_seal + 16, claims[1].data(), 32) == 0,
+    ZKH_TRY(verify_under(jc.get(), info->root_seal, info->root_seal_words, jroot, "session_verify: root receipt"));
+    std::vector<claims::Digest> top;
+    ZKH_TRY(claim_err(claims::pair_fold(leaf_claims, 2, claims::hashed_level(HASH_PAIR), &top)));
+    ZKH_REQUIRE(info->root_seal_words > 24 && memcmp(info->root_seal + 8, top[0].data(), 32) == 0 && memcmp(info->root_seal + 16, top[1].data(), 32) == 0,
                 "session_verify: the root receipt does not commit to the claim tree of these segments");
     return nullptr;
+}
+
+extern "C" const char* zkh_session_verify(zkh_session* s, const zkh_segment* segs, const zkh_prove_info* info, size_t join_po2) {
+    ZKH_REQUIRE(s && segs && info && info->n_segments, "session_verify: bad argument");
+    CircuitPtr hc;
+    ZKH_TRY(load_host_circuit(s->desc, &hc));
+    ControlRoots roots;                                       // the control root of every segment size first (lane 0's GPU for built-in circuits)
+    for (size_t i = 0; i < info->n_segments; i++) ZKH_TRY(roots.add(s, segs[i]));
+    std::vector<claims::Digest> leaf_claims(info->n_segments);
+    ZKH_TRY(verify_leaves(hc.get(), segs, info, roots, leaf_claims));
+    if (s->chained) ZKH_TRY(verify_continuity(s, info));
+    if (!info->root_seal) return nullptr;
+    if (info->n_lifts) return verify_recursion_root(s, hc.get(), info, leaf_claims);
+    return verify_join_root(s, info, join_po2, leaf_claims);
 }
