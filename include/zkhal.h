@@ -536,9 +536,14 @@ const char* zkh_page_ordered_witgen(zkh_ctx*, const zkh_circuit*, size_t po2, si
  * seals a page-out of any size; the verifier is told h.  The trace is B = (2^po2 - zk_cycles) / 31 blocks of P2-JOIN's 31 rows, one
  * tree node each, old and new permutation side by side; a parent reads its children over a bus in the accum group (24 columns), which
  * zkh_accumulate fills from the circuit's ZKA1 arguments (zkh_circuit_set_arguments with p2_tree.arguments()): zkh_syn_accum does not
- * serve kind 7.  The columns, the constraints and why the bus forces a tree: p2_tree.py.  Still NOT constrained: which words of a pair
- * changed, and that the table is the page table of a paging segment's seal.  W > 16, h = 2 .. 27, B >= h.
- * zkh_page_tree_code: `code` of 41 x 2^po2 words, a function of (po2, zk_cycles) alone: one control root for every image size.
+ * serve kind 7.  The columns, the constraints and why the bus forces a tree: p2_tree.py.  NOT constrained by kind 7: which words of a pair
+ * were touched, and that the table is the page table of a paging segment's seal; P2-TREE-tied constrains both.  W > 16, h = 2 .. 27, B >= h.
+ * P2-TREE-tied (circuit kind 9, zeth_amd/circuits/p2_tree_tied.py): P2-TREE's code group and data columns 0 .. 105, then ch[16] and wa[16]
+ * (138 data columns: on the input row of a pair block, which of its 16 words the part touches, and their addresses), an OPEN bus of 12
+ * Fp4 accum columns (48; zkh_accumulate_open) and out = P2-TREE's 18 words ‖ base ‖ alpha ‖ beta ‖ F (31).  Both calls below serve it:
+ * the circuit's own kind decides the shape, and a circuit of neither kind is refused in P2-TREE's words.
+ * zkh_page_tree_code: `code` of 41 x 2^po2 words, a function of (po2, zk_cycles) alone: one control root for every image size; the
+ * same words for kind 7 and kind 9.
  * zkh_page_tree_plan (HOST ONLY): the parts of a table with the addresses addrs[0 .. D) (strictly increasing, below image_words), greedy:
  * a part takes whole pairs of leaves while its nodes stay at most B, its first pair costing h nodes and every later one bit_length(pair
  * index xor the one before).  parts[2 p], parts[2 p + 1] = (first, count) of part p for p < parts_cap; *n_parts is the number of parts
@@ -555,8 +560,9 @@ const char* zkh_page_ordered_witgen(zkh_ctx*, const zkh_circuit*, size_t po2, si
  * LOWEST row of the whole table that breaks the table's rule, in zkh_page_tree_witgen's words: "row R: address A outside the image of
  * W words" or "row R: address A does not follow a smaller one (row R-1: address A')".  On a refusal nothing is written, *n_parts
  * included.
- * zkh_page_tree_witgen: zkh_page_ordered_witgen's operands with the part as (first, count), `data` of 106 x 2^po2 words, out[18].  Both
- * trees are the WHOLE page-out's for every part.  One read-back at the end, no atomics, one writer per cell.  Refusals after
+ * zkh_page_tree_witgen: zkh_page_ordered_witgen's operands with the part as (first, count), `data` of 106 x 2^po2 words (kind 9: 138 x
+ * 2^po2, the 32 word columns by one more kernel, one lane per cell), out[18] for both kinds (kind 9: the caller appends base =
+ * Montgomery(2^(h+3)), the challenge and the total).  Both trees are the WHOLE page-out's for every part.  One read-back at the end, no atomics, one writer per cell.  Refusals after
  * "page_tree_witgen: " (the shape ones also after "page_tree_code: " / "page_tree_plan: "): "the circuit does not have P2-TREE's shape
  * (kind 7, 41 / 106 / 24 columns, 18 outputs)"; "an image of W words has a single pair of leaves (W > 16: ...)"; "no room for the h H
  * nodes of one path in B block slots"; the proof header's and the tree buffers' as zkh_page_circuit_witgen; "the part [F, E) of a table
@@ -608,7 +614,8 @@ size_t zkh_ctx_h2d_bytes(const zkh_ctx*);
  *   kind 5 P2-PAGE   has a generator of its own, zkh_page_circuit_code / zkh_page_circuit_witgen above (its inputs are a proof and
  *                    two trees, not a seed); zkh_syn_accum builds its accum group, which is P2-JOIN's.
  *   kind 6 P2-PAGE-ordered  likewise: zkh_page_ordered_code / zkh_page_ordered_witgen above, and zkh_syn_accum.
- *   kind 7 P2-TREE   zkh_page_tree_code / zkh_page_tree_witgen above; its accum group is a bus: zkh_accumulate, not zkh_syn_accum. */
+ *   kind 7 P2-TREE   zkh_page_tree_code / zkh_page_tree_witgen above; its accum group is a bus: zkh_accumulate, not zkh_syn_accum.
+ *   kind 9 P2-TREE-tied  the same two calls; its accum group is an open bus: zkh_accumulate_open. */
 /* BLINDING ROWS.  The last zk_cycles rows of every data / accum column are zero-knowledge blinding noise.  Upstream draws each
  * cell from the OS RNG (`Elem::random(&mut rng)`); here the randomness enters once per call as a 256-bit key — `noise_key`, 8
  * words — and every cell is ChaCha12(key; counter = (row, column), nonce = (group, "ZKN1")) folded mod P the way upstream's

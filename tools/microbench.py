@@ -23,7 +23,9 @@ parts of one page-out of 662 267 addresses under p2_tree's plan and under P2-PAG
 zkh_page_ordered_witgen and the seal of a part under both circuits, alternating, with every witness call's stages; M25: P2-TREE's plan
 of M24's table by zkh_page_tree_plan_device next to the read-back of the table and zkh_page_tree_plan, alternating; M26: zkh_reduce_elem
 at SYN-A's code and data widths next to zkh_eltwise_copy_elem over the same bytes, alternating; M27: the tie, zkh_data_root of a P2-PAGE-tied
-part next to its seal, zkh_accumulate_open next to zkh_accumulate, zkh_table_fingerprint next to a copy of the same bytes, alternating) on one MI355X, through the C ABI (HipHal).
+part next to its seal, zkh_accumulate_open next to zkh_accumulate, zkh_table_fingerprint next to a copy of the same bytes, alternating;
+M28: P2-TREE-tied, the witness and the seal of a kind-9 part next to the kind-7 part's, alternating, and the page-out side of a whole tied
+group under P2-TREE-tied next to P2-PAGE-tied's on the same table) on one MI355X, through the C ABI (HipHal).
 
 Each line of output is one JSON object: the op, its shape, the average wall time of one call (stream drained on both
 sides of `reps` back-to-back calls), its ALGORITHMIC bytes (SURVEY.md §8a "B_alg": inputs read once + outputs written
@@ -1367,6 +1369,114 @@ def main() -> None:
                           "open_over_closed": round(med["accumulate_open_tied"] / med["accumulate_paged"], 4),
                           "fingerprint_over_copy": round(med["table_fingerprint"] / med["eltwise_copy_elem_same_bytes"], 4),
                           "fingerprint_rows_per_us": round(D / med["table_fingerprint"] / 1e6, 1)}), flush=True)
+    if want("M28"):
+        # P2-TREE-tied (DESIGN.md §2 "THE TIE"): what tying P2-TREE costs, on M24's table (662 267 random addresses over an image of 2^20
+        # words), in one run, alternating windows, median and spread.  The witness of a kind-9 part next to the kind-7 part's (the same
+        # part of the same plan: 32 more columns by one more kernel, and a wider tail); a tied part's seal (zkh_accumulate_open over 12
+        # Fp4 columns, 138 data columns) next to the P2-TREE part's seal (zkh_accumulate over 6, 106); and the page-out side of a whole
+        # tied group, both passes of every part (witness, data root; witness, open accumulate, seal), timed once each, P2-TREE-tied's
+        # parts next to P2-PAGE-tied's.  The yardsticks are the parent's kind-7 and P2-PAGE-tied paths in this run.  No threshold.
+        from zeth_amd import hal as zhal
+        from zeth_amd.circuits import p2_page, p2_page_tied, p2_tree, p2_tree_tied
+        from zeth_amd.prover import Segment, SegmentProver
+        runs, zk, D, W = 7, 1994, 662267, 1 << 20
+        spread = lambda ts: {"median_ms": round(float(np.median(ts)) * 1e3, 4), "min_ms": round(min(ts) * 1e3, 4), "max_ms": round(max(ts) * 1e3, 4)}   # noqa: E731
+        h = p2_page.tree_height(W)
+        image_h = rand_fp(rng, W)
+        addrs = np.sort(rng.choice(W, D, replace=False)).astype(np.int64)
+        outs = rand_fp(rng, D)
+        table = np.stack([addrs.astype(np.uint32), image_h[addrs], outs], axis=1).reshape(-1)
+        proof_h = np.concatenate([np.array([0x5A4B5531, W, D, 0, h] + [0] * h, dtype=np.uint32), table])
+        image = hal.alloc_elem("m28i", W)
+        image.write(image_h)
+        before = hal.image_commit(image)
+        image_h[addrs] = outs
+        image.write(image_h)
+        after = hal.image_commit(image)
+        del image
+        proof = hal.copy_from("m28p", proof_h)
+        challenge = zhal.tie_challenge(rand_fp(rng, 16))
+        seg = Segment(index=0, po2=args.po2, zk_cycles=zk, noise_seed=0x2E80)
+        plan = hal.page_tree_plan(args.po2, zk, W, addrs)
+        mods = {"tree": p2_tree, "tree_tied": p2_tree_tied}
+        provers = {"tree": SegmentProver(hal, p2_tree.p2_tree_circuit(), arguments=p2_tree.arguments()),
+                   "tree_tied": SegmentProver(hal, p2_tree_tied.p2_tree_tied_circuit(), arguments=p2_tree_tied.arguments())}
+        code = hal.page_tree_code(provers["tree"].circuit, args.po2, zk)         # one code group serves both kinds
+        datas = {k: hal.alloc_elem("m28d", m.WD * n) for k, m in mods.items()}
+        accum = hal.alloc_elem("m28a", p2_tree_tied.WA * n)
+        prefix = {}
+        witness = lambda k, part: lambda: prefix.__setitem__(k, hal.page_tree_witgen(provers[k].circuit, args.po2, zk, code, proof, proof_h.size, before, after,   # noqa: E731
+                                                                                      part[0], part[1], datas[k], seg.noise_seed))
+
+        def tied_out(total):
+            return np.concatenate([prefix["tree_tied"], [p2_tree_tied.out_base(h)], challenge, total]).astype(np.uint32)
+
+        def seal_tied_part():
+            total = hal.accumulate_open(provers["tree_tied"].circuit, args.po2, zk, seg.noise_seed, code, datas["tree_tied"], challenge, accum)
+            return provers["tree_tied"].seal_with_accum(seg, code, datas["tree_tied"], tied_out(total), lambda _mix: accum)
+        seal_tree_part = lambda: provers["tree"].seal_with_accum(seg, code, datas["tree"], prefix["tree"].copy(),   # noqa: E731
+                                                                 provers["tree"].args_accumulate(seg, code, datas["tree"]))
+        fns = [("witness_tree_part_0", witness("tree", plan[0])), ("witness_tree_tied_part_0", witness("tree_tied", plan[0]))]
+        seals = [("seal_tree_part", seal_tree_part), ("seal_tree_tied_part", seal_tied_part)]
+        t = {name: [] for name, _ in fns + seals}
+        for _ in range(runs):
+            for name, fn in fns:
+                t[name].append(timed(hal, fn, args.reps))
+        assert np.array_equal(prefix["tree"], prefix["tree_tied"]), "the two kinds do not state the same 18 words"
+        steps = {}
+        for name, fn in fns:
+            hal.prof_enable(True)
+            hal.prof_reset()
+            for _ in range(args.reps):
+                fn()
+            hal.sync()
+            steps[name] = {r["name"]: {"calls_per_call": r["calls"] // args.reps, "ms_per_call": round(r["total_ms"] / args.reps, 4)} for r in hal.prof_get()
+                           if r["calls"] and r["name"].startswith(("page_", "tree_"))}
+            hal.prof_enable(False)
+        for _ in range(runs):
+            for name, fn in seals:
+                t[name].append(timed(hal, fn, args.reps))
+        # the page-out side of a whole group, once: pass one (witness, data root) and pass two (witness, accumulate, seal) of every part
+        totals = np.zeros(4, dtype=np.uint64)
+
+        def tree_group():
+            totals[:] = 0
+            for part in plan:
+                witness("tree_tied", part)()
+                provers["tree_tied"].data_root(datas["tree_tied"], args.po2)
+            for part in plan:
+                witness("tree_tied", part)()
+                total = hal.accumulate_open(provers["tree_tied"].circuit, args.po2, zk, seg.noise_seed, code, datas["tree_tied"], challenge, accum)
+                totals[:] = (totals + total) % np.uint64(P)
+                provers["tree_tied"].seal_with_accum(seg, code, datas["tree_tied"], tied_out(total), lambda _mix: accum)
+        group = {"tree_tied": {"parts": len(plan), "total_ms": round(timed(hal, tree_group, 1) * 1e3, 2)}}
+        want_total = hal.table_fingerprint(proof, 5 + h, D, challenge).astype(np.uint64)
+        assert not ((totals + want_total) % np.uint64(P)).any(), "the parts' open totals are not minus the fingerprint of the table"
+        del datas, accum
+        page = SegmentProver(hal, p2_page_tied.p2_page_tied_circuit(), arguments=p2_page_tied.arguments())
+        page_code = hal.page_ordered_code(page.circuit, args.po2, zk, W)
+        page_data = hal.alloc_elem("m28pd", p2_page_tied.WD * n)
+        page_accum = hal.alloc_elem("m28pa", p2_page_tied.WA * n)
+        page_plan = p2_page.parts(args.po2, zk, W, D)
+        page_witness = lambda first: hal.page_ordered_witgen(page.circuit, args.po2, zk, page_code, proof, proof_h.size, before, after, first, page_data, seg.noise_seed)   # noqa: E731
+
+        def page_group():
+            for first, _count in page_plan:
+                page_witness(first)
+                page.data_root(page_data, args.po2)
+            for first, _count in page_plan:
+                words = page_witness(first)
+                total = hal.accumulate_open(page.circuit, args.po2, zk, seg.noise_seed, page_code, page_data, challenge, page_accum)
+                page.seal_with_accum(seg, page_code, page_data, np.concatenate([words[:p2_page_tied.PREFIX_WORDS], challenge, total]), lambda _mix: page_accum)
+        group["page_tied"] = {"parts": len(page_plan), "total_ms": round(timed(hal, page_group, 1) * 1e3, 2)}
+        med = {name: float(np.median(v)) for name, v in t.items()}
+        print(json.dumps({"bench": "M28", "library": os.path.basename(os.environ.get("ZKH_LIBRARY", "") or "libzkhal_mi355x.so"), "po2": args.po2,
+                          "image_words": W, "layers": h, "table_rows": D, "block_slots": p2_tree.block_slots(args.po2, zk), "runs": runs, "reps": args.reps,
+                          **{name: spread(v) for name, v in t.items()}, "steps": steps, "group_page_out_side": group,
+                          "columns": {k: {"code": m.WC, "data": m.WD, "accum": m.WA} for k, m in mods.items()},
+                          "witness_tied_over_tree": round(med["witness_tree_tied_part_0"] / med["witness_tree_part_0"], 4),
+                          "seal_tied_over_tree": round(med["seal_tree_tied_part"] / med["seal_tree_part"], 4),
+                          "group_tree_tied_over_page_tied": round(group["tree_tied"]["total_ms"] / group["page_tied"]["total_ms"], 4)}), flush=True)
     hal.close()
 
 

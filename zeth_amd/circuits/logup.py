@@ -73,6 +73,15 @@ zero.  The terms of the open tag are the ones another seal answers: they are no 
 no sorted copy has that tag, and a bus check (`reference_bus`, zkh_check_bus) skips its keys.  Every other term nets to zero inside
 the seal, so the total is the sum of the open tag's terms: `table_fingerprint` of the rows they carry.
 
+THE SPLIT CLOSURE (`LogupBuilder(..., open_bus=..., split_close=True)`; p2_tree_tied.py).  "Every other term nets to zero inside the seal"
+is what the prover's accumulate finds, not what the one closing equation sum_c S_c = F constrains: a closed term left over in one seal
+only moves that seal's F, and the group check sum F = 0 then balances the closed tuples across the GROUP.  A circuit whose closed bus
+must balance per seal (P2-TREE's digest bus: a child produced in one part must not be consumed in another) asks for the split closure:
+a column is open when all its terms carry the open tag and closed when none does (a mixed column is refused), and `last` states
+sum over closed columns S_c = 0 and sum over open columns S_c = out[total ..].  The challenge is drawn after every data root of the
+group is fixed, so the closed bus balances inside the seal with the usual probability and F is the open terms alone.  The blob is the
+same version-8 blob: the accumulate, the bus check and the OPEN record do not know how the description closes.
+
 A derived term is the table side of a lookup (`check_derived`): sign -1, its multiplicity a data column that no tuple and no other
 term names, and every other term of its tag a lookup of sign +1.  Its multiplicity column is then a function of the traces:
 on each table key's representative (the entry of smallest (blob term index, row)) the number of lookups of that key, 0 on the
@@ -769,10 +778,14 @@ class Arguments:
 class LogupBuilder(CircuitBuilder):
     """CircuitBuilder that also records argument terms and emits their constraints (`arguments`)."""
 
-    def __init__(self, group_sizes, global_sizes, alpha: int = 0, beta: int = 4, kind: int = 0, open_bus: Optional[Tuple[int, int]] = None):
+    def __init__(self, group_sizes, global_sizes, alpha: int = 0, beta: int = 4, kind: int = 0, open_bus: Optional[Tuple[int, int]] = None,
+                 split_close: bool = False):
         """open_bus = (tag, total): the OPEN mode (the module docstring's open bus).  alpha and beta are then `out` word offsets, every
         term reads the challenges there, the terms of `tag` are answered by another seal and `arguments` closes the bus on the four
-        `out` words at `total`.  The blob gets an OPEN record (ZKA1 version 8)."""
+        `out` words at `total`.  The blob gets an OPEN record (ZKA1 version 8).
+        split_close (open mode only; the module docstring's THE SPLIT CLOSURE): an accum column is OPEN when every term of it has the
+        open tag and CLOSED when none has, a column that mixes them is refused, and `arguments` closes twice: the closed columns on
+        zero, the open ones on the total.  The blob does not change: the description alone says how the bus closes."""
         super().__init__(tuple(group_sizes), tuple(global_sizes), kind=kind)
         if group_sizes[GROUP_ACCUM] % 4:
             raise ValueError("the accum group holds Fp4 columns: its width is a multiple of 4")
@@ -783,6 +796,9 @@ class LogupBuilder(CircuitBuilder):
         self.terms: List[Term] = []
         self.records: List[Record] = []
         self.open: Optional[Open] = None
+        self.split_close = bool(split_close)
+        if split_close and open_bus is None:
+            raise ValueError("split_close is an option of the open bus (open_bus=...): a closed bus closes on zero as it stands")
         if open_bus is not None:
             self.open = Open(int(open_bus[0]), int(alpha), int(beta), int(open_bus[1]), int(global_sizes[0]))
             problem = check_open([Term(0, ((GROUP_DATA, 0),), tag=self.open.tag)], [self.open])     # the offsets; the terms come later
@@ -821,12 +837,18 @@ class LogupBuilder(CircuitBuilder):
         if problem:
             self.terms.pop()
             raise ValueError(problem)
+        if self.split_close and len({self._is_open(x) for x in self.terms if x.col == col}) > 1:
+            self.terms.pop()
+            raise ValueError(f"accum column {col} mixes terms of the open tag {self.open.tag} with others (split_close: a column is open or closed)")
         deg = column_degree([x for x in self.terms if x.col == col])
         if deg > MAX_DEGREE:
             self.terms.pop()
             raise ValueError(f"accum column {col}: constraint degree {deg} exceeds {MAX_DEGREE} (at most 3 terms of single-column "
                              f"selectors and multiplicities per column)")
         return t
+
+    def _is_open(self, t: Term) -> bool:
+        return self.open is not None and t.tag % P == self.open.tag % P
 
     def _record(self, rec):
         # LIMBS / ORDER records, then LINK records, then the PAGES record, which names its LINK by index: that index moves with the LINK
@@ -1062,6 +1084,23 @@ class LogupBuilder(CircuitBuilder):
                 body_inner = self.and_eqz(body_inner, b[i] if b[i] is not None else self.const(0))
         chain = self.and_cond(chain, first, first_inner)
         chain = self.and_cond(chain, body, body_inner)
+        if self.split_close:                                                 # two closing steps: the closed columns on zero, the open ones on the total
+            last_inner = self.true()
+            kinds = [{self._is_open(t) for t in ts} for ts in cols]
+            for c, kind in enumerate(kinds):
+                if len(kind) != 1:                                           # a column without terms was refused above: every column is in one sum
+                    raise ValueError(f"accum column {c} mixes terms of the open tag {self.open.tag} with others (split_close: a column is open or closed)"
+                                     if kind else f"accum column {c} has no terms")
+            for is_open in (False, True):
+                tot = [None] * 4
+                for c, kind in enumerate(kinds):
+                    if kind == {is_open}:
+                        tot = self._e_add(tot, acc(c))
+                if is_open:
+                    tot = self._e_sub(tot, self._mix4(self.open.total))
+                for i in range(4):
+                    last_inner = self.and_eqz(last_inner, tot[i] if tot[i] is not None else self.const(0))
+            return self.and_cond(chain, last, last_inner)
         tot = [None] * 4
         for c in range(self.k):
             tot = self._e_add(tot, acc(c))

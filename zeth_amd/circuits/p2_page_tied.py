@@ -19,7 +19,8 @@ circuit as they stand.  What differs is the accum group and `out`:
   out (30 words): P2-PAGE-ordered's 18 ‖ alpha (4) ‖ beta (4) ‖ F (4).
 Globals: mix = 4 words, which no constraint reads.
 
-NOT constrained here: nothing about the segment; the group verifier holds the other half.
+NOT constrained here: nothing about the segment; the group verifier holds the other half.  This circuit costs one Merkle path per word;
+P2-TREE-tied (p2_tree_tied.py) states the same tie over P2-TREE's dirty nodes, a few seals where this one takes hundreds.
 """
 from __future__ import annotations
 

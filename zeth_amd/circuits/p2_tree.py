@@ -54,9 +54,9 @@ are forced by the keys.  Depth is forced too: leaf = 1 blocks are range-checked 
 inside [2^(h-1), 2^h), so a pair block sits h - 1 levels below the root, and leaf = 0 blocks that consume nothing have old = new on
 both halves: they are no-ops.  (A block with up = 0 that is not the root slot is cut off from the tree: nothing reads it.)
 
-NOT constrained here: which words of a pair changed, and that the updates are the page table of a particular paging segment's seal
-(p2_page_tied.py ties P2-PAGE-ordered's rows to it over a bus across seals; a pair block's input row holds the 16 old and the 16 new
-words of its addresses, and once it constrains which of them changed, this circuit plugs into the same bus).
+NOT constrained here: which words of a pair were touched, and that the updates are the page table of a particular paging segment's seal.
+P2-TREE-tied (p2_tree_tied.py, kind 9) is this circuit plus both: this constraint text (`build_tree`) with the family `words` over 32 more
+data columns, and the touched words of its pair blocks on the bus across seals that p2_page_tied.py put P2-PAGE-ordered's rows on.
 Not a shipped circuit: it is loaded the way SYN-LOOKUP is, and its control root is zkh_code_root of its code group.
 """
 from __future__ import annotations
@@ -95,6 +95,15 @@ def block_slots(po2: int, zk_cycles: int) -> int:
 def build_p2_tree() -> Tuple[np.ndarray, np.ndarray]:
     """-> (ZKC1 description, ZKA1 argument blob)"""
     b = LogupBuilder((WA, WC, WD), (OUT_WORDS, MIX_WORDS), alpha=0, beta=4, kind=KIND_P2_TREE)
+    blobs, FAMILIES[:] = build_tree(b)
+    return blobs
+
+
+def build_tree(b, after_root=None, terms=None):
+    """-> ((ZKC1 description, ZKA1 argument blob), families): P2-TREE's constraint text emitted into the LogupBuilder `b`, whose data
+    columns 0 .. 105 and code columns are P2-TREE's.  after_root = (name, emit): emit(b, chain) -> chain emits one more family, `name`,
+    between `root` and `bus`; terms: the bus's terms as LogupBuilder.term keywords in place of `bus_terms()` (p2_tree_tied.py gives
+    both); without them this is P2-TREE word for word."""
     code = lambda c, back=0: b.get(GROUP_CODE, c, back)
     dat = lambda c, back=0: b.get(GROUP_DATA, c, back)
     out = lambda i: b.get_global(GLOBAL_OUT, i)
@@ -142,8 +151,13 @@ def build_p2_tree() -> Tuple[np.ndarray, np.ndarray]:
     chain = gated(b, chain, code(C_LAST_TOP), [b.sub(ident, one), up] + [b.sub(So(j), out(j)) for j in range(8)] + [b.sub(Sn(j), out(8 + j)) for j in range(8)])
     family("root", start)
 
+    if after_root is not None:
+        start = len(b.steps)
+        chain = after_root[1](b, chain)
+        family(after_root[0], start)
+
     # the bus: three terms per tag, one accum column per tag
-    for term in bus_terms():
+    for term in (bus_terms() if terms is None else terms):
         b.term(**term)
     start = len(b.steps)
     chain = b.arguments(chain, first, body, code(C_LAST))
@@ -152,19 +166,19 @@ def build_p2_tree() -> Tuple[np.ndarray, np.ndarray]:
     start = len(b.steps)
     chain = p2_blocks.sanity(b, chain, active, first, body)
     family("sanity", start)
-    FAMILIES[:] = families
-    return b.finish_all(chain)
+    return b.finish_all(chain), families
 
 
-def bus_terms() -> List[dict]:
-    """the 18 terms as LogupBuilder.term keywords: per tag 1 .. 6 the producer, the left consumer, the right consumer"""
+def bus_terms(first_tag: int = 1) -> List[dict]:
+    """the 18 terms as LogupBuilder.term keywords: per tag first_tag .. first_tag + 5 (P2-TREE: 1 .. 6) the producer, the left
+    consumer, the right consumer"""
     words = lambda lo_j: [D_SO + lo_j + j for j in range(8)] + [D_SN + lo_j + j for j in range(8)]      # X = old ‖ new of one digest pair
     terms = []
     for k in range(6):
         cut = slice(3 * k, min(3 * k + 3, 16))
         for sign, sel, mult, key, xs in ((-1, C_OUT_ROW, D_UP, D_ID, words(0)), (1, C_IN_ROW, D_DL, D_IDL, words(0)), (1, C_IN_ROW, D_DR, D_IDR, words(8))):
             terms.append(dict(col=k, tuple_cols=[(GROUP_DATA, key)] + [(GROUP_DATA, c) for c in xs[cut]], sign=sign, sel=sel,
-                              mult=(GROUP_DATA, mult), tag=k + 1))
+                              mult=(GROUP_DATA, mult), tag=first_tag + k))
     return terms
 
 

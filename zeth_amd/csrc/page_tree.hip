@@ -15,7 +15,7 @@
 // KERNELS.  k_tree_check: ONE workgroup; k_page_check's refusals over the whole table, a part that splits a pair of leaves, the part's
 // node and pair counts (LDS sums, no atomics).  Every other kernel returns at once when the record holds a refusal, so no address at
 // or past W ever indexes `nodes_*` and no slot past B is written.  k_tree_edges: one wave, lane 0 the old chain, lane 1 the new one.
-// k_tree_place: ONE workgroup, one lane per update, 256 at a time: the slot list (p2_tree.py slot order) by two block scans with a
+// k_tree_words (P2-TREE-tied only): one lane per (row, word column).  k_tree_place: ONE workgroup, one lane per update, 256 at a time: the slot list (p2_tree.py slot order) by two block scans with a
 // carry.  k_tree_blocks: one lane per (slot, side), the literal round loop of k_p2join_blocks.  k_tree_book: one lane per (row,
 // bookkeeping column).  The tail rows are k_rows_tail's (circuit.hip, p2_rows_tail).  One writer per cell (of the record and the slot list
 // too), one read-back of the record at the end.  The plan of the parts, on the host (zkh_page_tree_plan) and over the table where it
@@ -30,11 +30,18 @@ using namespace zkh;
 namespace {
 
 constexpr uint32_t PT_KIND = 7, PT_WC = 41, PT_WD = 106, PT_WA = 24, PT_OUT = 18, PT_MIN_H = 2, PT_MAX_H = 27, PT_GAP_BITS = 29;
-constexpr PageShape TREE = {"P2-TREE", PT_KIND, PT_WC, PT_WD, PT_WA, PT_OUT, PT_MAX_H, ""};     // p2_rows.h
+constexpr PageShape TREE = {"P2-TREE", PT_KIND, PT_WC, PT_WD, PT_WA, PT_OUT, PT_MAX_H, ""},     // p2_rows.h
+                    // P2-TREE-tied (p2_tree_tied.py): P2-TREE's code group and data columns 0 .. 105 column for column, then ch[16] and wa[16]; its
+                    // out is P2-TREE's 18 words ‖ base ‖ alpha ‖ beta ‖ F, of which the generator writes the 18
+                    TREE_TIED = {"P2-TREE-tied", 9, PT_WC, PT_WD + 2 * 16, 48, 31, PT_MAX_H, ""};
+// the shape both P2-TREE calls serve: the circuit's own kind decides
+inline const PageShape& tree_shape(const zkh_circuit* c) { return c && c->kind == TREE_TIED.kind ? TREE_TIED : TREE; }
 // code columns (p2_tree.py C_*)
 enum : uint32_t { TC_LIN = 3, TC_FULLR, TC_PARTR, TC_LF, TC_LP, TC_IN_ROW, TC_OUT_ROW, TC_BLOCK_FIRST, TC_CARRY, TC_LAST_TOP, TC_GSEL, TC_GPOW, TC_GEND, TC_RC, TC_LAST = 40 };
 // data columns (p2_tree.py D_*)
 enum : uint32_t { TD_SO = 0, TD_QO = 24, TD_SN = 48, TD_QN = 72, TD_ID = 96, TD_IDL, TD_IDR, TD_LEAF, TD_UP, TD_DL, TD_DR, TD_LO, TD_GBIT, TD_GACC };
+// P2-TREE-tied's word columns (p2_tree_tied.py D_CH, D_WA): 16 each, behind P2-TREE's
+enum : uint32_t { TD_CH = 106, TD_WA = 122, PT_PAIR_WORDS = 16 };
 // the record: k_page_check's refusal (row, its address, the one before), the row at which the part splits a pair of leaves, the part's
 // nodes (saturated) and pairs, lo and hi as the trace holds them, whether anything is refused, both roots, both edge chains (h digests
 // each: step t's is the node of layer t + 1)
@@ -294,6 +301,23 @@ __global__ __launch_bounds__(PT_THREADS) void k_tree_book(uint32_t* __restrict__
     data[(size_t)col * n + r] = v;
 }
 
+// P2-TREE-tied only.  grid (ceil(31 B / 256), 32): the word columns ch[16] ‖ wa[16] of the rows of the blocks, stores coalesced along the
+// rows, one writer per cell.  Only the input row of a pair block holds anything: wa[j] = the address 16 (id - 2^(h-1)) + j of word j,
+// ch[j] = whether the part touches it.  Every other lane (30 rows in 31, and the blocks that are no pair blocks) stores its zero on a
+// path of its own that never enters the binary search; which side of that branch a wave runs first is the compiler's choice, and the
+// kernel is right either way.  Measured (M28): 0.11 ms for the 32 columns at po2 20.
+__global__ __launch_bounds__(PT_THREADS) void k_tree_words(uint32_t* __restrict__ data, uint32_t n, uint32_t h, uint32_t B, const uint32_t* __restrict__ ids,
+                                                           const uint32_t* __restrict__ table, uint32_t first, uint32_t count, const uint32_t* __restrict__ rec) {
+    const uint32_t r = blockIdx.x * PT_THREADS + threadIdx.x, y = blockIdx.y, rows = PJ_BLOCK * B;
+    if (r >= rows || rec[TR_REFUSED]) return;
+    uint32_t* cell = data + (size_t)(TD_CH + y) * n + r;
+    const uint32_t slot = r / PJ_BLOCK, half = 1u << (h - 1);
+    const uint32_t id = r % PJ_BLOCK == 0 ? ids[slot] : 0;                 // only an input row asks for its block's id
+    if (id < half) { *cell = 0; return; }
+    const uint32_t a = ((id - half) << 4) + (y & (PT_PAIR_WORDS - 1));     // id < 2^27: below 2^31
+    *cell = y >= PT_PAIR_WORDS ? pj_encode(a) : (part_touches(table, first, count, a, a + 1) ? R1 : 0);
+}
+
 // ---- THE PLAN ON THE DEVICE (zkh_page_tree_plan_device; DESIGN.md "THE PLAN AS A SCAN").  Row i costs c_i = bit_length(q_i xor q_{i-1})
 // for the pair indices q = a >> 4 (c_0 = 0; 0 inside a pair), S_i = c_0 + .. + c_i, and the part that starts at row f ends before the first
 // row i with S_i > S_f + B - h.  S_i = base[i / 256] + local[i]: k_plan_costs leaves the locals and every workgroup's sum, k_plan_scan
@@ -413,7 +437,7 @@ const char* tree_image_shape(const char* who, size_t po2, size_t zk_cycles, size
 extern "C" const char* zkh_page_tree_code(zkh_ctx* ctx, const zkh_circuit* c, size_t po2, size_t zk_cycles, zkh_buf* code) {
     const char* who = "page_tree_code";
     ZKH_REQUIRE(ctx && c && code, "%s: null argument", who);
-    ZKH_TRY(page_circuit_shape(who, TREE, c, po2, zk_cycles));
+    ZKH_TRY(page_circuit_shape(who, tree_shape(c), c, po2, zk_cycles));
     const size_t n = (size_t)1 << po2;
     ZKH_REQUIRE(code->len == (size_t)PT_WC * n, "%s: buffer shape mismatch", who);
     const uint32_t A = (uint32_t)(n - zk_cycles), B = A / PJ_BLOCK;
@@ -522,7 +546,8 @@ extern "C" const char* zkh_page_tree_witgen(zkh_ctx* ctx, const zkh_circuit* c, 
     const char* who = "page_tree_witgen";
     uint32_t h, B;
     PageOpen o;
-    ZKH_TRY(page_open(who, TREE, ctx, c, po2, zk_cycles, code, proof, proof_words, nodes_before, nodes_after, data, out, noise_key,
+    const PageShape& sh = tree_shape(c);
+    ZKH_TRY(page_open(who, sh, ctx, c, po2, zk_cycles, code, proof, proof_words, nodes_before, nodes_after, data, out, noise_key,
                       [&](size_t W) { return tree_image_shape(who, po2, zk_cycles, W, &h, &B); }, &o));
     const size_t n = o.n, L = o.L;
     const uint32_t W = o.W, D = o.D, *table = o.table;
@@ -557,14 +582,20 @@ extern "C" const char* zkh_page_tree_witgen(zkh_ctx* ctx, const zkh_circuit* c, 
         ZKH_TRY(last_launch_error("tree_blocks"));
     }
     {
-        ProfScope prof(ctx, "tree_book", 4.0 * (PT_WD - TD_ID) * rows + 4.0 * PT_WD * (n - rows));
+        ProfScope prof(ctx, "tree_book", 4.0 * (PT_WD - TD_ID) * rows + 4.0 * sh.wd * (n - rows));
         k_tree_book<<<dim3((rows + PT_THREADS - 1) / PT_THREADS, PT_WD - TD_ID), PT_THREADS, 0, ctx->stream>>>(data->ptr(), (uint32_t)n, h, B, ids->ptr(), table, first,
                                                                                                                count, rec->ptr());
         ZKH_TRY(last_launch_error("tree_book"));
         if (rows < n) {
-            p2_rows_tail(ctx, data, PT_WD, n, A, rows, nk);
+            p2_rows_tail(ctx, data, sh.wd, n, A, rows, nk);
             ZKH_TRY(last_launch_error("page_tail"));
         }
+    }
+    if (sh.wd > PT_WD) {                                // P2-TREE-tied: the 32 word columns
+        ProfScope prof(ctx, "tree_words", 4.0 * (sh.wd - PT_WD) * rows);
+        k_tree_words<<<dim3((rows + PT_THREADS - 1) / PT_THREADS, sh.wd - PT_WD), PT_THREADS, 0, ctx->stream>>>(data->ptr(), (uint32_t)n, h, B, ids->ptr(), table, first,
+                                                                                                                count, rec->ptr());
+        ZKH_TRY(last_launch_error("tree_words"));
     }
     uint32_t r[TR_ROOTS + 16];
     ZKH_TRY(zkh_read(ctx, rec, r, 0, TR_ROOTS + 16));

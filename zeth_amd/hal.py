@@ -1081,8 +1081,9 @@ class HipHal:
         return out
 
     def page_tree_code(self, circuit: Circuit, po2: int, zk_cycles: int, code: Optional[Buffer] = None) -> Buffer:
-        """the code group of P2-TREE (circuits/p2_tree.py) for (po2, zk_cycles): it does not depend on the image (zkh_page_tree_code; the
-        host twin: p2_tree.reference_tree_code).  code: a Buffer of 41 x 2^po2 words to write (default: a new one)"""
+        """the code group of P2-TREE (circuits/p2_tree.py) and of P2-TREE-tied (circuits/p2_tree_tied.py: the same words) for (po2,
+        zk_cycles): it does not depend on the image (zkh_page_tree_code; the host twin: p2_tree.reference_tree_code).  code: a Buffer of
+        41 x 2^po2 words to write (default: a new one)"""
         if code is None:
             code = self.alloc_elem("code", int(circuit.desc[4]) << po2)
         _check(_lib.zkh_page_tree_code(self.ctx, circuit.h, po2, zk_cycles, code.h))
@@ -1114,7 +1115,8 @@ class HipHal:
         """the data group of P2-TREE for the part [first, first + count) of the page-out a ZKU1 proof describes (zkh_page_tree_witgen; the
         host twin: p2_tree.reference_tree_part) -> the out globals, root_before ‖ root_after ‖ lo ‖ hi (18 words: lo and hi bound the
         heap ids of the part's pair blocks, p2_tree.decode).  The other operands are page_ordered_witgen's, `data` of 106 x 2^po2
-        words, both trees the whole page-out's; the part is one of page_tree_plan's.  Raises HalError with one message per cause
+        words, both trees the whole page-out's; the part is one of page_tree_plan's.  A P2-TREE-tied circuit (kind 9) gets its 138
+        columns (the host twin: p2_tree_tied.reference_tree_tied_part) and the same 18 words.  Raises HalError with one message per cause
         (include/zkhal.h "P2-TREE"); `data` is unspecified then"""
         out = np.zeros(2 * DIGEST_WORDS + 2, dtype=np.uint32)
         _k, kp = _key_ptr(noise_seed)

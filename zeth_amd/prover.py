@@ -461,7 +461,13 @@ class SegmentProver:
         there, and check=True names the key.  The other operands are seal_page_out_parts'; the control root does not depend on the
         image's size.  plan="device" plans where the table lies (zkh_page_tree_plan_device over (proof, 5 + h, D)): only the header is
         read back; the parts, and so the receipts, are the same.  -> the receipts, in the order of the parts."""
-        who, where = "seal_page_out_tree", plan
+        who = "seal_page_out_tree"
+        return self._seal_page_chain(who, segs, proof, proof_words, nodes_before, nodes_after, check, self._open_tree_chain(who, plan, proof_words),
+                                     self.hal.page_tree_witgen, lambda seg, code, data: self.args_accumulate(seg, code, data, check=check))
+
+    def _open_tree_chain(self, who: str, where: str, proof_words: int):
+        """open_chain of the circuits that lay out one block per dirty node (P2-TREE, P2-TREE-tied): the plan is zkh_page_tree_plan's, made
+        on the "host" or on the "device" (`where`), a part's operands its (first, count)"""
         if where not in ("host", "device"):
             raise _hal.HalError(f'{who}: plan="{where}" (the plan is made on the "host" or on the "device")')
 
@@ -480,9 +486,7 @@ class SegmentProver:
             fit(plan, D, f"{((1 << po2) - zk) // 31} block slots")
             return self.hal.page_tree_code(self.circuit, po2, zk), plan
 
-        return self._seal_page_chain(who, segs, proof, proof_words, nodes_before, nodes_after, check, open_chain, self.hal.page_tree_witgen,
-                                     lambda seg, code, data: self.args_accumulate(seg, code, data, check=check))
-
+        return open_chain
 
     def prove_segment(self, seg: Segment) -> SegmentReceipt:
         code, data, out = self.witgen(seg)
@@ -603,7 +607,30 @@ def seal_tied(seg_prover: SegmentProver, seg: Segment, code, data, out_prefix, p
          accumulate_open, out = prefix ‖ challenge ‖ total, zkh_prove_begin, with `check` check_witness, zkh_prove_finish.
     Every receipt carries its code group's root as `control_root`."""
     from .circuits import p2_page_tied as pt
-    who = "seal_tied"
+    return _seal_tied_group("seal_tied", seg_prover, seg, code, data, out_prefix, page_prover, page_segs, proof, proof_words, nodes_before, nodes_after, check,
+                            check_table, page_prover._open_path_chain(seg_prover.hal.page_ordered_code), seg_prover.hal.page_ordered_witgen,
+                            lambda words, _h: words[:pt.PREFIX_WORDS])
+
+
+def seal_tied_tree(seg_prover: SegmentProver, seg: Segment, code, data, out_prefix, page_prover: SegmentProver, page_segs, proof, proof_words: int,
+                   nodes_before, nodes_after, check: bool = False, check_table: bool = True, plan: str = "host"):
+    """`seal_tied` with P2-TREE-tied parts (circuits/p2_tree_tied.py): the page-out side of the group is one block per DIRTY NODE, not one
+    path per word.  page_prover: a prover of P2-TREE-tied with p2_tree_tied.arguments(); the plan is seal_page_out_tree's, made on the
+    "host" or on the "device" (`plan`); every other operand, both passes and the fingerprint check between them are seal_tied's.  A part's
+    out = the witness call's 18 words ‖ p2_tree_tied.out_base(h) ‖ the challenge ‖ its open total.  -> (the segment's receipt, [the parts'
+    receipts]), for `verify_tied_tree`."""
+    from .circuits import p2_tree_tied as tt
+    who = "seal_tied_tree"
+    return _seal_tied_group(who, seg_prover, seg, code, data, out_prefix, page_prover, page_segs, proof, proof_words, nodes_before, nodes_after, check,
+                            check_table, page_prover._open_tree_chain(who, plan, proof_words), seg_prover.hal.page_tree_witgen,
+                            lambda words, h: np.concatenate([words[:tt.PREFIX_WORDS], [tt.out_base(h)]]).astype(np.uint32))
+
+
+def _seal_tied_group(who: str, seg_prover: SegmentProver, seg: Segment, code, data, out_prefix, page_prover: SegmentProver, page_segs, proof, proof_words: int,
+                     nodes_before, nodes_after, check: bool, check_table: bool, open_chain, witgen, part_prefix):
+    """The two passes of `seal_tied` and `seal_tied_tree`.  open_chain(proof, po2, zk, fit) -> (the page-out's code group, the plan: per
+    part the witness call's own operands), as _seal_page_chain takes it; witgen: the hal's witness call of the page-out circuit;
+    part_prefix(the words it returns, h) -> the part's `out` words before alpha."""
     hal = seg_prover.hal
     for name, p in (("segment", seg_prover), ("page-out", page_prover)):
         if p.circuit.open_bus() is None:
@@ -621,13 +648,13 @@ def seal_tied(seg_prover: SegmentProver, seg: Segment, code, data, out_prefix, p
         if len(page_segs) != len(plan):
             raise _hal.HalError(f"{who}: {len(page_segs)} segments, but a table of {D} rows takes {len(plan)} parts of {room} at po2 {po2}")
 
-    page_code, plan = page_prover._open_path_chain(hal.page_ordered_code)(proof, po2, zk, fit)
+    page_code, plan = open_chain(proof, po2, zk, fit)
     head = proof.slice(0, 5).to_vec()
-    rows, table_at = int(head[2]), 5 + int(head[4])
+    rows, h, table_at = int(head[2]), int(head[4]), 5 + int(head[4])
     page_data = hal.alloc_elem("data", page_prover.group_sizes()[2] << po2)
 
     def part_witness(s, part):
-        return hal.page_ordered_witgen(page_prover.circuit, po2, zk, page_code, proof, proof_words, nodes_before, nodes_after, *part, page_data, s.noise_seed)
+        return witgen(page_prover.circuit, po2, zk, page_code, proof, proof_words, nodes_before, nodes_after, *part, page_data, s.noise_seed)
 
     # pass one: the data roots, the segment's first
     roots = [seg_prover.data_root(data, seg.po2)]
@@ -657,8 +684,8 @@ def seal_tied(seg_prover: SegmentProver, seg: Segment, code, data, out_prefix, p
     page_root = page_prover.code_root(page_code, po2)
     receipts = []
     for s, part in zip(page_segs, plan):
-        prefix = part_witness(s, part)
-        accum, _total, out, _ = open_seal(page_prover, s, page_code, page_data, prefix[:pt.PREFIX_WORDS], None)
+        prefix = part_prefix(part_witness(s, part), h)
+        accum, _total, out, _ = open_seal(page_prover, s, page_code, page_data, prefix, None)
         receipt = page_prover.seal_with_accum(s, page_code, page_data, out, lambda _mix, accum=accum: accum, check=check)
         receipt.control_root = page_root.copy()
         receipts.append(receipt)
@@ -676,15 +703,28 @@ def verify_tied(seg_receipt, seg_circuit, seg_control_root, part_receipts, page_
     from .circuits import p2_page_tied as pt
     who = "verify_tied"
     part_receipts = list(part_receipts)
-    seg_hc = _hal.HostCircuit(np.asarray(seg_circuit, dtype=np.uint32))
-    seg_out_size = int(np.asarray(seg_circuit, dtype=np.uint32)[7])
-    if seg_out_size < TIE_WORDS:
-        raise _hal.HalError(f"{who}: the segment circuit has {seg_out_size} out words: no room for alpha, beta and the total")
-    seg_hc.verify_segment(seg_receipt.seal, seg_control_root)
+    seg_hc, seg_out_size = _verified_tied_segment(who, seg_receipt, seg_circuit, seg_control_root)
     linked = link_page_parts(who, _verified_parts(part_receipts, pt.p2_page_tied_circuit, page_control_root, pt.decode), root_before,
                              first_lo=(0, "0: addresses below it are not covered"))
     page_hc = _hal.HostCircuit(pt.p2_page_tied_circuit())
-    seals = [("the segment", seg_hc, seg_receipt.seal, seg_out_size)] + [(f"part {p}", page_hc, r.seal, pt.OUT_WORDS) for p, r in enumerate(part_receipts)]
+    _check_tied_totals(who, [("the segment", seg_hc, seg_receipt.seal, seg_out_size)] + [(f"part {p}", page_hc, r.seal, pt.OUT_WORDS) for p, r in enumerate(part_receipts)])
+    return linked
+
+
+def _verified_tied_segment(who: str, seg_receipt, seg_circuit, seg_control_root):
+    """the segment's seal of a tied group, verified against its control root -> (its HostCircuit, its `out` words)"""
+    desc = np.asarray(seg_circuit, dtype=np.uint32)
+    seg_hc, seg_out_size = _hal.HostCircuit(desc), int(desc[7])
+    if seg_out_size < TIE_WORDS:
+        raise _hal.HalError(f"{who}: the segment circuit has {seg_out_size} out words: no room for alpha, beta and the total")
+    seg_hc.verify_segment(seg_receipt.seal, seg_control_root)
+    return seg_hc, seg_out_size
+
+
+def _check_tied_totals(who: str, seals) -> None:
+    """The challenge and total checks of a tied group whose seals are verified.  seals: (name, HostCircuit, seal, out words) per seal, the
+    segment's first.  Every seal must state the challenge `hal.tie_challenge` gives for the data roots read out of the seals in that
+    order, and the totals F must add up to zero in Fp4.  Raises HalError, one line per cause."""
     want = _hal.tie_challenge(np.concatenate([hc.seal_data_root(seal) for _, hc, seal, _ in seals]))
     total = np.zeros(4, dtype=np.uint64)
     for name, _, seal, out_size in seals[1:] + seals[:1]:                     # a part that was swapped in is named before the segment
@@ -695,6 +735,39 @@ def verify_tied(seg_receipt, seg_circuit, seg_control_root, part_receipts, page_
     if total.any():
         raise _hal.HalError(f"{who}: the totals do not cancel: the segment's F plus the parts' is {_fmt_words(total)}, not zero: the parts' rows are not "
                             f"the segment's page table")
+
+
+def link_tied_tree_chain(outs, h: int, root_before=None) -> Tuple[np.ndarray, np.ndarray, int]:
+    """What verify_tied_tree checks of the parts' `out` words (31 each) besides the group's challenge and totals -> (root_before, root_after,
+    hi): `link_page_tree_chain` on their first 18 words, then every part's out[18] must be p2_tree_tied.out_base(h), the word that turns a
+    pair block's id into its addresses.  Raises HalError, one message per cause."""
+    from .circuits import p2_tree_tied as tt
+    outs = [np.asarray(out, dtype=np.uint32) for out in outs]
+    linked = link_page_tree_chain([out[:tt.PREFIX_WORDS] for out in outs], h, root_before)
+    for p, out in enumerate(outs):
+        if int(out[tt.OUT_BASE]) != tt.out_base(h):
+            raise _hal.HalError(f"verify_tied_tree: part {p}: base {tt.decode(out[tt.OUT_BASE])} is not {1 << (h + 3)} = 16 * 2^{h - 1}, sixteen times the id of "
+                                f"the first pair of leaves of a tree of height {h}")
+    return linked
+
+
+def verify_tied_tree(seg_receipt, seg_circuit, seg_control_root, part_receipts, page_control_root, h: int, root_before=None) -> Tuple[np.ndarray, np.ndarray, int]:
+    """Verify a tied group whose page-out side is P2-TREE-tied's (`seal_tied_tree`), HOST ONLY -> (root_before, root_after, hi): the page
+    table of the segment `seg_receipt` seals, applied to the image under root_before, leaves root_after; hi is one more than the id of
+    the last pair of leaves it touches.  The verifier is told h, the height of the image's tree.  Every seal verifies against its
+    control root; the parts link as P2-TREE's do and state base = 16 * 2^(h-1) (`link_tied_tree_chain`); then `verify_tied`'s checks of
+    the challenge and of the totals.  Raises HalError, one line per cause."""
+    from .circuits import p2_tree_tied as tt
+    who = "verify_tied_tree"
+    part_receipts = list(part_receipts)
+    seg_hc, seg_out_size = _verified_tied_segment(who, seg_receipt, seg_circuit, seg_control_root)
+    if not part_receipts:
+        raise _hal.HalError(f"{who}: no receipt (a page-out of no rows still has one part)")
+    page_hc = _hal.HostCircuit(tt.p2_tree_tied_circuit())
+    for r in part_receipts:
+        page_hc.verify_segment(r.seal, page_control_root)
+    linked = link_tied_tree_chain([r.seal[:tt.OUT_WORDS] for r in part_receipts], h, root_before)
+    _check_tied_totals(who, [("the segment", seg_hc, seg_receipt.seal, seg_out_size)] + [(f"part {p}", page_hc, r.seal, tt.OUT_WORDS) for p, r in enumerate(part_receipts)])
     return linked
 
 
