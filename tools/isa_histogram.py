@@ -6,6 +6,7 @@ modelled issue cycles, against the multiply floor — the evidence behind "Posei
     python tools/isa_histogram.py --csrc <another checkout>/zeth_amd/csrc      (the same count for another tree's hash.hip)
     python tools/isa_histogram.py --kernel fold                                 (k_hash_fold: one permutation, no block loop)
     python tools/isa_histogram.py --grouped                                     (the instantiation with the grouped partial rounds)
+    python tools/isa_histogram.py --loads                                       (both kernels: registers and the table loads only)
 
 Compiles zeth_amd/csrc/hash.hip for gfx950 with the build's flags (`-S`, device only), takes the first copy of the block
 loop of k_hash_rows (interior blocks of the sponge: 16 absorbed columns, one permutation), finds its inner loops from the
@@ -20,6 +21,9 @@ and the alternative that the last block of a sponge takes count zero.
 Issue cycles per wave64 instruction from tools/ubench_valu.hip (profiles/r01_ubench_valu.txt): 32-bit multiplies,
 v_mad_*64*, fp64 and v_cvt_f64 4.0; plain add / sub / logic / shift / mov 2.5 (measured 2.46); v_min / v_add3 / v_lshl_add 4.0;
 compare-select pairs 2.1 + 2.1.
+Table loads (table_loads): every scalar, global, flat or LDS load of the permutation that reads a constant table, by kind, and for each
+the number of VALU + MFMA instructions issued between the load and the s_waitcnt that covers it.  A wait that directly follows its
+load (distance 0) exposes a whole cache round trip to the in-order wave.
 """
 from __future__ import annotations
 
@@ -145,18 +149,105 @@ def path_weights(body, labels, outer, merged, trips):
     return weight
 
 
-def main():
+def compile_asm(csrc=None):
+    """hash.hip of `csrc` (default: this tree's) as gfx950 assembly lines, with the build's flags"""
     sys.path.insert(0, ROOT)
     from zeth_amd import build as B
-    csrc = sys.argv[sys.argv.index("--csrc") + 1] if "--csrc" in sys.argv else B.CSRC
+    csrc = csrc or B.CSRC
     with tempfile.TemporaryDirectory() as tmp:
         out = os.path.join(tmp, "hash.s")
-        cmd = [B.HIPCC, *B.FLAGS, *B.EXTRA_FLAGS.get("hash.hip", []), "--cuda-device-only", "-S", os.path.join(csrc, "hash.hip"), "-o", out]
+        cmd = [B.HIPCC, *B.FLAGS, *B.EXTRA_FLAGS.get("hash.hip", []), "-I", B.CSRC, "--cuda-device-only", "-S", os.path.join(csrc, "hash.hip"), "-o", out]
         subprocess.run(cmd, check=True, capture_output=True)
-        lines = open(out).read().split("\n")
-    kernel = sys.argv[sys.argv.index("--kernel") + 1] if "--kernel" in sys.argv else "rows"
+        return open(out).read().split("\n")
+
+
+VM_OPS = ("global_", "flat_", "scratch_", "buffer_")
+LGKM_OPS = ("s_load", "s_buffer_load", "ds_", "flat_")
+
+
+def load_kind(op):
+    if op.startswith(("s_load", "s_buffer_load")):
+        return "scalar"
+    if op.startswith("global_load"):
+        return "global"
+    if op.startswith("flat_load"):
+        return "flat"
+    if op.startswith(("ds_read", "ds_load")):
+        return "LDS"
+    return None
+
+
+def table_loads(body, lo, hi, loops, first_loop):
+    """The table loads among body[lo..hi] as (line, kind, distance): distance = VALU + MFMA instructions between the load and the wait
+    that covers it, None if no wait in the region does.  Not table loads: the kernel's arguments (scalar loads off s[0:1] ahead of the
+    first wait) and its data, which are the vector loads ahead of the first full-round loop (columns, child digests).
+    Counters as the hardware keeps them: vector memory returns in order (vmcnt(N) covers a load once N others were issued behind it);
+    scalar loads return out of order (only lgkmcnt(0) covers them); LDS in order unless a scalar load is in flight beside it; a flat
+    load needs both.  A load in a loop body may be waited for at the top of the next trip: the shorter of the two ways counts."""
+    def opcode(i):
+        l = body[i]
+        if not l.startswith("\t") or not l.strip() or l.strip().startswith((".", ";")):
+            return None
+        return l.strip().split()[0]
+    def walk(start, kind, path):
+        n_vm = n_lgkm = n_smem = dist = 0
+        need_vm, need_lgkm = kind in ("global", "flat"), kind in ("scalar", "LDS", "flat")
+        for i in path:
+            op = opcode(i)
+            if op is None:
+                continue
+            if op == "s_waitcnt":
+                vm, lg = re.search(r"vmcnt\((\d+)\)", body[i]), re.search(r"lgkmcnt\((\d+)\)", body[i])
+                if need_vm and vm and n_vm >= int(vm.group(1)):
+                    need_vm = False
+                if need_lgkm and lg and (int(lg.group(1)) == 0 or (kind == "LDS" and not n_smem and n_lgkm >= int(lg.group(1)))):
+                    need_lgkm = False
+                if not need_vm and not need_lgkm:
+                    return dist
+                continue
+            if op.startswith("v_"):
+                dist += 1
+            if op.startswith(VM_OPS):
+                n_vm += 1
+            if op.startswith(LGKM_OPS):
+                n_lgkm += 1
+                n_smem += op.startswith("s_")
+        return None
+    found, first_wait = [], next((i for i in range(lo, hi + 1) if opcode(i) == "s_waitcnt"), hi)
+    for i in range(lo, hi + 1):
+        op = opcode(i)
+        kind = load_kind(op) if op else None
+        if kind is None:
+            continue
+        if kind == "scalar" and i < first_wait and re.search(r",\s*s\[0:1\],", body[i]):
+            continue                                    # a kernel argument
+        if kind in ("global", "flat") and i < first_loop:
+            continue                                    # the kernel's data
+        ways = [walk(i, kind, range(i + 1, hi + 1))]
+        for a, b in loops:
+            if a <= i <= b:
+                ways.append(walk(i, kind, list(range(i + 1, b + 1)) + list(range(a, i))))
+        ways = [w for w in ways if w is not None]
+        found.append((i, kind, min(ways) if ways else None))
+    return found
+
+
+def resources(lines, start):
+    """registers, scratch and occupancy of the kernel whose label is lines[start], from the compiler's own summary behind it"""
+    res = {}
+    for l in lines[start:]:
+        m = re.match(r";\s*(NumVgprs|NumAgprs|TotalNumSgprs|ScratchSize|Occupancy|LDSByteSize):\s*(\d+)", l)
+        if m:
+            res[m.group(1)] = int(m.group(2))
+        if "Occupancy" in res and "ScratchSize" in res and "NumVgprs" in res and "TotalNumSgprs" in res:
+            break
+    return res
+
+
+def analyze(lines, kernel="rows", grouped=False):
+    """Everything the report prints, as a dict (tests/test_hash_table_loads_static.py reads it)."""
     heads = [i for i, l in enumerate(lines) if re.match(r"^_ZN\S*k_hash_%s(I\S*Ev|E)\S*:" % kernel, l)]
-    want = "ILb0E" if "--grouped" in sys.argv else "ILb1E"           # templated on the linear partial rounds where that path exists
+    want = "ILb0E" if grouped else "ILb1E"           # templated on the linear partial rounds where that path exists
     start = next((i for i in heads if want in lines[i]), heads[0])
     end = next(i for i in range(start, len(lines)) if lines[i].startswith(".Lfunc_end"))
     body = lines[start + 1:end]
@@ -170,7 +261,8 @@ def main():
     # first loop nest = the block loop: from its header to the last branch back to that header (blocks the compiler placed
     # after that latch belong to the tail block's predicated loads and are not part of a steady-state block)
     if kernel == "rows":
-        outer = (back[0][0], max(b[1] for b in back if b[0] == back[0][0]))
+        head = max(back, key=lambda b: b[1] - b[0])[0]     # the widest loop nest (a short staging loop may come first)
+        outer = (head, max(b[1] for b in back if b[0] == head))
     else:                                               # no block loop: the whole kernel is one permutation
         outer = (0, len(body) - 1)
     inner = [b for b in back if outer[0] < b[0] and b[1] < outer[1]]
@@ -208,6 +300,47 @@ def main():
             other[op.split("_")[0] + "_" + op.split("_")[1] if "_" in op else op] += weight[i]
     total = sum(hist.values())
     tot_cyc = sum(cycles(op) * n for op, n in hist.items())
+    loads = table_loads(body, outer[0], outer[1], merged, merged[0][0] if merged else outer[0])
+    return dict(name=lines[start].split(":")[0], kernel=kernel, body=body, outer=outer, merged=merged, kinds=kinds, trips=trips, peeled=peeled,
+                weight=weight, hist=hist, static=static, other=other, mfma=mfma, total=total, tot_cyc=tot_cyc, loads=loads,
+                resources=resources(lines, start))
+
+
+def loads_summary(d):
+    """by kind: (count, [distances]); and the count of loads that no wait in the region covers"""
+    kinds = {k: [x[2] for x in d["loads"] if x[1] == k and x[2] is not None] for k in ("scalar", "global", "flat", "LDS")}
+    return kinds, sum(1 for x in d["loads"] if x[2] is None)
+
+
+def print_loads(d):
+    kinds, unwaited = loads_summary(d)
+    r = d["resources"]
+    print(f"# {d['name']}")
+    print(f"#   VGPRs {r.get('NumVgprs')}, AGPRs {r.get('NumAgprs')}, SGPRs {r.get('TotalNumSgprs')}, scratch {r.get('ScratchSize')} bytes, occupancy {r.get('Occupancy')} waves per SIMD;"
+          f" VALU per wave-permutation {d['total']:.0f}, MFMA {sum(d['mfma'].values()):.0f}")
+    print("#   table loads (static), and the VALU + MFMA instructions between each load and the wait that covers it:")
+    print(f"#   {'kind':8s} {'loads':>6s} {'min':>6s} {'median':>7s} {'zero':>6s}")
+    for k, ds in kinds.items():
+        n = sum(1 for x in d["loads"] if x[1] == k)
+        sd = sorted(ds)
+        print(f"    {k:8s} {n:6d} {(str(sd[0]) if sd else '-'):>6s} {(str(sd[len(sd) // 2]) if sd else '-'):>7s} {sum(1 for x in ds if x == 0):6d}")
+    every = sorted(x for ds in kinds.values() for x in ds)
+    print(f"    {'all':8s} {len(d['loads']):6d} {(str(every[0]) if every else '-'):>6s} {(str(every[len(every) // 2]) if every else '-'):>7s} {sum(1 for x in every if x == 0):6d}"
+          + (f"   ({unwaited} requested and never read in this region)" if unwaited else ""))
+
+
+def main():
+    csrc = sys.argv[sys.argv.index("--csrc") + 1] if "--csrc" in sys.argv else None
+    lines = compile_asm(csrc)
+    if "--loads" in sys.argv:
+        for kernel in ("rows", "fold"):
+            print_loads(analyze(lines, kernel, "--grouped" in sys.argv))
+        return
+    kernel = sys.argv[sys.argv.index("--kernel") + 1] if "--kernel" in sys.argv else "rows"
+    d = analyze(lines, kernel, "--grouped" in sys.argv)
+    body, outer, merged, kinds, trips, peeled, weight = d["body"], d["outer"], d["merged"], d["kinds"], d["trips"], d["peeled"], d["weight"]
+    hist, static, other, mfma, total, tot_cyc, start = d["hist"], d["static"], d["other"], d["mfma"], d["total"], d["tot_cyc"], 0
+    lines = [d["name"] + ":"]
     print(f"# {lines[start].rstrip(':')}")
     print("# k_hash_%s, %s = ONE Poseidon2 permutation per lane (gfx950, hipcc -O3 -enable-misched=0)" %
           (kernel, "steady-state absorb block" if kernel == "rows" else "the whole kernel"))
@@ -255,6 +388,8 @@ def main():
     out_loops = sum(n for op, n in static.items()) - 0
     print("#   inner loops) are ~%d instructions per block (%.1f %%); v_cvt_f64 (3.3 %%) has no cheaper form; nothing else is not a multiply or an M_ext add." %
           (sum(1 for i in range(outer[0], outer[1] + 1) if weight[i] == 1.0 and body[i].startswith("\tv_")), 100.0 * sum(1 for i in range(outer[0], outer[1] + 1) if weight[i] == 1.0 and body[i].startswith("\tv_")) / total))
+    print("#")
+    print_loads(d)
 
 
 if __name__ == "__main__":

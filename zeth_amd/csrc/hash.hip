@@ -42,11 +42,14 @@ __global__ __launch_bounds__(256, 4) void k_hash_rows(uint32_t* __restrict__ out
     const size_t lane_row = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     const bool live = lane_row < rows;
     if (!LINEAR && !live) return;
-    const size_t r = live ? lane_row : rows - 1;
+    // The lane's row as (the workgroup's first row: uniform) + (dr < 256): every address below is a scalar base plus one 32-bit
+    // per-lane offset, so the only per-lane value live across the block loop is one register, not a 64-bit pointer or two.
+    const size_t row0 = (size_t)blockIdx.x * blockDim.x;
+    uint32_t dr = live ? threadIdx.x : (uint32_t)(rows - 1 - row0);
+    asm("" : "+v"(dr));                          // (one value: not threadIdx.x kept beside it for the live lanes' store)
     uint32_t s[CELLS];
 #pragma unroll
     for (int i = 0; i < CELLS; i++) s[i] = 0;
-    const uint32_t* src = matrix + r;
     const uint32_t full = cols / RATE, tail = cols % RATE;
     const uint32_t blocks = full + (tail || cols == 0 ? 1u : 0u);
     // No register double-buffer for the next 16 columns: the partial rounds need the VGPRs (127 with the matrix products'
@@ -56,16 +59,20 @@ __global__ __launch_bounds__(256, 4) void k_hash_rows(uint32_t* __restrict__ out
     // last block the digest, either one in s[16..24) (poseidon2_mix_sponge: a scalar branch around the last eight
     // reductions).  The capacity stays a nearly centred signed word from block to block; only the digest is canonicalised.
     for (uint32_t b = 0; b < blocks; b++) {
-        const uint32_t* bsrc = src + (size_t)b * RATE * rows;
+        const uint32_t* bsrc = matrix + (size_t)b * RATE * rows + row0;
         if (b < full) {
 #pragma unroll
-            for (int i = 0; i < RATE; i++) s[i] = bsrc[(size_t)i * rows];
+            for (int i = 0; i < RATE; i++) s[i] = (bsrc + (size_t)i * rows)[dr];
         } else {
 #pragma unroll
-            for (int i = 0; i < RATE; i++) s[i] = (uint32_t)i < tail ? bsrc[(size_t)i * rows] : 0u;
+            for (int i = 0; i < RATE; i++) s[i] = (uint32_t)i < tail ? (bsrc + (size_t)i * rows)[dr] : 0u;
         }
-        const uint32_t* lin_here = lin;
-        asm volatile("" : "+s"(lin_here));       // the table's 200 scalar words are loaded where they are used, not hoisted out of this loop and spilled
+        // The table's ~230 uniform words are loaded where they are used, not hoisted out of this loop and spilled: an opaque
+        // zero OFFSET makes the address new in every block.  (Laundering the pointer itself loses its address space: every
+        // table word then arrives through a per-lane flat load and lands in a VGPR.)
+        uint32_t lin_off = 0;
+        asm volatile("" : "+s"(lin_off));
+        const uint32_t* __restrict__ lin_here = lin + lin_off;
         if (LINEAR) poseidon2_mix_sponge_linear(s, diag, lin_here, b + 1 == blocks);
         else        poseidon2_mix_sponge(s, rc, diag, b + 1 == blocks);
 #pragma unroll
@@ -74,7 +81,7 @@ __global__ __launch_bounds__(256, 4) void k_hash_rows(uint32_t* __restrict__ out
 #pragma unroll
     for (int i = 0; i < OUT; i++) s[i] = canon((int32_t)s[RATE + i]);
     if (!live) return;
-    uint4* o = (uint4*)(out + r * 8);
+    uint4* o = (uint4*)(out + row0 * 8) + 2 * dr;
     o[0] = make_uint4(s[0], s[1], s[2], s[3]);
     o[1] = make_uint4(s[4], s[5], s[6], s[7]);
 }

@@ -195,6 +195,14 @@ inline bool poseidon2_partial_table(uint32_t* t, const uint32_t* rc_canonical, c
     for (int i = 0; i < 3 * CELLS; i++) t[P2_TAB_EXIT + i] = (uint32_t)center(p2_mulm(t[i], mu));
     return lam[2 * HALF_FULL] == R1;
 }
+// Behind a group of loads whose values are read much later: keeps the request where the source has it.  Left alone the compiler
+// moves such a load down to its first use (and merges a row requested ahead of a loop and inside it into one load at the loop's top),
+// where the wait exposes the whole round trip.
+ZKH_HD void p2_request_here() {
+#if defined(__HIP_DEVICE_COMPILE__)
+    __builtin_amdgcn_sched_barrier(0);
+#endif
+}
 }  // namespace zkh
 #define ZKH_POSEIDON2_H_PARTS
 #include "poseidon2_linear.h"   // the partial rounds as one affine map on the matrix cores (k_hash_rows, k_hash_fold)
@@ -222,6 +230,14 @@ ZKH_HD void poseidon2_mix_core(uint32_t (&s)[CELLS], const uint32_t* __restrict_
     const uint32_t* __restrict__ rcf = diag + P2_TAB_FULL;
     const uint32_t* __restrict__ rcf2 = LINEAR ? lin + LIN_RCF : rcf;          // rows of the second half
     double d[CELLS], c[4];
+    // LINEAR: a full round's constant row is requested one round ahead, right behind the s-boxes that read the row before it (the
+    // same scalar registers: they are dead by then), so the wait at the next round's first s-box finds it there after a whole
+    // M_ext.  The first row is requested before the first M_ext; the fifth round's row is zero (its constants sit in the map).
+    uint32_t k[CELLS];
+    if constexpr (LINEAR) {
+#pragma unroll
+        for (int i = 0; i < CELLS; i++) k[i] = rcf[i];
+    }
 #pragma unroll
     for (int i = 0; i < LIVE; i++) d[i] = (double)(int32_t)s[i];
     m_ext_f64_blocks<LIVE>(d, c);
@@ -229,7 +245,12 @@ ZKH_HD void poseidon2_mix_core(uint32_t (&s)[CELLS], const uint32_t* __restrict_
 #pragma unroll 1
     for (int r = 0; r < HALF_FULL; r++) {
 #pragma unroll
-        for (int i = 0; i < CELLS; i++) d[i] = (double)sbox7_lazy(s[i], rcf[r * CELLS + i]);
+        for (int i = 0; i < CELLS; i++) d[i] = (double)sbox7_lazy(s[i], LINEAR ? k[i] : rcf[r * CELLS + i]);
+        if constexpr (LINEAR) {                                                // (after the fourth round: a row nobody reads)
+#pragma unroll
+            for (int i = 0; i < CELLS; i++) k[i] = rcf[(r + 1) * CELLS + i];
+            p2_request_here();
+        }
         m_ext_f64(s, d);
     }
     if constexpr (LINEAR) {
@@ -321,15 +342,24 @@ ZKH_HD void poseidon2_mix_core(uint32_t (&s)[CELLS], const uint32_t* __restrict_
 #pragma unroll
     for (int i = 1; i < CELLS; i++) s[i] = canon((int32_t)s[i]);
     }
+    if constexpr (LINEAR) {
+#pragma unroll
+        for (int i = 0; i < CELLS; i++) k[i] = 0u;
+    }
 #pragma unroll 1
     for (int r = HALF_FULL; r < 2 * HALF_FULL - 1; r++) {
 #pragma unroll
-        for (int i = 0; i < CELLS; i++) d[i] = (double)sbox7_lazy(s[i], rcf2[r * CELLS + i]);
+        for (int i = 0; i < CELLS; i++) d[i] = (double)sbox7_lazy(s[i], LINEAR ? k[i] : rcf2[r * CELLS + i]);
+        if constexpr (LINEAR) {
+#pragma unroll
+            for (int i = 0; i < CELLS; i++) k[i] = rcf2[(r + 1) * CELLS + i];
+            p2_request_here();
+        }
         m_ext_f64(s, d);
     }
     // F8, peeled: every block product and column sum, but the last add and the reduction only of the cells the caller reads
 #pragma unroll
-    for (int i = 0; i < CELLS; i++) d[i] = (double)sbox7_lazy(s[i], rcf2[(2 * HALF_FULL - 1) * CELLS + i]);
+    for (int i = 0; i < CELLS; i++) d[i] = (double)sbox7_lazy(s[i], LINEAR ? k[i] : rcf2[(2 * HALF_FULL - 1) * CELLS + i]);
     m_ext_f64_blocks<CELLS>(d, c);
     if (SEL && low) m_ext_f64_reduce<CELLS, 0, KEEP_LO, KEEP_N>(s, d, c);
     else            m_ext_f64_reduce<CELLS, KEEP_LO, KEEP_LO, KEEP_N>(s, d, c);

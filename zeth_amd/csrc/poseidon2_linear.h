@@ -81,16 +81,33 @@ ZKH_HD int64_t lin_recombine(int32_t r0, int32_t r1, int32_t r2, int32_t r3, int
 ZKH_HD bool lin_fold_before(int n) { return n == 4; }
 ZKH_HD bool lin_fold_last(int n) { return n >= 2; }
 struct LinStats { int64_t acc = 0, lo = 0, t = 0, out = 0; };      // largest |digit sum|, |lo| or |hi|, |reduced sum|, |output word|
-// round r >= 1: z[r] from row alpha_r's recombined sum t and z[0..r)
-ZKH_HD void lin_chain_round(int r, int64_t t, int32_t (&z)[PARTIAL], const uint32_t* __restrict__ lin, LinStats* st) {
+// row r of beta (r words), requested: the wait is wherever its first word is read (poseidon2.h's p2_request_here keeps the request here)
+ZKH_HD void lin_beta_row(int r, uint32_t (&beta)[LIN_ALPHA], const uint32_t* __restrict__ lin) {
+#pragma unroll
+    for (int j = 0; j < LIN_ALPHA; j++)
+        if (j < r) beta[j] = lin[lin_beta_at(r, j)];
+    p2_request_here();
+}
+// round r >= 1: z[r] from row alpha_r's recombined sum t and z[0..r).  beta[r % 3] holds row r.  Rows 1..3 are requested ahead of the
+// chain (lin_beta_first); round r >= 3 requests row r + 1 behind its first product, into the buffer row r - 2 has left.  Where, and why:
+//   - scalar loads return out of order, so every wait for one is a wait for all of them: a request ahead of the first read of row r
+//     would be waited for together with row r, at once;
+//   - the products of round r + 1 that do not read z[r] issue under round r's reduction and s-box, so row r + 1 is first read right
+//     behind round r's last product: a request there would be waited for at once as well.
+// Between the two lie round r's other r - 1 products.
+ZKH_HD void lin_beta_first(uint32_t (&beta)[3][LIN_ALPHA], const uint32_t* __restrict__ lin) {
+    lin_beta_row(1, beta[1], lin); lin_beta_row(2, beta[2], lin); lin_beta_row(3, beta[0], lin);
+}
+ZKH_HD void lin_chain_round(int r, int64_t t, int32_t (&z)[PARTIAL], uint32_t (&beta)[3][LIN_ALPHA], const uint32_t* __restrict__ lin, LinStats* st) {
     int64_t acc = t;
     int n = 0;
 #pragma unroll
     for (int j = 0; j < PARTIAL - 1; j++)
         if (j < r) {
             if (lin_fold_before(n)) { acc = fold_acc_s(acc); n = 0; }
-            acc = mad_i64_k(z[j], (int32_t)lin[lin_beta_at(r, j)], acc);
+            acc = mad_i64_k(z[j], (int32_t)beta[r % 3][j], acc);
             n++;
+            if (j == 0 && r >= 3 && r < LIN_ALPHA) lin_beta_row(r + 1, beta[(r + 1) % 3], lin);
         }
     if (lin_fold_last(n)) acc = fold_acc_s(acc);
 #if !defined(__HIP_DEVICE_COMPILE__)
@@ -123,6 +140,14 @@ __device__ __forceinline__ lin_v4 lin_b(const uint32_t (&v)[NPOS], int ks, int t
     b[0] = (int)v[8 * ks + 4 * tile]; b[1] = (int)v[8 * ks + 4 * tile + 1]; b[2] = (int)v[8 * ks + 4 * tile + 2]; b[3] = (int)v[8 * ks + 4 * tile + 3];
     return b;
 }
+// A fragment f of the table, this lane's 16 bytes.  The address is (uniform base of f's group of four) + (lane's 32-bit offset) +
+// (immediate below 4 KiB): one VGPR for all 27 fragments.  Left to itself the compiler keeps a 64-bit per-lane pointer for every
+// 4 KiB of the table; the opaque scalar offset keeps the base in scalar registers (the pointer itself stays a global one).
+__device__ __forceinline__ lin_v4 lin_frag(const uint32_t* __restrict__ lin, int f, uint32_t lane16) {
+    uint32_t group = (uint32_t)(f & ~3) * LIN_FRAG * 4;
+    asm("" : "+s"(group));
+    return *(const lin_v4*)((const char*)lin + group + (uint32_t)(f & 3) * LIN_FRAG * 4 + lane16);
+}
 // After two column tiles' products every lane gathers rows of its OWN permutation: the swap of accumulator register 4 g + i of the
 // pair brings digit sum i of the tile's outputs 2 g (first) and 2 g + 1 (second).  Returns both recombined sums.
 __device__ __forceinline__ void lin_gather2(int64_t& t0, int64_t& t1, const lin_v16& c0, const lin_v16& c1, int g, int32_t k0, int32_t k1) {
@@ -135,7 +160,8 @@ __device__ __forceinline__ void lin_gather2(int64_t& t0, int64_t& t1, const lin_
 #endif
 
 // The partial rounds.  In: s as the fourth full round leaves it (nearly centred words at the entry scale, + F64_OFF).  Out: every
-// cell as the signed s-box operand of the fifth full round, |.| < P (that round reads the zero row of lin + LIN_RCF).
+// cell as the signed s-box operand of the fifth full round, |.| < P (that round adds no constants: the row of lin + LIN_RCF that
+// would be its own is zero, and poseidon2_mix_core does not load it).
 // On the device a whole wave must arrive here together.  The host form is the model of it: same digits, same bytes, same
 // recombination and chain, the tile products as plain int32 loops.
 ZKH_HD void poseidon2_partial_linear(uint32_t (&s)[CELLS], const uint32_t* __restrict__ lin, LinStats* st = nullptr) {
@@ -146,17 +172,24 @@ ZKH_HD void poseidon2_partial_linear(uint32_t (&s)[CELLS], const uint32_t* __res
     for (int q = 0; q < CELLS - 1; q++) vx[q] = s[q + 1] ^ LIN_XOR;
     vx[CELLS - 1] = 1u;
     int32_t z[PARTIAL];
-    z[0] = lin_sbox(u0);
+    uint32_t beta[3][LIN_ALPHA];                           // rows of beta in flight (lin_chain_round)
 #if defined(__HIP_DEVICE_COMPILE__)
+    // Table data is requested ahead of its use, in source order (hash.hip is built without the machine scheduler): the A fragments
+    // are double-buffered, the next one requested before the products of the current one issue, and the first fragment of a row
+    // tile before the work that precedes it (the operand swaps, the previous tile's eight chain rounds); beta as lin_chain_round says.
+    const uint32_t lane16 = __lane_id() * 16;              // (recomputed here: threadIdx.x would be one more register live across the kernel)
+    lin_v4 next = lin_frag(lin, LIN_A1 / LIN_FRAG, lane16);
+    lin_beta_first(beta, lin);
+    z[0] = lin_sbox(u0);
     // each row tile of alpha right before the eight rounds it feeds: eight sums live at a time, not twenty
-    const lin_v4* __restrict__ frag = (const lin_v4*)lin + (threadIdx.x & 63);
     lin_operands(vx);
 #pragma unroll
     for (int T = 0; T < LIN_TILES; T++) {
         lin_v16 a0 = {0}, a1 = {0};
 #pragma unroll
         for (int ks = 0; ks < LIN_KS; ks++) {
-            const lin_v4 a = frag[(LIN_A1 / LIN_FRAG + T * LIN_KS + ks) * 64];
+            const lin_v4 a = next;
+            next = lin_frag(lin, LIN_A1 / LIN_FRAG + T * LIN_KS + ks + 1, lane16);  // after the last of alpha: Gamma | Delta's first (LIN_A2 follows LIN_A1)
             a0 = __builtin_amdgcn_mfma_i32_32x32x32_i8(a, lin_b(vx, ks, 0), a0, 0, 0, 0);
             a1 = __builtin_amdgcn_mfma_i32_32x32x32_i8(a, lin_b(vx, ks, 1), a1, 0, 0, 0);
         }
@@ -166,7 +199,7 @@ ZKH_HD void poseidon2_partial_linear(uint32_t (&s)[CELLS], const uint32_t* __res
             if (8 * T + 2 * g < LIN_ALPHA) lin_gather2(t[2 * g], t[2 * g + 1], a0, a1, g, c0, c1);
 #pragma unroll
         for (int o = 0; o < 8; o++)
-            if (8 * T + o < LIN_ALPHA) lin_chain_round(8 * T + o + 1, t[o], z, lin, nullptr);
+            if (8 * T + o < LIN_ALPHA) lin_chain_round(8 * T + o + 1, t[o], z, beta, lin, nullptr);
     }
 #pragma unroll
     for (int q = 0; q < LIN_POS; q++) vz[q] = q < PARTIAL ? (uint32_t)z[q] ^ LIN_XOR : 0u;
@@ -176,7 +209,8 @@ ZKH_HD void poseidon2_partial_linear(uint32_t (&s)[CELLS], const uint32_t* __res
         lin_v16 a0 = {0}, a1 = {0};
 #pragma unroll
         for (int ks = 0; ks < 2 * LIN_KS; ks++) {
-            const lin_v4 a = frag[(LIN_A2 / LIN_FRAG + T * 2 * LIN_KS + ks) * 64];
+            const lin_v4 a = next;
+            if (ks + 1 < 2 * LIN_KS) next = lin_frag(lin, LIN_A2 / LIN_FRAG + T * 2 * LIN_KS + ks + 1, lane16);
             a0 = __builtin_amdgcn_mfma_i32_32x32x32_i8(a, ks < LIN_KS ? lin_b(vx, ks, 0) : lin_b(vz, ks - LIN_KS, 0), a0, 0, 0, 0);
             a1 = __builtin_amdgcn_mfma_i32_32x32x32_i8(a, ks < LIN_KS ? lin_b(vx, ks, 1) : lin_b(vz, ks - LIN_KS, 1), a1, 0, 0, 0);
         }
@@ -185,10 +219,15 @@ ZKH_HD void poseidon2_partial_linear(uint32_t (&s)[CELLS], const uint32_t* __res
             int64_t t0, t1;
             lin_gather2(t0, t1, a0, a1, g, c0, c1);
             s[8 * T + 2 * g] = (uint32_t)smont_reduce(t0); s[8 * T + 2 * g + 1] = (uint32_t)smont_reduce(t1);
+            // the next tile's first fragment: behind the first gather, which has freed eight accumulator registers (both operand
+            // blocks, both accumulators and the outputs so far are live here: the kernel's register peak)
+            if (g == 0 && T + 1 < LIN_TILES) next = lin_frag(lin, LIN_A2 / LIN_FRAG + (T + 1) * 2 * LIN_KS, lane16);
         }
     }
     (void)st;
 #else
+    z[0] = lin_sbox(u0);
+    lin_beta_first(beta, lin);
     auto track = [](int64_t& m, int64_t v) { if (v < 0) v = -v; if (v > m) m = v; };
     auto byte_of = [](const uint32_t (&v)[LIN_POS], int k) { return (int32_t)(int8_t)(v[k >> 2] >> (8 * (k & 3))); };
     auto output = [&](int second, int o, int64_t* lo_hi_track) {
@@ -206,7 +245,7 @@ ZKH_HD void poseidon2_partial_linear(uint32_t (&s)[CELLS], const uint32_t* __res
     };
     int64_t scratch = 0;
     int64_t* lh = st ? &st->lo : &scratch;
-    for (int o = 0; o < LIN_ALPHA; o++) lin_chain_round(o + 1, output(0, o, lh), z, lin, st);
+    for (int o = 0; o < LIN_ALPHA; o++) lin_chain_round(o + 1, output(0, o, lh), z, beta, lin, st);
     for (int q = 0; q < LIN_POS; q++) vz[q] = q < PARTIAL ? (uint32_t)z[q] ^ LIN_XOR : 0u;
     for (int o = 0; o < CELLS; o++) {
         const int64_t tt = output(1, o, lh);
