@@ -1018,14 +1018,27 @@ class HipHal:
         _check(_lib.zkh_read(self.ctx, nodes.h, _ptr(out), DIGEST_WORDS, DIGEST_WORDS))
         return out
 
+    def _page_code(self, fn, circuit: Circuit, po2: int, code: Optional[Buffer], *shape) -> Buffer:
+        """a page-out circuit's code call `fn` over (po2, *shape) into `code`, or into a new buffer of the circuit's code columns"""
+        if code is None:
+            code = self.alloc_elem("code", int(circuit.desc[4]) << po2)
+        _check(fn(self.ctx, circuit.h, po2, *shape, code.h))
+        return code
+
+    def _page_witgen(self, fn, out_words: int, circuit: Circuit, po2: int, zk_cycles: int, code: Buffer, proof: Buffer, proof_words: int, nodes_before: Buffer,
+                     nodes_after: Buffer, part: tuple, data: Buffer, noise_seed: int) -> np.ndarray:
+        """a page-out circuit's witness call `fn` for the part `part` (the call's own operands: none, first, or first and count) -> its
+        `out_words` out globals"""
+        out = np.zeros(out_words, dtype=np.uint32)
+        _k, kp = _key_ptr(noise_seed)
+        _check(fn(self.ctx, circuit.h, po2, zk_cycles, code.h, proof.h, proof_words, nodes_before.h, nodes_after.h, *part, data.h, _ptr(out), kp))
+        return out
+
     def page_circuit_code(self, circuit: Circuit, po2: int, zk_cycles: int, image_words: int, code: Optional[Buffer] = None) -> Buffer:
         """the code group of P2-PAGE (circuits/p2_page.py) for (po2, zk_cycles, the tree height of an image of `image_words` words)
         (zkh_page_circuit_code; the host twin: p2_page.reference_page_code).  code: a Buffer of 39 x 2^po2 words to write (default: a
         new one).  Raises HalError on a circuit of another shape, W <= 8, h > 27 and a trace without room for one path"""
-        if code is None:
-            code = self.alloc_elem("code", int(circuit.desc[4]) << po2)
-        _check(_lib.zkh_page_circuit_code(self.ctx, circuit.h, po2, zk_cycles, image_words, code.h))
-        return code
+        return self._page_code(_lib.zkh_page_circuit_code, circuit, po2, code, zk_cycles, image_words)
 
     def page_circuit_witgen(self, circuit: Circuit, po2: int, zk_cycles: int, code: Buffer, proof: Buffer, proof_words: int, nodes_before: Buffer,
                             nodes_after: Buffer, data: Buffer, noise_seed: int) -> np.ndarray:
@@ -1034,11 +1047,7 @@ class HipHal:
         `proof_words` words are the proof (only its header and table are read); nodes_before / nodes_after: the committed tree before
         and after page_out_tree; code: page_circuit_code of the same (po2, zk_cycles, image size).  Raises HalError with one message
         per cause (include/zkhal.h "P2-PAGE"); `data` is unspecified then"""
-        out = np.zeros(2 * DIGEST_WORDS, dtype=np.uint32)
-        _k, kp = _key_ptr(noise_seed)
-        _check(_lib.zkh_page_circuit_witgen(self.ctx, circuit.h, po2, zk_cycles, code.h, proof.h, proof_words, nodes_before.h, nodes_after.h, data.h,
-                                            _ptr(out), kp))
-        return out
+        return self._page_witgen(_lib.zkh_page_circuit_witgen, 2 * DIGEST_WORDS, circuit, po2, zk_cycles, code, proof, proof_words, nodes_before, nodes_after, (), data, noise_seed)
 
     def page_circuit_slots(self, po2: int, zk_cycles: int, image_words: int) -> int:
         """N, the path slots of a P2-PAGE trace of 2^po2 rows over an image of `image_words` words, 0 where page_circuit_code refuses the
@@ -1052,20 +1061,13 @@ class HipHal:
         update `first` ‖ the root after the part's last update (16 words).  Every other operand is page_circuit_witgen's, and both trees
         are the whole page-out's whichever part is laid out.  A table of any size is refused only for first >= D (first = D = 0 is
         the empty table's one part); the other refusals are page_circuit_witgen's after "page_circuit_witgen_part: " """
-        out = np.zeros(2 * DIGEST_WORDS, dtype=np.uint32)
-        _k, kp = _key_ptr(noise_seed)
-        _check(_lib.zkh_page_circuit_witgen_part(self.ctx, circuit.h, po2, zk_cycles, code.h, proof.h, proof_words, nodes_before.h, nodes_after.h, first,
-                                                 data.h, _ptr(out), kp))
-        return out
+        return self._page_witgen(_lib.zkh_page_circuit_witgen_part, 2 * DIGEST_WORDS, circuit, po2, zk_cycles, code, proof, proof_words, nodes_before, nodes_after, (first,), data, noise_seed)
 
     def page_ordered_code(self, circuit: Circuit, po2: int, zk_cycles: int, image_words: int, code: Optional[Buffer] = None) -> Buffer:
         """the code group of P2-PAGE-ordered (circuits/p2_page_ordered.py) for (po2, zk_cycles, the tree height of an image of
         `image_words` words) (zkh_page_ordered_code; the host twin: p2_page_ordered.reference_ordered_code).  code: a Buffer of 42 x
         2^po2 words to write (default: a new one).  Raises HalError as page_circuit_code does, and on h > 26"""
-        if code is None:
-            code = self.alloc_elem("code", int(circuit.desc[4]) << po2)
-        _check(_lib.zkh_page_ordered_code(self.ctx, circuit.h, po2, zk_cycles, image_words, code.h))
-        return code
+        return self._page_code(_lib.zkh_page_ordered_code, circuit, po2, code, zk_cycles, image_words)
 
     def page_ordered_witgen(self, circuit: Circuit, po2: int, zk_cycles: int, code: Buffer, proof: Buffer, proof_words: int, nodes_before: Buffer,
                             nodes_after: Buffer, first: int, data: Buffer, noise_seed: int) -> np.ndarray:
@@ -1074,20 +1076,13 @@ class HipHal:
         and hi as the trace holds them, p2_page_ordered.decode).  The operands are page_circuit_witgen_part's, `data` of 129 x 2^po2
         words; first = 0 with D <= N is the single-seal case.  Raises HalError with one message per cause (include/zkhal.h
         "P2-PAGE-ordered"); `data` is unspecified then"""
-        out = np.zeros(2 * DIGEST_WORDS + 2, dtype=np.uint32)
-        _k, kp = _key_ptr(noise_seed)
-        _check(_lib.zkh_page_ordered_witgen(self.ctx, circuit.h, po2, zk_cycles, code.h, proof.h, proof_words, nodes_before.h, nodes_after.h, first,
-                                            data.h, _ptr(out), kp))
-        return out
+        return self._page_witgen(_lib.zkh_page_ordered_witgen, 2 * DIGEST_WORDS + 2, circuit, po2, zk_cycles, code, proof, proof_words, nodes_before, nodes_after, (first,), data, noise_seed)
 
     def page_tree_code(self, circuit: Circuit, po2: int, zk_cycles: int, code: Optional[Buffer] = None) -> Buffer:
         """the code group of P2-TREE (circuits/p2_tree.py) and of P2-TREE-tied (circuits/p2_tree_tied.py: the same words) for (po2,
         zk_cycles): it does not depend on the image (zkh_page_tree_code; the host twin: p2_tree.reference_tree_code).  code: a Buffer of
         41 x 2^po2 words to write (default: a new one)"""
-        if code is None:
-            code = self.alloc_elem("code", int(circuit.desc[4]) << po2)
-        _check(_lib.zkh_page_tree_code(self.ctx, circuit.h, po2, zk_cycles, code.h))
-        return code
+        return self._page_code(_lib.zkh_page_tree_code, circuit, po2, code, zk_cycles)
 
     def page_tree_plan(self, po2: int, zk_cycles: int, image_words: int, addrs) -> list:
         """the module's page_tree_plan (host only: it needs no context)"""
@@ -1118,11 +1113,7 @@ class HipHal:
         words, both trees the whole page-out's; the part is one of page_tree_plan's.  A P2-TREE-tied circuit (kind 9) gets its 138
         columns (the host twin: p2_tree_tied.reference_tree_tied_part) and the same 18 words.  Raises HalError with one message per cause
         (include/zkhal.h "P2-TREE"); `data` is unspecified then"""
-        out = np.zeros(2 * DIGEST_WORDS + 2, dtype=np.uint32)
-        _k, kp = _key_ptr(noise_seed)
-        _check(_lib.zkh_page_tree_witgen(self.ctx, circuit.h, po2, zk_cycles, code.h, proof.h, proof_words, nodes_before.h, nodes_after.h, first, count,
-                                         data.h, _ptr(out), kp))
-        return out
+        return self._page_witgen(_lib.zkh_page_tree_witgen, 2 * DIGEST_WORDS + 2, circuit, po2, zk_cycles, code, proof, proof_words, nodes_before, nodes_after, (first, count), data, noise_seed)
 
     def derive_multiplicities(self, circuit: Circuit, po2: int, zk_cycles: int, code: Buffer, data: Buffer) -> None:
         """fill the derived multiplicity columns of `data` on the active rows (zkh_derive_multiplicities): raises HalError on a table

@@ -1,0 +1,356 @@
+"""Sealing and verifying a page-out: the host layer over the page-out circuits.  `PAGE_KINDS` states every circuit kind
+that seals one, once.  `seal_chain` seals a page-out as a chain of parts (SegmentProver.seal_page_out, _parts, _ordered, _tree) and
+`seal_tied_group` a paging segment and its page-out as one tied group (`seal_tied`, `seal_tied_tree`), both on `open_chain`;
+`verify_chain` and `verify_tied_group` are their verifiers, HOST ONLY.  A prover reaches this module as an object (prover.py imports this
+module, not the reverse), a receipt as what its `seal_with_accum` returns; the verifiers read only a receipt's `.seal`."""
+from __future__ import annotations
+
+import importlib
+from dataclasses import dataclass
+from typing import Tuple
+
+import numpy as np
+
+from . import hal as _hal
+
+TIE_WORDS = 12                                  # alpha (4) ‖ beta (4) ‖ F (4): the last words of `out` of every seal of a tied group
+
+
+@dataclass(frozen=True)
+class PageKind:
+    """One circuit kind that seals a page-out.  module: zeth_amd/circuits/<module>.py, whose <module>_circuit() is the description and
+    whose constants and `decode` are the kind's; code, witgen: the hal's code call and witness call, by method name.  family: "path" lays
+    out one path per update (the plan is p2_page.parts, a part's operand is (first,), room is page_circuit_slots "slots"); "tree" lays out
+    one block per dirty node (the plan is zkh_page_tree_plan's, made on the host or on the device, a part's operands are (first, count),
+    room is "block slots").  ordered: the parts carry lo and hi; a path chain then starts at lo = 0, a tree chain is told h, checks its
+    range and runs from 2^(h-1) to at most 2^h.  accum: "syn" (syn_accumulate), "args" (args_accumulate, with the chain's `check`) or
+    "open": the kind is tied (the open accumulate); a tied tree part also states out_base(h) after its prefix, which its verifier checks."""
+    kind: int
+    module: str
+    code: str
+    witgen: str
+    family: str
+    ordered: bool
+    accum: str
+    mod = property(lambda self: importlib.import_module(f".circuits.{self.module}", __package__))
+    out_words = property(lambda self: self.mod.OUT_WORDS)
+    prefix_words = property(lambda self: getattr(self.mod, "PREFIX_WORDS", self.mod.OUT_WORDS))        # what the witness call returns
+    desc = lambda self: getattr(self.mod, self.module + "_circuit")()
+
+    def part(self, out) -> tuple:
+        """link_page_parts' operands in a part's `out` words: root_before ‖ root_after and, ordered, lo ‖ hi, the last words of the prefix"""
+        return (out[:8], out[8:16]) + (tuple(self.mod.decode(w) for w in out[self.prefix_words - 2:self.prefix_words]) if self.ordered else ())
+
+
+PAGE_KINDS = {k.kind: k for k in (PageKind(5, "p2_page", "page_circuit_code", "page_circuit_witgen_part", "path", False, "syn"),
+                                  PageKind(6, "p2_page_ordered", "page_ordered_code", "page_ordered_witgen", "path", True, "syn"),
+                                  PageKind(7, "p2_tree", "page_tree_code", "page_tree_witgen", "tree", True, "args"),
+                                  PageKind(8, "p2_page_tied", "page_ordered_code", "page_ordered_witgen", "path", True, "open"),
+                                  PageKind(9, "p2_tree_tied", "page_tree_code", "page_tree_witgen", "tree", True, "open"))}
+
+
+def _fmt_words(w) -> str:
+    return " ".join(f"{int(x):08x}" for x in w)
+
+
+def open_chain(who: str, prover, k: PageKind, segs: list, proof, proof_words: int, plan_where: str = "host", no_segment: str = "", buses=(), single: bool = False):
+    """What a chain of parts and a tied group both open with -> (the proof on the device, po2, zk_cycles, the code group, the plan: per
+    part the witness call's own operands).  segs: one Segment per part, all of one (po2, zk_cycles), each with its own noise seed;
+    HalError if their number is not the plan's.  proof: a device Buffer whose first `proof_words` words are the proof, or the proof's
+    words (uploaded).  plan_where: where a tree chain plans, refused before anything else unless "host" or "device"; buses: (name, prover)
+    of the provers whose circuits must have an open bus, checked next; no_segment: the words after "no segment" for an empty `segs`.
+    A path chain builds the code group (which refuses a shape without a path slot; P2-PAGE-ordered: and h > 26) and then plans; a tree
+    chain plans (refusing W <= 16, B < h, addresses out of order), compares the plan with the segments and then builds the code group.
+    single: P2-PAGE's one seal of a whole table (seal_page_out): one part, W from the header, no plan to compare with."""
+    path = k.family == "path"
+    if not path and plan_where not in ("host", "device"):
+        raise _hal.HalError(f'{who}: plan="{plan_where}" (the plan is made on the "host" or on the "device")')
+    for name, p in buses:
+        if p.circuit.open_bus() is None:
+            raise _hal.HalError(f"{who}: the {name} prover's circuit has no open bus (its arguments hold no OPEN record)")
+    if not segs:
+        raise _hal.HalError(f"{who}: no segment{no_segment}")
+    hal, po2, zk = prover.hal, segs[0].po2, segs[0].zk_cycles
+    if any((s.po2, s.zk_cycles) != (po2, zk) for s in segs):
+        raise _hal.HalError(f"{who}: the parts share one code group: every segment must have the same (po2, zk_cycles)")
+    if not isinstance(proof, _hal.Buffer):
+        proof = hal.copy_from("image_proof", np.ascontiguousarray(proof, dtype=np.uint32).reshape(-1))
+    if not path and not prover.circuit.has_arguments():
+        raise _hal.HalError(f"{who}: the prover was built without P2-TREE's arguments (arguments=p2_tree.arguments())")
+    header = [int(w) for w in proof.slice(0, min(5, proof.size())).to_vec()]
+    code_call = lambda *shape: getattr(hal, k.code)(prover.circuit, po2, zk, *shape)
+    if single:
+        return proof, po2, zk, code_call(header[1] if len(header) > 1 else 0), [()]
+    if path:
+        from .circuits import p2_page
+        W, D = header[1:3] if len(header) > 2 else (0, 0)
+        code = code_call(W)
+        plan, room = [(first,) for first, _count in p2_page.parts(po2, zk, W, D)], f"{hal.page_circuit_slots(po2, zk, W)} slots"
+    else:
+        W, D, h = (header[1], header[2], header[4]) if len(header) > 4 else (0, 0, 0)
+        if 5 + h + 3 * D > min(proof_words, proof.size()):
+            raise _hal.HalError(f"{who}: a proof of {proof_words} words does not hold its header and a table of {D} rows")
+        if plan_where == "device":                                             # the table stays where zkh_page_out_proof left it
+            plan = hal.page_tree_plan_device(po2, zk, W, proof, 5 + h, D)
+        else:
+            plan = hal.page_tree_plan(po2, zk, W, proof.slice(5 + h, 3 * D).to_vec()[::3] if D else np.zeros(0, dtype=np.uint32))
+        room = f"{((1 << po2) - zk) // 31} block slots"
+    if len(segs) != len(plan):
+        raise _hal.HalError(f"{who}: {len(segs)} segments, but a table of {D} rows takes {len(plan)} parts of {room} at po2 {po2}")
+    return proof, po2, zk, code if path else code_call(), plan
+
+
+def seal_chain(who: str, prover, kind: int, segs, proof, proof_words: int, nodes_before, nodes_after, check: bool, plan_where: str = "host", single: bool = False) -> list:
+    """Seal a page-out as a chain of parts of the untied kind `kind` -> the receipts, in the order of the parts.  segs, proof, single:
+    open_chain's; nodes_before / nodes_after: the committed tree before and after the page-out.  Both trees are the WHOLE page-out's for
+    every part, so the parts could be sealed in any order, or on several ranks.  The code group and its control root are built once,
+    before the first witness, and the data buffer is reused.  A single seal's witness call is page_circuit_witgen."""
+    k, segs = PAGE_KINDS[kind], list(segs)
+    proof, po2, zk, code, plan = open_chain(who, prover, k, segs, proof, proof_words, plan_where, single=single)
+    witgen = getattr(prover.hal, "page_circuit_witgen" if single else k.witgen)
+    control_root = prover.code_root(code, po2)
+    data = prover.hal.alloc_elem("data", prover.group_sizes()[2] << po2)
+    receipts = []
+    for seg, part in zip(segs, plan):
+        out = witgen(prover.circuit, po2, zk, code, proof, proof_words, nodes_before, nodes_after, *part, data, seg.noise_seed)
+        accum = prover.args_accumulate(seg, code, data, check=check) if k.accum == "args" else prover.syn_accumulate(seg, data)
+        receipts.append(prover.seal_with_accum(seg, code, data, out, accum, check=check))
+        receipts[-1].control_root = control_root.copy()
+    return receipts
+
+
+def seal_tied_group(who: str, kind: int, seg_prover, seg, code, data, out_prefix, page_prover, page_segs, proof, proof_words: int, nodes_before, nodes_after,
+                    check: bool, check_table: bool, plan_where: str = "host"):
+    """The two passes of `seal_tied` (kind 8) and `seal_tied_tree` (kind 9), on open_chain -> (the segment's receipt, [the parts'
+    receipts]).  A part's `out` words before alpha are the kind's prefix of what the witness call returns and, for kind 9, out_base(h)."""
+    k, hal, page_segs = PAGE_KINDS[kind], seg_prover.hal, list(page_segs)
+    proof, po2, zk, page_code, plan = open_chain(who, page_prover, k, page_segs, proof, proof_words, plan_where,
+                                                 " for the page-out (a page-out of no rows still has one part)", (("segment", seg_prover), ("page-out", page_prover)))
+    head = proof.slice(0, 5).to_vec()
+    rows, h, table_at = int(head[2]), int(head[4]), 5 + int(head[4])
+    page_data = hal.alloc_elem("data", page_prover.group_sizes()[2] << po2)
+
+    def part_witness(s, part):
+        return getattr(hal, k.witgen)(page_prover.circuit, po2, zk, page_code, proof, proof_words, nodes_before, nodes_after, *part, page_data, s.noise_seed)
+
+    # pass one: the data roots, the segment's first
+    roots = [seg_prover.data_root(data, seg.po2)]
+    for s, part in zip(page_segs, plan):
+        part_witness(s, part)
+        roots.append(page_prover.data_root(page_data, po2))
+    challenge = _hal.tie_challenge(np.concatenate(roots))
+
+    def open_seal(prover, s, code, data, prefix):
+        accum = hal.alloc_elem("accum", prover.group_sizes()[0] << s.po2)
+        total = hal.accumulate_open(prover.circuit, s.po2, s.zk_cycles, s.noise_seed, code, data, challenge, accum)
+        out = np.concatenate([np.asarray(prefix, dtype=np.uint32).reshape(-1), challenge, total]).astype(np.uint32)
+        if out.size != prover.out_size():
+            raise _hal.HalError(f"{who}: {out.size} out words (a prefix of {out.size - TIE_WORDS}, alpha, beta, the total), the circuit has {prover.out_size()}")
+        return accum, total, out
+
+    seg_accum, seg_total, seg_out = open_seal(seg_prover, seg, code, data, out_prefix)
+    if check_table:
+        want = hal.table_fingerprint(proof, table_at, rows, challenge)
+        if not np.array_equal(seg_total, want):
+            raise _hal.HalError(f"{who}: the proof's table is not the segment's page table: the segment's open total is {_fmt_words(seg_total)}, "
+                                f"the fingerprint of the proof's {rows} rows is {_fmt_words(want)}")
+    # pass two: the seals
+    seg_receipt = seg_prover.seal_with_accum(seg, code, data, seg_out, lambda _mix: seg_accum, check=check)
+    seg_receipt.control_root = seg_prover.code_root(code, seg.po2)
+    del seg_accum
+    page_root = page_prover.code_root(page_code, po2)
+    receipts = []
+    for s, part in zip(page_segs, plan):
+        prefix = np.concatenate([part_witness(s, part)[:k.prefix_words], [k.mod.out_base(h)] if k.family == "tree" else []])
+        accum, _total, out = open_seal(page_prover, s, page_code, page_data, prefix)
+        receipts.append(page_prover.seal_with_accum(s, page_code, page_data, out, lambda _mix, accum=accum: accum, check=check))
+        receipts[-1].control_root = page_root.copy()
+    return seg_receipt, receipts
+
+
+def seal_tied(seg_prover, seg, code, data, out_prefix, page_prover, page_segs, proof, proof_words: int,
+              nodes_before, nodes_after, check: bool = False, check_table: bool = True):
+    """Seal a paging segment and the page-out of its memory as ONE tied group (DESIGN.md §2 "THE TIE") -> (the segment's receipt, [the
+    parts' receipts]): the seals share a bus under a challenge drawn from all their data roots, and `verify_tied` accepts them only
+    together.  seg_prover: a prover of an open-bus paging circuit (SYN-LOOKUP-tied, built with its arguments); code, data: the segment's
+    traces on the device, derived and reduced (what seal_host_witness hands its accumulate); out_prefix: the segment's `out` words before
+    alpha.  page_prover: a prover of P2-PAGE-tied with p2_page_tied.arguments(); page_segs, proof, proof_words, nodes_before, nodes_after:
+    seal_page_out_ordered's operands.  Two passes, so that one part's traces are held at a time:
+      1. the roots: the segment's data root (zkh_data_root); per part the witness, its data root, and the buffer is reused; the
+         challenge alpha ‖ beta = hal.tie_challenge(the roots, the segment's first).
+      between, with check_table: the segment's open total must be hal.table_fingerprint of the proof's table under that challenge, else
+         HalError "the proof's table is not the segment's page table": no part is sealed on a table that cannot cancel.
+      2. the segment and then every part: the part's witness again (the same noise key gives the same trace, hence the same root),
+         accumulate_open, out = prefix ‖ challenge ‖ total, zkh_prove_begin, with `check` check_witness, zkh_prove_finish.
+    Every receipt carries its code group's root as `control_root`."""
+    return seal_tied_group("seal_tied", 8, seg_prover, seg, code, data, out_prefix, page_prover, page_segs, proof, proof_words, nodes_before, nodes_after, check, check_table)
+
+
+def seal_tied_tree(seg_prover, seg, code, data, out_prefix, page_prover, page_segs, proof, proof_words: int,
+                   nodes_before, nodes_after, check: bool = False, check_table: bool = True, plan: str = "host"):
+    """`seal_tied` with P2-TREE-tied parts (circuits/p2_tree_tied.py): the page-out side of the group is one block per DIRTY NODE, not one
+    path per word.  page_prover: a prover of P2-TREE-tied with p2_tree_tied.arguments(); the plan is seal_page_out_tree's, made on the
+    "host" or on the "device" (`plan`); every other operand, both passes and the fingerprint check between them are seal_tied's.  A part's
+    out = the witness call's 18 words ‖ p2_tree_tied.out_base(h) ‖ the challenge ‖ its open total.  -> (the segment's receipt, [the parts'
+    receipts]), for `verify_tied_tree`."""
+    return seal_tied_group("seal_tied_tree", 9, seg_prover, seg, code, data, out_prefix, page_prover, page_segs, proof, proof_words, nodes_before, nodes_after, check, check_table, plan)
+
+
+def link_page_parts(who: str, parts, root_before=None, first_lo=None, last_hi=None) -> tuple:
+    """The links of a chain of page-out seals, HOST ONLY: what verify_page_out_chain, verify_page_ordered_chain and
+    link_page_tree_chain check once a seal is verified -> (root_before, root_after) of the whole page-out, and hi where the parts have
+    one.  parts: per part (the root it opens, the root it leaves) or (…, lo, hi), lo and hi as integers; an iterator is consumed part
+    by part, so a caller may verify each seal as it hands it over.  who: the prefix of every message.  Part p + 1 must open the root
+    part p left; with a `root_before`, part 0 must open it.  Parts with lo and hi: every lo and hi must be at most 2^29 (what the
+    circuits' 29-bit gaps are sound for); part p + 1 must start at the hi part p left; first_lo = (the lo part 0 must have, the words
+    that say why); last_hi, if given = (the bound of the last hi, the words that say why).  Raises HalError, one message per cause."""
+    from .circuits.p2_blocks import GAP_BITS
+    chain = []
+    for p, part in enumerate(parts):
+        for name, v in zip(("lo", "hi"), part[2:]):
+            if v > 1 << GAP_BITS:
+                raise _hal.HalError(f"{who}: part {p}: {name} {v} is above 2^{GAP_BITS}, the bound the order check is sound for")
+        chain.append((np.array(part[0], dtype=np.uint32), np.array(part[1], dtype=np.uint32)) + tuple(part[2:]))
+    if not chain:
+        raise _hal.HalError(f"{who}: no receipt (a page-out of no rows still has one part)")
+    ordered = len(chain[0]) > 2
+    if ordered and chain[0][2] != first_lo[0]:
+        raise _hal.HalError(f"{who}: part 0 starts at lo {chain[0][2]}, not {first_lo[1]}")
+    if root_before is not None and not np.array_equal(chain[0][0], np.asarray(root_before, dtype=np.uint32)):
+        raise _hal.HalError(f"{who}: part 0 opens root {_fmt_words(chain[0][0])}, not root_before {_fmt_words(root_before)}")
+    for p in range(len(chain) - 1):
+        if not np.array_equal(chain[p + 1][0], chain[p][1]):
+            raise _hal.HalError(f"{who}: part {p + 1} opens root {_fmt_words(chain[p + 1][0])}, but part {p} left root {_fmt_words(chain[p][1])}")
+        if ordered and chain[p + 1][2] != chain[p][3]:
+            raise _hal.HalError(f"{who}: part {p + 1} starts at lo {chain[p + 1][2]}, but part {p} left hi {chain[p][3]}")
+    if ordered and last_hi is not None and chain[-1][3] > last_hi[0]:
+        raise _hal.HalError(f"{who}: the last part leaves hi {chain[-1][3]}, above {last_hi[1]}")
+    return (chain[0][0], chain[-1][1]) + chain[-1][3:]
+
+
+def link_page_tree_chain(outs, h: int, root_before=None) -> Tuple[np.ndarray, np.ndarray, int]:
+    """What verify_page_tree_chain checks of the parts' `out` words (18 each) once every seal is verified -> (root_before, root_after,
+    hi).  Every lo and hi must decode to at most 2^29; part 0 must have lo = 2^(h-1), the id of the first pair of leaves; part p + 1
+    must open the root part p left and start at the hi part p left; the last hi must be at most 2^h, so every pair block's id lies in
+    [2^(h-1), 2^h): h - 1 levels below the root; with a `root_before`, part 0 must open it.  Raises HalError, one message per cause."""
+    from .circuits import p2_tree as pt
+    who = "verify_page_tree_chain"
+    if not pt.MIN_H <= h <= pt.MAX_H:
+        raise _hal.HalError(f"{who}: h {h} ({pt.MIN_H} .. {pt.MAX_H})")
+    return link_page_parts(who, (PAGE_KINDS[7].part(out) for out in outs), root_before,
+                           first_lo=(1 << (h - 1), f"2^{h - 1} = {1 << (h - 1)}, the id of the first pair of leaves of a tree of height {h}"),
+                           last_hi=(1 << h, f"2^{h} = {1 << h}: a pair block outside a tree of height {h}"))
+
+
+def link_tied_tree_chain(outs, h: int, root_before=None) -> Tuple[np.ndarray, np.ndarray, int]:
+    """What verify_tied_tree checks of the parts' `out` words (31 each) besides the group's challenge and totals -> (root_before, root_after,
+    hi): `link_page_tree_chain` on their first 18 words, then every part's out[18] must be p2_tree_tied.out_base(h), the word that turns a
+    pair block's id into its addresses.  Raises HalError, one message per cause."""
+    from .circuits import p2_tree_tied as tt
+    outs = [np.asarray(out, dtype=np.uint32) for out in outs]
+    linked = link_page_tree_chain([out[:tt.PREFIX_WORDS] for out in outs], h, root_before)
+    for p, out in enumerate(outs):
+        if int(out[tt.OUT_BASE]) != tt.out_base(h):
+            raise _hal.HalError(f"verify_tied_tree: part {p}: base {tt.decode(out[tt.OUT_BASE])} is not {1 << (h + 3)} = 16 * 2^{h - 1}, sixteen times the id of "
+                                f"the first pair of leaves of a tree of height {h}")
+    return linked
+
+
+def _verified_parts(receipts, k: PageKind, control_root):
+    """per receipt, once its seal is verified against the kind's description and `control_root`: the operands of link_page_parts"""
+    hc = None
+    for r in receipts:
+        hc = hc or _hal.HostCircuit(k.desc())
+        hc.verify_segment(r.seal, control_root)
+        yield k.part(r.seal)
+
+
+def verify_chain(who: str, kind: int, receipts, control_root, root_before=None, h=None) -> tuple:
+    """Verify the chain of seals of one page-out whose parts are of kind `kind`, HOST ONLY -> (root_before, root_after) and, where the
+    parts have one, hi.  Every seal is verified against the kind's description and `control_root` (one for all parts), and the parts link
+    by the kind's rule.  A path chain verifies part p and bounds its lo and hi before it verifies part p + 1.  A tree chain is told h: it
+    refuses an empty list, verifies every seal, and only then looks at h and links (as verify_page_tree_chain, whoever asks)."""
+    k, receipts = PAGE_KINDS[kind], list(receipts)
+    parts = _verified_parts(receipts, k, control_root)
+    if k.family == "path":
+        return link_page_parts(who, parts, root_before, first_lo=(0, "0: addresses below it are not covered") if k.ordered else None)
+    if not receipts:
+        raise _hal.HalError(f"{who}: no receipt (a page-out of no rows still has one part)")
+    list(parts)
+    return (link_tied_tree_chain if k.accum == "open" else link_page_tree_chain)([r.seal[:k.out_words] for r in receipts], h, root_before)
+
+
+def verify_tied_group(who: str, kind: int, seg_receipt, seg_circuit, seg_control_root, part_receipts, page_control_root, root_before=None, h=None) -> tuple:
+    """Verify a tied group whose parts are of kind `kind`, HOST ONLY -> (root_before, root_after, hi): the segment's seal first, then
+    the chain of parts as verify_chain does, then `_check_tied_totals` over all seals."""
+    k, part_receipts = PAGE_KINDS[kind], list(part_receipts)
+    desc = np.asarray(seg_circuit, dtype=np.uint32)
+    seg_hc, seg_out_size = _hal.HostCircuit(desc), int(desc[7])
+    if seg_out_size < TIE_WORDS:
+        raise _hal.HalError(f"{who}: the segment circuit has {seg_out_size} out words: no room for alpha, beta and the total")
+    seg_hc.verify_segment(seg_receipt.seal, seg_control_root)
+    linked = verify_chain(who, kind, part_receipts, page_control_root, root_before, h)
+    page_hc = _hal.HostCircuit(k.desc())
+    _check_tied_totals(who, [("the segment", seg_hc, seg_receipt.seal, seg_out_size)] + [(f"part {p}", page_hc, r.seal, k.out_words) for p, r in enumerate(part_receipts)])
+    return linked
+
+
+def _check_tied_totals(who: str, seals) -> None:
+    """The challenge and total checks of a tied group whose seals are verified.  seals: (name, HostCircuit, seal, out words) per seal, the
+    segment's first.  Every seal must state the challenge `hal.tie_challenge` gives for the data roots read out of the seals in that
+    order, and the totals F must add up to zero in Fp4.  Raises HalError, one line per cause."""
+    want = _hal.tie_challenge(np.concatenate([hc.seal_data_root(seal) for _, hc, seal, _ in seals]))
+    total = np.zeros(4, dtype=np.uint64)
+    for name, _, seal, out_size in seals[1:] + seals[:1]:                     # a part that was swapped in is named before the segment
+        stated = np.asarray(seal[out_size - TIE_WORDS:out_size - 4], dtype=np.uint32)
+        if not np.array_equal(stated, want):
+            raise _hal.HalError(f"{who}: {name}: its challenge {_fmt_words(stated)} is not the one the data roots give, {_fmt_words(want)}")
+        total = (total + np.asarray(seal[out_size - 4:out_size], dtype=np.uint64)) % np.uint64(_hal.P)
+    if total.any():
+        raise _hal.HalError(f"{who}: the totals do not cancel: the segment's F plus the parts' is {_fmt_words(total)}, not zero: the parts' rows are not "
+                            f"the segment's page table")
+
+
+def verify_page_out_chain(receipts, control_root, root_before=None) -> Tuple[np.ndarray, np.ndarray]:
+    """Verify the chain of P2-PAGE seals of one page-out (SegmentProver.seal_page_out_parts), HOST ONLY -> (root_before, root_after) of
+    the whole page-out.  Every seal is verified against P2-PAGE's description and `control_root` (the code group's: one for all
+    parts); part p + 1 must open the root part p left; with a `root_before`, part 0 must open it.  Raises HalError on a seal the
+    verifier rejects, on a chain that does not link, on another first root, and on an empty list."""
+    return verify_chain("verify_page_out_chain", 5, receipts, control_root, root_before)
+
+
+def verify_page_ordered_chain(receipts, control_root, root_before=None) -> Tuple[np.ndarray, np.ndarray, int]:
+    """Verify the chain of P2-PAGE-ordered seals of one page-out (SegmentProver.seal_page_out_ordered), HOST ONLY -> (root_before,
+    root_after, hi) of the whole page-out: its live updates have strictly increasing addresses, the last of them hi - 1 (hi = 0: none).
+    Every seal is verified against P2-PAGE-ordered's description and `control_root` (one for all parts); every lo and hi must decode
+    to at most 2^29 (what the circuit's 29-bit gaps are sound for); part 0 must have lo = 0; part p + 1 must open the root part p left
+    and start at the hi part p left; with a `root_before`, part 0 must open it.  Raises HalError, one message per cause."""
+    return verify_chain("verify_page_ordered_chain", 6, receipts, control_root, root_before)
+
+
+def verify_page_tree_chain(receipts, control_root, h: int, root_before=None) -> Tuple[np.ndarray, np.ndarray, int]:
+    """Verify the chain of P2-TREE seals of one page-out (SegmentProver.seal_page_out_tree), HOST ONLY -> (root_before, root_after, hi)
+    of the whole page-out.  Every seal is verified against P2-TREE's description and `control_root` (one per (po2, zk_cycles), for
+    every image size); then the parts' outputs must link (`link_page_tree_chain`): the verifier is told h, the height of the image's
+    tree.  Raises HalError on a seal the verifier rejects, and one message per cause on a chain that does not link."""
+    return verify_chain("verify_page_tree_chain", 7, receipts, control_root, root_before, h)
+
+
+def verify_tied(seg_receipt, seg_circuit, seg_control_root, part_receipts, page_control_root, root_before=None) -> Tuple[np.ndarray, np.ndarray, int]:
+    """Verify a tied group (`seal_tied`), HOST ONLY -> (root_before, root_after, hi): the page table of the segment `seg_receipt` seals,
+    applied in order to the image under root_before, leaves root_after, its last address hi - 1 (hi = 0: the segment touched no memory).
+    seg_circuit: the segment circuit's description (its `out` ends on alpha ‖ beta ‖ F, as every tied circuit's does); the parts are
+    P2-PAGE-tied's.  On top of the ordered chain (`link_page_parts`, as verify_page_ordered_chain) it makes the four checks of the design:
+    every seal verifies against its control root; every seal states the challenge that `hal.tie_challenge` gives for the data roots read
+    out of the seals themselves, the segment's first (one comparison per seal: they then all state the same one); the totals F of all
+    seals add up to zero in Fp4.  Raises HalError, one line per cause, naming the seal and the two values that differ."""
+    return verify_tied_group("verify_tied", 8, seg_receipt, seg_circuit, seg_control_root, part_receipts, page_control_root, root_before)
+
+
+def verify_tied_tree(seg_receipt, seg_circuit, seg_control_root, part_receipts, page_control_root, h: int, root_before=None) -> Tuple[np.ndarray, np.ndarray, int]:
+    """Verify a tied group whose page-out side is P2-TREE-tied's (`seal_tied_tree`), HOST ONLY -> (root_before, root_after, hi): the page
+    table of the segment `seg_receipt` seals, applied to the image under root_before, leaves root_after; hi is one more than the id of
+    the last pair of leaves it touches.  The verifier is told h, the height of the image's tree.  Every seal verifies against its
+    control root; the parts link as P2-TREE's do and state base = 16 * 2^(h-1) (`link_tied_tree_chain`); then `verify_tied`'s checks of
+    the challenge and of the totals.  Raises HalError, one line per cause."""
+    return verify_tied_group("verify_tied_tree", 9, seg_receipt, seg_circuit, seg_control_root, part_receipts, page_control_root, root_before, h)

@@ -24,8 +24,11 @@ from typing import Callable, Dict, Optional, Tuple
 
 import numpy as np
 
-from . import hal as _hal
+from . import hal as _hal, page_seal as _page_seal
 from .circuits import syn_air
+# what seals or verifies a page-out lives in page_seal.py; its public names stay importable from here
+from .page_seal import (TIE_WORDS, link_page_parts, link_page_tree_chain, link_tied_tree_chain, seal_tied, seal_tied_tree,  # noqa: F401
+                        verify_page_ordered_chain, verify_page_out_chain, verify_page_tree_chain, verify_tied, verify_tied_tree)
 
 DEFAULT_SEGMENT_PO2 = 20      # upstream default segment_limit_po2 (lib.rs:132-135 passes None -> 20)
 _CONTROL_ROOTS_JSON = os.path.join(os.path.dirname(os.path.abspath(__file__)), "circuits", "control_roots.json")
@@ -375,72 +378,15 @@ class SegmentProver:
         The receipt's output is root_before ‖ root_after; `control_root` is the committed code group's root, which depends on the
         tree height as well as on po2.  check: check the witness row by row first (check_witness); a table that does not match
         the trees is named there."""
-        if not isinstance(proof, _hal.Buffer):
-            proof = self.hal.copy_from("image_proof", np.ascontiguousarray(proof, dtype=np.uint32).reshape(-1))
-        header = proof.slice(0, min(2, proof.size())).to_vec()
-        W = int(header[1]) if header.size > 1 else 0
-        wa, wc, wd = self.group_sizes()
-        code = self.hal.page_circuit_code(self.circuit, seg.po2, seg.zk_cycles, W)
-        data = self.hal.alloc_elem("data", wd << seg.po2)
-        out = self.hal.page_circuit_witgen(self.circuit, seg.po2, seg.zk_cycles, code, proof, proof_words, nodes_before, nodes_after, data, seg.noise_seed)
-        receipt = self.seal_with_accum(seg, code, data, out, self.syn_accumulate(seg, data), check=check)
-        receipt.control_root = self.code_root(code, seg.po2)
-        return receipt
-
-    def _seal_page_chain(self, who: str, segs, proof, proof_words: int, nodes_before, nodes_after, check: bool, open_chain, witgen, accum) -> list:
-        """Seal a page-out as a chain of parts: what seal_page_out_parts, seal_page_out_ordered and seal_page_out_tree share.  segs: one
-        Segment per part, all of one (po2, zk_cycles), each with its own noise seed; HalError if their number is not the plan's.
-        open_chain(proof, po2, zk, fit) -> (the code group, the plan: per part the witness call's own operands), made in the order in
-        which the kind's code call and plan refuse, with fit(plan, D, room) called where the kind compares the plan with the segments
-        (D: the table's rows; room: what a part holds, in words for the message).  witgen: the hal's witness call;
-        accum(seg, code, data) -> the accum group.  Both trees are the WHOLE page-out's for every part, so the parts could be sealed
-        in any order, or on several ranks.  The code group and its control root are built once and the data buffer is reused.
-        -> the receipts, in the order of the parts."""
-        segs = list(segs)
-        if not segs:
-            raise _hal.HalError(f"{who}: no segment")
-        po2, zk = segs[0].po2, segs[0].zk_cycles
-        if any((s.po2, s.zk_cycles) != (po2, zk) for s in segs):
-            raise _hal.HalError(f"{who}: the parts share one code group: every segment must have the same (po2, zk_cycles)")
-        if not isinstance(proof, _hal.Buffer):
-            proof = self.hal.copy_from("image_proof", np.ascontiguousarray(proof, dtype=np.uint32).reshape(-1))
-
-        def fit(plan, D, room):
-            if len(segs) != len(plan):
-                raise _hal.HalError(f"{who}: {len(segs)} segments, but a table of {D} rows takes {len(plan)} parts of {room} at po2 {po2}")
-
-        code, plan = open_chain(proof, po2, zk, fit)
-        control_root = self.code_root(code, po2)
-        data = self.hal.alloc_elem("data", self.group_sizes()[2] << po2)
-        receipts = []
-        for seg, part in zip(segs, plan):
-            out = witgen(self.circuit, po2, zk, code, proof, proof_words, nodes_before, nodes_after, *part, data, seg.noise_seed)
-            receipt = self.seal_with_accum(seg, code, data, out, accum(seg, code, data), check=check)
-            receipt.control_root = control_root.copy()
-            receipts.append(receipt)
-        return receipts
-
-    def _open_path_chain(self, code_call):
-        """open_chain of the circuits that lay out one path per update: the plan is p2_page.parts, a part's operand its first update"""
-        def open_chain(proof, po2, zk, fit):
-            from .circuits import p2_page
-            header = proof.slice(0, min(3, proof.size())).to_vec()
-            W, D = (int(header[1]), int(header[2])) if header.size > 2 else (0, 0)
-            code = code_call(self.circuit, po2, zk, W)                         # refuses a shape without a path slot (P2-PAGE-ordered: and h > 26)
-            plan = [(first,) for first, _count in p2_page.parts(po2, zk, W, D)]
-            fit(plan, D, f"{self.hal.page_circuit_slots(po2, zk, W)} slots")
-            return code, plan
-        return open_chain
+        return _page_seal.seal_chain("seal_page_out", self, 5, [seg], proof, proof_words, nodes_before, nodes_after, check, single=True)[0]
 
     def seal_page_out_parts(self, segs, proof, proof_words: int, nodes_before, nodes_after, check: bool = False) -> list:
         """Seal a page-out of ANY size with P2-PAGE as a chain of parts (circuits/p2_page.py `parts`): part p lays out the updates
         [first, first + count) of the ZKU1 proof's table (zkh_page_circuit_witgen_part), and its receipt's output is the root before
         update `first` ‖ the root after the part's last update, so part p + 1 opens the root part p left (`verify_page_out_chain`).
-        segs: one Segment per part (_seal_page_chain); the other operands are seal_page_out's.  -> the receipts, in the order of the
+        segs: one Segment per part (page_seal.seal_chain); the other operands are seal_page_out's.  -> the receipts, in the order of the
         parts."""
-        return self._seal_page_chain("seal_page_out_parts", segs, proof, proof_words, nodes_before, nodes_after, check,
-                                     self._open_path_chain(self.hal.page_circuit_code), self.hal.page_circuit_witgen_part,
-                                     lambda seg, code, data: self.syn_accumulate(seg, data))
+        return _page_seal.seal_chain("seal_page_out_parts", self, 5, segs, proof, proof_words, nodes_before, nodes_after, check)
 
     def seal_page_out_ordered(self, segs, proof, proof_words: int, nodes_before, nodes_after, check: bool = False) -> list:
         """Seal a page-out of any size with P2-PAGE-ordered (this prover's circuit: circuits/p2_page_ordered.py) as a chain of parts:
@@ -448,9 +394,7 @@ class SegmentProver:
         hi of its run of updates (zkh_page_ordered_witgen), so part p + 1 opens the root and starts at the `hi` part p left
         (`verify_page_ordered_chain`).  The operands and the plan (p2_page.parts) are seal_page_out_parts'.  -> the receipts, in the
         order of the parts."""
-        return self._seal_page_chain("seal_page_out_ordered", segs, proof, proof_words, nodes_before, nodes_after, check,
-                                     self._open_path_chain(self.hal.page_ordered_code), self.hal.page_ordered_witgen,
-                                     lambda seg, code, data: self.syn_accumulate(seg, data))
+        return _page_seal.seal_chain("seal_page_out_ordered", self, 6, segs, proof, proof_words, nodes_before, nodes_after, check)
 
     def seal_page_out_tree(self, segs, proof, proof_words: int, nodes_before, nodes_after, check: bool = False, plan: str = "host") -> list:
         """Seal a page-out of any size with P2-TREE (this prover's circuit: circuits/p2_tree.py, built with arguments=p2_tree.arguments())
@@ -461,314 +405,11 @@ class SegmentProver:
         there, and check=True names the key.  The other operands are seal_page_out_parts'; the control root does not depend on the
         image's size.  plan="device" plans where the table lies (zkh_page_tree_plan_device over (proof, 5 + h, D)): only the header is
         read back; the parts, and so the receipts, are the same.  -> the receipts, in the order of the parts."""
-        who = "seal_page_out_tree"
-        return self._seal_page_chain(who, segs, proof, proof_words, nodes_before, nodes_after, check, self._open_tree_chain(who, plan, proof_words),
-                                     self.hal.page_tree_witgen, lambda seg, code, data: self.args_accumulate(seg, code, data, check=check))
-
-    def _open_tree_chain(self, who: str, where: str, proof_words: int):
-        """open_chain of the circuits that lay out one block per dirty node (P2-TREE, P2-TREE-tied): the plan is zkh_page_tree_plan's, made
-        on the "host" or on the "device" (`where`), a part's operands its (first, count)"""
-        if where not in ("host", "device"):
-            raise _hal.HalError(f'{who}: plan="{where}" (the plan is made on the "host" or on the "device")')
-
-        def open_chain(proof, po2, zk, fit):
-            if not self.circuit.has_arguments():
-                raise _hal.HalError(f"{who}: the prover was built without P2-TREE's arguments (arguments=p2_tree.arguments())")
-            header = proof.slice(0, min(5, proof.size())).to_vec()
-            W, D, h = (int(header[1]), int(header[2]), int(header[4])) if header.size > 4 else (0, 0, 0)
-            if 5 + h + 3 * D > min(proof_words, proof.size()):
-                raise _hal.HalError(f"{who}: a proof of {proof_words} words does not hold its header and a table of {D} rows")
-            if where == "device":                                              # the table stays where zkh_page_out_proof left it
-                plan = self.hal.page_tree_plan_device(po2, zk, W, proof, 5 + h, D)
-            else:
-                addrs = proof.slice(5 + h, 3 * D).to_vec()[::3] if D else np.zeros(0, dtype=np.uint32)
-                plan = self.hal.page_tree_plan(po2, zk, W, addrs)              # refuses W <= 16, B < h, addresses out of order
-            fit(plan, D, f"{((1 << po2) - zk) // 31} block slots")
-            return self.hal.page_tree_code(self.circuit, po2, zk), plan
-
-        return open_chain
+        return _page_seal.seal_chain("seal_page_out_tree", self, 7, segs, proof, proof_words, nodes_before, nodes_after, check, plan)
 
     def prove_segment(self, seg: Segment) -> SegmentReceipt:
         code, data, out = self.witgen(seg)
         return self.seal(seg, code, data, out)
-
-
-def link_page_parts(who: str, parts, root_before=None, first_lo=None, last_hi=None) -> tuple:
-    """The links of a chain of page-out seals, HOST ONLY: what verify_page_out_chain, verify_page_ordered_chain and
-    link_page_tree_chain check once a seal is verified -> (root_before, root_after) of the whole page-out, and hi where the parts have
-    one.  parts: per part (the root it opens, the root it leaves) or (…, lo, hi), lo and hi as integers; an iterator is consumed part
-    by part, so a caller may verify each seal as it hands it over.  who: the prefix of every message.  Part p + 1 must open the root
-    part p left; with a `root_before`, part 0 must open it.  Parts with lo and hi: every lo and hi must be at most 2^29 (what the
-    circuits' 29-bit gaps are sound for); part p + 1 must start at the hi part p left; first_lo = (the lo part 0 must have, the words
-    that say why); last_hi, if given = (the bound of the last hi, the words that say why).  Raises HalError, one message per cause."""
-    from .circuits.p2_blocks import GAP_BITS
-    fmt = lambda r: " ".join(f"{int(w):08x}" for w in r)
-    chain = []
-    for p, part in enumerate(parts):
-        for name, v in zip(("lo", "hi"), part[2:]):
-            if v > 1 << GAP_BITS:
-                raise _hal.HalError(f"{who}: part {p}: {name} {v} is above 2^{GAP_BITS}, the bound the order check is sound for")
-        chain.append((np.array(part[0], dtype=np.uint32), np.array(part[1], dtype=np.uint32)) + tuple(part[2:]))
-    if not chain:
-        raise _hal.HalError(f"{who}: no receipt (a page-out of no rows still has one part)")
-    ordered = len(chain[0]) > 2
-    if ordered and chain[0][2] != first_lo[0]:
-        raise _hal.HalError(f"{who}: part 0 starts at lo {chain[0][2]}, not {first_lo[1]}")
-    if root_before is not None and not np.array_equal(chain[0][0], np.asarray(root_before, dtype=np.uint32)):
-        raise _hal.HalError(f"{who}: part 0 opens root {fmt(chain[0][0])}, not root_before {fmt(root_before)}")
-    for p in range(len(chain) - 1):
-        if not np.array_equal(chain[p + 1][0], chain[p][1]):
-            raise _hal.HalError(f"{who}: part {p + 1} opens root {fmt(chain[p + 1][0])}, but part {p} left root {fmt(chain[p][1])}")
-        if ordered and chain[p + 1][2] != chain[p][3]:
-            raise _hal.HalError(f"{who}: part {p + 1} starts at lo {chain[p + 1][2]}, but part {p} left hi {chain[p][3]}")
-    if ordered and last_hi is not None and chain[-1][3] > last_hi[0]:
-        raise _hal.HalError(f"{who}: the last part leaves hi {chain[-1][3]}, above {last_hi[1]}")
-    return (chain[0][0], chain[-1][1]) + chain[-1][3:]
-
-
-def _verified_parts(receipts, desc, control_root, decode=None):
-    """per receipt, once its seal is verified against the description desc() and `control_root`: the operands of link_page_parts"""
-    hc = None
-    for r in receipts:
-        hc = hc or _hal.HostCircuit(desc())
-        hc.verify_segment(r.seal, control_root)
-        yield (r.seal[:8], r.seal[8:16]) + ((decode(r.seal[16]), decode(r.seal[17])) if decode else ())
-
-
-def verify_page_out_chain(receipts, control_root, root_before=None) -> Tuple[np.ndarray, np.ndarray]:
-    """Verify the chain of P2-PAGE seals of one page-out (SegmentProver.seal_page_out_parts), HOST ONLY -> (root_before, root_after) of
-    the whole page-out.  Every seal is verified against P2-PAGE's description and `control_root` (the code group's: one for all
-    parts); part p + 1 must open the root part p left; with a `root_before`, part 0 must open it.  Raises HalError on a seal the
-    verifier rejects, on a chain that does not link, on another first root, and on an empty list."""
-    from .circuits import p2_page
-    return link_page_parts("verify_page_out_chain", _verified_parts(receipts, p2_page.p2_page_circuit, control_root), root_before)
-
-
-def verify_page_ordered_chain(receipts, control_root, root_before=None) -> Tuple[np.ndarray, np.ndarray, int]:
-    """Verify the chain of P2-PAGE-ordered seals of one page-out (SegmentProver.seal_page_out_ordered), HOST ONLY -> (root_before,
-    root_after, hi) of the whole page-out: its live updates have strictly increasing addresses, the last of them hi - 1 (hi = 0: none).
-    Every seal is verified against P2-PAGE-ordered's description and `control_root` (one for all parts); every lo and hi must decode
-    to at most 2^29 (what the circuit's 29-bit gaps are sound for); part 0 must have lo = 0; part p + 1 must open the root part p left
-    and start at the hi part p left; with a `root_before`, part 0 must open it.  Raises HalError, one message per cause."""
-    from .circuits import p2_page_ordered as po
-    return link_page_parts("verify_page_ordered_chain", _verified_parts(receipts, po.p2_page_ordered_circuit, control_root, po.decode), root_before,
-                           first_lo=(0, "0: addresses below it are not covered"))
-
-
-def link_page_tree_chain(outs, h: int, root_before=None) -> Tuple[np.ndarray, np.ndarray, int]:
-    """What verify_page_tree_chain checks of the parts' `out` words (18 each) once every seal is verified -> (root_before, root_after,
-    hi).  Every lo and hi must decode to at most 2^29; part 0 must have lo = 2^(h-1), the id of the first pair of leaves; part p + 1
-    must open the root part p left and start at the hi part p left; the last hi must be at most 2^h, so every pair block's id lies in
-    [2^(h-1), 2^h): h - 1 levels below the root; with a `root_before`, part 0 must open it.  Raises HalError, one message per cause."""
-    from .circuits import p2_tree as pt
-    who = "verify_page_tree_chain"
-    if not pt.MIN_H <= h <= pt.MAX_H:
-        raise _hal.HalError(f"{who}: h {h} ({pt.MIN_H} .. {pt.MAX_H})")
-    parts = ((out[:8], out[8:16], pt.decode(out[pt.OUT_LO]), pt.decode(out[pt.OUT_HI])) for out in outs)
-    return link_page_parts(who, parts, root_before, first_lo=(1 << (h - 1), f"2^{h - 1} = {1 << (h - 1)}, the id of the first pair of leaves of a tree of height {h}"),
-                           last_hi=(1 << h, f"2^{h} = {1 << h}: a pair block outside a tree of height {h}"))
-
-
-def verify_page_tree_chain(receipts, control_root, h: int, root_before=None) -> Tuple[np.ndarray, np.ndarray, int]:
-    """Verify the chain of P2-TREE seals of one page-out (SegmentProver.seal_page_out_tree), HOST ONLY -> (root_before, root_after, hi)
-    of the whole page-out.  Every seal is verified against P2-TREE's description and `control_root` (one per (po2, zk_cycles), for
-    every image size); then the parts' outputs must link (`link_page_tree_chain`): the verifier is told h, the height of the image's
-    tree.  Raises HalError on a seal the verifier rejects, and one message per cause on a chain that does not link."""
-    from .circuits import p2_tree as pt
-    receipts = list(receipts)
-    if not receipts:
-        raise _hal.HalError("verify_page_tree_chain: no receipt (a page-out of no rows still has one part)")
-    hc = _hal.HostCircuit(pt.p2_tree_circuit())
-    for r in receipts:
-        hc.verify_segment(r.seal, control_root)
-    return link_page_tree_chain([r.seal[:pt.OUT_WORDS] for r in receipts], h, root_before)
-
-
-TIE_WORDS = 12                                  # alpha (4) ‖ beta (4) ‖ F (4): the last words of `out` of every seal of a tied group
-
-
-def _fmt_words(w) -> str:
-    return " ".join(f"{int(x):08x}" for x in w)
-
-
-def seal_tied(seg_prover: SegmentProver, seg: Segment, code, data, out_prefix, page_prover: SegmentProver, page_segs, proof, proof_words: int,
-              nodes_before, nodes_after, check: bool = False, check_table: bool = True):
-    """Seal a paging segment and the page-out of its memory as ONE tied group (DESIGN.md §2 "THE TIE") -> (the segment's receipt, [the
-    parts' receipts]): the seals share a bus under a challenge drawn from all their data roots, and `verify_tied` accepts them only
-    together.  seg_prover: a prover of an open-bus paging circuit (SYN-LOOKUP-tied, built with its arguments); code, data: the segment's
-    traces on the device, derived and reduced (what seal_host_witness hands its accumulate); out_prefix: the segment's `out` words before
-    alpha.  page_prover: a prover of P2-PAGE-tied with p2_page_tied.arguments(); page_segs, proof, proof_words, nodes_before, nodes_after:
-    seal_page_out_ordered's operands.  Two passes, so that one part's traces are held at a time:
-      1. the roots: the segment's data root (zkh_data_root); per part the witness, its data root, and the buffer is reused; the
-         challenge alpha ‖ beta = hal.tie_challenge(the roots, the segment's first).
-      between, with check_table: the segment's open total must be hal.table_fingerprint of the proof's table under that challenge, else
-         HalError "the proof's table is not the segment's page table": no part is sealed on a table that cannot cancel.
-      2. the segment and then every part: the part's witness again (the same noise key gives the same trace, hence the same root),
-         accumulate_open, out = prefix ‖ challenge ‖ total, zkh_prove_begin, with `check` check_witness, zkh_prove_finish.
-    Every receipt carries its code group's root as `control_root`."""
-    from .circuits import p2_page_tied as pt
-    return _seal_tied_group("seal_tied", seg_prover, seg, code, data, out_prefix, page_prover, page_segs, proof, proof_words, nodes_before, nodes_after, check,
-                            check_table, page_prover._open_path_chain(seg_prover.hal.page_ordered_code), seg_prover.hal.page_ordered_witgen,
-                            lambda words, _h: words[:pt.PREFIX_WORDS])
-
-
-def seal_tied_tree(seg_prover: SegmentProver, seg: Segment, code, data, out_prefix, page_prover: SegmentProver, page_segs, proof, proof_words: int,
-                   nodes_before, nodes_after, check: bool = False, check_table: bool = True, plan: str = "host"):
-    """`seal_tied` with P2-TREE-tied parts (circuits/p2_tree_tied.py): the page-out side of the group is one block per DIRTY NODE, not one
-    path per word.  page_prover: a prover of P2-TREE-tied with p2_tree_tied.arguments(); the plan is seal_page_out_tree's, made on the
-    "host" or on the "device" (`plan`); every other operand, both passes and the fingerprint check between them are seal_tied's.  A part's
-    out = the witness call's 18 words ‖ p2_tree_tied.out_base(h) ‖ the challenge ‖ its open total.  -> (the segment's receipt, [the parts'
-    receipts]), for `verify_tied_tree`."""
-    from .circuits import p2_tree_tied as tt
-    who = "seal_tied_tree"
-    return _seal_tied_group(who, seg_prover, seg, code, data, out_prefix, page_prover, page_segs, proof, proof_words, nodes_before, nodes_after, check,
-                            check_table, page_prover._open_tree_chain(who, plan, proof_words), seg_prover.hal.page_tree_witgen,
-                            lambda words, h: np.concatenate([words[:tt.PREFIX_WORDS], [tt.out_base(h)]]).astype(np.uint32))
-
-
-def _seal_tied_group(who: str, seg_prover: SegmentProver, seg: Segment, code, data, out_prefix, page_prover: SegmentProver, page_segs, proof, proof_words: int,
-                     nodes_before, nodes_after, check: bool, check_table: bool, open_chain, witgen, part_prefix):
-    """The two passes of `seal_tied` and `seal_tied_tree`.  open_chain(proof, po2, zk, fit) -> (the page-out's code group, the plan: per
-    part the witness call's own operands), as _seal_page_chain takes it; witgen: the hal's witness call of the page-out circuit;
-    part_prefix(the words it returns, h) -> the part's `out` words before alpha."""
-    hal = seg_prover.hal
-    for name, p in (("segment", seg_prover), ("page-out", page_prover)):
-        if p.circuit.open_bus() is None:
-            raise _hal.HalError(f"{who}: the {name} prover's circuit has no open bus (its arguments hold no OPEN record)")
-    page_segs = list(page_segs)
-    if not page_segs:
-        raise _hal.HalError(f"{who}: no segment for the page-out (a page-out of no rows still has one part)")
-    po2, zk = page_segs[0].po2, page_segs[0].zk_cycles
-    if any((s.po2, s.zk_cycles) != (po2, zk) for s in page_segs):
-        raise _hal.HalError(f"{who}: the parts share one code group: every segment must have the same (po2, zk_cycles)")
-    if not isinstance(proof, _hal.Buffer):
-        proof = hal.copy_from("image_proof", np.ascontiguousarray(proof, dtype=np.uint32).reshape(-1))
-
-    def fit(plan, D, room):
-        if len(page_segs) != len(plan):
-            raise _hal.HalError(f"{who}: {len(page_segs)} segments, but a table of {D} rows takes {len(plan)} parts of {room} at po2 {po2}")
-
-    page_code, plan = open_chain(proof, po2, zk, fit)
-    head = proof.slice(0, 5).to_vec()
-    rows, h, table_at = int(head[2]), int(head[4]), 5 + int(head[4])
-    page_data = hal.alloc_elem("data", page_prover.group_sizes()[2] << po2)
-
-    def part_witness(s, part):
-        return witgen(page_prover.circuit, po2, zk, page_code, proof, proof_words, nodes_before, nodes_after, *part, page_data, s.noise_seed)
-
-    # pass one: the data roots, the segment's first
-    roots = [seg_prover.data_root(data, seg.po2)]
-    for s, part in zip(page_segs, plan):
-        part_witness(s, part)
-        roots.append(page_prover.data_root(page_data, po2))
-    challenge = _hal.tie_challenge(np.concatenate(roots))
-
-    def open_seal(prover, s, code, data, prefix, control_root):
-        accum = hal.alloc_elem("accum", prover.group_sizes()[0] << s.po2)
-        total = hal.accumulate_open(prover.circuit, s.po2, s.zk_cycles, s.noise_seed, code, data, challenge, accum)
-        out = np.concatenate([np.asarray(prefix, dtype=np.uint32).reshape(-1), challenge, total]).astype(np.uint32)
-        if out.size != prover.out_size():
-            raise _hal.HalError(f"{who}: {out.size} out words (a prefix of {out.size - TIE_WORDS}, alpha, beta, the total), the circuit has {prover.out_size()}")
-        return accum, total, out, control_root
-
-    seg_accum, seg_total, seg_out, _ = open_seal(seg_prover, seg, code, data, out_prefix, None)
-    if check_table:
-        want = hal.table_fingerprint(proof, table_at, rows, challenge)
-        if not np.array_equal(seg_total, want):
-            raise _hal.HalError(f"{who}: the proof's table is not the segment's page table: the segment's open total is {_fmt_words(seg_total)}, "
-                                f"the fingerprint of the proof's {rows} rows is {_fmt_words(want)}")
-    # pass two: the seals
-    seg_receipt = seg_prover.seal_with_accum(seg, code, data, seg_out, lambda _mix: seg_accum, check=check)
-    seg_receipt.control_root = seg_prover.code_root(code, seg.po2)
-    del seg_accum
-    page_root = page_prover.code_root(page_code, po2)
-    receipts = []
-    for s, part in zip(page_segs, plan):
-        prefix = part_prefix(part_witness(s, part), h)
-        accum, _total, out, _ = open_seal(page_prover, s, page_code, page_data, prefix, None)
-        receipt = page_prover.seal_with_accum(s, page_code, page_data, out, lambda _mix, accum=accum: accum, check=check)
-        receipt.control_root = page_root.copy()
-        receipts.append(receipt)
-    return seg_receipt, receipts
-
-
-def verify_tied(seg_receipt, seg_circuit, seg_control_root, part_receipts, page_control_root, root_before=None) -> Tuple[np.ndarray, np.ndarray, int]:
-    """Verify a tied group (`seal_tied`), HOST ONLY -> (root_before, root_after, hi): the page table of the segment `seg_receipt` seals,
-    applied in order to the image under root_before, leaves root_after, its last address hi - 1 (hi = 0: the segment touched no memory).
-    seg_circuit: the segment circuit's description (its `out` ends on alpha ‖ beta ‖ F, as every tied circuit's does); the parts are
-    P2-PAGE-tied's.  On top of the ordered chain (`link_page_parts`, as verify_page_ordered_chain) it makes the four checks of the design:
-    every seal verifies against its control root; every seal states the challenge that `hal.tie_challenge` gives for the data roots read
-    out of the seals themselves, the segment's first (one comparison per seal: they then all state the same one); the totals F of all
-    seals add up to zero in Fp4.  Raises HalError, one line per cause, naming the seal and the two values that differ."""
-    from .circuits import p2_page_tied as pt
-    who = "verify_tied"
-    part_receipts = list(part_receipts)
-    seg_hc, seg_out_size = _verified_tied_segment(who, seg_receipt, seg_circuit, seg_control_root)
-    linked = link_page_parts(who, _verified_parts(part_receipts, pt.p2_page_tied_circuit, page_control_root, pt.decode), root_before,
-                             first_lo=(0, "0: addresses below it are not covered"))
-    page_hc = _hal.HostCircuit(pt.p2_page_tied_circuit())
-    _check_tied_totals(who, [("the segment", seg_hc, seg_receipt.seal, seg_out_size)] + [(f"part {p}", page_hc, r.seal, pt.OUT_WORDS) for p, r in enumerate(part_receipts)])
-    return linked
-
-
-def _verified_tied_segment(who: str, seg_receipt, seg_circuit, seg_control_root):
-    """the segment's seal of a tied group, verified against its control root -> (its HostCircuit, its `out` words)"""
-    desc = np.asarray(seg_circuit, dtype=np.uint32)
-    seg_hc, seg_out_size = _hal.HostCircuit(desc), int(desc[7])
-    if seg_out_size < TIE_WORDS:
-        raise _hal.HalError(f"{who}: the segment circuit has {seg_out_size} out words: no room for alpha, beta and the total")
-    seg_hc.verify_segment(seg_receipt.seal, seg_control_root)
-    return seg_hc, seg_out_size
-
-
-def _check_tied_totals(who: str, seals) -> None:
-    """The challenge and total checks of a tied group whose seals are verified.  seals: (name, HostCircuit, seal, out words) per seal, the
-    segment's first.  Every seal must state the challenge `hal.tie_challenge` gives for the data roots read out of the seals in that
-    order, and the totals F must add up to zero in Fp4.  Raises HalError, one line per cause."""
-    want = _hal.tie_challenge(np.concatenate([hc.seal_data_root(seal) for _, hc, seal, _ in seals]))
-    total = np.zeros(4, dtype=np.uint64)
-    for name, _, seal, out_size in seals[1:] + seals[:1]:                     # a part that was swapped in is named before the segment
-        stated = np.asarray(seal[out_size - TIE_WORDS:out_size - 4], dtype=np.uint32)
-        if not np.array_equal(stated, want):
-            raise _hal.HalError(f"{who}: {name}: its challenge {_fmt_words(stated)} is not the one the data roots give, {_fmt_words(want)}")
-        total = (total + np.asarray(seal[out_size - 4:out_size], dtype=np.uint64)) % np.uint64(_hal.P)
-    if total.any():
-        raise _hal.HalError(f"{who}: the totals do not cancel: the segment's F plus the parts' is {_fmt_words(total)}, not zero: the parts' rows are not "
-                            f"the segment's page table")
-
-
-def link_tied_tree_chain(outs, h: int, root_before=None) -> Tuple[np.ndarray, np.ndarray, int]:
-    """What verify_tied_tree checks of the parts' `out` words (31 each) besides the group's challenge and totals -> (root_before, root_after,
-    hi): `link_page_tree_chain` on their first 18 words, then every part's out[18] must be p2_tree_tied.out_base(h), the word that turns a
-    pair block's id into its addresses.  Raises HalError, one message per cause."""
-    from .circuits import p2_tree_tied as tt
-    outs = [np.asarray(out, dtype=np.uint32) for out in outs]
-    linked = link_page_tree_chain([out[:tt.PREFIX_WORDS] for out in outs], h, root_before)
-    for p, out in enumerate(outs):
-        if int(out[tt.OUT_BASE]) != tt.out_base(h):
-            raise _hal.HalError(f"verify_tied_tree: part {p}: base {tt.decode(out[tt.OUT_BASE])} is not {1 << (h + 3)} = 16 * 2^{h - 1}, sixteen times the id of "
-                                f"the first pair of leaves of a tree of height {h}")
-    return linked
-
-
-def verify_tied_tree(seg_receipt, seg_circuit, seg_control_root, part_receipts, page_control_root, h: int, root_before=None) -> Tuple[np.ndarray, np.ndarray, int]:
-    """Verify a tied group whose page-out side is P2-TREE-tied's (`seal_tied_tree`), HOST ONLY -> (root_before, root_after, hi): the page
-    table of the segment `seg_receipt` seals, applied to the image under root_before, leaves root_after; hi is one more than the id of
-    the last pair of leaves it touches.  The verifier is told h, the height of the image's tree.  Every seal verifies against its
-    control root; the parts link as P2-TREE's do and state base = 16 * 2^(h-1) (`link_tied_tree_chain`); then `verify_tied`'s checks of
-    the challenge and of the totals.  Raises HalError, one line per cause."""
-    from .circuits import p2_tree_tied as tt
-    who = "verify_tied_tree"
-    part_receipts = list(part_receipts)
-    seg_hc, seg_out_size = _verified_tied_segment(who, seg_receipt, seg_circuit, seg_control_root)
-    if not part_receipts:
-        raise _hal.HalError(f"{who}: no receipt (a page-out of no rows still has one part)")
-    page_hc = _hal.HostCircuit(tt.p2_tree_tied_circuit())
-    for r in part_receipts:
-        page_hc.verify_segment(r.seal, page_control_root)
-    linked = link_tied_tree_chain([r.seal[:tt.OUT_WORDS] for r in part_receipts], h, root_before)
-    _check_tied_totals(who, [("the segment", seg_hc, seg_receipt.seal, seg_out_size)] + [(f"part {p}", page_hc, r.seal, tt.OUT_WORDS) for p, r in enumerate(part_receipts)])
-    return linked
 
 
 def _generate_control_roots(po2s=range(13, 25)) -> None:
