@@ -454,12 +454,27 @@ const char* zkh_page_out_tree(zkh_ctx*, const zkh_circuit*, size_t po2, size_t z
  * parents, one Poseidon2 lane per hash_pair); one read-back fetches a 32-word record: the lowest index of every cause (atomicMin:
  * the result does not depend on arrival order; there are no other atomics), the values its message prints, both top digests.  No
  * kernel reads a proof word at or past `words` whatever the proof holds: a stage does nothing when an earlier refusal removes its
- * precondition.  Scratch comes from the context's pool, a small multiple of the proof's own size.  D = 0 launches nothing. */
+ * precondition.  Scratch comes from the context's pool, a small multiple of the proof's own size.  D = 0 launches nothing.
+ * zkh_image_proof_nodes is zkh_image_proof_walk (its stages, its verdicts: the same root_after, or the same message after
+ * "image_proof_nodes: "), and on success it also leaves in `dirty` the DIRTY-NODE TABLE of the page-out: every digest the walk
+ * recomputes, which is everything a P2-TREE block of any part can ask for (zkh_page_tree_witgen_nodes).  Words (csrc/zkn1.h; the numpy
+ * twin: logup.reference_page_out_nodes): 'ZKN1', W, D, h, n_1 .. n_h; then per layer k = 1 .. h (layer 0 the leaves, h the root) the
+ * n_k heap ids of the layer's dirty nodes, increasing (the walk's list S_k), and n_k records of 32 words, the four digests of a node's
+ * two children: left old ‖ left new ‖ right old ‖ right new.  A clean child has old = new, the proof's sibling; the children of a
+ * layer-1 node are two leaves, 16 memory words.  The table's length is 4 + h + 33 sum n_k; zkh_image_dirty_words(W, D) = 4 + h +
+ * 33 sum_k min(D, L >> k) bounds it for every table of D rows, a function of (W, D) alone (0 for W = 0).  `dirty` shorter than that
+ * bound, or a bound past 2^32 - 1 words, is refused after the header's refusals and before any launch.  root_after and `dirty` are
+ * written only on success (the table is built in scratch of the bound's size and copied once the record has come back clean); words of
+ * `dirty` past the table's length are never written.  No atomics beyond the walk's record, one writer per word.  An empty table (D = 0)
+ * is refused where the walk would succeed: "an empty table (D = 0) has no dirty nodes: its proof is the header alone and holds no
+ * node, not even the root's children; such a page-out is sealed from the tree (zkh_page_tree_witgen)". */
 size_t zkh_image_proof_words(size_t image_words, size_t pages);
+size_t zkh_image_dirty_words(size_t image_words, size_t pages);
 const char* zkh_page_out_proof(zkh_ctx*, const zkh_circuit*, size_t po2, size_t zk_cycles, const zkh_buf* data, const zkh_buf* image, const zkh_buf* nodes,
                                zkh_buf* proof);
 const char* zkh_image_proof_verify(const uint32_t* proof, size_t words, const uint32_t root_before[8], uint32_t root_after[8]);
 const char* zkh_image_proof_walk(zkh_ctx*, const zkh_buf* proof, size_t words, const uint32_t root_before[8], uint32_t root_after[8]);
+const char* zkh_image_proof_nodes(zkh_ctx*, const zkh_buf* proof, size_t words, const uint32_t root_before[8], uint32_t root_after[8], zkh_buf* dirty);
 /* P2-PAGE (circuit kind 5, zeth_amd/circuits/p2_page.py; csrc/page_circuit.hip): the circuit that consumes a ZKU1 proof's table.  Its
  * seal proves "D single-word updates, applied one after the other, take root_before to root_after": out = root_before (8) ‖ root_after
  * (8).  Every update is one Merkle path of h = log2 L blocks of 31 rows (P2-JOIN's rows), the old path and the new one side by side;
@@ -569,7 +584,20 @@ const char* zkh_page_ordered_witgen(zkh_ctx*, const zkh_circuit*, size_t po2, si
  * of D rows"; then, from the check pass over the whole table and before any tree is indexed: "row R: address A outside the image of W
  * words", "row R: address A does not follow a smaller one (row R-1: address A')", "the part [F, E) splits a pair of leaves: rows R-1
  * and R write the same 16 words", "the part [F, E) has N dirty nodes, but po2 P leaves B block slots".  A table that does not match
- * the trees is not refused here: its bus does not balance, zkh_accumulate refuses it and zkh_check_bus names the key. */
+ * the trees is not refused here: its bus does not balance, zkh_accumulate refuses it and zkh_check_bus names the key.
+ * zkh_page_tree_witgen_nodes: the same witness, cell for cell, from (proof, dirty) alone: zkh_page_tree_witgen's operands with the
+ * dirty-node table zkh_image_proof_nodes left (THE UPDATE'S PROOF above) in place of the two trees, for a rank that holds neither.
+ * The source rule is the same (a child below the part's edge address is the new tree's, one above it the old tree's, the one that
+ * holds it comes from the edge chain); a block finds its node by ONE binary search of its layer's ids and takes the record's old or
+ * new digest.  Refusals after "page_tree_witgen_nodes: ": zkh_page_tree_witgen's in its order, with, in the place of the tree
+ * buffers', the table's header against the buffer's length and the proof, all on the host before any launch: "dirty nodes of N
+ * words: the header alone has 4"; "dirty nodes: bad magic .."; "dirty nodes: h H, but an image of W words has h H'"; "dirty nodes: N
+ * nodes on layer K, but D rows dirty at most C of its X"; "dirty nodes of N words, but the header describes at least M"; "dirty nodes
+ * of D rows over W words (h H), but the proof has D' rows over W' words (h H')"; "an empty table (D = 0) has no dirty nodes; such a
+ * page-out is sealed from the tree"; and last, from the one read-back: "node N of layer K is not in the dirty nodes (the table is
+ * another proof's)", N the lowest such heap id (one atomicMin on the record), after which no cell of a block is written.  No index
+ * read from `dirty` is used before it is bounded by a count the host has checked.  A table with the right ids and other digests is
+ * not refused here, as a tree that does not match is not: the bus does not balance. */
 const char* zkh_page_tree_code(zkh_ctx*, const zkh_circuit*, size_t po2, size_t zk_cycles, zkh_buf* code);
 const char* zkh_page_tree_plan(size_t po2, size_t zk_cycles, size_t image_words, const uint32_t* addrs, size_t D, size_t* parts, size_t parts_cap,
                                size_t* n_parts);
@@ -578,6 +606,8 @@ const char* zkh_page_tree_plan_device(zkh_ctx*, size_t po2, size_t zk_cycles, si
 const char* zkh_page_tree_witgen(zkh_ctx*, const zkh_circuit*, size_t po2, size_t zk_cycles, const zkh_buf* code, const zkh_buf* proof, size_t proof_words,
                                  const zkh_buf* nodes_before, const zkh_buf* nodes_after, size_t first, size_t count, zkh_buf* data, uint32_t out[18],
                                  const uint32_t noise_key[8]);
+const char* zkh_page_tree_witgen_nodes(zkh_ctx*, const zkh_circuit*, size_t po2, size_t zk_cycles, const zkh_buf* code, const zkh_buf* proof, size_t proof_words,
+                                       const zkh_buf* dirty, size_t first, size_t count, zkh_buf* data, uint32_t out[18], const uint32_t noise_key[8]);
 /* Everything a circuit's arguments derive, in the one order in which it is sound: sorted copies, then columns, then links, then
  * multiplicities (a LIMBS / ORDER record may read a sorted copy's column, and the multiplicities count the limbs that the records and
  * the links derive).  Call it after the data upload and before zkh_prove_begin: what it writes belongs to the data group.  It runs

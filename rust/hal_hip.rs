@@ -468,6 +468,22 @@ impl HipCircuitHal {
         after
     }
 
+    /// The bound on the words of the dirty-node table of a page-out of `pages` rows over an image of `image_words` words
+    /// (`zkh_image_dirty_words`): 4 + h + 33 sum_k min(pages, L >> k).
+    pub fn image_dirty_words(image_words: usize, pages: usize) -> usize {
+        unsafe { sys::zkh_image_dirty_words(image_words, pages) }
+    }
+
+    /// `image_proof_walk` that keeps what it recomputes (`zkh_image_proof_nodes`): on success `dirty` (at least `image_dirty_words(W, D)`
+    /// words) starts with the dirty-node table of the page-out, what `page_tree_witgen_nodes` reads in place of the two trees.  The
+    /// walk's root and the walk's message per cause; `dirty` is written only on success; an empty table (D = 0) panics: it is sealed
+    /// from the tree.
+    pub fn image_proof_nodes(&self, proof: &HipBuffer<u32>, words: usize, root_before: &[u32; 8], dirty: &HipBuffer<u32>) -> [u32; 8] {
+        let mut after = [0u32; 8];
+        ffi(|| unsafe { sys::zkh_image_proof_nodes(self.hal.ctx.0, proof.raw, words, root_before.as_ptr(), after.as_mut_ptr(), dirty.raw) });
+        after
+    }
+
     /// The code group of P2-PAGE, the circuit that seals a page-out from root to root (`zkh_page_circuit_code`): a function of the trace's
     /// size and of the tree height of an image of `image_words` words.  `self` holds the P2-PAGE description.  Panics on a circuit of
     /// another shape, on `image_words <= 8`, and on a trace without room for one path.
@@ -577,6 +593,19 @@ impl HipCircuitHal {
         let mut out = [0u32; 18];
         ffi(|| unsafe { sys::zkh_page_tree_witgen(self.hal.ctx.0, self.circuit, po2, sys::ZK_CYCLES, code.raw, proof.raw, words, nodes_before.raw,
                                                   nodes_after.raw, first, count, data.raw, out.as_mut_ptr(), noise_key.map_or(std::ptr::null(), |k| k.as_ptr())) });
+        out
+    }
+
+    /// `page_tree_witgen` from (proof, dirty) alone (`zkh_page_tree_witgen_nodes`): `dirty`, the table `image_proof_nodes` left, stands
+    /// in place of the two trees, for a rank that holds neither; the same cells and the same 18 words, for P2-TREE and P2-TREE-tied.
+    /// Panics as `page_tree_witgen` does, on a table whose header does not fit its buffer or the proof, and on a table of another proof
+    /// ("node N of layer K is not in the dirty nodes").
+    pub fn page_tree_witgen_nodes(&self, code: &HipBuffer<BabyBearElem>, proof: &HipBuffer<u32>, words: usize, dirty: &HipBuffer<u32>, first: usize, count: usize,
+                                  data: &HipBuffer<BabyBearElem>, steps: usize, noise_key: Option<&[u32; 8]>) -> [u32; 18] {
+        let po2 = steps.trailing_zeros() as usize;
+        let mut out = [0u32; 18];
+        ffi(|| unsafe { sys::zkh_page_tree_witgen_nodes(self.hal.ctx.0, self.circuit, po2, sys::ZK_CYCLES, code.raw, proof.raw, words, dirty.raw, first, count,
+                                                        data.raw, out.as_mut_ptr(), noise_key.map_or(std::ptr::null(), |k| k.as_ptr())) });
         out
     }
 

@@ -25,7 +25,9 @@ of M24's table by zkh_page_tree_plan_device next to the read-back of the table a
 at SYN-A's code and data widths next to zkh_eltwise_copy_elem over the same bytes, alternating; M27: the tie, zkh_data_root of a P2-PAGE-tied
 part next to its seal, zkh_accumulate_open next to zkh_accumulate, zkh_table_fingerprint next to a copy of the same bytes, alternating;
 M28: P2-TREE-tied, the witness and the seal of a kind-9 part next to the kind-7 part's, alternating, and the page-out side of a whole tied
-group under P2-TREE-tied next to P2-PAGE-tied's on the same table) on one MI355X, through the C ABI (HipHal).
+group under P2-TREE-tied next to P2-PAGE-tied's on the same table; M29: P2-TREE from the proof alone, zkh_image_proof_nodes next to
+zkh_image_proof_walk and part 0's witness from the dirty nodes next to part 0's witness from the two trees on M24's table, alternating, with
+the words of the table, of the proof and of the two trees, and the copy of the tree that keep_before makes) on one MI355X, through the C ABI (HipHal).
 
 Each line of output is one JSON object: the op, its shape, the average wall time of one call (stream drained on both
 sides of `reps` back-to-back calls), its ALGORITHMIC bytes (SURVEY.md §8a "B_alg": inputs read once + outputs written
@@ -1477,6 +1479,99 @@ def main() -> None:
                           "witness_tied_over_tree": round(med["witness_tree_tied_part_0"] / med["witness_tree_part_0"], 4),
                           "seal_tied_over_tree": round(med["seal_tree_tied_part"] / med["seal_tree_part"], 4),
                           "group_tree_tied_over_page_tied": round(group["tree_tied"]["total_ms"] / group["page_tied"]["total_ms"], 4)}), flush=True)
+    if want("M29"):
+        # P2-TREE from the proof alone: on M24's table (662 267 random addresses, po2 20, W = 2^20 and 2^26), zkh_image_proof_nodes (the walk
+        # that keeps the dirty-node table) next to zkh_image_proof_walk, the yardstick, and part 0's witness from the dirty nodes
+        # (zkh_page_tree_witgen_nodes) next to part 0's witness from the two trees (zkh_page_tree_witgen, the parent's path), and the copy
+        # of the tree that page_out(keep_before=True) makes, in one run, alternating, M24's windows; every call's stages by their events;
+        # the words of the table, of its bound, of the proof and of the two trees it replaces.  The proof is built on the host from the
+        # device's tree, read back once.  Both witnesses must be the same buffer; no threshold on any time.
+        from zeth_amd import hal as zhal
+        from zeth_amd.circuits import p2_page, p2_tree
+        from zeth_amd.prover import SegmentProver
+        runs, zk, D = 7, 1994, 662267
+        spread = lambda ts: {"median_ms": round(float(np.median(ts)) * 1e3, 4), "min_ms": round(min(ts) * 1e3, 4), "max_ms": round(max(ts) * 1e3, 4)}   # noqa: E731
+        prover = SegmentProver(hal, p2_tree.p2_tree_circuit(), arguments=p2_tree.arguments())
+        code = hal.page_tree_code(prover.circuit, args.po2, zk)
+        datas = {k: hal.alloc_elem("m29d", p2_tree.WD * n) for k in ("nodes", "trees")}
+        u32p = zhal._u32p
+        key = zhal.noise_key(0x2E80)
+        for W in (1 << 20, 1 << 26):
+            h = p2_page.tree_height(W)
+            L = 1 << h
+            image_h = rand_fp(rng, W)
+            addrs = np.sort(rng.choice(W, D, replace=False)).astype(np.int64)
+            outs = rand_fp(rng, D)
+            table = np.stack([addrs.astype(np.uint32), image_h[addrs], outs], axis=1).reshape(-1)
+            image = hal.alloc_elem("m29i", W)
+            image.write(image_h)
+            before = hal.image_commit(image)
+            tree_h = before.to_vec().reshape(-1, 8)
+            S = np.unique(addrs >> 3)                                        # the ZKU1 proof: logup.reference_page_out_proof's sections
+            counts, sections = [], [tree_h[L + S].reshape(-1)]
+            for k in range(h):
+                clean = (S ^ 1)[~np.isin(S ^ 1, S)]
+                counts.append(clean.size)
+                sections.append(tree_h[(L >> k) + clean].reshape(-1))
+                S = np.unique(S >> 1)
+            proof_h = np.concatenate([np.array([0x5A4B5531, W, D, sections[0].size // 8, h] + counts, dtype=np.uint32), table] + sections).astype(np.uint32)
+            root_before = tree_h[1].copy()
+            del tree_h, sections
+            image_h[addrs] = outs
+            image.write(image_h)
+            after = hal.image_commit(image)
+            del image
+            proof = hal.copy_from("m29p", proof_h)
+            plan = hal.page_tree_plan(args.po2, zk, W, addrs)
+            bound = hal.image_dirty_words(W, D)
+            dirty = hal.alloc("m29n", bound)
+            copy = hal.alloc("m29c", before.size())
+            root = {k: np.zeros(8, dtype=np.uint32) for k in ("walk", "nodes")}
+            outw = {k: np.zeros(18, dtype=np.uint32) for k in datas}
+            rb = root_before.ctypes.data_as(u32p)
+            walk_fn = lambda: zhal._check(zhal._lib.zkh_image_proof_walk(hal.ctx, proof.h, proof_h.size, rb, root["walk"].ctypes.data_as(u32p)))   # noqa: E731
+            nodes_fn = lambda: zhal._check(zhal._lib.zkh_image_proof_nodes(hal.ctx, proof.h, proof_h.size, rb, root["nodes"].ctypes.data_as(u32p), dirty.h))   # noqa: E731
+            wit_nodes = lambda: zhal._check(zhal._lib.zkh_page_tree_witgen_nodes(hal.ctx, prover.circuit.h, args.po2, zk, code.h, proof.h, proof_h.size, dirty.h,   # noqa: E731
+                                                                                 plan[0][0], plan[0][1], datas["nodes"].h, outw["nodes"].ctypes.data_as(u32p),
+                                                                                 key.ctypes.data_as(u32p)))
+            wit_trees = lambda: zhal._check(zhal._lib.zkh_page_tree_witgen(hal.ctx, prover.circuit.h, args.po2, zk, code.h, proof.h, proof_h.size, before.h, after.h,   # noqa: E731
+                                                                           plan[0][0], plan[0][1], datas["trees"].h, outw["trees"].ctypes.data_as(u32p),
+                                                                           key.ctypes.data_as(u32p)))
+            copy_fn = lambda: hal.eltwise_copy_elem(copy, before)             # noqa: E731
+            fns = [("image_proof_walk", walk_fn), ("image_proof_nodes", nodes_fn), ("witness_part_0_from_trees", wit_trees), ("witness_part_0_from_dirty_nodes", wit_nodes),
+                   ("keep_before_tree_copy", copy_fn)]
+            for _name, fn in fns:
+                fn()
+            hal.sync()
+            assert np.array_equal(root["walk"], root["nodes"]) and np.array_equal(root["nodes"], hal.image_root(after)), "the walks do not reach the tree's root"
+            assert np.array_equal(outw["nodes"], outw["trees"]) and np.array_equal(datas["nodes"].to_vec(), datas["trees"].to_vec()), "the two witnesses differ"
+            head = dirty.slice(0, 4 + h).to_vec()
+            dirty_words = 4 + h + 33 * int(head[4:].astype(np.uint64).sum())
+            t = {name: [] for name, _ in fns}
+            for _ in range(runs):
+                for name, fn in fns:
+                    t[name].append(timed(hal, fn, args.reps))
+            steps = {}
+            for name, fn in fns[:4]:
+                hal.prof_enable(True)
+                for _ in range(2):                                           # the first pass creates the scopes' events: only the second is kept
+                    hal.prof_reset()
+                    for _ in range(args.reps):
+                        fn()
+                    hal.sync()
+                steps[name] = {r["name"]: {"calls_per_call": r["calls"] // args.reps, "ms_per_call": round(r["total_ms"] / args.reps, 4)} for r in hal.prof_get()
+                               if r["calls"] and r["name"].startswith(("walk_", "tree_", "page_"))}
+                hal.prof_enable(False)
+            med = {k: float(np.median(v)) for k, v in t.items()}
+            print(json.dumps({"bench": "M29", "library": os.path.basename(os.environ.get("ZKH_LIBRARY", "") or "libzkhal_mi355x.so"), "po2": args.po2,
+                              "image_words": W, "layers": h, "table_rows": D, "block_slots": p2_tree.block_slots(args.po2, zk), "parts": len(plan),
+                              "part_0_rows": plan[0][1], "dirty_nodes_per_layer": [int(x) for x in head[4:]],
+                              "words": {"dirty": dirty_words, "dirty_bound": bound, "proof": int(proof_h.size), "two_trees": 2 * before.size()},
+                              "runs": runs, "reps": args.reps, **{k: spread(v) for k, v in t.items()}, "steps": steps,
+                              "nodes_over_walk": round(med["image_proof_nodes"] / med["image_proof_walk"], 4),
+                              "witness_nodes_over_trees": round(med["witness_part_0_from_dirty_nodes"] / med["witness_part_0_from_trees"], 4)}), flush=True)
+            del before, after, proof, dirty, copy
+        del datas
     hal.close()
 
 

@@ -143,6 +143,9 @@ zkh_image_proof_walk on the device, from the buffer zkh_page_out_proof wrote and
 SegmentProver.page_out(..., proof=True, walk=True) checks the proof it returns against the tree's root after the page-out).  For every
 (proof, root_before) both succeed with the same root_after or fail with the same message after their prefixes; the host verifier's
 order of causes decides when several apply, and this module's `check_page_out_proof` states that order.
+THE DIRTY-NODE TABLE, ZKN1 (`reference_page_out_nodes`, `image_dirty_words`; zkh_image_proof_nodes, zkh_image_dirty_words; csrc/zkn1.h):
+the walk keeping what it recomputes: per layer the heap ids of the dirty nodes and, per node, its two children old and new, which is
+what a P2-TREE block of any part reads (zkh_page_tree_witgen_nodes), so a part is sealed from (proof, root_before) without the trees.
 Left out: sessions do not thread an image, and a blob pages one memory of one value word per address.  The circuits that check p_in /
 p_out against those roots are the page-out circuits (p2_page.py and after it), and THE OPEN BUS below ties their rows to this table.
 
@@ -1634,9 +1637,11 @@ def _digest_hex(d) -> str:
     return " ".join(f"{int(w):08x}" for w in d)
 
 
-def check_page_out_proof(proof, root_before) -> np.ndarray:
+def check_page_out_proof(proof, root_before, keep=None) -> np.ndarray:
     """zkh_image_proof_verify in numpy, one `_hash_pairs` batch per layer: the walk from a ZKU1 proof and root_before to root_after (8
-    words), with nothing else in hand.  Raises ReferenceError with the C verifier's message (after its "image_proof_verify: ")."""
+    words), with nothing else in hand.  Raises ReferenceError with the C verifier's message (after its "image_proof_verify: ").
+    keep: a list that takes, per layer k = 1 .. h, (the heap ids of the layer's dirty nodes, their children as the walk hashes them: left
+    old, left new, right old, right new, 8 words each): what `reference_page_out_nodes` lays out."""
     pf = np.asarray(proof, dtype=np.uint32).reshape(-1)
     rb = np.asarray(root_before, dtype=np.uint32).reshape(-1)
     if pf.size < PROOF_HEADER:
@@ -1716,9 +1721,42 @@ def check_page_out_proof(proof, root_before) -> np.ndarray:
         both = _hash_pairs(np.concatenate([lo, ln]), np.concatenate([ro, rn]))
         old, new = both[:parents], both[parents:]
         S = S[heads] >> 1
+        if keep is not None:
+            keep.append(((image_tree_leaves(W) >> (k + 1)) + S, np.concatenate([lo, ln, ro, rn], axis=1)))
     if not np.array_equal(old[0], rb):
         raise ReferenceError(f"the proof opens root {_digest_hex(old[0])}, not root_before")
     return new[0].copy()
+
+
+NODES_MAGIC = 0x5A4B4E31                                                     # 'ZKN1'
+NODES_HEADER = 4
+
+
+def image_dirty_words(image_words: int, pages: int) -> int:
+    """zkh_image_dirty_words: the bound 4 + h + 33 sum_{k=1..h} min(D, L >> k) on the words of the dirty-node table of a page-out of D
+    rows over an image of W words (a row dirties one node per layer); 0 for W = 0"""
+    W, D = int(image_words), int(pages)
+    if not W:
+        return 0
+    L = image_tree_leaves(W)
+    return NODES_HEADER + _tree_height(W) + 33 * sum(min(D, L >> k) for k in range(1, _tree_height(W) + 1))
+
+
+def reference_page_out_nodes(proof, root_before) -> Tuple[np.ndarray, np.ndarray]:
+    """The dirty-node table zkh_image_proof_nodes writes (include/zkhal.h "THE UPDATE'S PROOF"; csrc/zkn1.h), word for word, from a ZKU1
+    proof and root_before alone -> (root_after, the table).  Words: 'ZKN1', W, D, h, n_1 .. n_h; then per layer k = 1 .. h (layer 0 the
+    leaves, layer h the root) the n_k heap ids of the layer's dirty nodes, increasing, and n_k records of 32 words: the node's left child
+    old ‖ new, its right child old ‖ new, as the walk of `check_page_out_proof` hashes them (a clean child is the proof's sibling,
+    old = new; a layer-1 node's children are two leaves).  Raises ReferenceError as check_page_out_proof does, and on D = 0."""
+    pf = np.asarray(proof, dtype=np.uint32).reshape(-1)
+    keep = []
+    root_after = check_page_out_proof(pf, root_before, keep)
+    W, D, h = int(pf[1]), int(pf[2]), int(pf[4])
+    if D == 0:
+        raise ReferenceError("an empty table (D = 0) has no dirty nodes: its proof is the header alone and holds no node, not even the root's children; "
+                             "such a page-out is sealed from the tree (zkh_page_tree_witgen)")
+    header = np.array([NODES_MAGIC, W, D, h] + [ids.size for ids, _ in keep], dtype=np.uint32)
+    return root_after, np.concatenate([header] + [part.reshape(-1) for ids, records in keep for part in (ids, records)]).astype(np.uint32)
 
 
 def bus_slots(A: int, distinct_keys: int) -> int:

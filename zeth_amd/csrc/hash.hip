@@ -133,10 +133,15 @@ __global__ __launch_bounds__(256, 4) void k_hash_fold_list(uint32_t* __restrict_
 // from[r] of the layer's list, its digests at cur[16 item, +16) (old, new); the other child is the item after it (sib[r] = NONE), or the
 // clean sibling at rank sib[r] of the proof's section C_k (word *off; word aligned), the same for old and new, on the left when the
 // item's index is odd.  The parent's digests go to next[16 r, +16).  Lanes past the count leave: a refusal leaves a count of 0.
+// kKeep (zkh_image_proof_nodes; zkn1.h): the lane also leaves the two children it has just read in the parent's record of the dirty-node
+// table, the section of this layer's parents at word *keep_at of `keep`: behind the section's *count ids, record r, the left child at
+// words [8 v, +8), the right one at [16 + 8 v, +8).  One writer per word; the records are word aligned.  Without kKeep the kernel is
+// the walk's as it was.
+template <bool kKeep>
 __global__ __launch_bounds__(256, 4) void k_hash_walk(const uint32_t* __restrict__ list, const uint32_t* __restrict__ from, const uint32_t* __restrict__ sib,
                                                    const uint32_t* __restrict__ count, const uint32_t* __restrict__ proof, const uint32_t* __restrict__ off,
                                                    const uint32_t* __restrict__ cur, uint32_t* __restrict__ next, const uint32_t* __restrict__ rc,
-                                                   const uint32_t* __restrict__ diag) {
+                                                   const uint32_t* __restrict__ diag, uint32_t* __restrict__ keep, const uint32_t* __restrict__ keep_at) {
     const uint32_t lane = blockIdx.x * blockDim.x + threadIdx.x, r = lane >> 1, v = lane & 1;
     if (r >= *count) return;
     const uint32_t item = from[r], clean = sib[r];
@@ -148,6 +153,11 @@ __global__ __launch_bounds__(256, 4) void k_hash_walk(const uint32_t* __restrict
     uint32_t s[CELLS];
 #pragma unroll
     for (int k = 0; k < 8; k++) { s[k] = left[k]; s[8 + k] = right[k]; }
+    if (kKeep) {
+        uint32_t* record = keep + *keep_at + *count + 32 * (size_t)r + 8 * v;
+#pragma unroll
+        for (int k = 0; k < 8; k++) { record[k] = s[k]; record[16 + k] = s[8 + k]; }
+    }
 #pragma unroll
     for (int k = RATE; k < CELLS; k++) s[k] = 0;
     poseidon2_mix_raw<0, OUT, RATE>(s, rc, diag);             // as fold_one: the zero capacity is not fed through the first M_ext
@@ -341,9 +351,11 @@ const char* zkh::hash_fold_listed(zkh_ctx* c, zkh_buf* nodes, size_t width, cons
     return last_launch_error("image_sparse");
 }
 const char* zkh::hash_walk_layer(zkh_ctx* c, const uint32_t* list, const uint32_t* from, const uint32_t* sib, const uint32_t* count, const uint32_t* proof,
-                                 const uint32_t* off, const uint32_t* cur, uint32_t* next, uint32_t bound) {
+                                 const uint32_t* off, const uint32_t* cur, uint32_t* next, uint32_t bound, uint32_t* keep, const uint32_t* keep_at) {
     ZKH_REQUIRE(bound && bound <= 0x7fffffffu, "hash_walk_layer: %u parents", bound);
-    ProfScope prof(c, "walk_hash", 200.0 * bound);
-    k_hash_walk<<<(unsigned)((2 * (size_t)bound + 255) / 256), 256, 0, c->stream>>>(list, from, sib, count, proof, off, cur, next, c->tab.rc, c->tab.diag);
+    ProfScope prof(c, "walk_hash", (keep ? 328.0 : 200.0) * bound);
+    const unsigned grid = (unsigned)((2 * (size_t)bound + 255) / 256);
+    if (keep) k_hash_walk<true><<<grid, 256, 0, c->stream>>>(list, from, sib, count, proof, off, cur, next, c->tab.rc, c->tab.diag, keep, keep_at);
+    else k_hash_walk<false><<<grid, 256, 0, c->stream>>>(list, from, sib, count, proof, off, cur, next, c->tab.rc, c->tab.diag, nullptr, nullptr);
     return last_launch_error("walk_hash");
 }

@@ -27,6 +27,7 @@
 #include "scan.h"
 #include "sort.h"
 #include "zku1.h"
+#include "zkn1.h"
 
 #include <cstring>
 #include <vector>
@@ -386,6 +387,12 @@ const char* refuse_root(const char* who, const uint32_t* top) {
     return make_err("%s: the proof opens root %08x %08x %08x %08x %08x %08x %08x %08x, not root_before", who, top[0], top[1], top[2], top[3], top[4], top[5], top[6], top[7]);
 }
 
+// zkh_image_proof_nodes alone, where the walk of an empty table would pass
+const char* refuse_empty_nodes(const char* who) {
+    return make_err("%s: an empty table (D = 0) has no dirty nodes: its proof is the header alone and holds no node, not even the root's children; "
+                    "such a page-out is sealed from the tree (zkh_page_tree_witgen)", who);
+}
+
 // D = 0 after the header, the words and root_before have passed: the header must describe nothing
 const char* proof_empty(const char* who, const uint32_t* head) {
     if (head[PROOF_M]) return refuse_leaves(who, head[PROOF_M], 0);
@@ -499,6 +506,15 @@ extern "C" const char* zkh_image_proof_verify(const uint32_t* proof, size_t word
 // first row; a parent's digest: the lane of that permutation; lists and ranks: the head lanes, as in image_proof_build); a launch reads
 // what earlier launches wrote, in stream order.  Two calls give the same record.
 //
+// THE DIRTY NODES (zkh_image_proof_nodes; zkn1.h).  The same stages, and nothing above changes: no stage reads a word it did not read
+// before, and what it keeps it writes into a scratch buffer of the table's BOUND, never into the caller's.  A section's count is the
+// count the walk itself runs the layer's parents under (|S_{k+1}| <= min(D, M, L, the layer's nodes), 0 once a gate is shut), and the
+// bound counts min(D, its nodes) items for layer k: whatever the proof holds, the packed sections end inside the scratch buffer.
+// Writers: a section's ids the head lanes of k_walk_parents (the lanes that write `next`), its records the two lanes of each
+// permutation of k_hash_walk (the children they have just read), its count and the next section's first word lane 0 of
+// k_walk_parents, the header lane 0 of k_walk_leaves: one writer per word, no atomic.  The caller's buffer takes one device copy of
+// the table's words after the record has come back clean.
+//
 // NARROW LAYERS.  Every layer is its own four launches (flags, the counter scan, parents, hash) whatever its list holds: the simplest
 // of the three candidates (one launch per layer; one workgroup walking the narrow layers with barriers; hash.hip's 8-lane permutation),
 // and the only one built.  No constant switches a code path but the workgroup size.  What it reads: DESIGN.md §2 ARGUMENTS, M20.
@@ -514,11 +530,13 @@ enum {
     WR_ROW_A = 9, WR_ROW_BEFORE = 10,                   // the refused row's address and the one before it
     WR_IN_IN = 11, WR_IN_A = 12,                        // that row's `in` and address
     WR_TOP_ITEMS = 13,  // the items of the top layer (1 after a walk that went through)
+    WR_DIRTY_END = 14,  // the word where the dirty-node table ends (zkh_image_proof_nodes)
     WR_DIGESTS = 16,    // the old and the new top digest
     WR_WORDS = 32
 };
-// per layer on the device: the items of S_k, the word where C_k starts, and the two totals of the layer's counter scan
-enum { WM_ITEMS = 0, WM_OFF = 1, WM_TAKE = 2, WM_HEADS = 3, WM_WORDS = 4 };
+// per layer on the device: the items of S_k, the word where C_k starts, the two totals of the layer's counter scan, and the word of the
+// dirty-node table (zkn1.h) where the section of S_{k+1} starts
+enum { WM_ITEMS = 0, WM_OFF = 1, WM_TAKE = 2, WM_HEADS = 3, WM_DIRTY = 4, WM_WORDS = 5 };
 static_assert(WM_ITEMS == PM_ITEMS, "k_proof_flags reads the layer's count at PM_ITEMS");
 
 __device__ __forceinline__ void lowest(unsigned long long* slot, uint32_t index, uint32_t value) {
@@ -550,14 +568,18 @@ __global__ __launch_bounds__(IMG_THREADS) void k_walk_rows(const uint32_t* __res
 
 // grid ceil(D / IMG_THREADS), after the counter scan (st[WR_COUNT]).  The lane of a leaf's first row owns the leaf: its index to
 // list[rank], the old digest (the proof's leaf) and the new one (the rows' `out` put in) to dig[16 rank, +16), every `in` of the leaf's
-// rows (at most 8, consecutive) compared with the old word.  Lane 0 hands layer 0 its count and the siblings' first word.
+// rows (at most 8, consecutive) compared with the old word.  Lane 0 hands layer 0 its count, the siblings' first word and the dirty-node
+// table's first section, and writes that table's header (`dirty`, or null: W, D, h are the proof's).
 __global__ __launch_bounds__(IMG_THREADS) void k_walk_leaves(const uint32_t* __restrict__ proof, uint32_t t0, uint32_t D, uint32_t M, const uint32_t* __restrict__ local,
                                                              const uint32_t* __restrict__ sums, uint32_t* __restrict__ st, uint32_t* __restrict__ list,
-                                                             uint32_t* __restrict__ dig, uint32_t* __restrict__ meta) {
+                                                             uint32_t* __restrict__ dig, uint32_t* __restrict__ meta, uint32_t W, uint32_t h, uint32_t* __restrict__ dirty) {
     const uint32_t t = blockIdx.x * IMG_THREADS + threadIdx.x;
     const size_t l0 = (size_t)t0 + PROOF_ROW * (size_t)D;
     const bool ok = clean64(st, WR_RANGE) && st[WR_ROW] == NONE && st[WR_COUNT] == M;
-    if (t == 0) { meta[WM_ITEMS] = ok ? M : 0; meta[WM_OFF] = (uint32_t)(l0 + 8 * (size_t)M); }
+    if (t == 0) {
+        meta[WM_ITEMS] = ok ? M : 0; meta[WM_OFF] = (uint32_t)(l0 + 8 * (size_t)M); meta[WM_DIRTY] = NODES_HEADER + h;
+        if (dirty) { dirty[0] = NODES_MAGIC; dirty[NODES_W] = W; dirty[NODES_D] = D; dirty[NODES_H] = h; }
+    }
     if (t >= D || !ok) return;
     const uint32_t* table = proof + t0;
     const uint32_t leaf = table_addr(table, t) >> 3;
@@ -589,16 +611,22 @@ __global__ __launch_bounds__(IMG_THREADS) void k_walk_leaves(const uint32_t* __r
 // siblings the walk takes; meta[WM_HEADS] = |S_{k+1}|).  Gated on every earlier refusal and on take = c_k.  A head writes, at its
 // parent's rank: the parent's index (next), its own item (from) and the rank of the clean sibling it takes, NONE when it pairs with
 // the item after it (sib).  Lane 0 hands the next layer its count (0: the gate is shut) and the word where C_{k+1} starts, and records
-// the layer when its count is the first that differs.
+// the layer when its count is the first that differs.  `dirty` (or null; zkn1.h): lane 0 writes the count to its header as n_{k+1} and
+// hands the next layer the word where this section ends; a head writes its parent's heap id, `up` + the parent's index (`up` = the
+// nodes of layer k + 1), at its rank into the section's ids.
 __global__ __launch_bounds__(IMG_THREADS) void k_walk_parents(const uint32_t* __restrict__ list, uint32_t* __restrict__ meta, const uint32_t* __restrict__ local,
                                                               const uint32_t* __restrict__ sums, uint32_t nb, uint32_t k, const uint32_t* __restrict__ proof,
-                                                              uint32_t* __restrict__ st, uint32_t* __restrict__ next, uint32_t* __restrict__ from, uint32_t* __restrict__ sib) {
+                                                              uint32_t* __restrict__ st, uint32_t* __restrict__ next, uint32_t* __restrict__ from, uint32_t* __restrict__ sib,
+                                                              uint32_t up, uint32_t* __restrict__ dirty) {
     const uint32_t m = meta[WM_ITEMS], take = meta[WM_TAKE], c = proof[PROOF_HEADER + k];
     const uint32_t t = blockIdx.x * IMG_THREADS + threadIdx.x;
     const bool before = clean64(st, WR_RANGE) && clean64(st, WR_IN) && st[WR_ROW] == NONE, ok = before && take == c;
     if (t == 0) {
-        meta[WM_WORDS + WM_ITEMS] = ok ? meta[WM_HEADS] : 0;
+        const uint32_t heads = ok ? meta[WM_HEADS] : 0;
+        meta[WM_WORDS + WM_ITEMS] = heads;
         meta[WM_WORDS + WM_OFF] = meta[WM_OFF] + 8 * c;
+        meta[WM_WORDS + WM_DIRTY] = meta[WM_DIRTY] + NODES_ITEM * heads;
+        if (dirty) dirty[NODES_HEADER + k] = heads;
         if (before && m && take != c && st[WR_LAYER] == NONE) { st[WR_LAYER] = k; st[WR_LAYER_C] = c; st[WR_LAYER_TAKE] = take; }
     }
     if (t >= m || !ok) return;
@@ -609,15 +637,17 @@ __global__ __launch_bounds__(IMG_THREADS) void k_walk_parents(const uint32_t* __
     next[r] = x >> 1;
     from[r] = t;
     sib[r] = f & 1 ? (ranks & 0xffff) + sums[blockIdx.x] - 1 : NONE;
+    if (dirty) dirty[meta[WM_DIRTY] + r] = up + (x >> 1);
 }
 
 // one workgroup of 64: the top digests when the walk went through (items = the count of the top layer), and the values the messages of
-// a refused row and of a differing `in` print
+// a refused row and of a differing `in` print; and the word where the dirty-node table ends (`items` is the top layer's meta)
 __global__ __launch_bounds__(64) void k_walk_top(const uint32_t* __restrict__ proof, uint32_t t0, const uint32_t* __restrict__ items, const uint32_t* __restrict__ dig,
                                                  uint32_t* __restrict__ st) {
     const uint32_t t = threadIdx.x, n = *items;
     if (t < 16 && n == 1) st[WR_DIGESTS + t] = dig[t];
     if (t == 16) st[WR_TOP_ITEMS] = n;
+    if (t == 19) st[WR_DIRTY_END] = items[WM_DIRTY];
     if (t == 17 && st[WR_ROW] != NONE) {
         const uint32_t i = st[WR_ROW];
         st[WR_ROW_A] = table_addr(proof + t0, i);
@@ -632,9 +662,8 @@ __global__ __launch_bounds__(64) void k_walk_top(const uint32_t* __restrict__ pr
 
 }  // namespace
 
-extern "C" const char* zkh_image_proof_walk(zkh_ctx* ctx, const zkh_buf* proof, size_t words, const uint32_t root_before[8], uint32_t root_after[8]) {
-    static const char who[] = "image_proof_walk";
-    ZKH_REQUIRE(ctx && proof && root_before && root_after, "%s: null argument", who);
+// Both entry points; `dirty` is zkh_image_proof_nodes' (null for the walk: THE DIRTY NODES above)
+static const char* proof_walk(const char* who, zkh_ctx* ctx, const zkh_buf* proof, size_t words, const uint32_t root_before[8], uint32_t root_after[8], zkh_buf* dirty) {
     ZKH_REQUIRE(words <= proof->len, "%s: a proof of %zu words in a buffer of %zu", who, words, proof->len);
     ZKH_REQUIRE(words <= 0xffffffffull, "%s: a proof of %zu words (at most 2^32 - 1)", who, words);
     bind_thread(ctx);
@@ -644,10 +673,16 @@ extern "C" const char* zkh_image_proof_walk(zkh_ctx* ctx, const zkh_buf* proof, 
     const ProofShape ps = proof_shape(head);
     const uint32_t W = ps.W, D = ps.D, M = ps.M, h = ps.h;
     const size_t L = image_leaves(W), t0 = ps.table, l0 = ps.leaves;
+    const unsigned long long bound = image_nodes_bound(W, D);
+    if (dirty) {
+        ZKH_REQUIRE(bound <= 0xffffffffull, "%s: the dirty nodes of %u rows over %u words may take %llu words (at most 2^32 - 1)", who, D, W, bound);
+        ZKH_REQUIRE(dirty->len >= bound, "%s: dirty nodes of %zu words; %u rows over %u words may take %llu (zkh_image_dirty_words)", who, dirty->len, D, W, bound);
+    }
     bool root_ok = true;
     for (int j = 0; j < 8; j++) root_ok = root_ok && root_before[j] < P;
     if (words == t0) {                                  // D = 0 and nothing after the header: nothing to launch
         if (!root_ok) return refuse_root_range(who);
+        if (dirty) return refuse_empty_nodes(who);
         memmove(root_after, root_before, 32);
         return nullptr;
     }
@@ -662,7 +697,12 @@ extern "C" const char* zkh_image_proof_walk(zkh_ctx* ctx, const zkh_buf* proof, 
     if (!items0) items0 = 1;                            // M = 0 on a table with rows: the gate stays shut, the stages still report
     const bool rows = D && root_ok;                     // a root_before that is not below P: only a word >= P is reported before it
     const uint32_t nb0 = (D + IMG_THREADS - 1) / IMG_THREADS;
-    Tmp lists[2], local, sums, meta, from, sib, dig[2];
+    Tmp lists[2], local, sums, meta, from, sib, dig[2], kept;
+    uint32_t* keep = nullptr;
+    if (dirty && rows) {
+        ZKH_TRY(new_buf(ctx, (size_t)bound, false, kept.out()));
+        keep = kept->ptr();
+    }
     {
         ProfScope prof(ctx, "walk_check", 4.0 * (words - t0) + (rows ? 12.0 * D + 8.0 * nb0 : 0.0));
         k_walk_range<<<(unsigned)((words - t0 + IMG_THREADS - 1) / IMG_THREADS), IMG_THREADS, 0, ctx->stream>>>(pw, t0, l0, words, st->ptr());
@@ -686,7 +726,8 @@ extern "C" const char* zkh_image_proof_walk(zkh_ctx* ctx, const zkh_buf* proof, 
         ZKH_TRY(new_buf(ctx, WM_WORDS * ((size_t)h + 2), false, meta.out()));
         {
             ProfScope prof(ctx, "walk_leaves", 20.0 * D + 100.0 * items0);
-            k_walk_leaves<<<nb0, IMG_THREADS, 0, ctx->stream>>>(pw, (uint32_t)t0, D, M, local->ptr(), sums->ptr(), st->ptr(), lists[0]->ptr(), dig[0]->ptr(), meta->ptr());
+            k_walk_leaves<<<nb0, IMG_THREADS, 0, ctx->stream>>>(pw, (uint32_t)t0, D, M, local->ptr(), sums->ptr(), st->ptr(), lists[0]->ptr(), dig[0]->ptr(), meta->ptr(), W, h,
+                                                                keep);
             ZKH_TRY(last_launch_error("walk_leaves"));
         }
         int cur = 0;
@@ -702,10 +743,11 @@ extern "C" const char* zkh_image_proof_walk(zkh_ctx* ctx, const zkh_buf* proof, 
                 scan_counters(ctx, sums->ptr(), 2, nb, mk + WM_TAKE, 1);
                 ZKH_TRY(last_launch_error("walk_carry"));
                 k_walk_parents<<<nb, IMG_THREADS, 0, ctx->stream>>>(lists[cur]->ptr(), mk, local->ptr(), sums->ptr(), nb, k, pw, st->ptr(), lists[cur ^ 1]->ptr(), from->ptr(),
-                                                                    sib->ptr());
+                                                                    sib->ptr(), (uint32_t)(width >> 1), keep);
                 ZKH_TRY(last_launch_error("walk_parents"));
             }
-            ZKH_TRY(hash_walk_layer(ctx, lists[cur]->ptr(), from->ptr(), sib->ptr(), mk + WM_WORDS + WM_ITEMS, pw, mk + WM_OFF, dig[cur]->ptr(), dig[cur ^ 1]->ptr(), parents));
+            ZKH_TRY(hash_walk_layer(ctx, lists[cur]->ptr(), from->ptr(), sib->ptr(), mk + WM_WORDS + WM_ITEMS, pw, mk + WM_OFF, dig[cur]->ptr(), dig[cur ^ 1]->ptr(), parents, keep,
+                                    mk + WM_DIRTY));
         }
         {
             ProfScope prof(ctx, "walk_top", 128.0);
@@ -724,6 +766,25 @@ extern "C" const char* zkh_image_proof_walk(zkh_ctx* ctx, const zkh_buf* proof, 
     if (rec[WR_LAYER] != NONE) return refuse_layer(who, rec[WR_LAYER], rec[WR_LAYER_C], rec[WR_LAYER_TAKE]);
     ZKH_REQUIRE(rec[WR_TOP_ITEMS] == 1, "%s: the walk ended on %u nodes (a fault of the walk, not of the proof)", who, rec[WR_TOP_ITEMS]);
     if (memcmp(rec + WR_DIGESTS, root_before, 32)) return refuse_root(who, rec + WR_DIGESTS);
+    if (dirty) {
+        ZKH_REQUIRE(rec[WR_DIRTY_END] <= bound, "%s: the dirty nodes ended at word %u of %llu (a fault of the walk, not of the proof)", who, rec[WR_DIRTY_END], bound);
+        ProfScope prof(ctx, "walk_keep", 8.0 * rec[WR_DIRTY_END]);
+        ZKH_HIP(hipMemcpyAsync(dirty->ptr(), keep, 4 * (size_t)rec[WR_DIRTY_END], hipMemcpyDeviceToDevice, ctx->stream));
+    }
     memcpy(root_after, rec + WR_DIGESTS + 8, 32);
     return nullptr;
 }
+
+extern "C" const char* zkh_image_proof_walk(zkh_ctx* ctx, const zkh_buf* proof, size_t words, const uint32_t root_before[8], uint32_t root_after[8]) {
+    static const char who[] = "image_proof_walk";
+    ZKH_REQUIRE(ctx && proof && root_before && root_after, "%s: null argument", who);
+    return proof_walk(who, ctx, proof, words, root_before, root_after, nullptr);
+}
+
+extern "C" const char* zkh_image_proof_nodes(zkh_ctx* ctx, const zkh_buf* proof, size_t words, const uint32_t root_before[8], uint32_t root_after[8], zkh_buf* dirty) {
+    static const char who[] = "image_proof_nodes";
+    ZKH_REQUIRE(ctx && proof && root_before && root_after && dirty, "%s: null argument", who);
+    return proof_walk(who, ctx, proof, words, root_before, root_after, dirty);
+}
+
+extern "C" size_t zkh_image_dirty_words(size_t image_words, size_t pages) { return image_words ? (size_t)image_nodes_bound(image_words, pages) : 0; }

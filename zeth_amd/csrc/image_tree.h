@@ -30,9 +30,10 @@ const char* hash_fold_listed(zkh_ctx* c, zkh_buf* nodes, size_t width, const uin
 // hash.hip: one layer of the walk of a ZKU1 proof (image.hip, zkh_image_proof_walk): the parents [0, *count) of the layer, two lanes
 // each (hash_pair of the old children, of the new ones).  Parent r's children: item from[r] of `list` with its two digests at
 // cur[16 item, +16), and the item after it (sib[r] = all ones) or the clean sibling at rank sib[r] of the proof's section at word *off.
-// The two digests of parent r go to next[16 r, +16).  `bound` >= *count sizes the grid.  Profiler scope walk_hash.
+// The two digests of parent r go to next[16 r, +16).  `bound` >= *count sizes the grid.  Profiler scope walk_hash.  `keep` (or null):
+// the dirty-node table (zkn1.h) whose section at word *keep_at takes, behind its *count ids, the parents' records: the children as read.
 const char* hash_walk_layer(zkh_ctx* c, const uint32_t* list, const uint32_t* from, const uint32_t* sib, const uint32_t* count, const uint32_t* proof,
-                            const uint32_t* off, const uint32_t* cur, uint32_t* next, uint32_t bound);
+                            const uint32_t* off, const uint32_t* cur, uint32_t* next, uint32_t bound, uint32_t* keep, const uint32_t* keep_at);
 
 // image.hip: after a page-out has scattered into `image`: `addrs` is the page table's address column (raw words), its rows [0, D) strictly
 // increasing addresses below image->len; `nodes` becomes what zkh_image_commit writes for the new image.  D = 0: nothing is launched.

@@ -183,12 +183,13 @@ inline const char* page_circuit_shape(const char* who, const PageShape& sh, cons
 // buffers', the proof's head (read back: one small copy), the image's shape by `image_shape(W)` (the circuit's own refusals), the
 // trees' length.  Nothing is launched or written.  -> n rows, the image's W words, h and L leaves, the table (3 D words inside the
 // proof: its length is what the header describes), the noise key.
+// page_open_proof is all of it but the trees: what a call that reads no tree opens with (zkh_page_tree_witgen_nodes).
 struct PageOpen { size_t n, L; uint32_t W, D, h; const uint32_t* table; NoiseKey nk; };
 template <class ImageShape>
-const char* page_open(const char* who, const PageShape& sh, zkh_ctx* ctx, const zkh_circuit* c, size_t po2, size_t zk_cycles, const zkh_buf* code, const zkh_buf* proof,
-                      size_t proof_words, const zkh_buf* nodes_before, const zkh_buf* nodes_after, const zkh_buf* data, const uint32_t* out, const uint32_t* noise_key,
-                      ImageShape image_shape, PageOpen* o) {
-    ZKH_REQUIRE(ctx && c && code && proof && nodes_before && nodes_after && data && out, "%s: null argument", who);
+const char* page_open_proof(const char* who, const PageShape& sh, zkh_ctx* ctx, const zkh_circuit* c, size_t po2, size_t zk_cycles, const zkh_buf* code,
+                            const zkh_buf* proof, size_t proof_words, const zkh_buf* data, const uint32_t* out, const uint32_t* noise_key, ImageShape image_shape,
+                            PageOpen* o) {
+    ZKH_REQUIRE(ctx && c && code && proof && data && out, "%s: null argument", who);
     ZKH_TRY(page_circuit_shape(who, sh, c, po2, zk_cycles));
     o->n = (size_t)1 << po2;
     ZKH_REQUIRE(code->len == (size_t)sh.wc * o->n && data->len == (size_t)sh.wd * o->n, "%s: buffer shape mismatch%s", who, sh.buffers);
@@ -204,9 +205,17 @@ const char* page_open(const char* who, const PageShape& sh, zkh_ctx* ctx, const 
     ZKH_TRY(image_shape(o->W));
     o->h = ps.h;                                        // the header passed: h is W's
     o->L = image_leaves(o->W);
+    o->table = proof->ptr() + ps.table;
+    return nullptr;
+}
+template <class ImageShape>
+const char* page_open(const char* who, const PageShape& sh, zkh_ctx* ctx, const zkh_circuit* c, size_t po2, size_t zk_cycles, const zkh_buf* code, const zkh_buf* proof,
+                      size_t proof_words, const zkh_buf* nodes_before, const zkh_buf* nodes_after, const zkh_buf* data, const uint32_t* out, const uint32_t* noise_key,
+                      ImageShape image_shape, PageOpen* o) {
+    ZKH_REQUIRE(ctx && c && code && proof && nodes_before && nodes_after && data && out, "%s: null argument", who);
+    ZKH_TRY(page_open_proof(who, sh, ctx, c, po2, zk_cycles, code, proof, proof_words, data, out, noise_key, image_shape, o));
     ZKH_REQUIRE(nodes_before->len == 16 * o->L && nodes_after->len == 16 * o->L, "%s: nodes of %zu and %zu words; an image of %u words has a tree of %zu (zkh_image_tree_words)",
                 who, nodes_before->len, nodes_after->len, o->W, 16 * o->L);
-    o->table = proof->ptr() + ps.table;
     return nullptr;
 }
 

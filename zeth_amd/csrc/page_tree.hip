@@ -20,10 +20,21 @@
 // bookkeeping column).  The tail rows are k_rows_tail's (circuit.hip, p2_rows_tail).  One writer per cell (of the record and the slot list
 // too), one read-back of the record at the end.  The plan of the parts, on the host (zkh_page_tree_plan) and over the table where it
 // lies (zkh_page_tree_plan_device: k_plan_costs, k_plan_scan, k_plan_walk, many workgroups), is described above those kernels.
+//
+// FROM THE DIRTY NODES (zkh_page_tree_witgen_nodes; zkn1.h; DESIGN.md §2 "P2-TREE from the proof alone").  The same witness without the
+// two trees.  The source rule above does not change, only the fetch: a block's node is dirty, so the dirty-node table of the page-out's
+// proof holds its record, both children on both sides, and "the NEW tree's" is the record's new digest, "the OLD tree's" its old one (a
+// clean child has both equal).  k_tree_find: one lane per slot, ONE binary search of the layer's ids, the record's rank into `pos`; a
+// miss (the table is another proof's) leaves the lowest missing id in the record (atomicMin, the one atomic of this file: which lane
+// arrives first must not choose the message).  k_tree_edges_nodes: k_tree_edges over the records; it shuts the gate (TR_REFUSED) after
+// a miss, so no block, bookkeeping or word cell is written.  k_tree_blocks_nodes: k_tree_blocks' inputs from the record at pos[slot],
+// the rows through p2_rows.h pj_block_rows.  Every index into the table is below a count the host has checked (NodesShape, by value).
+// The order of the launches is check, place, find, edges, blocks; the rest is shared with the two-tree call.
 #include <vector>
 
 #include "p2_rows.h"
 #include "scan.h"
+#include "zkn1.h"
 
 using namespace zkh;
 
@@ -45,7 +56,8 @@ enum : uint32_t { TD_CH = 106, TD_WA = 122, PT_PAIR_WORDS = 16 };
 // the record: k_page_check's refusal (row, its address, the one before), the row at which the part splits a pair of leaves, the part's
 // nodes (saturated) and pairs, lo and hi as the trace holds them, whether anything is refused, both roots, both edge chains (h digests
 // each: step t's is the node of layer t + 1)
-enum : uint32_t { TR_ROW = 0, TR_A, TR_BEFORE, TR_SPLIT, TR_NODES, TR_PAIRS, TR_LO, TR_HI, TR_REFUSED, TR_ROOTS = 16, TR_EDGES = 32, TR_WORDS = TR_EDGES + 16 * PT_MAX_H };
+// (TR_MISS, the dirty-node path alone: the lowest id of a block that the table does not hold)
+enum : uint32_t { TR_ROW = 0, TR_A, TR_BEFORE, TR_SPLIT, TR_NODES, TR_PAIRS, TR_LO, TR_HI, TR_REFUSED, TR_MISS, TR_ROOTS = 16, TR_EDGES = 32, TR_WORDS = TR_EDGES + 16 * PT_MAX_H };
 constexpr uint32_t PT_THREADS = 256;
 
 __device__ __forceinline__ uint32_t bit_length(uint32_t x) { return 32u - (uint32_t)__clz((int)x); }   // __clz(0) = 32
@@ -254,6 +266,108 @@ __global__ __launch_bounds__(64) void k_tree_blocks(uint32_t* __restrict__ data,
     }
     const size_t rl = r0 + PJ_BLOCK - 1;
     for (uint32_t j = 0; j < PJ_T; j++) { data[(size_t)(s_col + j) * n + rl] = s[j]; data[(size_t)(q_col + j) * n + rl] = 0; }
+}
+
+// ---- the same from the dirty nodes (the header of this file, FROM THE DIRTY NODES).  count > 0: an empty table has no dirty-node table.
+// The layer of the node with heap id `id` (1 <= id < L): h + 1 - bit_length(id); a pair block's is 1.
+
+// grid ceil(B / 256), one lane per slot: the rank of the slot's id among its layer's ids into pos[slot]; a dead slot (id 0) takes 0
+__global__ __launch_bounds__(PT_THREADS) void k_tree_find(const uint32_t* __restrict__ ids, uint32_t B, uint32_t h, const uint32_t* __restrict__ dirty, const NodesShape ns,
+                                                          uint32_t* __restrict__ pos, uint32_t* __restrict__ rec) {
+    const uint32_t slot = blockIdx.x * PT_THREADS + threadIdx.x;
+    if (slot >= B || rec[TR_REFUSED]) return;
+    const uint32_t id = ids[slot];
+    uint32_t p = 0;
+    if (id) {
+        p = ns.find(dirty, h + 1 - bit_length(id), id);
+        if (p == NODES_NONE) atomicMin(rec + TR_MISS, id);
+    }
+    pos[slot] = p;
+}
+
+// ONE wave, k_tree_edges' two chains: the node of layer t + 1 on the edge address's path is a block of the part, its record holds the
+// path's child (recomputed here) beside its sibling.  All lanes stay to the end: lane 0 shuts the gate after a miss, k_tree_find's or
+// (it cannot happen once every slot was found: the path's nodes are slots) one of the two chains'.
+__global__ __launch_bounds__(64) void k_tree_edges_nodes(uint32_t h, const uint32_t* __restrict__ table, uint32_t first, uint32_t count, const uint32_t* __restrict__ dirty,
+                                                         const NodesShape ns, size_t L, uint32_t* rec, const uint32_t* __restrict__ rc, const uint32_t* __restrict__ diag) {
+    const uint32_t lane = threadIdx.x;
+    if (rec[TR_REFUSED]) return;
+    bool missed = rec[TR_MISS] != PJ_NONE;
+    if (lane < 2 && !missed) {
+        const uint32_t side = lane;
+        const uint32_t a = table_addr(table, side ? first + count - 1 : first);
+        uint32_t s[CELLS];
+        for (uint32_t t = 0; t < h && !missed; t++) {
+            const uint32_t id = (uint32_t)(L >> (t + 1)) + (a >> (4 + t));
+            const uint32_t p = ns.find(dirty, t + 1, id);
+            if (p == NODES_NONE) { atomicMin(rec + TR_MISS, id); missed = true; break; }
+            const uint32_t* r = ns.record(dirty, t + 1, p);
+            if (t == 0) {
+                const uint32_t x0 = a & ~15u;
+#pragma unroll
+                for (uint32_t j = 0; j < 16; j++) {
+                    const bool done = side ? x0 + j <= a : x0 + j < a;
+                    s[j] = r[16 * (j >> 3) + (done ? 8 : 0) + (j & 7)];
+                }
+            } else {
+                const bool right = (a >> (3 + t)) & 1;                     // a right node's sibling lies below the edge: the new digest
+                const uint32_t* sib = r + (right ? 8 : 16);
+#pragma unroll
+                for (uint32_t j = 0; j < 8; j++) {
+                    const uint32_t own = s[j], other = sib[j];
+                    s[j] = right ? other : own;
+                    s[8 + j] = right ? own : other;
+                }
+            }
+#pragma unroll
+            for (int j = RATE; j < CELLS; j++) s[j] = 0;
+            poseidon2_mix_raw<0, OUT, RATE>(s, rc, diag);
+#pragma unroll
+            for (int j = 0; j < OUT; j++) s[j] = p2_finish(s[j]);
+#pragma unroll
+            for (uint32_t j = 0; j < 8; j++) rec[TR_EDGES + 8 * (side * h + t) + j] = s[j];
+        }
+        if (!missed) {
+#pragma unroll
+            for (uint32_t j = 0; j < 8; j++) rec[TR_ROOTS + 8 * side + j] = s[j];
+        }
+    }
+    if (__any(missed) && lane == 0) rec[TR_REFUSED] = 1;
+}
+
+// One lane per (slot, side), as k_tree_blocks; the 16 input words from the record at pos[slot]: a child below the edge address its new
+// digest, one above it its old one, the one that holds it from the edge chain.  The rows are pj_block_rows' (p2_rows.h).
+__global__ __launch_bounds__(64) void k_tree_blocks_nodes(uint32_t* __restrict__ data, uint32_t n, uint32_t h, uint32_t B, const uint32_t* __restrict__ ids,
+                                                          const uint32_t* __restrict__ pos, const uint32_t* __restrict__ table, uint32_t first, uint32_t count,
+                                                          const uint32_t* __restrict__ dirty, const NodesShape ns, const uint32_t* __restrict__ rec,
+                                                          const uint32_t* __restrict__ tab) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= 2 * B || rec[TR_REFUSED]) return;
+    const uint32_t slot = i >> 1, side = i & 1, id = ids[slot], half = 1u << (h - 1);
+    uint32_t s[PJ_T];
+    for (uint32_t j = 0; j < PJ_T; j++) s[j] = 0;
+    if (id) {
+        const uint32_t a = table_addr(table, side ? first + count - 1 : first);
+        const uint32_t k = h + 1 - bit_length(id);
+        const uint32_t* r = ns.record(dirty, k, pos[slot]);                // pos[slot] < n[k]: k_tree_find found it, or the gate is shut
+        if (id >= half) {                                                  // a pair block: 16 memory words
+            const uint32_t x0 = (id - half) << 4;
+            for (uint32_t j = 0; j < 16; j++) {
+                const uint32_t x = x0 + j;
+                const bool done = side ? x <= a : x < a;
+                s[j] = r[16 * (j >> 3) + (done ? 8 : 0) + (j & 7)];
+            }
+        } else {                                                           // children 2 id, 2 id + 1: nodes of layer t = k - 1 >= 1
+            const uint32_t t = k - 1;
+            const uint32_t on_edge = a >> (3 + t);
+            for (uint32_t c = 0; c < 2; c++) {
+                const uint32_t x = 2 * id + c - (1u << (h - t));
+                const uint32_t* src = x == on_edge ? rec + TR_EDGES + 8 * (side * h + t - 1) : r + 16 * c + (x < on_edge ? 8 : 0);
+                for (uint32_t j = 0; j < 8; j++) s[8 * c + j] = src[j];
+            }
+        }
+    }
+    pj_block_rows(data, n, (size_t)PJ_BLOCK * slot, side ? TD_SN : TD_SO, side ? TD_QN : TD_QO, s, tab);
 }
 
 // whether an address of the part lies in [x, y): a binary search of its `count` increasing addresses
@@ -540,15 +654,28 @@ extern "C" const char* zkh_page_tree_plan_device(zkh_ctx* ctx, size_t po2, size_
     return nullptr;
 }
 
-extern "C" const char* zkh_page_tree_witgen(zkh_ctx* ctx, const zkh_circuit* c, size_t po2, size_t zk_cycles, const zkh_buf* code, const zkh_buf* proof,
-                                            size_t proof_words, const zkh_buf* nodes_before, const zkh_buf* nodes_after, size_t first_row, size_t count_rows,
-                                            zkh_buf* data, uint32_t out[18], const uint32_t* noise_key) {
-    const char* who = "page_tree_witgen";
+namespace {
+
+// Both witness calls.  `dirty` null: the two trees (nodes_before, nodes_after); else the dirty-node table of the proof, and no tree.
+const char* tree_witgen(const char* who, zkh_ctx* ctx, const zkh_circuit* c, size_t po2, size_t zk_cycles, const zkh_buf* code, const zkh_buf* proof, size_t proof_words,
+                        const zkh_buf* nodes_before, const zkh_buf* nodes_after, const zkh_buf* dirty, size_t first_row, size_t count_rows, zkh_buf* data,
+                        uint32_t out[18], const uint32_t* noise_key) {
     uint32_t h, B;
     PageOpen o;
+    NodesShape ns;
     const PageShape& sh = tree_shape(c);
-    ZKH_TRY(page_open(who, sh, ctx, c, po2, zk_cycles, code, proof, proof_words, nodes_before, nodes_after, data, out, noise_key,
-                      [&](size_t W) { return tree_image_shape(who, po2, zk_cycles, W, &h, &B); }, &o));
+    const auto image_shape = [&](size_t W) { return tree_image_shape(who, po2, zk_cycles, W, &h, &B); };
+    if (dirty) {
+        ZKH_TRY(page_open_proof(who, sh, ctx, c, po2, zk_cycles, code, proof, proof_words, data, out, noise_key, image_shape, &o));
+        uint32_t head[NODES_HEAD_MAX] = {0};
+        ZKH_TRY(zkh_read(ctx, dirty, head, 0, dirty->len < NODES_HEAD_MAX ? dirty->len : NODES_HEAD_MAX));
+        ZKH_TRY(image_nodes_header(who, head, dirty->len, &ns));
+        ZKH_REQUIRE(head[NODES_W] == o.W && head[NODES_D] == o.D && head[NODES_H] == o.h, "%s: dirty nodes of %u rows over %u words (h %u), but the proof has %u rows over %u words (h %u)",
+                    who, head[NODES_D], head[NODES_W], head[NODES_H], o.D, o.W, o.h);
+        ZKH_REQUIRE(o.D, "%s: an empty table (D = 0) has no dirty nodes; such a page-out is sealed from the tree (zkh_page_tree_witgen)", who);
+    } else {
+        ZKH_TRY(page_open(who, sh, ctx, c, po2, zk_cycles, code, proof, proof_words, nodes_before, nodes_after, data, out, noise_key, image_shape, &o));
+    }
     const size_t n = o.n, L = o.L;
     const uint32_t W = o.W, D = o.D, *table = o.table;
     const NoiseKey& nk = o.nk;
@@ -556,16 +683,23 @@ extern "C" const char* zkh_page_tree_witgen(zkh_ctx* ctx, const zkh_circuit* c, 
                 who, first_row, first_row + count_rows, D);
     const uint32_t first = (uint32_t)first_row, count = (uint32_t)count_rows;     // 3 D words fit the proof: D < 2^31
     const uint32_t A = (uint32_t)(n - zk_cycles), rows = PJ_BLOCK * B;
-    Tmp tab, rec, ids;
+    Tmp tab, rec, ids, pos;
     ZKH_TRY(p2_rows_tables(ctx, tab));
-    ZKH_TRY(new_buf(ctx, TR_WORDS, false, rec.out()));
+    if (dirty) {                                        // the record starts with no miss
+        std::vector<uint32_t> init(TR_WORDS, 0);
+        init[TR_MISS] = PJ_NONE;
+        ZKH_TRY(zkh_copy_from(ctx, "tree_record", init.data(), TR_WORDS, rec.out()));
+        ZKH_TRY(new_buf(ctx, B, false, pos.out()));
+    } else {
+        ZKH_TRY(new_buf(ctx, TR_WORDS, false, rec.out()));
+    }
     ZKH_TRY(new_buf(ctx, B, false, ids.out()));
     {
         ProfScope prof(ctx, "tree_check", 12.0 * D + 12.0 * count);
         k_tree_check<<<1, PT_THREADS, 0, ctx->stream>>>(table, D, W, h, B, first, count, rec->ptr());
         ZKH_TRY(last_launch_error("tree_check"));
     }
-    {
+    if (!dirty) {
         ProfScope prof(ctx, "tree_edges", 4.0 * 32 * h);
         k_tree_edges<<<1, 64, 0, ctx->stream>>>(h, table, first, count, nodes_before->ptr(), nodes_after->ptr(), L, rec->ptr(), ctx->tab.rc, ctx->tab.diag);
         ZKH_TRY(last_launch_error("tree_edges"));
@@ -575,10 +709,24 @@ extern "C" const char* zkh_page_tree_witgen(zkh_ctx* ctx, const zkh_circuit* c, 
         k_tree_place<<<1, PT_THREADS, 0, ctx->stream>>>(ids->ptr(), B, h, table, first, count, rec->ptr());
         ZKH_TRY(last_launch_error("tree_place"));
     }
+    if (dirty) {
+        {
+            ProfScope prof(ctx, "tree_find", 8.0 * B + 4.0 * h * B);
+            k_tree_find<<<(B + PT_THREADS - 1) / PT_THREADS, PT_THREADS, 0, ctx->stream>>>(ids->ptr(), B, h, dirty->ptr(), ns, pos->ptr(), rec->ptr());
+            ZKH_TRY(last_launch_error("tree_find"));
+        }
+        {
+            ProfScope prof(ctx, "tree_edges", 4.0 * 32 * h);
+            k_tree_edges_nodes<<<1, 64, 0, ctx->stream>>>(h, table, first, count, dirty->ptr(), ns, L, rec->ptr(), ctx->tab.rc, ctx->tab.diag);
+            ZKH_TRY(last_launch_error("tree_edges"));
+        }
+    }
     {
         ProfScope prof(ctx, "tree_blocks", 4.0 * 96 * rows);
-        k_tree_blocks<<<(2 * B + 63) / 64, 64, 0, ctx->stream>>>(data->ptr(), (uint32_t)n, h, B, ids->ptr(), table, first, count, nodes_before->ptr(),
-                                                                 nodes_after->ptr(), L, rec->ptr(), tab->ptr());
+        if (dirty) k_tree_blocks_nodes<<<(2 * B + 63) / 64, 64, 0, ctx->stream>>>(data->ptr(), (uint32_t)n, h, B, ids->ptr(), pos->ptr(), table, first, count, dirty->ptr(), ns,
+                                                                                  rec->ptr(), tab->ptr());
+        else k_tree_blocks<<<(2 * B + 63) / 64, 64, 0, ctx->stream>>>(data->ptr(), (uint32_t)n, h, B, ids->ptr(), table, first, count, nodes_before->ptr(),
+                                                                      nodes_after->ptr(), L, rec->ptr(), tab->ptr());
         ZKH_TRY(last_launch_error("tree_blocks"));
     }
     {
@@ -604,8 +752,28 @@ extern "C" const char* zkh_page_tree_witgen(zkh_ctx* ctx, const zkh_circuit* c, 
                 first + count, r[TR_SPLIT] - 1, r[TR_SPLIT]);
     ZKH_REQUIRE(r[TR_NODES] <= B, "%s: the part [%u, %u) has %u%s dirty nodes, but po2 %zu leaves %u block slots (zkh_page_tree_plan)", who, first, first + count,
                 r[TR_NODES], r[TR_NODES] == 0xfffffffeu ? " or more" : "", po2, B);
+    if (dirty) {
+        const uint32_t miss = r[TR_MISS];
+        ZKH_REQUIRE(miss == PJ_NONE, "%s: node %u of layer %u is not in the dirty nodes (the table is another proof's)", who, miss, h + 1 - (32u - (uint32_t)__builtin_clz(miss | 1)));
+    }
     memcpy(out, r + TR_ROOTS, 4 * 16);
     out[16] = r[TR_LO];
     out[17] = r[TR_HI];
     return nullptr;
+}
+
+}  // namespace
+
+extern "C" const char* zkh_page_tree_witgen(zkh_ctx* ctx, const zkh_circuit* c, size_t po2, size_t zk_cycles, const zkh_buf* code, const zkh_buf* proof,
+                                            size_t proof_words, const zkh_buf* nodes_before, const zkh_buf* nodes_after, size_t first_row, size_t count_rows,
+                                            zkh_buf* data, uint32_t out[18], const uint32_t* noise_key) {
+    return tree_witgen("page_tree_witgen", ctx, c, po2, zk_cycles, code, proof, proof_words, nodes_before, nodes_after, nullptr, first_row, count_rows, data, out, noise_key);
+}
+
+extern "C" const char* zkh_page_tree_witgen_nodes(zkh_ctx* ctx, const zkh_circuit* c, size_t po2, size_t zk_cycles, const zkh_buf* code, const zkh_buf* proof,
+                                                  size_t proof_words, const zkh_buf* dirty, size_t first_row, size_t count_rows, zkh_buf* data, uint32_t out[18],
+                                                  const uint32_t* noise_key) {
+    const char* who = "page_tree_witgen_nodes";
+    ZKH_REQUIRE(dirty, "%s: null argument", who);
+    return tree_witgen(who, ctx, c, po2, zk_cycles, code, proof, proof_words, nullptr, nullptr, dirty, first_row, count_rows, data, out, noise_key);
 }

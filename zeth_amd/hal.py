@@ -195,6 +195,8 @@ ABI = {
     "zkh_page_out_proof": (_err, [_vp, _vp, _sz, _sz, _vp, _vp, _vp, _vp]),
     "zkh_image_proof_verify": (_err, [_u32p, _sz, _u32p, _u32p]),
     "zkh_image_proof_walk": (_err, [_vp, _vp, _sz, _u32p, _u32p]),
+    "zkh_image_dirty_words": (_sz, [_sz, _sz]),
+    "zkh_image_proof_nodes": (_err, [_vp, _vp, _sz, _u32p, _u32p, _vp]),
     "zkh_page_circuit_code": (_err, [_vp, _vp, _sz, _sz, _sz, _vp]),
     "zkh_page_circuit_witgen": (_err, [_vp, _vp, _sz, _sz, _vp, _vp, _sz, _vp, _vp, _vp, _u32p, _u32p]),
     "zkh_page_circuit_witgen_part": (_err, [_vp, _vp, _sz, _sz, _vp, _vp, _sz, _vp, _vp, _sz, _vp, _u32p, _u32p]),
@@ -205,6 +207,7 @@ ABI = {
     "zkh_page_tree_plan": (_err, [_sz, _sz, _sz, _u32p, _sz, C.POINTER(C.c_size_t), _sz, C.POINTER(C.c_size_t)]),
     "zkh_page_tree_plan_device": (_err, [_vp, _sz, _sz, _sz, _vp, _sz, _sz, C.POINTER(C.c_size_t), _sz, C.POINTER(C.c_size_t), _u32p]),
     "zkh_page_tree_witgen": (_err, [_vp, _vp, _sz, _sz, _vp, _vp, _sz, _vp, _vp, _sz, _sz, _vp, _u32p, _u32p]),
+    "zkh_page_tree_witgen_nodes": (_err, [_vp, _vp, _sz, _sz, _vp, _vp, _sz, _vp, _sz, _sz, _vp, _u32p, _u32p]),
     "zkh_circuit_derived_data_columns": (_err, [_vp, _u32p, _sz, C.POINTER(_sz)]),
     "zkh_upload_data_trace": (_err, [_vp, _vp, _sz, _sz, _vp, _u32p, _i]),
     "zkh_ctx_h2d_bytes": (_sz, [_vp]),
@@ -663,6 +666,13 @@ def page_tree_plan(po2: int, zk_cycles: int, image_words: int, addrs) -> list:
     return [(int(parts[2 * p]), int(parts[2 * p + 1])) for p in range(n.value)]
 
 
+def image_dirty_words(image_words: int, pages: int) -> int:
+    """the bound on the words of the dirty-node table of a page-out of `pages` rows over an image of `image_words` words
+    (zkh_image_dirty_words: host only, no GPU; the Python twin is logup.image_dirty_words): 4 + h + 33 sum_k min(D, L >> k)"""
+    load_library()
+    return int(_lib.zkh_image_dirty_words(image_words, pages))
+
+
 class HipHal:
     """`impl Hal for HipHal` — one MI355X, one HIP stream, one driving thread."""
 
@@ -1012,6 +1022,30 @@ class HipHal:
         _check(_lib.zkh_image_proof_walk(self.ctx, proof.h, words, _ptr(before), _ptr(after)))
         return after
 
+    def image_dirty_words(self, image_words: int, pages: int) -> int:
+        """the module's image_dirty_words (host only: it needs no context)"""
+        return image_dirty_words(image_words, pages)
+
+    def image_proof_nodes(self, proof, root_before, words: Optional[int] = None, dirty: Optional[Buffer] = None):
+        """image_proof_walk that keeps what it recomputes (zkh_image_proof_nodes) -> (root_after, dirty): `dirty` is a Buffer that
+        starts with the DIRTY-NODE TABLE of the page-out (include/zkhal.h "THE UPDATE'S PROOF"; the numpy twin:
+        logup.reference_page_out_nodes), what page_tree_witgen_nodes reads in place of the two trees.  proof, root_before, words:
+        image_proof_walk's.  dirty: a Buffer of at least image_dirty_words(W, D) words to write (default: a new one of that size); it
+        is written only on success.  Raises HalError with the walk's message per cause after "image_proof_nodes: ", and on D = 0"""
+        before, after = _u32(root_before).reshape(-1), np.empty(DIGEST_WORDS, dtype=np.uint32)
+        if before.size != DIGEST_WORDS:
+            raise HalError(f"image_proof_nodes: root_before of {before.size} words")
+        if not isinstance(proof, Buffer):
+            proof = self.copy_from("image_proof", _u32(proof).reshape(-1))
+        if words is None:
+            words = proof.size()
+        if dirty is None:
+            head = proof.slice(0, 3).to_vec() if min(words, proof.size()) >= 3 else np.zeros(3, dtype=np.uint32)
+            bound = image_dirty_words(int(head[1]), int(head[2]))
+            dirty = self.alloc("image_dirty", bound if 0 < bound < 1 << 32 else 1)   # a bound past 32 bits, or a header that lies: the call refuses
+        _check(_lib.zkh_image_proof_nodes(self.ctx, proof.h, words, _ptr(before), _ptr(after), dirty.h))
+        return after, dirty
+
     def image_root(self, nodes: Buffer) -> np.ndarray:
         """the root of a committed tree: digest 1 of `nodes`, 8 words"""
         out = np.empty(DIGEST_WORDS, dtype=np.uint32)
@@ -1114,6 +1148,17 @@ class HipHal:
         columns (the host twin: p2_tree_tied.reference_tree_tied_part) and the same 18 words.  Raises HalError with one message per cause
         (include/zkhal.h "P2-TREE"); `data` is unspecified then"""
         return self._page_witgen(_lib.zkh_page_tree_witgen, 2 * DIGEST_WORDS + 2, circuit, po2, zk_cycles, code, proof, proof_words, nodes_before, nodes_after, (first, count), data, noise_seed)
+
+    def page_tree_witgen_nodes(self, circuit: Circuit, po2: int, zk_cycles: int, code: Buffer, proof: Buffer, proof_words: int, dirty: Buffer, first: int, count: int,
+                               data: Buffer, noise_seed: int) -> np.ndarray:
+        """page_tree_witgen from (proof, dirty) alone (zkh_page_tree_witgen_nodes): `dirty`, the table image_proof_nodes left, stands
+        in place of the two trees; the same cells and the same 18 words, for kinds 7 and 9.  Raises HalError as page_tree_witgen does,
+        on a table whose header does not fit its buffer or the proof, and with "node N of layer K is not in the dirty nodes" on a table
+        of another proof (include/zkhal.h "P2-TREE")"""
+        out = np.zeros(2 * DIGEST_WORDS + 2, dtype=np.uint32)
+        _k, kp = _key_ptr(noise_seed)
+        _check(_lib.zkh_page_tree_witgen_nodes(self.ctx, circuit.h, po2, zk_cycles, code.h, proof.h, proof_words, dirty.h, first, count, data.h, _ptr(out), kp))
+        return out
 
     def derive_multiplicities(self, circuit: Circuit, po2: int, zk_cycles: int, code: Buffer, data: Buffer) -> None:
         """fill the derived multiplicity columns of `data` on the active rows (zkh_derive_multiplicities): raises HalError on a table

@@ -100,19 +100,36 @@ def open_chain(who: str, prover, k: PageKind, segs: list, proof, proof_words: in
     return proof, po2, zk, code if path else code_call(), plan
 
 
-def seal_chain(who: str, prover, kind: int, segs, proof, proof_words: int, nodes_before, nodes_after, check: bool, plan_where: str = "host", single: bool = False) -> list:
+def part_witgen(who: str, prover, k: PageKind, nodes_before, nodes_after, dirty, single: bool = False):
+    """The witness call of one part, by its source -> f(circuit, po2, zk_cycles, code, proof, proof_words, *part, data, noise_seed), a
+    call of `prover`'s hal.  The two committed trees (nodes_before, nodes_after: the kind's own call), or `dirty`, the dirty-node table of
+    the page-out's proof (HipHal.image_proof_nodes): then both trees must be None, the kind a tree kind, and the call is
+    page_tree_witgen_nodes.  Only the keywords are looked at here: nothing of the prover is touched before the first witness."""
+    if dirty is None:
+        name = "page_circuit_witgen" if single else k.witgen
+        return lambda circuit, po2, zk, code, proof, words, *rest: getattr(prover.hal, name)(circuit, po2, zk, code, proof, words, nodes_before, nodes_after, *rest)
+    if k.family != "tree":
+        raise _hal.HalError(f"{who}: dirty nodes seal the tree kinds (7, 9); kind {k.kind} lays out paths, which read the two trees")
+    if nodes_before is not None or nodes_after is not None:
+        raise _hal.HalError(f"{who}: dirty nodes stand in place of the two trees: nodes_before and nodes_after must be None")
+    return lambda circuit, po2, zk, code, proof, words, *rest: prover.hal.page_tree_witgen_nodes(circuit, po2, zk, code, proof, words, dirty, *rest)
+
+
+def seal_chain(who: str, prover, kind: int, segs, proof, proof_words: int, nodes_before, nodes_after, check: bool, plan_where: str = "host", single: bool = False,
+               dirty=None) -> list:
     """Seal a page-out as a chain of parts of the untied kind `kind` -> the receipts, in the order of the parts.  segs, proof, single:
     open_chain's; nodes_before / nodes_after: the committed tree before and after the page-out.  Both trees are the WHOLE page-out's for
-    every part, so the parts could be sealed in any order, or on several ranks.  The code group and its control root are built once,
-    before the first witness, and the data buffer is reused.  A single seal's witness call is page_circuit_witgen."""
+    every part, so the parts could be sealed in any order, or on several ranks; with `dirty` (part_witgen: the tree kinds) a rank needs
+    neither tree, only the proof and its dirty-node table.  The code group and its control root are built once, before the first
+    witness, and the data buffer is reused.  A single seal's witness call is page_circuit_witgen."""
     k, segs = PAGE_KINDS[kind], list(segs)
+    witgen = part_witgen(who, prover, k, nodes_before, nodes_after, dirty, single)
     proof, po2, zk, code, plan = open_chain(who, prover, k, segs, proof, proof_words, plan_where, single=single)
-    witgen = getattr(prover.hal, "page_circuit_witgen" if single else k.witgen)
     control_root = prover.code_root(code, po2)
     data = prover.hal.alloc_elem("data", prover.group_sizes()[2] << po2)
     receipts = []
     for seg, part in zip(segs, plan):
-        out = witgen(prover.circuit, po2, zk, code, proof, proof_words, nodes_before, nodes_after, *part, data, seg.noise_seed)
+        out = witgen(prover.circuit, po2, zk, code, proof, proof_words, *part, data, seg.noise_seed)
         accum = prover.args_accumulate(seg, code, data, check=check) if k.accum == "args" else prover.syn_accumulate(seg, data)
         receipts.append(prover.seal_with_accum(seg, code, data, out, accum, check=check))
         receipts[-1].control_root = control_root.copy()
@@ -120,10 +137,12 @@ def seal_chain(who: str, prover, kind: int, segs, proof, proof_words: int, nodes
 
 
 def seal_tied_group(who: str, kind: int, seg_prover, seg, code, data, out_prefix, page_prover, page_segs, proof, proof_words: int, nodes_before, nodes_after,
-                    check: bool, check_table: bool, plan_where: str = "host"):
+                    check: bool, check_table: bool, plan_where: str = "host", dirty=None):
     """The two passes of `seal_tied` (kind 8) and `seal_tied_tree` (kind 9), on open_chain -> (the segment's receipt, [the parts'
-    receipts]).  A part's `out` words before alpha are the kind's prefix of what the witness call returns and, for kind 9, out_base(h)."""
+    receipts]).  A part's `out` words before alpha are the kind's prefix of what the witness call returns and, for kind 9, out_base(h).
+    dirty: part_witgen's (kind 9: the parts' witnesses from the dirty-node table, both trees None)."""
     k, hal, page_segs = PAGE_KINDS[kind], seg_prover.hal, list(page_segs)
+    witgen = part_witgen(who, seg_prover, k, nodes_before, nodes_after, dirty)
     proof, po2, zk, page_code, plan = open_chain(who, page_prover, k, page_segs, proof, proof_words, plan_where,
                                                  " for the page-out (a page-out of no rows still has one part)", (("segment", seg_prover), ("page-out", page_prover)))
     head = proof.slice(0, 5).to_vec()
@@ -131,7 +150,7 @@ def seal_tied_group(who: str, kind: int, seg_prover, seg, code, data, out_prefix
     page_data = hal.alloc_elem("data", page_prover.group_sizes()[2] << po2)
 
     def part_witness(s, part):
-        return getattr(hal, k.witgen)(page_prover.circuit, po2, zk, page_code, proof, proof_words, nodes_before, nodes_after, *part, page_data, s.noise_seed)
+        return witgen(page_prover.circuit, po2, zk, page_code, proof, proof_words, *part, page_data, s.noise_seed)
 
     # pass one: the data roots, the segment's first
     roots = [seg_prover.data_root(data, seg.po2)]
@@ -187,13 +206,15 @@ def seal_tied(seg_prover, seg, code, data, out_prefix, page_prover, page_segs, p
 
 
 def seal_tied_tree(seg_prover, seg, code, data, out_prefix, page_prover, page_segs, proof, proof_words: int,
-                   nodes_before, nodes_after, check: bool = False, check_table: bool = True, plan: str = "host"):
+                   nodes_before, nodes_after, check: bool = False, check_table: bool = True, plan: str = "host", dirty=None):
     """`seal_tied` with P2-TREE-tied parts (circuits/p2_tree_tied.py): the page-out side of the group is one block per DIRTY NODE, not one
     path per word.  page_prover: a prover of P2-TREE-tied with p2_tree_tied.arguments(); the plan is seal_page_out_tree's, made on the
     "host" or on the "device" (`plan`); every other operand, both passes and the fingerprint check between them are seal_tied's.  A part's
-    out = the witness call's 18 words ‖ p2_tree_tied.out_base(h) ‖ the challenge ‖ its open total.  -> (the segment's receipt, [the parts'
-    receipts]), for `verify_tied_tree`."""
-    return seal_tied_group("seal_tied_tree", 9, seg_prover, seg, code, data, out_prefix, page_prover, page_segs, proof, proof_words, nodes_before, nodes_after, check, check_table, plan)
+    out = the witness call's 18 words ‖ p2_tree_tied.out_base(h) ‖ the challenge ‖ its open total.  dirty: the dirty-node table of the
+    proof (HipHal.image_proof_nodes) in place of the two trees, which are then None: the same seals, byte for byte.  -> (the segment's
+    receipt, [the parts' receipts]), for `verify_tied_tree`."""
+    return seal_tied_group("seal_tied_tree", 9, seg_prover, seg, code, data, out_prefix, page_prover, page_segs, proof, proof_words, nodes_before, nodes_after, check, check_table, plan,
+                           dirty)
 
 
 def link_page_parts(who: str, parts, root_before=None, first_lo=None, last_hi=None) -> tuple:

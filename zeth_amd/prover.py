@@ -331,7 +331,7 @@ class SegmentProver:
             self.page_out(seg, data, image, tree=tree)
         return receipt
 
-    def page_out(self, seg: Segment, data, image, tree=None, proof: bool = False, walk: bool = False, keep_before: bool = False):
+    def page_out(self, seg: Segment, data, image, tree=None, proof: bool = False, walk: bool = False, keep_before: bool = False, dirty: bool = False):
         """write the page table of the segment's derived data trace (a device Buffer) back into the memory image: image[p_addr] = p_out
         on the rows with p_on = 1 (zkh_page_out).  A call of its own, after the seal: a refused witness never touches the image.
         tree: the image's committed tree (hal.image_commit of the image as it is now), brought up to the new image in the same call
@@ -341,7 +341,15 @@ class SegmentProver:
         walk: with proof, the prover checks what it ships: the proof is walked on the device (zkh_image_proof_walk) from the tree's
         root as it is, and after the page-out the walked root must be the tree's; HalError, naming both roots, if it is not.
         keep_before: with proof, the tree is copied (zkh_eltwise_copy_elem) before the update and (words, the copy) is returned: the
-        two trees and the proof are what a P2-PAGE prover's `seal_page_out` takes."""
+        two trees and the proof are what a P2-PAGE prover's `seal_page_out` takes.
+        dirty: with proof, (words, dirty) is returned, `dirty` the dirty-node table of the proof (hal.image_proof_nodes: the walk from
+        the tree's root as it was, keeping what it recomputes), which with the proof is all that `seal_page_out_tree(dirty=...)` and
+        `seal_tied_tree(dirty=...)` read on any rank.  No tree is copied.  As with walk, the root that comes back must be the updated
+        tree's.  An empty page table is refused by image_proof_nodes (it is sealed from the tree)."""
+        if dirty and not proof:
+            raise _hal.HalError("page_out: dirty=True needs proof=True (the dirty nodes are read off the proof)")
+        if dirty and keep_before:
+            raise _hal.HalError("page_out: dirty=True with keep_before=True (the dirty nodes stand in place of the copied tree: ask for one)")
         if keep_before and not proof:
             raise _hal.HalError("page_out: keep_before=True needs proof=True (the copy goes with the proof)")
         if proof and tree is None:
@@ -351,8 +359,12 @@ class SegmentProver:
         if tree is None:
             self.hal.page_out(self.circuit, seg.po2, seg.zk_cycles, data, image)
             return None
-        words = walked = None
-        if proof and walk:
+        words = walked = table = None
+        if proof and dirty:
+            root_before = self.hal.image_root(tree)
+            buf = self.hal.alloc("image_proof", self.hal.image_proof_words(image.size(), (1 << seg.po2) - seg.zk_cycles))
+            words = self.hal.page_out_proof(self.circuit, seg.po2, seg.zk_cycles, data, image, tree, proof=buf)
+        elif proof and walk:
             buf = self.hal.alloc("image_proof", self.hal.image_proof_words(image.size(), (1 << seg.po2) - seg.zk_cycles))
             words = self.hal.page_out_proof(self.circuit, seg.po2, seg.zk_cycles, data, image, tree, proof=buf)
             walked = self.hal.image_proof_walk(buf, self.hal.image_root(tree), words=words.size)
@@ -363,12 +375,14 @@ class SegmentProver:
             before = self.hal.alloc("image_nodes_before", tree.size())
             self.hal.eltwise_copy_elem(before, tree)
         self.hal.page_out_tree(self.circuit, seg.po2, seg.zk_cycles, data, image, tree)
+        if dirty:
+            walked, table = self.hal.image_proof_nodes(buf, root_before, words=words.size)
         if walked is not None:
             root = self.hal.image_root(tree)
             if not np.array_equal(walked, root):
                 fmt = lambda r: " ".join(f"{int(w):08x}" for w in r)
                 raise _hal.HalError(f"page_out: the proof walks to root {fmt(walked)}, but the tree's root after the page-out is {fmt(root)}")
-        return (words, before) if keep_before else words
+        return (words, before) if keep_before else (words, table) if dirty else words
 
     def seal_page_out(self, seg: Segment, proof, proof_words: int, nodes_before, nodes_after, check: bool = False) -> SegmentReceipt:
         """Seal a page-out from root to root with P2-PAGE (this prover's circuit: circuits/p2_page.py): the code group for the image's
@@ -396,7 +410,7 @@ class SegmentProver:
         order of the parts."""
         return _page_seal.seal_chain("seal_page_out_ordered", self, 6, segs, proof, proof_words, nodes_before, nodes_after, check)
 
-    def seal_page_out_tree(self, segs, proof, proof_words: int, nodes_before, nodes_after, check: bool = False, plan: str = "host") -> list:
+    def seal_page_out_tree(self, segs, proof, proof_words: int, nodes_before, nodes_after, check: bool = False, plan: str = "host", dirty=None) -> list:
         """Seal a page-out of any size with P2-TREE (this prover's circuit: circuits/p2_tree.py, built with arguments=p2_tree.arguments())
         as a chain of parts: one block per DIRTY NODE of the tree instead of one path per word.  Part p's receipt's output is
         root_before ‖ root_after ‖ lo ‖ hi of its run of pairs of leaves (zkh_page_tree_witgen), so part p + 1 opens the root and
@@ -404,8 +418,10 @@ class SegmentProver:
         back once (D words).  The accum group is the circuit's bus (args_accumulate): a table that does not match the trees is refused
         there, and check=True names the key.  The other operands are seal_page_out_parts'; the control root does not depend on the
         image's size.  plan="device" plans where the table lies (zkh_page_tree_plan_device over (proof, 5 + h, D)): only the header is
-        read back; the parts, and so the receipts, are the same.  -> the receipts, in the order of the parts."""
-        return _page_seal.seal_chain("seal_page_out_tree", self, 7, segs, proof, proof_words, nodes_before, nodes_after, check, plan)
+        read back; the parts, and so the receipts, are the same.  dirty: the proof's dirty-node table (hal.image_proof_nodes, or
+        `page_out(..., proof=True, dirty=True)`) in place of the two trees, which are then None (zkh_page_tree_witgen_nodes): the same
+        receipts from (proof, dirty) alone.  -> the receipts, in the order of the parts."""
+        return _page_seal.seal_chain("seal_page_out_tree", self, 7, segs, proof, proof_words, nodes_before, nodes_after, check, plan, dirty=dirty)
 
     def prove_segment(self, seg: Segment) -> SegmentReceipt:
         code, data, out = self.witgen(seg)
