@@ -381,9 +381,9 @@ const char* zkh_derive_links(zkh_ctx*, const zkh_circuit*, size_t po2, size_t zk
  * comes first and a refusal leaves the image unchanged: the lowest row whose p_on is not 0 / 1, whose address is >= W, or whose address
  * does not follow a smaller one on a row with p_on = 1 (the table is a prefix of strictly increasing addresses, as the circuit demands:
  * a host-made table that repeats an address is refused, not resolved).  It is a call of its own so that a refused or aborted seal never
- * touches the image.  The prover can commit to the image, prove a page-out between two roots and seal that step (below: P2-PAGE); no
- * circuit ties p_in / p_out of a paging segment's OWN seal to that commitment yet, so the verifier of that seal does not learn which
- * image (ARGUMENTS). */
+ * touches the image.  The prover can commit to the image, prove a page-out between two roots and seal that step (below: P2-PAGE); a
+ * tied group (P2-PAGE-tied, P2-TREE-tied: zkh_accumulate_open, zkh_tie_challenge) ties p_in / p_out of a paging segment's OWN seal to
+ * that commitment over one shared bus, so the verifier of the group learns which image (THE TIE). */
 int zkh_circuit_pages(const zkh_circuit*);
 const char* zkh_derive_links_paged(zkh_ctx*, const zkh_circuit*, size_t po2, size_t zk_cycles, const zkh_buf* code, zkh_buf* data, const zkh_buf* image);
 const char* zkh_page_out(zkh_ctx*, const zkh_circuit*, size_t po2, size_t zk_cycles, const zkh_buf* data, zkh_buf* image);
@@ -731,8 +731,32 @@ void zkh_prove_abort(zkh_seal_job*);
 const char* zkh_code_root(zkh_prover*, const zkh_buf* code, size_t po2, uint32_t root[8]);
 /* zkh_data_root commits a data trace as zkh_prove_begin will: the root the seal of this trace carries, known before the seal is made
  * (the shared challenge of a tied group hashes the data roots of all its seals: zkh_tie_challenge).  zkh_prove_begin commits the group
- * again. */
+ * again; to commit it ONCE, hold the commitment:
+ *   zkh_commit_data      : zkh_data_root that keeps what it built (REDUCED WORDS IN, as above).  The commitment holds three device
+ *                          buffers of its own (coefficients, 4n evaluations, Merkle nodes) and does not alias `data`: the caller may
+ *                          overwrite or release the trace afterwards.  zkh_data_root is this call and a release.
+ *   zkh_commitment_root  : the root zkh_data_root gives.
+ *   zkh_commitment_bytes : the device bytes of the three buffers as zkh_ctx_memory's live_bytes counts them: 4 n (5 W + 64) for W
+ *                          columns at n = 2^po2 rows (0 for NULL).
+ *   zkh_prove_begin_held : zkh_prove_begin with the data group shared from the commitment instead of committed from a trace: the same
+ *                          header, transcript order (code, then data) and mix draw, code == NULL with a resident code group as there,
+ *                          hence the same seal byte for byte.  It SHARES and does not consume: the job takes its own references, so the
+ *                          commitment may be released before zkh_prove_finish, and one commitment may seed several jobs.  It refuses,
+ *                          before any launch and before a job exists, each with its own message naming both values: a NULL argument; a
+ *                          commitment made by a prover of another context; one whose column count is not this circuit's W_data; one
+ *                          whose po2 is not the call's; and what zkh_prove_begin refuses of po2 and out_global, in the same words after
+ *                          the prefix.  A refusal leaves the commitment untouched and usable.
+ *   zkh_commitment_release: drops the commitment's references (NULL is a no-op).
+ * DESTRUCTION ORDER: a commitment holds its buffers by reference count and keeps no pointer to the prover that made it, so it may be
+ * released after zkh_prover_destroy; like every zkh_buf it must be released before zkh_ctx_destroy. */
+typedef struct zkh_commitment zkh_commitment;
 const char* zkh_data_root(zkh_prover*, size_t po2, const zkh_buf* data, uint32_t root[8]);
+const char* zkh_commit_data(zkh_prover*, size_t po2, const zkh_buf* data, zkh_commitment** out);
+const char* zkh_commitment_root(const zkh_commitment*, uint32_t root[8]);
+size_t zkh_commitment_bytes(const zkh_commitment*);
+void zkh_commitment_release(zkh_commitment*);
+const char* zkh_prove_begin_held(zkh_prover*, size_t po2, const zkh_buf* code, const zkh_commitment* data, const uint32_t* out_global,
+                                 zkh_seal_job** job, uint32_t* mix_global);
 const char* zkh_syn_control_root(zkh_prover*, size_t po2, size_t zk_cycles, uint32_t root[8]);
 
 /* ---- verifier: risc0_zkp::verify::verify — what `receipt.verify(image_id)` (cli.rs:103) runs per segment ----

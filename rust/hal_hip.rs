@@ -723,6 +723,48 @@ pub fn data_root(prover: *mut sys::ZkhProver, po2: usize, data: &HipBuffer<BabyB
     root
 }
 
+/// A data group committed once and kept for the seal (`zkh_commit_data`): coefficients, 4n evaluations and Merkle nodes in buffers of its
+/// own, none of them the trace.  It holds no pointer to the prover that made it, so it may outlive that prover; like a `HipBuffer` it
+/// must be dropped before the context.
+pub struct HeldCommitment { raw: *mut sys::ZkhCommitment }
+
+impl HeldCommitment {
+    pub fn commit(prover: *mut sys::ZkhProver, po2: usize, data: &HipBuffer<BabyBearElem>) -> Self {
+        let mut raw: *mut sys::ZkhCommitment = std::ptr::null_mut();
+        ffi(|| unsafe { sys::zkh_commit_data(prover, po2, data.raw, &mut raw) });
+        HeldCommitment { raw }
+    }
+    /// the root `data_root` gives for the same trace
+    pub fn root(&self) -> [u32; 8] {
+        let mut root = [0u32; 8];
+        ffi(|| unsafe { sys::zkh_commitment_root(self.raw, root.as_mut_ptr()) });
+        root
+    }
+    /// device bytes of the three buffers held, as the context counts live bytes
+    pub fn bytes(&self) -> usize {
+        unsafe { sys::zkh_commitment_bytes(self.raw) }
+    }
+}
+
+impl Drop for HeldCommitment {
+    fn drop(&mut self) {
+        unsafe { sys::zkh_commitment_release(self.raw) };
+    }
+}
+
+/// `zkh_prove_begin` from a held commitment (`zkh_prove_begin_held`): nothing of the data group is computed again, and the seal is the one
+/// `zkh_prove_begin` of the committed trace gives.  The job takes references of its own: `held` may be dropped before `zkh_prove_finish`
+/// and may seed further jobs.  `code` = None shares the prover's resident code group.  -> (the job, the mix challenges).
+pub fn prove_begin_held(prover: *mut sys::ZkhProver, po2: usize, code: Option<&HipBuffer<BabyBearElem>>, held: &HeldCommitment, out_global: &[u32],
+                        mix_words: usize) -> (*mut sys::ZkhSealJob, Vec<u32>) {
+    let mut job: *mut sys::ZkhSealJob = std::ptr::null_mut();
+    let mut mix = vec![0u32; mix_words.max(1)];
+    let code_raw = code.map_or(std::ptr::null(), |c| c.raw as *const sys::ZkhBuf);
+    ffi(|| unsafe { sys::zkh_prove_begin_held(prover, po2, code_raw, held.raw, out_global.as_ptr(), &mut job, mix.as_mut_ptr()) });
+    mix.truncate(mix_words);
+    (job, mix)
+}
+
 /// alpha ‖ beta of a tied group from its data roots in order, the segment's first (`zkh_tie_challenge`; host only): prover and
 /// verifier call the same function.
 pub fn tie_challenge(roots: &[[u32; 8]]) -> [u32; 8] {

@@ -27,7 +27,9 @@ part next to its seal, zkh_accumulate_open next to zkh_accumulate, zkh_table_fin
 M28: P2-TREE-tied, the witness and the seal of a kind-9 part next to the kind-7 part's, alternating, and the page-out side of a whole tied
 group under P2-TREE-tied next to P2-PAGE-tied's on the same table; M29: P2-TREE from the proof alone, zkh_image_proof_nodes next to
 zkh_image_proof_walk and part 0's witness from the dirty nodes next to part 0's witness from the two trees on M24's table, alternating, with
-the words of the table, of the proof and of the two trees, and the copy of the tree that keep_before makes) on one MI355X, through the C ABI (HipHal).
+the words of the table, of the proof and of the two trees, and the copy of the tree that keep_before makes; M30: held commitments, a
+whole tied group on M28's setup sealed in two passes next to the same group with hold_bytes for everything, alternating, and for one
+part zkh_commit_data + zkh_prove_begin_held next to zkh_data_root + zkh_prove_begin, with the bytes held) on one MI355X, through the C ABI (HipHal).
 
 Each line of output is one JSON object: the op, its shape, the average wall time of one call (stream drained on both
 sides of `reps` back-to-back calls), its ALGORITHMIC bytes (SURVEY.md §8a "B_alg": inputs read once + outputs written
@@ -1572,6 +1574,94 @@ def main() -> None:
                               "witness_nodes_over_trees": round(med["witness_part_0_from_dirty_nodes"] / med["witness_part_0_from_trees"], 4)}), flush=True)
             del before, after, proof, dirty, copy
         del datas
+    if want("M30"):
+        # Held commitments (DESIGN.md §2 "THE TIE"): a whole tied group sealed in two passes (hold_bytes = 0, the parent's path: every data
+        # group committed twice, every part's witness generated twice) next to the same group with a budget that holds everything
+        # (zkh_commit_data in pass one, zkh_prove_begin_held in pass two), on M28's setup: po2 20, M24's table of 662 267 addresses over
+        # 2^20 words, kind 9, 4 parts; the segment is SYN-LOOKUP-tied FULL over M27's traces, whose page table is not this table, so the
+        # group is sealed with check_table=False: every seal is made, at the cost it has in a group that cancels.  Beside it, for one
+        # part, zkh_commit_data + zkh_prove_begin_held next to zkh_data_root + zkh_prove_begin (the job is dropped: no finish).  One
+        # run, alternating windows, median and spread; the bytes a part's commitment holds and the live high-water mark after each arm's
+        # first group (meaningful with --only M30: the mark is the context's).  The seals of the two arms must be the same.  No threshold.
+        import ctypes as C
+        from zeth_amd import hal as zhal, page_seal
+        from zeth_amd.circuits import p2_page, p2_tree, p2_tree_tied, syn_lookup
+        from zeth_amd.prover import Segment, SegmentProver
+        runs, zk, D, W = 7, 1994, 662267, 1 << 20
+        spread = lambda ts: {"median_ms": round(float(np.median(ts)) * 1e3, 4), "min_ms": round(min(ts) * 1e3, 4), "max_ms": round(max(ts) * 1e3, 4)}   # noqa: E731
+        h = p2_page.tree_height(W)
+        image_h = rand_fp(rng, W)
+        addrs = np.sort(rng.choice(W, D, replace=False)).astype(np.int64)
+        outs = rand_fp(rng, D)
+        table = np.stack([addrs.astype(np.uint32), image_h[addrs], outs], axis=1).reshape(-1)
+        proof_h = np.concatenate([np.array([0x5A4B5531, W, D, 0, h] + [0] * h, dtype=np.uint32), table])
+        image = hal.alloc_elem("m30i", W)
+        image.write(image_h)
+        before = hal.image_commit(image)
+        image_h[addrs] = outs
+        image.write(image_h)
+        after = hal.image_commit(image)
+        del image
+        proof = hal.copy_from("m30p", proof_h)
+        page = SegmentProver(hal, p2_tree_tied.p2_tree_tied_circuit(), arguments=p2_tree_tied.arguments())
+        plan = hal.page_tree_plan(args.po2, zk, W, addrs)
+        desc, blob = syn_lookup.build_syn_lookup(syn_lookup.FULL, link=True, reads=True, pages=True, tied=True)
+        segp = SegmentProver(hal, desc, arguments=blob)
+        code_h, data_h, _out = syn_lookup.witness(syn_lookup.FULL, args.po2, zk, seed=17, link=True, reads=True, pages=True, image=np.zeros(1 << 20, dtype=np.uint32))
+        scode, sdata = hal.copy_from("m30sc", code_h), hal.copy_from("m30sd", data_h)
+        del code_h, data_h
+        seg = Segment(index=0, po2=args.po2, zk_cycles=zk, noise_seed=0x2E80)
+        parts = [Segment(index=1 + p, po2=args.po2, zk_cycles=zk, noise_seed=0x2E81 + p) for p in range(len(plan))]
+        prefix = np.zeros(segp.out_size() - page_seal.TIE_WORDS, dtype=np.uint32)
+        sealed = {}
+
+        def group(name, hold):
+            def fn():
+                sealed[name] = page_seal.seal_tied_tree(segp, seg, scode, sdata, prefix, page, parts, proof, proof_h.size, before, after, check_table=False, hold_bytes=hold)
+            return fn
+        arms = [("group_two_passes", group("two_passes", 0)), ("group_held", group("held", 1 << 50))]
+        live0, peaks = hal.memory()["live"], {}
+        for name, fn in arms:                                                # the first group of each arm: the mark it leaves, and the seals
+            fn()
+            peaks[name] = hal.memory()["peak"] - live0
+        (seg_a, parts_a), (seg_b, parts_b) = sealed["two_passes"], sealed["held"]
+        assert np.array_equal(seg_a.seal, seg_b.seal) and all(np.array_equal(a.seal, b.seal) for a, b in zip(parts_a, parts_b)), "the held group's seals differ"
+        # one part: the commit and the begin, the job dropped
+        code = hal.page_tree_code(page.circuit, args.po2, zk)
+        data = hal.alloc_elem("m30d", p2_tree_tied.WD * n)
+        hal.page_tree_witgen(page.circuit, args.po2, zk, code, proof, proof_h.size, before, after, plan[0][0], plan[0][1], data, seg.noise_seed)
+        out = np.zeros(page.out_size(), dtype=np.uint32)
+        mix = np.zeros(max(1, int(page.circuit.desc[8])), dtype=np.uint32)
+        job, u32p = C.c_void_p(), zhal._u32p
+        part_bytes = {}
+
+        def part_two_passes():
+            page.data_root(data, args.po2)
+            zhal._check(zhal._lib.zkh_prove_begin(page.h, args.po2, code.h, data.h, out.ctypes.data_as(u32p), C.byref(job), mix.ctypes.data_as(u32p)))
+            zhal._lib.zkh_prove_abort(job)
+
+        def part_held():
+            com = page.commit_data(data, args.po2)
+            part_bytes["commitment"] = com.bytes
+            zhal._check(zhal._lib.zkh_prove_begin_held(page.h, args.po2, code.h, com.h, out.ctypes.data_as(u32p), C.byref(job), mix.ctypes.data_as(u32p)))
+            zhal._lib.zkh_prove_abort(job)
+            com.release()
+        fns = arms + [("part_data_root_then_prove_begin", part_two_passes), ("part_commit_data_then_prove_begin_held", part_held)]
+        t = {name: [] for name, _ in fns}
+        for _ in range(runs):
+            for name, fn in fns:
+                t[name].append(timed(hal, fn, args.reps))
+        med = {name: float(np.median(v)) for name, v in t.items()}
+        print(json.dumps({"bench": "M30", "library": os.path.basename(os.environ.get("ZKH_LIBRARY", "") or "libzkhal_mi355x.so"), "po2": args.po2,
+                          "image_words": W, "layers": h, "table_rows": D, "block_slots": p2_tree.block_slots(args.po2, zk), "parts": len(plan),
+                          "runs": runs, "reps": args.reps, **{name: spread(v) for name, v in t.items()},
+                          "columns": {"segment_data": segp.group_sizes()[2], "part_data": p2_tree_tied.WD},
+                          "bytes": {"part_commitment": part_bytes["commitment"], "part_trace": 4 * p2_tree_tied.WD * n,
+                                    "segment_commitment": page_seal.commitment_bytes(segp.group_sizes()[2], args.po2),
+                                    "peak_live_over_start": peaks},
+                          "group_held_over_two_passes": round(med["group_held"] / med["group_two_passes"], 4),
+                          "part_held_over_two_passes": round(med["part_commit_data_then_prove_begin_held"] / med["part_data_root_then_prove_begin"], 4)}), flush=True)
+        del scode, sdata, code, data, before, after, proof
     hal.close()
 
 

@@ -200,6 +200,15 @@ struct zkh_prover {
     std::map<size_t, std::unique_ptr<PolyGroup>> code_cache;   // po2 -> the committed code group, resident (zkh_prover_cache_code)
 };
 
+// A committed data group kept for a later seal (zkh_commit_data): the PolyGroup and what zkh_prove_begin_held compares.  It holds its
+// three device buffers by their own references and no pointer to the prover that made it, so it outlives that prover; like every
+// buffer it is released into a live context.
+struct zkh_commitment {
+    zkh_ctx* ctx;
+    size_t po2;
+    PolyGroup group;
+};
+
 extern "C" const char* zkh_prover_create(zkh_ctx* ctx, const zkh_circuit* circuit, zkh_prover** out) {
     ZKH_REQUIRE(ctx && circuit, "prover_create: null argument");
     *out = new zkh_prover{ctx, circuit, HostHash{ctx->h_rc, ctx->h_diag}, {}};
@@ -260,23 +269,30 @@ extern "C" const char* zkh_prover_cached_code_root(zkh_prover* pr, size_t po2, u
     return nullptr;
 }
 
-extern "C" const char* zkh_prove_begin(zkh_prover* pr, size_t po2, const zkh_buf* code, const zkh_buf* data,
-                                       const uint32_t* out_global, zkh_seal_job** out_job, uint32_t* mix_out) {
-    ZKH_REQUIRE(pr && data && out_global && out_job, "prove_begin: null argument");
-    ZKH_REQUIRE(code || pr->code_cache.count(po2), "prove_begin: no code trace and no resident code group for po2 %zu (zkh_prover_cache_code)", po2);
+// zkh_prove_begin and zkh_prove_begin_held: the data group is committed from the trace `data`, or shared from the commitment `held`
+// (exactly one of the two is given).  `who` is the prefix of every refusal; all of them come before a launch and before a job exists.
+static const char* prove_begin_impl(const char* who, zkh_prover* pr, size_t po2, const zkh_buf* code, const zkh_buf* data, const zkh_commitment* held,
+                                    const uint32_t* out_global, zkh_seal_job** out_job, uint32_t* mix_out) {
+    ZKH_REQUIRE(pr && (data || held) && out_global && out_job, "%s: null argument", who);
+    ZKH_REQUIRE(code || pr->code_cache.count(po2), "%s: no code trace and no resident code group for po2 %zu (zkh_prover_cache_code)", who, po2);
     zkh_ctx* c = pr->ctx;
     const zkh_circuit* cir = pr->circuit;
-    ZKH_REQUIRE(po2 >= 1 && po2 + 2 <= (size_t)MAX_LOG_N, "prove_begin: po2 %zu too large (max %d)", po2, MAX_LOG_N - 2);
+    ZKH_REQUIRE(po2 >= 1 && po2 + 2 <= (size_t)MAX_LOG_N, "%s: po2 %zu too large (max %d)", who, po2, MAX_LOG_N - 2);
     const size_t n = (size_t)1 << po2;
     const size_t wc = cir->group_size[GROUP_CODE], wd = cir->group_size[GROUP_DATA];
     const size_t out_size = cir->global_size[GLOBAL_OUT];
+    if (held) {
+        ZKH_REQUIRE(held->ctx == c, "%s: the commitment was made by a prover of context %p, this prover's is %p", who, (void*)held->ctx, (void*)c);
+        ZKH_REQUIRE(held->group.count == wd, "%s: the commitment holds %zu columns, the circuit's data group has %zu", who, held->group.count, wd);
+        ZKH_REQUIRE(held->po2 == po2, "%s: the commitment was made at po2 %zu, the call's is %zu", who, held->po2, po2);
+    }
+    for (size_t i = 0; i < out_size; i++) ZKH_REQUIRE(out_global[i] < P, "%s: output global %zu is not a reduced element", who, i);
     std::unique_ptr<zkh_seal_job> job(new zkh_seal_job());
     job->pr = pr; job->po2 = po2;
     Iop& iop = job->iop;
     iop.rng.h = &pr->hash;
     // ---- header: out globals + po2, both as field elements (write_field_elem_slice), bound into the transcript ----
     job->out_global.assign(out_global, out_global + out_size);
-    for (size_t i = 0; i < out_size; i++) ZKH_REQUIRE(out_global[i] < P, "prove_begin: output global %zu is not a reduced element", i);
     {
         std::vector<uint32_t> hdr(job->out_global);
         hdr.push_back(fp_encode((uint32_t)po2).v);
@@ -289,16 +305,28 @@ extern "C" const char* zkh_prove_begin(zkh_prover* pr, size_t po2, const zkh_buf
     // root is read back; the transcript still absorbs them in upstream's order (code, then data)
     if (code) ZKH_TRY(commit_group_enqueue(c, job->groups[GROUP_CODE], code, wc, n));
     else ZKH_TRY(job->groups[GROUP_CODE].share_from(*pr->code_cache[po2]));      // resident: nothing to compute
-    ZKH_TRY(commit_group_enqueue(c, job->groups[GROUP_DATA], data, wd, n));
+    if (held) ZKH_TRY(job->groups[GROUP_DATA].share_from(held->group));          // held: the job's own references, nothing to compute
+    else ZKH_TRY(commit_group_enqueue(c, job->groups[GROUP_DATA], data, wd, n));
     if (code) ZKH_TRY(commit_group_finish(c, iop, job->groups[GROUP_CODE]));
     else job->groups[GROUP_CODE].merkle.commit(iop);
-    ZKH_TRY(commit_group_finish(c, iop, job->groups[GROUP_DATA]));
+    if (held) job->groups[GROUP_DATA].merkle.commit(iop);
+    else ZKH_TRY(commit_group_finish(c, iop, job->groups[GROUP_DATA]));
     // ---- accum mix challenges ----
     job->mix_global.resize(cir->global_size[GLOBAL_MIX] ? cir->global_size[GLOBAL_MIX] : 1);
     for (size_t i = 0; i < cir->global_size[GLOBAL_MIX]; i++) job->mix_global[i] = iop.rng.random_elem();
     if (mix_out) memcpy(mix_out, job->mix_global.data(), 4 * cir->global_size[GLOBAL_MIX]);
     *out_job = job.release();
     return nullptr;
+}
+extern "C" const char* zkh_prove_begin(zkh_prover* pr, size_t po2, const zkh_buf* code, const zkh_buf* data,
+                                       const uint32_t* out_global, zkh_seal_job** out_job, uint32_t* mix_out) {
+    return prove_begin_impl("prove_begin", pr, po2, code, data, nullptr, out_global, out_job, mix_out);
+}
+// The same begin from a data group committed earlier (zkh_commit_data).  It shares: the job takes its own references on the three
+// buffers, so the commitment may be released before zkh_prove_finish and may seed any number of jobs.
+extern "C" const char* zkh_prove_begin_held(zkh_prover* pr, size_t po2, const zkh_buf* code, const zkh_commitment* data,
+                                            const uint32_t* out_global, zkh_seal_job** out_job, uint32_t* mix_out) {
+    return prove_begin_impl("prove_begin_held", pr, po2, code, nullptr, data, out_global, out_job, mix_out);
 }
 
 static const char* prove_finish_impl(zkh_seal_job* job, const zkh_buf* accum, uint32_t** seal, size_t* seal_words);
@@ -340,15 +368,39 @@ extern "C" const char* zkh_code_root(zkh_prover* pr, const zkh_buf* code, size_t
     return nullptr;
 }
 // Its sibling for the data group: the root a seal of this data trace carries (zkh_seal_data_root reads it out of the seal), before any seal
-// is made.  The roots of a tied group's data traces are what its shared challenge is drawn from (zkh_tie_challenge).  zkh_prove_begin
-// commits the data group again: a begin that takes a held commitment is not part of this.
+// is made.  The roots of a tied group's data traces are what its shared challenge is drawn from (zkh_tie_challenge).  zkh_commit_data keeps
+// what the commit built (coefficients, 4n evaluations, Merkle nodes: none of them aliases `data`) for zkh_prove_begin_held, which then
+// commits nothing; zkh_data_root is that call and a release, and zkh_prove_begin after it commits the group again.
+static const char* commit_data_impl(const char* who, zkh_prover* pr, size_t po2, const zkh_buf* data, bool has_out, zkh_commitment** com) {
+    ZKH_REQUIRE(pr && data && has_out, "%s: null argument", who);
+    ZKH_REQUIRE(po2 >= 1 && po2 + 2 <= (size_t)MAX_LOG_N, "%s: po2 %zu out of range", who, po2);
+    std::unique_ptr<zkh_commitment> held(new zkh_commitment{pr->ctx, po2, {}});
+    ZKH_TRY(commit_group_enqueue(pr->ctx, held->group, data, pr->circuit->group_size[GROUP_DATA], (size_t)1 << po2));
+    ZKH_TRY(held->group.merkle.fetch_top(pr->ctx));
+    *com = held.release();
+    return nullptr;
+}
+extern "C" const char* zkh_commit_data(zkh_prover* pr, size_t po2, const zkh_buf* data, zkh_commitment** out) {
+    return commit_data_impl("commit_data", pr, po2, data, out != nullptr, out);
+}
+extern "C" const char* zkh_commitment_root(const zkh_commitment* com, uint32_t root[8]) {
+    ZKH_REQUIRE(com && root, "commitment_root: null argument");
+    memcpy(root, com->group.merkle.root(), 32);
+    return nullptr;
+}
+// device bytes of the three buffers held, as the context's allocator counts them (zkh_ctx_memory's live_bytes)
+extern "C" size_t zkh_commitment_bytes(const zkh_commitment* com) {
+    if (!com) return 0;
+    size_t bytes = 0;
+    for (const zkh_buf* b : {com->group.coeffs.b, com->group.evaluated.b, com->group.merkle.nodes.b}) bytes += (b->a->bytes + 255) & ~(size_t)255;
+    return bytes;
+}
+extern "C" void zkh_commitment_release(zkh_commitment* com) { delete com; }
 extern "C" const char* zkh_data_root(zkh_prover* pr, size_t po2, const zkh_buf* data, uint32_t root[8]) {
-    ZKH_REQUIRE(pr && data && root, "data_root: null argument");
-    ZKH_REQUIRE(po2 >= 1 && po2 + 2 <= (size_t)MAX_LOG_N, "data_root: po2 %zu out of range", po2);
-    PolyGroup pg;
-    ZKH_TRY(commit_group_enqueue(pr->ctx, pg, data, pr->circuit->group_size[GROUP_DATA], (size_t)1 << po2));
-    ZKH_TRY(pg.merkle.fetch_top(pr->ctx));
-    memcpy(root, pg.merkle.root(), 32);
+    zkh_commitment* com = nullptr;
+    ZKH_TRY(commit_data_impl("data_root", pr, po2, data, root != nullptr, &com));
+    memcpy(root, com->group.merkle.root(), 32);
+    zkh_commitment_release(com);
     return nullptr;
 }
 extern "C" const char* zkh_syn_control_root(zkh_prover* pr, size_t po2, size_t zk_cycles, uint32_t root[8]) {

@@ -229,6 +229,11 @@ ABI = {
     "zkh_prove_abort": (None, [_vp]),
     "zkh_code_root": (_err, [_vp, _vp, _sz, _u32p]),
     "zkh_data_root": (_err, [_vp, _sz, _vp, _u32p]),
+    "zkh_commit_data": (_err, [_vp, _sz, _vp, C.POINTER(_vp)]),
+    "zkh_commitment_root": (_err, [_vp, _u32p]),
+    "zkh_commitment_bytes": (_sz, [_vp]),
+    "zkh_commitment_release": (None, [_vp]),
+    "zkh_prove_begin_held": (_err, [_vp, _sz, _vp, _vp, _u32p, C.POINTER(_vp), _u32p]),
     "zkh_syn_control_root": (_err, [_vp, _sz, _sz, _u32p]),
     "zkh_seal_data_root": (_err, [_vp, _u32p, _sz, _u32p]),
     "zkh_tie_challenge": (_err, [_u32p, _sz, _u32p]),
@@ -343,10 +348,13 @@ class Buffer:
     def __init__(self, hal: "HipHal", handle):
         self.hal, self.h = hal, handle
 
-    def __del__(self):
+    def release(self) -> None:
+        """give the handle back now instead of when the object is collected; idempotent (the buffer is unusable afterwards)"""
         h, self.h = getattr(self, "h", None), None
         if h and _lib is not None and getattr(self.hal, "ctx", None):
             _lib.zkh_release(h)      # (a context that is already closed has freed its pool)
+
+    __del__ = release
 
     def size(self) -> int:
         return _lib.zkh_size(self.h)

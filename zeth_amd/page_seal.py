@@ -136,28 +136,48 @@ def seal_chain(who: str, prover, kind: int, segs, proof, proof_words: int, nodes
     return receipts
 
 
+def commitment_bytes(columns: int, po2: int) -> int:
+    """the device bytes a held commitment of `columns` columns at 2^po2 rows takes (zkh_commitment_bytes; include/zkhal.h): coefficients,
+    4n evaluations, Merkle nodes.  Pass one of a tied group decides by it whether a seal fits before it commits."""
+    return 4 * (5 * columns + 64) << po2
+
+
 def seal_tied_group(who: str, kind: int, seg_prover, seg, code, data, out_prefix, page_prover, page_segs, proof, proof_words: int, nodes_before, nodes_after,
-                    check: bool, check_table: bool, plan_where: str = "host", dirty=None):
+                    check: bool, check_table: bool, plan_where: str = "host", dirty=None, hold_bytes: int = 0):
     """The two passes of `seal_tied` (kind 8) and `seal_tied_tree` (kind 9), on open_chain -> (the segment's receipt, [the parts'
     receipts]).  A part's `out` words before alpha are the kind's prefix of what the witness call returns and, for kind 9, out_base(h).
-    dirty: part_witgen's (kind 9: the parts' witnesses from the dirty-node table, both trees None)."""
+    dirty: part_witgen's (kind 9: the parts' witnesses from the dirty-node table, both trees None).
+    hold_bytes: the device bytes pass one may keep for pass two (`seal_tied`); 0 holds nothing.  The held seals are a prefix of the
+    group in its order, the segment first: `held` lists per held seal (its commitment, its trace if the trace is this call's, what its
+    witness call returned).  Whatever ends the call, a refusal included, every held commitment and trace is released first."""
     k, hal, page_segs = PAGE_KINDS[kind], seg_prover.hal, list(page_segs)
     witgen = part_witgen(who, seg_prover, k, nodes_before, nodes_after, dirty)
     proof, po2, zk, page_code, plan = open_chain(who, page_prover, k, page_segs, proof, proof_words, plan_where,
                                                  " for the page-out (a page-out of no rows still has one part)", (("segment", seg_prover), ("page-out", page_prover)))
     head = proof.slice(0, 5).to_vec()
     rows, h, table_at = int(head[2]), int(head[4]), 5 + int(head[4])
-    page_data = hal.alloc_elem("data", page_prover.group_sizes()[2] << po2)
+    page_words = page_prover.group_sizes()[2] << po2
+    page_data = hal.alloc_elem("data", page_words)
+    held, room, holding = [], hold_bytes, hold_bytes > 0
 
-    def part_witness(s, part):
-        return witgen(page_prover.circuit, po2, zk, page_code, proof, proof_words, *part, page_data, s.noise_seed)
+    def part_witness(s, part, into):
+        return witgen(page_prover.circuit, po2, zk, page_code, proof, proof_words, *part, into, s.noise_seed)
 
-    # pass one: the data roots, the segment's first
-    roots = [seg_prover.data_root(data, seg.po2)]
-    for s, part in zip(page_segs, plan):
-        part_witness(s, part)
-        roots.append(page_prover.data_root(page_data, po2))
-    challenge = _hal.tie_challenge(np.concatenate(roots))
+    def commit(prover, trace, trace_po2, own_trace, out):
+        """pass one of one seal -> its data root.  The seal is held if every seal before it is and it fits in what is left of the budget:
+        its commitment and, if the trace is this call's (a part's), the trace."""
+        nonlocal room, holding
+        trace_bytes = 4 * trace.size() if own_trace else 0
+        holding = holding and commitment_bytes(prover.group_sizes()[2], trace_po2) + trace_bytes <= room
+        if not holding:
+            return prover.data_root(trace, trace_po2)
+        com = prover.commit_data(trace, trace_po2)
+        held.append((com, trace if own_trace else None, out))
+        room -= com.bytes + trace_bytes
+        if room < 0:                                                            # the allocator rounded a tiny buffer up: not held after all
+            holding = False
+            held.pop()[0].release()
+        return com.root
 
     def open_seal(prover, s, code, data, prefix):
         accum = hal.alloc_elem("accum", prover.group_sizes()[0] << s.po2)
@@ -167,28 +187,62 @@ def seal_tied_group(who: str, kind: int, seg_prover, seg, code, data, out_prefix
             raise _hal.HalError(f"{who}: {out.size} out words (a prefix of {out.size - TIE_WORDS}, alpha, beta, the total), the circuit has {prover.out_size()}")
         return accum, total, out
 
-    seg_accum, seg_total, seg_out = open_seal(seg_prover, seg, code, data, out_prefix)
-    if check_table:
-        want = hal.table_fingerprint(proof, table_at, rows, challenge)
-        if not np.array_equal(seg_total, want):
-            raise _hal.HalError(f"{who}: the proof's table is not the segment's page table: the segment's open total is {_fmt_words(seg_total)}, "
-                                f"the fingerprint of the proof's {rows} rows is {_fmt_words(want)}")
-    # pass two: the seals
-    seg_receipt = seg_prover.seal_with_accum(seg, code, data, seg_out, lambda _mix: seg_accum, check=check)
-    seg_receipt.control_root = seg_prover.code_root(code, seg.po2)
-    del seg_accum
-    page_root = page_prover.code_root(page_code, po2)
-    receipts = []
-    for s, part in zip(page_segs, plan):
-        prefix = np.concatenate([part_witness(s, part)[:k.prefix_words], [k.mod.out_base(h)] if k.family == "tree" else []])
-        accum, _total, out = open_seal(page_prover, s, page_code, page_data, prefix)
-        receipts.append(page_prover.seal_with_accum(s, page_code, page_data, out, lambda _mix, accum=accum: accum, check=check))
-        receipts[-1].control_root = page_root.copy()
-    return seg_receipt, receipts
+    try:
+        # pass one: the data roots, the segment's first
+        roots = [commit(seg_prover, data, seg.po2, False, None)]
+        for s, part in zip(page_segs, plan):
+            if page_data is None:                                               # a held part kept the buffer: it is not reused
+                page_data = hal.alloc_elem("data", page_words)
+            n_held, out = len(held), part_witness(s, part, page_data)
+            roots.append(commit(page_prover, page_data, po2, True, out))
+            if len(held) > n_held:
+                page_data = None
+        challenge = _hal.tie_challenge(np.concatenate(roots))
+
+        seg_accum, seg_total, seg_out = open_seal(seg_prover, seg, code, data, out_prefix)
+        if check_table:
+            want = hal.table_fingerprint(proof, table_at, rows, challenge)
+            if not np.array_equal(seg_total, want):
+                raise _hal.HalError(f"{who}: the proof's table is not the segment's page table: the segment's open total is {_fmt_words(seg_total)}, "
+                                    f"the fingerprint of the proof's {rows} rows is {_fmt_words(want)}")
+        # pass two: the seals; a held seal begins from its commitment, which is then released with its trace
+        begin = lambda p: {"held": held[p][0]} if p < len(held) else {}
+        seg_receipt = seg_prover.seal_with_accum(seg, code, data, seg_out, lambda _mix: seg_accum, check=check, **begin(0))
+        if held:
+            _release(held[0])
+        seg_receipt.control_root = seg_prover.code_root(code, seg.po2)
+        del seg_accum
+        page_root = page_prover.code_root(page_code, po2)
+        receipts = []
+        for p, (s, part) in enumerate(zip(page_segs, plan), 1):
+            if p < len(held):
+                _com, trace, out = held[p]
+            else:
+                if page_data is None:
+                    page_data = hal.alloc_elem("data", page_words)
+                trace, out = page_data, part_witness(s, part, page_data)
+            prefix = np.concatenate([out[:k.prefix_words], [k.mod.out_base(h)] if k.family == "tree" else []])
+            accum, _total, out = open_seal(page_prover, s, page_code, trace, prefix)
+            receipts.append(page_prover.seal_with_accum(s, page_code, trace, out, lambda _mix, accum=accum: accum, check=check, **begin(p)))
+            receipts[-1].control_root = page_root.copy()
+            if p < len(held):
+                _release(held[p])
+        return seg_receipt, receipts
+    finally:
+        for seal in held:
+            _release(seal)
+
+
+def _release(held_seal) -> None:
+    """give back what pass one kept of one seal: its commitment and, if it is the call's own, its trace (both releases are idempotent)"""
+    com, trace, _out = held_seal
+    com.release()
+    if trace is not None:
+        trace.release()
 
 
 def seal_tied(seg_prover, seg, code, data, out_prefix, page_prover, page_segs, proof, proof_words: int,
-              nodes_before, nodes_after, check: bool = False, check_table: bool = True):
+              nodes_before, nodes_after, check: bool = False, check_table: bool = True, hold_bytes: int = 0):
     """Seal a paging segment and the page-out of its memory as ONE tied group (DESIGN.md §2 "THE TIE") -> (the segment's receipt, [the
     parts' receipts]): the seals share a bus under a challenge drawn from all their data roots, and `verify_tied` accepts them only
     together.  seg_prover: a prover of an open-bus paging circuit (SYN-LOOKUP-tied, built with its arguments); code, data: the segment's
@@ -201,12 +255,20 @@ def seal_tied(seg_prover, seg, code, data, out_prefix, page_prover, page_segs, p
          HalError "the proof's table is not the segment's page table": no part is sealed on a table that cannot cancel.
       2. the segment and then every part: the part's witness again (the same noise key gives the same trace, hence the same root),
          accumulate_open, out = prefix ‖ challenge ‖ total, zkh_prove_begin, with `check` check_witness, zkh_prove_finish.
+    hold_bytes: device bytes pass one may keep for pass two, 0 (the default) none.  Pass one walks the seals in their order, the segment
+    first, and holds a seal (commit_data instead of data_root) while the running sum stays within the budget: the commitment's bytes
+    (page_seal.commitment_bytes) and, for a part, the bytes of its data trace, which is then not reused for the next part.  The held
+    seals are a prefix: the first that does not fit and every one after it go the two passes above.  In pass two a held seal neither
+    generates its witness nor commits again: accumulate_open on the kept trace, seal_with_accum(held=...) (zkh_prove_begin_held), then
+    commitment and trace are released.  The seals are byte for byte those of hold_bytes = 0.  Whatever ends the call, the table
+    refusal between the passes, a failed check_witness and a refused accumulate included, what is held is released first.
     Every receipt carries its code group's root as `control_root`."""
-    return seal_tied_group("seal_tied", 8, seg_prover, seg, code, data, out_prefix, page_prover, page_segs, proof, proof_words, nodes_before, nodes_after, check, check_table)
+    return seal_tied_group("seal_tied", 8, seg_prover, seg, code, data, out_prefix, page_prover, page_segs, proof, proof_words, nodes_before, nodes_after, check, check_table,
+                           hold_bytes=hold_bytes)
 
 
 def seal_tied_tree(seg_prover, seg, code, data, out_prefix, page_prover, page_segs, proof, proof_words: int,
-                   nodes_before, nodes_after, check: bool = False, check_table: bool = True, plan: str = "host", dirty=None):
+                   nodes_before, nodes_after, check: bool = False, check_table: bool = True, plan: str = "host", dirty=None, hold_bytes: int = 0):
     """`seal_tied` with P2-TREE-tied parts (circuits/p2_tree_tied.py): the page-out side of the group is one block per DIRTY NODE, not one
     path per word.  page_prover: a prover of P2-TREE-tied with p2_tree_tied.arguments(); the plan is seal_page_out_tree's, made on the
     "host" or on the "device" (`plan`); every other operand, both passes and the fingerprint check between them are seal_tied's.  A part's
@@ -214,7 +276,7 @@ def seal_tied_tree(seg_prover, seg, code, data, out_prefix, page_prover, page_se
     proof (HipHal.image_proof_nodes) in place of the two trees, which are then None: the same seals, byte for byte.  -> (the segment's
     receipt, [the parts' receipts]), for `verify_tied_tree`."""
     return seal_tied_group("seal_tied_tree", 9, seg_prover, seg, code, data, out_prefix, page_prover, page_segs, proof, proof_words, nodes_before, nodes_after, check, check_table, plan,
-                           dirty)
+                           dirty, hold_bytes)
 
 
 def link_page_parts(who: str, parts, root_before=None, first_lo=None, last_hi=None) -> tuple:

@@ -116,6 +116,25 @@ class SegmentReceipt:
             raise _hal.HalError("verify_segment: receipt output does not match the seal's output globals")
 
 
+class Commitment:
+    """A data group committed once and kept for its seal (zkh_commit_data): `root` is what data_root gives for the trace, `bytes` the
+    device bytes of the three buffers held (coefficients, 4n evaluations, Merkle nodes; none aliases the trace).  `release()` gives
+    them back; it is idempotent and runs on __del__.  The commitment may outlive the prover that made it, not the context."""
+
+    def __init__(self, hal: "_hal.HipHal", handle, po2: int):
+        self.hal, self.h, self.po2 = hal, handle, po2
+        root = np.zeros(8, dtype=np.uint32)
+        _hal._check(_hal._lib.zkh_commitment_root(handle, root.ctypes.data_as(C.POINTER(C.c_uint32))))
+        self.root, self.bytes = root, int(_hal._lib.zkh_commitment_bytes(handle))
+
+    def release(self) -> None:
+        h, self.h = getattr(self, "h", None), None
+        if h and _hal._lib is not None and getattr(self.hal, "ctx", None):     # like Buffer: only released into a live context
+            _hal._lib.zkh_commitment_release(h)
+
+    __del__ = release
+
+
 class SegmentProver:
     """`SegmentProverImpl<H, C>` analogue bound to one HipHal (one GPU)."""
 
@@ -167,6 +186,13 @@ class SegmentProver:
         root = np.zeros(8, dtype=np.uint32)
         _hal._check(_hal._lib.zkh_data_root(self.h, po2, data.h, root.ctypes.data_as(C.POINTER(C.c_uint32))))
         return root
+
+    def commit_data(self, data, po2: int) -> Commitment:
+        """commit the data trace `data` once and keep the commitment (zkh_commit_data): `.root` is data_root's, and
+        seal_with_accum(held=...) begins the seal from it without committing again.  `data` is not aliased."""
+        h = C.c_void_p()
+        _hal._check(_hal._lib.zkh_commit_data(self.h, po2, data.h, C.byref(h)))
+        return Commitment(self.hal, h, po2)
 
     def witgen(self, seg: Segment):
         """Witness generation (code + data traces resident in HBM) — reported separately from the seal."""
@@ -245,16 +271,20 @@ class SegmentProver:
             raise _hal.HalError(line)
 
     def seal_with_accum(self, seg: Segment, code, data, out_global,
-                        accumulate: Callable[[np.ndarray], "_hal.Buffer"], check: bool = False) -> SegmentReceipt:
+                        accumulate: Callable[[np.ndarray], "_hal.Buffer"], check: bool = False, held: Optional[Commitment] = None) -> SegmentReceipt:
         """The same seal through the circuit-agnostic halves: zkh_prove_begin (header, code, data -> mix challenges),
         `accumulate(mix_global) -> accum buffer` supplied by the caller (CircuitHal::accumulate), zkh_prove_finish.
-        check: run check_witness between the accumulate and zkh_prove_finish; a witness that fails it raises, and no seal is made."""
+        check: run check_witness between the accumulate and zkh_prove_finish; a witness that fails it raises, and no seal is made.
+        held: the commitment of `data` (commit_data): the begin is zkh_prove_begin_held, which commits nothing, and the seal is the
+        same byte for byte.  `data` is still passed: `accumulate` and check_witness read the raw trace.  The commitment is shared, not
+        consumed: the caller releases it, before or after this call."""
         out = np.ascontiguousarray(out_global, dtype=np.uint32)
         wa = self.group_sizes()[0]
         job = C.c_void_p()
         mix = np.zeros(max(1, int(self.circuit.desc[8])), dtype=np.uint32)
-        _hal._check(_hal._lib.zkh_prove_begin(self.h, seg.po2, self._code_handle(seg, code), data.h, out.ctypes.data_as(C.POINTER(C.c_uint32)),
-                                              C.byref(job), mix.ctypes.data_as(C.POINTER(C.c_uint32))))
+        begin, operand = (_hal._lib.zkh_prove_begin, data.h) if held is None else (_hal._lib.zkh_prove_begin_held, held.h)
+        _hal._check(begin(self.h, seg.po2, self._code_handle(seg, code), operand, out.ctypes.data_as(C.POINTER(C.c_uint32)),
+                          C.byref(job), mix.ctypes.data_as(C.POINTER(C.c_uint32))))
         try:
             accum = accumulate(mix[: int(self.circuit.desc[8])])
             if accum.size() != wa << seg.po2:
