@@ -75,6 +75,39 @@ def test_forward_path_switches(hal, oracle, log_n, bits):
     assert m is None, f"log_n {log_n} expand_bits {bits}: {m}"
 
 
+# ---- 2b. the kernels launched are the planned ones ----
+PLAN_CASES = ([("fwd", log_n, bits) for log_n, bits in ((16, 0), (18, 2), (18, 5), (20, 2), (21, 0), (22, 5))] +
+              [("inv", log_n, zk) for log_n in (13, 16, 18, 20, 21, 22) for zk in ("plain", "zk")])
+
+
+@pytest.mark.parametrize("direction,log_n,arg", PLAN_CASES)
+def test_launches_match_the_plan(hal, direction, log_n, arg):
+    """One column, profiler on: the scopes the call records are the kernel sequence tests/golden/ntt_plan.json holds for the case
+    (the smallest size of each sequence), one launch each — a pass that moved to another kernel would still compute the same words."""
+    from test_ntt_plan import kernels_of, load_golden
+    n = 1 << log_n
+    if direction == "fwd":
+        op = "batch_expand_into_evaluate_ntt"
+        out, src = hal.alloc_elem("out", n), hal.copy_from("in", np.zeros(n >> arg, np.uint32))
+        call = lambda: hal.batch_expand_into_evaluate_ntt(out, src, 1, arg)
+    else:
+        op = "batch_interpolate_ntt_zk_shift" if arg == "zk" else "batch_interpolate_ntt"
+        io = hal.copy_from("io", np.zeros(n, np.uint32))
+        call = (lambda: hal.batch_interpolate_ntt_zk_shift(io, 1)) if arg == "zk" else (lambda: hal.batch_interpolate_ntt(io, 1))
+    want = {}
+    for k in kernels_of(load_golden()[f"{direction} {log_n} {arg}"]):
+        want[f"{op}:k_ntt_{k}"] = want.get(f"{op}:k_ntt_{k}", 0) + 1
+    hal.prof_enable(True)
+    try:
+        hal.prof_reset()
+        call()
+        hal.sync()
+        got = {r["name"]: r["calls"] for r in hal.prof_get() if r["calls"]}
+    finally:
+        hal.prof_enable(False)
+    assert got == want
+
+
 # ---- 3. inverse, every entry point ----
 SENTINEL = 0xDEADBEEF       # not a field element: a word of `out` that a transform left behind shows
 

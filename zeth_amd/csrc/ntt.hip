@@ -12,6 +12,7 @@
 //   HBM traffic: 8 B per element per pass (one read + one write), i.e. 16 B/elem for k <= 22, 24 B/elem up to 2^26.
 #include "common.h"
 #include "ntt_lazy.h"
+#include "ntt_plan.h"
 
 using namespace zkh;
 
@@ -32,17 +33,21 @@ struct PassParams {
     uint32_t twiddle;        // 1: apply the inter-pass twiddle (pre for DIT, post for DIF)
     uint32_t scale;          // inverse last pass: multiply by n^-1 (Montgomery word) ...
     uint32_t zk_shift;       // ... and by 3^bitrev(i)
-    const uint32_t* tile_tw; // w_{2^12}^j
+    const uint32_t* tile_tw; // w_{2^12}^j (k_ntt_pass alone)
     const uint32_t* layer_tw; // per-layer tables: [2^(j-1) + e] = w_j^e
     const uint32_t* tw_lo;   // w_{2^26}^lo
     const uint32_t* tw_hi;   // w_{2^26}^(4096 hi), hi < 2^14
     const uint32_t* sh_lo;
     const uint32_t* sh_hi;
     uint32_t tiles_per_col;
-    uint32_t lazy;           // forward register-radix pair (low12 + high<8|10>): see radix_layers<..., LAZY>
     uint32_t lazy_comp;      // R^(number of lazy reductions on a path) as a Montgomery word: folded into the four-step twiddle
     uint32_t shift16[16];    // inverse last pass: n^-1 * 3^(bitrev4(k) << (log_n - 4)), k < 16 (Montgomery; 0 = unused)
 };
+
+// base^ex from a two-level table pair: lo[k] = base^k, hi[k] = base^(4096 k)
+__device__ __forceinline__ uint32_t two_level(const uint32_t* lo, const uint32_t* hi, uint32_t ex) {
+    return mul_mod(lo[ex & (TW_SIZE - 1)], hi[ex >> TW_BITS]);
+}
 
 // global index of tile element (m, t):  a*2^(L+R) + m*2^L + l0 + t
 template <bool INVERSE>
@@ -73,7 +78,7 @@ __global__ __launch_bounds__(NTT_THREADS) void k_ntt_pass(PassParams p) {
         if (!INVERSE && p.twiddle) {
             const uint32_t r = __brev(m) >> (32 - p.R);
             const uint32_t ex = ((l0 + t) * r) << tw_shift;          // < 2^26
-            const uint32_t w = mul_mod(p.tw_lo[ex & (TW_SIZE - 1)], p.tw_hi[ex >> TW_BITS]);
+            const uint32_t w = two_level(p.tw_lo, p.tw_hi, ex);
             v = mul_mod(v, w);
         }
         tile[e] = v;
@@ -121,100 +126,18 @@ __global__ __launch_bounds__(NTT_THREADS) void k_ntt_pass(PassParams p) {
             if (p.twiddle) {
                 const uint32_t r = __brev(m) >> (32 - p.R);
                 const uint32_t ex = ((l0 + t) * r) << tw_shift;
-                const uint32_t w = mul_mod(p.tw_lo[ex & (TW_SIZE - 1)], p.tw_hi[ex >> TW_BITS]);
+                const uint32_t w = two_level(p.tw_lo, p.tw_hi, ex);
                 v = mul_mod(v, w);
             }
             if (p.scale) v = mul_mod(v, p.scale);
             if (p.zk_shift) {
                 const uint32_t pos = (uint32_t)gi;                     // position within the column
                 const uint32_t ex = __brev(pos) >> (32 - p.log_n);
-                v = mul_mod(v, mul_mod(p.sh_lo[ex & (TW_SIZE - 1)], p.sh_hi[ex >> TW_BITS]));
+                v = mul_mod(v, two_level(p.sh_lo, p.sh_hi, ex));
             }
         }
         out[gi] = v;
     }
-}
-
-// Top pass, index bits [L, L + R) with L + R = log_n, L >= 12 and R in 1..4 — what is left above the register-radix passes at 2^21 and
-// 2^23 .. 2^26 (po2 19, 21 .. 24).  One lane = 4 consecutive low indices x ALL 2^R rows, in registers: rows are 2^L words apart, so every
-// load and store is a 16-byte piece of a contiguous run (the pass streams the columns once, at HBM speed), the R butterfly layers use
-// wave-uniform twiddles (w_{2^j}^low: scalar loads), and the four-step twiddle of row m at low index j is (w^j)^bitrev(m): ONE two-level
-// table root per lane, the neighbours and the powers by products.  Same arithmetic as k_ntt_pass on the same tile (canonical words in,
-// canonical words out): results are identical.  (round 5: the generic LDS kernel spent 8.8 ms per po2-21 seal here, 15.3 at po2 22.)
-template <int R, bool INVERSE>
-__global__ __launch_bounds__(256) void k_ntt_top(PassParams p) {
-    constexpr int N = 1 << R;
-    const uint32_t j0 = (blockIdx.x * 256u + threadIdx.x) << 2;             // first of this lane's 4 low indices, < 2^L
-    const uint32_t* in = p.in + (size_t)blockIdx.y * p.in_col_stride + j0;
-    uint32_t* out = p.out + (size_t)blockIdx.y * p.out_col_stride + j0;
-    const uint32_t tw_shift = MAX_LOG_N - p.log_n;
-    uint32_t v[N][4];
-#pragma unroll
-    for (int m = 0; m < N; m++) {
-        const uint4 w = *(const uint4*)(in + ((size_t)m << p.L));
-        v[m][0] = w.x; v[m][1] = w.y; v[m][2] = w.z; v[m][3] = w.w;
-    }
-    auto root = [&](uint32_t e) -> uint32_t {                                // w_{log_n}^e, e < 2^log_n
-        const uint32_t ex = e << tw_shift;
-        return mul_mod(p.tw_lo[ex & (TW_SIZE - 1)], p.tw_hi[ex >> TW_BITS]);
-    };
-    // v[m][c] *= (w^(j0 + c))^bitrev_R(m): forward before the layers (DIT pre-twiddle), inverse after them (DIF post-twiddle)
-    auto four_step = [&]() {
-        const uint32_t step = root(1u);                                      // (wave-uniform)
-        uint32_t g = root(j0);
-#pragma unroll
-        for (int c = 0; c < 4; c++) {
-            uint32_t pw[N];
-            pw[1] = g;
-#pragma unroll
-            for (int r = 2; r < N; r++) pw[r] = mul_mod(pw[r - 1], g);
-#pragma unroll
-            for (int m = 1; m < N; m++) {
-                const int r = (int)(__builtin_bitreverse32((uint32_t)m) >> (32 - R));
-                v[m][c] = mul_mod(v[m][c], pw[r]);
-            }
-            if (c < 3) g = mul_mod(g, step);
-        }
-    };
-    if (!INVERSE) {
-        four_step();
-#pragma unroll
-        for (int j = 1; j <= R; j++) {
-            const int hb = j - 1;
-#pragma unroll
-            for (int i0 = 0; i0 < N; i0++) {
-                if (i0 & (1 << hb)) continue;
-                const int low = i0 & ((1 << hb) - 1), i1 = i0 + (1 << hb);
-                const uint32_t w = low ? p.tile_tw[(uint32_t)low << (LDS_TW_LOG - j)] : 0u;     // low == 0: the unit twiddle, no product
-#pragma unroll
-                for (int c = 0; c < 4; c++) {
-                    const uint32_t x = v[i0][c], y = low ? mul_mod(v[i1][c], w) : v[i1][c];
-                    v[i0][c] = add_mod(x, y);
-                    v[i1][c] = sub_mod(x, y);
-                }
-            }
-        }
-    } else {
-#pragma unroll
-        for (int j = R; j >= 1; j--) {
-            const int hb = j - 1;
-#pragma unroll
-            for (int i0 = 0; i0 < N; i0++) {
-                if (i0 & (1 << hb)) continue;
-                const int low = i0 & ((1 << hb) - 1), i1 = i0 + (1 << hb);
-                const uint32_t w = low ? p.tile_tw[(uint32_t)low << (LDS_TW_LOG - j)] : 0u;
-#pragma unroll
-                for (int c = 0; c < 4; c++) {
-                    const uint32_t x = v[i0][c], y = v[i1][c];
-                    v[i0][c] = add_mod(x, y);
-                    v[i1][c] = low ? mul_mod(x - y + P, w) : sub_mod(x, y);    // lazy difference in (0, 2P): a valid Montgomery operand
-                }
-            }
-        }
-        four_step();
-    }
-#pragma unroll
-    for (int m = 0; m < N; m++) *(uint4*)(out + ((size_t)m << p.L)) = make_uint4(v[m][0], v[m][1], v[m][2], v[m][3]);
 }
 
 // zk_shift alone (Hal::zk_shift): io[c][i] *= 3^bitrev(i)
@@ -223,7 +146,7 @@ __global__ void k_zk_shift(uint32_t* io, size_t total, uint32_t log_n, const uin
     if (i >= total) return;
     const uint32_t pos = (uint32_t)(i & (((size_t)1 << log_n) - 1));
     const uint32_t ex = log_n ? __brev(pos) >> (32 - log_n) : 0;
-    io[i] = mul_mod(io[i], mul_mod(sh_lo[ex & (TW_SIZE - 1)], sh_hi[ex >> TW_BITS]));
+    io[i] = mul_mod(io[i], two_level(sh_lo, sh_hi, ex));
 }
 
 // In-place bit reversal of each column through LDS tiles so that both the read and the write side are contiguous
@@ -285,7 +208,7 @@ template <int LOGR, bool INVERSE, bool BASE0, int J_LO, bool LAZY = false>
 __device__ __forceinline__ void radix_layers(uint32_t (&v)[1 << LOGR], const uint32_t* __restrict__ ltab,
                                              const uint32_t base_low, const int first_b) {
     constexpr int N = 1 << LOGR;
-    if (!INVERSE && LAZY) {
+    if constexpr (!INVERSE && LAZY) {       // (constexpr: lazy rounds exist for even LOGR only)
         lazy_layers<LOGR, BASE0, J_LO>(v, ltab, base_low, first_b);     // ntt_lazy.h
     } else if (INVERSE) {
 #pragma unroll
@@ -363,7 +286,7 @@ __global__ __launch_bounds__(256) void k_ntt_low12(PassParams p) {
             // 3^bitrev(pos0 + k) = 3^bitrev(pos0) * 3^(bitrev4(k) << (log_n - 4)): one two-level lookup per lane, the 16
             // k-dependent factors (already times n^-1) are kernel arguments
             const uint32_t ex = __brev((uint32_t)pos0) >> (32 - p.log_n);
-            const uint32_t b = mul_mod(p.sh_lo[ex & (TW_SIZE - 1)], p.sh_hi[ex >> TW_BITS]);
+            const uint32_t b = two_level(p.sh_lo, p.sh_hi, ex);
 #pragma unroll
             for (int k = 0; k < 16; k++) v[k] = mul_mod(mul_mod(v[k], b), p.shift16[k]);
         } else if (p.scale) {
@@ -490,6 +413,9 @@ __global__ __launch_bounds__(1 << RH) void k_ntt_high(PassParams p) {
 #pragma unroll
                 for (int k = 0; k < 4; k++) {
                     uint32_t x = mul_mod(u[k], tw[4 * i + k]);
+                    // never taken: a strided pass is not the last inverse one, so p.scale is 0 here (tests/cpp/ntt_plan_test.cpp).  It
+                    // stays for what the uniform branch does to the schedule: each word is stored as soon as it is ready; as one
+                    // straight-line block the kernel ran 3 % longer (2.09 against 2.02 ms, 208 x 2^22: profiles/r37_ntt_plan.json)
                     if (p.scale) x = mul_mod(x, p.scale);
                     TILE_OUT(m0 + k) = x;
                 }
@@ -533,11 +459,7 @@ __global__ __launch_bounds__(1 << RH) void k_ntt_high(PassParams p) {
             for (int k = 0; k < 16; k++) v[k] = lds[(g * 16 + k) * TW + t];
             radix_layers<4, true, true, 1>(v, ltab, 0, 0);                      // 4..1
 #pragma unroll
-            for (int k = 0; k < 16; k++) {
-                uint32_t x = mul_mod(v[k], tw[k]);
-                if (p.scale) x = mul_mod(x, p.scale);
-                TILE_OUT(g * 16 + k) = x;
-            }
+            for (int k = 0; k < 16; k++) TILE_OUT(g * 16 + k) = mul_mod(v[k], tw[k]);
         } else {
 #pragma unroll
             for (int k = 0; k < 16; k++) {
@@ -559,73 +481,75 @@ __global__ __launch_bounds__(1 << RH) void k_ntt_high(PassParams p) {
 #undef TILE_IN
 #undef TILE_OUT
 
-struct Pass { uint32_t L, R; };
-// Cut log_n index bits into HBM passes of <= 12 bits.  The lowest pass works on contiguous runs (cheapest), the
-// strided passes above it are kept <= 10 bits so a 2^R x 16-word tile stays <= 64 KiB.
-std::vector<Pass> plan_passes(uint32_t log_n) {
-    std::vector<Pass> v;
-    if (log_n <= 12) { v.push_back({0, log_n}); return v; }
-    if (log_n < 18) {                       // two balanced LDS passes
-        const uint32_t low = (log_n + 1) / 2;
-        v.push_back({0, low});
-        v.push_back({low, log_n - low});
-        return v;
+// Top pass, index bits [L, L + R) with L + R = log_n, L >= 12 and R in 1..4 — what is left above the register-radix passes at 2^21 and
+// 2^23 .. 2^26 (po2 19, 21 .. 24).  One lane = 4 consecutive low indices x ALL 2^R rows, in registers: rows are 2^L words apart, so every
+// load and store is a 16-byte piece of a contiguous run (the pass streams the columns once, at HBM speed), the R butterfly layers use
+// wave-uniform twiddles (w_{2^j}^low: scalar loads), and the four-step twiddle of row m at low index j is (w^j)^bitrev(m): ONE two-level
+// table root per lane, the neighbours and the powers by products.  Same arithmetic as k_ntt_pass on the same tile (canonical words in,
+// canonical words out): results are identical.  (round 5: the generic LDS kernel spent 8.8 ms per po2-21 seal here, 15.3 at po2 22.)
+template <int R, bool INVERSE>
+__global__ __launch_bounds__(256) void k_ntt_top(PassParams p) {
+    constexpr int N = 1 << R;
+    const uint32_t j0 = (blockIdx.x * 256u + threadIdx.x) << 2;             // first of this lane's 4 low indices, < 2^L
+    const uint32_t* in = p.in + (size_t)blockIdx.y * p.in_col_stride + j0;
+    uint32_t* out = p.out + (size_t)blockIdx.y * p.out_col_stride + j0;
+    const uint32_t tw_shift = MAX_LOG_N - p.log_n;
+    uint32_t v[4][N];                                                        // [low index][row]: one column of rows per radix_layers call
+#pragma unroll
+    for (int m = 0; m < N; m++) {
+        const uint4 w = *(const uint4*)(in + ((size_t)m << p.L));
+        v[0][m] = w.x; v[1][m] = w.y; v[2][m] = w.z; v[3][m] = w.w;
     }
-    // >= 2^18: the contiguous 4096-word register-radix pass, then strided passes.  2^8 and 2^10 rows have
-    // register-radix kernels; what is left over (1..4 bits at 2^21, 2^23 .. 2^26: po2 19, 21 .. 24) goes to a last streaming pass in
-    // registers (k_ntt_top) instead of a 9..12-layer LDS sweep.
-    const uint32_t rem = log_n - 12;
-    v.push_back({0, 12});
-    if (rem == 8 || rem == 10 || rem <= 7) v.push_back({12, rem});
-    else if (rem == 9) { v.push_back({12, 8}); v.push_back({20, 1}); }
-    else if (rem == 11 || rem == 12) { v.push_back({12, 8}); v.push_back({20, rem - 8}); }     // the top pass streams 1..4 bits at the same cost: the cheaper strided pass below it
-    else { v.push_back({12, 10}); v.push_back({22, rem - 10}); }
-    return v;
+    auto root = [&](uint32_t e) -> uint32_t {                                // w_{log_n}^e, e < 2^log_n
+        return two_level(p.tw_lo, p.tw_hi, e << tw_shift);
+    };
+    // v[c][m] *= (w^(j0 + c))^bitrev_R(m): forward before the layers (DIT pre-twiddle), inverse after them (DIF post-twiddle)
+    auto four_step = [&]() {
+        const uint32_t step = root(1u);                                      // (wave-uniform)
+        uint32_t g = root(j0);
+#pragma unroll
+        for (int c = 0; c < 4; c++) {
+            uint32_t pw[N];
+            pw[1] = g;
+#pragma unroll
+            for (int r = 2; r < N; r++) pw[r] = mul_mod(pw[r - 1], g);
+#pragma unroll
+            for (int m = 1; m < N; m++) {
+                const int r = (int)(__builtin_bitreverse32((uint32_t)m) >> (32 - R));
+                v[c][m] = mul_mod(v[c][m], pw[r]);
+            }
+            if (c < 3) g = mul_mod(g, step);
+        }
+    };
+    if (!INVERSE) four_step();
+#pragma unroll
+    for (int c = 0; c < 4; c++) radix_layers<R, INVERSE, true, 1>(v[c], p.layer_tw, 0, 0);      // layers 1..R (inverse: R..1), uniform twiddles
+    if (INVERSE) four_step();
+#pragma unroll
+    for (int m = 0; m < N; m++) *(uint4*)(out + ((size_t)m << p.L)) = make_uint4(v[0][m], v[1][m], v[2][m], v[3][m]);
 }
 
 const char* run_transform(zkh_ctx* c, bool inverse, const uint32_t* in, size_t in_col_stride, uint32_t* out,
                           size_t out_col_stride, uint32_t log_n, size_t count, uint32_t expand_bits, bool zk, const char* name) {
     ZKH_REQUIRE(log_n <= (uint32_t)MAX_LOG_N, "%s: transform size 2^%u exceeds the supported 2^%d", name, log_n, MAX_LOG_N);
     ZKH_REQUIRE(count <= 65535, "%s: too many columns (%zu)", name, count);
-    std::vector<Pass> passes = plan_passes(log_n);
+    const NttPlan plan = plan_transform(log_n, inverse, expand_bits, zk);            // every decision: ntt_plan.h
     const size_t n = (size_t)1 << log_n;
     Fp ninv = fp_inv(fp_encode((uint32_t)(n % P)));
-    const size_t npass = passes.size();
-    // forward transforms whose two passes are both register-radix kernels (2^20 and 2^22: what po2-18/20 seals
-    // expand into) run the lazy signed butterflies; the constant R^(layers run) rides on the four-step twiddle
-    // (letting the lazy pair also run under a third pass - 2^21 / 2^23 / 2^24 - is bit-exact and was measured flat twice; the
-    // per-shape twiddle matrix, 32-byte tiles and the column-fast grid were measured slower: profiles/README.md, r03_ntt_matrix.txt,
-    // r03_ntt_ab*.jsonl.  None of those variants is in the library any more.)
-    const bool lazy = !inverse && npass == 2 && passes[0].R == 12 && (passes[1].R == 8 || passes[1].R == 10) && expand_bits <= 4;
-    // reductions on a path: the low pass's rounds of 4 layers (the first without its expand_bits skipped ones), the strided
-    // pass's rounds of 4 + 4 (+ 2) layers, one per pair of layers and one per single layer
-    const uint32_t lazy_reds = lazy ? lazy_reductions(4, expand_bits) + 2 * lazy_reductions(4, 0) + lazy_reductions(passes[1].R, 0) : 0;
-    const uint32_t lazy_comp = lazy ? fp_pow(Fp::raw(R2), lazy_reds).v : 0;
-    for (size_t pi = 0; pi < npass; pi++) {
-        // inverse: high bits first; forward: low bits first
-        const Pass ps = inverse ? passes[npass - 1 - pi] : passes[pi];
+    const bool lazy = plan.lazy;
+    const uint32_t lazy_comp = lazy ? fp_pow(Fp::raw(R2), plan.lazy_reds).v : 0;
+    for (size_t pi = 0; pi < plan.passes.size(); pi++) {
+        const PassPlan& pp = plan.passes[pi];
         PassParams p{};
-        const bool first = pi == 0, last = pi + 1 == npass;
-        p.in = first ? in : out;
-        p.in_col_stride = first ? in_col_stride : out_col_stride;
+        p.in = pi == 0 ? in : out;
+        p.in_col_stride = pi == 0 ? in_col_stride : out_col_stride;
         p.out = out; p.out_col_stride = out_col_stride;
-        p.log_n = log_n; p.L = ps.L; p.R = ps.R;
-        // tile width: 16 words for the register-radix strided kernels; the generic kernel takes as wide a run as a
-        // 4096-element tile allows (a 1..3-bit top pass then moves 2..8 KiB contiguous runs)
-        const bool reg_high = ps.L >= 4 && (ps.R == 8 || ps.R == 10);
-        p.log_t = ps.L == 0 ? 0 : (ps.L < 4 ? ps.L : 4);
-        // the generic kernel on a strided pass: 4096-element tiles, i.e. runs of 2^(12 - R) consecutive words (a 1..3-bit top pass
-        // at 2^21 / 2^23 / 2^24 then streams 2..8 KiB runs; with 16-word runs it moved 64 elements per workgroup: 0.6 TB/s)
-        if (ps.L != 0 && !reg_high && ps.R < 12) p.log_t = std::max<uint32_t>(p.log_t, std::min<uint32_t>(ps.L, 12 - ps.R));
-        // keep the tile <= 64 KiB
-        while (p.R + p.log_t > 14 && p.log_t > 0) p.log_t--;
-        p.expand_bits = (!inverse && first) ? expand_bits : 0;
-        // the first pass skips the layers it owns; what expand_bits asks beyond them it accounts for in its load (k_ntt_pass: pad_mask)
-        p.first_layer = (!inverse && first) ? std::min(expand_bits, ps.R) + 1 : 1;
-        p.twiddle = ps.L != 0;
-        p.scale = (inverse && last) ? ninv.v : 0;
-        p.zk_shift = (inverse && last && zk) ? 1 : 0;
-        p.lazy = lazy; p.lazy_comp = lazy_comp;
+        p.log_n = log_n; p.L = pp.L; p.R = pp.R; p.log_t = pp.log_t;
+        p.expand_bits = pp.expand_bits; p.first_layer = pp.first_layer;
+        p.twiddle = pp.twiddle;
+        p.scale = pp.scale ? ninv.v : 0;
+        p.zk_shift = pp.zk_shift;
+        p.lazy_comp = lazy_comp;
         p.tile_tw = inverse ? c->tab.tile_rev : c->tab.tile_fwd;
         p.layer_tw = inverse ? c->tab.layer_rev : (lazy ? c->tab.layer_fwd_lazy : c->tab.layer_fwd);
         p.tw_lo = inverse ? c->tab.tw_rev_lo : c->tab.tw_fwd_lo;
@@ -636,47 +560,24 @@ const char* run_transform(zkh_ctx* c, bool inverse, const uint32_t* in, size_t i
             for (uint32_t k = 0; k < 16; k++)
                 p.shift16[k] = (ninv * fp_pow(three, (uint64_t)(bitrev32(k) >> 28) << (log_n - 4))).v;
         }
-        p.tiles_per_col = (uint32_t)(n >> (p.R + p.log_t));
-        const size_t lds = ((size_t)4 << (p.R + p.log_t));
-        dim3 grid(p.tiles_per_col, (unsigned)count);
+        p.tiles_per_col = pp.grid_x;
         // algorithmic bytes in SURVEY.md §8d's sense (operands read once + written once, whatever the number of HBM passes):
         // charged to the first pass, the other passes of the same transform add time only
         const double alg_bytes = pi == 0 ? 4.0 * count * (double)(((size_t)1 << log_n) >> expand_bits) + 4.0 * count * (double)n : 0.0;
-        const bool scale_here = p.scale != 0;
-        // profiler record = "<Hal op>:<kernel>", so both the op totals and the per-kernel (per-pass) times can be read off
-        const bool k_low = ps.L == 0 && ps.R == 12 && p.expand_bits <= 4;
-        const bool k_h10 = !k_low && ps.L >= 4 && p.log_t == 4 && ps.R == 10 && !(scale_here && p.zk_shift);
-        const bool k_h8 = !k_low && !k_h10 && ps.L >= 4 && p.log_t == 4 && ps.R == 8 && !(scale_here && p.zk_shift);
-        const bool k_top = !k_low && !k_h10 && !k_h8 && ps.L >= 12 && ps.L + ps.R == log_n && ps.R >= 1 && ps.R <= 4 && p.twiddle &&
-                           p.expand_bits == 0 && p.first_layer == 1 && !scale_here && !p.zk_shift;
-        const std::string pname = std::string(name) + (k_low ? ":k_ntt_low12" : k_h10 ? ":k_ntt_high10" : k_h8 ? ":k_ntt_high8" : k_top ? ":k_ntt_top" : ":k_ntt_pass");
-        ProfScope prof(c, pname.c_str(), alg_bytes);
-        if (ps.L == 0 && ps.R == 12 && p.expand_bits <= 4) {
-            if (inverse) k_ntt_low12<true><<<grid, 256, 0, c->stream>>>(p);
-            else if (lazy) k_ntt_low12<false, true><<<grid, 256, 0, c->stream>>>(p);
-            else k_ntt_low12<false><<<grid, 256, 0, c->stream>>>(p);
-        } else if (ps.L >= 4 && p.log_t == 4 && ps.R == 10 && !(scale_here && p.zk_shift)) {
-            if (inverse) k_ntt_high<10, true><<<grid, 1024, lds, c->stream>>>(p);
-            else if (lazy) k_ntt_high<10, false, true><<<grid, 1024, lds, c->stream>>>(p);
-            else k_ntt_high<10, false><<<grid, 1024, lds, c->stream>>>(p);
-        } else if (ps.L >= 4 && p.log_t == 4 && ps.R == 8 && !(scale_here && p.zk_shift)) {
-            if (inverse) k_ntt_high<8, true><<<grid, 256, lds, c->stream>>>(p);
-            else if (lazy) k_ntt_high<8, false, true><<<grid, 256, lds, c->stream>>>(p);
-            else k_ntt_high<8, false><<<grid, 256, lds, c->stream>>>(p);
-        } else if (k_top) {
-            const dim3 tg((unsigned)(((size_t)1 << ps.L) >> 10), (unsigned)count);          // 256 lanes x 4 low indices per workgroup
-            switch (ps.R * 2 + (inverse ? 1 : 0)) {
-            case 2: k_ntt_top<1, false><<<tg, 256, 0, c->stream>>>(p); break;
-            case 3: k_ntt_top<1, true><<<tg, 256, 0, c->stream>>>(p); break;
-            case 4: k_ntt_top<2, false><<<tg, 256, 0, c->stream>>>(p); break;
-            case 5: k_ntt_top<2, true><<<tg, 256, 0, c->stream>>>(p); break;
-            case 6: k_ntt_top<3, false><<<tg, 256, 0, c->stream>>>(p); break;
-            case 7: k_ntt_top<3, true><<<tg, 256, 0, c->stream>>>(p); break;
-            case 8: k_ntt_top<4, false><<<tg, 256, 0, c->stream>>>(p); break;
-            default: k_ntt_top<4, true><<<tg, 256, 0, c->stream>>>(p); break;
-            }
-        } else if (inverse) k_ntt_pass<true><<<grid, NTT_THREADS, lds, c->stream>>>(p);
-        else k_ntt_pass<false><<<grid, NTT_THREADS, lds, c->stream>>>(p);
+        ProfScope prof(c, (std::string(name) + NTT_KERNEL_SCOPE[(int)pp.kernel]).c_str(), alg_bytes);
+        void (*kernel)(PassParams) = nullptr;
+        switch (pp.kernel) {
+        case NttKernel::pass: kernel = inverse ? k_ntt_pass<true> : k_ntt_pass<false>; break;
+        case NttKernel::low12: kernel = inverse ? k_ntt_low12<true> : lazy ? k_ntt_low12<false, true> : k_ntt_low12<false>; break;
+        case NttKernel::high8: kernel = inverse ? k_ntt_high<8, true> : lazy ? k_ntt_high<8, false, true> : k_ntt_high<8, false>; break;
+        case NttKernel::high10: kernel = inverse ? k_ntt_high<10, true> : lazy ? k_ntt_high<10, false, true> : k_ntt_high<10, false>; break;
+        case NttKernel::top:
+            kernel = pp.R == 1 ? (inverse ? k_ntt_top<1, true> : k_ntt_top<1, false>)
+                   : pp.R == 3 ? (inverse ? k_ntt_top<3, true> : k_ntt_top<3, false>)
+                               : (inverse ? k_ntt_top<4, true> : k_ntt_top<4, false>);
+            break;
+        }
+        kernel<<<dim3(pp.grid_x, (unsigned)count), pp.block, pp.lds_bytes, c->stream>>>(p);
         ZKH_TRY(last_launch_error(name));
     }
     return nullptr;
