@@ -383,9 +383,29 @@ const char* zkh_derive_links(zkh_ctx*, const zkh_circuit*, size_t po2, size_t zk
  * a host-made table that repeats an address is refused, not resolved).  It is a call of its own so that a refused or aborted seal never
  * touches the image.  The prover can commit to the image, prove a page-out between two roots and seal that step (below: P2-PAGE); a
  * tied group (P2-PAGE-tied, P2-TREE-tied: zkh_accumulate_open, zkh_tie_challenge) ties p_in / p_out of a paging segment's OWN seal to
- * that commitment over one shared bus, so the verifier of the group learns which image (THE TIE). */
+ * that commitment over one shared bus, so the verifier of the group learns which image (THE TIE).
+ * PAGING IN FROM A PAGE TABLE (zkh_derive_links_paged_table, zkh_derive_all_paged_table): a rank that does not hold the image derives the
+ * same witness from the page table a ZKU1 proof ships.  The words of `table` from `table_at` on are D rows of 3 words (a_i, in_i, out_i),
+ * as zkh_table_fingerprint and zkh_page_tree_plan_device take them (for a proof table_at = 5 + h), over an image of image_words words; the
+ * table stands for the image: image[a_i] is the raw word table[3 i + 1].  Only an unlinked access of the paged record uses the image's word
+ * (the read rule of a first load, prev_1 of a first access, p_in of its page), and it knows its page i from the page scan: one indexed read
+ * and one address comparison per first access, no search, no W-word buffer.  EQUIVALENCE: for every (code, data, image) that
+ * zkh_derive_links_paged accepts, the table (a_i, image[a_i] % P, anything) of its own page table makes this call leave `data` equal to the
+ * image variant's, cell for cell as residues, and word for word when every image word it read is below P; after zkh_reduce_elem the two
+ * traces are the same bytes.  REFUSALS: the image variant's, with the same text and precedence (`image_words` in W's place; "the image holds
+ * .. at its address" for a first load the table contradicts), and three of its own, reported under the PAGES record's index R, the first two
+ * tested on a row after "outside the image" and before the clock:
+ *   "derive_links: record R at row r: address A is page I of the trace, but row I of the page table holds address B: the witness is refused"
+ *   "derive_links: record R at row r: address A is page I of the trace, but the page table has D rows: the witness is refused"
+ *   and, when no row is refused, "derive_links: record R: the trace pages D' addresses, but the page table has D rows: the witness is refused".
+ * Before any launch: "a table of D rows of 3 words at word T does not fit a buffer of N words"; "an image of W words (1 .. 2^32 - 1)".  A
+ * refusal leaves `data` unchanged; `table` and `code` are only read, rows [A, n) never touched; for a message the host reads single words of
+ * the table, never the table.  Without a PAGES record the table is ignored (NULL or not) and the call is the plain one; with one, a NULL
+ * table is refused ("a page table is required"). */
 int zkh_circuit_pages(const zkh_circuit*);
 const char* zkh_derive_links_paged(zkh_ctx*, const zkh_circuit*, size_t po2, size_t zk_cycles, const zkh_buf* code, zkh_buf* data, const zkh_buf* image);
+const char* zkh_derive_links_paged_table(zkh_ctx*, const zkh_circuit*, size_t po2, size_t zk_cycles, const zkh_buf* code, zkh_buf* data, const zkh_buf* table,
+                                         size_t table_at, size_t D, size_t image_words);
 const char* zkh_page_out(zkh_ctx*, const zkh_circuit*, size_t po2, size_t zk_cycles, const zkh_buf* data, zkh_buf* image);
 /* THE IMAGE'S COMMITMENT: a Merkle root that the prover keeps current from segment to segment.  An image is W >= 1 raw Montgomery words,
  * W <= 2^32 - 1, as zkh_page_out takes it.  The commitment is a function of the RESIDUES, not of the raw words: image[a] and
@@ -619,6 +639,10 @@ const char* zkh_derive_all(zkh_ctx*, const zkh_circuit*, size_t po2, size_t zk_c
 /* ... and the same with the memory image that the links stage of a paging circuit reads (zkh_derive_links_paged); zkh_derive_all is this
  * call with no image.  A paging circuit without an image is refused before any stage has written. */
 const char* zkh_derive_all_paged(zkh_ctx*, const zkh_circuit*, size_t po2, size_t zk_cycles, const zkh_buf* code, zkh_buf* data, const zkh_buf* image);
+/* ... and with the page table of a ZKU1 proof in the image's place (zkh_derive_links_paged_table, PAGING above): the links stage gets the
+ * table where zkh_derive_all_paged hands it the image; every other stage is the same. */
+const char* zkh_derive_all_paged_table(zkh_ctx*, const zkh_circuit*, size_t po2, size_t zk_cycles, const zkh_buf* code, zkh_buf* data, const zkh_buf* table,
+                                       size_t table_at, size_t D, size_t image_words);
 /* The data columns that zkh_derive_sorted, zkh_derive_columns, zkh_derive_links and zkh_derive_multiplicities write on the active rows: their sorted
  * union in cols[0 .. *n) (cap = room in cols; *n is set even when the call fails for lack of room).
  * zkh_upload_data_trace copies a caller's data trace (`host`, W_data x 2^po2 words) into `data` without what the library derives:

@@ -406,6 +406,23 @@ impl HipCircuitHal {
         ffi(|| unsafe { sys::zkh_derive_all_paged(self.hal.ctx.0, self.circuit, po2, sys::ZK_CYCLES, ctrl.raw, data.raw, image.raw) });
     }
 
+    /// `derive_links_paged` from the page table of a ZKU1 proof in the image's place (`zkh_derive_links_paged_table`): the words of
+    /// `table` from `table_at` on are `rows` rows (address, in, out) over an image of `image_words` words (for a proof `table_at = 5 + h`),
+    /// and row i's `in` stands for `image[a_i]`.  The result is `derive_links_paged`'s on the image the table was made from, cell for
+    /// cell as residues.  Panics as `derive_links_paged` does, and when the table's rows are not the trace's pages; `data` is then unchanged.
+    pub fn derive_links_paged_table(&self, ctrl: &HipBuffer<BabyBearElem>, data: &HipBuffer<BabyBearElem>, table: &HipBuffer<u32>, table_at: usize, rows: usize,
+                                    image_words: usize, steps: usize) {
+        let po2 = steps.trailing_zeros() as usize;
+        ffi(|| unsafe { sys::zkh_derive_links_paged_table(self.hal.ctx.0, self.circuit, po2, sys::ZK_CYCLES, ctrl.raw, data.raw, table.raw, table_at, rows, image_words) });
+    }
+
+    /// `derive_all_paged` with that page table where the links stage gets the image (`zkh_derive_all_paged_table`).
+    pub fn derive_all_paged_table(&self, ctrl: &HipBuffer<BabyBearElem>, data: &HipBuffer<BabyBearElem>, table: &HipBuffer<u32>, table_at: usize, rows: usize,
+                                  image_words: usize, steps: usize) {
+        let po2 = steps.trailing_zeros() as usize;
+        ffi(|| unsafe { sys::zkh_derive_all_paged_table(self.hal.ctx.0, self.circuit, po2, sys::ZK_CYCLES, ctrl.raw, data.raw, table.raw, table_at, rows, image_words) });
+    }
+
     /// Write the page table of `data` back into `image` (`zkh_page_out`): `image[p_addr] = p_out` on every active row with `p_on` = 1.
     /// A call of its own, after the seal, so that a refused or aborted seal never touches the image.  Panics, with the image unchanged,
     /// on a `p_on` other than 0 / 1, an address outside the image, or page addresses that do not strictly increase over a prefix of rows.

@@ -29,7 +29,9 @@ group under P2-TREE-tied next to P2-PAGE-tied's on the same table; M29: P2-TREE 
 zkh_image_proof_walk and part 0's witness from the dirty nodes next to part 0's witness from the two trees on M24's table, alternating, with
 the words of the table, of the proof and of the two trees, and the copy of the tree that keep_before makes; M30: held commitments, a
 whole tied group on M28's setup sealed in two passes next to the same group with hold_bytes for everything, alternating, and for one
-part zkh_commit_data + zkh_prove_begin_held next to zkh_data_root + zkh_prove_begin, with the bytes held) on one MI355X, through the C ABI (HipHal).
+part zkh_commit_data + zkh_prove_begin_held next to zkh_data_root + zkh_prove_begin, with the bytes held; M31: paging in from a page
+table, zkh_derive_links_paged_table next to zkh_derive_links_paged on the same SYN-LOOKUP-paged FULL trace at two image sizes, alternating,
+with both calls' passes) on one MI355X, through the C ABI (HipHal).
 
 Each line of output is one JSON object: the op, its shape, the average wall time of one call (stream drained on both
 sides of `reps` back-to-back calls), its ALGORITHMIC bytes (SURVEY.md §8a "B_alg": inputs read once + outputs written
@@ -1662,6 +1664,61 @@ def main() -> None:
                           "group_held_over_two_passes": round(med["group_held"] / med["group_two_passes"], 4),
                           "part_held_over_two_passes": round(med["part_commit_data_then_prove_begin_held"] / med["part_data_root_then_prove_begin"], 4)}), flush=True)
         del scode, sdata, code, data, before, after, proof
+    if want("M31"):
+        # Paging in from a page table (zkh_derive_links_paged_table: the rows (a_i, in_i, out_i) of the proof's table in the image's
+        # place) next to its yardstick in the same run, zkh_derive_links_paged on the same trace with the image itself, for an image of
+        # 2^20 and of 2^26 words with the addresses drawn over the whole image.  SYN-LOOKUP-paged FULL; the table is read off the image
+        # variant's own output and lies where a proof would hold it (after 5 + h header words).  Timed in alternation, `runs` windows of
+        # `reps` calls; median and spread (min, max) of the windows; then the passes by their events.  No threshold.
+        from zeth_amd.circuits import logup, p2_page, syn_lookup
+        runs, zk = 7, 1994
+        A = n - zk
+        shape = syn_lookup.FULL
+        desc, blob = syn_lookup.build_syn_lookup(shape, link=True, reads=True, pages=True)
+        pargs = logup.Arguments.parse(blob)
+        spread = lambda ts: {"median_ms": round(float(np.median(ts)) * 1e3, 4), "min_ms": round(min(ts) * 1e3, 4), "max_ms": round(max(ts) * 1e3, 4)}   # noqa: E731
+        for W in (1 << 20, 1 << 26):
+            image_h = np.random.default_rng(31).integers(1, P, W, dtype=np.uint64).astype(np.uint32)
+            code_h, full_h, _out = syn_lookup.witness(shape, args.po2, zk, seed=17, addr_range=W, link=True, reads=True, pages=True, image=image_h)
+            paged = hal.load_circuit(desc, jit=False)
+            paged.set_arguments(blob)
+            full = full_h.reshape(-1, n)
+            on = full[pargs.pages.p_on, :A] != 0
+            D, at = int(on.sum()), 5 + p2_page.tree_height(W)
+            rows = np.stack([logup._dec(full[pargs.pages.p_addr, :A][on]).astype(np.uint32), full[pargs.pages.p_in, :A][on] % P, full[pargs.pages.p_out, :A][on] % P], axis=1)
+            bare_h = full.copy()
+            bare_h[paged.derived_data_columns(), :A] = 0
+            code, data_i, data_t, image = (hal.alloc_elem(nm, sz) for nm, sz in (("code", code_h.size), ("data_i", bare_h.size), ("data_t", bare_h.size), ("image", W)))
+            table = hal.copy_from("m31t", np.concatenate([np.zeros(at, dtype=np.uint32), rows.reshape(-1).astype(np.uint32)]))
+            code.write(code_h)
+            data_i.write(bare_h.reshape(-1))
+            data_t.write(bare_h.reshape(-1))
+            image.write(image_h)
+            image_fn = lambda: hal.derive_links_paged(paged, args.po2, zk, code, data_i, image)                              # noqa: E731
+            table_fn = lambda: hal.derive_links_paged_table(paged, args.po2, zk, code, data_t, table, W, table_at=at, D=D)    # noqa: E731
+            image_fn()
+            table_fn()
+            assert np.array_equal(data_i.to_vec(), full_h) and np.array_equal(data_t.to_vec() % P, full_h % P), "the table variant's trace differs"
+            fns = (("derive_links_paged", image_fn), ("derive_links_paged_table", table_fn))
+            t = {name: [] for name, _ in fns}
+            for _ in range(runs):
+                for name, fn in fns:
+                    t[name].append(timed(hal, fn, args.reps))
+            steps = {}
+            for name, fn in fns:
+                hal.prof_enable(True)
+                hal.prof_reset()
+                for _ in range(args.reps):
+                    fn()
+                hal.sync()
+                steps[name] = {r["name"]: round(r["total_ms"] / max(r["calls"], 1), 4) for r in hal.prof_get()
+                               if r["calls"] and r["name"].startswith(("sort_", "links_", "pages_"))}
+                hal.prof_enable(False)
+            med = {k: float(np.median(v)) for k, v in t.items()}
+            print(json.dumps({"bench": "M31", "circuit": "SYN-LOOKUP-paged FULL", "po2": args.po2, "accesses": A, "pages": D, "image_words": W, "table_words": 3 * D,
+                              "runs": runs, "reps": args.reps, **{k: spread(v) for k, v in t.items()}, "steps_ms": steps,
+                              "table_vs_image": round(med["derive_links_paged_table"] / med["derive_links_paged"], 3)}), flush=True)
+            del code, data_i, data_t, image, table, image_h, code_h, full_h, bare_h
     hal.close()
 
 

@@ -1394,7 +1394,7 @@ def _link_chain(key, rows):
 PAGES_NEED_IMAGE = "the arguments page memory: an image is required (zkh_derive_all_paged)"
 
 
-def reference_links(args: Arguments, po2: int, zk_cycles: int, code, data, image=None) -> np.ndarray:
+def reference_links(args: Arguments, po2: int, zk_cycles: int, code, data, image=None, table=None, image_words=None) -> np.ndarray:
     """The data trace zkh_derive_links leaves (raw Montgomery words, a copy): every LINK record's destination columns on the active rows
     (module docstring), rows [A, n) as given.  Raises ReferenceError on a selector other than 0 / 1 (the lowest (record, row) over all
     records, before any clock is looked at), then on the lowest (record, row) whose clock difference d = c_0 - prev_0 - 1 is negative
@@ -1404,18 +1404,32 @@ def reference_links(args: Arguments, po2: int, zk_cycles: int, code, data, image
     zkh_derive_links_paged).  The paged LINK record then takes, for an unlinked access to address a (the canonical value of its key),
     the image as the previous access — prev_1 = the raw word image[a], prev_0 = 0, the limbs those of d = clock - 0 - 1 — refuses an
     address >= W, a clock 0 ("clock 0 is the image's") and an unlinked load whose residue is not image[a]'s (on one row: write flag,
-    address, clock, read rule), and the PAGES record's destinations get the page table (module docstring, PAGING)."""
+    address, clock, read rule), and the PAGES record's destinations get the page table (module docstring, PAGING).
+    table, image_words: the page table of a ZKU1 proof in the image's place (zkh_derive_links_paged_table): D rows (a_i, in_i, out_i) over
+    an image of image_words words, exactly one of `image` / `table` being given.  The table stands for the image: with a_0 < a_1 < .. the
+    distinct addresses of the paged record's accesses, an unlinked access to its address number I (page I of the trace) takes in_I where
+    it took image[a].  The results and the messages are the image's (image_words in W's place), and three refusals are the table's own,
+    under the PAGES record's index R: on a row, after the address and before the clock, "address A is page I of the trace, but the page
+    table has D rows" and "... but row I of the page table holds address B"; and, when no row is refused, "record R: the trace pages D'
+    addresses, but the page table has D rows"."""
     n = 1 << po2
     A = n - zk_cycles
     groups = {GROUP_CODE: np.asarray(code, dtype=np.uint32).reshape(-1, n), GROUP_DATA: np.array(data, dtype=np.uint32).reshape(-1, n)}
     out = groups[GROUP_DATA]                                                 # sources are never destinations
     links = [(i, r) for i, r in enumerate(args.records) if isinstance(r, Link)]
     pages = args.pages
-    if pages is not None and image is None:
+    if image is not None and table is not None:
+        raise ValueError("reference_links: exactly one of image / table")
+    if pages is not None and image is None and table is None:
         raise ReferenceError(PAGES_NEED_IMAGE)
-    if pages is not None:
+    if pages is not None and table is None:
         image = np.asarray(image, dtype=np.uint32).reshape(-1)
         W = image.size
+    elif pages is not None:
+        if image_words is None or not 1 <= image_words <= 0xffffffff:
+            raise ReferenceError(f"an image of {image_words} words (1 .. 2^32 - 1)")
+        table = np.asarray(table, dtype=np.uint32).reshape(-1, 3)
+        W, R, short = image_words, args.records.index(pages), None
     on = {}
     for i, r in links:
         sel = np.ones(A, dtype=np.uint64) if r.sel is None else _dec(groups[GROUP_CODE][r.sel, :A])
@@ -1438,8 +1452,17 @@ def reference_links(args: Arguments, po2: int, zk_cycles: int, code, data, image
         bad = (d < 0) | (d >> (L * nl) != 0)
         if paged:
             outside = addr >= W
-            word = image[np.where(outside, 0, addr)] if W else np.zeros(rows.size, dtype=np.uint32)      # the image's word of an unlinked access
-            bad = bad | outside
+            if table is None:
+                word = image[np.where(outside, 0, addr)] if W else np.zeros(rows.size, dtype=np.uint32)      # the image's word of an unlinked access
+                unlisted = np.zeros(rows.size, dtype=bool)
+            else:                                                            # ... by its page: the number of its address among the trace's
+                page = np.searchsorted(np.unique(addr), addr)
+                row_of = np.minimum(page, max(len(table) - 1, 0))
+                listed = (page < len(table)) & (table[row_of, 0] == addr if len(table) else False)
+                word = np.where(page < len(table), table[row_of, 1] if len(table) else 0, 0).astype(np.uint32)
+                unlisted = ~linked & ~outside & ~listed
+                short = (np.unique(addr).size, len(table))
+            bad = bad | outside | unlisted
         if r.write is not None:
             w = _dec(groups[r.write[0]][r.write[1], rows])
             now = [_dec(groups[g][c, rows]) for g, c in r.carried]
@@ -1453,6 +1476,10 @@ def reference_links(args: Arguments, po2: int, zk_cycles: int, code, data, image
                 raise ReferenceError(f"{at}: write flag {int(w[j])}, not 0 or 1")
             if paged and outside[j]:
                 raise ReferenceError(f"{at}: address {int(addr[j])} outside the image of {W} words")
+            if paged and unlisted[j]:
+                page_at = f"record {R} at row {int(rows[j])}: address {int(addr[j])} is page {int(page[j])} of the trace, but "
+                raise ReferenceError(page_at + (f"the page table has {len(table)} rows" if page[j] >= len(table) else
+                                                f"row {int(page[j])} of the page table holds address {int(table[page[j], 0])}"))
             if paged and not linked[j] and clock[j] == 0:
                 raise ReferenceError(f"{at}: clock 0 is the image's")
             if r.write is not None and d[j] >= 0 and d[j] >> (L * nl) == 0:
@@ -1486,7 +1513,7 @@ def reference_links(args: Arguments, po2: int, zk_cycles: int, code, data, image
             writes.append((list(pages.dsts), slice(0, A), 0))
             writes.append((pages.p_on, top, np.uint32(_R)))
             writes.append((pages.p_addr, top, groups[r.key[0]][r.key[1], first]))
-            writes.append((pages.p_in, top, image[a]))
+            writes.append((pages.p_in, top, image[a] if table is None else table[:D, 1]))
             writes.append((pages.p_out, top, groups[r.carried[1][0]][r.carried[1][1], final]))
             writes.append((pages.p_time, top, groups[g0][c0, final]))
             for j in range(ng):
@@ -1494,6 +1521,8 @@ def reference_links(args: Arguments, po2: int, zk_cycles: int, code, data, image
                 writes.append((pages.gaps[j], top, _enc((gap >> (j * Lp)) & ((1 << Lp) - 1)).astype(np.uint32)))
     if late:
         raise ReferenceError(late)
+    if pages is not None and table is not None and short is not None and short[0] != short[1]:
+        raise ReferenceError(f"record {R}: the trace pages {short[0]} addresses, but the page table has {short[1]} rows")
     for cols, rows, words in writes:
         out[cols, rows] = words
     return out.reshape(-1)

@@ -1,7 +1,7 @@
 // arguments.h — lookup and permutation arguments as data (ZKA1 blob; zeth_amd/circuits/logup.py; DESIGN.md §2 ARGUMENTS): the decoded
 // form every consumer reads, and what the consumers share.  arguments.hip owns the blob format and the rules a blob must keep;
 // accumulate.hip (zkh_accumulate), multiplicities.hip (zkh_derive_multiplicities), sort.hip (zkh_derive_sorted), columns.hip
-// (zkh_derive_columns), links.hip (zkh_derive_links, zkh_derive_links_paged) and page_out.hip (zkh_page_out, zkh_page_out_tree,
+// (zkh_derive_columns), links.hip (zkh_derive_links, zkh_derive_links_paged, zkh_derive_links_paged_table) and page_out.hip (zkh_page_out, zkh_page_out_tree,
 // zkh_page_out_proof) read zkh_circuit::args and never see a blob word.
 //
 // WHO WRITES A DATA COLUMN (the module docstring of logup.py says the same; check_owned in arguments.hip keeps it).  A data column has at
@@ -124,6 +124,17 @@ inline uint32_t entry_words(const Term& t) { return t.w + (t.sel != NONE) + (t.m
 // circuit's widths at 2^po2 rows.  `who` prefixes the messages.  *n = rows, *A = active rows.
 const char* trace_rows(const char* who, const zkh_circuit* c, size_t po2, size_t zk_cycles, const zkh_buf* code, const zkh_buf* data,
                        const zkh_buf* accum, size_t* n, uint32_t* A);
+
+// Where the links stage of a paging circuit takes the memory image from: the image's W words (zkh_derive_links_paged), or the rows (address,
+// in, out) of a ZKU1 page table from word table_at of `table`, D rows over an image of image_words words (zkh_derive_links_paged_table); both
+// NULL: no image, and a circuit with a PAGES record is refused.  Without a PAGES record none of it is looked at.
+struct PagedFrom {
+    const zkh_buf* image = nullptr;
+    const zkh_buf* table = nullptr;
+    size_t table_at = 0, D = 0, image_words = 0;
+};
+// the links stage (links.hip): what zkh_derive_links and its paged variants call, and the stage table of arguments.hip
+const char* derive_links_from(zkh_ctx* ctx, const zkh_circuit* c, size_t po2, size_t zk_cycles, const zkh_buf* code, zkh_buf* data, const PagedFrom& mem);
 
 // the canonical value of a raw trace word (raw words >= P are legal)
 __host__ __device__ __forceinline__ uint32_t canonical(uint32_t raw) { return fp_decode(Fp::raw(raw % P)); }

@@ -499,28 +499,39 @@ extern "C" int zkh_circuit_open_bus(const zkh_circuit* c, uint32_t where[4]) {
 // THE DERIVE STAGES, IN THEIR ORDER (arguments.h, WHO WRITES A DATA COLUMN): the one statement of the order in code.  A LIMBS / ORDER
 // record may read a sorted copy's column, and the multiplicities count the limbs that the records and the links derive.
 namespace {
-using Derive = const char* (*)(zkh_ctx*, const zkh_circuit*, size_t, size_t, const zkh_buf*, zkh_buf*, const zkh_buf*);
+using Derive = const char* (*)(zkh_ctx*, const zkh_circuit*, size_t, size_t, const zkh_buf*, zkh_buf*, const PagedFrom&);
 template <const char* (*F)(zkh_ctx*, const zkh_circuit*, size_t, size_t, const zkh_buf*, zkh_buf*)>
-const char* no_image(zkh_ctx* ctx, const zkh_circuit* c, size_t po2, size_t zk_cycles, const zkh_buf* code, zkh_buf* data, const zkh_buf*) {
+const char* no_image(zkh_ctx* ctx, const zkh_circuit* c, size_t po2, size_t zk_cycles, const zkh_buf* code, zkh_buf* data, const PagedFrom&) {
     return F(ctx, c, po2, zk_cycles, code, data);
 }
 const struct { const char* name; int (*derives)(const zkh_circuit*); Derive derive; } STAGES[] = {
     {"sorted", zkh_circuit_derives_sorted, no_image<zkh_derive_sorted>},
     {"columns", zkh_circuit_derives_columns, no_image<zkh_derive_columns>},
-    {"links", zkh_circuit_derives_links, zkh_derive_links_paged},           // the one stage that reads the memory image (a PAGES record)
+    {"links", zkh_circuit_derives_links, derive_links_from},                // the one stage that reads the memory image (a PAGES record), as words or as a page table
     {"multiplicities", zkh_circuit_derives_multiplicities, no_image<zkh_derive_multiplicities>},
 };
 }  // namespace
 
 // every stage the circuit's arguments have, with the arguments as given: the stage's own checks and messages are the call's.  A circuit
-// whose arguments page memory is refused without an image before any stage writes.
+// whose arguments page memory is refused without an image, or a page table in its place, before any stage writes.
+static const char* derive_all_from(zkh_ctx* ctx, const zkh_circuit* c, size_t po2, size_t zk_cycles, const zkh_buf* code, zkh_buf* data, const PagedFrom& mem) {
+    ZKH_REQUIRE(c, "derive_all: null circuit");
+    ZKH_REQUIRE(mem.image || mem.table || !zkh_circuit_pages(c), "derive_all: the arguments page memory: an image is required (zkh_derive_all_paged)");
+    for (const auto& s : STAGES)
+        if (s.derives(c)) ZKH_TRY(s.derive(ctx, c, po2, zk_cycles, code, data, mem));
+    return nullptr;
+}
+
 extern "C" const char* zkh_derive_all_paged(zkh_ctx* ctx, const zkh_circuit* c, size_t po2, size_t zk_cycles, const zkh_buf* code, zkh_buf* data,
                                             const zkh_buf* image) {
+    return derive_all_from(ctx, c, po2, zk_cycles, code, data, PagedFrom{image});
+}
+
+extern "C" const char* zkh_derive_all_paged_table(zkh_ctx* ctx, const zkh_circuit* c, size_t po2, size_t zk_cycles, const zkh_buf* code, zkh_buf* data,
+                                                  const zkh_buf* table, size_t table_at, size_t D, size_t image_words) {
     ZKH_REQUIRE(c, "derive_all: null circuit");
-    ZKH_REQUIRE(image || !zkh_circuit_pages(c), "derive_all: the arguments page memory: an image is required (zkh_derive_all_paged)");
-    for (const auto& s : STAGES)
-        if (s.derives(c)) ZKH_TRY(s.derive(ctx, c, po2, zk_cycles, code, data, image));
-    return nullptr;
+    ZKH_REQUIRE(table || !zkh_circuit_pages(c), "derive_all: the arguments page memory: a page table is required (zkh_derive_all_paged_table)");
+    return derive_all_from(ctx, c, po2, zk_cycles, code, data, PagedFrom{nullptr, table, table_at, D, image_words});
 }
 
 extern "C" const char* zkh_derive_all(zkh_ctx* ctx, const zkh_circuit* c, size_t po2, size_t zk_cycles, const zkh_buf* code, zkh_buf* data) {

@@ -47,6 +47,19 @@
 // the new refusals to the same wave minimum and the same atomicMin; the paged write pass also fills the table — head lanes p_on, p_addr,
 // p_in, alimb and gap (the previous address re-read from the trace at rows[t - 1]: packed keys drop bits and are no addresses), tail lanes
 // p_out and p_time, lanes D <= t < A zeros (coalesced).  No atomic but that min: the result is a function of the traces and the image.
+//
+// PAGING FROM A PAGE TABLE (zkh_derive_links_paged_table; `reference_links(..., table=, image_words=)`): the image's words reach the derive as
+// the rows (a_i, in_i, out_i) of a ZKU1 table, where it lies in a device buffer (rows of 3 words from word `table_at`; a_i an integer, in_i
+// the raw word that stands for image[a_i]), in place of the W words.  Only an unlinked access of the paged record uses the image's word, and
+// it is a head: the page scan has run before the check pass, so head_rank gives its page i, and image[a] is table[3 i + 1] once table[3 i]
+// is a: one indexed read and one comparison per head, no search, no W-word buffer.  This is the third mode of k_links' paging parameter
+// (PAGED_TABLE); the plain and the image passes are the instantiations they were.  Three refusals are its own, under the PAGES record's index:
+// a head whose page the table does not have ("the page table has D rows"), a head whose row of the table holds another address, both
+// tested on the row after "outside the image" and before the clock; and, when no row is refused, a table of more rows than the trace pages,
+// which the host reads off the scan's total (it comes back in the check pass's one read-back).  The table is only read.
+#include <algorithm>
+#include <functional>
+
 #include "scan.h"
 #include "sort.h"
 
@@ -60,11 +73,13 @@ constexpr uint32_t LINK_THREADS = 256;
 constexpr uint32_t PG_TOTAL = 0;                        // word 0 of the carry buffer: D, the pages; the workgroups' carries follow from word 1
 
 // what the paged passes of k_links read on top of the plain ones'; the plain passes get a zeroed one and read none of it
+enum : int { PAGED_NO = 0, PAGED_IMAGE = 1, PAGED_TABLE = 2 };      // k_links' kPaged: no PAGES record; the image as W words; the image as a page table
 struct Paging {
     const Pages* pg;                                    // the PAGES record
     uint32_t paged;                                     // the place among the LINK records of the record it pages
-    const uint32_t* image;
+    const uint32_t* image;                              // PAGED_TABLE: the table's rows of 3 words (address, in, out)
     uint32_t W;                                         // the image's words
+    uint32_t rows;                                      // PAGED_TABLE: the table's rows
     const uint32_t *local, *sums;                       // the page scan: k_page_heads' local indices; D and the workgroups' carries
 };
 
@@ -84,16 +99,17 @@ __global__ __launch_bounds__(LINK_THREADS) void k_page_heads(const uint32_t* __r
 // pass over a witness that passed.  kReads: the check pass of a blob in which a record has READS; the flag is uniform per record, so the
 // branch is scalar, and which rule a row broke the host finds out by reading its few cells back.  kPaged: the blob has a PAGES record, and
 // `pages` says whether blockIdx.y is the record it pages (uniform: a scalar branch); without kPaged `pages` is the constant false, `word`
-// the constant 0, and nothing of `pa` is read.  The record's words are read through the uniform pointer (scalar loads): nothing is indexed
+// the constant 0, and nothing of `pa` is read.  kPaged = PAGED_TABLE: the image's word of a head is its row's of the page table, and a head that the
+// table does not list is refused.  The record's words are read through the uniform pointer (scalar loads): nothing is indexed
 // in registers.
-template <bool kWrite, bool kReads, bool kPaged>
+template <bool kWrite, bool kReads, int kPaged>
 __global__ __launch_bounds__(LINK_THREADS) void k_links(const uint32_t* __restrict__ code, uint32_t* data, const Link* __restrict__ links,
                                                         const uint32_t* __restrict__ status, const unsigned long long* __restrict__ keys,
                                                         const uint32_t* __restrict__ rows, uint32_t n, uint32_t A, unsigned long long* __restrict__ bad,
                                                         const Paging pa) {
     const uint32_t p = blockIdx.y;
     const Link* __restrict__ rec = links + p;
-    const bool pages = kPaged && p == pa.paged;
+    const bool pages = kPaged != PAGED_NO && p == pa.paged;
     const uint32_t m = status[ST_HEAD + ST_WORDS * p + ST_M];                 // the record's accesses: m <= A
     const uint32_t t = blockIdx.x * LINK_THREADS + threadIdx.x;             // a sorted position (t < m) and, in the write pass, a row (t < A)
     const size_t base = (size_t)p * A;
@@ -120,7 +136,13 @@ __global__ __launch_bounds__(LINK_THREADS) void k_links(const uint32_t* __restri
     if (pages && access) {
         addr = canonical(group_ptr(code, data, rec->kg)[(size_t)rec->kc * n + row]);
         inside = addr < pa.W;
-        if (inside) word = pa.image[addr];
+        if constexpr (kPaged == PAGED_TABLE) {
+            if (inside && !linked) {                      // a head: row `page` of the table must be its address's; not listed: refused as `inside` is
+                const uint32_t page = head_rank(pa.local, pa.sums + 1, t);
+                inside = page < pa.rows && pa.image[(size_t)3 * page] == addr;
+                if (page < pa.rows) word = pa.image[(size_t)3 * page + 1];
+            }
+        } else if (inside) word = pa.image[addr];
     }
     const uint32_t L = rec->L, nl = rec->nl;
     if (!kWrite) {
@@ -150,6 +172,8 @@ __global__ __launch_bounds__(LINK_THREADS) void k_links(const uint32_t* __restri
             if ((threadIdx.x & 63) == 0) atomicMin(bad, ((unsigned long long)p << 32) | mine);
         }
         if (pages) report_bad_row(bad, gridDim.y, access && (addr >> (pa.pg->L * pa.pg->ng)) != 0 ? row : NONE);     // an address the limbs do not hold
+        if constexpr (kPaged == PAGED_TABLE)              // the trace's pages ride back with the refused row (BadRow's third word): one lane, no read-back of its own
+            if (pages && t == 0) ((uint32_t*)bad)[2] = pa.sums[PG_TOTAL];
         return;
     }
     const uint32_t nc = rec->nc, n_dst = rec->n_dst;
@@ -192,7 +216,10 @@ __global__ __launch_bounds__(LINK_THREADS) void k_links(const uint32_t* __restri
 
 // Which rule the refused access `row` of the LINK record r broke, as the reference names it (pages: r is the paged record, and `image` its
 // image): the access and its previous one are found on the host as the reference finds them, from the key and the selector of rows [0, row].
-const char* refusal(zkh_ctx* ctx, const zkh_buf* code, const zkh_buf* data, size_t n, const Link& r, uint32_t row, bool pages, const zkh_buf* image) {
+// With a page table (mem.table) the image's word is the row's of the table: `page_of` gives the page of the refused row, and two words of
+// that row are read; the table is never read back.
+const char* refusal(zkh_ctx* ctx, const zkh_buf* code, const zkh_buf* data, size_t n, const Link& r, uint32_t row, bool pages, const PagedFrom& mem,
+                    uint32_t pages_index, const std::function<const char*(uint32_t*)>& page_of) {
     std::vector<uint32_t> key(row + 1), sel(row + 1, R1);
     ZKH_TRY(zkh_read(ctx, r.kg == GROUP_CODE ? code : data, key.data(), (size_t)r.kc * n, row + 1));
     if (r.sel != NONE) ZKH_TRY(zkh_read(ctx, code, sel.data(), (size_t)r.sel * n, row + 1));
@@ -208,9 +235,22 @@ const char* refusal(zkh_ctx* ctx, const zkh_buf* code, const zkh_buf* data, size
     const uint32_t addr = canonical(key[row]);
     uint32_t word = 0;                                    // paged: the image's word at the address, canonical
     if (pages) {
-        const uint32_t W = (uint32_t)image->len;
+        const uint32_t W = (uint32_t)(mem.table ? mem.image_words : mem.image->len);
         if (addr >= W) return make_err("derive_links: record %u at row %u: address %u outside the image of %u words: the witness is refused", r.index, row, addr, W);
-        ZKH_TRY(zkh_read(ctx, image, &word, addr, 1));
+        if (!mem.table) {
+            ZKH_TRY(zkh_read(ctx, mem.image, &word, addr, 1));
+        } else if (!linked) {                             // the head's page, then its row of the table: its address, its in word
+            uint32_t page, listed;
+            ZKH_TRY(page_of(&page));
+            if (page >= mem.D)
+                return make_err("derive_links: record %u at row %u: address %u is page %u of the trace, but the page table has %zu rows: the witness is refused",
+                                pages_index, row, addr, page, mem.D);
+            ZKH_TRY(zkh_read(ctx, mem.table, &listed, mem.table_at + (size_t)3 * page, 1));
+            if (listed != addr)
+                return make_err("derive_links: record %u at row %u: address %u is page %u of the trace, but row %u of the page table holds address %u: the witness "
+                                "is refused", pages_index, row, addr, page, page, listed);
+            ZKH_TRY(zkh_read(ctx, mem.table, &word, mem.table_at + (size_t)3 * page + 1, 1));
+        }
         word = canonical(word);
     }
     if (linked || pages) {
@@ -245,21 +285,39 @@ const char* refusal(zkh_ctx* ctx, const zkh_buf* code, const zkh_buf* data, size
     return make_err("derive_links: record %u at row %u was refused, but the host finds no rule it breaks", r.index, row);
 }
 
-// zkh_derive_links (image = NULL) and zkh_derive_links_paged: one sort, the check pass, one read-back, the write pass.  With a PAGES record
-// both passes are k_links' paged ones and the page scan runs between the sort and the check.
-const char* derive_links(zkh_ctx* ctx, const zkh_circuit* c, size_t po2, size_t zk_cycles, const zkh_buf* code, zkh_buf* data, const zkh_buf* image) {
+// grid ceil(A / LINK_THREADS), k_page_heads' geometry (head_rank reads the workgroup's carry): the page of the access `row` of the paged
+// record, for the host's message about a refused row.  A row is at one sorted position: one writer.
+__global__ __launch_bounds__(LINK_THREADS) void k_page_of(const uint32_t* __restrict__ status, const uint32_t* __restrict__ rows, uint32_t p, uint32_t A, uint32_t row,
+                                                          const uint32_t* __restrict__ local, const uint32_t* __restrict__ sums, uint32_t* __restrict__ page) {
+    const uint32_t m = status[ST_HEAD + ST_WORDS * p + ST_M];
+    const uint32_t t = blockIdx.x * LINK_THREADS + threadIdx.x;
+    if (t < m && rows[(size_t)p * A + t] == row) *page = head_rank(local, sums + 1, t);
+}
+
+}  // namespace
+
+// zkh_derive_links (no image), zkh_derive_links_paged (mem.image) and zkh_derive_links_paged_table (mem.table): one sort, the check pass, one
+// read-back, the write pass.  With a PAGES record both passes are k_links' paged ones and the page scan runs between the sort and the check.
+const char* zkh::derive_links_from(zkh_ctx* ctx, const zkh_circuit* c, size_t po2, size_t zk_cycles, const zkh_buf* code, zkh_buf* data, const PagedFrom& mem) {
     ZKH_REQUIRE(ctx && c && data, "derive_links: null argument");
     ZKH_REQUIRE(code, "derive_links: the raw code trace is required (the selectors and code-group source columns of the records read it)");
     ZKH_REQUIRE(zkh_circuit_derives_links(c), "derive_links: the circuit's arguments hold no LINK record (ZKA1 version 5)");
     const bool paging = !c->args->pages.empty();
-    ZKH_REQUIRE(image || !paging, "derive_links: the arguments page memory: an image is required (zkh_derive_all_paged)");
+    const bool tabled = paging && mem.table;            // the image's words come as a page table
+    const zkh_buf* image = mem.image;
+    ZKH_REQUIRE(image || tabled || !paging, "derive_links: the arguments page memory: an image is required (zkh_derive_all_paged)");
+    if (tabled) {
+        ZKH_REQUIRE(mem.table_at <= mem.table->len && mem.D <= (mem.table->len - mem.table_at) / 3,
+                    "derive_links: a table of %zu rows of 3 words at word %zu does not fit a buffer of %zu words", mem.D, mem.table_at, mem.table->len);
+        ZKH_REQUIRE(mem.image_words >= 1 && mem.image_words <= 0xffffffffull, "derive_links: an image of %zu words (1 .. 2^32 - 1)", mem.image_words);
+    }
     size_t n;
     uint32_t A;
     ZKH_TRY(trace_rows("derive_links", c, po2, zk_cycles, code, data, nullptr, &n, &A));
     const std::vector<Link>& links = c->args->links;
     const uint32_t nr = (uint32_t)links.size();
     ZKH_REQUIRE(nr <= 65535, "derive_links: %u LINK records in one blob (at most 65535)", nr);
-    ZKH_REQUIRE(!paging || image->len <= 0xffffffffull, "derive_links: an image of %zu words (at most 2^32 - 1)", paging ? image->len : 0);
+    ZKH_REQUIRE(!paging || tabled || image->len <= 0xffffffffull, "derive_links: an image of %zu words (at most 2^32 - 1)", paging && !tabled ? image->len : 0);
     const int paged = paging ? c->args->paged_link() : -1;
     ZKH_REQUIRE(!paging || paged >= 0, "derive_links: the PAGES record names no LINK record");    // set_arguments has refused such a blob
     std::vector<SortPair> pairs(nr, SortPair{});
@@ -293,7 +351,9 @@ const char* derive_links(zkh_ctx* ctx, const zkh_circuit* c, size_t po2, size_t 
         ZKH_TRY(zkh_copy_from(ctx, "pages_record", (const uint32_t*)&g, sizeof(Pages) / 4, dpages.out()));
         ZKH_TRY(new_buf(ctx, A, false, local.out()));
         ZKH_TRY(new_buf(ctx, 1 + (size_t)nb, false, sums.out()));
-        pa = Paging{(const Pages*)dpages->ptr(), (uint32_t)paged, image->ptr(), (uint32_t)image->len, local->ptr(), sums->ptr()};
+        pa = tabled ? Paging{(const Pages*)dpages->ptr(), (uint32_t)paged, mem.table->ptr() + mem.table_at, (uint32_t)mem.image_words,
+                             (uint32_t)std::min<size_t>(mem.D, 0xffffffffu), local->ptr(), sums->ptr()}       // a trace pages at most A rows: more never match
+                    : Paging{(const Pages*)dpages->ptr(), (uint32_t)paged, image->ptr(), (uint32_t)image->len, 0, local->ptr(), sums->ptr()};
         ProfScope prof(ctx, "pages_scan", 12.0 * A + 8.0 * nb);            // the keys of every position, its index, the workgroups' totals twice
         k_page_heads<<<nb, LINK_THREADS, 0, ctx->stream>>>(sorted.status->ptr(), sorted.keys(), (uint32_t)paged, A, local->ptr(), sums->ptr());
         ZKH_TRY(last_launch_error("pages_heads"));
@@ -308,7 +368,7 @@ const char* derive_links(zkh_ctx* ctx, const zkh_circuit* c, size_t po2, size_t 
         double cells = 0;                                 // with READS: the write flag and, at most, the value cells at both rows
         for (const Link& r : links) cells += r.flags & LINK_READS ? 1 + 2 * (r.nc - 1) : 0;
         ProfScope prof(ctx, "links_check", (20.0 * nr + 4.0 * cells + (paging ? 8.0 : 0.0)) * A);   // key and row of every item; the clock at both rows; paged: the key and the image's word
-        pass(paging ? k_links<false, true, true> : reads ? k_links<false, true, false> : k_links<false, false, false>);
+        pass(tabled ? k_links<false, true, PAGED_TABLE> : paging ? k_links<false, true, PAGED_IMAGE> : reads ? k_links<false, true, PAGED_NO> : k_links<false, false, PAGED_NO>);
         ZKH_TRY(last_launch_error("links_check"));
     }
     ZKH_TRY(bad.read(ctx));
@@ -318,23 +378,41 @@ const char* derive_links(zkh_ctx* ctx, const zkh_circuit* c, size_t po2, size_t 
         ZKH_TRY(read_cell(ctx, code, data, links[paged].kg, links[paged].kc, n, bad.lo, &a));
         return make_err("derive_links: record %u at row %u: address %u does not fit %u limbs of %u bits: the witness is refused", g.index, bad.lo, a, g.ng, g.L);
     }
-    if (bad.found) return refusal(ctx, code, data, n, links[bad.hi], bad.lo, (int)bad.hi == paged, image);
+    if (bad.found) {
+        const auto page_of = [&](uint32_t* page) -> const char* {      // the refused head's page: one more launch, on a refusal only
+            Tmp at;
+            ZKH_TRY(new_buf(ctx, 1, true, at.out()));
+            k_page_of<<<nb, LINK_THREADS, 0, ctx->stream>>>(sorted.status->ptr(), sorted.rows(), (uint32_t)paged, A, bad.lo, pa.local, pa.sums, at->ptr());
+            ZKH_TRY(last_launch_error("links_page_of"));
+            return zkh_read(ctx, at, page, 0, 1);
+        };
+        return refusal(ctx, code, data, n, links[bad.hi], bad.lo, (int)bad.hi == paged, mem, paging ? c->args->pages[0].index : 0, page_of);
+    }
+    if (tabled) {                                       // no row is refused: every head is listed, so the table has at least the trace's pages
+        const uint32_t D = bad.extra;                   // the scan's total, which the check pass sent back with its verdict
+        ZKH_REQUIRE(D == mem.D, "derive_links: record %u: the trace pages %u addresses, but the page table has %zu rows: the witness is refused", c->args->pages[0].index,
+                    D, mem.D);
+    }
     {
         ProfScope prof(ctx, "links_write", (20.0 * nr + 4.0 * carried + 4.0 * dsts + (paging ? 12.0 + 4.0 * c->args->pages[0].n_dst : 0.0)) * A);
-        pass(paging ? k_links<true, false, true> : k_links<true, false, false>);
+        pass(tabled ? k_links<true, false, PAGED_TABLE> : paging ? k_links<true, false, PAGED_IMAGE> : k_links<true, false, PAGED_NO>);
         ZKH_TRY(last_launch_error("links_write"));
     }
     // the temporaries go back to the pool on return: the stream orders their next use after these launches
     return nullptr;
 }
 
-}  // namespace
-
 extern "C" const char* zkh_derive_links(zkh_ctx* ctx, const zkh_circuit* c, size_t po2, size_t zk_cycles, const zkh_buf* code, zkh_buf* data) {
-    return derive_links(ctx, c, po2, zk_cycles, code, data, nullptr);
+    return derive_links_from(ctx, c, po2, zk_cycles, code, data, PagedFrom{});
 }
 
 extern "C" const char* zkh_derive_links_paged(zkh_ctx* ctx, const zkh_circuit* c, size_t po2, size_t zk_cycles, const zkh_buf* code, zkh_buf* data,
                                               const zkh_buf* image) {
-    return derive_links(ctx, c, po2, zk_cycles, code, data, image);
+    return derive_links_from(ctx, c, po2, zk_cycles, code, data, PagedFrom{image});
+}
+
+extern "C" const char* zkh_derive_links_paged_table(zkh_ctx* ctx, const zkh_circuit* c, size_t po2, size_t zk_cycles, const zkh_buf* code, zkh_buf* data,
+                                                    const zkh_buf* table, size_t table_at, size_t D, size_t image_words) {
+    ZKH_REQUIRE(table || !zkh_circuit_pages(c), "derive_links: the arguments page memory: a page table is required (zkh_derive_all_paged_table)");
+    return derive_links_from(ctx, c, po2, zk_cycles, code, data, PagedFrom{nullptr, table, table_at, D, image_words});
 }

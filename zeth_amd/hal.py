@@ -187,6 +187,8 @@ ABI = {
     "zkh_circuit_pages": (_i, [_vp]),
     "zkh_derive_links_paged": (_err, [_vp, _vp, _sz, _sz, _vp, _vp, _vp]),
     "zkh_derive_all_paged": (_err, [_vp, _vp, _sz, _sz, _vp, _vp, _vp]),
+    "zkh_derive_links_paged_table": (_err, [_vp, _vp, _sz, _sz, _vp, _vp, _vp, _sz, _sz, _sz]),
+    "zkh_derive_all_paged_table": (_err, [_vp, _vp, _sz, _sz, _vp, _vp, _vp, _sz, _sz, _sz]),
     "zkh_page_out": (_err, [_vp, _vp, _sz, _sz, _vp, _vp]),
     "zkh_image_tree_words": (_sz, [_sz]),
     "zkh_image_commit": (_err, [_vp, _vp, _vp]),
@@ -964,6 +966,41 @@ class HipHal:
         outside the image, a clock 0 and an unlinked load that does not return the image's word (`data` is then unchanged).  Without a
         PAGES record the image is ignored"""
         _check(_lib.zkh_derive_links_paged(self.ctx, circuit.h, po2, zk_cycles, code.h, data.h, None if image is None else image.h))
+
+    def _page_table(self, who: str, table, table_at: int, D: Optional[int], image_words: int):
+        """the page-table operands of the `_table` derives -> (Buffer or None, table_at, D): a Buffer with `table_at` and `D`, or a (D, 3) array
+        of rows (address, in, out), which is uploaded; None (a circuit without a PAGES record ignores the table) passes NULL"""
+        if table is None:
+            return None, 0, 0
+        if not isinstance(table, Buffer):
+            rows = _u32(table)
+            if rows.ndim != 2 or rows.shape[1] != 3:
+                raise HalError(f"{who}: a page table of shape {rows.shape} (rows of 3 words: address, in, out)")
+            if D is not None and D != rows.shape[0] or table_at:
+                raise HalError(f"{who}: a page table given as rows is uploaded whole: table_at {table_at} and D {D} go with a Buffer")
+            table, D = self.copy_from("page_table", rows) if rows.size else self.alloc("page_table", 1), rows.shape[0]
+        if D is None:
+            raise HalError(f"{who}: a page table in a Buffer needs its rows (D)")
+        if min(table_at, D, image_words) < 0:
+            raise HalError(f"{who}: negative argument (table_at {table_at}, D {D}, image_words {image_words})")
+        return table, table_at, D
+
+    def derive_links_paged_table(self, circuit: Circuit, po2: int, zk_cycles: int, code: Buffer, data: Buffer, table, image_words: int,
+                                 table_at: int = 0, D: Optional[int] = None) -> None:
+        """derive_links_paged from the page table of a ZKU1 proof in place of the image (zkh_derive_links_paged_table): row i of the table
+        is (a_i, in_i, out_i), and in_i stands for image[a_i].  table: a Buffer that holds D rows of 3 words from word `table_at` (a
+        proof: table_at = 5 + h), or a (D, 3) array, which is uploaded; image_words: W.  The result is derive_links_paged's on the image
+        the table was made from, cell for cell as residues.  Raises HalError as derive_links_paged does, and when the table's rows are
+        not the trace's pages (`data` is then unchanged).  Without a PAGES record the table is ignored"""
+        buf, at, rows = self._page_table("derive_links_paged_table", table, table_at, D, image_words)
+        _check(_lib.zkh_derive_links_paged_table(self.ctx, circuit.h, po2, zk_cycles, code.h, data.h, None if buf is None else buf.h, at, rows, image_words))
+
+    def derive_all_paged_table(self, circuit: Circuit, po2: int, zk_cycles: int, code: Buffer, data: Buffer, table, image_words: int,
+                               table_at: int = 0, D: Optional[int] = None) -> None:
+        """derive_all_paged with the page table of a ZKU1 proof where the links stage gets the image (zkh_derive_all_paged_table); the
+        operands are derive_links_paged_table's"""
+        buf, at, rows = self._page_table("derive_all_paged_table", table, table_at, D, image_words)
+        _check(_lib.zkh_derive_all_paged_table(self.ctx, circuit.h, po2, zk_cycles, code.h, data.h, None if buf is None else buf.h, at, rows, image_words))
 
     def page_out(self, circuit: Circuit, po2: int, zk_cycles: int, data: Buffer, image: Buffer) -> None:
         """write the page table of `data` back into `image`: image[p_addr] = p_out on every active row with p_on = 1 (zkh_page_out).

@@ -1,7 +1,10 @@
 """Sealing and verifying a page-out: the host layer over the page-out circuits.  `PAGE_KINDS` states every circuit kind
 that seals one, once.  `seal_chain` seals a page-out as a chain of parts (SegmentProver.seal_page_out, _parts, _ordered, _tree) and
 `seal_tied_group` a paging segment and its page-out as one tied group (`seal_tied`, `seal_tied_tree`), both on `open_chain`;
-`verify_chain` and `verify_tied_group` are their verifiers, HOST ONLY.  A prover reaches this module as an object (prover.py imports this
+`verify_chain` and `verify_tied_group` are their verifiers, HOST ONLY.  A PAGED RUN is many segments over one memory:
+`preflight_paged_run` threads the image on the rank that holds it and ships one `PagedStep` per segment, `seal_paged_step`
+(`seal_tied_tree_from_proof`) seals a step's whole group on any rank from the proof alone, and `verify_paged_run` (`link_paged_run`) takes
+the groups from root_0 to root_S, HOST ONLY.  A prover reaches this module as an object (prover.py imports this
 module, not the reverse), a receipt as what its `seal_with_accum` returns; the verifiers read only a receipt's `.seal`."""
 from __future__ import annotations
 
@@ -277,6 +280,132 @@ def seal_tied_tree(seg_prover, seg, code, data, out_prefix, page_prover, page_se
     receipt, [the parts' receipts]), for `verify_tied_tree`."""
     return seal_tied_group("seal_tied_tree", 9, seg_prover, seg, code, data, out_prefix, page_prover, page_segs, proof, proof_words, nodes_before, nodes_after, check, check_table, plan,
                            dirty, hold_bytes)
+
+
+def _upload_traces(prover, seg, host_code, host_data, pinned: bool):
+    """the segment's host traces on the device as seal_host_witness uploads them (of the derived columns only the blinding rows) -> (code,
+    data).  pinned: both lie in hal.host_alloc blocks and the copies are enqueued; else any host memory, consumed before the return"""
+    hal = prover.hal
+    code, data = hal.alloc_elem("code", host_code.size), hal.alloc_elem("data", host_data.size)
+    if pinned:
+        hal.write_async(code, host_code)
+    else:
+        code.write(np.ascontiguousarray(host_code, dtype=np.uint32).reshape(-1))
+        host_data = np.ascontiguousarray(host_data, dtype=np.uint32).reshape(-1)
+    hal.upload_data_trace(prover.circuit, seg.po2, seg.zk_cycles, data, host_data, pinned_async=pinned)
+    return code, data
+
+
+def seal_tied_tree_from_proof(seg_prover, seg, host_code, host_data, out_prefix, page_prover, page_segs, proof, root_before, check: bool = False,
+                              check_table: bool = True, plan: str = "device", hold_bytes: int = 0, pinned: bool = False):
+    """Seal a whole tied group (`seal_tied_tree`) on a rank that holds NEITHER the image NOR its tree, from what the rank that does ships:
+    the segment's underived host traces (host_code, host_data: what seal_host_witness is handed), the ZKU1 proof of its page-out and
+    root_before -> (the segment's receipt, [the parts' receipts], root_after).  In order: hal.image_proof_nodes(proof, root_before), which
+    refuses a proof that does not open root_before before anything is derived and leaves the dirty-node table; the upload; the derive
+    stages with the proof's table where it lies in the image's place (derive_all_paged_table, table_at = 5 + h, W and D from the header);
+    reduce_elem on both traces; seal_tied_group with both trees None.  With the same noise seeds the seals are byte for byte those of
+    `seal_tied_tree` on the rank that holds the image.  proof: the proof's words, or a device Buffer that is the proof.  page_segs: a
+    list, one Segment per part, or a callable p -> Segment asked once per part of the plan (made as `plan` says).  pinned: the host
+    traces lie in hal.host_alloc blocks (the uploads are then enqueued, as seal_host_witness does).  The other operands are
+    seal_tied_tree's."""
+    who, hal = "seal_tied_tree_from_proof", seg_prover.hal
+    if not isinstance(proof, _hal.Buffer):
+        proof = hal.copy_from("image_proof", np.ascontiguousarray(proof, dtype=np.uint32).reshape(-1))
+    words = proof.size()
+    root_after, dirty = hal.image_proof_nodes(proof, root_before, words=words)
+    head = proof.slice(0, 5).to_vec()                                        # image_proof_nodes has checked the header against the words
+    W, D, h = int(head[1]), int(head[2]), int(head[4])
+    if callable(page_segs):
+        if plan not in ("host", "device"):
+            raise _hal.HalError(f'{who}: plan="{plan}" (the plan is made on the "host" or on the "device")')
+        first = page_segs(0)                                                 # every part has one (po2, zk_cycles): the first one's
+        parts = (hal.page_tree_plan_device(first.po2, first.zk_cycles, W, proof, 5 + h, D) if plan == "device" else
+                 hal.page_tree_plan(first.po2, first.zk_cycles, W, proof.slice(5 + h, 3 * D).to_vec()[::3]))
+        page_segs = [first] + [page_segs(p) for p in range(1, len(parts))]
+    code, data = _upload_traces(seg_prover, seg, host_code, host_data, pinned)
+    hal.derive_all_paged_table(seg_prover.circuit, seg.po2, seg.zk_cycles, code, data, proof, W, table_at=5 + h, D=D)
+    hal.reduce_elem(code)
+    hal.reduce_elem(data)
+    seg_receipt, receipts = seal_tied_group(who, 9, seg_prover, seg, code, data, out_prefix, page_prover, page_segs, proof, words, None, None, check, check_table,
+                                            plan, dirty, hold_bytes)
+    return seg_receipt, receipts, root_after
+
+
+@dataclass(frozen=True)
+class PagedStep:
+    """What the rank that holds the image ships for one segment of a paged run (`preflight_paged_run`): the segment, its host traces as
+    they were given (underived), the words of the ZKU1 proof of its page-out, and the roots the page-out leads between.  It holds no
+    image, no tree and no derived trace: any rank seals the step's tied group from it (`seal_paged_step`)."""
+    seg: object
+    host_code: np.ndarray
+    host_data: np.ndarray
+    proof: np.ndarray
+    root_before: np.ndarray
+    root_after: np.ndarray
+
+
+def preflight_paged_run(seg_prover, segs, witnesses, image, tree, pinned: bool = False) -> list:
+    """Thread ONE memory image through the segments of a run, on the rank that holds it -> one PagedStep per segment.  segs: the
+    Segments, in the run's order; witnesses: per segment (host_code, host_data), underived; image, tree: the image as a device Buffer
+    and its committed tree (hal.image_commit), both the run's: they end as the last segment leaves them.  Per segment, in order: the
+    upload; derive_all_paged from the image as it is now; reduce_elem; SegmentProver.page_out(..., proof=True, walk=True), which builds
+    the proof from the tree as it is, writes the page table back, brings the tree up to date and checks that the proof walks to the new
+    root.  No derived trace is kept.  A segment that pages no address (an empty table) is refused here: its group has no dirty node and
+    is sealed from the tree (`seal_tied_tree`); its page-out has changed nothing."""
+    segs, witnesses, hal = list(segs), list(witnesses), seg_prover.hal
+    if len(segs) != len(witnesses):
+        raise _hal.HalError(f"preflight_paged_run: {len(segs)} segments, but {len(witnesses)} witnesses")
+    steps = []
+    for k, (seg, (host_code, host_data)) in enumerate(zip(segs, witnesses)):
+        code, data = _upload_traces(seg_prover, seg, host_code, host_data, pinned)
+        hal.derive_all_paged(seg_prover.circuit, seg.po2, seg.zk_cycles, code, data, image)
+        hal.reduce_elem(data)
+        root_before = hal.image_root(tree)
+        proof = seg_prover.page_out(seg, data, image, tree=tree, proof=True, walk=True)
+        if int(proof[2]) == 0:
+            raise _hal.HalError(f"preflight_paged_run: segment {k} pages no address (an empty table has no dirty nodes): its group is sealed from the tree "
+                                f"(seal_tied_tree)")
+        steps.append(PagedStep(seg, host_code, host_data, proof, root_before, hal.image_root(tree)))
+    return steps
+
+
+def seal_paged_step(step: PagedStep, seg_prover, out_prefix, page_prover, page_segs, **kw):
+    """`seal_tied_tree_from_proof` on one step of `preflight_paged_run` -> (the segment's receipt, [the parts' receipts]).  It is handed no
+    image and no tree, and the steps of a run may be sealed in any order, on any rank.  HalError if the proof does not lead to the root
+    the step states."""
+    seg_receipt, receipts, root_after = seal_tied_tree_from_proof(seg_prover, step.seg, step.host_code, step.host_data, out_prefix, page_prover, page_segs, step.proof,
+                                                                  step.root_before, **kw)
+    if not np.array_equal(root_after, np.asarray(step.root_after, dtype=np.uint32)):
+        raise _hal.HalError(f"seal_paged_step: the proof leads to root {_fmt_words(root_after)}, but the step states root_after {_fmt_words(step.root_after)}")
+    return seg_receipt, receipts
+
+
+def link_paged_run(roots, root_before=None) -> Tuple[np.ndarray, np.ndarray]:
+    """The links of a paged run, HOST ONLY: what verify_paged_run checks once every group is verified -> (root_0, root_S).  roots: per
+    group, in the run's order, (the root it opens, the root it leaves); an iterator is consumed group by group.  Group k + 1 must open
+    the root group k left; with a `root_before`, group 0 must open it.  Raises HalError, one message per cause."""
+    who = "verify_paged_run"
+    chain = [(np.array(a, dtype=np.uint32), np.array(b, dtype=np.uint32)) for a, b in roots]
+    if not chain:
+        raise _hal.HalError(f"{who}: no group")
+    if root_before is not None and not np.array_equal(chain[0][0], np.asarray(root_before, dtype=np.uint32)):
+        raise _hal.HalError(f"{who}: group 0 opens root {_fmt_words(chain[0][0])}, not root_before {_fmt_words(root_before)}")
+    for k in range(1, len(chain)):
+        if not np.array_equal(chain[k][0], chain[k - 1][1]):
+            raise _hal.HalError(f"{who}: group {k} opens root {_fmt_words(chain[k][0])}, but group {k - 1} left root {_fmt_words(chain[k - 1][1])}")
+    return chain[0][0], chain[-1][1]
+
+
+def verify_paged_run(groups, seg_circuit, seg_control_root, page_control_root, h: int, root_before=None) -> Tuple[np.ndarray, np.ndarray]:
+    """Verify a paged run, HOST ONLY -> (root_0, root_S): the segments' page tables, applied in the run's order to the image under root_0,
+    leave root_S.  groups: per segment (its receipt, [the parts' receipts]) of a tied group whose parts are P2-TREE-tied's
+    (`seal_paged_step`, `seal_tied_tree`), in the run's order; one segment circuit, one control root each for the segments and for the
+    parts, one tree height h.  Every group goes through `verify_tied_group` (kind 9) as verify_tied_tree runs it; then the groups must
+    link (`link_paged_run`).  Raises HalError: a group's own message, or one line per cause on a run that does not link."""
+    def verified():
+        for seg_receipt, part_receipts in groups:
+            yield verify_tied_group("verify_tied_tree", 9, seg_receipt, seg_circuit, seg_control_root, part_receipts, page_control_root, None, h)[:2]
+    return link_paged_run(verified(), root_before)
 
 
 def link_page_parts(who: str, parts, root_before=None, first_lo=None, last_hi=None) -> tuple:

@@ -27,8 +27,9 @@ import numpy as np
 from . import hal as _hal, page_seal as _page_seal
 from .circuits import syn_air
 # what seals or verifies a page-out lives in page_seal.py; its public names stay importable from here
-from .page_seal import (TIE_WORDS, link_page_parts, link_page_tree_chain, link_tied_tree_chain, seal_tied, seal_tied_tree,  # noqa: F401
-                        verify_page_ordered_chain, verify_page_out_chain, verify_page_tree_chain, verify_tied, verify_tied_tree)
+from .page_seal import (TIE_WORDS, PagedStep, link_page_parts, link_page_tree_chain, link_paged_run, link_tied_tree_chain,  # noqa: F401
+                        preflight_paged_run, seal_paged_step, seal_tied, seal_tied_tree, seal_tied_tree_from_proof, verify_page_ordered_chain,
+                        verify_page_out_chain, verify_page_tree_chain, verify_paged_run, verify_tied, verify_tied_tree)
 
 DEFAULT_SEGMENT_PO2 = 20      # upstream default segment_limit_po2 (lib.rs:132-135 passes None -> 20)
 _CONTROL_ROOTS_JSON = os.path.join(os.path.dirname(os.path.abspath(__file__)), "circuits", "control_roots.json")
