@@ -282,6 +282,17 @@ const char* zkh_accumulate(zkh_ctx*, const zkh_circuit*, size_t po2, size_t zk_c
  * mix globals were.  It refuses a vanishing denominator as zkh_accumulate does; a total that is not zero is no refusal: total[4] = the
  * sum of the accum columns' last active row, 4 reduced Montgomery words, which the caller states in `out` next to the challenge.
  * zkh_accumulate refuses an open blob and zkh_accumulate_open a closed one; zkh_check_bus skips the keys of the open tag. */
+/* PORTS (ZKA1 version 9: version 8's layout, the OPEN record no longer required; header word 7 = the READS count | bit 16 exactly when the blob
+ * holds a PAGES record | bit 17 exactly when it holds an OPEN record | bit 18 (0x40000, PORTS) exactly when a LINK joins: a version-9 blob
+ * without bit 18 is no ZKA1 blob, bit 18 with no joining record is refused).  In LINK word [5] bit 1 = JOINS beside bit 0 = READS, and with
+ * JOINS word [31] is the blob record index of the HEAD (without it word [31] stays reserved = 0).  A memory is a run of k <= 8 consecutive LINK
+ * records, the head and the records that join it; port q is the record at head + q, with the head's nc, L, nl and READS-ness.  Its accesses
+ * are the (row, port) whose record's selector is 1, ordered by (row, port), and the previous access of one is the greatest one before it
+ * in that order with the same address, in whichever port.  zkh_derive_links, zkh_derive_links_paged, zkh_derive_links_paged_table and
+ * zkh_derive_all* derive such a circuit: destinations stay per record, a refusal names the port's own record and, where the previous access lies
+ * in another record, "row R of record Q".  A PAGES record names the head: an unlinked access of any port takes the image's word, the page
+ * table's heads and tails are those of the merged order, and a trace that pages more addresses than it has active rows is refused.  A blob
+ * without a joiner is what it was, format, launches and messages. */
 int zkh_circuit_open_bus(const zkh_circuit*, uint32_t where[4]);
 const char* zkh_accumulate_open(zkh_ctx*, const zkh_circuit*, size_t po2, size_t zk_cycles, const uint32_t noise_key[8], const zkh_buf* code,
                                 const zkh_buf* data, const uint32_t challenge[8], zkh_buf* accum, uint32_t total[4]);

@@ -379,7 +379,8 @@ impl HipCircuitHal {
     /// Fill the destination columns of the LINK records of `data` on the active rows (`zkh_derive_links`): every memory access gets
     /// the previous access to its own address (linked, last, the carried values, the limbs of the clock difference).  Panics on a
     /// refused witness (a selector other than 0 / 1, a clock that does not increase, a difference that does not fit its limbs), which
-    /// leaves `data` unchanged.
+    /// leaves `data` unchanged.  LINK records that join a head (ZKA1 version 9) are the ports of one memory: the previous access is
+    /// then the one before it in (row, port) order, in whichever port.
     pub fn derive_links(&self, ctrl: &HipBuffer<BabyBearElem>, data: &HipBuffer<BabyBearElem>, steps: usize) {
         let po2 = steps.trailing_zeros() as usize;
         ffi(|| unsafe { sys::zkh_derive_links(self.hal.ctx.0, self.circuit, po2, sys::ZK_CYCLES, ctrl.raw, data.raw) });

@@ -29,7 +29,8 @@ group under P2-TREE-tied next to P2-PAGE-tied's on the same table; M29: P2-TREE 
 zkh_image_proof_walk and part 0's witness from the dirty nodes next to part 0's witness from the two trees on M24's table, alternating, with
 the words of the table, of the proof and of the two trees, and the copy of the tree that keep_before makes; M30: held commitments, a
 whole tied group on M28's setup sealed in two passes next to the same group with hold_bytes for everything, alternating, and for one
-part zkh_commit_data + zkh_prove_begin_held next to zkh_data_root + zkh_prove_begin, with the bytes held; M31: paging in from a page
+part zkh_commit_data + zkh_prove_begin_held next to zkh_data_root + zkh_prove_begin, with the bytes held; M32: zkh_derive_links on three memory pairs as the PORTS of one memory (ZKA1 version 9) next to the version-6 blob of three separate
+memories; M31: paging in from a page
 table, zkh_derive_links_paged_table next to zkh_derive_links_paged on the same SYN-LOOKUP-paged FULL trace at two image sizes, alternating,
 with both calls' passes) on one MI355X, through the C ABI (HipHal).
 
@@ -1719,6 +1720,55 @@ def main() -> None:
                               "runs": runs, "reps": args.reps, **{k: spread(v) for k, v in t.items()}, "steps_ms": steps,
                               "table_vs_image": round(med["derive_links_paged_table"] / med["derive_links_paged"], 3)}), flush=True)
             del code, data_i, data_t, image, table, image_h, code_h, full_h, bare_h
+    if want("M32"):
+        # PORTS (ZKA1 version 9): zkh_derive_links on FULL widened to 3 memory pairs as the PORTS of one memory, next to its yardstick in the
+        # same run, the same library on the version-6 blob of three SEPARATE memories over the same columns.  Their clocks differ (one
+        # memory counts 3 row + port, three memories count rows), so each has its own valid witness over the same addresses' range.  One sort
+        # run of 3 A items against three runs of A.  Timed in alternation, `runs` windows of `reps` calls; median and spread (min, max) of the
+        # windows; then the passes by their events.  No threshold.
+        from zeth_amd.circuits import logup, syn_lookup
+        runs, zk = 7, 1994
+        A = n - zk
+        shape = syn_lookup.Shape(16, 4, 8, 3)
+        assert 3 * A < 1 << (syn_lookup.ORDER_LIMBS * shape.limb_bits), "the ported clocks must fit the link limbs"
+        spread = lambda ts: {"median_ms": round(float(np.median(ts)) * 1e3, 4), "min_ms": round(min(ts) * 1e3, 4), "max_ms": round(max(ts) * 1e3, 4)}   # noqa: E731
+        arms, fns, keep = {}, [], []
+        for name, ported in (("ports_v9", True), ("separate_v6", False)):
+            desc, blob = syn_lookup.build_syn_lookup(shape, link=True, reads=True, ports=ported)
+            assert int(blob[1]) == (9 if ported else 6)
+            code_h, full_h, _out = syn_lookup.witness(shape, args.po2, zk, seed=32, link=True, reads=True, ports=ported)
+            circuit = hal.load_circuit(desc, jit=False)
+            circuit.set_arguments(blob)
+            bare_h = full_h.reshape(-1, n).copy()
+            bare_h[circuit.derived_data_columns(), :A] = 0
+            code, data = hal.alloc_elem("code", code_h.size), hal.alloc_elem("data", bare_h.size)
+            code.write(code_h)
+            data.write(bare_h.reshape(-1))
+            fn = lambda circuit=circuit, code=code, data=data: hal.derive_links(circuit, args.po2, zk, code, data)      # noqa: E731
+            fn()
+            got, lk = data.to_vec().reshape(-1, n), [c for r in logup.Arguments.parse(blob).records if isinstance(r, logup.Link) for c in r.dsts]
+            assert np.array_equal(got[lk], full_h.reshape(-1, n)[lk]), f"{name}: the derived link columns differ from the host-made ones"
+            fns.append((name, fn))
+            keep.append((circuit, code, data))
+            del code_h, full_h, bare_h, got
+        t = {name: [] for name, _ in fns}
+        for _ in range(runs):
+            for name, fn in fns:
+                t[name].append(timed(hal, fn, args.reps))
+        for name, fn in fns:
+            hal.prof_enable(True)
+            hal.prof_reset()
+            for _ in range(args.reps):
+                fn()
+            hal.sync()
+            steps = {r["name"]: round(r["total_ms"] / max(r["calls"], 1), 4) for r in hal.prof_get() if r["calls"] and r["name"].startswith(("sort_", "links_"))}
+            hal.prof_enable(False)
+            sort_ms = sum(v for k, v in steps.items() if k.startswith("sort_"))
+            arms[name] = {**spread(t[name]), "steps_ms": steps, "sort_ms": round(sort_ms, 4), "check_ms": steps.get("links_check", 0), "write_ms": steps.get("links_write", 0)}
+        med = {k: float(np.median(v)) for k, v in t.items()}
+        print(json.dumps({"bench": "M32", "circuit": "SYN-LOOKUP-reads FULL widened to 3 memory pairs", "po2": args.po2, "accesses": 3 * A, "addresses_below": 1 << 20,
+                          "runs": runs, "reps": args.reps, **arms, "ports_vs_separate": round(med["ports_v9"] / med["separate_v6"], 3)}), flush=True)
+        del keep
     hal.close()
 
 

@@ -24,7 +24,7 @@ The degree of a column's constraint is 1 (gate) + max(1 + t, max_i(deg sel_i + d
 
 ZKA1 layout (u32 words; canonical integers, not Montgomery words)::
 
-    [0] magic 'ZKA1' = 0x5a4b4131   [1] version = 1 .. 7      [2] k = accum Fp4 columns   [3] alpha mix word offset
+    [0] magic 'ZKA1' = 0x5a4b4131   [1] version = 1 .. 9      [2] k = accum Fp4 columns   [3] alpha mix word offset
     [4] beta mix word offset       [5] n_terms       [6] reserved = 0 (version 4: n_records)
     [7] reserved = 0 (version 6: the number of LINK records with READS, at least 1; version 7: that number | 0x10000)
     terms: n_terms x 16 words, sorted by column:
@@ -65,6 +65,24 @@ ZKA1 layout (u32 words; canonical integers, not Montgomery words)::
       are `out` offsets, not mix offsets.  Header word 7 = (the READS count) | 0x10000 exactly when the blob holds a PAGES record | 0x20000:
       a version-8 blob without bit 17 is no ZKA1 blob, bit 17 without an OPEN record is refused; neither a READS count nor a PAGES record
       is required.  The builder writes version 8 only when an OPEN record exists.
+
+    Version 9: version 8's layout, but the OPEN record is no longer required, and a LINK record may JOIN the memory of an earlier LINK
+      record, its HEAD.  LINK word [5]: bit 0 = READS, bit 1 = JOINS, every other bit is refused; with JOINS word [31] is the blob record
+      index of the head, without it word [31] stays reserved = 0.  Header word 7 = (the READS count) | 0x10000 exactly when the blob holds a
+      PAGES record | 0x20000 exactly when it holds an OPEN record | 0x40000 (bit 18, PORTS) exactly when a LINK joins: a version-9 blob
+      without bit 18 is no ZKA1 blob, bit 18 with no joining record is refused.  The builder writes version 9 only when a record joins
+      (`derive_links(..., joins=head)`).
+
+PORTS (a LINK record with JOINS, ZKA1 version 9): several accesses per row to ONE memory.  A memory is a run of k <= 8 consecutive LINK
+records: the head, then the records that join it, in blob order; port q is the record at head + q, and every port has the head's nc, L, nl
+and READS-ness.  The memory's accesses are all the (row r < A, port q) whose record's selector is 1 at r, ordered by (r, q); the previous
+access of (r, q) with address K = x(key_q, r) is the greatest (r', q') < (r, q) in that order with x(key_q', r') = K.  Everything below keeps
+its meaning with "the previous access" read that way: prev_j of (r, q) is the raw word of record q' carried column j at r', the limbs are those
+of x(clock_q, r) - x(clock_q', r') - 1, the read rule compares record q's value columns at r with record q' value columns at r'.  Destinations
+stay per record: port q writes its own linked, last, prev and limb columns at row r.  A refusal names the port's own record and, where the
+previous access lies in another record, says so ("at row R of record Q").  A PAGES record names the head: an unlinked access of any port
+takes the image's word, the heads and tails of the page table are those of the merged order, p_addr and p_in come from the head access's
+record, p_out and p_time from the tail access's.  A memory of one record is what it always was, message for message.
 
 THE OPEN BUS (the OPEN record; `LogupBuilder(..., open_bus=...)`, zkh_accumulate_open; DESIGN.md §2 "THE TIE"): a bus across seals.  The
 challenges are words of `out` (a hash of the data roots of every seal of the group, drawn after all of them are committed:
@@ -333,6 +351,9 @@ KIND_LINK = 3
 LINK_WORDS = 32
 MAX_CARRIED = 3
 MAX_LINK_LIMBS = 4
+LINK_JOINS = 2                                 # LINK word 5, bit 1 (version 9): the record joins the memory of the head that word 31 names
+MAX_PORTS = 8                                  # the records of one memory, the head included
+PORTS_BIT = 0x40000                            # header word 7, bit 18 (version 9): a LINK record joins
 
 
 @dataclass(frozen=True)
@@ -349,6 +370,8 @@ class Link:
     write: Optional[Tuple[int, int]] = None    # READS (version 6): the (group, column) of the write flag; None = no read rule
     flag_word: Optional[int] = None            # the blob's word 5 where it sets a bit other than READS (parser only)
     stray_write: bool = False                  # words 14, 15 are not 0 although READS is not set (parser only, version 6)
+    joins: Optional[int] = None                # JOINS (version 9): the blob record index of the head whose memory this record is a port of
+    ports_word: bool = field(default=False, compare=False)   # the blob's version reads bit 1 of word 5 as JOINS (parser only: the text of the flag word's refusal)
     kind = KIND_LINK
 
     @property
@@ -379,19 +402,24 @@ class Link:
         return 2 + len(self.carried) + self.nl
 
     def words(self) -> List[int]:
-        w = [KIND_LINK, self.limb_bits, self.nl, len(self.carried), NONE if self.sel is None else self.sel, int(self.write is not None),
-             self.key[0], self.key[1]]
+        w = [KIND_LINK, self.limb_bits, self.nl, len(self.carried), NONE if self.sel is None else self.sel,
+             int(self.write is not None) | (LINK_JOINS if self.joins is not None else 0), self.key[0], self.key[1]]
         for g, c in self.carried:
             w += [g, c]
         w += [0] * (14 - len(w)) + list(self.write or (0, 0))
         w += list(self.dsts)
-        return w + [0] * (LINK_WORDS - len(w))
+        w += [0] * (LINK_WORDS - len(w))
+        if self.joins is not None:
+            w[LINK_WORDS - 1] = self.joins
+        return w
 
 
 def _links_clause_a(i: int, r: Link, group_sizes) -> Optional[str]:
     if not (1 <= r.nc <= MAX_CARRIED and 1 <= r.limb_bits <= 16 and 0 <= r.nl <= MAX_LINK_LIMBS and r.limb_bits * r.nl <= MAX_ORDER_BITS):
         return (f"record {i}: a LINK of {r.nc} carried columns and {r.nl} limbs of {r.limb_bits} bits (1..{MAX_CARRIED} carried columns, "
                 f"0..{MAX_LINK_LIMBS} limbs of 1..16 bits, at most {MAX_ORDER_BITS} bits in all)")
+    if r.flag_word is not None and r.ports_word:
+        return f"record {i}: word 5 of a LINK is {r.flag_word:#x} (bit 0: READS, the read rule; bit 1: JOINS, a port of its head's memory; the other bits are reserved)"
     if r.flag_word is not None:
         return f"record {i}: word 5 of a LINK is {r.flag_word:#x} (bit 0: READS, the read rule; the other bits are reserved)"
     if r.stray_write:
@@ -405,11 +433,40 @@ def _links_clause_a(i: int, r: Link, group_sizes) -> Optional[str]:
     return None
 
 
+def _joins_rule(i: int, r: Link, records: Sequence) -> Optional[str]:
+    """the rules of a joiner (version 9): its head is a LINK record without JOINS before it, every record between them joins the same
+    head, it has the head's nc, L, nl and READS-ness, and it is one of the head's first MAX_PORTS - 1 joiners"""
+    h = r.joins
+    if h is None:
+        return None
+    head = records[h] if 0 <= h < i else None
+    if not isinstance(head, Link) or head.joins is not None:
+        return f"record {i}: a LINK joins record {h}, which is no LINK record without JOINS before it (a port joins the head of its memory)"
+    for j in range(h + 1, i):
+        if not isinstance(records[j], Link) or records[j].joins != h:
+            return f"record {i}: a LINK joins record {h}, but record {j} between them does not (a memory is a run of consecutive LINK records)"
+    if (r.nc, r.limb_bits, r.nl, r.write is None) != (head.nc, head.limb_bits, head.nl, head.write is None):
+        return f"record {i}: a LINK joins record {h} with another nc, L, nl or READS (the ports of a memory have their head's)"
+    if i - h >= MAX_PORTS:
+        return f"record {i}: port {i - h} of the memory of record {h} (a memory has at most {MAX_PORTS} records)"
+    return None
+
+
+def memory_ports(records: Sequence, head: int) -> List[int]:
+    """the blob record indices of the ports of the memory whose head is the LINK record `head`: the head, then its joiners"""
+    ports = [head]
+    while ports[-1] + 1 < len(records) and isinstance(records[ports[-1] + 1], Link) and records[ports[-1] + 1].joins == head:
+        ports.append(ports[-1] + 1)
+    return ports
+
+
 def check_links(terms: Sequence[Term], records: Sequence, group_sizes=None) -> Optional[str]:
     """the first LINK record that breaks a rule, named by its index among all `records` (all of them are its peers), or None: (a) the
     ranges of nc, L, nl, the flag word and the write flag's words (version 6), the reserved words and the selector a code column, then
-    (b) .. (e) of `_check_owned`; the write flag of a READS record is one of its sources"""
-    return _check_owned(terms, records, Link, _links_clause_a, group_sizes)
+    (version 9) a joiner's rules: its head a LINK without JOINS before it, the records between them joiners of the same head, the head's
+    nc, L, nl and READS-ness, at most MAX_PORTS records in the memory; then (b) .. (e) of `_check_owned`; the write flag of a READS
+    record is one of its sources.  A port is a LINK like any other: one writer per column, and it reads no derived column"""
+    return _check_owned(terms, records, Link, lambda i, r, sizes: _links_clause_a(i, r, sizes) or _joins_rule(i, r, records), group_sizes)
 
 
 KIND_PAGES = 4
@@ -452,8 +509,9 @@ def _paged_link(records: Sequence, r: "Pages") -> Optional[Link]:
 
 def check_pages(terms: Sequence[Term], records: Sequence, group_sizes=None) -> Optional[str]:
     """the PAGES record that breaks a rule, named by its index among all `records` (all of them are its peers), or None: (a) the ranges
-    of L and ng, the reserved words, and its target a LINK record with READS and nc = 2; then (b) .. (e) of `_check_owned`, its sources
-    being its LINK's and p_on the one destination that may be a multiplicity"""
+    of L and ng, the reserved words, and its target a LINK record with READS and nc = 2 that joins no other (version 9: the head of its
+    memory, whose ports then have READS and nc = 2 as well); then (b) .. (e) of `_check_owned`, its sources being its LINK's and p_on
+    the one destination that may be a multiplicity"""
     def clause_a(i, r, _sizes):
         if not (1 <= r.limb_bits <= 16 and 1 <= r.ng <= MAX_PAGE_LIMBS and r.limb_bits * r.ng <= MAX_ORDER_BITS):
             return (f"record {i}: a PAGES record of {r.ng} limbs of {r.limb_bits} bits (1..{MAX_PAGE_LIMBS} limbs of 1..16 bits, at most "
@@ -462,6 +520,8 @@ def check_pages(terms: Sequence[Term], records: Sequence, group_sizes=None) -> O
             return f"record {i}: a reserved word of a PAGES record is not 0 (words 4..15 and the unused destination words)"
         if _paged_link(records, r) is None:
             return f"record {i}: a PAGES record pages record {r.link}, which is no LINK record with READS and two carried columns (a clock and one value)"
+        if _paged_link(records, r).joins is not None:
+            return f"record {i}: a PAGES record pages record {r.link}, which joins record {_paged_link(records, r).joins} (a PAGES record names the head of a memory)"
         return None
     return _check_owned(terms, records, Pages, clause_a, group_sizes)
 
@@ -655,7 +715,14 @@ class Arguments:
         return next((r for r in self.records if isinstance(r, Open)), None)
 
     @property
+    def ports(self) -> bool:
+        """a LINK record joins another's memory (version 9: bit 18 of header word 7)"""
+        return any(isinstance(r, Link) and r.joins is not None for r in self.records)
+
+    @property
     def version(self) -> int:
+        if self.ports:
+            return 9
         if self.open is not None:
             return 8
         if self.pages is not None:
@@ -672,7 +739,8 @@ class Arguments:
 
     def blob(self) -> np.ndarray:
         words = [ARGS_MAGIC, self.version, self.k, self.alpha, self.beta, len(self.terms), len(self.records),
-                 self.reads | (PAGES_BIT if self.pages is not None else 0) | (OPEN_BIT if self.open is not None else 0)]
+                 self.reads | (PAGES_BIT if self.pages is not None else 0) | (OPEN_BIT if self.open is not None else 0) |
+                 (PORTS_BIT if self.ports else 0)]
         for t in _by_column(self.terms):
             rec = [t.col, 0 if t.sign == 1 else 1, NONE if t.sel is None else t.sel,
                    NONE if t.mult is None else t.mult[0], 0 if t.mult is None else t.mult[1], t.tag % P, len(t.tuple_cols), t.flags()]
@@ -687,8 +755,8 @@ class Arguments:
     @staticmethod
     def parse(blob: Sequence[int]) -> "Arguments":
         d = [int(x) for x in np.asarray(blob, dtype=np.uint32)]
-        if len(d) < ARGS_HEADER or d[0] != ARGS_MAGIC or d[1] not in (1, 2, 3, 4, 5, 6, 7, 8) or (d[1] == 6 and d[7] == 0) or \
-                (d[1] == 7 and not d[7] & PAGES_BIT) or (d[1] == 8 and not d[7] & OPEN_BIT):
+        if len(d) < ARGS_HEADER or d[0] != ARGS_MAGIC or d[1] not in (1, 2, 3, 4, 5, 6, 7, 8, 9) or (d[1] == 6 and d[7] == 0) or \
+                (d[1] == 7 and not d[7] & PAGES_BIT) or (d[1] == 8 and not d[7] & OPEN_BIT) or (d[1] == 9 and not d[7] & PORTS_BIT):
             raise ValueError("not a ZKA1 argument blob")
         version = d[1]
         k, alpha, beta, n = d[2], d[3], d[4], d[5]
@@ -736,13 +804,15 @@ class Arguments:
             if sizes[i] == LINK_WORDS:
                 nc = min(r[3], MAX_CARRIED)
                 n_dst = min(16, 2 + nc + min(r[2], 16))
-                reserved = bool(any(r[8 + 2 * nc:14]) or any(r[16 + n_dst:]))
+                joins = version >= 9 and r[5] & LINK_JOINS != 0             # version 9: bit 1 of word 5, and word 31 names the head
+                reserved = bool(any(r[8 + 2 * nc:14]) or any(r[16 + n_dst:LINK_WORDS - 1 if joins else LINK_WORDS]))
                 reads = version >= 6 and r[5] & 1 == 1                     # version 5 reserves words 5, 14, 15; version 6 reads them
                 if version < 6:
                     reserved = reserved or bool(r[5] or r[14] or r[15])
                 records.append(Link(None if r[4] == NONE else r[4], (r[6], r[7]), tuple((r[8 + 2 * j], r[9 + 2 * j]) for j in range(nc)), r[1], r[2],
                                     tuple(r[16: 16 + n_dst]), reserved, None if r[3] == nc else r[3], (r[14], r[15]) if reads else None,
-                                    r[5] if version >= 6 and r[5] > 1 else None, bool(version >= 6 and not reads and (r[14] or r[15]))))
+                                    r[5] if version >= 6 and r[5] > (3 if version >= 9 else 1) else None,
+                                    bool(version >= 6 and not reads and (r[14] or r[15])), r[LINK_WORDS - 1] if joins else None, version >= 9))
                 continue
             n_src = r[3]
             n_dst = min(8, r[2] + (r[0] == KIND_ORDER and n_src == 2))
@@ -752,16 +822,23 @@ class Arguments:
         n_reads = sum(isinstance(r, Link) and r.write is not None for r in records)
         has_pages = any(isinstance(r, Pages) for r in records)
         word7 = d[7] ^ PAGES_BIT if version == 7 or (version >= 8 and d[7] & PAGES_BIT) else d[7]     # bit 16 says PAGES, the rest counts as before
-        if version >= 8:
+        has_open = any(isinstance(r, Open) for r in records)
+        if version == 8 or (version >= 9 and d[7] & OPEN_BIT):
             word7 ^= OPEN_BIT                                                # bit 17 says OPEN
+        if version >= 9:
+            word7 ^= PORTS_BIT                                               # bit 18 says PORTS
         if version >= 6 and word7 != n_reads:
             raise ValueError(f"ZKA1: header word 7 is {word7}, the blob has {n_reads} LINK records with READS")
         if version >= 7 and d[7] & PAGES_BIT and not has_pages:
             raise ValueError("ZKA1: header word 7 has bit 16 (PAGES), but the blob has no PAGES record")
         if version >= 8 and has_pages and not d[7] & PAGES_BIT:
             raise ValueError("ZKA1: the blob has a PAGES record, but header word 7 lacks bit 16 (PAGES)")
-        if version >= 8 and not any(isinstance(r, Open) for r in records):
+        if version >= 8 and d[7] & OPEN_BIT and not has_open:
             raise ValueError("ZKA1: header word 7 has bit 17 (OPEN), but the blob has no OPEN record")
+        if version >= 9 and has_open and not d[7] & OPEN_BIT:
+            raise ValueError("ZKA1: the blob has an OPEN record, but header word 7 lacks bit 17 (OPEN)")
+        if version >= 9 and not any(isinstance(r, Link) and r.joins is not None for r in records):
+            raise ValueError("ZKA1: header word 7 has bit 18 (PORTS), but no LINK record joins")
         problem = check_sorted(terms) or check_derived(terms) or check_open(terms, records, (alpha, beta)) or _check_records(terms, records)
         if problem:
             raise ValueError(f"ZKA1: {problem}")
@@ -857,7 +934,11 @@ class LogupBuilder(CircuitBuilder):
         # LIMBS / ORDER records, then LINK records, then the PAGES record, which names its LINK by index: that index moves with the LINK
         before = list(self.records)
         at = len(before) if isinstance(rec, Pages) else sum(isinstance(r, Record) or (isinstance(rec, Link) and isinstance(r, Link)) for r in before)
-        self.records = [replace(r, link=r.link + 1) if isinstance(r, Pages) and r.link >= at else r for r in before]
+        if isinstance(rec, Link) and rec.joins is not None:                  # a joiner goes after the last port of its memory: a memory is one run
+            at = memory_ports(before, rec.joins)[-1] + 1
+        moved = lambda r: (replace(r, link=r.link + 1) if isinstance(r, Pages) and r.link >= at else
+                           replace(r, joins=r.joins + 1) if isinstance(r, Link) and r.joins is not None and r.joins >= at else r)
+        self.records = [moved(r) for r in before]
         self.records.insert(at, rec)
         problem = _check_records(self.terms, self.records, self.group_sizes)
         if problem:
@@ -878,16 +959,23 @@ class LogupBuilder(CircuitBuilder):
         return self._record(Record(KIND_ORDER, int(limb_bits), len(dsts) - (len(keys) == 2), keys, tuple(int(c) for c in dsts)))
 
     def derive_links(self, sel: Optional[int], key: Tuple[int, int], carried: Sequence[Tuple[int, int]], dsts: Sequence[int], limb_bits: int,
-                     write: Optional[Tuple[int, int]] = None) -> Link:
+                     write: Optional[Tuple[int, int]] = None, joins: Optional[Link] = None) -> Link:
         """the library fills the data columns `dsts` (zkh_derive_links) = linked, last, one prev per carried column, then the limbs of
         the clock difference, for the accesses (selector code column `sel`, None = every active row) to the address `key`; `carried`
         are the (group, column) pairs whose value at the previous access is copied, carried[0] the clock (`reference_links`).
         write: the (group, column) of the write flag; the record then has READS (ZKA1 version 6) and a load that does not return the
-        last store, or 0 from an address never accessed, refuses the witness (the module docstring's read rule)"""
+        last store, or 0 from an address never accessed, refuses the witness (the module docstring's read rule).
+        joins: a LINK record of this builder without `joins`, the head: this record is one more PORT of the head's memory (ZKA1 version
+        9; the module docstring's PORTS), after the ports it has; the accesses of all ports are one memory's, ordered by (row, port)"""
         carried = tuple((int(g), int(c)) for g, c in carried)
+        head = None
+        if joins is not None:
+            head = next((i for i, r in enumerate(self.records) if r is joins), None) if joins not in self.records else self.records.index(joins)
+            if head is None:
+                raise ValueError("derive_links: the head (joins=) is not one of this builder's LINK records")
         return self._record(Link(None if sel is None else int(sel), (int(key[0]), int(key[1])), carried, int(limb_bits),
                                  len(dsts) - 2 - len(carried), tuple(int(c) for c in dsts),
-                                 write=None if write is None else (int(write[0]), int(write[1]))))
+                                 write=None if write is None else (int(write[0]), int(write[1])), joins=head))
 
     def derive_pages(self, link_record: Link, dsts: Sequence[int], limb_bits: int) -> Pages:
         """the memory of the LINK record `link_record` (one of this builder's, with READS and a clock and one value column) is PAGED
@@ -905,8 +993,9 @@ class LogupBuilder(CircuitBuilder):
         return self._record(Pages(int(limb_bits), (len(dsts) - 5) // 2, at, tuple(int(c) for c in dsts)))
 
     def paged(self, record: Link) -> Optional[Pages]:
-        """the PAGES record that pages the LINK `record`, or None"""
-        return next((r for r in self.records if isinstance(r, Pages) and 0 <= r.link < len(self.records) and self.records[r.link] == record), None)
+        """the PAGES record that pages the memory of the LINK `record` (the head it names, or a port that joins that head), or None"""
+        head = record if record.joins is None or not 0 <= record.joins < len(self.records) else self.records[record.joins]
+        return next((r for r in self.records if isinstance(r, Pages) and 0 <= r.link < len(self.records) and self.records[r.link] == head), None)
 
     def _limb_sum(self, cols, L):
         total = None
@@ -1439,22 +1528,40 @@ def reference_links(args: Arguments, po2: int, zk_cycles: int, code, data, image
             raise ReferenceError(f"record {i} at row {row}: selector {int(sel[row])}, not 0 or 1")
         on[i] = np.nonzero(sel == 1)[0]
     writes, late = [], None                                                  # (columns, rows, words): nothing is written before every record passed
-    for i, r in links:
-        rows, L, nl = on[i], r.limb_bits, r.nl
-        paged = pages is not None and pages.link == i
-        addr = _dec(groups[r.key[0]][r.key[1], rows]).astype(np.int64)
-        prev, last = _link_chain(addr, rows)
+    for i0, head in links:
+        if head.joins is not None:                                           # a port: its memory was its head's turn
+            continue
+        ports = [(i, args.records[i]) for i in memory_ports(args.records, i0)]
+        L, nl = head.limb_bits, head.nl
+        paged = pages is not None and pages.link == i0
+        # the memory's accesses (row, port) in that order; a memory of one record: its rows
+        row = np.concatenate([on[i] for i, _ in ports])
+        port = np.concatenate([np.full(on[i].size, q, dtype=np.int64) for q, (i, _) in enumerate(ports)])
+        by = np.lexsort((port, row))
+        row, port = row[by], port[by]
+        rec = np.asarray([i for i, _ in ports], dtype=np.int64)[port]
+
+        def take(cols, rows, at):
+            """the raw words of the per-port (group, column) `cols` at the accesses (rows, at)"""
+            out_ = np.zeros(rows.size, dtype=np.uint32)
+            for q, (g, c) in enumerate(cols):
+                out_[at == q] = groups[g][c, rows[at == q]]
+            return out_
+        keys, carried = [r.key for _, r in ports], [[r.carried[e] for _, r in ports] for e in range(len(head.carried))]
+        addr = _dec(take(keys, row, port)).astype(np.int64)
+        prev, last = _link_chain(addr, row)
         linked = prev >= 0
-        prow = rows[np.where(linked, prev, 0)] if rows.size else rows
-        g0, c0 = r.carried[0]
-        clock, pclock = _dec(groups[g0][c0, rows]).astype(np.int64), _dec(groups[g0][c0, prow]).astype(np.int64)
+        pat = np.where(linked, prev, 0)
+        prow, pport = (row[pat], port[pat]) if row.size else (row, port)
+        prec = rec[pat] if row.size else rec
+        clock, pclock = _dec(take(carried[0], row, port)).astype(np.int64), _dec(take(carried[0], prow, pport)).astype(np.int64)
         d = np.where(linked, clock - pclock - 1, clock - 1 if paged else 0)
         bad = (d < 0) | (d >> (L * nl) != 0)
         if paged:
             outside = addr >= W
             if table is None:
-                word = image[np.where(outside, 0, addr)] if W else np.zeros(rows.size, dtype=np.uint32)      # the image's word of an unlinked access
-                unlisted = np.zeros(rows.size, dtype=bool)
+                word = image[np.where(outside, 0, addr)] if W else np.zeros(row.size, dtype=np.uint32)      # the image's word of an unlinked access
+                unlisted = np.zeros(row.size, dtype=bool)
             else:                                                            # ... by its page: the number of its address among the trace's
                 page = np.searchsorted(np.unique(addr), addr)
                 row_of = np.minimum(page, max(len(table) - 1, 0))
@@ -1463,59 +1570,67 @@ def reference_links(args: Arguments, po2: int, zk_cycles: int, code, data, image
                 unlisted = ~linked & ~outside & ~listed
                 short = (np.unique(addr).size, len(table))
             bad = bad | outside | unlisted
-        if r.write is not None:
-            w = _dec(groups[r.write[0]][r.write[1], rows])
-            now = [_dec(groups[g][c, rows]) for g, c in r.carried]
-            before = [np.where(linked, _dec(groups[g][c, prow]), _dec(word) if paged and e == 1 else 0) for e, (g, c) in enumerate(r.carried)]
-            misread = [(w == 0) & (now[e] != before[e]) for e in range(1, len(r.carried))]
+        if head.write is not None:
+            w = _dec(take([r.write for _, r in ports], row, port))
+            now = [_dec(take(cols, row, port)) for cols in carried]
+            before = [np.where(linked, _dec(take(cols, prow, pport)), _dec(word) if paged and e == 1 else 0) for e, cols in enumerate(carried)]
+            misread = [(w == 0) & (now[e] != before[e]) for e in range(1, len(carried))]
             bad = bad | (w > 1) | np.logical_or.reduce(misread)
         if bad.any():
-            j = int(np.argmax(bad))
-            at = f"record {i} at row {int(rows[j])}"
-            if r.write is not None and w[j] > 1:
+            cand = np.nonzero(bad)[0]
+            j = int(cand[np.lexsort((row[cand], rec[cand]))[0]])             # the lowest (record, row), the record the port's own
+            at = f"record {int(rec[j])} at row {int(row[j])}"
+            there = f"row {int(prow[j])}" + (f" of record {int(prec[j])}" if prec[j] != rec[j] else "")      # the previous access, where it lies
+            if head.write is not None and w[j] > 1:
                 raise ReferenceError(f"{at}: write flag {int(w[j])}, not 0 or 1")
             if paged and outside[j]:
                 raise ReferenceError(f"{at}: address {int(addr[j])} outside the image of {W} words")
             if paged and unlisted[j]:
-                page_at = f"record {R} at row {int(rows[j])}: address {int(addr[j])} is page {int(page[j])} of the trace, but "
+                page_at = f"record {R} at row {int(row[j])}: address {int(addr[j])} is page {int(page[j])} of the trace, but "
                 raise ReferenceError(page_at + (f"the page table has {len(table)} rows" if page[j] >= len(table) else
                                                 f"row {int(page[j])} of the page table holds address {int(table[page[j], 0])}"))
             if paged and not linked[j] and clock[j] == 0:
                 raise ReferenceError(f"{at}: clock 0 is the image's")
-            if r.write is not None and d[j] >= 0 and d[j] >> (L * nl) == 0:
-                e = next(e for e in range(1, len(r.carried)) if misread[e - 1][j])
+            if head.write is not None and d[j] >= 0 and d[j] >> (L * nl) == 0:
+                e = next(e for e in range(1, len(carried)) if misread[e - 1][j])
                 raise ReferenceError(f"{at}: a load of carried column {e} returns {int(now[e][j])}, but " + (
-                    f"{int(before[e][j])} was last stored (row {int(prow[j])})" if linked[j] else
+                    f"{int(before[e][j])} was last stored ({there})" if linked[j] else
                     f"the image holds {int(before[e][j])} at its address {int(addr[j])}" if paged else "its address was never accessed: the value must be 0"))
             if d[j] < 0:
-                raise ReferenceError(f"{at}: clock not increasing ({int(clock[j])} after {int(pclock[j])} at row {int(prow[j])})")
-            after = f"after row {int(prow[j])}" if linked[j] else "after the image"
+                raise ReferenceError(f"{at}: clock not increasing ({int(clock[j])} after {int(pclock[j])} at {there})")
+            after = f"after {there}" if linked[j] else "after the image"
             raise ReferenceError(f"{at}: the clock difference {int(d[j])} ({after}) does not fit {nl} limbs of {L} bits")
-        vals = [np.where(linked, groups[g][c, prow], word if paged and e == 1 else 0).astype(np.uint32) for e, (g, c) in enumerate(r.carried)]
-        writes.append((list(r.dsts), slice(0, A), 0))
-        writes.append((r.linked, rows, _enc(linked.astype(np.uint64)).astype(np.uint32)))
-        writes.append((r.last, rows, _enc(last.astype(np.uint64)).astype(np.uint32)))
-        writes += [(c, rows, v) for c, v in zip(r.prevs, vals)]
-        writes += [(c, rows, _enc((d >> (j * L)) & ((1 << L) - 1)).astype(np.uint32)) for j, c in enumerate(r.limbs)]
+        vals = [np.where(linked, take(cols, prow, pport), word if paged and e == 1 else 0).astype(np.uint32) for e, cols in enumerate(carried)]
+        for q, (_, r) in enumerate(ports):                                   # destinations stay per record: port q writes its own columns
+            mine = port == q
+            rows = row[mine]
+            writes.append((list(r.dsts), slice(0, A), 0))
+            writes.append((r.linked, rows, _enc(linked[mine].astype(np.uint64)).astype(np.uint32)))
+            writes.append((r.last, rows, _enc(last[mine].astype(np.uint64)).astype(np.uint32)))
+            writes += [(c, rows, v[mine]) for c, v in zip(r.prevs, vals)]
+            writes += [(c, rows, _enc((d[mine] >> (j * L)) & ((1 << L) - 1)).astype(np.uint32)) for j, c in enumerate(r.limbs)]
         if paged:                                                            # the page table: the distinct addresses in order
-            first, final = rows[~linked], rows[last]                         # the first and the last access of every address ...
-            first, final = first[np.argsort(addr[~linked], kind="stable")], final[np.argsort(addr[last], kind="stable")]       # ... by address
-            a = np.sort(addr[~linked])
+            first, final = np.nonzero(~linked)[0], np.nonzero(last)[0]       # the first and the last access of every address ...
+            first, final = first[np.argsort(addr[first], kind="stable")], final[np.argsort(addr[final], kind="stable")]       # ... by address
+            a = addr[first]
             D, Lp, ng = a.size, pages.limb_bits, pages.ng
             wide = a >> (Lp * ng) != 0
             if wide.any():
-                j = int(np.argmin(np.where(wide, first, A)))                 # the PAGES record comes last: any LINK's refusal goes first
-                late = f"record {args.records.index(pages)} at row {int(first[j])}: address {int(a[j])} does not fit {ng} limbs of {Lp} bits"
+                j = int(np.min(first[wide]))                             # the lowest (row, port): the accesses are in that order
+                late = f"record {args.records.index(pages)} at row {int(row[j])}: address {int(addr[j])} does not fit {ng} limbs of {Lp} bits"
+                continue                                                     # the PAGES record comes last: any LINK's refusal goes first
+            if D > A:                                                        # only with ports: k A accesses may touch more than A addresses
+                late = f"record {args.records.index(pages)}: the trace pages {D} addresses, but the page table has the {A} active rows"
                 continue
             gap = np.zeros(D, dtype=np.int64)
             gap[1:] = a[1:] - a[:-1] - 1
             top = slice(0, D)
             writes.append((list(pages.dsts), slice(0, A), 0))
             writes.append((pages.p_on, top, np.uint32(_R)))
-            writes.append((pages.p_addr, top, groups[r.key[0]][r.key[1], first]))
+            writes.append((pages.p_addr, top, take(keys, row[first], port[first])))
             writes.append((pages.p_in, top, image[a] if table is None else table[:D, 1]))
-            writes.append((pages.p_out, top, groups[r.carried[1][0]][r.carried[1][1], final]))
-            writes.append((pages.p_time, top, groups[g0][c0, final]))
+            writes.append((pages.p_out, top, take(carried[1], row[final], port[final])))
+            writes.append((pages.p_time, top, take(carried[0], row[final], port[final])))
             for j in range(ng):
                 writes.append((pages.alimbs[j], top, _enc((a >> (j * Lp)) & ((1 << Lp) - 1)).astype(np.uint32)))
                 writes.append((pages.gaps[j], top, _enc((gap >> (j * Lp)) & ((1 << Lp) - 1)).astype(np.uint32)))

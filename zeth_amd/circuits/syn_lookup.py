@@ -57,6 +57,13 @@ OPEN bus (logup.py, "THE OPEN BUS"; ZKA1 version 8), ANOTHER description with it
 (p2_page_tied.py) take them off.  out = SYN-LOOKUP-paged's 4 words ‖ alpha ‖ beta ‖ F (16 words): every term reads the two challenges
 from `out`, and the `last` constraint closes on F = logup.table_fingerprint of the page table.  The witness is SYN-LOOKUP-paged's.
 Not a shipped circuit: its control root is zkh_code_root of its code trace.
+SYN-LOOKUP-reads-ported (`build_syn_lookup(shape, link=True, reads=True, ports=True)`): SYN-LOOKUP-reads' description BYTE FOR BYTE, and
+another blob (ZKA1 version 9): the n_mem memory pairs are the PORTS of one memory, pair 0 the head and the others LINK records that join it
+(logup.py, PORTS).  The terms of all pairs carry tag 1, so they were one bus all along; what changes is the witness: a row makes n_mem
+accesses to ONE memory, in port order.  `witness(..., ports=True)` orders the accesses by (row, port), gives access (r, q) the time
+n_mem r + q (+ 1 when paged) and shares one memory across the ports, and the host-made link columns come from one walk over that order.
+`pages=True` with `ports=True` lifts n_mem = 1: the PAGES record names the head, every port's link constraints are the paged ones, and
+the page table's four bus terms stand once for the whole memory.  n_mem A must stay below 2^(order_limbs L).
 """
 from __future__ import annotations
 
@@ -134,7 +141,7 @@ def pages_layout(n_words: int, n_limbs: int, n_mem: int = 1, order_limbs: int = 
 def build_syn_lookup(shape: Shape = FULL, derive: bool = False, sort: bool = False,
                      sort_keys: Tuple[int, ...] = SORT_KEYS, limbs: bool = False, order: bool = False,
                      order_limbs: int = ORDER_LIMBS, link: bool = False, reads: bool = False, pages: bool = False,
-                     tied: bool = False) -> Tuple[np.ndarray, np.ndarray]:
+                     tied: bool = False, ports: bool = False) -> Tuple[np.ndarray, np.ndarray]:
     """-> (ZKC1 description, ZKA1 argument blob); derive: the table term's multiplicity is derived by the library (version-2 blob,
     the description unchanged); sort: every permuted copy is the library's sorted copy of its memory tuple by the tuple positions
     `sort_keys` (version-3 blob, the description unchanged); limbs: every word's limbs are a LIMBS record (version-4 blob, the
@@ -143,13 +150,17 @@ def build_syn_lookup(shape: Shape = FULL, derive: bool = False, sort: bool = Fal
     blob); it has no sorted copy, so it refuses `sort` and `order`; reads: SYN-LOOKUP-reads, SYN-LOOKUP-linked with a write flag per
     memory pair and the read rule (version-6 blob, another description); it needs `link`; pages: SYN-LOOKUP-paged, SYN-LOOKUP-reads
     with its one memory paged in from an image and out again (version-7 blob, another description); it needs `link`, `reads` and n_mem = 1; tied: SYN-LOOKUP-tied, SYN-LOOKUP-paged on the open bus with
-    the page table's rows as one more term (version-8 blob, another description, 16 `out` words); it needs `pages`"""
+    the page table's rows as one more term (version-8 blob, another description, 16 `out` words); it needs `pages`; ports: the n_mem memory
+    pairs are the ports of ONE memory (version-9 blob; without `pages` SYN-LOOKUP-reads' description unchanged); it needs `link` and `reads`,
+    and with it `pages` takes any n_mem"""
     n_words, n_limbs, limb_bits, n_mem = shape
     if tied and not pages:
         raise ValueError("build_syn_lookup: tied=True ties the page table of a paged memory to its page-out: it needs pages=True")
     if pages and not (link and reads):
         raise ValueError("build_syn_lookup: pages=True pages the memory of a LINK record with the read rule: it needs link=True, reads=True")
-    if pages and n_mem != 1:
+    if ports and not (link and reads):
+        raise ValueError("build_syn_lookup: ports=True makes the memory pairs the ports of one memory with the read rule: it needs link=True, reads=True")
+    if pages and n_mem != 1 and not ports:
         raise ValueError(f"build_syn_lookup: pages=True pages one memory: n_mem is {n_mem}")
     if reads and not link:
         raise ValueError("build_syn_lookup: reads=True is the read rule of the LINK records: it needs link=True")
@@ -167,7 +178,7 @@ def build_syn_lookup(shape: Shape = FULL, derive: bool = False, sort: bool = Fal
     pcols = pages_layout(n_words, n_limbs, n_mem, order_limbs) if pages else []
     if pages:
         wd += len(pcols)
-        n_terms += 1 + 2 * order_limbs + bool(tied)
+        n_terms += 2 - n_mem + 2 * order_limbs + bool(tied)                     # a port: its access and its previous one; the table's two terms once
     k = (n_terms + 2) // 3
     if tied:
         b = LogupBuilder((4 * k, N_CODE, wd), (TIED_OUT, 8), alpha=OUT_ALPHA, beta=OUT_BETA, open_bus=(TIE_TAG, OUT_TOTAL))
@@ -188,6 +199,7 @@ def build_syn_lookup(shape: Shape = FULL, derive: bool = False, sort: bool = Fal
     for c_addr, c_val, c_time, c_linked, c_last, c_pval, c_ptime, *_ in lcols if pages else []:
         specs.append(dict(tuple_cols=[(GROUP_DATA, c_addr), (GROUP_DATA, c_val), (GROUP_DATA, c_time)], sign=1, tag=1))
         specs.append(dict(tuple_cols=[(GROUP_DATA, c_addr), (GROUP_DATA, c_pval), (GROUP_DATA, c_ptime)], sign=-1, tag=1))
+    if pages:
         specs.append(dict(tuple_cols=[(GROUP_DATA, pcols[1]), (GROUP_DATA, pcols[2])], sign=1, mult=(GROUP_DATA, pcols[0]), tag=1))
         specs.append(dict(tuple_cols=[(GROUP_DATA, pcols[1]), (GROUP_DATA, pcols[3]), (GROUP_DATA, pcols[4])], sign=-1, mult=(GROUP_DATA, pcols[0]), tag=1))
     for c_addr, c_val, c_time, c_linked, c_last, c_pval, c_ptime, *_ in [] if pages else lcols:
@@ -206,9 +218,10 @@ def build_syn_lookup(shape: Shape = FULL, derive: bool = False, sort: bool = Fal
             b.derive_limbs((GROUP_DATA, words[kk]), limbs[kk], limb_bits)
     records = [b.derive_order([(GROUP_DATA, perm[i][0]), (GROUP_DATA, perm[i][2])], cols, limb_bits) for i, cols in enumerate(ocols)]
     # the clock (time) is carried first, then the value; the destinations in the LINK's order: linked, last, ptime, pval, the limbs
-    links = [b.derive_links(None, (GROUP_DATA, c[0]), [(GROUP_DATA, c[2]), (GROUP_DATA, c[1])], [c[3], c[4], c[6], c[5]] + c[LINK_W:], limb_bits,
-                            write=None if w is None else (GROUP_DATA, w))
-             for c, w in zip(lcols, wcols)]
+    links = []
+    for c, w in zip(lcols, wcols):                                           # ports: pair 0 is the head, the others join its memory
+        links.append(b.derive_links(None, (GROUP_DATA, c[0]), [(GROUP_DATA, c[2]), (GROUP_DATA, c[1])], [c[3], c[4], c[6], c[5]] + c[LINK_W:], limb_bits,
+                                    write=None if w is None else (GROUP_DATA, w), joins=links[0] if ports and links else None))
     table = b.derive_pages(links[0], pcols, limb_bits) if pages else None
     # words = sum of their limbs, on active rows
     inner = b.true()
@@ -302,7 +315,7 @@ def _enc(x) -> np.ndarray:
 
 def witness(shape: Shape, po2: int, zk_cycles: int, seed: int = 1, count: bool = True, sort: bool = True, addr_range: int = 1 << 20,
             sort_keys: Tuple[int, ...] = SORT_KEYS, limbs: bool = True, order=None, order_limbs: int = ORDER_LIMBS, link=None,
-            reads: bool = False, pages=None, image=None):
+            reads: bool = False, pages=None, image=None, ports: bool = False):
     """-> (code, data, out_global) host arrays of raw Montgomery words: random words below min(P, 2^(n_limbs L)) split into limbs
     (limbs=False: zero, for the library to split), the table's multiplicities (count=False: zero, for the library to derive), random
     memory tuples (addresses below `addr_range`) and their copy stably sorted by the tuple positions `sort_keys`, (addr, time)
@@ -319,7 +332,13 @@ def witness(shape: Shape, po2: int, zk_cycles: int, seed: int = 1, count: bool =
     `link`, `reads` and `image`, the W raw Montgomery words of the memory image, each below P): the times are row + 1, the addresses
     below min(addr_range, W), a load takes the last store or else the image's word, an access without a previous one has (pval, ptime) =
     (image word, 0) and the limbs of time - 1, and the page table is host-made by a walk over the sorted distinct addresses (its limbs
-    counted) / left zero for the library"""
+    counted) / left zero for the library.
+    ports: SYN-LOOKUP-reads-ported's witness (`build_syn_lookup(..., ports=True)`; it needs `link` and `reads`): the n_mem pairs are the
+    ports of one memory.  The accesses are ordered by (row, port), access (r, q) has the time n_mem r + q (+ 1 when paged), a load takes
+    what the previous access of ANY port left at its address, and the link columns (and the one page table) are host-made by one walk
+    over that order with a dictionary"""
+    if ports and (link is None or not reads):
+        raise ValueError("witness: ports=True makes the pairs the ports of one memory with the read rule: it needs link= and reads=True")
     if pages is not None and (link is None or not reads or image is None):
         raise ValueError("witness: pages= pages the memory of the LINK record with the read rule: it needs link=, reads=True and image=")
     if reads and link is None:
@@ -337,10 +356,10 @@ def witness(shape: Shape, po2: int, zk_cycles: int, seed: int = 1, count: bool =
     A = n - zk_cycles
     T = 1 << limb_bits
     if pcols:
-        assert n_mem == 1, "one memory is paged"
+        assert n_mem == 1 or ports, "one memory is paged"
         image = np.asarray(image, dtype=np.uint32).reshape(-1)
         assert (image < P).all(), "the witness holds canonical Montgomery words: an image word >= P has no host-made twin"
-        assert A < 1 << (order_limbs * limb_bits), f"times reach {A}: they do not fit {order_limbs} limbs of {limb_bits} bits"
+        assert (n_mem if ports else 1) * A < 1 << (order_limbs * limb_bits), f"times reach {(n_mem if ports else 1) * A}: they do not fit {order_limbs} limbs of {limb_bits} bits"
         held0 = (image.astype(np.uint64) * np.uint64(pow((1 << 32) % P, -1, P)) % np.uint64(P)).tolist()     # the image, canonical
         addr_range = min(addr_range, image.size, 1 << (order_limbs * limb_bits))
     assert A >= T, f"po2 {po2}: {A} active rows do not hold the {T}-row table"
@@ -365,7 +384,9 @@ def witness(shape: Shape, po2: int, zk_cycles: int, seed: int = 1, count: bool =
             if limbs_on:
                 data[limbs[kk][j], :A] = limb
             counts += np.bincount(limb.astype(np.int64), minlength=T)
-    for i in range(n_mem):
+    if ports:
+        _ported_witness(data, rng, lcols, wcols, pcols, held0 if pcols else None, A, addr_range, limb_bits, order_limbs, link, pages, counts)
+    for i in range(0 if ports else n_mem):
         addr = rng.integers(0, addr_range, size=A, dtype=np.uint64)
         val = rng.integers(0, P, size=A, dtype=np.uint64)
         time = rng.permutation(A).astype(np.uint64)
@@ -468,6 +489,54 @@ def _paged_witness(data, cols, pcols, addr, val, image, A, limb_bits, order_limb
     for i, a in enumerate(sorted(seen)):                                     # the page table: one row per distinct address, in order
         gap = a - below - 1 if i else 0
         row = [1, a, image[a], int(val[seen[a]]), int(time[seen[a]])] + [(a >> (j * limb_bits)) & (T - 1) for j in range(order_limbs)] + \
+            [(gap >> (j * limb_bits)) & (T - 1) for j in range(order_limbs)]
+        assert a >> (order_limbs * limb_bits) == 0
+        if fill_pages:
+            data[pcols, i] = row
+        for v in row[PAGE_W:]:
+            counts[v] += 1
+        below = a
+    counts[0] += 2 * order_limbs * (A - len(seen))                           # the rows below the table look their zero limbs up as well
+
+
+def _ported_witness(data, rng, lcols, wcols, pcols, image, A, addr_range, limb_bits, order_limbs, fill, fill_pages, counts):
+    """the k memory pairs of SYN-LOOKUP-reads-ported as the ports of ONE memory, the host's way: one sequential walk over the accesses in
+    (row, port) order with the last access of every address in a dictionary.  image: the paged memory's image (canonical words), or None"""
+    k, T, paged = len(lcols), 1 << limb_bits, image is not None
+    assert k * A < 1 << (order_limbs * limb_bits), f"times reach {k * A}: they do not fit {order_limbs} limbs of {limb_bits} bits"
+    addr = [rng.integers(0, addr_range, size=A, dtype=np.uint64).tolist() for _ in range(k)]
+    val = [rng.integers(0, P, size=A, dtype=np.uint64).tolist() for _ in range(k)]
+    store = [rng.integers(0, 2, size=A, dtype=np.uint64).tolist() for _ in range(k)]
+    seen, first = {}, {}                                                     # address -> (row, port) of its last / first access so far
+    cols = [np.zeros((LINK_W + order_limbs, A), dtype=np.uint64) for _ in range(k)]
+    for r in range(A):
+        for q in range(k):                                                   # the walk: every access after the one before it in (row, port) order
+            a, time = addr[q][r], k * r + q + paged
+            at = seen.get(a)
+            if not store[q][r]:                                              # a load returns what the previous access left, the image's word or 0
+                val[q][r] = val[at[1]][at[0]] if at is not None else image[a] if paged else 0
+            pval, ptime = (val[at[1]][at[0]], k * at[0] + at[1] + paged) if at is not None else (image[a] if paged else 0, 0)
+            d = time - ptime - 1 if at is not None or paged else 0
+            assert 0 <= d < 1 << (order_limbs * limb_bits), "a time difference does not fit the link limbs"
+            limbs = [(d >> (j * limb_bits)) & (T - 1) for j in range(order_limbs)]
+            cols[q][:, r] = [a, val[q][r], time, at is not None, 1, pval, ptime] + limbs
+            if at is not None:
+                cols[at[1]][4, at[0]] = 0                                    # it is no longer the last access of its address
+            for v in limbs:
+                counts[v] += 1
+            first.setdefault(a, (r, q))
+            seen[a] = (r, q)
+    for q in range(k):
+        keep = slice(0, None) if fill else slice(0, 3)                       # addr, val, time are the host's whoever fills the rest
+        data[lcols[q][keep], :A] = cols[q][keep]
+        data[wcols[q], :A] = store[q]
+    if not paged:
+        return
+    below = -1
+    for i, a in enumerate(sorted(seen)):                                     # the page table: one row per distinct address, in order
+        gap = a - below - 1 if i else 0
+        (r, q) = seen[a]
+        row = [1, a, image[a], val[q][r], k * r + q + 1] + [(a >> (j * limb_bits)) & (T - 1) for j in range(order_limbs)] + \
             [(gap >> (j * limb_bits)) & (T - 1) for j in range(order_limbs)]
         assert a >> (order_limbs * limb_bits) == 0
         if fill_pages:

@@ -22,6 +22,7 @@
 // A derive that refuses a witness leaves `data` unchanged: its check pass reduces the lowest bad (record, row) into a BadRow, the host
 // reads that back, and only then does anything write.
 #pragma once
+#include <algorithm>
 #include <vector>
 
 #include "circuit.h"
@@ -38,6 +39,9 @@ constexpr uint32_t KIND_PAGES = 4, PAGES_WORDS = 32, MAX_PAGE_LIMBS = 4, MAX_PAG
 constexpr uint32_t PAGES_BIT = 0x10000;             // header word 7, bit 16 (version 7): the blob has a PAGES record
 constexpr uint32_t OPEN_BIT = 0x20000;              // header word 7, bit 17 (version 8): the blob has an OPEN record
 constexpr uint32_t KIND_OPEN = 5, OPEN_WORDS = 16;  // the OPEN record (version 8): the bus closes on `out` words, not on zero
+constexpr uint32_t LINK_JOINS = 2;                  // LINK word 5, bit 1 (version 9): the record joins the memory of the head that word 31 names
+constexpr uint32_t MAX_PORTS = 8;                   // the records of one memory, the head included
+constexpr uint32_t PORTS_BIT = 0x40000;             // header word 7, bit 18 (version 9): a LINK record joins
 constexpr uint32_t MAX_ORDER_BITS = 29;             // logup.MAX_ORDER_BITS: a negative difference stays out of the limbs' range
 
 // logup.Term as the blob gives it: the fields are the blob's words, checked by the rules of arguments.hip before a circuit keeps them
@@ -67,8 +71,11 @@ struct Link {
     uint32_t cg[MAX_CARRIED], cc[MAX_CARRIED];      // the carried columns, the first nc; c_0 is the clock
     uint32_t dst[MAX_LINK_DSTS];            // destination data columns: linked, last, prev_0 .. prev_{nc-1}, limb_0 .. limb_{nl-1}
     uint32_t n_dst, reserved;               // destinations in use; a word the format reserves was not 0
-    uint32_t flags, wg, wc;                 // version 6: word 5 (bit 0 = READS, LINK_READS) and words 14, 15, the write flag's (group, column)
+    uint32_t flags, wg, wc;                 // version 6: word 5 (bit 0 = READS, LINK_READS; version 9: bit 1 = JOINS) and words 14, 15, the write flag's (group, column)
 };
+// A memory (version 9, PORTS): a run of k consecutive LINK records, the head at place `first` among the LINK records and the records that join
+// it; port q is the record at first + q.  A LINK that nothing joins is a memory of one port.
+struct Memory { uint32_t first, k; };
 // logup.Pages, the PAGES record (version 7), as the blob gives it; the paged kernels of links.hip and the page-out of page_out.hip read it in this form
 struct Pages {
     uint32_t index;                         // its index among all records of the blob (it comes last)
@@ -90,6 +97,7 @@ struct Arguments {
     std::vector<Term> terms;
     std::vector<Record> records;            // the LIMBS / ORDER records: their index here is their index in the blob
     std::vector<Link> links;                // the LINK records
+    std::vector<uint32_t> heads;            // per LINK record (version 9): the blob record index of the head it joins (word 31), NONE: it joins none
     uint32_t late_record = NONE, late_after = 0;    // a LIMBS / ORDER record that follows a LINK record, and that LINK record (refused)
     uint32_t reads = 0;                     // the LINK records with READS (version 6: header word 7)
     std::vector<Pages> pages;               // the PAGES record (version 7; the rules allow one)
@@ -100,6 +108,15 @@ struct Arguments {
     bool second_open = false;               // ... and it is an OPEN record itself
     bool is_open() const { return !open.empty(); }
     bool open_tag(uint32_t tag) const { return !open.empty() && open[0].tag == tag; }
+    bool ports() const { return std::any_of(heads.begin(), heads.end(), [](uint32_t h) { return h != NONE; }); }
+    std::vector<Memory> memories() const {  // the LINK records as memories, in blob order (the rules have made every joiner follow its head's run)
+        std::vector<Memory> m;
+        for (uint32_t p = 0; p < links.size(); p++) {
+            if (heads[p] == NONE || m.empty()) m.push_back(Memory{p, 1});
+            else m.back().k++;
+        }
+        return m;
+    }
     int paged_link() const {                // the place among `links` of the LINK that the PAGES record names, -1: none (or no such LINK)
         for (size_t p = 0; !pages.empty() && p < links.size(); p++)
             if (links[p].index == pages[0].link) return (int)p;

@@ -1,6 +1,6 @@
 // arguments.hip — the ZKA1 argument blob (layout: zeth_amd/circuits/logup.py; DESIGN.md §2 ARGUMENTS): its decoding into
 // zkh::Arguments (terms, from version 4 derived-column records, from version 5 LINK records, from version 6 their read rule, from version 7 the PAGES
-// record, from version 8 the OPEN record), the rules a circuit's arguments keep (check_sorted, check_derived, then check_owned over the LIMBS / ORDER records, over the LINK records
+// record, from version 8 the OPEN record, from version 9 the ports of a memory: LINK records that join a head), the rules a circuit's arguments keep (check_sorted, check_derived, then check_owned over the LIMBS / ORDER records, over the LINK records
 // and over the PAGES record), and the entry points that attach them to a circuit and ask what they derive.
 // decode_arguments is the only code that knows the blob's words; everything else, here and in the consumers, reads decoded terms.
 #include "arguments.h"
@@ -17,7 +17,8 @@ namespace {
 // significant key first); bits 2, 3, 7, the position fields of unused keys and, without bit 1, everything above bit 0 are reserved.
 // A reserved bit is recorded, not refused: the rules refuse it where they reach the term (flag_word_rule), after the circuit-shape checks.
 const char* decode_arguments(const uint32_t* a, size_t words, Arguments* out) {
-    ZKH_REQUIRE(words >= ARGS_HEADER && a[0] == ARGS_MAGIC && a[1] >= 1 && a[1] <= 8 && (a[1] != 6 || a[7] != 0) && (a[1] != 7 || (a[7] & PAGES_BIT)) && (a[1] != 8 || (a[7] & OPEN_BIT)),
+    ZKH_REQUIRE(words >= ARGS_HEADER && a[0] == ARGS_MAGIC && a[1] >= 1 && a[1] <= 9 && (a[1] != 6 || a[7] != 0) && (a[1] != 7 || (a[7] & PAGES_BIT)) && (a[1] != 8 || (a[7] & OPEN_BIT)) &&
+                (a[1] != 9 || (a[7] & PORTS_BIT)),
                 "set_arguments: not a ZKA1 (version 1) argument blob");
     const uint32_t n_terms = a[5], n_records = a[1] >= 4 ? a[6] : 0;            // header word 6: the records of version 4, reserved before
     const size_t rec0 = ARGS_HEADER + (size_t)TERM_WORDS * n_terms;
@@ -60,6 +61,7 @@ const char* decode_arguments(const uint32_t* a, size_t words, Arguments* out) {
     // the READS count and, exactly when the blob holds a PAGES record, bit 16.
     out->records.clear();
     out->links.clear();
+    out->heads.clear();
     out->pages.clear();
     out->open.clear();
     const uint32_t* r = a + rec0;
@@ -98,8 +100,10 @@ const char* decode_arguments(const uint32_t* a, size_t words, Arguments* out) {
             else x.reserved = r[5] | r[14] | r[15];
             out->reads += x.flags & LINK_READS;
             for (uint32_t j = nc; j < MAX_CARRIED; j++) x.reserved |= x.cg[j] | x.cc[j];
-            for (uint32_t j = 16 + x.n_dst; j < LINK_WORDS; j++) x.reserved |= r[j];
+            const bool joins = out->version >= 9 && (x.flags & LINK_JOINS);      // version 9: bit 1 of word 5, and word 31 names the head
+            for (uint32_t j = 16 + x.n_dst; j < LINK_WORDS - (joins ? 1 : 0); j++) x.reserved |= r[j];
             out->links.push_back(x);
+            out->heads.push_back(joins ? r[LINK_WORDS - 1] : NONE);
             r += LINK_WORDS;
             continue;
         }
@@ -116,11 +120,15 @@ const char* decode_arguments(const uint32_t* a, size_t words, Arguments* out) {
         r += RECORD_WORDS;
     }
     const bool paged = out->version == 7 || (out->version >= 8 && (a[7] & PAGES_BIT));
-    const uint32_t word7 = (paged ? a[7] ^ PAGES_BIT : a[7]) ^ (out->version >= 8 ? OPEN_BIT : 0);     // bit 16 says PAGES, bit 17 OPEN, the rest counts as before
+    const bool opened = out->version == 8 || (out->version >= 9 && (a[7] & OPEN_BIT));
+    // bit 16 says PAGES, bit 17 OPEN, bit 18 (version 9) PORTS, the rest counts as before
+    const uint32_t word7 = (paged ? a[7] ^ PAGES_BIT : a[7]) ^ (opened ? OPEN_BIT : 0) ^ (out->version >= 9 ? PORTS_BIT : 0);
     ZKH_REQUIRE(out->version < 6 || word7 == out->reads, "set_arguments: header word 7 is %u, the blob has %u LINK records with READS", word7, out->reads);
     ZKH_REQUIRE(!paged || !out->pages.empty(), "set_arguments: header word 7 has bit 16 (PAGES), but the blob has no PAGES record");
     ZKH_REQUIRE(out->version < 8 || paged || out->pages.empty(), "set_arguments: the blob has a PAGES record, but header word 7 lacks bit 16 (PAGES)");
-    ZKH_REQUIRE(out->version < 8 || !out->open.empty(), "set_arguments: header word 7 has bit 17 (OPEN), but the blob has no OPEN record");
+    ZKH_REQUIRE(!opened || !out->open.empty(), "set_arguments: header word 7 has bit 17 (OPEN), but the blob has no OPEN record");
+    ZKH_REQUIRE(out->version < 9 || opened || out->open.empty(), "set_arguments: the blob has an OPEN record, but header word 7 lacks bit 17 (OPEN)");
+    ZKH_REQUIRE(out->version < 9 || out->ports(), "set_arguments: header word 7 has bit 18 (PORTS), but no LINK record joins");
     return nullptr;
 }
 
@@ -274,18 +282,35 @@ const char* columns_clause_a(const Record& r, uint32_t i) {
 }
 // logup.check_links' own clause (a): the ranges of nc, L, nl, the flag word and the write flag's words (version 6), the reserved words, and the
 // selector a code column
-const char* links_clause_a(const zkh_circuit* c, const Link& r) {
+const char* links_clause_a(const zkh_circuit* c, const Arguments& a, const Link& r) {
     const uint32_t i = r.index;
     ZKH_REQUIRE(r.nc >= 1 && r.nc <= MAX_CARRIED && r.L >= 1 && r.L <= 16 && r.nl <= MAX_LINK_LIMBS && r.L * r.nl <= MAX_ORDER_BITS,
                 "set_arguments: record %u: a LINK of %u carried columns and %u limbs of %u bits (1..%u carried columns, 0..%u limbs of 1..16 bits, at most "
                 "%u bits in all)", i, r.nc, r.nl, r.L, MAX_CARRIED, MAX_LINK_LIMBS, MAX_ORDER_BITS);
-    ZKH_REQUIRE(r.flags <= LINK_READS, "set_arguments: record %u: word 5 of a LINK is %#x (bit 0: READS, the read rule; the other bits are reserved)", i, r.flags);
-    ZKH_REQUIRE(r.flags || !(r.wg | r.wc), "set_arguments: record %u: words 14, 15 of a LINK name a write flag, but bit 0 of word 5 (READS) is not set", i);
-    ZKH_REQUIRE(!r.flags || r.nc >= 2, "set_arguments: record %u: READS needs a clock and a value column (2..%u carried columns), this LINK carries %u", i,
+    ZKH_REQUIRE(a.version < 9 || r.flags <= (LINK_READS | LINK_JOINS), "set_arguments: record %u: word 5 of a LINK is %#x (bit 0: READS, the read rule; bit 1: JOINS, "
+                "a port of its head's memory; the other bits are reserved)", i, r.flags);
+    ZKH_REQUIRE(a.version >= 9 || r.flags <= LINK_READS, "set_arguments: record %u: word 5 of a LINK is %#x (bit 0: READS, the read rule; the other bits are reserved)", i, r.flags);
+    ZKH_REQUIRE((r.flags & LINK_READS) || !(r.wg | r.wc), "set_arguments: record %u: words 14, 15 of a LINK name a write flag, but bit 0 of word 5 (READS) is not set", i);
+    ZKH_REQUIRE(!(r.flags & LINK_READS) || r.nc >= 2, "set_arguments: record %u: READS needs a clock and a value column (2..%u carried columns), this LINK carries %u", i,
                 MAX_CARRIED, r.nc);
     ZKH_REQUIRE(!r.reserved, "set_arguments: record %u: a reserved word of a LINK is not 0 (words 5, 14, 15, the unused carried pairs and the unused "
                 "destination words)", i);
     ZKH_REQUIRE(r.sel == NONE || r.sel < c->group_size[GROUP_CODE], "set_arguments: record %u: selector %u is not a code column", i, r.sel);
+    // logup._joins_rule (version 9): a joiner's head is a LINK record without JOINS before it, the records between them join the same head
+    // (the records of a blob that reaches this rule are in their order: whatever lies between two LINK records is a LINK record), it has the
+    // head's nc, L, nl and READS-ness, and a memory has at most MAX_PORTS records
+    const uint32_t h = a.heads[&r - a.links.data()];
+    if (h == NONE) return nullptr;
+    const Link* head = nullptr;
+    for (size_t p = 0; p < a.links.size(); p++)
+        if (a.links[p].index == h && h < i && a.heads[p] == NONE) head = &a.links[p];
+    ZKH_REQUIRE(head, "set_arguments: record %u: a LINK joins record %u, which is no LINK record without JOINS before it (a port joins the head of its memory)", i, h);
+    for (size_t p = 0; p < a.links.size(); p++)
+        ZKH_REQUIRE(a.links[p].index <= h || a.links[p].index >= i || a.heads[p] == h, "set_arguments: record %u: a LINK joins record %u, but record %u between them "
+                    "does not (a memory is a run of consecutive LINK records)", i, h, a.links[p].index);
+    ZKH_REQUIRE(r.nc == head->nc && r.L == head->L && r.nl == head->nl && (r.flags & LINK_READS) == (head->flags & LINK_READS), "set_arguments: record %u: a LINK joins "
+                "record %u with another nc, L, nl or READS (the ports of a memory have their head's)", i, h);
+    ZKH_REQUIRE(i - h < MAX_PORTS, "set_arguments: record %u: port %u of the memory of record %u (a memory has at most %u records)", i, i - h, h, MAX_PORTS);
     return nullptr;
 }
 
@@ -297,6 +322,8 @@ const char* pages_clause_a(const Arguments& a, const Pages& g) {
     ZKH_REQUIRE(!g.reserved, "set_arguments: record %u: a reserved word of a PAGES record is not 0 (words 4..15 and the unused destination words)", i);
     ZKH_REQUIRE(paged_link(a, g), "set_arguments: record %u: a PAGES record pages record %u, which is no LINK record with READS and two carried columns (a clock "
                 "and one value)", i, g.link);
+    const uint32_t h = a.heads[paged_link(a, g) - a.links.data()];
+    ZKH_REQUIRE(h == NONE, "set_arguments: record %u: a PAGES record pages record %u, which joins record %u (a PAGES record names the head of a memory)", i, g.link, h);
     return nullptr;
 }
 
@@ -319,7 +346,7 @@ const char* check_owned(const zkh_circuit* c, const Arguments& a, const std::vec
     for (size_t p = lo; p < top; p++) {
         const Owned& v = all[p];
         const uint32_t i = v.index;
-        ZKH_TRY(kind == 2 ? pages_clause_a(a, a.pages[p - n_link]) : links ? links_clause_a(c, a.links[p - n_rec]) : columns_clause_a(a.records[p], i));
+        ZKH_TRY(kind == 2 ? pages_clause_a(a, a.pages[p - n_link]) : links ? links_clause_a(c, a, a.links[p - n_rec]) : columns_clause_a(a.records[p], i));
         for (uint32_t s = 0; s < v.n_src; s++)
             ZKH_REQUIRE(is_column(c, v.sg[s], v.sc[s]), "set_arguments: record %u: source (%u, %u) is not a code or data column", i, v.sg[s], v.sc[s]);
         for (uint32_t e = 0; e < v.n_dst; e++) {

@@ -57,7 +57,17 @@
 // a head whose page the table does not have ("the page table has D rows"), a head whose row of the table holds another address, both
 // tested on the row after "outside the image" and before the clock; and, when no row is refused, a table of more rows than the trace pages,
 // which the host reads off the scan's total (it comes back in the check pass's one read-back).  The table is only read.
+//
+// PORTS (a LINK record with JOINS, ZKA1 version 9; `reference_links`' merged order): a memory is a run of k <= 8 consecutive records, the head
+// and the records that join it, and its accesses are the (row, port) whose record's selector is 1, in that order.  sort_rows sorts a MEMORY's
+// accesses as one run (sort.h: one lane per virtual row v = row k + port, the masks per memory), so position t holds (packed key, v) in (key,
+// row, port) order and the neighbours t - 1 and t + 1 still give linked, head and tail.  k_links<.., kPorts> runs over memories (grid.y): the
+// lane's record is links[first + v % k] and its row v / k, the previous access's record and row those of the neighbour's v; sources and
+// destinations are the lane's own port's, the previous cells the neighbour's port's.  The record's fields are then per lane, not uniform:
+// only this instantiation pays for that, a blob without a joiner runs the instantiations it always ran.  The refused (record, row) is the
+// port's own record's, a 64-bit minimum per wave.  The page scan, head_rank and k_page_of run over the memory's run.
 #include <algorithm>
+#include <cstdio>
 #include <functional>
 
 #include "scan.h"
@@ -82,8 +92,15 @@ struct Paging {
     uint32_t rows;                                      // PAGED_TABLE: the table's rows
     const uint32_t *local, *sums;                       // the page scan: k_page_heads' local indices; D and the workgroups' carries
 };
+// what the ported passes of k_links (kPorts) read on top: the memories, the items a run can hold (sort.h SortedRows::cap) and the number of
+// LINK records, under which the PAGES record's own refusal is reported; the other passes get a zeroed one and read none of it
+struct Ports {
+    const Memory* runs;
+    uint32_t cap, records;
+};
 
-// grid ceil(m_max / LINK_THREADS) over the sorted positions of the paged record (its place p among the LINK records): the heads stage
+// grid ceil(m_max / LINK_THREADS) over the sorted positions of the paged record (its place p among the LINK records; with ports: the paged
+// memory's place among the memories, and A the items a run can hold): the heads stage
 __global__ __launch_bounds__(LINK_THREADS) void k_page_heads(const uint32_t* __restrict__ status, const unsigned long long* __restrict__ keys, uint32_t p, uint32_t A,
                                                              uint32_t* __restrict__ local, uint32_t* __restrict__ sums) {
     __shared__ uint32_t buf[2][LINK_THREADS];
@@ -102,17 +119,23 @@ __global__ __launch_bounds__(LINK_THREADS) void k_page_heads(const uint32_t* __r
 // the constant 0, and nothing of `pa` is read.  kPaged = PAGED_TABLE: the image's word of a head is its row's of the page table, and a head that the
 // table does not list is refused.  The record's words are read through the uniform pointer (scalar loads): nothing is indexed
 // in registers.
-template <bool kWrite, bool kReads, int kPaged>
+// kPorts (the blob has a LINK that joins): grid (ceil(cap / LINK_THREADS), memories), blockIdx.y the memory and `pages` whether it is the
+// paged one; the item's source id v gives the lane its own record, links[first + v % k], and its row v / k, the neighbour's v the record and
+// row of the previous access (`prec`, prow): the record's words are per-lane loads here, and nowhere else.
+template <bool kWrite, bool kReads, int kPaged, bool kPorts = false>
 __global__ __launch_bounds__(LINK_THREADS) void k_links(const uint32_t* __restrict__ code, uint32_t* data, const Link* __restrict__ links,
                                                         const uint32_t* __restrict__ status, const unsigned long long* __restrict__ keys,
                                                         const uint32_t* __restrict__ rows, uint32_t n, uint32_t A, unsigned long long* __restrict__ bad,
-                                                        const Paging pa) {
+                                                        const Paging pa, const Ports po) {
     const uint32_t p = blockIdx.y;
-    const Link* __restrict__ rec = links + p;
+    const Link* const first = links + (kPorts ? po.runs[p].first : p);      // kPorts: the memory's head, port 0
+    const uint32_t k = kPorts ? po.runs[p].k : 1;
+    const Link* __restrict__ rec = first;                                    // the lane's record; kPorts: its own port's, once its item is read
+    const Link* __restrict__ prec = first;                                   // the record of the access before it: kPorts: the neighbour's port's
     const bool pages = kPaged != PAGED_NO && p == pa.paged;
-    const uint32_t m = status[ST_HEAD + ST_WORDS * p + ST_M];                 // the record's accesses: m <= A
+    const uint32_t m = status[ST_HEAD + ST_WORDS * p + ST_M];                 // the record's accesses: m <= A (kPorts: the memory's, m <= k A)
     const uint32_t t = blockIdx.x * LINK_THREADS + threadIdx.x;             // a sorted position (t < m) and, in the write pass, a row (t < A)
-    const size_t base = (size_t)p * A;
+    const size_t base = (size_t)p * (kPorts ? po.cap : A);
     const bool access = t < m;
     uint32_t row = 0, prow = 0;
     bool linked = false, last = false;
@@ -124,12 +147,20 @@ __global__ __launch_bounds__(LINK_THREADS) void k_links(const uint32_t* __restri
             prow = rows[base + t - 1];                    // linked: the previous access; a head of the paged record: the last access of the address below
         }
         last = t + 1 >= m || keys[base + t + 1] != key;
+        if constexpr (kPorts) {                           // the source ids are virtual rows v = row k + port
+            const uint32_t v = row, pv = prow;
+            row = v / k;
+            rec = first + (v - row * k);
+            prow = pv / k;
+            prec = first + (pv - prow * k);
+        }
     }
     const bool from_image = pages && access && !linked;  // an unlinked access of the paged record: the image is its previous access, at clock 0
     long long d = 0;
     if (linked || from_image) {
         const uint32_t* clock = group_ptr(code, data, rec->cg[0]) + (size_t)rec->cc[0] * n;
-        d = (long long)canonical(clock[row]) - (linked ? canonical(clock[prow]) : 0) - 1;       // clock 0 is the image's: d = -1 refuses it
+        const uint32_t* pclock = kPorts ? group_ptr(code, data, prec->cg[0]) + (size_t)prec->cc[0] * n : clock;
+        d = (long long)canonical(clock[row]) - (linked ? canonical(pclock[prow]) : 0) - 1;      // clock 0 is the image's: d = -1 refuses it
     }
     uint32_t addr = 0, word = 0;                          // the paged record's access: its address and, in range, the image's word
     bool inside = true;
@@ -156,12 +187,24 @@ __global__ __launch_bounds__(LINK_THREADS) void k_links(const uint32_t* __restri
                     const uint32_t nc = rec->nc;
                     for (uint32_t j = 1; j < nc; j++) {
                         const uint32_t* col = group_ptr(code, data, rec->cg[j]) + (size_t)rec->cc[j] * n;
-                        ok &= col[row] % P == (linked ? col[prow] % P : word % P);
+                        const uint32_t* pcol = kPorts ? group_ptr(code, data, prec->cg[j]) + (size_t)prec->cc[j] * n : col;
+                        ok &= col[row] % P == (linked ? pcol[prow] % P : word % P);
                     }
                 }
                 if (!ok) mine = row;
             }
         }
+        if constexpr (kPorts) {                           // the record is the lane's own port's: the wave's minimum over (record, row), 64 bits
+            unsigned long long worst = mine == NONE ? ~0ull : ((unsigned long long)(rec - links) << 32) | mine;
+            if (__ballot(mine != NONE) != 0) {
+#pragma unroll
+                for (int off = 32; off > 0; off >>= 1) {
+                    const unsigned long long o = __shfl_xor(worst, off, 64);
+                    worst = o < worst ? o : worst;
+                }
+                if ((threadIdx.x & 63) == 0) atomicMin(bad, worst);
+            }
+        } else
         // report_bad_row (arguments.h) written out: through the helper this kernel's argument loads are scheduled otherwise
         if (__ballot(mine != NONE) != 0) {                // wave-uniform: only a wave that found one reduces and writes
 #pragma unroll
@@ -171,12 +214,18 @@ __global__ __launch_bounds__(LINK_THREADS) void k_links(const uint32_t* __restri
             }
             if ((threadIdx.x & 63) == 0) atomicMin(bad, ((unsigned long long)p << 32) | mine);
         }
-        if (pages) report_bad_row(bad, gridDim.y, access && (addr >> (pa.pg->L * pa.pg->ng)) != 0 ? row : NONE);     // an address the limbs do not hold
-        if constexpr (kPaged == PAGED_TABLE)              // the trace's pages ride back with the refused row (BadRow's third word): one lane, no read-back of its own
+        if (pages) report_bad_row(bad, kPorts ? po.records : gridDim.y, access && (addr >> (pa.pg->L * pa.pg->ng)) != 0 ? row : NONE);     // an address the limbs do not hold
+        if constexpr (kPaged == PAGED_TABLE || (kPorts && kPaged != PAGED_NO))    // the trace's pages ride back with the refused row (BadRow's third word): one lane, no read-back of its own
             if (pages && t == 0) ((uint32_t*)bad)[2] = pa.sums[PG_TOTAL];
         return;
     }
     const uint32_t nc = rec->nc, n_dst = rec->n_dst;
+    if constexpr (kPorts) {                               // lane t is also the virtual row t: port t % k at row t / k, zeroed where it is no access
+        const uint32_t zrow = t / k;
+        const Link* __restrict__ z = first + (t - zrow * k);
+        if (zrow < A && z->sel != NONE && sel_class(code, z->sel, n, zrow) != 1)
+            for (uint32_t e = 0; e < z->n_dst; e++) data[(size_t)z->dst[e] * n + zrow] = 0;
+    } else
     if (rec->sel != NONE && t < A && sel_class(code, rec->sel, n, t) != 1)
         for (uint32_t e = 0; e < n_dst; e++) data[(size_t)rec->dst[e] * n + t] = 0;
     if (pages) {                                          // the page table
@@ -184,7 +233,7 @@ __global__ __launch_bounds__(LINK_THREADS) void k_links(const uint32_t* __restri
         const uint32_t D = pa.sums[PG_TOTAL];
         if (t >= D && t < A)                              // the rows below the table, coalesced
             for (uint32_t e = 0; e < pg->n_dst; e++) data[(size_t)pg->dst[e] * n + t] = 0;
-        if (access && (!linked || last)) {
+        if (access && (!linked || last)) {                // (with ports the host has refused a trace of more than A pages: i < A)
             const uint32_t i = head_rank(pa.local, pa.sums + 1, t);            // the page of t's address: the heads up to t, less one
             const uint32_t Lp = pg->L, ng = pg->ng, maskp = (1u << Lp) - 1;
             if (!linked) {                                // the head: the first access of the address
@@ -192,7 +241,8 @@ __global__ __launch_bounds__(LINK_THREADS) void k_links(const uint32_t* __restri
                 data[(size_t)pg->dst[PG_ON] * n + i] = R1;
                 data[(size_t)pg->dst[PG_ADDR] * n + i] = keycol[row];
                 data[(size_t)pg->dst[PG_IN] * n + i] = word;
-                const uint32_t gap = t ? addr - canonical(keycol[prow]) - 1 : 0;
+                const uint32_t* pkeycol = kPorts ? group_ptr(code, data, prec->kg) + (size_t)prec->kc * n : keycol;
+                const uint32_t gap = t ? addr - canonical(pkeycol[prow]) - 1 : 0;
                 for (uint32_t j = 0; j < ng; j++) {
                     data[(size_t)pg->dst[PG_LIMBS + j] * n + i] = fp_encode((addr >> (j * Lp)) & maskp).v;
                     data[(size_t)pg->dst[PG_LIMBS + ng + j] * n + i] = fp_encode((gap >> (j * Lp)) & maskp).v;
@@ -208,31 +258,42 @@ __global__ __launch_bounds__(LINK_THREADS) void k_links(const uint32_t* __restri
     data[(size_t)rec->dst[0] * n + row] = linked ? R1 : 0;
     data[(size_t)rec->dst[1] * n + row] = last ? R1 : 0;
     for (uint32_t j = 0; j < nc; j++)                     // the previous access's cells; an unlinked access: 0, and the image's word for the paged value
-        data[(size_t)rec->dst[2 + j] * n + row] = linked ? group_ptr(code, data, rec->cg[j])[(size_t)rec->cc[j] * n + prow] : j == 1 ? word : 0;
+        data[(size_t)rec->dst[2 + j] * n + row] = linked ? group_ptr(code, data, prec->cg[j])[(size_t)prec->cc[j] * n + prow] : j == 1 ? word : 0;
     const uint32_t mask = (1u << L) - 1;                  // L <= 16
     for (uint32_t j = 0; j < nl; j++)
         data[(size_t)rec->dst[2 + nc + j] * n + row] = fp_encode((uint32_t)((unsigned long long)d >> (j * L)) & mask).v;
 }
 
-// Which rule the refused access `row` of the LINK record r broke, as the reference names it (pages: r is the paged record, and `image` its
-// image): the access and its previous one are found on the host as the reference finds them, from the key and the selector of rows [0, row].
+// Which rule the refused access `row` of the LINK record r = links[place] broke, as the reference names it (pages: r is a port of the paged memory,
+// and `image` its image): the access and its previous one are found on the host as the reference finds them, from the keys and the selectors of
+// the memory's ports (`mem`: r's memory, one record unless a LINK joins) on rows [0, row], walking back in (row, port) order.
 // With a page table (mem.table) the image's word is the row's of the table: `page_of` gives the page of the refused row, and two words of
 // that row are read; the table is never read back.
-const char* refusal(zkh_ctx* ctx, const zkh_buf* code, const zkh_buf* data, size_t n, const Link& r, uint32_t row, bool pages, const PagedFrom& mem,
-                    uint32_t pages_index, const std::function<const char*(uint32_t*)>& page_of) {
-    std::vector<uint32_t> key(row + 1), sel(row + 1, R1);
-    ZKH_TRY(zkh_read(ctx, r.kg == GROUP_CODE ? code : data, key.data(), (size_t)r.kc * n, row + 1));
-    if (r.sel != NONE) ZKH_TRY(zkh_read(ctx, code, sel.data(), (size_t)r.sel * n, row + 1));
-    uint32_t prow = row;                                  // prow == row: no earlier access has its key (unlinked)
-    for (uint32_t q = row; q-- > 0;)
-        if (sel[q] % P == R1 && key[q] % P == key[row] % P) { prow = q; break; }
-    const bool linked = prow != row;
+const char* refusal(zkh_ctx* ctx, const zkh_buf* code, const zkh_buf* data, size_t n, const std::vector<Link>& links, const Memory& ports, uint32_t place, uint32_t row,
+                    bool pages, const PagedFrom& mem, uint32_t pages_index, const std::function<const char*(uint32_t*)>& page_of) {
+    const Link& r = links[place];
+    const uint32_t port = place - ports.first;
+    std::vector<std::vector<uint32_t>> key(ports.k, std::vector<uint32_t>(row + 1)), sel(ports.k, std::vector<uint32_t>(row + 1, R1));
+    for (uint32_t q = 0; q < ports.k; q++) {
+        const Link& x = links[ports.first + q];
+        ZKH_TRY(zkh_read(ctx, x.kg == GROUP_CODE ? code : data, key[q].data(), (size_t)x.kc * n, row + 1));
+        if (x.sel != NONE) ZKH_TRY(zkh_read(ctx, code, sel[q].data(), (size_t)x.sel * n, row + 1));
+    }
+    uint32_t prow = row, pport = port;                    // (prow, pport) == (row, port): no earlier access has its key (unlinked)
+    for (uint32_t at = row + 1; at-- > 0 && prow == row && pport == port;)
+        for (uint32_t q = at == row ? port : ports.k; q-- > 0;)
+            if (sel[q][at] % P == R1 && key[q][at] % P == key[port][row] % P) { prow = at; pport = q; break; }
+    const bool linked = prow != row || pport != port;
+    const Link& pr = links[ports.first + pport];          // the record of the previous access
+    char there[48];                                       // where it lies: "row R", and "of record Q" when that is not r
+    if (pport != port) snprintf(there, sizeof there, "row %u of record %u", prow, pr.index);
+    else snprintf(there, sizeof there, "row %u", prow);
     if (r.flags & LINK_READS) {
         uint32_t w;
         ZKH_TRY(read_cell(ctx, code, data, r.wg, r.wc, n, row, &w));
         if (w > 1) return make_err("derive_links: record %u at row %u: write flag %u, not 0 or 1: the witness is refused", r.index, row, w);
     }
-    const uint32_t addr = canonical(key[row]);
+    const uint32_t addr = canonical(key[port][row]);
     uint32_t word = 0;                                    // paged: the image's word at the address, canonical
     if (pages) {
         const uint32_t W = (uint32_t)(mem.table ? mem.image_words : mem.image->len);
@@ -256,14 +317,14 @@ const char* refusal(zkh_ctx* ctx, const zkh_buf* code, const zkh_buf* data, size
     if (linked || pages) {
         long long now, before = 0;
         ZKH_TRY(read_cell(ctx, code, data, r.cg[0], r.cc[0], n, row, &now));
-        if (linked) ZKH_TRY(read_cell(ctx, code, data, r.cg[0], r.cc[0], n, prow, &before));
+        if (linked) ZKH_TRY(read_cell(ctx, code, data, pr.cg[0], pr.cc[0], n, prow, &before));
         if (!linked && now == 0) return make_err("derive_links: record %u at row %u: clock 0 is the image's: the witness is refused", r.index, row);
         const long long d = now - before - 1;
         if (d < 0)
-            return make_err("derive_links: record %u at row %u: clock not increasing (%lld after %lld at row %u): the witness is refused", r.index, row, now, before, prow);
+            return make_err("derive_links: record %u at row %u: clock not increasing (%lld after %lld at %s): the witness is refused", r.index, row, now, before, there);
         if ((d >> (r.L * r.nl)) != 0 && linked)
-            return make_err("derive_links: record %u at row %u: the clock difference %lld (after row %u) does not fit %u limbs of %u bits: the witness is refused",
-                            r.index, row, d, prow, r.nl, r.L);
+            return make_err("derive_links: record %u at row %u: the clock difference %lld (after %s) does not fit %u limbs of %u bits: the witness is refused",
+                            r.index, row, d, there, r.nl, r.L);
         if ((d >> (r.L * r.nl)) != 0)
             return make_err("derive_links: record %u at row %u: the clock difference %lld (after the image) does not fit %u limbs of %u bits: the witness is refused",
                             r.index, row, d, r.nl, r.L);
@@ -271,11 +332,11 @@ const char* refusal(zkh_ctx* ctx, const zkh_buf* code, const zkh_buf* data, size
     for (uint32_t j = 1; (r.flags & LINK_READS) && j < r.nc; j++) {     // a load (the write flag is 0, or something above was named)
         uint32_t now, before = pages ? word : 0;
         ZKH_TRY(read_cell(ctx, code, data, r.cg[j], r.cc[j], n, row, &now));
-        if (linked) ZKH_TRY(read_cell(ctx, code, data, r.cg[j], r.cc[j], n, prow, &before));
+        if (linked) ZKH_TRY(read_cell(ctx, code, data, pr.cg[j], pr.cc[j], n, prow, &before));
         if (now == before) continue;
         if (linked)
-            return make_err("derive_links: record %u at row %u: a load of carried column %u returns %u, but %u was last stored (row %u): the witness is refused",
-                            r.index, row, j, now, before, prow);
+            return make_err("derive_links: record %u at row %u: a load of carried column %u returns %u, but %u was last stored (%s): the witness is refused",
+                            r.index, row, j, now, before, there);
         if (pages)
             return make_err("derive_links: record %u at row %u: a load of carried column %u returns %u, but the image holds %u at its address %u: the witness is "
                             "refused", r.index, row, j, now, before, addr);
@@ -285,7 +346,7 @@ const char* refusal(zkh_ctx* ctx, const zkh_buf* code, const zkh_buf* data, size
     return make_err("derive_links: record %u at row %u was refused, but the host finds no rule it breaks", r.index, row);
 }
 
-// grid ceil(A / LINK_THREADS), k_page_heads' geometry (head_rank reads the workgroup's carry): the page of the access `row` of the paged
+// grid ceil(A / LINK_THREADS), k_page_heads' geometry (with ports: p the paged memory, A the items a run can hold, `row` the virtual row) (head_rank reads the workgroup's carry): the page of the access `row` of the paged
 // record, for the host's message about a refused row.  A row is at one sorted position: one writer.
 __global__ __launch_bounds__(LINK_THREADS) void k_page_of(const uint32_t* __restrict__ status, const uint32_t* __restrict__ rows, uint32_t p, uint32_t A, uint32_t row,
                                                           const uint32_t* __restrict__ local, const uint32_t* __restrict__ sums, uint32_t* __restrict__ page) {
@@ -320,6 +381,11 @@ const char* zkh::derive_links_from(zkh_ctx* ctx, const zkh_circuit* c, size_t po
     ZKH_REQUIRE(!paging || tabled || image->len <= 0xffffffffull, "derive_links: an image of %zu words (at most 2^32 - 1)", paging && !tabled ? image->len : 0);
     const int paged = paging ? c->args->paged_link() : -1;
     ZKH_REQUIRE(!paging || paged >= 0, "derive_links: the PAGES record names no LINK record");    // set_arguments has refused such a blob
+    const bool ported = c->args->ports();               // a LINK joins: the passes run over memories, one sort run per memory
+    const std::vector<Memory> mems = c->args->memories();
+    std::vector<uint32_t> mem_of(nr);                   // the memory of every LINK record
+    for (uint32_t g = 0; g < mems.size(); g++)
+        for (uint32_t q = 0; q < mems[g].k; q++) mem_of[mems[g].first + q] = g;
     std::vector<SortPair> pairs(nr, SortPair{});
     for (uint32_t p = 0; p < nr; p++) {                 // the accesses of a record sorted by their key alone: the sort is stable
         pairs[p].d_term = links[p].index; pairs[p].nkeys = 1; pairs[p].sel = links[p].sel;
@@ -328,7 +394,7 @@ const char* zkh::derive_links_from(zkh_ctx* ctx, const zkh_circuit* c, size_t po
     }
     bind_thread(ctx);
     SortedRows sorted;
-    ZKH_TRY(sort_rows(ctx, code, data, n, A, pairs, &sorted));
+    ZKH_TRY(sort_rows(ctx, code, data, n, A, pairs, &sorted, ported ? &mems : nullptr));
     if (sorted.bad_selector) {
         const Link& r = links[sorted.bad_pair];
         uint32_t sel;
@@ -343,51 +409,68 @@ const char* zkh::derive_links_from(zkh_ctx* ctx, const zkh_circuit* c, size_t po
     ZKH_TRY(bad.init(ctx));
     double carried = 0, dsts = 0;
     for (const Link& r : links) { carried += r.nc; dsts += r.n_dst; }
-    const uint32_t nb = (A + LINK_THREADS - 1) / LINK_THREADS;
+    const uint32_t span = ported ? sorted.cap : A;      // the sorted positions of a run; with ports a memory's, at most k A
+    const uint32_t nb = (span + LINK_THREADS - 1) / LINK_THREADS, ny = ported ? (uint32_t)mems.size() : nr;
+    const uint32_t paged_run = paging ? (ported ? mem_of[paged] : (uint32_t)paged) : 0;     // the paged record's run of the sort
+    const Ports po = ported ? Ports{(const Memory*)sorted.runs->ptr(), sorted.cap, nr} : Ports{};
     const bool reads = c->args->reads != 0;             // a record has READS: the check pass with the read rule, over all records
     Paging pa{};
     if (paging) {                                       // every sorted position of the paged record gets its page: a two-level scan of the head flags
         const Pages& g = c->args->pages[0];
         ZKH_TRY(zkh_copy_from(ctx, "pages_record", (const uint32_t*)&g, sizeof(Pages) / 4, dpages.out()));
-        ZKH_TRY(new_buf(ctx, A, false, local.out()));
+        ZKH_TRY(new_buf(ctx, span, false, local.out()));
         ZKH_TRY(new_buf(ctx, 1 + (size_t)nb, false, sums.out()));
-        pa = tabled ? Paging{(const Pages*)dpages->ptr(), (uint32_t)paged, mem.table->ptr() + mem.table_at, (uint32_t)mem.image_words,
+        pa = tabled ? Paging{(const Pages*)dpages->ptr(), paged_run, mem.table->ptr() + mem.table_at, (uint32_t)mem.image_words,
                              (uint32_t)std::min<size_t>(mem.D, 0xffffffffu), local->ptr(), sums->ptr()}       // a trace pages at most A rows: more never match
-                    : Paging{(const Pages*)dpages->ptr(), (uint32_t)paged, image->ptr(), (uint32_t)image->len, 0, local->ptr(), sums->ptr()};
-        ProfScope prof(ctx, "pages_scan", 12.0 * A + 8.0 * nb);            // the keys of every position, its index, the workgroups' totals twice
-        k_page_heads<<<nb, LINK_THREADS, 0, ctx->stream>>>(sorted.status->ptr(), sorted.keys(), (uint32_t)paged, A, local->ptr(), sums->ptr());
+                    : Paging{(const Pages*)dpages->ptr(), paged_run, image->ptr(), (uint32_t)image->len, 0, local->ptr(), sums->ptr()};
+        ProfScope prof(ctx, "pages_scan", 12.0 * span + 8.0 * nb);            // the keys of every position, its index, the workgroups' totals twice
+        k_page_heads<<<nb, LINK_THREADS, 0, ctx->stream>>>(sorted.status->ptr(), sorted.keys(), paged_run, span, local->ptr(), sums->ptr());
         ZKH_TRY(last_launch_error("pages_heads"));
         scan_counters(ctx, sums->ptr() + 1, 1, nb, sums->ptr() + PG_TOTAL, 0);      // the totals become the workgroups' carries, their sum D
         ZKH_TRY(last_launch_error("pages_carry"));
     }
     auto pass = [&](auto* kernel) {
-        kernel<<<dim3(nb, nr), LINK_THREADS, 0, ctx->stream>>>(code->ptr(), data->ptr(), (const Link*)drecs->ptr(), sorted.status->ptr(), sorted.keys(), sorted.rows(),
-                                                              (uint32_t)n, A, bad.ptr(), pa);
+        kernel<<<dim3(nb, ny), LINK_THREADS, 0, ctx->stream>>>(code->ptr(), data->ptr(), (const Link*)drecs->ptr(), sorted.status->ptr(), sorted.keys(), sorted.rows(),
+                                                              (uint32_t)n, A, bad.ptr(), pa, po);
     };
     {
         double cells = 0;                                 // with READS: the write flag and, at most, the value cells at both rows
         for (const Link& r : links) cells += r.flags & LINK_READS ? 1 + 2 * (r.nc - 1) : 0;
         ProfScope prof(ctx, "links_check", (20.0 * nr + 4.0 * cells + (paging ? 8.0 : 0.0)) * A);   // key and row of every item; the clock at both rows; paged: the key and the image's word
-        pass(tabled ? k_links<false, true, PAGED_TABLE> : paging ? k_links<false, true, PAGED_IMAGE> : reads ? k_links<false, true, PAGED_NO> : k_links<false, false, PAGED_NO>);
+        if (ported) pass(tabled ? k_links<false, true, PAGED_TABLE, true> : paging ? k_links<false, true, PAGED_IMAGE, true> : k_links<false, true, PAGED_NO, true>);
+        else pass(tabled ? k_links<false, true, PAGED_TABLE> : paging ? k_links<false, true, PAGED_IMAGE> : reads ? k_links<false, true, PAGED_NO> : k_links<false, false, PAGED_NO>);
         ZKH_TRY(last_launch_error("links_check"));
     }
     ZKH_TRY(bad.read(ctx));
     if (bad.found && bad.hi >= nr) {                    // the PAGES record's own refusal: an address that its limbs do not hold
         const Pages& g = c->args->pages[0];
-        uint32_t a;
-        ZKH_TRY(read_cell(ctx, code, data, links[paged].kg, links[paged].kc, n, bad.lo, &a));
+        uint32_t a = 0;
+        const Memory& ports = mems[mem_of[paged]];      // the row's first port (the lowest (row, port)) whose access has such an address
+        for (uint32_t q = 0; q < ports.k; q++) {
+            const Link& x = links[ports.first + q];
+            uint32_t on = 1;
+            if (x.sel != NONE) ZKH_TRY(read_cell(ctx, code, data, GROUP_CODE, x.sel, n, bad.lo, &on));
+            ZKH_TRY(read_cell(ctx, code, data, x.kg, x.kc, n, bad.lo, &a));
+            if (on == 1 && (a >> (g.L * g.ng)) != 0) break;
+        }
         return make_err("derive_links: record %u at row %u: address %u does not fit %u limbs of %u bits: the witness is refused", g.index, bad.lo, a, g.ng, g.L);
     }
     if (bad.found) {
         const auto page_of = [&](uint32_t* page) -> const char* {      // the refused head's page: one more launch, on a refusal only
             Tmp at;
             ZKH_TRY(new_buf(ctx, 1, true, at.out()));
-            k_page_of<<<nb, LINK_THREADS, 0, ctx->stream>>>(sorted.status->ptr(), sorted.rows(), (uint32_t)paged, A, bad.lo, pa.local, pa.sums, at->ptr());
+            const Memory& ports = mems[mem_of[paged]];  // the refused access's source id: its virtual row
+            k_page_of<<<nb, LINK_THREADS, 0, ctx->stream>>>(sorted.status->ptr(), sorted.rows(), paged_run, span, bad.lo * ports.k + (bad.hi - ports.first), pa.local, pa.sums,
+                                                            at->ptr());
             ZKH_TRY(last_launch_error("links_page_of"));
             return zkh_read(ctx, at, page, 0, 1);
         };
-        return refusal(ctx, code, data, n, links[bad.hi], bad.lo, (int)bad.hi == paged, mem, paging ? c->args->pages[0].index : 0, page_of);
+        return refusal(ctx, code, data, n, links, mems[mem_of[bad.hi]], bad.hi, bad.lo, paging && mem_of[bad.hi] == mem_of[paged], mem, paging ? c->args->pages[0].index : 0,
+                       page_of);
     }
+    // with ports a memory has up to k A accesses, and their distinct addresses may be more than the A rows its page table has
+    ZKH_REQUIRE(!(ported && paging) || bad.extra <= A, "derive_links: record %u: the trace pages %u addresses, but the page table has the %u active rows: the witness is refused",
+                c->args->pages[0].index, bad.extra, A);
     if (tabled) {                                       // no row is refused: every head is listed, so the table has at least the trace's pages
         const uint32_t D = bad.extra;                   // the scan's total, which the check pass sent back with its verdict
         ZKH_REQUIRE(D == mem.D, "derive_links: record %u: the trace pages %u addresses, but the page table has %zu rows: the witness is refused", c->args->pages[0].index,
@@ -395,7 +478,8 @@ const char* zkh::derive_links_from(zkh_ctx* ctx, const zkh_circuit* c, size_t po
     }
     {
         ProfScope prof(ctx, "links_write", (20.0 * nr + 4.0 * carried + 4.0 * dsts + (paging ? 12.0 + 4.0 * c->args->pages[0].n_dst : 0.0)) * A);
-        pass(tabled ? k_links<true, false, PAGED_TABLE> : paging ? k_links<true, false, PAGED_IMAGE> : k_links<true, false, PAGED_NO>);
+        if (ported) pass(tabled ? k_links<true, false, PAGED_TABLE, true> : paging ? k_links<true, false, PAGED_IMAGE, true> : k_links<true, false, PAGED_NO, true>);
+        else pass(tabled ? k_links<true, false, PAGED_TABLE> : paging ? k_links<true, false, PAGED_IMAGE> : k_links<true, false, PAGED_NO>);
         ZKH_TRY(last_launch_error("links_write"));
     }
     // the temporaries go back to the pool on return: the stream orders their next use after these launches

@@ -52,27 +52,36 @@ __device__ __forceinline__ uint32_t extract_bits(uint32_t v, uint32_t mask) {
     return out;
 }
 
-// (a) grid (ceil(A / (SORT_THREADS * KEYS_ROUNDS)), pairs).  selcnt: groups words per pair
+// (a) grid (ceil(A / (SORT_THREADS * KEYS_ROUNDS)), pairs).  selcnt: groups words per pair.
+// kPorts (a run holds the accesses of the k pairs from runs[run].first on: the ports of one memory, links.hip): grid (ceil(cap / ..), runs), one
+// lane per VIRTUAL ROW v = row * k + port, so that the ballot compaction ranks a run's items in (row, port) order; the selector and the key
+// are the port's own pair's, the counts, the rank and the OR / AND masks the run's: packed keys of different ports are comparable.
+template <bool kPorts>
 __global__ __launch_bounds__(SORT_THREADS) void k_sort_keys(const uint32_t* __restrict__ code, const uint32_t* __restrict__ data,
                                                            const SortPair* __restrict__ pairs, uint32_t n, uint32_t A, uint32_t groups,
-                                                           uint32_t* __restrict__ selcnt, uint32_t* __restrict__ status) {
+                                                           uint32_t* __restrict__ selcnt, uint32_t* __restrict__ status,
+                                                           const Memory* __restrict__ runs, uint32_t cap) {
     __shared__ uint32_t red[2 * MAX_SORT_KEYS];
     const uint32_t p = blockIdx.y;
-    const SortPair t = pairs[p];
+    const uint32_t first = kPorts ? runs[p].first : p, k = kPorts ? runs[p].k : 1;
+    const SortPair t = pairs[first];
     if (threadIdx.x < 2 * MAX_SORT_KEYS) red[threadIdx.x] = threadIdx.x < MAX_SORT_KEYS ? 0u : ~0u;
     __syncthreads();
     uint32_t vor[MAX_SORT_KEYS] = {0, 0, 0}, vand[MAX_SORT_KEYS] = {~0u, ~0u, ~0u};
     for (uint32_t j = 0; j < KEYS_ROUNDS; j++) {
-        const uint32_t r = (blockIdx.x * KEYS_ROUNDS + j) * SORT_THREADS + threadIdx.x;      // a wave = one 64-row group
-        const uint32_t cls = r < A ? sel_class(code, t.sel, n, r) : 0;
-        if (cls == 2) atomicMin((unsigned long long*)status, ((unsigned long long)p << 32) | r);
+        const uint32_t at = (blockIdx.x * KEYS_ROUNDS + j) * SORT_THREADS + threadIdx.x;     // a wave = one 64-row group
+        uint32_t r = at, pair = p;
+        if constexpr (kPorts) { r = at / k; pair = first + (at - r * k); }
+        const SortPair& u = kPorts ? pairs[pair] : t;    // the lane's pair: its port's
+        const uint32_t cls = r < A ? sel_class(code, u.sel, n, r) : 0;
+        if (cls == 2) atomicMin((unsigned long long*)status, ((unsigned long long)pair << 32) | r);
         const unsigned long long on = __ballot(cls == 1);
-        if ((threadIdx.x & 63) == 0 && r < A) selcnt[(size_t)p * groups + r / 64] = __popcll(on);
+        if ((threadIdx.x & 63) == 0 && at < (kPorts ? cap : A)) selcnt[(size_t)p * groups + at / 64] = __popcll(on);
         if (cls == 1) {
 #pragma unroll
             for (uint32_t f = 0; f < MAX_SORT_KEYS; f++) {
-                if (f < t.nkeys) {
-                    const uint32_t v = fp_decode(Fp::raw(cell(code, data, t.kg[f], t.kc[f], n, r)));
+                if (f < u.nkeys) {
+                    const uint32_t v = fp_decode(Fp::raw(cell(code, data, u.kg[f], u.kc[f], n, r)));
                     vor[f] |= v;
                     vand[f] &= v;
                 }
@@ -109,20 +118,28 @@ __global__ __launch_bounds__(SCAN_THREADS) void k_sort_scan(uint32_t* __restrict
     if (total && t == SCAN_THREADS - 1) total[(size_t)blockIdx.x * total_stride] = incl;
 }
 
-// (b) grid (ceil(A / SORT_THREADS), pairs): the packed key and the source row of every selected row, at its rank
-template <bool kWide>
+// (b) grid (ceil(A / SORT_THREADS), pairs): the packed key and the source row of every selected row, at its rank.
+// kPorts: grid (ceil(cap / SORT_THREADS), runs), one lane per virtual row v = row * k + port as in k_sort_keys; the item's source id is v,
+// and run p's items start at p * cap.
+template <bool kWide, bool kPorts>
 __global__ __launch_bounds__(SORT_THREADS) void k_sort_pack(const uint32_t* __restrict__ code, const uint32_t* __restrict__ data,
                                                            const SortPair* __restrict__ pairs, uint32_t n, uint32_t A, uint32_t groups,
                                                            const uint32_t* __restrict__ selbase, const uint32_t* __restrict__ status,
                                                            unsigned long long* __restrict__ klo, uint32_t* __restrict__ khi,
-                                                           uint32_t* __restrict__ idx) {
+                                                           uint32_t* __restrict__ idx, const Memory* __restrict__ runs, uint32_t cap) {
     const uint32_t p = blockIdx.y;
-    const SortPair t = pairs[p];
-    const uint32_t r = blockIdx.x * SORT_THREADS + threadIdx.x;
+    const uint32_t at0 = blockIdx.x * SORT_THREADS + threadIdx.x;
+    uint32_t r = at0, pair = p;
+    if constexpr (kPorts) {
+        const uint32_t k = runs[p].k;
+        r = at0 / k;
+        pair = runs[p].first + (at0 - r * k);
+    }
+    const SortPair t = pairs[pair];
     const bool on = r < A && sel_class(code, t.sel, n, r) == 1;
     const unsigned long long mask = __ballot(on);
     if (!on) return;
-    const uint32_t rank = selbase[(size_t)p * groups + r / 64] + __popcll(mask & ((1ull << (threadIdx.x & 63)) - 1));
+    const uint32_t rank = selbase[(size_t)p * groups + at0 / 64] + __popcll(mask & ((1ull << (threadIdx.x & 63)) - 1));
     const uint32_t* st = status + ST_HEAD + ST_WORDS * p;
     unsigned long long lo = 0;
     uint32_t hi = 0;
@@ -138,10 +155,10 @@ __global__ __launch_bounds__(SORT_THREADS) void k_sort_pack(const uint32_t* __re
             }
         }
     }
-    const size_t at = (size_t)p * A + rank;
+    const size_t at = (size_t)p * (kPorts ? cap : A) + rank;
     klo[at] = lo;
     if (kWide) khi[at] = hi;
-    idx[at] = r;
+    idx[at] = at0;
 }
 
 template <bool kWide>
@@ -273,12 +290,22 @@ void zkh::scan_counters(zkh_ctx* ctx, uint32_t* v, uint32_t segments, uint32_t l
 }
 
 // (a) .. (c) for both callers.  The launches, uploads and read-back of a call are a function of (pairs, A) and the live key bits alone.
-const char* zkh::sort_rows(zkh_ctx* ctx, const zkh_buf* code, const zkh_buf* data, size_t n, uint32_t A, const std::vector<SortPair>& pairs, SortedRows* out) {
-    const uint32_t np = (uint32_t)pairs.size();
+// With `runs` (the memories of links.hip: run r holds the accesses of the runs[r].k pairs from runs[r].first on) every "pair" of the launches
+// below is a run of capacity cap = kmax * A items, kmax the most ports of a run: the histogram, offsets and scatter kernels see runs of `cap`
+// items where they saw pairs of A, and only the keys and the pack kernels know what a port is.  Without it cap = A and np = the pairs.
+const char* zkh::sort_rows(zkh_ctx* ctx, const zkh_buf* code, const zkh_buf* data, size_t n, uint32_t A0, const std::vector<SortPair>& pairs, SortedRows* out,
+                           const std::vector<Memory>* runs) {
+    const uint32_t np = runs ? (uint32_t)runs->size() : (uint32_t)pairs.size();
+    uint32_t kmax = 1;
+    for (uint32_t r = 0; runs && r < np; r++) kmax = std::max(kmax, (*runs)[r].k);
+    const uint32_t A = out->cap = kmax * A0;             // the items a run can hold (A0 <= 2^24 rows, kmax <= MAX_PORTS)
     const uint32_t groups = out->groups = (A + 63) / 64, tiles = (A + SORT_TILE - 1) / SORT_TILE;
     static_assert(sizeof(SortPair) % 4 == 0, "word records");
     Tmp &dtab = out->pairs, &status = out->status, &selcnt = out->selbase;
     ZKH_TRY(zkh_copy_from(ctx, "sort_pairs", (const uint32_t*)pairs.data(), pairs.size() * (sizeof(SortPair) / 4), dtab.out()));
+    static_assert(sizeof(Memory) == 8, "word records");
+    if (runs) ZKH_TRY(zkh_copy_from(ctx, "sort_runs", (const uint32_t*)runs->data(), runs->size() * 2, out->runs.out()));
+    const Memory* d_runs = runs ? (const Memory*)out->runs->ptr() : nullptr;
     const size_t st_words = ST_HEAD + (size_t)ST_WORDS * np;
     std::vector<uint32_t>& st = out->st;
     st.assign(st_words, 0);
@@ -289,12 +316,19 @@ const char* zkh::sort_rows(zkh_ctx* ctx, const zkh_buf* code, const zkh_buf* dat
     ZKH_TRY(new_buf(ctx, (size_t)np * groups, false, selcnt.out()));
     const SortPair* d_pairs = (const SortPair*)dtab->ptr();
     const unsigned rows_x = (unsigned)((A + SORT_THREADS - 1) / SORT_THREADS);
-    double key_words = 0;
+    double key_words = 0;                                // the ProfScope bytes count the rows read and the items a run can have, k A0, not its capacity
     for (const SortPair& q : pairs) key_words += q.nkeys + (q.sel != NONE);
+    double alg_items = 0;
+    for (uint32_t r = 0; r < np; r++) alg_items += (double)(runs ? (*runs)[r].k : 1) * A0;
     {
-        ProfScope prof(ctx, "sort_keys", 4.0 * key_words * A);
+        ProfScope prof(ctx, "sort_keys", 4.0 * key_words * A0);
         const unsigned bx = (unsigned)((A + SORT_THREADS * KEYS_ROUNDS - 1) / (SORT_THREADS * KEYS_ROUNDS));
-        k_sort_keys<<<dim3(bx, np), SORT_THREADS, 0, ctx->stream>>>(code->ptr(), data->ptr(), d_pairs, (uint32_t)n, A, groups, selcnt->ptr(), status->ptr());
+        if (runs)
+            k_sort_keys<true><<<dim3(bx, np), SORT_THREADS, 0, ctx->stream>>>(code->ptr(), data->ptr(), d_pairs, (uint32_t)n, A0, groups, selcnt->ptr(), status->ptr(),
+                                                                              d_runs, A);
+        else
+            k_sort_keys<false><<<dim3(bx, np), SORT_THREADS, 0, ctx->stream>>>(code->ptr(), data->ptr(), d_pairs, (uint32_t)n, A, groups, selcnt->ptr(), status->ptr(),
+                                                                               nullptr, A);
         scan_counters(ctx, selcnt->ptr(), np, groups, status->ptr() + ST_HEAD + ST_M, ST_WORDS);
         ZKH_TRY(last_launch_error("sort_keys"));
     }
@@ -309,7 +343,7 @@ const char* zkh::sort_rows(zkh_ctx* ctx, const zkh_buf* code, const zkh_buf* dat
     for (uint32_t p = 0; p < np; p++) {
         uint32_t b = 0;
         const uint32_t* s = st.data() + ST_HEAD + ST_WORDS * p;
-        for (uint32_t f = 0; f < pairs[p].nkeys; f++) b += (uint32_t)__builtin_popcount(s[ST_OR + f] & ~s[ST_AND + f]);
+        for (uint32_t f = 0; f < pairs[runs ? (*runs)[p].first : p].nkeys; f++) b += (uint32_t)__builtin_popcount(s[ST_OR + f] & ~s[ST_AND + f]);
         bits = std::max(bits, b);
     }
     const bool wide = out->wide = bits > 64;
@@ -323,13 +357,13 @@ const char* zkh::sort_rows(zkh_ctx* ctx, const zkh_buf* code, const zkh_buf* dat
     }
     auto lo_of = [&](int i) { return (unsigned long long*)klo[i]->ptr(); };
     {
-        ProfScope prof(ctx, "sort_pack", 4.0 * key_words * A + (wide ? 16.0 : 12.0) * items);
-        if (wide)
-            k_sort_pack<true><<<dim3(rows_x, np), SORT_THREADS, 0, ctx->stream>>>(code->ptr(), data->ptr(), d_pairs, (uint32_t)n, A, groups, selcnt->ptr(),
-                                                                               status->ptr(), lo_of(0), khi[0]->ptr(), idx[0]->ptr());
-        else
-            k_sort_pack<false><<<dim3(rows_x, np), SORT_THREADS, 0, ctx->stream>>>(code->ptr(), data->ptr(), d_pairs, (uint32_t)n, A, groups, selcnt->ptr(),
-                                                                                status->ptr(), lo_of(0), khi[0]->ptr(), idx[0]->ptr());
+        ProfScope prof(ctx, "sort_pack", 4.0 * key_words * A0 + (wide ? 16.0 : 12.0) * alg_items);
+        auto pack = [&](auto* kernel, uint32_t rows) {
+            kernel<<<dim3(rows_x, np), SORT_THREADS, 0, ctx->stream>>>(code->ptr(), data->ptr(), d_pairs, (uint32_t)n, rows, groups, selcnt->ptr(), status->ptr(), lo_of(0),
+                                                                      khi[0]->ptr(), idx[0]->ptr(), d_runs, A);
+        };
+        if (runs) pack(wide ? k_sort_pack<true, true> : k_sort_pack<false, true>, A0);
+        else pack(wide ? k_sort_pack<true, false> : k_sort_pack<false, false>, A);
         ZKH_TRY(last_launch_error("sort_pack"));
     }
     int cur = 0;
@@ -337,7 +371,7 @@ const char* zkh::sort_rows(zkh_ctx* ctx, const zkh_buf* code, const zkh_buf* dat
         ZKH_TRY(new_buf(ctx, (size_t)np * SORT_BINS * tiles, false, hist.out()));
         ZKH_TRY(new_buf(ctx, (size_t)passes * np * SORT_BINS, true, totals.out()));       // the bin totals of every pass, zeroed once
         // per pass: the items read twice and written once, the counters written, scanned and read
-        ProfScope prof(ctx, "sort_passes", passes * (3.0 * (wide ? 16.0 : 12.0) * items + 16.0 * np * SORT_BINS * tiles));
+        ProfScope prof(ctx, "sort_passes", passes * (3.0 * (wide ? 16.0 : 12.0) * alg_items + 16.0 * np * SORT_BINS * tiles));
         for (uint32_t d = 0; d < passes; d++, cur ^= 1) {
             const dim3 grid(tiles, np);
             uint32_t* tot = totals->ptr() + (size_t)d * np * SORT_BINS;

@@ -961,7 +961,8 @@ class HipHal:
         _check(_lib.zkh_derive_all_paged(self.ctx, circuit.h, po2, zk_cycles, code.h, data.h, None if image is None else image.h))
 
     def derive_links_paged(self, circuit: Circuit, po2: int, zk_cycles: int, code: Buffer, data: Buffer, image: Optional[Buffer]) -> None:
-        """derive_links from a memory image (zkh_derive_links_paged): an unlinked access of the paged LINK record takes image[address] as
+        """derive_links from a memory image (zkh_derive_links_paged): an unlinked access of the paged LINK record (with ZKA1 version 9: of any
+        port of the paged memory) takes image[address] as
         its previous access, and the PAGES record's page table is written.  Raises HalError as derive_links does, and on an address
         outside the image, a clock 0 and an unlinked load that does not return the image's word (`data` is then unchanged).  Without a
         PAGES record the image is ignored"""
