@@ -412,8 +412,26 @@ const char* zkh_derive_links(zkh_ctx*, const zkh_circuit*, size_t po2, size_t zk
  * Before any launch: "a table of D rows of 3 words at word T does not fit a buffer of N words"; "an image of W words (1 .. 2^32 - 1)".  A
  * refusal leaves `data` unchanged; `table` and `code` are only read, rows [A, n) never touched; for a message the host reads single words of
  * the table, never the table.  Without a PAGES record the table is ignored (NULL or not) and the call is the plain one; with one, a NULL
- * table is refused ("a page table is required"). */
+ * table is refused ("a page table is required").
+ * WIDE (ZKA1 version 10; versions 1..9 are word for word what they were): a paged memory of V = 2 value words per address, the two 16-bit
+ * halves of a 32-bit machine word.  The PAGES record may name a LINK with READS and nc = 3 (a clock and two value columns; its ports, if
+ * any, carry the same).  PAGES word 4 holds V - 1 (0 in every earlier blob; a value that is not the LINK's nc - 2 is refused), and the
+ * record has 3 + 2 V + 2 ng destinations: p_on, p_addr, p_in_0 .. p_in_{V-1}, p_out_0 .. p_out_{V-1}, p_time, alimb_*, gap_*.  Header word 7
+ * carries bit 19 (WIDE) exactly when V = 2: a version-10 blob without it is no ZKA1 blob, and bit 19 with V = 1 is refused; bits 16, 17
+ * and 18 are set exactly when the blob holds a PAGES record, an OPEN record, a LINK that joins.  zkh_circuit_page_words: V, and 0 without
+ * a PAGES record.  THE IMAGE IS FLAT: V W raw Montgomery words, word j of address a at image[V a + j]; a length that is no multiple of V
+ * is refused before any launch ("an image of N words is not a whole number of addresses of V value words"), and "address A outside the
+ * image of W words" counts W in addresses.  An unlinked access takes prev_{1+j} = image[V a + j] and prev_0 = 0, an unlinked load must
+ * return both words (residues; a refusal names the lowest j first); the head of page i writes p_in_j = image[V a_i + j], the tail
+ * p_out_j from its value columns.  zkh_page_out sets image[V a_i + j] = p_out_j[i].  THE FLAT TABLE: to the tree update, the ZKU1
+ * proof, the walk, ZKN1 and the page-out circuits a wide page table of D rows is the table of V D rows (V a_i + j, in_j, out_j), i
+ * major, j minor: strictly increasing flat addresses over the flat image, so none of them knows V, and zkh_image_proof_words is asked
+ * about (V W, V D).  The proof's fourth refusal says "p_in word j X at address A" when V = 2.  zkh_derive_links_paged_table takes the flat
+ * table: D counts its flat rows and image_words the flat image's words, the head of page i reads rows V i + j and checks each address
+ * against V a + j, the trace's D' pages must meet V D' rows, and the three table refusals name the flat row.  The tie of a wide memory
+ * (kinds 8 and 9) is not built: its table's rows on the open bus would need flat-address columns in the trace. */
 int zkh_circuit_pages(const zkh_circuit*);
+int zkh_circuit_page_words(const zkh_circuit*);
 const char* zkh_derive_links_paged(zkh_ctx*, const zkh_circuit*, size_t po2, size_t zk_cycles, const zkh_buf* code, zkh_buf* data, const zkh_buf* image);
 const char* zkh_derive_links_paged_table(zkh_ctx*, const zkh_circuit*, size_t po2, size_t zk_cycles, const zkh_buf* code, zkh_buf* data, const zkh_buf* table,
                                          size_t table_at, size_t D, size_t image_words);

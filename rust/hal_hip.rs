@@ -392,6 +392,12 @@ impl HipCircuitHal {
         unsafe { sys::zkh_circuit_pages(self.circuit) != 0 }
     }
 
+    /// V, the value words per address of the paged memory (`zkh_circuit_page_words`): 0 without a PAGES record, else 1 or (ZKA1
+    /// version 10: the paged LINK carries two values) 2.  The image is then V W words, word j of address a at V a + j.
+    pub fn page_words(&self) -> usize {
+        unsafe { sys::zkh_circuit_page_words(self.circuit) as usize }
+    }
+
     /// `derive_links` from a memory image of raw Montgomery words (`zkh_derive_links_paged`): an unlinked access of the paged LINK
     /// record takes `image[address]` as its previous access (at clock 0), and the PAGES record's page table is written.  Panics on a
     /// refused witness as `derive_links` does, and on an address outside the image, a clock 0 or an unlinked load that does not return

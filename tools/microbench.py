@@ -30,7 +30,8 @@ zkh_image_proof_walk and part 0's witness from the dirty nodes next to part 0's 
 the words of the table, of the proof and of the two trees, and the copy of the tree that keep_before makes; M30: held commitments, a
 whole tied group on M28's setup sealed in two passes next to the same group with hold_bytes for everything, alternating, and for one
 part zkh_commit_data + zkh_prove_begin_held next to zkh_data_root + zkh_prove_begin, with the bytes held; M32: zkh_derive_links on three memory pairs as the PORTS of one memory (ZKA1 version 9) next to the version-6 blob of three separate
-memories; M31: paging in from a page
+memories; M33: WIDE (ZKA1 version 10), zkh_derive_links_paged and zkh_page_out_tree on SYN-LOOKUP-paged-wide FULL (two value words per address)
+next to SYN-LOOKUP-paged FULL on the same addresses and clocks, alternating; M31: paging in from a page
 table, zkh_derive_links_paged_table next to zkh_derive_links_paged on the same SYN-LOOKUP-paged FULL trace at two image sizes, alternating,
 with both calls' passes) on one MI355X, through the C ABI (HipHal).
 
@@ -1768,6 +1769,70 @@ def main() -> None:
         med = {k: float(np.median(v)) for k, v in t.items()}
         print(json.dumps({"bench": "M32", "circuit": "SYN-LOOKUP-reads FULL widened to 3 memory pairs", "po2": args.po2, "accesses": 3 * A, "addresses_below": 1 << 20,
                           "runs": runs, "reps": args.reps, **arms, "ports_vs_separate": round(med["ports_v9"] / med["separate_v6"], 3)}), flush=True)
+        del keep
+    if want("M33"):
+        # WIDE (ZKA1 version 10): what the second value word costs.  SYN-LOOKUP-paged-wide FULL (two value words per address, the image 2 W
+        # words) next to SYN-LOOKUP-paged FULL in the same run, the same library, on the same addresses, write flags and clocks (the witnesses
+        # of one seed): zkh_derive_links_paged, and zkh_page_out_tree into a committed image (the wide one lays out the flat table of 2 D rows
+        # first and its tree has twice the leaves).  Timed in alternation, `runs` windows of `reps` calls; median and spread (min, max) of
+        # the windows; then the passes by their events.  No threshold.
+        from zeth_amd.circuits import logup, syn_lookup
+        runs, zk = 7, 1994
+        A = n - zk
+        shape, W = syn_lookup.FULL, 1 << 20
+        image_w = rand_fp(np.random.default_rng(33), 2 * W)
+        spread = lambda ts: {"median_ms": round(float(np.median(ts)) * 1e3, 4), "min_ms": round(min(ts) * 1e3, 4), "max_ms": round(max(ts) * 1e3, 4)}   # noqa: E731
+        arms, fns, keep, pages = {}, [], [], {}
+        for name, wide in (("wide_v10", True), ("narrow_v7", False)):
+            desc, blob = syn_lookup.build_syn_lookup(shape, link=True, reads=True, pages=True, wide=wide)
+            pargs = logup.Arguments.parse(blob)
+            assert int(blob[1]) == (10 if wide else 7)
+            image_h = image_w if wide else image_w[:W].copy()
+            code_h, full_h, _out = syn_lookup.witness(shape, args.po2, zk, seed=33, link=True, reads=True, pages=True, image=image_h, wide=wide)
+            circuit = hal.load_circuit(desc, jit=False)
+            circuit.set_arguments(blob)
+            assert circuit.page_words() == (2 if wide else 1)
+            bare_h = full_h.reshape(-1, n).copy()
+            bare_h[circuit.derived_data_columns(), :A] = 0
+            code, data, image = hal.alloc_elem("code", code_h.size), hal.alloc_elem("data", bare_h.size), hal.alloc_elem("image", image_h.size)
+            paged = hal.alloc_elem("image_out", image_h.size)                # the page-out's own image and tree: the derive pages in from the first image every time
+            code.write(code_h)
+            data.write(bare_h.reshape(-1))
+            image.write(image_h)
+            paged.write(image_h)
+            nodes = hal.image_commit(paged)
+            derive = lambda circuit=circuit, code=code, data=data, image=image: hal.derive_links_paged(circuit, args.po2, zk, code, data, image)      # noqa: E731
+            out = lambda circuit=circuit, data=data, image=paged, nodes=nodes: hal.page_out_tree(circuit, args.po2, zk, data, image, nodes)         # noqa: E731  (after the first call it rewrites what is there)
+            derive()
+            lk = [c for r in pargs.records if isinstance(r, (logup.Link, logup.Pages)) for c in r.dsts]
+            assert np.array_equal(data.to_vec().reshape(-1, n)[lk], full_h.reshape(-1, n)[lk]), f"{name}: the derived columns differ from the host-made ones"
+            out()
+            assert np.array_equal(paged.to_vec(), logup.reference_page_out(pargs, args.po2, zk, full_h, image_h)), f"{name}: the image differs from the twin's"
+            assert np.array_equal(nodes.to_vec(), hal.image_commit(paged).to_vec()), f"{name}: the updated tree is not the fresh commit's"
+            pages[name] = int((full_h.reshape(-1, n)[pargs.pages.p_on, :A] != 0).sum())
+            fns += [(name + ".derive_links_paged", derive), (name + ".page_out_tree", out)]
+            keep.append((circuit, code, data, image, paged, nodes))
+            del code_h, full_h, bare_h
+        assert pages["wide_v10"] == pages["narrow_v7"], "the two witnesses page the same addresses"
+        t = {name: [] for name, _ in fns}
+        for _ in range(runs):
+            for name, fn in fns:
+                t[name].append(timed(hal, fn, args.reps))
+        for name, fn in fns:
+            hal.prof_enable(True)
+            hal.prof_reset()
+            for _ in range(args.reps):
+                fn()
+            hal.sync()
+            steps = {r["name"]: round(r["total_ms"] / max(r["calls"], 1), 4) for r in hal.prof_get()
+                     if r["calls"] and r["name"].startswith(("sort_", "links_", "pages_", "page_out_", "image_"))}
+            hal.prof_enable(False)
+            arms[name] = {**spread(t[name]), "steps_ms": steps}
+        med = {k: float(np.median(v)) for k, v in t.items()}
+        print(json.dumps({"bench": "M33", "circuit": "SYN-LOOKUP-paged-wide FULL next to SYN-LOOKUP-paged FULL", "po2": args.po2, "accesses": A, "pages": pages["wide_v10"],
+                          "image_addresses": W, "runs": runs, "reps": args.reps, **arms,
+                          "derive_wide_vs_narrow": round(med["wide_v10.derive_links_paged"] / med["narrow_v7.derive_links_paged"], 3),
+                          "page_out_tree_wide_vs_narrow": round(med["wide_v10.page_out_tree"] / med["narrow_v7.page_out_tree"], 3)}), flush=True)
         del keep
     hal.close()
 

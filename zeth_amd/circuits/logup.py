@@ -24,7 +24,7 @@ The degree of a column's constraint is 1 (gate) + max(1 + t, max_i(deg sel_i + d
 
 ZKA1 layout (u32 words; canonical integers, not Montgomery words)::
 
-    [0] magic 'ZKA1' = 0x5a4b4131   [1] version = 1 .. 9      [2] k = accum Fp4 columns   [3] alpha mix word offset
+    [0] magic 'ZKA1' = 0x5a4b4131   [1] version = 1 .. 10     [2] k = accum Fp4 columns   [3] alpha mix word offset
     [4] beta mix word offset       [5] n_terms       [6] reserved = 0 (version 4: n_records)
     [7] reserved = 0 (version 6: the number of LINK records with READS, at least 1; version 7: that number | 0x10000)
     terms: n_terms x 16 words, sorted by column:
@@ -72,6 +72,15 @@ ZKA1 layout (u32 words; canonical integers, not Montgomery words)::
       PAGES record | 0x20000 exactly when it holds an OPEN record | 0x40000 (bit 18, PORTS) exactly when a LINK joins: a version-9 blob
       without bit 18 is no ZKA1 blob, bit 18 with no joining record is refused.  The builder writes version 9 only when a record joins
       (`derive_links(..., joins=head)`).
+
+    Version 10: version 9's layout, and the PAGES record may page a memory of V = 2 VALUE WORDS per address: it may name a LINK with READS
+      and nc = 3 (a clock and two value columns; its ports, if any, share the head's nc as they must).  PAGES word [4] holds V - 1: 0 means
+      one word, which is what every earlier blob holds there; a value above 1, and one that is not the LINK's nc - 2, is refused.  The
+      record has 3 + 2 V + 2 ng destinations, in this order: p_on, p_addr, p_in_0 .. p_in_{V-1}, p_out_0 .. p_out_{V-1}, p_time, alimb_*,
+      gap_* (V = 2 and ng = 4: 15 of the 16 slots).  Header word 7 = (the READS count) | bits 16, 17, 18 exactly when the blob holds a PAGES
+      record, an OPEN record, a LINK that joins | 0x80000 (bit 19, WIDE) exactly when V = 2: a version-10 blob without bit 19 is no ZKA1
+      blob, bit 19 with V = 1 is refused.  The builder writes version 10 only then (`derive_pages` on a LINK that carries two values takes
+      the wider destination list).
 
 PORTS (a LINK record with JOINS, ZKA1 version 9): several accesses per row to ONE memory.  A memory is a run of k <= 8 consecutive LINK
 records: the head, then the records that join it, in blob order; port q is the record at head + q, and every port has the head's nc, L, nl
@@ -164,7 +173,23 @@ order of causes decides when several apply, and this module's `check_page_out_pr
 THE DIRTY-NODE TABLE, ZKN1 (`reference_page_out_nodes`, `image_dirty_words`; zkh_image_proof_nodes, zkh_image_dirty_words; csrc/zkn1.h):
 the walk keeping what it recomputes: per layer the heap ids of the dirty nodes and, per node, its two children old and new, which is
 what a P2-TREE block of any part reads (zkh_page_tree_witgen_nodes), so a part is sealed from (proof, root_before) without the trees.
-Left out: sessions do not thread an image, and a blob pages one memory of one value word per address.  The circuits that check p_in /
+WIDE (the PAGES record with V = 2, ZKA1 version 10): BabyBear is a 31-bit field, so a 32-bit machine word is two field elements, and the
+paged memory holds V value words per address, V the paged LINK's nc - 1 (1 or 2).  Everything above is V = 1; with V = 2, stated once:
+  * THE IMAGE is V W raw Montgomery words, FLAT: word j of address a is image[V a + j].  An image whose length is no multiple of V is
+    refused before anything else ("an image of N words is not a whole number of addresses of V value words"); a >= W is refused with
+    the text above, W counted in addresses.
+  * An unlinked access of the paged memory takes prev_{1+j} = image[V a + j] (copies) and prev_0 = 0; an unlinked load must return both
+    words, compared as residues, and a refusal names the lowest j first, as the read rule does.
+  * THE PAGE TABLE: the head access writes p_in_j = image[V a_i + j], the tail access p_out_j from its own record's value columns.
+  * PAGE-OUT sets image[V a_i + j] = p_out_j[i].  The proof's fourth rule: p_in_j is the word the tree's leaf layer holds at V a_i + j
+    ("p_in word j X at address A" in its text only when V = 2).
+  * THE FLAT TABLE.  To everything behind the page-out (the tree's update, ZKU1, the walk, ZKN1, the page-out circuits) a wide page table
+    of D rows is the table of V D rows (V a_i + j, in_j, out_j), i major, j minor: strictly increasing flat addresses over a flat image
+    of V W words.  None of that code knows V; image_proof_words is asked about (V W, V D).
+  * PAGING FROM A TABLE: `table` is the flat one and image_words the flat image's.  The head of page i reads rows V i .. V i + V - 1 and
+    checks each row's address against V a + j; D pages of the trace must meet V D rows.  The three table refusals keep their shape and
+    name the flat row.
+Left out: one paged memory per blob; the tie of a wide memory.  The circuits that check p_in /
 p_out against those roots are the page-out circuits (p2_page.py and after it), and THE OPEN BUS below ties their rows to this table.
 
 WHO WRITES A DATA COLUMN (`_check_owned` behind `check_columns` and `check_links`; csrc/arguments.h says the same).  A data column
@@ -472,52 +497,65 @@ def check_links(terms: Sequence[Term], records: Sequence, group_sizes=None) -> O
 KIND_PAGES = 4
 PAGES_WORDS = 32
 MAX_PAGE_LIMBS = 4
+MAX_PAGE_WORDS = 2                             # V, the value words per address of a paged memory (version 10: 1 or 2)
 PAGES_BIT = 0x10000                            # header word 7, bit 16 (version 7): the blob has a PAGES record
+WIDE_BIT = 0x80000                             # header word 7, bit 19 (version 10): the PAGES record pages two value words per address
 
 
 @dataclass(frozen=True)
 class Pages:
-    """A PAGES record as the blob holds it (ZKA1 version 7): the fields are the blob's words, `check_pages` the rules"""
+    """A PAGES record as the blob holds it (ZKA1 version 7; version 10: `nv`): the fields are the blob's words, `check_pages` the rules"""
     limb_bits: int                             # L
     ng: int                                    # limbs of a page address and of a gap
     link: int                                  # the blob record index of the LINK record it pages
-    dsts: Tuple[int, ...]                      # data columns: p_on, p_addr, p_in, p_out, p_time, alimb_0 .. alimb_{ng-1}, gap_0 .. gap_{ng-1}
+    dsts: Tuple[int, ...]                      # data columns: p_on, p_addr, p_in_0 .., p_out_0 .., p_time, alimb_0 .. alimb_{ng-1}, gap_0 .. gap_{ng-1}
     reserved: bool = False                     # a word the format reserves was not 0 (parser only)
+    nv: int = 1                                # V, the value words per address (version 10: word 4 holds V - 1); the paged LINK's nc - 1
+    nv_word: Optional[int] = None              # the blob's word 4 where it is above 1 (parser only, version 10)
+    wide_word: bool = field(default=False, compare=False)    # the blob's version reads word 4 as V - 1 (parser only: the text of the reserved words' refusal)
     kind = KIND_PAGES
 
     p_on = property(lambda self: self.dsts[0])
     p_addr = property(lambda self: self.dsts[1])
     p_in = property(lambda self: self.dsts[2])
-    p_out = property(lambda self: self.dsts[3])
-    p_time = property(lambda self: self.dsts[4])
-    alimbs = property(lambda self: self.dsts[5: 5 + self.ng])
-    gaps = property(lambda self: self.dsts[5 + self.ng:])
+    p_ins = property(lambda self: self.dsts[2: 2 + self.nv])
+    p_out = property(lambda self: self.dsts[2 + self.nv])
+    p_outs = property(lambda self: self.dsts[2 + self.nv: 2 + 2 * self.nv])
+    p_time = property(lambda self: self.dsts[2 + 2 * self.nv])
+    alimbs = property(lambda self: self.dsts[3 + 2 * self.nv: 3 + 2 * self.nv + self.ng])
+    gaps = property(lambda self: self.dsts[3 + 2 * self.nv + self.ng:])
 
     def n_dsts(self) -> int:
-        return 5 + 2 * self.ng
+        return 3 + 2 * self.nv + 2 * self.ng
 
     def words(self) -> List[int]:
-        w = [KIND_PAGES, self.limb_bits, self.ng, self.link] + [0] * 12 + list(self.dsts)
+        w = [KIND_PAGES, self.limb_bits, self.ng, self.link, self.nv - 1] + [0] * 11 + list(self.dsts)
         return w + [0] * (PAGES_WORDS - len(w))
 
 
 def _paged_link(records: Sequence, r: "Pages") -> Optional[Link]:
-    """the LINK record that the PAGES record `r` names, where it is one the rules allow: READS, a clock and one value column"""
+    """the LINK record that the PAGES record `r` names, where it is one the rules allow: READS, a clock and V = r.nv value columns"""
     t = records[r.link] if 0 <= r.link < len(records) else None
-    return t if isinstance(t, Link) and t.write is not None and t.nc == 2 and len(t.carried) == 2 else None
+    return t if isinstance(t, Link) and t.write is not None and t.nc == 1 + r.nv and len(t.carried) == 1 + r.nv else None
 
 
 def check_pages(terms: Sequence[Term], records: Sequence, group_sizes=None) -> Optional[str]:
     """the PAGES record that breaks a rule, named by its index among all `records` (all of them are its peers), or None: (a) the ranges
-    of L and ng, the reserved words, and its target a LINK record with READS and nc = 2 that joins no other (version 9: the head of its
-    memory, whose ports then have READS and nc = 2 as well); then (b) .. (e) of `_check_owned`, its sources being its LINK's and p_on
-    the one destination that may be a multiplicity"""
+    of L and ng, the reserved words, word 4 (version 10: V - 1, 0 or 1), and its target a LINK record with READS and nc = 1 + V that joins
+    no other (version 9: the head of its memory, whose ports then have READS and the same nc as well); then (b) .. (e) of `_check_owned`,
+    its sources being its LINK's and p_on the one destination that may be a multiplicity"""
     def clause_a(i, r, _sizes):
         if not (1 <= r.limb_bits <= 16 and 1 <= r.ng <= MAX_PAGE_LIMBS and r.limb_bits * r.ng <= MAX_ORDER_BITS):
             return (f"record {i}: a PAGES record of {r.ng} limbs of {r.limb_bits} bits (1..{MAX_PAGE_LIMBS} limbs of 1..16 bits, at most "
                     f"{MAX_ORDER_BITS} bits in all)")
+        if r.nv_word is not None:
+            return f"record {i}: word 4 of a PAGES record is {r.nv_word} (V - 1: 0 = one value word per address, 1 = two)"
         if r.reserved or len(r.dsts) != r.n_dsts():
-            return f"record {i}: a reserved word of a PAGES record is not 0 (words 4..15 and the unused destination words)"
+            return (f"record {i}: a reserved word of a PAGES record is not 0 (words 5..15 and the unused destination words)" if r.wide_word or r.nv > 1 else
+                    f"record {i}: a reserved word of a PAGES record is not 0 (words 4..15 and the unused destination words)")
+        if _paged_link(records, r) is None and r.nv > 1:
+            return (f"record {i}: a PAGES record of two value words per address pages record {r.link}, which is no LINK record with READS and three carried "
+                    f"columns (a clock and two values)")
         if _paged_link(records, r) is None:
             return f"record {i}: a PAGES record pages record {r.link}, which is no LINK record with READS and two carried columns (a clock and one value)"
         if _paged_link(records, r).joins is not None:
@@ -720,7 +758,14 @@ class Arguments:
         return any(isinstance(r, Link) and r.joins is not None for r in self.records)
 
     @property
+    def wide(self) -> bool:
+        """the PAGES record pages two value words per address (version 10: bit 19 of header word 7)"""
+        return self.pages is not None and self.pages.nv > 1
+
+    @property
     def version(self) -> int:
+        if self.wide:
+            return 10
         if self.ports:
             return 9
         if self.open is not None:
@@ -740,7 +785,7 @@ class Arguments:
     def blob(self) -> np.ndarray:
         words = [ARGS_MAGIC, self.version, self.k, self.alpha, self.beta, len(self.terms), len(self.records),
                  self.reads | (PAGES_BIT if self.pages is not None else 0) | (OPEN_BIT if self.open is not None else 0) |
-                 (PORTS_BIT if self.ports else 0)]
+                 (PORTS_BIT if self.ports else 0) | (WIDE_BIT if self.wide else 0)]
         for t in _by_column(self.terms):
             rec = [t.col, 0 if t.sign == 1 else 1, NONE if t.sel is None else t.sel,
                    NONE if t.mult is None else t.mult[0], 0 if t.mult is None else t.mult[1], t.tag % P, len(t.tuple_cols), t.flags()]
@@ -755,8 +800,9 @@ class Arguments:
     @staticmethod
     def parse(blob: Sequence[int]) -> "Arguments":
         d = [int(x) for x in np.asarray(blob, dtype=np.uint32)]
-        if len(d) < ARGS_HEADER or d[0] != ARGS_MAGIC or d[1] not in (1, 2, 3, 4, 5, 6, 7, 8, 9) or (d[1] == 6 and d[7] == 0) or \
-                (d[1] == 7 and not d[7] & PAGES_BIT) or (d[1] == 8 and not d[7] & OPEN_BIT) or (d[1] == 9 and not d[7] & PORTS_BIT):
+        if len(d) < ARGS_HEADER or d[0] != ARGS_MAGIC or d[1] not in (1, 2, 3, 4, 5, 6, 7, 8, 9, 10) or (d[1] == 6 and d[7] == 0) or \
+                (d[1] == 7 and not d[7] & PAGES_BIT) or (d[1] == 8 and not d[7] & OPEN_BIT) or (d[1] == 9 and not d[7] & PORTS_BIT) or \
+                (d[1] == 10 and not d[7] & WIDE_BIT):
             raise ValueError("not a ZKA1 argument blob")
         version = d[1]
         k, alpha, beta, n = d[2], d[3], d[4], d[5]
@@ -798,8 +844,10 @@ class Arguments:
                 records.append(Open(r[1], r[2], r[3], r[4], r[5], bool(any(r[6:]))))
                 continue
             if sizes[i] == PAGES_WORDS and r[0] == KIND_PAGES:
-                n_dst = min(16, 5 + 2 * min(r[2], 8))
-                records.append(Pages(r[1], r[2], r[3], tuple(r[16: 16 + n_dst]), bool(any(r[4:16]) or any(r[16 + n_dst:]))))
+                nv = 1 + min(r[4], MAX_PAGE_WORDS - 1) if version >= 10 else 1      # version 10: word 4 holds V - 1; reserved before
+                n_dst = min(16, 3 + 2 * nv + 2 * min(r[2], 8))
+                records.append(Pages(r[1], r[2], r[3], tuple(r[16: 16 + n_dst]), bool(any(r[5 if version >= 10 else 4:16]) or any(r[16 + n_dst:])), nv,
+                                     r[4] if version >= 10 and r[4] >= MAX_PAGE_WORDS else None, version >= 10))
                 continue
             if sizes[i] == LINK_WORDS:
                 nc = min(r[3], MAX_CARRIED)
@@ -825,8 +873,10 @@ class Arguments:
         has_open = any(isinstance(r, Open) for r in records)
         if version == 8 or (version >= 9 and d[7] & OPEN_BIT):
             word7 ^= OPEN_BIT                                                # bit 17 says OPEN
-        if version >= 9:
+        if version == 9 or (version >= 10 and d[7] & PORTS_BIT):
             word7 ^= PORTS_BIT                                               # bit 18 says PORTS
+        if version >= 10:
+            word7 ^= WIDE_BIT                                                # bit 19 says WIDE
         if version >= 6 and word7 != n_reads:
             raise ValueError(f"ZKA1: header word 7 is {word7}, the blob has {n_reads} LINK records with READS")
         if version >= 7 and d[7] & PAGES_BIT and not has_pages:
@@ -837,8 +887,13 @@ class Arguments:
             raise ValueError("ZKA1: header word 7 has bit 17 (OPEN), but the blob has no OPEN record")
         if version >= 9 and has_open and not d[7] & OPEN_BIT:
             raise ValueError("ZKA1: the blob has an OPEN record, but header word 7 lacks bit 17 (OPEN)")
-        if version >= 9 and not any(isinstance(r, Link) and r.joins is not None for r in records):
+        joiner = any(isinstance(r, Link) and r.joins is not None for r in records)
+        if (version == 9 or (version >= 10 and d[7] & PORTS_BIT)) and not joiner:
             raise ValueError("ZKA1: header word 7 has bit 18 (PORTS), but no LINK record joins")
+        if version >= 10 and joiner and not d[7] & PORTS_BIT:
+            raise ValueError("ZKA1: a LINK record joins, but header word 7 lacks bit 18 (PORTS)")
+        if version >= 10 and not any(isinstance(r, Pages) and (r.nv > 1 or r.nv_word is not None) for r in records):
+            raise ValueError("ZKA1: header word 7 has bit 19 (WIDE), but no PAGES record pages two value words per address")
         problem = check_sorted(terms) or check_derived(terms) or check_open(terms, records, (alpha, beta)) or _check_records(terms, records)
         if problem:
             raise ValueError(f"ZKA1: {problem}")
@@ -982,15 +1037,20 @@ class LogupBuilder(CircuitBuilder):
         (ZKA1 version 7): its first access to an address takes the word of an image as its previous access, at clock 0, and the
         library fills the data columns `dsts` = p_on, p_addr, p_in, p_out, p_time, alimb_0 .., gap_0 .. (5 + 2 ng of them) with the page
         table: the distinct addresses in order, each with the image's word and what its last access left (`reference_links` with an
-        image; zkh_derive_links_paged)"""
+        image; zkh_derive_links_paged).  A LINK that carries two values (nc = 3) pages a memory of two value words per address (ZKA1
+        version 10) and takes the wider list p_on, p_addr, p_in_0, p_in_1, p_out_0, p_out_1, p_time, alimb_0 .., gap_0 .. (7 + 2 ng)"""
         at = next((i for i, r in enumerate(self.records) if r is link_record), None)
         if at is None:
             at = self.records.index(link_record) if link_record in self.records else -1
         if at < 0:
             raise ValueError("derive_pages: the LINK record is not one of this builder's")
-        if len(dsts) < 7 or (len(dsts) - 5) % 2:
+        nv = 2 if isinstance(link_record, Link) and link_record.nc == 3 else 1  # the link carries two values: the wider list
+        if nv == 2 and (len(dsts) < 9 or (len(dsts) - 7) % 2):
+            raise ValueError(f"derive_pages: {len(dsts)} destinations (7 + 2 ng for a LINK that carries two values: p_on, p_addr, p_in_0, p_in_1, p_out_0, "
+                             f"p_out_1, p_time, ng address limbs, ng gap limbs; 5 + 2 ng for one value)")
+        if nv == 1 and (len(dsts) < 7 or (len(dsts) - 5) % 2):
             raise ValueError(f"derive_pages: {len(dsts)} destinations (5 + 2 ng: p_on, p_addr, p_in, p_out, p_time, ng address limbs, ng gap limbs)")
-        return self._record(Pages(int(limb_bits), (len(dsts) - 5) // 2, at, tuple(int(c) for c in dsts)))
+        return self._record(Pages(int(limb_bits), (len(dsts) - 3 - 2 * nv) // 2, at, tuple(int(c) for c in dsts), nv=nv))
 
     def paged(self, record: Link) -> Optional[Pages]:
         """the PAGES record that pages the memory of the LINK `record` (the head it names, or a port that joins that head), or None"""
@@ -1032,7 +1092,8 @@ class LogupBuilder(CircuitBuilder):
         returns what the previous access left, or 0.  linked prev_j and not prev_j alone, so that nothing rests on the host having
         zeroed prev_j on an unlinked row.  Degree 4 with the gate.
         A PAGED record (`derive_pages`): linked, last and w are 0 / 1, and UNGATED sum_j 2^(jL) limb_j = c_0 - prev_0 - 1 and
-        (1 - w) (c_1 - prev_1) = 0: the first access to an address has the image's word at clock 0 as its previous access."""
+        (1 - w) (c_j - prev_j) = 0 for every value column (j = 1; a wide memory: j = 1, 2): the first access to an address has the image's
+        words at clock 0 as its previous access."""
         if not isinstance(record, Link):
             raise ValueError("link_constraints: not a LINK record")
         L, nl = record.limb_bits, record.nl
@@ -1047,7 +1108,9 @@ class LogupBuilder(CircuitBuilder):
             inner = self.and_eqz(inner, self.mul(w, self.sub(one, w)))
             d = self.sub(self.sub(self.get(*record.carried[0]), self.get(GROUP_DATA, record.prevs[0])), one)
             inner = self.and_eqz(inner, self.sub(self._limb_sum(record.limbs, L), d))
-            return self.and_eqz(inner, self.mul(self.sub(one, w), self.sub(self.get(*record.carried[1]), self.get(GROUP_DATA, record.prevs[1]))))
+            for src, prev in zip(record.carried[1:], record.prevs[1:]):      # one value, or (version 10) two
+                inner = self.and_eqz(inner, self.mul(self.sub(one, w), self.sub(self.get(*src), self.get(GROUP_DATA, prev))))
+            return inner
         total = self.const(0)
         for j, c in enumerate(record.limbs):
             v = self.get(GROUP_DATA, c) if j == 0 else self.mul(self.const(1 << (j * L)), self.get(GROUP_DATA, c))
@@ -1483,6 +1546,11 @@ def _link_chain(key, rows):
 PAGES_NEED_IMAGE = "the arguments page memory: an image is required (zkh_derive_all_paged)"
 
 
+def image_not_whole(words: int, nv: int) -> str:
+    """the refusal of an image whose length is no multiple of the value words per address, before any launch"""
+    return f"an image of {words} words is not a whole number of addresses of {nv} value words"
+
+
 def reference_links(args: Arguments, po2: int, zk_cycles: int, code, data, image=None, table=None, image_words=None) -> np.ndarray:
     """The data trace zkh_derive_links leaves (raw Montgomery words, a copy): every LINK record's destination columns on the active rows
     (module docstring), rows [A, n) as given.  Raises ReferenceError on a selector other than 0 / 1 (the lowest (record, row) over all
@@ -1511,14 +1579,19 @@ def reference_links(args: Arguments, po2: int, zk_cycles: int, code, data, image
         raise ValueError("reference_links: exactly one of image / table")
     if pages is not None and image is None and table is None:
         raise ReferenceError(PAGES_NEED_IMAGE)
+    V = pages.nv if pages is not None else 1                                # the value words per address: the image and the table are FLAT, word j of address a at V a + j
     if pages is not None and table is None:
         image = np.asarray(image, dtype=np.uint32).reshape(-1)
-        W = image.size
+        if image.size % V:
+            raise ReferenceError(image_not_whole(image.size, V))
+        W = image.size // V
     elif pages is not None:
         if image_words is None or not 1 <= image_words <= 0xffffffff:
             raise ReferenceError(f"an image of {image_words} words (1 .. 2^32 - 1)")
+        if image_words % V:
+            raise ReferenceError(image_not_whole(image_words, V))
         table = np.asarray(table, dtype=np.uint32).reshape(-1, 3)
-        W, R, short = image_words, args.records.index(pages), None
+        W, R, short = image_words // V, args.records.index(pages), None
     on = {}
     for i, r in links:
         sel = np.ones(A, dtype=np.uint64) if r.sel is None else _dec(groups[GROUP_CODE][r.sel, :A])
@@ -1559,21 +1632,27 @@ def reference_links(args: Arguments, po2: int, zk_cycles: int, code, data, image
         bad = (d < 0) | (d >> (L * nl) != 0)
         if paged:
             outside = addr >= W
-            if table is None:
-                word = image[np.where(outside, 0, addr)] if W else np.zeros(row.size, dtype=np.uint32)      # the image's word of an unlinked access
+            if table is None:                                                # the image's words of an unlinked access: words[j] = image[V a + j]
+                words = [image[V * np.where(outside, 0, addr) + j] if W else np.zeros(row.size, dtype=np.uint32) for j in range(V)]
                 unlisted = np.zeros(row.size, dtype=bool)
-            else:                                                            # ... by its page: the number of its address among the trace's
+            else:                                                            # ... by its page: the number of its address among the trace's, rows V page + j
                 page = np.searchsorted(np.unique(addr), addr)
-                row_of = np.minimum(page, max(len(table) - 1, 0))
-                listed = (page < len(table)) & (table[row_of, 0] == addr if len(table) else False)
-                word = np.where(page < len(table), table[row_of, 1] if len(table) else 0, 0).astype(np.uint32)
+                words, listed, flat = [], np.ones(row.size, dtype=bool), np.zeros(row.size, dtype=np.int64)
+                for j in reversed(range(V)):                                 # `flat`: the lowest flat row that does not list the access
+                    at = V * page + j
+                    row_of = np.minimum(at, max(len(table) - 1, 0))
+                    here = (at < len(table)) & (table[row_of, 0] == V * addr + j if len(table) else False)
+                    words.insert(0, np.where(at < len(table), table[row_of, 1] if len(table) else 0, 0).astype(np.uint32))
+                    flat = np.where(here, flat, at)
+                    listed &= here
                 unlisted = ~linked & ~outside & ~listed
-                short = (np.unique(addr).size, len(table))
+                short = (V * np.unique(addr).size, len(table), np.unique(addr).size)
+            word = words[0]
             bad = bad | outside | unlisted
         if head.write is not None:
             w = _dec(take([r.write for _, r in ports], row, port))
             now = [_dec(take(cols, row, port)) for cols in carried]
-            before = [np.where(linked, _dec(take(cols, prow, pport)), _dec(word) if paged and e == 1 else 0) for e, cols in enumerate(carried)]
+            before = [np.where(linked, _dec(take(cols, prow, pport)), _dec(words[e - 1]) if paged and e >= 1 else 0) for e, cols in enumerate(carried)]
             misread = [(w == 0) & (now[e] != before[e]) for e in range(1, len(carried))]
             bad = bad | (w > 1) | np.logical_or.reduce(misread)
         if bad.any():
@@ -1587,8 +1666,8 @@ def reference_links(args: Arguments, po2: int, zk_cycles: int, code, data, image
                 raise ReferenceError(f"{at}: address {int(addr[j])} outside the image of {W} words")
             if paged and unlisted[j]:
                 page_at = f"record {R} at row {int(row[j])}: address {int(addr[j])} is page {int(page[j])} of the trace, but "
-                raise ReferenceError(page_at + (f"the page table has {len(table)} rows" if page[j] >= len(table) else
-                                                f"row {int(page[j])} of the page table holds address {int(table[page[j], 0])}"))
+                raise ReferenceError(page_at + (f"the page table has {len(table)} rows" if flat[j] >= len(table) else
+                                                f"row {int(flat[j])} of the page table holds address {int(table[flat[j], 0])}"))
             if paged and not linked[j] and clock[j] == 0:
                 raise ReferenceError(f"{at}: clock 0 is the image's")
             if head.write is not None and d[j] >= 0 and d[j] >> (L * nl) == 0:
@@ -1600,7 +1679,7 @@ def reference_links(args: Arguments, po2: int, zk_cycles: int, code, data, image
                 raise ReferenceError(f"{at}: clock not increasing ({int(clock[j])} after {int(pclock[j])} at {there})")
             after = f"after {there}" if linked[j] else "after the image"
             raise ReferenceError(f"{at}: the clock difference {int(d[j])} ({after}) does not fit {nl} limbs of {L} bits")
-        vals = [np.where(linked, take(cols, prow, pport), word if paged and e == 1 else 0).astype(np.uint32) for e, cols in enumerate(carried)]
+        vals = [np.where(linked, take(cols, prow, pport), words[e - 1] if paged and e >= 1 else 0).astype(np.uint32) for e, cols in enumerate(carried)]
         for q, (_, r) in enumerate(ports):                                   # destinations stay per record: port q writes its own columns
             mine = port == q
             rows = row[mine]
@@ -1628,8 +1707,9 @@ def reference_links(args: Arguments, po2: int, zk_cycles: int, code, data, image
             writes.append((list(pages.dsts), slice(0, A), 0))
             writes.append((pages.p_on, top, np.uint32(_R)))
             writes.append((pages.p_addr, top, take(keys, row[first], port[first])))
-            writes.append((pages.p_in, top, image[a] if table is None else table[:D, 1]))
-            writes.append((pages.p_out, top, take(carried[1], row[final], port[final])))
+            for j in range(V):                                               # the head writes p_in_j, the tail p_out_j from its own record
+                writes.append((pages.p_ins[j], top, image[V * a + j] if table is None else table[j:V * D:V, 1] if len(table) >= V * D else 0))
+                writes.append((pages.p_outs[j], top, take(carried[1 + j], row[final], port[final])))
             writes.append((pages.p_time, top, take(carried[0], row[final], port[final])))
             for j in range(ng):
                 writes.append((pages.alimbs[j], top, _enc((a >> (j * Lp)) & ((1 << Lp) - 1)).astype(np.uint32)))
@@ -1637,7 +1717,7 @@ def reference_links(args: Arguments, po2: int, zk_cycles: int, code, data, image
     if late:
         raise ReferenceError(late)
     if pages is not None and table is not None and short is not None and short[0] != short[1]:
-        raise ReferenceError(f"record {R}: the trace pages {short[0]} addresses, but the page table has {short[1]} rows")
+        raise ReferenceError(f"record {R}: the trace pages {short[2]} addresses, but the page table has {short[1]} rows")
     for cols, rows, words in writes:
         out[cols, rows] = words
     return out.reshape(-1)
@@ -1653,7 +1733,8 @@ def reference_page_out(args: Arguments, po2: int, zk_cycles: int, data, image) -
     d, live = _page_table(args, po2, zk_cycles, data, out.size)
     A = (1 << po2) - zk_cycles
     pages = args.pages
-    out[_dec(d[pages.p_addr, :A][live]).astype(np.int64)] = d[pages.p_out, :A][live]
+    for j, c in enumerate(pages.p_outs):                                     # the image is flat: word j of address a at V a + j
+        out[pages.nv * _dec(d[pages.p_addr, :A][live]).astype(np.int64) + j] = d[c, :A][live]
     return out
 
 
@@ -1726,7 +1807,12 @@ def _page_table(args: Arguments, po2: int, zk_cycles: int, data, W: int, leaves=
     pages = args.pages
     if pages is None:
         raise ReferenceError("the arguments hold no PAGES record (ZKA1 version 7)")
-    i = args.records.index(pages)
+    i, V = args.records.index(pages), pages.nv
+    if W % V:
+        raise ReferenceError(image_not_whole(W, V))
+    if V > 1 and W > P:
+        raise ReferenceError(f"an image of {W} words of a memory of two value words per address (at most P: its flat addresses are field elements)")
+    W //= V                                                                  # W: the flat image's words on entry, its addresses from here on
     d = np.asarray(data, dtype=np.uint32).reshape(-1, n)
     on, addr = _dec(d[pages.p_on, :A]).astype(np.int64), _dec(d[pages.p_addr, :A]).astype(np.int64)
     pon, paddr = np.concatenate([[1], on[:-1]]), np.concatenate([[-1], addr[:-1]])
@@ -1734,8 +1820,9 @@ def _page_table(args: Arguments, po2: int, zk_cycles: int, data, W: int, leaves=
     follows = (pon == 1) & (paddr < addr)
     bad = (on > 1) | (live & ((addr >= W) | ~follows))
     if leaves is not None:
-        held = leaves[np.where(live & (addr < W), addr, 0)]
-        bad |= live & (d[pages.p_in, :A] % np.uint32(P) != held)
+        held = [leaves[V * np.where(live & (addr < W), addr, 0) + j] for j in range(V)]
+        differs = [live & (d[c, :A] % np.uint32(P) != held[j]) for j, c in enumerate(pages.p_ins)]
+        bad |= np.logical_or.reduce(differs)
     if bad.any():
         r = int(np.argmax(bad))
         at = f"record {i} at row {r}"
@@ -1745,7 +1832,8 @@ def _page_table(args: Arguments, po2: int, zk_cycles: int, data, W: int, leaves=
             raise ReferenceError(f"{at}: address {int(addr[r])} outside the image of {W} words")
         if not follows[r]:
             raise ReferenceError(f"{at}: page address {int(addr[r])} does not follow a smaller one (row {r - 1}: p_on {int(pon[r])}, address {int(paddr[r])})")
-        raise ReferenceError(f"{at}: p_in {int(_dec(d[pages.p_in, r]))} at address {int(addr[r])}, the tree holds {int(_dec(held[r]))}")
+        j = next(j for j in range(V) if differs[j][r])                      # the lowest word first; "word j" only where there are two
+        raise ReferenceError(f"{at}: p_in {f'word {j} ' if V > 1 else ''}{int(_dec(d[pages.p_ins[j], r]))} at address {int(addr[r])}, the tree holds {int(_dec(held[j][r]))}")
     return d, live
 
 
@@ -1763,9 +1851,11 @@ def reference_page_out_proof(args: Arguments, po2: int, zk_cycles: int, data, im
     d, live = _page_table(args, po2, zk_cycles, data, W, leaves=nodes[L:].reshape(-1))
     A = (1 << po2) - zk_cycles
     pages = args.pages
-    a = _dec(d[pages.p_addr, :A][live]).astype(np.int64)
+    V = pages.nv                                                             # THE FLAT TABLE: V rows (V a_i + j, in_j, out_j) per page, i major, j minor
+    a = (V * _dec(d[pages.p_addr, :A][live]).astype(np.int64)[:, None] + np.arange(V)).reshape(-1)
     h = L.bit_length() - 1
-    table = np.stack([a.astype(np.uint32), d[pages.p_in, :A][live] % np.uint32(P), d[pages.p_out, :A][live] % np.uint32(P)], axis=1)
+    flat = lambda cols: np.stack([d[c, :A][live] % np.uint32(P) for c in cols], axis=1).reshape(-1)
+    table = np.stack([a.astype(np.uint32), flat(pages.p_ins), flat(pages.p_outs)], axis=1)
     S = np.unique(a >> 3)
     counts, sections = [], [nodes[L + S].reshape(-1)]
     for k in range(h):

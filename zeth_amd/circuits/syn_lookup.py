@@ -64,6 +64,14 @@ accesses to ONE memory, in port order.  `witness(..., ports=True)` orders the ac
 n_mem r + q (+ 1 when paged) and shares one memory across the ports, and the host-made link columns come from one walk over that order.
 `pages=True` with `ports=True` lifts n_mem = 1: the PAGES record names the head, every port's link constraints are the paged ones, and
 the page table's four bus terms stand once for the whole memory.  n_mem A must stay below 2^(order_limbs L).
+SYN-LOOKUP-paged-wide (`build_syn_lookup(shape, link=True, reads=True, pages=True, wide=True)`; `ports=True` is accepted as well): ANOTHER
+description, SYN-LOOKUP-paged over a memory of TWO value words per address, the two halves of a 32-bit machine word (ZKA1 version 10).
+Every memory pair gains a second value column and its previous value, after the pair's link limbs (`link_layout(wide=True)`: val1, pval1),
+and the page table its 2 V value columns (`pages_layout(wide=True)`: p_on, p_addr, p_in_0, p_in_1, p_out_0, p_out_1, p_time, the limbs).  On
+the bus (tag 1): the access +(addr, v0, v1, time), the previous access -(addr, pv0, pv1, ptime), the page-in +p_on (p_addr, p_in_0, p_in_1),
+the key (addr, v0, v1, 0), and the page-out -p_on (p_addr, p_out_0, p_out_1, p_time).  The LINK carries (time, val, val1), the PAGES record
+has V = 2, and logup.link_constraints states (1 - w)(c_j - prev_j) = 0 for both values.  The image is 2 W words, word j of address a at
+2 a + j (`witness(..., wide=True)`).  It does not combine with `tied`: the tie of a wide memory is not built.
 """
 from __future__ import annotations
 
@@ -114,16 +122,17 @@ def order_layout(n_words: int, n_limbs: int, n_mem: int, order_limbs: int = ORDE
 LINK_W = 7                          # addr, val, time, linked, last, pval, ptime
 
 
-def link_layout(n_words: int, n_limbs: int, n_mem: int, order_limbs: int = ORDER_LIMBS):
+def link_layout(n_words: int, n_limbs: int, n_mem: int, order_limbs: int = ORDER_LIMBS, wide: bool = False):
     """data column indices of SYN-LOOKUP-linked's memory pairs, after `layout`'s m: per pair [addr, val, time, linked, last, pval, ptime,
-    limb_0 .. limb_{order_limbs-1}]"""
+    limb_0 .. limb_{order_limbs-1}]; wide: then [val1, pval1], the second value word and its previous one"""
     base = n_words + n_words * n_limbs + 1
-    return [[base + (LINK_W + order_limbs) * i + e for e in range(LINK_W + order_limbs)] for i in range(n_mem)]
+    w = LINK_W + order_limbs + 2 * bool(wide)
+    return [[base + w * i + e for e in range(w)] for i in range(n_mem)]
 
 
-def reads_layout(n_words: int, n_limbs: int, n_mem: int, order_limbs: int = ORDER_LIMBS):
+def reads_layout(n_words: int, n_limbs: int, n_mem: int, order_limbs: int = ORDER_LIMBS, wide: bool = False):
     """data column indices of SYN-LOOKUP-reads' write flags, one per memory pair, after `link_layout`'s columns"""
-    base = n_words + n_words * n_limbs + 1 + (LINK_W + order_limbs) * n_mem
+    base = n_words + n_words * n_limbs + 1 + (LINK_W + order_limbs + 2 * bool(wide)) * n_mem
     return [base + i for i in range(n_mem)]
 
 
@@ -131,17 +140,17 @@ PAGE_W = 5                          # p_on, p_addr, p_in, p_out, p_time
 TIED_OUT, OUT_ALPHA, OUT_BETA, OUT_TOTAL = 16, 4, 8, 12      # SYN-LOOKUP-tied's out: 4 zero words ‖ alpha ‖ beta ‖ F
 
 
-def pages_layout(n_words: int, n_limbs: int, n_mem: int = 1, order_limbs: int = ORDER_LIMBS):
+def pages_layout(n_words: int, n_limbs: int, n_mem: int = 1, order_limbs: int = ORDER_LIMBS, wide: bool = False):
     """data column indices of SYN-LOOKUP-paged's page table, after `reads_layout`'s write flag: [p_on, p_addr, p_in, p_out, p_time,
-    alimb_0 .. alimb_{order_limbs-1}, gap_0 .. gap_{order_limbs-1}]"""
-    base = n_words + n_words * n_limbs + 1 + (LINK_W + order_limbs) * n_mem + n_mem
-    return [base + e for e in range(PAGE_W + 2 * order_limbs)]
+    alimb_0 .. alimb_{order_limbs-1}, gap_0 .. gap_{order_limbs-1}]; wide: [p_on, p_addr, p_in_0, p_in_1, p_out_0, p_out_1, p_time, the limbs]"""
+    base = n_words + n_words * n_limbs + 1 + (LINK_W + order_limbs + 2 * bool(wide)) * n_mem + n_mem
+    return [base + e for e in range(PAGE_W + 2 * bool(wide) + 2 * order_limbs)]
 
 
 def build_syn_lookup(shape: Shape = FULL, derive: bool = False, sort: bool = False,
                      sort_keys: Tuple[int, ...] = SORT_KEYS, limbs: bool = False, order: bool = False,
                      order_limbs: int = ORDER_LIMBS, link: bool = False, reads: bool = False, pages: bool = False,
-                     tied: bool = False, ports: bool = False) -> Tuple[np.ndarray, np.ndarray]:
+                     tied: bool = False, ports: bool = False, wide: bool = False) -> Tuple[np.ndarray, np.ndarray]:
     """-> (ZKC1 description, ZKA1 argument blob); derive: the table term's multiplicity is derived by the library (version-2 blob,
     the description unchanged); sort: every permuted copy is the library's sorted copy of its memory tuple by the tuple positions
     `sort_keys` (version-3 blob, the description unchanged); limbs: every word's limbs are a LIMBS record (version-4 blob, the
@@ -152,8 +161,14 @@ def build_syn_lookup(shape: Shape = FULL, derive: bool = False, sort: bool = Fal
     with its one memory paged in from an image and out again (version-7 blob, another description); it needs `link`, `reads` and n_mem = 1; tied: SYN-LOOKUP-tied, SYN-LOOKUP-paged on the open bus with
     the page table's rows as one more term (version-8 blob, another description, 16 `out` words); it needs `pages`; ports: the n_mem memory
     pairs are the ports of ONE memory (version-9 blob; without `pages` SYN-LOOKUP-reads' description unchanged); it needs `link` and `reads`,
-    and with it `pages` takes any n_mem"""
+    and with it `pages` takes any n_mem; wide: SYN-LOOKUP-paged-wide, the paged memory holds two value words per address (version-10 blob,
+    another description); it needs `pages`, takes `ports`, and refuses `tied`"""
     n_words, n_limbs, limb_bits, n_mem = shape
+    if wide and tied:
+        raise ValueError("build_syn_lookup: tied=True with wide=True: the tie of a memory of two value words per address is not built (its table's rows on the "
+                         "open bus need flat-address columns in the trace)")
+    if wide and not pages:
+        raise ValueError("build_syn_lookup: wide=True gives the paged memory two value words per address: it needs pages=True")
     if tied and not pages:
         raise ValueError("build_syn_lookup: tied=True ties the page table of a paged memory to its page-out: it needs pages=True")
     if pages and not (link and reads):
@@ -168,14 +183,15 @@ def build_syn_lookup(shape: Shape = FULL, derive: bool = False, sort: bool = Fal
         raise ValueError("build_syn_lookup: link=True has no sorted copy: it does not combine with sort= / order=")
     words, limb_cols, m, mem, perm = layout(n_words, n_limbs, n_mem)
     ocols = order_layout(n_words, n_limbs, n_mem, order_limbs) if order else []
-    lcols = link_layout(n_words, n_limbs, n_mem, order_limbs) if link else []
+    lcols = link_layout(n_words, n_limbs, n_mem, order_limbs, wide) if link else []
     wd = m + 1 + 2 * MEM_W * n_mem + sum(len(c) for c in ocols)
     n_terms = n_words * n_limbs + 1 + 2 * n_mem + n_mem * order_limbs * bool(order)
     if link:
         wd = m + 1 + sum(len(c) for c in lcols) + n_mem * bool(reads)
         n_terms = n_words * n_limbs + 1 + 3 * n_mem + n_mem * order_limbs
-    wcols = reads_layout(n_words, n_limbs, n_mem, order_limbs) if reads else [None] * n_mem
-    pcols = pages_layout(n_words, n_limbs, n_mem, order_limbs) if pages else []
+    wcols = reads_layout(n_words, n_limbs, n_mem, order_limbs, wide) if reads else [None] * n_mem
+    pcols = pages_layout(n_words, n_limbs, n_mem, order_limbs, wide) if pages else []
+    pw = PAGE_W + 2 * bool(wide)                                             # the table's columns before its limbs
     if pages:
         wd += len(pcols)
         n_terms += 2 - n_mem + 2 * order_limbs + bool(tied)                     # a port: its access and its previous one; the table's two terms once
@@ -196,10 +212,14 @@ def build_syn_lookup(shape: Shape = FULL, derive: bool = False, sort: bool = Fal
         specs.append(dict(tuple_cols=[(GROUP_DATA, c) for c in mem[i]], sign=1, tag=1))
         copy = dict(sorted_from=len(specs) - 1, sort_keys=sort_keys) if sort else {}
         specs.append(dict(tuple_cols=[(GROUP_DATA, c) for c in perm[i]], sign=-1, tag=1, **copy))
-    for c_addr, c_val, c_time, c_linked, c_last, c_pval, c_ptime, *_ in lcols if pages else []:
-        specs.append(dict(tuple_cols=[(GROUP_DATA, c_addr), (GROUP_DATA, c_val), (GROUP_DATA, c_time)], sign=1, tag=1))
-        specs.append(dict(tuple_cols=[(GROUP_DATA, c_addr), (GROUP_DATA, c_pval), (GROUP_DATA, c_ptime)], sign=-1, tag=1))
-    if pages:
+    for c_addr, c_val, c_time, c_linked, c_last, c_pval, c_ptime, *rest in lcols if pages else []:
+        val1, pval1 = ([(GROUP_DATA, rest[-2])], [(GROUP_DATA, rest[-1])]) if wide else ([], [])
+        specs.append(dict(tuple_cols=[(GROUP_DATA, c_addr), (GROUP_DATA, c_val)] + val1 + [(GROUP_DATA, c_time)], sign=1, tag=1))
+        specs.append(dict(tuple_cols=[(GROUP_DATA, c_addr), (GROUP_DATA, c_pval)] + pval1 + [(GROUP_DATA, c_ptime)], sign=-1, tag=1))
+    if wide:                                                                 # +p_on (p_addr, p_in_0, p_in_1), the key (addr, v0, v1, 0); -p_on (p_addr, p_out_0, p_out_1, p_time)
+        specs.append(dict(tuple_cols=[(GROUP_DATA, pcols[e]) for e in (1, 2, 3)], sign=1, mult=(GROUP_DATA, pcols[0]), tag=1))
+        specs.append(dict(tuple_cols=[(GROUP_DATA, pcols[e]) for e in (1, 4, 5, 6)], sign=-1, mult=(GROUP_DATA, pcols[0]), tag=1))
+    elif pages:
         specs.append(dict(tuple_cols=[(GROUP_DATA, pcols[1]), (GROUP_DATA, pcols[2])], sign=1, mult=(GROUP_DATA, pcols[0]), tag=1))
         specs.append(dict(tuple_cols=[(GROUP_DATA, pcols[1]), (GROUP_DATA, pcols[3]), (GROUP_DATA, pcols[4])], sign=-1, mult=(GROUP_DATA, pcols[0]), tag=1))
     for c_addr, c_val, c_time, c_linked, c_last, c_pval, c_ptime, *_ in [] if pages else lcols:
@@ -207,8 +227,8 @@ def build_syn_lookup(shape: Shape = FULL, derive: bool = False, sort: bool = Fal
         specs.append(dict(tuple_cols=[(GROUP_DATA, c_addr), (GROUP_DATA, c_pval), (GROUP_DATA, c_ptime)], sign=-1, mult=(GROUP_DATA, c_linked), tag=1))
         specs.append(dict(tuple_cols=[(GROUP_DATA, c_addr), (GROUP_DATA, c_val), (GROUP_DATA, c_time)], sign=-1, mult=(GROUP_DATA, c_last), tag=1))
     specs += [dict(tuple_cols=[(GROUP_DATA, c)], tag=0) for cols in ocols for c in cols[1:]]
-    specs += [dict(tuple_cols=[(GROUP_DATA, c)], tag=0) for cols in lcols for c in cols[LINK_W:]]
-    specs += [dict(tuple_cols=[(GROUP_DATA, c)], tag=0) for c in pcols[PAGE_W:]]
+    specs += [dict(tuple_cols=[(GROUP_DATA, c)], tag=0) for cols in lcols for c in cols[LINK_W:LINK_W + order_limbs]]
+    specs += [dict(tuple_cols=[(GROUP_DATA, c)], tag=0) for c in pcols[pw:]]
     if tied:                                                                 # the table's rows, for the page-out chain to take off the bus
         specs.append(dict(tuple_cols=[(GROUP_DATA, pcols[1]), (GROUP_DATA, pcols[2]), (GROUP_DATA, pcols[3])], sign=1, mult=(GROUP_DATA, pcols[0]), tag=TIE_TAG))
     for i, s in enumerate(specs):
@@ -220,8 +240,9 @@ def build_syn_lookup(shape: Shape = FULL, derive: bool = False, sort: bool = Fal
     # the clock (time) is carried first, then the value; the destinations in the LINK's order: linked, last, ptime, pval, the limbs
     links = []
     for c, w in zip(lcols, wcols):                                           # ports: pair 0 is the head, the others join its memory
-        links.append(b.derive_links(None, (GROUP_DATA, c[0]), [(GROUP_DATA, c[2]), (GROUP_DATA, c[1])], [c[3], c[4], c[6], c[5]] + c[LINK_W:], limb_bits,
-                                    write=None if w is None else (GROUP_DATA, w), joins=links[0] if ports and links else None))
+        carried, prevs = ([(GROUP_DATA, c[-2])], [c[-1]]) if wide else ([], [])                  # wide: the second value word and its previous one
+        links.append(b.derive_links(None, (GROUP_DATA, c[0]), [(GROUP_DATA, c[2]), (GROUP_DATA, c[1])] + carried, [c[3], c[4], c[6], c[5]] + prevs + c[LINK_W:LINK_W + order_limbs],
+                                    limb_bits, write=None if w is None else (GROUP_DATA, w), joins=links[0] if ports and links else None))
     table = b.derive_pages(links[0], pcols, limb_bits) if pages else None
     # words = sum of their limbs, on active rows
     inner = b.true()
@@ -315,7 +336,7 @@ def _enc(x) -> np.ndarray:
 
 def witness(shape: Shape, po2: int, zk_cycles: int, seed: int = 1, count: bool = True, sort: bool = True, addr_range: int = 1 << 20,
             sort_keys: Tuple[int, ...] = SORT_KEYS, limbs: bool = True, order=None, order_limbs: int = ORDER_LIMBS, link=None,
-            reads: bool = False, pages=None, image=None, ports: bool = False):
+            reads: bool = False, pages=None, image=None, ports: bool = False, wide: bool = False):
     """-> (code, data, out_global) host arrays of raw Montgomery words: random words below min(P, 2^(n_limbs L)) split into limbs
     (limbs=False: zero, for the library to split), the table's multiplicities (count=False: zero, for the library to derive), random
     memory tuples (addresses below `addr_range`) and their copy stably sorted by the tuple positions `sort_keys`, (addr, time)
@@ -336,7 +357,13 @@ def witness(shape: Shape, po2: int, zk_cycles: int, seed: int = 1, count: bool =
     ports: SYN-LOOKUP-reads-ported's witness (`build_syn_lookup(..., ports=True)`; it needs `link` and `reads`): the n_mem pairs are the
     ports of one memory.  The accesses are ordered by (row, port), access (r, q) has the time n_mem r + q (+ 1 when paged), a load takes
     what the previous access of ANY port left at its address, and the link columns (and the one page table) are host-made by one walk
-    over that order with a dictionary"""
+    over that order with a dictionary.
+    wide: SYN-LOOKUP-paged-wide's witness (`build_syn_lookup(..., pages=True, wide=True)`; it needs `pages`): two value words per address.
+    `image` is the FLAT image of 2 W words, word j of address a at 2 a + j; every access has a second value column, a load takes both
+    words of the last store or of the image, and the page table carries p_in_0, p_in_1, p_out_0, p_out_1.  The addresses, write flags and
+    clocks of a seed are those of the witness without `wide` over an image of W words"""
+    if wide and pages is None:
+        raise ValueError("witness: wide=True gives the paged memory two value words per address: it needs pages=")
     if ports and (link is None or not reads):
         raise ValueError("witness: ports=True makes the pairs the ports of one memory with the read rule: it needs link= and reads=True")
     if pages is not None and (link is None or not reads or image is None):
@@ -347,10 +374,11 @@ def witness(shape: Shape, po2: int, zk_cycles: int, seed: int = 1, count: bool =
     words, limb_cols, m_col, mem, perm = layout(n_words, n_limbs, n_mem)
     limbs_on, limbs = limbs, limb_cols
     ocols = order_layout(n_words, n_limbs, n_mem, order_limbs) if order is not None else []
-    lcols = link_layout(n_words, n_limbs, n_mem, order_limbs) if link is not None else []
+    lcols = link_layout(n_words, n_limbs, n_mem, order_limbs, wide) if link is not None else []
     wd = m_col + 1 + (sum(len(c) for c in lcols) + n_mem * bool(reads) if lcols else 2 * MEM_W * n_mem + sum(len(c) for c in ocols))
-    wcols = reads_layout(n_words, n_limbs, n_mem, order_limbs) if reads else []
-    pcols = pages_layout(n_words, n_limbs, n_mem, order_limbs) if pages is not None else []
+    wcols = reads_layout(n_words, n_limbs, n_mem, order_limbs, wide) if reads else []
+    pcols = pages_layout(n_words, n_limbs, n_mem, order_limbs, wide) if pages is not None else []
+    V = 2 if wide else 1
     wd += len(pcols)
     n = 1 << po2
     A = n - zk_cycles
@@ -361,7 +389,8 @@ def witness(shape: Shape, po2: int, zk_cycles: int, seed: int = 1, count: bool =
         assert (image < P).all(), "the witness holds canonical Montgomery words: an image word >= P has no host-made twin"
         assert (n_mem if ports else 1) * A < 1 << (order_limbs * limb_bits), f"times reach {(n_mem if ports else 1) * A}: they do not fit {order_limbs} limbs of {limb_bits} bits"
         held0 = (image.astype(np.uint64) * np.uint64(pow((1 << 32) % P, -1, P)) % np.uint64(P)).tolist()     # the image, canonical
-        addr_range = min(addr_range, image.size, 1 << (order_limbs * limb_bits))
+        assert image.size % V == 0, "the flat image of a wide memory has two words per address"
+        addr_range = min(addr_range, image.size // V, 1 << (order_limbs * limb_bits))
     assert A >= T, f"po2 {po2}: {A} active rows do not hold the {T}-row table"
     rng = np.random.default_rng(seed)
     code = np.zeros((N_CODE, n), dtype=np.uint64)
@@ -385,21 +414,27 @@ def witness(shape: Shape, po2: int, zk_cycles: int, seed: int = 1, count: bool =
                 data[limbs[kk][j], :A] = limb
             counts += np.bincount(limb.astype(np.int64), minlength=T)
     if ports:
-        _ported_witness(data, rng, lcols, wcols, pcols, held0 if pcols else None, A, addr_range, limb_bits, order_limbs, link, pages, counts)
+        _ported_witness(data, rng, lcols, wcols, pcols, held0 if pcols else None, A, addr_range, limb_bits, order_limbs, link, pages, counts, wide)
     for i in range(0 if ports else n_mem):
         addr = rng.integers(0, addr_range, size=A, dtype=np.uint64)
         val = rng.integers(0, P, size=A, dtype=np.uint64)
         time = rng.permutation(A).astype(np.uint64)
         if wcols:                                                            # a load returns what the previous access left, or 0
             store = rng.integers(0, 2, size=A, dtype=np.uint64)
+            val1 = rng.integers(0, P, size=A, dtype=np.uint64) if wide else None       # drawn last: the other draws are those of the narrow witness
             held = {}
             for r, a in enumerate(addr.tolist()):
                 if not store[r]:
-                    val[r] = held.get(a, held0[a] if pcols else 0)
+                    val[r] = held.get(a, held0[V * a] if pcols else 0)
                 held[a] = val[r]
+            held = {}
+            for r, a in enumerate(addr.tolist() if wide else []):            # the second word: a load takes the last store's, or the image's
+                if not store[r]:
+                    val1[r] = held.get(a, held0[2 * a + 1])
+                held[a] = val1[r]
             data[wcols[i], :A] = store
         if pcols:
-            _paged_witness(data, lcols[i], pcols, addr, val, held0, A, limb_bits, order_limbs, link, pages, counts)
+            _paged_witness(data, lcols[i], pcols, addr, val, held0, A, limb_bits, order_limbs, link, pages, counts, val1 if wide else None)
             continue
         if lcols:
             _link_witness(data, lcols[i], addr, val, A, limb_bits, order_limbs, link, counts)
@@ -457,10 +492,14 @@ def _link_witness(data, cols, addr, val, A, limb_bits, order_limbs, fill, counts
         counts += np.bincount(limb, minlength=T)
 
 
-def _paged_witness(data, cols, pcols, addr, val, image, A, limb_bits, order_limbs, fill, fill_pages, counts):
+def _paged_witness(data, cols, pcols, addr, val, image, A, limb_bits, order_limbs, fill, fill_pages, counts, val1=None):
     """the memory pair of SYN-LOOKUP-paged: `_link_witness` with times row + 1 and the image (canonical words) behind every first access,
-    and the page table from a walk over the distinct addresses in order"""
+    and the page table from a walk over the distinct addresses in order.  val1: the second value word of every access (wide: the image
+    is flat, two words per address, and the pair's columns end on val1, pval1)"""
     c_addr, c_val, c_time, c_linked, c_last, c_pval, c_ptime, *c_limbs = cols
+    V = 1 if val1 is None else 2
+    if V == 2:
+        *c_limbs, c_val1, c_pval1 = c_limbs
     T = 1 << limb_bits
     time = np.arange(1, A + 1, dtype=np.uint64)
     data[c_addr, :A], data[c_val, :A], data[c_time, :A] = addr, val, time
@@ -475,11 +514,15 @@ def _paged_witness(data, cols, pcols, addr, val, image, A, limb_bits, order_limb
     linked, last = on.astype(np.uint64), np.ones(A, dtype=np.uint64)
     last[prev[on]] = 0
     img = np.asarray(image, dtype=np.uint64)
-    pval, ptime = np.where(on, val[q], img[addr.astype(np.int64)]).astype(np.uint64), np.where(on, time[q], 0).astype(np.uint64)
+    pval, ptime = np.where(on, val[q], img[V * addr.astype(np.int64)]).astype(np.uint64), np.where(on, time[q], 0).astype(np.uint64)
     d = time.astype(np.int64) - ptime.astype(np.int64) - 1
     assert (d >> (order_limbs * limb_bits) == 0).all(), "a time difference does not fit the link limbs"
+    if V == 2:
+        data[c_val1, :A] = val1
     if fill:
         data[c_linked, :A], data[c_last, :A], data[c_pval, :A], data[c_ptime, :A] = linked, last, pval, ptime
+        if V == 2:
+            data[c_pval1, :A] = np.where(on, val1[q], img[2 * addr.astype(np.int64) + 1]).astype(np.uint64)
     for j, c in enumerate(c_limbs):
         limb = (d >> (j * limb_bits)) & (T - 1)
         if fill:
@@ -488,38 +531,44 @@ def _paged_witness(data, cols, pcols, addr, val, image, A, limb_bits, order_limb
     below = -1
     for i, a in enumerate(sorted(seen)):                                     # the page table: one row per distinct address, in order
         gap = a - below - 1 if i else 0
-        row = [1, a, image[a], int(val[seen[a]]), int(time[seen[a]])] + [(a >> (j * limb_bits)) & (T - 1) for j in range(order_limbs)] + \
+        ins, outs = [image[V * a + j] for j in range(V)], [int(val[seen[a]])] + ([int(val1[seen[a]])] if V == 2 else [])
+        row = [1, a] + ins + outs + [int(time[seen[a]])] + [(a >> (j * limb_bits)) & (T - 1) for j in range(order_limbs)] + \
             [(gap >> (j * limb_bits)) & (T - 1) for j in range(order_limbs)]
         assert a >> (order_limbs * limb_bits) == 0
         if fill_pages:
             data[pcols, i] = row
-        for v in row[PAGE_W:]:
+        for v in row[3 + 2 * V:]:
             counts[v] += 1
         below = a
     counts[0] += 2 * order_limbs * (A - len(seen))                           # the rows below the table look their zero limbs up as well
 
 
-def _ported_witness(data, rng, lcols, wcols, pcols, image, A, addr_range, limb_bits, order_limbs, fill, fill_pages, counts):
+def _ported_witness(data, rng, lcols, wcols, pcols, image, A, addr_range, limb_bits, order_limbs, fill, fill_pages, counts, wide=False):
     """the k memory pairs of SYN-LOOKUP-reads-ported as the ports of ONE memory, the host's way: one sequential walk over the accesses in
-    (row, port) order with the last access of every address in a dictionary.  image: the paged memory's image (canonical words), or None"""
-    k, T, paged = len(lcols), 1 << limb_bits, image is not None
+    (row, port) order with the last access of every address in a dictionary.  image: the paged memory's image (canonical words), or None.
+    wide: two value words per address (the image flat, the pairs' columns ending on val1, pval1)"""
+    k, T, paged, V = len(lcols), 1 << limb_bits, image is not None, 2 if wide else 1
     assert k * A < 1 << (order_limbs * limb_bits), f"times reach {k * A}: they do not fit {order_limbs} limbs of {limb_bits} bits"
     addr = [rng.integers(0, addr_range, size=A, dtype=np.uint64).tolist() for _ in range(k)]
     val = [rng.integers(0, P, size=A, dtype=np.uint64).tolist() for _ in range(k)]
     store = [rng.integers(0, 2, size=A, dtype=np.uint64).tolist() for _ in range(k)]
+    val1 = [rng.integers(0, P, size=A, dtype=np.uint64).tolist() for _ in range(k)] if wide else None     # drawn last: the other draws are the narrow witness's
     seen, first = {}, {}                                                     # address -> (row, port) of its last / first access so far
-    cols = [np.zeros((LINK_W + order_limbs, A), dtype=np.uint64) for _ in range(k)]
+    cols = [np.zeros((LINK_W + order_limbs + 2 * wide, A), dtype=np.uint64) for _ in range(k)]
     for r in range(A):
         for q in range(k):                                                   # the walk: every access after the one before it in (row, port) order
             a, time = addr[q][r], k * r + q + paged
             at = seen.get(a)
             if not store[q][r]:                                              # a load returns what the previous access left, the image's word or 0
-                val[q][r] = val[at[1]][at[0]] if at is not None else image[a] if paged else 0
-            pval, ptime = (val[at[1]][at[0]], k * at[0] + at[1] + paged) if at is not None else (image[a] if paged else 0, 0)
+                val[q][r] = val[at[1]][at[0]] if at is not None else image[V * a] if paged else 0
+                if wide:
+                    val1[q][r] = val1[at[1]][at[0]] if at is not None else image[2 * a + 1]
+            pval, ptime = (val[at[1]][at[0]], k * at[0] + at[1] + paged) if at is not None else (image[V * a] if paged else 0, 0)
             d = time - ptime - 1 if at is not None or paged else 0
             assert 0 <= d < 1 << (order_limbs * limb_bits), "a time difference does not fit the link limbs"
             limbs = [(d >> (j * limb_bits)) & (T - 1) for j in range(order_limbs)]
-            cols[q][:, r] = [a, val[q][r], time, at is not None, 1, pval, ptime] + limbs
+            more = [val1[q][r], val1[at[1]][at[0]] if at is not None else image[2 * a + 1]] if wide else []
+            cols[q][:, r] = [a, val[q][r], time, at is not None, 1, pval, ptime] + limbs + more
             if at is not None:
                 cols[at[1]][4, at[0]] = 0                                    # it is no longer the last access of its address
             for v in limbs:
@@ -529,6 +578,8 @@ def _ported_witness(data, rng, lcols, wcols, pcols, image, A, addr_range, limb_b
     for q in range(k):
         keep = slice(0, None) if fill else slice(0, 3)                       # addr, val, time are the host's whoever fills the rest
         data[lcols[q][keep], :A] = cols[q][keep]
+        if wide:
+            data[lcols[q][-2], :A] = cols[q][-2]                             # ... and so is the second value word
         data[wcols[q], :A] = store[q]
     if not paged:
         return
@@ -536,12 +587,13 @@ def _ported_witness(data, rng, lcols, wcols, pcols, image, A, addr_range, limb_b
     for i, a in enumerate(sorted(seen)):                                     # the page table: one row per distinct address, in order
         gap = a - below - 1 if i else 0
         (r, q) = seen[a]
-        row = [1, a, image[a], val[q][r], k * r + q + 1] + [(a >> (j * limb_bits)) & (T - 1) for j in range(order_limbs)] + \
+        ins, outs = [image[V * a + j] for j in range(V)], [val[q][r]] + ([val1[q][r]] if wide else [])
+        row = [1, a] + ins + outs + [k * r + q + 1] + [(a >> (j * limb_bits)) & (T - 1) for j in range(order_limbs)] + \
             [(gap >> (j * limb_bits)) & (T - 1) for j in range(order_limbs)]
         assert a >> (order_limbs * limb_bits) == 0
         if fill_pages:
             data[pcols, i] = row
-        for v in row[PAGE_W:]:
+        for v in row[3 + 2 * V:]:
             counts[v] += 1
         below = a
     counts[0] += 2 * order_limbs * (A - len(seen))                           # the rows below the table look their zero limbs up as well

@@ -13,7 +13,8 @@
 // (records never chain); a LINK reads none; the multiplicities count lookup tuples, and those read every derived column freely.
 // Nothing reads a derived multiplicity.  A term's multiplicity is the host's column or a derived one, and of a LINK's destinations
 // linked and last (only they) may be the multiplicity of a term that is not derived.  The PAGES record (version 7) is one more writer of
-// the links stage: it reads what the LINK it pages reads, writes the page table, and of its destinations p_on may be such a multiplicity.
+// the links stage: it reads what the LINK it pages reads, writes the page table, and of its destinations p_on may be such a multiplicity
+// (version 10, two value words per address: p_in_1 and p_out_1 are destinations like the others; still only p_on).
 //
 // THE READ RULE (a LINK record with READS, ZKA1 version 6; links.hip's header has it in full): the write flag is one more source of the
 // record, the host's column.  On an access it must be 0 or 1; a load (0) returns, in every carried column but the clock, what the
@@ -35,13 +36,15 @@ constexpr uint32_t MAX_TUPLE = 4, MAX_TERMS = 3, MAX_SORT_KEYS = 3, NONE = 0xfff
 constexpr uint32_t RECORD_WORDS = 16, KIND_LIMBS = 1, KIND_ORDER = 2, MAX_LIMBS = 8;
 constexpr uint32_t KIND_LINK = 3, LINK_WORDS = 32, MAX_CARRIED = 3, MAX_LINK_LIMBS = 4, MAX_LINK_DSTS = 2 + MAX_CARRIED + MAX_LINK_LIMBS;
 constexpr uint32_t LINK_READS = 1;                  // LINK word 5, bit 0 (version 6): the record carries the read rule
-constexpr uint32_t KIND_PAGES = 4, PAGES_WORDS = 32, MAX_PAGE_LIMBS = 4, MAX_PAGE_DSTS = 5 + 2 * MAX_PAGE_LIMBS;   // a PAGES record (version 7)
+constexpr uint32_t KIND_PAGES = 4, PAGES_WORDS = 32, MAX_PAGE_LIMBS = 4, MAX_PAGE_WORDS = 2;   // a PAGES record (version 7); V, its value words per address (version 10)
+constexpr uint32_t MAX_PAGE_DSTS = 3 + 2 * MAX_PAGE_WORDS + 2 * MAX_PAGE_LIMBS;
 constexpr uint32_t PAGES_BIT = 0x10000;             // header word 7, bit 16 (version 7): the blob has a PAGES record
 constexpr uint32_t OPEN_BIT = 0x20000;              // header word 7, bit 17 (version 8): the blob has an OPEN record
 constexpr uint32_t KIND_OPEN = 5, OPEN_WORDS = 16;  // the OPEN record (version 8): the bus closes on `out` words, not on zero
 constexpr uint32_t LINK_JOINS = 2;                  // LINK word 5, bit 1 (version 9): the record joins the memory of the head that word 31 names
 constexpr uint32_t MAX_PORTS = 8;                   // the records of one memory, the head included
 constexpr uint32_t PORTS_BIT = 0x40000;             // header word 7, bit 18 (version 9): a LINK record joins
+constexpr uint32_t WIDE_BIT = 0x80000;              // header word 7, bit 19 (version 10): the PAGES record pages two value words per address
 constexpr uint32_t MAX_ORDER_BITS = 29;             // logup.MAX_ORDER_BITS: a negative difference stays out of the limbs' range
 
 // logup.Term as the blob gives it: the fields are the blob's words, checked by the rules of arguments.hip before a circuit keeps them
@@ -80,8 +83,9 @@ struct Memory { uint32_t first, k; };
 struct Pages {
     uint32_t index;                         // its index among all records of the blob (it comes last)
     uint32_t L, ng, link;                   // limb bits; limbs of an address and of a gap; the blob record index of the LINK it pages
-    uint32_t dst[MAX_PAGE_DSTS];            // destination data columns: p_on, p_addr, p_in, p_out, p_time, alimb_0 .., gap_0 ..
+    uint32_t dst[MAX_PAGE_DSTS];            // destination data columns: p_on, p_addr, p_in_0 .., p_out_0 .., p_time, alimb_0 .., gap_0 ..
     uint32_t n_dst, reserved;               // destinations in use; a word the format reserves was not 0
+    uint32_t V, word4;                      // the value words per address (version 10: word 4 holds V - 1; 1 before), clamped to 1..2; word 4 as the blob has it
 };
 // logup.Open, the OPEN record (version 8), as the blob gives it: the terms of `tag` are answered by another seal, the challenges and the
 // bus total are words of `out` (accumulate.hip zkh_accumulate_open; bus.hip skips the tag's keys)
@@ -90,7 +94,12 @@ struct Open {
     uint32_t tag, alpha, beta, total;       // the open tag; the `out` word offsets of alpha, beta and the total (4 words each)
     uint32_t out_words, reserved;           // the circuit's `out` words; a word the format reserves was not 0
 };
-enum { PG_ON = 0, PG_ADDR = 1, PG_IN = 2, PG_OUT = 3, PG_TIME = 4, PG_LIMBS = 5 };      // the places of Pages::dst
+enum { PG_ON = 0, PG_ADDR = 1, PG_IN = 2, PG_OUT = 3, PG_TIME = 4, PG_LIMBS = 5 };      // the places of Pages::dst of a record with V = 1
+// ... and with V value words per address: p_in_j at PG_IN + j, p_out_j at pg_out(V) + j, then p_time and the limbs
+constexpr uint32_t pg_out(uint32_t V) { return PG_IN + V; }
+constexpr uint32_t pg_time(uint32_t V) { return PG_IN + 2 * V; }
+constexpr uint32_t pg_limbs(uint32_t V) { return PG_IN + 2 * V + 1; }
+static_assert(pg_out(1) == PG_OUT && pg_time(1) == PG_TIME && pg_limbs(1) == PG_LIMBS, "one value word: the places they always were");
 // logup.Arguments
 struct Arguments {
     uint32_t version, k, alpha, beta;       // blob version; accum Fp4 columns; mix word offsets of the two challenges (OPEN: `out` offsets)
@@ -117,6 +126,7 @@ struct Arguments {
         }
         return m;
     }
+    uint32_t page_words() const { return pages.empty() ? 0 : pages[0].V; }     // V of the paged memory, 0: none
     int paged_link() const {                // the place among `links` of the LINK that the PAGES record names, -1: none (or no such LINK)
         for (size_t p = 0; !pages.empty() && p < links.size(); p++)
             if (links[p].index == pages[0].link) return (int)p;

@@ -66,6 +66,17 @@
 // destinations are the lane's own port's, the previous cells the neighbour's port's.  The record's fields are then per lane, not uniform:
 // only this instantiation pays for that, a blob without a joiner runs the instantiations it always ran.  The refused (record, row) is the
 // port's own record's, a 64-bit minimum per wave.  The page scan, head_rank and k_page_of run over the memory's run.
+//
+// WIDE (ZKA1 version 10; logup.py states it once): the paged memory holds V = 2 value words per address, the paged LINK carries nc = 3.
+// The image is FLAT, V W raw words, word j of address a at image[V a + j] (a length that is no multiple of V is refused before any launch;
+// W counts addresses).  An unlinked access takes prev_{1+j} = image[V a + j] and prev_0 = 0, an unlinked load must return both words
+// (residues; the host names the lowest j first).  The head lane of page i writes p_in_j, the tail lane p_out_j from its own record's value
+// columns; the PAGES record's destinations are p_on, p_addr, p_in_0 .., p_out_0 .., p_time, alimb_*, gap_* (arguments.h pg_out, pg_time,
+// pg_limbs).  V is k_links' compile-time kV, in image and table mode, with and without ports; a blob with V = 1 launches the
+// instantiations it always launched.  IMAGE MODE: the two words of an address are adjacent and 8-byte aligned (the image's first word is:
+// checked before the launch), so they are ONE 64-bit load.  TABLE MODE: the table is the FLAT one, V rows (V a + j, in_j, out_j) per page,
+// i major: the head of page i reads rows V i + j (`table_at` is arbitrary: 4-byte loads) and checks each row's address against V a + j; D'
+// pages of the trace must meet V D' rows, and the three table refusals name the flat row.
 #include <algorithm>
 #include <cstdio>
 #include <functional>
@@ -87,9 +98,9 @@ enum : int { PAGED_NO = 0, PAGED_IMAGE = 1, PAGED_TABLE = 2 };      // k_links' 
 struct Paging {
     const Pages* pg;                                    // the PAGES record
     uint32_t paged;                                     // the place among the LINK records of the record it pages
-    const uint32_t* image;                              // PAGED_TABLE: the table's rows of 3 words (address, in, out)
-    uint32_t W;                                         // the image's words
-    uint32_t rows;                                      // PAGED_TABLE: the table's rows
+    const uint32_t* image;                              // PAGED_TABLE: the table's rows of 3 words (address, in, out); kV = 2: the flat image, the flat table
+    uint32_t W;                                         // the image's addresses (kV = 1: its words)
+    uint32_t rows;                                      // PAGED_TABLE: the table's (flat) rows
     const uint32_t *local, *sums;                       // the page scan: k_page_heads' local indices; D and the workgroups' carries
 };
 // what the ported passes of k_links (kPorts) read on top: the memories, the items a run can hold (sort.h SortedRows::cap) and the number of
@@ -122,7 +133,8 @@ __global__ __launch_bounds__(LINK_THREADS) void k_page_heads(const uint32_t* __r
 // kPorts (the blob has a LINK that joins): grid (ceil(cap / LINK_THREADS), memories), blockIdx.y the memory and `pages` whether it is the
 // paged one; the item's source id v gives the lane its own record, links[first + v % k], and its row v / k, the neighbour's v the record and
 // row of the previous access (`prec`, prow): the record's words are per-lane loads here, and nowhere else.
-template <bool kWrite, bool kReads, int kPaged, bool kPorts = false>
+// kV (the paged instantiations): the value words per address of the paged memory, 1 or 2 (this file's header, WIDE).
+template <bool kWrite, bool kReads, int kPaged, bool kPorts = false, int kV = 1>
 __global__ __launch_bounds__(LINK_THREADS) void k_links(const uint32_t* __restrict__ code, uint32_t* data, const Link* __restrict__ links,
                                                         const uint32_t* __restrict__ status, const unsigned long long* __restrict__ keys,
                                                         const uint32_t* __restrict__ rows, uint32_t n, uint32_t A, unsigned long long* __restrict__ bad,
@@ -163,15 +175,28 @@ __global__ __launch_bounds__(LINK_THREADS) void k_links(const uint32_t* __restri
         d = (long long)canonical(clock[row]) - (linked ? canonical(pclock[prow]) : 0) - 1;      // clock 0 is the image's: d = -1 refuses it
     }
     uint32_t addr = 0, word = 0;                          // the paged record's access: its address and, in range, the image's word
+    [[maybe_unused]] uint32_t word1 = 0;                  // kV = 2: the image's second word of the address
     bool inside = true;
     if (pages && access) {
         addr = canonical(group_ptr(code, data, rec->kg)[(size_t)rec->kc * n + row]);
         inside = addr < pa.W;
-        if constexpr (kPaged == PAGED_TABLE) {
+        if constexpr (kPaged == PAGED_TABLE && kV == 2) {
+            if (inside && !linked) {                      // a head: the flat rows 2 page, 2 page + 1 must hold the flat addresses 2 addr, 2 addr + 1
+                const size_t at = (size_t)2 * head_rank(pa.local, pa.sums + 1, t);
+                inside = at + 1 < pa.rows && pa.image[3 * at] == 2 * addr && pa.image[3 * at + 3] == 2 * addr + 1;      // addr < W <= 2^31: no wrap
+                if (at < pa.rows) word = pa.image[3 * at + 1];
+                if (at + 1 < pa.rows) word1 = pa.image[3 * at + 4];
+            }
+        } else if constexpr (kPaged == PAGED_TABLE) {
             if (inside && !linked) {                      // a head: row `page` of the table must be its address's; not listed: refused as `inside` is
                 const uint32_t page = head_rank(pa.local, pa.sums + 1, t);
                 inside = page < pa.rows && pa.image[(size_t)3 * page] == addr;
                 if (page < pa.rows) word = pa.image[(size_t)3 * page + 1];
+            }
+        } else if constexpr (kV == 2) {
+            if (inside) {                                 // the two words of an address: adjacent, 8-byte aligned, one 64-bit load
+                const uint2 both = *(const uint2*)(pa.image + (size_t)2 * addr);
+                word = both.x; word1 = both.y;
             }
         } else if (inside) word = pa.image[addr];
     }
@@ -188,7 +213,8 @@ __global__ __launch_bounds__(LINK_THREADS) void k_links(const uint32_t* __restri
                     for (uint32_t j = 1; j < nc; j++) {
                         const uint32_t* col = group_ptr(code, data, rec->cg[j]) + (size_t)rec->cc[j] * n;
                         const uint32_t* pcol = kPorts ? group_ptr(code, data, prec->cg[j]) + (size_t)prec->cc[j] * n : col;
-                        ok &= col[row] % P == (linked ? pcol[prow] % P : word % P);
+                        if constexpr (kV == 2) ok &= col[row] % P == (linked ? pcol[prow] % P : (j == 1 ? word : word1) % P);
+                        else ok &= col[row] % P == (linked ? pcol[prow] % P : word % P);
                     }
                 }
                 if (!ok) mine = row;
@@ -241,16 +267,18 @@ __global__ __launch_bounds__(LINK_THREADS) void k_links(const uint32_t* __restri
                 data[(size_t)pg->dst[PG_ON] * n + i] = R1;
                 data[(size_t)pg->dst[PG_ADDR] * n + i] = keycol[row];
                 data[(size_t)pg->dst[PG_IN] * n + i] = word;
+                if constexpr (kV == 2) data[(size_t)pg->dst[PG_IN + 1] * n + i] = word1;
                 const uint32_t* pkeycol = kPorts ? group_ptr(code, data, prec->kg) + (size_t)prec->kc * n : keycol;
                 const uint32_t gap = t ? addr - canonical(pkeycol[prow]) - 1 : 0;
                 for (uint32_t j = 0; j < ng; j++) {
-                    data[(size_t)pg->dst[PG_LIMBS + j] * n + i] = fp_encode((addr >> (j * Lp)) & maskp).v;
-                    data[(size_t)pg->dst[PG_LIMBS + ng + j] * n + i] = fp_encode((gap >> (j * Lp)) & maskp).v;
+                    data[(size_t)pg->dst[pg_limbs(kV) + j] * n + i] = fp_encode((addr >> (j * Lp)) & maskp).v;
+                    data[(size_t)pg->dst[pg_limbs(kV) + ng + j] * n + i] = fp_encode((gap >> (j * Lp)) & maskp).v;
                 }
             }
             if (last) {                                   // the tail: the last access of the address
-                data[(size_t)pg->dst[PG_OUT] * n + i] = group_ptr(code, data, rec->cg[1])[(size_t)rec->cc[1] * n + row];
-                data[(size_t)pg->dst[PG_TIME] * n + i] = group_ptr(code, data, rec->cg[0])[(size_t)rec->cc[0] * n + row];
+                data[(size_t)pg->dst[pg_out(kV)] * n + i] = group_ptr(code, data, rec->cg[1])[(size_t)rec->cc[1] * n + row];
+                if constexpr (kV == 2) data[(size_t)pg->dst[pg_out(kV) + 1] * n + i] = group_ptr(code, data, rec->cg[2])[(size_t)rec->cc[2] * n + row];
+                data[(size_t)pg->dst[pg_time(kV)] * n + i] = group_ptr(code, data, rec->cg[0])[(size_t)rec->cc[0] * n + row];
             }
         }
     }
@@ -258,7 +286,8 @@ __global__ __launch_bounds__(LINK_THREADS) void k_links(const uint32_t* __restri
     data[(size_t)rec->dst[0] * n + row] = linked ? R1 : 0;
     data[(size_t)rec->dst[1] * n + row] = last ? R1 : 0;
     for (uint32_t j = 0; j < nc; j++)                     // the previous access's cells; an unlinked access: 0, and the image's word for the paged value
-        data[(size_t)rec->dst[2 + j] * n + row] = linked ? group_ptr(code, data, prec->cg[j])[(size_t)prec->cc[j] * n + prow] : j == 1 ? word : 0;
+        if constexpr (kV == 2) data[(size_t)rec->dst[2 + j] * n + row] = linked ? group_ptr(code, data, prec->cg[j])[(size_t)prec->cc[j] * n + prow] : j == 1 ? word : j == 2 ? word1 : 0;
+        else data[(size_t)rec->dst[2 + j] * n + row] = linked ? group_ptr(code, data, prec->cg[j])[(size_t)prec->cc[j] * n + prow] : j == 1 ? word : 0;
     const uint32_t mask = (1u << L) - 1;                  // L <= 16
     for (uint32_t j = 0; j < nl; j++)
         data[(size_t)rec->dst[2 + nc + j] * n + row] = fp_encode((uint32_t)((unsigned long long)d >> (j * L)) & mask).v;
@@ -270,7 +299,7 @@ __global__ __launch_bounds__(LINK_THREADS) void k_links(const uint32_t* __restri
 // With a page table (mem.table) the image's word is the row's of the table: `page_of` gives the page of the refused row, and two words of
 // that row are read; the table is never read back.
 const char* refusal(zkh_ctx* ctx, const zkh_buf* code, const zkh_buf* data, size_t n, const std::vector<Link>& links, const Memory& ports, uint32_t place, uint32_t row,
-                    bool pages, const PagedFrom& mem, uint32_t pages_index, const std::function<const char*(uint32_t*)>& page_of) {
+                    bool pages, const PagedFrom& mem, uint32_t pages_index, const std::function<const char*(uint32_t*)>& page_of, uint32_t V = 1) {
     const Link& r = links[place];
     const uint32_t port = place - ports.first;
     std::vector<std::vector<uint32_t>> key(ports.k, std::vector<uint32_t>(row + 1)), sel(ports.k, std::vector<uint32_t>(row + 1, R1));
@@ -294,25 +323,28 @@ const char* refusal(zkh_ctx* ctx, const zkh_buf* code, const zkh_buf* data, size
         if (w > 1) return make_err("derive_links: record %u at row %u: write flag %u, not 0 or 1: the witness is refused", r.index, row, w);
     }
     const uint32_t addr = canonical(key[port][row]);
-    uint32_t word = 0;                                    // paged: the image's word at the address, canonical
+    uint32_t words[MAX_PAGE_WORDS] = {};                  // paged: the image's words at the address (V of them, flat: V addr + j), canonical
     if (pages) {
-        const uint32_t W = (uint32_t)(mem.table ? mem.image_words : mem.image->len);
+        const uint32_t W = (uint32_t)((mem.table ? mem.image_words : mem.image->len) / V);      // in addresses
         if (addr >= W) return make_err("derive_links: record %u at row %u: address %u outside the image of %u words: the witness is refused", r.index, row, addr, W);
         if (!mem.table) {
-            ZKH_TRY(zkh_read(ctx, mem.image, &word, addr, 1));
-        } else if (!linked) {                             // the head's page, then its row of the table: its address, its in word
+            ZKH_TRY(zkh_read(ctx, mem.image, words, (size_t)V * addr, V));
+        } else if (!linked) {                             // the head's page, then its rows of the (flat) table: their addresses, their in words; the lowest j first
             uint32_t page, listed;
             ZKH_TRY(page_of(&page));
-            if (page >= mem.D)
-                return make_err("derive_links: record %u at row %u: address %u is page %u of the trace, but the page table has %zu rows: the witness is refused",
-                                pages_index, row, addr, page, mem.D);
-            ZKH_TRY(zkh_read(ctx, mem.table, &listed, mem.table_at + (size_t)3 * page, 1));
-            if (listed != addr)
-                return make_err("derive_links: record %u at row %u: address %u is page %u of the trace, but row %u of the page table holds address %u: the witness "
-                                "is refused", pages_index, row, addr, page, page, listed);
-            ZKH_TRY(zkh_read(ctx, mem.table, &word, mem.table_at + (size_t)3 * page + 1, 1));
+            for (uint32_t j = 0; j < V; j++) {
+                const size_t at = (size_t)V * page + j;
+                if (at >= mem.D)
+                    return make_err("derive_links: record %u at row %u: address %u is page %u of the trace, but the page table has %zu rows: the witness is refused",
+                                    pages_index, row, addr, page, mem.D);
+                ZKH_TRY(zkh_read(ctx, mem.table, &listed, mem.table_at + 3 * at, 1));
+                if (listed != V * addr + j)
+                    return make_err("derive_links: record %u at row %u: address %u is page %u of the trace, but row %zu of the page table holds address %u: the witness "
+                                    "is refused", pages_index, row, addr, page, at, listed);
+                ZKH_TRY(zkh_read(ctx, mem.table, &words[j], mem.table_at + 3 * at + 1, 1));
+            }
         }
-        word = canonical(word);
+        for (uint32_t j = 0; j < V; j++) words[j] = canonical(words[j]);
     }
     if (linked || pages) {
         long long now, before = 0;
@@ -330,7 +362,7 @@ const char* refusal(zkh_ctx* ctx, const zkh_buf* code, const zkh_buf* data, size
                             r.index, row, d, r.nl, r.L);
     }
     for (uint32_t j = 1; (r.flags & LINK_READS) && j < r.nc; j++) {     // a load (the write flag is 0, or something above was named)
-        uint32_t now, before = pages ? word : 0;
+        uint32_t now, before = pages && j <= V ? words[j - 1] : 0;
         ZKH_TRY(read_cell(ctx, code, data, r.cg[j], r.cc[j], n, row, &now));
         if (linked) ZKH_TRY(read_cell(ctx, code, data, pr.cg[j], pr.cc[j], n, prow, &before));
         if (now == before) continue;
@@ -379,6 +411,11 @@ const char* zkh::derive_links_from(zkh_ctx* ctx, const zkh_circuit* c, size_t po
     const uint32_t nr = (uint32_t)links.size();
     ZKH_REQUIRE(nr <= 65535, "derive_links: %u LINK records in one blob (at most 65535)", nr);
     ZKH_REQUIRE(!paging || tabled || image->len <= 0xffffffffull, "derive_links: an image of %zu words (at most 2^32 - 1)", paging && !tabled ? image->len : 0);
+    const uint32_t V = paging ? c->args->pages[0].V : 1;    // the value words per address: the image and the table are flat
+    const size_t flat_words = !paging ? 0 : tabled ? mem.image_words : image->len;
+    ZKH_REQUIRE(flat_words % V == 0, "derive_links: an image of %zu words is not a whole number of addresses of %u value words", flat_words, V);
+    ZKH_REQUIRE(V == 1 || tabled || ((uintptr_t)image->ptr() & 7) == 0, "derive_links: the image of a memory of two value words per address begins at an odd word of its "
+                "buffer (the two words of an address are one 64-bit load)");
     const int paged = paging ? c->args->paged_link() : -1;
     ZKH_REQUIRE(!paging || paged >= 0, "derive_links: the PAGES record names no LINK record");    // set_arguments has refused such a blob
     const bool ported = c->args->ports();               // a LINK joins: the passes run over memories, one sort run per memory
@@ -420,9 +457,9 @@ const char* zkh::derive_links_from(zkh_ctx* ctx, const zkh_circuit* c, size_t po
         ZKH_TRY(zkh_copy_from(ctx, "pages_record", (const uint32_t*)&g, sizeof(Pages) / 4, dpages.out()));
         ZKH_TRY(new_buf(ctx, span, false, local.out()));
         ZKH_TRY(new_buf(ctx, 1 + (size_t)nb, false, sums.out()));
-        pa = tabled ? Paging{(const Pages*)dpages->ptr(), paged_run, mem.table->ptr() + mem.table_at, (uint32_t)mem.image_words,
+        pa = tabled ? Paging{(const Pages*)dpages->ptr(), paged_run, mem.table->ptr() + mem.table_at, (uint32_t)(mem.image_words / V),
                              (uint32_t)std::min<size_t>(mem.D, 0xffffffffu), local->ptr(), sums->ptr()}       // a trace pages at most A rows: more never match
-                    : Paging{(const Pages*)dpages->ptr(), paged_run, image->ptr(), (uint32_t)image->len, 0, local->ptr(), sums->ptr()};
+                    : Paging{(const Pages*)dpages->ptr(), paged_run, image->ptr(), (uint32_t)(image->len / V), 0, local->ptr(), sums->ptr()};
         ProfScope prof(ctx, "pages_scan", 12.0 * span + 8.0 * nb);            // the keys of every position, its index, the workgroups' totals twice
         k_page_heads<<<nb, LINK_THREADS, 0, ctx->stream>>>(sorted.status->ptr(), sorted.keys(), paged_run, span, local->ptr(), sums->ptr());
         ZKH_TRY(last_launch_error("pages_heads"));
@@ -436,8 +473,10 @@ const char* zkh::derive_links_from(zkh_ctx* ctx, const zkh_circuit* c, size_t po
     {
         double cells = 0;                                 // with READS: the write flag and, at most, the value cells at both rows
         for (const Link& r : links) cells += r.flags & LINK_READS ? 1 + 2 * (r.nc - 1) : 0;
-        ProfScope prof(ctx, "links_check", (20.0 * nr + 4.0 * cells + (paging ? 8.0 : 0.0)) * A);   // key and row of every item; the clock at both rows; paged: the key and the image's word
-        if (ported) pass(tabled ? k_links<false, true, PAGED_TABLE, true> : paging ? k_links<false, true, PAGED_IMAGE, true> : k_links<false, true, PAGED_NO, true>);
+        ProfScope prof(ctx, "links_check", (20.0 * nr + 4.0 * cells + (paging ? 4.0 + 4.0 * V : 0.0)) * A);   // key and row of every item; the clock at both rows; paged: the key and the image's words
+        if (V == 2 && ported) pass(tabled ? k_links<false, true, PAGED_TABLE, true, 2> : k_links<false, true, PAGED_IMAGE, true, 2>);
+        else if (V == 2) pass(tabled ? k_links<false, true, PAGED_TABLE, false, 2> : k_links<false, true, PAGED_IMAGE, false, 2>);
+        else if (ported) pass(tabled ? k_links<false, true, PAGED_TABLE, true> : paging ? k_links<false, true, PAGED_IMAGE, true> : k_links<false, true, PAGED_NO, true>);
         else pass(tabled ? k_links<false, true, PAGED_TABLE> : paging ? k_links<false, true, PAGED_IMAGE> : reads ? k_links<false, true, PAGED_NO> : k_links<false, false, PAGED_NO>);
         ZKH_TRY(last_launch_error("links_check"));
     }
@@ -466,19 +505,21 @@ const char* zkh::derive_links_from(zkh_ctx* ctx, const zkh_circuit* c, size_t po
             return zkh_read(ctx, at, page, 0, 1);
         };
         return refusal(ctx, code, data, n, links, mems[mem_of[bad.hi]], bad.hi, bad.lo, paging && mem_of[bad.hi] == mem_of[paged], mem, paging ? c->args->pages[0].index : 0,
-                       page_of);
+                       page_of, V);
     }
     // with ports a memory has up to k A accesses, and their distinct addresses may be more than the A rows its page table has
     ZKH_REQUIRE(!(ported && paging) || bad.extra <= A, "derive_links: record %u: the trace pages %u addresses, but the page table has the %u active rows: the witness is refused",
                 c->args->pages[0].index, bad.extra, A);
     if (tabled) {                                       // no row is refused: every head is listed, so the table has at least the trace's pages
         const uint32_t D = bad.extra;                   // the scan's total, which the check pass sent back with its verdict
-        ZKH_REQUIRE(D == mem.D, "derive_links: record %u: the trace pages %u addresses, but the page table has %zu rows: the witness is refused", c->args->pages[0].index,
-                    D, mem.D);
+        ZKH_REQUIRE((size_t)V * D == mem.D, "derive_links: record %u: the trace pages %u addresses, but the page table has %zu rows: the witness is refused",
+                    c->args->pages[0].index, D, mem.D);                 // the flat table: V rows per page
     }
     {
         ProfScope prof(ctx, "links_write", (20.0 * nr + 4.0 * carried + 4.0 * dsts + (paging ? 12.0 + 4.0 * c->args->pages[0].n_dst : 0.0)) * A);
-        if (ported) pass(tabled ? k_links<true, false, PAGED_TABLE, true> : paging ? k_links<true, false, PAGED_IMAGE, true> : k_links<true, false, PAGED_NO, true>);
+        if (V == 2 && ported) pass(tabled ? k_links<true, false, PAGED_TABLE, true, 2> : k_links<true, false, PAGED_IMAGE, true, 2>);
+        else if (V == 2) pass(tabled ? k_links<true, false, PAGED_TABLE, false, 2> : k_links<true, false, PAGED_IMAGE, false, 2>);
+        else if (ported) pass(tabled ? k_links<true, false, PAGED_TABLE, true> : paging ? k_links<true, false, PAGED_IMAGE, true> : k_links<true, false, PAGED_NO, true>);
         else pass(tabled ? k_links<true, false, PAGED_TABLE> : paging ? k_links<true, false, PAGED_IMAGE> : k_links<true, false, PAGED_NO>);
         ZKH_TRY(last_launch_error("links_write"));
     }

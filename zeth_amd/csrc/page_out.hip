@@ -5,6 +5,12 @@
 // address is >= W or does not follow a smaller one on a row with p_on = 1: a table that repeats an address is REFUSED, so the scatter
 // never writes one word twice; with `nodes` the update of the image's tree follows (image.hip).  THE PROOF (zkh_page_out_proof) only
 // reads: its check pass has a fourth rule, p_in is the word the tree holds, and the ZKU1 proof is built from `nodes` (image.hip).
+// WIDE (ZKA1 version 10; logup.py states it once): V = 2 value words per address.  The image is flat, V W words, and the page-out sets
+// image[V a_i + j] = p_out_j[i]; the proof's fourth rule is that p_in_j is the word the tree's leaf layer holds at V a_i + j ("word j" in its
+// text).  THE FLAT TABLE: to image_tree_update, image_proof_build and everything behind them a wide table of D rows is the table of V D rows
+// (V a_i + j, in_j, out_j), i major, j minor: strictly increasing flat addresses over a flat image.  None of that code knows V: k_page_flat
+// lays the three flat columns out in temporaries (the addresses Montgomery-encoded, as p_addr is: they are read as a column of raw words)
+// and hands them over.  A blob with V = 1 launches what it always launched.
 #include "arguments.h"
 #include "image_tree.h"
 
@@ -20,7 +26,8 @@ constexpr uint32_t PAGE_THREADS = 256;
 // kWrite = true scatters p_out into the image (addresses checked distinct and inside: no word is written twice).
 // kProof (zkh_page_out_proof's check pass): `image` is the LEAF LAYER of the image's tree, the residue of word a at image[a], and a row
 // that passes the three rules is refused when p_in % P is not that word.
-template <bool kWrite, bool kProof = false>
+// kV = 2 (WIDE): W counts addresses, `image` is the flat image (kProof: the flat leaf layer), and every row reads or writes its two words.
+template <bool kWrite, bool kProof = false, int kV = 1>
 __global__ __launch_bounds__(PAGE_THREADS) void k_page_out(const uint32_t* __restrict__ data, const Pages* __restrict__ pg, uint32_t n, uint32_t A, uint32_t* image,
                                                            uint32_t W, unsigned long long* __restrict__ bad, uint32_t* __restrict__ last) {
     const uint32_t t = blockIdx.x * PAGE_THREADS + threadIdx.x;
@@ -32,14 +39,31 @@ __global__ __launch_bounds__(PAGE_THREADS) void k_page_out(const uint32_t* __res
         if (!kWrite) {
             bool ok = v == 0 || v == R1;
             if (v == R1) ok = a < W && (t == 0 || (on[t - 1] % P == R1 && canonical(addrs[t - 1]) < a));
-            if (kProof && ok && v == R1) ok = data[(size_t)pg->dst[PG_IN] * n + t] % P == image[a];
+            if (kProof && ok && v == R1) ok = data[(size_t)pg->dst[PG_IN] * n + t] % P == image[(size_t)kV * a];
+            if constexpr (kV == 2) { if (kProof && ok && v == R1) ok = data[(size_t)pg->dst[PG_IN + 1] * n + t] % P == image[(size_t)2 * a + 1]; }
             if (!ok) mine = t;
             if (v == R1 && (t + 1 == A || on[t + 1] % P != R1)) *last = t;
         } else if (v == R1 && a < W) {
-            image[a] = data[(size_t)pg->dst[PG_OUT] * n + t];
+            image[(size_t)kV * a] = data[(size_t)pg->dst[pg_out(kV)] * n + t];
+            if constexpr (kV == 2) image[(size_t)2 * a + 1] = data[(size_t)pg->dst[pg_out(kV) + 1] * n + t];
         }
     }
     if (!kWrite) report_bad_row(bad, 0, mine);
+}
+
+// WIDE: the flat columns of the table's rows [0, D), one lane per row: addr[2 t + j] = Montgomery(2 a_t + j), in[2 t + j] = p_in_j[t],
+// out[2 t + j] = p_out_j[t] (raw words, copies).  The check pass has passed: a_t < W, so 2 a_t + 1 < the flat image's words <= P.
+__global__ __launch_bounds__(PAGE_THREADS) void k_page_flat(const uint32_t* __restrict__ data, const Pages* __restrict__ pg, uint32_t n, uint32_t D, uint32_t* __restrict__ addr,
+                                                            uint32_t* __restrict__ in, uint32_t* __restrict__ out) {
+    const uint32_t t = blockIdx.x * PAGE_THREADS + threadIdx.x;
+    if (t >= D) return;
+    const uint32_t a = canonical(data[(size_t)pg->dst[PG_ADDR] * n + t]);
+#pragma unroll
+    for (uint32_t j = 0; j < 2; j++) {
+        addr[(size_t)2 * t + j] = fp_encode(2 * a + j).v;
+        in[(size_t)2 * t + j] = data[(size_t)pg->dst[PG_IN + j] * n + t];
+        out[(size_t)2 * t + j] = data[(size_t)pg->dst[pg_out(2) + j] * n + t];
+    }
 }
 
 // Which rule the refused row of the page table broke, as the reference names it: `who` and `tail` frame the text.  nodes: the proof's
@@ -57,9 +81,13 @@ const char* page_refusal(zkh_ctx* ctx, const char* who, const char* tail, const 
     if (!nodes || (row && (pon != 1 || pa >= a)))
         return make_err("%s: record %u at row %u: page address %u does not follow a smaller one (row %u: p_on %u, address %u)%s", who, g.index, row, a, row - 1, pon, pa,
                         tail);
-    uint32_t in, held;
-    ZKH_TRY(read_cell(ctx, data, data, GROUP_DATA, g.dst[PG_IN], n, row, &in));
-    ZKH_TRY(zkh_read(ctx, nodes, &held, nodes->len / 2 + a, 1));
+    uint32_t in = 0, held = 0, j = 0;
+    for (; j < g.V; j++) {                              // the lowest word that differs; "word j" only where there are two
+        ZKH_TRY(read_cell(ctx, data, data, GROUP_DATA, g.dst[PG_IN + j], n, row, &in));
+        ZKH_TRY(zkh_read(ctx, nodes, &held, nodes->len / 2 + (size_t)g.V * a + j, 1));
+        if (in != canonical(held) || j + 1 == g.V) break;
+    }
+    if (g.V > 1) return make_err("%s: record %u at row %u: p_in word %u %u at address %u, the tree holds %u%s", who, g.index, row, j, in, a, canonical(held), tail);
     return make_err("%s: record %u at row %u: p_in %u at address %u, the tree holds %u%s", who, g.index, row, in, a, canonical(held), tail);
 }
 
@@ -68,7 +96,7 @@ const char* page_refusal(zkh_ctx* ctx, const char* who, const char* tail, const 
 // `nodes`), and its one read-back gives the refused row, named by page_refusal, or D.  `who` and `tail` frame every message.
 struct PageOut {
     size_t n;
-    uint32_t A, W, D, nb;                               // active rows; the image's words; the table's rows [0, D); the grid
+    uint32_t A, W, D, nb, V;                            // active rows; the image's addresses (V = 1: its words); the table's rows [0, D); the grid; the value words per address
     const Pages* g;                                     // the PAGES record, and its copy on the device
     Tmp dpages;
     const Pages* record() const { return (const Pages*)dpages->ptr(); }
@@ -82,7 +110,11 @@ const char* page_out_open(zkh_ctx* ctx, const char* who, const char* tail, bool 
     ZKH_REQUIRE(!nodes || (image->len && nodes->len == zkh_image_tree_words(image->len)), "%s: nodes of %zu words; an image of %zu words has a tree of %zu (zkh_image_tree_words)%s",
                 who, nodes ? nodes->len : 0, image->len, zkh_image_tree_words(image->len), tail);
     o->g = &c->args->pages[0];
-    o->W = (uint32_t)image->len;
+    o->V = o->g->V;
+    ZKH_REQUIRE(image->len % o->V == 0, "%s: an image of %zu words is not a whole number of addresses of %u value words%s", who, image->len, o->V, tail);
+    ZKH_REQUIRE(o->V == 1 || image->len <= P, "%s: an image of %zu words of a memory of two value words per address (at most P: its flat addresses are field elements)%s", who,
+                image->len, tail);
+    o->W = (uint32_t)(image->len / o->V);
     o->nb = (o->A + PAGE_THREADS - 1) / PAGE_THREADS;
     bind_thread(ctx);
     BadRow bad;
@@ -90,7 +122,9 @@ const char* page_out_open(zkh_ctx* ctx, const char* who, const char* tail, bool 
     ZKH_TRY(bad.init(ctx));
     {
         ProfScope prof(ctx, "page_out_check", (proof ? 16.0 : 8.0) * o->A);       // p_on and p_addr; the proof's: p_in and the tree's word
-        if (proof) k_page_out<false, true><<<o->nb, PAGE_THREADS, 0, ctx->stream>>>(data->ptr(), o->record(), (uint32_t)o->n, o->A, nodes->ptr() + nodes->len / 2, o->W, bad.ptr(), bad.extra_ptr());
+        if (proof && o->V == 2) k_page_out<false, true, 2><<<o->nb, PAGE_THREADS, 0, ctx->stream>>>(data->ptr(), o->record(), (uint32_t)o->n, o->A, nodes->ptr() + nodes->len / 2, o->W, bad.ptr(), bad.extra_ptr());
+        else if (o->V == 2) k_page_out<false, false, 2><<<o->nb, PAGE_THREADS, 0, ctx->stream>>>(data->ptr(), o->record(), (uint32_t)o->n, o->A, image->ptr(), o->W, bad.ptr(), bad.extra_ptr());
+        else if (proof) k_page_out<false, true><<<o->nb, PAGE_THREADS, 0, ctx->stream>>>(data->ptr(), o->record(), (uint32_t)o->n, o->A, nodes->ptr() + nodes->len / 2, o->W, bad.ptr(), bad.extra_ptr());
         else k_page_out<false><<<o->nb, PAGE_THREADS, 0, ctx->stream>>>(data->ptr(), o->record(), (uint32_t)o->n, o->A, image->ptr(), o->W, bad.ptr(), bad.extra_ptr());
         ZKH_TRY(last_launch_error("page_out_check"));
     }
@@ -101,14 +135,35 @@ const char* page_out_open(zkh_ctx* ctx, const char* who, const char* tail, bool 
     return nullptr;
 }
 
+// WIDE: the flat table of a table that passed, 2 D rows in three temporaries (this file's header), for the tree's update and the proof
+struct FlatTable {
+    Tmp addr, in, out;
+    const char* build(zkh_ctx* ctx, const PageOut& o, const zkh_buf* data) {
+        const size_t rows = std::max<size_t>((size_t)2 * o.D, 1);
+        ZKH_TRY(new_buf(ctx, rows, false, addr.out()));
+        ZKH_TRY(new_buf(ctx, rows, false, in.out()));
+        ZKH_TRY(new_buf(ctx, rows, false, out.out()));
+        if (!o.D) return nullptr;
+        ProfScope prof(ctx, "page_out_flat", 44.0 * o.D);                       // p_addr, two p_in, two p_out; six flat words
+        k_page_flat<<<(o.D + PAGE_THREADS - 1) / PAGE_THREADS, PAGE_THREADS, 0, ctx->stream>>>(data->ptr(), o.record(), (uint32_t)o.n, o.D, addr->ptr(), in->ptr(), out->ptr());
+        return last_launch_error("page_out_flat");
+    }
+};
+
 // zkh_page_out (nodes = NULL) and zkh_page_out_tree: the opening, the scatter, and with `nodes` the tree's update over the D addresses
 const char* page_out(zkh_ctx* ctx, const zkh_circuit* c, size_t po2, size_t zk_cycles, const zkh_buf* data, zkh_buf* image, zkh_buf* nodes) {
     PageOut o;
     ZKH_TRY(page_out_open(ctx, "page_out", ": the image is unchanged", false, c, po2, zk_cycles, data, image, nodes, &o));
     {
         ProfScope prof(ctx, "page_out_write", 16.0 * o.A);
-        k_page_out<true><<<o.nb, PAGE_THREADS, 0, ctx->stream>>>(data->ptr(), o.record(), (uint32_t)o.n, o.A, image->ptr(), o.W, nullptr, nullptr);
+        if (o.V == 2) k_page_out<true, false, 2><<<o.nb, PAGE_THREADS, 0, ctx->stream>>>(data->ptr(), o.record(), (uint32_t)o.n, o.A, image->ptr(), o.W, nullptr, nullptr);
+        else k_page_out<true><<<o.nb, PAGE_THREADS, 0, ctx->stream>>>(data->ptr(), o.record(), (uint32_t)o.n, o.A, image->ptr(), o.W, nullptr, nullptr);
         ZKH_TRY(last_launch_error("page_out_write"));
+    }
+    if (nodes && o.V == 2) {                            // the tree sees the flat table: 2 D strictly increasing flat addresses
+        FlatTable flat;
+        ZKH_TRY(flat.build(ctx, o, data));
+        return image_tree_update(ctx, flat.addr->ptr(), 2 * o.D, image, nodes);
     }
     return nodes ? image_tree_update(ctx, o.column(data, PG_ADDR), o.D, image, nodes) : nullptr;
 }
@@ -121,9 +176,14 @@ extern "C" const char* zkh_page_out_proof(zkh_ctx* ctx, const zkh_circuit* c, si
     ZKH_REQUIRE(ctx && c && data && image && nodes && proof, "page_out_proof: null argument");
     PageOut o;
     ZKH_TRY(page_out_open(ctx, "page_out_proof", "", true, c, po2, zk_cycles, data, image, nodes, &o));
-    const size_t bound = zkh_image_proof_words(o.W, o.D);
+    const size_t bound = zkh_image_proof_words(image->len, (size_t)o.V * o.D);      // WIDE: asked about the flat image and the flat table
     ZKH_REQUIRE(proof->len >= bound && bound <= 0xffffffffull, "page_out_proof: a proof buffer of %zu words; %u pages over an image of %u words take up to %zu (zkh_image_proof_words)",
                 proof->len, o.D, o.W, bound);
+    if (o.V == 2) {
+        FlatTable flat;
+        ZKH_TRY(flat.build(ctx, o, data));
+        return image_proof_build(ctx, flat.addr->ptr(), flat.in->ptr(), flat.out->ptr(), 2 * o.D, image->len, nodes, proof);
+    }
     return image_proof_build(ctx, o.column(data, PG_ADDR), o.column(data, PG_IN), o.column(data, PG_OUT), o.D, image->len, nodes, proof);
 }
 

@@ -185,6 +185,7 @@ ABI = {
     "zkh_derive_links": (_err, [_vp, _vp, _sz, _sz, _vp, _vp]),
     "zkh_derive_all": (_err, [_vp, _vp, _sz, _sz, _vp, _vp]),
     "zkh_circuit_pages": (_i, [_vp]),
+    "zkh_circuit_page_words": (_i, [_vp]),
     "zkh_derive_links_paged": (_err, [_vp, _vp, _sz, _sz, _vp, _vp, _vp]),
     "zkh_derive_all_paged": (_err, [_vp, _vp, _sz, _sz, _vp, _vp, _vp]),
     "zkh_derive_links_paged_table": (_err, [_vp, _vp, _sz, _sz, _vp, _vp, _vp, _sz, _sz, _sz]),
@@ -444,6 +445,12 @@ class Circuit:
         """the arguments (ZKA1 version 7) hold a PAGES record: the memory of its LINK starts from an image (derive_links_paged,
         derive_all_paged) and page_out writes it back; derive_links and derive_all refuse such a circuit"""
         return bool(_lib.zkh_circuit_pages(self.h))
+
+    def page_words(self) -> int:
+        """V, the value words per address of the paged memory (zkh_circuit_page_words): 0 without a PAGES record, else 1 or (ZKA1 version
+        10, a LINK that carries two values) 2.  The image is then V W words, word j of address a at V a + j, and the page-out's table
+        is the flat one of V D rows"""
+        return int(_lib.zkh_circuit_page_words(self.h))
 
     def open_bus(self) -> Optional[Tuple[int, int, int, int]]:
         """(the open tag, the `out` offsets of alpha, beta and the total) of arguments that are an OPEN bus (ZKA1 version 8), else None"""
@@ -992,7 +999,8 @@ class HipHal:
         is (a_i, in_i, out_i), and in_i stands for image[a_i].  table: a Buffer that holds D rows of 3 words from word `table_at` (a
         proof: table_at = 5 + h), or a (D, 3) array, which is uploaded; image_words: W.  The result is derive_links_paged's on the image
         the table was made from, cell for cell as residues.  Raises HalError as derive_links_paged does, and when the table's rows are
-        not the trace's pages (`data` is then unchanged).  Without a PAGES record the table is ignored"""
+        not the trace's pages (`data` is then unchanged).  Without a PAGES record the table is ignored.  A circuit whose page_words() is
+        2 takes the FLAT table: two rows (2 a + j, in_j, out_j) per page, D its flat rows, image_words the flat image's words"""
         buf, at, rows = self._page_table("derive_links_paged_table", table, table_at, D, image_words)
         _check(_lib.zkh_derive_links_paged_table(self.ctx, circuit.h, po2, zk_cycles, code.h, data.h, None if buf is None else buf.h, at, rows, image_words))
 
@@ -1041,7 +1049,7 @@ class HipHal:
         image_proof_words(W, the active rows) words).  Returns exactly the proof's words.  Raises HalError as page_out does, when a
         p_in is not the word the tree holds, and on a `nodes` or `proof` of the wrong size"""
         if proof is None:
-            proof = self.alloc("image_proof", self.image_proof_words(image.size(), (1 << po2) - zk_cycles))
+            proof = self.alloc("image_proof", self.image_proof_words(image.size(), max(1, circuit.page_words()) * ((1 << po2) - zk_cycles)))
         _check(_lib.zkh_page_out_proof(self.ctx, circuit.h, po2, zk_cycles, data.h, image.h, nodes.h, proof.h))
         h = proof.get_at(4)
         header = proof.slice(0, 5 + h).to_vec()

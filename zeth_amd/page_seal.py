@@ -145,6 +145,14 @@ def commitment_bytes(columns: int, po2: int) -> int:
     return 4 * (5 * columns + 64) << po2
 
 
+def _refuse_wide(who: str, seg_prover) -> None:
+    """The tie puts (p_addr, p_in, p_out) on the open bus: a memory of two value words per address would need one row per word there, hence
+    flat-address columns in the trace.  Refused before anything is sealed."""
+    words = getattr(seg_prover.circuit, "page_words", lambda: 1)()           # a circuit handle that cannot be asked pages what every circuit paged before
+    if words > 1:
+        raise _hal.HalError(f"{who}: the segment's memory holds {words} value words per address (ZKA1 version 10): the tie of a wide memory is not built")
+
+
 def seal_tied_group(who: str, kind: int, seg_prover, seg, code, data, out_prefix, page_prover, page_segs, proof, proof_words: int, nodes_before, nodes_after,
                     check: bool, check_table: bool, plan_where: str = "host", dirty=None, hold_bytes: int = 0):
     """The two passes of `seal_tied` (kind 8) and `seal_tied_tree` (kind 9), on open_chain -> (the segment's receipt, [the parts'
@@ -153,6 +161,7 @@ def seal_tied_group(who: str, kind: int, seg_prover, seg, code, data, out_prefix
     hold_bytes: the device bytes pass one may keep for pass two (`seal_tied`); 0 holds nothing.  The held seals are a prefix of the
     group in its order, the segment first: `held` lists per held seal (its commitment, its trace if the trace is this call's, what its
     witness call returned).  Whatever ends the call, a refusal included, every held commitment and trace is released first."""
+    _refuse_wide(who, seg_prover)
     k, hal, page_segs = PAGE_KINDS[kind], seg_prover.hal, list(page_segs)
     witgen = part_witgen(who, seg_prover, k, nodes_before, nodes_after, dirty)
     proof, po2, zk, page_code, plan = open_chain(who, page_prover, k, page_segs, proof, proof_words, plan_where,
@@ -309,6 +318,7 @@ def seal_tied_tree_from_proof(seg_prover, seg, host_code, host_data, out_prefix,
     traces lie in hal.host_alloc blocks (the uploads are then enqueued, as seal_host_witness does).  The other operands are
     seal_tied_tree's."""
     who, hal = "seal_tied_tree_from_proof", seg_prover.hal
+    _refuse_wide(who, seg_prover)
     if not isinstance(proof, _hal.Buffer):
         proof = hal.copy_from("image_proof", np.ascontiguousarray(proof, dtype=np.uint32).reshape(-1))
     words = proof.size()
@@ -352,6 +362,7 @@ def preflight_paged_run(seg_prover, segs, witnesses, image, tree, pinned: bool =
     the proof from the tree as it is, writes the page table back, brings the tree up to date and checks that the proof walks to the new
     root.  No derived trace is kept.  A segment that pages no address (an empty table) is refused here: its group has no dirty node and
     is sealed from the tree (`seal_tied_tree`); its page-out has changed nothing."""
+    _refuse_wide("preflight_paged_run", seg_prover)
     segs, witnesses, hal = list(segs), list(witnesses), seg_prover.hal
     if len(segs) != len(witnesses):
         raise _hal.HalError(f"preflight_paged_run: {len(segs)} segments, but {len(witnesses)} witnesses")

@@ -393,10 +393,10 @@ class SegmentProver:
         words = walked = table = None
         if proof and dirty:
             root_before = self.hal.image_root(tree)
-            buf = self.hal.alloc("image_proof", self.hal.image_proof_words(image.size(), (1 << seg.po2) - seg.zk_cycles))
+            buf = self.hal.alloc("image_proof", self.hal.image_proof_words(image.size(), max(1, self.circuit.page_words()) * ((1 << seg.po2) - seg.zk_cycles)))
             words = self.hal.page_out_proof(self.circuit, seg.po2, seg.zk_cycles, data, image, tree, proof=buf)
         elif proof and walk:
-            buf = self.hal.alloc("image_proof", self.hal.image_proof_words(image.size(), (1 << seg.po2) - seg.zk_cycles))
+            buf = self.hal.alloc("image_proof", self.hal.image_proof_words(image.size(), max(1, self.circuit.page_words()) * ((1 << seg.po2) - seg.zk_cycles)))
             words = self.hal.page_out_proof(self.circuit, seg.po2, seg.zk_cycles, data, image, tree, proof=buf)
             walked = self.hal.image_proof_walk(buf, self.hal.image_root(tree), words=words.size)
         elif proof:
