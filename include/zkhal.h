@@ -429,9 +429,19 @@ const char* zkh_derive_links(zkh_ctx*, const zkh_circuit*, size_t po2, size_t zk
  * about (V W, V D).  The proof's fourth refusal says "p_in word j X at address A" when V = 2.  zkh_derive_links_paged_table takes the flat
  * table: D counts its flat rows and image_words the flat image's words, the head of page i reads rows V i + j and checks each address
  * against V a + j, the trace's D' pages must meet V D' rows, and the three table refusals name the flat row.  The tie of a wide memory
- * (kinds 8 and 9) is not built: its table's rows on the open bus would need flat-address columns in the trace. */
+ * (kinds 8 and 9) needs flat-address columns in the trace: its table's rows on the open bus are the flat table's.
+ * FLAT (ZKA1 version 11; versions 1..10 are word for word what they were): PAGES word 5 holds F, the number of flat-address destinations,
+ * 0 or 2 and 2 only with V = 2 (any other value, and F = 2 with V = 1, is refused); words 6, 7 hold the data columns p_flat_0, p_flat_1 (0
+ * when F = 0), words 8..15 stay reserved.  Header word 7 carries bit 20 (0x100000, FLAT) exactly when F = 2: a version-11 blob without it
+ * is no ZKA1 blob, bit 20 with no record of F = 2 is refused.  The links stage writes p_flat_j[i] = the canonical Montgomery encoding of
+ * 2 a_i + j on page i < D (from the decoded address; p_addr stays the raw key word) and 0 on rows D <= i < A, in image and in table
+ * mode, with and without ports, in the write pass it always ran: no new launch, the refusals unchanged.  p_flat_j are destinations like
+ * the others (one writer, no record reads them, none is a multiplicity; terms may read them).  zkh_circuit_page_flats: F, and 0 without a
+ * PAGES record.  A circuit constrains p_on (p_flat_j - 2 p_addr - j) = 0 and puts +p_on (p_flat_j, p_in_j, p_out_j) on the open bus, so
+ * that a wide segment's open total is zkh_table_fingerprint of its flat table and kinds 8 and 9 tie it to its page-out as they are. */
 int zkh_circuit_pages(const zkh_circuit*);
 int zkh_circuit_page_words(const zkh_circuit*);
+int zkh_circuit_page_flats(const zkh_circuit*);
 const char* zkh_derive_links_paged(zkh_ctx*, const zkh_circuit*, size_t po2, size_t zk_cycles, const zkh_buf* code, zkh_buf* data, const zkh_buf* image);
 const char* zkh_derive_links_paged_table(zkh_ctx*, const zkh_circuit*, size_t po2, size_t zk_cycles, const zkh_buf* code, zkh_buf* data, const zkh_buf* table,
                                          size_t table_at, size_t D, size_t image_words);

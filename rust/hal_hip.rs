@@ -398,6 +398,12 @@ impl HipCircuitHal {
         unsafe { sys::zkh_circuit_page_words(self.circuit) as usize }
     }
 
+    /// F, the flat-address destinations of the PAGES record (`zkh_circuit_page_flats`): 2 when the links stage writes
+    /// `p_flat_j = 2 a + j` beside a wide page table (ZKA1 version 11), which the tie of a wide memory needs; else 0.
+    pub fn page_flats(&self) -> usize {
+        unsafe { sys::zkh_circuit_page_flats(self.circuit) as usize }
+    }
+
     /// `derive_links` from a memory image of raw Montgomery words (`zkh_derive_links_paged`): an unlinked access of the paged LINK
     /// record takes `image[address]` as its previous access (at clock 0), and the PAGES record's page table is written.  Panics on a
     /// refused witness as `derive_links` does, and on an address outside the image, a clock 0 or an unlinked load that does not return

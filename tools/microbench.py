@@ -31,7 +31,9 @@ the words of the table, of the proof and of the two trees, and the copy of the t
 whole tied group on M28's setup sealed in two passes next to the same group with hold_bytes for everything, alternating, and for one
 part zkh_commit_data + zkh_prove_begin_held next to zkh_data_root + zkh_prove_begin, with the bytes held; M32: zkh_derive_links on three memory pairs as the PORTS of one memory (ZKA1 version 9) next to the version-6 blob of three separate
 memories; M33: WIDE (ZKA1 version 10), zkh_derive_links_paged and zkh_page_out_tree on SYN-LOOKUP-paged-wide FULL (two value words per address)
-next to SYN-LOOKUP-paged FULL on the same addresses and clocks, alternating; M31: paging in from a page
+next to SYN-LOOKUP-paged FULL on the same addresses and clocks, alternating; M34: FLAT (ZKA1 version 11), zkh_derive_links_paged on the
+version-11 blob (flat-address columns) next to the version-10 blob on M33's addresses, and zkh_accumulate_open on SYN-LOOKUP-tied-wide next to
+SYN-LOOKUP-tied, alternating; M31: paging in from a page
 table, zkh_derive_links_paged_table next to zkh_derive_links_paged on the same SYN-LOOKUP-paged FULL trace at two image sizes, alternating,
 with both calls' passes) on one MI355X, through the C ABI (HipHal).
 
@@ -1833,6 +1835,89 @@ def main() -> None:
                           "image_addresses": W, "runs": runs, "reps": args.reps, **arms,
                           "derive_wide_vs_narrow": round(med["wide_v10.derive_links_paged"] / med["narrow_v7.derive_links_paged"], 3),
                           "page_out_tree_wide_vs_narrow": round(med["wide_v10.page_out_tree"] / med["narrow_v7.page_out_tree"], 3)}), flush=True)
+        del keep
+    if want("M34"):
+        # FLAT (ZKA1 version 11): what the two flat-address columns cost.  (a) zkh_derive_links_paged on the version-11 blob (SYN-LOOKUP-paged-wide
+        # with flats) next to the version-10 blob (SYN-LOOKUP-paged-wide) in the same run, on M33's addresses, write flags, clocks and values: the
+        # version-10 arm's data group is the version-11 arm's without its last two columns.  Two more scattered 4-byte stores per page and two
+        # more coalesced ones per row below the table, in the write pass.  (b) zkh_accumulate_open on SYN-LOOKUP-tied-wide (two tie terms of
+        # width 3 and the wide memory's terms) next to SYN-LOOKUP-tied.  Timed in alternation, `runs` windows of `reps` calls; median and
+        # spread (min, max) of the windows; then the passes by their events.  No threshold.
+        from zeth_amd.circuits import logup, syn_lookup
+        runs, zk = 7, 1994
+        A = n - zk
+        shape, W = syn_lookup.FULL, 1 << 20
+        image_w = rand_fp(np.random.default_rng(33), 2 * W)                  # M33's image
+        spread = lambda ts: {"median_ms": round(float(np.median(ts)) * 1e3, 4), "min_ms": round(min(ts) * 1e3, 4), "max_ms": round(max(ts) * 1e3, 4)}   # noqa: E731
+        kw = dict(link=True, reads=True, pages=True)
+        code_h, flat_h, _out = syn_lookup.witness(shape, args.po2, zk, seed=33, image=image_w, wide=True, flat=True, **kw)
+        _code, narrow_h, _out = syn_lookup.witness(shape, args.po2, zk, seed=33, image=image_w[:W].copy(), **kw)
+        assert np.array_equal(_code, code_h)
+        challenge = rand_fp(np.random.default_rng(34), 8)
+        arms, fns, keep, pages = {}, [], [], {}
+        for name, build, full_h, image_h in (("flat_v11", dict(wide=True, flat=True), flat_h, image_w),
+                                             ("wide_v10", dict(wide=True), flat_h.reshape(-1, n)[:-2].reshape(-1), image_w),
+                                             ("tied_wide_v11", dict(wide=True, flat=True, tied=True), flat_h, image_w),
+                                             ("tied_v8", dict(tied=True), narrow_h, image_w[:W].copy())):
+            desc, blob = syn_lookup.build_syn_lookup(shape, **kw, **build)
+            pargs = logup.Arguments.parse(blob)
+            assert int(blob[1]) == (11 if build.get("flat") else 10 if build.get("wide") else 8)
+            circuit = hal.load_circuit(desc, jit=False)
+            circuit.set_arguments(blob)
+            assert circuit.page_flats() == (2 if build.get("flat") else 0)
+            bare_h = full_h.reshape(-1, n).copy()
+            bare_h[circuit.derived_data_columns(), :A] = 0
+            code, data, image = hal.alloc_elem("code", code_h.size), hal.alloc_elem("data", bare_h.size), hal.alloc_elem("image", image_h.size)
+            code.write(code_h)
+            data.write(bare_h.reshape(-1))
+            image.write(image_h)
+            derive = lambda circuit=circuit, code=code, data=data, image=image: hal.derive_links_paged(circuit, args.po2, zk, code, data, image)      # noqa: E731
+            derive()
+            lk = [c for r in pargs.records if isinstance(r, (logup.Link, logup.Pages)) for c in r.dsts] + list(pargs.pages.flats)
+            assert np.array_equal(data.to_vec().reshape(-1, n)[lk], full_h.reshape(-1, n)[lk]), f"{name}: the derived columns differ from the host-made ones"
+            pages[name] = int((full_h.reshape(-1, n)[pargs.pages.p_on, :A] != 0).sum())
+            if build.get("tied"):
+                data.write(np.ascontiguousarray(full_h).reshape(-1))
+                hal.reduce_elem(code)
+                hal.reduce_elem(data)
+                accum = hal.alloc_elem("accum", (4 * pargs.k) << args.po2)
+                fn = lambda circuit=circuit, code=code, data=data, accum=accum: hal.accumulate_open(circuit, args.po2, zk, 0x34, code, data, challenge, accum)      # noqa: E731
+                total = fn()
+                rows = pages[name] * (2 if build.get("wide") else 1)
+                d = full_h.reshape(-1, n)
+                cols = ([(pargs.pages.flats[j], pargs.pages.p_ins[j], pargs.pages.p_outs[j]) for j in range(2)] if build.get("wide") else
+                        [(pargs.pages.p_addr, pargs.pages.p_in, pargs.pages.p_out)])
+                table = np.stack([np.stack([d[c, :pages[name]] for c in trio], axis=1) for trio in cols], axis=1).reshape(-1, 3)
+                table[:, 0] = logup._dec(table[:, 0]).astype(np.uint32)       # ZKU1 rows hold the address as an integer
+                want_total = hal.table_fingerprint(hal.copy_from("table", table.reshape(-1)), 0, rows, challenge)
+                assert np.array_equal(total, want_total), f"{name}: the open total is not the fingerprint of the (flat) table"
+                fns.append((name + ".accumulate_open", fn))
+                keep.append((circuit, code, data, image, accum))
+            else:
+                fns.append((name + ".derive_links_paged", derive))
+                keep.append((circuit, code, data, image))
+            del bare_h
+        assert pages["flat_v11"] == pages["wide_v10"] == pages["tied_wide_v11"] == pages["tied_v8"], "the witnesses page the same addresses"
+        t = {name: [] for name, _ in fns}
+        for _ in range(runs):
+            for name, fn in fns:
+                t[name].append(timed(hal, fn, args.reps))
+        for name, fn in fns:
+            hal.prof_enable(True)
+            hal.prof_reset()
+            for _ in range(args.reps):
+                fn()
+            hal.sync()
+            steps = {r["name"]: round(r["total_ms"] / max(r["calls"], 1), 4) for r in hal.prof_get() if r["calls"]}
+            hal.prof_enable(False)
+            arms[name] = {**spread(t[name]), "steps_ms": steps}
+        med = {k: float(np.median(v)) for k, v in t.items()}
+        print(json.dumps({"bench": "M34", "circuit": "SYN-LOOKUP-paged-wide FULL with flat-address columns next to without; SYN-LOOKUP-tied-wide next to SYN-LOOKUP-tied",
+                          "po2": args.po2, "accesses": A, "pages": pages["flat_v11"], "image_addresses": W, "runs": runs, "reps": args.reps, **arms,
+                          "derive_flat_vs_wide": round(med["flat_v11.derive_links_paged"] / med["wide_v10.derive_links_paged"], 3),
+                          "links_write_flat_vs_wide_ms": [arms["flat_v11.derive_links_paged"]["steps_ms"].get("links_write"),
+                                                          arms["wide_v10.derive_links_paged"]["steps_ms"].get("links_write")],
+                          "accumulate_open_tied_wide_vs_tied": round(med["tied_wide_v11.accumulate_open"] / med["tied_v8.accumulate_open"], 3)}), flush=True)
         del keep
     hal.close()
 

@@ -24,7 +24,7 @@ The degree of a column's constraint is 1 (gate) + max(1 + t, max_i(deg sel_i + d
 
 ZKA1 layout (u32 words; canonical integers, not Montgomery words)::
 
-    [0] magic 'ZKA1' = 0x5a4b4131   [1] version = 1 .. 10     [2] k = accum Fp4 columns   [3] alpha mix word offset
+    [0] magic 'ZKA1' = 0x5a4b4131   [1] version = 1 .. 11     [2] k = accum Fp4 columns   [3] alpha mix word offset
     [4] beta mix word offset       [5] n_terms       [6] reserved = 0 (version 4: n_records)
     [7] reserved = 0 (version 6: the number of LINK records with READS, at least 1; version 7: that number | 0x10000)
     terms: n_terms x 16 words, sorted by column:
@@ -81,6 +81,14 @@ ZKA1 layout (u32 words; canonical integers, not Montgomery words)::
       record, an OPEN record, a LINK that joins | 0x80000 (bit 19, WIDE) exactly when V = 2: a version-10 blob without bit 19 is no ZKA1
       blob, bit 19 with V = 1 is refused.  The builder writes version 10 only then (`derive_pages` on a LINK that carries two values takes
       the wider destination list).
+
+    Version 11: version 10's layout, and the PAGES record may have the two FLAT-ADDRESS destinations.  PAGES word [5] holds F, their
+      number: 0 or 2, and 2 only with V = 2; any other value, and F = 2 with V = 1, is refused.  Words [6], [7] hold the data columns
+      p_flat_0, p_flat_1 (0 when F = 0); words 8..15 stay reserved.  The 16 destination slots could not take them: V = 2 with ng = 4 uses
+      15.  Header word 7 carries bit 20 (0x100000, FLAT) exactly when F = 2: a version-11 blob without bit 20 is no ZKA1 blob, bit 20 with
+      no record of F = 2 is refused; bits 16 .. 19 are set exactly when the blob holds what they name.  p_flat_j are destinations like the
+      others: one writer, no record reads them, none is a multiplicity (still only p_on); terms may read them.  The builder writes
+      version 11 only when a PAGES record has flats (`derive_pages(..., flats=)`).
 
 PORTS (a LINK record with JOINS, ZKA1 version 9): several accesses per row to ONE memory.  A memory is a run of k <= 8 consecutive LINK
 records: the head, then the records that join it, in blob order; port q is the record at head + q, and every port has the head's nc, L, nl
@@ -189,7 +197,17 @@ paged memory holds V value words per address, V the paged LINK's nc - 1 (1 or 2)
   * PAGING FROM A TABLE: `table` is the flat one and image_words the flat image's.  The head of page i reads rows V i .. V i + V - 1 and
     checks each row's address against V a + j; D pages of the trace must meet V D rows.  The three table refusals keep their shape and
     name the flat row.
-Left out: one paged memory per blob; the tie of a wide memory.  The circuits that check p_in /
+FLAT (the PAGES record's flats, ZKA1 version 11): the tie puts one row (address, in, out) per word of the flat table on the open bus, and
+a wide page row holds two of them, so the trace carries their addresses.  Stated once:
+  * For page i < D with address a_i: p_flat_j[i] = the canonical Montgomery encoding of the integer 2 a_i + j, j = 0, 1.  p_addr stays the
+    raw key word and may be >= P; the flat columns come from the decoded address and never are.  Rows D <= i < A hold 0, like the rest
+    of the table.  In image and in table mode, with and without ports; the check passes and every refusal are what they were.
+  * THE CONSTRAINT (`page_constraints`): p_on (p_flat_j - 2 p_addr - j) = 0.  The address limbs bound p_addr below 2^29, so
+    2 p_addr + 1 < 2^30 < P and the field equation names one integer; page addresses increase strictly, so the flat addresses are distinct.
+    A row with p_on = 0 is not constrained and need not be: every term that reads p_flat_j has the multiplicity p_on.
+  * THE TIE: the terms +p_on (p_flat_j, p_in_j, p_out_j) under TIE_TAG are the rows of the flat table, so the open total of a wide
+    segment is `table_fingerprint` of its flat table, and nothing behind the page-out knows V.
+Left out: one paged memory per blob; the tie of a wide memory WITHOUT flats is refused.  The circuits that check p_in /
 p_out against those roots are the page-out circuits (p2_page.py and after it), and THE OPEN BUS below ties their rows to this table.
 
 WHO WRITES A DATA COLUMN (`_check_owned` behind `check_columns` and `check_links`; csrc/arguments.h says the same).  A data column
@@ -500,11 +518,13 @@ MAX_PAGE_LIMBS = 4
 MAX_PAGE_WORDS = 2                             # V, the value words per address of a paged memory (version 10: 1 or 2)
 PAGES_BIT = 0x10000                            # header word 7, bit 16 (version 7): the blob has a PAGES record
 WIDE_BIT = 0x80000                             # header word 7, bit 19 (version 10): the PAGES record pages two value words per address
+FLAT_BIT = 0x100000                            # header word 7, bit 20 (version 11): the PAGES record has the two flat-address destinations
 
 
 @dataclass(frozen=True)
 class Pages:
-    """A PAGES record as the blob holds it (ZKA1 version 7; version 10: `nv`): the fields are the blob's words, `check_pages` the rules"""
+    """A PAGES record as the blob holds it (ZKA1 version 7; version 10: `nv`; version 11: `flats`): the fields are the blob's words,
+    `check_pages` the rules"""
     limb_bits: int                             # L
     ng: int                                    # limbs of a page address and of a gap
     link: int                                  # the blob record index of the LINK record it pages
@@ -513,6 +533,9 @@ class Pages:
     nv: int = 1                                # V, the value words per address (version 10: word 4 holds V - 1); the paged LINK's nc - 1
     nv_word: Optional[int] = None              # the blob's word 4 where it is above 1 (parser only, version 10)
     wide_word: bool = field(default=False, compare=False)    # the blob's version reads word 4 as V - 1 (parser only: the text of the reserved words' refusal)
+    flats: Tuple[int, ...] = ()                # the flat-address destinations p_flat_0, p_flat_1 (version 11: word 5 holds F = 0 or 2, words 6, 7 the columns)
+    nf_word: Optional[int] = None              # the blob's word 5 where it is neither 0 nor 2 (parser only, version 11)
+    flat_word: bool = field(default=False, compare=False)    # the blob's version reads word 5 as F (parser only: the text of the reserved words' refusal)
     kind = KIND_PAGES
 
     p_on = property(lambda self: self.dsts[0])
@@ -529,7 +552,7 @@ class Pages:
         return 3 + 2 * self.nv + 2 * self.ng
 
     def words(self) -> List[int]:
-        w = [KIND_PAGES, self.limb_bits, self.ng, self.link, self.nv - 1] + [0] * 11 + list(self.dsts)
+        w = [KIND_PAGES, self.limb_bits, self.ng, self.link, self.nv - 1, len(self.flats)] + list(self.flats) + [0] * (10 - len(self.flats)) + list(self.dsts)
         return w + [0] * (PAGES_WORDS - len(w))
 
 
@@ -541,15 +564,21 @@ def _paged_link(records: Sequence, r: "Pages") -> Optional[Link]:
 
 def check_pages(terms: Sequence[Term], records: Sequence, group_sizes=None) -> Optional[str]:
     """the PAGES record that breaks a rule, named by its index among all `records` (all of them are its peers), or None: (a) the ranges
-    of L and ng, the reserved words, word 4 (version 10: V - 1, 0 or 1), and its target a LINK record with READS and nc = 1 + V that joins
+    of L and ng, the reserved words, word 4 (version 10: V - 1, 0 or 1), word 5 (version 11: F, 0 or 2, and 2 only with V = 2), and its target a LINK record with READS and nc = 1 + V that joins
     no other (version 9: the head of its memory, whose ports then have READS and the same nc as well); then (b) .. (e) of `_check_owned`,
-    its sources being its LINK's and p_on the one destination that may be a multiplicity"""
+    its sources being its LINK's and p_on the one destination that may be a multiplicity (p_flat_j are destinations like the others)"""
     def clause_a(i, r, _sizes):
         if not (1 <= r.limb_bits <= 16 and 1 <= r.ng <= MAX_PAGE_LIMBS and r.limb_bits * r.ng <= MAX_ORDER_BITS):
             return (f"record {i}: a PAGES record of {r.ng} limbs of {r.limb_bits} bits (1..{MAX_PAGE_LIMBS} limbs of 1..16 bits, at most "
                     f"{MAX_ORDER_BITS} bits in all)")
         if r.nv_word is not None:
             return f"record {i}: word 4 of a PAGES record is {r.nv_word} (V - 1: 0 = one value word per address, 1 = two)"
+        if r.nf_word is not None:
+            return f"record {i}: word 5 of a PAGES record is {r.nf_word} (F, the flat-address destinations: 0 or 2)"
+        if r.flats and r.nv == 1:
+            return f"record {i}: a PAGES record of one value word per address has {len(r.flats)} flat-address destinations (they are the flat addresses of two value words)"
+        if (r.reserved or len(r.dsts) != r.n_dsts()) and (r.flat_word or r.flats):
+            return f"record {i}: a reserved word of a PAGES record is not 0 (words 8..15, words 6 and 7 without flat-address destinations, and the unused destination words)"
         if r.reserved or len(r.dsts) != r.n_dsts():
             return (f"record {i}: a reserved word of a PAGES record is not 0 (words 5..15 and the unused destination words)" if r.wide_word or r.nv > 1 else
                     f"record {i}: a reserved word of a PAGES record is not 0 (words 4..15 and the unused destination words)")
@@ -639,7 +668,7 @@ def _check_owned(terms: Sequence[Term], records: Sequence, of, clause_a, group_s
     def view(i, r):
         if isinstance(r, Pages):
             t = _paged_link(records, r)
-            return _Owned(i, () if t is None else tuple(t.srcs), tuple(r.dsts), True, 1)
+            return _Owned(i, () if t is None else tuple(t.srcs), tuple(r.dsts) + tuple(r.flats), True, 1)
         return _Owned(i, tuple(r.srcs), tuple(r.dsts), isinstance(r, Link), 2 if isinstance(r, Link) else 0)
     peers = [view(i, r) for i, r in enumerate(records)]
     mine = peers if of is None else [v for v in peers if isinstance(records[v.index], of)]
@@ -763,7 +792,14 @@ class Arguments:
         return self.pages is not None and self.pages.nv > 1
 
     @property
+    def flat(self) -> bool:
+        """the PAGES record has the flat-address destinations (version 11: bit 20 of header word 7)"""
+        return self.pages is not None and len(self.pages.flats) > 0
+
+    @property
     def version(self) -> int:
+        if self.flat:
+            return 11
         if self.wide:
             return 10
         if self.ports:
@@ -785,7 +821,7 @@ class Arguments:
     def blob(self) -> np.ndarray:
         words = [ARGS_MAGIC, self.version, self.k, self.alpha, self.beta, len(self.terms), len(self.records),
                  self.reads | (PAGES_BIT if self.pages is not None else 0) | (OPEN_BIT if self.open is not None else 0) |
-                 (PORTS_BIT if self.ports else 0) | (WIDE_BIT if self.wide else 0)]
+                 (PORTS_BIT if self.ports else 0) | (WIDE_BIT if self.wide else 0) | (FLAT_BIT if self.flat else 0)]
         for t in _by_column(self.terms):
             rec = [t.col, 0 if t.sign == 1 else 1, NONE if t.sel is None else t.sel,
                    NONE if t.mult is None else t.mult[0], 0 if t.mult is None else t.mult[1], t.tag % P, len(t.tuple_cols), t.flags()]
@@ -800,9 +836,9 @@ class Arguments:
     @staticmethod
     def parse(blob: Sequence[int]) -> "Arguments":
         d = [int(x) for x in np.asarray(blob, dtype=np.uint32)]
-        if len(d) < ARGS_HEADER or d[0] != ARGS_MAGIC or d[1] not in (1, 2, 3, 4, 5, 6, 7, 8, 9, 10) or (d[1] == 6 and d[7] == 0) or \
+        if len(d) < ARGS_HEADER or d[0] != ARGS_MAGIC or d[1] not in (1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11) or (d[1] == 6 and d[7] == 0) or \
                 (d[1] == 7 and not d[7] & PAGES_BIT) or (d[1] == 8 and not d[7] & OPEN_BIT) or (d[1] == 9 and not d[7] & PORTS_BIT) or \
-                (d[1] == 10 and not d[7] & WIDE_BIT):
+                (d[1] == 10 and not d[7] & WIDE_BIT) or (d[1] == 11 and not d[7] & FLAT_BIT):
             raise ValueError("not a ZKA1 argument blob")
         version = d[1]
         k, alpha, beta, n = d[2], d[3], d[4], d[5]
@@ -846,8 +882,11 @@ class Arguments:
             if sizes[i] == PAGES_WORDS and r[0] == KIND_PAGES:
                 nv = 1 + min(r[4], MAX_PAGE_WORDS - 1) if version >= 10 else 1      # version 10: word 4 holds V - 1; reserved before
                 n_dst = min(16, 3 + 2 * nv + 2 * min(r[2], 8))
-                records.append(Pages(r[1], r[2], r[3], tuple(r[16: 16 + n_dst]), bool(any(r[5 if version >= 10 else 4:16]) or any(r[16 + n_dst:])), nv,
-                                     r[4] if version >= 10 and r[4] >= MAX_PAGE_WORDS else None, version >= 10))
+                nf = 2 if version >= 11 and r[5] == 2 else 0                # version 11: word 5 holds F, words 6, 7 the columns; reserved before
+                records.append(Pages(r[1], r[2], r[3], tuple(r[16: 16 + n_dst]),
+                                     bool(any(r[6 + nf if version >= 11 else 5 if version >= 10 else 4:16]) or any(r[16 + n_dst:])), nv,
+                                     r[4] if version >= 10 and r[4] >= MAX_PAGE_WORDS else None, version >= 10, tuple(r[6: 6 + nf]),
+                                     r[5] if version >= 11 and r[5] not in (0, 2) else None, version >= 11))
                 continue
             if sizes[i] == LINK_WORDS:
                 nc = min(r[3], MAX_CARRIED)
@@ -875,8 +914,10 @@ class Arguments:
             word7 ^= OPEN_BIT                                                # bit 17 says OPEN
         if version == 9 or (version >= 10 and d[7] & PORTS_BIT):
             word7 ^= PORTS_BIT                                               # bit 18 says PORTS
-        if version >= 10:
+        if version == 10 or (version >= 11 and d[7] & WIDE_BIT):
             word7 ^= WIDE_BIT                                                # bit 19 says WIDE
+        if version >= 11:
+            word7 ^= FLAT_BIT                                                # bit 20 says FLAT
         if version >= 6 and word7 != n_reads:
             raise ValueError(f"ZKA1: header word 7 is {word7}, the blob has {n_reads} LINK records with READS")
         if version >= 7 and d[7] & PAGES_BIT and not has_pages:
@@ -892,8 +933,13 @@ class Arguments:
             raise ValueError("ZKA1: header word 7 has bit 18 (PORTS), but no LINK record joins")
         if version >= 10 and joiner and not d[7] & PORTS_BIT:
             raise ValueError("ZKA1: a LINK record joins, but header word 7 lacks bit 18 (PORTS)")
-        if version >= 10 and not any(isinstance(r, Pages) and (r.nv > 1 or r.nv_word is not None) for r in records):
+        two = any(isinstance(r, Pages) and (r.nv > 1 or r.nv_word is not None) for r in records)
+        if (version == 10 or (version >= 11 and d[7] & WIDE_BIT)) and not two:
             raise ValueError("ZKA1: header word 7 has bit 19 (WIDE), but no PAGES record pages two value words per address")
+        if version >= 11 and two and not d[7] & WIDE_BIT:
+            raise ValueError("ZKA1: a PAGES record pages two value words per address, but header word 7 lacks bit 19 (WIDE)")
+        if version >= 11 and not any(isinstance(r, Pages) and (r.flats or r.nf_word is not None) for r in records):
+            raise ValueError("ZKA1: header word 7 has bit 20 (FLAT), but no PAGES record has flat-address destinations")
         problem = check_sorted(terms) or check_derived(terms) or check_open(terms, records, (alpha, beta)) or _check_records(terms, records)
         if problem:
             raise ValueError(f"ZKA1: {problem}")
@@ -1032,13 +1078,15 @@ class LogupBuilder(CircuitBuilder):
                                  len(dsts) - 2 - len(carried), tuple(int(c) for c in dsts),
                                  write=None if write is None else (int(write[0]), int(write[1])), joins=head))
 
-    def derive_pages(self, link_record: Link, dsts: Sequence[int], limb_bits: int) -> Pages:
+    def derive_pages(self, link_record: Link, dsts: Sequence[int], limb_bits: int, flats: Optional[Sequence[int]] = None) -> Pages:
         """the memory of the LINK record `link_record` (one of this builder's, with READS and a clock and one value column) is PAGED
         (ZKA1 version 7): its first access to an address takes the word of an image as its previous access, at clock 0, and the
         library fills the data columns `dsts` = p_on, p_addr, p_in, p_out, p_time, alimb_0 .., gap_0 .. (5 + 2 ng of them) with the page
         table: the distinct addresses in order, each with the image's word and what its last access left (`reference_links` with an
         image; zkh_derive_links_paged).  A LINK that carries two values (nc = 3) pages a memory of two value words per address (ZKA1
-        version 10) and takes the wider list p_on, p_addr, p_in_0, p_in_1, p_out_0, p_out_1, p_time, alimb_0 .., gap_0 .. (7 + 2 ng)"""
+        version 10) and takes the wider list p_on, p_addr, p_in_0, p_in_1, p_out_0, p_out_1, p_time, alimb_0 .., gap_0 .. (7 + 2 ng).
+        flats = (p_flat_0, p_flat_1), only on such a LINK (ZKA1 version 11): two more data columns, which the library fills with the flat
+        addresses 2 a_i + j of page i (the module docstring, FLAT); `page_constraints` ties them to p_addr"""
         at = next((i for i, r in enumerate(self.records) if r is link_record), None)
         if at is None:
             at = self.records.index(link_record) if link_record in self.records else -1
@@ -1050,7 +1098,13 @@ class LogupBuilder(CircuitBuilder):
                              f"p_out_1, p_time, ng address limbs, ng gap limbs; 5 + 2 ng for one value)")
         if nv == 1 and (len(dsts) < 7 or (len(dsts) - 5) % 2):
             raise ValueError(f"derive_pages: {len(dsts)} destinations (5 + 2 ng: p_on, p_addr, p_in, p_out, p_time, ng address limbs, ng gap limbs)")
-        return self._record(Pages(int(limb_bits), (len(dsts) - 3 - 2 * nv) // 2, at, tuple(int(c) for c in dsts), nv=nv))
+        flats = tuple(int(c) for c in flats) if flats is not None else ()
+        if flats and nv == 1:
+            raise ValueError("derive_pages: flat-address columns on a LINK that carries one value (they are the flat addresses 2 a + j of a memory of two "
+                             "value words per address)")
+        if flats and len(flats) != 2:
+            raise ValueError(f"derive_pages: {len(flats)} flat-address columns (2: p_flat_0, p_flat_1)")
+        return self._record(Pages(int(limb_bits), (len(dsts) - 3 - 2 * nv) // 2, at, tuple(int(c) for c in dsts), nv=nv, flats=flats))
 
     def paged(self, record: Link) -> Optional[Pages]:
         """the PAGES record that pages the memory of the LINK `record` (the head it names, or a port that joins that head), or None"""
@@ -1069,7 +1123,11 @@ class LogupBuilder(CircuitBuilder):
         `body_inner` (gated by the body selector: every active row but the first) p_on (1 - p_on@1) = 0, so that p_on is a prefix, and
         p_on (p_addr - p_addr@1 - 1 - sum_j 2^(jL) gap_j) = 0 -> (inner, body_inner).  Degree 3 with the gates.  Range-checked address
         limbs and range-checked gaps (lookups, L ng <= 29 as in `order_constraints`) make the page addresses strictly increasing, hence
-        distinct: no address is paged in twice, and memory cannot fork."""
+        distinct: no address is paged in twice, and memory cannot fork.
+        A record with FLATS (ZKA1 version 11) adds onto `inner` p_on (p_flat_j - 2 p_addr - j) = 0 for j = 0, 1, degree 3 with the gate.  The
+        address limbs bound p_addr below 2^29, so 2 p_addr + 1 < 2^30 < P and the field equation names one integer, the flat address; the
+        page addresses increase strictly, so the flat addresses 2 a_i + j are pairwise distinct.  A record without flats emits exactly
+        what it emitted."""
         if not isinstance(record, Pages):
             raise ValueError("page_constraints: not a PAGES record")
         L = record.limb_bits
@@ -1082,6 +1140,9 @@ class LogupBuilder(CircuitBuilder):
         body_inner = self.and_eqz(body_inner, self.mul(on, self.sub(one, self.get(GROUP_DATA, record.p_on, 1))))
         gap = self.sub(self.sub(self.sub(addr, self.get(GROUP_DATA, record.p_addr, 1)), one), self._limb_sum(record.gaps, L))
         body_inner = self.and_eqz(body_inner, self.mul(on, gap))
+        for j, c in enumerate(record.flats):                                 # p_on (p_flat_j - 2 p_addr - j) = 0
+            flat = self.sub(self.get(GROUP_DATA, c), self.mul(self.const(2), addr))
+            inner = self.and_eqz(inner, self.mul(on, flat if j == 0 else self.sub(flat, self.const(j))))
         return inner, body_inner
 
     def link_constraints(self, inner, record: Link):
@@ -1704,7 +1765,9 @@ def reference_links(args: Arguments, po2: int, zk_cycles: int, code, data, image
             gap = np.zeros(D, dtype=np.int64)
             gap[1:] = a[1:] - a[:-1] - 1
             top = slice(0, D)
-            writes.append((list(pages.dsts), slice(0, A), 0))
+            writes.append((list(pages.dsts) + list(pages.flats), slice(0, A), 0))
+            for j, c in enumerate(pages.flats):                              # FLAT: the canonical encoding of 2 a_i + j, from the decoded address
+                writes.append((c, top, _enc(2 * a + j).astype(np.uint32)))
             writes.append((pages.p_on, top, np.uint32(_R)))
             writes.append((pages.p_addr, top, take(keys, row[first], port[first])))
             for j in range(V):                                               # the head writes p_in_j, the tail p_out_j from its own record

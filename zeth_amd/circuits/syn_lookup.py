@@ -71,7 +71,15 @@ and the page table its 2 V value columns (`pages_layout(wide=True)`: p_on, p_add
 the bus (tag 1): the access +(addr, v0, v1, time), the previous access -(addr, pv0, pv1, ptime), the page-in +p_on (p_addr, p_in_0, p_in_1),
 the key (addr, v0, v1, 0), and the page-out -p_on (p_addr, p_out_0, p_out_1, p_time).  The LINK carries (time, val, val1), the PAGES record
 has V = 2, and logup.link_constraints states (1 - w)(c_j - prev_j) = 0 for both values.  The image is 2 W words, word j of address a at
-2 a + j (`witness(..., wide=True)`).  It does not combine with `tied`: the tie of a wide memory is not built.
+2 a + j (`witness(..., wide=True)`).  It does not combine with `tied` as it is: its table's rows on the open bus need flat-address columns.
+`flat=True` (with `wide`; ZKA1 version 11) gives them: the page table gains p_flat_0, p_flat_1 after its gap limbs (`pages_layout(flat=True)`),
+the PAGES record has them as its flats, so the library fills them with 2 a_i + j, and logup.page_constraints adds p_on (p_flat_j - 2 p_addr
+- j) = 0.  Without `tied` it is a closed-bus circuit of its own, whose two columns no term reads.
+SYN-LOOKUP-tied-wide (`syn_lookup_tied_wide`, `build_syn_lookup(shape, link=True, reads=True, pages=True, wide=True, flat=True, tied=True)`;
+`ports=True` is accepted): that circuit on the OPEN bus, out = 16 words as SYN-LOOKUP-tied's, ANOTHER description with its own control root.
+Two more terms, the last ones: +p_on (p_flat_j, p_in_j, p_out_j) of tag 2 (logup.TIE_TAG), j = 0, 1: the rows of the FLAT table
+(2 a_i + j, in_j, out_j), which is the table the page-out's proof holds and its chain takes off the bus.  `last` closes on
+F = logup.table_fingerprint of that flat table.  `witness(..., wide=True, flat=True)` is the wide witness with the two columns.
 """
 from __future__ import annotations
 
@@ -140,17 +148,18 @@ PAGE_W = 5                          # p_on, p_addr, p_in, p_out, p_time
 TIED_OUT, OUT_ALPHA, OUT_BETA, OUT_TOTAL = 16, 4, 8, 12      # SYN-LOOKUP-tied's out: 4 zero words ‖ alpha ‖ beta ‖ F
 
 
-def pages_layout(n_words: int, n_limbs: int, n_mem: int = 1, order_limbs: int = ORDER_LIMBS, wide: bool = False):
+def pages_layout(n_words: int, n_limbs: int, n_mem: int = 1, order_limbs: int = ORDER_LIMBS, wide: bool = False, flat: bool = False):
     """data column indices of SYN-LOOKUP-paged's page table, after `reads_layout`'s write flag: [p_on, p_addr, p_in, p_out, p_time,
-    alimb_0 .. alimb_{order_limbs-1}, gap_0 .. gap_{order_limbs-1}]; wide: [p_on, p_addr, p_in_0, p_in_1, p_out_0, p_out_1, p_time, the limbs]"""
+    alimb_0 .. alimb_{order_limbs-1}, gap_0 .. gap_{order_limbs-1}]; wide: [p_on, p_addr, p_in_0, p_in_1, p_out_0, p_out_1, p_time, the limbs]; flat (with wide):
+    then [p_flat_0, p_flat_1], the flat addresses of the page's two words"""
     base = n_words + n_words * n_limbs + 1 + (LINK_W + order_limbs + 2 * bool(wide)) * n_mem + n_mem
-    return [base + e for e in range(PAGE_W + 2 * bool(wide) + 2 * order_limbs)]
+    return [base + e for e in range(PAGE_W + 2 * bool(wide) + 2 * order_limbs + 2 * bool(flat))]
 
 
 def build_syn_lookup(shape: Shape = FULL, derive: bool = False, sort: bool = False,
                      sort_keys: Tuple[int, ...] = SORT_KEYS, limbs: bool = False, order: bool = False,
                      order_limbs: int = ORDER_LIMBS, link: bool = False, reads: bool = False, pages: bool = False,
-                     tied: bool = False, ports: bool = False, wide: bool = False) -> Tuple[np.ndarray, np.ndarray]:
+                     tied: bool = False, ports: bool = False, wide: bool = False, flat: bool = False) -> Tuple[np.ndarray, np.ndarray]:
     """-> (ZKC1 description, ZKA1 argument blob); derive: the table term's multiplicity is derived by the library (version-2 blob,
     the description unchanged); sort: every permuted copy is the library's sorted copy of its memory tuple by the tuple positions
     `sort_keys` (version-3 blob, the description unchanged); limbs: every word's limbs are a LIMBS record (version-4 blob, the
@@ -162,11 +171,15 @@ def build_syn_lookup(shape: Shape = FULL, derive: bool = False, sort: bool = Fal
     the page table's rows as one more term (version-8 blob, another description, 16 `out` words); it needs `pages`; ports: the n_mem memory
     pairs are the ports of ONE memory (version-9 blob; without `pages` SYN-LOOKUP-reads' description unchanged); it needs `link` and `reads`,
     and with it `pages` takes any n_mem; wide: SYN-LOOKUP-paged-wide, the paged memory holds two value words per address (version-10 blob,
-    another description); it needs `pages`, takes `ports`, and refuses `tied`"""
+    another description); it needs `pages`, takes `ports`, and refuses `tied` without `flat`; flat: the wide page table has the two
+    flat-address columns p_flat_j = 2 p_addr + j (version-11 blob, another description); it needs `wide`, and with `tied` it is
+    SYN-LOOKUP-tied-wide, whose tie terms are the flat table's rows"""
     n_words, n_limbs, limb_bits, n_mem = shape
-    if wide and tied:
+    if flat and not wide:
+        raise ValueError("build_syn_lookup: flat=True adds the flat-address columns of a memory of two value words per address: it needs wide=True")
+    if wide and tied and not flat:
         raise ValueError("build_syn_lookup: tied=True with wide=True: the tie of a memory of two value words per address is not built (its table's rows on the "
-                         "open bus need flat-address columns in the trace)")
+                         "open bus need flat-address columns in the trace): flat=True adds them")
     if wide and not pages:
         raise ValueError("build_syn_lookup: wide=True gives the paged memory two value words per address: it needs pages=True")
     if tied and not pages:
@@ -190,11 +203,12 @@ def build_syn_lookup(shape: Shape = FULL, derive: bool = False, sort: bool = Fal
         wd = m + 1 + sum(len(c) for c in lcols) + n_mem * bool(reads)
         n_terms = n_words * n_limbs + 1 + 3 * n_mem + n_mem * order_limbs
     wcols = reads_layout(n_words, n_limbs, n_mem, order_limbs, wide) if reads else [None] * n_mem
-    pcols = pages_layout(n_words, n_limbs, n_mem, order_limbs, wide) if pages else []
+    pcols = pages_layout(n_words, n_limbs, n_mem, order_limbs, wide, flat) if pages else []
     pw = PAGE_W + 2 * bool(wide)                                             # the table's columns before its limbs
+    fcols = pcols[pw + 2 * order_limbs:]                                     # flat: p_flat_0, p_flat_1, after the limbs
     if pages:
         wd += len(pcols)
-        n_terms += 2 - n_mem + 2 * order_limbs + bool(tied)                     # a port: its access and its previous one; the table's two terms once
+        n_terms += 2 - n_mem + 2 * order_limbs + (2 if flat else 1) * bool(tied)                     # a port: its access and its previous one; the table's two terms once
     k = (n_terms + 2) // 3
     if tied:
         b = LogupBuilder((4 * k, N_CODE, wd), (TIED_OUT, 8), alpha=OUT_ALPHA, beta=OUT_BETA, open_bus=(TIE_TAG, OUT_TOTAL))
@@ -228,8 +242,11 @@ def build_syn_lookup(shape: Shape = FULL, derive: bool = False, sort: bool = Fal
         specs.append(dict(tuple_cols=[(GROUP_DATA, c_addr), (GROUP_DATA, c_val), (GROUP_DATA, c_time)], sign=-1, mult=(GROUP_DATA, c_last), tag=1))
     specs += [dict(tuple_cols=[(GROUP_DATA, c)], tag=0) for cols in ocols for c in cols[1:]]
     specs += [dict(tuple_cols=[(GROUP_DATA, c)], tag=0) for cols in lcols for c in cols[LINK_W:LINK_W + order_limbs]]
-    specs += [dict(tuple_cols=[(GROUP_DATA, c)], tag=0) for c in pcols[pw:]]
-    if tied:                                                                 # the table's rows, for the page-out chain to take off the bus
+    specs += [dict(tuple_cols=[(GROUP_DATA, c)], tag=0) for c in pcols[pw:pw + 2 * order_limbs]]
+    if tied and flat:                                                        # the FLAT table's rows (2 a + j, in_j, out_j): one term per word
+        for j in range(2):
+            specs.append(dict(tuple_cols=[(GROUP_DATA, fcols[j]), (GROUP_DATA, pcols[2 + j]), (GROUP_DATA, pcols[4 + j])], sign=1, mult=(GROUP_DATA, pcols[0]), tag=TIE_TAG))
+    elif tied:                                                               # the table's rows, for the page-out chain to take off the bus
         specs.append(dict(tuple_cols=[(GROUP_DATA, pcols[1]), (GROUP_DATA, pcols[2]), (GROUP_DATA, pcols[3])], sign=1, mult=(GROUP_DATA, pcols[0]), tag=TIE_TAG))
     for i, s in enumerate(specs):
         b.term(i // 3, **s)
@@ -243,7 +260,9 @@ def build_syn_lookup(shape: Shape = FULL, derive: bool = False, sort: bool = Fal
         carried, prevs = ([(GROUP_DATA, c[-2])], [c[-1]]) if wide else ([], [])                  # wide: the second value word and its previous one
         links.append(b.derive_links(None, (GROUP_DATA, c[0]), [(GROUP_DATA, c[2]), (GROUP_DATA, c[1])] + carried, [c[3], c[4], c[6], c[5]] + prevs + c[LINK_W:LINK_W + order_limbs],
                                     limb_bits, write=None if w is None else (GROUP_DATA, w), joins=links[0] if ports and links else None))
-    table = b.derive_pages(links[0], pcols, limb_bits) if pages else None
+    table = None
+    if pages:
+        table = b.derive_pages(links[0], pcols[:pw + 2 * order_limbs], limb_bits, flats=fcols) if flat else b.derive_pages(links[0], pcols, limb_bits)
     # words = sum of their limbs, on active rows
     inner = b.true()
     for kk in range(n_words):
@@ -330,13 +349,21 @@ def syn_lookup_tied() -> Tuple[np.ndarray, np.ndarray]:
     return build_syn_lookup(FULL, link=True, reads=True, pages=True, tied=True)
 
 
+def syn_lookup_tiny_tied_wide() -> Tuple[np.ndarray, np.ndarray]:
+    return build_syn_lookup(TINY, link=True, reads=True, pages=True, tied=True, wide=True, flat=True)
+
+
+def syn_lookup_tied_wide() -> Tuple[np.ndarray, np.ndarray]:
+    return build_syn_lookup(FULL, link=True, reads=True, pages=True, tied=True, wide=True, flat=True)
+
+
 def _enc(x) -> np.ndarray:
     return ((np.asarray(x, dtype=np.uint64) % np.uint64(P)) * np.uint64((1 << 32) % P) % np.uint64(P)).astype(np.uint32)
 
 
 def witness(shape: Shape, po2: int, zk_cycles: int, seed: int = 1, count: bool = True, sort: bool = True, addr_range: int = 1 << 20,
             sort_keys: Tuple[int, ...] = SORT_KEYS, limbs: bool = True, order=None, order_limbs: int = ORDER_LIMBS, link=None,
-            reads: bool = False, pages=None, image=None, ports: bool = False, wide: bool = False):
+            reads: bool = False, pages=None, image=None, ports: bool = False, wide: bool = False, flat: bool = False):
     """-> (code, data, out_global) host arrays of raw Montgomery words: random words below min(P, 2^(n_limbs L)) split into limbs
     (limbs=False: zero, for the library to split), the table's multiplicities (count=False: zero, for the library to derive), random
     memory tuples (addresses below `addr_range`) and their copy stably sorted by the tuple positions `sort_keys`, (addr, time)
@@ -361,7 +388,12 @@ def witness(shape: Shape, po2: int, zk_cycles: int, seed: int = 1, count: bool =
     wide: SYN-LOOKUP-paged-wide's witness (`build_syn_lookup(..., pages=True, wide=True)`; it needs `pages`): two value words per address.
     `image` is the FLAT image of 2 W words, word j of address a at 2 a + j; every access has a second value column, a load takes both
     words of the last store or of the image, and the page table carries p_in_0, p_in_1, p_out_0, p_out_1.  The addresses, write flags and
-    clocks of a seed are those of the witness without `wide` over an image of W words"""
+    clocks of a seed are those of the witness without `wide` over an image of W words.
+    flat: the witness of `build_syn_lookup(..., wide=True, flat=True)` (it needs `wide`): the page table's two flat-address columns,
+    2 a_i + j on the table's rows, host-made when `pages` is True and zero when it is False.  Nothing new is drawn: the addresses, flags,
+    clocks and values of a seed are those of the wide witness (the blinding rows, drawn last, cover two more columns)"""
+    if flat and not wide:
+        raise ValueError("witness: flat=True adds the flat-address columns of a memory of two value words per address: it needs wide=True")
     if wide and pages is None:
         raise ValueError("witness: wide=True gives the paged memory two value words per address: it needs pages=")
     if ports and (link is None or not reads):
@@ -377,9 +409,10 @@ def witness(shape: Shape, po2: int, zk_cycles: int, seed: int = 1, count: bool =
     lcols = link_layout(n_words, n_limbs, n_mem, order_limbs, wide) if link is not None else []
     wd = m_col + 1 + (sum(len(c) for c in lcols) + n_mem * bool(reads) if lcols else 2 * MEM_W * n_mem + sum(len(c) for c in ocols))
     wcols = reads_layout(n_words, n_limbs, n_mem, order_limbs, wide) if reads else []
-    pcols = pages_layout(n_words, n_limbs, n_mem, order_limbs, wide) if pages is not None else []
+    pcols = pages_layout(n_words, n_limbs, n_mem, order_limbs, wide, flat) if pages is not None else []
     V = 2 if wide else 1
     wd += len(pcols)
+    pcols, fcols = (pcols[:-2], pcols[-2:]) if flat else (pcols, [])         # the walks fill the table's own columns, then the flat ones
     n = 1 << po2
     A = n - zk_cycles
     T = 1 << limb_bits
@@ -414,7 +447,7 @@ def witness(shape: Shape, po2: int, zk_cycles: int, seed: int = 1, count: bool =
                 data[limbs[kk][j], :A] = limb
             counts += np.bincount(limb.astype(np.int64), minlength=T)
     if ports:
-        _ported_witness(data, rng, lcols, wcols, pcols, held0 if pcols else None, A, addr_range, limb_bits, order_limbs, link, pages, counts, wide)
+        _ported_witness(data, rng, lcols, wcols, pcols, held0 if pcols else None, A, addr_range, limb_bits, order_limbs, link, pages, counts, wide, fcols)
     for i in range(0 if ports else n_mem):
         addr = rng.integers(0, addr_range, size=A, dtype=np.uint64)
         val = rng.integers(0, P, size=A, dtype=np.uint64)
@@ -434,7 +467,7 @@ def witness(shape: Shape, po2: int, zk_cycles: int, seed: int = 1, count: bool =
                 held[a] = val1[r]
             data[wcols[i], :A] = store
         if pcols:
-            _paged_witness(data, lcols[i], pcols, addr, val, held0, A, limb_bits, order_limbs, link, pages, counts, val1 if wide else None)
+            _paged_witness(data, lcols[i], pcols, addr, val, held0, A, limb_bits, order_limbs, link, pages, counts, val1 if wide else None, fcols)
             continue
         if lcols:
             _link_witness(data, lcols[i], addr, val, A, limb_bits, order_limbs, link, counts)
@@ -492,10 +525,10 @@ def _link_witness(data, cols, addr, val, A, limb_bits, order_limbs, fill, counts
         counts += np.bincount(limb, minlength=T)
 
 
-def _paged_witness(data, cols, pcols, addr, val, image, A, limb_bits, order_limbs, fill, fill_pages, counts, val1=None):
+def _paged_witness(data, cols, pcols, addr, val, image, A, limb_bits, order_limbs, fill, fill_pages, counts, val1=None, fcols=()):
     """the memory pair of SYN-LOOKUP-paged: `_link_witness` with times row + 1 and the image (canonical words) behind every first access,
     and the page table from a walk over the distinct addresses in order.  val1: the second value word of every access (wide: the image
-    is flat, two words per address, and the pair's columns end on val1, pval1)"""
+    is flat, two words per address, and the pair's columns end on val1, pval1).  fcols: the two flat-address columns, or none"""
     c_addr, c_val, c_time, c_linked, c_last, c_pval, c_ptime, *c_limbs = cols
     V = 1 if val1 is None else 2
     if V == 2:
@@ -537,13 +570,15 @@ def _paged_witness(data, cols, pcols, addr, val, image, A, limb_bits, order_limb
         assert a >> (order_limbs * limb_bits) == 0
         if fill_pages:
             data[pcols, i] = row
+            if len(fcols):
+                data[fcols, i] = [2 * a, 2 * a + 1]
         for v in row[3 + 2 * V:]:
             counts[v] += 1
         below = a
     counts[0] += 2 * order_limbs * (A - len(seen))                           # the rows below the table look their zero limbs up as well
 
 
-def _ported_witness(data, rng, lcols, wcols, pcols, image, A, addr_range, limb_bits, order_limbs, fill, fill_pages, counts, wide=False):
+def _ported_witness(data, rng, lcols, wcols, pcols, image, A, addr_range, limb_bits, order_limbs, fill, fill_pages, counts, wide=False, fcols=()):
     """the k memory pairs of SYN-LOOKUP-reads-ported as the ports of ONE memory, the host's way: one sequential walk over the accesses in
     (row, port) order with the last access of every address in a dictionary.  image: the paged memory's image (canonical words), or None.
     wide: two value words per address (the image flat, the pairs' columns ending on val1, pval1)"""
@@ -593,6 +628,8 @@ def _ported_witness(data, rng, lcols, wcols, pcols, image, A, addr_range, limb_b
         assert a >> (order_limbs * limb_bits) == 0
         if fill_pages:
             data[pcols, i] = row
+            if len(fcols):
+                data[fcols, i] = [2 * a, 2 * a + 1]
         for v in row[3 + 2 * V:]:
             counts[v] += 1
         below = a

@@ -14,7 +14,8 @@
 // Nothing reads a derived multiplicity.  A term's multiplicity is the host's column or a derived one, and of a LINK's destinations
 // linked and last (only they) may be the multiplicity of a term that is not derived.  The PAGES record (version 7) is one more writer of
 // the links stage: it reads what the LINK it pages reads, writes the page table, and of its destinations p_on may be such a multiplicity
-// (version 10, two value words per address: p_in_1 and p_out_1 are destinations like the others; still only p_on).
+// (version 10, two value words per address: p_in_1 and p_out_1 are destinations like the others; still only p_on.  Version 11: so are the
+// flat-address destinations p_flat_0, p_flat_1: one writer, no record reads them, none is a multiplicity; terms may read them).
 //
 // THE READ RULE (a LINK record with READS, ZKA1 version 6; links.hip's header has it in full): the write flag is one more source of the
 // record, the host's column.  On an access it must be 0 or 1; a load (0) returns, in every carried column but the clock, what the
@@ -38,6 +39,7 @@ constexpr uint32_t KIND_LINK = 3, LINK_WORDS = 32, MAX_CARRIED = 3, MAX_LINK_LIM
 constexpr uint32_t LINK_READS = 1;                  // LINK word 5, bit 0 (version 6): the record carries the read rule
 constexpr uint32_t KIND_PAGES = 4, PAGES_WORDS = 32, MAX_PAGE_LIMBS = 4, MAX_PAGE_WORDS = 2;   // a PAGES record (version 7); V, its value words per address (version 10)
 constexpr uint32_t MAX_PAGE_DSTS = 3 + 2 * MAX_PAGE_WORDS + 2 * MAX_PAGE_LIMBS;
+constexpr uint32_t MAX_PAGE_FLATS = 2;              // F, the flat-address destinations of a PAGES record (version 11: 0 or 2, in words 6, 7; word 5 holds F)
 constexpr uint32_t PAGES_BIT = 0x10000;             // header word 7, bit 16 (version 7): the blob has a PAGES record
 constexpr uint32_t OPEN_BIT = 0x20000;              // header word 7, bit 17 (version 8): the blob has an OPEN record
 constexpr uint32_t KIND_OPEN = 5, OPEN_WORDS = 16;  // the OPEN record (version 8): the bus closes on `out` words, not on zero
@@ -45,6 +47,7 @@ constexpr uint32_t LINK_JOINS = 2;                  // LINK word 5, bit 1 (versi
 constexpr uint32_t MAX_PORTS = 8;                   // the records of one memory, the head included
 constexpr uint32_t PORTS_BIT = 0x40000;             // header word 7, bit 18 (version 9): a LINK record joins
 constexpr uint32_t WIDE_BIT = 0x80000;              // header word 7, bit 19 (version 10): the PAGES record pages two value words per address
+constexpr uint32_t FLAT_BIT = 0x100000;             // header word 7, bit 20 (version 11): the PAGES record has the two flat-address destinations
 constexpr uint32_t MAX_ORDER_BITS = 29;             // logup.MAX_ORDER_BITS: a negative difference stays out of the limbs' range
 
 // logup.Term as the blob gives it: the fields are the blob's words, checked by the rules of arguments.hip before a circuit keeps them
@@ -86,6 +89,9 @@ struct Pages {
     uint32_t dst[MAX_PAGE_DSTS];            // destination data columns: p_on, p_addr, p_in_0 .., p_out_0 .., p_time, alimb_0 .., gap_0 ..
     uint32_t n_dst, reserved;               // destinations in use; a word the format reserves was not 0
     uint32_t V, word4;                      // the value words per address (version 10: word 4 holds V - 1; 1 before), clamped to 1..2; word 4 as the blob has it
+    // behind every field an earlier kernel reads, so that none of their offsets moves:
+    uint32_t F, word5;                      // the flat-address destinations in use (version 11: word 5 holds F; 0 before), 0 or 2; word 5 as the blob has it
+    uint32_t flat[MAX_PAGE_FLATS];          // p_flat_0, p_flat_1: the data columns that take 2 a_i + j (links.hip kFlat)
 };
 // logup.Open, the OPEN record (version 8), as the blob gives it: the terms of `tag` are answered by another seal, the challenges and the
 // bus total are words of `out` (accumulate.hip zkh_accumulate_open; bus.hip skips the tag's keys)
@@ -127,6 +133,7 @@ struct Arguments {
         return m;
     }
     uint32_t page_words() const { return pages.empty() ? 0 : pages[0].V; }     // V of the paged memory, 0: none
+    uint32_t page_flats() const { return pages.empty() ? 0 : pages[0].F; }     // F of the PAGES record: 2 with flat-address destinations, else 0
     int paged_link() const {                // the place among `links` of the LINK that the PAGES record names, -1: none (or no such LINK)
         for (size_t p = 0; !pages.empty() && p < links.size(); p++)
             if (links[p].index == pages[0].link) return (int)p;

@@ -1,6 +1,6 @@
 // arguments.hip — the ZKA1 argument blob (layout: zeth_amd/circuits/logup.py; DESIGN.md §2 ARGUMENTS): its decoding into
 // zkh::Arguments (terms, from version 4 derived-column records, from version 5 LINK records, from version 6 their read rule, from version 7 the PAGES
-// record, from version 8 the OPEN record, from version 9 the ports of a memory: LINK records that join a head, from version 10 a PAGES record of two value words per address), the rules a circuit's arguments keep (check_sorted, check_derived, then check_owned over the LIMBS / ORDER records, over the LINK records
+// record, from version 8 the OPEN record, from version 9 the ports of a memory: LINK records that join a head, from version 10 a PAGES record of two value words per address, from version 11 its flat-address destinations), the rules a circuit's arguments keep (check_sorted, check_derived, then check_owned over the LIMBS / ORDER records, over the LINK records
 // and over the PAGES record), and the entry points that attach them to a circuit and ask what they derive.
 // decode_arguments is the only code that knows the blob's words; everything else, here and in the consumers, reads decoded terms.
 #include "arguments.h"
@@ -17,8 +17,8 @@ namespace {
 // significant key first); bits 2, 3, 7, the position fields of unused keys and, without bit 1, everything above bit 0 are reserved.
 // A reserved bit is recorded, not refused: the rules refuse it where they reach the term (flag_word_rule), after the circuit-shape checks.
 const char* decode_arguments(const uint32_t* a, size_t words, Arguments* out) {
-    ZKH_REQUIRE(words >= ARGS_HEADER && a[0] == ARGS_MAGIC && a[1] >= 1 && a[1] <= 10 && (a[1] != 6 || a[7] != 0) && (a[1] != 7 || (a[7] & PAGES_BIT)) && (a[1] != 8 || (a[7] & OPEN_BIT)) &&
-                (a[1] != 9 || (a[7] & PORTS_BIT)) && (a[1] != 10 || (a[7] & WIDE_BIT)),
+    ZKH_REQUIRE(words >= ARGS_HEADER && a[0] == ARGS_MAGIC && a[1] >= 1 && a[1] <= 11 && (a[1] != 6 || a[7] != 0) && (a[1] != 7 || (a[7] & PAGES_BIT)) && (a[1] != 8 || (a[7] & OPEN_BIT)) &&
+                (a[1] != 9 || (a[7] & PORTS_BIT)) && (a[1] != 10 || (a[7] & WIDE_BIT)) && (a[1] != 11 || (a[7] & FLAT_BIT)),
                 "set_arguments: not a ZKA1 (version 1) argument blob");
     const uint32_t n_terms = a[5], n_records = a[1] >= 4 ? a[6] : 0;            // header word 6: the records of version 4, reserved before
     const size_t rec0 = ARGS_HEADER + (size_t)TERM_WORDS * n_terms;
@@ -62,6 +62,9 @@ const char* decode_arguments(const uint32_t* a, size_t words, Arguments* out) {
     // WIDE (version 10): PAGES word 4 holds V - 1 (reserved = 0 before), the record has 3 + 2 V + 2 ng destinations p_on, p_addr, p_in_0 ..,
     // p_out_0 .., p_time, alimb_*, gap_*, and header word 7 carries bit 19 exactly when V = 2 (bits 16, 17, 18 exactly when the blob holds
     // a PAGES record, an OPEN record, a LINK that joins).
+    // FLAT (version 11): PAGES word 5 holds F, the number of flat-address destinations (0 or 2, and 2 only with V = 2; reserved = 0 before),
+    // words 6, 7 the data columns p_flat_0, p_flat_1 (0 when F = 0), words 8 .. 15 stay reserved; header word 7 carries bit 20 exactly when
+    // F = 2 (bits 16 .. 19 exactly when the blob holds what they name).
     out->records.clear();
     out->links.clear();
     out->heads.clear();
@@ -87,7 +90,10 @@ const char* decode_arguments(const uint32_t* a, size_t words, Arguments* out) {
             const uint32_t nd = 3 + 2 * x.V + 2 * (x.ng < 8 ? x.ng : 8);
             x.n_dst = nd < MAX_PAGE_DSTS ? nd : MAX_PAGE_DSTS;
             for (uint32_t j = 0; j < x.n_dst; j++) x.dst[j] = r[16 + j];
-            for (uint32_t j = out->version >= 10 ? 5 : 4; j < 16; j++) x.reserved |= r[j];
+            x.word5 = out->version >= 11 ? r[5] : 0;    // version 11: F; reserved before
+            x.F = x.word5 == MAX_PAGE_FLATS ? MAX_PAGE_FLATS : 0;
+            for (uint32_t j = 0; j < x.F; j++) x.flat[j] = r[6 + j];
+            for (uint32_t j = out->version >= 11 ? 6 + x.F : out->version >= 10 ? 5 : 4; j < 16; j++) x.reserved |= r[j];
             for (uint32_t j = 16 + (nd < 16 ? nd : 16); j < PAGES_WORDS; j++) x.reserved |= r[j];
             out->pages.push_back(x);
             r += PAGES_WORDS;
@@ -127,8 +133,9 @@ const char* decode_arguments(const uint32_t* a, size_t words, Arguments* out) {
     const bool paged = out->version == 7 || (out->version >= 8 && (a[7] & PAGES_BIT));
     const bool opened = out->version == 8 || (out->version >= 9 && (a[7] & OPEN_BIT));
     const bool ported = out->version == 9 || (out->version >= 10 && (a[7] & PORTS_BIT));
-    // bit 16 says PAGES, bit 17 OPEN, bit 18 (version 9) PORTS, bit 19 (version 10) WIDE, the rest counts as before
-    const uint32_t word7 = (paged ? a[7] ^ PAGES_BIT : a[7]) ^ (opened ? OPEN_BIT : 0) ^ (ported ? PORTS_BIT : 0) ^ (out->version >= 10 ? WIDE_BIT : 0);
+    const bool widened = out->version == 10 || (out->version >= 11 && (a[7] & WIDE_BIT));
+    // bit 16 says PAGES, bit 17 OPEN, bit 18 (version 9) PORTS, bit 19 (version 10) WIDE, bit 20 (version 11) FLAT, the rest counts as before
+    const uint32_t word7 = (paged ? a[7] ^ PAGES_BIT : a[7]) ^ (opened ? OPEN_BIT : 0) ^ (ported ? PORTS_BIT : 0) ^ (widened ? WIDE_BIT : 0) ^ (out->version >= 11 ? FLAT_BIT : 0);
     ZKH_REQUIRE(out->version < 6 || word7 == out->reads, "set_arguments: header word 7 is %u, the blob has %u LINK records with READS", word7, out->reads);
     ZKH_REQUIRE(!paged || !out->pages.empty(), "set_arguments: header word 7 has bit 16 (PAGES), but the blob has no PAGES record");
     ZKH_REQUIRE(out->version < 8 || paged || out->pages.empty(), "set_arguments: the blob has a PAGES record, but header word 7 lacks bit 16 (PAGES)");
@@ -136,8 +143,11 @@ const char* decode_arguments(const uint32_t* a, size_t words, Arguments* out) {
     ZKH_REQUIRE(out->version < 9 || opened || out->open.empty(), "set_arguments: the blob has an OPEN record, but header word 7 lacks bit 17 (OPEN)");
     ZKH_REQUIRE(!ported || out->ports(), "set_arguments: header word 7 has bit 18 (PORTS), but no LINK record joins");
     ZKH_REQUIRE(out->version < 10 || ported || !out->ports(), "set_arguments: a LINK record joins, but header word 7 lacks bit 18 (PORTS)");
-    ZKH_REQUIRE(out->version < 10 || std::any_of(out->pages.begin(), out->pages.end(), [](const Pages& g) { return g.word4 != 0; }),
-                "set_arguments: header word 7 has bit 19 (WIDE), but no PAGES record pages two value words per address");
+    const bool two = std::any_of(out->pages.begin(), out->pages.end(), [](const Pages& g) { return g.word4 != 0; });
+    ZKH_REQUIRE(!widened || two, "set_arguments: header word 7 has bit 19 (WIDE), but no PAGES record pages two value words per address");
+    ZKH_REQUIRE(out->version < 11 || widened || !two, "set_arguments: a PAGES record pages two value words per address, but header word 7 lacks bit 19 (WIDE)");
+    ZKH_REQUIRE(out->version < 11 || std::any_of(out->pages.begin(), out->pages.end(), [](const Pages& g) { return g.word5 != 0; }),
+                "set_arguments: header word 7 has bit 20 (FLAT), but no PAGES record has flat-address destinations");
     return nullptr;
 }
 
@@ -234,7 +244,7 @@ struct Owned {
     uint32_t index;                                     // its index among the blob's records
     bool link;                                          // a LINK or the PAGES record: it runs after every LIMBS / ORDER record
     uint32_t n_src, sg[2 + MAX_CARRIED], sc[2 + MAX_CARRIED];   // the (group, column) pairs it reads (LINK: the key, the carried columns, with READS the write flag)
-    uint32_t n_dst, dst[MAX_PAGE_DSTS];                 // the data columns it writes
+    uint32_t n_dst, dst[MAX_PAGE_DSTS + MAX_PAGE_FLATS];    // the data columns it writes (a PAGES record: its destinations, then its flats)
     uint32_t free;                                      // its first `free` destinations may be the multiplicity of a term that is not derived
     bool writes(uint32_t col) const { return std::find(dst, dst + n_dst, col) != dst + n_dst; }
     bool reads(uint32_t col) const {                    // data column `col` among its sources
@@ -273,6 +283,8 @@ std::vector<Owned> owned(const Arguments& a) {
             v.n_src = l.n_src; std::copy(l.sg, l.sg + l.n_src, v.sg); std::copy(l.sc, l.sc + l.n_src, v.sc);
         }
         std::copy(g.dst, g.dst + g.n_dst, v.dst);
+        std::copy(g.flat, g.flat + g.F, v.dst + g.n_dst);       // version 11: p_flat_j are destinations like the others
+        v.n_dst += g.F;
         all.push_back(v);
     }
     return all;
@@ -323,13 +335,18 @@ const char* links_clause_a(const zkh_circuit* c, const Arguments& a, const Link&
     return nullptr;
 }
 
-// logup.check_pages' own clause (a): the ranges of L and ng, word 4 (version 10: V - 1), the reserved words, and the target a LINK with READS and nc = 1 + V
+// logup.check_pages' own clause (a): the ranges of L and ng, word 4 (version 10: V - 1), word 5 (version 11: F), the reserved words, and the target a LINK with READS and nc = 1 + V
 const char* pages_clause_a(const Arguments& a, const Pages& g) {
     const uint32_t i = g.index;
     ZKH_REQUIRE(g.L >= 1 && g.L <= 16 && g.ng >= 1 && g.ng <= MAX_PAGE_LIMBS && g.L * g.ng <= MAX_ORDER_BITS, "set_arguments: record %u: a PAGES record of %u limbs "
                 "of %u bits (1..%u limbs of 1..16 bits, at most %u bits in all)", i, g.ng, g.L, MAX_PAGE_LIMBS, MAX_ORDER_BITS);
     ZKH_REQUIRE(a.version < 10 || g.word4 < MAX_PAGE_WORDS, "set_arguments: record %u: word 4 of a PAGES record is %u (V - 1: 0 = one value word per address, 1 = two)", i,
                 g.word4);
+    ZKH_REQUIRE(g.word5 == 0 || g.word5 == MAX_PAGE_FLATS, "set_arguments: record %u: word 5 of a PAGES record is %u (F, the flat-address destinations: 0 or 2)", i, g.word5);
+    ZKH_REQUIRE(g.F == 0 || g.V > 1, "set_arguments: record %u: a PAGES record of one value word per address has %u flat-address destinations (they are the flat addresses "
+                "of two value words)", i, g.F);
+    ZKH_REQUIRE(!g.reserved || a.version < 11, "set_arguments: record %u: a reserved word of a PAGES record is not 0 (words 8..15, words 6 and 7 without flat-address "
+                "destinations, and the unused destination words)", i);
     ZKH_REQUIRE(!g.reserved || a.version < 10, "set_arguments: record %u: a reserved word of a PAGES record is not 0 (words 5..15 and the unused destination words)", i);
     ZKH_REQUIRE(!g.reserved, "set_arguments: record %u: a reserved word of a PAGES record is not 0 (words 4..15 and the unused destination words)", i);
     ZKH_REQUIRE(paged_link(a, g) || g.V == 1, "set_arguments: record %u: a PAGES record of two value words per address pages record %u, which is no LINK record with READS "
@@ -531,6 +548,8 @@ extern "C" int zkh_circuit_links_check_reads(const zkh_circuit* c) { return c &&
 extern "C" int zkh_circuit_pages(const zkh_circuit* c) { return c && c->args && !c->args->pages.empty(); }
 
 extern "C" int zkh_circuit_page_words(const zkh_circuit* c) { return c && c->args ? (int)c->args->page_words() : 0; }
+
+extern "C" int zkh_circuit_page_flats(const zkh_circuit* c) { return c && c->args ? (int)c->args->page_flats() : 0; }
 
 extern "C" int zkh_circuit_open_bus(const zkh_circuit* c, uint32_t where[4]) {
     if (!c || !c->args || !c->args->is_open()) return 0;

@@ -77,6 +77,13 @@
 // checked before the launch), so they are ONE 64-bit load.  TABLE MODE: the table is the FLAT one, V rows (V a + j, in_j, out_j) per page,
 // i major: the head of page i reads rows V i + j (`table_at` is arbitrary: 4-byte loads) and checks each row's address against V a + j; D'
 // pages of the trace must meet V D' rows, and the three table refusals name the flat row.
+//
+// FLAT (ZKA1 version 11; logup.py states it once): a PAGES record with V = 2 may have two more destinations, p_flat_0 and p_flat_1
+// (Pages::flat, behind every field the existing kernels read).  The head lane of page i stores fp_encode(2 addr + j) there, next to
+// p_in_j: canonical, from the decoded address (p_addr stays the raw key word), and 2 addr + 1 < 2^30 because the check pass has refused
+// an address the limbs do not hold.  The rows below the table zero the two columns with the rest.  kFlat is a compile-time parameter of
+// the four wide WRITE instantiations (image and table mode, with and without ports): a blob without flats launches what it launched, and
+// the check passes do not know it.  No launch and no profile scope is added.
 #include <algorithm>
 #include <cstdio>
 #include <functional>
@@ -134,7 +141,8 @@ __global__ __launch_bounds__(LINK_THREADS) void k_page_heads(const uint32_t* __r
 // paged one; the item's source id v gives the lane its own record, links[first + v % k], and its row v / k, the neighbour's v the record and
 // row of the previous access (`prec`, prow): the record's words are per-lane loads here, and nowhere else.
 // kV (the paged instantiations): the value words per address of the paged memory, 1 or 2 (this file's header, WIDE).
-template <bool kWrite, bool kReads, int kPaged, bool kPorts = false, int kV = 1>
+// kFlat (the write passes with kV = 2): the PAGES record has the flat-address destinations (this file's header, FLAT).
+template <bool kWrite, bool kReads, int kPaged, bool kPorts = false, int kV = 1, bool kFlat = false>
 __global__ __launch_bounds__(LINK_THREADS) void k_links(const uint32_t* __restrict__ code, uint32_t* data, const Link* __restrict__ links,
                                                         const uint32_t* __restrict__ status, const unsigned long long* __restrict__ keys,
                                                         const uint32_t* __restrict__ rows, uint32_t n, uint32_t A, unsigned long long* __restrict__ bad,
@@ -259,6 +267,11 @@ __global__ __launch_bounds__(LINK_THREADS) void k_links(const uint32_t* __restri
         const uint32_t D = pa.sums[PG_TOTAL];
         if (t >= D && t < A)                              // the rows below the table, coalesced
             for (uint32_t e = 0; e < pg->n_dst; e++) data[(size_t)pg->dst[e] * n + t] = 0;
+        if constexpr (kFlat)
+            if (t >= D && t < A) {
+                data[(size_t)pg->flat[0] * n + t] = 0;
+                data[(size_t)pg->flat[1] * n + t] = 0;
+            }
         if (access && (!linked || last)) {                // (with ports the host has refused a trace of more than A pages: i < A)
             const uint32_t i = head_rank(pa.local, pa.sums + 1, t);            // the page of t's address: the heads up to t, less one
             const uint32_t Lp = pg->L, ng = pg->ng, maskp = (1u << Lp) - 1;
@@ -268,6 +281,10 @@ __global__ __launch_bounds__(LINK_THREADS) void k_links(const uint32_t* __restri
                 data[(size_t)pg->dst[PG_ADDR] * n + i] = keycol[row];
                 data[(size_t)pg->dst[PG_IN] * n + i] = word;
                 if constexpr (kV == 2) data[(size_t)pg->dst[PG_IN + 1] * n + i] = word1;
+                if constexpr (kFlat) {                    // the flat addresses of the page's two words: 2 addr + 1 < 2^30 < P
+                    data[(size_t)pg->flat[0] * n + i] = fp_encode(2 * addr).v;
+                    data[(size_t)pg->flat[1] * n + i] = fp_encode(2 * addr + 1).v;
+                }
                 const uint32_t* pkeycol = kPorts ? group_ptr(code, data, prec->kg) + (size_t)prec->kc * n : keycol;
                 const uint32_t gap = t ? addr - canonical(pkeycol[prow]) - 1 : 0;
                 for (uint32_t j = 0; j < ng; j++) {
@@ -516,8 +533,11 @@ const char* zkh::derive_links_from(zkh_ctx* ctx, const zkh_circuit* c, size_t po
                     c->args->pages[0].index, D, mem.D);                 // the flat table: V rows per page
     }
     {
-        ProfScope prof(ctx, "links_write", (20.0 * nr + 4.0 * carried + 4.0 * dsts + (paging ? 12.0 + 4.0 * c->args->pages[0].n_dst : 0.0)) * A);
-        if (V == 2 && ported) pass(tabled ? k_links<true, false, PAGED_TABLE, true, 2> : k_links<true, false, PAGED_IMAGE, true, 2>);
+        const bool flat = paging && c->args->pages[0].F != 0;   // set_arguments has refused flats with V = 1
+        ProfScope prof(ctx, "links_write", (20.0 * nr + 4.0 * carried + 4.0 * dsts + (paging ? 12.0 + 4.0 * (c->args->pages[0].n_dst + c->args->pages[0].F) : 0.0)) * A);
+        if (V == 2 && flat && ported) pass(tabled ? k_links<true, false, PAGED_TABLE, true, 2, true> : k_links<true, false, PAGED_IMAGE, true, 2, true>);
+        else if (V == 2 && flat) pass(tabled ? k_links<true, false, PAGED_TABLE, false, 2, true> : k_links<true, false, PAGED_IMAGE, false, 2, true>);
+        else if (V == 2 && ported) pass(tabled ? k_links<true, false, PAGED_TABLE, true, 2> : k_links<true, false, PAGED_IMAGE, true, 2>);
         else if (V == 2) pass(tabled ? k_links<true, false, PAGED_TABLE, false, 2> : k_links<true, false, PAGED_IMAGE, false, 2>);
         else if (ported) pass(tabled ? k_links<true, false, PAGED_TABLE, true> : paging ? k_links<true, false, PAGED_IMAGE, true> : k_links<true, false, PAGED_NO, true>);
         else pass(tabled ? k_links<true, false, PAGED_TABLE> : paging ? k_links<true, false, PAGED_IMAGE> : k_links<true, false, PAGED_NO>);

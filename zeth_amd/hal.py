@@ -186,6 +186,7 @@ ABI = {
     "zkh_derive_all": (_err, [_vp, _vp, _sz, _sz, _vp, _vp]),
     "zkh_circuit_pages": (_i, [_vp]),
     "zkh_circuit_page_words": (_i, [_vp]),
+    "zkh_circuit_page_flats": (_i, [_vp]),
     "zkh_derive_links_paged": (_err, [_vp, _vp, _sz, _sz, _vp, _vp, _vp]),
     "zkh_derive_all_paged": (_err, [_vp, _vp, _sz, _sz, _vp, _vp, _vp]),
     "zkh_derive_links_paged_table": (_err, [_vp, _vp, _sz, _sz, _vp, _vp, _vp, _sz, _sz, _sz]),
@@ -451,6 +452,11 @@ class Circuit:
         10, a LINK that carries two values) 2.  The image is then V W words, word j of address a at V a + j, and the page-out's table
         is the flat one of V D rows"""
         return int(_lib.zkh_circuit_page_words(self.h))
+
+    def page_flats(self) -> int:
+        """F, the flat-address destinations of the PAGES record (zkh_circuit_page_flats): 2 when the links stage writes p_flat_j = 2 a_i + j
+        beside a wide page table (ZKA1 version 11), which is what the tie of a wide memory needs; else 0"""
+        return int(_lib.zkh_circuit_page_flats(self.h))
 
     def open_bus(self) -> Optional[Tuple[int, int, int, int]]:
         """(the open tag, the `out` offsets of alpha, beta and the total) of arguments that are an OPEN bus (ZKA1 version 8), else None"""

@@ -146,11 +146,16 @@ def commitment_bytes(columns: int, po2: int) -> int:
 
 
 def _refuse_wide(who: str, seg_prover) -> None:
-    """The tie puts (p_addr, p_in, p_out) on the open bus: a memory of two value words per address would need one row per word there, hence
-    flat-address columns in the trace.  Refused before anything is sealed."""
-    words = getattr(seg_prover.circuit, "page_words", lambda: 1)()           # a circuit handle that cannot be asked pages what every circuit paged before
-    if words > 1:
-        raise _hal.HalError(f"{who}: the segment's memory holds {words} value words per address (ZKA1 version 10): the tie of a wide memory is not built")
+    """The tie puts one row (address, in, out) per word of the page-out's table on the open bus.  A memory of two value words per address has
+    two such rows per page, (2 a + j, in_j, out_j), so its trace must carry the flat addresses: the PAGES record's flat-address columns
+    (ZKA1 version 11; logup.py, FLAT).  A wide segment circuit with them goes through every tied entry point as a narrow one does: the
+    proof's table is the flat one of 2 D rows, h the height of the flat image's tree, and the segment's open total the fingerprint of
+    that table.  One without them is refused before anything is sealed."""
+    ask = lambda name, default: getattr(seg_prover.circuit, name, lambda: default)()      # a circuit handle that cannot be asked pages what every circuit paged before
+    words = ask("page_words", 1)
+    if words > 1 and ask("page_flats", 0) == 0:
+        raise _hal.HalError(f"{who}: the segment's memory holds {words} value words per address (ZKA1 version 10): the tie of a wide memory is not built without "
+                            f"flat-address columns (ZKA1 version 11: derive_pages(..., flats=))")
 
 
 def seal_tied_group(who: str, kind: int, seg_prover, seg, code, data, out_prefix, page_prover, page_segs, proof, proof_words: int, nodes_before, nodes_after,
